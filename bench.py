@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path named by BASELINE.json: songs/sec for batched 22 050 Hz f32 analysis (all features) on
-N MI355X, synthetic white-noise PCM resident in HBM, with the HBM and FP32 rooflines, the CPU oracle timed beside it,
-and pairwise distances/sec over 100 k feature vectors.
+N MI355X, synthetic white-noise PCM resident in HBM.  A plain run sets up, warms up, times --steps steps and prints the
+line; --full adds the HBM, FP32 and VALU rooflines (from a second, profiled pass), the CPU oracle timed beside it with
+its parity spot check, the host-feed and small-call rates, and pairwise distances/sec over 100 k feature vectors.
+--dump-outputs DIR writes what the last timed step computed (DIR/<name>.npy), for comparing two builds on the same inputs.
 
     python bench.py --gpus 1 --steps 3 --warmup 1                      # configs[1]: 1024 three-minute songs per GPU
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full               # ... and everything the line carried beside the rate
     python bench.py --config mixed                                     # configs[4]: this GPU's share of the 30 s - 10 min corpus
     python bench.py --config library                                   # configs[2]: 10 000 songs, all-gather, sharded pairwise
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -74,7 +77,37 @@ def parse():
                     help="drive N GPUs from THIS process through the C-ABI node API (blissgpu_node_*: what a Rust host "
                          "would call) instead of one torch.distributed rank per GPU; configs batch / library")
     ap.add_argument("--node-devices", default="", help="HIP ordinals of the node's ranks, e.g. 0,0 = two loopback ranks on one GPU")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the profiled pass with per-kernel times and the HBM / FP32 / VALU rooflines, "
+                         "the CPU baseline and in-run oracle check, host feed, small calls, pairwise and playlist (the --no-* "
+                         "options, --cpu-songs, --host-feed-songs, --pairwise-n and --traffic apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy: features (the gathered rows when N > 1), "
+                         "status (rank 0's songs), pairwise (--config library: rank 0's row block)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+DUMP_BYTES = 16 << 20   # per output (sampled rows + their indices); at most three outputs, so at most 48 MiB in all
+
+
+def dump_outputs(path, arrays):
+    """name -> host array, written as DIR/<name>.npy in float32 (float64 stays float64; integer status codes are exact in
+    float32).  An output larger than DUMP_BYTES is replaced by a fixed seeded sample of its rows; the sampled row indices
+    then go to DIR/<name>_rows.npy (float64)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a if a.dtype == np.float64 else a.astype(np.float32)
+        row_bytes = a.nbytes // max(len(a), 1)
+        if a.nbytes > DUMP_BYTES:
+            k = DUMP_BYTES // (row_bytes + 8)
+            rows = np.sort(np.random.default_rng(0).choice(len(a), k, replace=False))
+            a = a[rows]
+            np.save(os.path.join(path, f"{name}_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def mixed_lengths(n_total, seed):
@@ -258,6 +291,8 @@ def main_node(args):
         step()
     elapsed = time.perf_counter() - t0
     rows = node.features(0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"features": rows})
     total_samples = float(all_lens.sum())
     algo = 4.0 * total_samples + 4.0 * d * n_total
     result = {
@@ -273,9 +308,9 @@ def main_node(args):
                                      else "one grouped ncclAllGather of the feature rows over xGMI")},
         "whole_job_GBps": round(algo * args.steps / elapsed / 1e9, 2),
         "rows_finite": bool(np.isfinite(rows).all()),
-        "note": "per-kernel roofline and cpu_baseline are reported by the one-rank-per-GPU form (bench.py --gpus N)",
+        "note": "per-kernel roofline and cpu_baseline are reported by the one-rank-per-GPU form (bench.py --gpus N --full)",
     }
-    if args.config == "library" and not args.no_pairwise:
+    if args.full and args.config == "library" and not args.no_pairwise:
         t0 = time.perf_counter()
         D = node.pairwise("euclidean")
         result["node_pairwise"] = {"n": n_total, "ms_including_D2H_of_the_matrix": round((time.perf_counter() - t0) * 1e3, 1),
@@ -448,18 +483,24 @@ def main():
         full = step()
     fence()
     elapsed = time.perf_counter() - t0
-    # the same steps again with HIP events around every launch (on the stream each kernel runs on): the kernel durations of
-    # the roofline.  Kept out of the timed region: the events cost a few microseconds per launch.
-    ctx.profile_enable(True)
-    ctx.profile_reset()
-    t0p = time.perf_counter()
-    for _ in range(args.steps):
-        full = step()
-    fence()
-    elapsed_profiled = time.perf_counter() - t0p
-    prof = ctx.profile()
-    ctx.profile_enable(False)
     chunks = ctx.last_chunks()
+    if args.dump_outputs and rank == 0:
+        outputs = {"features": full.cpu().numpy(), "status": status.cpu().numpy()}
+        if D_block is not None:
+            outputs["pairwise"] = D_block.cpu().numpy()
+        dump_outputs(args.dump_outputs, outputs)
+    if args.full:
+        # the same steps again with HIP events around every launch (on the stream each kernel runs on): the kernel durations of
+        # the roofline.  Kept out of the timed region: the events cost a few microseconds per launch.
+        ctx.profile_enable(True)
+        ctx.profile_reset()
+        t0p = time.perf_counter()
+        for _ in range(args.steps):
+            full = step()
+        fence()
+        elapsed_profiled = time.perf_counter() - t0p
+        prof = ctx.profile()
+        ctx.profile_enable(False)
     red_dev = "cpu" if args.share_device else "cuda"
     tot = torch.tensor([float(n), float(total_samples)], dtype=torch.float64, device=red_dev)
     if world > 1:
@@ -470,7 +511,8 @@ def main():
     job_songs, job_samples = float(tot[0].item()), float(tot[1].item())
     value = job_songs * args.steps / elapsed
 
-    if rank == 0:
+    def full_sections(result):
+        """--full: what the run measures besides the headline figure (rank 0, after the profiled pass)"""
         # ---- HBM roofline of the dominant kernel: algorithmic bytes (SURVEY.md 8d: 4*N + 4*d per song, PCM read once
         # + the feature row) of one launch / its average HIP-event duration (chunked runs: per chunk launch) ----
         skip = ("pairwise_kernel", "synth_kernel", "set_distance_kernel", "song_to_song_kernel")
@@ -538,27 +580,9 @@ def main():
                 valu["source"] = "profiles/valu_busy.json: " + vb.get("note", "")
         except Exception as e:  # noqa: BLE001
             valu["source"] = f"profiles/valu_busy.json: {type(e).__name__}"
+        result.update(roofline=roofline, roofline_fp32=fp32, roofline_valu=valu)
 
-        result = {
-            "metric": "songs/sec (3-min 22 050 Hz f32) at 1/2/4/8 GPU; HBM GB/s vs roofline",
-            "value": round(value, 2), "unit": "songs/sec", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f32",
-            "data": ("synthetic white noise (Philox4x32-10, uniform [-0.5,0.5)), generated in HBM" if musical_songs is None else
-                     "synthetic musical signals (seeded generator, tests/tools/musical_check.py), generated on the host, resident in HBM before the timed region"),
-            "config": {"workload": workload, "name": args.config, "songs_per_gpu": n, "songs_total": int(job_songs),
-                       "samples_per_song": N, "features": d, "chunks_per_step": int(chunks),
-                       "parallelism": f"songs sharded x{world}, all-gather of feature rows" if world > 1 else "single GPU"},
-            "samples_per_sec": round(job_samples * args.steps / elapsed, 1),
-            "three_minute_song_equivalents_per_sec": round(job_samples * args.steps / elapsed / SONG_SAMPLES, 2),
-            "roofline": roofline, "roofline_fp32": fp32, "roofline_valu": valu,
-        }
-        result.update(notes)
-        if args.share_device:
-            result["share_device"] = (f"{world} ranks on ONE device, collectives over gloo through the host: a check of the "
-                                      f"N > 1 control flow on a 1-GPU box, not a measurement")
-
-        # The headline numbers above are complete at this point; the sections below are extras.  Each one is guarded so
+        # The sections below are extras.  Each one is guarded so
         # that a failure there (a full host, no room for the 40 GB distance matrix, ...) is reported inside the JSON
         # line instead of losing it.
         def guarded(name, fn):
@@ -607,8 +631,6 @@ def main():
                                                 "GBps": round(pbytes / (kms * 1e-3) / 1e9, 1)}
 
         extras = args.config == "batch" and world == 1
-        if musical_songs is not None:
-            result["config"]["not_the_metric_workload"] = "BASELINE.json's metric is quoted on white noise: --config batch"
 
         # ---- PCIe-inclusive rate of the host-buffer entry points (never `value`) ----
         def section_host_feed():
@@ -779,6 +801,29 @@ def main():
 
         if extras and not args.no_playlist and not args.no_pairwise:
             guarded("playlist", section_playlist)
+
+    if rank == 0:
+        result = {
+            "metric": "songs/sec (3-min 22 050 Hz f32) at 1/2/4/8 GPU; HBM GB/s vs roofline",
+            "value": round(value, 2), "unit": "songs/sec", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f32",
+            "data": ("synthetic white noise (Philox4x32-10, uniform [-0.5,0.5)), generated in HBM" if musical_songs is None else
+                     "synthetic musical signals (seeded generator, tests/tools/musical_check.py), generated on the host, resident in HBM before the timed region"),
+            "config": {"workload": workload, "name": args.config, "songs_per_gpu": n, "songs_total": int(job_songs),
+                       "samples_per_song": N, "features": d, "chunks_per_step": int(chunks),
+                       "parallelism": f"songs sharded x{world}, all-gather of feature rows" if world > 1 else "single GPU"},
+            "samples_per_sec": round(job_samples * args.steps / elapsed, 1),
+            "three_minute_song_equivalents_per_sec": round(job_samples * args.steps / elapsed / SONG_SAMPLES, 2),
+        }
+        if musical_songs is not None:
+            result["config"]["not_the_metric_workload"] = "BASELINE.json's metric is quoted on white noise: --config batch"
+        result.update(notes)
+        if args.share_device:
+            result["share_device"] = (f"{world} ranks on ONE device, collectives over gloo through the host: a check of the "
+                                      f"N > 1 control flow on a 1-GPU box, not a measurement")
+        if args.full:
+            full_sections(result)
         print(json.dumps(result))
     if world > 1:
         dist.destroy_process_group()

@@ -456,7 +456,7 @@ def test_bench_two_ranks_sharing_the_device(config):
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--config", config, "--songs", "24", "--samples", "400000", "--share-device", "--no-cpu-baseline", "--no-pairwise",
+           "--config", config, "--songs", "24", "--samples", "400000", "--share-device", "--full", "--no-cpu-baseline", "--no-pairwise",
            "--no-host-feed", "--no-playlist", "--no-small-calls"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]

@@ -243,6 +243,38 @@ def test_bench_refuses_more_gpus_than_the_box_has():
     assert out.returncode != 0 and not [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
 
 
+def test_bench_plain_line_and_dumped_outputs(bliss, tmp_path):
+    """A plain run prints the headline line only (what moved behind --full is absent), and --dump-outputs holds the rows of
+    the last timed step: bit for bit what the context API computes for the same generated songs."""
+    import json
+
+    import torch
+
+    n, N = 8, 400000
+    out = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--songs", str(n), "--samples", str(N),
+                  "--dump-outputs", str(tmp_path)])
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    r = json.loads(lines[0])
+    assert r["steps"] == 2 and r["ms_per_step"] > 0 and r["unit"] == "songs/sec" and r["dtype"] == "f32"
+    assert r["higher_is_better"] is True and abs(r["value"] - n / (r["ms_per_step"] * 1e-3)) < 0.01 * r["value"]
+    assert not {"roofline", "roofline_fp32", "roofline_valu", "cpu_baseline", "host_feed", "small_calls", "pairwise",
+                "playlist"} & set(r)
+    rows, status = np.load(tmp_path / "features.npy"), np.load(tmp_path / "status.npy")
+    assert rows.dtype == np.float32 and rows.shape == (n, 23) and status.dtype == np.float32 and (status == 0).all()
+    ctx = bliss.Context(0)
+    lens = np.full(n, N, np.uint64)
+    padded = (N + 63) // 64 * 64
+    offs = np.arange(n, dtype=np.uint64) * np.uint64(padded)
+    pcm = torch.empty(n * padded + 64, dtype=torch.float32, device="cuda")   # bench.py's layout
+    ctx.synth_white_noise(pcm, offs, lens, song_index=np.arange(n))
+    ref, _ = ctx.analyze(pcm, offs, lens, 2)
+    ctx.synchronize()
+    assert np.array_equal(ref.cpu().numpy().view(np.uint32), rows.view(np.uint32))
+    ctx.close()
+
+
 # ---------------------------------------------------------------------------------------------
 # two or more GPUs: the first RCCL N > 1 evidence (skipped with the reason on a one-GPU box)
 # ---------------------------------------------------------------------------------------------

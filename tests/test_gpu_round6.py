@@ -331,7 +331,7 @@ def test_bench_musical_config_runs_and_checks_itself_against_the_oracle():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "musical", "--songs", "12", "--samples", "661500",
-                          "--steps", "2", "--warmup", "1", "--cpu-songs", "12", "--no-pairwise", "--no-host-feed", "--no-playlist",
+                          "--steps", "2", "--warmup", "1", "--full", "--cpu-songs", "12", "--no-pairwise", "--no-host-feed", "--no-playlist",
                           "--no-small-calls"], capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

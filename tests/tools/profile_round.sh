@@ -10,12 +10,12 @@ R=$PWD; TAG=${TAG:-r04}; O=$R/gpurun_out/round; rm -rf $O; mkdir -p $O
 SONGS=${HBM_SONGS:-256} bash tests/tools/hbm_traffic.sh > $O/hbm.log 2>&1; tail -16 $O/hbm.log
 cp gpurun_out/hbm/hbm_traffic.json $O/hbm_traffic.json; cp gpurun_out/hbm/hbm_traffic.json profiles/hbm_traffic.json
 cp gpurun_out/hbm/hbm_traffic.txt $O/${TAG}_hbm_traffic_256songs.txt
-python bench.py > $O/${TAG}_bench_batch.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 400 $O/${TAG}_bench_batch.json; echo
-python bench.py --config mixed --steps 2 --warmup 1 > $O/${TAG}_bench_mixed.json 2> $O/bench_mixed.err; echo "mixed rc=$?"; head -c 300 $O/${TAG}_bench_mixed.json; echo
-python bench.py --config library --steps 2 --warmup 1 > $O/${TAG}_bench_library.json 2> $O/bench_library.err; echo "library rc=$?"; head -c 300 $O/${TAG}_bench_library.json; echo
+python bench.py --full > $O/${TAG}_bench_batch.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 400 $O/${TAG}_bench_batch.json; echo
+python bench.py --full --config mixed --steps 2 --warmup 1 > $O/${TAG}_bench_mixed.json 2> $O/bench_mixed.err; echo "mixed rc=$?"; head -c 300 $O/${TAG}_bench_mixed.json; echo
+python bench.py --full --config library --steps 2 --warmup 1 > $O/${TAG}_bench_library.json 2> $O/bench_library.err; echo "library rc=$?"; head -c 300 $O/${TAG}_bench_library.json; echo
 python bench.py --node 2 --node-devices 0,0 --songs 512 > $O/${TAG}_bench_node_2_loopback_ranks.json 2> $O/bench_node.err; echo "node rc=$?"; head -c 200 $O/${TAG}_bench_node_2_loopback_ranks.json; echo
 cd /tmp; export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/trace -o bench -- python $R/bench.py --no-cpu-baseline --no-host-feed --no-playlist --no-small-calls > $O/trace.log 2>&1; echo "trace rc=$?"
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/trace -o bench -- python $R/bench.py --full --no-cpu-baseline --no-host-feed --no-playlist --no-small-calls > $O/trace.log 2>&1; echo "trace rc=$?"
 cd $R
 DB=$(find $O/trace -name "*.db" | head -1)
 python tests/tools/rocpd_stats.py $DB > $O/${TAG}_bench_1024songs.kernel_stats.txt; head -16 $O/${TAG}_bench_1024songs.kernel_stats.txt
