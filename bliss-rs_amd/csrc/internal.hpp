@@ -53,7 +53,7 @@ struct SongDesc {
     uint32_t n_t;       // timbral frames   floor((n-512)/128)+1
     uint32_t n_b;       // tempo frames     floor((n-512)/256)+1
     uint32_t n_f;       // FFT-512 frames actually computed = max(n_t, 2*n_b)
-    uint32_t n_c;       // chroma frames    min(ceil_f32(n/2205), n/2205+1)
+    uint32_t n_c;       // chroma frames    ceil_f32(n/2205); frames past the last window (f * 2205 > n) are zero rows
     uint32_t n_e;       // 256-sample blocks ceil(n/256)
     uint32_t n_l;       // loudness chunks  ceil(n/1024)
     uint32_t row;       // output row

@@ -34,9 +34,10 @@ void fill_counts(SongDesc& d) {
     d.n_t = (uint32_t)((n - W512) / HOP_T + 1);
     d.n_b = (uint32_t)((n - W512) / HOP_B + 1);
     d.n_f = std::max(d.n_t, 2u * d.n_b);
-    // src/utils.rs:29-32: rows = (len as f32 / hop as f32).ceil(); the zip with windows() caps it at n/hop + 1
-    const uint32_t rows = (uint32_t)ceilf((float)n / (float)HOP_C);
-    d.n_c = (uint32_t)std::min<uint64_t>(rows, n / HOP_C + 1);
+    // src/utils.rs:29-32: rows = (len as f32 / hop as f32).ceil(), every one of them part of the spectrogram.  The zip with
+    // windows() (:44-47) fills only the first min(rows, n/hop + 1): for n >= 2^26 the f32 ceiling can exceed the window
+    // count by one, and that last row stays all zero (the STFT kernel writes it without loading a sample).
+    d.n_c = (uint32_t)ceilf((float)n / (float)HOP_C);
     d.n_e = (uint32_t)((n + 255) / 256);
     d.n_l = (uint32_t)((n + LOUD_W - 1) / LOUD_W);
 }

@@ -317,7 +317,7 @@ def test_workspace_chunking(bliss, oracle):
     assert np.array_equal(ref, got) and (status == 0).all()
 
 
-def test_frame_and_tile_boundary_lengths(ctx, oracle):
+def frame_and_tile_boundary_lengths():
     """Song lengths that sit on (and one sample either side of) every framing / tiling boundary of the kernels: the
     8192-sample minimum, the chroma hop 2205 (ceil(N/2205) frames, last window dropped at exact multiples), 16-frame
     STFT tiles, 64-frame chroma tiles, the FFT-512 hop 128 / tempo hop 256 / 512-frame tiles, 256-sample energy blocks,
@@ -334,7 +334,13 @@ def test_frame_and_tile_boundary_lengths(ctx, oracle):
     for n_t in (63, 64, 65, 95, 96, 97, 127, 128, 129, 511, 512, 513, 543, 544, 545, 1023, 1024, 1025):
         for r in (0, 127):
             lengths.add(128 * (n_t - 1) + 512 + r)
-    lengths = sorted(lengths)
+    return sorted(lengths)
+
+
+def test_frame_and_tile_boundary_lengths(ctx, oracle):
+    """Every length of frame_and_tile_boundary_lengths() through the features (tests/test_gpu_stage_frames.py checks the same
+    songs frame by frame)."""
+    lengths = frame_and_tile_boundary_lengths()
     songs = [oracle.white_noise(700 + i, n) for i, n in enumerate(lengths)]
     got, status = _run(ctx, songs)
     tuning, n_bpms = ctx.last_tuning(len(songs))
