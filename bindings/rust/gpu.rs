@@ -21,6 +21,8 @@
 //!   * `euclidean_distance` / `cosine_distance` / `mahalanobis_distance`
 //!                                             src/playlist.rs:65-79,140-142 -> [`distance`], [`pairwise`]
 //!   * `closest_to_songs` / `song_to_song`     src/playlist.rs:256-326     -> [`order_on_device`]
+//!   * `dedup_playlist` / `dedup_playlist_custom_distance`
+//!                                             src/playlist.rs:343-402     -> [`dedup_on_device`]
 //!
 //! build.rs of the crate, under the feature:
 //! ```ignore
@@ -132,6 +134,11 @@ pub mod sys {
                                          m_matrix: *const f32, order: *mut u32, dist: *mut f32) -> c_int;
         pub fn blissgpu_song_to_song(seeds: *const f32, n_seeds: u32, cand: *const f32, n: u64, d: u32, metric: c_int,
                                      m_matrix: *const f32, order: *mut u32) -> c_int;
+        pub fn blissgpu_dedup_playlist(x: *const f32, n: u64, d: u32, seq: *const u32, len: u64, meta: *const u32, metric: c_int,
+                                       m_matrix: *const f32, threshold: f32, kept: *mut u32, n_kept: *mut u64) -> c_int;
+        pub fn blissgpu_dedup_playlist_device(ctx: *mut blissgpu_ctx, d_x: *const f32, n: u64, d: u32, d_seq: *const u32,
+                                              len: u64, d_meta: *const u32, metric: c_int, d_m: *const f32, threshold: f32,
+                                              d_kept: *mut u32, d_n_kept: *mut u64) -> c_int;
 
         // ---- one process, every GPU of the node ----
         pub fn blissgpu_node_create(n_devices: c_int, devices: *const c_int, node: *mut *mut blissgpu_node) -> c_int;
@@ -335,6 +342,42 @@ pub fn order_on_device<T: AsRef<Song> + Clone>(initial: &[T], candidates: &[T], 
         return Err(gpu_err(rc));
     }
     Ok(order.into_iter().map(|i| candidates[i as usize].clone()).collect())
+}
+
+/// `dedup_playlist_custom_distance` (src/playlist.rs:367-402) for the built-in metrics in one library call: a song absorbs
+/// the songs that follow it while they are closer than `distance_threshold` (default 0.05) or carry the same `Some` title
+/// and artist.  A NaN distance the CPU iterator would evaluate is `BLISSGPU_ERR_NAN` here where `n32()` panics.
+pub fn dedup_on_device<T: AsRef<Song> + Clone>(playlist: &[T], distance_threshold: Option<f32>, metric: Metric,
+                                               m: Option<&Array2<f32>>) -> BlissResult<Vec<T>> {
+    if playlist.is_empty() {
+        return Ok(Vec::new());
+    }
+    let d = playlist[0].as_ref().analysis.as_vec().len();
+    let x = playlist.iter().flat_map(|s| s.as_ref().analysis.as_vec()).collect::<Vec<f32>>();
+    // one key per song: 0 when the title or the artist is None, equal keys for equal (title, artist)
+    let mut seen = std::collections::HashMap::new();
+    let meta = playlist
+        .iter()
+        .map(|s| match (&s.as_ref().title, &s.as_ref().artist) {
+            (Some(t), Some(a)) => {
+                let next = seen.len() as u32 + 1;
+                *seen.entry((t.clone(), a.clone())).or_insert(next)
+            }
+            _ => 0,
+        })
+        .collect::<Vec<u32>>();
+    let (_keep, mp) = matrix_ptr(m);
+    let mut kept = vec![0u32; playlist.len()];
+    let mut n_kept = 0u64;
+    let rc = unsafe {
+        sys::blissgpu_dedup_playlist(x.as_ptr(), playlist.len() as u64, d as u32, std::ptr::null(), playlist.len() as u64,
+                                     meta.as_ptr(), metric.code(), mp, distance_threshold.unwrap_or(0.05), kept.as_mut_ptr(),
+                                     &mut n_kept)
+    };
+    if rc != sys::BLISSGPU_OK {
+        return Err(gpu_err(rc));
+    }
+    Ok(kept[..n_kept as usize].iter().map(|&i| playlist[i as usize].clone()).collect())
 }
 
 /// One process driving every GPU of the node: songs sharded by sample count, one `ncclAllGather` of the feature rows over

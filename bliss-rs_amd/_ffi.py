@@ -79,6 +79,10 @@ SIGNATURES = {
     "blissgpu_set_distance": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp]),
     "blissgpu_closest_to_songs": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, _vp]),
     "blissgpu_song_to_song": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp]),
+    "blissgpu_dedup_playlist": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, C.c_int, _vp, C.c_float, _vp,
+                                          _u64p]),
+    "blissgpu_dedup_playlist_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, C.c_int, _vp,
+                                                 C.c_float, _vp, _vp]),
     "blissgpu_set_distance_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp]),
     "blissgpu_closest_to_songs_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp,
                                                    _vp]),

@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstdint>
 #include <functional>
+#include <map>
 #include <optional>
 #include <stdexcept>
 #include <string>
@@ -457,32 +458,22 @@ std::vector<T> song_to_song(const std::vector<T>& initial_songs, const std::vect
 // dedup_playlist_custom_distance / dedup_playlist (src/playlist.rs:343-402)
 template <typename T>
 std::vector<T> dedup_playlist_custom_distance(const std::vector<T>& playlist, std::optional<float> distance_threshold, const MetricBuilder& mb) {
-    const float thr = distance_threshold.value_or(0.05f);
+    if (playlist.empty()) return {};
     size_t d = 0;
     const auto x = feature_matrix(playlist, d);
-    const size_t n = playlist.size(), window = 64;
-    std::vector<T> out;
-    std::vector<float> dist(window);
-    size_t i = 0;
-    while (i < n) {
-        size_t j = i + 1;
-        bool stopped = false;
-        while (j < n && !stopped) {
-            const size_t hi = std::min(n, j + window);
-            check(blissgpu_set_distance(x.data() + i * d, 1, x.data() + j * d, hi - j, (uint32_t)d, mb.metric, mb.mptr(), dist.data()));
-            size_t k = j;
-            for (; k < hi; k++) {
-                const float dk = dist[k - j];
-                if (dk != dk) throw std::domain_error("NaN distance");
-                const Song &a = as_song(playlist[i]), &b = as_song(playlist[k]);
-                const bool same = dk < thr || (a.title && b.title && a.artist && b.artist && *a.title == *b.title && *a.artist == *b.artist);
-                if (!same) { stopped = true; break; }
-            }
-            j = k;
-        }
-        out.push_back(playlist[i]);
-        i = j;
+    // one key per song for the title / artist rule: 0 when either is None, equal keys for equal (title, artist)
+    std::map<std::pair<std::string, std::string>, uint32_t> seen;
+    std::vector<uint32_t> meta(playlist.size(), 0);
+    for (size_t i = 0; i < playlist.size(); i++) {
+        const Song& s = as_song(playlist[i]);
+        if (s.title && s.artist) meta[i] = seen.emplace(std::make_pair(*s.title, *s.artist), (uint32_t)seen.size() + 1).first->second;
     }
+    std::vector<uint32_t> kept(playlist.size());
+    uint64_t n_kept = 0;
+    check_ordering(blissgpu_dedup_playlist(x.data(), playlist.size(), (uint32_t)d, nullptr, playlist.size(), meta.data(), mb.metric,
+                                           mb.mptr(), distance_threshold.value_or(0.05f), kept.data(), &n_kept));
+    std::vector<T> out;
+    for (uint64_t k = 0; k < n_kept; k++) out.push_back(playlist[kept[k]]);
     return out;
 }
 template <typename T>

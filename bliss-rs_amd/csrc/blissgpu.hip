@@ -23,7 +23,8 @@ thread_local std::string g_last_error;
 
 const char* const kKernelNames[K_COUNT] = {
     "fft512_kernel",     "onset_kernel",      "beat_kernel",   "stft8192_kernel", "tune_select_kernel",
-    "tune_pass2_kernel", "tune_final_kernel", "chroma_kernel",     "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel", "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel"};
+    "tune_pass2_kernel", "tune_final_kernel", "chroma_kernel",     "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel", "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel",
+    "dedup_next_kernel", "dedup_walk_kernel"};
 }  // namespace
 
 namespace bg {
@@ -331,7 +332,7 @@ int blissgpu_ctx_destroy(blissgpu_ctx* c) {
         (void)hipFree(c->bt_rwv); (void)hipFree(c->bt_dfwv); (void)hipFree(c->chroma_bank);
         scheduler_release(c);
         c->dbg_tuning.release(); c->dbg_nbpms.release(); c->dbg_chroma.release(); c->dbg_interval.release();
-        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release();
+        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_next.release(); c->st_idx.release();
         c->st_a.release(); c->st_b.release(); c->st_m.release(); c->st_dist.release(); c->st_out.release();
         if (c->h_scalar) (void)hipHostFree(c->h_scalar);
         if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
@@ -645,6 +646,55 @@ int blissgpu_song_to_song_device(blissgpu_ctx* c, const float* d_seeds, uint32_t
     return nan_check(c, c->pl_sync.p + 1, "blissgpu_song_to_song_device");
 }
 
+// ---- dedup_playlist_custom_distance (src/playlist.rs:343-402) over a playlist of rows ----
+static int dedup_args_ok(const char* who, const void* x, uint64_t n, uint32_t d, const void* seq, uint64_t len, int metric,
+                         const float* M, const void* kept, const void* n_kept) {
+    int rc = playlist_args_ok(who, x, x, kept, n ? 1u : 0u, n, d, metric, M);
+    if (rc) return rc;
+    if (!n_kept) return fail(BLISSGPU_ERR_INVALID, who, "NULL argument");
+    if (!seq && len && len != n) return fail(BLISSGPU_ERR_INVALID, who, "seq == NULL needs len == n");
+    if (len > 0x7FFFFFFEull) return fail(BLISSGPU_ERR_INVALID, who, "more than 2^31 - 2 playlist entries");
+    if (len && !n) return fail(BLISSGPU_ERR_INVALID, who, "seq entries must be < n");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_dedup_playlist_device(blissgpu_ctx* c, const float* d_x, uint64_t n, uint32_t d, const uint32_t* d_seq,
+                                   uint64_t len, const uint32_t* d_meta, int metric, const float* d_M, float threshold,
+                                   uint32_t* d_kept, uint64_t* d_n_kept) {
+    const char* who = "blissgpu_dedup_playlist_device";
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    int rc = dedup_args_ok(who, d_x, n, d, d_seq, len, metric, d_M, d_kept, d_n_kept);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    if (len == 0) {
+        HIP_TRY(hipMemsetAsync(d_n_kept, 0, sizeof(uint64_t), c->stream));
+        return BLISSGPU_OK;
+    }
+    const uint32_t len32 = (uint32_t)len;
+    rc = c->pl_sync.ensure(4);
+    if (!rc) rc = c->pl_next.ensure(len32);
+    if (rc) return rc;
+    // pl_sync: [1] NaN on the chain, [3] a seq entry >= n
+    HIP_TRY(hipMemsetAsync(c->pl_sync.p, 0, 4 * sizeof(uint32_t), c->stream));
+    {
+        Prof p(c, K_DEDUP_NEXT);
+        launch_dedup_next(d_x, n, d, d_seq, len32, d_meta, metric, d_M, threshold, c->pl_next.p, c->pl_sync.p + 3, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    {
+        Prof p(c, K_DEDUP_WALK);
+        launch_dedup_walk(d_x, n, d, d_seq, len32, d_meta, metric, d_M, threshold, c->pl_next.p, d_kept, d_n_kept,
+                          c->pl_sync.p + 1, c->pl_sync.p + 3, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    uint32_t flags[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(flags, c->pl_sync.p, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (flags[3]) return fail(BLISSGPU_ERR_INVALID, who, "seq entries must be < n");
+    if (flags[1]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance (the reference panics here)");
+    return BLISSGPU_OK;
+}
+
 }  // extern "C"
 
 // host-pointer wrappers: stage seeds / candidates / M in the context's buffers, run the device form, copy the result back
@@ -726,6 +776,48 @@ int blissgpu_song_to_song(const float* seeds, uint32_t n_seeds, const float* can
     rc = s.up(seeds, n_seeds, cand, n, d, metric, M, n * sizeof(uint32_t), false);
     if (!rc) rc = blissgpu_song_to_song_device(c, s.seeds, n_seeds, s.cand, n, d, metric, s.M, (uint32_t*)s.out);
     if (!rc) rc = s.down(order, n * sizeof(uint32_t), nullptr, 0);
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+int blissgpu_dedup_playlist(const float* x, uint64_t n, uint32_t d, const uint32_t* seq, uint64_t len, const uint32_t* meta,
+                            int metric, const float* M, float threshold, uint32_t* kept, uint64_t* n_kept) {
+    const char* who = "blissgpu_dedup_playlist";
+    int rc = dedup_args_ok(who, x, n, d, seq, len, metric, M, kept, n_kept);
+    if (rc) return rc;
+    if (seq)
+        for (uint64_t i = 0; i < len; i++)
+            if (seq[i] >= n) return fail(BLISSGPU_ERR_INVALID, who, "seq entries must be < n");
+    *n_kept = 0;
+    if (len == 0) return BLISSGPU_OK;
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    // st_idx: n_kept (two words) | kept[len] | seq[len] | meta[n]
+    const size_t o_kept = 2, o_seq = o_kept + len, o_meta = o_seq + (seq ? len : 0);
+    const float* dM = nullptr;
+    rc = c->st_b.ensure(std::max<size_t>(1, n * d));
+    if (!rc) rc = c->st_idx.ensure(o_meta + (meta ? n : 0));
+    if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
+    if (rc) return rc;
+    uint32_t* idx = c->st_idx.p;
+    hipError_t e = hipMemcpyAsync(c->st_b.p, x, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && seq) e = hipMemcpyAsync(idx + o_seq, seq, len * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && meta) e = hipMemcpyAsync(idx + o_meta, meta, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(dedup)", hipGetErrorString(e));
+    if (!rc)
+        rc = blissgpu_dedup_playlist_device(c, c->st_b.p, n, d, seq ? idx + o_seq : nullptr, len, meta ? idx + o_meta : nullptr,
+                                            metric, dM, threshold, idx + o_kept, reinterpret_cast<uint64_t*>(idx));
+    uint64_t nk = 0;
+    if (!rc) {  // the device form has synchronised: the count is there
+        e = hipMemcpyAsync(&nk, idx, sizeof(nk), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess && nk) e = hipMemcpyAsync(kept, idx + o_kept, nk * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(dedup)", hipGetErrorString(e));
+        if (!rc) *n_kept = nk;
+    }
     (void)hipStreamSynchronize(c->stream);
     return rc;
 }

@@ -259,10 +259,12 @@ struct blissgpu_ctx {
     // distances / playlist ordering scratch
     int n_cus = 0;
     bg::DevBuf<uint32_t> pl_sync, pl_keys;
+    bg::DevBuf<uint32_t> pl_next;                  // dedup: next[] of every playlist position
     bg::DevBuf<uint8_t> pl_tmp;
     bg::DevBuf<unsigned long long> pl_slots;
     bg::DevBuf<float> st_a, st_b, st_m, st_dist;   // staging of the host-pointer distance / playlist forms
     bg::DevBuf<uint8_t> st_out;
+    bg::DevBuf<uint32_t> st_idx;                   // staging of the dedup form: n_kept | kept | seq | meta
     std::vector<float> m_cache;                    // host copy of the matrix in st_m (skip the upload when unchanged)
     float* h_scalar = nullptr;                     // page-locked word the single-pair kernel writes its result to
     // profiling

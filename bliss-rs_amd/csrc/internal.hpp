@@ -112,6 +112,7 @@ enum KernelId : int {
     K_PAIRWISE, K_SET_DISTANCE, K_SONG_TO_SONG,
     K_SYNTH,
     K_ROLLFIX,
+    K_DEDUP_NEXT, K_DEDUP_WALK,  // playlist deduplication: never launched by the analysis path
     K_COUNT
 };
 
@@ -212,6 +213,13 @@ hipError_t sort_pairs_u32(void* tmp, size_t* tmp_bytes, uint32_t* keys_in, uint3
 void launch_song_to_song(const float* seeds, uint32_t n_seeds, const float* cand, uint32_t n, uint32_t d, int metric,
                          const float* M, uint32_t* order, unsigned long long* slots, uint32_t* sync, uint32_t grid,
                          hipStream_t st);
+// dedup_playlist_custom_distance over the playlist seq[0..len) (NULL: identity) of rows of x: next[p] for every position,
+// then the chain walk -> kept[0..*n_kept); a NaN on the chain sets *nan_flag, a seq entry >= n sets *bad
+void launch_dedup_next(const float* x, uint64_t n, uint32_t d, const uint32_t* seq, uint32_t len, const uint32_t* meta,
+                       int metric, const float* M, float thr, uint32_t* next, uint32_t* bad, hipStream_t st);
+void launch_dedup_walk(const float* x, uint64_t n, uint32_t d, const uint32_t* seq, uint32_t len, const uint32_t* meta,
+                       int metric, const float* M, float thr, const uint32_t* next, uint32_t* kept, uint64_t* n_kept,
+                       uint32_t* nan_flag, uint32_t* bad, hipStream_t st);
 void launch_pairwise(const float* A, uint64_t n, const float* B, uint64_t m, uint32_t d, int metric, const float* M,
                      int m_is_diag, float* out, uint64_t ld_out, hipStream_t);
 void launch_synth(float* pcm, const SongDesc* songs, uint32_t n_songs, const uint32_t* pfx_e, uint32_t tiles_e,

@@ -457,4 +457,183 @@ void launch_pair_distance(const float* a, const float* b, uint32_t d, int metric
     hipLaunchKernelGGL(pair_distance_kernel, dim3(1), dim3(64), 0, st, p, d, metric, d_M, out);
 }
 
+// ---- dedup_playlist_custom_distance (src/playlist.rs:367-402) over a playlist given as row indices seq[0..len) ----
+// The current song p absorbs the songs that follow it while n32(dist(p, q)) < threshold or both carry the same non-empty
+// (title, artist) -- the distance first: a NaN there panics even when the metadata match --, and the walk resumes at the
+// first song not absorbed.  The chain of kept songs is a forward pointer chain p -> next(p), so:
+//   dedup_next_kernel  one lane per position p: next(p) among q = p+1 .. p+DD_W (almost every lane stops at q = p+1);
+//                      NaN stops flagged, a window of DD_W duplicates leaves the entry OPEN
+//   dedup_walk_kernel  one workgroup follows the chain from 0 through LDS tiles of next[] (each entry read from HBM at
+//                      most once; a 64-entry window per wavefront, its chain by pointer doubling); at an OPEN node
+//                      p the workgroup scans q = p+DD_W+1 .. itself, 256 distances at a time, first stop by a min-reduction.
+// Scans hang off chain nodes and end where the chain goes on, so they are disjoint: at most len * DD_W + len + 256 per OPEN
+// node distances in all, whatever the playlist.  Only a NaN met ON the chain is the reference's panic; next(p) of a song
+// the chain skips is never looked at.
+// meta: one key per row of x (0 = title or artist is None; equal non-zero keys = equal (title, artist)), or NULL.
+constexpr uint32_t DD_W = 64;                 // look-ahead of one lane of dedup_next_kernel
+constexpr uint32_t DD_NAN = 0x80000000u;      // next[p] = q | DD_NAN: dist(p, q) is NaN (len < 2^31, checked by the host)
+constexpr uint32_t DD_OPEN = 0xFFFFFFFFu;     // next[p]: the DD_W songs after p are all duplicates of p
+constexpr uint32_t DD_TILE = 4096;            // entries of next[] per LDS tile (16 KiB)
+
+// row of playlist position p; an entry >= n raises the caller's flag and reads row 0 instead (never out of bounds)
+__device__ __forceinline__ uint32_t dd_row(const uint32_t* __restrict__ seq, uint32_t p, uint64_t n, uint32_t* bad) {
+    if (!seq) return p;
+    const uint32_t r = seq[p];
+    if ((uint64_t)r >= n) {
+        atomicOr(bad, 1u);
+        return 0u;
+    }
+    return r;
+}
+
+// 0: q is not a duplicate of p, 1: it is, 2: the distance is NaN
+__device__ __forceinline__ int dd_same(const float* a, const float* b, uint32_t d, int metric, const float* __restrict__ M,
+                                       float thr, uint32_t ka, uint32_t kb) {
+    const float v = pl_distance(a, b, d, metric, M);
+    if (v != v) return 2;
+    return (v < thr || (ka != 0u && ka == kb)) ? 1 : 0;
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void dedup_next_kernel(const float* __restrict__ x, uint64_t n, uint32_t d_rt,
+                                                         const uint32_t* __restrict__ seq, uint32_t len,
+                                                         const uint32_t* __restrict__ meta, int metric,
+                                                         const float* __restrict__ M, float thr, uint32_t* __restrict__ next,
+                                                         uint32_t* bad) {
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= len) return;
+    const uint32_t d = D > 0 ? (uint32_t)D : d_rt;
+    const uint32_t rp = dd_row(seq, p, n, bad);
+    const uint32_t kp = meta ? meta[rp] : 0u;
+    float a[D > 0 ? D : 1];
+    if (D > 0) {
+#pragma unroll
+        for (int k = 0; k < D; k++) a[k] = x[(size_t)rp * D + k];
+    }
+    const float* ap = D > 0 ? a : x + (size_t)rp * d;
+    const uint32_t hi = len - p - 1 < DD_W ? len : p + 1 + DD_W;
+    uint32_t out = hi == len ? len : DD_OPEN;
+    for (uint32_t q = p + 1; q < hi; q++) {
+        const uint32_t rq = dd_row(seq, q, n, bad);
+        const int s = dd_same(ap, x + (size_t)rq * d, d, metric, M, thr, kp, meta ? meta[rq] : 0u);
+        if (s != 1) {
+            out = s == 2 ? (q | DD_NAN) : q;
+            break;
+        }
+    }
+    next[p] = out;
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void dedup_walk_kernel(const float* __restrict__ x, uint64_t n, uint32_t d_rt,
+                                                         const uint32_t* __restrict__ seq, uint32_t len,
+                                                         const uint32_t* __restrict__ meta, int metric,
+                                                         const float* __restrict__ M, float thr,
+                                                         const uint32_t* __restrict__ next, uint32_t* __restrict__ kept,
+                                                         uint64_t* __restrict__ n_kept, uint32_t* nan_flag, uint32_t* bad) {
+    __shared__ uint32_t s_next[DD_TILE];
+    __shared__ uint32_t red[4];
+    const uint32_t d = D > 0 ? (uint32_t)D : d_rt;
+    const uint32_t tid = threadIdx.x;
+    const int lane = lane_id(), wave = wave_id();
+    // Every wavefront runs the same walk on the same LDS data (the control flow is workgroup-uniform); wavefront 0 writes.
+    uint32_t cur = 0, tile = DD_OPEN, nk = 0;
+    bool nan = false;
+    while (cur < len) {
+        const uint32_t tb = cur / DD_TILE * DD_TILE;
+        if (tb != tile) {
+            __syncthreads();  // everyone is done with the previous tile
+            const uint32_t cnt = len - tb < DD_TILE ? len - tb : DD_TILE;
+            for (uint32_t i = tid; i < cnt; i += 256u) s_next[i] = next[tb + i];
+            __syncthreads();
+            tile = tb;
+        }
+        // a window of up to 64 positions from cur (not past the tile or the playlist): the chain inside it, lane by lane
+        const uint32_t lim = len - tb < DD_TILE ? len : tb + DD_TILE;
+        const uint32_t wl = lim - cur < 64u ? lim - cur : 64u;
+        // Pointer doubling over the window: f(l) = the window offset next[] points to, 64 = leaves the window (or ends,
+        // or is flagged); g[b] = f^(2^b); lane k composes the powers of its bits -> v = f^k(0), the k-th chain node of the
+        // window.  Eleven lane permutations per window instead of one dependent step per kept song.
+        const uint32_t w = (uint32_t)lane < wl ? s_next[cur - tb + lane] : 0u;
+        const bool inside = (uint32_t)lane < wl && w != DD_OPEN && !(w & DD_NAN) && w < len && w - cur < wl;
+        int g[6];
+        g[0] = inside ? (int)(w - cur) : 64;
+#pragma unroll
+        for (int b = 1; b < 6; b++) {
+            const int y = __shfl(g[b - 1], g[b - 1] & 63, WAVE);
+            g[b] = g[b - 1] < 64 ? y : 64;
+        }
+        int v = 0;
+#pragma unroll
+        for (int b = 0; b < 6; b++) {
+            const int y = __shfl(g[b], v & 63, WAVE);
+            if ((lane >> b) & 1) v = v < 64 ? y : 64;
+        }
+        // the chain nodes of the window are v_0 < v_1 < ... < v_(m-1) (lanes 0 .. m-1): kept in order
+        const uint32_t m = (uint32_t)__popcll(__ballot(v < 64));
+        if (wave == 0 && v < 64) kept[nk + (uint32_t)lane] = cur + (uint32_t)v;
+        nk += m;
+        const uint32_t off = (uint32_t)__builtin_amdgcn_readlane(v, (int)(m - 1));
+        const uint32_t nx = (uint32_t)__builtin_amdgcn_readlane((int)w, (int)off);
+        if (nx == DD_OPEN) {
+            // the DD_W songs after p are duplicates of p: the workgroup goes on scanning from p + DD_W + 1
+            const uint32_t p = cur + off;
+            const uint32_t rp = dd_row(seq, p, n, bad);
+            const uint32_t kp = meta ? meta[rp] : 0u;
+            uint32_t stop = DD_OPEN;  // 2q (+1 when NaN) of the first song that is not absorbed
+            for (uint32_t base = p + DD_W + 1; base < len && stop == DD_OPEN; base += 256u) {
+                uint32_t key = DD_OPEN;
+                const uint32_t q = base + tid;
+                if (q < len) {
+                    const uint32_t rq = dd_row(seq, q, n, bad);
+                    const int s = dd_same(x + (size_t)rp * d, x + (size_t)rq * d, d, metric, M, thr, kp, meta ? meta[rq] : 0u);
+                    if (s != 1) key = 2u * q + (s == 2 ? 1u : 0u);
+                }
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    const uint32_t other = (uint32_t)__shfl_xor((int)key, o, WAVE);
+                    key = other < key ? other : key;
+                }
+                if (lane == 0) red[wave] = key;
+                __syncthreads();
+                for (int i = 0; i < 4; i++) stop = red[i] < stop ? red[i] : stop;
+                __syncthreads();  // red is rewritten by the next round
+            }
+            if (stop == DD_OPEN) break;  // every song to the end is a duplicate of p
+            if (stop & 1u) { nan = true; break; }
+            cur = stop >> 1;
+        } else if (nx & DD_NAN) {
+            nan = true;
+            break;
+        } else {
+            cur = nx;  // == len: the playlist ends in duplicates of the last kept song
+        }
+    }
+    if (tid == 0) {
+        *n_kept = nk;
+        if (nan) *nan_flag = 1u;
+    }
+}
+
+void launch_dedup_next(const float* x, uint64_t n, uint32_t d, const uint32_t* seq, uint32_t len, const uint32_t* meta,
+                       int metric, const float* M, float thr, uint32_t* next, uint32_t* bad, hipStream_t st) {
+    const dim3 grid((len + 255u) / 256u);
+#define DD(DD_D) hipLaunchKernelGGL((dedup_next_kernel<DD_D>), grid, dim3(256), 0, st, x, n, d, seq, len, meta, metric, M, thr, next, bad)
+    if (d == 23) DD(23);
+    else if (d == 20) DD(20);
+    else DD(0);
+#undef DD
+}
+
+void launch_dedup_walk(const float* x, uint64_t n, uint32_t d, const uint32_t* seq, uint32_t len, const uint32_t* meta,
+                       int metric, const float* M, float thr, const uint32_t* next, uint32_t* kept, uint64_t* n_kept,
+                       uint32_t* nan_flag, uint32_t* bad, hipStream_t st) {
+#define DD(DD_D) hipLaunchKernelGGL((dedup_walk_kernel<DD_D>), dim3(1), dim3(256), 0, st, x, n, d, seq, len, meta, metric, M, thr, \
+                                    next, kept, n_kept, nan_flag, bad)
+    if (d == 23) DD(23);
+    else if (d == 20) DD(20);
+    else DD(0);
+#undef DD
+}
+
 }  // namespace bg

@@ -303,6 +303,36 @@ class Context:
         self._post()
         return order.to(torch.int64)
 
+    def dedup_playlist(self, X, seq=None, meta=None, metric: str = "euclidean", M=None, threshold=None):
+        """dedup_playlist_custom_distance over the playlist X[seq] (seq = None: every row): (kept, n_kept) -- kept is an
+        int32 tensor of len(seq) slots whose first n_kept (a one-element int64 tensor) hold the kept positions into seq.
+        Stays on the device: nothing is copied back.  meta: one int32 key per row of X (playlist.meta_keys) or None.
+        Raises BlissGpuError(ERR_NAN) for a NaN distance on the chain of kept songs (synchronises for that check)."""
+        from .playlist import _METRICS
+
+        torch = self.torch
+        assert X.is_cuda and X.dtype == torch.float32 and X.dim() == 2
+        X = X.contiguous()
+        n, d = X.shape
+        length = n if seq is None else seq.shape[0]
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        if seq is not None:
+            assert seq.is_cuda and seq.dtype == torch.int32
+            seq = seq.contiguous()
+        if meta is not None:
+            assert meta.is_cuda and meta.dtype == torch.int32 and meta.shape[0] == n
+            meta = meta.contiguous()
+        if M is not None:
+            M = M.contiguous()
+        kept = torch.empty((max(length, 1),), dtype=torch.int32, device=X.device)
+        n_kept = torch.empty((1,), dtype=torch.int64, device=X.device)
+        self._pre()
+        _ffi.check(self._L.blissgpu_dedup_playlist_device(self._h, ptr(X), n, d, ptr(seq), length, ptr(meta), _METRICS[metric],
+                                                          ptr(M), float(0.05 if threshold is None else threshold), ptr(kept),
+                                                          ptr(n_kept)))
+        self._post()
+        return kept[:length], n_kept
+
     # ---- profiling ----
     def profile_enable(self, on: bool = True):
         _ffi.check(self._L.blissgpu_profile_enable(self._h, int(on)))

@@ -15,14 +15,25 @@ two without re-analysing anything:
                           the current schema (track_number text -> integer, disc_number, training_triplet,
                           version not null default 1), keyed on `pragma user_version` like the crate
 
+and the reference's library playlists (`Library::songs_from_library` / `song_from_path` / `songs_from_album` /
+`playlist_from` / `playlist_from_custom` / `album_playlist_from`, src/library.rs:762-893, 1355-1460) as functions of a
+database:
+
+    songs_from_library, song_from_path, songs_from_album
+    playlist_from, playlist_from_custom   seeds first, seeds removed from the pool by path, the order and ONE
+                                          deduplication of the whole chain on the device (playlist.dedup_order)
+    album_playlist_from                   closest_album_to_group, cropped after `number_albums` album changes
+
 SQLite stores `real` as f64; an f32 feature widens exactly on the way in and narrows exactly on the way out, so a
-round trip is bit-exact.  Pure host code: nothing here touches the GPU.
+round trip is bit-exact.  The schema, load and store helpers are host code; the playlists run their distances on the
+GPU like the rest of the playlist module.
 """
 import sqlite3
 from typing import List, Sequence, Tuple, Union
 
 import numpy as np
 
+from . import playlist
 from .song import Analysis, FeaturesVersion, ProviderError, Song
 
 _SONG_COLUMNS = ("path", "artist", "title", "album", "album_artist", "track_number", "disc_number", "genre", "duration",
@@ -152,6 +163,10 @@ def load_feature_matrix(db: Conn, features_version: FeaturesVersion = FeaturesVe
 
 def load_songs(db: Conn, features_version: FeaturesVersion = FeaturesVersion.LATEST) -> List[Song]:
     """`songs_from_library` (src/library.rs:1355-1372) without the extra_info payload."""
+    return _load_songs_and_matrix(db, features_version)[0]
+
+
+def _load_songs_and_matrix(db: Conn, features_version: FeaturesVersion):
     version = FeaturesVersion(features_version)
     conn, own = _connect(db)
     try:
@@ -168,7 +183,7 @@ def load_songs(db: Conn, features_version: FeaturesVersion = FeaturesVersion.LAT
         kw.pop("version")
         kw["duration"] = float(kw["duration"] or 0.0)
         out.append(Song(analysis=Analysis(feats, version), features_version=version, **kw))
-    return out
+    return out, matrix
 
 
 def store_song(db: Conn, song: Song) -> None:
@@ -203,3 +218,136 @@ def store_songs(db: Conn, songs: Sequence[Song]) -> None:
     finally:
         if own:
             conn.close()
+
+
+# ---------------------------------------------------------------------------------------------------
+# library playlists (src/library.rs:762-893)
+# ---------------------------------------------------------------------------------------------------
+def _song_from_row(row, feats, version) -> Song:
+    kw = dict(zip(_SONG_COLUMNS, row))
+    kw.pop("version")
+    kw["duration"] = float(kw["duration"] or 0.0)
+    return Song(analysis=Analysis(feats, version), features_version=version, **kw)
+
+
+def songs_from_library(db: Conn, features_version: FeaturesVersion = FeaturesVersion.LATEST) -> List[Song]:
+    """`Library::songs_from_library` (src/library.rs:1355-1372): the analysed songs of that features version, by id."""
+    return load_songs(db, features_version)
+
+
+def song_from_path(db: Conn, path: str) -> Song:
+    """`Library::song_from_path` (src/library.rs:1414-1460): the analysed song at `path`, whatever its features version."""
+    conn, own = _connect(db)
+    try:
+        row = conn.execute(f"select {', '.join(_SONG_COLUMNS)} from song where path = ? and analyzed = true",
+                           (path,)).fetchone()
+        if row is None:
+            raise ProviderError("Query returned no rows")
+        feats = [r[0] for r in conn.execute("select feature from feature join song on song.id = feature.song_id "
+                                            "where song.path = ? order by feature_index", (path,))]
+    finally:
+        if own:
+            conn.close()
+    version = FeaturesVersion(row[_SONG_COLUMNS.index("version")])
+    if len(feats) != version.feature_count():
+        raise ProviderError(f"song has more or less than {FeaturesVersion.LATEST.feature_count()} features")
+    return _song_from_row(row, np.array(feats, np.float64).astype(np.float32), version)
+
+
+def songs_from_album(db: Conn, album_title: str, features_version: FeaturesVersion = FeaturesVersion.LATEST) -> List[Song]:
+    """`Library::songs_from_album` (src/library.rs:1379-1411): the album's analysed songs of that features version,
+    ordered by disc then track number (SQLite: NULL first)."""
+    version = FeaturesVersion(features_version)
+    conn, own = _connect(db)
+    try:
+        rows = conn.execute(f"select {', '.join(_SONG_COLUMNS)}, id from song where album = ? and analyzed = true and "
+                            "version = ? order by disc_number, track_number", (album_title, int(version))).fetchall()
+        feats = {}
+        for value, song_id in conn.execute(
+                "select feature, song.id from feature join song on song.id = feature.song_id where album = ? and "
+                "analyzed = true and version = ? order by song_id, feature_index", (album_title, int(version))):
+            feats.setdefault(song_id, []).append(value)
+    finally:
+        if own:
+            conn.close()
+    if not rows:
+        raise ProviderError("target album was not found in the database.")
+    out = []
+    for row in rows:
+        f = feats.get(row[-1], [])
+        if len(f) != version.feature_count():
+            raise ProviderError(f"Song with ID {row[-1]} and path {row[0]} has a different feature number than expected. "
+                                "Please rescan or update the song library.")
+        out.append(_song_from_row(row[:-1], np.array(f, np.float64).astype(np.float32), version))
+    return out
+
+
+def playlist_from(db: Conn, song_paths: Sequence[str]) -> List[Song]:
+    """`Library::playlist_from` (src/library.rs:762-767): euclidean distance, closest_to_songs, deduplicated."""
+    return playlist_from_custom(db, song_paths, playlist.euclidean_distance, playlist.closest_to_songs, True)
+
+
+def playlist_from_custom(db: Conn, initial_song_paths: Sequence[str], metric_builder=playlist.euclidean_distance,
+                         sort_by=playlist.closest_to_songs, deduplicate: bool = True) -> List[Song]:
+    """`Library::playlist_from_custom` (src/library.rs:803-850): the initial songs, then the rest of the library ordered
+    by `sort_by(initial_songs, songs, metric_builder)`, deduplicated over the whole chain when `deduplicate`.
+
+    With this package's closest_to_songs / song_to_song the library matrix is read once, the order comes from the device
+    and the deduplication is ONE device call over the rows (seeds first) -- no per-song call, no second copy of the rows.
+    Any other `sort_by` runs on the host and its result goes through the same single call.  The metric is one of the
+    device metrics (playlist._metric_of)."""
+    initial_song_paths = list(initial_song_paths)
+    initial = []
+    for p in initial_song_paths:
+        try:
+            initial.append(song_from_path(db, p))
+        except Exception as e:
+            raise ProviderError(f"song '{p}' has not been analyzed") from e
+    songs, X = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
+    metric, m = playlist._metric_of(metric_builder)
+    chosen = set(initial_song_paths)
+    pool = [i for i, s in enumerate(songs) if s.path not in chosen]
+    if sort_by not in (playlist.closest_to_songs, playlist.song_to_song):
+        ordered = list(sort_by(initial, [songs[i] for i in pool], metric_builder))
+        chain = initial + ordered
+        return playlist.dedup_playlist_custom_distance(chain, None, metric_builder) if deduplicate else chain
+    # the rows of the library; a seed's row is its library row, or appended when it is not one of them (another
+    # features version)
+    in_library = {s.path for s in songs}
+    extra = [s for s in initial if s.path not in in_library]
+    rows = songs + extra
+    if not rows:
+        return []
+    if extra:
+        X = np.vstack([X] + [np.asarray(s.analysis.as_vec(), np.float32)[None, :] for s in extra])
+    row_of = {s.path: i for i, s in enumerate(rows)}
+    seed_rows = np.asarray([row_of[s.path] for s in initial], np.int64)
+    order = np.zeros(0, np.int64)
+    if pool:
+        pool_idx = np.asarray(pool, np.int64)
+        if sort_by is playlist.closest_to_songs:
+            o, _ = playlist.closest_to_songs_order(X[seed_rows], X[pool_idx], metric, m)
+        else:
+            o = playlist.song_to_song_order(X[seed_rows], X[pool_idx], metric, m)
+        order = pool_idx[o.astype(np.int64)]
+    seq = np.concatenate([seed_rows, order])
+    kept = (playlist.dedup_order(X, seq, playlist.meta_keys(rows), metric, m) if deduplicate
+            else np.arange(seq.shape[0]))
+    return [initial[k] if k < len(initial) else rows[int(seq[k])] for k in kept]
+
+
+def album_playlist_from(db: Conn, album_title: str, number_albums: int) -> List[Song]:
+    """`Library::album_playlist_from` (src/library.rs:857-893): the album, then the albums closest to it
+    (closest_album_to_group), cut after `number_albums` changes of album."""
+    album = songs_from_album(db, album_title)
+    pl = playlist.closest_album_to_group(album, songs_from_library(db))
+    count, index, current = 0, 0, album_title
+    for s in pl:
+        if s.album != current:
+            count += 1
+            if count > number_albums:
+                break
+            current = s.album
+        index += 1
+    return pl[:index]
+

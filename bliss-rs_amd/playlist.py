@@ -202,44 +202,62 @@ def song_to_song(initial_songs, candidate_songs, metric_builder=euclidean_distan
     return [candidate_songs[i] for i in order]
 
 
-def _same_title_artist(a, b) -> bool:
-    a, b = _song_of(a), _song_of(b)
-    return (a.title is not None and b.title is not None and a.artist is not None and b.artist is not None
-            and a.title == b.title and a.artist == b.artist)
+def meta_keys(songs) -> np.ndarray:
+    """One u32 key per song for the title / artist rule of dedup_playlist_custom_distance (src/playlist.rs:383-389:
+    both titles and both artists Some, and equal): 0 when the title or the artist is None, otherwise equal keys
+    exactly for equal (title, artist) -- a dictionary, so there are no collisions."""
+    seen, keys = {}, np.zeros(len(songs), np.uint32)
+    for i, s in enumerate(songs):
+        s = _song_of(s)
+        if s.title is not None and s.artist is not None:
+            keys[i] = seen.setdefault((s.title, s.artist), len(seen) + 1)
+    return keys
+
+
+def dedup_order(X, seq=None, meta=None, metric="euclidean", m=None, threshold=None) -> np.ndarray:
+    """Index form of dedup_playlist_custom_distance (src/playlist.rs:367-402) in one device call: the playlist is
+    X[seq] (seq = None: every row of X in order), meta holds one key per ROW of X (see meta_keys; None: no title /
+    artist rule).  Returns the kept positions into seq (int64).  A NaN distance the reference would evaluate raises
+    ValueError, like its n32() panic."""
+    X = np.ascontiguousarray(np.atleast_2d(X), dtype=np.float32)
+    n, d = X.shape
+    seq_p = None
+    if seq is not None:
+        seq = np.ascontiguousarray(seq, dtype=np.uint32).reshape(-1)
+        seq_p = seq.ctypes.data
+    length = n if seq is None else seq.shape[0]
+    meta_p = None
+    if meta is not None:
+        meta = np.ascontiguousarray(meta, dtype=np.uint32).reshape(-1)
+        if meta.shape[0] != n:
+            raise ValueError("meta needs one key per row of X")
+        meta_p = meta.ctypes.data
+    mp = None
+    if m is not None:
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        mp = m.ctypes.data
+    kept, n_kept = np.empty(max(length, 1), np.uint32), C.c_uint64()
+    try:
+        _ffi.check(_ffi.lib().blissgpu_dedup_playlist(X.ctypes.data, n, d, seq_p, length, meta_p, _METRICS[metric], mp,
+                                                      np.float32(0.05 if threshold is None else threshold),
+                                                      kept.ctypes.data, C.byref(n_kept)))
+    except _ffi.BlissGpuError as e:
+        if e.code == _ffi.ERR_NAN:
+            raise ValueError("NaN distance (noisy_float::n32 panic in the reference)") from e
+        raise
+    return kept[:n_kept.value].astype(np.int64)
 
 
 def dedup_playlist_custom_distance(playlist, distance_threshold=None, metric_builder=euclidean_distance, window=64):
     """src/playlist.rs:367-402: a song absorbs the songs that follow it while they are closer than the threshold
-    (default 0.05) or carry the same non-empty title and artist.  Distances from the current song to the next
-    `window` songs are evaluated in one device call."""
+    (default 0.05) or carry the same non-empty title and artist.  One device call for the whole playlist
+    (dedup_order); `window` is accepted for compatibility and unused."""
     playlist = list(playlist)
-    thr = np.float32(0.05 if distance_threshold is None else distance_threshold)
+    if not playlist:
+        return []
     metric, m = _metric_of(metric_builder)
-    X = _matrix(playlist)
-    out, i, n = [], 0, len(playlist)
-    while i < n:
-        j = i + 1
-        while j < n:
-            hi = min(n, j + window)
-            try:
-                dist = set_distances(X[i:i + 1], X[j:hi], metric, m)
-            except _ffi.BlissGpuError as e:  # pragma: no cover
-                _nan_to_panic(e)
-            stop = None
-            for k in range(j, hi):
-                dk = dist[k - j]
-                if np.isnan(dk):
-                    raise ValueError("NaN distance (noisy_float::n32 panic in the reference)")
-                if not (dk < thr or _same_title_artist(playlist[i], playlist[k])):
-                    stop = k
-                    break
-            if stop is not None:
-                j = stop
-                break
-            j = hi
-        out.append(playlist[i])
-        i = j
-    return out
+    kept = dedup_order(_matrix(playlist), None, meta_keys(playlist), metric, m, distance_threshold)
+    return [playlist[i] for i in kept]
 
 
 def dedup_playlist(playlist, distance_threshold=None):

@@ -283,6 +283,23 @@ int blissgpu_closest_to_songs_device(blissgpu_ctx *ctx, const float *d_seeds, ui
 int blissgpu_song_to_song_device(blissgpu_ctx *ctx, const float *d_seeds, uint32_t n_seeds, const float *d_cand,
                                  uint64_t n, uint32_t d, int metric, const float *d_M, uint32_t *d_order);
 
+/* dedup_playlist_custom_distance (src/playlist.rs:343-402) over the playlist seq[0..len) of rows of the n x d matrix x:
+ * a song absorbs the songs that follow it while n32(metric(song, next)) < threshold (the reference's default is 0.05f) or
+ * both have the same non-empty title and artist; the walk resumes at the first song not absorbed.  seq may be NULL
+ * (identity, len == n); every entry must be < n.  meta (may be NULL: no title / artist rule) holds one key per ROW of x:
+ * 0 = title or artist is None, equal non-zero keys = equal (title, artist).  kept[0..*n_kept) (room for len entries)
+ * receives positions into seq, in order; len == 0 keeps nothing, len == 1 keeps [0].  A NaN distance the reference
+ * evaluates (one on the chain of kept songs) returns BLISSGPU_ERR_NAN; the distances it never evaluates do not matter.
+ * Two launches whatever the playlist (dedup_next_kernel, dedup_walk_kernel: DESIGN.md 3.9), at most len * 65 distances. */
+int blissgpu_dedup_playlist(const float *x, uint64_t n, uint32_t d, const uint32_t *seq, uint64_t len,
+                            const uint32_t *meta, int metric, const float *M, float threshold, uint32_t *kept,
+                            uint64_t *n_kept);
+/* Device-resident form (device pointers, d_n_kept included); asynchronous except for the NaN / seq check, which
+ * synchronises the context's stream before returning. */
+int blissgpu_dedup_playlist_device(blissgpu_ctx *ctx, const float *d_x, uint64_t n, uint32_t d, const uint32_t *d_seq,
+                                   uint64_t len, const uint32_t *d_meta, int metric, const float *d_M, float threshold,
+                                   uint32_t *d_kept, uint64_t *d_n_kept);
+
 /* FeaturesVersion::feature_weights (src/lib.rs:168-173, 209-234): d x d row-major diagonal matrix. */
 int blissgpu_feature_weights(uint32_t features_version, float *M);
 
