@@ -23,6 +23,8 @@
 //!   * `closest_to_songs` / `song_to_song`     src/playlist.rs:256-326     -> [`order_on_device`]
 //!   * `dedup_playlist` / `dedup_playlist_custom_distance`
 //!                                             src/playlist.rs:343-402     -> [`dedup_on_device`]
+//!   * `closest_to_songs(&[song], ..)` cut after k, many songs per call (`Library::playlist_from(..).take(k)`)
+//!                                             src/playlist.rs:256-270     -> [`nearest_on_device`]
 //!
 //! build.rs of the crate, under the feature:
 //! ```ignore
@@ -139,6 +141,11 @@ pub mod sys {
         pub fn blissgpu_dedup_playlist_device(ctx: *mut blissgpu_ctx, d_x: *const f32, n: u64, d: u32, d_seq: *const u32,
                                               len: u64, d_meta: *const u32, metric: c_int, d_m: *const f32, threshold: f32,
                                               d_kept: *mut u32, d_n_kept: *mut u64) -> c_int;
+        pub fn blissgpu_knn(queries: *const f32, q: u64, cand: *const f32, n: u64, d: u32, metric: c_int, m_matrix: *const f32,
+                            skip: *const u32, k: u32, idx: *mut u32, dist: *mut f32) -> c_int;
+        pub fn blissgpu_knn_device(ctx: *mut blissgpu_ctx, d_queries: *const f32, q: u64, d_cand: *const f32, n: u64, d: u32,
+                                   metric: c_int, d_m: *const f32, d_skip: *const u32, k: u32, d_idx: *mut u32,
+                                   d_dist: *mut f32) -> c_int;
 
         // ---- one process, every GPU of the node ----
         pub fn blissgpu_node_create(n_devices: c_int, devices: *const c_int, node: *mut *mut blissgpu_node) -> c_int;
@@ -378,6 +385,34 @@ pub fn dedup_on_device<T: AsRef<Song> + Clone>(playlist: &[T], distance_threshol
         return Err(gpu_err(rc));
     }
     Ok(kept[..n_kept as usize].iter().map(|&i| playlist[i as usize].clone()).collect())
+}
+
+/// `closest_to_songs(&[song], candidates, metric)` cut after `k` (src/playlist.rs:256-270) for every song of `songs` in one
+/// library call -- what `Library::playlist_from(&[song])?.take(k)` (src/library.rs:762-850) asks per song: the `k` nearest
+/// candidates in ascending distance, equal distances in candidate order, no distance matrix.  `exclude_self` leaves the
+/// first candidate equal to the song (`Song: PartialEq`) out of that song's list.  A NaN distance is `BLISSGPU_ERR_NAN`.
+pub fn nearest_on_device<T: AsRef<Song> + Clone>(songs: &[T], candidates: &[T], k: usize, metric: Metric, m: Option<&Array2<f32>>,
+                                                 exclude_self: bool) -> BlissResult<Vec<Vec<T>>> {
+    if songs.is_empty() || candidates.is_empty() {
+        return Ok(vec![Vec::new(); songs.len()]);
+    }
+    let d = candidates[0].as_ref().analysis.as_vec().len();
+    let flat = |songs: &[T]| songs.iter().flat_map(|s| s.as_ref().analysis.as_vec()).collect::<Vec<f32>>();
+    let (queries, cand) = (flat(songs), flat(candidates));
+    let skip = songs
+        .iter()
+        .map(|s| if exclude_self { candidates.iter().position(|c| c.as_ref() == s.as_ref()).map_or(u32::MAX, |j| j as u32) } else { u32::MAX })
+        .collect::<Vec<u32>>();
+    let (_keep, mp) = matrix_ptr(m);
+    let mut idx = vec![0u32; songs.len() * k];
+    let rc = unsafe {
+        sys::blissgpu_knn(queries.as_ptr(), songs.len() as u64, cand.as_ptr(), candidates.len() as u64, d as u32, metric.code(), mp,
+                          skip.as_ptr(), k as u32, idx.as_mut_ptr(), std::ptr::null_mut())
+    };
+    if rc != sys::BLISSGPU_OK {
+        return Err(gpu_err(rc));
+    }
+    Ok(idx.chunks(k).map(|row| row.iter().filter(|&&j| j != u32::MAX).map(|&j| candidates[j as usize].clone()).collect()).collect())
 }
 
 /// One process driving every GPU of the node: songs sharded by sample count, one `ncclAllGather` of the feature rows over

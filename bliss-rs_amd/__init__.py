@@ -9,6 +9,7 @@ bliss-rs / `bliss-audio` 0.13.0):
     Decoder.{decode, song_from_path, analyze_paths}  src/song/decoder.rs:115-333
     cue.{cue_track_bounds, analyze_cue_tracks}    BlissCueFile::get_songs, src/cue.rs:205-246 (sheet parsing stays with the host)
     euclidean / cosine / mahalanobis distance, closest_to_songs, song_to_song, dedup, ...   src/playlist.rs
+    playlist.nearest_order / nearest_songs, library.similar_songs: the k closest songs of many songs in one call
     library.{load_feature_matrix, load_songs, store_song}   feature table of src/library.rs:500-531, 1355-1372, 1560-1630
     library.{playlist_from, playlist_from_custom, album_playlist_from, songs_from_album}   src/library.rs:762-893
 

@@ -83,6 +83,9 @@ SIGNATURES = {
                                           _u64p]),
     "blissgpu_dedup_playlist_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, C.c_int, _vp,
                                                  C.c_float, _vp, _vp]),
+    "blissgpu_knn": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, C.c_uint32, _vp, _vp]),
+    "blissgpu_knn_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, C.c_uint32, _vp,
+                                      _vp]),
     "blissgpu_set_distance_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp]),
     "blissgpu_closest_to_songs_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp,
                                                    _vp]),

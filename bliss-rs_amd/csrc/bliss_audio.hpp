@@ -440,6 +440,47 @@ std::vector<T> closest_to_songs(const std::vector<T>& initial_songs, const std::
     return out;
 }
 
+// closest_to_songs for many single seeds at once, cut after k (src/playlist.rs:256-270; Library::playlist_from(&[song])
+// .take(k), src/library.rs:762-850): row i of idx = the k candidates closest to queries[i] in ascending distance, equal
+// distances in candidate order, without candidate skip[i] (0xFFFFFFFF: none); short rows end in 0xFFFFFFFF / +inf.
+// queries / candidates are row-major q x d / n x d; one device call, no distance matrix.
+struct NearestOrder { std::vector<uint32_t> idx; std::vector<float> dist; };
+inline NearestOrder nearest_order(const std::vector<float>& queries, size_t q, const std::vector<float>& candidates, size_t n, size_t d,
+                                  uint32_t k, const MetricBuilder& mb, const std::vector<uint32_t>* skip = nullptr) {
+    NearestOrder out{std::vector<uint32_t>(q * k), std::vector<float>(q * k)};
+    check_ordering(blissgpu_knn(queries.data(), q, candidates.data(), n, (uint32_t)d, mb.metric, mb.mptr(), skip ? skip->data() : nullptr,
+                                k, out.idx.data(), out.dist.data()));
+    return out;
+}
+
+// for every song: closest_to_songs(&[song], candidate_songs, metric)[..k]; exclude_self leaves out the first candidate whose
+// Song equals the query song (Song: PartialEq, compared as closest_album_to_group does)
+template <typename T>
+std::vector<std::vector<T>> nearest_songs(const std::vector<T>& songs, const std::vector<T>& candidate_songs, uint32_t k, const MetricBuilder& mb,
+                                          bool exclude_self = false) {
+    std::vector<std::vector<T>> out(songs.size());
+    if (songs.empty() || candidate_songs.empty()) return out;
+    size_t d = 0, dq = 0;
+    const auto x = feature_matrix(candidate_songs, d);
+    const auto s = feature_matrix(songs, dq);
+    std::vector<uint32_t> skip(songs.size(), 0xFFFFFFFFu);
+    if (exclude_self)
+        for (size_t i = 0; i < songs.size(); i++)
+            for (size_t j = 0; j < candidate_songs.size(); j++)
+            {
+                const Song &a = as_song(candidate_songs[j]), &b = as_song(songs[i]);
+                if (a.path == b.path && a.analysis == b.analysis && a.album == b.album && a.title == b.title && a.artist == b.artist &&
+                    a.track_number == b.track_number && a.disc_number == b.disc_number) { skip[i] = (uint32_t)j; break; }
+            }
+    const auto r = nearest_order(s, songs.size(), x, candidate_songs.size(), d, k, mb, &skip);
+    for (size_t i = 0; i < songs.size(); i++)
+        for (uint32_t c = 0; c < k; c++) {
+            const uint32_t j = r.idx[i * k + c];
+            if (j != 0xFFFFFFFFu) out[i].push_back(candidate_songs[j]);
+        }
+    return out;
+}
+
 // song_to_song (src/playlist.rs:272-326)
 template <typename T>
 std::vector<T> song_to_song(const std::vector<T>& initial_songs, const std::vector<T>& candidate_songs, const MetricBuilder& mb) {

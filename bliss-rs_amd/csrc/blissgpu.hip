@@ -24,7 +24,7 @@ thread_local std::string g_last_error;
 const char* const kKernelNames[K_COUNT] = {
     "fft512_kernel",     "onset_kernel",      "beat_kernel",   "stft8192_kernel", "tune_select_kernel",
     "tune_pass2_kernel", "tune_final_kernel", "chroma_kernel",     "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel", "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel",
-    "dedup_next_kernel", "dedup_walk_kernel"};
+    "dedup_next_kernel", "dedup_walk_kernel", "knn_scan_kernel", "knn_merge_kernel"};
 }  // namespace
 
 namespace bg {
@@ -817,6 +817,110 @@ int blissgpu_dedup_playlist(const float* x, uint64_t n, uint32_t d, const uint32
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(dedup)", hipGetErrorString(e));
         if (!rc) *n_kept = nk;
+    }
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+// ---- k nearest candidates per query: closest_to_songs(&[query], candidates, metric) cut after k (src/playlist.rs:256-270), the
+// primitive behind Library::playlist_from(&[song]).take(k) (src/library.rs:762-850), for q queries in one call ----
+// everything that can be said about the arguments without a device (both forms check it BEFORE the device is touched)
+static int knn_args_ok(const char* who, const void* queries, uint64_t q, const void* cand, uint64_t n, uint32_t d, int metric,
+                       const float* M, uint32_t k, const void* idx) {
+    if (k == 0 || k > BLISSGPU_KNN_MAX_K) return fail(BLISSGPU_ERR_INVALID, who, "k must be 1 .. BLISSGPU_KNN_MAX_K");
+    if (d == 0 || d > 64) return fail(BLISSGPU_ERR_INVALID, who, "d must be 1 .. 64");
+    if (metric < 0 || metric > 2) return fail(BLISSGPU_ERR_INVALID, who, "unknown metric");
+    if (metric == BLISSGPU_METRIC_MAHALANOBIS && !M) return fail(BLISSGPU_ERR_INVALID, who, "mahalanobis needs M");
+    if (n >= 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "n must be below 2^32 - 1 candidates");
+    if (q > (1ull << 40)) return fail(BLISSGPU_ERR_INVALID, who, "q must be at most 2^40 queries");
+    if (q && !queries) return fail(BLISSGPU_ERR_INVALID, who, "queries is NULL");
+    if (q && n && !cand) return fail(BLISSGPU_ERR_INVALID, who, "cand is NULL");
+    if (q && !idx) return fail(BLISSGPU_ERR_INVALID, who, "idx is NULL");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_knn_device(blissgpu_ctx* c, const float* d_queries, uint64_t q, const float* d_cand, uint64_t n, uint32_t d,
+                        int metric, const float* d_M, const uint32_t* d_skip, uint32_t k, uint32_t* d_idx, float* d_dist) {
+    const char* who = "blissgpu_knn_device";
+    int rc = knn_args_ok(who, d_queries, q, d_cand, n, d, metric, d_M, k, d_idx);
+    if (rc) return rc;
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    if (q == 0) return BLISSGPU_OK;
+    CTX_ENTER(c, who);
+    int diag = 0;
+    if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
+        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
+            diag = is_diag(c->m_cache.data(), d);
+        } else {
+            std::vector<float> hM((size_t)d * d);
+            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            diag = is_diag(hM.data(), d);
+        }
+    }
+    // workspace: the sorted k best keys of every (query, split) -- O(q k), see knn_plan; no q x n tile exists anywhere
+    const KnnPlan plan = knn_plan(q, n, k, c->n_cus);
+    rc = c->pl_sync.ensure(4);
+    if (!rc) rc = c->pl_tmp.ensure((size_t)plan.part_keys * sizeof(unsigned long long));
+    if (rc) return rc;
+    unsigned long long* part = reinterpret_cast<unsigned long long*>(c->pl_tmp.p);
+    // pl_sync: [1] NaN among the evaluated distances, [3] a skip entry >= n
+    HIP_TRY(hipMemsetAsync(c->pl_sync.p, 0, 4 * sizeof(uint32_t), c->stream));
+    {
+        Prof p(c, K_KNN_SCAN);
+        launch_knn_scan(d_queries, q, d_cand, (uint32_t)n, d, metric, d_M, diag, d_skip, k, plan, part, c->pl_sync.p + 1,
+                        c->pl_sync.p + 3, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    {
+        Prof p(c, K_KNN_MERGE);
+        launch_knn_merge(part, q, k, plan, d_idx, d_dist, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    uint32_t flags[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(flags, c->pl_sync.p, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (flags[3]) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
+    if (flags[1]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance (the reference panics here)");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_knn(const float* queries, uint64_t q, const float* cand, uint64_t n, uint32_t d, int metric, const float* M,
+                 const uint32_t* skip, uint32_t k, uint32_t* idx, float* dist) {
+    const char* who = "blissgpu_knn";
+    int rc = knn_args_ok(who, queries, q, cand, n, d, metric, M, k, idx);
+    if (rc) return rc;
+    if (skip)
+        for (uint64_t i = 0; i < q; i++)
+            if (skip[i] != 0xFFFFFFFFu && skip[i] >= n) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
+    if (q == 0) return BLISSGPU_OK;
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    // queries that ARE the candidate matrix (the similar-songs table of a library) travel once
+    const bool shared = queries == cand && q <= n;
+    const size_t out_n = (size_t)q * k;
+    const float* dM = nullptr;
+    rc = c->st_b.ensure(std::max<size_t>(1, n * d));
+    if (!rc && !shared) rc = c->st_a.ensure(q * d);
+    if (!rc) rc = c->st_idx.ensure(out_n + (skip ? q : 0));
+    if (!rc && dist) rc = c->st_dist.ensure(out_n);
+    if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
+    if (rc) return rc;
+    const float* dQ = shared ? c->st_b.p : c->st_a.p;
+    uint32_t *d_idx = c->st_idx.p, *d_skip = skip ? c->st_idx.p + out_n : nullptr;
+    hipError_t e = hipSuccess;
+    if (n) e = hipMemcpyAsync(c->st_b.p, cand, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && !shared) e = hipMemcpyAsync(c->st_a.p, queries, q * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && skip) e = hipMemcpyAsync(d_skip, skip, q * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(knn)", hipGetErrorString(e));
+    if (!rc) rc = blissgpu_knn_device(c, dQ, q, c->st_b.p, n, d, metric, dM, d_skip, k, d_idx, dist ? c->st_dist.p : nullptr);
+    if (!rc) {
+        e = hipMemcpyAsync(idx, d_idx, out_n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(knn)", hipGetErrorString(e));
     }
     (void)hipStreamSynchronize(c->stream);
     return rc;

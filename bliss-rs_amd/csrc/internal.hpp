@@ -113,6 +113,7 @@ enum KernelId : int {
     K_SYNTH,
     K_ROLLFIX,
     K_DEDUP_NEXT, K_DEDUP_WALK,  // playlist deduplication: never launched by the analysis path
+    K_KNN_SCAN, K_KNN_MERGE,     // k-nearest search (kernels_knn.hip)
     K_COUNT
 };
 
@@ -220,6 +221,22 @@ void launch_dedup_next(const float* x, uint64_t n, uint32_t d, const uint32_t* s
 void launch_dedup_walk(const float* x, uint64_t n, uint32_t d, const uint32_t* seq, uint32_t len, const uint32_t* meta,
                        int metric, const float* M, float thr, const uint32_t* next, uint32_t* kept, uint64_t* n_kept,
                        uint32_t* nan_flag, uint32_t* bad, hipStream_t st);
+// k nearest candidates per query (kernels_knn.hip): the split of the work for (q, n, k), then the two launches.  `part` holds
+// part_keys 64-bit keys; a NaN among the evaluated distances sets *nan_flag, a skip entry >= n (other than 0xFFFFFFFF) *bad_flag
+struct KnnPlan {
+    uint32_t cap;               // keys of a query's threshold buffer: a power of two, >= k + 64
+    uint32_t qb;                // queries per workgroup
+    uint32_t n_split;           // workgroups that share a query's candidates
+    uint32_t blocks_per_split;  // 256-candidate blocks each of them walks
+    uint32_t grid_qb;           // query blocks in the grid (the kernel strides over the rest)
+    uint64_t part_keys;         // q * n_split * k
+};
+KnnPlan knn_plan(uint64_t q, uint64_t n, uint32_t k, int n_cus);
+void launch_knn_scan(const float* Q, uint64_t q, const float* X, uint32_t n, uint32_t d, int metric, const float* M,
+                     int m_is_diag, const uint32_t* skip, uint32_t k, const KnnPlan& p, unsigned long long* part,
+                     uint32_t* nan_flag, uint32_t* bad_flag, hipStream_t st);
+void launch_knn_merge(const unsigned long long* part, uint64_t q, uint32_t k, const KnnPlan& p, uint32_t* idx, float* dist,
+                      hipStream_t st);
 void launch_pairwise(const float* A, uint64_t n, const float* B, uint64_t m, uint32_t d, int metric, const float* M,
                      int m_is_diag, float* out, uint64_t ld_out, hipStream_t);
 void launch_synth(float* pcm, const SongDesc* songs, uint32_t n_songs, const uint32_t* pfx_e, uint32_t tiles_e,

@@ -24,6 +24,7 @@
 
 #include "device_utils.hpp"
 #include "internal.hpp"
+#include "pairwise_math.hpp"
 
 // store flavours of the two halves of a self-distance block (1 = non-temporal, the shipped form; 0 = plain: measured in
 // profiles/r06_pairwise_staging_ab.txt)
@@ -41,19 +42,6 @@ constexpr int PW_ROWS = 128, PW_COLS = 256, PW_CPT = 4;  // tile rows, tile cols
 #ifndef PW_RT
 #define PW_RT 8   // 128-row tiles a workgroup walks with its 256 columns in registers (even: the self-distance kernel works in 256 x 256 blocks)
 #endif
-enum { METRIC_EUCLIDEAN = 0, METRIC_COSINE = 1, METRIC_MAHALANOBIS = 2 };
-
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-// compile-time loop: f(std::integral_constant<int, 0>{}), ..., f(std::integral_constant<int, N-1>{})
-template <int N, typename F, int I = 0>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<N, F, I + 1>(static_cast<F&&>(f));
-    }
-}
-__device__ __forceinline__ f2 splat(float x) { f2 r; r.x = x; r.y = x; return r; }
 // an index every lane of the wavefront computed alike, moved to scalar registers: with a 32-bit lane offset on top the store
 // takes the `saddr + voffset` form and no lane keeps a 64-bit address (two VGPRs each) across the arithmetic
 __device__ __forceinline__ uint64_t wave_uniform(uint64_t v) {
@@ -87,59 +75,6 @@ __device__ __forceinline__ f2 sqrt_rn2(f2 x) {
     return r;
 }
 
-// (a, a) - b and (a, a) * b where a is the LO (HI = false) or HI half of a register pair: the broadcast
-// is an op_sel modifier of the packed instruction instead of two v_mov per element
-template <bool HI>
-__device__ __forceinline__ f2 bsub(f2 apair, f2 b) {
-    f2 r;
-    if (HI) asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(apair), "v"(b));
-    else asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(apair), "v"(b));
-    return r;
-}
-template <bool HI>
-__device__ __forceinline__ f2 bmul(f2 apair, f2 b) {
-    f2 r;
-    if (HI) asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(r) : "v"(apair), "v"(b));
-    else asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1]" : "=v"(r) : "v"(apair), "v"(b));
-    return r;
-}
-
-// ndarray::numeric_util::unrolled_dot over compile-time length D, evaluated for TWO pairs at once in packed
-// f32 (v_pk_mul_f32 / v_pk_add_f32: each half rounds exactly like the scalar op; this translation unit is
-// compiled with -ffp-contract=off so the multiply and the add stay separate, as in the reference).
-template <int D, typename FX, typename FY>
-__device__ __forceinline__ f2 unrolled_dot2(FX xs, FY ys) {
-    f2 p[8];
-#pragma unroll
-    for (int u = 0; u < 8; u++) p[u] = splat(0.0f);
-    constexpr int BODY = (D / 8) * 8;
-#pragma unroll
-    for (int k = 0; k < BODY; k++) p[k & 7] = p[k & 7] + xs(k) * ys(k);
-    f2 sum = splat(0.0f);
-    sum = sum + (p[0] + p[4]);
-    sum = sum + (p[1] + p[5]);
-    sum = sum + (p[2] + p[6]);
-    sum = sum + (p[3] + p[7]);
-#pragma unroll
-    for (int k = BODY; k < D; k++) sum = sum + xs(k) * ys(k);
-    return sum;
-}
-
-template <int D, typename FX, typename FY>
-__device__ __forceinline__ float unrolled_dot(FX xs, FY ys) {
-    float p[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    constexpr int BODY = (D / 8) * 8;
-#pragma unroll
-    for (int k = 0; k < BODY; k++) p[k & 7] = p[k & 7] + xs(k) * ys(k);
-    float sum = 0.0f;
-    sum = sum + (p[0] + p[4]);
-    sum = sum + (p[1] + p[5]);
-    sum = sum + (p[2] + p[6]);
-    sum = sum + (p[3] + p[7]);
-#pragma unroll
-    for (int k = BODY; k < D; k++) sum = sum + xs(k) * ys(k);
-    return sum;
-}
 
 // SYM: A and B are the same matrix.  Every metric here is symmetric bit for bit (negating a - b leaves its squares, the
 // quadratic form and the dot products unchanged, and both norm tables come from the same rows), so only the 256 x 256
@@ -247,50 +182,7 @@ __global__ __launch_bounds__(256, (METRIC == METRIC_EUCLIDEAN ? 3 : 2)) void pai
     };
     // the reference's sum for the two columns of pair h (before the square root / the cosine's division)
     auto row_sum = [&](const f2 (&ap)[DP / 2], auto hc) __attribute__((always_inline)) -> f2 {
-        constexpr int h = decltype(hc)::value;
-        // term k of the unrolled_dot for the two columns of pair h
-        auto term = [&](auto kc) __attribute__((always_inline)) -> f2 {
-            constexpr int k = decltype(kc)::value;
-            constexpr bool HI = (k & 1) != 0;
-            if (METRIC == METRIC_COSINE) return bmul<HI>(ap[k / 2], bp[h][k]);
-            const f2 v = bsub<HI>(ap[k / 2], bp[h][k]);
-            if (METRIC == METRIC_EUCLIDEAN) return v * v;
-            if (DIAG) return (v * splat(wdiag[k])) * v;
-            return v;  // (general M: the difference itself)
-        };
-        if (METRIC == METRIC_MAHALANOBIS && !DIAG) {
-            f2 v[D], t[D];
-            static_for<D>([&](auto kc) { v[decltype(kc)::value] = term(kc); });
-#pragma unroll 1
-            for (int jj = 0; jj < D; jj++) {
-                f2 acc = splat(0.0f);
-#pragma unroll
-                for (int ii = 0; ii < D; ii++) acc = acc + v[ii] * splat(sm[ii * D + jj]);
-                t[jj] = acc;
-            }
-            return unrolled_dot2<D>([&](int k) { return t[k]; }, [&](int k) { return v[k]; });
-        }
-        f2 p[8];
-        constexpr int BODY = (D / 8) * 8;
-        f2 sum;
-        if (METRIC == METRIC_EUCLIDEAN && BODY >= 8) {
-            // every term is a square (>= +0), so the reference's `0.0 + term` and `0.0 + (p0 + p4)` are exact
-            // identities: start the eight partial sums at their first term (10 of 78 packed instructions less)
-            static_for<8>([&](auto kc) { p[decltype(kc)::value] = term(kc); });
-            static_for<BODY - 8>([&](auto kc) { constexpr int k = 8 + decltype(kc)::value; p[k & 7] = p[k & 7] + term(std::integral_constant<int, k>{}); });
-            sum = p[0] + p[4];
-        } else {
-#pragma unroll
-            for (int u = 0; u < 8; u++) p[u] = splat(0.0f);
-            static_for<BODY>([&](auto kc) { constexpr int k = decltype(kc)::value; p[k & 7] = p[k & 7] + term(kc); });
-            sum = splat(0.0f);
-            sum = sum + (p[0] + p[4]);
-        }
-        sum = sum + (p[1] + p[5]);
-        sum = sum + (p[2] + p[6]);
-        sum = sum + (p[3] + p[7]);
-        static_for<D - BODY>([&](auto kc) { sum = sum + term(std::integral_constant<int, BODY + decltype(kc)::value>{}); });
-        return sum;
+        return pair_sum<D, METRIC, DIAG>(ap, bp[decltype(hc)::value], wdiag, sm);
     };
     // sum -> distance, the branch-free part (exact unless one of the four sums is a tiny positive number: fix_row)
     auto finish_fast = [&](f2 sum, int h, int r) __attribute__((always_inline)) -> f2 {

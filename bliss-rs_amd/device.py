@@ -333,6 +333,33 @@ class Context:
         self._post()
         return kept[:length], n_kept
 
+    def knn(self, Q, X, k: int, metric: str = "euclidean", M=None, skip=None):
+        """The k nearest rows of X for every row of Q without the distance matrix: row i = closest_to_songs(&[Q[i]], X without
+        row skip[i], metric) cut after k (src/playlist.rs:256-270, src/library.rs:762-850).  -> (idx int32 [q, k], dist float32
+        [q, k]) on the device; equal distances in candidate order; rows with fewer than k eligible candidates end in -1 (the
+        library's 0xFFFFFFFF) / inf.  skip: int32 tensor of q candidate indices, -1 = none, or None.  Raises
+        BlissGpuError(ERR_NAN) for a NaN among the evaluated distances (synchronises for that check)."""
+        from .playlist import _METRICS
+
+        torch = self.torch
+        assert Q.is_cuda and X.is_cuda and Q.dtype == torch.float32 and X.dtype == torch.float32
+        assert Q.dim() == 2 and X.dim() == 2 and Q.shape[1] == X.shape[1]
+        Q, X = Q.contiguous(), X.contiguous()
+        q, n, k = Q.shape[0], X.shape[0], int(k)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        if skip is not None:
+            assert skip.is_cuda and skip.dtype == torch.int32 and skip.shape[0] == q
+            skip = skip.contiguous()
+        if M is not None:
+            M = M.contiguous()
+        idx = torch.empty((q, max(k, 0)), dtype=torch.int32, device=X.device)
+        dist = torch.empty((q, max(k, 0)), dtype=torch.float32, device=X.device)
+        self._pre()
+        _ffi.check(self._L.blissgpu_knn_device(self._h, ptr(Q), q, ptr(X), n, Q.shape[1], _METRICS[metric], ptr(M), ptr(skip), k,
+                                               ptr(idx), ptr(dist)))
+        self._post()
+        return idx, dist
+
     # ---- profiling ----
     def profile_enable(self, on: bool = True):
         _ffi.check(self._L.blissgpu_profile_enable(self._h, int(on)))

@@ -23,6 +23,8 @@ database:
     playlist_from, playlist_from_custom   seeds first, seeds removed from the pool by path, the order and ONE
                                           deduplication of the whole chain on the device (playlist.dedup_order)
     album_playlist_from                   closest_album_to_group, cropped after `number_albums` album changes
+    similar_songs                         the k closest songs of every song (or of some), one device call
+                                          (playlist.nearest_order): playlist_from(&[song]).take(k) for the whole library
 
 SQLite stores `real` as f64; an f32 feature widens exactly on the way in and narrows exactly on the way out, so a
 round trip is bit-exact.  The schema, load and store helpers are host code; the playlists run their distances on the
@@ -334,6 +336,30 @@ def playlist_from_custom(db: Conn, initial_song_paths: Sequence[str], metric_bui
     kept = (playlist.dedup_order(X, seq, playlist.meta_keys(rows), metric, m) if deduplicate
             else np.arange(seq.shape[0]))
     return [initial[k] if k < len(initial) else rows[int(seq[k])] for k in kept]
+
+
+def similar_songs(db: Conn, k: int, metric_builder=playlist.euclidean_distance, song_paths: Sequence[str] = None):
+    """The "similar songs" table of a library: {path: [(path, distance), ...]} with the k songs closest to each song --
+    `Library::playlist_from(&[path])?.take(k)` (src/library.rs:762-850, examples/library.rs:194-198) without the seed itself
+    and without the deduplication, for every analysed song of FeaturesVersion.LATEST (`song_paths` = None) or for those
+    paths only; an unknown path is the ProviderError playlist_from_custom raises.  The matrix is read once and ONE device
+    call (playlist.nearest_order, each song skipping its own row) answers every song: no distance matrix is built."""
+    _, paths, X = load_feature_matrix(db, FeaturesVersion.LATEST)
+    metric, m = playlist._metric_of(metric_builder)
+    if song_paths is None:
+        rows, Q = np.arange(len(paths), dtype=np.int64), X
+    else:
+        row_of = {p: i for i, p in enumerate(paths)}
+        for p in song_paths:
+            if p not in row_of:
+                raise ProviderError(f"song '{p}' has not been analyzed")
+        rows = np.asarray([row_of[p] for p in song_paths], np.int64)
+        Q = X[rows]
+    if rows.size == 0:
+        return {}
+    idx, dist = playlist.nearest_order(Q, X, k, metric, m, skip=rows)
+    return {paths[int(r)]: [(paths[int(j)], float(v)) for j, v in zip(idx[i], dist[i]) if j >= 0]
+            for i, r in enumerate(rows)}
 
 
 def album_playlist_from(db: Conn, album_title: str, number_albums: int) -> List[Song]:

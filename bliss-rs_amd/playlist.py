@@ -4,6 +4,7 @@
     DistanceMetricBuilder / FunctionDistanceMetric               :24-59
     variance_based_weight_matrix                                 :173-221
     closest_to_songs, song_to_song                               :256-326
+    nearest_order, nearest_songs (closest_to_songs cut after k, for many seeds at once)
     dedup_playlist, dedup_playlist_custom_distance               :343-402
     closest_album_to_group                                       :424-485
 
@@ -200,6 +201,69 @@ def song_to_song(initial_songs, candidate_songs, metric_builder=euclidean_distan
     metric, m = _metric_of(metric_builder)
     order = song_to_song_order(_matrix(initial_songs), _matrix(candidate_songs), metric, m)
     return [candidate_songs[i] for i in order]
+
+
+def nearest_order(queries, candidates, k, metric="euclidean", m=None, skip=None):
+    """The k nearest candidates of every query in one device call, without the distance matrix: row i of the result is
+    closest_to_songs(&[queries[i]], candidates without skip[i], metric) (src/playlist.rs:256-270) cut after k -- what
+    Library::playlist_from(&[song]).take(k) asks per song (src/library.rs:762-850).  -> (idx int64[q, k], dist
+    float32[q, k]); equal distances come in candidate order; rows with fewer than k eligible candidates end in -1 / inf.
+    `skip`: None, or one candidate index per query that is left out of that query's list (-1: none).  Passing the same
+    array object as queries and candidates uploads it once.  A NaN distance raises ValueError (the reference's n32()
+    panic)."""
+    X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
+    Q = X if queries is candidates else np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+    if Q.ndim != 2 or X.ndim != 2 or Q.shape[1] != X.shape[1]:
+        raise ValueError("queries and candidates must be [q, d] and [n, d]")
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be at least 1")
+    q, d = Q.shape
+    n = X.shape[0]
+    skip_p = None
+    if skip is not None:
+        skip = np.asarray(skip, dtype=np.int64).reshape(-1)
+        if skip.shape[0] != q:
+            raise ValueError("skip needs one entry per query")
+        if ((skip < -1) | (skip >= max(n, 0))).any():
+            raise ValueError("skip entries must be candidate indices or -1")
+        skip = np.where(skip < 0, 0xFFFFFFFF, skip).astype(np.uint32)
+        skip_p = skip.ctypes.data
+    mp = None
+    if m is not None:
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        mp = m.ctypes.data
+    idx, dist = np.empty((q, k), np.uint32), np.empty((q, k), np.float32)
+    try:
+        _ffi.check(_ffi.lib().blissgpu_knn(Q.ctypes.data, q, X.ctypes.data, n, d, _METRICS[metric], mp, skip_p, k,
+                                           idx.ctypes.data, dist.ctypes.data))
+    except _ffi.BlissGpuError as e:
+        _nan_to_panic(e)
+    out = idx.astype(np.int64)
+    out[idx == 0xFFFFFFFF] = -1
+    return out, dist
+
+
+def nearest_songs(songs, candidate_songs, k, metric_builder=euclidean_distance, exclude_self=False):
+    """For every song of `songs`, closest_to_songs(&[song], candidate_songs, metric_builder)[..k] (src/playlist.rs:256-270)
+    -- all of them in one device call.  `exclude_self`: the first candidate that == the song (Song: PartialEq, as
+    closest_album_to_group removes the group from its pool) is left out of that song's list."""
+    songs, candidate_songs = list(songs), list(candidate_songs)
+    if not songs:
+        return []
+    if not candidate_songs:
+        return [[] for _ in songs]
+    metric, m = _metric_of(metric_builder)
+    skip = None
+    if exclude_self:
+        skip = np.full(len(songs), -1, np.int64)
+        for i, s in enumerate(songs):
+            for j, c in enumerate(candidate_songs):
+                if _song_of(c) == _song_of(s):
+                    skip[i] = j
+                    break
+    idx, _ = nearest_order(_matrix(songs), _matrix(candidate_songs), k, metric, m, skip)
+    return [[candidate_songs[j] for j in row if j >= 0] for row in idx]
 
 
 def meta_keys(songs) -> np.ndarray:

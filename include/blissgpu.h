@@ -300,6 +300,27 @@ int blissgpu_dedup_playlist_device(blissgpu_ctx *ctx, const float *d_x, uint64_t
                                    uint64_t len, const uint32_t *d_meta, int metric, const float *d_M, float threshold,
                                    uint32_t *d_kept, uint64_t *d_n_kept);
 
+/* ---- k nearest candidates of every query (src/playlist.rs:256-270, src/library.rs:762-850) ----
+ * For query i: the first k entries of closest_to_songs(&[queries[i]], candidates without skip[i], metric), i.e. of the STABLE
+ * ascending sort of metric(queries[i], cand[j]) over j != skip[i] -- what Library::playlist_from(&[song]).take(k) asks, for
+ * q songs in one call.  idx and dist are q x k row-major; dist may be NULL.  Equal distances come in candidate order (-0.0
+ * and +0.0 are equal); every distance is bit for bit what blissgpu_pairwise_device writes for the same pair.
+ * skip (may be NULL) holds one candidate index per query that is left out of that query's result and not evaluated (how a song
+ * is kept out of its own list when the queries are rows of the candidate matrix); 0xFFFFFFFF skips nothing, any other value
+ * >= n is BLISSGPU_ERR_INVALID.  Rows with fewer than k eligible candidates end in idx 0xFFFFFFFF / dist +inf.  A NaN among the
+ * evaluated distances returns BLISSGPU_ERR_NAN (the reference's n32() panic); the outputs are then unspecified.
+ * 1 <= k <= BLISSGPU_KNN_MAX_K, 1 <= d <= 64, n < 2^32 - 1; q == 0 or n == 0 is BLISSGPU_OK.  Arguments are checked before the
+ * device is touched.  No q x n matrix is ever stored: the workspace is O(q k), two launches whatever q and n.
+ * queries == cand (the same pointer, q <= n) uploads the matrix once. */
+#define BLISSGPU_KNN_MAX_K 1024u
+int blissgpu_knn(const float *queries, uint64_t q, const float *cand, uint64_t n, uint32_t d, int metric, const float *M,
+                 const uint32_t *skip, uint32_t k, uint32_t *idx, float *dist);
+/* Device-resident form (device pointers, d_skip included; d_dist may be NULL); asynchronous except for the NaN / skip check,
+ * which synchronises the context's stream before returning. */
+int blissgpu_knn_device(blissgpu_ctx *ctx, const float *d_queries, uint64_t q, const float *d_cand, uint64_t n,
+                        uint32_t d, int metric, const float *d_M, const uint32_t *d_skip, uint32_t k,
+                        uint32_t *d_idx, float *d_dist);
+
 /* FeaturesVersion::feature_weights (src/lib.rs:168-173, 209-234): d x d row-major diagonal matrix. */
 int blissgpu_feature_weights(uint32_t features_version, float *M);
 
