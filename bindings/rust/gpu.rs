@@ -25,6 +25,7 @@
 //!                                             src/playlist.rs:343-402     -> [`dedup_on_device`]
 //!   * `closest_to_songs(&[song], ..)` cut after k, many songs per call (`Library::playlist_from(..).take(k)`)
 //!                                             src/playlist.rs:256-270     -> [`nearest_on_device`]
+//!   * `closest_to_songs(.., &ForestOptions)`  src/playlist.rs:230-270     -> [`forest_order_on_device`]
 //!
 //! build.rs of the crate, under the feature:
 //! ```ignore
@@ -146,6 +147,22 @@ pub mod sys {
         pub fn blissgpu_knn_device(ctx: *mut blissgpu_ctx, d_queries: *const f32, q: u64, d_cand: *const f32, n: u64, d: u32,
                                    metric: c_int, d_m: *const f32, d_skip: *const u32, k: u32, d_idx: *mut u32,
                                    d_dist: *mut f32) -> c_int;
+
+        // ---- extended isolation forest (ForestOptions, src/playlist.rs:230-251) ----
+        pub fn blissgpu_forest_build(seeds: *const f32, n_seeds: u64, d: u32, n_trees: u32, sample_size: u32, max_tree_depth: u32,
+                                     extension_level: u32, seed: u64, forest: *mut *mut c_void) -> c_int;
+        pub fn blissgpu_forest_destroy(forest: *mut c_void) -> c_int;
+        pub fn blissgpu_forest_info(forest: *const c_void, d: *mut u32, n_trees: *mut u32, psi: *mut u32, depth_limit: *mut u32,
+                                    extension_level: *mut u32, n_nodes: *mut u64) -> c_int;
+        pub fn blissgpu_forest_export(forest: *const c_void, sample_idx: *mut u32, tree_first: *mut u64, normal: *mut f32,
+                                      b: *mut f32, left: *mut u32, right: *mut u32, leaf_size: *mut u32, leaf_q: *mut u32) -> c_int;
+        pub fn blissgpu_forest_score(forest: *mut c_void, cand: *const f32, n: u64, score: *mut f32, path_sum: *mut u64) -> c_int;
+        pub fn blissgpu_forest_closest_to_songs(forest: *mut c_void, cand: *const f32, n: u64, order: *mut u32,
+                                                score: *mut f32) -> c_int;
+        pub fn blissgpu_forest_score_device(ctx: *mut blissgpu_ctx, forest: *mut c_void, d_cand: *const f32, n: u64,
+                                            d_score: *mut f32, d_path_sum: *mut u64) -> c_int;
+        pub fn blissgpu_forest_closest_to_songs_device(ctx: *mut blissgpu_ctx, forest: *mut c_void, d_cand: *const f32, n: u64,
+                                                       d_order: *mut u32, d_score: *mut f32) -> c_int;
 
         // ---- one process, every GPU of the node ----
         pub fn blissgpu_node_create(n_devices: c_int, devices: *const c_int, node: *mut *mut blissgpu_node) -> c_int;
@@ -413,6 +430,45 @@ pub fn nearest_on_device<T: AsRef<Song> + Clone>(songs: &[T], candidates: &[T], 
         return Err(gpu_err(rc));
     }
     Ok(idx.chunks(k).map(|row| row.iter().filter(|&&j| j != u32::MAX).map(|&j| candidates[j as usize].clone()).collect()).collect())
+}
+
+/// `ForestOptions` of the CPU crate (src/playlist.rs:230-251) plus the 64-bit seed that makes the forest reproducible:
+/// the same (seed songs, options, seed) give the same forest and therefore the same playlist.
+#[derive(Clone, Copy, Debug)]
+pub struct ForestOptions {
+    pub n_trees: usize,
+    pub sample_size: usize,
+    pub max_tree_depth: Option<usize>,
+    pub extension_level: usize,
+    pub seed: u64,
+}
+
+/// `closest_to_songs(initial, candidates, &ForestOptions)` (src/playlist.rs:256-270 with the metric of :230-251): the forest is
+/// built on the host from the initial songs (at least two: the forest does not work for a single song), every candidate is
+/// scored on the device and the stable order of the scores comes back.  Scores are always finite: no `BLISSGPU_ERR_NAN` here.
+pub fn forest_order_on_device<T: AsRef<Song> + Clone>(initial: &[T], candidates: &[T], options: &ForestOptions) -> BlissResult<Vec<T>> {
+    if candidates.is_empty() {
+        return Ok(Vec::new());
+    }
+    let d = candidates[0].as_ref().analysis.as_vec().len();
+    let flat = |songs: &[T]| songs.iter().flat_map(|s| s.as_ref().analysis.as_vec()).collect::<Vec<f32>>();
+    let (seeds, cand) = (flat(initial), flat(candidates));
+    let mut forest: *mut c_void = std::ptr::null_mut();
+    let rc = unsafe {
+        sys::blissgpu_forest_build(seeds.as_ptr(), initial.len() as u64, d as u32, options.n_trees as u32, options.sample_size.min(u32::MAX as usize) as u32,
+                                   options.max_tree_depth.map_or(0, |k| k.max(1).min(u32::MAX as usize) as u32), options.extension_level as u32,
+                                   options.seed, &mut forest)
+    };
+    if rc != sys::BLISSGPU_OK {
+        return Err(gpu_err(rc));
+    }
+    let mut order = vec![0u32; candidates.len()];
+    let rc = unsafe { sys::blissgpu_forest_closest_to_songs(forest, cand.as_ptr(), candidates.len() as u64, order.as_mut_ptr(), std::ptr::null_mut()) };
+    unsafe { sys::blissgpu_forest_destroy(forest) };
+    if rc != sys::BLISSGPU_OK {
+        return Err(gpu_err(rc));
+    }
+    Ok(order.into_iter().map(|i| candidates[i as usize].clone()).collect())
 }
 
 /// One process driving every GPU of the node: songs sharded by sample count, one `ncclAllGather` of the feature rows over

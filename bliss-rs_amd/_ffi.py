@@ -20,6 +20,7 @@ OPT_SERIAL, OPT_TAIL_MODE, OPT_PIPELINE_CHUNKS, OPT_CAND_BUDGET, OPT_ROLLOFF_EXA
 OPT_STFT_SHAPE = 7
 OPT_FLUX_ORDER = 8
 OPT_STAGE_LANES, OPT_STAGE_SLAB_KIB, OPT_STAGE_SLABS, OPT_STAGE_NUMA = 9, 10, 11, 12
+OPT_FOREST_SPLIT, OPT_FOREST_WALK = 13, 14
 
 _f32p = C.POINTER(C.c_float)
 _f64p = C.POINTER(C.c_double)
@@ -86,6 +87,15 @@ SIGNATURES = {
     "blissgpu_knn": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, C.c_uint32, _vp, _vp]),
     "blissgpu_knn_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, C.c_uint32, _vp,
                                       _vp]),
+    "blissgpu_forest_build": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                        C.POINTER(_vp)]),
+    "blissgpu_forest_destroy": (C.c_int, [_vp]),
+    "blissgpu_forest_info": (C.c_int, [_vp, _u32p, _u32p, _u32p, _u32p, _u32p, _u64p]),
+    "blissgpu_forest_export": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "blissgpu_forest_score": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp]),
+    "blissgpu_forest_closest_to_songs": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp]),
+    "blissgpu_forest_score_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp]),
+    "blissgpu_forest_closest_to_songs_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp]),
     "blissgpu_set_distance_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp]),
     "blissgpu_closest_to_songs_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp,
                                                    _vp]),

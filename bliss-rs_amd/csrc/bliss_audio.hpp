@@ -440,6 +440,37 @@ std::vector<T> closest_to_songs(const std::vector<T>& initial_songs, const std::
     return out;
 }
 
+// extended_isolation_forest::ForestOptions as a metric builder (src/playlist.rs:230-251) plus the seed that makes the
+// forest -- and so the playlist -- reproducible.  max_tree_depth 0 = None (ceil(log2(min(sample_size, seeds)))).
+struct ForestOptions {
+    uint32_t n_trees;
+    uint32_t sample_size;
+    uint32_t max_tree_depth;
+    uint32_t extension_level;
+    uint64_t seed;
+};
+
+// closest_to_songs with the forest metric (src/playlist.rs:256-270): the forest is built on the host from the initial
+// songs (at least two, or std::invalid_argument from check()), the candidates are scored and ordered on the GPU.
+template <typename T>
+std::vector<T> closest_to_songs(const std::vector<T>& initial_songs, const std::vector<T>& candidate_songs, const ForestOptions& opts) {
+    if (candidate_songs.empty()) return {};
+    size_t d = 0, ds = 0;
+    const auto x = feature_matrix(candidate_songs, d);
+    const auto s = feature_matrix(initial_songs, ds);
+    if (!initial_songs.empty() && ds != d) throw std::logic_error("Mismatched features version between two songs or analysis");
+    void* forest = nullptr;
+    check(blissgpu_forest_build(s.data(), initial_songs.size(), (uint32_t)d, opts.n_trees, opts.sample_size, opts.max_tree_depth,
+                                opts.extension_level, opts.seed, &forest));
+    std::vector<uint32_t> order(candidate_songs.size());
+    const int rc = blissgpu_forest_closest_to_songs(forest, x.data(), candidate_songs.size(), order.data(), nullptr);
+    blissgpu_forest_destroy(forest);
+    check(rc);
+    std::vector<T> out;
+    for (uint32_t i : order) out.push_back(candidate_songs[i]);
+    return out;
+}
+
 // closest_to_songs for many single seeds at once, cut after k (src/playlist.rs:256-270; Library::playlist_from(&[song])
 // .take(k), src/library.rs:762-850): row i of idx = the k candidates closest to queries[i] in ascending distance, equal
 // distances in candidate order, without candidate skip[i] (0xFFFFFFFF: none); short rows end in 0xFFFFFFFF / +inf.

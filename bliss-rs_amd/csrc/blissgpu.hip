@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "forest.hpp"
 
 using namespace bg;
 
@@ -24,7 +25,8 @@ thread_local std::string g_last_error;
 const char* const kKernelNames[K_COUNT] = {
     "fft512_kernel",     "onset_kernel",      "beat_kernel",   "stft8192_kernel", "tune_select_kernel",
     "tune_pass2_kernel", "tune_final_kernel", "chroma_kernel",     "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel", "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel",
-    "dedup_next_kernel", "dedup_walk_kernel", "knn_scan_kernel", "knn_merge_kernel"};
+    "dedup_next_kernel", "dedup_walk_kernel", "knn_scan_kernel", "knn_merge_kernel",
+    "forest_walk_kernel", "forest_finish_kernel"};
 }  // namespace
 
 namespace bg {
@@ -387,6 +389,8 @@ int blissgpu_ctx_set_option(blissgpu_ctx* c, int option, int64_t value) {
         case BLISSGPU_OPT_STAGE_SLAB_KIB: c->feed.stage_cfg.slab_bytes = (size_t)std::max<int64_t>(64, std::min<int64_t>(value, 65536)) << 10; break;
         case BLISSGPU_OPT_STAGE_NUMA: c->feed.stage_numa = value != 0; break;
         case BLISSGPU_OPT_STAGE_SLABS: c->feed.stage_cfg.slabs_per_lane = (int)std::max<int64_t>(1, std::min<int64_t>(value, 8)); break;
+        case BLISSGPU_OPT_FOREST_SPLIT: c->forest_split = std::max<int64_t>(0, std::min<int64_t>(value, 65535)); break;
+        case BLISSGPU_OPT_FOREST_WALK: c->forest_global = value == 1; break;
         case BLISSGPU_OPT_CAND_BUDGET: c->cand_budget = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 714)); break;
         default: return fail(BLISSGPU_ERR_INVALID, "blissgpu_ctx_set_option", "unknown option");
     }
@@ -924,6 +928,150 @@ int blissgpu_knn(const float* queries, uint64_t q, const float* cand, uint64_t n
     }
     (void)hipStreamSynchronize(c->stream);
     return rc;
+}
+
+// ---- extended isolation forest (ForestOptions, src/playlist.rs:230-251): build / info / export are host-only ----
+int blissgpu_forest_build(const float* seeds, uint64_t n_seeds, uint32_t d, uint32_t n_trees, uint32_t sample_size,
+                          uint32_t max_tree_depth, uint32_t extension_level, uint64_t seed, void** forest) {
+    if (!forest) return fail(BLISSGPU_ERR_INVALID, "blissgpu_forest_build", "NULL argument");
+    *forest = nullptr;
+    Forest* f = nullptr;
+    int rc = forest_build(seeds, n_seeds, d, n_trees, sample_size, max_tree_depth, extension_level, seed, &f);
+    if (!rc) *forest = f;
+    return rc;
+}
+
+int blissgpu_forest_destroy(void* forest) {
+    forest_destroy(static_cast<Forest*>(forest));
+    return BLISSGPU_OK;
+}
+
+int blissgpu_forest_info(const void* forest, uint32_t* d, uint32_t* n_trees, uint32_t* psi, uint32_t* depth_limit,
+                         uint32_t* extension_level, uint64_t* n_nodes) {
+    if (!forest) return fail(BLISSGPU_ERR_INVALID, "blissgpu_forest_info", "forest is NULL");
+    const Forest* f = static_cast<const Forest*>(forest);
+    if (d) *d = f->d;
+    if (n_trees) *n_trees = f->n_trees;
+    if (psi) *psi = f->psi;
+    if (depth_limit) *depth_limit = f->limit;
+    if (extension_level) *extension_level = f->ext;
+    if (n_nodes) *n_nodes = f->right.size();
+    return BLISSGPU_OK;
+}
+
+int blissgpu_forest_export(const void* forest, uint32_t* sample_idx, uint64_t* tree_first, float* normal, float* b, uint32_t* left,
+                           uint32_t* right, uint32_t* leaf_size, uint32_t* leaf_q) {
+    if (!forest) return fail(BLISSGPU_ERR_INVALID, "blissgpu_forest_export", "forest is NULL");
+    forest_export(static_cast<const Forest*>(forest), sample_idx, tree_first, normal, b, left, right, leaf_size, leaf_q);
+    return BLISSGPU_OK;
+}
+
+// everything that can be said about a scoring call without a device
+static int forest_args_ok(const char* who, const void* forest, const void* cand, uint64_t n, const void* out) {
+    if (!forest) return fail(BLISSGPU_ERR_INVALID, who, "forest is NULL");
+    if (n > 0xFFFFFF00ull) return fail(BLISSGPU_ERR_INVALID, who, "more than 0xFFFFFF00 candidates");
+    if (n && (!cand || !out)) return fail(BLISSGPU_ERR_INVALID, who, "NULL argument");
+    return BLISSGPU_OK;
+}
+
+// walk + finish on the context's stream: d_sum (may be NULL: context scratch), d_score (may be NULL), keys / idx (both or none)
+static int forest_run(blissgpu_ctx* c, Forest* f, const float* d_cand, uint32_t n, float* d_score, uint64_t* d_sum, uint32_t* keys,
+                      uint32_t* idx, const char* who) {
+    const ForestImage* im = nullptr;
+    int rc = forest_device_image(f, c->device, c->stream, &im);
+    if (rc) return rc;
+    if (!d_sum) {
+        if ((rc = c->pl_slots.ensure(n))) return rc;
+        d_sum = reinterpret_cast<uint64_t*>(c->pl_slots.p);
+    }
+    unsigned long long* sum = reinterpret_cast<unsigned long long*>(d_sum);
+    const uint32_t split = forest_split_plan(f, n, c->n_cus, c->forest_split);
+    if (split > 1) HIP_TRY(hipMemsetAsync(sum, 0, (size_t)n * sizeof(unsigned long long), c->stream));
+    {
+        Prof p(c, K_FOREST_WALK);
+        HIP_TRY(launch_forest_walk(f, *im, d_cand, n, split, !c->forest_global, sum, c->stream));
+    }
+    {
+        Prof p(c, K_FOREST_FINISH);
+        launch_forest_finish(f, sum, n, d_score, keys, idx, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    return BLISSGPU_OK;
+}
+
+int blissgpu_forest_score_device(blissgpu_ctx* c, void* forest, const float* d_cand, uint64_t n, float* d_score,
+                                 uint64_t* d_path_sum) {
+    const char* who = "blissgpu_forest_score_device";
+    int rc = forest_args_ok(who, forest, d_cand, n, d_score);
+    if (rc) return rc;
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    if (n == 0) return BLISSGPU_OK;
+    CTX_ENTER(c, who);
+    return forest_run(c, static_cast<Forest*>(forest), d_cand, (uint32_t)n, d_score, d_path_sum, nullptr, nullptr, who);
+}
+
+int blissgpu_forest_closest_to_songs_device(blissgpu_ctx* c, void* forest, const float* d_cand, uint64_t n, uint32_t* d_order,
+                                            float* d_score) {
+    const char* who = "blissgpu_forest_closest_to_songs_device";
+    int rc = forest_args_ok(who, forest, d_cand, n, d_order);
+    if (rc) return rc;
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    if (n == 0) return BLISSGPU_OK;
+    CTX_ENTER(c, who);
+    const uint32_t n32 = (uint32_t)n;
+    size_t tmp_bytes = 0;
+    HIP_TRY(sort_pairs_u32(nullptr, &tmp_bytes, nullptr, nullptr, nullptr, nullptr, n32, c->stream));
+    rc = c->pl_sync.ensure(4);
+    if (!rc) rc = c->pl_keys.ensure((size_t)3 * n32);  // keys in | keys out | indices in
+    if (!rc) rc = c->pl_tmp.ensure(tmp_bytes);
+    if (rc) return rc;
+    uint32_t *keys_in = c->pl_keys.p, *keys_out = keys_in + n32, *idx_in = keys_out + n32;
+    HIP_TRY(hipMemsetAsync(c->pl_sync.p, 0, 4 * sizeof(uint32_t), c->stream));
+    rc = forest_run(c, static_cast<Forest*>(forest), d_cand, n32, d_score, nullptr, keys_in, idx_in, who);
+    if (rc) return rc;
+    // the same stable radix sort as blissgpu_closest_to_songs_device (single launch only while its workgroups are co-resident)
+    HIP_TRY(sort_pairs_u32(c->pl_tmp.p, &tmp_bytes, keys_in, keys_out, idx_in, d_order, n32, c->stream, c->pl_sync.p + 2,
+                           live_contexts(c->device) <= 2 ? (uint32_t)std::max(1, c->n_cus) : 0u));
+    return BLISSGPU_OK;
+}
+
+// host-pointer forms: candidates staged in st_b, results in st_dist (scores), st_out (path sums or the order)
+static int forest_host(const char* who, void* forest, const float* cand, uint64_t n, float* score, uint64_t* path_sum,
+                       uint32_t* order) {
+    blissgpu_ctx* c;
+    int rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    Forest* f = static_cast<Forest*>(forest);
+    rc = c->st_b.ensure(n * f->d);
+    if (!rc) rc = c->st_dist.ensure(n);
+    if (!rc) rc = c->st_out.ensure(n * sizeof(uint64_t));
+    if (rc) return rc;
+    hipError_t e = hipMemcpyAsync(c->st_b.p, cand, n * f->d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(forest)", hipGetErrorString(e));
+    if (order) rc = blissgpu_forest_closest_to_songs_device(c, forest, c->st_b.p, n, reinterpret_cast<uint32_t*>(c->st_out.p), c->st_dist.p);
+    else rc = blissgpu_forest_score_device(c, forest, c->st_b.p, n, c->st_dist.p, path_sum ? reinterpret_cast<uint64_t*>(c->st_out.p) : nullptr);
+    if (!rc) {
+        if (score) e = hipMemcpyAsync(score, c->st_dist.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && order) e = hipMemcpyAsync(order, c->st_out.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && path_sum) e = hipMemcpyAsync(path_sum, c->st_out.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(forest)", hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+int blissgpu_forest_score(void* forest, const float* cand, uint64_t n, float* score, uint64_t* path_sum) {
+    int rc = forest_args_ok("blissgpu_forest_score", forest, cand, n, score);
+    if (rc || n == 0) return rc;
+    return forest_host("blissgpu_forest_score", forest, cand, n, score, path_sum, nullptr);
+}
+
+int blissgpu_forest_closest_to_songs(void* forest, const float* cand, uint64_t n, uint32_t* order, float* score) {
+    int rc = forest_args_ok("blissgpu_forest_closest_to_songs", forest, cand, n, order);
+    if (rc || n == 0) return rc;
+    return forest_host("blissgpu_forest_closest_to_songs", forest, cand, n, score, nullptr, order);
 }
 
 int blissgpu_malloc(void** p, uint64_t bytes) {

@@ -257,6 +257,8 @@ struct blissgpu_ctx {
     size_t swr_bytes = 0;
     uint64_t swr_clock = 0;
     // distances / playlist ordering scratch
+    int64_t forest_split = 0;                      // BLISSGPU_OPT_FOREST_SPLIT
+    bool forest_global = false;                    // BLISSGPU_OPT_FOREST_WALK = 1
     int n_cus = 0;
     bg::DevBuf<uint32_t> pl_sync, pl_keys;
     bg::DevBuf<uint32_t> pl_next;                  // dedup: next[] of every playlist position

@@ -114,6 +114,7 @@ enum KernelId : int {
     K_ROLLFIX,
     K_DEDUP_NEXT, K_DEDUP_WALK,  // playlist deduplication: never launched by the analysis path
     K_KNN_SCAN, K_KNN_MERGE,     // k-nearest search (kernels_knn.hip)
+    K_FOREST_WALK, K_FOREST_FINISH,  // isolation-forest scores (kernels_forest.hip)
     K_COUNT
 };
 

@@ -84,7 +84,7 @@ class Context:
                "debug_chroma": _ffi.OPT_DEBUG_CHROMA, "tail_split": _ffi.OPT_TAIL_SPLIT,
                "stft_shape": _ffi.OPT_STFT_SHAPE, "flux_order": _ffi.OPT_FLUX_ORDER,
                "stage_lanes": _ffi.OPT_STAGE_LANES, "stage_slab_kib": _ffi.OPT_STAGE_SLAB_KIB, "stage_slabs": _ffi.OPT_STAGE_SLABS,
-               "stage_numa": _ffi.OPT_STAGE_NUMA}
+               "stage_numa": _ffi.OPT_STAGE_NUMA, "forest_split": _ffi.OPT_FOREST_SPLIT, "forest_walk": _ffi.OPT_FOREST_WALK}
 
     def set_option(self, name: str, value: int):
         """Scheduling knobs for the measurement tools and the tests (blissgpu_ctx_set_option)."""
@@ -359,6 +359,38 @@ class Context:
                                                ptr(idx), ptr(dist)))
         self._post()
         return idx, dist
+
+    # ---- the isolation-forest metric on device-resident candidates (src/playlist.rs:230-251) ----
+    def forest_scores(self, forest, cand, return_path_sum=False):
+        """Scores of the candidate rows against a playlist.Forest (float32 tensor; with return_path_sum also the exact
+        integer path sums as an int64 tensor).  The forest is uploaded to this device on first use.  Asynchronous."""
+        torch = self.torch
+        assert cand.is_cuda and cand.dtype == torch.float32 and cand.dim() == 2 and (cand.shape[0] == 0 or cand.shape[1] == forest.d)
+        cand = cand.contiguous()
+        n = cand.shape[0]
+        score = torch.empty((n,), dtype=torch.float32, device=cand.device)
+        ps = torch.empty((n,), dtype=torch.int64, device=cand.device) if return_path_sum else None
+        self._pre()
+        _ffi.check(self._L.blissgpu_forest_score_device(self._h, forest.handle, C.c_void_p(cand.data_ptr()), n,
+                                                        C.c_void_p(score.data_ptr()), None if ps is None else C.c_void_p(ps.data_ptr())))
+        self._post()
+        return (score, ps) if return_path_sum else score
+
+    def forest_closest_to_songs(self, forest, cand, return_scores=False):
+        """Indices of the candidates sorted (stably) by their forest score (int64 tensor): closest_to_songs with a
+        ForestOptions metric."""
+        torch = self.torch
+        assert cand.is_cuda and cand.dtype == torch.float32 and cand.dim() == 2 and (cand.shape[0] == 0 or cand.shape[1] == forest.d)
+        cand = cand.contiguous()
+        n = cand.shape[0]
+        order = torch.empty((n,), dtype=torch.int32, device=cand.device)
+        score = torch.empty((n,), dtype=torch.float32, device=cand.device)
+        self._pre()
+        _ffi.check(self._L.blissgpu_forest_closest_to_songs_device(self._h, forest.handle, C.c_void_p(cand.data_ptr()), n,
+                                                                   C.c_void_p(order.data_ptr()), C.c_void_p(score.data_ptr())))
+        self._post()
+        order = order.to(torch.int64)
+        return (order, score) if return_scores else order
 
     # ---- profiling ----
     def profile_enable(self, on: bool = True):

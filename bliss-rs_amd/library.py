@@ -297,7 +297,19 @@ def playlist_from_custom(db: Conn, initial_song_paths: Sequence[str], metric_bui
     With this package's closest_to_songs / song_to_song the library matrix is read once, the order comes from the device
     and the deduplication is ONE device call over the rows (seeds first) -- no per-song call, no second copy of the rows.
     Any other `sort_by` runs on the host and its result goes through the same single call.  The metric is one of the
-    device metrics (playlist._metric_of)."""
+    device metrics (playlist._metric_of) or a playlist.ForestOptions.
+
+    A ForestOptions works with closest_to_songs and deduplicate=False (at least two initial songs; the matrix is still read
+    once and the forest scores come from the device).  With deduplicate=True the reference would build one-song forests,
+    which do not work (src/playlist.rs:230-240, 367-402): ValueError.  To deduplicate a forest playlist, pass the result to
+    playlist.dedup_playlist (euclidean).  song_to_song with a forest is refused for the same reason (:285-295)."""
+    forest = isinstance(metric_builder, playlist.ForestOptions)
+    if forest:
+        if deduplicate:
+            playlist._no_forest(metric_builder, "deduplicate=True builds one-song metrics (:367-402); use "
+                                                "playlist.dedup_playlist(result) on the playlist instead")
+        if sort_by is playlist.song_to_song:
+            playlist._no_forest(metric_builder, "song_to_song rebuilds its metric from one song after the first step (:285-295)")
     initial_song_paths = list(initial_song_paths)
     initial = []
     for p in initial_song_paths:
@@ -306,7 +318,7 @@ def playlist_from_custom(db: Conn, initial_song_paths: Sequence[str], metric_bui
         except Exception as e:
             raise ProviderError(f"song '{p}' has not been analyzed") from e
     songs, X = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
-    metric, m = playlist._metric_of(metric_builder)
+    metric, m = (metric_builder, None) if forest else playlist._metric_of(metric_builder)
     chosen = set(initial_song_paths)
     pool = [i for i, s in enumerate(songs) if s.path not in chosen]
     if sort_by not in (playlist.closest_to_songs, playlist.song_to_song):
@@ -344,6 +356,7 @@ def similar_songs(db: Conn, k: int, metric_builder=playlist.euclidean_distance, 
     and without the deduplication, for every analysed song of FeaturesVersion.LATEST (`song_paths` = None) or for those
     paths only; an unknown path is the ProviderError playlist_from_custom raises.  The matrix is read once and ONE device
     call (playlist.nearest_order, each song skipping its own row) answers every song: no distance matrix is built."""
+    playlist._no_forest(metric_builder, "similar_songs builds one metric per song")
     _, paths, X = load_feature_matrix(db, FeaturesVersion.LATEST)
     metric, m = playlist._metric_of(metric_builder)
     if song_paths is None:

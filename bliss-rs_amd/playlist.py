@@ -3,17 +3,20 @@
     euclidean / cosine / mahalanobis distance, builders          :65-79, 129-142
     DistanceMetricBuilder / FunctionDistanceMetric               :24-59
     variance_based_weight_matrix                                 :173-221
+    ForestOptions (the extended isolation forest metric)         :19-23, 230-251
     closest_to_songs, song_to_song                               :256-326
     nearest_order, nearest_songs (closest_to_songs cut after k, for many seeds at once)
     dedup_playlist, dedup_playlist_custom_distance               :343-402
     closest_album_to_group                                       :424-485
 
 A metric builder is one of the strings "euclidean" / "cosine", a `MahalanobisBuilder` (or the pair
-("mahalanobis", M)), i.e. the metrics the device implements; arbitrary Python callables are not accepted
+("mahalanobis", M)), or a `ForestOptions` (closest_to_songs and library.playlist_from_custom only: the forest needs at
+least two seed songs), i.e. the metrics the device implements; arbitrary Python callables are not accepted
 because the distances are evaluated by the HIP kernels (there is no CPU path).  Songs are anything with an
 `.analysis` (Analysis) -- `Song` or a wrapper holding one in `.bliss_song`, like the reference's
 `AsRef<Song>`."""
 import ctypes as C
+import os
 from typing import Callable, Sequence
 
 import numpy as np
@@ -104,6 +107,131 @@ class MahalanobisBuilder:
         self.m = np.ascontiguousarray(m, dtype=np.float32).copy()
 
 
+class ForestOptions:
+    """extended_isolation_forest::ForestOptions as a metric builder (src/playlist.rs:230-251): the metric meant for
+    playlists grown from SEVERAL seed songs (:19-23).  The four fields of the reference are required (`max_tree_depth`
+    may be None: ceil(log2(min(sample_size, number of seeds)))).  `seed` makes the forest a pure function of (seed songs,
+    options, seed), which the reference's (thread RNG) is not; None draws one from os.urandom and keeps it in `.seed`, so
+    any playlist can be reproduced after the fact."""
+
+    def __init__(self, n_trees, sample_size, max_tree_depth, extension_level, seed=None):
+        self.n_trees, self.sample_size, self.extension_level = int(n_trees), int(sample_size), int(extension_level)
+        self.max_tree_depth = None if max_tree_depth is None else int(max_tree_depth)
+        self.seed = int.from_bytes(os.urandom(8), "little") if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+
+    def __repr__(self):
+        return (f"ForestOptions(n_trees={self.n_trees}, sample_size={self.sample_size}, max_tree_depth={self.max_tree_depth}, "
+                f"extension_level={self.extension_level}, seed={self.seed})")
+
+
+_FOREST_SINGLE = ("the isolation forest does not work for a single song (min(sample_size, seeds) < 2, "
+                  "src/playlist.rs:230-240): {what}")
+
+
+def _no_forest(builder, what):
+    """The entry points whose metric is built from ONE song refuse a ForestOptions (psi < 2)."""
+    if isinstance(builder, ForestOptions):
+        raise ValueError(_FOREST_SINGLE.format(what=what))
+
+
+class Forest:
+    """A forest built from seed rows (host code, no device needed): the DistanceMetric ForestOptions::build returns
+    (src/playlist.rs:230-251).  `export()` gives the canonical dense form documented in include/blissgpu.h."""
+
+    def __init__(self, seeds, options: ForestOptions):
+        S = np.ascontiguousarray(np.atleast_2d(seeds), dtype=np.float32)
+        if not isinstance(options, ForestOptions):
+            raise TypeError("options must be a ForestOptions")
+        depth = options.max_tree_depth
+        if depth is not None and not 1 <= depth <= 128:
+            raise ValueError("max_tree_depth must be None or 1 .. 128")
+        for name in ("n_trees", "sample_size", "extension_level"):
+            if not 0 <= getattr(options, name) <= 0xFFFFFFFF:
+                raise ValueError(f"{name} out of range")
+        if min(options.sample_size, S.shape[0]) < 2:
+            raise ValueError(_FOREST_SINGLE.format(what=f"{S.shape[0]} seed(s), sample_size {options.sample_size}"))
+        self.options, self._h = options, None
+        h = C.c_void_p()
+        try:
+            _ffi.check(_ffi.lib().blissgpu_forest_build(S.ctypes.data, S.shape[0], S.shape[1], options.n_trees, options.sample_size,
+                                                        depth or 0, options.extension_level, options.seed, C.byref(h)))
+        except _ffi.BlissGpuError as e:
+            if e.code == _ffi.ERR_INVALID:
+                raise ValueError(str(e)) from e
+            raise
+        self._h = h
+        v = [C.c_uint32() for _ in range(5)]
+        nn = C.c_uint64()
+        _ffi.check(_ffi.lib().blissgpu_forest_info(h, *[C.byref(x) for x in v], C.byref(nn)))
+        self.d, self.n_trees, self.psi, self.depth_limit, self.extension_level = (int(x.value) for x in v)
+        self.n_nodes = int(nn.value)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if self._h is not None:
+            _ffi.lib().blissgpu_forest_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover - interpreter shutdown
+            pass
+
+    def export(self) -> dict:
+        T, N, d = self.n_trees, self.n_nodes, self.d
+        out = {"sample_idx": np.empty((T, self.psi), np.uint32), "tree_first": np.empty(T + 1, np.uint64),
+               "normal": np.empty((N, d), np.float32), "b": np.empty(N, np.float32), "left": np.empty(N, np.uint32),
+               "right": np.empty(N, np.uint32), "leaf_size": np.empty(N, np.uint32), "leaf_q": np.empty(N, np.uint32)}
+        _ffi.check(_ffi.lib().blissgpu_forest_export(self._h, *[a.ctypes.data for a in out.values()]))
+        return out
+
+    def _cand(self, candidates):
+        X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
+        if X.ndim != 2 or (X.shape[0] and X.shape[1] != self.d):
+            raise ValueError(f"candidates must be [n, {self.d}]")
+        return X
+
+    def scores(self, candidates, return_path_sum=False):
+        """-> score f32[n] (and the exact u64 path sums)."""
+        X = self._cand(candidates)
+        n = X.shape[0]
+        score, ps = np.empty(n, np.float32), np.empty(n, np.uint64)
+        _ffi.check(_ffi.lib().blissgpu_forest_score(self._h, X.ctypes.data, n, score.ctypes.data,
+                                                    ps.ctypes.data if return_path_sum else None))
+        return (score, ps) if return_path_sum else score
+
+    def closest_to_songs_order(self, candidates):
+        """-> (order u32[n], score f32[n]): stable ascending order of the scores."""
+        X = self._cand(candidates)
+        n = X.shape[0]
+        order, score = np.empty(n, np.uint32), np.empty(n, np.float32)
+        _ffi.check(_ffi.lib().blissgpu_forest_closest_to_songs(self._h, X.ctypes.data, n, order.ctypes.data, score.ctypes.data))
+        return order, score
+
+
+def forest_scores(seeds, candidates, options: ForestOptions) -> np.ndarray:
+    """ForestOptions::build(seeds).distance(candidate) for every row of `candidates` (src/playlist.rs:230-251): f32[n],
+    low for songs like the seeds, high for outliers."""
+    f = Forest(seeds, options)
+    try:
+        return f.scores(candidates)
+    finally:
+        f.close()
+
+
+def forest_closest_to_songs_order(seeds, candidates, options: ForestOptions):
+    """Index form of closest_to_songs with a forest: -> (order u32[n], scores f32[n])."""
+    f = Forest(seeds, options)
+    try:
+        return f.closest_to_songs_order(candidates)
+    finally:
+        f.close()
+
+
 def _metric_of(builder):
     """-> (metric name, M or None)"""
     if isinstance(builder, MahalanobisBuilder):
@@ -150,7 +278,10 @@ def set_distances(seeds, candidates, metric="euclidean", m=None) -> np.ndarray:
 
 
 def closest_to_songs_order(seeds, candidates, metric="euclidean", m=None):
-    """Index form of closest_to_songs: -> (order u32[n], distances f32[n])."""
+    """Index form of closest_to_songs: -> (order u32[n], distances f32[n]).  `metric` may be a ForestOptions (the forest
+    scores are the distances; see forest_closest_to_songs_order)."""
+    if isinstance(metric, ForestOptions):
+        return forest_closest_to_songs_order(seeds, candidates, metric)
     S = np.ascontiguousarray(np.atleast_2d(seeds), dtype=np.float32)
     X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
     order, dist = np.empty(X.shape[0], np.uint32), np.empty(X.shape[0], np.float32)
@@ -188,6 +319,9 @@ def closest_to_songs(initial_songs, candidate_songs, metric_builder=euclidean_di
     candidate_songs = list(candidate_songs)
     if not candidate_songs:
         return []
+    if isinstance(metric_builder, ForestOptions):
+        order, _ = forest_closest_to_songs_order(_matrix(initial_songs), _matrix(candidate_songs), metric_builder)
+        return [candidate_songs[i] for i in order]
     metric, m = _metric_of(metric_builder)
     order, _ = closest_to_songs_order(_matrix(initial_songs), _matrix(candidate_songs), metric, m)
     return [candidate_songs[i] for i in order]
@@ -195,6 +329,7 @@ def closest_to_songs(initial_songs, candidate_songs, metric_builder=euclidean_di
 
 def song_to_song(initial_songs, candidate_songs, metric_builder=euclidean_distance):
     """src/playlist.rs:272-326: each song is followed by the remaining song closest to it."""
+    _no_forest(metric_builder, "song_to_song rebuilds its metric from one song after the first step (:285-295)")
     candidate_songs = list(candidate_songs)
     if not candidate_songs:
         return []
@@ -248,6 +383,7 @@ def nearest_songs(songs, candidate_songs, k, metric_builder=euclidean_distance, 
     """For every song of `songs`, closest_to_songs(&[song], candidate_songs, metric_builder)[..k] (src/playlist.rs:256-270)
     -- all of them in one device call.  `exclude_self`: the first candidate that == the song (Song: PartialEq, as
     closest_album_to_group removes the group from its pool) is left out of that song's list."""
+    _no_forest(metric_builder, "nearest_songs builds one metric per query song")
     songs, candidate_songs = list(songs), list(candidate_songs)
     if not songs:
         return []
@@ -316,6 +452,7 @@ def dedup_playlist_custom_distance(playlist, distance_threshold=None, metric_bui
     """src/playlist.rs:367-402: a song absorbs the songs that follow it while they are closer than the threshold
     (default 0.05) or carry the same non-empty title and artist.  One device call for the whole playlist
     (dedup_order); `window` is accepted for compatibility and unused."""
+    _no_forest(metric_builder, "dedup_playlist_custom_distance builds its metric from single songs (:367-402)")
     playlist = list(playlist)
     if not playlist:
         return []

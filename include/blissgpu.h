@@ -125,6 +125,10 @@ int blissgpu_ctx_synchronize(blissgpu_ctx *ctx);
                                            the scheduler puts them -- near the caller's buffers, which measured better: a worker
                                            reading the caller's memory across the socket link is slower than the DMA engine
                                            reading the slab across it (profiles/r06_stage_numa_ab.txt) */
+#define BLISSGPU_OPT_FOREST_SPLIT 13    /* forest scoring: workgroups that share one candidate block's trees; 0 (default) = enough to
+                                           fill the device.  path_sum is an integer sum, so every setting gives the same result */
+#define BLISSGPU_OPT_FOREST_WALK 14     /* forest scoring: 0 (default) = trees staged in LDS chunk by chunk, 1 = every tree walked
+                                           from global memory (measurement form; same result) */
 int blissgpu_ctx_set_option(blissgpu_ctx *ctx, int option, int64_t value);
 /* Bytes of pageable host PCM this context has staged through its pinned ring since it was created (0: every source so far
  * was page-locked, small, or the ring is switched off). */
@@ -320,6 +324,61 @@ int blissgpu_knn(const float *queries, uint64_t q, const float *cand, uint64_t n
 int blissgpu_knn_device(blissgpu_ctx *ctx, const float *d_queries, uint64_t q, const float *d_cand, uint64_t n,
                         uint32_t d, int metric, const float *d_M, const uint32_t *d_skip, uint32_t k,
                         uint32_t *d_idx, float *d_dist);
+
+/* ---- extended isolation forest: the ForestOptions metric of src/playlist.rs:230-251 ----
+ * The reference builds extended_isolation_forest::Forest<f32, 23> from the seed songs with the thread RNG and uses its score
+ * as the "distance" of closest_to_songs (:247-250): seeds-like songs score low, outliers high.  Here the forest is a pure
+ * function of (seed rows, options, 64-bit seed), after Hariri, Carrasco Kind, Brunner, "Extended Isolation Forest" (IEEE TKDE
+ * 2019):
+ *   psi   = min(sample_size, n_seeds) (src/playlist.rs:237-240); psi < 2 is BLISSGPU_ERR_INVALID (c(psi) = 0: the forest does
+ *           not work for a single song).  limit = max_tree_depth (1 .. BLISSGPU_FOREST_MAX_DEPTH; 0 = None) or ceil(log2 psi).
+ *   tree t: psi distinct seed rows.  A node with m samples at depth k is a leaf if m <= 1 or k == limit.  Otherwise: a normal
+ *           with exactly extension_level + 1 non-zero standard-normal components (the d - extension_level - 1 dropped ones are
+ *           drawn uniformly without replacement), an intercept point p uniform in the box of the node's samples,
+ *           b = dot(normal, p); samples with dot(normal, x) < b go left, the others right.  A child may be empty.
+ *   dot:    DEFINED arithmetic: s = +0.0f; for j ascending with normal[j] != 0: s = s + normal[j] * x[j], product and sum each
+ *           rounded to f32.  Dropped components are skipped, not multiplied: a NaN or inf of x in a dimension the node does
+ *           not use never reaches s.  A NaN s compares false and goes right.  Builder and kernel use the same test.
+ *   leaf:   path length k + c(m), c(m) = 2 (ln(m - 1) + 0.5772156649) - 2 (m - 1) / m for m > 2, c(2) = 1, c(0) = c(1) = 0,
+ *           computed in f64 and stored as leaf_q = round(value * 2^24) in a u32.
+ *   score:  path_sum = the u64 sum of leaf_q over the trees (order-free, hence exact on the device);
+ *           score = (float)exp2(-(path_sum / 2^24 / n_trees) / c(psi)), evaluated in f64.  Always finite: no BLISSGPU_ERR_NAN here.
+ *   draws:  draw i of tree t = word (i & 3) of Philox4x32-10(counter = (i / 4 low, i / 4 high, t, 0x45494630), key = (seed low,
+ *           seed high)); the forest does not depend on how many threads build it.
+ * Limits: 1 <= d <= BLISSGPU_FOREST_MAX_D, 1 <= n_trees <= BLISSGPU_FOREST_MAX_TREES, 0 <= extension_level <= d - 1, psi is capped
+ * at BLISSGPU_FOREST_MAX_PSI, fewer than 2^32 - 1 nodes in all, finite seed rows; anything else is BLISSGPU_ERR_INVALID.
+ * The forest handle is opaque (void *).  build / info / export / destroy are host-only and work without a GPU. */
+#define BLISSGPU_FOREST_MAX_D 32u
+#define BLISSGPU_FOREST_MAX_TREES 1048576u
+#define BLISSGPU_FOREST_MAX_PSI 65536u
+#define BLISSGPU_FOREST_MAX_DEPTH 128u
+int blissgpu_forest_build(const float *seeds, uint64_t n_seeds, uint32_t d, uint32_t n_trees, uint32_t sample_size,
+                          uint32_t max_tree_depth, uint32_t extension_level, uint64_t seed, void **forest);
+int blissgpu_forest_destroy(void *forest); /* also frees the device copies; NULL is fine */
+/* Any pointer may be NULL. */
+int blissgpu_forest_info(const void *forest, uint32_t *d, uint32_t *n_trees, uint32_t *psi, uint32_t *depth_limit,
+                         uint32_t *extension_level, uint64_t *n_nodes);
+/* The forest in its canonical dense form (any pointer may be NULL).  With T = n_trees, N = n_nodes:
+ *   sample_idx[T * psi]  the seed rows tree t was grown from, sample_idx[t * psi .. (t + 1) * psi)
+ *   tree_first[T + 1]    tree t owns the nodes tree_first[t] .. tree_first[t + 1), its root first
+ *   normal[N * d]        the node's normal, zeros where dropped (all zero on a leaf)
+ *   b[N]                 the node's threshold (0 on a leaf)
+ *   left[N], right[N]    node indices of the children, 0xFFFFFFFF on a leaf
+ *   leaf_size[N]         samples of the tree that ended in the leaf (0 on an inner node)
+ *   leaf_q[N]            the leaf's u32 path length (0 on an inner node) */
+int blissgpu_forest_export(const void *forest, uint32_t *sample_idx, uint64_t *tree_first, float *normal, float *b,
+                           uint32_t *left, uint32_t *right, uint32_t *leaf_size, uint32_t *leaf_q);
+/* score[j] and (path_sum may be NULL) path_sum[j] of the n candidates, rows of d floats, d the forest's.  n == 0 is BLISSGPU_OK;
+ * n <= 0xFFFFFF00.  The device copy of the forest is uploaded once per (forest, device) and freed with the forest. */
+int blissgpu_forest_score(void *forest, const float *cand, uint64_t n, float *score, uint64_t *path_sum);
+/* closest_to_songs with the forest as the metric (src/playlist.rs:256-270): order[k] = the candidate with the k-th lowest score
+ * (stable: equal scores keep the candidates' order); score (may be NULL) receives the scores in candidate order. */
+int blissgpu_forest_closest_to_songs(void *forest, const float *cand, uint64_t n, uint32_t *order, float *score);
+/* Device-resident forms (device pointers); asynchronous on the context's stream but for the first upload of the forest. */
+int blissgpu_forest_score_device(blissgpu_ctx *ctx, void *forest, const float *d_cand, uint64_t n, float *d_score,
+                                 uint64_t *d_path_sum);
+int blissgpu_forest_closest_to_songs_device(blissgpu_ctx *ctx, void *forest, const float *d_cand, uint64_t n,
+                                            uint32_t *d_order, float *d_score);
 
 /* FeaturesVersion::feature_weights (src/lib.rs:168-173, 209-234): d x d row-major diagonal matrix. */
 int blissgpu_feature_weights(uint32_t features_version, float *M);
