@@ -193,7 +193,6 @@ struct HostFeed {
     DevBuf<float> pcm[N_FEED_BUFFERS];
     DevBuf<uint8_t> raw[N_FEED_BUFFERS];
     DevBuf<float> out[N_FEED_BUFFERS];
-    PinnedBuf<float> h_rows;  // (FEED_ROWS_STAGED builds only: the call's rows through a page-locked buffer, see scheduler.hip)
     hipEvent_t ev_copied[N_FEED_BUFFERS][N_COPY_STREAMS] = {}, ev_done[N_FEED_BUFFERS] = {};
     hipStream_t copy_stream[N_COPY_STREAMS] = {};
     // pageable sources (what a Rust Vec<f32> or a decoder's frame buffer is): staged by the library through page-locked slabs

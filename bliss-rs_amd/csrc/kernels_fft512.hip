@@ -34,9 +34,6 @@
 
 namespace bg {
 
-#ifndef FFT512_PAIR_SPLIT
-#define FFT512_PAIR_SPLIT 1
-#endif
 constexpr int GROUPS_PER_WG = 16;
 constexpr int FRAMES_PER_GROUP = F512_TILE / GROUPS_PER_WG;
 // rolloff: distance (relative to the frame's energy) below which the parallel and the sequential summation orders might
@@ -184,7 +181,6 @@ __device__ __forceinline__ void fft512_compute(f2 (&raw)[16], int l, f2* tile, c
     for (int k2 = 0; k2 < 16; k2++) tile[k2 * 17 + l] = v[R16(k2)];  // Z[k] at k + (k >> 4)
     __builtin_amdgcn_wave_barrier();
     const f2 z0 = tile[0];
-#if FFT512_PAIR_SPLIT
     // Z[k] and Z[256 - k] yield X[k] AND X[256 - k] (split_pair_sq: 10 instructions for two bins, the single form 7 for one).
     // The mirrors of lane l's bins 16 l + e, e = 1 .. 15, are lane 15 - l's bins 16 (15 - l) + 16 - e: every lane splits its
     // pairs e = 1 .. 8, keeps its own eight bins and hands the mirrored ones to its partner by one row_mirror DPP move each
@@ -194,7 +190,8 @@ __device__ __forceinline__ void fft512_compute(f2 (&raw)[16], int l, f2* tile, c
     // same bits: with Z[k] and Z[256 - k] exchanged and W_512^(256 - k) = -conj(W_512^k) (exact in the table: sin and cos
     // of mirrored angles are rounded from the same f64 values) every intermediate of the single form is the conjugate or
     // the negative of the pair form's, and IEEE operations are sign-symmetric.  Measured: rows bit-identical to round 3's
-    // (kbench hashes), FFT-512 kernel 12.55 -> 11.88 ms per 1024 songs.
+    // (kbench hashes), FFT-512 kernel 12.55 -> 11.88 ms per 1024 songs.  (Round 3's sixteen single splits per lane are kept in
+    // tests/tools/probes/lab_switches/.)
     {
         const f2 zk = tile[l * 17], zm = tile[(l == 0) ? 0 : 17 * (16 - l)];  // k = 0 pairs with itself
         out.m[0] = mag_from_sq(split_one_sq(zk, zm, tabs.tw512[0]));
@@ -210,16 +207,6 @@ __device__ __forceinline__ void fft512_compute(f2 (&raw)[16], int l, f2* tile, c
     }
 #pragma unroll
     for (int e = 9; e < 16; e++) out.m[e] = dpp_mov<DPP_ROW_MIRROR>(mir[16 - e]);
-#else
-#pragma unroll
-    for (int e = 0; e < 16; e++) {
-        const f2 zk = tile[l * 17 + e];
-        // Z[256 - k], k = 16 l + e  (k = 0 pairs with itself)
-        const int mi = (e == 0) ? ((l == 0) ? 0 : 17 * (16 - l)) : (17 * (15 - l) + 16 - e);
-        const f2 zm = tile[mi];
-        out.m[e] = mag_from_sq(split_one_sq(zk, zm, tabs.tw512[e]));  // W_512^k, k = 16 l + e
-    }
-#endif
     // Z is halved (half window): X[0] = 2 (Re Z[0] + Im Z[0]), X[256] = 2 (Re Z[0] - Im Z[0])
     if (l == 0) out.m[0] = 2.0f * fabsf(z0.x + z0.y);
     out.nyq = 2.0f * fabsf(z0.x - z0.y);

@@ -236,9 +236,6 @@ __global__ __launch_bounds__(64) void rolloff_fix_kernel(const float* __restrict
         }
     }
     __syncthreads();  // the list is complete
-#ifdef RF_SCAN_ONLY  // (timing probe: what the search alone costs)
-    if (count < 4096) return;
-#endif
     for (uint32_t base = 0; base < count; base += 64) {
         // piece p of the chunk's 64 frames: 16 loads in flight together (the wavefront pays the memory latency once per piece)
         auto fetch = [&](int p, float4 (&v)[16]) {

@@ -394,7 +394,6 @@ void scheduler_release(blissgpu_ctx* c) {
     c->swr_bytes = 0;
     for (hipStream_t& cs : f.copy_stream)
         if (cs) { (void)hipStreamSynchronize(cs); (void)hipStreamDestroy(cs); cs = nullptr; }
-    f.h_rows.release();
     for (int b = 0; b < N_FEED_BUFFERS; b++) {
         f.pcm[b].release(); f.raw[b].release(); f.out[b].release();
         for (hipEvent_t& ev : f.ev_copied[b])
@@ -642,9 +641,6 @@ int analyze_host_songs(blissgpu_ctx* c, const FeedSong* in, uint32_t n_songs, ui
         if (!rc && any_raw) rc = f.raw[b].ensure(max_raw + 256);
         if (!rc) rc = f.out[b].ensure(max_n * d);
     }
-#ifdef FEED_ROWS_STAGED
-    if (!rc) rc = f.h_rows.ensure((size_t)n_songs * d);
-#endif
     if (rc) return rc;
 
     std::vector<uint64_t> ticket(groups.size(), 0);
@@ -747,12 +743,8 @@ int analyze_host_songs(blissgpu_ctx* c, const FeedSong* in, uint32_t n_songs, ui
         const double t_enq = ms_now();
         // (The rows go straight into the caller's array.  Through a page-locked buffer of the context the calling thread would
         // not be held here until the group's analysis has finished -- and the feed measured 5 - 10 % SLOWER that way:
-        // FEED_ROWS_STAGED, profiles/r06_feed_rows_ab.txt.)
-#ifdef FEED_ROWS_STAGED
-        e = hipMemcpyAsync(f.h_rows.p + (size_t)g.i0 * d, f.out[b].p, (size_t)g.n * d * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-#else
+        // profiles/r06_feed_rows_ab.txt; the staged form is kept in tests/tools/probes/lab_switches/.)
         e = hipMemcpyAsync(out + (size_t)g.i0 * d, f.out[b].p, (size_t)g.n * d * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-#endif
         if (e == hipSuccess && d_rows)
             e = hipMemcpyAsync(d_rows + (size_t)g.i0 * d, f.out[b].p, (size_t)g.n * d * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
         if (e == hipSuccess) e = hipEventRecord(f.ev_done[b], c->stream);
@@ -774,9 +766,6 @@ int analyze_host_songs(blissgpu_ctx* c, const FeedSong* in, uint32_t n_songs, ui
     if (rc) return rc;
     if (e == hipSuccess) e = e1 != hipSuccess ? e1 : e2;
     if (e != hipSuccess) return fail(BLISSGPU_ERR_HIP, who, hipGetErrorString(e));
-#ifdef FEED_ROWS_STAGED
-    memcpy(out, f.h_rows.p, (size_t)n_songs * d * sizeof(float));
-#endif
     return BLISSGPU_OK;
 }
 
