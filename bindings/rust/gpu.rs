@@ -147,6 +147,13 @@ pub mod sys {
         pub fn blissgpu_knn_device(ctx: *mut blissgpu_ctx, d_queries: *const f32, q: u64, d_cand: *const f32, n: u64, d: u32,
                                    metric: c_int, d_m: *const f32, d_skip: *const u32, k: u32, d_idx: *mut u32,
                                    d_dist: *mut f32) -> c_int;
+        pub fn blissgpu_duplicate_groups(x: *const f32, n: u64, d: u32, meta: *const u32, metric: c_int, m_matrix: *const f32,
+                                         threshold: f32, label: *mut u32, n_pairs: *mut u64, pairs: *mut u32, pair_dist: *mut f32,
+                                         max_pairs: u64) -> c_int;
+        pub fn blissgpu_duplicate_groups_device(ctx: *mut blissgpu_ctx, d_x: *const f32, n: u64, d: u32, d_meta: *const u32,
+                                                metric: c_int, d_m: *const f32, threshold: f32, d_label: *mut u32,
+                                                d_n_pairs: *mut u64, d_pairs: *mut u32, d_pair_dist: *mut f32,
+                                                max_pairs: u64) -> c_int;
 
         // ---- extended isolation forest (ForestOptions, src/playlist.rs:230-251) ----
         pub fn blissgpu_forest_build(seeds: *const f32, n_seeds: u64, d: u32, n_trees: u32, sample_size: u32, max_tree_depth: u32,
@@ -430,6 +437,47 @@ pub fn nearest_on_device<T: AsRef<Song> + Clone>(songs: &[T], candidates: &[T], 
         return Err(gpu_err(rc));
     }
     Ok(idx.chunks(k).map(|row| row.iter().filter(|&&j| j != u32::MAX).map(|&j| candidates[j as usize].clone()).collect()).collect())
+}
+
+/// The duplicate rule of `dedup_playlist_custom_distance` (src/playlist.rs:381-388) over EVERY pair of `songs`, closed
+/// transitively: the groups of two or more songs that are closer than `distance_threshold` (default 0.05) or carry the same
+/// `Some` title and artist, directly or through a chain of such pairs.  Groups come by their first member, members in the
+/// order of `songs`; one library call, no distance matrix.  A NaN distance is `BLISSGPU_ERR_NAN`.
+pub fn duplicate_groups_on_device<T: AsRef<Song> + Clone>(songs: &[T], distance_threshold: Option<f32>, metric: Metric,
+                                                          m: Option<&Array2<f32>>) -> BlissResult<Vec<Vec<T>>> {
+    if songs.is_empty() {
+        return Ok(Vec::new());
+    }
+    let d = songs[0].as_ref().analysis.as_vec().len();
+    let x = songs.iter().flat_map(|s| s.as_ref().analysis.as_vec()).collect::<Vec<f32>>();
+    let mut seen = std::collections::HashMap::new();
+    let meta = songs
+        .iter()
+        .map(|s| match (&s.as_ref().title, &s.as_ref().artist) {
+            (Some(t), Some(a)) => {
+                let next = seen.len() as u32 + 1;
+                *seen.entry((t.clone(), a.clone())).or_insert(next)
+            }
+            _ => 0,
+        })
+        .collect::<Vec<u32>>();
+    let (_keep, mp) = matrix_ptr(m);
+    let mut label = vec![0u32; songs.len()];
+    let mut n_pairs = 0u64;
+    let rc = unsafe {
+        sys::blissgpu_duplicate_groups(x.as_ptr(), songs.len() as u64, d as u32, meta.as_ptr(), metric.code(), mp,
+                                       distance_threshold.unwrap_or(0.05), label.as_mut_ptr(), &mut n_pairs, std::ptr::null_mut(),
+                                       std::ptr::null_mut(), 0)
+    };
+    if rc != sys::BLISSGPU_OK {
+        return Err(gpu_err(rc));
+    }
+    // a label is its group's smallest row: walking the rows in order yields groups by first member, members ascending
+    let mut groups = std::collections::BTreeMap::<u32, Vec<T>>::new();
+    for (i, s) in songs.iter().enumerate() {
+        groups.entry(label[i]).or_default().push(s.clone());
+    }
+    Ok(groups.into_values().filter(|g| g.len() >= 2).collect())
 }
 
 /// `ForestOptions` of the CPU crate (src/playlist.rs:230-251) plus the 64-bit seed that makes the forest reproducible:

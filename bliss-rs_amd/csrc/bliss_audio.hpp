@@ -553,6 +553,37 @@ std::vector<T> dedup_playlist(const std::vector<T>& playlist, std::optional<floa
     return dedup_playlist_custom_distance(playlist, distance_threshold, euclidean_builder());
 }
 
+// duplicate_groups: the duplicate rule of dedup_playlist_custom_distance (src/playlist.rs:381-388) over EVERY pair of a
+// collection, closed transitively -- the groups of two or more songs that are "the same song", ordered by their first member,
+// members in the caller's order.  One device call, no distance matrix.
+template <typename T>
+std::vector<std::vector<T>> duplicate_groups(const std::vector<T>& songs, std::optional<float> distance_threshold, const MetricBuilder& mb) {
+    if (songs.empty()) return {};
+    size_t d = 0;
+    const auto x = feature_matrix(songs, d);
+    std::map<std::pair<std::string, std::string>, uint32_t> seen;
+    std::vector<uint32_t> meta(songs.size(), 0);
+    for (size_t i = 0; i < songs.size(); i++) {
+        const Song& s = as_song(songs[i]);
+        if (s.title && s.artist) meta[i] = seen.emplace(std::make_pair(*s.title, *s.artist), (uint32_t)seen.size() + 1).first->second;
+    }
+    std::vector<uint32_t> label(songs.size());
+    uint64_t n_pairs = 0;
+    check_ordering(blissgpu_duplicate_groups(x.data(), songs.size(), (uint32_t)d, meta.data(), mb.metric, mb.mptr(),
+                                             distance_threshold.value_or(0.05f), label.data(), &n_pairs, nullptr, nullptr, 0));
+    // a label is the smallest member: rows in order, so groups come by first member and members ascend
+    std::map<uint32_t, std::vector<T>> by_label;
+    for (size_t i = 0; i < songs.size(); i++) by_label[label[i]].push_back(songs[i]);
+    std::vector<std::vector<T>> out;
+    for (auto& kv : by_label)
+        if (kv.second.size() >= 2) out.push_back(std::move(kv.second));
+    return out;
+}
+template <typename T>
+std::vector<std::vector<T>> duplicate_groups(const std::vector<T>& songs, std::optional<float> distance_threshold) {
+    return duplicate_groups(songs, distance_threshold, euclidean_builder());
+}
+
 // closest_album_to_group (src/playlist.rs:424-485): the albums of `pool` (songs of `group` removed, songs without an
 // album dropped) ordered by the euclidean distance of their mean analysis to the group's mean analysis, each album
 // ordered by (disc number, track number); `group` itself comes first.

@@ -26,7 +26,8 @@ const char* const kKernelNames[K_COUNT] = {
     "fft512_kernel",     "onset_kernel",      "beat_kernel",   "stft8192_kernel", "tune_select_kernel",
     "tune_pass2_kernel", "tune_final_kernel", "chroma_kernel",     "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel", "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel",
     "dedup_next_kernel", "dedup_walk_kernel", "knn_scan_kernel", "knn_merge_kernel",
-    "forest_walk_kernel", "forest_finish_kernel"};
+    "forest_walk_kernel", "forest_finish_kernel",
+    "dup_init_kernel", "dup_join_kernel", "dup_flatten_kernel"};
 }  // namespace
 
 namespace bg {
@@ -925,6 +926,139 @@ int blissgpu_knn(const float* queries, uint64_t q, const float* cand, uint64_t n
         if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(knn)", hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+// ---- duplicate groups of a collection: the rule of dedup_playlist_custom_distance (src/playlist.rs:381-388) over EVERY pair
+// i < j of the rows, and the connected components of those edges ----
+// everything that can be said about the arguments without a device (both forms check it BEFORE the device is touched)
+static int dup_args_ok(const char* who, const void* x, uint64_t n, uint32_t d, int metric, const float* M, float threshold,
+                       const void* label, const void* n_pairs) {
+    if (d == 0 || d > 64) return fail(BLISSGPU_ERR_INVALID, who, "d must be 1 .. 64");
+    if (metric < 0 || metric > 2) return fail(BLISSGPU_ERR_INVALID, who, "unknown metric");
+    if (metric == BLISSGPU_METRIC_MAHALANOBIS && !M) return fail(BLISSGPU_ERR_INVALID, who, "mahalanobis needs M");
+    if (n >= 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "n must be below 2^32 - 1 rows");
+    if (threshold != threshold) return fail(BLISSGPU_ERR_INVALID, who, "threshold is NaN");
+    if (!n_pairs) return fail(BLISSGPU_ERR_INVALID, who, "n_pairs is NULL");
+    if (n && !x) return fail(BLISSGPU_ERR_INVALID, who, "x is NULL");
+    if (n && !label) return fail(BLISSGPU_ERR_INVALID, who, "label is NULL");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_duplicate_groups_device(blissgpu_ctx* c, const float* d_x, uint64_t n, uint32_t d, const uint32_t* d_meta,
+                                     int metric, const float* d_M, float threshold, uint32_t* d_label, uint64_t* d_n_pairs,
+                                     uint32_t* d_pairs, float* d_pair_dist, uint64_t max_pairs) {
+    const char* who = "blissgpu_duplicate_groups_device";
+    int rc = dup_args_ok(who, d_x, n, d, metric, d_M, threshold, d_label, d_n_pairs);
+    if (rc) return rc;
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    CTX_ENTER(c, who);
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_n_pairs, 0, sizeof(uint64_t), c->stream));
+        return BLISSGPU_OK;
+    }
+    int diag = 0;
+    if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
+        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
+            diag = is_diag(c->m_cache.data(), d);
+        } else {
+            std::vector<float> hM((size_t)d * d);
+            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            diag = is_diag(hM.data(), d);
+        }
+    }
+    // workspace: none but the caller's label array (the union-find's parents) and pair buffer, and eight words of the context
+    // -- pl_sync: [1] NaN among the distances of the pairs i < j, [4..5] the pair list's cursor
+    rc = c->pl_sync.ensure(8);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(c->pl_sync.p, 0, 8 * sizeof(uint32_t), c->stream));
+    unsigned long long* cursor = reinterpret_cast<unsigned long long*>(c->pl_sync.p + 4);
+    unsigned long long* np = reinterpret_cast<unsigned long long*>(d_n_pairs);
+    if (!d_pairs || max_pairs == 0) {
+        d_pairs = nullptr;
+        d_pair_dist = nullptr;
+        max_pairs = 0;
+    }
+    const DupPlan plan = dup_plan(n, c->n_cus);
+    {
+        Prof p(c, K_DUP_INIT);
+        launch_dup_init(d_label, (uint32_t)n, np, cursor, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    {
+        Prof p(c, K_DUP_JOIN);
+        launch_dup_join(d_x, (uint32_t)n, d, metric, d_M, diag, d_meta, threshold, plan, d_label, np, cursor, d_pairs, d_pair_dist,
+                        max_pairs, c->pl_sync.p + 1, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    {
+        Prof p(c, K_DUP_FLATTEN);
+        launch_dup_flatten(d_label, (uint32_t)n, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    return nan_check(c, c->pl_sync.p + 1, who);
+}
+
+int blissgpu_duplicate_groups(const float* x, uint64_t n, uint32_t d, const uint32_t* meta, int metric, const float* M,
+                              float threshold, uint32_t* label, uint64_t* n_pairs, uint32_t* pairs, float* pair_dist,
+                              uint64_t max_pairs) {
+    const char* who = "blissgpu_duplicate_groups";
+    int rc = dup_args_ok(who, x, n, d, metric, M, threshold, label, n_pairs);
+    if (rc) return rc;
+    *n_pairs = 0;
+    if (n == 0) return BLISSGPU_OK;
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    if (!pairs) max_pairs = 0;
+    // st_idx: n_pairs (two words) | label[n] | meta[n] | pairs[max_pairs][2]
+    const size_t o_label = 2, o_meta = o_label + n, o_pairs = o_meta + (meta ? n : 0);
+    const float* dM = nullptr;
+    rc = c->st_b.ensure(n * d);
+    if (!rc) rc = c->st_idx.ensure(o_pairs + 2 * max_pairs);
+    if (!rc && pair_dist && max_pairs) rc = c->st_dist.ensure(max_pairs);
+    if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
+    if (rc) return rc;
+    uint32_t* idx = c->st_idx.p;
+    float* d_dist = (pair_dist && max_pairs) ? c->st_dist.p : nullptr;
+    hipError_t e = hipMemcpyAsync(c->st_b.p, x, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && meta) e = hipMemcpyAsync(idx + o_meta, meta, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(duplicates)", hipGetErrorString(e));
+    if (!rc)
+        rc = blissgpu_duplicate_groups_device(c, c->st_b.p, n, d, meta ? idx + o_meta : nullptr, metric, dM, threshold,
+                                              idx + o_label, reinterpret_cast<uint64_t*>(idx), max_pairs ? idx + o_pairs : nullptr,
+                                              d_dist, max_pairs);
+    if (!rc) {  // the device form has synchronised: the count is there
+        uint64_t np = 0;
+        e = hipMemcpyAsync(&np, idx, sizeof(np), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(label, idx + o_label, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess && np && np <= max_pairs) {
+            // the list in ascending (i, j): the device appends in the order the wavefronts meet the edges
+            std::vector<uint32_t> hp(2 * np);
+            std::vector<float> hd(d_dist ? np : 0);
+            e = hipMemcpyAsync(hp.data(), idx + o_pairs, hp.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess && d_dist) e = hipMemcpyAsync(hd.data(), d_dist, np * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e == hipSuccess) {
+                std::vector<uint64_t> at(np);
+                for (uint64_t k = 0; k < np; k++) at[k] = k;
+                std::sort(at.begin(), at.end(), [&](uint64_t a, uint64_t b) {
+                    return hp[2 * a] != hp[2 * b] ? hp[2 * a] < hp[2 * b] : hp[2 * a + 1] < hp[2 * b + 1];
+                });
+                for (uint64_t k = 0; k < np; k++) {
+                    pairs[2 * k] = hp[2 * at[k]];
+                    pairs[2 * k + 1] = hp[2 * at[k] + 1];
+                    if (d_dist) pair_dist[k] = hd[at[k]];
+                }
+            }
+        }
+        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(duplicates)", hipGetErrorString(e));
+        if (!rc) *n_pairs = np;
     }
     (void)hipStreamSynchronize(c->stream);
     return rc;

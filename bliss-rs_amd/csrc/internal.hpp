@@ -115,6 +115,7 @@ enum KernelId : int {
     K_DEDUP_NEXT, K_DEDUP_WALK,  // playlist deduplication: never launched by the analysis path
     K_KNN_SCAN, K_KNN_MERGE,     // k-nearest search (kernels_knn.hip)
     K_FOREST_WALK, K_FOREST_FINISH,  // isolation-forest scores (kernels_forest.hip)
+    K_DUP_INIT, K_DUP_JOIN, K_DUP_FLATTEN,  // duplicate groups of a collection (kernels_duplicates.hip)
     K_COUNT
 };
 
@@ -238,6 +239,22 @@ void launch_knn_scan(const float* Q, uint64_t q, const float* X, uint32_t n, uin
                      uint32_t* nan_flag, uint32_t* bad_flag, hipStream_t st);
 void launch_knn_merge(const unsigned long long* part, uint64_t q, uint32_t k, const KnnPlan& p, uint32_t* idx, float* dist,
                       hipStream_t st);
+// duplicate groups (kernels_duplicates.hip): the split of the triangle of tile pairs for n rows, then the three launches.
+// `label` doubles as the union-find's parent array; *n_pairs counts the edges, *cursor hands out pair-list slots (both zeroed
+// by the init launch); a NaN distance of a pair i < j sets *nan_flag
+struct DupPlan {
+    uint32_t nb;         // blocks of 256 rows
+    uint32_t row_split;  // workgroups that share a tile's rows (1 unless the triangle is small)
+    uint64_t n_work;     // tile pairs I <= J times row_split
+    uint32_t grid;
+};
+DupPlan dup_plan(uint64_t n, int n_cus);
+float dup_bound(float threshold);  // sums above it cannot be closer than the threshold after the rounded square root
+void launch_dup_init(uint32_t* label, uint32_t n, unsigned long long* n_pairs, unsigned long long* cursor, hipStream_t st);
+void launch_dup_join(const float* X, uint32_t n, uint32_t d, int metric, const float* M, int m_is_diag, const uint32_t* meta,
+                     float thr, const DupPlan& p, uint32_t* label, unsigned long long* n_pairs, unsigned long long* cursor,
+                     uint32_t* pairs, float* pair_dist, uint64_t max_pairs, uint32_t* nan_flag, hipStream_t st);
+void launch_dup_flatten(uint32_t* label, uint32_t n, hipStream_t st);
 void launch_pairwise(const float* A, uint64_t n, const float* B, uint64_t m, uint32_t d, int metric, const float* M,
                      int m_is_diag, float* out, uint64_t ld_out, hipStream_t);
 void launch_synth(float* pcm, const SongDesc* songs, uint32_t n_songs, const uint32_t* pfx_e, uint32_t tiles_e,

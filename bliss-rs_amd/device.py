@@ -360,6 +360,42 @@ class Context:
         self._post()
         return idx, dist
 
+    def duplicate_labels(self, x, meta=None, metric: str = "euclidean", m=None, threshold=0.05, max_pairs: int = 0):
+        """Which rows of x are the same song (blissgpu_duplicate_groups_device): the pair i < j is an edge when its distance
+        is < threshold or meta[i] != 0 and meta[i] == meta[j] (int32 keys, playlist.meta_keys; None: no such rule).  ->
+        (labels, n_pairs): labels an int32 tensor, the smallest row of each row's connected component; n_pairs a one-element
+        int64 tensor, the number of edges.  With max_pairs > 0 -> (labels, n_pairs, pairs int32 [max_pairs, 2], dist float32
+        [max_pairs]): the first n_pairs entries hold the edges in unspecified order when n_pairs <= max_pairs, otherwise the
+        contents are unspecified.  Stays on the device; raises BlissGpuError(ERR_NAN) for a NaN distance (synchronises for
+        that check)."""
+        from .playlist import _METRICS
+
+        torch = self.torch
+        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
+        x = x.contiguous()
+        n, d = x.shape
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        if meta is not None:
+            assert meta.is_cuda and meta.dtype == torch.int32 and meta.shape[0] == n
+            meta = meta.contiguous()
+        if m is not None:
+            m = m.contiguous()
+        max_pairs = int(max_pairs)
+        labels = torch.empty((max(n, 1),), dtype=torch.int32, device=x.device)
+        n_pairs = torch.empty((1,), dtype=torch.int64, device=x.device)
+        pairs = dist = None
+        if max_pairs > 0:
+            pairs = torch.empty((max_pairs, 2), dtype=torch.int32, device=x.device)
+            dist = torch.empty((max_pairs,), dtype=torch.float32, device=x.device)
+        self._pre()
+        _ffi.check(self._L.blissgpu_duplicate_groups_device(self._h, ptr(x), n, d, ptr(meta), _METRICS[metric], ptr(m),
+                                                            float(threshold), ptr(labels), ptr(n_pairs), ptr(pairs), ptr(dist),
+                                                            max(max_pairs, 0)))
+        self._post()
+        if max_pairs > 0:
+            return labels[:n], n_pairs, pairs, dist
+        return labels[:n], n_pairs
+
     # ---- the isolation-forest metric on device-resident candidates (src/playlist.rs:230-251) ----
     def forest_scores(self, forest, cand, return_path_sum=False):
         """Scores of the candidate rows against a playlist.Forest (float32 tensor; with return_path_sum also the exact

@@ -25,6 +25,9 @@ database:
     album_playlist_from                   closest_album_to_group, cropped after `number_albums` album changes
     similar_songs                         the k closest songs of every song (or of some), one device call
                                           (playlist.nearest_order): playlist_from(&[song]).take(k) for the whole library
+    duplicate_songs                       the groups of songs that are the same song by the rule of dedup_playlist
+                                          (closer than the threshold, or the same title and artist) over EVERY pair of the
+                                          library, one device call (playlist.duplicate_labels); nothing is deleted
 
 SQLite stores `real` as f64; an f32 feature widens exactly on the way in and narrows exactly on the way out, so a
 round trip is bit-exact.  The schema, load and store helpers are host code; the playlists run their distances on the
@@ -373,6 +376,21 @@ def similar_songs(db: Conn, k: int, metric_builder=playlist.euclidean_distance, 
     idx, dist = playlist.nearest_order(Q, X, k, metric, m, skip=rows)
     return {paths[int(r)]: [(paths[int(j)], float(v)) for j, v in zip(idx[i], dist[i]) if j >= 0]
             for i, r in enumerate(rows)}
+
+
+def duplicate_songs(db: Conn, distance_threshold: float = None, metric_builder=playlist.euclidean_distance) -> List[List[Song]]:
+    """Which songs of the library are the same song: the duplicate rule of `dedup_playlist_custom_distance`
+    (src/playlist.rs:381-388: closer than the threshold, default 0.05, or the same `Some` title and artist) over every pair
+    of the analysed songs of FeaturesVersion.LATEST, closed transitively.  -> a list of groups (two or more `Song` each, in
+    id order; groups by their first song).  The library is read once (load_songs) and ONE device call answers
+    (playlist.duplicate_labels); nothing is deduplicated or deleted."""
+    playlist._no_forest(metric_builder, "duplicate_songs builds its metric from single songs")
+    songs, X = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
+    if not songs:
+        return []
+    metric, m = playlist._metric_of(metric_builder)
+    labels = playlist.duplicate_labels(X, playlist.meta_keys(songs), metric, m, distance_threshold)
+    return [[songs[i] for i in g] for g in playlist.groups_from_labels(labels)]
 
 
 def album_playlist_from(db: Conn, album_title: str, number_albums: int) -> List[Song]:

@@ -7,6 +7,7 @@
     closest_to_songs, song_to_song                               :256-326
     nearest_order, nearest_songs (closest_to_songs cut after k, for many seeds at once)
     dedup_playlist, dedup_playlist_custom_distance               :343-402
+    duplicate_labels, duplicate_groups (the rule of :381-388 over every pair of a collection, closed transitively)
     closest_album_to_group                                       :424-485
 
 A metric builder is one of the strings "euclidean" / "cosine", a `MahalanobisBuilder` (or the pair
@@ -464,6 +465,93 @@ def dedup_playlist_custom_distance(playlist, distance_threshold=None, metric_bui
 def dedup_playlist(playlist, distance_threshold=None):
     """src/playlist.rs:343-348"""
     return dedup_playlist_custom_distance(playlist, distance_threshold, euclidean_distance)
+
+
+def duplicate_labels(X, meta=None, metric="euclidean", m=None, threshold=None, return_pairs=False):
+    """Which rows of X are the same song: the duplicate rule of dedup_playlist_custom_distance (src/playlist.rs:381-388)
+    over EVERY pair i < j -- distance < threshold (default 0.05; the distance is bit for bit pairwise_distances(X, X)[i, j]),
+    or meta[i] != 0 and meta[i] == meta[j] (see meta_keys; None: no title / artist rule) -- and the connected components of
+    those edges, in one device call without the distance matrix.  -> labels int64[n]: the smallest row of each row's
+    component.  With `return_pairs` -> (labels, pairs int64[e, 2] in ascending (i, j), dist float32[e]).  A NaN distance
+    raises ValueError, like the reference's n32() panic."""
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    if X.ndim != 2:
+        raise ValueError("X must be [n, d]")
+    n, d = X.shape
+    if not 1 <= d <= 64:
+        raise ValueError("d must be 1 .. 64")
+    if metric not in _METRICS:
+        raise ValueError(f"unknown metric {metric!r}")
+    thr = np.float32(0.05 if threshold is None else threshold)
+    if np.isnan(thr):
+        raise ValueError("threshold is NaN")
+    meta_p = None
+    if meta is not None:
+        meta = np.ascontiguousarray(meta, dtype=np.uint32).reshape(-1)
+        if meta.shape[0] != n:
+            raise ValueError("meta needs one key per row of X")
+        meta_p = meta.ctypes.data
+    mp = None
+    if m is not None:
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        if m.shape != (d, d):
+            raise ValueError("m must be [d, d]")
+        mp = m.ctypes.data
+    elif metric == "mahalanobis":
+        raise ValueError("mahalanobis needs m")
+    labels, n_pairs = np.empty(max(n, 1), np.uint32), C.c_uint64()
+
+    def run(cap):
+        pairs = np.empty((max(cap, 1), 2), np.uint32) if return_pairs else None
+        dist = np.empty(max(cap, 1), np.float32) if return_pairs else None
+        try:
+            _ffi.check(_ffi.lib().blissgpu_duplicate_groups(X.ctypes.data, n, d, meta_p, _METRICS[metric], mp, thr,
+                                                            labels.ctypes.data, C.byref(n_pairs),
+                                                            pairs.ctypes.data if return_pairs else None,
+                                                            dist.ctypes.data if return_pairs else None,
+                                                            cap if return_pairs else 0))
+        except _ffi.BlissGpuError as e:
+            if e.code == _ffi.ERR_NAN:
+                raise ValueError("NaN distance (noisy_float::n32 panic in the reference)") from e
+            raise
+        return pairs, dist
+
+    cap = max(1024, n)  # duplicates are rare in a real library; a fuller list is fetched by the second call
+    pairs, dist = run(cap)
+    if return_pairs and n_pairs.value > cap:
+        cap = n_pairs.value
+        pairs, dist = run(cap)
+    out = labels[:n].astype(np.int64)
+    if not return_pairs:
+        return out
+    e = n_pairs.value
+    return out, pairs[:e].astype(np.int64), dist[:e].copy()
+
+
+def groups_from_labels(labels):
+    """Component labels (label = smallest member, as duplicate_labels returns them) -> the components of two or more
+    members as index arrays (int64, ascending), ordered by their smallest member."""
+    labels = np.asarray(labels, dtype=np.int64).reshape(-1)
+    if labels.size == 0:
+        return []
+    order = np.argsort(labels, kind="stable")  # by label; members of one label stay ascending
+    cuts = np.flatnonzero(np.diff(labels[order])) + 1
+    return [g for g in np.split(order, cuts) if g.size >= 2]
+
+
+def duplicate_groups(songs, distance_threshold=None, metric_builder=euclidean_distance):
+    """The songs of a collection that are the same song: groups (lists of the caller's own objects, two or more each) of
+    songs joined -- directly or through a chain -- by the duplicate rule of dedup_playlist_custom_distance
+    (src/playlist.rs:381-388): closer than the threshold (default 0.05) or the same non-empty title and artist.  Unlike
+    dedup_playlist, which compares the neighbours of an ordered playlist, every pair is looked at.  Groups come by their
+    first member, members in the order of `songs`."""
+    _no_forest(metric_builder, "duplicate_groups builds its metric from single songs")
+    songs = list(songs)
+    if not songs:
+        return []
+    metric, m = _metric_of(metric_builder)
+    labels = duplicate_labels(_matrix(songs), meta_keys(songs), metric, m, distance_threshold)
+    return [[songs[i] for i in g] for g in groups_from_labels(labels)]
 
 
 def variance_based_weight_matrix(seeds) -> np.ndarray:

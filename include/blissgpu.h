@@ -325,6 +325,32 @@ int blissgpu_knn_device(blissgpu_ctx *ctx, const float *d_queries, uint64_t q, c
                         uint32_t d, int metric, const float *d_M, const uint32_t *d_skip, uint32_t k,
                         uint32_t *d_idx, float *d_dist);
 
+/* ---- duplicate songs of a whole collection ----
+ * The duplicate rule of dedup_playlist_custom_distance (src/playlist.rs:381-388) applied to EVERY pair of the n x d matrix x
+ * instead of the neighbours of an ordered playlist: the pair (i, j), i < j, is an edge when D[i][j] < threshold (D[i][j] is bit
+ * for bit what blissgpu_pairwise_device(x, x) writes at row i, column j; the reference's default threshold is 0.05f) or when
+ * meta != NULL && meta[i] != 0 && meta[i] == meta[j] (one title / artist key per row, as for blissgpu_dedup_playlist).
+ *   label[i]  the smallest row index of i's connected component of that graph (the closure is transitive)
+ *   *n_pairs  the number of edges; always written
+ *   pairs     may be NULL; [max_pairs][2], every edge as (i, j) with i < j; pair_dist (may be NULL, only written along with
+ *             pairs) holds D[i][j] of the same entry, also for an edge that exists through meta only.  With *n_pairs <=
+ *             max_pairs the host form returns the edges in ascending (i, j), the device form the same set in unspecified order;
+ *             with *n_pairs > max_pairs the list's contents are unspecified and the call is still BLISSGPU_OK (size the buffer
+ *             and call again).  Nothing is written past max_pairs entries; the labels never depend on the pair buffer.
+ * label, *n_pairs and the set of pairs are functions of the inputs alone.  A NaN D[i][j] for any i < j returns
+ * BLISSGPU_ERR_NAN (the reference's n32() panic); the outputs are then unspecified.  threshold <= 0: no distance edges; a NaN
+ * threshold, d outside 1 .. 64, n >= 2^32 - 1, an unknown metric or Mahalanobis without M are BLISSGPU_ERR_INVALID, checked
+ * before the device is touched.  n == 0 is BLISSGPU_OK.  No n x n or slab x n array exists: the workspace is the label array
+ * and the caller's pair buffer; three launches whatever n. */
+int blissgpu_duplicate_groups(const float *x, uint64_t n, uint32_t d, const uint32_t *meta, int metric, const float *M,
+                              float threshold, uint32_t *label, uint64_t *n_pairs, uint32_t *pairs, float *pair_dist,
+                              uint64_t max_pairs);
+/* Device-resident form (device pointers, d_n_pairs included); asynchronous except for the NaN check, which synchronises the
+ * context's stream before returning. */
+int blissgpu_duplicate_groups_device(blissgpu_ctx *ctx, const float *d_x, uint64_t n, uint32_t d, const uint32_t *d_meta,
+                                     int metric, const float *d_M, float threshold, uint32_t *d_label, uint64_t *d_n_pairs,
+                                     uint32_t *d_pairs, float *d_pair_dist, uint64_t max_pairs);
+
 /* ---- extended isolation forest: the ForestOptions metric of src/playlist.rs:230-251 ----
  * The reference builds extended_isolation_forest::Forest<f32, 23> from the seed songs with the thread RNG and uses its score
  * as the "distance" of closest_to_songs (:247-250): seeds-like songs score low, outliers high.  Here the forest is a pure
