@@ -147,6 +147,11 @@ pub mod sys {
         pub fn blissgpu_knn_device(ctx: *mut blissgpu_ctx, d_queries: *const f32, q: u64, d_cand: *const f32, n: u64, d: u32,
                                    metric: c_int, d_m: *const f32, d_skip: *const u32, k: u32, d_idx: *mut u32,
                                    d_dist: *mut f32) -> c_int;
+        pub fn blissgpu_group_knn(seeds: *const f32, group_offsets: *const u64, n_groups: u64, cand: *const f32, n: u64, d: u32,
+                                  metric: c_int, m_matrix: *const f32, skip: *const u32, k: u32, idx: *mut u32, dist: *mut f32) -> c_int;
+        pub fn blissgpu_group_knn_device(ctx: *mut blissgpu_ctx, d_seeds: *const f32, group_offsets: *const u64, n_groups: u64,
+                                         d_cand: *const f32, n: u64, d: u32, metric: c_int, d_m: *const f32, d_skip: *const u32, k: u32,
+                                         d_idx: *mut u32, d_dist: *mut f32) -> c_int;
         pub fn blissgpu_duplicate_groups(x: *const f32, n: u64, d: u32, meta: *const u32, metric: c_int, m_matrix: *const f32,
                                          threshold: f32, label: *mut u32, n_pairs: *mut u64, pairs: *mut u32, pair_dist: *mut f32,
                                          max_pairs: u64) -> c_int;
@@ -432,6 +437,40 @@ pub fn nearest_on_device<T: AsRef<Song> + Clone>(songs: &[T], candidates: &[T], 
     let rc = unsafe {
         sys::blissgpu_knn(queries.as_ptr(), songs.len() as u64, cand.as_ptr(), candidates.len() as u64, d as u32, metric.code(), mp,
                           skip.as_ptr(), k as u32, idx.as_mut_ptr(), std::ptr::null_mut())
+    };
+    if rc != sys::BLISSGPU_OK {
+        return Err(gpu_err(rc));
+    }
+    Ok(idx.chunks(k).map(|row| row.iter().filter(|&&j| j != u32::MAX).map(|&j| candidates[j as usize].clone()).collect()).collect())
+}
+
+/// `closest_to_songs(group, candidates without the group's songs, metric)` cut after `k` (src/playlist.rs:36-59, 256-270) for
+/// every group of `groups` in one library call -- what `Library::playlist_from(&[several songs])?.take(k)`
+/// (src/library.rs:762-842) asks per album, artist or saved playlist: a candidate's score is the sequential sum of its
+/// distances to the group's songs, in their order; equal scores come in candidate order.  `exclude_members` leaves the first
+/// candidate equal to each member (`Song: PartialEq`) out of that group's list.  A NaN score is `BLISSGPU_ERR_NAN`.
+pub fn group_playlists_on_device<T: AsRef<Song> + Clone>(groups: &[Vec<T>], candidates: &[T], k: usize, metric: Metric,
+                                                         m: Option<&Array2<f32>>, exclude_members: bool) -> BlissResult<Vec<Vec<T>>> {
+    if groups.is_empty() || candidates.is_empty() {
+        return Ok(vec![Vec::new(); groups.len()]);
+    }
+    let d = candidates[0].as_ref().analysis.as_vec().len();
+    let cand = candidates.iter().flat_map(|s| s.as_ref().analysis.as_vec()).collect::<Vec<f32>>();
+    let seeds = groups.iter().flatten().flat_map(|s| s.as_ref().analysis.as_vec()).collect::<Vec<f32>>();
+    let mut offsets = vec![0u64; groups.len() + 1];
+    for (g, group) in groups.iter().enumerate() {
+        offsets[g + 1] = offsets[g] + group.len() as u64;
+    }
+    let skip = groups
+        .iter()
+        .flatten()
+        .map(|s| if exclude_members { candidates.iter().position(|c| c.as_ref() == s.as_ref()).map_or(u32::MAX, |j| j as u32) } else { u32::MAX })
+        .collect::<Vec<u32>>();
+    let (_keep, mp) = matrix_ptr(m);
+    let mut idx = vec![0u32; groups.len() * k];
+    let rc = unsafe {
+        sys::blissgpu_group_knn(seeds.as_ptr(), offsets.as_ptr(), groups.len() as u64, cand.as_ptr(), candidates.len() as u64, d as u32,
+                                metric.code(), mp, skip.as_ptr(), k as u32, idx.as_mut_ptr(), std::ptr::null_mut())
     };
     if rc != sys::BLISSGPU_OK {
         return Err(gpu_err(rc));

@@ -87,6 +87,12 @@ SIGNATURES = {
     "blissgpu_knn": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, C.c_uint32, _vp, _vp]),
     "blissgpu_knn_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, C.c_uint32, _vp,
                                       _vp]),
+    "blissgpu_group_knn": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, C.c_uint32, _vp,
+                                     _vp]),
+    "blissgpu_group_knn_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp,
+                                            C.c_uint32, _vp, _vp]),
+    "blissgpu_group_knn_plan": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _u64p, _u32p,
+                                          _u32p]),
     "blissgpu_duplicate_groups": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.c_int, _vp, C.c_float, _vp, _u64p, _vp, _vp,
                                             C.c_uint64]),
     "blissgpu_duplicate_groups_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_int, _vp, C.c_float, _vp, _vp, _vp,

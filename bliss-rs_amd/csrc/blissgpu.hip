@@ -27,7 +27,8 @@ const char* const kKernelNames[K_COUNT] = {
     "tune_pass2_kernel", "tune_final_kernel", "chroma_kernel",     "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel", "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel",
     "dedup_next_kernel", "dedup_walk_kernel", "knn_scan_kernel", "knn_merge_kernel",
     "forest_walk_kernel", "forest_finish_kernel",
-    "dup_init_kernel", "dup_join_kernel", "dup_flatten_kernel"};
+    "dup_init_kernel", "dup_join_kernel", "dup_flatten_kernel",
+    "group_knn_scan_kernel", "group_knn_merge_kernel"};
 }  // namespace
 
 namespace bg {
@@ -926,6 +927,151 @@ int blissgpu_knn(const float* queries, uint64_t q, const float* cand, uint64_t n
         if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(knn)", hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+// ---- k nearest candidates per seed GROUP: closest_to_songs(&group, candidates, metric) cut after k (src/playlist.rs:36-59,
+// 256-270), the primitive behind Library::playlist_from(&[several songs]).take(k) (src/library.rs:762-842), for every group of
+// a library in one call ----
+// everything that can be said about the arguments without a device (both forms check it BEFORE the device is touched)
+static int group_knn_args_ok(const char* who, const void* seeds, const uint64_t* off, uint64_t n_groups, const void* cand,
+                             uint64_t n, uint32_t d, int metric, const float* M, uint32_t k, const void* idx) {
+    if (k == 0 || k > BLISSGPU_KNN_MAX_K) return fail(BLISSGPU_ERR_INVALID, who, "k must be 1 .. BLISSGPU_KNN_MAX_K");
+    if (d == 0 || d > 64) return fail(BLISSGPU_ERR_INVALID, who, "d must be 1 .. 64");
+    if (metric < 0 || metric > 2) return fail(BLISSGPU_ERR_INVALID, who, "unknown metric");
+    if (metric == BLISSGPU_METRIC_MAHALANOBIS && !M) return fail(BLISSGPU_ERR_INVALID, who, "mahalanobis needs M");
+    if (n >= 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "n must be below 2^32 - 1 candidates");
+    if (n_groups >= 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "n_groups must be below 2^32 - 1");
+    if (n_groups == 0) return BLISSGPU_OK;
+    if (!off) return fail(BLISSGPU_ERR_INVALID, who, "group_offsets is NULL");
+    if (off[0] != 0) return fail(BLISSGPU_ERR_INVALID, who, "group_offsets[0] must be 0");
+    for (uint64_t g = 0; g < n_groups; g++)
+        if (off[g + 1] < off[g]) return fail(BLISSGPU_ERR_INVALID, who, "group_offsets must not decrease");
+    if (off[n_groups] > 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "2^32 seeds or more");
+    if (off[n_groups] && !seeds) return fail(BLISSGPU_ERR_INVALID, who, "seeds is NULL");
+    if (n && !cand) return fail(BLISSGPU_ERR_INVALID, who, "cand is NULL");
+    if (!idx) return fail(BLISSGPU_ERR_INVALID, who, "idx is NULL");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_group_knn_plan(const uint64_t* group_offsets, uint64_t n_groups, uint64_t n, uint32_t k, uint32_t n_cus,
+                            uint32_t* items, uint64_t max_items, uint64_t* n_items, uint32_t* cand_block, uint32_t* seed_tile) {
+    const char* who = "blissgpu_group_knn_plan";
+    const float some = 0.0f;  // (the plan reads neither seeds nor candidates)
+    uint32_t none = 0;
+    int rc = group_knn_args_ok(who, &some, group_offsets, n_groups, &some, n, 1, 0, nullptr, k, &none);
+    if (rc) return rc;
+    if (n_cus == 0) return fail(BLISSGPU_ERR_INVALID, who, "n_cus must be at least 1");
+    if (!n_items || (max_items && !items)) return fail(BLISSGPU_ERR_INVALID, who, "NULL argument");
+    const GroupKnnPlan p = group_knn_plan(group_offsets, n_groups, n, k, n_cus);
+    *n_items = p.items.size();
+    if (cand_block) *cand_block = p.cand_block;
+    if (seed_tile) *seed_tile = p.seed_tile;
+    for (uint64_t i = 0; i < p.items.size() && i < max_items; i++) {
+        items[4 * i + 0] = p.items[i].g_lo;
+        items[4 * i + 1] = p.items[i].g_hi;
+        items[4 * i + 2] = p.items[i].c_lo;
+        items[4 * i + 3] = p.items[i].c_hi;
+    }
+    return BLISSGPU_OK;
+}
+
+int blissgpu_group_knn_device(blissgpu_ctx* c, const float* d_seeds, const uint64_t* group_offsets, uint64_t n_groups,
+                              const float* d_cand, uint64_t n, uint32_t d, int metric, const float* d_M, const uint32_t* d_skip,
+                              uint32_t k, uint32_t* d_idx, float* d_dist) {
+    const char* who = "blissgpu_group_knn_device";
+    int rc = group_knn_args_ok(who, d_seeds, group_offsets, n_groups, d_cand, n, d, metric, d_M, k, d_idx);
+    if (rc) return rc;
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    if (n_groups == 0) return BLISSGPU_OK;
+    CTX_ENTER(c, who);
+    int diag = 0;
+    if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
+        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
+            diag = is_diag(c->m_cache.data(), d);
+        } else {
+            std::vector<float> hM((size_t)d * d);
+            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            diag = is_diag(hM.data(), d);
+        }
+    }
+    // the plan and its tables: group offsets (32 bits: fewer than 2^32 seeds) | list offsets | items.  Workspace: the sorted k
+    // best keys of every (group, item that covers it) -- no seeds x n or groups x n array exists anywhere
+    const GroupKnnPlan plan = group_knn_plan(group_offsets, n_groups, n, k, (uint32_t)std::max(1, c->n_cus));
+    const size_t n_off = (size_t)n_groups + 1, n_item_words = plan.items.size() * (sizeof(GroupKnnItem) / sizeof(uint32_t));
+    std::vector<uint32_t> table(2 * n_off + n_item_words);
+    for (size_t g = 0; g < n_off; g++) table[g] = (uint32_t)group_offsets[g];
+    std::copy(plan.list_off.begin(), plan.list_off.end(), table.begin() + n_off);
+    if (n_item_words) memcpy(table.data() + 2 * n_off, plan.items.data(), n_item_words * sizeof(uint32_t));
+    const uint64_t n_lists = plan.list_off[n_groups];
+    rc = c->pl_sync.ensure(4);
+    if (!rc) rc = c->pl_keys.ensure(table.size());
+    if (!rc) rc = c->pl_tmp.ensure(std::max<size_t>(8, (size_t)n_lists * k * sizeof(unsigned long long)));
+    if (rc) return rc;
+    const uint32_t *d_goff = c->pl_keys.p, *d_list_off = d_goff + n_off;
+    const GroupKnnItem* d_items = reinterpret_cast<const GroupKnnItem*>(d_list_off + n_off);
+    unsigned long long* part = reinterpret_cast<unsigned long long*>(c->pl_tmp.p);
+    HIP_TRY(hipMemcpyAsync(c->pl_keys.p, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    // pl_sync: [1] NaN among the scores of eligible pairs, [3] a skip entry >= n
+    HIP_TRY(hipMemsetAsync(c->pl_sync.p, 0, 4 * sizeof(uint32_t), c->stream));
+    {
+        Prof p(c, K_GROUP_KNN_SCAN);
+        launch_group_knn_scan(d_seeds, d_goff, d_cand, (uint32_t)n, d, metric, d_M, diag, d_skip, k, plan, d_items, d_list_off,
+                              part, c->pl_sync.p + 1, c->pl_sync.p + 3, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    {
+        Prof p(c, K_GROUP_KNN_MERGE);
+        launch_group_knn_merge(part, d_list_off, n_groups, k, plan, d_idx, d_dist, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    uint32_t flags[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(flags, c->pl_sync.p, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (the tables above have left the host by now too)
+    if (flags[3]) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
+    if (flags[1]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance (the reference panics here)");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_group_knn(const float* seeds, const uint64_t* group_offsets, uint64_t n_groups, const float* cand, uint64_t n,
+                       uint32_t d, int metric, const float* M, const uint32_t* skip, uint32_t k, uint32_t* idx, float* dist) {
+    const char* who = "blissgpu_group_knn";
+    int rc = group_knn_args_ok(who, seeds, group_offsets, n_groups, cand, n, d, metric, M, k, idx);
+    if (rc) return rc;
+    if (n_groups == 0) return BLISSGPU_OK;
+    const uint64_t n_seeds = group_offsets[n_groups];
+    if (skip)
+        for (uint64_t i = 0; i < n_seeds; i++)
+            if (skip[i] != 0xFFFFFFFFu && skip[i] >= n) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    const size_t out_n = (size_t)n_groups * k;
+    const float* dM = nullptr;
+    rc = c->st_b.ensure(std::max<size_t>(1, n * d));
+    if (!rc) rc = c->st_a.ensure(std::max<size_t>(1, n_seeds * d));
+    if (!rc) rc = c->st_idx.ensure(out_n + (skip ? n_seeds : 0));
+    if (!rc && dist) rc = c->st_dist.ensure(out_n);
+    if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
+    if (rc) return rc;
+    uint32_t *d_idx = c->st_idx.p, *d_skip = skip ? c->st_idx.p + out_n : nullptr;
+    hipError_t e = hipSuccess;
+    if (n) e = hipMemcpyAsync(c->st_b.p, cand, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && n_seeds) e = hipMemcpyAsync(c->st_a.p, seeds, n_seeds * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && skip && n_seeds) e = hipMemcpyAsync(d_skip, skip, n_seeds * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(group_knn)", hipGetErrorString(e));
+    if (!rc)
+        rc = blissgpu_group_knn_device(c, c->st_a.p, group_offsets, n_groups, c->st_b.p, n, d, metric, dM, d_skip, k, d_idx,
+                                       dist ? c->st_dist.p : nullptr);
+    if (!rc) {
+        e = hipMemcpyAsync(idx, d_idx, out_n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(group_knn)", hipGetErrorString(e));
     }
     (void)hipStreamSynchronize(c->stream);
     return rc;

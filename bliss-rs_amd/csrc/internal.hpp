@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 namespace bg {
 
 constexpr uint32_t SAMPLE_RATE = 22050;   // src/lib.rs:140
@@ -116,6 +118,7 @@ enum KernelId : int {
     K_KNN_SCAN, K_KNN_MERGE,     // k-nearest search (kernels_knn.hip)
     K_FOREST_WALK, K_FOREST_FINISH,  // isolation-forest scores (kernels_forest.hip)
     K_DUP_INIT, K_DUP_JOIN, K_DUP_FLATTEN,  // duplicate groups of a collection (kernels_duplicates.hip)
+    K_GROUP_KNN_SCAN, K_GROUP_KNN_MERGE,    // k-nearest search per seed group (kernels_group_knn.hip)
     K_COUNT
 };
 
@@ -239,6 +242,27 @@ void launch_knn_scan(const float* Q, uint64_t q, const float* X, uint32_t n, uin
                      uint32_t* nan_flag, uint32_t* bad_flag, hipStream_t st);
 void launch_knn_merge(const unsigned long long* part, uint64_t q, uint32_t k, const KnnPlan& p, uint32_t* idx, float* dist,
                       hipStream_t st);
+// k nearest candidates per seed GROUP (kernels_group_knn.hip): the groups x candidates plane dealt out in items, then the two
+// launches.  `part` holds list_off[n_groups] lists of k 64-bit keys; flags as for knn
+constexpr int GROUP_KNN_SEED_TILE = 32;  // the most seed rows of one group held in LDS at a time
+struct GroupKnnItem {
+    uint32_t g_lo, g_hi;  // groups [g_lo, g_hi)
+    uint32_t c_lo, c_hi;  // candidates [c_lo, c_hi): c_lo a multiple of the candidate block
+    uint32_t split;       // which of its groups' partial lists the item writes
+};
+struct GroupKnnPlan {
+    uint32_t cap = 0, qb = 0;               // keys of a group's threshold buffer, groups a workgroup holds at a time
+    uint32_t cand_block = 0, seed_tile = 0;
+    std::vector<GroupKnnItem> items;
+    std::vector<uint32_t> list_off;         // [n_groups + 1]: group g's partial lists are list_off[g] .. list_off[g + 1]
+};
+GroupKnnPlan group_knn_plan(const uint64_t* off, uint64_t n_groups, uint64_t n, uint32_t k, uint32_t n_cus);
+void launch_group_knn_scan(const float* S, const uint32_t* goff, const float* X, uint32_t n, uint32_t d, int metric,
+                           const float* M, int m_is_diag, const uint32_t* skip, uint32_t k, const GroupKnnPlan& p,
+                           const GroupKnnItem* items, const uint32_t* list_off, unsigned long long* part, uint32_t* nan_flag,
+                           uint32_t* bad_flag, hipStream_t st);
+void launch_group_knn_merge(const unsigned long long* part, const uint32_t* list_off, uint64_t n_groups, uint32_t k,
+                            const GroupKnnPlan& p, uint32_t* idx, float* dist, hipStream_t st);
 // duplicate groups (kernels_duplicates.hip): the split of the triangle of tile pairs for n rows, then the three launches.
 // `label` doubles as the union-find's parent array; *n_pairs counts the edges, *cursor hands out pair-list slots (both zeroed
 // by the init launch); a NaN distance of a pair i < j sets *nan_flag

@@ -360,6 +360,39 @@ class Context:
         self._post()
         return idx, dist
 
+    def group_knn(self, S, offsets, X, k: int, metric: str = "euclidean", M=None, skip=None):
+        """The k nearest rows of X for every seed GROUP without a groups x candidates matrix: group g's seeds are the rows
+        offsets[g] .. offsets[g + 1] of S (offsets: a HOST sequence of G + 1 integers starting at 0), its row =
+        closest_to_songs(those seeds, X without the group's skipped rows, metric) cut after k (src/playlist.rs:36-59, 256-270,
+        src/library.rs:762-842); a candidate's score is the sequential f32 sum over the seeds in order.  -> (idx int32 [G, k],
+        dist float32 [G, k]) on the device; equal scores in candidate order; rows with fewer than k eligible candidates end in
+        -1 (the library's 0xFFFFFFFF) / inf.  skip: int32 tensor with one candidate index per SEED ROW, -1 = none, or None.
+        Raises BlissGpuError(ERR_NAN) for a NaN among the scores (synchronises for that check)."""
+        import numpy as np
+
+        from .playlist import _METRICS
+
+        torch = self.torch
+        assert S.is_cuda and X.is_cuda and S.dtype == torch.float32 and X.dtype == torch.float32
+        assert S.dim() == 2 and X.dim() == 2 and S.shape[1] == X.shape[1]
+        S, X = S.contiguous(), X.contiguous()
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1)).astype(np.uint64)
+        assert off.shape[0] >= 1 and int(off[-1]) == S.shape[0]
+        G, n, k = off.shape[0] - 1, X.shape[0], int(k)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        if skip is not None:
+            assert skip.is_cuda and skip.dtype == torch.int32 and skip.shape[0] == S.shape[0]
+            skip = skip.contiguous()
+        if M is not None:
+            M = M.contiguous()
+        idx = torch.empty((G, max(k, 0)), dtype=torch.int32, device=X.device)
+        dist = torch.empty((G, max(k, 0)), dtype=torch.float32, device=X.device)
+        self._pre()
+        _ffi.check(self._L.blissgpu_group_knn_device(self._h, ptr(S), off.ctypes.data, G, ptr(X), n, X.shape[1], _METRICS[metric],
+                                                     ptr(M), ptr(skip), k, ptr(idx), ptr(dist)))
+        self._post()
+        return idx, dist
+
     def duplicate_labels(self, x, meta=None, metric: str = "euclidean", m=None, threshold=0.05, max_pairs: int = 0):
         """Which rows of x are the same song (blissgpu_duplicate_groups_device): the pair i < j is an edge when its distance
         is < threshold or meta[i] != 0 and meta[i] == meta[j] (int32 keys, playlist.meta_keys; None: no such rule).  ->

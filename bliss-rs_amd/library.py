@@ -378,6 +378,48 @@ def similar_songs(db: Conn, k: int, metric_builder=playlist.euclidean_distance, 
             for i, r in enumerate(rows)}
 
 
+_GROUP_COLUMNS = ("album", "artist", "album_artist", "genre")
+
+
+def group_playlists(db: Conn, k: int, by: str = "album", metric_builder=playlist.euclidean_distance, groups=None):
+    """A k-song playlist for every album (artist, album artist, genre) of a library, or for arbitrary seed sets:
+    {key: [(path, score), ...]} where entry `key` is
+    `playlist_from_custom(db, paths, metric_builder, closest_to_songs, deduplicate=False)[len(paths):][:k]` with the scores
+    (src/library.rs:762-842: the songs closest to the SET of initial songs, the initial songs themselves left out).  The
+    library is read once and ONE device call (playlist.nearest_to_groups) answers every group.
+
+    `by`: the column that groups the analysed songs of FeaturesVersion.LATEST; a song whose key is NULL belongs to no group
+    but stays a candidate; groups come in order of first appearance by id, their members in id order.  `groups` =
+    {name: [paths]} gives the seed sets instead (a saved playlist): order as given, a repeated path is a seed twice, an
+    unknown path is the ProviderError playlist_from_custom raises."""
+    playlist._no_forest(metric_builder, "group_playlists would build one forest per group; use playlist_from_custom per group")
+    if groups is None and by not in _GROUP_COLUMNS:
+        raise ValueError(f"by must be one of {_GROUP_COLUMNS}")
+    songs, X = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
+    metric, m = playlist._metric_of(metric_builder)
+    members = {}
+    if groups is None:
+        for i, s in enumerate(songs):
+            key = getattr(s, by)
+            if key is not None:
+                members.setdefault(key, []).append(i)
+    else:
+        row_of = {s.path: i for i, s in enumerate(songs)}
+        for name, paths in groups.items():
+            for p in paths:
+                if p not in row_of:
+                    raise ProviderError(f"song '{p}' has not been analyzed")
+            members[name] = [row_of[p] for p in paths]
+    if not members:
+        return {}
+    keys = list(members)
+    offsets = np.zeros(len(keys) + 1, np.int64)
+    offsets[1:] = np.cumsum([len(members[key]) for key in keys])
+    rows = np.asarray([i for key in keys for i in members[key]], np.int64)
+    idx, dist = playlist.nearest_to_groups((X[rows].reshape(rows.shape[0], X.shape[1]), offsets), X, k, metric, m, skip=rows)
+    return {key: [(songs[int(j)].path, float(v)) for j, v in zip(idx[g], dist[g]) if j >= 0] for g, key in enumerate(keys)}
+
+
 def duplicate_songs(db: Conn, distance_threshold: float = None, metric_builder=playlist.euclidean_distance) -> List[List[Song]]:
     """Which songs of the library are the same song: the duplicate rule of `dedup_playlist_custom_distance`
     (src/playlist.rs:381-388: closer than the threshold, default 0.05, or the same `Some` title and artist) over every pair

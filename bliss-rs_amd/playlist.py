@@ -403,6 +403,120 @@ def nearest_songs(songs, candidate_songs, k, metric_builder=euclidean_distance, 
     return [[candidate_songs[j] for j in row if j >= 0] for row in idx]
 
 
+def _seed_groups(seed_groups):
+    """-> (S f32[total, d] or None when there is no seed at all, offsets u64[G + 1])"""
+    if isinstance(seed_groups, tuple) and len(seed_groups) == 2 and not isinstance(seed_groups[0], (list, tuple)) \
+            and np.ndim(seed_groups[0]) == 2 and np.ndim(seed_groups[1]) == 1:
+        S = np.ascontiguousarray(seed_groups[0], dtype=np.float32)
+        off = np.asarray(seed_groups[1], dtype=np.int64).reshape(-1)
+        if off.shape[0] < 1 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != S.shape[0]:
+            raise ValueError("offsets must start at 0, not decrease and end at the number of seed rows")
+        return S, off.astype(np.uint64)
+    groups = [np.asarray(g, dtype=np.float32) for g in seed_groups]
+    groups = [g.reshape(0, g.shape[-1] if g.ndim == 2 else 0) if g.size == 0 else np.atleast_2d(g) for g in groups]
+    off = np.zeros(len(groups) + 1, np.uint64)
+    off[1:] = np.cumsum([g.shape[0] for g in groups])
+    full = [g for g in groups if g.shape[0]]
+    if any(g.ndim != 2 for g in full) or len({g.shape[1] for g in full}) > 1:
+        raise ValueError("every seed group must be [s_g, d] with the same d")
+    return (np.ascontiguousarray(np.concatenate(full)) if full else None), off
+
+
+def nearest_to_groups(seed_groups, candidates, k, metric="euclidean", m=None, skip=None):
+    """The k nearest candidates of every seed GROUP in one device call, without a groups x candidates matrix: row g of the
+    result is closest_to_songs(seed_groups[g], candidates without skip[g], metric) (src/playlist.rs:36-59, 256-270) cut
+    after k -- what Library::playlist_from(&[several songs]).take(k) asks per album, artist or saved playlist
+    (src/library.rs:762-842).  A candidate's score is the sequential f32 sum of its distances to the group's seeds, in seed
+    order (set_distances bit for bit); an empty group scores 0 everywhere.  -> (idx int64[G, k], dist float32[G, k]); equal
+    scores come in candidate order; rows with fewer than k eligible candidates end in -1 / inf.
+    `seed_groups`: a sequence of [s_g, d] arrays, or (S [total, d], offsets [G + 1]).  `skip`: None, one array of
+    candidate indices per group (left out of that group's list), or one flat array with an entry per seed row (-1: none).
+    A NaN score raises ValueError (the reference's n32() panic).  A ForestOptions is refused: a forest is built per seed
+    set, use closest_to_songs per group."""
+    _no_forest(metric, "nearest_to_groups would build one forest per seed group; use closest_to_songs per group")
+    S, off = _seed_groups(seed_groups)
+    X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
+    if X.ndim != 2 or (S is not None and S.shape[1] != X.shape[1]):
+        raise ValueError("seed groups and candidates must be [s_g, d] and [n, d]")
+    if metric not in _METRICS:
+        raise ValueError(f"unknown metric {metric!r}")
+    k = int(k)
+    if not 1 <= k <= 1024:
+        raise ValueError("k must be 1 .. 1024")
+    n, d = X.shape
+    if not 1 <= d <= 64:
+        raise ValueError("d must be 1 .. 64")
+    G, total = off.shape[0] - 1, int(off[-1])
+    skip_p = None
+    if skip is not None:
+        if isinstance(skip, np.ndarray) and skip.dtype != object and skip.ndim == 1 or \
+                (len(skip) != G or total == G) and all(np.ndim(s) == 0 for s in skip):
+            flat = np.asarray(skip, dtype=np.int64).reshape(-1)  # one entry per seed row
+            if flat.shape[0] != total:
+                raise ValueError("a flat skip needs one entry per seed row")
+        else:
+            if len(skip) != G:
+                raise ValueError("skip needs one index array per group")
+            flat = np.full(total, -1, np.int64)
+            for g, sk in enumerate(skip):
+                sk = np.unique(np.asarray(sk, dtype=np.int64).reshape(-1))
+                sk = sk[sk != -1]
+                a, b = int(off[g]), int(off[g + 1])
+                if sk.shape[0] > b - a:
+                    raise ValueError(f"group {g} skips {sk.shape[0]} candidates but has {b - a} seeds (one skip per seed row)")
+                flat[a:a + sk.shape[0]] = sk
+        if ((flat < -1) | (flat >= max(n, 0))).any():
+            raise ValueError("skip entries must be candidate indices or -1")
+        skip = np.where(flat < 0, 0xFFFFFFFF, flat).astype(np.uint32)
+        skip_p = skip.ctypes.data
+    mp = None
+    if metric == "mahalanobis":
+        if m is None:
+            raise ValueError("mahalanobis needs m")
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        if m.shape != (d, d):
+            raise ValueError("m must be [d, d]")
+        mp = m.ctypes.data
+    idx, dist = np.empty((G, k), np.uint32), np.empty((G, k), np.float32)
+    try:
+        _ffi.check(_ffi.lib().blissgpu_group_knn(None if S is None else S.ctypes.data, off.ctypes.data, G, X.ctypes.data, n, d,
+                                                 _METRICS[metric], mp, skip_p, k, idx.ctypes.data, dist.ctypes.data))
+    except _ffi.BlissGpuError as e:
+        _nan_to_panic(e)
+    out = idx.astype(np.int64)
+    out[idx == 0xFFFFFFFF] = -1
+    return out, dist
+
+
+def group_playlists(groups, candidate_songs, k, metric_builder=euclidean_distance, exclude_members=True):
+    """For every group of songs, closest_to_songs(group, candidate_songs without the group's songs, metric_builder)[..k]
+    (src/playlist.rs:256-270) -- a playlist "in the vibe of these songs" per album, artist or saved playlist, all of them
+    in one device call.  `exclude_members`: the first candidate that == each member (Song: PartialEq, as
+    nearest_songs(exclude_self=True)) is left out of that group's list."""
+    _no_forest(metric_builder, "group_playlists would build one forest per group; use closest_to_songs per group")
+    groups, candidate_songs = [list(g) for g in groups], list(candidate_songs)
+    if not groups:
+        return []
+    if not candidate_songs:
+        return [[] for _ in groups]
+    metric, m = _metric_of(metric_builder)
+    X = _matrix(candidate_songs)
+    seeds = [_matrix(g) if g else np.zeros((0, X.shape[1]), np.float32) for g in groups]
+    skip = None
+    if exclude_members:
+        skip = np.full(sum(len(g) for g in groups), -1, np.int64)
+        row = 0
+        for g in groups:
+            for s in g:
+                for j, c in enumerate(candidate_songs):
+                    if _song_of(c) == _song_of(s):
+                        skip[row] = j
+                        break
+                row += 1
+    idx, _ = nearest_to_groups(seeds, X, k, metric, m, skip)
+    return [[candidate_songs[j] for j in row if j >= 0] for row in idx]
+
+
 def meta_keys(songs) -> np.ndarray:
     """One u32 key per song for the title / artist rule of dedup_playlist_custom_distance (src/playlist.rs:383-389:
     both titles and both artists Some, and equal): 0 when the title or the artist is None, otherwise equal keys

@@ -325,6 +325,40 @@ int blissgpu_knn_device(blissgpu_ctx *ctx, const float *d_queries, uint64_t q, c
                         uint32_t d, int metric, const float *d_M, const uint32_t *d_skip, uint32_t k,
                         uint32_t *d_idx, float *d_dist);
 
+/* The k nearest candidates of every seed GROUP: closest_to_songs(&group, candidates, metric) cut after k, what
+ * Library::playlist_from(&[several songs]).take(k) (src/library.rs:762-842) asks per album, artist, genre or saved playlist,
+ * for n_groups groups in one call.  seeds is [group_offsets[n_groups]][d] row-major; group g's seeds are the rows
+ * group_offsets[g] .. group_offsets[g + 1], in sum order (group_offsets[0] == 0, non-decreasing; a HOST pointer in both forms:
+ * the work is dealt out before anything is launched).  A candidate's score is 0.0f + m(seed_0, cand) + m(seed_1, cand) + ...,
+ * added sequentially in f32 in seed order: bit for bit what blissgpu_set_distance writes for the same seeds.  An empty group
+ * scores +0.0 everywhere (its row is the first k candidates).  Row g of idx / dist ([n_groups][k], dist may be NULL) is the
+ * first k entries of the stable ascending order of the group's eligible candidates: equal scores in candidate order, rows with
+ * fewer than k eligible candidates end in idx 0xFFFFFFFF / dist +inf.  skip is NULL or one candidate index per SEED ROW: that
+ * candidate is left out of the seed's group and none of its distances to the group is looked at (how playlist_from keeps the
+ * initial songs out; with one seed per group it is blissgpu_knn's skip); 0xFFFFFFFF skips nothing, any other value >= n is
+ * BLISSGPU_ERR_INVALID.  A NaN score of an eligible (group, candidate) pair returns BLISSGPU_ERR_NAN; the outputs are then
+ * unspecified.  1 <= k <= BLISSGPU_KNN_MAX_K, 1 <= d <= 64, n < 2^32 - 1, fewer than 2^32 seeds and 2^32 - 1 groups;
+ * n_groups == 0 or n == 0 is BLISSGPU_OK (n == 0: every row is padding).  Arguments are checked before the device is touched,
+ * the host form's skip on the host.  No seeds x n or n_groups x n array is ever stored: the workspace is O(items x k) keys,
+ * two launches whatever n_groups, n and the group sizes. */
+int blissgpu_group_knn(const float *seeds, const uint64_t *group_offsets, uint64_t n_groups, const float *cand, uint64_t n,
+                       uint32_t d, int metric, const float *M, const uint32_t *skip, uint32_t k, uint32_t *idx, float *dist);
+/* Device-resident form (device pointers, d_skip included; group_offsets stays a host pointer); asynchronous except for the
+ * NaN / skip check, which synchronises the context's stream before returning. */
+int blissgpu_group_knn_device(blissgpu_ctx *ctx, const float *d_seeds, const uint64_t *group_offsets, uint64_t n_groups,
+                              const float *d_cand, uint64_t n, uint32_t d, int metric, const float *d_M,
+                              const uint32_t *d_skip, uint32_t k, uint32_t *d_idx, float *d_dist);
+/* How the two entry points above deal out the work for a device of n_cus compute units (>= 1): device-free.  Items are
+ * rectangles, groups [g_lo, g_hi) x candidates [c_lo, c_hi), written as items[i][4] = g_lo, g_hi, c_lo, c_hi; they tile the
+ * n_groups x n plane exactly once and c_lo is a multiple of *cand_block (the candidates of one staged block).  *seed_tile is
+ * the most seed rows of one group held in LDS at once; a larger group streams through it without restarting its sum.  An
+ * item's cost is (seeds of its groups) x (its candidates); no item costs more than
+ * max(total cost / n_cus, cand_block x largest group) -- a group's sum cannot be split over workgroups without changing its
+ * order, so one block of one group is the smallest unit.  *n_items is always written; nothing is written past max_items. */
+int blissgpu_group_knn_plan(const uint64_t *group_offsets, uint64_t n_groups, uint64_t n, uint32_t k, uint32_t n_cus,
+                            uint32_t *items, uint64_t max_items, uint64_t *n_items, uint32_t *cand_block,
+                            uint32_t *seed_tile);
+
 /* ---- duplicate songs of a whole collection ----
  * The duplicate rule of dedup_playlist_custom_distance (src/playlist.rs:381-388) applied to EVERY pair of the n x d matrix x
  * instead of the neighbours of an ordered playlist: the pair (i, j), i < j, is an edge when D[i][j] < threshold (D[i][j] is bit
