@@ -69,6 +69,12 @@ static void fft_free(bo_fft *p) {
 static int g_fft_double = 0;
 void bo_set_fft_double(int on) { g_fft_double = on; }
 
+/* tests only: the three expf calls of beattracking_checkstate as (float)exp((double)x), the correctly rounded form the
+ * device evaluates.  Off (the default) is the reference's expf. */
+static int g_exp_via_double = 0;
+void bo_set_exp_via_double(int on) { g_exp_via_double = on; }
+static float checkstate_expf(float x) { return g_exp_via_double ? (float)exp((double)x) : expf(x); }
+
 static void fft_forward_f64(const bo_fft *p, float *re32, float *im32) {
     const size_t n = p->n;
     double *re = (double *)malloc(sizeof(double) * n), *im = (double *)malloc(sizeof(double) * n);
@@ -911,7 +917,7 @@ static void beattracking_checkstate(bo_beattracking *b) {
         b->timesig = get_timesig(b->acf, acflen, (size_t)gp);
         for (size_t j = 0; j < laglen; j++) {
             const float diff = (float)(j + 1) - gp;
-            b->gwv[j] = expf(-0.5f * diff * diff / (b->g_var * b->g_var));
+            b->gwv[j] = checkstate_expf(-0.5f * diff * diff / (b->g_var * b->g_var));
         }
         bp = gp;
         for (size_t j = 0; j < 2 * laglen; j++) b->phwv[j] = 1.0f;
@@ -920,7 +926,7 @@ static void beattracking_checkstate(bo_beattracking *b) {
         if ((float)step > b->lastbeat) {
             for (size_t j = 0; j < 2 * laglen; j++) {
                 const float diff = 1.0f + (float)j - (float)step + b->lastbeat;
-                b->phwv[j] = expf(-0.5f * diff * diff / (bp / 8.0f));
+                b->phwv[j] = checkstate_expf(-0.5f * diff * diff / (bp / 8.0f));
             }
         } else {
             for (size_t j = 0; j < 2 * laglen; j++) b->phwv[j] = 1.0f;
@@ -1005,6 +1011,7 @@ struct bo_bpm_desc {
     long blockpos;
     size_t winlen, step, hop_size;
     fvec bpms, onset_series, thresholded_series;
+    fvec runs; /* BO_RUN_STRIDE floats per beattracking_do, see bo_bpm_desc_runs */
 };
 
 bo_bpm_desc *bo_bpm_desc_new(uint32_t sr) {
@@ -1026,19 +1033,17 @@ bo_bpm_desc *bo_bpm_desc_new(uint32_t sr) {
     return d;
 }
 
-/* Tempo::do_ :1378-1443 followed by BPMDesc::do_ (src/temporal.rs:50-58) */
-void bo_bpm_desc_do(bo_bpm_desc *d, const float *chunk, size_t chunk_len) {
+/* Tempo::do_ :1378-1443 from the onset value on, followed by BPMDesc::do_ (src/temporal.rs:50-58) */
+static void bpm_desc_step(bo_bpm_desc *d, const float *chunk, size_t chunk_len, float of) {
     const size_t winlen = d->winlen, step = d->step;
-    pvoc_spectrum(&d->pv, chunk);
-    pvoc_norms_full(&d->pv, d->norm);
-    float of = 0.0f; /* SpecFlux :455-467 */
-    for (size_t j = 0; j < 257; j++) {
-        if (d->norm[j] > d->oldmag[j]) of += d->norm[j] - d->oldmag[j];
-        d->oldmag[j] = d->norm[j];
-    }
     fvec_push(&d->onset_series, of);
     if (d->blockpos == (long)step - 1) {
         beattracking_do(&d->bt, d->dfframe, d->out);
+        /* the per-run trace (BO_RUN_* order); the last slot counts this run's pushes to bpms */
+        const bo_beattracking *b = &d->bt;
+        const float rec[BO_RUN_STRIDE] = {beattracking_get_bpm(b), b->rp, b->gp, b->bp, (float)b->timesig, (float)b->flagstep,
+                                          (float)b->counter, b->lastbeat, d->out[0], 0.0f};
+        for (size_t i = 0; i < BO_RUN_STRIDE; i++) fvec_push(&d->runs, rec[i]);
         for (size_t i = 0; i < winlen - step; i++) d->dfframe[i] = d->dfframe[i + step];
         for (size_t i = winlen - step; i < winlen; i++) d->dfframe[i] = 0.0f;
         d->blockpos = -1;
@@ -1057,8 +1062,25 @@ void bo_bpm_desc_do(bo_bpm_desc *d, const float *chunk, size_t chunk_len) {
             if (is_silence(chunk, chunk_len, d->silence)) tempo_out = 0.0f;
         }
     }
-    if (tempo_out > 0.0f) fvec_push(&d->bpms, beattracking_get_bpm(&d->bt));
+    if (tempo_out > 0.0f) {
+        fvec_push(&d->bpms, beattracking_get_bpm(&d->bt));
+        d->runs.v[d->runs.n - 1] += 1.0f; /* a beat implies out[0] > 1, so a run has been traced */
+    }
 }
+
+void bo_bpm_desc_do(bo_bpm_desc *d, const float *chunk, size_t chunk_len) {
+    pvoc_spectrum(&d->pv, chunk);
+    pvoc_norms_full(&d->pv, d->norm);
+    float of = 0.0f; /* SpecFlux :455-467 */
+    for (size_t j = 0; j < 257; j++) {
+        if (d->norm[j] > d->oldmag[j]) of += d->norm[j] - d->oldmag[j];
+        d->oldmag[j] = d->norm[j];
+    }
+    bpm_desc_step(d, chunk, chunk_len, of);
+}
+
+/* replay: the chain after SpecFlux on the caller's onset value; the chunk still feeds is_silence */
+void bo_bpm_desc_do_onset(bo_bpm_desc *d, const float *chunk, size_t chunk_len, float onset) { bpm_desc_step(d, chunk, chunk_len, onset); }
 
 static int cmp_f32(const void *a, const void *b) {
     const float x = *(const float *)a, y = *(const float *)b;
@@ -1080,6 +1102,7 @@ float bo_bpm_desc_get_value(bo_bpm_desc *d) {
 }
 
 size_t bo_bpm_desc_bpms(bo_bpm_desc *d, const float **bpms) { if (bpms) *bpms = d->bpms.v; return d->bpms.n; }
+size_t bo_bpm_desc_runs(bo_bpm_desc *d, const float **records, size_t *stride) { *records = d->runs.v; *stride = BO_RUN_STRIDE; return d->runs.n / BO_RUN_STRIDE; }
 size_t bo_bpm_desc_series(bo_bpm_desc *d, const float **onset, const float **thresholded) {
     if (onset) *onset = d->onset_series.v;
     if (thresholded) *thresholded = d->thresholded_series.v;
@@ -1090,7 +1113,7 @@ void bo_bpm_desc_free(bo_bpm_desc *d) {
     if (!d) return;
     pvoc_release(&d->pv);
     beattracking_release(&d->bt);
-    free(d->dfframe); free(d->out); free(d->bpms.v); free(d->onset_series.v); free(d->thresholded_series.v);
+    free(d->dfframe); free(d->out); free(d->bpms.v); free(d->onset_series.v); free(d->thresholded_series.v); free(d->runs.v);
     free(d);
 }
 

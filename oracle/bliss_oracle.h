@@ -78,6 +78,14 @@ float bo_bpm_desc_get_value(bo_bpm_desc *d);
 size_t bo_bpm_desc_bpms(bo_bpm_desc *d, const float **bpms);
 /* debug taps for stage-by-stage parity: onset (specflux) and thresholded series so far */
 size_t bo_bpm_desc_series(bo_bpm_desc *d, const float **onset, const float **thresholded);
+/* replay (tests): Tempo::do_ from the onset value on -- peak picker, beat tracker, BPMDesc -- fed the caller's SpecFlux
+ * value in place of the phase vocoder's; the chunk is read by is_silence only */
+void bo_bpm_desc_do_onset(bo_bpm_desc *d, const float *chunk, size_t chunk_len, float onset);
+/* per-run trace: one record of BO_RUN_STRIDE floats after every BeatTracking::do_, the tracker's state as that run left
+ * it; `count` is the number of values this run pushed to bpms (beats found in the frames that followed it) */
+enum { BO_RUN_BPM, BO_RUN_RP, BO_RUN_GP, BO_RUN_BP, BO_RUN_TIMESIG, BO_RUN_FLAGSTEP, BO_RUN_COUNTER, BO_RUN_LASTBEAT,
+       BO_RUN_NBEATS, BO_RUN_COUNT, BO_RUN_STRIDE };
+size_t bo_bpm_desc_runs(bo_bpm_desc *d, const float **records, size_t *stride);
 void bo_bpm_desc_free(bo_bpm_desc *d);
 
 void bo_loudness(const float *x, size_t n, int chunks_exact, float out[2]); /* src/misc.rs:39-71 */
@@ -138,6 +146,8 @@ void bo_white_noise(uint32_t song_index, size_t n, float *out);
 
 /* tests only: evaluate every FFT in f64 (rounded to f32 once) to measure FFT-rounding sensitivity */
 void bo_set_fft_double(int on);
+/* tests only: checkstate's Gaussian weights (gwv, phwv) as (float)exp((double)x) instead of expf(x) */
+void bo_set_exp_via_double(int on);
 
 #ifdef __cplusplus
 }

@@ -71,6 +71,8 @@ def lib():
             "bo_bpm_desc_get_value": (C.c_float, [C.c_void_p]),
             "bo_bpm_desc_bpms": (sz, [C.c_void_p, C.POINTER(f32p)]),
             "bo_bpm_desc_series": (sz, [C.c_void_p, C.POINTER(f32p), C.POINTER(f32p)]),
+            "bo_bpm_desc_do_onset": (None, [C.c_void_p, f32p, sz, C.c_float]),
+            "bo_bpm_desc_runs": (sz, [C.c_void_p, C.POINTER(f32p), C.POINTER(sz)]),
             "bo_bpm_desc_free": (None, [C.c_void_p]),
             "bo_loudness": (None, [f32p, sz, C.c_int, f32p]),
             "bo_zcr": (C.c_float, [f32p, sz]),
@@ -95,6 +97,7 @@ def lib():
             "bo_decode_to_mono": (C.c_uint64, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, f32p]),
             "bo_white_noise": (None, [C.c_uint32, sz, f32p]),
             "bo_set_fft_double": (None, [C.c_int]),
+            "bo_set_exp_via_double": (None, [C.c_int]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -313,6 +316,26 @@ class BPMDesc:
                 fn(self._h, C.cast(base + 4 * s, C.POINTER(C.c_float)), 256)
         return self
 
+    def run_onsets(self, x, onset):
+        """Replay (analyze framing): frame t is the chunk x[256t : 256t+512] with onset[t] in place of its SpecFlux value."""
+        x, onset = _f32(x), _f32(onset)
+        assert len(onset) == (max(0, (len(x) - 512) // 256 + 1) if len(x) >= 512 else 0), (len(x), len(onset))
+        base = x.ctypes.data
+        fn = lib().bo_bpm_desc_do_onset
+        for t in range(len(onset)):
+            fn(self._h, C.cast(base + 4 * 256 * t, C.POINTER(C.c_float)), 512, float(onset[t]))
+        return self
+
+    RUN_FIELDS = ("bpm", "rp", "gp", "bp", "timesig", "flagstep", "counter", "lastbeat", "nbeats", "count")
+
+    def runs(self):
+        """One record per BeatTracking::do_ (bo_bpm_desc_runs): a structured float32 array with RUN_FIELDS."""
+        p, stride = C.POINTER(C.c_float)(), C.c_size_t()
+        n = lib().bo_bpm_desc_runs(self._h, C.byref(p), C.byref(stride))
+        assert stride.value == len(self.RUN_FIELDS)
+        a = np.ctypeslib.as_array(p, shape=(n, stride.value)).copy() if n else np.empty((0, stride.value), np.float32)
+        return np.rec.fromarrays(a.T, names=self.RUN_FIELDS)
+
     def get_value(self):
         return float(lib().bo_bpm_desc_get_value(self._h))
 
@@ -513,6 +536,11 @@ def white_noise(song_index, n):
 def set_fft_double(on):
     """tests only: FFTs evaluated in f64 then rounded -- measures sensitivity to FFT rounding"""
     lib().bo_set_fft_double(int(bool(on)))
+
+
+def set_exp_via_double(on):
+    """tests only: checkstate's three expf calls as (float)exp((double)x), the device's exp_f32; off = the reference's expf"""
+    lib().bo_set_exp_via_double(int(bool(on)))
 
 
 # ---- the decoder's conversion to mono 22 050 Hz f32 (libswresample as FFmpegDecoder drives it, ffmpeg.rs:36-109) ----

@@ -13,6 +13,9 @@ error.  Here every frame of every tap is held to a reference of its own:
   4. the FFT-512 series at every framing / tiling boundary length, frame by frame
   5. songs stay inside their bounds: odd offsets, NaN (or -32768) gaps, adjacent and overlapping songs give the same
      rows and taps, bit for bit, as the aligned zero-gap layout
+  6. the tempo chain, free of FFT rounding: the oracle's peak picker, beat tracker and median replayed on the device's OWN
+     flux tap must give the device's thresholded series, every run's bpm and beat count and the tempo feature bit for bit
+     (the CPU tests of the section pin the replay, the per-run trace and what the song set reaches)
 
 The CPU tests (no marker) run in the default `-m "not gpu"` pass; the GPU tests are marked one by one.
 """
@@ -549,3 +552,333 @@ def test_songs_stay_inside_their_bounds(bliss, oracle):
     assert dctx.staged_bytes() > before, "the batch did not go through the staging ring"
     for i in range(n):
         assert np.array_equal(outh[i].view(np.uint32), ref[i].view(np.uint32)), f"host f32 song {i} (offset {offs[i]}): row differs"
+
+
+# ---------------------------------------------------------------------------------------------
+# 6. the tempo chain on the device's own flux
+# ---------------------------------------------------------------------------------------------
+# Everything after SpecFlux (onset_kernel, beat_acf_kernel, beat_track_kernel) is written to round like the reference, so
+# the oracle's chain fed the device's flux tap must reproduce the device's taps exactly.  No tolerance appears below: the
+# only f32 operations whose rounding is not pinned by IEEE 754 are the three expf calls of checkstate, which the device
+# evaluates as (float)exp((double)x); the oracle is switched to the same form (set_exp_via_double) and the reference's expf
+# is measured beside it.
+BT_STEP = 128
+TRACE = ("rp", "gp", "bp", "timesig", "flagstep", "counter", "lastbeat")
+TEMPO_BOUNDARY_NB = (127, 128, 129, 255, 256, 257, 511, 512, 513, 639, 640, 641)   # first run; padded frames 0..3; m >= 4
+TEMPO_CHUNK_LIMIT = 64 << 20   # 0.2 MB of scratch per second of audio: the set (~ 760 s) is cut into three or more chunks
+
+
+def _clicks(rng, n, bpm, amp=0.8, accent=0, floor=0.0):
+    """n samples of 60-sample uniform noise bursts at `bpm`; with accent = k every beat but each k-th has half the amplitude;
+    floor: amplitude of a uniform noise bed (0 = digital silence between the clicks)"""
+    x = rng.uniform(-floor, floor, n) if floor else np.zeros(n)
+    period = 60.0 / bpm * SR
+    for k in range(int(n / period) + 1):
+        a = int(round(k * period))
+        m = min(60, n - a)
+        if m <= 0:
+            break
+        x[a:a + m] = rng.uniform(-amp, amp, 60)[:m] * (0.5 if accent and k % accent else 1.0)
+    return x.astype(np.float32)
+
+
+def tempo_songs(oracle, golden_pcm):
+    rng = np.random.default_rng(60606)
+    n40 = 40 * SR
+    songs = {}
+    for bpm, accent in ((60, 0), (90, 3), (120, 4), (140, 0), (192, 3), (250, 4)):
+        songs[f"click_{bpm}" + (f"_accent{accent}" if accent else "")] = _clicks(rng, n40, bpm, accent=accent)
+    songs["change_120_to_90"] = np.concatenate([_clicks(rng, n40 // 2, 120), _clicks(rng, n40 // 2, 90)])
+    songs["change_100_to_160"] = np.concatenate([_clicks(rng, n40 // 2, 100, accent=4), _clicks(rng, n40 // 2, 160, accent=4)])
+    z = np.zeros(10 * SR, np.float32)
+    songs["silence_clicks_silence"] = np.concatenate([z, _clicks(rng, 20 * SR, 120), z])
+    loud = _clicks(rng, n40 // 2, 120)
+    songs["loud_then_quiet"] = np.concatenate([loud, loud * np.float32(2e-6 / 0.8)])
+    songs["noise"] = (0.3 * rng.standard_normal(n40)).astype(np.float32)
+    # found by mutating the oracle (a period below 25 frames that is not noise; a phase comb that needs its last tooth; the
+    # two thresholds of the lock): songs on which a changed constant of checkstate / the phase comb changes a run
+    songs["click_211"] = _clicks(rng, n40, 211)
+    r2 = np.random.default_rng(102)
+    songs["medley"] = np.concatenate([_clicks(r2, int(r2.integers(6, 12)) * SR, float(r2.uniform(55, 230)),
+                                              accent=int(r2.choice([0, 3, 4]))) for _ in range(4)])
+    t = np.arange(n40)
+    songs["am_noise"] = (0.15 * (1.1 + np.sin(2 * np.pi * t / (120 * 256.0))) * rng.uniform(-1, 1, n40)).astype(np.float32)
+    songs["am_tone"] = (0.2 * (1.1 + np.sin(2 * np.pi * t / (90 * 256.0))) * np.sin(2 * np.pi * 1000.0 * t / SR)).astype(np.float32)
+    songs["long_click_110"] = _clicks(rng, 104 * SR, 110, accent=4)      # 8957 tempo frames, 69 runs
+    songs["short_no_run"] = _clicks(rng, 20000, 120, floor=0.01)         # 77 tempo frames
+    songs["silence"] = np.zeros(10 * SR, np.float32)
+    songs["dc"] = np.full(10 * SR, 0.25, np.float32)
+    songs["white_noise"] = oracle.white_noise(9600, n40)
+    songs["golden"] = golden_pcm
+    for n_b in TEMPO_BOUNDARY_NB:
+        for r in (0, 100, 255):
+            songs[f"nb_{n_b}+{r}"] = _clicks(rng, 256 * (n_b - 1) + 512 + r, 120, floor=0.01)
+    return songs
+
+
+def _n_b(x):
+    return (len(x) - 512) // 256 + 1
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(a.dtype.str.replace("f", "u"))
+
+
+def _same(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
+
+
+def _chain(d):
+    """What a BPMDesc holds after a run: (thresholded, bpms, value, runs)"""
+    return d.series()[1], d.bpms(), d.get_value(), d.runs()
+
+
+def _same_runs(a, b):
+    return a.dtype == b.dtype and all(_same(a[k], b[k]) for k in a.dtype.names)
+
+
+@pytest.fixture(scope="module")
+def tempo_set(oracle, golden_pcm):
+    """(songs, {song: (flux, thresholded, bpms, value, runs)} of the oracle's own analysis), computed once"""
+    oracle.set_exp_via_double(False)
+    songs = tempo_songs(oracle, golden_pcm)
+    own = {}
+    for k, x in songs.items():
+        d = oracle.BPMDesc().run(x)
+        own[k] = (d.series()[0],) + _chain(d)
+    return songs, own
+
+
+def test_tempo_replay_reproduces_the_oracle(oracle, tempo_set):
+    """Fed its own SpecFlux series, the replay entry point is the oracle: thresholded, bpms, value and the trace bit for bit."""
+    songs, own = tempo_set
+    for k, x in songs.items():
+        flux, thr, bpms, value, runs = own[k]
+        assert len(flux) == _n_b(x), k
+        r_thr, r_bpms, r_value, r_runs = _chain(oracle.BPMDesc().run_onsets(x, flux))
+        assert _same(r_thr, thr) and _same(r_bpms, bpms), k
+        assert _same(np.float32(r_value), np.float32(value)), (k, r_value, value)
+        assert _same_runs(r_runs, runs), k
+
+
+def test_tempo_trace_is_consistent(tempo_set):
+    """The trace's bpm and count columns are the bpms series run by run, and there is one record per 128 tempo frames."""
+    songs, own = tempo_set
+    for k, x in songs.items():
+        _, _, bpms, value, runs = own[k]
+        n_b = _n_b(x)
+        assert len(runs) == ((n_b - BT_STEP) // BT_STEP + 1 if n_b >= BT_STEP else 0), (k, n_b, len(runs))
+        count = runs.count.astype(np.int64)
+        assert (count == runs.count).all() and int(count.sum()) == len(bpms), (k, count.sum(), len(bpms))
+        assert _same(np.repeat(runs.bpm, count), bpms), k
+        assert (value == -1.0) == (len(bpms) == 0), (k, value)
+
+
+def _locks(runs):
+    """Runs in which checkstate locked onto a new period (flagconst): the counter went from 1 straight to 0"""
+    return np.flatnonzero((runs.counter[1:] == 0) & (runs.counter[:-1] == 1)) + 1
+
+
+def test_tempo_song_set_reaches_the_chain(tempo_set):
+    """Conditions on the oracle alone, so that the device test cannot pass on a degenerate set.
+
+    `bp == 0` (a run_bpm of 0) is NOT among them: it cannot occur.  The Rayleigh period rp is either the interpolated
+    position of a maximum at lag 1 .. 126 (at least 0.5: the last index attaining the maximum is taken, so the parabola's
+    offset lies within half a lag) or rayparam = 43; the Gaussian-weighted period gp is taken from comb sums whose last
+    entry is always (+-)0.0 (the comb loop stops at lag 126), so its maximum search never falls through to index 0 with
+    gp == 0; and the doubling loop only raises bp.  A song in which no beat is ever found (silence: rp = 43 in every run)
+    therefore has run_bpm = 60 / (256 * 43 / 22050) = 120.18 until the tracker locks (onto 43, then onto the last lag, 127:
+    40.69), with a count of 0 in every run, and the value -1."""
+    songs, own = tempo_set
+    all_runs = np.concatenate([own[k][4] for k in songs if len(own[k][4])]).view(np.recarray)
+    assert (all_runs.bp > 0).all() and (all_runs.bpm > 0).all()
+    silent = own["silence"][4]
+    assert (silent.bpm[silent.timesig == 0] == np.float32(60.0) / (np.float32(256.0 * 43.0) / np.float32(22050.0))).all()
+    assert (silent.rp == 43.0).all() and (silent.nbeats > 1).all() and not silent.count.any()
+    assert {0, 3, 4} <= set(all_runs.timesig.astype(int).tolist())
+    two_locks, gaussian, doubled = [], [], []
+    for k in songs:
+        runs = own[k][4]
+        if not len(runs):
+            continue
+        locks = _locks(runs)
+        if len(locks) >= 2 and (runs.flagstep == 1).any():
+            two_locks.append(k)
+        lock = np.zeros(len(runs), bool)
+        lock[locks] = True
+        prev_lastbeat = np.concatenate([[np.float32(0.0)], runs.lastbeat[:-1]])
+        if ((runs.timesig > 0) & ~lock & (prev_lastbeat < BT_STEP)).any():
+            gaussian.append(k)
+        source = np.where(runs.timesig > 0, runs.gp, runs.rp)   # what checkstate assigns to bp before the doubling loop
+        assert ((source >= 25.0) <= (runs.bp == source)).all(), k
+        if (source < 25.0).any():
+            assert (runs.bp[source < 25.0] >= 25.0).all(), k
+            doubled.append(k)
+    print(f"two locks: {two_locks}\ngaussian phase weight: {len(gaussian)} songs, doubled period: {doubled}")
+    assert "change_120_to_90" in two_locks or "change_100_to_160" in two_locks, two_locks
+    assert gaussian and doubled
+    assert len(own["silence"][4]) > 0 and len(own["silence"][2]) == 0 and own["silence"][3] == -1.0
+    assert len(own["short_no_run"][4]) == 0 and own["short_no_run"][3] == -1.0 and _n_b(songs["short_no_run"]) < BT_STEP
+    assert {len(own[k][2]) % 2 for k in songs if len(own[k][2])} == {0, 1}, "both Midpoint-median cases"
+    # beats in windows that is_silence drops: the quiet half has beats in its runs' output but none recorded
+    runs = own["loud_then_quiet"][4]
+    half = len(runs) // 2
+    assert runs.count[:half].sum() > 0 and (runs.nbeats[half + 4:-1] > 1).all() and runs.count[half + 4:].sum() == 0, runs
+    assert 0.3 * runs.count[:half].sum() < len(own["loud_then_quiet"][2]) / 2 < runs.count[:half].sum()
+    assert len(own["long_click_110"][4]) > 64 and len(songs["long_click_110"]) >= 100 * SR
+
+
+def test_tempo_windows_are_clear_of_the_silence_threshold(tempo_set):
+    """The device sums a window's level from its two energy256 blocks, the reference sequentially over 512 samples: the test
+    must not depend on which side of -90 dB (1e-9) a rounding puts a window.  Every tempo window's level, in float64, is
+    exactly 0 or a factor of 10 in power away from the threshold -- every window from 127 on, that is: is_silence is
+    evaluated only where a beat of a finished run falls, and the first run happens at window 127 (the reference's
+    recording fades in through the threshold in its windows 0 and 1, which nothing reads)."""
+    songs, _ = tempo_set
+    for k, x in songs.items():
+        n_b = _n_b(x)
+        e = np.add.reduceat(x.astype(np.float64) ** 2, np.arange(0, len(x), 256))
+        level = (e[:n_b] + e[1:n_b + 1]) / 512.0
+        bad = np.flatnonzero((level != 0.0) & (level >= 1e-10) & (level <= 1e-8))
+        bad = bad[bad >= BT_STEP - 1]
+        assert not len(bad), f"{k}: window {bad[0]} has level {level[bad[0]]:.3g}"
+
+
+def test_tempo_set_is_clear_of_expf_rounding(oracle, tempo_set):
+    """(float)exp((double)x) and expf(x) give the same chain on the oracle's own flux for every song of the set, so a
+    difference between the two replays of the device test is about the device's flux, not about the set."""
+    songs, own = tempo_set
+    oracle.set_exp_via_double(True)
+    try:
+        for k, x in songs.items():
+            flux, thr, bpms, value, runs = own[k]
+            _, r_bpms, r_value, r_runs = _chain(oracle.BPMDesc().run_onsets(x, flux))
+            assert _same_runs(r_runs, runs) and _same(r_bpms, bpms), k
+            assert _same(np.float32(r_value), np.float32(value)), (k, r_value, value)
+    finally:
+        oracle.set_exp_via_double(False)
+
+
+def _record(runs, m):
+    return "{" + ", ".join(f"{f} {runs[f][m]!r}" for f in ("bpm",) + TRACE + ("nbeats", "count")) + "}"
+
+
+def _first_run_difference(run_bpm, run_count, runs):
+    """-> None, or (run, description with the oracle's trace of that run and the one before)"""
+    n = min(len(run_bpm), len(runs))
+    diff = (_bits(run_bpm[:n]) != _bits(runs.bpm[:n])) | (run_count[:n] != runs.count[:n].astype(np.int64))
+    if len(run_bpm) == len(run_count) == len(runs) and not diff.any():
+        return None
+    if not diff.any():
+        return n, f"{len(run_bpm)} / {len(run_count)} device runs, the replay has {len(runs)}"
+    m = int(np.flatnonzero(diff)[0])
+    text = f"first differing run {m}: device bpm {run_bpm[m]!r} count {run_count[m]}, replay {_record(runs, m)}"
+    if m > 0:
+        text += f"; run {m - 1}: device bpm {run_bpm[m - 1]!r} count {run_count[m - 1]}, replay {_record(runs, m - 1)}"
+    return m, text
+
+
+def _check_tempo_chain(ctx, oracle, names, songs, rows, n_bpms, what):
+    """Replays the oracle's chain on the flux tap of every song whose taps can be fetched (those of the last chunk) and
+    demands the device's taps, feature 0 and bpm count bit for bit.  -> {song: (flux, thresholded, run_bpm, run_count, runs)}"""
+    from bliss_rs_amd import BlissGpuError
+
+    checked = {}
+    for i, k in enumerate(names):
+        try:
+            flux = ctx.debug_fetch("flux", i)
+        except BlissGpuError:   # not in the last chunk
+            continue
+        x = songs[k]
+        thr, run_bpm, run_count = (ctx.debug_fetch(t, i) for t in ("thresholded", "run_bpm", "run_count"))
+        assert len(flux) == len(thr) == _n_b(x), (what, k, len(flux), len(thr), _n_b(x))
+        r_thr, r_bpms, r_value, runs = _chain(oracle.BPMDesc().run_onsets(x, flux))
+        if not _same(thr, r_thr):
+            t = int(np.flatnonzero(_bits(thr) != _bits(r_thr))[0])
+            raise AssertionError(f"{what} {k}: thresholded frame {t} (run {max(0, t - 127) // 128}): device {thr[t]!r}, replay {r_thr[t]!r}")
+        bad = _first_run_difference(run_bpm, run_count, runs)
+        assert bad is None, f"{what} {k}: {bad[1]}"
+        assert _same(rows[i, 0], np.float32(r_value)), \
+            f"{what} {k}: tempo feature {rows[i, 0]!r}, replay {np.float32(r_value)!r} over {len(r_bpms)} bpms (taps equal)"
+        assert int(n_bpms[i]) == len(r_bpms), f"{what} {k}: n_bpms {n_bpms[i]}, replay {len(r_bpms)}"
+        checked[k] = (flux, thr, run_bpm, run_count, runs)
+    return checked
+
+
+def _analyze_tempo_set(ctx, names, songs):
+    rows, status = _run(ctx, [songs[k] for k in names])
+    assert (status == 0).all(), status
+    return rows, ctx.last_tuning(len(names))[1]
+
+
+@pytest.mark.gpu
+def test_tempo_chain_on_the_device_flux(bliss, oracle, tempo_set):
+    """Every song, every run, bit for bit, with the oracle's checkstate exponentials in the device's form; then the
+    reference's expf: the songs whose replay leaves the device are printed (expected: none) and held to TEMPO_TOL."""
+    from conftest import TEMPO_TOL
+
+    songs, _ = tempo_set
+    names = list(songs)
+    ctx = bliss.Context(0)
+    try:
+        rows, n_bpms = _analyze_tempo_set(ctx, names, songs)
+        oracle.set_exp_via_double(True)
+        checked = _check_tempo_chain(ctx, oracle, names, songs, rows, n_bpms, "default")
+        assert len(checked) == len(names) and ctx.last_chunks() == 1
+        n_runs = sum(len(v[4]) for v in checked.values())
+        print(f"tempo chain on the device's flux: {len(checked)} songs, {n_runs} runs, {int(n_bpms.sum())} beats, all bit for bit")
+        oracle.set_exp_via_double(False)
+        differing = []
+        for i, k in enumerate(names):
+            flux, thr, run_bpm, run_count, _ = checked[k]
+            r_thr, r_bpms, r_value, runs = _chain(oracle.BPMDesc().run_onsets(songs[k], flux))
+            assert _same(thr, r_thr), k   # (no exponential before the peak picker)
+            bad = _first_run_difference(run_bpm, run_count, runs)
+            if bad is not None or not _same(rows[i, 0], np.float32(r_value)):
+                differing.append(k)
+                print(f"reference expf, {k}: {bad[1] if bad else 'runs equal'}; feature {rows[i, 0]!r} vs {np.float32(r_value)!r}")
+                assert abs(float(rows[i, 0]) - r_value) <= TEMPO_TOL, (k, rows[i, 0], r_value)
+        print(f"reference expf: {len(differing)} of {len(names)} songs differ from the device: {differing}")
+    finally:
+        oracle.set_exp_via_double(False)
+        ctx.close()
+
+
+@pytest.mark.gpu
+def test_tempo_chain_options_do_not_change_a_bit(bliss, oracle, tempo_set):
+    """The same batch with SpecFlux in the reference's bin order, with the beat tracker forced before / after the FFT-8192
+    kernel and with the batch cut into chunks: each run's taps equal the replay of its OWN flux tap, and (flux_order aside,
+    which may round the flux differently) equal the default run's taps."""
+    songs, _ = tempo_set
+    names = list(songs)
+    oracle.set_exp_via_double(True)
+    try:
+        ctx = bliss.Context(0)
+        rows, n_bpms = _analyze_tempo_set(ctx, names, songs)
+        base = _check_tempo_chain(ctx, oracle, names, songs, rows, n_bpms, "default")
+        ctx.close()
+        assert len(base) == len(names)
+        for what, option, value in (("flux_order=1", "flux_order", 1), ("tail_mode=0", "tail_mode", 0),
+                                    ("tail_mode=1", "tail_mode", 1), ("chunked", None, None)):
+            c = bliss.Context(0)
+            if option:
+                c.set_option(option, value)
+            else:
+                c.set_workspace_limit(TEMPO_CHUNK_LIMIT)
+            r2, nb2 = _analyze_tempo_set(c, names, songs)
+            got = _check_tempo_chain(c, oracle, names, songs, r2, nb2, what)
+            if option:
+                assert len(got) == len(names) and c.last_chunks() == 1, (what, len(got), c.last_chunks())
+            else:
+                assert c.last_chunks() > 1 and 0 < len(got) < len(names), (c.last_chunks(), len(got))
+            if option != "flux_order":
+                assert _same(r2[:, 0], rows[:, 0]) and np.array_equal(nb2, n_bpms), what
+                for k, taps in got.items():
+                    for tap, a, b in zip(("flux", "thresholded", "run_bpm", "run_count"), taps, base[k]):
+                        assert _same(a, b), f"{what} {k}: tap {tap} differs from the default run's"
+            print(f"{what}: {len(got)} songs checked, {c.last_chunks()} chunk(s)")
+            c.close()
+    finally:
+        oracle.set_exp_via_double(False)
