@@ -152,6 +152,18 @@ pub mod sys {
         pub fn blissgpu_group_knn_device(ctx: *mut blissgpu_ctx, d_seeds: *const f32, group_offsets: *const u64, n_groups: u64,
                                          d_cand: *const f32, n: u64, d: u32, metric: c_int, d_m: *const f32, d_skip: *const u32, k: u32,
                                          d_idx: *mut u32, d_dist: *mut f32) -> c_int;
+        // one diagonal metric per seed group: variance_based_weight_matrix of every group, and the search under it
+        pub fn blissgpu_group_weights(seeds: *const f32, group_offsets: *const u64, n_groups: u64, d: u32, weights: *mut f32,
+                                      group_status: *mut i32) -> c_int;
+        pub fn blissgpu_group_weights_device(ctx: *mut blissgpu_ctx, d_seeds: *const f32, group_offsets: *const u64, n_groups: u64,
+                                             d: u32, d_weights: *mut f32, d_group_status: *mut i32) -> c_int;
+        pub fn blissgpu_group_knn_weighted(seeds: *const f32, group_offsets: *const u64, n_groups: u64, cand: *const f32, n: u64,
+                                           d: u32, weights: *const f32, skip: *const u32, k: u32, idx: *mut u32, dist: *mut f32,
+                                           group_status: *mut i32) -> c_int;
+        pub fn blissgpu_group_knn_weighted_device(ctx: *mut blissgpu_ctx, d_seeds: *const f32, group_offsets: *const u64,
+                                                  n_groups: u64, d_cand: *const f32, n: u64, d: u32, d_weights: *const f32,
+                                                  d_skip: *const u32, k: u32, d_idx: *mut u32, d_dist: *mut f32,
+                                                  d_group_status: *mut i32) -> c_int;
         pub fn blissgpu_duplicate_groups(x: *const f32, n: u64, d: u32, meta: *const u32, metric: c_int, m_matrix: *const f32,
                                          threshold: f32, label: *mut u32, n_pairs: *mut u64, pairs: *mut u32, pair_dist: *mut f32,
                                          max_pairs: u64) -> c_int;

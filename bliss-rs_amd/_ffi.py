@@ -93,6 +93,12 @@ SIGNATURES = {
                                             C.c_uint32, _vp, _vp]),
     "blissgpu_group_knn_plan": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _u64p, _u32p,
                                           _u32p]),
+    "blissgpu_group_weights": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp]),
+    "blissgpu_group_weights_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp]),
+    "blissgpu_group_knn_weighted": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp,
+                                              _vp]),
+    "blissgpu_group_knn_weighted_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, _vp, _vp,
+                                                     C.c_uint32, _vp, _vp, _vp]),
     "blissgpu_duplicate_groups": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.c_int, _vp, C.c_float, _vp, _u64p, _vp, _vp,
                                             C.c_uint64]),
     "blissgpu_duplicate_groups_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_int, _vp, C.c_float, _vp, _vp, _vp,

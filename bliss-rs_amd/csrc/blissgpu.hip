@@ -28,7 +28,7 @@ const char* const kKernelNames[K_COUNT] = {
     "dedup_next_kernel", "dedup_walk_kernel", "knn_scan_kernel", "knn_merge_kernel",
     "forest_walk_kernel", "forest_finish_kernel",
     "dup_init_kernel", "dup_join_kernel", "dup_flatten_kernel",
-    "group_knn_scan_kernel", "group_knn_merge_kernel"};
+    "group_knn_scan_kernel", "group_knn_merge_kernel", "group_weights_kernel"};
 }  // namespace
 
 namespace bg {
@@ -978,17 +978,19 @@ int blissgpu_group_knn_plan(const uint64_t* group_offsets, uint64_t n_groups, ui
     return BLISSGPU_OK;
 }
 
-int blissgpu_group_knn_device(blissgpu_ctx* c, const float* d_seeds, const uint64_t* group_offsets, uint64_t n_groups,
-                              const float* d_cand, uint64_t n, uint32_t d, int metric, const float* d_M, const uint32_t* d_skip,
-                              uint32_t k, uint32_t* d_idx, float* d_dist) {
-    const char* who = "blissgpu_group_knn_device";
-    int rc = group_knn_args_ok(who, d_seeds, group_offsets, n_groups, d_cand, n, d, metric, d_M, k, d_idx);
-    if (rc) return rc;
-    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
-    if (n_groups == 0) return BLISSGPU_OK;
-    CTX_ENTER(c, who);
+// both device forms after their argument checks.  weighted: the metric is Mahalanobis with one diagonal M per group, rows of
+// d_weights ([n_groups][d]) or, with d_weights == NULL, the variance-based weights of each group's own seeds, computed into
+// the workspace by one more launch; d_status (may be NULL) is then written
+static int group_knn_run(blissgpu_ctx* c, const char* who, const float* d_seeds, const uint64_t* group_offsets, uint64_t n_groups,
+                         const float* d_cand, uint64_t n, uint32_t d, int metric, const float* d_M, bool weighted,
+                         const float* d_weights, int32_t* d_status, const uint32_t* d_skip, uint32_t k, uint32_t* d_idx,
+                         float* d_dist) {
+    int rc;
     int diag = 0;
-    if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
+    if (weighted) {
+        metric = BLISSGPU_METRIC_MAHALANOBIS;
+        diag = GROUP_KNN_M_PER_GROUP;
+    } else if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
         if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
             diag = is_diag(c->m_cache.data(), d);
         } else {
@@ -1007,9 +1009,12 @@ int blissgpu_group_knn_device(blissgpu_ctx* c, const float* d_seeds, const uint6
     std::copy(plan.list_off.begin(), plan.list_off.end(), table.begin() + n_off);
     if (n_item_words) memcpy(table.data() + 2 * n_off, plan.items.data(), n_item_words * sizeof(uint32_t));
     const uint64_t n_lists = plan.list_off[n_groups];
+    // (derived weights: n_groups x d floats behind the lists)
+    const bool derive = weighted && !d_weights;
+    const size_t part_bytes = std::max<size_t>(8, (size_t)n_lists * k * sizeof(unsigned long long));
     rc = c->pl_sync.ensure(4);
     if (!rc) rc = c->pl_keys.ensure(table.size());
-    if (!rc) rc = c->pl_tmp.ensure(std::max<size_t>(8, (size_t)n_lists * k * sizeof(unsigned long long)));
+    if (!rc) rc = c->pl_tmp.ensure(part_bytes + (derive ? (size_t)n_groups * d * sizeof(float) : 0));
     if (rc) return rc;
     const uint32_t *d_goff = c->pl_keys.p, *d_list_off = d_goff + n_off;
     const GroupKnnItem* d_items = reinterpret_cast<const GroupKnnItem*>(d_list_off + n_off);
@@ -1017,6 +1022,18 @@ int blissgpu_group_knn_device(blissgpu_ctx* c, const float* d_seeds, const uint6
     HIP_TRY(hipMemcpyAsync(c->pl_keys.p, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     // pl_sync: [1] NaN among the scores of eligible pairs, [3] a skip entry >= n
     HIP_TRY(hipMemsetAsync(c->pl_sync.p, 0, 4 * sizeof(uint32_t), c->stream));
+    if (derive) {
+        float* w = reinterpret_cast<float*>(c->pl_tmp.p + part_bytes);
+        {
+            Prof p(c, K_GROUP_WEIGHTS);
+            launch_group_weights(d_seeds, d_goff, n_groups, d, w, d_status, c->stream);
+        }
+        HIP_TRY(hipGetLastError());
+        d_M = w;
+    } else if (weighted) {
+        if (d_status) HIP_TRY(hipMemsetAsync(d_status, 0, (size_t)n_groups * sizeof(int32_t), c->stream));  // BLISSGPU_GROUP_OK
+        d_M = d_weights;
+    }
     {
         Prof p(c, K_GROUP_KNN_SCAN);
         launch_group_knn_scan(d_seeds, d_goff, d_cand, (uint32_t)n, d, metric, d_M, diag, d_skip, k, plan, d_items, d_list_off,
@@ -1034,6 +1051,19 @@ int blissgpu_group_knn_device(blissgpu_ctx* c, const float* d_seeds, const uint6
     if (flags[3]) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
     if (flags[1]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance (the reference panics here)");
     return BLISSGPU_OK;
+}
+
+int blissgpu_group_knn_device(blissgpu_ctx* c, const float* d_seeds, const uint64_t* group_offsets, uint64_t n_groups,
+                              const float* d_cand, uint64_t n, uint32_t d, int metric, const float* d_M, const uint32_t* d_skip,
+                              uint32_t k, uint32_t* d_idx, float* d_dist) {
+    const char* who = "blissgpu_group_knn_device";
+    int rc = group_knn_args_ok(who, d_seeds, group_offsets, n_groups, d_cand, n, d, metric, d_M, k, d_idx);
+    if (rc) return rc;
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    if (n_groups == 0) return BLISSGPU_OK;
+    CTX_ENTER(c, who);
+    return group_knn_run(c, who, d_seeds, group_offsets, n_groups, d_cand, n, d, metric, d_M, false, nullptr, nullptr, d_skip, k,
+                         d_idx, d_dist);
 }
 
 int blissgpu_group_knn(const float* seeds, const uint64_t* group_offsets, uint64_t n_groups, const float* cand, uint64_t n,
@@ -1072,6 +1102,141 @@ int blissgpu_group_knn(const float* seeds, const uint64_t* group_offsets, uint64
         if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(group_knn)", hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+// ---- one diagonal metric per seed group: variance_based_weight_matrix (src/playlist.rs:173-221) of every group on the device,
+// and the k-nearest search per group under M_g = diag(weights[g]) ----
+static int group_weights_args_ok(const char* who, const void* seeds, const uint64_t* off, uint64_t n_groups, uint32_t d,
+                                 const void* weights) {
+    const float some = 0.0f;  // (no candidates, no k, no metric here)
+    int rc = group_knn_args_ok(who, seeds, off, n_groups, &some, 0, d, BLISSGPU_METRIC_EUCLIDEAN, nullptr, 1, &some);
+    if (rc) return rc;
+    if (n_groups && !weights) return fail(BLISSGPU_ERR_INVALID, who, "weights is NULL");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_group_weights_device(blissgpu_ctx* c, const float* d_seeds, const uint64_t* group_offsets, uint64_t n_groups,
+                                  uint32_t d, float* d_weights, int32_t* d_group_status) {
+    const char* who = "blissgpu_group_weights_device";
+    int rc = group_weights_args_ok(who, d_seeds, group_offsets, n_groups, d, d_weights);
+    if (rc) return rc;
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    if (n_groups == 0) return BLISSGPU_OK;
+    CTX_ENTER(c, who);
+    std::vector<uint32_t> goff((size_t)n_groups + 1);  // 32 bits: fewer than 2^32 seeds
+    for (size_t g = 0; g < goff.size(); g++) goff[g] = (uint32_t)group_offsets[g];
+    rc = c->pl_keys.ensure(goff.size());
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(c->pl_keys.p, goff.data(), goff.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    {
+        Prof p(c, K_GROUP_WEIGHTS);
+        launch_group_weights(d_seeds, c->pl_keys.p, n_groups, d, d_weights, d_group_status, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (the offsets have left the host)
+    return BLISSGPU_OK;
+}
+
+// the host forms' staging of weights and status: st_out holds [n_groups][d] floats, then n_groups status words
+static int stage_group_weights(blissgpu_ctx* c, uint64_t n_groups, uint32_t d, float** d_w, int32_t** d_status) {
+    const size_t w_bytes = (size_t)n_groups * d * sizeof(float);
+    int rc = c->st_out.ensure(w_bytes + (size_t)n_groups * sizeof(int32_t));
+    if (rc) return rc;
+    *d_w = reinterpret_cast<float*>(c->st_out.p);
+    *d_status = reinterpret_cast<int32_t*>(c->st_out.p + w_bytes);
+    return BLISSGPU_OK;
+}
+
+int blissgpu_group_weights(const float* seeds, const uint64_t* group_offsets, uint64_t n_groups, uint32_t d, float* weights,
+                           int32_t* group_status) {
+    const char* who = "blissgpu_group_weights";
+    int rc = group_weights_args_ok(who, seeds, group_offsets, n_groups, d, weights);
+    if (rc) return rc;
+    if (n_groups == 0) return BLISSGPU_OK;
+    const uint64_t n_seeds = group_offsets[n_groups];
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    float* d_w = nullptr;
+    int32_t* d_status = nullptr;
+    rc = c->st_a.ensure(std::max<size_t>(1, n_seeds * d));
+    if (!rc) rc = stage_group_weights(c, n_groups, d, &d_w, &d_status);
+    if (rc) return rc;
+    hipError_t e = hipSuccess;
+    if (n_seeds) e = hipMemcpyAsync(c->st_a.p, seeds, n_seeds * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(group_weights)", hipGetErrorString(e));
+    if (!rc) rc = blissgpu_group_weights_device(c, c->st_a.p, group_offsets, n_groups, d, d_w, d_status);
+    if (!rc) {
+        e = hipMemcpyAsync(weights, d_w, (size_t)n_groups * d * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && group_status)
+            e = hipMemcpyAsync(group_status, d_status, (size_t)n_groups * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(group_weights)", hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+int blissgpu_group_knn_weighted_device(blissgpu_ctx* c, const float* d_seeds, const uint64_t* group_offsets, uint64_t n_groups,
+                                       const float* d_cand, uint64_t n, uint32_t d, const float* d_weights,
+                                       const uint32_t* d_skip, uint32_t k, uint32_t* d_idx, float* d_dist,
+                                       int32_t* d_group_status) {
+    const char* who = "blissgpu_group_knn_weighted_device";
+    int rc = group_knn_args_ok(who, d_seeds, group_offsets, n_groups, d_cand, n, d, BLISSGPU_METRIC_EUCLIDEAN, nullptr, k, d_idx);
+    if (rc) return rc;
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    if (n_groups == 0) return BLISSGPU_OK;
+    CTX_ENTER(c, who);
+    return group_knn_run(c, who, d_seeds, group_offsets, n_groups, d_cand, n, d, BLISSGPU_METRIC_MAHALANOBIS, nullptr, true,
+                         d_weights, d_group_status, d_skip, k, d_idx, d_dist);
+}
+
+int blissgpu_group_knn_weighted(const float* seeds, const uint64_t* group_offsets, uint64_t n_groups, const float* cand,
+                                uint64_t n, uint32_t d, const float* weights, const uint32_t* skip, uint32_t k, uint32_t* idx,
+                                float* dist, int32_t* group_status) {
+    const char* who = "blissgpu_group_knn_weighted";
+    int rc = group_knn_args_ok(who, seeds, group_offsets, n_groups, cand, n, d, BLISSGPU_METRIC_EUCLIDEAN, nullptr, k, idx);
+    if (rc) return rc;
+    if (n_groups == 0) return BLISSGPU_OK;
+    const uint64_t n_seeds = group_offsets[n_groups];
+    if (skip)
+        for (uint64_t i = 0; i < n_seeds; i++)
+            if (skip[i] != 0xFFFFFFFFu && skip[i] >= n) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    const size_t out_n = (size_t)n_groups * k;
+    float* d_w = nullptr;
+    int32_t* d_status = nullptr;
+    rc = c->st_b.ensure(std::max<size_t>(1, n * d));
+    if (!rc) rc = c->st_a.ensure(std::max<size_t>(1, n_seeds * d));
+    if (!rc) rc = c->st_idx.ensure(out_n + (skip ? n_seeds : 0));
+    if (!rc && dist) rc = c->st_dist.ensure(out_n);
+    if (!rc) rc = stage_group_weights(c, n_groups, d, &d_w, &d_status);
+    if (rc) return rc;
+    uint32_t *d_idx = c->st_idx.p, *d_skip = skip ? c->st_idx.p + out_n : nullptr;
+    hipError_t e = hipSuccess;
+    if (n) e = hipMemcpyAsync(c->st_b.p, cand, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && n_seeds) e = hipMemcpyAsync(c->st_a.p, seeds, n_seeds * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && skip && n_seeds) e = hipMemcpyAsync(d_skip, skip, n_seeds * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && weights)
+        e = hipMemcpyAsync(d_w, weights, (size_t)n_groups * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(group_knn_weighted)", hipGetErrorString(e));
+    if (!rc)
+        rc = blissgpu_group_knn_weighted_device(c, c->st_a.p, group_offsets, n_groups, c->st_b.p, n, d, weights ? d_w : nullptr,
+                                                d_skip, k, d_idx, dist ? c->st_dist.p : nullptr, group_status ? d_status : nullptr);
+    if (!rc) {
+        e = hipMemcpyAsync(idx, d_idx, out_n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && group_status)
+            e = hipMemcpyAsync(group_status, d_status, (size_t)n_groups * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(group_knn_weighted)", hipGetErrorString(e));
     }
     (void)hipStreamSynchronize(c->stream);
     return rc;

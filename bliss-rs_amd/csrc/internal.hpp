@@ -119,6 +119,7 @@ enum KernelId : int {
     K_FOREST_WALK, K_FOREST_FINISH,  // isolation-forest scores (kernels_forest.hip)
     K_DUP_INIT, K_DUP_JOIN, K_DUP_FLATTEN,  // duplicate groups of a collection (kernels_duplicates.hip)
     K_GROUP_KNN_SCAN, K_GROUP_KNN_MERGE,    // k-nearest search per seed group (kernels_group_knn.hip)
+    K_GROUP_WEIGHTS,                        // variance-based weights of every seed group (kernels_group_knn.hip)
     K_COUNT
 };
 
@@ -245,6 +246,7 @@ void launch_knn_merge(const unsigned long long* part, uint64_t q, uint32_t k, co
 // k nearest candidates per seed GROUP (kernels_group_knn.hip): the groups x candidates plane dealt out in items, then the two
 // launches.  `part` holds list_off[n_groups] lists of k 64-bit keys; flags as for knn
 constexpr int GROUP_KNN_SEED_TILE = 32;  // the most seed rows of one group held in LDS at a time
+constexpr int GROUP_KNN_M_PER_GROUP = 2;  // m_is_diag of launch_group_knn_scan: M is [n_groups][d], row g = the diagonal of group g's M
 struct GroupKnnItem {
     uint32_t g_lo, g_hi;  // groups [g_lo, g_hi)
     uint32_t c_lo, c_hi;  // candidates [c_lo, c_hi): c_lo a multiple of the candidate block
@@ -263,6 +265,9 @@ void launch_group_knn_scan(const float* S, const uint32_t* goff, const float* X,
                            uint32_t* bad_flag, hipStream_t st);
 void launch_group_knn_merge(const unsigned long long* part, const uint32_t* list_off, uint64_t n_groups, uint32_t k,
                             const GroupKnnPlan& p, uint32_t* idx, float* dist, hipStream_t st);
+// W[g][0..d) = the diagonal of variance_based_weight_matrix of group g's seed rows, ones (status 1) under two seeds; status may be NULL
+void launch_group_weights(const float* S, const uint32_t* goff, uint64_t n_groups, uint32_t d, float* W, int32_t* status,
+                          hipStream_t st);
 // duplicate groups (kernels_duplicates.hip): the split of the triangle of tile pairs for n rows, then the three launches.
 // `label` doubles as the union-find's parent array; *n_pairs counts the edges, *cursor hands out pair-list slots (both zeroed
 // by the init launch); a NaN distance of a pair i < j sets *nan_flag

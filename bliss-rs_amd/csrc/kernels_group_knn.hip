@@ -24,6 +24,11 @@
 //   group_knn_merge_kernel  a wavefront per group: its list_off[g + 1] - list_off[g] partial lists through the same threshold
 //                           buffer, then keys -> (index, score) with the 0xFFFFFFFF / +inf padding.
 //
+//   group_weights_kernel   the per-group metric (blissgpu_group_knn_weighted with weights == NULL): variance_based_weight_matrix
+//                           (src/playlist.rs:173-221) of every group's own seeds, a wavefront per group, lane j owning
+//                           dimension j.  The scan's PERGROUP form then takes the diagonal of M from row g of that array
+//                           (or of the caller's) each time a wavefront turns to its next group.
+//
 // group_knn_plan deals the groups x candidates plane out in items of bounded cost (seeds x candidates): see there.
 #include <math.h>
 
@@ -72,9 +77,23 @@ struct GkMath {
     }
 };
 
+// pl_distance(a, b, d, PL_MAHALANOBIS, diag(w)) without the d x d matrix.  Column jj of the reference's vector-matrix product
+// is 0.0 + ... + diff_jj * w_jj + ... with every other term diff_ii * 0.0: a zero of either sign while every difference is
+// finite (the sum starts at +0.0, so the signs never show), a NaN as soon as one is not.  `poison` carries exactly that: it is
+// +0.0 or NaN, and reaches the result only when another column exists (d >= 2).
+__device__ __forceinline__ float gk_distance_diag(const float* a, const float* b, uint32_t d, const float* __restrict__ w) {
+    float poison = 0.0f;
+    for (uint32_t kk = 0; kk < d; kk++) poison = poison + (a[kk] - b[kk]) * 0.0f;
+    const float q = pl_udot([&](uint32_t kk) { return 0.0f + (a[kk] - b[kk]) * w[kk]; }, [&](uint32_t kk) { return a[kk] - b[kk]; }, d);
+    return sqrtf(d >= 2u ? q + poison : q);
+}
+
 // D > 0: compile-time feature count, euclidean / cosine / diagonal M.  D == 0: any d <= 64 and any M through pl_distance, seeds
 // and candidates read from global memory / L2 (slow, exact).
-template <int D, int METRIC, int KEYS>
+// PERGROUP (Mahalanobis only): M is not one d x d matrix but [n_groups][d], row g the DIAGONAL of group g's matrix.  The group a
+// wavefront works on is wave-uniform, so its row is fetched with scalar loads into the registers the shared diagonal occupies
+// in the other form; every other instantiation compiles to what it was.
+template <int D, int METRIC, int KEYS, bool PERGROUP = false>
 __global__ __launch_bounds__(256, (KEYS == KNN_KEYS_SMALL ? 2 : 1)) void group_knn_scan_kernel(
     const float* __restrict__ S, const uint32_t* __restrict__ goff, const float* __restrict__ X, uint32_t n, uint32_t d_rt,
     int metric_rt, const float* __restrict__ M, const uint32_t* __restrict__ skip, uint32_t k, uint32_t cap, uint32_t qb_rt,
@@ -108,9 +127,10 @@ __global__ __launch_bounds__(256, (KEYS == KNN_KEYS_SMALL ? 2 : 1)) void group_k
     const uint32_t blk1 = (uint32_t)(((uint64_t)it.c_hi + KNN_COLS - 1) / KNN_COLS);
     bool saw_nan = false;
 
+    static_assert(!PERGROUP || METRIC == METRIC_MAHALANOBIS, "a per-group diagonal is a Mahalanobis metric");
     float wdiag[DD];
 #pragma unroll
-    for (int kk = 0; kk < DD; kk++) wdiag[kk] = (!GENERIC && METRIC == METRIC_MAHALANOBIS) ? M[kk * DD + kk] : 0.0f;  // (uniform: scalar registers)
+    for (int kk = 0; kk < DD; kk++) wdiag[kk] = (!GENERIC && !PERGROUP && METRIC == METRIC_MAHALANOBIS) ? M[kk * DD + kk] : 0.0f;  // (uniform: scalar registers)
 
     for (uint32_t gc = it.g_lo; gc < it.g_hi; gc += QB) {
         const uint32_t rows_here = (it.g_hi - gc < QB) ? it.g_hi - gc : QB;
@@ -197,6 +217,12 @@ __global__ __launch_bounds__(256, (KEYS == KNN_KEYS_SMALL ? 2 : 1)) void group_k
             for (uint32_t r = wave_u; r < rows_here; r += 4u) {
                 const uint32_t g0 = s_g0[r], gn = s_gn[r], roff = s_roff[r];
                 float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // the running scores of the lane's four candidates
+                // the group's own diagonal (gc + r is wave-uniform: scalar loads, scalar registers)
+                const float* wrow = PERGROUP ? M + (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(gc + r)) * d : nullptr;
+                if constexpr (PERGROUP && !GENERIC) {
+#pragma unroll
+                    for (int kk = 0; kk < DD; kk++) wdiag[kk] = wrow[kk];
+                }
                 if constexpr (GENERIC) {
 #pragma unroll 1
                     for (int c = 0; c < 4; c++) {
@@ -204,7 +230,11 @@ __global__ __launch_bounds__(256, (KEYS == KNN_KEYS_SMALL ? 2 : 1)) void group_k
                         if (lc < cols_here) {
                             const float* x = X + (uint64_t)(j0 + lc) * d;
                             float a = 0.0f;
-                            for (uint32_t s = 0; s < gn; s++) a = a + pl_distance(S + (uint64_t)(g0 + s) * d, x, d, metric_rt, M);
+                            if constexpr (PERGROUP) {
+                                for (uint32_t s = 0; s < gn; s++) a = a + gk_distance_diag(S + (uint64_t)(g0 + s) * d, x, d, wrow);
+                            } else {
+                                for (uint32_t s = 0; s < gn; s++) a = a + pl_distance(S + (uint64_t)(g0 + s) * d, x, d, metric_rt, M);
+                            }
                             acc[c] = a;
                         } else {
                             acc[c] = INFINITY;
@@ -335,6 +365,75 @@ __global__ __launch_bounds__(256) void group_knn_merge_kernel(const unsigned lon
     }
 }
 
+// variance_based_weight_matrix (src/playlist.rs:173-221) of every seed group: W[g][0..d) is the diagonal of the matrix the
+// reference returns for the rows goff[g] .. goff[g + 1] of S.  A wavefront per group, lane j owns dimension j (d <= 64); both
+// passes walk the group's rows in seed order -- the adds are a dependent chain, the loads are not, so eight rows travel at a
+// time.  Every operation rounds on its own, in the reference's order:
+//   mean = (0 + s_0 + s_1 + ...) / (float)count;  var = (0 + diff_0 * diff_0 + ...) / (float)count;  w = 1 / (var + 1e-6);
+//   total = ndarray's sum() (unrolled_fold: eight partial sums over k mod 8 for the whole eights, 0 + (p0 + p4) + (p1 + p5) +
+//   (p2 + p6) + (p3 + p7), then the tail in order) -- the lanes' weights meet in LDS and every lane adds them in that order;
+//   w = w * ((float)d / total).
+// A group of fewer than two seeds gets the identity's diagonal (euclidean_distance's own M, src/playlist.rs:69) and status 1.
+__global__ __launch_bounds__(256) void group_weights_kernel(const float* __restrict__ S, const uint32_t* __restrict__ goff,
+                                                            uint64_t n_groups, uint32_t d, float* __restrict__ W,
+                                                            int32_t* __restrict__ status) {
+    __shared__ float s_w[4][64];
+    const int lane = lane_id(), wave = wave_id();
+    const bool mine = (uint32_t)lane < d;
+    const uint32_t col = mine ? (uint32_t)lane : 0u;  // (the idle lanes read column 0 and store nothing)
+    for (uint64_t g = (uint64_t)blockIdx.x * 4 + (uint64_t)wave; g < n_groups; g += (uint64_t)gridDim.x * 4) {
+        const uint32_t a = goff[g], cnt = goff[g + 1] - a;
+        float w = 1.0f;
+        if (cnt >= 2u) {  // (wave-uniform)
+            const float* x = S + (uint64_t)a * d + col;
+            const float ns = (float)cnt;
+            float mean = 0.0f, var = 0.0f, v[8];
+            uint32_t s = 0;
+            for (; s + 8u <= cnt; s += 8u) {
+#pragma unroll
+                for (int i = 0; i < 8; i++) v[i] = x[(uint64_t)(s + (uint32_t)i) * d];
+#pragma unroll
+                for (int i = 0; i < 8; i++) mean = mean + v[i];
+            }
+            for (; s < cnt; s++) mean = mean + x[(uint64_t)s * d];
+            mean = mean / ns;
+            for (s = 0; s + 8u <= cnt; s += 8u) {
+#pragma unroll
+                for (int i = 0; i < 8; i++) v[i] = x[(uint64_t)(s + (uint32_t)i) * d];
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    const float diff = v[i] - mean;
+                    var = var + diff * diff;
+                }
+            }
+            for (; s < cnt; s++) {
+                const float diff = x[(uint64_t)s * d] - mean;
+                var = var + diff * diff;
+            }
+            var = var / ns;
+            w = 1.0f / (var + 1e-6f);
+            s_w[wave][lane] = w;
+            knn_wave_sync();
+            const float* sw = s_w[wave];
+            float p[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            uint32_t kk = 0;
+            for (; kk + 8u <= d; kk += 8u)
+#pragma unroll
+                for (int u = 0; u < 8; u++) p[u] = p[u] + sw[kk + (uint32_t)u];
+            float total = 0.0f;
+            total = total + (p[0] + p[4]);
+            total = total + (p[1] + p[5]);
+            total = total + (p[2] + p[6]);
+            total = total + (p[3] + p[7]);
+            for (; kk < d; kk++) total = total + sw[kk];
+            w = w * ((float)d / total);
+            knn_wave_sync();  // the weights are read before the wavefront's next group overwrites them
+        }
+        if (mine) W[g * d + (uint64_t)lane] = w;
+        if (status && lane == 0) status[g] = cnt >= 2u ? 0 : 1;
+    }
+}
+
 // The plan.  An item is a rectangle of the groups x candidates plane; its cost is (seeds of its groups) x (its candidates).
 // With total = all seeds x n and T = max(total / (4 n_cus), 256 x largest group):
 //   * consecutive groups are gathered into a band while band seeds x n <= T; the band is ONE item over every candidate;
@@ -390,12 +489,15 @@ GroupKnnPlan group_knn_plan(const uint64_t* off, uint64_t n_groups, uint64_t n, 
 
 template <int D, int KEYS>
 static void gk_scan_d(const float* S, const uint32_t* goff, const float* X, uint32_t n, uint32_t d, int metric, const float* M,
-                      const uint32_t* skip, uint32_t k, const GroupKnnPlan& p, const GroupKnnItem* items, const uint32_t* list_off,
+                      bool pergroup, const uint32_t* skip, uint32_t k, const GroupKnnPlan& p, const GroupKnnItem* items, const uint32_t* list_off,
                       unsigned long long* part, uint32_t* nan_flag, uint32_t* bad_flag, hipStream_t st) {
     const dim3 grid((uint32_t)p.items.size());
 #define GK_GO(DD, MM) hipLaunchKernelGGL((group_knn_scan_kernel<DD, MM, KEYS>), grid, dim3(256), 0, st, S, goff, X, n, d, metric, M, skip, \
                                          k, p.cap, p.qb, items, list_off, part, nan_flag, bad_flag)
-    if constexpr (D == 0) {
+    if (pergroup) {  // M is [n_groups][d]: one diagonal per group
+        hipLaunchKernelGGL((group_knn_scan_kernel<D, METRIC_MAHALANOBIS, KEYS, true>), grid, dim3(256), 0, st, S, goff, X, n, d,
+                           metric, M, skip, k, p.cap, p.qb, items, list_off, part, nan_flag, bad_flag);
+    } else if constexpr (D == 0) {
         GK_GO(0, METRIC_EUCLIDEAN);  // (the metric is a run-time argument of the generic path)
     } else {
         if (metric == METRIC_EUCLIDEAN) GK_GO(D, METRIC_EUCLIDEAN);
@@ -411,16 +513,24 @@ void launch_group_knn_scan(const float* S, const uint32_t* goff, const float* X,
                            uint32_t* bad_flag, hipStream_t st) {
     if (p.items.empty()) return;
     const bool small = p.cap <= 256;
+    const bool pergroup = m_is_diag == GROUP_KNN_M_PER_GROUP;  // (Mahalanobis; M holds a diagonal per group)
     const bool packed = (d == 23 || d == 20) && (metric != METRIC_MAHALANOBIS || m_is_diag);  // general M: pl_distance
 #define GK_D(DD)                                                                                                                  \
     do {                                                                                                                          \
-        if (small) gk_scan_d<DD, KNN_KEYS_SMALL>(S, goff, X, n, d, metric, M, skip, k, p, items, list_off, part, nan_flag, bad_flag, st); \
-        else gk_scan_d<DD, KNN_KEYS_BIG>(S, goff, X, n, d, metric, M, skip, k, p, items, list_off, part, nan_flag, bad_flag, st);   \
+        if (small) gk_scan_d<DD, KNN_KEYS_SMALL>(S, goff, X, n, d, metric, M, pergroup, skip, k, p, items, list_off, part, nan_flag, bad_flag, st); \
+        else gk_scan_d<DD, KNN_KEYS_BIG>(S, goff, X, n, d, metric, M, pergroup, skip, k, p, items, list_off, part, nan_flag, bad_flag, st);   \
     } while (0)
     if (packed && d == 23) GK_D(23);
     else if (packed && d == 20) GK_D(20);
     else GK_D(0);
 #undef GK_D
+}
+
+void launch_group_weights(const float* S, const uint32_t* goff, uint64_t n_groups, uint32_t d, float* W, int32_t* status,
+                          hipStream_t st) {
+    if (n_groups == 0) return;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n_groups + 3) / 4, 1u << 20);
+    hipLaunchKernelGGL(group_weights_kernel, dim3(grid), dim3(256), 0, st, S, goff, n_groups, d, W, status);
 }
 
 void launch_group_knn_merge(const unsigned long long* part, const uint32_t* list_off, uint64_t n_groups, uint32_t k,

@@ -360,14 +360,39 @@ class Context:
         self._post()
         return idx, dist
 
-    def group_knn(self, S, offsets, X, k: int, metric: str = "euclidean", M=None, skip=None):
+    def group_weights(self, S, offsets):
+        """variance_based_weight_matrix (src/playlist.rs:173-221) of every seed group on the device: group g's seeds are the
+        rows offsets[g] .. offsets[g + 1] of S (offsets: a HOST sequence of G + 1 integers starting at 0).  -> (weights float32
+        [G, d], status int32 [G]) on the device: row g is the DIAGONAL of the reference's matrix; a group of fewer than two
+        seeds gets ones and status 1 (BLISSGPU_GROUP_TOO_FEW_SEEDS), every other group status 0."""
+        import numpy as np
+
+        torch = self.torch
+        assert S.is_cuda and S.dtype == torch.float32 and S.dim() == 2
+        S = S.contiguous()
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1)).astype(np.uint64)
+        assert off.shape[0] >= 1 and int(off[-1]) == S.shape[0]
+        G, d = off.shape[0] - 1, S.shape[1]
+        weights = torch.empty((G, d), dtype=torch.float32, device=S.device)
+        status = torch.empty((G,), dtype=torch.int32, device=S.device)
+        self._pre()
+        _ffi.check(self._L.blissgpu_group_weights_device(self._h, C.c_void_p(S.data_ptr()), off.ctypes.data, G, d,
+                                                         C.c_void_p(weights.data_ptr()), C.c_void_p(status.data_ptr())))
+        self._post()
+        return weights, status
+
+    def group_knn(self, S, offsets, X, k: int, metric: str = "euclidean", M=None, skip=None, weights=None):
         """The k nearest rows of X for every seed GROUP without a groups x candidates matrix: group g's seeds are the rows
         offsets[g] .. offsets[g + 1] of S (offsets: a HOST sequence of G + 1 integers starting at 0), its row =
         closest_to_songs(those seeds, X without the group's skipped rows, metric) cut after k (src/playlist.rs:36-59, 256-270,
         src/library.rs:762-842); a candidate's score is the sequential f32 sum over the seeds in order.  -> (idx int32 [G, k],
         dist float32 [G, k]) on the device; equal scores in candidate order; rows with fewer than k eligible candidates end in
         -1 (the library's 0xFFFFFFFF) / inf.  skip: int32 tensor with one candidate index per SEED ROW, -1 = none, or None.
-        Raises BlissGpuError(ERR_NAN) for a NaN among the scores (synchronises for that check)."""
+        Raises BlissGpuError(ERR_NAN) for a NaN among the scores (synchronises for that check).
+        `weights` (metric and M are then not looked at): one DIAGONAL Mahalanobis metric per group, M_g = diag(weights[g]) -- a
+        float32 [G, d] tensor, or the string "variance" for the variance-based weights of each group's own seeds, computed on
+        the device (group_weights) in the same call.  -> (idx, dist, status int32 [G]): status as group_weights returns it
+        (all 0 with given weights)."""
         import numpy as np
 
         from .playlist import _METRICS
@@ -387,6 +412,20 @@ class Context:
             M = M.contiguous()
         idx = torch.empty((G, max(k, 0)), dtype=torch.int32, device=X.device)
         dist = torch.empty((G, max(k, 0)), dtype=torch.float32, device=X.device)
+        if weights is not None:
+            if isinstance(weights, str):
+                if weights != "variance":
+                    raise ValueError('weights must be a [G, d] tensor or "variance"')
+                weights = None
+            else:
+                assert weights.is_cuda and weights.dtype == torch.float32 and tuple(weights.shape) == (G, X.shape[1])
+                weights = weights.contiguous()
+            status = torch.empty((G,), dtype=torch.int32, device=X.device)
+            self._pre()
+            _ffi.check(self._L.blissgpu_group_knn_weighted_device(self._h, ptr(S), off.ctypes.data, G, ptr(X), n, X.shape[1],
+                                                                  ptr(weights), ptr(skip), k, ptr(idx), ptr(dist), ptr(status)))
+            self._post()
+            return idx, dist, status
         self._pre()
         _ffi.check(self._L.blissgpu_group_knn_device(self._h, ptr(S), off.ctypes.data, G, ptr(X), n, X.shape[1], _METRICS[metric],
                                                      ptr(M), ptr(skip), k, ptr(idx), ptr(dist)))

@@ -302,11 +302,22 @@ def playlist_from_custom(db: Conn, initial_song_paths: Sequence[str], metric_bui
     Any other `sort_by` runs on the host and its result goes through the same single call.  The metric is one of the
     device metrics (playlist._metric_of) or a playlist.ForestOptions.
 
+    A VarianceWeights works with closest_to_songs and deduplicate=False: M = variance_based_weight_matrix(the initial
+    songs' analyses) (src/playlist.rs:173-221), at least two initial songs unless few_seeds="euclidean".  deduplicate=True and
+    song_to_song are refused: they build one-song metrics.
+
     A ForestOptions works with closest_to_songs and deduplicate=False (at least two initial songs; the matrix is still read
     once and the forest scores come from the device).  With deduplicate=True the reference would build one-song forests,
     which do not work (src/playlist.rs:230-240, 367-402): ValueError.  To deduplicate a forest playlist, pass the result to
     playlist.dedup_playlist (euclidean).  song_to_song with a forest is refused for the same reason (:285-295)."""
     forest = isinstance(metric_builder, playlist.ForestOptions)
+    variance = isinstance(metric_builder, playlist.VarianceWeights)
+    if variance:
+        if deduplicate:
+            playlist._no_variance(metric_builder, "deduplicate=True builds one-song metrics (:367-402); use "
+                                                  "playlist.dedup_playlist(result) on the playlist instead")
+        if sort_by is playlist.song_to_song:
+            playlist._no_variance(metric_builder, "song_to_song rebuilds its metric from one song after the first step (:285-295)")
     if forest:
         if deduplicate:
             playlist._no_forest(metric_builder, "deduplicate=True builds one-song metrics (:367-402); use "
@@ -314,6 +325,8 @@ def playlist_from_custom(db: Conn, initial_song_paths: Sequence[str], metric_bui
         if sort_by is playlist.song_to_song:
             playlist._no_forest(metric_builder, "song_to_song rebuilds its metric from one song after the first step (:285-295)")
     initial_song_paths = list(initial_song_paths)
+    if variance:
+        metric_builder.check_counts([len(initial_song_paths)])
     initial = []
     for p in initial_song_paths:
         try:
@@ -321,7 +334,7 @@ def playlist_from_custom(db: Conn, initial_song_paths: Sequence[str], metric_bui
         except Exception as e:
             raise ProviderError(f"song '{p}' has not been analyzed") from e
     songs, X = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
-    metric, m = (metric_builder, None) if forest else playlist._metric_of(metric_builder)
+    metric, m = (metric_builder, None) if forest or variance else playlist._metric_of(metric_builder)
     chosen = set(initial_song_paths)
     pool = [i for i, s in enumerate(songs) if s.path not in chosen]
     if sort_by not in (playlist.closest_to_songs, playlist.song_to_song):
@@ -360,6 +373,7 @@ def similar_songs(db: Conn, k: int, metric_builder=playlist.euclidean_distance, 
     paths only; an unknown path is the ProviderError playlist_from_custom raises.  The matrix is read once and ONE device
     call (playlist.nearest_order, each song skipping its own row) answers every song: no distance matrix is built."""
     playlist._no_forest(metric_builder, "similar_songs builds one metric per song")
+    playlist._no_variance(metric_builder, "similar_songs builds one metric per song; use group_playlists for seed sets")
     _, paths, X = load_feature_matrix(db, FeaturesVersion.LATEST)
     metric, m = playlist._metric_of(metric_builder)
     if song_paths is None:
@@ -386,7 +400,10 @@ def group_playlists(db: Conn, k: int, by: str = "album", metric_builder=playlist
     {key: [(path, score), ...]} where entry `key` is
     `playlist_from_custom(db, paths, metric_builder, closest_to_songs, deduplicate=False)[len(paths):][:k]` with the scores
     (src/library.rs:762-842: the songs closest to the SET of initial songs, the initial songs themselves left out).  The
-    library is read once and ONE device call (playlist.nearest_to_groups) answers every group.
+    library is read once and ONE device call (playlist.nearest_to_groups) answers every group.  With
+    metric_builder=playlist.VarianceWeights(...) every group is searched under the variance-based weights of its OWN members
+    (src/playlist.rs:173-221), computed on the device in that same call; a group of one song (or none) is the reference's
+    ProviderError unless few_seeds="euclidean", decided before the device is touched.
 
     `by`: the column that groups the analysed songs of FeaturesVersion.LATEST; a song whose key is NULL belongs to no group
     but stays a candidate; groups come in order of first appearance by id, their members in id order.  `groups` =
@@ -396,7 +413,8 @@ def group_playlists(db: Conn, k: int, by: str = "album", metric_builder=playlist
     if groups is None and by not in _GROUP_COLUMNS:
         raise ValueError(f"by must be one of {_GROUP_COLUMNS}")
     songs, X = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
-    metric, m = playlist._metric_of(metric_builder)
+    variance = isinstance(metric_builder, playlist.VarianceWeights)
+    metric, m = (metric_builder, None) if variance else playlist._metric_of(metric_builder)
     members = {}
     if groups is None:
         for i, s in enumerate(songs):
@@ -427,6 +445,7 @@ def duplicate_songs(db: Conn, distance_threshold: float = None, metric_builder=p
     id order; groups by their first song).  The library is read once (load_songs) and ONE device call answers
     (playlist.duplicate_labels); nothing is deduplicated or deleted."""
     playlist._no_forest(metric_builder, "duplicate_songs builds its metric from single songs")
+    playlist._no_variance(metric_builder, "duplicate_songs builds its metric from single songs")
     songs, X = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
     if not songs:
         return []

@@ -4,6 +4,7 @@
     DistanceMetricBuilder / FunctionDistanceMetric               :24-59
     variance_based_weight_matrix                                 :173-221
     ForestOptions (the extended isolation forest metric)         :19-23, 230-251
+    VarianceWeights (that matrix as a metric builder), group_variance_weights (every seed group's, one device call)
     closest_to_songs, song_to_song                               :256-326
     nearest_order, nearest_songs (closest_to_songs cut after k, for many seeds at once)
     dedup_playlist, dedup_playlist_custom_distance               :343-402
@@ -11,8 +12,9 @@
     closest_album_to_group                                       :424-485
 
 A metric builder is one of the strings "euclidean" / "cosine", a `MahalanobisBuilder` (or the pair
-("mahalanobis", M)), or a `ForestOptions` (closest_to_songs and library.playlist_from_custom only: the forest needs at
-least two seed songs), i.e. the metrics the device implements; arbitrary Python callables are not accepted
+("mahalanobis", M)), a `ForestOptions` (closest_to_songs and library.playlist_from_custom only: the forest needs at
+least two seed songs) or a `VarianceWeights` (the entry points that build a metric from a seed SET: closest_to_songs,
+set_distances, nearest_to_groups, group_playlists and their library forms), i.e. the metrics the device implements; arbitrary Python callables are not accepted
 because the distances are evaluated by the HIP kernels (there is no CPU path).  Songs are anything with an
 `.analysis` (Analysis) -- `Song` or a wrapper holding one in `.bliss_song`, like the reference's
 `AsRef<Song>`."""
@@ -133,6 +135,58 @@ def _no_forest(builder, what):
     """The entry points whose metric is built from ONE song refuse a ForestOptions (psi < 2)."""
     if isinstance(builder, ForestOptions):
         raise ValueError(_FOREST_SINGLE.format(what=what))
+
+
+_TOO_FEW_SEEDS = "seeds must contain more than one element"  # variance_based_weight_matrix, src/playlist.rs:174-178
+
+
+class VarianceWeights:
+    """mahalanobis_distance_builder(variance_based_weight_matrix(seeds)) as a metric builder (src/playlist.rs:129-131,
+    173-221): a diagonal metric built from the seed SET, so an album whose songs agree on tempo and timbre but not on key
+    gets a playlist that follows tempo and timbre.  `few_seeds`: what a seed set of fewer than two songs means -- "raise"
+    (the default) is the reference's ProviderError("seeds must contain more than one element"), decided before the device is
+    touched; "euclidean" takes the identity (euclidean_distance's own M, src/playlist.rs:69) for such a set."""
+
+    def __init__(self, few_seeds="raise"):
+        if few_seeds not in ("raise", "euclidean"):
+            raise ValueError('few_seeds must be "raise" or "euclidean"')
+        self.few_seeds = few_seeds
+
+    def __repr__(self):
+        return f"VarianceWeights(few_seeds={self.few_seeds!r})"
+
+    def check_counts(self, counts):
+        """the policy for seed sets of these sizes (nothing but the sizes is looked at)"""
+        from .song import ProviderError
+
+        if self.few_seeds == "raise" and any(int(c) < 2 for c in counts):
+            raise ProviderError(_TOO_FEW_SEEDS)
+
+    def matrix(self, seeds):
+        """-> ("mahalanobis", M) for ONE seed set, M from the host arithmetic (variance_based_weight_matrix); ("euclidean",
+        None) for fewer than two seeds when few_seeds is "euclidean" """
+        seeds = np.atleast_2d(np.asarray(seeds, dtype=np.float32))
+        self.check_counts([seeds.shape[0]])
+        if seeds.shape[0] < 2:
+            return "euclidean", None
+        return "mahalanobis", variance_based_weight_matrix(list(seeds))
+
+
+_VARIANCE_SINGLE = ("variance-based weights need a seed set of more than one song (variance_based_weight_matrix, "
+                    "src/playlist.rs:173-178): {what}")
+
+
+def _no_variance(builder, what):
+    """The entry points whose metric is built from ONE song refuse a VarianceWeights (fewer than two seeds)."""
+    if isinstance(builder, VarianceWeights):
+        raise ValueError(_VARIANCE_SINGLE.format(what=what))
+
+
+def _seed_set_metric(metric, m, seeds):
+    """(metric, m) of an entry point that builds ONE metric from ONE seed set: a VarianceWeights becomes its matrix"""
+    if isinstance(metric, VarianceWeights):
+        return metric.matrix(seeds)
+    return metric, m
 
 
 class Forest:
@@ -265,8 +319,10 @@ def _nan_to_panic(e: "_ffi.BlissGpuError"):
 
 
 def set_distances(seeds, candidates, metric="euclidean", m=None) -> np.ndarray:
-    """FunctionDistanceMetric::distance (src/playlist.rs:52-58) for every row of `candidates`."""
+    """FunctionDistanceMetric::distance (src/playlist.rs:52-58) for every row of `candidates`.  `metric` may be a
+    VarianceWeights: M is then variance_based_weight_matrix(seeds)."""
     S = np.ascontiguousarray(np.atleast_2d(seeds), dtype=np.float32)
+    metric, m = _seed_set_metric(metric, m, S)
     X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
     out = np.empty(X.shape[0], np.float32)
     mp = None
@@ -284,6 +340,7 @@ def closest_to_songs_order(seeds, candidates, metric="euclidean", m=None):
     if isinstance(metric, ForestOptions):
         return forest_closest_to_songs_order(seeds, candidates, metric)
     S = np.ascontiguousarray(np.atleast_2d(seeds), dtype=np.float32)
+    metric, m = _seed_set_metric(metric, m, S)  # (a VarianceWeights: M = variance_based_weight_matrix(seeds))
     X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
     order, dist = np.empty(X.shape[0], np.uint32), np.empty(X.shape[0], np.float32)
     mp = None
@@ -323,7 +380,7 @@ def closest_to_songs(initial_songs, candidate_songs, metric_builder=euclidean_di
     if isinstance(metric_builder, ForestOptions):
         order, _ = forest_closest_to_songs_order(_matrix(initial_songs), _matrix(candidate_songs), metric_builder)
         return [candidate_songs[i] for i in order]
-    metric, m = _metric_of(metric_builder)
+    metric, m = (metric_builder, None) if isinstance(metric_builder, VarianceWeights) else _metric_of(metric_builder)
     order, _ = closest_to_songs_order(_matrix(initial_songs), _matrix(candidate_songs), metric, m)
     return [candidate_songs[i] for i in order]
 
@@ -331,6 +388,7 @@ def closest_to_songs(initial_songs, candidate_songs, metric_builder=euclidean_di
 def song_to_song(initial_songs, candidate_songs, metric_builder=euclidean_distance):
     """src/playlist.rs:272-326: each song is followed by the remaining song closest to it."""
     _no_forest(metric_builder, "song_to_song rebuilds its metric from one song after the first step (:285-295)")
+    _no_variance(metric_builder, "song_to_song rebuilds its metric from one song after the first step (:285-295)")
     candidate_songs = list(candidate_songs)
     if not candidate_songs:
         return []
@@ -385,6 +443,7 @@ def nearest_songs(songs, candidate_songs, k, metric_builder=euclidean_distance, 
     -- all of them in one device call.  `exclude_self`: the first candidate that == the song (Song: PartialEq, as
     closest_album_to_group removes the group from its pool) is left out of that song's list."""
     _no_forest(metric_builder, "nearest_songs builds one metric per query song")
+    _no_variance(metric_builder, "nearest_songs builds one metric per query song; use nearest_to_groups for seed sets")
     songs, candidate_songs = list(songs), list(candidate_songs)
     if not songs:
         return []
@@ -432,13 +491,22 @@ def nearest_to_groups(seed_groups, candidates, k, metric="euclidean", m=None, sk
     `seed_groups`: a sequence of [s_g, d] arrays, or (S [total, d], offsets [G + 1]).  `skip`: None, one array of
     candidate indices per group (left out of that group's list), or one flat array with an entry per seed row (-1: none).
     A NaN score raises ValueError (the reference's n32() panic).  A ForestOptions is refused: a forest is built per seed
-    set, use closest_to_songs per group."""
+    set, use closest_to_songs per group.
+    One DIAGONAL Mahalanobis metric per group, still one call (blissgpu_group_knn_weighted): metric="diagonal" with m a [G, d]
+    array, row g the diagonal of group g's M; metric="variance" for variance_based_weight_matrix (src/playlist.rs:173-221) of
+    each group's own seeds, computed on the device, a group of fewer than two seeds taking the identity (euclidean); or a
+    VarianceWeights, which is "variance" under its few_seeds policy (ProviderError for such a group by default, decided from
+    the group sizes before the device is touched)."""
     _no_forest(metric, "nearest_to_groups would build one forest per seed group; use closest_to_songs per group")
     S, off = _seed_groups(seed_groups)
     X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
     if X.ndim != 2 or (S is not None and S.shape[1] != X.shape[1]):
         raise ValueError("seed groups and candidates must be [s_g, d] and [n, d]")
-    if metric not in _METRICS:
+    if isinstance(metric, VarianceWeights):
+        metric.check_counts(np.diff(off.astype(np.int64)))
+        metric = "variance"
+    per_group = isinstance(metric, str) and metric in ("variance", "diagonal")
+    if not per_group and metric not in _METRICS:
         raise ValueError(f"unknown metric {metric!r}")
     k = int(k)
     if not 1 <= k <= 1024:
@@ -477,15 +545,48 @@ def nearest_to_groups(seed_groups, candidates, k, metric="euclidean", m=None, sk
         if m.shape != (d, d):
             raise ValueError("m must be [d, d]")
         mp = m.ctypes.data
+    elif metric == "diagonal":
+        if m is None:
+            raise ValueError("diagonal needs m, one row of d weights per group")
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        if m.shape != (G, d):
+            raise ValueError("m must be [G, d]")
+        mp = m.ctypes.data
     idx, dist = np.empty((G, k), np.uint32), np.empty((G, k), np.float32)
     try:
-        _ffi.check(_ffi.lib().blissgpu_group_knn(None if S is None else S.ctypes.data, off.ctypes.data, G, X.ctypes.data, n, d,
-                                                 _METRICS[metric], mp, skip_p, k, idx.ctypes.data, dist.ctypes.data))
+        if per_group:
+            _ffi.check(_ffi.lib().blissgpu_group_knn_weighted(None if S is None else S.ctypes.data, off.ctypes.data, G,
+                                                              X.ctypes.data, n, d, mp, skip_p, k, idx.ctypes.data,
+                                                              dist.ctypes.data, None))
+        else:
+            _ffi.check(_ffi.lib().blissgpu_group_knn(None if S is None else S.ctypes.data, off.ctypes.data, G, X.ctypes.data, n,
+                                                     d, _METRICS[metric], mp, skip_p, k, idx.ctypes.data, dist.ctypes.data))
     except _ffi.BlissGpuError as e:
         _nan_to_panic(e)
     out = idx.astype(np.int64)
     out[idx == 0xFFFFFFFF] = -1
     return out, dist
+
+
+def group_variance_weights(seed_groups):
+    """variance_based_weight_matrix (src/playlist.rs:173-221) of every seed group in one device call
+    (blissgpu_group_weights).  `seed_groups` as for nearest_to_groups.  -> (weights float32[G, d], few_seeds bool[G]): row g is
+    the DIAGONAL of the reference's matrix, bit for bit variance_based_weight_matrix(seed_groups[g]); a group of fewer than
+    two seeds (where the reference returns its ProviderError) gets ones, the identity, and few_seeds[g] = True."""
+    S, off = _seed_groups(seed_groups)
+    G = off.shape[0] - 1
+    if S is None:  # (a list of groups without a single seed: the width of an empty [0, d] array, if one was given)
+        d = max([np.shape(g)[1] for g in seed_groups if np.ndim(g) == 2] + [0])
+        if d == 0:
+            raise ValueError("the feature count cannot be told from empty seed groups; pass (S [0, d], offsets)")
+        S = np.zeros((0, d), np.float32)
+    d = S.shape[1]
+    if not 1 <= d <= 64:
+        raise ValueError("d must be 1 .. 64")
+    weights, status = np.empty((G, d), np.float32), np.empty(G, np.int32)
+    _ffi.check(_ffi.lib().blissgpu_group_weights(S.ctypes.data if S.shape[0] else None, off.ctypes.data, G, d,
+                                                 weights.ctypes.data, status.ctypes.data))
+    return weights, status != 0
 
 
 def group_playlists(groups, candidate_songs, k, metric_builder=euclidean_distance, exclude_members=True):
@@ -497,9 +598,11 @@ def group_playlists(groups, candidate_songs, k, metric_builder=euclidean_distanc
     groups, candidate_songs = [list(g) for g in groups], list(candidate_songs)
     if not groups:
         return []
+    if isinstance(metric_builder, VarianceWeights):
+        metric_builder.check_counts([len(g) for g in groups])
     if not candidate_songs:
         return [[] for _ in groups]
-    metric, m = _metric_of(metric_builder)
+    metric, m = (metric_builder, None) if isinstance(metric_builder, VarianceWeights) else _metric_of(metric_builder)
     X = _matrix(candidate_songs)
     seeds = [_matrix(g) if g else np.zeros((0, X.shape[1]), np.float32) for g in groups]
     skip = None
@@ -568,6 +671,7 @@ def dedup_playlist_custom_distance(playlist, distance_threshold=None, metric_bui
     (default 0.05) or carry the same non-empty title and artist.  One device call for the whole playlist
     (dedup_order); `window` is accepted for compatibility and unused."""
     _no_forest(metric_builder, "dedup_playlist_custom_distance builds its metric from single songs (:367-402)")
+    _no_variance(metric_builder, "dedup_playlist_custom_distance builds its metric from single songs (:367-402)")
     playlist = list(playlist)
     if not playlist:
         return []
@@ -660,6 +764,7 @@ def duplicate_groups(songs, distance_threshold=None, metric_builder=euclidean_di
     dedup_playlist, which compares the neighbours of an ordered playlist, every pair is looked at.  Groups come by their
     first member, members in the order of `songs`."""
     _no_forest(metric_builder, "duplicate_groups builds its metric from single songs")
+    _no_variance(metric_builder, "duplicate_groups builds its metric from single songs")
     songs = list(songs)
     if not songs:
         return []

@@ -359,6 +359,48 @@ int blissgpu_group_knn_plan(const uint64_t *group_offsets, uint64_t n_groups, ui
                             uint32_t *items, uint64_t max_items, uint64_t *n_items, uint32_t *cand_block,
                             uint32_t *seed_tile);
 
+/* ---- one DIAGONAL metric per seed group ----
+ * variance_based_weight_matrix (src/playlist.rs:173-221) is built from a seed set: an album whose songs agree on tempo and timbre
+ * but not on key gets a playlist that follows tempo and timbre.  The two pairs of entry points below compute it for every group
+ * on the device and search every group's k nearest candidates under its own metric, in one call. */
+#define BLISSGPU_GROUP_OK 0
+#define BLISSGPU_GROUP_TOO_FEW_SEEDS 1 /* fewer than 2 seeds: the reference's ProviderError("seeds must contain more than one element") */
+
+/* variance_based_weight_matrix of EVERY seed group: weights[g][0 .. d) ([n_groups][d] row-major) is the DIAGONAL of the matrix
+ * the reference returns for the rows group_offsets[g] .. group_offsets[g + 1] of seeds (a HOST pointer in both forms, as above).
+ * The arithmetic is defined, every operation rounded to f32 on its own: mean = the sequential sum over the seeds in seed order,
+ * divided by (float)count; var = var + diff * diff over the seeds in order, divided by the count; w = 1.0f / (var + 1e-6f);
+ * total = ndarray's sum() (eight partial sums over k mod 8 for the whole eights, 0 + (p0 + p4) + (p1 + p5) + (p2 + p6) + (p3 + p7),
+ * then the tail in order); w *= (float)d / total.  A group of fewer than two seeds (an empty one included) gets a row of 1.0f --
+ * the identity, euclidean_distance's own M (src/playlist.rs:69) -- and BLISSGPU_GROUP_TOO_FEW_SEEDS in group_status ([n_groups],
+ * may be NULL); every other group BLISSGPU_GROUP_OK.  That is not an error of the call.  Non-finite seeds give whatever this
+ * arithmetic gives.  1 <= d <= 64, fewer than 2^32 seeds and 2^32 - 1 groups; n_groups == 0 is BLISSGPU_OK.  Arguments are
+ * checked before the device is touched.  One launch whatever the groups (a wavefront per group). */
+int blissgpu_group_weights(const float *seeds, const uint64_t *group_offsets, uint64_t n_groups, uint32_t d, float *weights,
+                           int32_t *group_status);
+/* Device-resident form (device pointers; group_offsets stays a host pointer); synchronises the context's stream before returning. */
+int blissgpu_group_weights_device(blissgpu_ctx *ctx, const float *d_seeds, const uint64_t *group_offsets, uint64_t n_groups,
+                                  uint32_t d, float *d_weights, int32_t *d_group_status);
+
+/* blissgpu_group_knn with metric = Mahalanobis and ONE DIAGONAL M PER GROUP: M_g = diag(weights[g][0 .. d)), weights
+ * [n_groups][d] row-major.  weights == NULL: the variance-based weights of each group's own seeds, computed on the device as
+ * above; group_status (may be NULL) is then written as above, and with weights given it is filled with BLISSGPU_GROUP_OK.
+ * Everything else is blissgpu_group_knn's contract -- sum order, stable order, skip, padding, the NaN rule (a NaN weight makes
+ * its group's scores NaN: BLISSGPU_ERR_NAN when one of them belongs to an eligible candidate), limits, arguments checked before
+ * the device is touched, no seeds x n or n_groups x n array -- with group g's metric mahalanobis_distance(., ., diag(weights[g])):
+ * a score is bit for bit what blissgpu_set_distance returns for that group's seeds with M = diag(weights[g]).  Three launches
+ * with derived weights, two with given ones, whatever n_groups, n and the group sizes; blissgpu_group_knn_plan describes the
+ * split unchanged; the workspace grows by n_groups x d floats. */
+int blissgpu_group_knn_weighted(const float *seeds, const uint64_t *group_offsets, uint64_t n_groups, const float *cand,
+                                uint64_t n, uint32_t d, const float *weights, const uint32_t *skip, uint32_t k,
+                                uint32_t *idx, float *dist, int32_t *group_status);
+/* Device-resident form (device pointers, d_weights, d_skip and d_group_status included; group_offsets stays a host pointer);
+ * asynchronous except for the NaN / skip check, which synchronises the context's stream before returning. */
+int blissgpu_group_knn_weighted_device(blissgpu_ctx *ctx, const float *d_seeds, const uint64_t *group_offsets,
+                                       uint64_t n_groups, const float *d_cand, uint64_t n, uint32_t d, const float *d_weights,
+                                       const uint32_t *d_skip, uint32_t k, uint32_t *d_idx, float *d_dist,
+                                       int32_t *d_group_status);
+
 /* ---- duplicate songs of a whole collection ----
  * The duplicate rule of dedup_playlist_custom_distance (src/playlist.rs:381-388) applied to EVERY pair of the n x d matrix x
  * instead of the neighbours of an ordered playlist: the pair (i, j), i < j, is an edge when D[i][j] < threshold (D[i][j] is bit
