@@ -6,7 +6,7 @@
 //   beat_acf_kernel   : the state-independent half of BeatTracking::do_ (src/aubio.rs:966-1003): the
 //                  autocorrelation of every run's detection-function frame, its comb filterbank sums
 //                  for both time signatures, the Rayleigh-weighted period and get_timesig (:864-907)
-//                  -- one workgroup per (song, run), ~124 k of them for 1024 three-minute songs.
+//                  -- one workgroup per eight consecutive runs of a song, ~124 k runs for 1024 three-minute songs.
 //   beat_track_kernel : the sequential half: checkstate (:1096-1227), beat phase (:1025-1054),
 //                  Tempo::do_'s beat / silence test (:1378-1443), get_bpm and BPMDesc's median
 //                  (src/temporal.rs:50-77).  The chain (gp/rp1/rp2/counter/flagstep/timesig/lastbeat/
@@ -144,146 +144,169 @@ static_assert(BT_PRE_STRIDE >= 260, "per-run record");
 
 typedef float bt_f2 __attribute__((ext_vector_type(2)));
 
-// acc01 += f[i] * (w[i], w[i+1]), acc23 += f[i] * (w[i+2], w[i+3]) for 16 consecutive i: the four lags (L .. L + 3) of
-// one thread, w = frame + L.  The packed multiply / add takes two lags per instruction; w1 is the same series one element
-// on (a second copy in LDS), so that the odd steps' operand pairs also arrive in even-aligned register pairs (gfx950 takes
-// 64-bit operands from aligned pairs only, and a copy per step costs more than the LDS read).  Four lags per thread
-// instead of two halve the LDS bytes per multiply-add: 18 + 18 values feed 64 of them.
-template <typename F>
-__device__ __forceinline__ void acf_block16(bt_f2& acc01, bt_f2& acc23, const float* w, const float* w1, F&& f_at) {
-    float r[18], r1[18];
+// A workgroup takes ACF_RUNS consecutive runs of one song; each of its four wavefronts takes one quarter of the lags of
+// all of them (see beat_acf_kernel).  A run's frame lies in LDS at a pitch of ACF_PITCH floats: 512 values, then zeros up to
+// the last index a lane reads (575 in df, 576 == df1[575]); 580 = 4 (mod 64) spreads the eight runs of a wavefront over
+// the banks (a lane reads 16-byte pieces at a stride of 8 floats inside a run).  (Frame starts at 0, 4, 36, 32 mod 64 make
+// every read conflict-free and buy nothing: the kernel waits for its multiply-adds, not for LDS.)
+constexpr int ACF_RUNS = 8, ACF_PITCH = 580;
+static_assert(ACF_PITCH >= BT_WINLEN + 65 && ACF_PITCH % 4 == 0, "zero padding behind a frame, 16-byte aligned frames");
+
+// acc[k] += f[i] * (w[i + 2k], w[i + 2k + 1]) for 16 consecutive i: the eight lags (L .. L + 7) of one thread, w = frame + L.
+// The packed multiply / add takes two lags per instruction; w1 is the same series one element on (a second copy in LDS),
+// so that the odd steps' operand pairs also arrive in even-aligned register pairs (gfx950 takes 64-bit operands from
+// aligned pairs only, and a copy per step costs more than the LDS read).  Eight lags per thread: 22 + 22 values and the
+// 16 first factors feed 128 multiply-adds, and every sum is one of four independent chains.
+__device__ __forceinline__ void acf_block16(bt_f2 (&acc)[4], const float* w, const float* w1, const float* f) {
+    float r[24], r1[24], fv[16];
 #pragma unroll
-    for (int u = 0; u < 18; u++) { r[u] = w[u]; r1[u] = w1[u]; }
+    for (int u = 0; u < 24; u++) { r[u] = w[u]; r1[u] = w1[u]; }
+#pragma unroll
+    for (int u = 0; u < 16; u++) fv[u] = f[u];
 #pragma unroll
     for (int u = 0; u < 16; u += 2) {
-        const float f0 = f_at(u), f1 = f_at(u + 1);
-        const bt_f2 fv0 = {f0, f0}, fv1 = {f1, f1};
-        const bt_f2 e01 = {r[u], r[u + 1]}, e23 = {r[u + 2], r[u + 3]};      // step u:     w[u .. u+3]
-        const bt_f2 o01 = {r1[u], r1[u + 1]}, o23 = {r1[u + 2], r1[u + 3]};  // step u + 1: w[u+1 .. u+4]
-        acc01 = acc01 + fv0 * e01;
-        acc23 = acc23 + fv0 * e23;
-        acc01 = acc01 + fv1 * o01;
-        acc23 = acc23 + fv1 * o23;
+        const bt_f2 fv0 = {fv[u], fv[u]}, fv1 = {fv[u + 1], fv[u + 1]};
+#pragma unroll
+        for (int k = 0; k < 4; k++) {  // step u: w[u .. u+7]
+            const bt_f2 e = {r[u + 2 * k], r[u + 2 * k + 1]};
+            acc[k] = acc[k] + fv0 * e;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {  // step u + 1: w[u+1 .. u+8]
+            const bt_f2 o = {r1[u + 2 * k], r1[u + 2 * k + 1]};
+            acc[k] = acc[k] + fv1 * o;
+        }
     }
 }
 
-__global__ __launch_bounds__(64) void beat_acf_kernel(const SongDesc* __restrict__ songs,
-                                                      const float* __restrict__ thresholded,
-                                                      const float* __restrict__ rwv_tab,
-                                                      float* __restrict__ pre_all) {
-    __shared__ float df[2 * BT_WINLEN];  // [512, 1024) stays zero: the ACF loops read past the frame instead of predicating
-    __shared__ float df1[2 * BT_WINLEN];  // df1[j] = df[j + 1]
-    __shared__ float acf[BT_WINLEN];
-    __shared__ float acfout[2][BT_LAGLEN];
+__global__ __launch_bounds__(256) void beat_acf_kernel(const SongDesc* __restrict__ songs,
+                                                       const float* __restrict__ thresholded,
+                                                       const float* __restrict__ rwv_tab,
+                                                       float* __restrict__ pre_all) {
+    // df[r]: the frame of run m0 + r, zeros behind it (the ACF loops read past the frame instead of predicating);
+    // df1[r][j] = df[r][j + 1].  Once the autocorrelation is done the same memory holds acf[r][512] and acfout[r][2][128].
+    __shared__ __attribute__((aligned(16))) float df[ACF_RUNS * ACF_PITCH];
+    __shared__ __attribute__((aligned(16))) float df1[ACF_RUNS * ACF_PITCH];
+    static_assert(ACF_PITCH >= BT_WINLEN && ACF_PITCH >= 2 * BT_LAGLEN, "acf / acfout live in a run's own frame");
     const uint32_t s = blockIdx.y;
-    const long m = blockIdx.x;
+    const long m0 = (long)blockIdx.x * ACF_RUNS;
     const SongDesc sd = songs[s];
     if (!sd.ok) return;
     const long n_b = sd.n_b;
     const long n_runs = (n_b >= BT_STEP) ? (n_b - BT_STEP) / BT_STEP + 1 : 0;
-    if (m >= n_runs) return;
-    const int tid = threadIdx.x;  // one wavefront per run
+    if (m0 >= n_runs) return;  // uniform over the workgroup
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // in a scalar register: the loop bounds below depend on it
     const float* thr = thresholded + sd.b_off;
-    float* pre = pre_all + ((size_t)(sd.b_off / BT_STEP) + s + (size_t)m) * BT_PRE_STRIDE;
 
-    // ---- dfframe for run m: s[128(m+1)-512+i], s[x] = 0 for x <= 0, thr[x-1] otherwise (Tempo::do_ :1389-1416) ----
+    // ---- dfframe for run m: s[128(m+1)-512+i], s[x] = 0 for x <= 0, thr[x-1] otherwise (Tempo::do_ :1389-1416); runs
+    //      behind the song's last one get a frame of zeros (their results are never stored) ----
     {
-        float v[8];
+        constexpr int per = ACF_RUNS * ACF_PITCH / 256 + 1;
+        float v[per];
 #pragma unroll
-        for (int q = 0; q < 8; q++) {  // all eight loads in flight together; the address is clamped instead of branching
-            const long xi = 128 * (m + 1) - 512 + tid + 64 * q;
-            const float x = thr[xi > 0 ? xi - 1 : 0];
-            v[q] = (xi <= 0) ? 0.0f : x;
+        for (int q = 0; q < per; q++) {  // all loads in flight together; the address is clamped instead of branching
+            const int e = tid + 256 * q, r = e / ACF_PITCH, i = e - r * ACF_PITCH;
+            const long m = m0 + r, xi = 128 * (m + 1) - 512 + i;
+            const bool live = e < ACF_RUNS * ACF_PITCH && i < BT_WINLEN && m < n_runs && xi > 0;
+            const float x = thr[live ? xi - 1 : 0];
+            v[q] = live ? x : 0.0f;
         }
 #pragma unroll
-        for (int q = 0; q < 8; q++) {
-            const int i = tid + 64 * q;
-            df[i] = v[q];
-            if (i > 0) df1[i - 1] = v[q];
-            df[BT_WINLEN + i] = 0.0f;
-            df1[BT_WINLEN - 1 + i] = 0.0f;
+        for (int q = 0; q < per; q++) {
+            const int e = tid + 256 * q, r = e / ACF_PITCH, i = e - r * ACF_PITCH;
+            if (e < ACF_RUNS * ACF_PITCH) {
+                df[e] = v[q];
+                if (i > 0) df1[e - 1] = v[q];
+                if (i == ACF_PITCH - 1) df1[e] = 0.0f;
+            }
         }
     }
     __syncthreads();
-    // vec_autocorr (:819-828): acf[L] = (sum_{j=L}^{511} f[j-L] f[j]) / (512 - L), summed in j order.  A thread owns
-    // the lag quads (4t .. 4t+3) and (508-4t .. 511-4t) -- a long and a short one -- and runs i = j - L over the four
-    // lags of a quad at once (packed multiply, packed add: two lags per instruction).  The first factor f[i] is
-    // wave-uniform, so for runs whose frame lies inside the song it comes from SCALAR loads of the thresholded series
-    // (the kernel is bound by LDS bandwidth; a broadcast LDS read of f[i] would add to it).  The loops run to the
-    // wave-uniform bounds 512 and 256 (the smallest lag of each kind is 0 and 256) and read the zero padding behind the
-    // frame instead of predicating (x + f * 0 == x exactly, so every sum is bit-identical to the reference's).
+    // vec_autocorr (:819-828): acf[L] = (sum_{j=L}^{511} f[j-L] f[j]) / (512 - L), summed in j order.  Wavefront w owns the
+    // lags [64 w, 64 w + 64) and [448 - 64 w, 512 - 64 w) -- a long and a short quarter -- of all eight runs: lane 8 r + g
+    // has the lag octets (64 w + 8 g ..) and (504 - 64 w - 8 g ..) of run r and runs i = j - L over the eight lags of an
+    // octet at once (packed multiply, packed add: two lags per instruction).  The loops run to bounds that are uniform over
+    // the wavefront, 512 - 64 w and 64 (w + 1) steps (what its smallest lag of each kind needs; 576 together for every
+    // wavefront, where one wavefront with all lags of a run would need 512 + 256), and read the zero padding behind the
+    // frame instead of predicating (x + f * 0 == x exactly, so every sum is bit-identical to the reference's).  The first
+    // factor f[i] differs between the runs of a wavefront, so it is an LDS read too (the same address for the 8 lanes of a run).
+    const int r = lane >> 3, g = lane & 7;
+    const int la = 64 * wave + 8 * g, lb = BT_WINLEN - 8 - 64 * wave - 8 * g;
+    bt_f2 sa[4], sb[4];
     {
-        const int la = 4 * tid, lb = BT_WINLEN - 4 - 4 * tid;
-        constexpr int na = BT_WINLEN, nb = BT_WINLEN / 2;
-        bt_f2 a01 = {0.0f, 0.0f}, a23 = {0.0f, 0.0f}, b01 = {0.0f, 0.0f}, b23 = {0.0f, 0.0f};
-        if (m >= 4) {
-            const float* __restrict__ fs = thr + (128 * (m + 1) - 512) - 1;  // fs[i] == dfframe[i], wave-uniform
-            for (int i = 0; i < na; i += 16) {
-                float sv[16];
+        const int na = BT_WINLEN - 64 * wave, nb = 64 * (wave + 1);
+        const float* fr = df + r * ACF_PITCH;
+        const float* fr1 = df1 + r * ACF_PITCH;
 #pragma unroll
-                for (int u = 0; u < 16; u++) sv[u] = fs[i + u];
-                acf_block16(a01, a23, df + la + i, df1 + la + i, [&](int u) { return sv[u]; });
-            }
-            for (int i = 0; i < nb; i += 16) {
-                float sv[16];
+        for (int k = 0; k < 4; k++) { sa[k] = bt_f2{0.0f, 0.0f}; sb[k] = bt_f2{0.0f, 0.0f}; }
+        for (int i = 0; i < na; i += 16) acf_block16(sa, fr + la + i, fr1 + la + i, fr + i);
+        for (int i = 0; i < nb; i += 16) acf_block16(sb, fr + lb + i, fr1 + lb + i, fr + i);
+    }
+    __syncthreads();  // every frame has been read: its memory becomes the run's acf / acfout
+    {
+        float* acf = df + r * ACF_PITCH;
 #pragma unroll
-                for (int u = 0; u < 16; u++) sv[u] = fs[i + u];
-                acf_block16(b01, b23, df + lb + i, df1 + lb + i, [&](int u) { return sv[u]; });
-            }
-        } else {
-            for (int i = 0; i < na; i += 16) acf_block16(a01, a23, df + la + i, df1 + la + i, [&](int u) { return df[i + u]; });
-            for (int i = 0; i < nb; i += 16) acf_block16(b01, b23, df + lb + i, df1 + lb + i, [&](int u) { return df[i + u]; });
+        for (int k = 0; k < 4; k++) {
+            acf[la + 2 * k] = sa[k].x / (float)(BT_WINLEN - la - 2 * k);
+            acf[la + 2 * k + 1] = sa[k].y / (float)(BT_WINLEN - la - 2 * k - 1);
+            acf[lb + 2 * k] = sb[k].x / (float)(BT_WINLEN - lb - 2 * k);
+            acf[lb + 2 * k + 1] = sb[k].y / (float)(BT_WINLEN - lb - 2 * k - 1);
         }
-        acf[la] = a01.x / (float)(BT_WINLEN - la);
-        acf[la + 1] = a01.y / (float)(BT_WINLEN - la - 1);
-        acf[la + 2] = a23.x / (float)(BT_WINLEN - la - 2);
-        acf[la + 3] = a23.y / (float)(BT_WINLEN - la - 3);
-        acf[lb] = b01.x / (float)(BT_WINLEN - lb);
-        acf[lb + 1] = b01.y / (float)(BT_WINLEN - lb - 1);
-        acf[lb + 2] = b23.x / (float)(BT_WINLEN - lb - 2);
-        acf[lb + 3] = b23.y / (float)(BT_WINLEN - lb - 3);
     }
     __syncthreads();
+    // From here a wavefront finishes two of the runs, one after the other (nothing below for a run behind the song's end).
     // shift-invariant comb filterbank (:987-1003): the sums run a = 1 .. numelem in order, so the numelem = 4 value is
     // the numelem = 3 value continued.  Rayleigh path: terms divided by 2a - 1, weighted by rwv; the unweighted sums
     // are what checkstate weights by its Gaussian (:1110-1124).
+    for (int rr = 2 * wave; rr < 2 * wave + 2; rr++) {
+        const long m = m0 + rr;
+        if (m >= n_runs) break;  // uniform over the wavefront
+        const float* acf = df + rr * ACF_PITCH;
+        float* acfout = df1 + rr * ACF_PITCH;  // [2][BT_LAGLEN]
+        float* pre = pre_all + ((size_t)(sd.b_off / BT_STEP) + s + (size_t)m) * BT_PRE_STRIDE;
 #pragma unroll
-    for (int half = 0; half < 2; half++) {
-        const int l = tid + 64 * half;
-        float v3 = 0.0f, v4 = 0.0f, g3 = 0.0f, g4 = 0.0f;
-        if (l >= 1 && l < BT_LAGLEN - 1) {
-            float v = 0.0f, g = 0.0f;
-            for (int a = 1; a <= 4; a++) {
-                if (a == 4) { v3 = v; g3 = g; }
-                for (int b = 1; b < 2 * a; b++) {
-                    const int idx = l * a + b - 1;
-                    if (idx < BT_WINLEN) {
-                        v += acf[idx] / (2.0f * (float)a - 1.0f);
-                        g += acf[idx];
+        for (int half = 0; half < 2; half++) {
+            const int l = lane + 64 * half;
+            float v3 = 0.0f, v4 = 0.0f, g3 = 0.0f, g4 = 0.0f;
+            if (l >= 1 && l < BT_LAGLEN - 1) {
+                float v = 0.0f, gs = 0.0f;
+                for (int a = 1; a <= 4; a++) {
+                    if (a == 4) { v3 = v; g3 = gs; }
+                    for (int b = 1; b < 2 * a; b++) {
+                        const int idx = l * a + b - 1;
+                        if (idx < BT_WINLEN) {
+                            v += acf[idx] / (2.0f * (float)a - 1.0f);
+                            gs += acf[idx];
+                        }
                     }
                 }
+                v4 = v; g4 = gs;
             }
-            v4 = v; g4 = g;
+            const float rw = rwv_tab[l];
+            acfout[l] = v3 * rw;
+            acfout[BT_LAGLEN + l] = v4 * rw;
+            pre[BT_PRE_G3 + l] = g3;
+            pre[BT_PRE_G4 + l] = g4;
         }
-        const float r = rwv_tab[l];
-        acfout[0][l] = v3 * r;
-        acfout[1][l] = v4 * r;
-        pre[BT_PRE_G3 + l] = g3;
-        pre[BT_PRE_G4 + l] = g4;
-    }
-    __syncthreads();
+        // acfout[rr] is written and read by this wavefront alone; LDS operations of a wavefront complete in order
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
-    for (int which = 0; which < 2; which++) {
-        const float x[2] = {acfout[which][tid], acfout[which][tid + 64]};
-        float best;
-        int maxindex;
-        wave_argmax_last(x, &best, &maxindex);
-        if (tid == 0) {
-            const int rayparam = 43;  // (60*22050/120/256) as u32
-            const float rp = (maxindex > 0 && maxindex < BT_LAGLEN - 1) ? quad_peak_pos(acfout[which], BT_LAGLEN, maxindex)
-                                                                       : (float)rayparam;
-            pre[BT_PRE_RP3 + which] = rp;
-            pre[BT_PRE_TS3 + which] = bt_timesig(acf, (long)rp);
+        for (int which = 0; which < 2; which++) {
+            const float* ao = acfout + which * BT_LAGLEN;
+            const float x[2] = {ao[lane], ao[lane + 64]};
+            float best;
+            int maxindex;
+            wave_argmax_last(x, &best, &maxindex);
+            if (lane == 0) {
+                const int rayparam = 43;  // (60*22050/120/256) as u32
+                const float rp = (maxindex > 0 && maxindex < BT_LAGLEN - 1) ? quad_peak_pos(ao, BT_LAGLEN, maxindex)
+                                                                           : (float)rayparam;
+                pre[BT_PRE_RP3 + which] = rp;
+                pre[BT_PRE_TS3 + which] = bt_timesig(acf, (long)rp);
+            }
         }
     }
 }
@@ -542,8 +565,8 @@ void launch_beat_acf(const Batch& b, const Workspace& w, const DeviceTables& t, 
     if (b.n_songs == 0) return;
     const uint32_t max_runs = b.max_nb >= (uint32_t)BT_STEP ? (b.max_nb - BT_STEP) / BT_STEP + 1 : 0;
     if (max_runs > 0)
-        hipLaunchKernelGGL(beat_acf_kernel, dim3(max_runs, b.n_songs), dim3(64), 0, st, b.songs, w.thresholded, t.bt_rwv,
-                           w.bt_pre);
+        hipLaunchKernelGGL(beat_acf_kernel, dim3((max_runs + ACF_RUNS - 1) / ACF_RUNS, b.n_songs), dim3(256), 0, st, b.songs,
+                           w.thresholded, t.bt_rwv, w.bt_pre);
 }
 
 void launch_beat_track(const Batch& b, const Workspace& w, const DeviceTables& t, hipStream_t st) {
