@@ -16,6 +16,7 @@ SAMPLE_F32, SAMPLE_S16, SAMPLE_S32 = 0, 1, 2
 SAMPLE_RATE = 22050
 SONG_OK, SONG_TOO_SHORT = 0, 1
 METRIC_EUCLIDEAN, METRIC_COSINE, METRIC_MAHALANOBIS = 0, 1, 2
+CHAINS_AUTO, CHAINS_STEPS, CHAINS_LISTS = 0, 1, 2
 OPT_SERIAL, OPT_TAIL_MODE, OPT_PIPELINE_CHUNKS, OPT_CAND_BUDGET, OPT_ROLLOFF_EXACT_ALL, OPT_DEBUG_CHROMA, OPT_TAIL_SPLIT = 0, 1, 2, 3, 4, 5, 6
 OPT_STFT_SHAPE = 7
 OPT_FLUX_ORDER = 8
@@ -99,6 +100,11 @@ SIGNATURES = {
                                               _vp]),
     "blissgpu_group_knn_weighted_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, _vp, _vp,
                                                      C.c_uint32, _vp, _vp, _vp]),
+    "blissgpu_chains": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, C.c_uint32, C.c_int, _vp,
+                                  _vp]),
+    "blissgpu_chains_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, C.c_uint32,
+                                         C.c_int, _vp, _vp]),
+    "blissgpu_chains_plan": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.POINTER(C.c_int), _u32p]),
     "blissgpu_duplicate_groups": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.c_int, _vp, C.c_float, _vp, _u64p, _vp, _vp,
                                             C.c_uint64]),
     "blissgpu_duplicate_groups_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_int, _vp, C.c_float, _vp, _vp, _vp,

@@ -28,7 +28,8 @@ const char* const kKernelNames[K_COUNT] = {
     "dedup_next_kernel", "dedup_walk_kernel", "knn_scan_kernel", "knn_merge_kernel",
     "forest_walk_kernel", "forest_finish_kernel",
     "dup_init_kernel", "dup_join_kernel", "dup_flatten_kernel",
-    "group_knn_scan_kernel", "group_knn_merge_kernel", "group_weights_kernel"};
+    "group_knn_scan_kernel", "group_knn_merge_kernel", "group_weights_kernel",
+    "chain_step_kernel", "chain_walk_kernel"};
 }  // namespace
 
 namespace bg {
@@ -336,7 +337,7 @@ int blissgpu_ctx_destroy(blissgpu_ctx* c) {
         (void)hipFree(c->bt_rwv); (void)hipFree(c->bt_dfwv); (void)hipFree(c->chroma_bank);
         scheduler_release(c);
         c->dbg_tuning.release(); c->dbg_nbpms.release(); c->dbg_chroma.release(); c->dbg_interval.release();
-        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_next.release(); c->st_idx.release();
+        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->pl_next.release(); c->st_idx.release();
         c->st_a.release(); c->st_b.release(); c->st_m.release(); c->st_dist.release(); c->st_out.release();
         if (c->h_scalar) (void)hipHostFree(c->h_scalar);
         if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
@@ -1237,6 +1238,203 @@ int blissgpu_group_knn_weighted(const float* seeds, const uint64_t* group_offset
             e = hipMemcpyAsync(group_status, d_status, (size_t)n_groups * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(group_knn_weighted)", hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+// ---- song-to-song chains cut after k, one per seed group: song_to_song(&group, candidates, metric).take(k)
+// (src/playlist.rs:272-326) for every group in one call, without a grid barrier (kernels_chains.hip) ----
+// The lists route pays n x n pairs (one k-nearest search of the candidates among themselves) plus the walk, the steps route
+// (k - 1) x n_groups x n pairs.  LISTS is taken when c x n < (k - 1) x n_groups, c = CHAINS_LISTS_COST_NUM / _DEN = 1/2: measured
+// at n = 10^5, d = 23, k = 20 (tests/tools/chains_bench.py, profiles/chains_bench_100k.json) the two routes
+// cross between n/64 chains (break-even c = 0.33, steps faster) and n/16 (0.88, lists faster), near 2 650 chains.  c is below 1
+// because a step over few chains runs an under-filled device (80 ms per 10^10 pairs at n/64 chains against 17 at n).
+constexpr uint64_t CHAINS_LISTS_COST_NUM = 1, CHAINS_LISTS_COST_DEN = 2;
+
+// L = k + largest group - 1: entries of a candidate's list that always hold the chain's next song
+static uint64_t chains_list_len(const uint64_t* off, uint64_t n_groups, uint32_t k) {
+    uint64_t gmax = 0;
+    for (uint64_t g = 0; g < n_groups; g++) gmax = std::max(gmax, off[g + 1] - off[g]);
+    return (uint64_t)k + gmax - 1u;  // (k >= 1)
+}
+// what the lists route keeps on the device beside the outputs: the lists' indices and distances, the keys of the search that
+// makes them, and the candidates' own indices as its skip array
+static unsigned __int128 chains_lists_bytes(uint64_t n, uint64_t L) {
+    return (unsigned __int128)n * L * (sizeof(uint32_t) + sizeof(float) + sizeof(unsigned long long)) + (unsigned __int128)n * sizeof(uint32_t);
+}
+static bool chains_lists_fit(uint64_t n, uint32_t k, uint64_t L, uint64_t workspace_bytes) {
+    return k >= 2 && n > 0 && L >= 1 && L <= BLISSGPU_KNN_MAX_K && chains_lists_bytes(n, L) <= (unsigned __int128)workspace_bytes;
+}
+static int chains_route(uint64_t n_groups, uint64_t n, uint32_t k, uint64_t L, uint64_t workspace_bytes) {
+    if (!chains_lists_fit(n, k, L, workspace_bytes)) return BLISSGPU_CHAINS_STEPS;
+    const unsigned __int128 lists = (unsigned __int128)CHAINS_LISTS_COST_NUM * n;
+    const unsigned __int128 steps = (unsigned __int128)CHAINS_LISTS_COST_DEN * (k - 1u) * n_groups;
+    return lists < steps ? BLISSGPU_CHAINS_LISTS : BLISSGPU_CHAINS_STEPS;
+}
+
+// everything that can be said about the arguments without a device (every form checks it BEFORE the device is touched)
+static int chains_args_ok(const char* who, const void* seeds, const uint64_t* off, uint64_t n_groups, const void* cand, uint64_t n,
+                          uint32_t d, int metric, const float* M, uint32_t k, int route, const void* idx) {
+    if (route != BLISSGPU_CHAINS_AUTO && route != BLISSGPU_CHAINS_STEPS && route != BLISSGPU_CHAINS_LISTS)
+        return fail(BLISSGPU_ERR_INVALID, who, "unknown route");
+    int rc = group_knn_args_ok(who, seeds, off, n_groups, cand, n, d, metric, M, k, idx);
+    if (rc) return rc;
+    if (route == BLISSGPU_CHAINS_LISTS && n_groups && k >= 2 && chains_list_len(off, n_groups, k) > BLISSGPU_KNN_MAX_K)
+        return fail(BLISSGPU_ERR_INVALID, who, "the lists route needs k + largest group - 1 <= BLISSGPU_KNN_MAX_K");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_chains_plan(const uint64_t* group_offsets, uint64_t n_groups, uint64_t n, uint32_t k, uint64_t workspace_bytes,
+                         int* route, uint32_t* list_len) {
+    const char* who = "blissgpu_chains_plan";
+    const float some = 0.0f;  // (the plan reads neither seeds nor candidates)
+    uint32_t none = 0;
+    int rc = chains_args_ok(who, &some, group_offsets, n_groups, &some, n, 1, 0, nullptr, k, BLISSGPU_CHAINS_AUTO, &none);
+    if (rc) return rc;
+    if (!route) return fail(BLISSGPU_ERR_INVALID, who, "route is NULL");
+    const uint64_t L = n_groups ? chains_list_len(group_offsets, n_groups, k) : (uint64_t)k - 1u;
+    if (list_len) *list_len = (uint32_t)std::min<uint64_t>(L, 0xFFFFFFFFull);
+    *route = n_groups ? chains_route(n_groups, n, k, L, workspace_bytes) : BLISSGPU_CHAINS_STEPS;
+    return BLISSGPU_OK;
+}
+
+int blissgpu_chains_device(blissgpu_ctx* c, const float* d_seeds, const uint64_t* group_offsets, uint64_t n_groups,
+                           const float* d_cand, uint64_t n, uint32_t d, int metric, const float* d_M, const uint32_t* d_skip,
+                           uint32_t k, int route, uint32_t* d_idx, float* d_dist) {
+    const char* who = "blissgpu_chains_device";
+    int rc = chains_args_ok(who, d_seeds, group_offsets, n_groups, d_cand, n, d, metric, d_M, k, route, d_idx);
+    if (rc) return rc;
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    if (n_groups == 0) return BLISSGPU_OK;
+    CTX_ENTER(c, who);
+    const uint64_t L = chains_list_len(group_offsets, n_groups, k);
+    if (route == BLISSGPU_CHAINS_LISTS && k >= 2 && n && !chains_lists_fit(n, k, L, c->ws_limit))
+        return fail(BLISSGPU_ERR_INVALID, who, "the lists do not fit the context's workspace limit");
+    if (route == BLISSGPU_CHAINS_AUTO) route = chains_route(n_groups, n, k, L, c->ws_limit);
+    if (k < 2 || n == 0) route = BLISSGPU_CHAINS_STEPS;  // (step 0 alone: nothing to walk)
+    int diag = 0;
+    if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
+        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
+            diag = is_diag(c->m_cache.data(), d);
+        } else {
+            std::vector<float> hM((size_t)d * d);
+            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            diag = is_diag(hM.data(), d);
+        }
+    }
+    // pl_chain: minima u64[G] | flags u32[4] ([0] NaN on a chain, [1] a list too short) | offsets u32[G + 1] | step 0: idx u32[G],
+    // dist f32[G] | lists route: the candidates' own indices u32[n], lists u32[n][L], their distances f32[n][L]
+    const size_t G = (size_t)n_groups, out_n = G * k;
+    const bool lists = route == BLISSGPU_CHAINS_LISTS;
+    const size_t o_flags = G * sizeof(unsigned long long), o_goff = o_flags + 4 * sizeof(uint32_t);
+    const size_t o_idx0 = o_goff + (G + 1) * sizeof(uint32_t), o_dist0 = o_idx0 + G * sizeof(uint32_t);
+    const size_t o_self = o_dist0 + G * sizeof(float), o_lists = o_self + (lists ? (size_t)n * sizeof(uint32_t) : 0);
+    const size_t o_ldist = o_lists + (lists ? (size_t)n * L * sizeof(uint32_t) : 0);
+    const size_t total = o_ldist + (lists && d_dist ? (size_t)n * L * sizeof(float) : 0);
+    rc = c->pl_chain.ensure(total);
+    if (rc) return rc;
+    unsigned long long* best = reinterpret_cast<unsigned long long*>(c->pl_chain.p);
+    uint32_t* flags = reinterpret_cast<uint32_t*>(c->pl_chain.p + o_flags);
+    uint32_t* d_goff = reinterpret_cast<uint32_t*>(c->pl_chain.p + o_goff);
+    uint32_t* idx0 = reinterpret_cast<uint32_t*>(c->pl_chain.p + o_idx0);
+    float* dist0 = d_dist ? reinterpret_cast<float*>(c->pl_chain.p + o_dist0) : nullptr;
+    std::vector<uint32_t> table(G + 1 + (lists ? (size_t)n : 0));
+    for (size_t g = 0; g <= G; g++) table[g] = (uint32_t)group_offsets[g];
+    for (size_t j = 0; lists && j < (size_t)n; j++) table[G + 1 + j] = (uint32_t)j;
+    HIP_TRY(hipMemcpyAsync(d_goff, table.data(), (G + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (lists)
+        HIP_TRY(hipMemcpyAsync(c->pl_chain.p + o_self, table.data() + G + 1, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    auto pad = [&]() -> hipError_t {  // every row: 0xFFFFFFFF / +inf until a step writes it
+        hipError_t e = hipMemsetAsync(d_idx, 0xFF, out_n * sizeof(uint32_t), c->stream);
+        if (e == hipSuccess && d_dist) e = hipMemsetD32Async((hipDeviceptr_t)d_dist, 0x7F800000, out_n, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(flags, 0, 4 * sizeof(uint32_t), c->stream);
+        return e;
+    };
+    HIP_TRY(pad());
+    // step 0: the group search with k = 1 (it synchronises: the tables above have left the host when it returns)
+    rc = group_knn_run(c, who, d_seeds, group_offsets, n_groups, d_cand, n, d, metric, d_M, false, nullptr, nullptr, d_skip, 1u, idx0,
+                       dist0);
+    if (rc) return rc;
+    uint32_t h_flags[4] = {0, 0, 0, 0};
+    if (lists) {
+        uint32_t* self = reinterpret_cast<uint32_t*>(c->pl_chain.p + o_self);
+        uint32_t* l_idx = reinterpret_cast<uint32_t*>(c->pl_chain.p + o_lists);
+        float* l_dist = d_dist ? reinterpret_cast<float*>(c->pl_chain.p + o_ldist) : nullptr;
+        rc = blissgpu_knn_device(c, d_cand, n, d_cand, n, d, metric, d_M, self, (uint32_t)L, l_idx, l_dist);
+        if (rc == BLISSGPU_OK) {
+            {
+                Prof p(c, K_CHAIN_WALK);
+                launch_chain_walk(l_idx, l_dist, (uint32_t)L, d_goff, d_skip, idx0, dist0, (uint32_t)n_groups, k, d_idx, d_dist, flags + 1,
+                                  c->stream);
+            }
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            if (!h_flags[1]) return BLISSGPU_OK;
+        } else if (rc != BLISSGPU_ERR_NAN) {
+            return rc;
+        }
+        // the all-pairs search met a NaN that perhaps no chain evaluates (or a list was too short): the steps decide
+        HIP_TRY(pad());
+    }
+    const ChainPlan plan = chain_plan(n_groups, n, c->n_cus);
+    HIP_TRY(hipMemsetAsync(best, 0xFF, G * sizeof(unsigned long long), c->stream));
+    {
+        Prof p(c, K_CHAIN_STEP);
+        launch_chain_first(idx0, dist0, (uint32_t)n_groups, k, d_idx, d_dist, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    const uint32_t steps = (uint32_t)std::min<uint64_t>(k, n);  // (a chain is no longer than the candidates)
+    for (uint32_t t = 1; t < steps; t++) {
+        Prof p(c, K_CHAIN_STEP);
+        launch_chain_step(d_cand, (uint32_t)n, d, metric, d_M, diag, d_goff, d_skip, (uint32_t)n_groups, k, t, plan, d_idx, d_dist, best,
+                          flags, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (h_flags[0]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance (the reference panics here)");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_chains(const float* seeds, const uint64_t* group_offsets, uint64_t n_groups, const float* cand, uint64_t n, uint32_t d,
+                    int metric, const float* M, const uint32_t* skip, uint32_t k, int route, uint32_t* idx, float* dist) {
+    const char* who = "blissgpu_chains";
+    int rc = chains_args_ok(who, seeds, group_offsets, n_groups, cand, n, d, metric, M, k, route, idx);
+    if (rc) return rc;
+    if (n_groups == 0) return BLISSGPU_OK;
+    const uint64_t n_seeds = group_offsets[n_groups];
+    if (skip)
+        for (uint64_t i = 0; i < n_seeds; i++)
+            if (skip[i] != 0xFFFFFFFFu && skip[i] >= n) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    const size_t out_n = (size_t)n_groups * k;
+    const float* dM = nullptr;
+    rc = c->st_b.ensure(std::max<size_t>(1, n * d));
+    if (!rc) rc = c->st_a.ensure(std::max<size_t>(1, n_seeds * d));
+    if (!rc) rc = c->st_idx.ensure(out_n + (skip ? n_seeds : 0));
+    if (!rc && dist) rc = c->st_dist.ensure(out_n);
+    if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
+    if (rc) return rc;
+    uint32_t *d_idx = c->st_idx.p, *d_skip = skip ? c->st_idx.p + out_n : nullptr;
+    hipError_t e = hipSuccess;
+    if (n) e = hipMemcpyAsync(c->st_b.p, cand, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && n_seeds) e = hipMemcpyAsync(c->st_a.p, seeds, n_seeds * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && skip && n_seeds) e = hipMemcpyAsync(d_skip, skip, n_seeds * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(chains)", hipGetErrorString(e));
+    if (!rc)
+        rc = blissgpu_chains_device(c, c->st_a.p, group_offsets, n_groups, c->st_b.p, n, d, metric, dM, d_skip, k, route, d_idx,
+                                    dist ? c->st_dist.p : nullptr);
+    if (!rc) {
+        e = hipMemcpyAsync(idx, d_idx, out_n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(chains)", hipGetErrorString(e));
     }
     (void)hipStreamSynchronize(c->stream);
     return rc;

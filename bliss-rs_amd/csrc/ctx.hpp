@@ -263,6 +263,7 @@ struct blissgpu_ctx {
     bg::DevBuf<uint32_t> pl_next;                  // dedup: next[] of every playlist position
     bg::DevBuf<uint8_t> pl_tmp;
     bg::DevBuf<unsigned long long> pl_slots;
+    bg::DevBuf<uint8_t> pl_chain;                  // chains: offsets, step 0, minima, and the candidates' lists of the lists route
     bg::DevBuf<float> st_a, st_b, st_m, st_dist;   // staging of the host-pointer distance / playlist forms
     bg::DevBuf<uint8_t> st_out;
     bg::DevBuf<uint32_t> st_idx;                   // staging of the dedup form: n_kept | kept | seq | meta

@@ -120,6 +120,7 @@ enum KernelId : int {
     K_DUP_INIT, K_DUP_JOIN, K_DUP_FLATTEN,  // duplicate groups of a collection (kernels_duplicates.hip)
     K_GROUP_KNN_SCAN, K_GROUP_KNN_MERGE,    // k-nearest search per seed group (kernels_group_knn.hip)
     K_GROUP_WEIGHTS,                        // variance-based weights of every seed group (kernels_group_knn.hip)
+    K_CHAIN_STEP, K_CHAIN_WALK,             // song-to-song chains cut after k (kernels_chains.hip)
     K_COUNT
 };
 
@@ -268,6 +269,28 @@ void launch_group_knn_merge(const unsigned long long* part, const uint32_t* list
 // W[g][0..d) = the diagonal of variance_based_weight_matrix of group g's seed rows, ones (status 1) under two seeds; status may be NULL
 void launch_group_weights(const float* S, const uint32_t* goff, uint64_t n_groups, uint32_t d, float* W, int32_t* status,
                           hipStream_t st);
+// song-to-song chains cut after k, one per seed group (kernels_chains.hip).  Step 0 is the group search with k = 1; a later step
+// t reads idx[chain][0 .. t) and writes idx / dist [chain][t], directly or -- several workgroups per chain -- through the
+// 64-bit minima best[n_chains] (all KNN_NONE before the first step; reset by the step's second launch).  A NaN among the
+// distances a chain evaluates sets *nan_flag
+struct ChainPlan {
+    uint32_t qb;                // chains per workgroup
+    uint32_t n_split;           // workgroups that share a chain's candidates
+    uint32_t blocks_per_split;  // 256-candidate blocks each of them walks
+    uint32_t grid_cb;           // chain blocks in the grid (the kernel strides over the rest)
+};
+ChainPlan chain_plan(uint64_t n_chains, uint64_t n, int n_cus);
+void launch_chain_step(const float* X, uint32_t n, uint32_t d, int metric, const float* M, int m_is_diag, const uint32_t* goff,
+                       const uint32_t* skip, uint32_t n_chains, uint32_t k, uint32_t t, const ChainPlan& p, uint32_t* idx,
+                       float* dist, unsigned long long* best, uint32_t* nan_flag, hipStream_t st);
+// column 0 of idx / dist from step 0's [n_chains] arrays
+void launch_chain_first(const uint32_t* idx0, const float* dist0, uint32_t n_chains, uint32_t k, uint32_t* idx, float* dist,
+                        hipStream_t st);
+// the whole chains from the candidates' own k-nearest lists ([n][L], list c without c): column 0 as above, then the first entry
+// of the current song's list that the chain has neither taken nor skipped; *short_flag: a list was too short to tell
+void launch_chain_walk(const uint32_t* lists, const float* list_dist, uint32_t L, const uint32_t* goff, const uint32_t* skip,
+                       const uint32_t* first, const float* first_dist, uint32_t n_chains, uint32_t k, uint32_t* idx, float* dist,
+                       uint32_t* short_flag, hipStream_t st);
 // duplicate groups (kernels_duplicates.hip): the split of the triangle of tile pairs for n rows, then the three launches.
 // `label` doubles as the union-find's parent array; *n_pairs counts the edges, *cursor hands out pair-list slots (both zeroed
 // by the init launch); a NaN distance of a pair i < j sets *nan_flag

@@ -432,6 +432,40 @@ class Context:
         self._post()
         return idx, dist
 
+    def chains(self, S, offsets, X, k: int, metric: str = "euclidean", M=None, skip=None, route: str = "auto"):
+        """The first k songs of song_to_song(group, X without the group's skipped rows, metric) (src/playlist.rs:272-326) for
+        every seed GROUP in one call: group g's seeds are the rows offsets[g] .. offsets[g + 1] of S (offsets: a HOST sequence of
+        G + 1 integers starting at 0).  Song 0 is the candidate closest to the seed set (group_knn's score), song t the candidate
+        not yet taken that is closest to song t - 1; equal distances go to the lower index.  -> (idx int32 [G, k], dist float32
+        [G, k]) on the device; rows with fewer than k eligible candidates end in -1 (the library's 0xFFFFFFFF) / inf.  skip:
+        int32 tensor with one candidate index per SEED ROW, -1 = none, or None.  route: "auto", "steps" (a launch per step) or
+        "lists" (the candidates' own k-nearest lists, then one walk); the result does not depend on it.  Raises
+        BlissGpuError(ERR_NAN) for a NaN among the distances a chain evaluates (synchronises for that check)."""
+        import numpy as np
+
+        from .playlist import _METRICS, _ROUTES
+
+        torch = self.torch
+        assert S.is_cuda and X.is_cuda and S.dtype == torch.float32 and X.dtype == torch.float32
+        assert S.dim() == 2 and X.dim() == 2 and S.shape[1] == X.shape[1]
+        S, X = S.contiguous(), X.contiguous()
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1)).astype(np.uint64)
+        assert off.shape[0] >= 1 and int(off[-1]) == S.shape[0]
+        G, n, k = off.shape[0] - 1, X.shape[0], int(k)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        if skip is not None:
+            assert skip.is_cuda and skip.dtype == torch.int32 and skip.shape[0] == S.shape[0]
+            skip = skip.contiguous()
+        if M is not None:
+            M = M.contiguous()
+        idx = torch.empty((G, max(k, 0)), dtype=torch.int32, device=X.device)
+        dist = torch.empty((G, max(k, 0)), dtype=torch.float32, device=X.device)
+        self._pre()
+        _ffi.check(self._L.blissgpu_chains_device(self._h, ptr(S), off.ctypes.data, G, ptr(X), n, X.shape[1], _METRICS[metric],
+                                                  ptr(M), ptr(skip), k, _ROUTES[route], ptr(idx), ptr(dist)))
+        self._post()
+        return idx, dist
+
     def duplicate_labels(self, x, meta=None, metric: str = "euclidean", m=None, threshold=0.05, max_pairs: int = 0):
         """Which rows of x are the same song (blissgpu_duplicate_groups_device): the pair i < j is an edge when its distance
         is < threshold or meta[i] != 0 and meta[i] == meta[j] (int32 keys, playlist.meta_keys; None: no such rule).  ->

@@ -438,6 +438,57 @@ def group_playlists(db: Conn, k: int, by: str = "album", metric_builder=playlist
     return {key: [(songs[int(j)].path, float(v)) for j, v in zip(idx[g], dist[g]) if j >= 0] for g, key in enumerate(keys)}
 
 
+def chain_playlists(db: Conn, k: int, by: str = "song", metric_builder=playlist.euclidean_distance, groups=None,
+                    song_paths: Sequence[str] = None):
+    """A k-song "journey" playlist starting at every song (album, artist, album artist, genre) of a library, or at arbitrary
+    seed sets: {key: [(path, distance), ...]} where entry `key` is
+    `playlist_from_custom(db, paths, metric_builder, song_to_song, deduplicate=False)[len(paths):][:k]` (src/playlist.rs:272-326,
+    src/library.rs:803-850: the song closest to the SET of initial songs, then from each song to the closest one not played
+    yet, the initial songs themselves left out) with the distance that chose each song.  The library is read once and ONE
+    device call (playlist.chain_order) answers every key: k steps, not one per song of the library.
+
+    by="song": a chain for every analysed song of FeaturesVersion.LATEST, or for `song_paths` only, keyed by path; each song
+    skips its own row.  `by` in album / artist / album_artist / genre, or `groups` = {name: [paths]}: as group_playlists.  An
+    unknown path is the ProviderError playlist_from_custom raises.  VarianceWeights and ForestOptions are refused:
+    song_to_song rebuilds a one-song metric after the first step."""
+    why = "song_to_song rebuilds its metric from one song after the first step (:285-295)"
+    playlist._no_forest(metric_builder, why)
+    playlist._no_variance(metric_builder, why)
+    if groups is None and by != "song" and by not in _GROUP_COLUMNS:
+        raise ValueError(f"by must be 'song' or one of {_GROUP_COLUMNS}")
+    songs, X = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
+    metric, m = playlist._metric_of(metric_builder)
+    row_of = {s.path: i for i, s in enumerate(songs)}
+    members = {}
+    if groups is not None:
+        for name, paths in groups.items():
+            for p in paths:
+                if p not in row_of:
+                    raise ProviderError(f"song '{p}' has not been analyzed")
+            members[name] = [row_of[p] for p in paths]
+    elif by == "song":
+        if song_paths is None:
+            members = {s.path: [i] for i, s in enumerate(songs)}
+        else:
+            for p in song_paths:
+                if p not in row_of:
+                    raise ProviderError(f"song '{p}' has not been analyzed")
+                members[p] = [row_of[p]]
+    else:
+        for i, s in enumerate(songs):
+            key = getattr(s, by)
+            if key is not None:
+                members.setdefault(key, []).append(i)
+    if not members:
+        return {}
+    keys = list(members)
+    offsets = np.zeros(len(keys) + 1, np.int64)
+    offsets[1:] = np.cumsum([len(members[key]) for key in keys])
+    rows = np.asarray([i for key in keys for i in members[key]], np.int64)
+    idx, dist = playlist.chain_order((X[rows].reshape(rows.shape[0], X.shape[1]), offsets), X, k, metric, m, skip=rows)
+    return {key: [(songs[int(j)].path, float(v)) for j, v in zip(idx[g], dist[g]) if j >= 0] for g, key in enumerate(keys)}
+
+
 def duplicate_songs(db: Conn, distance_threshold: float = None, metric_builder=playlist.euclidean_distance) -> List[List[Song]]:
     """Which songs of the library are the same song: the duplicate rule of `dedup_playlist_custom_distance`
     (src/playlist.rs:381-388: closer than the threshold, default 0.05, or the same `Some` title and artist) over every pair

@@ -66,6 +66,7 @@ def mahalanobis_distance_builder(m) -> Callable[[np.ndarray, np.ndarray], float]
 
 
 _METRICS = {"euclidean": _ffi.METRIC_EUCLIDEAN, "cosine": _ffi.METRIC_COSINE, "mahalanobis": _ffi.METRIC_MAHALANOBIS}
+_ROUTES = {"auto": _ffi.CHAINS_AUTO, "steps": _ffi.CHAINS_STEPS, "lists": _ffi.CHAINS_LISTS}  # chain_order
 
 
 def pairwise_distances(A, B, metric="euclidean", m=None) -> np.ndarray:
@@ -355,8 +356,16 @@ def closest_to_songs_order(seeds, candidates, metric="euclidean", m=None):
     return order, dist
 
 
-def song_to_song_order(seeds, candidates, metric="euclidean", m=None) -> np.ndarray:
-    """Index form of song_to_song."""
+def song_to_song_order(seeds, candidates, metric="euclidean", m=None, k=None) -> np.ndarray:
+    """Index form of song_to_song.  `k`: only the first k songs of the chain, through one chain_order call (k steps instead
+    of one per candidate); None walks the whole pool."""
+    if k is not None:
+        X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
+        k = min(int(k), X.shape[0])
+        if k < 1:
+            return np.zeros(0, np.uint32)
+        idx, _ = chain_order([np.atleast_2d(np.asarray(seeds, dtype=np.float32))], X, k, metric, m)
+        return idx[0][idx[0] >= 0].astype(np.uint32)
     S = np.ascontiguousarray(np.atleast_2d(seeds), dtype=np.float32)
     X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
     order = np.empty(X.shape[0], np.uint32)
@@ -385,15 +394,16 @@ def closest_to_songs(initial_songs, candidate_songs, metric_builder=euclidean_di
     return [candidate_songs[i] for i in order]
 
 
-def song_to_song(initial_songs, candidate_songs, metric_builder=euclidean_distance):
-    """src/playlist.rs:272-326: each song is followed by the remaining song closest to it."""
+def song_to_song(initial_songs, candidate_songs, metric_builder=euclidean_distance, number_songs=None):
+    """src/playlist.rs:272-326: each song is followed by the remaining song closest to it.  `number_songs`: the first that
+    many songs only (the reference's iterator with .take(number_songs)), computed in that many steps."""
     _no_forest(metric_builder, "song_to_song rebuilds its metric from one song after the first step (:285-295)")
     _no_variance(metric_builder, "song_to_song rebuilds its metric from one song after the first step (:285-295)")
     candidate_songs = list(candidate_songs)
     if not candidate_songs:
         return []
     metric, m = _metric_of(metric_builder)
-    order = song_to_song_order(_matrix(initial_songs), _matrix(candidate_songs), metric, m)
+    order = song_to_song_order(_matrix(initial_songs), _matrix(candidate_songs), metric, m, k=number_songs)
     return [candidate_songs[i] for i in order]
 
 
@@ -481,6 +491,33 @@ def _seed_groups(seed_groups):
     return (np.ascontiguousarray(np.concatenate(full)) if full else None), off
 
 
+def _group_skip(skip, off, n):
+    """The `skip` argument of nearest_to_groups / chain_order -> None or u32[seed rows] (0xFFFFFFFF: none): one array of
+    candidate indices per group, or one flat array with an entry per seed row (-1: none)."""
+    if skip is None:
+        return None
+    G, total = off.shape[0] - 1, int(off[-1])
+    if isinstance(skip, np.ndarray) and skip.dtype != object and skip.ndim == 1 or \
+            (len(skip) != G or total == G) and all(np.ndim(s) == 0 for s in skip):
+        flat = np.asarray(skip, dtype=np.int64).reshape(-1)  # one entry per seed row
+        if flat.shape[0] != total:
+            raise ValueError("a flat skip needs one entry per seed row")
+    else:
+        if len(skip) != G:
+            raise ValueError("skip needs one index array per group")
+        flat = np.full(total, -1, np.int64)
+        for g, sk in enumerate(skip):
+            sk = np.unique(np.asarray(sk, dtype=np.int64).reshape(-1))
+            sk = sk[sk != -1]
+            a, b = int(off[g]), int(off[g + 1])
+            if sk.shape[0] > b - a:
+                raise ValueError(f"group {g} skips {sk.shape[0]} candidates but has {b - a} seeds (one skip per seed row)")
+            flat[a:a + sk.shape[0]] = sk
+    if ((flat < -1) | (flat >= max(n, 0))).any():
+        raise ValueError("skip entries must be candidate indices or -1")
+    return np.where(flat < 0, 0xFFFFFFFF, flat).astype(np.uint32)
+
+
 def nearest_to_groups(seed_groups, candidates, k, metric="euclidean", m=None, skip=None):
     """The k nearest candidates of every seed GROUP in one device call, without a groups x candidates matrix: row g of the
     result is closest_to_songs(seed_groups[g], candidates without skip[g], metric) (src/playlist.rs:36-59, 256-270) cut
@@ -515,28 +552,8 @@ def nearest_to_groups(seed_groups, candidates, k, metric="euclidean", m=None, sk
     if not 1 <= d <= 64:
         raise ValueError("d must be 1 .. 64")
     G, total = off.shape[0] - 1, int(off[-1])
-    skip_p = None
-    if skip is not None:
-        if isinstance(skip, np.ndarray) and skip.dtype != object and skip.ndim == 1 or \
-                (len(skip) != G or total == G) and all(np.ndim(s) == 0 for s in skip):
-            flat = np.asarray(skip, dtype=np.int64).reshape(-1)  # one entry per seed row
-            if flat.shape[0] != total:
-                raise ValueError("a flat skip needs one entry per seed row")
-        else:
-            if len(skip) != G:
-                raise ValueError("skip needs one index array per group")
-            flat = np.full(total, -1, np.int64)
-            for g, sk in enumerate(skip):
-                sk = np.unique(np.asarray(sk, dtype=np.int64).reshape(-1))
-                sk = sk[sk != -1]
-                a, b = int(off[g]), int(off[g + 1])
-                if sk.shape[0] > b - a:
-                    raise ValueError(f"group {g} skips {sk.shape[0]} candidates but has {b - a} seeds (one skip per seed row)")
-                flat[a:a + sk.shape[0]] = sk
-        if ((flat < -1) | (flat >= max(n, 0))).any():
-            raise ValueError("skip entries must be candidate indices or -1")
-        skip = np.where(flat < 0, 0xFFFFFFFF, flat).astype(np.uint32)
-        skip_p = skip.ctypes.data
+    skip = _group_skip(skip, off, n)
+    skip_p = None if skip is None else skip.ctypes.data
     mp = None
     if metric == "mahalanobis":
         if m is None:
@@ -589,6 +606,20 @@ def group_variance_weights(seed_groups):
     return weights, status != 0
 
 
+def _member_skip(groups, candidate_songs):
+    """One entry per member of every group: the first candidate that == it (Song: PartialEq), -1 when there is none."""
+    skip = np.full(sum(len(g) for g in groups), -1, np.int64)
+    row = 0
+    for g in groups:
+        for s in g:
+            for j, c in enumerate(candidate_songs):
+                if _song_of(c) == _song_of(s):
+                    skip[row] = j
+                    break
+            row += 1
+    return skip
+
+
 def group_playlists(groups, candidate_songs, k, metric_builder=euclidean_distance, exclude_members=True):
     """For every group of songs, closest_to_songs(group, candidate_songs without the group's songs, metric_builder)[..k]
     (src/playlist.rs:256-270) -- a playlist "in the vibe of these songs" per album, artist or saved playlist, all of them
@@ -605,18 +636,77 @@ def group_playlists(groups, candidate_songs, k, metric_builder=euclidean_distanc
     metric, m = (metric_builder, None) if isinstance(metric_builder, VarianceWeights) else _metric_of(metric_builder)
     X = _matrix(candidate_songs)
     seeds = [_matrix(g) if g else np.zeros((0, X.shape[1]), np.float32) for g in groups]
-    skip = None
-    if exclude_members:
-        skip = np.full(sum(len(g) for g in groups), -1, np.int64)
-        row = 0
-        for g in groups:
-            for s in g:
-                for j, c in enumerate(candidate_songs):
-                    if _song_of(c) == _song_of(s):
-                        skip[row] = j
-                        break
-                row += 1
+    skip = _member_skip(groups, candidate_songs) if exclude_members else None
     idx, _ = nearest_to_groups(seeds, X, k, metric, m, skip)
+    return [[candidate_songs[j] for j in row if j >= 0] for row in idx]
+
+
+def chain_order(seed_groups, candidates, k, metric="euclidean", m=None, skip=None, route="auto"):
+    """The first k songs of song_to_song(seed_groups[g], candidates without skip[g], metric) (src/playlist.rs:272-326) for
+    every seed GROUP in one device call (blissgpu_chains): song 0 is the candidate closest to the group's seed set (the score
+    of nearest_to_groups), song t the candidate not yet in the chain that is closest to song t - 1; equal distances go to the
+    lower index.  -> (idx int64[G, k], dist float32[G, k]): dist[g][t] is the distance that chose idx[g][t]; rows with fewer
+    than k eligible candidates end in -1 / inf.  `seed_groups` and `skip` as for nearest_to_groups.  `route`: "auto", "steps"
+    (one launch per step over every chain) or "lists" (the candidates' own k-nearest lists, then one walk; needs
+    k + largest group - 1 <= 1024); the result does not depend on it.  A NaN distance on a chain raises ValueError (the
+    reference's argmin().unwrap() panic).  VarianceWeights and ForestOptions are refused: song_to_song rebuilds a one-song
+    metric after the first step."""
+    _no_forest(metric, "song_to_song rebuilds its metric from one song after the first step (:285-295)")
+    _no_variance(metric, "song_to_song rebuilds its metric from one song after the first step (:285-295)")
+    S, off = _seed_groups(seed_groups)
+    X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
+    if X.ndim != 2 or (S is not None and S.shape[1] != X.shape[1]):
+        raise ValueError("seed groups and candidates must be [s_g, d] and [n, d]")
+    if metric not in _METRICS:
+        raise ValueError(f"unknown metric {metric!r}")
+    if route not in _ROUTES:
+        raise ValueError(f"route must be one of {tuple(_ROUTES)}")
+    k = int(k)
+    if not 1 <= k <= 1024:
+        raise ValueError("k must be 1 .. 1024")
+    n, d = X.shape
+    if not 1 <= d <= 64:
+        raise ValueError("d must be 1 .. 64")
+    G = off.shape[0] - 1
+    if route == "lists" and k >= 2 and G and k + int(np.diff(off.astype(np.int64)).max()) - 1 > 1024:
+        raise ValueError("the lists route needs k + largest group - 1 <= 1024")
+    skip = _group_skip(skip, off, n)
+    skip_p = None if skip is None else skip.ctypes.data
+    mp = None
+    if metric == "mahalanobis":
+        if m is None:
+            raise ValueError("mahalanobis needs m")
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        if m.shape != (d, d):
+            raise ValueError("m must be [d, d]")
+        mp = m.ctypes.data
+    idx, dist = np.empty((G, k), np.uint32), np.empty((G, k), np.float32)
+    try:
+        _ffi.check(_ffi.lib().blissgpu_chains(None if S is None else S.ctypes.data, off.ctypes.data, G, X.ctypes.data, n, d,
+                                              _METRICS[metric], mp, skip_p, k, _ROUTES[route], idx.ctypes.data, dist.ctypes.data))
+    except _ffi.BlissGpuError as e:
+        _nan_to_panic(e)
+    out = idx.astype(np.int64)
+    out[idx == 0xFFFFFFFF] = -1
+    return out, dist
+
+
+def song_chains(groups, candidate_songs, k, metric_builder=euclidean_distance, exclude_members=True):
+    """For every group of songs, the first k songs of song_to_song(group, candidate_songs without the group's songs,
+    metric_builder) (src/playlist.rs:272-326) -- a playlist that starts "in the vibe of these songs" and then wanders from
+    each song to its nearest remaining neighbour, all groups in one device call.  `exclude_members` as for group_playlists."""
+    _no_forest(metric_builder, "song_to_song rebuilds its metric from one song after the first step (:285-295)")
+    _no_variance(metric_builder, "song_to_song rebuilds its metric from one song after the first step (:285-295)")
+    groups, candidate_songs = [list(g) for g in groups], list(candidate_songs)
+    if not groups:
+        return []
+    if not candidate_songs:
+        return [[] for _ in groups]
+    metric, m = _metric_of(metric_builder)
+    X = _matrix(candidate_songs)
+    seeds = [_matrix(g) if g else np.zeros((0, X.shape[1]), np.float32) for g in groups]
+    skip = _member_skip(groups, candidate_songs) if exclude_members else None
+    idx, _ = chain_order(seeds, X, k, metric, m, skip)
     return [[candidate_songs[j] for j in row if j >= 0] for row in idx]
 
 

@@ -401,6 +401,48 @@ int blissgpu_group_knn_weighted_device(blissgpu_ctx *ctx, const float *d_seeds, 
                                        const uint32_t *d_skip, uint32_t k, uint32_t *d_idx, float *d_dist,
                                        int32_t *d_group_status);
 
+/* ---- song-to-song chains cut after k, one per seed group (src/playlist.rs:272-326) ----
+ * Row g of idx / dist ([n_groups][k], dist may be NULL) is the first k songs of song_to_song(&group g, candidates without the
+ * group's skipped rows, metric) -- a "journey" playlist starting at every song, album or saved playlist of a library, in one
+ * call.  seeds, group_offsets (a HOST pointer in every form) and skip are blissgpu_group_knn's.  For group g:
+ *   idx[g][0]  the eligible candidate with the smallest set distance to the group's seeds: the sequential f32 sum in seed
+ *              order, bit for bit blissgpu_set_distance (an empty group scores +0.0 everywhere: the first eligible candidate);
+ *   idx[g][t]  t >= 1: the eligible candidate not yet taken by this chain with the smallest 0.0f + metric(cand[idx[g][t - 1]],
+ *              cand[j]), bit for bit what blissgpu_song_to_song evaluates;
+ * dist[g][t] is the winning value.  Among equal values the lowest candidate index wins (-0.0 and +0.0 are equal).  A row with
+ * fewer than k eligible candidates ends in idx 0xFFFFFFFF / dist +inf.  BLISSGPU_ERR_NAN is returned exactly when a chain
+ * evaluates a NaN within the steps it runs (the reference's argmin().unwrap() panic); the distances FROM the k-th song, and those
+ * to skipped or already taken candidates, are never looked at.  Metrics: euclidean, cosine, Mahalanobis with one M.
+ * 1 <= k <= BLISSGPU_KNN_MAX_K, 1 <= d <= 64, n < 2^32 - 1, fewer than 2^32 seeds and 2^32 - 1 groups; n_groups == 0 or n == 0
+ * is BLISSGPU_OK (n == 0: every row is padding).  Arguments are checked before the device is touched, the host form's skip on
+ * the host.
+ * route picks how the steps after the first are computed; the result and the error do not depend on it:
+ *   BLISSGPU_CHAINS_STEPS  one launch per step over every chain (two when several workgroups share a chain's candidates):
+ *                          (k - 1) x n_groups x n pairs, no grid barrier, no workspace beyond O(n_groups);
+ *   BLISSGPU_CHAINS_LISTS  the L = k + largest group - 1 nearest candidates of EVERY candidate (blissgpu_knn over the candidates
+ *                          themselves, n x n pairs), then one walk over those lists.  Needs L <= BLISSGPU_KNN_MAX_K (else
+ *                          BLISSGPU_ERR_INVALID, before the device is touched) and 16 n L + 4 n bytes within the context's
+ *                          workspace limit (else BLISSGPU_ERR_INVALID).  A NaN met by the all-pairs search that no chain
+ *                          evaluates does not fail the call: it is then answered by steps;
+ *   BLISSGPU_CHAINS_AUTO   what blissgpu_chains_plan says for the context's workspace limit. */
+#define BLISSGPU_CHAINS_AUTO 0
+#define BLISSGPU_CHAINS_STEPS 1
+#define BLISSGPU_CHAINS_LISTS 2
+int blissgpu_chains(const float *seeds, const uint64_t *group_offsets, uint64_t n_groups, const float *cand, uint64_t n,
+                    uint32_t d, int metric, const float *M, const uint32_t *skip, uint32_t k, int route, uint32_t *idx,
+                    float *dist);
+/* Device-resident form (device pointers, d_skip included; group_offsets stays a host pointer); synchronises the context's
+ * stream before returning (the NaN / skip check). */
+int blissgpu_chains_device(blissgpu_ctx *ctx, const float *d_seeds, const uint64_t *group_offsets, uint64_t n_groups,
+                           const float *d_cand, uint64_t n, uint32_t d, int metric, const float *d_M, const uint32_t *d_skip,
+                           uint32_t k, int route, uint32_t *d_idx, float *d_dist);
+/* The route BLISSGPU_CHAINS_AUTO takes with a workspace limit of workspace_bytes: a pure function of the sizes, device-free.
+ * *list_len (may be NULL) = k + largest group - 1.  *route = BLISSGPU_CHAINS_LISTS when k >= 2, *list_len <=
+ * BLISSGPU_KNN_MAX_K, the lists fit workspace_bytes and c x n < (k - 1) x n_groups -- c the measured cost of a pair of the lists
+ * route in pairs of a step; BLISSGPU_CHAINS_STEPS otherwise. */
+int blissgpu_chains_plan(const uint64_t *group_offsets, uint64_t n_groups, uint64_t n, uint32_t k, uint64_t workspace_bytes,
+                         int *route, uint32_t *list_len);
+
 /* ---- duplicate songs of a whole collection ----
  * The duplicate rule of dedup_playlist_custom_distance (src/playlist.rs:381-388) applied to EVERY pair of the n x d matrix x
  * instead of the neighbours of an ordered playlist: the pair (i, j), i < j, is an edge when D[i][j] < threshold (D[i][j] is bit
