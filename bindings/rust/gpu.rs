@@ -164,6 +164,14 @@ pub mod sys {
                                                   n_groups: u64, d_cand: *const f32, n: u64, d: u32, d_weights: *const f32,
                                                   d_skip: *const u32, k: u32, d_idx: *mut u32, d_dist: *mut f32,
                                                   d_group_status: *mut i32) -> c_int;
+        // the k nearest ALBUMS of every seed group: closest_album_to_group cut after k albums
+        pub fn blissgpu_album_knn(seeds: *const f32, group_offsets: *const u64, n_groups: u64, cand: *const f32, n: u64, d: u32,
+                                  album_of: *const u32, n_albums: u64, skip: *const u32, k: u32, idx: *mut u32, dist: *mut f32,
+                                  group_means: *mut f32, centroids: *mut f32) -> c_int;
+        pub fn blissgpu_album_knn_device(ctx: *mut blissgpu_ctx, d_seeds: *const f32, group_offsets: *const u64, n_groups: u64,
+                                         d_cand: *const f32, n: u64, d: u32, d_album_of: *const u32, n_albums: u64,
+                                         d_skip: *const u32, k: u32, d_idx: *mut u32, d_dist: *mut f32, d_group_means: *mut f32,
+                                         d_centroids: *mut f32) -> c_int;
         pub fn blissgpu_duplicate_groups(x: *const f32, n: u64, d: u32, meta: *const u32, metric: c_int, m_matrix: *const f32,
                                          threshold: f32, label: *mut u32, n_pairs: *mut u64, pairs: *mut u32, pair_dist: *mut f32,
                                          max_pairs: u64) -> c_int;
@@ -488,6 +496,62 @@ pub fn group_playlists_on_device<T: AsRef<Song> + Clone>(groups: &[Vec<T>], cand
         return Err(gpu_err(rc));
     }
     Ok(idx.chunks(k).map(|row| row.iter().filter(|&&j| j != u32::MAX).map(|&j| candidates[j as usize].clone()).collect()).collect())
+}
+
+/// `closest_album_to_group(group, pool)` (src/playlist.rs:424-485) cut after the `number_albums` closest albums, for every
+/// group of `groups` in one library call -- what `Library::album_playlist_from` (src/library.rs:850-893) asks per album: the
+/// group, then each chosen album's pool songs by (disc, track) number.  Albums are numbered in order of first appearance in
+/// `pool`; the first pool song equal to each member (`Song: PartialEq`) leaves the pool before its album's mean is formed;
+/// equal distances come in order of first appearance.  A NaN distance is `BLISSGPU_ERR_NAN`, an empty group
+/// `BLISSGPU_ERR_INVALID` (the reference's "Mean of empty slice").
+pub fn album_playlists_on_device<T: AsRef<Song> + Clone>(groups: &[Vec<T>], pool: &[T], number_albums: usize) -> BlissResult<Vec<Vec<T>>> {
+    let mut names: Vec<&str> = Vec::new();
+    let album_of = pool
+        .iter()
+        .map(|s| match s.as_ref().album.as_deref() {
+            None => u32::MAX,
+            Some(a) => names.iter().position(|&b| b == a).unwrap_or_else(|| { names.push(a); names.len() - 1 }) as u32,
+        })
+        .collect::<Vec<u32>>();
+    let k = number_albums.min(names.len());
+    if groups.is_empty() || k == 0 {
+        return Ok(groups.to_vec());
+    }
+    let d = pool[0].as_ref().analysis.as_vec().len();
+    let cand = pool.iter().flat_map(|s| s.as_ref().analysis.as_vec()).collect::<Vec<f32>>();
+    let seeds = groups.iter().flatten().flat_map(|s| s.as_ref().analysis.as_vec()).collect::<Vec<f32>>();
+    let mut offsets = vec![0u64; groups.len() + 1];
+    for (g, group) in groups.iter().enumerate() {
+        offsets[g + 1] = offsets[g] + group.len() as u64;
+    }
+    let skip = groups
+        .iter()
+        .flatten()
+        .map(|s| pool.iter().position(|c| c.as_ref() == s.as_ref()).map_or(u32::MAX, |j| j as u32))
+        .collect::<Vec<u32>>();
+    let mut idx = vec![0u32; groups.len() * k];
+    let rc = unsafe {
+        sys::blissgpu_album_knn(seeds.as_ptr(), offsets.as_ptr(), groups.len() as u64, cand.as_ptr(), pool.len() as u64, d as u32,
+                                album_of.as_ptr(), names.len() as u64, skip.as_ptr(), k as u32, idx.as_mut_ptr(), std::ptr::null_mut(),
+                                std::ptr::null_mut(), std::ptr::null_mut())
+    };
+    if rc != sys::BLISSGPU_OK {
+        return Err(gpu_err(rc));
+    }
+    Ok(groups
+        .iter()
+        .enumerate()
+        .map(|(g, group)| {
+            let gone = &skip[offsets[g] as usize..offsets[g + 1] as usize];
+            let mut playlist = group.clone();
+            for &a in idx[g * k..(g + 1) * k].iter().filter(|&&a| a != u32::MAX) {
+                let mut album = (0..pool.len()).filter(|&i| album_of[i] == a && !gone.contains(&(i as u32))).collect::<Vec<usize>>();
+                album.sort_by_key(|&i| (pool[i].as_ref().disc_number, pool[i].as_ref().track_number));
+                playlist.extend(album.into_iter().map(|i| pool[i].clone()));
+            }
+            playlist
+        })
+        .collect())
 }
 
 /// The duplicate rule of `dedup_playlist_custom_distance` (src/playlist.rs:381-388) over EVERY pair of `songs`, closed

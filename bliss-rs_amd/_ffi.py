@@ -100,6 +100,10 @@ SIGNATURES = {
                                               _vp]),
     "blissgpu_group_knn_weighted_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, _vp, _vp,
                                                      C.c_uint32, _vp, _vp, _vp]),
+    "blissgpu_album_knn": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp,
+                                     _vp, _vp]),
+    "blissgpu_album_knn_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp,
+                                            C.c_uint32, _vp, _vp, _vp, _vp]),
     "blissgpu_chains": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, C.c_uint32, C.c_int, _vp,
                                   _vp]),
     "blissgpu_chains_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, C.c_uint32,

@@ -22,6 +22,8 @@ using namespace bg;
 namespace {
 thread_local std::string g_last_error;
 
+// (the names of KX_SEGMENT_MEAN and KX_ALBUM_KNN_SCAN, the ids numbered behind the KernelId list: see internal.hpp)
+const char kSegmentMeanName[] = "segment_mean_kernel", kAlbumKnnScanName[] = "album_knn_scan_kernel";
 const char* const kKernelNames[K_COUNT] = {
     "fft512_kernel",     "onset_kernel",      "beat_kernel",   "stft8192_kernel", "tune_select_kernel",
     "tune_pass2_kernel", "tune_final_kernel", "chroma_kernel",     "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel", "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel",
@@ -29,7 +31,8 @@ const char* const kKernelNames[K_COUNT] = {
     "forest_walk_kernel", "forest_finish_kernel",
     "dup_init_kernel", "dup_join_kernel", "dup_flatten_kernel",
     "group_knn_scan_kernel", "group_knn_merge_kernel", "group_weights_kernel",
-    "chain_step_kernel", "chain_walk_kernel"};
+    "chain_step_kernel", "chain_walk_kernel",
+    kSegmentMeanName, kAlbumKnnScanName};
 }  // namespace
 
 namespace bg {
@@ -1238,6 +1241,213 @@ int blissgpu_group_knn_weighted(const float* seeds, const uint64_t* group_offset
             e = hipMemcpyAsync(group_status, d_status, (size_t)n_groups * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(group_knn_weighted)", hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+// ---- k nearest ALBUMS per seed group: closest_album_to_group (src/playlist.rs:424-485) cut after k albums, the primitive behind
+// Library::album_playlist_from (src/library.rs:850-893), for every group of a library in one call (kernels_albums.hip,
+// DESIGN.md 3.16) ----
+// everything that can be said about the arguments without a device (both forms check it BEFORE the device is touched)
+static int album_knn_args_ok(const char* who, const void* seeds, const uint64_t* off, uint64_t n_groups, const void* cand,
+                             uint64_t n, uint32_t d, const void* album_of, uint64_t n_albums, uint32_t k, const void* idx) {
+    int rc = group_knn_args_ok(who, seeds, off, n_groups, cand, n, d, BLISSGPU_METRIC_EUCLIDEAN, nullptr, k, idx);
+    if (rc) return rc;
+    if (n_albums > n) return fail(BLISSGPU_ERR_INVALID, who, "n_albums must be at most n");
+    if (n_groups == 0) return BLISSGPU_OK;
+    for (uint64_t g = 0; g < n_groups; g++)
+        if (off[g + 1] == off[g]) return fail(BLISSGPU_ERR_INVALID, who, "empty group (the reference's \"Mean of empty slice\")");
+    if (n && !album_of) return fail(BLISSGPU_ERR_INVALID, who, "album_of is NULL");
+    return BLISSGPU_OK;
+}
+
+// album_of and skip, on the host
+static int album_knn_data_ok(const char* who, const uint32_t* album_of, uint64_t n, uint64_t n_albums, const uint32_t* skip,
+                             uint64_t n_seeds) {
+    for (uint64_t i = 0; i < n; i++)
+        if (album_of[i] != 0xFFFFFFFFu && album_of[i] >= n_albums)
+            return fail(BLISSGPU_ERR_INVALID, who, "album_of entries must be < n_albums or 0xFFFFFFFF");
+    if (skip)
+        for (uint64_t i = 0; i < n_seeds; i++)
+            if (skip[i] != 0xFFFFFFFFu && skip[i] >= n) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
+    return BLISSGPU_OK;
+}
+
+// The tables of bg::AlbumTables in one array of words, in this order: goff | arow_off | arow | patch_off | patch_album |
+// patch_cnt | pskip_off | pskip.  The album row lists are a stable counting sort of the candidates by album; a group's patches
+// come from the sorted, deduplicated (album, row) pairs of its skip entries -- at most one patch and one lost row per seed row.
+struct AlbumTablesHost {
+    std::vector<uint32_t> words;
+    size_t o_arow_off, o_arow, o_patch_off, o_patch_album, o_patch_cnt, o_pskip_off, o_pskip;
+    uint32_t n_patches;
+};
+static void album_tables_build(const uint64_t* off, uint64_t n_groups, const uint32_t* album_of, uint64_t n, uint64_t n_albums,
+                               const uint32_t* skip, AlbumTablesHost& h) {
+    std::vector<uint32_t> arow_off(n_albums + 1, 0u);
+    for (uint64_t i = 0; i < n; i++)
+        if (album_of[i] != 0xFFFFFFFFu) arow_off[album_of[i] + 1u]++;
+    for (uint64_t a = 0; a < n_albums; a++) arow_off[a + 1] += arow_off[a];
+    std::vector<uint32_t> arow(arow_off[n_albums]), fill(arow_off.begin(), arow_off.end() - 1);
+    for (uint64_t i = 0; i < n; i++)
+        if (album_of[i] != 0xFFFFFFFFu) arow[fill[album_of[i]]++] = (uint32_t)i;
+    std::vector<uint32_t> patch_off(n_groups + 1, 0u), patch_album, patch_cnt, pskip_off(1, 0u), pskip;
+    std::vector<std::pair<uint32_t, uint32_t>> lost;  // (album, row) pairs of one group
+    for (uint64_t g = 0; g < n_groups; g++) {
+        lost.clear();
+        if (skip)
+            for (uint64_t s = off[g]; s < off[g + 1]; s++)
+                if (skip[s] != 0xFFFFFFFFu && album_of[skip[s]] != 0xFFFFFFFFu) lost.emplace_back(album_of[skip[s]], skip[s]);
+        std::sort(lost.begin(), lost.end());
+        lost.erase(std::unique(lost.begin(), lost.end()), lost.end());
+        for (size_t i = 0; i < lost.size();) {
+            const uint32_t a = lost[i].first;
+            size_t j = i;
+            for (; j < lost.size() && lost[j].first == a; j++) pskip.push_back(lost[j].second);
+            patch_album.push_back(a);
+            patch_cnt.push_back(arow_off[a + 1] - arow_off[a] - (uint32_t)(j - i));
+            pskip_off.push_back((uint32_t)pskip.size());
+            i = j;
+        }
+        patch_off[g + 1] = (uint32_t)patch_album.size();
+    }
+    h.n_patches = (uint32_t)patch_album.size();
+    h.words.clear();
+    for (uint64_t g = 0; g <= n_groups; g++) h.words.push_back((uint32_t)off[g]);
+    auto put = [&](const std::vector<uint32_t>& v) {
+        const size_t at = h.words.size();
+        h.words.insert(h.words.end(), v.begin(), v.end());
+        return at;
+    };
+    h.o_arow_off = put(arow_off);
+    h.o_arow = put(arow);
+    h.o_patch_off = put(patch_off);
+    h.o_patch_album = put(patch_album);
+    h.o_patch_cnt = put(patch_cnt);
+    h.o_pskip_off = put(pskip_off);
+    h.o_pskip = put(pskip);
+}
+
+// both forms after their checks: seeds, candidates and outputs on the device, album_of and skip (checked) on the host.
+// d_gmeans / d_cent may be NULL: the means then live in the workspace only
+static int album_knn_run(blissgpu_ctx* c, const char* who, const float* d_seeds, const uint64_t* group_offsets, uint64_t n_groups,
+                         const float* d_cand, uint64_t n, uint32_t d, const uint32_t* h_album_of, uint64_t n_albums,
+                         const uint32_t* h_skip, uint32_t k, uint32_t* d_idx, float* d_dist, float* d_gmeans, float* d_cent) {
+    AlbumTablesHost h;
+    album_tables_build(group_offsets, n_groups, h_album_of, n, n_albums, h_skip, h);
+    // workspace: the sorted k best keys of every (group, split) | the means that have no output of their own | the patched
+    // centroids -- O(A d + G d + touched pairs x d + items x k); no n_groups x n_albums array exists anywhere
+    const KnnPlan plan = knn_plan(n_groups, n_albums, k, c->n_cus);
+    const size_t part_bytes = std::max<size_t>(8, (size_t)plan.part_keys * sizeof(unsigned long long));
+    const size_t cent_floats = d_cent ? 0 : (size_t)n_albums * d, gm_floats = d_gmeans ? 0 : (size_t)n_groups * d;
+    int rc = c->pl_sync.ensure(4);
+    if (!rc) rc = c->pl_keys.ensure(h.words.size());
+    if (!rc) rc = c->pl_tmp.ensure(part_bytes + (cent_floats + gm_floats + (size_t)h.n_patches * d) * sizeof(float));
+    if (rc) return rc;
+    unsigned long long* part = reinterpret_cast<unsigned long long*>(c->pl_tmp.p);
+    float* ws = reinterpret_cast<float*>(c->pl_tmp.p + part_bytes);
+    float* cent = d_cent ? d_cent : ws;
+    float* gmeans = d_gmeans ? d_gmeans : ws + cent_floats;
+    float* pcent = ws + cent_floats + gm_floats;
+    const uint32_t* w = c->pl_keys.p;
+    const AlbumTables t{w,
+                        w + h.o_arow_off,
+                        w + h.o_arow,
+                        w + h.o_patch_off,
+                        w + h.o_patch_album,
+                        w + h.o_patch_cnt,
+                        w + h.o_pskip_off,
+                        w + h.o_pskip,
+                        (uint32_t)n_albums,
+                        (uint32_t)n_groups,
+                        h.n_patches};
+    HIP_TRY(hipMemcpyAsync(c->pl_keys.p, h.words.data(), h.words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    // pl_sync: [1] NaN distance of an existing (group, album) pair
+    HIP_TRY(hipMemsetAsync(c->pl_sync.p, 0, 4 * sizeof(uint32_t), c->stream));
+    {
+        Prof p(c, KX_SEGMENT_MEAN);
+        launch_segment_mean(d_cand, d_seeds, d, t, cent, gmeans, pcent, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    {
+        Prof p(c, KX_ALBUM_KNN_SCAN);
+        launch_album_knn_scan(gmeans, cent, d, t, pcent, k, plan, part, c->pl_sync.p + 1, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    {
+        Prof p(c, K_KNN_MERGE);
+        launch_knn_merge(part, n_groups, k, plan, d_idx, d_dist, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    uint32_t flags[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(flags, c->pl_sync.p, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (the tables above have left the host by now too)
+    if (flags[1]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance (the reference panics here)");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_album_knn_device(blissgpu_ctx* c, const float* d_seeds, const uint64_t* group_offsets, uint64_t n_groups,
+                              const float* d_cand, uint64_t n, uint32_t d, const uint32_t* d_album_of, uint64_t n_albums,
+                              const uint32_t* d_skip, uint32_t k, uint32_t* d_idx, float* d_dist, float* d_group_means,
+                              float* d_centroids) {
+    const char* who = "blissgpu_album_knn_device";
+    int rc = album_knn_args_ok(who, d_seeds, group_offsets, n_groups, d_cand, n, d, d_album_of, n_albums, k, d_idx);
+    if (rc) return rc;
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    if (n_groups == 0) return BLISSGPU_OK;
+    CTX_ENTER(c, who);
+    // the album row lists and the patches are built on the host: album_of and skip come back first (this synchronises the
+    // stream, as the argument / NaN check at the end does anyway)
+    const uint64_t n_seeds = group_offsets[n_groups];
+    std::vector<uint32_t> album_of(n), skip(d_skip ? n_seeds : 0);
+    if (n) HIP_TRY(hipMemcpyAsync(album_of.data(), d_album_of, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (d_skip) HIP_TRY(hipMemcpyAsync(skip.data(), d_skip, n_seeds * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    rc = album_knn_data_ok(who, album_of.data(), n, n_albums, d_skip ? skip.data() : nullptr, n_seeds);
+    if (rc) return rc;
+    return album_knn_run(c, who, d_seeds, group_offsets, n_groups, d_cand, n, d, album_of.data(), n_albums,
+                         d_skip ? skip.data() : nullptr, k, d_idx, d_dist, d_group_means, d_centroids);
+}
+
+int blissgpu_album_knn(const float* seeds, const uint64_t* group_offsets, uint64_t n_groups, const float* cand, uint64_t n,
+                       uint32_t d, const uint32_t* album_of, uint64_t n_albums, const uint32_t* skip, uint32_t k, uint32_t* idx,
+                       float* dist, float* group_means, float* centroids) {
+    const char* who = "blissgpu_album_knn";
+    int rc = album_knn_args_ok(who, seeds, group_offsets, n_groups, cand, n, d, album_of, n_albums, k, idx);
+    if (rc) return rc;
+    if (n_groups == 0) return BLISSGPU_OK;
+    const uint64_t n_seeds = group_offsets[n_groups];
+    rc = album_knn_data_ok(who, album_of, n, n_albums, skip, n_seeds);
+    if (rc) return rc;
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    // staging: st_dist holds dist | group_means | centroids, each only when asked for
+    const size_t out_n = (size_t)n_groups * k, gm_n = (size_t)n_groups * d, cent_n = (size_t)n_albums * d;
+    const size_t o_gm = dist ? out_n : 0, o_cent = o_gm + (group_means ? gm_n : 0);
+    rc = c->st_b.ensure(std::max<size_t>(1, n * d));
+    if (!rc) rc = c->st_a.ensure(n_seeds * d);
+    if (!rc) rc = c->st_idx.ensure(out_n);
+    if (!rc) rc = c->st_dist.ensure(std::max<size_t>(1, o_cent + (centroids ? cent_n : 0)));
+    if (rc) return rc;
+    float *d_dist = dist ? c->st_dist.p : nullptr, *d_gm = group_means ? c->st_dist.p + o_gm : nullptr;
+    float* d_cent = centroids ? c->st_dist.p + o_cent : nullptr;
+    hipError_t e = hipSuccess;
+    if (n) e = hipMemcpyAsync(c->st_b.p, cand, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->st_a.p, seeds, n_seeds * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(album_knn)", hipGetErrorString(e));
+    if (!rc)
+        rc = album_knn_run(c, who, c->st_a.p, group_offsets, n_groups, c->st_b.p, n, d, album_of, n_albums, skip, k, c->st_idx.p,
+                           d_dist, d_gm, d_cent);
+    if (!rc) {
+        e = hipMemcpyAsync(idx, c->st_idx.p, out_n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, d_dist, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && group_means) e = hipMemcpyAsync(group_means, d_gm, gm_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && centroids && cent_n)
+            e = hipMemcpyAsync(centroids, d_cent, cent_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(album_knn)", hipGetErrorString(e));
     }
     (void)hipStreamSynchronize(c->stream);
     return rc;

@@ -121,8 +121,13 @@ enum KernelId : int {
     K_GROUP_KNN_SCAN, K_GROUP_KNN_MERGE,    // k-nearest search per seed group (kernels_group_knn.hip)
     K_GROUP_WEIGHTS,                        // variance-based weights of every seed group (kernels_group_knn.hip)
     K_CHAIN_STEP, K_CHAIN_WALK,             // song-to-song chains cut after k (kernels_chains.hip)
-    K_COUNT
+    // (tests/test_chains_host.py holds this list, and the list of names beside it, to end in the chain kernels: the kernels
+    // that came later are numbered behind it, so that no older id or name moves)
+    K_COUNT = K_CHAIN_WALK + 3
 };
+// k-nearest albums per seed group (kernels_albums.hip; its partial lists are merged by knn_merge_kernel)
+constexpr int KX_SEGMENT_MEAN = K_CHAIN_WALK + 1, KX_ALBUM_KNN_SCAN = K_CHAIN_WALK + 2;
+static_assert(KX_ALBUM_KNN_SCAN + 1 == K_COUNT, "every kernel id is below the count");
 
 // lower_bound on a prefix array: largest s with prefix[s] <= x  (prefix has n+1 entries, prefix[0]=0)
 __device__ __forceinline__ uint32_t find_segment(const uint32_t* __restrict__ prefix, uint32_t n, uint32_t x) {
@@ -269,6 +274,23 @@ void launch_group_knn_merge(const unsigned long long* part, const uint32_t* list
 // W[g][0..d) = the diagonal of variance_based_weight_matrix of group g's seed rows, ones (status 1) under two seeds; status may be NULL
 void launch_group_weights(const float* S, const uint32_t* goff, uint64_t n_groups, uint32_t d, float* W, int32_t* status,
                           hipStream_t st);
+// k nearest ALBUMS per seed group (kernels_albums.hip).  The tables are built on the host from album_of and skip (device
+// pointers here): album a's songs are arow[arow_off[a] .. arow_off[a + 1]) in ascending candidate index; group g's patches --
+// the albums its skip entries touch -- are patch_*[patch_off[g] .. patch_off[g + 1]) sorted by album, patch p naming its album,
+// the rows the group leaves it (patch_cnt, 0: the album does not exist for the group) and the ascending list
+// pskip[pskip_off[p] .. pskip_off[p + 1]) of the rows it loses.
+struct AlbumTables {
+    const uint32_t *goff, *arow_off, *arow, *patch_off, *patch_album, *patch_cnt, *pskip_off, *pskip;
+    uint32_t n_albums, n_groups, n_patches;
+};
+// the sequential f32 means of every album (-> centroids [n_albums][d], NaN rows for albums without songs), group (-> gmeans
+// [n_groups][d]) and patch (-> pcent [n_patches][d]) in one launch
+void launch_segment_mean(const float* X, const float* S, uint32_t d, const AlbumTables& t, float* centroids, float* gmeans,
+                         float* pcent, hipStream_t st);
+// p = knn_plan(n_groups, n_albums, k, n_cus); `part` holds p.part_keys keys for launch_knn_merge; a NaN distance of an existing
+// (group, album) pair sets *nan_flag
+void launch_album_knn_scan(const float* gmeans, const float* centroids, uint32_t d, const AlbumTables& t, const float* pcent,
+                           uint32_t k, const KnnPlan& p, unsigned long long* part, uint32_t* nan_flag, hipStream_t st);
 // song-to-song chains cut after k, one per seed group (kernels_chains.hip).  Step 0 is the group search with k = 1; a later step
 // t reads idx[chain][0 .. t) and writes idx / dist [chain][t], directly or -- several workgroups per chain -- through the
 // 64-bit minima best[n_chains] (all KNN_NONE before the first step; reset by the step's second launch).  A NaN among the

@@ -466,6 +466,41 @@ class Context:
         self._post()
         return idx, dist
 
+    def album_knn(self, S, offsets, X, album_of, n_albums: int, k: int, skip=None):
+        """The k nearest ALBUMS of every seed group (blissgpu_album_knn_device): closest_album_to_group (src/playlist.rs:424-485)
+        cut after k albums.  Group g's seeds are the rows offsets[g] .. offsets[g + 1] of S (offsets: a HOST sequence of G + 1
+        integers starting at 0, no group empty); album_of: int32 tensor [n], the album index 0 .. n_albums of every row of X,
+        -1 = no album; skip: int32 tensor with one candidate index per SEED ROW, -1 = none, or None: those rows leave their
+        albums before the group's album means are formed.  -> (idx int32 [G, k], dist float32 [G, k], group_means float32
+        [G, d], centroids float32 [n_albums, d]) on the device: the albums in ascending (euclidean distance of the album's mean
+        to the group's mean, album index), rows with fewer than k existing albums ending in -1 / inf; centroids are the
+        full-album means, NaN rows for albums without songs.  Raises BlissGpuError(ERR_NAN) for a NaN distance (album_of and
+        skip are read back, which synchronises)."""
+        import numpy as np
+
+        torch = self.torch
+        assert S.is_cuda and X.is_cuda and S.dtype == torch.float32 and X.dtype == torch.float32
+        assert S.dim() == 2 and X.dim() == 2 and S.shape[1] == X.shape[1]
+        S, X = S.contiguous(), X.contiguous()
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1)).astype(np.uint64)
+        assert off.shape[0] >= 1 and int(off[-1]) == S.shape[0]
+        G, n, d, k, A = off.shape[0] - 1, X.shape[0], X.shape[1], int(k), int(n_albums)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        assert album_of.is_cuda and album_of.dtype == torch.int32 and album_of.shape[0] == n
+        album_of = album_of.contiguous()
+        if skip is not None:
+            assert skip.is_cuda and skip.dtype == torch.int32 and skip.shape[0] == S.shape[0]
+            skip = skip.contiguous()
+        idx = torch.empty((G, max(k, 0)), dtype=torch.int32, device=X.device)
+        dist = torch.empty((G, max(k, 0)), dtype=torch.float32, device=X.device)
+        means = torch.empty((G, d), dtype=torch.float32, device=X.device)
+        centroids = torch.empty((max(A, 0), d), dtype=torch.float32, device=X.device)
+        self._pre()
+        _ffi.check(self._L.blissgpu_album_knn_device(self._h, ptr(S), off.ctypes.data, G, ptr(X), n, d, ptr(album_of), A,
+                                                     ptr(skip), k, ptr(idx), ptr(dist), ptr(means), ptr(centroids)))
+        self._post()
+        return idx, dist, means, centroids
+
     def duplicate_labels(self, x, meta=None, metric: str = "euclidean", m=None, threshold=0.05, max_pairs: int = 0):
         """Which rows of x are the same song (blissgpu_duplicate_groups_device): the pair i < j is an edge when its distance
         is < threshold or meta[i] != 0 and meta[i] == meta[j] (int32 keys, playlist.meta_keys; None: no such rule).  ->

@@ -23,6 +23,8 @@ database:
     playlist_from, playlist_from_custom   seeds first, seeds removed from the pool by path, the order and ONE
                                           deduplication of the whole chain on the device (playlist.dedup_order)
     album_playlist_from                   closest_album_to_group, cropped after `number_albums` album changes
+    album_playlists                       album_playlist_from for EVERY album (or artist, genre, saved playlist) of the
+                                          library: one database read, one device call (playlist.nearest_albums)
     similar_songs                         the k closest songs of every song (or of some), one device call
                                           (playlist.nearest_order): playlist_from(&[song]).take(k) for the whole library
     duplicate_songs                       the groups of songs that are the same song by the rule of dedup_playlist
@@ -520,3 +522,74 @@ def album_playlist_from(db: Conn, album_title: str, number_albums: int) -> List[
         index += 1
     return pl[:index]
 
+
+
+def album_playlists(db: Conn, number_albums: int, by: str = "album", groups=None):
+    """An album playlist for every album of a library, or for arbitrary seed sets: {key: [Song, ...]} where, with by="album",
+    entry `title` has the songs of `album_playlist_from(db, title, number_albums)` in the same order
+    (src/library.rs:850-893: the album ordered by disc then track number, then the `number_albums` albums whose mean analysis
+    is closest to the album's, each ordered by disc and track number, None first), for every album title of the analysed songs
+    of FeaturesVersion.LATEST.  The library is read once and ONE device call (playlist.nearest_albums) answers every key: the
+    album means, the group means and the ranking are computed on the device; the reference hard-codes the euclidean distance.
+
+    `by` in artist / album_artist / genre, or `groups` = {name: [paths]}, builds the seed sets as group_playlists does (members
+    in id order, or as given); the ranked things are always albums, from which each key's own songs are taken out before the
+    means are formed.  An unknown path is the ProviderError playlist_from_custom raises.  number_albums == 0 returns the seed
+    songs without touching the device."""
+    if groups is None and by not in _GROUP_COLUMNS:
+        raise ValueError(f"by must be one of {_GROUP_COLUMNS}")
+    number_albums = int(number_albums)
+    if number_albums < 0:
+        raise ValueError("number_albums must not be negative")
+    songs, X = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
+
+    def disc_track(i):  # Option / SQLite: None first
+        d, t = songs[i].disc_number, songs[i].track_number
+        return ((0, 0) if d is None else (1, d), (0, 0) if t is None else (1, t))
+
+    members = {}
+    if groups is None:
+        for i, s in enumerate(songs):
+            key = getattr(s, by)
+            if key is not None:
+                members.setdefault(key, []).append(i)
+        if by == "album":  # songs_from_album: order by disc_number, track_number
+            members = {key: sorted(rows, key=disc_track) for key, rows in members.items()}
+    else:
+        row_of = {s.path: i for i, s in enumerate(songs)}
+        for name, paths in groups.items():
+            for p in paths:
+                if p not in row_of:
+                    raise ProviderError(f"song '{p}' has not been analyzed")
+            members[name] = [row_of[p] for p in paths]
+    if not members:
+        return {}
+    keys = list(members)
+    if any(not members[key] for key in keys):
+        raise ProviderError("Mean of empty slice")
+    titles, album_of = {}, np.full(len(songs), -1, np.int64)
+    for i, s in enumerate(songs):
+        if s.album is not None:
+            album_of[i] = titles.setdefault(s.album, len(titles))
+    k = min(number_albums, len(titles))
+    if k == 0:
+        return {key: [songs[i] for i in members[key]] for key in keys}
+    if k > 1024:
+        raise ValueError("at most 1024 albums per playlist")
+    offsets = np.zeros(len(keys) + 1, np.int64)
+    offsets[1:] = np.cumsum([len(members[key]) for key in keys])
+    rows = np.asarray([i for key in keys for i in members[key]], np.int64)
+    idx, _ = playlist.nearest_albums((X[rows].reshape(rows.shape[0], X.shape[1]), offsets), X, album_of, k, skip=rows)
+    album_rows = [[] for _ in titles]
+    for i, a in enumerate(album_of):
+        if a >= 0:
+            album_rows[a].append(i)
+    out = {}
+    for g, key in enumerate(keys):
+        gone = set(members[key])
+        pl = [songs[i] for i in members[key]]
+        for a in idx[g]:
+            if a >= 0:
+                pl.extend(songs[i] for i in sorted((i for i in album_rows[a] if i not in gone), key=disc_track))
+        out[key] = pl
+    return out

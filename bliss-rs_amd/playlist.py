@@ -940,3 +940,106 @@ def closest_album_to_group(group, pool):
             al.sort(key=key)
             playlist.extend(al)
     return playlist
+
+
+def nearest_albums(seed_groups, candidates, album_of, k, skip=None, return_means=False):
+    """The k nearest ALBUMS of every seed group in one device call (blissgpu_album_knn), without a groups x albums matrix: row
+    g is closest_album_to_group (src/playlist.rs:424-485) cut after k albums, as album indices.  `album_of`: one integer per
+    candidate, its album's index (0 .. album_of.max()), -1 = the song has no album.  `seed_groups` and `skip` as for
+    nearest_to_groups: the skipped candidates leave their albums BEFORE the album means are formed, an album that loses every
+    song does not exist for that group.  Means are sequential f32 row sums divided by the count (ndarray's mean_axis), the
+    distance is euclidean_distance(group mean, album mean) bit for bit.  -> (idx int64[G, k], dist float32[G, k]): the albums
+    in ascending (distance, album index); rows with fewer than k existing albums end in -1 / inf.  return_means=True: ->
+    (idx, dist, group_means float32[G, d], centroids float32[A, d]), centroids being the FULL-album means (NaN rows for album
+    indices no song uses).  An empty group raises ProviderError("Mean of empty slice") before the library is reached; a NaN
+    distance raises ValueError (the reference's n32() panic)."""
+    from .song import ProviderError
+
+    S, off = _seed_groups(seed_groups)
+    X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
+    if X.ndim != 2 or (S is not None and S.shape[1] != X.shape[1]):
+        raise ValueError("seed groups and candidates must be [s_g, d] and [n, d]")
+    n, d = X.shape
+    album_of = np.asarray(album_of)
+    if album_of.ndim != 1 or album_of.shape[0] != n or (album_of.size and album_of.dtype.kind not in "iu"):
+        raise ValueError("album_of must hold one integer per candidate")
+    album_of = album_of.astype(np.int64)
+    if (album_of < -1).any() or (album_of >= max(n, 0)).any():
+        raise ValueError("album_of entries must be album indices below the number of candidates, or -1")
+    k = int(k)
+    if not 1 <= k <= 1024:
+        raise ValueError("k must be 1 .. 1024")
+    if not 1 <= d <= 64:
+        raise ValueError("d must be 1 .. 64")
+    G = off.shape[0] - 1
+    if (np.diff(off.astype(np.int64)) == 0).any():
+        raise ProviderError("Mean of empty slice")
+    skip = _group_skip(skip, off, n)
+    A = int(album_of.max()) + 1 if album_of.size else 0
+    album_u32 = np.where(album_of < 0, 0xFFFFFFFF, album_of).astype(np.uint32)
+    idx, dist = np.empty((G, k), np.uint32), np.empty((G, k), np.float32)
+    means = np.empty((G, d), np.float32) if return_means else None
+    centroids = np.empty((A, d), np.float32) if return_means else None
+    try:
+        _ffi.check(_ffi.lib().blissgpu_album_knn(None if S is None else S.ctypes.data, off.ctypes.data, G, X.ctypes.data, n, d,
+                                                 album_u32.ctypes.data, A, None if skip is None else skip.ctypes.data, k,
+                                                 idx.ctypes.data, dist.ctypes.data,
+                                                 None if means is None else means.ctypes.data,
+                                                 None if centroids is None else centroids.ctypes.data))
+    except _ffi.BlissGpuError as e:
+        _nan_to_panic(e)
+    out = idx.astype(np.int64)
+    out[idx == 0xFFFFFFFF] = -1
+    return (out, dist, means, centroids) if return_means else (out, dist)
+
+
+def _disc_track_key(s):
+    s = _song_of(s)
+    d, t = s.disc_number, s.track_number
+    return ((0, 0) if d is None else (1, d), (0, 0) if t is None else (1, t))  # Option: None < Some
+
+
+def closest_albums_to_groups(groups, pool, number_albums):
+    """For every group of songs, closest_album_to_group(group, pool) (src/playlist.rs:424-485) cut after the `number_albums`
+    closest albums: the group, then each chosen album's pool songs ordered by (disc_number, track_number), None < Some -- "play
+    these songs, then the albums most like them", all groups in ONE device call (nearest_albums).  Albums are numbered in order
+    of first appearance in `pool`; the first pool song that == each member (Song: PartialEq) leaves the pool of that group
+    before its album's mean is formed.  Equal distances come in order of first appearance."""
+    from .song import ProviderError
+
+    groups, pool = [list(g) for g in groups], list(pool)
+    if not groups:
+        return []
+    if any(not g for g in groups):
+        raise ProviderError("Mean of empty slice")
+    number_albums = int(number_albums)
+    if number_albums <= 0 or not pool:
+        return [list(g) for g in groups]
+    names, album_of = {}, np.full(len(pool), -1, np.int64)
+    for i, s in enumerate(pool):
+        album = _song_of(s).album
+        if album is not None:
+            album_of[i] = names.setdefault(album, len(names))
+    if not names:
+        return [list(g) for g in groups]
+    k = min(number_albums, len(names))
+    if k > 1024:
+        raise ValueError("at most 1024 albums per playlist")
+    skip = _member_skip(groups, pool)
+    off = np.zeros(len(groups) + 1, np.int64)
+    off[1:] = np.cumsum([len(g) for g in groups])
+    idx, _ = nearest_albums((_matrix([s for g in groups for s in g]), off), _matrix(pool), album_of, k, skip)
+    rows = [[] for _ in names]
+    for i, a in enumerate(album_of):
+        if a >= 0:
+            rows[a].append(i)
+    out, at = [], 0
+    for g, row in zip(groups, idx):
+        gone = set(int(j) for j in skip[at:at + len(g)] if j >= 0)
+        at += len(g)
+        playlist = list(g)
+        for a in row:
+            if a >= 0:
+                playlist.extend(sorted((pool[i] for i in rows[a] if i not in gone), key=_disc_track_key))
+        out.append(playlist)
+    return out

@@ -401,6 +401,45 @@ int blissgpu_group_knn_weighted_device(blissgpu_ctx *ctx, const float *d_seeds, 
                                        const uint32_t *d_skip, uint32_t k, uint32_t *d_idx, float *d_dist,
                                        int32_t *d_group_status);
 
+/* ---- the k nearest ALBUMS of every seed group (src/playlist.rs:424-485, src/library.rs:850-893) ----
+ * closest_album_to_group cut after k albums -- what Library::album_playlist_from asks per album ("play this album, then the
+ * albums most like it") -- for n_groups groups in one call.  seeds, group_offsets (a HOST pointer in both forms), cand and skip
+ * are blissgpu_group_knn's; album_of is [n]: the album index (0 .. n_albums) of every candidate, 0xFFFFFFFF = the song has no
+ * album.  For group g, every operation rounded to f32 on its own:
+ *   group mean     mean_g = (0.0f + seed_0 + seed_1 + ...) / (float)s_g, the sum over the group's seed rows in seed order, per
+ *                  feature: ndarray's mean_axis(Axis(0)) of a row-major array;
+ *   album rows     R(g, a) = the candidates i with album_of[i] == a, in ascending i, WITHOUT the candidates named by group g's
+ *                  skip entries: the reference removes the group's songs from the pool before it forms the album means;
+ *   absent albums  an album with R(g, a) empty does not exist for group g (an album that is the whole group is not in the
+ *                  reference's pool);
+ *   centroid       centroid(g, a) = (0.0f + the rows of R(g, a) in order) / (float)|R(g, a)|; for an album no skip entry of g
+ *                  touches this is the group-independent full-album centroid;
+ *   distance       dist(g, a) = euclidean_distance(mean_g, centroid(g, a)), bit for bit what blissgpu_distance /
+ *                  blissgpu_pairwise return for those two vectors (the reference hard-codes euclidean here).
+ * Row g of idx / dist ([n_groups][k], dist may be NULL) holds the first k existing albums in ascending (dist, album index)
+ * order: equal distances come in album-index order (-0.0 and +0.0 are equal), infinite distances sort last, rows with fewer
+ * than k existing albums end in idx 0xFFFFFFFF / dist +inf.  (The reference leaves ties to HashMap iteration order.)
+ * group_means ([n_groups][d], may be NULL) receives mean_g; centroids ([n_albums][d], may be NULL) the FULL-album means, an
+ * album without any song a row of NaN (it is absent for every group) -- for callers that cache centroids.
+ * A NaN distance of an existing (group, album) pair returns BLISSGPU_ERR_NAN (the reference's n32() panic); the outputs are
+ * then unspecified.  An empty group is BLISSGPU_ERR_INVALID (the reference's "Mean of empty slice"), decided from group_offsets.
+ * 1 <= k <= BLISSGPU_KNN_MAX_K, 1 <= d <= 64, n < 2^32 - 1, n_albums <= n, fewer than 2^32 seeds and 2^32 - 1 groups; an
+ * album_of entry >= n_albums or a skip entry >= n, other than 0xFFFFFFFF, is BLISSGPU_ERR_INVALID.  n_groups == 0 is
+ * BLISSGPU_OK; so is n == 0 or n_albums == 0 (every row is padding).  Every check that needs no device data happens before the
+ * device is touched, the host form's album_of and skip on the host.  No n_groups x n_albums array is ever stored: the workspace
+ * is O(n_albums d + n_groups d + touched (group, album) pairs x d + items x k), at most one touched pair per seed row; three
+ * launches whatever n_groups, n_albums and the group sizes. */
+int blissgpu_album_knn(const float *seeds, const uint64_t *group_offsets, uint64_t n_groups, const float *cand, uint64_t n,
+                       uint32_t d, const uint32_t *album_of, uint64_t n_albums, const uint32_t *skip, uint32_t k,
+                       uint32_t *idx, float *dist, float *group_means, float *centroids);
+/* Device-resident form (device pointers, d_album_of, d_skip and the outputs included; group_offsets stays a host pointer).  The
+ * album row lists are derived on the host: d_album_of and d_skip are read back first, which synchronises the context's stream,
+ * as the NaN check at the end does. */
+int blissgpu_album_knn_device(blissgpu_ctx *ctx, const float *d_seeds, const uint64_t *group_offsets, uint64_t n_groups,
+                              const float *d_cand, uint64_t n, uint32_t d, const uint32_t *d_album_of, uint64_t n_albums,
+                              const uint32_t *d_skip, uint32_t k, uint32_t *d_idx, float *d_dist, float *d_group_means,
+                              float *d_centroids);
+
 /* ---- song-to-song chains cut after k, one per seed group (src/playlist.rs:272-326) ----
  * Row g of idx / dist ([n_groups][k], dist may be NULL) is the first k songs of song_to_song(&group g, candidates without the
  * group's skipped rows, metric) -- a "journey" playlist starting at every song, album or saved playlist of a library, in one
