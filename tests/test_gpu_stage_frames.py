@@ -16,10 +16,19 @@ error.  Here every frame of every tap is held to a reference of its own:
   6. the tempo chain, free of FFT rounding: the oracle's peak picker, beat tracker and median replayed on the device's OWN
      flux tap must give the device's thresholded series, every run's bpm and beat count and the tempo feature bit for bit
      (the CPU tests of the section pin the replay, the per-run trace and what the song set reaches)
+  7. features 1..9, free of FFT rounding: utils::mean and ndarray's std_axis (the oracle's mean / std) replayed on the device's
+     OWN centroid, rolloff, flatness, energy256 and crossings256 taps must give the row's features 1..7 bit for bit and its
+     features 8, 9 within the image of log10f's error bound (the CPU tests pin the oracle's Welford step on an exact fused
+     multiply-add, the replay on the oracle's zcr / loudness, and what the song set reaches from its lengths alone)
+  8. features 10..22, on the device's OWN interval tap: ChromaDesc::get_values / get_values_version_1 in plain NumPy must give
+     features 10..21 bit for bit and feature 22 within one f32 ulp (double atan2), with songs on and off the 1.0 clamps of
+     features 20 and 21 (the CPU tests pin the replay on the oracle and which songs sit on which clamp)
 
 The CPU tests (no marker) run in the default `-m "not gpu"` pass; the GPU tests are marked one by one.
 """
 import ctypes as C
+import math
+from fractions import Fraction
 
 import numpy as np
 import pytest
@@ -882,3 +891,511 @@ def test_tempo_chain_options_do_not_change_a_bit(bliss, oracle, tempo_set):
             c.close()
     finally:
         oracle.set_exp_via_double(False)
+
+
+# ---------------------------------------------------------------------------------------------
+# 7. features 1..9 on the device's own series
+# ---------------------------------------------------------------------------------------------
+# summary_kernel (kernels_finalize.hip) is sequential f32 arithmetic in the reference's order: fed the device's taps, the
+# oracle's mean / std and the f32 expressions below must reproduce features 1..7 exactly.  Features 8 and 9 end in log10f,
+# whose rounding IEEE 754 does not fix.  No header or document of the ROCm installation states an error bound for the device
+# library's log10f (the HIP headers hand it to __builtin_log10f without a word on accuracy), so the bound is LOG10F_ULP = 2
+# ulp of the logarithm.  Its image in the feature is taken exactly, not by a derivative: every f32 within 2 ulp of the true
+# log10(v) lies between the two f32 values `lo` and `hi` below, every later step (x 10, + 90, x 2, / 90, - 1, each rounded to
+# f32) is monotone, so the feature lies between the f32 features of `lo` and `hi`; one more f32 ulp is allowed on either side
+# for the rounding of the result.  (A derivative would be unsound here: 10 log10(v) + 90 has an ulp of 7.6e-6 near 85, which the
+# later steps turn into 1.7e-7 = 3 ulp of a feature near 0.9, however small the error of the logarithm that tipped it.)
+F32 = np.float32
+LOUD_W = 1024
+LOG10F_ULP = 2
+SUMMARY_SERIES = (("centroid", 2, 11025.0), ("rolloff", 4, 11025.0), ("flatness", 6, 1.0))   # tap, feature of the mean, max
+SUMMARY_RESIDUES = (0, 1, 255, 256, 257, 511, 768, 1023)
+SUMMARY_SHORT = {7: 0, 49: 1, 96: 100, 139: 8191}   # position in the batch: length of a too-short song
+
+
+def _normalize(v, mn, mx):
+    """Normalize (src/utils.rs: 2. * (value - min) / (max - min) - 1.) in f32 scalars, in that order of operations"""
+    v, mn, mx = F32(v), F32(mn), F32(mx)
+    return F32(F32(F32(2.0) * F32(v - mn)) / F32(mx - mn)) - F32(1.0)
+
+
+def _ord32(a):
+    """f32 -> integers in which neighbouring floats differ by one, so that a difference is a distance in ulp"""
+    i = np.asarray(a, np.float32).view(np.int32).astype(np.int64)
+    return np.where(i < 0, -(i & 0x7FFFFFFF), i)
+
+
+def _ulps(a, b):
+    return np.abs(_ord32(a) - _ord32(b))
+
+
+def _same_f32(a, b):
+    """bit for bit"""
+    a, b = F32(a), F32(b)
+    return a.view(np.uint32) == b.view(np.uint32)
+
+
+def _round_to_f32(q):
+    """An exact rational rounded ONCE to f32, to nearest, ties to even"""
+    if q == 0:
+        return F32(0.0)
+    a = abs(q)
+    e = a.numerator.bit_length() - a.denominator.bit_length()
+    if a < Fraction(2) ** e:
+        e -= 1
+    assert Fraction(2) ** e <= a < Fraction(2) ** (e + 1)
+    quantum = Fraction(2) ** (max(e, -126) - 23)
+    m = a / quantum
+    n = m.numerator // m.denominator
+    r = m - n
+    if r > Fraction(1, 2) or (r == Fraction(1, 2) and n & 1):
+        n += 1
+    return F32(float(n * quantum) * (-1.0 if q < 0 else 1.0))   # n <= 2^24 times a power of two: exact in a double
+
+
+def welford_std(x, fused):
+    """ndarray's std_axis(Axis(0), 0.) on a 1-D f32 array, restated apart from the oracle.  fused: sum_sq = fma(x - mean,
+    delta, sum_sq) from exact rationals rounded once (math.fma is a float64 operation: rounding its result to f32 would round
+    twice); not fused: the product rounded to f32, then the sum"""
+    mean, sum_sq = F32(0.0), F32(0.0)
+    for i, v in enumerate(np.asarray(x, F32)):
+        delta = F32(v - mean)
+        mean = F32(mean + F32(delta / F32(i + 1)))
+        d2 = F32(v - mean)
+        if fused:
+            sum_sq = _round_to_f32(Fraction(float(d2)) * Fraction(float(delta)) + Fraction(float(sum_sq)))
+        else:
+            sum_sq = F32(F32(d2 * delta) + sum_sq)
+    return F32(np.sqrt(F32(sum_sq / F32(F32(len(x)) - F32(0.0)))))
+
+
+def replay_timbral(oracle, series, mx):
+    """features (2, 3), (4, 5) or (6, 7) from one per-frame series (src/timbral.rs:54-63, 78-87, 108-117)"""
+    return _normalize(F32(oracle.mean(series)), 0.0, mx), _normalize(F32(oracle.std(series)), 0.0, mx)
+
+
+def replay_zcr(crossings256, n):
+    """feature 1 (src/timbral.rs:250-252) from the crossings of the 256-sample blocks"""
+    return _normalize(F32(int(np.sum(crossings256, dtype=np.int64))) / F32(int(n)), 0.0, 1.0)
+
+
+def replay_levels(e256, n):
+    """level of every 1024-sample chunk (src/misc.rs:12-18, 44-48): its up to four block energies added in order in f32 from
+    0.0f, over the chunk's true length"""
+    assert len(e256) == -(-n // 256), (len(e256), n)
+    n_l = -(-n // LOUD_W)
+    e = np.zeros((n_l, 4), F32)
+    e.reshape(-1)[:len(e256)] = e256          # a missing block adds +0.0f to a non-negative sum: no change
+    en = F32(0.0) + e[:, 0]
+    for k in (1, 2, 3):
+        en = (en + e[:, k]).astype(F32)
+    lens = np.full(n_l, LOUD_W, np.int64)
+    lens[-1] = n - LOUD_W * (n_l - 1)
+    return (en / lens.astype(F32)).astype(F32)
+
+
+def _f32_at_or_below(v):
+    f = F32(v)
+    return f if float(f) <= v else np.nextafter(f, F32(-np.inf))
+
+
+def _f32_at_or_above(v):
+    f = F32(v)
+    return f if float(f) >= v else np.nextafter(f, F32(np.inf))
+
+
+def loudness_feature(v):
+    """v: the clamped f32 mean or std of the levels.  -> (reference, lowest, highest f32 the device may give): the reference
+    is 10 log10(v) in float64, rounded to f32 and normalised in f32; the range is the image of LOG10F_ULP ulp of the logarithm
+    (see the section's head) widened by one f32 ulp of the feature"""
+    log = math.log10(float(v))
+    ref = _normalize(F32(10.0 * log), -90.0, 0.0)
+    ulp = float(np.spacing(_f32_at_or_below(abs(log))))
+    lo, hi = _f32_at_or_below(log - LOG10F_ULP * ulp), _f32_at_or_above(log + LOG10F_ULP * ulp)
+    f_lo, f_hi = (_normalize(F32(F32(10.0) * w), -90.0, 0.0) for w in (lo, hi))
+    assert f_lo <= ref <= f_hi
+    return ref, np.nextafter(f_lo, F32(-np.inf)), np.nextafter(f_hi, F32(np.inf))
+
+
+def replay_loudness(oracle, levels):
+    """features 8 and 9 (src/misc.rs:51-65) -> [(reference, lowest, highest, clamp taken)] for the mean and the std"""
+    out = []
+    for v in (F32(oracle.mean(levels)), F32(oracle.std(levels))):
+        clamped = bool(v < F32(1e-9))
+        out.append(loudness_feature(F32(1e-9) if clamped else v) + (clamped,))
+    return out
+
+
+def gated_tone(n, period):
+    """A 10 kHz tone switched on and off (digital silence) every period / 2 samples.  Its per-frame series jump between
+    nothing and the top of their range, so their std lies near the middle of it and the std features (3, 5, 7) near 0, where
+    an f32 is fine enough to show one ulp of the std.  On white noise the std is a few per cent of the range, `2 std / max - 1`
+    sits near -1 and swallows four of its bits: no white-noise song of the set tells a fused Welford step from a separately
+    rounded one in its row, one gated song in four does (test_summary_song_set_reaches_the_kernel counts them)."""
+    t = np.arange(n)
+    return (0.5 * np.sin(2 * np.pi * 10000.0 * t / SR) * ((t // (period // 2)) % 2 == 0)).astype(F32)
+
+
+def summary_songs(oracle):
+    """-> (names, songs) of section 7's batch, in the caller's order"""
+    live = [(f"noise_nt{61 + j}", oracle.white_noise(9700 + j, 8192 + 128 * j)) for j in range(41)]
+    k = 0
+    for base in (8192, 12288, 20480, 30720, 38912):
+        for r in SUMMARY_RESIDUES:
+            if base + r > 8192:   # 8192 itself is noise_nt61
+                live.append((f"res_{base}+{r}", oracle.white_noise(9800 + k, base + r)))
+                k += 1
+    live += [(f"filler_{k}", oracle.white_noise(9900 + k, 8192 + 613 * k + k % 7)) for k in range(26)]
+    live += [(f"gated_{k}", gated_tone(8192 + 613 * k + k % 7, 1536 + 128 * (k % 9))) for k in range(26, 52)]
+    t = np.arange(33333)
+    live += [
+        ("silence", np.zeros(30000, F32)),
+        ("dc", np.full(25000, 0.25, F32)),
+        ("square", np.where(np.arange(20001) % 50 < 25, 1.0, -1.0).astype(F32)),
+        ("tone_440", (0.5 * np.sin(2 * np.pi * 440.0 * t / SR)).astype(F32)),
+        ("noise_1e-12", (oracle.white_noise(9990, 22222) * F32(1e-12)).astype(F32)),
+        ("noise_1e4", (oracle.white_noise(9991, 17777) * F32(1e4)).astype(F32)),
+        ("noise_60s", oracle.white_noise(9992, 60 * SR)),
+    ]
+    names, songs = [k for k, _ in live], [x for _, x in live]
+    for pos in sorted(SUMMARY_SHORT):
+        n = SUMMARY_SHORT[pos]
+        names.insert(pos, f"short_{n}")
+        songs.insert(pos, oracle.white_noise(9995, 8191)[:n])
+    return names, songs
+
+
+@pytest.fixture(scope="module")
+def summary_set(oracle):
+    return summary_songs(oracle)
+
+
+def _blocks_of(x):
+    """(energy, crossings) of the 256-sample blocks of x, the energies in float64 (exact for the inputs of the CPU test)"""
+    edges = np.arange(0, len(x), 256)
+    pos = x > 0.0
+    flips = np.concatenate([[False], pos[1:] != pos[:-1]])   # number_crossings (src/utils.rs:81-95): was_positive starts at x[0]
+    return np.add.reduceat(x.astype(np.float64) ** 2, edges), np.add.reduceat(flips.astype(np.int64), edges)
+
+
+def test_oracle_std_is_the_fused_welford(oracle):
+    """oracle.std, the `std` of every replay below, is ndarray's Welford step with ONE rounding in its multiply-add: bit for
+    bit against exact rationals rounded once, on series among which the separately rounded form gives another f32."""
+    rng = np.random.default_rng(707)
+    series = {
+        "noise_200": oracle.white_noise(9701, 200),
+        "noise_97": oracle.white_noise(9008, 97),
+        "noise_61": oracle.white_noise(9002, 61),
+        "noise_5": oracle.white_noise(9011, 5),
+        "centroids_97": rng.uniform(500.0, 6000.0, 97).astype(F32),
+        "rolloffs_61": (rng.integers(20, 250, 61) * 43.06640625).astype(F32),
+        "levels_33": (rng.uniform(0.0, 1.0, 33) ** 2).astype(F32),
+        "constant_64": np.full(64, 0.0625, F32),
+        "single": np.array([3.5], F32),
+        "tiny_50": (rng.standard_normal(50) * 1e-20).astype(F32),
+    }
+    differs = []
+    for k, s in series.items():
+        assert len(s) <= 200
+        fused, plain = welford_std(s, True), welford_std(s, False)
+        got = F32(oracle.std(s))
+        assert _same_f32(got, fused), f"{k}: oracle.std {got!r}, Welford with an exact fused multiply-add {fused!r} (separately rounded {plain!r})"
+        if not _same_f32(fused, plain):
+            differs.append(k)
+    print("series on which a separately rounded multiply-add gives another std:", differs)
+    # (a rounding of the product moves the sum only while the sum is small, and most such differences are absorbed as the sum
+    # grows: about one white-noise series in eight ends in another f32 -- the device test has over 500 series)
+    assert differs, "no series of the set tells a fused multiply-add from a separately rounded one"
+    assert _same_f32(welford_std(series["constant_64"], True), F32(0.0))
+
+
+def test_summary_replay_reproduces_the_oracle(oracle):
+    """The replay of features 1, 8 and 9 is the oracle's zcr / loudness.  The songs take values k / 16, |k| <= 16: every f32
+    sum of up to 1024 of their squares is exact, so block sums added in order ARE the reference's sequential sums, and the
+    only difference left is the host's log10f against float64 -- held to the allowance of the device test."""
+    rng = np.random.default_rng(708)
+    worst = [0, 0]
+    lengths = [8192 + r for r in SUMMARY_RESIDUES] + [20480 + r for r in SUMMARY_RESIDUES] + [8192 + 613 * 7 + 3]
+    songs = [(rng.integers(-16, 17, n) / 16.0).astype(F32) for n in lengths]
+    songs += [np.zeros(9000, F32), np.full(25000, 0.25, F32), np.where(np.arange(20001) % 50 < 25, 1.0, -1.0).astype(F32)]
+    clamps = []
+    for x in songs:
+        n = len(x)
+        e, zc = _blocks_of(x)
+        assert int(zc.sum()) == oracle.number_crossings(x), n
+        assert _same_f32(replay_zcr(zc, n), F32(oracle.zcr(x))), n
+        levels = replay_levels(e.astype(F32), n)
+        assert len(levels) == -(-n // LOUD_W)
+        ref = oracle.loudness(x)
+        for k, (want, lo, hi, clamped) in enumerate(replay_loudness(oracle, levels)):
+            assert lo <= ref[k] <= hi, (n, 8 + k, ref[k], want, lo, hi)
+            if clamped:
+                assert ref[k] == F32(-1.0) and want == F32(-1.0), (n, 8 + k, ref[k], want)
+            worst[k] = max(worst[k], int(_ulps(ref[k], want)))
+            clamps.append((n, 8 + k, clamped))
+    print(f"oracle.loudness against the replay: worst {worst[0]} / {worst[1]} ulp of features 8 / 9")
+    assert {(f, c) for _, f, c in clamps} == {(8, False), (8, True), (9, False), (9, True)}
+
+
+def _scheduler_order(lengths):
+    """The batch scheduler keeps a chunk's songs longest first, equal lengths in the caller's order"""
+    return sorted(range(len(lengths)), key=lambda i: -lengths[i])
+
+
+def test_summary_song_set_reaches_the_kernel(oracle, summary_set):
+    """From the lengths alone: what section 7's batch puts in front of seq_for_each, of the loudness chunks and of the
+    64-songs-per-wavefront mapping; from the oracle, which songs take the two clamps."""
+    names, songs = summary_set
+    lengths = [len(x) for x in songs]
+    live = [n for n in lengths if n >= 8192]
+    assert 140 <= len(songs) <= 160 and sum(8192 <= n <= 40000 for n in lengths) >= len(songs) - 6
+    # three blocks of 64 lanes, the last one part filled, also when only the live songs count
+    assert 128 < len(live) <= len(songs) < 192 and len(songs) % 64 and len(live) % 64
+    short = [i for i, n in enumerate(lengths) if n < 8192]
+    assert [lengths[i] for i in short] == [0, 1, 100, 8191] and short == sorted(SUMMARY_SHORT)
+    assert short[0] > 0 and short[-1] < len(songs) - 1 and min(np.diff(short)) > 32, short   # live songs on both sides of each
+    # the white-noise ladder: every residue of n_t mod 4 and mod 32, one or two whole chunks (and more) after a prologue
+    n_t = [(n - 512) // 128 + 1 for n in lengths[:7] + lengths[8:42]]
+    assert n_t == list(range(61, 102)), n_t
+    assert {v % 32 for v in n_t} == set(range(32)) and {v % 4 for v in n_t} == set(range(4))
+    assert {(v - 3) // 32 for v in n_t} | {v // 32 for v in n_t} >= {1, 2, 3}
+    # every start alignment of a series (float index mod 4 within a 256-byte aligned buffer), in the scheduler's order and in
+    # the caller's; the series lie back to back, so an offset is the sum of the counts before it
+    for order in (_scheduler_order(lengths), list(range(len(lengths)))):
+        ordered = [lengths[i] for i in order if lengths[i] >= 8192]
+        for count in (lambda n: (n - 512) // 128 + 1, lambda n: -(-n // 256)):
+            starts = np.concatenate([[0], np.cumsum([count(n) for n in ordered])[:-1]])
+            assert all((starts % 4 == a).sum() >= 8 for a in range(4)), [(starts % 4 == a).sum() for a in range(4)]
+    # the loudness chunks: every listed residue, a last chunk of 1, 2, 3 and 4 blocks, short last blocks, and series of
+    # 32 .. 35 blocks (less than one whole 32-element step once a prologue of 1 .. 3 has run)
+    assert {n % LOUD_W for n in live} >= set(SUMMARY_RESIDUES)
+    assert {-(-(n % LOUD_W or LOUD_W) // 256) for n in live} == {1, 2, 3, 4}
+    assert sum(n % 256 != 0 for n in live) > 100
+    assert {-(-n // 256) for n in live} >= {32, 33, 34, 35}
+    assert max(live) == 60 * SR and -(-max(live) // 256) > 5000      # the long chain
+    # the Welford step's fused multiply-add must show in a ROW: on the oracle's own series, the std features of the gated songs
+    # that come out differently when the product is rounded on its own (5 of 78)
+    shows = []
+    for k, x in zip(names, songs):
+        if k.startswith("gated_"):
+            for series, (_, f, mx) in zip(oracle.SpectralDesc().run(x).series(), SUMMARY_SERIES):
+                if not _same_f32(_normalize(welford_std(series, True), 0.0, mx), _normalize(welford_std(series, False), 0.0, mx)):
+                    shows.append((k, f + 1))
+    print("std features that tell a fused multiply-add from a separately rounded one:", shows)
+    assert len(shows) >= 3, shows
+    # the clamps, on the oracle (exact inputs, or clear of the threshold by orders of magnitude)
+    taken = {8: [], 9: []}
+    for k, x in zip(names, songs):
+        if len(x) >= 8192 and not k.startswith(("noise_nt", "res_", "filler_", "gated_")):
+            e, _ = _blocks_of(x)
+            for f, (want, _, _, clamped) in zip((8, 9), replay_loudness(oracle, replay_levels(e.astype(F32), len(x)))):
+                if clamped:
+                    taken[f].append(k)
+                    assert want == F32(-1.0) and oracle.loudness(x)[f - 8] == F32(-1.0), (k, f)
+    print("oracle: mean clamp (feature 8):", taken[8], " std clamp (feature 9):", taken[9])
+    assert taken[8] == ["silence", "noise_1e-12"] and taken[9] == ["silence", "dc", "square", "noise_1e-12"], taken
+
+
+@pytest.mark.gpu
+def test_summary_features_on_the_device_series(bliss, oracle, summary_set):
+    """Features 1..7 of every live song bit for bit, features 8 and 9 within the image of LOG10F_ULP = 2 ulp of log10f plus
+    one ulp of the feature, exactly -1.0f where a clamp is taken; too-short songs: status 1, a NaN row, no taps, and the rows
+    of the others are those of the batch without them.
+
+    Measured on the MI355X: 973 values bit for bit (139 songs x features 1..7); features 8 / 9 at most 4 / 8 ulp of the
+    feature from the float64 reference (noise_nt82 / filler_13; the widest allowed range is 17 ulp: the bound on log10f is
+    2 ulp, but one ulp of 10 log10(v) + 90 near 85 is 1.7e-7 in the feature, many ulp of a feature near 0); mean clamp:
+    silence, noise_1e-12; std clamp: silence, dc, square, noise_1e-12.  With the Welford step's fused multiply-add replaced
+    by a product and a sum, 10 of the 973 values differ (by one ulp); with the last loudness chunk over 1024, features 8 / 9
+    are up to 220 202 ulp away; with the prologue of seq_for_each starting at 1, 684 of the 973 differ."""
+    names, songs = summary_set
+    ctx = bliss.Context(0)
+    try:
+        rows, status = _run(ctx, songs)
+        assert ctx.last_chunks() == 1
+        bad, exact, differ, worst, widest, taken = [], 0, 0, {8: (0, ""), 9: (0, "")}, 0, {8: [], 9: []}
+        for i, (k, x) in enumerate(zip(names, songs)):
+            n = len(x)
+            if n < 8192:
+                assert status[i] == 1 and np.isnan(rows[i]).all(), (k, status[i], rows[i])
+                assert all(len(ctx.debug_fetch_raw(tap, i)) == 0 for tap in ("centroid", "energy256", "crossings256")), k
+                continue
+            assert status[i] == 0 and np.isfinite(rows[i]).all(), (k, status[i], rows[i])
+            want = {}
+            for tap, f, mx in SUMMARY_SERIES:
+                series = ctx.debug_fetch(tap, i)
+                assert len(series) == (n - 512) // 128 + 1, (k, tap, len(series))
+                want[f], want[f + 1] = replay_timbral(oracle, series, mx)
+            e, zc = ctx.debug_fetch("energy256", i), ctx.debug_fetch("crossings256", i)
+            assert int(zc.sum(dtype=np.int64)) == oracle.number_crossings(x), k
+            want[1] = replay_zcr(zc, n)
+            for f in range(1, 8):
+                exact += 1
+                if not _same_f32(rows[i, f], want[f]):
+                    differ += 1
+                    bad.append(f"{k} (n = {n}): feature {f}: device {rows[i, f]!r}, replay {want[f]!r} ({int(_ulps(rows[i, f], want[f]))} ulp)")
+            for f, (ref, lo, hi, clamped) in zip((8, 9), replay_loudness(oracle, replay_levels(e, n))):
+                got = rows[i, f]
+                d = int(_ulps(got, ref))
+                widest = max(widest, int(_ulps(lo, ref)), int(_ulps(hi, ref)))
+                if d > worst[f][0]:
+                    worst[f] = (d, k)
+                if clamped:
+                    taken[f].append(k)
+                    if got != F32(-1.0):
+                        bad.append(f"{k}: feature {f} takes the 1e-9 clamp and must be -1.0f: device {got!r}")
+                elif not lo <= got <= hi:
+                    bad.append(f"{k} (n = {n}): feature {f}: device {got!r}, float64 reference {ref!r} ({d} ulp), allowed {lo!r} .. {hi!r}")
+        print(f"features 1..7 of {exact // 7} songs: {exact} values compared bit for bit, {differ} differ")
+        print(f"features 8 / 9 against the float64 reference: worst {worst[8][0]} ulp ({worst[8][1]}) / {worst[9][0]} ulp ({worst[9][1]}); "
+              f"the widest allowed range is {widest} ulp")
+        print("mean clamp (feature 8):", taken[8], " std clamp (feature 9):", taken[9])
+        assert not bad, f"{len(bad)} differences; the first: " + "; ".join(bad[:6])
+        assert taken[8] == ["silence", "noise_1e-12"] and taken[9] == ["silence", "dc", "square", "noise_1e-12"], taken
+        # the too-short songs do not shift their neighbours: the same rows without them
+        keep = [i for i, x in enumerate(songs) if len(x) >= 8192]
+        rows2, status2 = _run(ctx, [songs[i] for i in keep])
+        assert (status2 == 0).all() and _same(rows2, rows[keep])
+    finally:
+        ctx.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# 8. the chroma features on the device's own interval means
+# ---------------------------------------------------------------------------------------------
+CHORDS = {   # semitones from A = 440, equal tempered
+    "chord_augmented": (-9, -5, -1),
+    "chord_dim7": (-9, -6, -3, 0),
+    "chord_tritone": (-9, -3),
+    "chord_major": (-9, -5, -2),
+}
+CLAMP_20 = ["chord_augmented", "chord_dim7", "chord_tritone"]   # the songs whose feature 20 (21) sits on the 1.0 clamp
+CLAMP_21 = ["chord_augmented", "chord_dim7"]
+
+
+def chroma_songs(oracle, musical=True):
+    """Section 8's songs: those of test_chroma_stage_on_detuned_songs, and four-second sine chords"""
+    songs = {}
+    if musical:
+        import os
+        import sys
+
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+        import musical_check
+
+        rng = np.random.default_rng(404)
+        for i in range(12):
+            songs[f"musical_{i}"] = musical_check.make_song(rng)[0]
+    songs["noise_64_frames+17"] = oracle.white_noise(31, 64 * HOP + 17)
+    songs["min_len_8192"] = oracle.white_noise(32, 8192)
+    songs["silence"] = np.zeros(3 * SR, F32)
+    t = np.arange(4 * SR) / SR
+    for k, semis in CHORDS.items():
+        songs[k] = (0.2 * sum(np.sin(2 * np.pi * 440.0 * 2.0 ** (s / 12.0) * t) for s in semis)).astype(F32)
+    return songs
+
+
+def replay_chroma_v1(interval):
+    """ChromaDesc::get_values_version_1 (src/chroma.rs:128-132) of the ten interval means -> features 10..19"""
+    return np.array([_normalize(F32(v), 0.0, 0.12) for v in interval], F32)
+
+
+def replay_chroma_v2(interval):
+    """ChromaDesc::get_values (src/chroma.rs:97-126) of the ten interval means -> features 10..22: the two norms summed in
+    index order, the divisions where a norm is positive, the f32 cast and 2 v - 1, the two clamped norms, the angle"""
+    raw = [float(v) for v in interval]
+    n1 = n2 = 0.0
+    for t in range(6):
+        n1 += raw[t] * raw[t]
+    for t in range(6, 10):
+        n2 += raw[t] * raw[t]
+    n1, n2 = math.sqrt(n1), math.sqrt(n2)
+    if n1 > 0.0:
+        raw[:6] = [v / n1 for v in raw[:6]]
+    if n2 > 0.0:
+        raw[6:] = [v / n2 for v in raw[6:]]
+    out = [_normalize(F32(v), 0.0, 1.0) for v in raw]
+    out.append(min(_normalize(F32(n1), 0.0, 0.25), F32(1.0)))
+    out.append(min(_normalize(F32(n2), 0.0, 0.025), F32(1.0)))
+    out.append(_normalize(F32(math.atan2(20.0 * n2, n1 + 1e-12)), 0.0, F32(1.57079632679489661923)))
+    return np.array(out, F32)
+
+
+def _check_chroma_row(row, interval, version, what):
+    """-> (values equal bit for bit, 1 if feature 22 differs (by one ulp) else 0)"""
+    want = replay_chroma_v1(interval) if version == 1 else replay_chroma_v2(interval)
+    assert len(row) == 10 + len(want), (what, len(row))
+    exact = min(len(want), 12)
+    got = np.ascontiguousarray(row[10:], F32)
+    diff = np.flatnonzero(got[:exact].view(np.uint32) != want[:exact].view(np.uint32))
+    assert not len(diff), f"{what}: feature {10 + diff[0]}: {got[diff[0]]!r}, replay {want[diff[0]]!r}; interval means {interval.tolist()}"
+    if version == 1:
+        return exact, 0
+    d = int(_ulps(got[12], want[12]))
+    assert d <= 1, f"{what}: feature 22: {got[12]!r}, replay {want[12]!r}: {d} ulp"
+    return exact, d
+
+
+def test_chroma_replay_and_clamps_on_the_oracle(oracle):
+    """The NumPy replay is the oracle's get_values / get_values_version_1 on the oracle's own interval means (features
+    10..21 bit for bit, 22 within an ulp), and the chords sit where section 8 needs them: the augmented triad and the
+    diminished seventh on both 1.0 clamps, the tritone on the first with feature 21 near -0.96, the major triad and the
+    other songs on neither; silence has a uniform chroma and positive norms."""
+    on20, on21 = [], []
+    for k, x in chroma_songs(oracle, musical=False).items():
+        chroma, _ = oracle.chroma_desc(x)
+        interval = oracle.chroma_interval_features(chroma)
+        v2 = oracle.chroma_get_values(chroma, 2)
+        _check_chroma_row(np.concatenate([np.zeros(10, F32), v2]), interval, 2, k)
+        _check_chroma_row(np.concatenate([np.zeros(10, F32), oracle.chroma_get_values(chroma, 1)]), interval, 1, k)
+        assert (v2[10:12] <= 1.0).all()
+        if v2[10] == 1.0:
+            on20.append(k)
+        if v2[11] == 1.0:
+            on21.append(k)
+        if k == "chord_tritone":
+            assert abs(float(v2[11]) + 0.96) < 0.02, v2[11]
+        if k == "silence":
+            # chroma_stft gives zeros; exp(15 x) and the column normalisation of chroma_interval_features make every pitch
+            # class 1 / 12: the interval means are 1 / 12 and 1 / 144, neither norm is zero and both divisions happen
+            assert not chroma.any() and np.allclose(interval, [1 / 12] * 6 + [1 / 144] * 4, rtol=1e-12), (chroma[:, 0], interval)
+            assert (v2[:10] > -1.0).all() and (v2[10:12] < 1.0).all(), v2
+    print("oracle: feature 20 on the clamp:", on20, " feature 21 on the clamp:", on21)
+    assert on20 == CLAMP_20 and on21 == CLAMP_21, (on20, on21)
+
+
+@pytest.mark.gpu
+def test_chroma_features_on_the_device_interval(bliss, oracle):
+    """Features 10..19 (v1) and 10..21 (v2) of every song bit for bit from the interval tap of the same run, feature 22 within
+    one f32 ulp; features 0..9 of the v1 and v2 rows identical.
+
+    Measured on the MI355X: 19 songs, 190 + 228 values bit for bit; feature 22 differs (by one ulp) on 0 songs; feature 20 on
+    the clamp: the augmented triad, the diminished seventh, the tritone; feature 21: the first two."""
+    songs = chroma_songs(oracle)
+    names = list(songs)
+    ctx = bliss.Context(0)
+    ctx.set_option("debug_chroma", 1)
+    try:
+        rows, exact, differ22 = {}, {1: 0, 2: 0}, []
+        for version in (1, 2):
+            rows[version], status = _run(ctx, [songs[k] for k in names], version)
+            assert (status == 0).all() and ctx.last_chunks() == 1
+            assert rows[version].shape == (len(names), 20 if version == 1 else 23)
+            for i, k in enumerate(names):
+                interval = ctx.debug_fetch("interval", i)
+                assert interval.shape == (10,) and interval.dtype == np.float64
+                n, d = _check_chroma_row(rows[version][i], interval, version, f"v{version} {k}")
+                exact[version] += n
+                if d:
+                    differ22.append(k)
+        assert _same(rows[1][:, :10], rows[2][:, :10]), "features 0..9 differ between the v1 and the v2 row"
+        on20 = [k for i, k in enumerate(names) if rows[2][i, 20] == 1.0]
+        on21 = [k for i, k in enumerate(names) if rows[2][i, 21] == 1.0]
+        print(f"{len(names)} songs: {exact[1]} (v1) + {exact[2]} (v2) chroma features compared bit for bit; feature 22 differs by "
+              f"one ulp on {len(differ22)} songs: {differ22}")
+        print("feature 20 on the clamp:", on20, " feature 21 on the clamp:", on21)
+        assert (rows[2][:, 20:22] <= 1.0).all()
+        assert on20 == CLAMP_20 and on21 == CLAMP_21, (on20, on21)
+    finally:
+        ctx.set_option("debug_chroma", 0)
+        ctx.close()
