@@ -26,6 +26,7 @@
 //!   * `closest_to_songs(&[song], ..)` cut after k, many songs per call (`Library::playlist_from(..).take(k)`)
 //!                                             src/playlist.rs:256-270     -> [`nearest_on_device`]
 //!   * `closest_to_songs(.., &ForestOptions)`  src/playlist.rs:230-270     -> [`forest_order_on_device`]
+//!   * the same per album, in one call                                     -> [`forest_group_playlists_on_device`]
 //!
 //! build.rs of the crate, under the feature:
 //! ```ignore
@@ -195,6 +196,19 @@ pub mod sys {
                                             d_score: *mut f32, d_path_sum: *mut u64) -> c_int;
         pub fn blissgpu_forest_closest_to_songs_device(ctx: *mut blissgpu_ctx, forest: *mut c_void, d_cand: *const f32, n: u64,
                                                        d_order: *mut u32, d_score: *mut f32) -> c_int;
+        // one forest per seed group: the k lowest forest scores of every group in one call
+        pub fn blissgpu_group_forest_knn(seeds: *const f32, group_offsets: *const u64, n_groups: u64, cand: *const f32, n: u64, d: u32,
+                                         n_trees: u32, sample_size: u32, max_tree_depth: u32, extension_level: u32, seed: u64,
+                                         skip: *const u32, k: u32, idx: *mut u32, score: *mut f32, group_status: *mut i32) -> c_int;
+        pub fn blissgpu_group_forest_knn_device(ctx: *mut blissgpu_ctx, d_seeds: *const f32, h_seeds: *const f32,
+                                                group_offsets: *const u64, n_groups: u64, d_cand: *const f32, n: u64, d: u32,
+                                                n_trees: u32, sample_size: u32, max_tree_depth: u32, extension_level: u32, seed: u64,
+                                                d_skip: *const u32, k: u32, d_idx: *mut u32, d_score: *mut f32,
+                                                d_group_status: *mut i32) -> c_int;
+        pub fn blissgpu_group_forest_plan(group_offsets: *const u64, n_groups: u64, d: u32, n_trees: u32, sample_size: u32,
+                                          max_tree_depth: u32, extension_level: u32, node_budget: u64, batch_first: *mut u64,
+                                          max_batches: u64, n_batches: *mut u64) -> c_int;
+        pub fn blissgpu_debug_group_forest_stats(ctx: *mut blissgpu_ctx, build_ms: *mut f64, wait_ms: *mut f64, n_batches: *mut u64) -> c_int;
 
         // ---- one process, every GPU of the node ----
         pub fn blissgpu_node_create(n_devices: c_int, devices: *const c_int, node: *mut *mut blissgpu_node) -> c_int;
@@ -632,6 +646,40 @@ pub fn forest_order_on_device<T: AsRef<Song> + Clone>(initial: &[T], candidates:
         return Err(gpu_err(rc));
     }
     Ok(order.into_iter().map(|i| candidates[i as usize].clone()).collect())
+}
+
+/// `closest_to_songs(group, candidates without the group's songs, &ForestOptions)` cut after `k` for every group of `groups`
+/// in one library call: one forest per group (same options, same seed), built on the host while the device scores the
+/// previous ones.  A group with `min(sample_size, members) < 2` has no forest and gets an empty list.
+pub fn forest_group_playlists_on_device<T: AsRef<Song> + Clone>(groups: &[Vec<T>], candidates: &[T], k: usize, options: &ForestOptions,
+                                                                exclude_members: bool) -> BlissResult<Vec<Vec<T>>> {
+    if groups.is_empty() || candidates.is_empty() {
+        return Ok(vec![Vec::new(); groups.len()]);
+    }
+    let d = candidates[0].as_ref().analysis.as_vec().len();
+    let cand = candidates.iter().flat_map(|s| s.as_ref().analysis.as_vec()).collect::<Vec<f32>>();
+    let seeds = groups.iter().flatten().flat_map(|s| s.as_ref().analysis.as_vec()).collect::<Vec<f32>>();
+    let mut offsets = vec![0u64; groups.len() + 1];
+    for (g, group) in groups.iter().enumerate() {
+        offsets[g + 1] = offsets[g] + group.len() as u64;
+    }
+    let skip = groups
+        .iter()
+        .flatten()
+        .map(|s| if exclude_members { candidates.iter().position(|c| c.as_ref() == s.as_ref()).map_or(u32::MAX, |j| j as u32) } else { u32::MAX })
+        .collect::<Vec<u32>>();
+    let mut idx = vec![0u32; groups.len() * k];
+    let rc = unsafe {
+        sys::blissgpu_group_forest_knn(seeds.as_ptr(), offsets.as_ptr(), groups.len() as u64, cand.as_ptr(), candidates.len() as u64,
+                                       d as u32, options.n_trees as u32, options.sample_size.min(u32::MAX as usize) as u32,
+                                       options.max_tree_depth.map_or(0, |k| k.max(1).min(u32::MAX as usize) as u32),
+                                       options.extension_level as u32, options.seed, skip.as_ptr(), k as u32, idx.as_mut_ptr(),
+                                       std::ptr::null_mut(), std::ptr::null_mut())
+    };
+    if rc != sys::BLISSGPU_OK {
+        return Err(gpu_err(rc));
+    }
+    Ok(idx.chunks(k).map(|row| row.iter().filter(|&&j| j != u32::MAX).map(|&j| candidates[j as usize].clone()).collect()).collect())
 }
 
 /// One process driving every GPU of the node: songs sharded by sample count, one `ncclAllGather` of the feature rows over

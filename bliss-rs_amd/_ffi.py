@@ -22,6 +22,8 @@ OPT_STFT_SHAPE = 7
 OPT_FLUX_ORDER = 8
 OPT_STAGE_LANES, OPT_STAGE_SLAB_KIB, OPT_STAGE_SLABS, OPT_STAGE_NUMA = 9, 10, 11, 12
 OPT_FOREST_SPLIT, OPT_FOREST_WALK = 13, 14
+OPT_FOREST_GROUP_NODES = 15
+GROUP_OK, GROUP_TOO_FEW_SEEDS = 0, 1
 
 _f32p = C.POINTER(C.c_float)
 _f64p = C.POINTER(C.c_double)
@@ -122,6 +124,13 @@ SIGNATURES = {
     "blissgpu_forest_closest_to_songs": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp]),
     "blissgpu_forest_score_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp]),
     "blissgpu_forest_closest_to_songs_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp]),
+    "blissgpu_group_forest_knn": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                            C.c_uint32, C.c_uint64, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "blissgpu_group_forest_knn_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                   C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "blissgpu_group_forest_plan": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                             C.c_uint64, _vp, C.c_uint64, _u64p]),
+    "blissgpu_debug_group_forest_stats": (C.c_int, [_vp, _f64p, _f64p, _u64p]),
     "blissgpu_set_distance_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp]),
     "blissgpu_closest_to_songs_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp,
                                                    _vp]),

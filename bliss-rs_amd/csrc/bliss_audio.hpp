@@ -471,6 +471,42 @@ std::vector<T> closest_to_songs(const std::vector<T>& initial_songs, const std::
     return out;
 }
 
+// closest_to_songs with the forest metric for every GROUP of songs in one call, cut after k: one forest per group (same
+// options, same seed), the group's own songs left out when exclude_members (the first candidate equal to each member).  A
+// group with min(sample_size, members) < 2 has no forest and gets an empty list.
+template <typename T>
+std::vector<std::vector<T>> forest_group_playlists(const std::vector<std::vector<T>>& groups, const std::vector<T>& candidate_songs,
+                                                   uint32_t k, const ForestOptions& opts, bool exclude_members = true) {
+    std::vector<std::vector<T>> out(groups.size());
+    if (groups.empty() || candidate_songs.empty()) return out;
+    size_t d = 0, ds = 0;
+    const auto x = feature_matrix(candidate_songs, d);
+    std::vector<T> flat;
+    std::vector<uint64_t> off(groups.size() + 1, 0);
+    for (size_t g = 0; g < groups.size(); g++) {
+        flat.insert(flat.end(), groups[g].begin(), groups[g].end());
+        off[g + 1] = flat.size();
+    }
+    const auto s = feature_matrix(flat, ds);
+    if (!flat.empty() && ds != d) throw std::logic_error("Mismatched features version between two songs or analysis");
+    std::vector<uint32_t> skip(flat.size(), 0xFFFFFFFFu);
+    if (exclude_members)
+        for (size_t i = 0; i < flat.size(); i++)
+            for (size_t j = 0; j < candidate_songs.size(); j++) {
+                const Song &a = as_song(candidate_songs[j]), &b = as_song(flat[i]);
+                if (a.path == b.path && a.analysis == b.analysis && a.album == b.album && a.title == b.title && a.artist == b.artist &&
+                    a.track_number == b.track_number && a.disc_number == b.disc_number) { skip[i] = (uint32_t)j; break; }
+            }
+    std::vector<uint32_t> idx(groups.size() * (size_t)k);
+    check(blissgpu_group_forest_knn(s.data(), off.data(), groups.size(), x.data(), candidate_songs.size(), (uint32_t)d, opts.n_trees,
+                                    opts.sample_size, opts.max_tree_depth, opts.extension_level, opts.seed, skip.data(), k, idx.data(),
+                                    nullptr, nullptr));
+    for (size_t g = 0; g < groups.size(); g++)
+        for (uint32_t i = 0; i < k; i++)
+            if (idx[g * k + i] != 0xFFFFFFFFu) out[g].push_back(candidate_songs[idx[g * k + i]]);
+    return out;
+}
+
 // closest_to_songs for many single seeds at once, cut after k (src/playlist.rs:256-270; Library::playlist_from(&[song])
 // .take(k), src/library.rs:762-850): row i of idx = the k candidates closest to queries[i] in ascending distance, equal
 // distances in candidate order, without candidate skip[i] (0xFFFFFFFF: none); short rows end in 0xFFFFFFFF / +inf.

@@ -24,6 +24,7 @@ thread_local std::string g_last_error;
 
 // (the names of KX_SEGMENT_MEAN and KX_ALBUM_KNN_SCAN, the ids numbered behind the KernelId list: see internal.hpp)
 const char kSegmentMeanName[] = "segment_mean_kernel", kAlbumKnnScanName[] = "album_knn_scan_kernel";
+const char kGroupForestScanName[] = "group_forest_scan_kernel";  // KX_GROUP_FOREST_SCAN
 const char* const kKernelNames[K_COUNT] = {
     "fft512_kernel",     "onset_kernel",      "beat_kernel",   "stft8192_kernel", "tune_select_kernel",
     "tune_pass2_kernel", "tune_final_kernel", "chroma_kernel",     "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel", "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel",
@@ -32,7 +33,7 @@ const char* const kKernelNames[K_COUNT] = {
     "dup_init_kernel", "dup_join_kernel", "dup_flatten_kernel",
     "group_knn_scan_kernel", "group_knn_merge_kernel", "group_weights_kernel",
     "chain_step_kernel", "chain_walk_kernel",
-    kSegmentMeanName, kAlbumKnnScanName};
+    kSegmentMeanName, kAlbumKnnScanName, kGroupForestScanName};
 }  // namespace
 
 namespace bg {
@@ -342,6 +343,11 @@ int blissgpu_ctx_destroy(blissgpu_ctx* c) {
         c->dbg_tuning.release(); c->dbg_nbpms.release(); c->dbg_chroma.release(); c->dbg_interval.release();
         c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->pl_next.release(); c->st_idx.release();
         c->st_a.release(); c->st_b.release(); c->st_m.release(); c->st_dist.release(); c->st_out.release();
+        for (int s = 0; s < 2; s++) {
+            c->gf_img[s].release();
+            c->gf_host[s].release();
+            if (c->gf_ev[s]) (void)hipEventDestroy(c->gf_ev[s]);
+        }
         if (c->h_scalar) (void)hipHostFree(c->h_scalar);
         if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
         if (c->chr_stream) (void)hipStreamDestroy(c->chr_stream);
@@ -397,6 +403,7 @@ int blissgpu_ctx_set_option(blissgpu_ctx* c, int option, int64_t value) {
         case BLISSGPU_OPT_STAGE_SLABS: c->feed.stage_cfg.slabs_per_lane = (int)std::max<int64_t>(1, std::min<int64_t>(value, 8)); break;
         case BLISSGPU_OPT_FOREST_SPLIT: c->forest_split = std::max<int64_t>(0, std::min<int64_t>(value, 65535)); break;
         case BLISSGPU_OPT_FOREST_WALK: c->forest_global = value == 1; break;
+        case BLISSGPU_OPT_FOREST_GROUP_NODES: c->forest_group_nodes = std::max<int64_t>(0, value); break;
         case BLISSGPU_OPT_CAND_BUDGET: c->cand_budget = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 714)); break;
         default: return fail(BLISSGPU_ERR_INVALID, "blissgpu_ctx_set_option", "unknown option");
     }
@@ -1925,6 +1932,134 @@ int blissgpu_forest_closest_to_songs(void* forest, const float* cand, uint64_t n
     int rc = forest_args_ok("blissgpu_forest_closest_to_songs", forest, cand, n, order);
     if (rc || n == 0) return rc;
     return forest_host("blissgpu_forest_closest_to_songs", forest, cand, n, score, nullptr, order);
+}
+
+// ---- one forest per seed GROUP: the k lowest forest scores of every group in one call ----
+// everything that can be said about the arguments without a device and without building a forest
+static int group_forest_args_ok(const char* who, const float* h_seeds, bool seeds_given, const uint64_t* off, uint64_t n_groups,
+                                const void* cand, uint64_t n, uint32_t d, uint32_t n_trees, uint32_t max_tree_depth,
+                                uint32_t extension_level, uint32_t k, const void* idx) {
+    if (k == 0 || k > BLISSGPU_KNN_MAX_K) return fail(BLISSGPU_ERR_INVALID, who, "k must be 1 .. BLISSGPU_KNN_MAX_K");
+    if (d == 0 || d > BLISSGPU_FOREST_MAX_D) return fail(BLISSGPU_ERR_INVALID, who, "d must be 1 .. BLISSGPU_FOREST_MAX_D");
+    if (n_trees == 0 || n_trees > BLISSGPU_FOREST_MAX_TREES) return fail(BLISSGPU_ERR_INVALID, who, "n_trees must be 1 .. BLISSGPU_FOREST_MAX_TREES");
+    if (extension_level > d - 1) return fail(BLISSGPU_ERR_INVALID, who, "extension_level must be 0 .. d - 1");
+    if (max_tree_depth > BLISSGPU_FOREST_MAX_DEPTH) return fail(BLISSGPU_ERR_INVALID, who, "max_tree_depth must be 1 .. 128 (0: none)");
+    if (n >= 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "n must be below 2^32 - 1 candidates");
+    if (n_groups >= 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "n_groups must be below 2^32 - 1");
+    if (n_groups == 0) return BLISSGPU_OK;
+    if (!off) return fail(BLISSGPU_ERR_INVALID, who, "group_offsets is NULL");
+    if (off[0] != 0) return fail(BLISSGPU_ERR_INVALID, who, "group_offsets[0] must be 0");
+    for (uint64_t g = 0; g < n_groups; g++)
+        if (off[g + 1] < off[g]) return fail(BLISSGPU_ERR_INVALID, who, "group_offsets must not decrease");
+    if (off[n_groups] > 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "2^32 seeds or more");
+    if (off[n_groups] && !seeds_given) return fail(BLISSGPU_ERR_INVALID, who, "seeds is NULL");
+    if (n && !cand) return fail(BLISSGPU_ERR_INVALID, who, "cand is NULL");
+    if (!idx) return fail(BLISSGPU_ERR_INVALID, who, "idx is NULL");
+    if (h_seeds)
+        for (uint64_t i = 0; i < off[n_groups] * d; i++)
+            if (!std::isfinite(h_seeds[i])) return fail(BLISSGPU_ERR_INVALID, who, "seed rows must be finite");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_group_forest_plan(const uint64_t* group_offsets, uint64_t n_groups, uint32_t d, uint32_t n_trees, uint32_t sample_size,
+                               uint32_t max_tree_depth, uint32_t extension_level, uint64_t node_budget, uint64_t* batch_first,
+                               uint64_t max_batches, uint64_t* n_batches) {
+    const char* who = "blissgpu_group_forest_plan";
+    uint32_t none = 0;  // (the plan reads neither seeds nor candidates)
+    int rc = group_forest_args_ok(who, nullptr, true, group_offsets, n_groups, nullptr, 0, d, n_trees, max_tree_depth, extension_level, 1,
+                                  &none);
+    if (rc) return rc;
+    if (!n_batches || (max_batches && !batch_first)) return fail(BLISSGPU_ERR_INVALID, who, "NULL argument");
+    if (n_groups == 0) { *n_batches = 0; return BLISSGPU_OK; }
+    if (node_budget == 0) node_budget = group_forest_budget(~0ull, extension_level);
+    const std::vector<uint64_t> first = group_forest_batches(group_offsets, n_groups, n_trees, sample_size, node_budget);
+    *n_batches = first.size() - 1;
+    for (uint64_t i = 0; i < first.size() && i < max_batches; i++) batch_first[i] = first[i];
+    return BLISSGPU_OK;
+}
+
+int blissgpu_group_forest_knn_device(blissgpu_ctx* c, const float* d_seeds, const float* h_seeds, const uint64_t* group_offsets,
+                                     uint64_t n_groups, const float* d_cand, uint64_t n, uint32_t d, uint32_t n_trees,
+                                     uint32_t sample_size, uint32_t max_tree_depth, uint32_t extension_level, uint64_t seed,
+                                     const uint32_t* d_skip, uint32_t k, uint32_t* d_idx, float* d_score, int32_t* d_group_status) {
+    const char* who = "blissgpu_group_forest_knn_device";
+    int rc = group_forest_args_ok(who, h_seeds, d_seeds || h_seeds, group_offsets, n_groups, d_cand, n, d, n_trees, max_tree_depth,
+                                  extension_level, k, d_idx);
+    if (rc) return rc;
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    if (n_groups == 0) return BLISSGPU_OK;
+    CTX_ENTER(c, who);
+    std::vector<float> copy;
+    const uint64_t n_seeds = group_offsets[n_groups];
+    if (!h_seeds && n_seeds) {  // the forests are built on the host: the one device-to-host copy of the seed rows
+        copy.resize((size_t)n_seeds * d);
+        HIP_TRY(hipMemcpyAsync(copy.data(), d_seeds, copy.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (float v : copy)
+            if (!std::isfinite(v)) return fail(BLISSGPU_ERR_INVALID, who, "seed rows must be finite");
+        h_seeds = copy.data();
+    }
+    const GroupForestOpts o{d, n_trees, sample_size, max_tree_depth, extension_level, seed};
+    return group_forest_run(c, who, h_seeds, group_offsets, n_groups, d_cand, n, o, d_skip, k, d_idx, d_score, d_group_status, nullptr);
+}
+
+int blissgpu_group_forest_knn(const float* seeds, const uint64_t* group_offsets, uint64_t n_groups, const float* cand, uint64_t n,
+                              uint32_t d, uint32_t n_trees, uint32_t sample_size, uint32_t max_tree_depth, uint32_t extension_level,
+                              uint64_t seed, const uint32_t* skip, uint32_t k, uint32_t* idx, float* score, int32_t* group_status) {
+    const char* who = "blissgpu_group_forest_knn";
+    int rc = group_forest_args_ok(who, seeds, seeds != nullptr, group_offsets, n_groups, cand, n, d, n_trees, max_tree_depth,
+                                  extension_level, k, idx);
+    if (rc) return rc;
+    if (n_groups == 0) return BLISSGPU_OK;
+    const uint64_t n_seeds = group_offsets[n_groups];
+    if (skip)
+        for (uint64_t i = 0; i < n_seeds; i++)
+            if (skip[i] != 0xFFFFFFFFu && skip[i] >= n) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
+    const size_t out_n = (size_t)n_groups * k;
+    if (n == 0) {  // no candidates: rows of padding and the status, written here -- no forest, no device
+        std::fill(idx, idx + out_n, 0xFFFFFFFFu);
+        if (score) std::fill(score, score + out_n, INFINITY);
+        if (group_status)
+            for (uint64_t g = 0; g < n_groups; g++)
+                group_status[g] = std::min<uint64_t>(sample_size, group_offsets[g + 1] - group_offsets[g]) < 2 ? BLISSGPU_GROUP_TOO_FEW_SEEDS
+                                                                                                            : BLISSGPU_GROUP_OK;
+        return BLISSGPU_OK;
+    }
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    rc = c->st_b.ensure(std::max<size_t>(1, n * d));
+    if (!rc) rc = c->st_idx.ensure(out_n + (skip ? n_seeds : 0));
+    if (!rc && score) rc = c->st_dist.ensure(out_n);
+    if (rc) return rc;
+    uint32_t *d_idx = c->st_idx.p, *d_skip = (skip && n_seeds) ? c->st_idx.p + out_n : nullptr;
+    hipError_t e = hipSuccess;
+    if (n) e = hipMemcpyAsync(c->st_b.p, cand, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && d_skip) e = hipMemcpyAsync(d_skip, skip, n_seeds * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(group_forest_knn)", hipGetErrorString(e));
+    if (!rc) {
+        const GroupForestOpts o{d, n_trees, sample_size, max_tree_depth, extension_level, seed};
+        rc = group_forest_run(c, who, seeds, group_offsets, n_groups, c->st_b.p, n, o, d_skip, k, d_idx, score ? c->st_dist.p : nullptr,
+                              nullptr, group_status);
+    }
+    if (!rc) {
+        e = hipMemcpyAsync(idx, d_idx, out_n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && score) e = hipMemcpyAsync(score, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(group_forest_knn)", hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+int blissgpu_debug_group_forest_stats(blissgpu_ctx* c, double* build_ms, double* wait_ms, uint64_t* n_batches) {
+    if (!c) return fail(BLISSGPU_ERR_INVALID, "blissgpu_debug_group_forest_stats", "ctx is NULL");
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    if (build_ms) *build_ms = c->gf_build_ms;
+    if (wait_ms) *wait_ms = c->gf_wait_ms;
+    if (n_batches) *n_batches = c->gf_batches;
+    return BLISSGPU_OK;
 }
 
 int blissgpu_malloc(void** p, uint64_t bytes) {

@@ -258,6 +258,13 @@ struct blissgpu_ctx {
     // distances / playlist ordering scratch
     int64_t forest_split = 0;                      // BLISSGPU_OPT_FOREST_SPLIT
     bool forest_global = false;                    // BLISSGPU_OPT_FOREST_WALK = 1
+    // one forest per seed group (blissgpu_group_forest_knn): the two batch images and their page-locked staging
+    int64_t forest_group_nodes = 0;                // BLISSGPU_OPT_FOREST_GROUP_NODES (0: derived from ws_limit)
+    bg::DevBuf<uint32_t> gf_img[2];
+    bg::PinnedBuf<uint32_t> gf_host[2];
+    hipEvent_t gf_ev[2] = {nullptr, nullptr};      // batch b & 1 has left its staging buffer
+    double gf_build_ms = 0.0, gf_wait_ms = 0.0;    // the last call: host time building and packing forests / waiting for the device
+    uint64_t gf_batches = 0;
     int n_cus = 0;
     bg::DevBuf<uint32_t> pl_sync, pl_keys;
     bg::DevBuf<uint32_t> pl_next;                  // dedup: next[] of every playlist position

@@ -84,7 +84,8 @@ class Context:
                "debug_chroma": _ffi.OPT_DEBUG_CHROMA, "tail_split": _ffi.OPT_TAIL_SPLIT,
                "stft_shape": _ffi.OPT_STFT_SHAPE, "flux_order": _ffi.OPT_FLUX_ORDER,
                "stage_lanes": _ffi.OPT_STAGE_LANES, "stage_slab_kib": _ffi.OPT_STAGE_SLAB_KIB, "stage_slabs": _ffi.OPT_STAGE_SLABS,
-               "stage_numa": _ffi.OPT_STAGE_NUMA, "forest_split": _ffi.OPT_FOREST_SPLIT, "forest_walk": _ffi.OPT_FOREST_WALK}
+               "stage_numa": _ffi.OPT_STAGE_NUMA, "forest_split": _ffi.OPT_FOREST_SPLIT, "forest_walk": _ffi.OPT_FOREST_WALK,
+               "forest_group_nodes": _ffi.OPT_FOREST_GROUP_NODES}
 
     def set_option(self, name: str, value: int):
         """Scheduling knobs for the measurement tools and the tests (blissgpu_ctx_set_option)."""
@@ -568,6 +569,49 @@ class Context:
         self._post()
         order = order.to(torch.int64)
         return (order, score) if return_scores else order
+
+    def group_forest_knn(self, S, offsets, X, k: int, options, skip=None, seeds_host=None):
+        """The k lowest isolation-forest scores of the rows of X for every seed GROUP (blissgpu_group_forest_knn_device): group
+        g's forest is playlist.Forest(S[offsets[g]:offsets[g + 1]], options), every group with the same options and seed.
+        -> (idx int32 [G, k], score float32 [G, k], status int32 [G]) on the device: row g = the first k of the stable ascending
+        order of that forest's scores over X without the group's skipped rows, ending in -1 / inf where fewer are eligible;
+        status 1 (BLISSGPU_GROUP_TOO_FEW_SEEDS) and a row of padding for a group with min(sample_size, seeds) < 2.
+        skip: int32 tensor with one candidate index per SEED ROW, -1 = none, or None.  The forests are built on the host:
+        `seeds_host` (a float32 array equal to S) saves the device-to-host copy of S.  Synchronises before it returns."""
+        import numpy as np
+
+        torch = self.torch
+        assert S.is_cuda and X.is_cuda and S.dtype == torch.float32 and X.dtype == torch.float32
+        assert S.dim() == 2 and X.dim() == 2 and S.shape[1] == X.shape[1]
+        S, X = S.contiguous(), X.contiguous()
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1)).astype(np.uint64)
+        assert off.shape[0] >= 1 and int(off[-1]) == S.shape[0]
+        G, n, k = off.shape[0] - 1, X.shape[0], int(k)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        if skip is not None:
+            assert skip.is_cuda and skip.dtype == torch.int32 and skip.shape[0] == S.shape[0]
+            skip = skip.contiguous()
+        hs = None
+        if seeds_host is not None:
+            hs = np.ascontiguousarray(seeds_host, dtype=np.float32)
+            assert hs.shape == tuple(S.shape)
+        idx = torch.empty((G, max(k, 0)), dtype=torch.int32, device=X.device)
+        score = torch.empty((G, max(k, 0)), dtype=torch.float32, device=X.device)
+        status = torch.empty((G,), dtype=torch.int32, device=X.device)
+        depth = options.max_tree_depth
+        self._pre()
+        _ffi.check(self._L.blissgpu_group_forest_knn_device(self._h, ptr(S), None if hs is None else hs.ctypes.data, off.ctypes.data,
+                                                            G, ptr(X), n, X.shape[1], options.n_trees, options.sample_size,
+                                                            depth or 0, options.extension_level, options.seed, ptr(skip), k,
+                                                            ptr(idx), ptr(score), ptr(status)))
+        self._post()
+        return idx, score, status
+
+    def group_forest_stats(self):
+        """(host ms building forests, host ms waiting for the device, batches) of the last group_forest_knn on this context."""
+        a, b, nb = C.c_double(), C.c_double(), C.c_uint64()
+        _ffi.check(self._L.blissgpu_debug_group_forest_stats(self._h, C.byref(a), C.byref(b), C.byref(nb)))
+        return a.value, b.value, int(nb.value)
 
     # ---- profiling ----
     def profile_enable(self, on: bool = True):

@@ -411,7 +411,7 @@ def group_playlists(db: Conn, k: int, by: str = "album", metric_builder=playlist
     but stays a candidate; groups come in order of first appearance by id, their members in id order.  `groups` =
     {name: [paths]} gives the seed sets instead (a saved playlist): order as given, a repeated path is a seed twice, an
     unknown path is the ProviderError playlist_from_custom raises."""
-    playlist._no_forest(metric_builder, "group_playlists would build one forest per group; use playlist_from_custom per group")
+    playlist._no_forest(metric_builder, "group_playlists takes the distance metrics; forest_playlists builds one forest per group")
     if groups is None and by not in _GROUP_COLUMNS:
         raise ValueError(f"by must be one of {_GROUP_COLUMNS}")
     songs, X = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
@@ -438,6 +438,59 @@ def group_playlists(db: Conn, k: int, by: str = "album", metric_builder=playlist
     rows = np.asarray([i for key in keys for i in members[key]], np.int64)
     idx, dist = playlist.nearest_to_groups((X[rows].reshape(rows.shape[0], X.shape[1]), offsets), X, k, metric, m, skip=rows)
     return {key: [(songs[int(j)].path, float(v)) for j, v in zip(idx[g], dist[g]) if j >= 0] for g, key in enumerate(keys)}
+
+
+def forest_playlists(db: Conn, k: int, options, by: str = "album", groups=None, few_seeds: str = "raise"):
+    """group_playlists with the extended isolation forest (playlist.ForestOptions, src/playlist.rs:230-251), the metric the
+    reference means for playlists grown from several seed songs: {key: [(path, score), ...]} where entry `key` is
+    `playlist_from_custom(db, paths, options, closest_to_songs, deduplicate=False)[len(paths):][:k]` with the forest scores.
+    The library is read once and ONE call (playlist.forest_nearest_to_groups) answers every group: a forest per group, built
+    on the host while the device scores the previous ones, the seeds of a group skipped.  Grouping (`by`, `groups`), ordering
+    and unknown paths as in group_playlists.
+
+    `few_seeds`: a group with min(sample_size, members) < 2 has no forest, and singles are common in a real library.
+    "raise" (the default) is a ValueError, decided before the device is touched; "empty" gives such a group an empty list;
+    "euclidean" answers those groups by one playlist.nearest_to_groups call under euclidean_distance -- the scores of THOSE
+    rows are euclidean distance sums, not forest scores."""
+    if groups is None and by not in _GROUP_COLUMNS:
+        raise ValueError(f"by must be one of {_GROUP_COLUMNS}")
+    if few_seeds not in ("raise", "empty", "euclidean"):
+        raise ValueError('few_seeds must be one of "raise", "empty", "euclidean"')
+    if not isinstance(options, playlist.ForestOptions):
+        raise TypeError("options must be a playlist.ForestOptions")
+    songs, X = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
+    members = {}
+    if groups is None:
+        for i, s in enumerate(songs):
+            key = getattr(s, by)
+            if key is not None:
+                members.setdefault(key, []).append(i)
+    else:
+        row_of = {s.path: i for i, s in enumerate(songs)}
+        for name, paths in groups.items():
+            for p in paths:
+                if p not in row_of:
+                    raise ProviderError(f"song '{p}' has not been analyzed")
+            members[name] = [row_of[p] for p in paths]
+    if not members:
+        return {}
+    keys = list(members)
+    counts = [len(members[key]) for key in keys]
+    few = playlist._forest_few_seeds(few_seeds, counts, options, ("raise", "empty", "euclidean"))
+    offsets = np.zeros(len(keys) + 1, np.int64)
+    offsets[1:] = np.cumsum(counts)
+    rows = np.asarray([i for key in keys for i in members[key]], np.int64)
+    S = X[rows].reshape(rows.shape[0], X.shape[1])
+    idx, score = playlist.forest_nearest_to_groups((S, offsets), X, k, options, skip=rows, few_seeds="empty")
+    if few_seeds == "euclidean" and few.any():
+        sel = np.nonzero(few)[0]
+        sub_rows = [rows[offsets[g]:offsets[g + 1]] for g in sel]
+        sub_off = np.concatenate([[0], np.cumsum([r.shape[0] for r in sub_rows])]).astype(np.int64)
+        flat = np.concatenate(sub_rows + [np.zeros(0, np.int64)])
+        sub_idx, sub_dist = playlist.nearest_to_groups((X[flat].reshape(flat.shape[0], X.shape[1]), sub_off), X, k, "euclidean",
+                                                       None, skip=flat)
+        idx[sel], score[sel] = sub_idx, sub_dist
+    return {key: [(songs[int(j)].path, float(v)) for j, v in zip(idx[g], score[g]) if j >= 0] for g, key in enumerate(keys)}
 
 
 def chain_playlists(db: Conn, k: int, by: str = "song", metric_builder=playlist.euclidean_distance, groups=None,

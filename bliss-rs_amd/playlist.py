@@ -527,14 +527,14 @@ def nearest_to_groups(seed_groups, candidates, k, metric="euclidean", m=None, sk
     scores come in candidate order; rows with fewer than k eligible candidates end in -1 / inf.
     `seed_groups`: a sequence of [s_g, d] arrays, or (S [total, d], offsets [G + 1]).  `skip`: None, one array of
     candidate indices per group (left out of that group's list), or one flat array with an entry per seed row (-1: none).
-    A NaN score raises ValueError (the reference's n32() panic).  A ForestOptions is refused: a forest is built per seed
-    set, use closest_to_songs per group.
+    A NaN score raises ValueError (the reference's n32() panic).  A ForestOptions is refused here: a forest is built per seed
+    set, which is forest_nearest_to_groups.
     One DIAGONAL Mahalanobis metric per group, still one call (blissgpu_group_knn_weighted): metric="diagonal" with m a [G, d]
     array, row g the diagonal of group g's M; metric="variance" for variance_based_weight_matrix (src/playlist.rs:173-221) of
     each group's own seeds, computed on the device, a group of fewer than two seeds taking the identity (euclidean); or a
     VarianceWeights, which is "variance" under its few_seeds policy (ProviderError for such a group by default, decided from
     the group sizes before the device is touched)."""
-    _no_forest(metric, "nearest_to_groups would build one forest per seed group; use closest_to_songs per group")
+    _no_forest(metric, "nearest_to_groups takes the distance metrics; forest_nearest_to_groups builds one forest per seed group")
     S, off = _seed_groups(seed_groups)
     X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
     if X.ndim != 2 or (S is not None and S.shape[1] != X.shape[1]):
@@ -625,7 +625,7 @@ def group_playlists(groups, candidate_songs, k, metric_builder=euclidean_distanc
     (src/playlist.rs:256-270) -- a playlist "in the vibe of these songs" per album, artist or saved playlist, all of them
     in one device call.  `exclude_members`: the first candidate that == each member (Song: PartialEq, as
     nearest_songs(exclude_self=True)) is left out of that group's list."""
-    _no_forest(metric_builder, "group_playlists would build one forest per group; use closest_to_songs per group")
+    _no_forest(metric_builder, "group_playlists takes the distance metrics; forest_group_playlists builds one forest per group")
     groups, candidate_songs = [list(g) for g in groups], list(candidate_songs)
     if not groups:
         return []
@@ -638,6 +638,92 @@ def group_playlists(groups, candidate_songs, k, metric_builder=euclidean_distanc
     seeds = [_matrix(g) if g else np.zeros((0, X.shape[1]), np.float32) for g in groups]
     skip = _member_skip(groups, candidate_songs) if exclude_members else None
     idx, _ = nearest_to_groups(seeds, X, k, metric, m, skip)
+    return [[candidate_songs[j] for j in row if j >= 0] for row in idx]
+
+
+_FEW_SEEDS = ("raise", "empty")
+
+
+def _forest_few_seeds(few_seeds, counts, options, allowed=_FEW_SEEDS):
+    """The few_seeds policy of the forest-per-group entry points, decided from the group sizes alone: -> bool[G], True where
+    min(sample_size, seeds) < 2"""
+    if few_seeds not in allowed:
+        raise ValueError("few_seeds must be one of " + ", ".join(repr(a) for a in allowed))
+    if not isinstance(options, ForestOptions):
+        raise TypeError("options must be a ForestOptions")
+    few = np.minimum(np.asarray(counts, np.int64), options.sample_size) < 2
+    if few_seeds == "raise" and few.any():
+        g = int(np.nonzero(few)[0][0])
+        raise ValueError(_FOREST_SINGLE.format(what=f"group {g} has {int(np.asarray(counts)[g])} seed(s), sample_size "
+                                                    f"{options.sample_size}; few_seeds chooses what such a group gets"))
+    return few
+
+
+def forest_nearest_to_groups(seed_groups, candidates, k, options, skip=None, few_seeds="raise"):
+    """nearest_to_groups with the extended isolation forest as the metric (ForestOptions, src/playlist.rs:230-251), for every
+    seed group in ONE call (blissgpu_group_forest_knn): group g's forest is Forest(seed_groups[g], options) -- every group
+    with the same options and the same options.seed -- and row g holds the first k of the stable ascending order of its
+    scores over the candidates without skip[g], bit for bit Forest(...).scores().  No groups x candidates array is stored;
+    the forests are built on the host, batch by batch, while the device scores the previous batch.
+    -> (idx int64[G, k], score float32[G, k]); rows with fewer than k eligible candidates end in -1 / inf.  `seed_groups` and
+    `skip` as for nearest_to_groups.  `few_seeds`: a group with min(sample_size, seeds) < 2 has no forest ("does not work for
+    a single song") -- "raise" (the default) is a ValueError, decided from the group sizes before the device is touched;
+    "empty" gives such a group a row of -1 / inf."""
+    S, off = _seed_groups(seed_groups)
+    _forest_few_seeds(few_seeds, np.diff(off.astype(np.int64)), options)
+    X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
+    if X.ndim != 2 or (S is not None and S.shape[1] != X.shape[1]):
+        raise ValueError("seed groups and candidates must be [s_g, d] and [n, d]")
+    k = int(k)
+    if not 1 <= k <= 1024:
+        raise ValueError("k must be 1 .. 1024")
+    n, d = X.shape
+    if not 1 <= d <= 32:
+        raise ValueError("d must be 1 .. 32")
+    depth = options.max_tree_depth
+    if depth is not None and not 1 <= depth <= 128:
+        raise ValueError("max_tree_depth must be None or 1 .. 128")
+    for name in ("n_trees", "sample_size", "extension_level"):
+        if not 0 <= getattr(options, name) <= 0xFFFFFFFF:
+            raise ValueError(f"{name} out of range")
+    G = off.shape[0] - 1
+    skip = _group_skip(skip, off, n)
+    idx, score, status = np.empty((G, k), np.uint32), np.empty((G, k), np.float32), np.zeros(G, np.int32)
+    try:
+        _ffi.check(_ffi.lib().blissgpu_group_forest_knn(None if S is None else S.ctypes.data, off.ctypes.data, G, X.ctypes.data, n, d,
+                                                        options.n_trees, options.sample_size, depth or 0, options.extension_level,
+                                                        options.seed, None if skip is None else skip.ctypes.data, k,
+                                                        idx.ctypes.data, score.ctypes.data, status.ctypes.data))
+    except _ffi.BlissGpuError as e:
+        if e.code == _ffi.ERR_INVALID:
+            raise ValueError(str(e)) from e
+        raise
+    out = idx.astype(np.int64)
+    out[idx == 0xFFFFFFFF] = -1
+    return out, score
+
+
+def forest_group_playlists(groups, candidate_songs, k, options, exclude_members=True, few_seeds="raise"):
+    """group_playlists with a ForestOptions: for every group of songs, closest_to_songs(group, candidate_songs without the
+    group's songs, options)[..k] (src/playlist.rs:230-251, 256-270), every group in one device call
+    (forest_nearest_to_groups).  `few_seeds` as there, and additionally "euclidean": the groups without a forest are answered
+    by ONE nearest_to_groups call under euclidean_distance (their lists are ordered by euclidean sums, not forest scores)."""
+    groups, candidate_songs = [list(g) for g in groups], list(candidate_songs)
+    few = _forest_few_seeds(few_seeds, [len(g) for g in groups], options, _FEW_SEEDS + ("euclidean",))
+    if not groups:
+        return []
+    if not candidate_songs:
+        return [[] for _ in groups]
+    X = _matrix(candidate_songs)
+    seeds = [_matrix(g) if g else np.zeros((0, X.shape[1]), np.float32) for g in groups]
+    skip = _member_skip(groups, candidate_songs) if exclude_members else None
+    idx, _ = forest_nearest_to_groups(seeds, X, k, options, skip, "empty")
+    if few_seeds == "euclidean" and few.any():
+        off = np.concatenate([[0], np.cumsum([len(g) for g in groups])])
+        rows = np.nonzero(few)[0]
+        sub_skip = None if skip is None else np.concatenate([skip[off[g]:off[g + 1]] for g in rows] + [np.zeros(0, np.int64)])
+        sub, _ = nearest_to_groups([seeds[g] for g in rows], X, k, "euclidean", None, sub_skip)
+        idx[rows] = sub
     return [[candidate_songs[j] for j in row if j >= 0] for row in idx]
 
 

@@ -129,6 +129,10 @@ int blissgpu_ctx_synchronize(blissgpu_ctx *ctx);
                                            fill the device.  path_sum is an integer sum, so every setting gives the same result */
 #define BLISSGPU_OPT_FOREST_WALK 14     /* forest scoring: 0 (default) = trees staged in LDS chunk by chunk, 1 = every tree walked
                                            from global memory (measurement form; same result) */
+#define BLISSGPU_OPT_FOREST_GROUP_NODES 15 /* blissgpu_group_forest_knn: the node budget of one batch of groups (their forests travel
+                                           to the device together); 0 (default) = derived from the workspace limit: what a 64 MiB
+                                           image holds, or an eighth of the limit if that is less.  Every setting gives the same
+                                           result */
 int blissgpu_ctx_set_option(blissgpu_ctx *ctx, int option, int64_t value);
 /* Bytes of pageable host PCM this context has staged through its pinned ring since it was created (0: every source so far
  * was page-locked, small, or the ring is switched off). */
@@ -562,6 +566,60 @@ int blissgpu_forest_score_device(blissgpu_ctx *ctx, void *forest, const float *d
                                  uint64_t *d_path_sum);
 int blissgpu_forest_closest_to_songs_device(blissgpu_ctx *ctx, void *forest, const float *d_cand, uint64_t n,
                                             uint32_t *d_order, float *d_score);
+
+/* ---- one forest per seed GROUP: an isolation-forest playlist for every album in one call ----
+ * blissgpu_group_knn with the forest as the metric: seeds, group_offsets (a HOST pointer in every form) and skip are
+ * blissgpu_group_knn's.
+ * Forest of group g: exactly blissgpu_forest_build(the seed rows of group g, the options, seed).  Every group uses the same
+ *   options and the same 64-bit seed; only the seed rows differ.  What is per forest stays per group: psi_g = min(sample_size,
+ *   count_g), the depth limit (ceil(log2 psi_g) when max_tree_depth == 0) and c(psi_g).
+ * Rows: row g of idx / score ([n_groups][k], score may be NULL) holds the first k entries of the stable ascending order of
+ *   blissgpu_forest_score over the group's eligible candidates: equal scores in candidate order, rows with fewer than k eligible
+ *   candidates end in idx 0xFFFFFFFF / score +inf.  A score is bit for bit what blissgpu_forest_score writes for that forest and
+ *   candidate (the same u64 path sum, the same f64 expression).
+ * skip: NULL, or one candidate index per SEED ROW: that candidate is left out of the seed's group; 0xFFFFFFFF skips nothing, any
+ *   other value >= n is BLISSGPU_ERR_INVALID.
+ * psi_g < 2 ("the forest does not work for a single song"): the group gets BLISSGPU_GROUP_TOO_FEW_SEEDS in group_status
+ *   ([n_groups], may be NULL; every other group BLISSGPU_GROUP_OK) and a row of padding.  That is not an error of the call;
+ *   sample_size < 2 makes every group such a group.
+ * Scores are always finite: there is no BLISSGPU_ERR_NAN.  1 <= k <= BLISSGPU_KNN_MAX_K, 1 <= d <= BLISSGPU_FOREST_MAX_D,
+ *   extension_level <= d - 1, the BLISSGPU_FOREST_* limits hold per group, n < 2^32 - 1, fewer than 2^32 seeds and 2^32 - 1
+ *   groups; n_groups == 0 or n == 0 is BLISSGPU_OK (n == 0: every row is padding, no forest is built, and the host form does
+ *   not touch the device).  Non-finite seed rows are
+ *   BLISSGPU_ERR_INVALID.  All arguments, skip and finiteness included, are checked before the device is touched and before any
+ *   forest is built.
+ * Memory and launches: no n_groups x n and no group x n array is ever stored -- the candidates' path sums live in registers and
+ *   the workspace holds partial lists of k keys.  The forests need not fit on the device at once: consecutive groups form a
+ *   batch while their planned nodes, n_trees x (2 psi_g - 1) per group (1 for a group without a forest), stay within the node
+ *   budget (BLISSGPU_OPT_FOREST_GROUP_NODES); a single group beyond the budget is a batch of its own.  (The plan counts a tree
+ *   without empty children; the rare split that leaves a child empty adds nodes, and the image buffers are sized from the built
+ *   forests.)  Per batch: the forests are built on up to 16 host threads dealt out over groups, packed into ONE image, uploaded
+ *   once, and scored by two launches (scan + merge) whatever the group sizes; batch b + 1 is built while the device scores
+ *   batch b.  The result does not depend on the batch split, the thread count or the device. */
+int blissgpu_group_forest_knn(const float *seeds, const uint64_t *group_offsets, uint64_t n_groups, const float *cand, uint64_t n,
+                              uint32_t d, uint32_t n_trees, uint32_t sample_size, uint32_t max_tree_depth,
+                              uint32_t extension_level, uint64_t seed, const uint32_t *skip, uint32_t k, uint32_t *idx,
+                              float *score, int32_t *group_status);
+/* Device-resident form: d_cand, d_skip, d_idx, d_score, d_group_status are device pointers.  The forests are built on the host,
+ * so the seed rows are needed THERE: h_seeds is a host copy of them (then d_seeds is not looked at and may be NULL); with
+ * h_seeds == NULL the call makes the one device-to-host copy of d_seeds itself, and their finiteness is checked after that copy.
+ * A skip entry >= n is found by the kernel, so it is reported after the kernels have run, and only the rows the kernel reads
+ * are looked at: those of the groups that have a forest, and none when n == 0.  Synchronises the context's stream before it returns (the host
+ * builds forests while the device works). */
+int blissgpu_group_forest_knn_device(blissgpu_ctx *ctx, const float *d_seeds, const float *h_seeds,
+                                     const uint64_t *group_offsets, uint64_t n_groups, const float *d_cand, uint64_t n,
+                                     uint32_t d, uint32_t n_trees, uint32_t sample_size, uint32_t max_tree_depth,
+                                     uint32_t extension_level, uint64_t seed, const uint32_t *d_skip, uint32_t k,
+                                     uint32_t *d_idx, float *d_score, int32_t *d_group_status);
+/* The batches of the two entry points above for a node budget (0: that of the default 64 MiB image): device-free.  Batch i is
+ * the groups batch_first[i] .. batch_first[i + 1] (n_batches + 1 entries: consecutive, every group once).  *n_batches is always
+ * written; nothing is written past max_batches entries. */
+int blissgpu_group_forest_plan(const uint64_t *group_offsets, uint64_t n_groups, uint32_t d, uint32_t n_trees,
+                               uint32_t sample_size, uint32_t max_tree_depth, uint32_t extension_level, uint64_t node_budget,
+                               uint64_t *batch_first, uint64_t max_batches, uint64_t *n_batches);
+/* The last blissgpu_group_forest_knn call on this context (measurement): host milliseconds spent building and packing forests,
+ * host milliseconds spent waiting for the device, and the number of batches.  Any pointer may be NULL. */
+int blissgpu_debug_group_forest_stats(blissgpu_ctx *ctx, double *build_ms, double *wait_ms, uint64_t *n_batches);
 
 /* FeaturesVersion::feature_weights (src/lib.rs:168-173, 209-234): d x d row-major diagonal matrix. */
 int blissgpu_feature_weights(uint32_t features_version, float *M);
