@@ -67,6 +67,8 @@ pub mod sys {
     pub const BLISSGPU_ERR_TIMEOUT: c_int = 7;
     pub const BLISSGPU_SONG_OK: i32 = 0;
     pub const BLISSGPU_SONG_TOO_SHORT: i32 = 1;
+    pub const BLISSGPU_SONG_DECODE_ERROR: i32 = 2;
+    pub const BLISSGPU_FLAC_INFO_WORDS: usize = 12;
     pub const BLISSGPU_METRIC_EUCLIDEAN: c_int = 0;
     pub const BLISSGPU_METRIC_COSINE: c_int = 1;
     pub const BLISSGPU_METRIC_MAHALANOBIS: c_int = 2;
@@ -224,6 +226,14 @@ pub mod sys {
         pub fn blissgpu_host_free(h_ptr: *mut c_void) -> c_int;
 
         pub fn blissgpu_strerror(code: c_int) -> *const c_char;
+        // FLAC decoded on the device: compressed files in, PCM / feature rows out
+        pub fn blissgpu_flac_info(file: *const c_void, nbytes: u64, info: *mut u64) -> c_int;
+        pub fn blissgpu_flac_index(file: *const c_void, nbytes: u64, verified: c_int, info: *mut u64, frames: *mut u64, max_frames: u64, n_frames: *mut u64) -> c_int;
+        pub fn blissgpu_flac_decode_device(ctx: *mut blissgpu_ctx, d_bytes: *const c_void, nbytes: u64, frames: *const u64, n_frames: u64, info: *const u64, d_pcm: *mut c_void, d_frame_status: *mut i32, d_frame_end: *mut u64) -> c_int;
+        pub fn blissgpu_flac_decode(file: *const c_void, nbytes: u64, pcm: *mut c_void, max_bytes: u64, info: *mut u64, status: *mut i32) -> c_int;
+        pub fn blissgpu_flac_decode_batch(files: *mut *const c_void, nbytes: *const u64, n_songs: u32, pcm: *mut *mut c_void, max_bytes: *const u64, info: *mut u64, status: *mut i32) -> c_int;
+        pub fn blissgpu_analyze_batch_flac(files: *mut *const c_void, nbytes: *const u64, n_songs: u32, features_version: u32, out: *mut f32, status: *mut i32) -> c_int;
+        pub fn blissgpu_ctx_flac_slow_songs(ctx: *mut blissgpu_ctx) -> u64;
         pub fn blissgpu_last_error() -> *const c_char;
         pub fn blissgpu_version() -> *const c_char;
     }

@@ -14,7 +14,8 @@ LIB_PATH = os.environ.get("BLISSGPU_LIB") or os.path.join(_HERE, "libblissgpu.so
 OK, ERR_NO_DEVICE, ERR_INVALID, ERR_HIP, ERR_OOM, ERR_NAN, ERR_RCCL, ERR_TIMEOUT = 0, 1, 2, 3, 4, 5, 6, 7
 SAMPLE_F32, SAMPLE_S16, SAMPLE_S32 = 0, 1, 2
 SAMPLE_RATE = 22050
-SONG_OK, SONG_TOO_SHORT = 0, 1
+SONG_OK, SONG_TOO_SHORT, SONG_DECODE_ERROR = 0, 1, 2
+FLAC_INFO_WORDS = 12
 METRIC_EUCLIDEAN, METRIC_COSINE, METRIC_MAHALANOBIS = 0, 1, 2
 CHAINS_AUTO, CHAINS_STEPS, CHAINS_LISTS = 0, 1, 2
 OPT_SERIAL, OPT_TAIL_MODE, OPT_PIPELINE_CHUNKS, OPT_CAND_BUDGET, OPT_ROLLOFF_EXACT_ALL, OPT_DEBUG_CHROMA, OPT_TAIL_SPLIT = 0, 1, 2, 3, 4, 5, 6
@@ -47,6 +48,13 @@ SIGNATURES = {
     "blissgpu_resampled_len": (C.c_uint64, [C.c_uint64, C.c_uint32]),
     "blissgpu_resample_filter": (C.c_int, [C.c_uint32, _vp, C.c_uint64, _u32p, _u32p]),
     "blissgpu_pcm_decode_device": (C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, _vp]),
+    "blissgpu_flac_info": (C.c_int, [_vp, C.c_uint64, _u64p]),
+    "blissgpu_flac_index": (C.c_int, [_vp, C.c_uint64, C.c_int, _u64p, _u64p, C.c_uint64, _u64p]),
+    "blissgpu_flac_decode_device": (C.c_int, [_vp, _vp, C.c_uint64, _u64p, C.c_uint64, _u64p, _vp, _vp, _vp]),
+    "blissgpu_flac_decode": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, _u64p, _i32p]),
+    "blissgpu_flac_decode_batch": (C.c_int, [C.POINTER(_vp), _u64p, C.c_uint32, C.POINTER(_vp), _u64p, _u64p, _i32p]),
+    "blissgpu_analyze_batch_flac": (C.c_int, [C.POINTER(_vp), _u64p, C.c_uint32, C.c_uint32, _vp, _i32p]),
+    "blissgpu_ctx_flac_slow_songs": (C.c_uint64, [_vp]),
     "blissgpu_ctx_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
     "blissgpu_ctx_destroy": (C.c_int, [_vp]),
     "blissgpu_ctx_set_stream": (C.c_int, [_vp, _vp]),

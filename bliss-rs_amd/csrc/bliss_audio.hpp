@@ -9,11 +9,14 @@
 //   bliss::Analysis, AnalysisIndex, FeaturesVersion  src/song/mod.rs:102-371, src/lib.rs:151-187
 //   bliss::BlissError {Decoding,Analysis,Provider}   src/lib.rs:236-252
 //   bliss::Decoder (decode / song_from_path / analyze_paths)   src/song/decoder.rs:115-333
+//   bliss::FlacDecoder: .flac files handed to the device COMPRESSED (blissgpu_analyze_batch_flac); no CPU entropy decoding
 //   bliss::euclidean_distance / cosine_distance / mahalanobis_distance   src/playlist.rs:65-142
 #pragma once
 #include <algorithm>
+#include <cctype>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <functional>
 #include <map>
 #include <optional>
@@ -387,6 +390,133 @@ class Decoder {
             else out.emplace_back(pending[i].path, pending[i].to_song(std::get<Analysis>(std::move(res[i])), opt.features_version));
         }
         return out;
+    }
+};
+
+// ---- FLAC: the file goes to the device compressed; the host reads STREAMINFO and the VORBIS_COMMENT block only ----
+struct FlacFile {
+    PreAnalyzedSong pre;          // tags and duration; sample_array stays empty
+    std::vector<uint8_t> bytes;   // the compressed file
+};
+
+class FlacDecoder {
+  public:
+    // file -> tags + the compressed bytes (artist, title, album, album_artist, track_number, disc_number, genre as the
+    // reference's FFmpeg decoder fills them, src/song/decoder/ffmpeg.rs:200-247; the duration from STREAMINFO); throws BlissError
+    static FlacFile decode(const std::string& path) {
+        FlacFile f;
+        f.pre.path = path;
+        FILE* fp = fopen(path.c_str(), "rb");
+        if (!fp) throw DecodingError("while opening format for file '" + path + "'");
+        uint8_t buf[65536];
+        for (size_t k; (k = fread(buf, 1, sizeof(buf), fp)) > 0;) f.bytes.insert(f.bytes.end(), buf, buf + k);
+        fclose(fp);
+        const std::vector<uint8_t>& d = f.bytes;
+        size_t p = 0;
+        if (d.size() >= 10 && d[0] == 'I' && d[1] == 'D' && d[2] == '3')
+            p = 10 + (size_t(d[6] & 0x7F) << 21 | size_t(d[7] & 0x7F) << 14 | size_t(d[8] & 0x7F) << 7 | size_t(d[9] & 0x7F)) + ((d[5] & 0x10) ? 10 : 0);
+        if (p + 4 > d.size() || std::string(d.begin() + p, d.begin() + p + 4) != "fLaC") throw DecodingError("'" + path + "' is not a FLAC stream");
+        p += 4;
+        uint64_t rate = 0, total = 0;
+        for (;;) {
+            if (p + 4 > d.size()) throw DecodingError("'" + path + "' is truncated in the metadata");
+            const uint8_t kind = d[p];
+            const size_t len = size_t(d[p + 1]) << 16 | size_t(d[p + 2]) << 8 | d[p + 3];
+            p += 4;
+            if (len > d.size() - p) throw DecodingError("'" + path + "' is truncated in the metadata");
+            if ((kind & 0x7F) == 0 && len >= 18) {
+                uint64_t v = 0;
+                for (size_t i = 10; i < 18; i++) v = (v << 8) | d[p + i];
+                rate = v >> 44;
+                total = v & ((1ull << 36) - 1);
+            } else if ((kind & 0x7F) == 4) {
+                comments(d.data() + p, len, &f.pre);
+            }
+            p += len;
+            if (kind & 0x80) break;
+        }
+        if (!rate) throw DecodingError("'" + path + "' has no STREAMINFO");
+        f.pre.duration = double(total) / double(rate);
+        return f;
+    }
+
+    // (path, Result) pairs from ONE device batch of compressed files; a bad file yields its DecodingError and never aborts the run
+    static std::vector<std::pair<std::string, BlissResult<Song>>> analyze_paths(const std::vector<std::string>& paths, const AnalysisOptions& opt = {}) {
+        std::vector<std::pair<std::string, BlissResult<Song>>> out;
+        std::vector<FlacFile> pending;
+        for (const auto& p : paths) {
+            try { pending.push_back(decode(p)); }
+            catch (const BlissError& e) { out.emplace_back(p, e); }
+        }
+        const uint32_t d = blissgpu_feature_count(static_cast<uint32_t>(opt.features_version));
+        const size_t n = pending.size();
+        std::vector<const void*> files(n);
+        std::vector<uint64_t> sizes(n);
+        for (size_t i = 0; i < n; i++) { files[i] = pending[i].bytes.data(); sizes[i] = pending[i].bytes.size(); }
+        std::vector<float> rows(n * d);
+        std::vector<int32_t> status(n, 0);
+        if (n) check(blissgpu_analyze_batch_flac(files.data(), sizes.data(), static_cast<uint32_t>(n), static_cast<uint32_t>(opt.features_version), rows.data(), status.data()));
+        for (size_t i = 0; i < n; i++) {
+            if (status[i] == BLISSGPU_SONG_OK)
+                out.emplace_back(pending[i].pre.path, pending[i].pre.to_song(Analysis(std::vector<float>(rows.begin() + i * d, rows.begin() + (i + 1) * d), opt.features_version), opt.features_version));
+            else if (status[i] == BLISSGPU_SONG_TOO_SHORT) out.emplace_back(pending[i].pre.path, AnalysisError("empty or too short song."));
+            else out.emplace_back(pending[i].pre.path, DecodingError("the FLAC stream of '" + pending[i].pre.path + "' cannot be decoded"));
+        }
+        return out;
+    }
+
+  private:
+    static std::optional<int32_t> number(const std::string& t) {  // "2" or "02/05" (ffmpeg.rs:224-241)
+        auto parse = [](const std::string& x) -> std::optional<int32_t> {
+            if (x.empty()) return std::nullopt;
+            size_t i = (x[0] == '-' || x[0] == '+') ? 1 : 0;
+            if (i == x.size() || x.size() - i > 10) return std::nullopt;
+            int64_t v = 0;
+            for (; i < x.size(); i++) {
+                if (x[i] < '0' || x[i] > '9') return std::nullopt;
+                v = v * 10 + (x[i] - '0');
+            }
+            if (x[0] == '-') v = -v;
+            if (v < INT32_MIN || v > INT32_MAX) return std::nullopt;
+            return static_cast<int32_t>(v);
+        };
+        if (auto v = parse(t)) return v;
+        const size_t slash = t.find('/');
+        return slash == std::string::npos ? std::nullopt : parse(t.substr(0, slash));
+    }
+    static void comments(const uint8_t* b, size_t n, PreAnalyzedSong* s) {
+        auto u32 = [&](size_t p) { return size_t(b[p]) | size_t(b[p + 1]) << 8 | size_t(b[p + 2]) << 16 | size_t(b[p + 3]) << 24; };
+        if (n < 8) return;
+        size_t p = 4 + u32(0);
+        if (p + 4 > n) return;
+        const size_t count = u32(p);
+        p += 4;
+        std::map<std::string, std::string> tags;
+        for (size_t i = 0; i < count && p + 4 <= n; i++) {
+            const size_t len = u32(p);
+            p += 4;
+            if (len > n - p) return;
+            const std::string entry(reinterpret_cast<const char*>(b + p), len);
+            p += len;
+            const size_t eq = entry.find('=');
+            if (eq == std::string::npos) continue;
+            std::string key = entry.substr(0, eq);
+            for (char& ch : key) ch = static_cast<char>(std::tolower(static_cast<unsigned char>(ch)));
+            if (key == "tracknumber") key = "track";
+            else if (key == "discnumber") key = "disc";
+            else if (key == "albumartist") key = "album_artist";
+            auto it = tags.find(key);
+            if (it == tags.end()) tags[key] = entry.substr(eq + 1);
+            else it->second += ";" + entry.substr(eq + 1);
+        }
+        auto text = [&](const char* k) -> std::optional<std::string> {
+            auto it = tags.find(k);
+            return it == tags.end() || it->second.empty() ? std::nullopt : std::optional<std::string>(it->second);
+        };
+        s->artist = text("artist"); s->title = text("title"); s->album = text("album"); s->album_artist = text("album_artist");
+        s->genre = text("genre");
+        if (auto t = text("track")) s->track_number = number(*t);
+        if (auto t = text("disc")) s->disc_number = number(*t);
     }
 };
 

@@ -343,6 +343,9 @@ int blissgpu_ctx_destroy(blissgpu_ctx* c) {
         c->dbg_tuning.release(); c->dbg_nbpms.release(); c->dbg_chroma.release(); c->dbg_interval.release();
         c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->pl_next.release(); c->st_idx.release();
         c->st_a.release(); c->st_b.release(); c->st_m.release(); c->st_dist.release(); c->st_out.release();
+        c->fl_bytes.release(); c->fl_tab.release(); c->fl_pcm.release(); c->fl_status.release(); c->fl_end.release();
+        c->fl_bad.release(); c->fl_mono.release(); c->fl_rows.release(); c->fl_htab.release();
+        if (c->fl_ev) (void)hipEventDestroy(c->fl_ev);
         for (int s = 0; s < 2; s++) {
             c->gf_img[s].release();
             c->gf_host[s].release();
@@ -2232,6 +2235,371 @@ int blissgpu_debug_fetch(blissgpu_ctx* c, int what, uint32_t song, void* dst, ui
     if (n_elems) *n_elems = n;
     const uint64_t k = std::min(n, max_elems);
     if (k) HIP_TRY(hipMemcpy(dst, src, k * esz, hipMemcpyDeviceToHost));
+    return BLISSGPU_OK;
+}
+
+}  // extern "C"
+
+// ---- FLAC: compressed files in, PCM / feature rows out (flac_index.hpp on the host, kernels_flac.hip on the device) ----
+#include <thread>
+
+#include "flac_frame.hpp"
+#include "flac_index.hpp"
+
+namespace {
+
+struct FlacPlan {  // one file of a call
+    const uint8_t* file = nullptr;
+    uint64_t nbytes = 0;
+    flac::StreamInfo si;
+    uint64_t total = 0;  // inter-channel samples the frame table holds
+    uint64_t base = 0;   // stream position of the first frame
+    std::vector<flac::FrameRow> rows;
+    bool error = false;  // not FLAC, unsupported, truncated, or frames that verified mode cannot repair
+    bool slow = false;   // the table is verified mode's
+    uint64_t byte_off = 0, pcm_off = 0, pcm_bytes = 0;
+};
+
+void flac_info_words(const flac::StreamInfo& si, uint64_t* info) {
+    info[0] = si.sample_rate; info[1] = si.channels; info[2] = si.bps; info[3] = si.total;
+    info[4] = si.min_block; info[5] = si.max_block; info[6] = si.min_frame; info[7] = si.first_frame;
+    memcpy(&info[8], si.md5, 16);
+    info[10] = 0; info[11] = 0;
+}
+
+void flac_index_plan(FlacPlan& p, bool verified) {
+    p.error = true;
+    int rc = flac::index_frames(p.file, p.nbytes, p.si, verified, &p.rows, &p.total, &p.base);
+    if (rc && !verified) {  // (a table the fast filter cannot close, e.g. after a false candidate: the exact mode decides)
+        verified = true;
+        rc = flac::index_frames(p.file, p.nbytes, p.si, true, &p.rows, &p.total, &p.base);
+    }
+    p.slow = verified;
+    if (rc) return;
+    p.pcm_bytes = p.total * p.si.channels * (p.si.bps > 16 ? 4 : 2);
+    p.error = false;
+}
+
+// (an exception -- no memory for the table of a file with millions of tiny frames -- costs that song, not the process)
+void flac_plan(FlacPlan& p) {
+    p.error = true;
+    try {
+        if (!p.file || flac::stream_info(p.file, p.nbytes, &p.si)) return;
+        if (p.si.bps < 4 || p.si.bps > 24 || p.si.sample_rate > MAX_SAMPLE_RATE) return;
+        flac_index_plan(p, false);
+    } catch (...) {
+        p.rows.clear();
+        p.error = true;
+    }
+}
+
+// what a song keeps resident while its sub-batch is decoded and analysed: compressed bytes, PCM, the mono 22 050 Hz stream
+uint64_t flac_resident_bytes(const FlacPlan& p) { return p.pcm_bytes + p.nbytes + 4 * p.total + 64; }
+
+// songs | frames into the context's table buffer (through its page-locked staging), asynchronous on the context's stream
+int flac_upload_tables(blissgpu_ctx* c, const std::vector<FlacSong>& songs, const std::vector<FlacFrame>& frames,
+                       const FlacSong** d_songs, const FlacFrame** d_frames) {
+    const size_t sb = songs.size() * sizeof(FlacSong), fb = frames.size() * sizeof(FlacFrame);
+    static_assert(sizeof(FlacSong) % 8 == 0 && sizeof(FlacFrame) == 32, "table rows keep their 8-byte alignment");
+    int rc = c->fl_tab.ensure(sb + fb + 8);
+    if (rc) return rc;
+    if (!c->fl_ev) HIP_TRY(hipEventCreateWithFlags(&c->fl_ev, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(c->fl_ev));
+    if ((rc = c->fl_htab.ensure(sb + fb + 8))) return rc;
+    memcpy(c->fl_htab.p, songs.data(), sb);
+    memcpy(c->fl_htab.p + sb, frames.data(), fb);
+    HIP_TRY(hipMemcpyAsync(c->fl_tab.p, c->fl_htab.p, sb + fb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(c->fl_ev, c->stream));
+    *d_songs = (const FlacSong*)c->fl_tab.p;
+    *d_frames = (const FlacFrame*)(c->fl_tab.p + sb);
+    return BLISSGPU_OK;
+}
+
+void flac_rows_of(const FlacPlan& p, uint32_t song, std::vector<FlacFrame>* frames) {
+    for (const flac::FrameRow& r : p.rows)
+        frames->push_back(FlacFrame{r.offset, r.nbytes, r.first_sample, (uint32_t)r.blocksize, song});
+    if (!p.rows.empty()) frames->back().song |= FLAC_LAST_FRAME;
+}
+
+// Upload, decode and check the planned files `sel` (indices into plans); afterwards plans[i].error says which of them have
+// no PCM, the others' PCM sits at c->fl_pcm.p + pcm_off.  Synchronises the context's stream.
+int flac_run(blissgpu_ctx* c, std::vector<FlacPlan>& plans, const std::vector<uint32_t>& sel, const char* who) {
+    std::vector<FlacSong> songs;
+    std::vector<FlacFrame> frames;
+    std::vector<uint32_t> live;  // plans that reach the device
+    uint64_t bytes = 0, pcm = 0;
+    for (uint32_t i : sel) {
+        FlacPlan& p = plans[i];
+        if (p.error) continue;
+        p.byte_off = bytes;
+        p.pcm_off = pcm;
+        bytes += (p.nbytes + flac::FILE_PAD + 15) & ~15ull;
+        pcm += (p.pcm_bytes + 15) & ~15ull;
+        if (frames.size() + p.rows.size() > 0x7FFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "more than 2^31 frames in one sub-batch");
+        flac_rows_of(p, (uint32_t)live.size(), &frames);
+        if (p.slow) c->fl_slow_songs++;  // (the fast filter could not close its table on the host already)
+        songs.push_back(FlacSong{p.byte_off, p.nbytes, p.pcm_off, p.total, p.base, p.si.channels, p.si.bps});
+        live.push_back(i);
+    }
+    if (live.empty()) return BLISSGPU_OK;
+    int rc = c->fl_bytes.ensure(bytes + flac::FILE_PAD);
+    if (!rc) rc = c->fl_pcm.ensure(pcm + 16);
+    if (!rc) rc = c->fl_bad.ensure(live.size());
+    if (rc) return rc;
+    for (uint32_t k = 0; k < live.size(); k++)
+        HIP_TRY(hipMemcpyAsync(c->fl_bytes.p + songs[k].byte_off, plans[live[k]].file, plans[live[k]].nbytes, hipMemcpyHostToDevice, c->stream));
+    std::vector<uint32_t> bad(live.size(), 0);
+    for (int pass = 0; pass < 2 && !frames.empty(); pass++) {
+        const FlacSong* d_songs;
+        const FlacFrame* d_frames;
+        if ((rc = c->fl_status.ensure(frames.size()))) return rc;
+        if ((rc = c->fl_end.ensure(frames.size()))) return rc;
+        if ((rc = flac_upload_tables(c, songs, frames, &d_songs, &d_frames))) return rc;
+        HIP_TRY(hipMemsetAsync(c->fl_bad.p, 0, live.size() * sizeof(uint32_t), c->stream));
+        launch_flac_decode(c->fl_bytes.p, d_songs, d_frames, (uint32_t)frames.size(), c->fl_pcm.p, c->fl_status.p, c->fl_end.p, c->stream);
+        launch_flac_check(d_frames, (uint32_t)frames.size(), c->fl_status.p, c->fl_end.p, c->fl_bad.p, c->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(bad.data(), c->fl_bad.p, live.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        // the songs the device refused go through verified mode and a second, small launch -- each of them alone
+        frames.clear();
+        for (uint32_t k = 0; k < live.size(); k++) {
+            FlacPlan& p = plans[live[k]];
+            if (!bad[k]) continue;
+            if (p.slow || pass == 1) { p.error = true; continue; }
+            c->fl_slow_songs++;
+            const uint64_t room = (p.pcm_bytes + 15) & ~15ull;  // the PCM region was sized by the fast table
+            try { flac_index_plan(p, true); } catch (...) { p.error = true; }
+            if (p.error || p.pcm_bytes > room) { p.error = true; continue; }
+            songs[k].total = p.total;
+            songs[k].base = p.base;
+            flac_rows_of(p, k, &frames);
+        }
+    }
+    return BLISSGPU_OK;
+}
+
+struct FlacDeviceRestore {
+    int prev = -1;
+    FlacDeviceRestore() { if (hipGetDevice(&prev) != hipSuccess) { prev = -1; (void)hipGetLastError(); } }
+    ~FlacDeviceRestore() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+}  // namespace
+
+extern "C" {
+
+int blissgpu_flac_info(const void* file, uint64_t nbytes, uint64_t* info) {
+    if (!file || !info) return fail(BLISSGPU_ERR_INVALID, "blissgpu_flac_info", "NULL argument");
+    flac::StreamInfo si;
+    const int rc = flac::stream_info((const uint8_t*)file, nbytes, &si);
+    if (rc) return fail(BLISSGPU_ERR_INVALID, "blissgpu_flac_info", rc == flac::INDEX_NOT_FLAC ? "not a FLAC stream" : "truncated in the metadata");
+    flac_info_words(si, info);
+    return BLISSGPU_OK;
+}
+
+int blissgpu_flac_index(const void* file, uint64_t nbytes, int verified, uint64_t* info, uint64_t* frames, uint64_t max_frames,
+                        uint64_t* n_frames) {
+    const char* who = "blissgpu_flac_index";
+    if (!file || !n_frames) return fail(BLISSGPU_ERR_INVALID, who, "NULL argument");
+    *n_frames = 0;
+    flac::StreamInfo si;
+    int rc = flac::stream_info((const uint8_t*)file, nbytes, &si);
+    if (rc) return fail(BLISSGPU_ERR_INVALID, who, rc == flac::INDEX_NOT_FLAC ? "not a FLAC stream" : "truncated in the metadata");
+    std::vector<flac::FrameRow> rows;
+    uint64_t total = 0, base = 0;
+    rc = flac::index_frames((const uint8_t*)file, nbytes, si, verified != 0, &rows, &total, &base);
+    *n_frames = rows.size();
+    if (frames) memcpy(frames, rows.data(), sizeof(flac::FrameRow) * (size_t)std::min<uint64_t>(max_frames, rows.size()));
+    if (info) {
+        flac_info_words(si, info);
+        info[3] = total;
+        info[10] = base;
+    }
+    if (rc) return fail(BLISSGPU_ERR_INVALID, who, rc == flac::INDEX_NO_FRAMES ? "no frame behind the metadata" : "frames are missing (truncated)");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_flac_decode_device(blissgpu_ctx* c, const void* d_bytes, uint64_t nbytes, const uint64_t* frames, uint64_t n_frames,
+                                const uint64_t* info, void* d_pcm, int32_t* d_frame_status, uint64_t* d_frame_end) {
+    const char* who = "blissgpu_flac_decode_device";
+    if (!d_bytes || !info || (n_frames && (!frames || !d_pcm || !d_frame_status || !d_frame_end))) return fail(BLISSGPU_ERR_INVALID, who, "NULL argument");
+    if (((uintptr_t)d_bytes & 7) != 0 || ((uintptr_t)d_pcm & 3) != 0) return fail(BLISSGPU_ERR_INVALID, who, "d_bytes must be 8-byte, d_pcm 4-byte aligned");
+    if (info[1] < 1 || info[1] > 8 || info[2] < 1 || info[2] > 32 || n_frames > 0x7FFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "bad info / n_frames");
+    CTX_ENTER(c, who);
+    if (n_frames == 0) return BLISSGPU_OK;
+    std::vector<FlacSong> songs{FlacSong{0, nbytes, 0, info[3], info[10], (uint32_t)info[1], (uint32_t)info[2]}};
+    std::vector<FlacFrame> rows((size_t)n_frames);
+    for (uint64_t i = 0; i < n_frames; i++) {
+        const uint64_t* r = frames + 4 * i;
+        if (r[0] > nbytes || r[1] > nbytes - r[0] || r[3] == 0 || r[3] > 65536) return fail(BLISSGPU_ERR_INVALID, who, "a frame row lies outside the file");
+        rows[i] = FlacFrame{r[0], r[1], r[2], (uint32_t)r[3], i + 1 == n_frames ? FLAC_LAST_FRAME : 0u};
+    }
+    const FlacSong* d_songs;
+    const FlacFrame* d_frames;
+    const int rc = flac_upload_tables(c, songs, rows, &d_songs, &d_frames);
+    if (rc) return rc;
+    launch_flac_decode((const uint8_t*)d_bytes, d_songs, d_frames, (uint32_t)n_frames, (uint8_t*)d_pcm, d_frame_status, d_frame_end, c->stream);
+    HIP_TRY(hipGetLastError());
+    return BLISSGPU_OK;
+}
+
+uint64_t blissgpu_ctx_flac_slow_songs(blissgpu_ctx* c) {
+    if (!c) return 0;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    return c->fl_slow_songs;
+}
+
+int blissgpu_flac_decode(const void* file, uint64_t nbytes, void* pcm, uint64_t max_bytes, uint64_t* info, int32_t* status) {
+    const char* who = "blissgpu_flac_decode";
+    if (!file || !info || !status) return fail(BLISSGPU_ERR_INVALID, who, "NULL argument");
+    std::vector<FlacPlan> plans(1);
+    plans[0].file = (const uint8_t*)file;
+    plans[0].nbytes = nbytes;
+    flac_plan(plans[0]);
+    flac_info_words(plans[0].si, info);
+    info[3] = plans[0].total;
+    info[10] = plans[0].base;
+    *status = BLISSGPU_SONG_DECODE_ERROR;
+    if (plans[0].error) return BLISSGPU_OK;
+    if (!pcm) { *status = BLISSGPU_SONG_OK; return BLISSGPU_OK; }  // sizes only (whether it fits the workspace limit shows with pcm)
+    if (max_bytes < plans[0].pcm_bytes) return fail(BLISSGPU_ERR_INVALID, who, "pcm is smaller than total x channels x sample width");
+    FlacDeviceRestore restore;
+    blissgpu_ctx* c;
+    int rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    if (flac_resident_bytes(plans[0]) > c->ws_limit) return BLISSGPU_OK;  // (*status says DECODE_ERROR)
+    if ((rc = flac_run(c, plans, {0}, who))) return rc;
+    info[3] = plans[0].total;
+    if (plans[0].error) return BLISSGPU_OK;
+    const uint64_t nb = plans[0].total * plans[0].si.channels * (plans[0].si.bps > 16 ? 4 : 2);
+    if (nb) HIP_TRY(hipMemcpy(pcm, c->fl_pcm.p + plans[0].pcm_off, nb, hipMemcpyDeviceToHost));
+    *status = BLISSGPU_SONG_OK;
+    return BLISSGPU_OK;
+}
+
+int blissgpu_flac_decode_batch(const void* const* files, const uint64_t* nbytes, uint32_t n_songs, void* const* pcm,
+                               const uint64_t* max_bytes, uint64_t* info, int32_t* status) {
+    const char* who = "blissgpu_flac_decode_batch";
+    if (n_songs && (!files || !nbytes || !pcm || !max_bytes || !info || !status)) return fail(BLISSGPU_ERR_INVALID, who, "NULL argument");
+    if (n_songs == 0) return BLISSGPU_OK;
+    FlacDeviceRestore restore;
+    blissgpu_ctx* c;
+    int rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    std::vector<FlacPlan> plans(n_songs);
+    std::vector<uint32_t> sel;
+    uint64_t resident = 0;
+    for (uint32_t i = 0; i < n_songs; i++) {
+        plans[i].file = (const uint8_t*)files[i];
+        plans[i].nbytes = nbytes[i];
+        flac_plan(plans[i]);
+        if (!plans[i].error && (plans[i].pcm_bytes > max_bytes[i] || (plans[i].pcm_bytes && !pcm[i]))) plans[i].error = true;
+        if (!plans[i].error && flac_resident_bytes(plans[i]) > c->ws_limit) plans[i].error = true;  // refused alone, as in the bulk form
+        if (!plans[i].error) resident += flac_resident_bytes(plans[i]);
+        sel.push_back(i);
+    }
+    if (resident > c->ws_limit) return fail(BLISSGPU_ERR_INVALID, who, "the files do not fit the workspace limit together");
+    if ((rc = flac_run(c, plans, sel, who))) return rc;
+    for (uint32_t i = 0; i < n_songs; i++) {
+        const FlacPlan& p = plans[i];
+        flac_info_words(p.si, info + (size_t)i * BLISSGPU_FLAC_INFO_WORDS);
+        info[(size_t)i * BLISSGPU_FLAC_INFO_WORDS + 3] = p.total;
+        info[(size_t)i * BLISSGPU_FLAC_INFO_WORDS + 10] = p.base;
+        status[i] = p.error ? BLISSGPU_SONG_DECODE_ERROR : BLISSGPU_SONG_OK;
+        const uint64_t nb = p.error ? 0 : p.total * p.si.channels * (p.si.bps > 16 ? 4 : 2);
+        if (nb) HIP_TRY(hipMemcpy(pcm[i], c->fl_pcm.p + p.pcm_off, nb, hipMemcpyDeviceToHost));
+    }
+    return BLISSGPU_OK;
+}
+
+int blissgpu_analyze_batch_flac(const void* const* files, const uint64_t* nbytes, uint32_t n_songs, uint32_t features_version,
+                                float* out, int32_t* status) {
+    const char* who = "blissgpu_analyze_batch_flac";
+    const uint32_t d = blissgpu_feature_count(features_version);
+    if (!d) return fail(BLISSGPU_ERR_INVALID, who, "features_version must be 1 or 2");
+    if (n_songs && (!files || !nbytes || !out)) return fail(BLISSGPU_ERR_INVALID, who, "NULL argument");
+    if (n_songs == 0) return BLISSGPU_OK;
+    FlacDeviceRestore restore;
+    blissgpu_ctx* c;
+    int rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    // 1. the frame tables, on at most as many threads as the context's staging ring has workers
+    std::vector<FlacPlan> plans(n_songs);
+    for (uint32_t i = 0; i < n_songs; i++) {
+        plans[i].file = (const uint8_t*)files[i];
+        plans[i].nbytes = nbytes[i];
+    }
+    {
+        const uint32_t workers = std::min<uint32_t>(n_songs, (uint32_t)std::max(1, std::min(c->feed.stage_cfg.lanes, MAX_STAGE_LANES)));
+        std::atomic<uint32_t> next{0};
+        auto work = [&]() {
+            for (uint32_t i; (i = next.fetch_add(1)) < n_songs;) flac_plan(plans[i]);
+        };
+        std::vector<std::thread> pool;
+        for (uint32_t w = 1; w < workers; w++) pool.emplace_back(work);
+        work();
+        for (std::thread& t : pool) t.join();
+    }
+    const float nan = nanf("");
+    auto refuse = [&](uint32_t i) {
+        for (uint32_t k = 0; k < d; k++) out[(size_t)i * d + k] = nan;
+        if (status) status[i] = BLISSGPU_SONG_DECODE_ERROR;
+    };
+    // 2. - 6. sub-batch by sub-batch: the decoded PCM of one has to fit the workspace limit
+    uint32_t i0 = 0;
+    while (i0 < n_songs) {
+        std::vector<uint32_t> sel;
+        uint64_t pcm_bytes = 0;
+        uint32_t i1 = i0;
+        for (; i1 < n_songs; i1++) {
+            // a song that does not fit the limit by itself (a few MB of CONSTANT frames can claim hundreds of GB) is refused
+            if (!plans[i1].error && flac_resident_bytes(plans[i1]) > c->ws_limit) plans[i1].error = true;
+            const uint64_t b = plans[i1].error ? 0 : flac_resident_bytes(plans[i1]);
+            if (!sel.empty() && pcm_bytes + b > c->ws_limit) break;
+            pcm_bytes += b;
+            sel.push_back(i1);
+        }
+        if ((rc = flac_run(c, plans, sel, who))) return rc;
+        std::vector<uint32_t> good;
+        std::vector<uint64_t> offs, lens;
+        uint64_t mono = 0;
+        for (uint32_t i : sel) {
+            if (plans[i].error) { refuse(i); continue; }
+            good.push_back(i);
+            offs.push_back(mono);
+            lens.push_back(blissgpu_resampled_len(plans[i].total, plans[i].si.sample_rate));
+            mono += (lens.back() + 3) & ~3ull;
+        }
+        if (!good.empty()) {
+            const size_t n = good.size();
+            if ((rc = c->fl_mono.ensure(mono + 4))) return rc;
+            if ((rc = c->fl_rows.ensure(n * d + n))) return rc;
+            for (size_t k = 0; k < n; k++) {
+                const FlacPlan& p = plans[good[k]];
+                if (!lens[k]) continue;
+                rc = enqueue_decode(c, c->fl_pcm.p + p.pcm_off, p.si.bps > 16 ? BLISSGPU_SAMPLE_S32 : BLISSGPU_SAMPLE_S16, p.si.channels, p.total,
+                                    p.si.sample_rate, c->fl_mono.p + offs[k], lens[k], c->stream, who);
+                if (rc) return rc;
+            }
+            int32_t* d_status = (int32_t*)(c->fl_rows.p + n * d);
+            rc = blissgpu_analyze_batch_device(c, c->fl_mono.p, offs.data(), lens.data(), (uint32_t)n, features_version, c->fl_rows.p, d_status);
+            if (rc) return rc;
+            std::vector<float> rows(n * d);
+            std::vector<int32_t> st(n);
+            HIP_TRY(hipMemcpyAsync(rows.data(), c->fl_rows.p, n * d * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(st.data(), d_status, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            for (size_t k = 0; k < n; k++) {
+                memcpy(out + (size_t)good[k] * d, rows.data() + k * d, d * sizeof(float));
+                if (status) status[good[k]] = st[k];
+            }
+        }
+        i0 = i1;
+    }
     return BLISSGPU_OK;
 }
 

@@ -276,6 +276,16 @@ struct blissgpu_ctx {
     bg::DevBuf<uint32_t> st_idx;                   // staging of the dedup form: n_kept | kept | seq | meta
     std::vector<float> m_cache;                    // host copy of the matrix in st_m (skip the upload when unchanged)
     float* h_scalar = nullptr;                     // page-locked word the single-pair kernel writes its result to
+    // FLAC (kernels_flac.hip): compressed bytes, tables (songs | frames), PCM, per-frame status / stop position, per-song
+    // flags, and the mono 22 050 Hz stream + rows of blissgpu_analyze_batch_flac
+    bg::DevBuf<uint8_t> fl_bytes, fl_tab, fl_pcm;
+    bg::DevBuf<int32_t> fl_status;
+    bg::DevBuf<uint64_t> fl_end;
+    bg::DevBuf<uint32_t> fl_bad;
+    bg::DevBuf<float> fl_mono, fl_rows;
+    bg::PinnedBuf<uint8_t> fl_htab;                // page-locked staging of fl_tab
+    hipEvent_t fl_ev = nullptr;                    // the last upload from fl_htab has left it
+    uint64_t fl_slow_songs = 0;                    // songs whose fast frame table the device refused (verified mode + a second launch)
     // profiling
     bool profiling = false;
     std::vector<bg::EventPair> events[bg::K_COUNT];

@@ -216,6 +216,27 @@ void launch_pcm_convert(const void* in, int sample_format, uint32_t channels, fl
 struct SwrPlan;
 hipError_t launch_resample(const void* in, int sample_format, uint32_t channels, uint64_t frames, const SwrPlan& plan,
                            const float* d_bank, float* out, uint64_t n_out, hipStream_t st);
+// FLAC frames -> interleaved PCM, one lane per frame (kernels_flac.hip; the decoding itself is flac_frame.hpp)
+constexpr int FLAC_LANES = 64;  // one wavefront per workgroup: 16 KiB of LDS for the predictor windows of orders 13..32
+struct FlacSong {        // one file of the batch
+    uint64_t byte_off;   // its first byte in the batch's compressed bytes (a multiple of 16; 16 bytes of padding follow the file)
+    uint64_t nbytes;
+    uint64_t pcm_off;    // its first byte in the batch's PCM
+    uint64_t total;      // inter-channel samples
+    uint64_t base;       // the stream position the file's first frame codes (variable-block-size headers count from it)
+    uint32_t channels, bps;
+};
+struct FlacFrame {       // one row of the frame table (flac_index.hpp)
+    uint64_t offset, nbytes, first_sample;  // byte range in the file, header to CRC-16
+    uint32_t blocksize, song;               // song: bit 31 = the song's last frame (FLAC_LAST_FRAME)
+};
+constexpr uint32_t FLAC_LAST_FRAME = 0x80000000u;
+void launch_flac_decode(const uint8_t* bytes, const FlacSong* songs, const FlacFrame* frames, uint32_t n_frames, uint8_t* pcm,
+                        int32_t* status, uint64_t* end, hipStream_t st);
+// song_bad[s] = 1 when a frame of song s failed or did not stop 2 bytes before its successor; a song's last frame may stop
+// earlier (an ID3v1 tag or padding behind the audio).  song_bad is zeroed by the caller
+void launch_flac_check(const FlacFrame* frames, uint32_t n_frames, const int32_t* status, const uint64_t* end, uint32_t* song_bad,
+                       hipStream_t st);
 // one pair distance with both vectors passed by value (no staging copies); result -> *out (device-visible host word)
 void launch_pair_distance(const float* a, const float* b, uint32_t d, int metric, const float* d_M, float* out, hipStream_t st);
 // playlist ordering (kernels_playlist.hip)

@@ -46,16 +46,21 @@ def cue_track_bounds(index: Sequence, n_samples: int) -> List[Tuple[int, int]]:
 def analyze_cue_tracks(ctx, samples, sample_rate: int, index_seconds: Sequence,
                        analysis_options: Optional[AnalysisOptions] = None) -> List[Union[Analysis, BlissError]]:
     """samples: what the decoder delivered for the CUE sheet's audio file (numpy, 1-D mono or [frames, channels]; int16 / int32 /
-    float32) at `sample_rate`; index_seconds: the tracks' INDEX 01 times as (secs, nanos) or (mm, ss, ff) -- see cue_track_bounds.  One Analysis (or
+    float32) at `sample_rate`, or the audio file itself when it is a .flac (a path or its bytes: `Context.flac_decode`, `sample_rate`
+    is then taken from the file); index_seconds: the tracks' INDEX 01 times as (secs, nanos) or (mm, ss, ff) -- see cue_track_bounds.  One Analysis (or
     the BlissError the reference would put in that slot) per track, in order."""
     import torch
 
     options = analysis_options or AnalysisOptions()
     version = FeaturesVersion(options.features_version)
-    a = np.ascontiguousarray(samples)
-    if a.dtype not in (np.int16, np.int32):
-        a = a.astype(np.float32, copy=False)
-    pcm = ctx.pcm_decode(torch.from_numpy(np.array(a)).to(f"cuda:{ctx.device}"), int(sample_rate))
+    if isinstance(samples, (str, bytes, bytearray)):   # a .flac file (path or bytes): decoded on the device, its own rate
+        raw, sample_rate = ctx.flac_decode(samples)
+        pcm = ctx.pcm_decode(raw, int(sample_rate))
+    else:
+        a = np.ascontiguousarray(samples)
+        if a.dtype not in (np.int16, np.int32):
+            a = a.astype(np.float32, copy=False)
+        pcm = ctx.pcm_decode(torch.from_numpy(np.array(a)).to(f"cuda:{ctx.device}"), int(sample_rate))
     bounds = cue_track_bounds(index_seconds, pcm.numel())
     for s, e in bounds:
         if not 0 <= s <= e <= pcm.numel():

@@ -1,6 +1,7 @@
 """Device-resident API: a blissgpu context driven with torch tensors (torch supplies device memory,
 streams and torch.distributed; the compute is the HIP library)."""
 import ctypes as C
+import os
 from typing import Optional, Sequence
 
 import numpy as np
@@ -245,6 +246,69 @@ class Context:
                                                       int(sample_rate), C.c_void_p(out.data_ptr())))
         self._post()
         return out[:n_out]
+
+    # ---- FLAC decoded on the device ----
+    def flac_slow_songs(self) -> int:
+        """Songs of this context whose fast frame table was refused and that went through verified mode."""
+        return int(self._L.blissgpu_ctx_flac_slow_songs(self._h))
+
+    def flac_decode(self, data, verified: bool = False, return_frames: bool = False):
+        """One .flac file (bytes, a uint8 array, or a path) -> (pcm, sample_rate): the decoder output on the device, interleaved
+        [frames, channels] (1-D for mono), int16 = sample << (16 - bps) up to 16 bits per sample, int32 = sample << (32 - bps)
+        above -- what the reference's FFmpeg decoder hands to its resampler, and what `pcm_decode` takes.  The host only
+        finds the frames (blissgpu_flac_index); every frame is decoded by one lane of flac_decode_kernel.  A frame table of
+        the fast mode that the device refuses (a frame that does not stop 2 bytes before the next) is replaced by the
+        verified one; what that cannot repair raises DecodingError.
+        return_frames: also the per-frame (status, end position) tensors and the table, as they came out of THIS mode."""
+        from .song import DecodingError
+
+        torch = self.torch
+        if isinstance(data, (str, os.PathLike)):
+            with open(data, "rb") as f:
+                data = f.read()
+        host = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
+        n = int(host.size)
+        info = np.zeros(_ffi.FLAC_INFO_WORDS, np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        src = host if n else np.zeros(1, np.uint8)
+        if self._L.blissgpu_flac_info(C.c_void_p(src.ctypes.data), n, info.ctypes.data_as(u64p)) != _ffi.OK:
+            raise DecodingError("not a FLAC stream: " + self._L.blissgpu_last_error().decode())
+        channels, bps = int(info[1]), int(info[2])
+        if not 4 <= bps <= 24:
+            raise DecodingError(f"{bps} bits per sample are not supported")
+        nf = C.c_uint64(0)
+        self._L.blissgpu_flac_index(C.c_void_p(src.ctypes.data), n, int(verified), info.ctypes.data_as(u64p), None, 0, C.byref(nf))
+        table = np.zeros((max(1, nf.value), 4), np.uint64)
+        rc = self._L.blissgpu_flac_index(C.c_void_p(src.ctypes.data), n, int(verified), info.ctypes.data_as(u64p),
+                                         table.ctypes.data_as(u64p), nf.value, C.byref(nf))
+        table = table[:nf.value]
+        if rc != _ffi.OK and verified:
+            raise DecodingError(self._L.blissgpu_last_error().decode())
+        total = int(info[3])
+        dev = f"cuda:{self.device}"
+        d_bytes = torch.zeros(((n + 16 + 7) // 8) * 8, dtype=torch.uint8, device=dev)
+        d_bytes[:n] = torch.from_numpy(host.copy()).to(dev)
+        pcm = torch.zeros((total, channels), dtype=torch.int32 if bps > 16 else torch.int16, device=dev)
+        status = torch.full((max(1, nf.value),), 8, dtype=torch.int32, device=dev)
+        end = torch.zeros((max(1, nf.value),), dtype=torch.int64, device=dev)
+        self._pre()
+        _ffi.check(self._L.blissgpu_flac_decode_device(self._h, C.c_void_p(d_bytes.data_ptr()), n, table.ctypes.data_as(u64p), nf.value,
+                                                       info.ctypes.data_as(u64p), C.c_void_p(pcm.data_ptr()),
+                                                       C.c_void_p(status.data_ptr()), C.c_void_p(end.data_ptr())))
+        self._post()
+        status, end = status[:nf.value], end[:nf.value]
+        stops = torch.from_numpy((table[:, 0] + table[:, 1]).astype(np.int64)).to(dev) - 2
+        # (the last frame runs to the end of the data in the table and may stop earlier: an ID3v1 tag, padding)
+        sound = (rc == _ffi.OK and nf.value > 0 and bool((status == 0).all()) and bool((end[:-1] == stops[:-1]).all())
+                 and bool(end[-1] <= stops[-1]))
+        out = pcm[:, 0] if channels == 1 else pcm
+        if return_frames:
+            return out, int(info[0]), status, end, table
+        if not sound:
+            if verified:
+                raise DecodingError("a frame of the stream cannot be decoded")
+            return self.flac_decode(host, verified=True)
+        return out, int(info[0])
 
     # ---- playlist ordering on device-resident feature matrices (src/playlist.rs:24-59, 256-326) ----
     def _pl_args(self, seeds, cand, M):

@@ -222,6 +222,96 @@ def analyze_decoded_batch(sample_arrays: Sequence[np.ndarray], sample_rates, opt
     return _results(out, status, version)
 
 
+def _file_bytes(item) -> np.ndarray:
+    if isinstance(item, (bytes, bytearray, memoryview)):
+        return np.frombuffer(bytes(item), np.uint8)
+    if isinstance(item, np.ndarray):
+        return np.ascontiguousarray(item, np.uint8)
+    try:
+        with open(item, "rb") as f:
+            return np.frombuffer(f.read(), np.uint8)
+    except OSError:
+        return np.zeros(0, np.uint8)   # an unreadable file is a DecodingError of that song, like any other bad file
+
+
+def analyze_flac_batch(files, options: Optional[AnalysisOptions] = None):
+    """Compressed .flac files (bytes, uint8 arrays or paths) -> one Analysis or BlissError per file.  The host only finds the
+    frames; the FLAC decoding, the conversion to mono 22 050 Hz and the analysis all run on the device
+    (blissgpu_analyze_batch_flac).  A file that is not FLAC, has an unsupported depth, is truncated or holds a frame that cannot
+    be decoded yields DecodingError and leaves every other song of the call untouched."""
+    options = options or AnalysisOptions()
+    version = FeaturesVersion(options.features_version)
+    blobs = [_file_bytes(f) for f in files]
+    n = len(blobs)
+    if n == 0:
+        return []
+    d = version.feature_count()
+    out = np.empty((n, d), np.float32)
+    status = np.zeros(n, np.int32)
+    keep = [b if b.size else np.zeros(1, np.uint8) for b in blobs]
+    ptrs = (C.c_void_p * n)(*[k.ctypes.data for k in keep])
+    sizes = np.array([b.size for b in blobs], np.uint64)
+    _ffi.check(_ffi.lib().blissgpu_analyze_batch_flac(ptrs, sizes.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(version),
+                                                      out.ctypes.data, status.ctypes.data_as(C.POINTER(C.c_int32))))
+    results = _results(out, status, version)
+    for i in range(n):
+        if status[i] == _ffi.SONG_DECODE_ERROR:
+            results[i] = DecodingError("the FLAC stream cannot be decoded")
+    return results
+
+
+def flac_decode_batch(files):
+    """Several .flac files through ONE upload and ONE decode launch (the decode half of analyze_flac_batch): a list with, per
+    file, (samples [frames, channels], sample_rate, bits_per_sample) or DecodingError (blissgpu_flac_decode_batch)."""
+    blobs = [_file_bytes(f) for f in files]
+    n = len(blobs)
+    if n == 0:
+        return []
+    L = _ffi.lib()
+    u64p = C.POINTER(C.c_uint64)
+    keep = [b if b.size else np.zeros(1, np.uint8) for b in blobs]
+    infos = np.zeros((n, _ffi.FLAC_INFO_WORDS), np.uint64)
+    pcm = []
+    for b, k, info in zip(blobs, keep, infos):   # sizes first (device-free)
+        nf = C.c_uint64(0)
+        ok = L.blissgpu_flac_index(C.c_void_p(k.ctypes.data), b.size, 0, info.ctypes.data_as(u64p), None, 0, C.byref(nf)) == _ffi.OK
+        ok = ok and 1 <= int(info[1]) <= 8 and 4 <= int(info[2]) <= 24
+        pcm.append(np.zeros((int(info[3]) if ok else 0, int(info[1]) if ok else 1), np.int32 if int(info[2]) > 16 else np.int16))
+    hold = [p if p.size else np.zeros((1, 1), p.dtype) for p in pcm]
+    files_p = (C.c_void_p * n)(*[k.ctypes.data for k in keep])
+    pcm_p = (C.c_void_p * n)(*[h.ctypes.data for h in hold])
+    sizes = np.array([b.size for b in blobs], np.uint64)
+    room = np.array([p.nbytes for p in pcm], np.uint64)
+    status = np.zeros(n, np.int32)
+    _ffi.check(L.blissgpu_flac_decode_batch(files_p, sizes.ctypes.data_as(u64p), n, pcm_p, room.ctypes.data_as(u64p),
+                                            infos.ctypes.data_as(u64p), status.ctypes.data_as(C.POINTER(C.c_int32))))
+    return [(p[:int(i[3])], int(i[0]), int(i[2])) if st == _ffi.SONG_OK else DecodingError("the FLAC stream cannot be decoded")
+            for p, i, st in zip(pcm, infos, status)]
+
+
+def flac_decode(data):
+    """One .flac file (bytes or a path) -> (samples, sample_rate, bits_per_sample), decoded on the device and copied back:
+    [frames, channels] int16 (sample << (16 - bps)) up to 16 bits per sample, int32 (sample << (32 - bps)) above
+    (blissgpu_flac_decode).  Raises DecodingError."""
+    blob = _file_bytes(data)
+    L = _ffi.lib()
+    info = np.zeros(_ffi.FLAC_INFO_WORDS, np.uint64)
+    st = C.c_int32(0)
+    src = blob if blob.size else np.zeros(1, np.uint8)
+    u64p = C.POINTER(C.c_uint64)
+    _ffi.check(L.blissgpu_flac_decode(C.c_void_p(src.ctypes.data), blob.size, None, 0, info.ctypes.data_as(u64p), C.byref(st)))
+    if st.value != _ffi.SONG_OK:
+        raise DecodingError("the FLAC stream cannot be decoded")
+    channels, bps = int(info[1]), int(info[2])
+    pcm = np.zeros((int(info[3]), channels), np.int32 if bps > 16 else np.int16)
+    if pcm.size:
+        _ffi.check(L.blissgpu_flac_decode(C.c_void_p(src.ctypes.data), blob.size, C.c_void_p(pcm.ctypes.data), pcm.nbytes,
+                                          info.ctypes.data_as(u64p), C.byref(st)))
+        if st.value != _ffi.SONG_OK:
+            raise DecodingError("the FLAC stream cannot be decoded")
+    return pcm[:int(info[3])], int(info[0]), bps
+
+
 def analyze_batch(sample_arrays: Sequence[np.ndarray], options: Optional[AnalysisOptions] = None):
     """Bulk Song::analyze_with_options: one GPU batch, per-song result (Analysis or BlissError), like the
     (path, BlissResult<Song>) pairs of analyze_paths_with_options (src/song/decoder.rs:278-332).  A single song goes

@@ -47,6 +47,8 @@ extern "C" {
 /* ---- per-song status, maps 1:1 onto BlissError (src/lib.rs:236-252) ---- */
 #define BLISSGPU_SONG_OK 0
 #define BLISSGPU_SONG_TOO_SHORT 1     /* AnalysisError("empty or too short song.") -- len < 8192 (src/song/mod.rs:417-430) */
+#define BLISSGPU_SONG_DECODE_ERROR 2  /* DecodingError (blissgpu_analyze_batch_flac): not FLAC, unsupported depth, truncated, or a
+                                       * frame error that the verified frame table cannot repair */
 
 /* ---- FeaturesVersion (src/lib.rs:151-187) ---- */
 #define BLISSGPU_FEATURES_V1 1u       /* 20 features */
@@ -236,6 +238,61 @@ int blissgpu_pcm_downmix_device(blissgpu_ctx *ctx, const void *d_in, int sample_
 /* decoder output at sample_rate -> mono 22 050 Hz f32; d_out holds blissgpu_resampled_len(frames, sample_rate) samples */
 int blissgpu_pcm_decode_device(blissgpu_ctx *ctx, const void *d_in, int sample_format, uint32_t channels, uint64_t frames,
                                uint32_t sample_rate, float *d_out);
+
+/* ---- FLAC decoded ON THE DEVICE: compressed files in, PCM / feature rows out ----
+ * The host only finds the frames (it never decodes a residual); flac_decode_kernel decodes one frame per lane into what the
+ * reference's FFmpeg decoder hands on: up to 16 bits per sample interleaved int16, sample << (16 - bps); above, interleaved
+ * int32, sample << (32 - bps).  Bit for bit -- FLAC is lossless and the stream's MD5 says so.  Handled: CONSTANT / VERBATIM /
+ * FIXED 0-4 / LPC 1-32 subframes, wasted bits, both Rice methods, escape partitions, every channel assignment, 1-8 channels,
+ * 4-24 bits per sample.  32 bits per sample and Ogg-FLAC are reported as decode errors.
+ * NOT checked on the hot path: CRC-16 (fast index mode) and the stream MD5.
+ *
+ * info: BLISSGPU_FLAC_INFO_WORDS 64-bit words -- [0] sample rate, [1] channels, [2] bits per sample, [3] total inter-channel
+ * samples (0 = unknown in STREAMINFO; blissgpu_flac_index and blissgpu_flac_decode replace it by the count the frame table
+ * holds), [4] / [5] min / max block size, [6] min frame size, [7] byte offset of the first frame, [8..9] the MD5 (16 bytes
+ * in file order), [10] the stream position the first frame's header codes (set by blissgpu_flac_index / _decode: 0 unless
+ * the file was cut out of a longer stream), [11] reserved (0).
+ * An ID3v2 tag in front of "fLaC" is skipped.  Device-free. */
+#define BLISSGPU_FLAC_INFO_WORDS 12u
+int blissgpu_flac_info(const void *file, uint64_t nbytes, uint64_t *info);
+/* The frame table: rows of 4 words -- byte offset, byte length (header to CRC-16), first sample, block size.  At most
+ * max_frames rows are written (frames may be NULL), *n_frames receives the count.  verified = 0: CRC-8 and the expected frame
+ * number only -- fast, and a header-shaped run of bytes inside a frame can fool it (the device notices: that frame does not
+ * stop 2 bytes before the next row); verified = 1: CRC-16 over every candidate frame, exact for every frame but the last (it
+ * runs to the end of the data; bytes behind the audio are left to the decoder's stop position).  info may be NULL.  Device-free.
+ * BLISSGPU_ERR_INVALID for a stream without frames or with fewer samples than STREAMINFO promises (the table is filled). */
+int blissgpu_flac_index(const void *file, uint64_t nbytes, int verified, uint64_t *info, uint64_t *frames, uint64_t max_frames,
+                        uint64_t *n_frames);
+/* Device to device, asynchronous on the context's stream: the frames of ONE file.  d_bytes = the file on the device, 8-byte
+ * aligned, with 16 readable bytes behind it; frames / info as blissgpu_flac_index returned them (host memory; info[3] is the
+ * size of d_pcm in inter-channel samples: no store goes beyond it).  d_frame_status[i] = 0 or the frame's error
+ * (flac_frame.hpp: 1 reserved subframe type, 2 reserved channel assignment, 3 header mismatch, 4 ran past the frame,
+ * 5 negative shift, 6 unsupported depth, 7 malformed subframe); d_frame_end[i] = the byte position frame i stopped at --
+ * frames[i].offset + frames[i].length - 2 for a frame that is what the table took it for (the last frame may stop earlier). */
+int blissgpu_flac_decode_device(blissgpu_ctx *ctx, const void *d_bytes, uint64_t nbytes, const uint64_t *frames, uint64_t n_frames,
+                                const uint64_t *info, void *d_pcm, int32_t *d_frame_status, uint64_t *d_frame_end);
+/* One file in host memory -> PCM in host memory (default context): fast table, end-position check, verified table and a second
+ * launch on a mismatch.  pcm = NULL: info and *status only (nothing runs on the device); otherwise max_bytes >= info[3] x
+ * channels x (2 or 4).  *status = BLISSGPU_SONG_OK or BLISSGPU_SONG_DECODE_ERROR (the call itself still returns BLISSGPU_OK). */
+int blissgpu_flac_decode(const void *file, uint64_t nbytes, void *pcm, uint64_t max_bytes, uint64_t *info, int32_t *status);
+/* Several files through ONE upload and ONE decode launch -- the decode half of blissgpu_analyze_batch_flac, its PCM handed
+ * back: pcm[i] (host, max_bytes[i] bytes) receives song i, info + i * BLISSGPU_FLAC_INFO_WORDS its info, status[i] its status.
+ * A song whose PCM does not fit max_bytes[i] gets BLISSGPU_SONG_DECODE_ERROR; BLISSGPU_ERR_INVALID when the files do not fit
+ * the workspace limit together (this form does not split). */
+int blissgpu_flac_decode_batch(const void *const *files, const uint64_t *nbytes, uint32_t n_songs, void *const *pcm,
+                               const uint64_t *max_bytes, uint64_t *info, int32_t *status);
+/* Bulk form: the bytes of n_songs .flac files -> n_songs feature rows.  Frame tables on the host (at most as many threads as
+ * the staging ring has workers), one upload of the compressed bytes, one decode launch for the batch, the end-position
+ * check, the device conversion to mono 22 050 Hz per song, the device-resident batch analysis.  The decoded PCM of a
+ * sub-batch (with its compressed bytes and mono stream) fits the context's workspace limit; the call is split when it does
+ * not, and a song that exceeds the limit by itself is a decode error.  A song's last frame may be followed by other bytes
+ * (an ID3v1 tag, padding).  status[i] = BLISSGPU_SONG_OK,
+ * _TOO_SHORT or _DECODE_ERROR (row = NaN); one bad file never affects another song of the call.  status may be NULL. */
+int blissgpu_analyze_batch_flac(const void *const *files, const uint64_t *nbytes, uint32_t n_songs, uint32_t features_version,
+                                float *out, int32_t *status);
+/* Songs of this context whose fast frame table the device refused, or could not be closed on the host: they went through
+ * verified mode (statistics). */
+uint64_t blissgpu_ctx_flac_slow_songs(blissgpu_ctx *ctx);
 
 /* Device-resident form: d_pcm / d_out / d_status are HIP device pointers (d_status may be NULL),
  * offsets / lengths stay on the host (they size the launch).  Asynchronous on the context's
