@@ -69,6 +69,12 @@ pub mod sys {
     pub const BLISSGPU_SONG_TOO_SHORT: i32 = 1;
     pub const BLISSGPU_SONG_DECODE_ERROR: i32 = 2;
     pub const BLISSGPU_FLAC_INFO_WORDS: usize = 12;
+    pub const BLISSGPU_FLAC_CHECK_CRC16: u32 = 1;
+    pub const BLISSGPU_FLAC_CHECK_MD5: u32 = 2;
+    pub const BLISSGPU_FLAC_BAD_STREAM: u32 = 1;
+    pub const BLISSGPU_FLAC_BAD_CRC16: u32 = 2;
+    pub const BLISSGPU_FLAC_BAD_MD5: u32 = 4;
+    pub const BLISSGPU_FLAC_MD5_UNCHECKED: u32 = 8;
     pub const BLISSGPU_METRIC_EUCLIDEAN: c_int = 0;
     pub const BLISSGPU_METRIC_COSINE: c_int = 1;
     pub const BLISSGPU_METRIC_MAHALANOBIS: c_int = 2;
@@ -234,6 +240,11 @@ pub mod sys {
         pub fn blissgpu_flac_decode_batch(files: *mut *const c_void, nbytes: *const u64, n_songs: u32, pcm: *mut *mut c_void, max_bytes: *const u64, info: *mut u64, status: *mut i32) -> c_int;
         pub fn blissgpu_analyze_batch_flac(files: *mut *const c_void, nbytes: *const u64, n_songs: u32, features_version: u32, out: *mut f32, status: *mut i32) -> c_int;
         pub fn blissgpu_ctx_flac_slow_songs(ctx: *mut blissgpu_ctx) -> u64;
+        // FLAC verified on the device: frame CRC-16 and stream MD5, a verdict per song
+        pub fn blissgpu_flac_verify_batch(files: *mut *const c_void, nbytes: *const u64, n_songs: u32, checks: u32, flags: *mut u32, first_bad_frame: *mut u32, md5: *mut c_void) -> c_int;
+        pub fn blissgpu_analyze_batch_flac_verified(files: *mut *const c_void, nbytes: *const u64, n_songs: u32, features_version: u32, checks: u32, out: *mut f32, status: *mut i32, flags: *mut u32, first_bad_frame: *mut u32) -> c_int;
+        pub fn blissgpu_flac_crc16_device(ctx: *mut blissgpu_ctx, d_bytes: *const c_void, nbytes: u64, frames: *const u64, n_frames: u64, d_frame_status: *const i32, d_frame_end: *const u64, d_frame_crc_ok: *mut i32) -> c_int;
+        pub fn blissgpu_flac_md5_device(ctx: *mut blissgpu_ctx, d_pcm: *const c_void, info: *const u64, d_md5: *mut c_void) -> c_int;
         pub fn blissgpu_last_error() -> *const c_char;
         pub fn blissgpu_version() -> *const c_char;
     }

@@ -8,6 +8,7 @@ bliss-rs / `bliss-audio` 0.13.0):
     Analysis, AnalysisIndex, FeaturesVersion      src/song/mod.rs:102-371, src/lib.rs:151-187
     Decoder.{decode, song_from_path, analyze_paths}  src/song/decoder.rs:115-333
     FlacDecoder, analyze_flac_batch, Context.flac_decode: .flac files decoded ON THE DEVICE, compressed bytes in, rows out
+    flac_verify_batch, analyze_flac_batch(verify=), Context.flac_crc16 / flac_md5: frame CRC-16 and stream MD5 checked on the device
     cue.{cue_track_bounds, analyze_cue_tracks}    BlissCueFile::get_songs, src/cue.rs:205-246 (sheet parsing stays with the host)
     euclidean / cosine / mahalanobis distance, closest_to_songs, song_to_song, dedup, ...   src/playlist.rs
     playlist.nearest_order / nearest_songs, library.similar_songs: the k closest songs of many songs in one call
@@ -25,7 +26,7 @@ from ._ffi import BlissGpuError, LIB_PATH  # noqa: F401
 from .song import (  # noqa: F401
     SAMPLE_RATE, CHANNELS, NUMBER_FEATURES, Analysis, AnalysisError, AnalysisIndex, AnalysisIndexv1,
     AnalysisOptions, BlissError, DecodingError, FeaturesVersion, ProviderError, Song, analyze_batch, analyze_decoded_batch,
-    analyze_flac_batch, flac_decode, flac_decode_batch, resampled_len)
+    FlacVerdict, analyze_flac_batch, flac_decode, flac_decode_batch, flac_verify_batch, resampled_len)
 from .decoder import Decoder, FlacDecoder, PreAnalyzedSong, RawPcmDecoder  # noqa: F401
 from . import playlist  # noqa: F401
 from . import cue  # noqa: F401

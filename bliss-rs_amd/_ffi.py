@@ -16,6 +16,8 @@ SAMPLE_F32, SAMPLE_S16, SAMPLE_S32 = 0, 1, 2
 SAMPLE_RATE = 22050
 SONG_OK, SONG_TOO_SHORT, SONG_DECODE_ERROR = 0, 1, 2
 FLAC_INFO_WORDS = 12
+FLAC_CHECK_CRC16, FLAC_CHECK_MD5 = 1, 2
+FLAC_BAD_STREAM, FLAC_BAD_CRC16, FLAC_BAD_MD5, FLAC_MD5_UNCHECKED = 1, 2, 4, 8
 METRIC_EUCLIDEAN, METRIC_COSINE, METRIC_MAHALANOBIS = 0, 1, 2
 CHAINS_AUTO, CHAINS_STEPS, CHAINS_LISTS = 0, 1, 2
 OPT_SERIAL, OPT_TAIL_MODE, OPT_PIPELINE_CHUNKS, OPT_CAND_BUDGET, OPT_ROLLOFF_EXACT_ALL, OPT_DEBUG_CHROMA, OPT_TAIL_SPLIT = 0, 1, 2, 3, 4, 5, 6
@@ -55,6 +57,10 @@ SIGNATURES = {
     "blissgpu_flac_decode_batch": (C.c_int, [C.POINTER(_vp), _u64p, C.c_uint32, C.POINTER(_vp), _u64p, _u64p, _i32p]),
     "blissgpu_analyze_batch_flac": (C.c_int, [C.POINTER(_vp), _u64p, C.c_uint32, C.c_uint32, _vp, _i32p]),
     "blissgpu_ctx_flac_slow_songs": (C.c_uint64, [_vp]),
+    "blissgpu_flac_verify_batch": (C.c_int, [C.POINTER(_vp), _u64p, C.c_uint32, C.c_uint32, _u32p, _u32p, _vp]),
+    "blissgpu_analyze_batch_flac_verified": (C.c_int, [C.POINTER(_vp), _u64p, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _i32p, _u32p, _u32p]),
+    "blissgpu_flac_crc16_device": (C.c_int, [_vp, _vp, C.c_uint64, _u64p, C.c_uint64, _vp, _vp, _vp]),
+    "blissgpu_flac_md5_device": (C.c_int, [_vp, _vp, _u64p, _vp]),
     "blissgpu_ctx_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
     "blissgpu_ctx_destroy": (C.c_int, [_vp]),
     "blissgpu_ctx_set_stream": (C.c_int, [_vp, _vp]),

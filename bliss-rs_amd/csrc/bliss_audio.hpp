@@ -13,6 +13,7 @@
 //   bliss::euclidean_distance / cosine_distance / mahalanobis_distance   src/playlist.rs:65-142
 #pragma once
 #include <algorithm>
+#include <array>
 #include <cctype>
 #include <cmath>
 #include <cstdint>
@@ -399,6 +400,19 @@ struct FlacFile {
     std::vector<uint8_t> bytes;   // the compressed file
 };
 
+// what to check beyond the structure (every frame stops 2 bytes before the next), on the device
+enum class FlacVerify : uint32_t { None = 0, Crc = BLISSGPU_FLAC_CHECK_CRC16, Md5 = BLISSGPU_FLAC_CHECK_CRC16 | BLISSGPU_FLAC_CHECK_MD5 };
+
+struct FlacVerdict {              // what the device found in one file (FlacDecoder::verify_paths)
+    uint32_t flags = 0;           // BLISSGPU_FLAC_BAD_STREAM | _BAD_CRC16 | _BAD_MD5 | _MD5_UNCHECKED
+    std::optional<uint32_t> first_bad_frame;  // the first frame whose CRC-16 failed
+    std::optional<std::array<uint8_t, 16>> md5;  // the digest of the decoded audio, when it was computed
+    bool ok() const { return (flags & 7u) == 0; }
+    bool stream_ok() const { return !(flags & BLISSGPU_FLAC_BAD_STREAM); }
+    bool crc_ok() const { return stream_ok() && !(flags & BLISSGPU_FLAC_BAD_CRC16); }
+    const char* md5_state() const { return (flags & BLISSGPU_FLAC_BAD_MD5) ? "mismatch" : (flags & BLISSGPU_FLAC_MD5_UNCHECKED) ? "unchecked" : "match"; }
+};
+
 class FlacDecoder {
   public:
     // file -> tags + the compressed bytes (artist, title, album, album_artist, track_number, disc_number, genre as the
@@ -440,8 +454,46 @@ class FlacDecoder {
         return f;
     }
 
-    // (path, Result) pairs from ONE device batch of compressed files; a bad file yields its DecodingError and never aborts the run
-    static std::vector<std::pair<std::string, BlissResult<Song>>> analyze_paths(const std::vector<std::string>& paths, const AnalysisOptions& opt = {}) {
+    // `flac -t` for a batch of files, on the device: every frame's CRC-16 and (md5) the MD5 of the decoded audio against
+    // STREAMINFO's -- one lane per song, slow for long songs; no analysis.  An unreadable file is BAD_STREAM
+    static std::vector<std::pair<std::string, FlacVerdict>> verify_paths(const std::vector<std::string>& paths, bool md5 = true) {
+        const size_t n = paths.size();
+        std::vector<std::vector<uint8_t>> bytes(n);
+        std::vector<const void*> files(n);
+        std::vector<uint64_t> sizes(n);
+        for (size_t i = 0; i < n; i++) {
+            if (FILE* fp = fopen(paths[i].c_str(), "rb")) {
+                uint8_t buf[65536];
+                for (size_t k; (k = fread(buf, 1, sizeof(buf), fp)) > 0;) bytes[i].insert(bytes[i].end(), buf, buf + k);
+                fclose(fp);
+            }
+            files[i] = bytes[i].data();
+            sizes[i] = bytes[i].size();
+        }
+        std::vector<uint32_t> flags(n, 0), first_bad(n, 0xFFFFFFFFu);
+        std::vector<uint8_t> digests(16 * n, 0);
+        const uint32_t checks = BLISSGPU_FLAC_CHECK_CRC16 | (md5 ? BLISSGPU_FLAC_CHECK_MD5 : 0u);
+        if (n) check(blissgpu_flac_verify_batch(files.data(), sizes.data(), static_cast<uint32_t>(n), checks, flags.data(), first_bad.data(), digests.data()));
+        std::vector<std::pair<std::string, FlacVerdict>> out;
+        for (size_t i = 0; i < n; i++) {
+            FlacVerdict v;
+            v.flags = flags[i];
+            if (first_bad[i] != 0xFFFFFFFFu) v.first_bad_frame = first_bad[i];
+            if (!(flags[i] & (BLISSGPU_FLAC_MD5_UNCHECKED | BLISSGPU_FLAC_BAD_STREAM))) {
+                std::array<uint8_t, 16> d;
+                std::copy(digests.begin() + 16 * i, digests.begin() + 16 * (i + 1), d.begin());
+                v.md5 = d;
+            }
+            out.emplace_back(paths[i], v);
+        }
+        return out;
+    }
+
+    // (path, Result) pairs from ONE device batch of compressed files; a bad file yields its DecodingError and never aborts the run.
+    // verify: also check every frame's CRC-16 (and the stream's MD5) on the device; a song that fails yields a DecodingError
+    // that names the check and the frame
+    static std::vector<std::pair<std::string, BlissResult<Song>>> analyze_paths(const std::vector<std::string>& paths, const AnalysisOptions& opt = {},
+                                                                               FlacVerify verify = FlacVerify::None) {
         std::vector<std::pair<std::string, BlissResult<Song>>> out;
         std::vector<FlacFile> pending;
         for (const auto& p : paths) {
@@ -455,12 +507,20 @@ class FlacDecoder {
         for (size_t i = 0; i < n; i++) { files[i] = pending[i].bytes.data(); sizes[i] = pending[i].bytes.size(); }
         std::vector<float> rows(n * d);
         std::vector<int32_t> status(n, 0);
-        if (n) check(blissgpu_analyze_batch_flac(files.data(), sizes.data(), static_cast<uint32_t>(n), static_cast<uint32_t>(opt.features_version), rows.data(), status.data()));
+        std::vector<uint32_t> flags(n, BLISSGPU_FLAC_BAD_STREAM), first_bad(n, 0xFFFFFFFFu);
+        if (n && verify == FlacVerify::None)
+            check(blissgpu_analyze_batch_flac(files.data(), sizes.data(), static_cast<uint32_t>(n), static_cast<uint32_t>(opt.features_version), rows.data(), status.data()));
+        else if (n)
+            check(blissgpu_analyze_batch_flac_verified(files.data(), sizes.data(), static_cast<uint32_t>(n), static_cast<uint32_t>(opt.features_version),
+                                                       static_cast<uint32_t>(verify), rows.data(), status.data(), flags.data(), first_bad.data()));
         for (size_t i = 0; i < n; i++) {
             if (status[i] == BLISSGPU_SONG_OK)
                 out.emplace_back(pending[i].pre.path, pending[i].pre.to_song(Analysis(std::vector<float>(rows.begin() + i * d, rows.begin() + (i + 1) * d), opt.features_version), opt.features_version));
             else if (status[i] == BLISSGPU_SONG_TOO_SHORT) out.emplace_back(pending[i].pre.path, AnalysisError("empty or too short song."));
-            else out.emplace_back(pending[i].pre.path, DecodingError("the FLAC stream of '" + pending[i].pre.path + "' cannot be decoded"));
+            else if (flags[i] & BLISSGPU_FLAC_BAD_STREAM) out.emplace_back(pending[i].pre.path, DecodingError("the FLAC stream of '" + pending[i].pre.path + "' cannot be decoded"));
+            else if (flags[i] & BLISSGPU_FLAC_BAD_CRC16)
+                out.emplace_back(pending[i].pre.path, DecodingError("the FLAC stream of '" + pending[i].pre.path + "' is damaged: CRC-16 mismatch in frame " + std::to_string(first_bad[i])));
+            else out.emplace_back(pending[i].pre.path, DecodingError("the FLAC stream of '" + pending[i].pre.path + "' is damaged: the MD5 of the decoded audio is not STREAMINFO's"));
         }
         return out;
     }

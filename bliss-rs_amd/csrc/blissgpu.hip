@@ -345,6 +345,7 @@ int blissgpu_ctx_destroy(blissgpu_ctx* c) {
         c->st_a.release(); c->st_b.release(); c->st_m.release(); c->st_dist.release(); c->st_out.release();
         c->fl_bytes.release(); c->fl_tab.release(); c->fl_pcm.release(); c->fl_status.release(); c->fl_end.release();
         c->fl_bad.release(); c->fl_mono.release(); c->fl_rows.release(); c->fl_htab.release();
+        c->fl_vsong.release(); c->fl_md5_jobs.release(); c->fl_md5.release();
         if (c->fl_ev) (void)hipEventDestroy(c->fl_ev);
         for (int s = 0; s < 2; s++) {
             c->gf_img[s].release();
@@ -2245,6 +2246,7 @@ int blissgpu_debug_fetch(blissgpu_ctx* c, int what, uint32_t song, void* dst, ui
 
 #include "flac_frame.hpp"
 #include "flac_index.hpp"
+#include "flac_verify.hpp"
 
 namespace {
 
@@ -2293,8 +2295,48 @@ void flac_plan(FlacPlan& p) {
     }
 }
 
+// The opt-in checks of a call: what was asked for, and per file of the call the verdict flags (BLISSGPU_FLAC_BAD_CRC16 /
+// _BAD_MD5 / _MD5_UNCHECKED; BAD_STREAM is the plan's error), the first frame whose CRC-16 failed, the computed digest.
+struct FlacVerify {
+    uint32_t checks = 0;
+    std::vector<uint32_t> flags, first_bad;
+    std::vector<uint8_t> md5;
+    FlacVerify(uint32_t checks_, size_t n) : checks(checks_), flags(n, BLISSGPU_FLAC_MD5_UNCHECKED), first_bad(n, 0xFFFFFFFFu), md5(16 * n, 0) {}
+};
+
 // what a song keeps resident while its sub-batch is decoded and analysed: compressed bytes, PCM, the mono 22 050 Hz stream
 uint64_t flac_resident_bytes(const FlacPlan& p) { return p.pcm_bytes + p.nbytes + 4 * p.total + 64; }
+
+// the frame tables of a call, on at most as many threads as the context's staging ring has workers
+void flac_plan_all(blissgpu_ctx* c, std::vector<FlacPlan>& plans) {
+    const uint32_t n_songs = (uint32_t)plans.size();
+    const uint32_t workers = std::min<uint32_t>(n_songs, (uint32_t)std::max(1, std::min(c->feed.stage_cfg.lanes, MAX_STAGE_LANES)));
+    std::atomic<uint32_t> next{0};
+    auto work = [&]() {
+        for (uint32_t i; (i = next.fetch_add(1)) < n_songs;) flac_plan(plans[i]);
+    };
+    std::vector<std::thread> pool;
+    for (uint32_t w = 1; w < workers; w++) pool.emplace_back(work);
+    work();
+    for (std::thread& t : pool) t.join();
+}
+
+// The next sub-batch of a call: the songs from i0 on whose resident bytes fit the workspace limit together (at least one
+// song) -> sel; returns the first song of the sub-batch after it.  A song that does not fit the limit by itself (a few MB of
+// CONSTANT frames can claim hundreds of GB) is refused: its plan's error is set
+uint32_t flac_next_subbatch(blissgpu_ctx* c, std::vector<FlacPlan>& plans, uint32_t i0, std::vector<uint32_t>* sel) {
+    sel->clear();
+    uint64_t resident = 0;
+    uint32_t i1 = i0;
+    for (; i1 < plans.size(); i1++) {
+        if (!plans[i1].error && flac_resident_bytes(plans[i1]) > c->ws_limit) plans[i1].error = true;
+        const uint64_t b = plans[i1].error ? 0 : flac_resident_bytes(plans[i1]);
+        if (!sel->empty() && resident + b > c->ws_limit) break;
+        resident += b;
+        sel->push_back(i1);
+    }
+    return i1;
+}
 
 // songs | frames into the context's table buffer (through its page-locked staging), asynchronous on the context's stream
 int flac_upload_tables(blissgpu_ctx* c, const std::vector<FlacSong>& songs, const std::vector<FlacFrame>& frames,
@@ -2323,7 +2365,9 @@ void flac_rows_of(const FlacPlan& p, uint32_t song, std::vector<FlacFrame>* fram
 
 // Upload, decode and check the planned files `sel` (indices into plans); afterwards plans[i].error says which of them have
 // no PCM, the others' PCM sits at c->fl_pcm.p + pcm_off.  Synchronises the context's stream.
-int flac_run(blissgpu_ctx* c, std::vector<FlacPlan>& plans, const std::vector<uint32_t>& sel, const char* who) {
+// v (may be NULL): the checks to run on the songs that decoded -- the CRC-16 of every frame of the table a song ended with,
+// then the MD5 of the PCM of the songs that are sound so far; v's entries of `sel` are filled, plans[i].error is left to the caller.
+int flac_run(blissgpu_ctx* c, std::vector<FlacPlan>& plans, const std::vector<uint32_t>& sel, const char* who, FlacVerify* v = nullptr) {
     std::vector<FlacSong> songs;
     std::vector<FlacFrame> frames;
     std::vector<uint32_t> live;  // plans that reach the device
@@ -2349,6 +2393,19 @@ int flac_run(blissgpu_ctx* c, std::vector<FlacPlan>& plans, const std::vector<ui
     for (uint32_t k = 0; k < live.size(); k++)
         HIP_TRY(hipMemcpyAsync(c->fl_bytes.p + songs[k].byte_off, plans[live[k]].file, plans[live[k]].nbytes, hipMemcpyHostToDevice, c->stream));
     std::vector<uint32_t> bad(live.size(), 0);
+    // the CRC-16 check: [first row | flag | first bad frame] per song, and which songs have rows in this pass
+    const bool crc = v && (v->checks & BLISSGPU_FLAC_CHECK_CRC16);
+    const size_t ns = live.size();
+    std::vector<uint32_t> vsong(crc ? 3 * ns : 0, 0);
+    std::vector<uint8_t> in_pass(ns, 1);
+    if (crc) {
+        if ((rc = c->fl_vsong.ensure(3 * ns))) return rc;
+        uint32_t row = 0;
+        for (size_t k = 0; k < ns; k++) {
+            vsong[k] = row;
+            row += (uint32_t)plans[live[k]].rows.size();
+        }
+    }
     for (int pass = 0; pass < 2 && !frames.empty(); pass++) {
         const FlacSong* d_songs;
         const FlacFrame* d_frames;
@@ -2358,9 +2415,23 @@ int flac_run(blissgpu_ctx* c, std::vector<FlacPlan>& plans, const std::vector<ui
         HIP_TRY(hipMemsetAsync(c->fl_bad.p, 0, live.size() * sizeof(uint32_t), c->stream));
         launch_flac_decode(c->fl_bytes.p, d_songs, d_frames, (uint32_t)frames.size(), c->fl_pcm.p, c->fl_status.p, c->fl_end.p, c->stream);
         launch_flac_check(d_frames, (uint32_t)frames.size(), c->fl_status.p, c->fl_end.p, c->fl_bad.p, c->stream);
+        if (crc) {
+            for (size_t k = 0; k < ns; k++) { vsong[ns + k] = 0; vsong[2 * ns + k] = 0xFFFFFFFFu; }
+            HIP_TRY(hipMemcpyAsync(c->fl_vsong.p, vsong.data(), 3 * ns * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+            launch_flac_crc(c->fl_bytes.p, d_songs, d_frames, (uint32_t)frames.size(), c->fl_status.p, c->fl_end.p, c->fl_vsong.p,
+                            c->fl_vsong.p + ns, c->fl_vsong.p + 2 * ns, nullptr, c->stream);
+        }
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(bad.data(), c->fl_bad.p, live.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (crc) HIP_TRY(hipMemcpyAsync(vsong.data() + ns, c->fl_vsong.p + ns, 2 * ns * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
+        if (crc)  // the verdict of the songs whose table stood in this pass
+            for (size_t k = 0; k < ns; k++)
+                if (in_pass[k] && !bad[k] && vsong[ns + k]) {
+                    v->flags[live[k]] |= BLISSGPU_FLAC_BAD_CRC16;
+                    v->first_bad[live[k]] = vsong[2 * ns + k];
+                }
+        std::fill(in_pass.begin(), in_pass.end(), 0);
         // the songs the device refused go through verified mode and a second, small launch -- each of them alone
         frames.clear();
         for (uint32_t k = 0; k < live.size(); k++) {
@@ -2373,8 +2444,39 @@ int flac_run(blissgpu_ctx* c, std::vector<FlacPlan>& plans, const std::vector<ui
             if (p.error || p.pcm_bytes > room) { p.error = true; continue; }
             songs[k].total = p.total;
             songs[k].base = p.base;
+            if (crc) vsong[k] = (uint32_t)frames.size();
+            in_pass[k] = 1;
             flac_rows_of(p, k, &frames);
         }
+    }
+    if (!v || !(v->checks & BLISSGPU_FLAC_CHECK_MD5)) return BLISSGPU_OK;
+    // the MD5 of the songs that are sound so far and whose STREAMINFO digest speaks of exactly these samples; longest first
+    std::vector<FlacMd5Job> jobs;
+    for (uint32_t k = 0; k < live.size(); k++) {
+        const FlacPlan& p = plans[live[k]];
+        static const uint8_t zero[16] = {0};
+        if (p.error || (v->flags[live[k]] & BLISSGPU_FLAC_BAD_CRC16) || !memcmp(p.si.md5, zero, 16) || p.base != 0 ||
+            (p.si.total != 0 && p.si.total != p.total))
+            continue;
+        jobs.push_back(FlacMd5Job{p.pcm_off, p.total * p.si.channels, p.si.bps, k});
+    }
+    if (jobs.empty()) return BLISSGPU_OK;
+    std::stable_sort(jobs.begin(), jobs.end(), [](const FlacMd5Job& a, const FlacMd5Job& b) {
+        return a.n_elems * flac::Md5Pcm::width_of(a.bps) > b.n_elems * flac::Md5Pcm::width_of(b.bps);
+    });
+    if ((rc = c->fl_md5_jobs.ensure(jobs.size()))) return rc;
+    if ((rc = c->fl_md5.ensure(16 * live.size()))) return rc;
+    std::vector<uint8_t> digests(16 * live.size());
+    HIP_TRY(hipMemcpyAsync(c->fl_md5_jobs.p, jobs.data(), jobs.size() * sizeof(FlacMd5Job), hipMemcpyHostToDevice, c->stream));
+    launch_flac_md5(c->fl_pcm.p, c->fl_md5_jobs.p, (uint32_t)jobs.size(), c->fl_md5.p, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(digests.data(), c->fl_md5.p, digests.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (const FlacMd5Job& j : jobs) {
+        const uint32_t i = live[j.slot];
+        memcpy(&v->md5[16 * (size_t)i], &digests[16 * (size_t)j.slot], 16);
+        v->flags[i] &= ~BLISSGPU_FLAC_MD5_UNCHECKED;
+        if (memcmp(&digests[16 * (size_t)j.slot], plans[i].si.md5, 16)) v->flags[i] |= BLISSGPU_FLAC_BAD_MD5;
     }
     return BLISSGPU_OK;
 }
@@ -2515,35 +2617,29 @@ int blissgpu_flac_decode_batch(const void* const* files, const uint64_t* nbytes,
     return BLISSGPU_OK;
 }
 
-int blissgpu_analyze_batch_flac(const void* const* files, const uint64_t* nbytes, uint32_t n_songs, uint32_t features_version,
-                                float* out, int32_t* status) {
-    const char* who = "blissgpu_analyze_batch_flac";
+// blissgpu_analyze_batch_flac, and with checks != 0 its verified form: a song that fails a check is refused like one that
+// does not decode; nothing else of the call changes
+static int flac_analyze(const void* const* files, const uint64_t* nbytes, uint32_t n_songs, uint32_t features_version, uint32_t checks,
+                        float* out, int32_t* status, uint32_t* flags, uint32_t* first_bad_frame, const char* who) {
     const uint32_t d = blissgpu_feature_count(features_version);
     if (!d) return fail(BLISSGPU_ERR_INVALID, who, "features_version must be 1 or 2");
-    if (n_songs && (!files || !nbytes || !out)) return fail(BLISSGPU_ERR_INVALID, who, "NULL argument");
+    if (n_songs && (!files || !nbytes || !out || (checks && !flags))) return fail(BLISSGPU_ERR_INVALID, who, "NULL argument");
+    if (checks & ~(BLISSGPU_FLAC_CHECK_CRC16 | BLISSGPU_FLAC_CHECK_MD5)) return fail(BLISSGPU_ERR_INVALID, who, "unknown check");
     if (n_songs == 0) return BLISSGPU_OK;
     FlacDeviceRestore restore;
     blissgpu_ctx* c;
     int rc = default_ctx(&c);
     if (rc) return rc;
     CTX_ENTER(c, who);
-    // 1. the frame tables, on at most as many threads as the context's staging ring has workers
+    FlacVerify verify(checks, checks ? n_songs : 0);
+    FlacVerify* v = checks ? &verify : nullptr;
+    // 1. the frame tables
     std::vector<FlacPlan> plans(n_songs);
     for (uint32_t i = 0; i < n_songs; i++) {
         plans[i].file = (const uint8_t*)files[i];
         plans[i].nbytes = nbytes[i];
     }
-    {
-        const uint32_t workers = std::min<uint32_t>(n_songs, (uint32_t)std::max(1, std::min(c->feed.stage_cfg.lanes, MAX_STAGE_LANES)));
-        std::atomic<uint32_t> next{0};
-        auto work = [&]() {
-            for (uint32_t i; (i = next.fetch_add(1)) < n_songs;) flac_plan(plans[i]);
-        };
-        std::vector<std::thread> pool;
-        for (uint32_t w = 1; w < workers; w++) pool.emplace_back(work);
-        work();
-        for (std::thread& t : pool) t.join();
-    }
+    flac_plan_all(c, plans);
     const float nan = nanf("");
     auto refuse = [&](uint32_t i) {
         for (uint32_t k = 0; k < d; k++) out[(size_t)i * d + k] = nan;
@@ -2553,21 +2649,18 @@ int blissgpu_analyze_batch_flac(const void* const* files, const uint64_t* nbytes
     uint32_t i0 = 0;
     while (i0 < n_songs) {
         std::vector<uint32_t> sel;
-        uint64_t pcm_bytes = 0;
-        uint32_t i1 = i0;
-        for (; i1 < n_songs; i1++) {
-            // a song that does not fit the limit by itself (a few MB of CONSTANT frames can claim hundreds of GB) is refused
-            if (!plans[i1].error && flac_resident_bytes(plans[i1]) > c->ws_limit) plans[i1].error = true;
-            const uint64_t b = plans[i1].error ? 0 : flac_resident_bytes(plans[i1]);
-            if (!sel.empty() && pcm_bytes + b > c->ws_limit) break;
-            pcm_bytes += b;
-            sel.push_back(i1);
-        }
-        if ((rc = flac_run(c, plans, sel, who))) return rc;
+        const uint32_t i1 = flac_next_subbatch(c, plans, i0, &sel);
+        if ((rc = flac_run(c, plans, sel, who, v))) return rc;
         std::vector<uint32_t> good;
         std::vector<uint64_t> offs, lens;
         uint64_t mono = 0;
         for (uint32_t i : sel) {
+            if (v) {
+                if (plans[i].error) v->flags[i] |= BLISSGPU_FLAC_BAD_STREAM;
+                flags[i] = v->flags[i];
+                if (first_bad_frame) first_bad_frame[i] = v->first_bad[i];
+                if (v->flags[i] & 7u) plans[i].error = true;
+            }
             if (plans[i].error) { refuse(i); continue; }
             good.push_back(i);
             offs.push_back(mono);
@@ -2600,6 +2693,88 @@ int blissgpu_analyze_batch_flac(const void* const* files, const uint64_t* nbytes
         }
         i0 = i1;
     }
+    return BLISSGPU_OK;
+}
+
+int blissgpu_analyze_batch_flac(const void* const* files, const uint64_t* nbytes, uint32_t n_songs, uint32_t features_version,
+                                float* out, int32_t* status) {
+    return flac_analyze(files, nbytes, n_songs, features_version, 0, out, status, nullptr, nullptr, "blissgpu_analyze_batch_flac");
+}
+
+int blissgpu_analyze_batch_flac_verified(const void* const* files, const uint64_t* nbytes, uint32_t n_songs, uint32_t features_version,
+                                         uint32_t checks, float* out, int32_t* status, uint32_t* flags, uint32_t* first_bad_frame) {
+    return flac_analyze(files, nbytes, n_songs, features_version, checks, out, status, flags, first_bad_frame,
+                        "blissgpu_analyze_batch_flac_verified");
+}
+
+int blissgpu_flac_verify_batch(const void* const* files, const uint64_t* nbytes, uint32_t n_songs, uint32_t checks, uint32_t* flags,
+                               uint32_t* first_bad_frame, void* md5) {
+    const char* who = "blissgpu_flac_verify_batch";
+    if (n_songs && (!files || !nbytes || !flags)) return fail(BLISSGPU_ERR_INVALID, who, "NULL argument");
+    if (checks & ~(BLISSGPU_FLAC_CHECK_CRC16 | BLISSGPU_FLAC_CHECK_MD5)) return fail(BLISSGPU_ERR_INVALID, who, "unknown check");
+    if (n_songs == 0) return BLISSGPU_OK;
+    FlacDeviceRestore restore;
+    blissgpu_ctx* c;
+    int rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    FlacVerify v(checks, n_songs);
+    std::vector<FlacPlan> plans(n_songs);
+    for (uint32_t i = 0; i < n_songs; i++) {
+        plans[i].file = (const uint8_t*)files[i];
+        plans[i].nbytes = nbytes[i];
+    }
+    flac_plan_all(c, plans);
+    // sub-batch by sub-batch, split like the bulk analysis
+    uint32_t i0 = 0;
+    while (i0 < n_songs) {
+        std::vector<uint32_t> sel;
+        const uint32_t i1 = flac_next_subbatch(c, plans, i0, &sel);
+        if ((rc = flac_run(c, plans, sel, who, &v))) return rc;
+        i0 = i1;
+    }
+    for (uint32_t i = 0; i < n_songs; i++) {
+        flags[i] = v.flags[i] | (plans[i].error ? BLISSGPU_FLAC_BAD_STREAM : 0u);
+        if (first_bad_frame) first_bad_frame[i] = v.first_bad[i];
+    }
+    if (md5) memcpy(md5, v.md5.data(), v.md5.size());
+    return BLISSGPU_OK;
+}
+
+int blissgpu_flac_crc16_device(blissgpu_ctx* c, const void* d_bytes, uint64_t nbytes, const uint64_t* frames, uint64_t n_frames,
+                               const int32_t* d_frame_status, const uint64_t* d_frame_end, int32_t* d_frame_crc_ok) {
+    const char* who = "blissgpu_flac_crc16_device";
+    if (!d_bytes || (n_frames && (!frames || !d_frame_status || !d_frame_end || !d_frame_crc_ok))) return fail(BLISSGPU_ERR_INVALID, who, "NULL argument");
+    if (((uintptr_t)d_bytes & 7) != 0) return fail(BLISSGPU_ERR_INVALID, who, "d_bytes must be 8-byte aligned");
+    if (n_frames > 0x7FFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "bad n_frames");
+    CTX_ENTER(c, who);
+    if (n_frames == 0) return BLISSGPU_OK;
+    std::vector<FlacSong> songs{FlacSong{0, nbytes, 0, 0, 0, 1, 16}};
+    std::vector<FlacFrame> rows((size_t)n_frames);
+    for (uint64_t i = 0; i < n_frames; i++) {
+        const uint64_t* r = frames + 4 * i;
+        if (r[0] > nbytes || r[1] > nbytes - r[0]) return fail(BLISSGPU_ERR_INVALID, who, "a frame row lies outside the file");
+        rows[i] = FlacFrame{r[0], r[1], r[2], (uint32_t)r[3], i + 1 == n_frames ? FLAC_LAST_FRAME : 0u};
+    }
+    const FlacSong* d_songs;
+    const FlacFrame* d_frames;
+    const int rc = flac_upload_tables(c, songs, rows, &d_songs, &d_frames);
+    if (rc) return rc;
+    launch_flac_crc((const uint8_t*)d_bytes, d_songs, d_frames, (uint32_t)n_frames, d_frame_status, d_frame_end, nullptr, nullptr, nullptr,
+                    d_frame_crc_ok, c->stream);
+    HIP_TRY(hipGetLastError());
+    return BLISSGPU_OK;
+}
+
+int blissgpu_flac_md5_device(blissgpu_ctx* c, const void* d_pcm, const uint64_t* info, void* d_md5) {
+    const char* who = "blissgpu_flac_md5_device";
+    if (!info || !d_md5 || (!d_pcm && info[3])) return fail(BLISSGPU_ERR_INVALID, who, "NULL argument");
+    if (((uintptr_t)d_pcm & 3) != 0 || ((uintptr_t)d_md5 & 3) != 0) return fail(BLISSGPU_ERR_INVALID, who, "d_pcm and d_md5 must be 4-byte aligned");
+    // (a stream codes its total in 36 bits: with 8 channels and 4 bytes per element every size below stays far inside 64 bits)
+    if (info[1] < 1 || info[1] > 8 || info[2] < 4 || info[2] > 24 || info[3] >> 36) return fail(BLISSGPU_ERR_INVALID, who, "bad info");
+    CTX_ENTER(c, who);
+    launch_flac_md5_one((const uint8_t*)d_pcm, FlacMd5Job{0, info[3] * info[1], (uint32_t)info[2], 0}, d_md5, c->stream);
+    HIP_TRY(hipGetLastError());
     return BLISSGPU_OK;
 }
 

@@ -283,6 +283,10 @@ struct blissgpu_ctx {
     bg::DevBuf<uint64_t> fl_end;
     bg::DevBuf<uint32_t> fl_bad;
     bg::DevBuf<float> fl_mono, fl_rows;
+    // the opt-in checks (kernels_flac_verify.hip): per song [first row | CRC flag | first bad frame], MD5 jobs, digests
+    bg::DevBuf<uint32_t> fl_vsong;
+    bg::DevBuf<bg::FlacMd5Job> fl_md5_jobs;
+    bg::DevBuf<uint8_t> fl_md5;
     bg::PinnedBuf<uint8_t> fl_htab;                // page-locked staging of fl_tab
     hipEvent_t fl_ev = nullptr;                    // the last upload from fl_htab has left it
     uint64_t fl_slow_songs = 0;                    // songs whose fast frame table the device refused (verified mode + a second launch)

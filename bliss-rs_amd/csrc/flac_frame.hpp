@@ -11,8 +11,9 @@
 //             is written outside the frame's own blocksize x channels region, clipped to the stream's total.
 //   * loops   every loop runs to the block size, a partition count (each turn consumes bits) or the frame's end; a unary run
 //             stops at the frame's last bit.  Once the reader has been refused a bit it stays refused and the loops wind down.
-// A violation is a frame status, never a fault.  Not checked here: CRC-8, CRC-16, the stream MD5 (flac_index.hpp checks the
-// CRCs on the host when asked to; the tests check the MD5).
+// A violation is a frame status, never a fault.  Not checked here: CRC-8, CRC-16, the stream MD5.  flac_index.hpp checks the
+// CRCs on the host when asked to; on the device the CRC-16 and the MD5 are flac_verify.hpp's (flac_crc_kernel and
+// flac_md5_kernel, kernels_flac_verify.hip), run when a caller asks for them.
 //
 // Prediction sums are 64-bit for every subframe (one v_mad_i64_i32 per tap on gfx950): exact for every valid stream, and
 // equal to libFLAC's 32-bit path wherever the format allows that path.

@@ -237,6 +237,20 @@ void launch_flac_decode(const uint8_t* bytes, const FlacSong* songs, const FlacF
 // earlier (an ID3v1 tag or padding behind the audio).  song_bad is zeroed by the caller
 void launch_flac_check(const FlacFrame* frames, uint32_t n_frames, const int32_t* status, const uint64_t* end, uint32_t* song_bad,
                        hipStream_t st);
+// The opt-in checks (kernels_flac_verify.hip; the arithmetic is flac_verify.hpp).  CRC-16 of every frame with status FRAME_OK
+// over [offset, end[i]), one wavefront per frame, against the two bytes at end[i].  A mismatch sets song_crc_bad[s] and takes
+// song_first_bad[s] down to the frame's index within its song, i - song_first[s] (song_crc_bad zeroed, song_first_bad set to
+// 0xFFFFFFFF by the caller; the three may be NULL together).  frame_ok (may be NULL): 1, 0, or -1 for a frame that was not OK
+void launch_flac_crc(const uint8_t* bytes, const FlacSong* songs, const FlacFrame* frames, uint32_t n_frames, const int32_t* status,
+                     const uint64_t* end, const uint32_t* song_first, uint32_t* song_crc_bad, uint32_t* song_first_bad, int32_t* frame_ok,
+                     hipStream_t st);
+struct FlacMd5Job {      // one song of flac_md5_kernel, one lane
+    uint64_t pcm_off;    // its first byte in the PCM (a multiple of 4)
+    uint64_t n_elems;    // total x channels: int16 up to 16 bits per sample, int32 above
+    uint32_t bps, slot;  // digests[16 * slot .. + 16) receives the MD5 of the FLAC message
+};
+void launch_flac_md5(const uint8_t* pcm, const FlacMd5Job* jobs, uint32_t n_jobs, void* digests, hipStream_t st);
+void launch_flac_md5_one(const uint8_t* pcm, const FlacMd5Job& job, void* digests, hipStream_t st);  // the job travels with the launch
 // one pair distance with both vectors passed by value (no staging copies); result -> *out (device-visible host word)
 void launch_pair_distance(const float* a, const float* b, uint32_t d, int metric, const float* d_M, float* out, hipStream_t st);
 // playlist ordering (kernels_playlist.hip)

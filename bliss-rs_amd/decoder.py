@@ -159,7 +159,8 @@ class FlacDecoder(Decoder):
     album, album_artist, track_number, disc_number and genre as the reference's FFmpeg decoder fills them
     (src/song/decoder/ffmpeg.rs:200-247; FFmpeg names TRACKNUMBER / DISCNUMBER / ALBUMARTIST track / disc / album_artist), the
     duration from STREAMINFO -- and keeps the COMPRESSED bytes in the PreAnalyzedSong.  `analyze_paths_with_options` sends
-    batches of compressed files through `analyze_flac_batch`: no residual is ever decoded on the CPU."""
+    batches of compressed files through `analyze_flac_batch`: no residual is ever decoded on the CPU.  `verify_paths` is
+    `flac -t` for a library: every frame's CRC-16 and the stream's MD5, checked on the device."""
 
     _KEYS = {"tracknumber": "track", "discnumber": "disc", "albumartist": "album_artist"}
 
@@ -225,28 +226,54 @@ class FlacDecoder(Decoder):
 
     @classmethod
     def analyze_paths_with_options(cls, paths: Iterable[str], analysis_options: AnalysisOptions,
-                                   batch_songs: int = 256) -> Iterator[Tuple[str, Union[Song, BlissError]]]:
+                                   batch_songs: int = 256, verify=None) -> Iterator[Tuple[str, Union[Song, BlissError]]]:
         """Yields (path, Song | BlissError), batches of compressed files at a time; a bad file yields its DecodingError and
-        never aborts the run (src/song/decoder.rs:313-325)."""
+        never aborts the run (src/song/decoder.rs:313-325).
+        verify: None | "crc" | "md5" -- also check every frame's CRC-16 (and the stream's MD5) on the device
+        (`analyze_flac_batch`); a song that fails yields a DecodingError that names the file, the check and the frame, e.g.
+        "... CRC-16 mismatch in frame 17", and the results keep the order of the paths."""
         version = FeaturesVersion(analysis_options.features_version)
-        pending = []
+        pending = []   # PreAnalyzedSong, or -- with verify -- the (path, error) of a file that could not be opened
 
         def flush():
-            results = analyze_flac_batch([p.flac for p in pending], analysis_options)
-            for pre, res in zip(pending, results):
+            songs = [p for p in pending if isinstance(p, PreAnalyzedSong)]
+            results = iter(analyze_flac_batch([p.flac for p in songs], analysis_options, verify=verify))
+            for pre in pending:
+                if not isinstance(pre, PreAnalyzedSong):
+                    yield pre
+                    continue
+                res = next(results)
+                if isinstance(res, DecodingError) and verify is not None:
+                    named = DecodingError(f"while decoding file '{pre.path}': {res.message}")
+                    named.flags, named.first_bad_frame = res.flags, res.first_bad_frame
+                    res = named
                 yield pre.path, (res if isinstance(res, BlissError) else pre._song(res, version))
             pending.clear()
 
         for path in paths:
             try:
                 pending.append(cls.decode(path))
-            except BlissError as e:
-                yield path, e
-                continue
             except Exception as e:
-                yield path, DecodingError(str(e))
-                continue
+                error = e if isinstance(e, BlissError) else DecodingError(str(e))
+                if verify is None:
+                    yield path, error
+                    continue
+                pending.append((path, error))
             if len(pending) >= batch_songs:
                 yield from flush()
         if pending:
             yield from flush()
+
+    @classmethod
+    def verify_paths(cls, paths: Iterable[str], md5: bool = True, batch_songs: int = 256):
+        """Yields (path, FlacVerdict), batches of files at a time (`flac_verify_batch`): no analysis, a verdict per file."""
+        from .song import flac_verify_batch
+
+        pending = []
+        for path in paths:
+            pending.append(path)
+            if len(pending) >= batch_songs:
+                yield from zip(pending, flac_verify_batch(pending, md5=md5))
+                pending = []
+        if pending:
+            yield from zip(pending, flac_verify_batch(pending, md5=md5))

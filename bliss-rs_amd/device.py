@@ -310,6 +310,50 @@ class Context:
             return self.flac_decode(host, verified=True)
         return out, int(info[0])
 
+    def flac_crc16(self, data, table, status, end):
+        """The CRC-16 of every frame of ONE file on the device (flac_crc_kernel, one wavefront per frame): data -- the file
+        (bytes, a uint8 array, or a path); table / status / end as `flac_decode(data, return_frames=True)` returned them.
+        -> int32 tensor per frame: 1 = the CRC over [offset, end) equals the two bytes at end, 0 = it does not, -1 = the
+        frame's status is not 0 (blissgpu_flac_crc16_device)."""
+        torch = self.torch
+        if isinstance(data, (str, os.PathLike)):
+            with open(data, "rb") as f:
+                data = f.read()
+        host = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
+        nbytes = int(host.size)
+        d_bytes = torch.zeros(((nbytes + 16 + 7) // 8) * 8, dtype=torch.uint8, device=status.device)
+        d_bytes[:nbytes] = torch.from_numpy(host.copy()).to(status.device)
+        table = np.ascontiguousarray(table, np.uint64).reshape(-1, 4)
+        nf = int(table.shape[0])
+        status = status.contiguous()
+        end = end.contiguous()
+        assert status.dtype == torch.int32 and end.dtype == torch.int64 and status.numel() >= nf and end.numel() >= nf
+        ok = torch.full((max(1, nf),), -2, dtype=torch.int32, device=d_bytes.device)
+        self._pre()
+        _ffi.check(self._L.blissgpu_flac_crc16_device(self._h, C.c_void_p(d_bytes.data_ptr()), int(nbytes),
+                                                      table.ctypes.data_as(C.POINTER(C.c_uint64)), nf, C.c_void_p(status.data_ptr()),
+                                                      C.c_void_p(end.data_ptr()), C.c_void_p(ok.data_ptr())))
+        self._post()
+        return ok[:nf]
+
+    def flac_md5(self, pcm, bps: int) -> str:
+        """The MD5 FLAC defines over the decoded audio, computed on the device by one lane (flac_md5_kernel): pcm -- what
+        `flac_decode` returned, [frames, channels] or 1-D, int16 (sample << (16 - bps)) or int32 (sample << (32 - bps)).
+        -> the digest as hex, comparable to STREAMINFO's (blissgpu_flac_md5_device)."""
+        torch = self.torch
+        pcm = pcm.contiguous()
+        assert pcm.is_cuda and pcm.dtype == (torch.int32 if bps > 16 else torch.int16) and 4 <= bps <= 24
+        frames = int(pcm.shape[0])
+        channels = 1 if pcm.dim() == 1 else int(pcm.shape[1])
+        info = np.zeros(_ffi.FLAC_INFO_WORDS, np.uint64)
+        info[1], info[2], info[3] = channels, bps, frames
+        out = torch.zeros(16, dtype=torch.uint8, device=pcm.device)
+        self._pre()
+        _ffi.check(self._L.blissgpu_flac_md5_device(self._h, C.c_void_p(pcm.data_ptr() if pcm.numel() else 0), info.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                    C.c_void_p(out.data_ptr())))
+        self._post()
+        return bytes(out.cpu().numpy().tobytes()).hex()
+
     # ---- playlist ordering on device-resident feature matrices (src/playlist.rs:24-59, 256-326) ----
     def _pl_args(self, seeds, cand, M):
         torch = self.torch

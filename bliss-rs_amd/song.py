@@ -234,11 +234,30 @@ def _file_bytes(item) -> np.ndarray:
         return np.zeros(0, np.uint8)   # an unreadable file is a DecodingError of that song, like any other bad file
 
 
-def analyze_flac_batch(files, options: Optional[AnalysisOptions] = None):
+_FLAC_CHECKS = {None: 0, "crc": _ffi.FLAC_CHECK_CRC16, "md5": _ffi.FLAC_CHECK_CRC16 | _ffi.FLAC_CHECK_MD5}
+
+
+def _flac_failure(flags: int, first_bad_frame: int) -> str:
+    """the message of a DecodingError that names the check and the frame"""
+    if flags & _ffi.FLAC_BAD_STREAM:
+        return "the FLAC stream cannot be decoded"
+    if flags & _ffi.FLAC_BAD_CRC16:
+        return f"the FLAC stream is damaged: CRC-16 mismatch in frame {first_bad_frame}"
+    return "the FLAC stream is damaged: the MD5 of the decoded audio is not STREAMINFO's"
+
+
+def analyze_flac_batch(files, options: Optional[AnalysisOptions] = None, verify: Optional[str] = None):
     """Compressed .flac files (bytes, uint8 arrays or paths) -> one Analysis or BlissError per file.  The host only finds the
     frames; the FLAC decoding, the conversion to mono 22 050 Hz and the analysis all run on the device
     (blissgpu_analyze_batch_flac).  A file that is not FLAC, has an unsupported depth, is truncated or holds a frame that cannot
-    be decoded yields DecodingError and leaves every other song of the call untouched."""
+    be decoded yields DecodingError and leaves every other song of the call untouched.
+    verify: None -- the structure only (every frame stops 2 bytes before the next); "crc" -- also every frame's CRC-16, checked
+    on the device; "md5" -- the CRC-16 and the MD5 of the decoded audio against STREAMINFO's (one lane per song: slow for long
+    songs, a "check my library" mode).  A song that fails a check yields a DecodingError that names the check and the frame
+    (its `flags` / `first_bad_frame` attributes hold the verdict); every other row is bit-identical to the unverified call's."""
+    if verify not in _FLAC_CHECKS:
+        raise ValueError('verify is None, "crc" or "md5"')
+    checks = _FLAC_CHECKS[verify]
     options = options or AnalysisOptions()
     version = FeaturesVersion(options.features_version)
     blobs = [_file_bytes(f) for f in files]
@@ -251,13 +270,75 @@ def analyze_flac_batch(files, options: Optional[AnalysisOptions] = None):
     keep = [b if b.size else np.zeros(1, np.uint8) for b in blobs]
     ptrs = (C.c_void_p * n)(*[k.ctypes.data for k in keep])
     sizes = np.array([b.size for b in blobs], np.uint64)
-    _ffi.check(_ffi.lib().blissgpu_analyze_batch_flac(ptrs, sizes.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(version),
-                                                      out.ctypes.data, status.ctypes.data_as(C.POINTER(C.c_int32))))
+    flags = np.zeros(n, np.uint32)
+    first_bad = np.full(n, 0xFFFFFFFF, np.uint32)
+    if checks:
+        u32p = C.POINTER(C.c_uint32)
+        _ffi.check(_ffi.lib().blissgpu_analyze_batch_flac_verified(
+            ptrs, sizes.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(version), checks, out.ctypes.data,
+            status.ctypes.data_as(C.POINTER(C.c_int32)), flags.ctypes.data_as(u32p), first_bad.ctypes.data_as(u32p)))
+    else:
+        _ffi.check(_ffi.lib().blissgpu_analyze_batch_flac(ptrs, sizes.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(version),
+                                                          out.ctypes.data, status.ctypes.data_as(C.POINTER(C.c_int32))))
     results = _results(out, status, version)
     for i in range(n):
         if status[i] == _ffi.SONG_DECODE_ERROR:
-            results[i] = DecodingError("the FLAC stream cannot be decoded")
+            # (no check failed -- none was asked for, or the song decoded and the analysis refused it: the stream is what is bad)
+            verdict = int(flags[i]) if checks and int(flags[i]) & 7 else int(flags[i]) | _ffi.FLAC_BAD_STREAM
+            results[i] = DecodingError(_flac_failure(verdict, int(first_bad[i])))
+            results[i].flags = verdict
+            results[i].first_bad_frame = int(first_bad[i]) if first_bad[i] != 0xFFFFFFFF else None
     return results
+
+
+@dataclass
+class FlacVerdict:
+    """What the device found in one .flac file (flac_verify_batch)."""
+    flags: int                      # BLISSGPU_FLAC_BAD_STREAM | _BAD_CRC16 | _BAD_MD5 | _MD5_UNCHECKED
+    first_bad_frame: Optional[int]  # the first frame whose CRC-16 failed
+    md5: Optional[str]              # the digest of the decoded audio (hex), None when it was not computed
+
+    @property
+    def ok(self) -> bool:
+        return (self.flags & 7) == 0
+
+    @property
+    def stream_ok(self) -> bool:
+        return not self.flags & _ffi.FLAC_BAD_STREAM
+
+    @property
+    def crc_ok(self) -> bool:
+        return self.stream_ok and not self.flags & _ffi.FLAC_BAD_CRC16
+
+    @property
+    def md5_state(self) -> str:
+        if self.flags & _ffi.FLAC_BAD_MD5:
+            return "mismatch"
+        return "unchecked" if self.flags & _ffi.FLAC_MD5_UNCHECKED else "match"
+
+
+def flac_verify_batch(files, md5: bool = True):
+    """`flac -t` for a batch of .flac files (bytes, uint8 arrays or paths), on the device: index, upload, decode, the
+    end-position check, every frame's CRC-16 and -- md5=True -- the MD5 of the decoded audio against STREAMINFO's; no
+    analysis.  One FlacVerdict per file; one bad file never affects another (blissgpu_flac_verify_batch).  The MD5 runs one
+    lane per song and is slow for long songs."""
+    blobs = [_file_bytes(f) for f in files]
+    n = len(blobs)
+    if n == 0:
+        return []
+    keep = [b if b.size else np.zeros(1, np.uint8) for b in blobs]
+    ptrs = (C.c_void_p * n)(*[k.ctypes.data for k in keep])
+    sizes = np.array([b.size for b in blobs], np.uint64)
+    flags = np.zeros(n, np.uint32)
+    first_bad = np.zeros(n, np.uint32)
+    digests = np.zeros((n, 16), np.uint8)
+    u32p = C.POINTER(C.c_uint32)
+    checks = _ffi.FLAC_CHECK_CRC16 | (_ffi.FLAC_CHECK_MD5 if md5 else 0)
+    _ffi.check(_ffi.lib().blissgpu_flac_verify_batch(ptrs, sizes.ctypes.data_as(C.POINTER(C.c_uint64)), n, checks, flags.ctypes.data_as(u32p),
+                                                     first_bad.ctypes.data_as(u32p), C.c_void_p(digests.ctypes.data)))
+    computed = (flags & (_ffi.FLAC_MD5_UNCHECKED | _ffi.FLAC_BAD_STREAM)) == 0
+    return [FlacVerdict(int(f), int(b) if b != 0xFFFFFFFF else None, d.tobytes().hex() if c else None)
+            for f, b, d, c in zip(flags, first_bad, digests, computed)]
 
 
 def flac_decode_batch(files):

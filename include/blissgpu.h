@@ -245,7 +245,8 @@ int blissgpu_pcm_decode_device(blissgpu_ctx *ctx, const void *d_in, int sample_f
  * int32, sample << (32 - bps).  Bit for bit -- FLAC is lossless and the stream's MD5 says so.  Handled: CONSTANT / VERBATIM /
  * FIXED 0-4 / LPC 1-32 subframes, wasted bits, both Rice methods, escape partitions, every channel assignment, 1-8 channels,
  * 4-24 bits per sample.  32 bits per sample and Ogg-FLAC are reported as decode errors.
- * NOT checked on the hot path: CRC-16 (fast index mode) and the stream MD5.
+ * The default calls check the structure only (every frame stops 2 bytes before the next).  The frame CRC-16 and the stream
+ * MD5 are checked on the device when asked for: blissgpu_flac_verify_batch, blissgpu_analyze_batch_flac_verified (below).
  *
  * info: BLISSGPU_FLAC_INFO_WORDS 64-bit words -- [0] sample rate, [1] channels, [2] bits per sample, [3] total inter-channel
  * samples (0 = unknown in STREAMINFO; blissgpu_flac_index and blissgpu_flac_decode replace it by the count the frame table
@@ -293,6 +294,42 @@ int blissgpu_analyze_batch_flac(const void *const *files, const uint64_t *nbytes
 /* Songs of this context whose fast frame table the device refused, or could not be closed on the host: they went through
  * verified mode (statistics). */
 uint64_t blissgpu_ctx_flac_slow_songs(blissgpu_ctx *ctx);
+
+/* ---- FLAC verified ON THE DEVICE (opt-in): every frame's CRC-16, the stream's MD5, a verdict per song ----
+ * checks: what to verify beyond the structure.  CRC16: flac_crc_kernel, one wavefront per frame, over the frame from its first
+ * header byte to the decoder's own stop position, against the two bytes there.  MD5: flac_md5_kernel, one lane per song, the
+ * digest of the decoded samples (interleaved, little-endian, ceil(bps / 8) bytes each) against STREAMINFO's -- a serial chain
+ * per song and slow for long songs (DESIGN.md section 3.19 has the figures): a "check my library" mode. */
+#define BLISSGPU_FLAC_CHECK_CRC16 1u
+#define BLISSGPU_FLAC_CHECK_MD5   2u
+/* verdict flags; a song failed when (flags & 7) != 0 */
+#define BLISSGPU_FLAC_BAD_STREAM    1u  /* what is BLISSGPU_SONG_DECODE_ERROR in the unverified calls */
+#define BLISSGPU_FLAC_BAD_CRC16     2u
+#define BLISSGPU_FLAC_BAD_MD5       4u
+#define BLISSGPU_FLAC_MD5_UNCHECKED 8u  /* informational: the MD5 check was not asked for, STREAMINFO's MD5 is all zero, the
+                                         * stream was cut out of a longer one (info[10] != 0), the frame table's sample count
+                                         * differs from a nonzero STREAMINFO total, or an earlier check of the song failed */
+/* Index, upload, decode, the end-position check and the requested checks of n_songs files, no analysis ("flac -t" for a
+ * library, in batches); split by the workspace limit like blissgpu_analyze_batch_flac; one bad file never affects another
+ * song.  flags[i]: the verdict; first_bad_frame[i] (may be NULL): the first frame of song i whose CRC-16 failed, 0xFFFFFFFF
+ * when none; md5 (may be NULL): 16 bytes per song, the computed digest, zeros when it was not computed. */
+int blissgpu_flac_verify_batch(const void *const *files, const uint64_t *nbytes, uint32_t n_songs, uint32_t checks,
+                               uint32_t *flags, uint32_t *first_bad_frame, void *md5);
+/* blissgpu_analyze_batch_flac plus the checks: a song that fails one gets BLISSGPU_SONG_DECODE_ERROR and a NaN row, every
+ * other row is bit-identical to the unverified call's.  checks = 0 is the unverified call (flags / first_bad_frame are not
+ * written and may be NULL). */
+int blissgpu_analyze_batch_flac_verified(const void *const *files, const uint64_t *nbytes, uint32_t n_songs,
+                                         uint32_t features_version, uint32_t checks, float *out, int32_t *status,
+                                         uint32_t *flags, uint32_t *first_bad_frame);
+/* Device to device, asynchronous on the context's stream, ONE file, beside blissgpu_flac_decode_device: d_bytes / frames as
+ * there, d_frame_status / d_frame_end as it wrote them.  d_frame_crc_ok[i] = 1 (the CRC-16 over [offset, end) equals the two
+ * bytes at end), 0 (it does not, or end does not lie inside the row), -1 (the frame's status is not 0: not checked). */
+int blissgpu_flac_crc16_device(blissgpu_ctx *ctx, const void *d_bytes, uint64_t nbytes, const uint64_t *frames, uint64_t n_frames,
+                               const int32_t *d_frame_status, const uint64_t *d_frame_end, int32_t *d_frame_crc_ok);
+/* d_md5 (16 bytes on the device) = the MD5 of the FLAC message of d_pcm: info[3] inter-channel samples of info[1] channels,
+ * int16 (info[2] <= 16 bits per sample) or int32, as blissgpu_flac_decode_device wrote them; d_pcm and d_md5 are 4-byte aligned,
+ * info[3] is below 2^36 (what STREAMINFO can code). */
+int blissgpu_flac_md5_device(blissgpu_ctx *ctx, const void *d_pcm, const uint64_t *info, void *d_md5);
 
 /* Device-resident form: d_pcm / d_out / d_status are HIP device pointers (d_status may be NULL),
  * offsets / lengths stay on the host (they size the launch).  Asynchronous on the context's
