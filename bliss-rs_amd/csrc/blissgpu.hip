@@ -25,6 +25,7 @@ thread_local std::string g_last_error;
 // (the names of KX_SEGMENT_MEAN and KX_ALBUM_KNN_SCAN, the ids numbered behind the KernelId list: see internal.hpp)
 const char kSegmentMeanName[] = "segment_mean_kernel", kAlbumKnnScanName[] = "album_knn_scan_kernel";
 const char kGroupForestScanName[] = "group_forest_scan_kernel";  // KX_GROUP_FOREST_SCAN
+const char kJourneyStepName[] = "journey_step_kernel";  // KX_JOURNEY_STEP
 const char* const kKernelNames[K_COUNT] = {
     "fft512_kernel",     "onset_kernel",      "beat_kernel",   "stft8192_kernel", "tune_select_kernel",
     "tune_pass2_kernel", "tune_final_kernel", "chroma_kernel",     "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel", "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel",
@@ -33,7 +34,7 @@ const char* const kKernelNames[K_COUNT] = {
     "dup_init_kernel", "dup_join_kernel", "dup_flatten_kernel",
     "group_knn_scan_kernel", "group_knn_merge_kernel", "group_weights_kernel",
     "chain_step_kernel", "chain_walk_kernel",
-    kSegmentMeanName, kAlbumKnnScanName, kGroupForestScanName};
+    kSegmentMeanName, kAlbumKnnScanName, kGroupForestScanName, kJourneyStepName};
 }  // namespace
 
 namespace bg {
@@ -1656,6 +1657,122 @@ int blissgpu_chains(const float* seeds, const uint64_t* group_offsets, uint64_t 
         if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(chains)", hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+// ---- journeys: waypoint and directed song-to-song playlists (kernels_chains.hip): the chains' steps with a
+// step 0 of their own, a waypoint query or a gate on one feature ----
+// everything that can be said about the arguments without a device (both forms check it BEFORE the device is touched)
+static int journeys_args_ok(const char* who, const void* from, const void* to, uint64_t n_journeys, const void* cand, uint64_t n,
+                            uint32_t d, int metric, const float* M, uint32_t k, int mode, int gate, uint32_t gate_feature,
+                            const void* idx) {
+    if (k == 0 || k > BLISSGPU_KNN_MAX_K) return fail(BLISSGPU_ERR_INVALID, who, "k must be 1 .. BLISSGPU_KNN_MAX_K");
+    if (d == 0 || d > 64) return fail(BLISSGPU_ERR_INVALID, who, "d must be 1 .. 64");
+    if (metric < 0 || metric > 2) return fail(BLISSGPU_ERR_INVALID, who, "unknown metric");
+    if (metric == BLISSGPU_METRIC_MAHALANOBIS && !M) return fail(BLISSGPU_ERR_INVALID, who, "mahalanobis needs M");
+    if (n >= 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "n must be below 2^32 - 1 candidates");
+    if (n_journeys >= 0x80000000ull) return fail(BLISSGPU_ERR_INVALID, who, "n_journeys must be below 2^31");
+    if (mode != BLISSGPU_JOURNEY_CHAIN && mode != BLISSGPU_JOURNEY_WAYPOINT) return fail(BLISSGPU_ERR_INVALID, who, "unknown mode");
+    if (gate != BLISSGPU_GATE_NONE && gate != BLISSGPU_GATE_UP && gate != BLISSGPU_GATE_DOWN)
+        return fail(BLISSGPU_ERR_INVALID, who, "unknown gate");
+    if (gate != BLISSGPU_GATE_NONE && mode == BLISSGPU_JOURNEY_WAYPOINT)
+        return fail(BLISSGPU_ERR_INVALID, who, "a gate cannot be combined with the waypoint mode");
+    if (gate != BLISSGPU_GATE_NONE && gate_feature >= d) return fail(BLISSGPU_ERR_INVALID, who, "gate_feature must be below d");
+    if (mode == BLISSGPU_JOURNEY_WAYPOINT && !to) return fail(BLISSGPU_ERR_INVALID, who, "the waypoint mode needs to");
+    if (mode != BLISSGPU_JOURNEY_WAYPOINT && to) return fail(BLISSGPU_ERR_INVALID, who, "to must be NULL unless the mode is waypoint");
+    if (n_journeys == 0) return BLISSGPU_OK;
+    if (!from) return fail(BLISSGPU_ERR_INVALID, who, "from is NULL");
+    if (n && !cand) return fail(BLISSGPU_ERR_INVALID, who, "cand is NULL");
+    if (!idx) return fail(BLISSGPU_ERR_INVALID, who, "idx is NULL");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_journeys_device(blissgpu_ctx* c, const float* d_from, const float* d_to, uint64_t n_journeys, const float* d_cand,
+                             uint64_t n, uint32_t d, int metric, const float* d_M, const uint32_t* d_skip, uint32_t k, int mode,
+                             int gate, uint32_t gate_feature, uint32_t* d_idx, float* d_dist) {
+    const char* who = "blissgpu_journeys_device";
+    int rc = journeys_args_ok(who, d_from, d_to, n_journeys, d_cand, n, d, metric, d_M, k, mode, gate, gate_feature, d_idx);
+    if (rc) return rc;
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    if (n_journeys == 0) return BLISSGPU_OK;
+    CTX_ENTER(c, who);
+    int diag = 0;
+    if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
+        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
+            diag = is_diag(c->m_cache.data(), d);
+        } else {
+            std::vector<float> hM((size_t)d * d);
+            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            diag = is_diag(hM.data(), d);
+        }
+    }
+    // pl_chain: minima u64[G] | flags u32[4] ([0] NaN on a journey)
+    const size_t G = (size_t)n_journeys, out_n = G * k;
+    rc = c->pl_chain.ensure(G * sizeof(unsigned long long) + 4 * sizeof(uint32_t));
+    if (rc) return rc;
+    unsigned long long* best = reinterpret_cast<unsigned long long*>(c->pl_chain.p);
+    uint32_t* flags = reinterpret_cast<uint32_t*>(c->pl_chain.p + G * sizeof(unsigned long long));
+    // every row: 0xFFFFFFFF / +inf until a step writes it
+    HIP_TRY(hipMemsetAsync(d_idx, 0xFF, out_n * sizeof(uint32_t), c->stream));
+    if (d_dist) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_dist, 0x7F800000, out_n, c->stream));
+    HIP_TRY(hipMemsetAsync(flags, 0, 4 * sizeof(uint32_t), c->stream));
+    HIP_TRY(hipMemsetAsync(best, 0xFF, G * sizeof(unsigned long long), c->stream));
+    const ChainPlan plan = chain_plan(n_journeys, n, c->n_cus);
+    const uint32_t steps = (uint32_t)std::min<uint64_t>(k, n);  // (a journey is no longer than the candidates)
+    for (uint32_t t = 0; t < steps; t++) {
+        const JourneyStep j{d_from, d_to, (float)(t + 1u) / (float)(k + 1u), gate, gate != BLISSGPU_GATE_NONE ? gate_feature : 0u};
+        Prof p(c, KX_JOURNEY_STEP);
+        launch_journey_step(d_cand, (uint32_t)n, d, metric, d_M, diag, d_skip, (uint32_t)n_journeys, k, t, plan, j, d_idx, d_dist, best,
+                            flags, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    uint32_t h_flags[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (h_flags[0]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_journeys(const float* from, const float* to, uint64_t n_journeys, const float* cand, uint64_t n, uint32_t d, int metric,
+                      const float* M, const uint32_t* skip, uint32_t k, int mode, int gate, uint32_t gate_feature, uint32_t* idx,
+                      float* dist) {
+    const char* who = "blissgpu_journeys";
+    int rc = journeys_args_ok(who, from, to, n_journeys, cand, n, d, metric, M, k, mode, gate, gate_feature, idx);
+    if (rc) return rc;
+    if (n_journeys == 0) return BLISSGPU_OK;
+    if (skip)
+        for (uint64_t i = 0; i < 2 * n_journeys; i++)
+            if (skip[i] != 0xFFFFFFFFu && skip[i] >= n) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    const size_t G = (size_t)n_journeys, out_n = G * k, row_n = G * d;
+    const float* dM = nullptr;
+    rc = c->st_b.ensure(std::max<size_t>(1, n * d));
+    if (!rc) rc = c->st_a.ensure(row_n * (to ? 2 : 1));  // from, then to
+    if (!rc) rc = c->st_idx.ensure(out_n + (skip ? 2 * G : 0));
+    if (!rc && dist) rc = c->st_dist.ensure(out_n);
+    if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
+    if (rc) return rc;
+    uint32_t *d_idx = c->st_idx.p, *d_skip = skip ? c->st_idx.p + out_n : nullptr;
+    hipError_t e = hipSuccess;
+    if (n) e = hipMemcpyAsync(c->st_b.p, cand, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->st_a.p, from, row_n * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && to) e = hipMemcpyAsync(c->st_a.p + row_n, to, row_n * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && skip) e = hipMemcpyAsync(d_skip, skip, 2 * G * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(journeys)", hipGetErrorString(e));
+    if (!rc)
+        rc = blissgpu_journeys_device(c, c->st_a.p, to ? c->st_a.p + row_n : nullptr, n_journeys, c->st_b.p, n, d, metric, dM, d_skip, k,
+                                      mode, gate, gate_feature, d_idx, dist ? c->st_dist.p : nullptr);
+    if (!rc) {
+        e = hipMemcpyAsync(idx, d_idx, out_n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(journeys)", hipGetErrorString(e));
     }
     (void)hipStreamSynchronize(c->stream);
     return rc;

@@ -123,13 +123,15 @@ enum KernelId : int {
     K_CHAIN_STEP, K_CHAIN_WALK,             // song-to-song chains cut after k (kernels_chains.hip)
     // (tests/test_chains_host.py holds this list, and the list of names beside it, to end in the chain kernels: the kernels
     // that came later are numbered behind it, so that no older id or name moves)
-    K_COUNT = K_CHAIN_WALK + 4
+    K_COUNT = K_CHAIN_WALK + 5
 };
 // k-nearest albums per seed group (kernels_albums.hip; its partial lists are merged by knn_merge_kernel)
 constexpr int KX_SEGMENT_MEAN = K_CHAIN_WALK + 1, KX_ALBUM_KNN_SCAN = K_CHAIN_WALK + 2;
 // the k lowest forest scores per seed group (kernels_forest.hip; its partial lists are merged by group_knn_merge_kernel)
 constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 3;
-static_assert(KX_GROUP_FOREST_SCAN + 1 == K_COUNT, "every kernel id is below the count");
+// a journey's step (kernels_chains.hip: the chains' scan with a waypoint query or a gate)
+constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 4;
+static_assert(KX_JOURNEY_STEP + 1 == K_COUNT, "every kernel id is below the count");
 
 // lower_bound on a prefix array: largest s with prefix[s] <= x  (prefix has n+1 entries, prefix[0]=0)
 __device__ __forceinline__ uint32_t find_segment(const uint32_t* __restrict__ prefix, uint32_t n, uint32_t x) {
@@ -342,6 +344,21 @@ ChainPlan chain_plan(uint64_t n_chains, uint64_t n, int n_cus);
 void launch_chain_step(const float* X, uint32_t n, uint32_t d, int metric, const float* M, int m_is_diag, const uint32_t* goff,
                        const uint32_t* skip, uint32_t n_chains, uint32_t k, uint32_t t, const ChainPlan& p, uint32_t* idx,
                        float* dist, unsigned long long* best, uint32_t* nan_flag, hipStream_t st);
+// journeys (kernels_chains.hip): chains with a step 0 of their own (the query is the journey's `from` row), two skip slots each
+// (skip[n_journeys][2] or NULL) and either a waypoint query -- to != NULL: step t looks around from + (to - from) * s -- or a
+// gate on one feature against the previous pick (GATE_*, the values of BLISSGPU_GATE_*).  Step t >= 0 writes idx / dist
+// [journey][t] like a chains' step; a journey whose step finds no eligible candidate keeps its padding from there on
+constexpr int GATE_NONE = 0, GATE_UP = 1, GATE_DOWN = 2;
+struct JourneyStep {
+    const float* from;      // [n_journeys][d]
+    const float* to;        // [n_journeys][d], NULL: the query is the previous pick
+    float s;                // (t + 1) / (k + 1), rounded once on the host
+    int gate;               // GATE_*
+    uint32_t gate_feature;  // < d
+};
+void launch_journey_step(const float* X, uint32_t n, uint32_t d, int metric, const float* M, int m_is_diag, const uint32_t* skip,
+                         uint32_t n_journeys, uint32_t k, uint32_t t, const ChainPlan& p, const JourneyStep& j, uint32_t* idx,
+                         float* dist, unsigned long long* best, uint32_t* nan_flag, hipStream_t st);
 // column 0 of idx / dist from step 0's [n_chains] arrays
 void launch_chain_first(const uint32_t* idx0, const float* dist0, uint32_t n_chains, uint32_t k, uint32_t* idx, float* dist,
                         hipStream_t st);

@@ -16,6 +16,10 @@
 //                       per chain block the winner goes straight to idx / dist; when several workgroups share the candidates
 //                       (few chains), each sends its minimum to best[chain] with a 64-bit atomicMin and chain_put_kernel -- the
 //                       second and last launch of the step -- writes it out.
+//   journey_step_kernel the same scan for JOURNEYS (blissgpu_journeys): waypoint playlists ("from song1 to song2 in
+//                       n songs, without repetitions") and directed ones ("the tempo goes down or stays the same"), which the
+//                       reference's TODO.md names and does not ship.  A journey is a chain with a step 0 of its own, two skip
+//                       slots, and either a waypoint query or a gate on one feature: see chain_step_body.
 //   chain_walk_kernel   many chains: the next song after c is the first entry of c's k-nearest list (blissgpu_knn over the
 //                       candidates themselves, c skipped) that the chain has neither taken nor skipped.  Taken and skipped
 //                       entries other than c number at most s_g + k - 2, so a list of L = k + max_g s_g - 1 entries always
@@ -49,13 +53,21 @@ __device__ __forceinline__ unsigned long long chain_wave_min(unsigned long long 
 // D > 0: compile-time feature count (packed arithmetic, candidates in registers).  D == 0: any d <= 64 through pl_distance,
 // candidates read from global memory / L2 (slow, exact).  Step t >= 1: reads idx[chain][0 .. t), writes idx / dist [chain][t]
 // (n_split == 1) or best[chain] (several workgroups per chain).
-template <int D, int METRIC, bool DIAG>
-__global__ __launch_bounds__(256, 2) void chain_step_kernel(const float* __restrict__ X, uint32_t n, uint32_t d_rt, int metric_rt,
-                                                            const float* __restrict__ M, const uint32_t* __restrict__ goff,
-                                                            const uint32_t* __restrict__ skip, uint32_t n_chains, uint32_t k,
-                                                            uint32_t t, uint32_t qb_rt, uint32_t n_split,
-                                                            uint32_t blocks_per_split, uint32_t* idx, float* dist,
-                                                            unsigned long long* best, uint32_t* nan_flag) {
+// J: the step of a JOURNEY (journey_step_kernel; with J == false nothing below differs from the chains' step).  A journey is a
+// chain with two skip slots (skip[2 g], skip[2 g + 1]; goff is not read), a step 0 of its own (t == 0: the query is its `from`
+// row), and either
+//   a waypoint query (j.to != NULL): step t looks for the candidate nearest from + (to - from) * j.s, computed as the rows are
+//   staged -- the previous pick only tells whether the journey has ended; or
+//   a gate (j.gate): a candidate is eligible only while cand[gate_feature] >= ref (UP) or <= ref (DOWN), ref the gated feature of
+//   the previous pick (of `from` at step 0), one float per chain in LDS.  The candidate's feature comes from the staged block,
+//   which stays in LDS through the row loop (D > 0), or from global memory (D == 0); a NaN on either side fails both
+//   comparisons.  The gate only narrows `valid`: the bound test stays the cheap rejection it is.
+template <int D, int METRIC, bool DIAG, bool J>
+__device__ __forceinline__ void chain_step_body(const float* __restrict__ X, uint32_t n, uint32_t d_rt, int metric_rt,
+                                                const float* __restrict__ M, const uint32_t* __restrict__ goff,
+                                                const uint32_t* __restrict__ skip, uint32_t n_chains, uint32_t k, uint32_t t,
+                                                uint32_t qb_rt, uint32_t n_split, uint32_t blocks_per_split, uint32_t* idx,
+                                                float* dist, unsigned long long* best, uint32_t* nan_flag, const JourneyStep& j) {
     constexpr bool GENERIC = D == 0;
     constexpr int DQ = GENERIC ? PL_DMAX : ((D + 3) & ~3);  // LDS pitch of a chain's row: 16-byte aligned -> ds_read_b128 broadcasts
     constexpr int XP = GENERIC ? 1 : (D | 1);               // LDS pitch of a staged candidate: odd, lanes l and l + 1 on different banks
@@ -69,6 +81,12 @@ __global__ __launch_bounds__(256, 2) void chain_step_kernel(const float* __restr
     __shared__ float s_bound[CH_QMAX];
     __shared__ uint32_t s_cur[CH_QMAX], s_g0[CH_QMAX], s_gn[CH_QMAX];
     __shared__ uint32_t s_mask[4][8];
+    float* s_ref = nullptr;  // the gate's reference value of every chain of the workgroup
+    if constexpr (J) {
+        __shared__ float ref_lds[CH_QMAX];
+        s_ref = ref_lds;
+    }
+    const bool gated = J && j.gate != GATE_NONE;  // (uniform over the grid)
 
     const int tid = threadIdx.x, lane = lane_id(), wave = wave_id();
     const uint32_t d = GENERIC ? d_rt : (uint32_t)D;
@@ -98,18 +116,35 @@ __global__ __launch_bounds__(256, 2) void chain_step_kernel(const float* __restr
         __syncthreads();  // every wavefront has finished with the previous chain block
         if ((uint32_t)tid < rows_here) {
             const uint32_t g = c0 + (uint32_t)tid;
-            const uint32_t a = goff[g];
-            s_g0[tid] = a;
-            s_gn[tid] = goff[g + 1] - a;
-            s_cur[tid] = idx[(uint64_t)g * k + (t - 1u)];  // CH_NONE: the chain has run out of candidates
+            if constexpr (J) {
+                s_g0[tid] = 2u * g;
+                s_gn[tid] = 2u;
+                const uint32_t cur = t ? idx[(uint64_t)g * k + (t - 1u)] : 0u;  // (step 0 has no predecessor: any song will do)
+                s_cur[tid] = cur;
+                if (gated && cur != CH_NONE)
+                    s_ref[tid] = t ? X[(uint64_t)cur * d + j.gate_feature] : j.from[(uint64_t)g * d + j.gate_feature];
+            } else {
+                const uint32_t a = goff[g];
+                s_g0[tid] = a;
+                s_gn[tid] = goff[g + 1] - a;
+                s_cur[tid] = idx[(uint64_t)g * k + (t - 1u)];  // CH_NONE: the chain has run out of candidates
+            }
             s_best[tid] = KNN_NONE;
             s_bound[tid] = INFINITY;
         }
         __syncthreads();
-        // the chains' current rows, gathered by index
+        // the chains' current rows, gathered by index (a journey: its waypoint, or at step 0 its `from` row)
         for (uint32_t e = (uint32_t)tid; e < rows_here * d; e += 256u) {
             const uint32_t r = e / d, cur = s_cur[r];
-            s_q[r][e % d] = cur != CH_NONE ? X[(uint64_t)cur * d + e % d] : 0.0f;
+            float v = 0.0f;
+            if (J && cur != CH_NONE && (j.to || t == 0u)) {
+                const uint64_t at = (uint64_t)(c0 + r) * d + e % d;
+                const float a = j.from[at];
+                v = j.to ? a + (j.to[at] - a) * j.s : a;
+            } else if (cur != CH_NONE) {
+                v = X[(uint64_t)cur * d + e % d];
+            }
+            s_q[r][e % d] = v;
         }
         __syncthreads();
         if (!GENERIC && METRIC == METRIC_COSINE) {
@@ -163,6 +198,7 @@ __global__ __launch_bounds__(256, 2) void chain_step_kernel(const float* __restr
 #pragma unroll 1
             for (uint32_t r = wave_u; r < rows_here; r += 4u) {
                 if (s_cur[r] == CH_NONE) continue;  // (wave-uniform)
+                const float ref = gated ? s_ref[r] : 0.0f;
                 // pv[c]: what the bound is compared with for candidate c of the lane -- the sum before the root (ROOT) or the distance
                 float pv[4];
                 if constexpr (GENERIC) {
@@ -209,12 +245,18 @@ __global__ __launch_bounds__(256, 2) void chain_step_kernel(const float* __restr
                 unsigned long long m = KNN_NONE;
 #pragma unroll
                 for (int c = 0; c < 4; c++) {
-                    const uint32_t lc = 64u * (uint32_t)c + (uint32_t)lane, j = j0 + lc;  // (j is only used where lc < cols_here)
+                    const uint32_t lc = 64u * (uint32_t)c + (uint32_t)lane, jc = j0 + lc;  // (jc is only used where lc < cols_here)
                     const bool gone = ((mask[lc >> 5] >> (lc & 31u)) & 1u) != 0u;
-                    const bool valid = lc < cols_here && !gone;  // a taken or skipped candidate's distance is never looked at
+                    bool valid = lc < cols_here && !gone;  // a taken or skipped candidate's distance is never looked at
+                    if (gated) {                           // ... nor that of one the gate keeps out
+                        float f;
+                        if constexpr (GENERIC) f = valid ? X[(uint64_t)jc * d + j.gate_feature] : 0.0f;
+                        else f = s_x[lc * (uint32_t)XP + j.gate_feature];
+                        valid = valid && (j.gate == GATE_UP ? f >= ref : f <= ref);
+                    }
                     const float v = 0.0f + (ROOT ? sqrtf(pv[c]) : pv[c]);
                     if (valid && v != v) saw_nan = true;
-                    const unsigned long long key = ((unsigned long long)f32_key(v) << 32) | j;
+                    const unsigned long long key = ((unsigned long long)f32_key(v) << 32) | jc;
                     if (valid && key < m) m = key;
                 }
                 m = chain_wave_min(m);
@@ -244,6 +286,29 @@ __global__ __launch_bounds__(256, 2) void chain_step_kernel(const float* __restr
         }
     }
     if (saw_nan) atomicOr(nan_flag, 1u);
+}
+
+template <int D, int METRIC, bool DIAG>
+__global__ __launch_bounds__(256, 2) void chain_step_kernel(const float* __restrict__ X, uint32_t n, uint32_t d_rt, int metric_rt,
+                                                            const float* __restrict__ M, const uint32_t* __restrict__ goff,
+                                                            const uint32_t* __restrict__ skip, uint32_t n_chains, uint32_t k,
+                                                            uint32_t t, uint32_t qb_rt, uint32_t n_split,
+                                                            uint32_t blocks_per_split, uint32_t* idx, float* dist,
+                                                            unsigned long long* best, uint32_t* nan_flag) {
+    chain_step_body<D, METRIC, DIAG, false>(X, n, d_rt, metric_rt, M, goff, skip, n_chains, k, t, qb_rt, n_split, blocks_per_split, idx,
+                                            dist, best, nan_flag, JourneyStep{});
+}
+
+// step t >= 0 of every journey: skip is [n_chains][2] or NULL
+template <int D, int METRIC, bool DIAG>
+__global__ __launch_bounds__(256, 2) void journey_step_kernel(const float* __restrict__ X, uint32_t n, uint32_t d_rt, int metric_rt,
+                                                              const float* __restrict__ M, const uint32_t* __restrict__ skip,
+                                                              uint32_t n_chains, uint32_t k, uint32_t t, uint32_t qb_rt,
+                                                              uint32_t n_split, uint32_t blocks_per_split, uint32_t* idx,
+                                                              float* dist, unsigned long long* best, uint32_t* nan_flag,
+                                                              JourneyStep j) {
+    chain_step_body<D, METRIC, DIAG, true>(X, n, d_rt, metric_rt, M, nullptr, skip, n_chains, k, t, qb_rt, n_split, blocks_per_split, idx,
+                                           dist, best, nan_flag, j);
 }
 
 // column t of idx / dist from the chains' minima (best != NULL: a step shared by several workgroups; the minima are reset for
@@ -348,34 +413,52 @@ ChainPlan chain_plan(uint64_t n_chains, uint64_t n, int n_cus) {
     return p;
 }
 
+// (j == NULL: a chains' step; otherwise a journeys' step, which reads no goff)
 template <int D>
 static void step_d(const float* X, uint32_t n, uint32_t d, int metric, const float* M, int diag, const uint32_t* goff,
                    const uint32_t* skip, uint32_t n_chains, uint32_t k, uint32_t t, const ChainPlan& p, uint32_t* idx, float* dist,
-                   unsigned long long* best, uint32_t* nan_flag, hipStream_t st) {
+                   unsigned long long* best, uint32_t* nan_flag, const JourneyStep* j, hipStream_t st) {
     const dim3 grid(p.grid_cb * p.n_split);
-#define CH_GO(DD, MM, DG) hipLaunchKernelGGL((chain_step_kernel<DD, MM, DG>), grid, dim3(256), 0, st, X, n, d, metric, M, goff, skip, \
-                                             n_chains, k, t, p.qb, p.n_split, p.blocks_per_split, idx, dist, best, nan_flag)
+#define CH_GO(DD, MM, DG)                                                                                                            \
+    if (j)                                                                                                                           \
+        hipLaunchKernelGGL((journey_step_kernel<DD, MM, DG>), grid, dim3(256), 0, st, X, n, d, metric, M, skip, n_chains, k, t, p.qb, \
+                           p.n_split, p.blocks_per_split, idx, dist, best, nan_flag, *j);                                            \
+    else                                                                                                                             \
+        hipLaunchKernelGGL((chain_step_kernel<DD, MM, DG>), grid, dim3(256), 0, st, X, n, d, metric, M, goff, skip, n_chains, k, t,   \
+                           p.qb, p.n_split, p.blocks_per_split, idx, dist, best, nan_flag)
     if constexpr (D == 0) {
         CH_GO(0, METRIC_EUCLIDEAN, false);  // (the metric is a run-time argument of the generic path)
     } else {
-        if (metric == METRIC_EUCLIDEAN) CH_GO(D, METRIC_EUCLIDEAN, false);
-        else if (metric == METRIC_COSINE) CH_GO(D, METRIC_COSINE, false);
-        else if (diag) CH_GO(D, METRIC_MAHALANOBIS, true);
-        else CH_GO(D, METRIC_MAHALANOBIS, false);
+        if (metric == METRIC_EUCLIDEAN) { CH_GO(D, METRIC_EUCLIDEAN, false); }
+        else if (metric == METRIC_COSINE) { CH_GO(D, METRIC_COSINE, false); }
+        else if (diag) { CH_GO(D, METRIC_MAHALANOBIS, true); }
+        else { CH_GO(D, METRIC_MAHALANOBIS, false); }
     }
 #undef CH_GO
+}
+
+static void step_any(const float* X, uint32_t n, uint32_t d, int metric, const float* M, int m_is_diag, const uint32_t* goff,
+                     const uint32_t* skip, uint32_t n_chains, uint32_t k, uint32_t t, const ChainPlan& p, uint32_t* idx, float* dist,
+                     unsigned long long* best, uint32_t* nan_flag, const JourneyStep* j, hipStream_t st) {
+    if (n_chains == 0 || n == 0) return;
+    if (d == 23) step_d<23>(X, n, d, metric, M, m_is_diag, goff, skip, n_chains, k, t, p, idx, dist, best, nan_flag, j, st);
+    else if (d == 20) step_d<20>(X, n, d, metric, M, m_is_diag, goff, skip, n_chains, k, t, p, idx, dist, best, nan_flag, j, st);
+    else step_d<0>(X, n, d, metric, M, m_is_diag, goff, skip, n_chains, k, t, p, idx, dist, best, nan_flag, j, st);
+    if (p.n_split > 1)
+        hipLaunchKernelGGL(chain_put_kernel, dim3((n_chains + 255u) / 256u), dim3(256), 0, st, best, nullptr, nullptr, n_chains, k, t,
+                           idx, dist);
 }
 
 void launch_chain_step(const float* X, uint32_t n, uint32_t d, int metric, const float* M, int m_is_diag, const uint32_t* goff,
                        const uint32_t* skip, uint32_t n_chains, uint32_t k, uint32_t t, const ChainPlan& p, uint32_t* idx,
                        float* dist, unsigned long long* best, uint32_t* nan_flag, hipStream_t st) {
-    if (n_chains == 0 || n == 0) return;
-    if (d == 23) step_d<23>(X, n, d, metric, M, m_is_diag, goff, skip, n_chains, k, t, p, idx, dist, best, nan_flag, st);
-    else if (d == 20) step_d<20>(X, n, d, metric, M, m_is_diag, goff, skip, n_chains, k, t, p, idx, dist, best, nan_flag, st);
-    else step_d<0>(X, n, d, metric, M, m_is_diag, goff, skip, n_chains, k, t, p, idx, dist, best, nan_flag, st);
-    if (p.n_split > 1)
-        hipLaunchKernelGGL(chain_put_kernel, dim3((n_chains + 255u) / 256u), dim3(256), 0, st, best, nullptr, nullptr, n_chains, k, t,
-                           idx, dist);
+    step_any(X, n, d, metric, M, m_is_diag, goff, skip, n_chains, k, t, p, idx, dist, best, nan_flag, nullptr, st);
+}
+
+void launch_journey_step(const float* X, uint32_t n, uint32_t d, int metric, const float* M, int m_is_diag, const uint32_t* skip,
+                         uint32_t n_journeys, uint32_t k, uint32_t t, const ChainPlan& p, const JourneyStep& j, uint32_t* idx,
+                         float* dist, unsigned long long* best, uint32_t* nan_flag, hipStream_t st) {
+    step_any(X, n, d, metric, M, m_is_diag, nullptr, skip, n_journeys, k, t, p, idx, dist, best, nan_flag, &j, st);
 }
 
 void launch_chain_first(const uint32_t* idx0, const float* dist0, uint32_t n_chains, uint32_t k, uint32_t* idx, float* dist,

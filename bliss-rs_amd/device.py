@@ -575,6 +575,42 @@ class Context:
         self._post()
         return idx, dist
 
+    def journeys(self, A, B, X, k: int, metric: str = "euclidean", M=None, skip=None, mode: str = "chain", gate: str = None,
+                 feature: int = 0):
+        """Waypoint and directed song-to-song playlists (blissgpu_journeys_device; the reference only names them, TODO.md "New
+        features"), k steps for every journey in one call.  Journey g starts at row g of A.  mode "chain": step 0 picks the
+        candidate nearest A[g], step t the candidate nearest the previous pick; `gate` "up" / "down" additionally keeps only
+        the candidates whose column `feature` is >= / <= that of the previous pick (of A[g] at step 0; equality passes, a NaN
+        on either side does not).  mode "waypoint" (B given, no gate): step t picks the candidate nearest
+        A[g] + (B[g] - A[g]) * ((t + 1) / (k + 1)).  A picked candidate is never picked again; skip: int32 tensor [G, 2] of
+        candidate indices that are never eligible, -1 = none, or None.  -> (idx int32 [G, k], dist float32 [G, k]) on the
+        device; a journey that runs out of eligible candidates ends in -1 (the library's 0xFFFFFFFF) / inf.  Raises
+        BlissGpuError(ERR_NAN) for a NaN distance of an eligible candidate (synchronises for that check)."""
+        from .playlist import _GATES, _JOURNEY_MODES, _METRICS
+
+        torch = self.torch
+        assert A.is_cuda and X.is_cuda and A.dtype == torch.float32 and X.dtype == torch.float32
+        assert A.dim() == 2 and X.dim() == 2 and A.shape[1] == X.shape[1]
+        A, X = A.contiguous(), X.contiguous()
+        G, n, k = A.shape[0], X.shape[0], int(k)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        if B is not None:
+            assert B.is_cuda and B.dtype == torch.float32 and tuple(B.shape) == tuple(A.shape)
+            B = B.contiguous()
+        if skip is not None:
+            assert skip.is_cuda and skip.dtype == torch.int32 and tuple(skip.shape) == (G, 2)
+            skip = skip.contiguous()
+        if M is not None:
+            M = M.contiguous()
+        idx = torch.empty((G, max(k, 0)), dtype=torch.int32, device=X.device)
+        dist = torch.empty((G, max(k, 0)), dtype=torch.float32, device=X.device)
+        self._pre()
+        _ffi.check(self._L.blissgpu_journeys_device(self._h, ptr(A), ptr(B), G, ptr(X), n, X.shape[1], _METRICS[metric], ptr(M),
+                                                    ptr(skip), k, _JOURNEY_MODES[mode], _GATES[gate], int(feature), ptr(idx),
+                                                    ptr(dist)))
+        self._post()
+        return idx, dist
+
     def album_knn(self, S, offsets, X, album_of, n_albums: int, k: int, skip=None):
         """The k nearest ALBUMS of every seed group (blissgpu_album_knn_device): closest_album_to_group (src/playlist.rs:424-485)
         cut after k albums.  Group g's seeds are the rows offsets[g] .. offsets[g + 1] of S (offsets: a HOST sequence of G + 1

@@ -41,7 +41,7 @@ from typing import List, Sequence, Tuple, Union
 import numpy as np
 
 from . import playlist
-from .song import Analysis, FeaturesVersion, ProviderError, Song
+from .song import Analysis, AnalysisIndex, FeaturesVersion, ProviderError, Song
 
 _SONG_COLUMNS = ("path", "artist", "title", "album", "album_artist", "track_number", "disc_number", "genre", "duration",
                  "version")
@@ -542,6 +542,53 @@ def chain_playlists(db: Conn, k: int, by: str = "song", metric_builder=playlist.
     rows = np.asarray([i for key in keys for i in members[key]], np.int64)
     idx, dist = playlist.chain_order((X[rows].reshape(rows.shape[0], X.shape[1]), offsets), X, k, metric, m, skip=rows)
     return {key: [(songs[int(j)].path, float(v)) for j, v in zip(idx[g], dist[g]) if j >= 0] for g, key in enumerate(keys)}
+
+
+def _rows_of(songs, paths):
+    row_of = {s.path: i for i, s in enumerate(songs)}
+    for p in paths:
+        if p not in row_of:
+            raise ProviderError(f"song '{p}' has not been analyzed")
+    return np.asarray([row_of[p] for p in paths], np.int64)
+
+
+def waypoint_playlists(db: Conn, pairs, k: int, metric_builder=playlist.euclidean_distance) -> List[List[Song]]:
+    """For every (from path, to path) of `pairs`, the k songs of the library between the two (playlist.waypoint_playlist: song
+    t is the song nearest the point (t + 1) / (k + 1) of the way, none twice, the end points left out), every pair in ONE
+    device call (playlist.journey_order) over the analysed songs of FeaturesVersion.LATEST.  -> one list of Songs per pair.
+    An unknown path is the ProviderError playlist_from_custom raises.  VarianceWeights and ForestOptions are refused."""
+    playlist._no_forest(metric_builder, playlist._JOURNEY_WHY)
+    playlist._no_variance(metric_builder, playlist._JOURNEY_WHY)
+    pairs = [tuple(p) for p in pairs]
+    songs, X = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
+    ends = _rows_of(songs, [p for pair in pairs for p in pair]).reshape(len(pairs), 2)
+    if not pairs:
+        return []
+    metric, m = playlist._metric_of(metric_builder)
+    idx, _ = playlist.journey_order(X[ends[:, 0]], X, k, X[ends[:, 1]], metric, m, skip=ends)
+    return [[songs[int(j)] for j in row if j >= 0] for row in idx]
+
+
+def directed_playlists(db: Conn, k: int, feature=AnalysisIndex.Tempo, direction: str = "down", song_paths: Sequence[str] = None,
+                       metric_builder=playlist.euclidean_distance):
+    """A directed playlist (playlist.directed_playlist) starting at every analysed song of FeaturesVersion.LATEST, or at
+    `song_paths` only: {path: [Song, ...]}, up to k songs, each the nearest song not yet played whose `feature` (an
+    AnalysisIndex or a column number) is <= ("down") or >= ("up") that of the song before it; the starting song is left out.
+    The library is read once and ONE device call (playlist.journey_order) answers every path.  An unknown path is the
+    ProviderError playlist_from_custom raises.  VarianceWeights and ForestOptions are refused."""
+    playlist._no_forest(metric_builder, playlist._JOURNEY_WHY)
+    playlist._no_variance(metric_builder, playlist._JOURNEY_WHY)
+    if direction not in ("up", "down"):
+        raise ValueError('direction must be "up" or "down"')
+    songs, X = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
+    paths = [s.path for s in songs] if song_paths is None else list(song_paths)
+    rows = _rows_of(songs, paths)
+    if not paths:
+        return {}
+    metric, m = playlist._metric_of(metric_builder)
+    skip = np.stack([rows, np.full_like(rows, -1)], axis=1)
+    idx, _ = playlist.journey_order(X[rows], X, k, None, metric, m, skip, direction, int(feature))
+    return {p: [songs[int(j)] for j in row if j >= 0] for p, row in zip(paths, idx)}
 
 
 def duplicate_songs(db: Conn, distance_threshold: float = None, metric_builder=playlist.euclidean_distance) -> List[List[Song]]:

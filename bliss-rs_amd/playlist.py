@@ -10,6 +10,7 @@
     dedup_playlist, dedup_playlist_custom_distance               :343-402
     duplicate_labels, duplicate_groups (the rule of :381-388 over every pair of a collection, closed transitively)
     closest_album_to_group                                       :424-485
+    journey_order, waypoint_playlist, directed_playlist (the waypoint and direction features of the reference's TODO.md)
 
 A metric builder is one of the strings "euclidean" / "cosine", a `MahalanobisBuilder` (or the pair
 ("mahalanobis", M)), a `ForestOptions` (closest_to_songs and library.playlist_from_custom only: the forest needs at
@@ -67,6 +68,8 @@ def mahalanobis_distance_builder(m) -> Callable[[np.ndarray, np.ndarray], float]
 
 _METRICS = {"euclidean": _ffi.METRIC_EUCLIDEAN, "cosine": _ffi.METRIC_COSINE, "mahalanobis": _ffi.METRIC_MAHALANOBIS}
 _ROUTES = {"auto": _ffi.CHAINS_AUTO, "steps": _ffi.CHAINS_STEPS, "lists": _ffi.CHAINS_LISTS}  # chain_order
+_JOURNEY_MODES = {"chain": _ffi.JOURNEY_CHAIN, "waypoint": _ffi.JOURNEY_WAYPOINT}  # journey_order
+_GATES = {None: _ffi.GATE_NONE, "up": _ffi.GATE_UP, "down": _ffi.GATE_DOWN}
 
 
 def pairwise_distances(A, B, metric="euclidean", m=None) -> np.ndarray:
@@ -794,6 +797,121 @@ def song_chains(groups, candidate_songs, k, metric_builder=euclidean_distance, e
     skip = _member_skip(groups, candidate_songs) if exclude_members else None
     idx, _ = chain_order(seeds, X, k, metric, m, skip)
     return [[candidate_songs[j] for j in row if j >= 0] for row in idx]
+
+
+_JOURNEY_WHY = "a journey's metric compares single songs, step by step"
+
+
+def journey_order(from_rows, candidates, k, to_rows=None, metric="euclidean", m=None, skip=None, direction=None, feature=None):
+    """Waypoint and directed playlists in one device call (blissgpu_journeys; the reference's roadmap names both under "New
+    features" in TODO.md and ships neither).  Journey g starts at from_rows[g].
+    to_rows given (a WAYPOINT journey): song t is the candidate nearest from + (to - from) * ((t + 1) / (k + 1)), t = 0 .. k - 1
+    -- k songs spread along the segment between the two end points, none twice.
+    to_rows None (a CHAIN): song 0 is the candidate nearest from_rows[g], song t the candidate nearest song t - 1; with
+    `direction` "up" / "down" only the candidates whose column `feature` is >= / <= that of the song before (of from_rows[g]
+    for song 0) are eligible -- equality passes, a NaN on either side does not.  A direction cannot be combined with to_rows.
+    Equal distances go to the lower index.  `skip`: [G, 2] candidate indices that are never eligible (-1: none), or None.
+    -> (idx int64[G, k], dist float32[G, k]); a journey that runs out of eligible candidates ends in -1 / inf.  A NaN distance
+    of an eligible candidate raises ValueError.  VarianceWeights and ForestOptions are refused."""
+    _no_forest(metric, _JOURNEY_WHY)
+    _no_variance(metric, _JOURNEY_WHY)
+    A = np.ascontiguousarray(np.atleast_2d(from_rows), dtype=np.float32)
+    X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
+    if A.ndim != 2 or X.ndim != 2 or A.shape[1] != X.shape[1]:
+        raise ValueError("from_rows and candidates must be [G, d] and [n, d]")
+    B = None
+    if to_rows is not None:
+        B = np.ascontiguousarray(np.atleast_2d(to_rows), dtype=np.float32)
+        if B.shape != A.shape:
+            raise ValueError("to_rows must have the shape of from_rows")
+    if metric not in _METRICS:
+        raise ValueError(f"unknown metric {metric!r}")
+    if direction not in _GATES:
+        raise ValueError('direction must be None, "up" or "down"')
+    k = int(k)
+    if not 1 <= k <= 1024:
+        raise ValueError("k must be 1 .. 1024")
+    (G, d), n = A.shape, X.shape[0]
+    if not 1 <= d <= 64:
+        raise ValueError("d must be 1 .. 64")
+    if direction is not None:
+        if B is not None:
+            raise ValueError("a direction cannot be combined with to_rows")
+        if feature is None or not 0 <= int(feature) < d:
+            raise ValueError("a direction needs a feature: an AnalysisIndex or a column number below d")
+    skip_p = None
+    if skip is not None:
+        skip = np.asarray(skip, dtype=np.int64)
+        if skip.shape != (G, 2):
+            raise ValueError("skip must be [G, 2]")
+        if ((skip < -1) | (skip >= n)).any():
+            raise ValueError("skip entries must be candidate indices or -1")
+        skip = np.ascontiguousarray(np.where(skip < 0, 0xFFFFFFFF, skip).astype(np.uint32))
+        skip_p = skip.ctypes.data
+    mp = None
+    if metric == "mahalanobis":
+        if m is None:
+            raise ValueError("mahalanobis needs m")
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        if m.shape != (d, d):
+            raise ValueError("m must be [d, d]")
+        mp = m.ctypes.data
+    idx, dist = np.empty((G, k), np.uint32), np.empty((G, k), np.float32)
+    try:
+        _ffi.check(_ffi.lib().blissgpu_journeys(A.ctypes.data, None if B is None else B.ctypes.data, G, X.ctypes.data, n, d,
+                                                _METRICS[metric], mp, skip_p, k,
+                                                _ffi.JOURNEY_CHAIN if B is None else _ffi.JOURNEY_WAYPOINT, _GATES[direction],
+                                                0 if direction is None else int(feature), idx.ctypes.data, dist.ctypes.data))
+    except _ffi.BlissGpuError as e:
+        _nan_to_panic(e)
+    out = idx.astype(np.int64)
+    out[idx == 0xFFFFFFFF] = -1
+    return out, dist
+
+
+def _end_point_skip(journeys, candidate_songs):
+    """[G, 2]: the first candidate that == each end point of every journey (one or two songs each), as _member_skip; -1: none."""
+    flat = _member_skip(journeys, candidate_songs)
+    skip, row = np.full((len(journeys), 2), -1, np.int64), 0
+    for g, ends in enumerate(journeys):
+        skip[g, :len(ends)] = flat[row:row + len(ends)]
+        row += len(ends)
+    return skip
+
+
+def waypoint_playlist(from_song, to_song, candidate_songs, number_songs, metric_builder=euclidean_distance):
+    """"Go from song1 to song2, both picked by the users, in n songs, without any repetitions" (the reference's TODO.md): the
+    `number_songs` songs between the two, in order -- song t is the candidate nearest the point (t + 1) / (number_songs + 1) of
+    the way from from_song to to_song (journey_order).  The end points themselves are kept out of the pool (the first
+    candidate that == each, as group_playlists does for members) and are not part of the result."""
+    _no_forest(metric_builder, _JOURNEY_WHY)
+    _no_variance(metric_builder, _JOURNEY_WHY)
+    candidate_songs = list(candidate_songs)
+    if not candidate_songs:
+        return []
+    metric, m = _metric_of(metric_builder)
+    ends = [from_song, to_song]
+    idx, _ = journey_order(_matrix(ends[:1]), _matrix(candidate_songs), number_songs, _matrix(ends[1:]), metric, m,
+                           _end_point_skip([ends], candidate_songs))
+    return [candidate_songs[j] for j in idx[0] if j >= 0]
+
+
+def directed_playlist(first_song, candidate_songs, number_songs, feature, direction="down", metric_builder=euclidean_distance):
+    """"I want the tempo to go down or stay the same" (the reference's TODO.md): up to `number_songs` songs after first_song,
+    each the nearest candidate not yet played whose `feature` (an AnalysisIndex or a column number) is <= ("down") or >= ("up")
+    that of the song before it.  The playlist ends early when no candidate qualifies.  first_song is kept out of the pool and
+    is not part of the result."""
+    _no_forest(metric_builder, _JOURNEY_WHY)
+    _no_variance(metric_builder, _JOURNEY_WHY)
+    if direction not in ("up", "down"):
+        raise ValueError('direction must be "up" or "down"')
+    candidate_songs = list(candidate_songs)
+    if not candidate_songs:
+        return []
+    metric, m = _metric_of(metric_builder)
+    idx, _ = journey_order(_matrix([first_song]), _matrix(candidate_songs), number_songs, None, metric, m,
+                           _end_point_skip([[first_song]], candidate_songs), direction, int(feature))
+    return [candidate_songs[j] for j in idx[0] if j >= 0]
 
 
 def meta_keys(songs) -> np.ndarray:

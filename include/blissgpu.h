@@ -580,6 +580,47 @@ int blissgpu_chains_device(blissgpu_ctx *ctx, const float *d_seeds, const uint64
 int blissgpu_chains_plan(const uint64_t *group_offsets, uint64_t n_groups, uint64_t n, uint32_t k, uint64_t workspace_bytes,
                          int *route, uint32_t *list_len);
 
+/* ---- journeys: waypoint and directed song-to-song playlists ----
+ * The reference has no code for these; its roadmap (TODO.md, "New features") names them: "A waypoint feature: go from song1
+ * to song2, both picked by the users, in n songs, without any repetitions" and "A direction feature ('I want the tempo to go
+ * down or stay the same')".  Both are the loop of blissgpu_chains -- k steps, each a masked nearest-candidate search over every
+ * candidate, one launch per step over every journey -- with another query row or a narrower set of eligible candidates.
+ * Journey g has a start row from[g] (d floats), in WAYPOINT mode an end row to[g], and two skip slots skip[g][0 .. 2): candidate
+ * indices that are never eligible and never evaluated (normally the rows of the end points when they are candidates
+ * themselves), 0xFFFFFFFF = none.  Row g of idx / dist ([n_journeys][k]) is the journey:
+ *   BLISSGPU_JOURNEY_CHAIN     the query of step 0 is from[g], the query of step t >= 1 is cand[idx[g][t - 1]];
+ *   BLISSGPU_JOURNEY_WAYPOINT  the query of step t is w_t[f] = from[g][f] + (to[g][f] - from[g][f]) * s_t with
+ *                              s_t = (float)(t + 1) / (float)(k + 1); difference, product and sum are each rounded to f32.
+ * idx[g][t] is the ELIGIBLE candidate j with the smallest 0.0f + metric(query, cand[j]) -- bit for bit what blissgpu_knn /
+ * blissgpu_pairwise_device give for that pair -- the lowest index among equal values; dist[g][t] (dist may be NULL) is that
+ * value.  Candidate j is eligible at step t when it is not in skip[g], not in idx[g][0 .. t) and, with a gate,
+ * cand[j][gate_feature] >= ref (BLISSGPU_GATE_UP) or <= ref (BLISSGPU_GATE_DOWN), ref = from[g][gate_feature] at step 0 and
+ * cand[idx[g][t - 1]][gate_feature] afterwards.  Equality passes ("down or stay the same"); a NaN on either side of the
+ * comparison makes the candidate ineligible; an ineligible candidate's distance is never looked at.  When no candidate is
+ * eligible the journey ends: that step and every later one keep the padding 0xFFFFFFFF / +inf.
+ * CHAIN with any gate and WAYPOINT with BLISSGPU_GATE_NONE are allowed; a gate with WAYPOINT is BLISSGPU_ERR_INVALID.  to is
+ * NULL unless WAYPOINT and must not be NULL in WAYPOINT mode; skip may be NULL.  Limits as for blissgpu_chains: 1 <= k <=
+ * BLISSGPU_KNN_MAX_K, 1 <= d <= 64, n < 2^32 - 1, n_journeys < 2^31, gate_feature < d (looked at only with a gate), metrics and M
+ * as for blissgpu_knn (a diagonal M is detected); the host form also refuses a skip entry >= n other than 0xFFFFFFFF.  All of
+ * this is BLISSGPU_ERR_INVALID and checked before the device is touched.  n_journeys == 0 or n == 0 is BLISSGPU_OK (n == 0:
+ * every row is padding).  BLISSGPU_ERR_NAN exactly when a step that runs evaluates a NaN distance for an eligible candidate
+ * (the outputs are then unspecified).  CHAIN with BLISSGPU_GATE_NONE is blissgpu_chains for one-seed groups, WAYPOINT with
+ * to == from the first k entries of blissgpu_knn for from, both bit for bit.  min(k, n) launches (twice that when few
+ * journeys share the device and several workgroups split a journey's candidates); the workspace is 8 bytes per journey. */
+#define BLISSGPU_JOURNEY_CHAIN 0
+#define BLISSGPU_JOURNEY_WAYPOINT 1
+#define BLISSGPU_GATE_NONE 0
+#define BLISSGPU_GATE_UP 1
+#define BLISSGPU_GATE_DOWN 2
+int blissgpu_journeys(const float *from, const float *to, uint64_t n_journeys, const float *cand, uint64_t n, uint32_t d,
+                      int metric, const float *M, const uint32_t *skip, uint32_t k, int mode, int gate, uint32_t gate_feature,
+                      uint32_t *idx, float *dist);
+/* Device-resident form (device pointers, d_skip included); synchronises the context's stream before returning (the NaN
+ * check). */
+int blissgpu_journeys_device(blissgpu_ctx *ctx, const float *d_from, const float *d_to, uint64_t n_journeys, const float *d_cand,
+                             uint64_t n, uint32_t d, int metric, const float *d_M, const uint32_t *d_skip, uint32_t k, int mode,
+                             int gate, uint32_t gate_feature, uint32_t *d_idx, float *d_dist);
+
 /* ---- duplicate songs of a whole collection ----
  * The duplicate rule of dedup_playlist_custom_distance (src/playlist.rs:381-388) applied to EVERY pair of the n x d matrix x
  * instead of the neighbours of an ordered playlist: the pair (i, j), i < j, is an edge when D[i][j] < threshold (D[i][j] is bit
