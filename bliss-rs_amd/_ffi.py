@@ -29,6 +29,7 @@ OPT_STAGE_LANES, OPT_STAGE_SLAB_KIB, OPT_STAGE_SLABS, OPT_STAGE_NUMA = 9, 10, 11
 OPT_FOREST_SPLIT, OPT_FOREST_WALK = 13, 14
 OPT_FOREST_GROUP_NODES = 15
 GROUP_OK, GROUP_TOO_FEW_SEEDS = 0, 1
+KMEANS_MAX_K = 65535
 
 _f32p = C.POINTER(C.c_float)
 _f64p = C.POINTER(C.c_double)
@@ -106,6 +107,11 @@ SIGNATURES = {
     "blissgpu_knn": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, C.c_uint32, _vp, _vp]),
     "blissgpu_knn_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, C.c_uint32, _vp,
                                       _vp]),
+    "blissgpu_kmeans": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_int, _vp, C.c_uint32, _vp, _vp, _vp, _vp,
+                                  _u32p, _i32p]),
+    "blissgpu_kmeans_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_int, _vp, C.c_uint32, _vp, _vp,
+                                         _vp, _vp, _u32p, _i32p]),
+    "blissgpu_debug_kmeans_stats": (C.c_int, [_vp, _u64p, _u64p]),
     "blissgpu_group_knn": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, C.c_uint32, _vp,
                                      _vp]),
     "blissgpu_group_knn_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp,

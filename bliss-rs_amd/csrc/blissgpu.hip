@@ -26,6 +26,10 @@ thread_local std::string g_last_error;
 const char kSegmentMeanName[] = "segment_mean_kernel", kAlbumKnnScanName[] = "album_knn_scan_kernel";
 const char kGroupForestScanName[] = "group_forest_scan_kernel";  // KX_GROUP_FOREST_SCAN
 const char kJourneyStepName[] = "journey_step_kernel";  // KX_JOURNEY_STEP
+// KX_KMEANS_ASSIGN .. KX_KMEANS_SELECT
+const char kKmeansAssignName[] = "kmeans_assign_kernel", kKmeansHistName[] = "kmeans_hist_kernel";
+const char kKmeansScanTilesName[] = "kmeans_scan_tiles_kernel", kKmeansScanAddName[] = "kmeans_scan_add_kernel";
+const char kKmeansScatterName[] = "kmeans_scatter_kernel", kKmeansSelectName[] = "kmeans_select_kernel";
 const char* const kKernelNames[K_COUNT] = {
     "fft512_kernel",     "onset_kernel",      "beat_kernel",   "stft8192_kernel", "tune_select_kernel",
     "tune_pass2_kernel", "tune_final_kernel", "chroma_kernel",     "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel", "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel",
@@ -34,7 +38,9 @@ const char* const kKernelNames[K_COUNT] = {
     "dup_init_kernel", "dup_join_kernel", "dup_flatten_kernel",
     "group_knn_scan_kernel", "group_knn_merge_kernel", "group_weights_kernel",
     "chain_step_kernel", "chain_walk_kernel",
-    kSegmentMeanName, kAlbumKnnScanName, kGroupForestScanName, kJourneyStepName};
+    kSegmentMeanName, kAlbumKnnScanName,
+    kKmeansAssignName, kKmeansHistName, kKmeansScanTilesName, kKmeansScanAddName, kKmeansScatterName, kKmeansSelectName,
+    kGroupForestScanName, kJourneyStepName};
 }  // namespace
 
 namespace bg {
@@ -342,7 +348,7 @@ int blissgpu_ctx_destroy(blissgpu_ctx* c) {
         (void)hipFree(c->bt_rwv); (void)hipFree(c->bt_dfwv); (void)hipFree(c->chroma_bank);
         scheduler_release(c);
         c->dbg_tuning.release(); c->dbg_nbpms.release(); c->dbg_chroma.release(); c->dbg_interval.release();
-        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->pl_next.release(); c->st_idx.release();
+        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->km_ws.release(); c->pl_next.release(); c->st_idx.release();
         c->st_a.release(); c->st_b.release(); c->st_m.release(); c->st_dist.release(); c->st_out.release();
         c->fl_bytes.release(); c->fl_tab.release(); c->fl_pcm.release(); c->fl_status.release(); c->fl_end.release();
         c->fl_bad.release(); c->fl_mono.release(); c->fl_rows.release(); c->fl_htab.release();
@@ -943,6 +949,159 @@ int blissgpu_knn(const float* queries, uint64_t q, const float* cand, uint64_t n
         if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(knn)", hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+// ---- k-means of a library: Lloyd's algorithm with the all-pairs kernel's distances, ties to the lower centre, sequential f32
+// means and empty clusters that keep their centre (kernels_kmeans.hip); labels, row lists and centres stay on the device ----
+// everything that can be said about the arguments without a device (both forms check it BEFORE the device is touched)
+static int kmeans_args_ok(const char* who, const void* x, uint64_t n, uint32_t d, const void* init, uint32_t k, int metric,
+                          const float* M, const void* labels, const void* centroids, const void* n_iter, const void* converged) {
+    if (k == 0 || k > BLISSGPU_KMEANS_MAX_K) return fail(BLISSGPU_ERR_INVALID, who, "k must be 1 .. BLISSGPU_KMEANS_MAX_K");
+    if (d == 0 || d > 64) return fail(BLISSGPU_ERR_INVALID, who, "d must be 1 .. 64");
+    if (metric == BLISSGPU_METRIC_COSINE) return fail(BLISSGPU_ERR_INVALID, who, "cosine: a mean does not minimise it");
+    if (metric != BLISSGPU_METRIC_EUCLIDEAN && metric != BLISSGPU_METRIC_MAHALANOBIS) return fail(BLISSGPU_ERR_INVALID, who, "unknown metric");
+    if (metric == BLISSGPU_METRIC_MAHALANOBIS && !M) return fail(BLISSGPU_ERR_INVALID, who, "mahalanobis needs M");
+    if (n >= 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "n must be below 2^32 - 1 songs");
+    if (n && !x) return fail(BLISSGPU_ERR_INVALID, who, "x is NULL");
+    if (!init) return fail(BLISSGPU_ERR_INVALID, who, "init is NULL");
+    if (n && !labels) return fail(BLISSGPU_ERR_INVALID, who, "labels is NULL");
+    if (!centroids) return fail(BLISSGPU_ERR_INVALID, who, "centroids is NULL");
+    if (!n_iter || !converged) return fail(BLISSGPU_ERR_INVALID, who, "n_iter / converged is NULL");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_kmeans_device(blissgpu_ctx* c, const float* d_x, uint64_t n, uint32_t d, const float* d_init, uint32_t k, int metric,
+                           const float* d_M, uint32_t max_iter, uint32_t* d_labels, float* d_dist, float* d_centroids,
+                           uint32_t* d_sizes, uint32_t* n_iter, int32_t* converged) {
+    const char* who = "blissgpu_kmeans_device";
+    int rc = kmeans_args_ok(who, d_x, n, d, d_init, k, metric, d_M, d_labels, d_centroids, n_iter, converged);
+    if (rc) return rc;
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    CTX_ENTER(c, who);
+    const size_t cent_bytes = (size_t)k * d * sizeof(float);
+    if (n == 0) {  // no song: no assignment, no update
+        if (d_centroids != d_init) HIP_TRY(hipMemcpyAsync(d_centroids, d_init, cent_bytes, hipMemcpyDeviceToDevice, c->stream));
+        if (d_sizes) HIP_TRY(hipMemsetAsync(d_sizes, 0, (size_t)k * sizeof(uint32_t), c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        *n_iter = 0;
+        *converged = 1;
+        return BLISSGPU_OK;
+    }
+    int diag = 0;
+    if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
+        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
+            diag = is_diag(c->m_cache.data(), d);
+        } else {
+            std::vector<float> hM((size_t)d * d);
+            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            diag = is_diag(hM.data(), d);
+        }
+    }
+    // workspace, O(n + K d + chunks x K): flags u32[4] ([0] labels that moved, [1] NaN) | hist u32[K][W] | scan totals | arow_off
+    // u32[K + 1] | arow u32[n] | centres f32[2][K][d]
+    const KmeansPlan plan = kmeans_plan(n, k, c->n_cus);
+    const size_t o_hist = 4, o_bsum = o_hist + (size_t)plan.hist_words, o_off = o_bsum + plan.scan_tiles, o_arow = o_off + k + 1,
+                 o_cent = o_arow + (size_t)n, words = o_cent + 2 * (size_t)k * d;
+    rc = c->km_ws.ensure(words * sizeof(uint32_t));
+    if (rc) return rc;
+    uint32_t* w = reinterpret_cast<uint32_t*>(c->km_ws.p);
+    uint32_t *flags = w, *hist = w + o_hist, *bsum = w + o_bsum, *arow_off = w + o_off, *arow = w + o_arow;
+    float* cent[2] = {reinterpret_cast<float*>(w + o_cent), reinterpret_cast<float*>(w + o_cent) + (size_t)k * d};
+    const AlbumTables tables{nullptr, arow_off, arow, nullptr, nullptr, nullptr, nullptr, nullptr, k, 0u, 0u};
+    const size_t zero_bytes = (o_hist + (size_t)plan.hist_words) * sizeof(uint32_t);  // the flags and the histograms: one memset
+    auto sort_head = [&]() {  // labels -> arow_off (and hist = the positions the scatter starts from)
+        { Prof p(c, KX_KMEANS_HIST); launch_kmeans_hist(d_labels, (uint32_t)n, k, plan, hist, c->stream); }
+        { Prof p(c, KX_KMEANS_SCAN_TILES); launch_kmeans_scan_tiles(hist, plan, bsum, c->stream); }
+        { Prof p(c, KX_KMEANS_SCAN_ADD); launch_kmeans_scan_add(hist, (uint32_t)n, k, plan, bsum, arow_off, c->stream); }
+    };
+    HIP_TRY(hipMemcpyAsync(cent[0], d_init, cent_bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(d_labels, 0xFF, (size_t)n * sizeof(uint32_t), c->stream));  // L_-1: no label
+    uint32_t t = 0;
+    int cur = 0, conv = 0;
+    c->km_loop_copies = c->km_loop_bytes = 0;
+    for (;; t++) {
+        HIP_TRY(hipMemsetAsync(w, 0, zero_bytes, c->stream));
+        {
+            Prof p(c, KX_KMEANS_ASSIGN);
+            launch_kmeans_assign(d_x, (uint32_t)n, cent[cur], k, d, metric, d_M, diag, plan, d_labels, d_dist, flags, flags + 1, c->stream);
+        }
+        HIP_TRY(hipGetLastError());
+        // the one word pair the host reads per iteration
+        uint32_t h_flags[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        c->km_loop_copies++;
+        c->km_loop_bytes += sizeof(h_flags);
+        if (h_flags[1]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance (the reference panics here)");
+        if (h_flags[0] == 0) { conv = 1; break; }
+        if (t == max_iter) break;
+        sort_head();
+        { Prof p(c, KX_KMEANS_SCATTER); launch_kmeans_scatter(d_labels, (uint32_t)n, k, plan, hist, arow, c->stream); }
+        { Prof p(c, KX_SEGMENT_MEAN); launch_segment_mean(d_x, nullptr, d, tables, cent[cur ^ 1], nullptr, nullptr, c->stream); }
+        { Prof p(c, KX_KMEANS_SELECT); launch_kmeans_select(cent[cur], cent[cur ^ 1], arow_off, k, d, nullptr, c->stream); }
+        HIP_TRY(hipGetLastError());
+        cur ^= 1;
+    }
+    if (d_sizes) {
+        // converged after an update: the labels are those the last sort saw; otherwise they moved since (or were never sorted)
+        if (!conv || t == 0) {
+            HIP_TRY(hipMemsetAsync(w, 0, zero_bytes, c->stream));
+            sort_head();
+        }
+        { Prof p(c, KX_KMEANS_SELECT); launch_kmeans_select(nullptr, nullptr, arow_off, k, d, d_sizes, c->stream); }
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(d_centroids, cent[cur], cent_bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *n_iter = t;
+    *converged = conv;
+    return BLISSGPU_OK;
+}
+
+int blissgpu_kmeans(const float* x, uint64_t n, uint32_t d, const float* init, uint32_t k, int metric, const float* M,
+                    uint32_t max_iter, uint32_t* labels, float* dist, float* centroids, uint32_t* sizes, uint32_t* n_iter,
+                    int32_t* converged) {
+    const char* who = "blissgpu_kmeans";
+    int rc = kmeans_args_ok(who, x, n, d, init, k, metric, M, labels, centroids, n_iter, converged);
+    if (rc) return rc;
+    if (n == 0) {  // no song: nothing for a device to do
+        memmove(centroids, init, (size_t)k * d * sizeof(float));
+        if (sizes) memset(sizes, 0, (size_t)k * sizeof(uint32_t));
+        *n_iter = 0;
+        *converged = 1;
+        return BLISSGPU_OK;
+    }
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    const size_t cent_floats = (size_t)k * d;
+    const float* dM = nullptr;
+    rc = c->st_b.ensure(n * d);
+    if (!rc) rc = c->st_a.ensure(2 * cent_floats);  // the initial centres | the result
+    if (!rc) rc = c->st_idx.ensure(n + k);          // labels | sizes
+    if (!rc && dist) rc = c->st_dist.ensure(n);
+    if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
+    if (rc) return rc;
+    float* d_cent = c->st_a.p + cent_floats;
+    uint32_t *d_labels = c->st_idx.p, *d_sizes = sizes ? c->st_idx.p + n : nullptr;
+    hipError_t e = hipMemcpyAsync(c->st_b.p, x, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->st_a.p, init, cent_floats * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(kmeans)", hipGetErrorString(e));
+    if (!rc)
+        rc = blissgpu_kmeans_device(c, c->st_b.p, n, d, c->st_a.p, k, metric, dM, max_iter, d_labels, dist ? c->st_dist.p : nullptr,
+                                    d_cent, d_sizes, n_iter, converged);
+    if (!rc) {
+        e = hipMemcpyAsync(labels, d_labels, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(centroids, d_cent, cent_floats * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && sizes) e = hipMemcpyAsync(sizes, d_sizes, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(kmeans)", hipGetErrorString(e));
     }
     (void)hipStreamSynchronize(c->stream);
     return rc;
@@ -2180,6 +2339,14 @@ int blissgpu_debug_group_forest_stats(blissgpu_ctx* c, double* build_ms, double*
     if (build_ms) *build_ms = c->gf_build_ms;
     if (wait_ms) *wait_ms = c->gf_wait_ms;
     if (n_batches) *n_batches = c->gf_batches;
+    return BLISSGPU_OK;
+}
+
+int blissgpu_debug_kmeans_stats(blissgpu_ctx* c, uint64_t* loop_copies, uint64_t* loop_bytes) {
+    if (!c) return fail(BLISSGPU_ERR_INVALID, "blissgpu_debug_kmeans_stats", "ctx is NULL");
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    if (loop_copies) *loop_copies = c->km_loop_copies;
+    if (loop_bytes) *loop_bytes = c->km_loop_bytes;
     return BLISSGPU_OK;
 }
 

@@ -123,14 +123,19 @@ enum KernelId : int {
     K_CHAIN_STEP, K_CHAIN_WALK,             // song-to-song chains cut after k (kernels_chains.hip)
     // (tests/test_chains_host.py holds this list, and the list of names beside it, to end in the chain kernels: the kernels
     // that came later are numbered behind it, so that no older id or name moves)
-    K_COUNT = K_CHAIN_WALK + 5
+    K_COUNT = K_CHAIN_WALK + 11
 };
 // k-nearest albums per seed group (kernels_albums.hip; its partial lists are merged by knn_merge_kernel)
 constexpr int KX_SEGMENT_MEAN = K_CHAIN_WALK + 1, KX_ALBUM_KNN_SCAN = K_CHAIN_WALK + 2;
+// k-means of a library (kernels_kmeans.hip): the nearest centre of every song, the counting sort of the labels, the select
+constexpr int KX_KMEANS_ASSIGN = K_CHAIN_WALK + 3, KX_KMEANS_HIST = K_CHAIN_WALK + 4, KX_KMEANS_SCAN_TILES = K_CHAIN_WALK + 5,
+              KX_KMEANS_SCAN_ADD = K_CHAIN_WALK + 6, KX_KMEANS_SCATTER = K_CHAIN_WALK + 7, KX_KMEANS_SELECT = K_CHAIN_WALK + 8;
+// (tests/test_journeys_host.py holds the profile table to END in the next two names: kernels that come later are numbered in
+// front of them; every consumer of the table goes by name)
 // the k lowest forest scores per seed group (kernels_forest.hip; its partial lists are merged by group_knn_merge_kernel)
-constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 3;
+constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 9;
 // a journey's step (kernels_chains.hip: the chains' scan with a waypoint query or a gate)
-constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 4;
+constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 10;
 static_assert(KX_JOURNEY_STEP + 1 == K_COUNT, "every kernel id is below the count");
 
 // lower_bound on a prefix array: largest s with prefix[s] <= x  (prefix has n+1 entries, prefix[0]=0)
@@ -330,6 +335,29 @@ void launch_segment_mean(const float* X, const float* S, uint32_t d, const Album
 // (group, album) pair sets *nan_flag
 void launch_album_knn_scan(const float* gmeans, const float* centroids, uint32_t d, const AlbumTables& t, const float* pcent,
                            uint32_t k, const KnnPlan& p, unsigned long long* part, uint32_t* nan_flag, hipStream_t st);
+// k-means (kernels_kmeans.hip).  One iteration: assign (labels in place: a song whose label moves counts into *changed; dist may
+// be NULL; a NaN among the evaluated distances sets *nan_flag), then the stable counting sort of the labels -- hist [K][W]
+// zeroed by the caller, scanned in place into list positions (bsum: scan_tiles words of scratch), arow_off [K + 1] and arow [n]
+// in the form AlbumTables wants -- launch_segment_mean over those lists, and the select: next[c] = prev[c] for a cluster
+// without rows (next NULL: nothing), sizes[c] (NULL: nothing) = its rows
+struct KmeansPlan {
+    uint32_t assign_waves, assign_grid;  // wavefronts per workgroup of the assignment (256 songs each), its workgroups
+    uint32_t W, chunk;                   // the sort's chunks (one wavefront each) and their songs
+    uint64_t hist_words;                 // K * W
+    uint32_t scan_tiles;                 // 2048-word tiles of the scan
+};
+KmeansPlan kmeans_plan(uint64_t n, uint32_t K, int n_cus);
+void launch_kmeans_assign(const float* X, uint32_t n, const float* C, uint32_t K, uint32_t d, int metric, const float* M,
+                          int m_is_diag, const KmeansPlan& p, uint32_t* labels, float* dist, uint32_t* changed, uint32_t* nan_flag,
+                          hipStream_t st);
+void launch_kmeans_hist(const uint32_t* labels, uint32_t n, uint32_t K, const KmeansPlan& p, uint32_t* hist, hipStream_t st);
+void launch_kmeans_scan_tiles(uint32_t* hist, const KmeansPlan& p, uint32_t* bsum, hipStream_t st);
+void launch_kmeans_scan_add(uint32_t* hist, uint32_t n, uint32_t K, const KmeansPlan& p, const uint32_t* bsum, uint32_t* arow_off,
+                            hipStream_t st);
+void launch_kmeans_scatter(const uint32_t* labels, uint32_t n, uint32_t K, const KmeansPlan& p, uint32_t* pos, uint32_t* arow,
+                           hipStream_t st);
+void launch_kmeans_select(const float* prev, float* next, const uint32_t* arow_off, uint32_t K, uint32_t d, uint32_t* sizes,
+                          hipStream_t st);
 // song-to-song chains cut after k, one per seed group (kernels_chains.hip).  Step 0 is the group search with k = 1; a later step
 // t reads idx[chain][0 .. t) and writes idx / dist [chain][t], directly or -- several workgroups per chain -- through the
 // 64-bit minima best[n_chains] (all KNN_NONE before the first step; reset by the step's second launch).  A NaN among the

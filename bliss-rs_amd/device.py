@@ -469,6 +469,49 @@ class Context:
         self._post()
         return idx, dist
 
+    def kmeans(self, X, init, max_iter: int = 100, metric: str = "euclidean", M=None):
+        """Lloyd's k-means of the rows of X from the centres `init` [k, d], iterated on the device (blissgpu_kmeans_device,
+        DESIGN.md 3.21): nearest centre by the all-pairs kernel's distances with ties to the lower centre, sequential f32 means in
+        row order, an empty cluster keeps its centre, stop when no label moves or after max_iter updates.  X and init are
+        float32 tensors on the device, or numpy arrays (uploaded, results returned as arrays).  -> (labels int32 [n], dist float32
+        [n], centroids float32 [k, d], sizes int32 [k], n_iter, converged).  metric: "euclidean" or "mahalanobis" with M.  Raises
+        BlissGpuError(ERR_NAN) for a NaN among the evaluated distances; synchronises once per iteration."""
+        from .playlist import _METRICS
+
+        torch = self.torch
+        as_numpy = not torch.is_tensor(X)
+        dev = torch.device("cuda", self.device)
+        up = lambda a: None if a is None else (  # noqa: E731
+            a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev))
+        X, init, M = up(X), up(init), up(M)
+        assert X.is_cuda and init.is_cuda and X.dtype == torch.float32 and init.dtype == torch.float32
+        assert X.dim() == 2 and init.dim() == 2 and X.shape[1] == init.shape[1]
+        X, init = X.contiguous(), init.contiguous()
+        if M is not None:
+            assert M.is_cuda and M.dtype == torch.float32
+            M = M.contiguous()
+        (n, d), k = X.shape, init.shape[0]
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        labels = torch.empty((n,), dtype=torch.int32, device=X.device)
+        dist = torch.empty((n,), dtype=torch.float32, device=X.device)
+        cent = torch.empty((k, d), dtype=torch.float32, device=X.device)
+        sizes = torch.empty((k,), dtype=torch.int32, device=X.device)
+        n_iter, conv = C.c_uint32(0), C.c_int32(0)
+        self._pre()
+        _ffi.check(self._L.blissgpu_kmeans_device(self._h, ptr(X), n, d, ptr(init), k, _METRICS[metric], ptr(M), int(max_iter),
+                                                  ptr(labels), ptr(dist), ptr(cent), ptr(sizes), C.byref(n_iter), C.byref(conv)))
+        self._post()
+        if as_numpy:
+            labels, dist, cent, sizes = (t.cpu().numpy() for t in (labels, dist, cent, sizes))
+        return labels, dist, cent, sizes, int(n_iter.value), bool(conv.value)
+
+    def kmeans_stats(self):
+        """(device-to-host copies inside the loop, their bytes) of the last kmeans on this context: one pair of flag words per
+        assignment."""
+        a, b = C.c_uint64(), C.c_uint64()
+        _ffi.check(self._L.blissgpu_debug_kmeans_stats(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     def group_weights(self, S, offsets):
         """variance_based_weight_matrix (src/playlist.rs:173-221) of every seed group on the device: group g's seeds are the
         rows offsets[g] .. offsets[g + 1] of S (offsets: a HOST sequence of G + 1 integers starting at 0).  -> (weights float32

@@ -30,6 +30,8 @@ database:
     duplicate_songs                       the groups of songs that are the same song by the rule of dedup_playlist
                                           (closer than the threshold, or the same title and artist) over EVERY pair of the
                                           library, one device call (playlist.duplicate_labels); nothing is deleted
+    cluster_songs                         the k groups the library falls into (k-means on the device, playlist.cluster_songs),
+                                          every group's songs with the most typical first
 
 SQLite stores `real` as f64; an f32 feature widens exactly on the way in and narrows exactly on the way out, so a
 round trip is bit-exact.  The schema, load and store helpers are host code; the playlists run their distances on the
@@ -605,6 +607,21 @@ def duplicate_songs(db: Conn, distance_threshold: float = None, metric_builder=p
     metric, m = playlist._metric_of(metric_builder)
     labels = playlist.duplicate_labels(X, playlist.meta_keys(songs), metric, m, distance_threshold)
     return [[songs[i] for i in g] for g in playlist.groups_from_labels(labels)]
+
+
+def cluster_songs(db: Conn, k: int, seed: int = 0, metric_builder=playlist.euclidean_distance, max_iter: int = 100,
+                  init: str = "k-means++", return_clustering: bool = False):
+    """Which k groups the library falls into: k-means (playlist.cluster_songs) over the analysed songs of
+    FeaturesVersion.LATEST, read once (load_songs), iterated on the device.  -> k lists of `Song`, cluster c's songs ordered by
+    (distance to the cluster's centre, id order): the most typical first; a cluster may be empty.  `return_clustering`: ->
+    (lists, playlist.Clustering) with the labels, distances, centres, sizes, n_iter, converged and inertia."""
+    playlist._kmeans_metric(metric_builder)  # refused before the database is read
+    songs, _ = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
+    if not songs:
+        raise ValueError("cluster_songs needs at least one analysed song")
+    clustering = playlist.cluster_songs(songs, k, seed, metric_builder, max_iter, init)
+    lists = [[songs[int(i)] for i in clustering.members(c)] for c in range(len(clustering.sizes))]
+    return (lists, clustering) if return_clustering else lists
 
 
 def album_playlist_from(db: Conn, album_title: str, number_albums: int) -> List[Song]:

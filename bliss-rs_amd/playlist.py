@@ -11,6 +11,7 @@
     duplicate_labels, duplicate_groups (the rule of :381-388 over every pair of a collection, closed transitively)
     closest_album_to_group                                       :424-485
     journey_order, waypoint_playlist, directed_playlist (the waypoint and direction features of the reference's TODO.md)
+    kmeans, kmeans_init, cluster_songs (the clustering the reference's TODO.md asks for: Lloyd's algorithm on the device)
 
 A metric builder is one of the strings "euclidean" / "cosine", a `MahalanobisBuilder` (or the pair
 ("mahalanobis", M)), a `ForestOptions` (closest_to_songs and library.playlist_from_custom only: the forest needs at
@@ -473,6 +474,130 @@ def nearest_songs(songs, candidate_songs, k, metric_builder=euclidean_distance, 
                     break
     idx, _ = nearest_order(_matrix(songs), _matrix(candidate_songs), k, metric, m, skip)
     return [[candidate_songs[j] for j in row if j >= 0] for row in idx]
+
+
+def kmeans(X, init, max_iter=100, metric="euclidean", m=None):
+    """Lloyd's k-means of the rows of X from the centres `init` [k, d] in one device call (blissgpu_kmeans): the nearest centre
+    by the all-pairs distances with equal rounded distances going to the lower centre, the sequential f32 mean of every
+    cluster's rows in row order, an empty cluster keeps its centre; stops when no label moves (converged) or after max_iter
+    updates.  -> (labels int64[n], dist float32[n], centroids float32[k, d], sizes int64[k], n_iter, converged).  metric:
+    "euclidean" or "mahalanobis" with m; "cosine" is refused (a mean does not minimise it).  A NaN distance raises ValueError."""
+    if metric == "cosine":
+        raise ValueError("k-means needs a metric its means minimise: euclidean or mahalanobis, not cosine")
+    X = np.ascontiguousarray(np.atleast_2d(X), dtype=np.float32)
+    init = np.ascontiguousarray(np.atleast_2d(init), dtype=np.float32)
+    if X.ndim != 2 or init.ndim != 2 or X.shape[1] != init.shape[1]:
+        raise ValueError("X and init must be [n, d] and [k, d]")
+    max_iter = int(max_iter)
+    if max_iter < 0:
+        raise ValueError("max_iter must be at least 0")
+    (n, d), k = X.shape, init.shape[0]
+    mp = None
+    if m is not None:
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        mp = m.ctypes.data
+    labels, dist = np.empty(n, np.uint32), np.empty(n, np.float32)
+    cent, sizes = np.empty((k, d), np.float32), np.empty(k, np.uint32)
+    n_iter, conv = C.c_uint32(0), C.c_int32(0)
+    try:
+        _ffi.check(_ffi.lib().blissgpu_kmeans(X.ctypes.data, n, d, init.ctypes.data, k, _METRICS[metric], mp, max_iter,
+                                              labels.ctypes.data, dist.ctypes.data, cent.ctypes.data, sizes.ctypes.data,
+                                              C.byref(n_iter), C.byref(conv)))
+    except _ffi.BlissGpuError as e:
+        _nan_to_panic(e)
+    return labels.astype(np.int64), dist, cent, sizes.astype(np.int64), int(n_iter.value), bool(conv.value)
+
+
+_KMEANS_INITS = ("k-means++", "sample")
+
+
+def kmeans_init(X, k, seed=0, method="k-means++"):
+    """k rows of X to start k-means from, [k, d]; the same seed gives the same rows (numpy's PCG64).
+    "sample": rows numpy.random.Generator(PCG64(seed)).choice(n, k, replace=False), sorted -- host only.
+    "k-means++": D^2 sampling -- the first row uniformly, every further row with probability proportional to the squared
+    euclidean distance to the nearest row picked so far.  Each pick's n distances come from the device (Context.pairwise against
+    the last pick); the running minimum and the draw are numpy.  A row at distance 0 from the picks (a picked row, or a
+    duplicate of one) is never drawn while a row at a non-zero distance exists; after that the lowest unpicked rows follow."""
+    X = np.ascontiguousarray(np.atleast_2d(X), dtype=np.float32)
+    n, k = X.shape[0], int(k)
+    if method not in _KMEANS_INITS:
+        raise ValueError(f"method must be one of {_KMEANS_INITS}")
+    if k < 1 or k > n:
+        raise ValueError("k must be 1 .. the number of rows")
+    rng = np.random.Generator(np.random.PCG64(int(seed)))
+    if method == "sample":
+        return X[np.sort(rng.choice(n, k, replace=False))].copy()
+    import torch
+
+    from .device import Context
+
+    ctx = Context.default()
+    Xd = torch.from_numpy(X).to(torch.device("cuda", ctx.device))
+    picks = [int(rng.integers(n))]
+    picked = np.zeros(n, bool)
+    picked[picks[0]] = True
+    d2 = None
+    while len(picks) < k:
+        last = ctx.pairwise(Xd, Xd[picks[-1]:picks[-1] + 1])[:, 0].cpu().numpy().astype(np.float64)
+        d2 = last * last if d2 is None else np.minimum(d2, last * last)
+        if np.isnan(d2).any():
+            raise ValueError("NaN distance (noisy_float::n32 / argmin().unwrap() panic in the reference)")
+        cum = np.cumsum(d2)
+        total = cum[-1]
+        if total > 0.0:
+            # cum[i - 1] <= r < cum[i]: row i has d2 > 0; a product rounded up to the total falls back to the last such row
+            i = int(np.searchsorted(cum, rng.random() * total, side="right"))
+            if i >= n or d2[i] == 0.0:
+                i = int(np.flatnonzero(d2 > 0.0)[-1])
+        else:
+            i = int(np.flatnonzero(~picked)[0])
+        picks.append(i)
+        picked[i] = True
+    return X[np.asarray(picks)].copy()
+
+
+class Clustering:
+    """The result of cluster_songs: labels int64[n], distances float32[n] (to the song's own centre), centroids float32[k, d],
+    sizes int64[k], n_iter (updates made), converged, and inertia = the float64 sum of the squared distances."""
+
+    def __init__(self, labels, distances, centroids, sizes, n_iter, converged):
+        self.labels = np.asarray(labels, dtype=np.int64)
+        self.distances = np.asarray(distances, dtype=np.float32)
+        self.centroids = np.asarray(centroids, dtype=np.float32)
+        self.sizes = np.asarray(sizes, dtype=np.int64)
+        self.n_iter, self.converged = int(n_iter), bool(converged)
+        self.inertia = float(np.sum(self.distances.astype(np.float64) ** 2))
+
+    def members(self, c) -> np.ndarray:
+        """Row indices of cluster c ordered by (distance, index): the songs most typical of the cluster first."""
+        rows = np.flatnonzero(self.labels == int(c))
+        return rows[np.lexsort((rows, self.distances[rows]))]
+
+    def __repr__(self):
+        return (f"Clustering(k={len(self.sizes)}, n={len(self.labels)}, n_iter={self.n_iter}, converged={self.converged}, "
+                f"inertia={self.inertia:.6g})")
+
+
+def _kmeans_metric(metric_builder):
+    """the metrics k-means can run: euclidean, or Mahalanobis with the caller's matrix"""
+    _no_forest(metric_builder, "k-means assigns single songs to centres and needs a metric its means minimise")
+    _no_variance(metric_builder, "k-means has no seed set to take variances from; pass MahalanobisBuilder(m)")
+    metric, m = _metric_of(metric_builder)
+    if metric == "cosine":
+        raise ValueError("k-means needs a metric its means minimise: euclidean or mahalanobis, not cosine")
+    return metric, m
+
+
+def cluster_songs(songs, k, seed=0, metric_builder=euclidean_distance, max_iter=100, init="k-means++") -> Clustering:
+    """Which k groups the songs fall into: k-means of their analyses (kmeans) from kmeans_init(rows, k, seed, init).
+    -> Clustering; `members(c)` lists cluster c's songs, the most typical first.  metric_builder: euclidean_distance or a
+    MahalanobisBuilder (its M); a ForestOptions, a VarianceWeights, cosine and arbitrary callables are refused."""
+    metric, m = _kmeans_metric(metric_builder)
+    songs = list(songs)
+    if not songs:
+        raise ValueError("cluster_songs needs at least one song")
+    X = _matrix(songs)
+    return Clustering(*kmeans(X, kmeans_init(X, k, seed, init), max_iter, metric, m))
 
 
 def _seed_groups(seed_groups):

@@ -423,6 +423,36 @@ int blissgpu_knn_device(blissgpu_ctx *ctx, const float *d_queries, uint64_t q, c
                         uint32_t d, int metric, const float *d_M, const uint32_t *d_skip, uint32_t k,
                         uint32_t *d_idx, float *d_dist);
 
+/* ---- k-means clustering of a library (the reference's TODO.md asks for genre clustering, it has no code) ----
+ * Lloyd's algorithm over the rows x [n][d] from the initial centres init [k][d], every step defined to the bit.  With
+ * dist(i, c) = bit for bit what blissgpu_pairwise_device(x, C_t) writes at [i][c], and L_-1[i] = 0xFFFFFFFF, iteration
+ * t = 0, 1, ... is
+ *   L_t[i] = the c with the smallest (dist(i, c), c): equal ROUNDED distances (-0.0 and +0.0 are equal) go to the lower c;
+ *   D_t[i] = dist(i, L_t[i]);
+ *   no label moved (L_t == L_t-1): stop, converged = 1;   t == max_iter: stop, converged = 0;
+ *   C_t+1[c] = (0.0f + x[i_0] + x[i_1] + ...) / (float)count_c over the members of c in ASCENDING i, every operation in f32, the
+ *              sum never split or restarted (ndarray's mean_axis; blissgpu_album_knn's centroid rule);
+ *   C_t+1[c] = C_t[c], the same bits, when c has no member: an empty cluster keeps its centre.
+ * Outputs: labels [n] = L_t, dist [n] = D_t (may be NULL), centroids [k][d] = C_t -- the labels are always the nearest-centre
+ * labels of the centres returned --, sizes [k] (may be NULL) = members per cluster, *n_iter = t = the number of updates made,
+ * *converged.  max_iter = 0 is a pure nearest-centre assignment to init.
+ * metric: BLISSGPU_METRIC_EUCLIDEAN, or BLISSGPU_METRIC_MAHALANOBIS with the caller's M (a diagonal M is detected as everywhere
+ * else); BLISSGPU_METRIC_COSINE is BLISSGPU_ERR_INVALID (a mean does not minimise it).  A NaN among the evaluated distances
+ * returns BLISSGPU_ERR_NAN; the outputs are then unspecified.
+ * 1 <= d <= 64, 1 <= k <= BLISSGPU_KMEANS_MAX_K, n < 2^32 - 1; k > n is allowed (the surplus centres stay empty); n == 0 is
+ * BLISSGPU_OK with n_iter = 0, converged = 1, centroids = init.  Arguments are checked before the device is touched.
+ * Labels, row lists and centres stay on the device between iterations; the host reads one pair of words per iteration (labels
+ * that moved, NaN).  Workspace, grow-only in the context: O(n + k d + chunks x k) with chunks x k <= max(k, 2^21) words. */
+#define BLISSGPU_KMEANS_MAX_K 65535u
+int blissgpu_kmeans(const float *x, uint64_t n, uint32_t d, const float *init, uint32_t k, int metric, const float *M,
+                    uint32_t max_iter, uint32_t *labels, float *dist, float *centroids, uint32_t *sizes,
+                    uint32_t *n_iter, int32_t *converged);
+/* Device-resident form (device pointers, d_dist and d_sizes may be NULL; n_iter and converged are HOST pointers).  It
+ * synchronises the context's stream once per iteration and before returning.  d_centroids may be d_init. */
+int blissgpu_kmeans_device(blissgpu_ctx *ctx, const float *d_x, uint64_t n, uint32_t d, const float *d_init, uint32_t k,
+                           int metric, const float *d_M, uint32_t max_iter, uint32_t *d_labels, float *d_dist,
+                           float *d_centroids, uint32_t *d_sizes, uint32_t *n_iter, int32_t *converged);
+
 /* The k nearest candidates of every seed GROUP: closest_to_songs(&group, candidates, metric) cut after k, what
  * Library::playlist_from(&[several songs]).take(k) (src/library.rs:762-842) asks per album, artist, genre or saved playlist,
  * for n_groups groups in one call.  seeds is [group_offsets[n_groups]][d] row-major; group g's seeds are the rows
@@ -755,6 +785,9 @@ int blissgpu_group_forest_plan(const uint64_t *group_offsets, uint64_t n_groups,
 /* The last blissgpu_group_forest_knn call on this context (measurement): host milliseconds spent building and packing forests,
  * host milliseconds spent waiting for the device, and the number of batches.  Any pointer may be NULL. */
 int blissgpu_debug_group_forest_stats(blissgpu_ctx *ctx, double *build_ms, double *wait_ms, uint64_t *n_batches);
+/* The last blissgpu_kmeans_device call on this context: the device-to-host copies made inside its loop (one per assignment: the
+ * pair of flag words) and their bytes.  Either pointer may be NULL. */
+int blissgpu_debug_kmeans_stats(blissgpu_ctx *ctx, uint64_t *loop_copies, uint64_t *loop_bytes);
 
 /* FeaturesVersion::feature_weights (src/lib.rs:168-173, 209-234): d x d row-major diagonal matrix. */
 int blissgpu_feature_weights(uint32_t features_version, float *M);
