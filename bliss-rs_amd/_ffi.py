@@ -30,6 +30,8 @@ OPT_FOREST_SPLIT, OPT_FOREST_WALK = 13, 14
 OPT_FOREST_GROUP_NODES = 15
 GROUP_OK, GROUP_TOO_FEW_SEEDS = 0, 1
 KMEANS_MAX_K = 65535
+METRIC_FORM_DIAGONAL, METRIC_FORM_FULL = 0, 1
+LEARN_CONVERGED, LEARN_MAX_ITER, LEARN_DIVERGED = 0, 1, 2
 
 _f32p = C.POINTER(C.c_float)
 _f64p = C.POINTER(C.c_double)
@@ -112,6 +114,14 @@ SIGNATURES = {
     "blissgpu_kmeans_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_int, _vp, C.c_uint32, _vp, _vp,
                                          _vp, _vp, _u32p, _i32p]),
     "blissgpu_debug_kmeans_stats": (C.c_int, [_vp, _u64p, _u64p]),
+    "blissgpu_triplet_step": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, C.c_double, _vp, _u64p, _f64p, _vp]),
+    "blissgpu_triplet_step_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, C.c_double, _vp, _u64p,
+                                               _f64p, _vp]),
+    "blissgpu_learn_metric": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, C.c_int, _vp, C.c_double, C.c_double,
+                                        C.c_double, C.c_uint32, _vp, _vp, _vp, _u32p, _u32p, _i32p]),
+    "blissgpu_learn_metric_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, C.c_int, _vp, C.c_double,
+                                               C.c_double, C.c_double, C.c_uint32, _vp, _vp, _vp, _u32p, _u32p, _i32p]),
+    "blissgpu_debug_metric_stats": (C.c_int, [_vp, _u64p, _u64p, _u64p]),
     "blissgpu_group_knn": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, C.c_uint32, _vp,
                                      _vp]),
     "blissgpu_group_knn_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp,

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "metric_learn.hpp"
 #include "forest.hpp"
 
 using namespace bg;
@@ -30,6 +31,7 @@ const char kJourneyStepName[] = "journey_step_kernel";  // KX_JOURNEY_STEP
 const char kKmeansAssignName[] = "kmeans_assign_kernel", kKmeansHistName[] = "kmeans_hist_kernel";
 const char kKmeansScanTilesName[] = "kmeans_scan_tiles_kernel", kKmeansScanAddName[] = "kmeans_scan_add_kernel";
 const char kKmeansScatterName[] = "kmeans_scatter_kernel", kKmeansSelectName[] = "kmeans_select_kernel";
+const char kTripletStepName[] = "triplet_step_kernel", kTripletReduceName[] = "triplet_reduce_kernel";  // KX_TRIPLET_*
 const char* const kKernelNames[K_COUNT] = {
     "fft512_kernel",     "onset_kernel",      "beat_kernel",   "stft8192_kernel", "tune_select_kernel",
     "tune_pass2_kernel", "tune_final_kernel", "chroma_kernel",     "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel", "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel",
@@ -40,6 +42,7 @@ const char* const kKernelNames[K_COUNT] = {
     "chain_step_kernel", "chain_walk_kernel",
     kSegmentMeanName, kAlbumKnnScanName,
     kKmeansAssignName, kKmeansHistName, kKmeansScanTilesName, kKmeansScanAddName, kKmeansScatterName, kKmeansSelectName,
+    kTripletStepName, kTripletReduceName,
     kGroupForestScanName, kJourneyStepName};
 }  // namespace
 
@@ -348,7 +351,7 @@ int blissgpu_ctx_destroy(blissgpu_ctx* c) {
         (void)hipFree(c->bt_rwv); (void)hipFree(c->bt_dfwv); (void)hipFree(c->chroma_bank);
         scheduler_release(c);
         c->dbg_tuning.release(); c->dbg_nbpms.release(); c->dbg_chroma.release(); c->dbg_interval.release();
-        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->km_ws.release(); c->pl_next.release(); c->st_idx.release();
+        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->km_ws.release(); c->mt_ws.release(); c->pl_next.release(); c->st_idx.release();
         c->st_a.release(); c->st_b.release(); c->st_m.release(); c->st_dist.release(); c->st_out.release();
         c->fl_bytes.release(); c->fl_tab.release(); c->fl_pcm.release(); c->fl_status.release(); c->fl_end.release();
         c->fl_bad.release(); c->fl_mono.release(); c->fl_rows.release(); c->fl_htab.release();
@@ -1105,6 +1108,204 @@ int blissgpu_kmeans(const float* x, uint64_t n, uint32_t d, const float* init, u
     }
     (void)hipStreamSynchronize(c->stream);
     return rc;
+}
+
+// ---- triplet metric learning (kernels_metric.hip, metric_learn.hpp): one gradient evaluation on the device, and the projected
+// gradient loop around it with X and the triplets resident; the host holds the d x d state ----
+static int triplet_args_ok(const char* who, const void* x, uint64_t n, uint32_t d, const void* triplets, uint64_t T, double margin) {
+    if (d == 0 || d > 64) return fail(BLISSGPU_ERR_INVALID, who, "d must be 1 .. 64");
+    if (!(margin >= 0.0) || !std::isfinite(margin)) return fail(BLISSGPU_ERR_INVALID, who, "margin must be finite and >= 0");
+    if (n >= 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "n must be below 2^32 - 1 rows");
+    if (T >= 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "T must be below 2^32 - 1 triplets");
+    if (T && !triplets) return fail(BLISSGPU_ERR_INVALID, who, "triplets is NULL");
+    if (T && n && !x) return fail(BLISSGPU_ERR_INVALID, who, "x is NULL");
+    return BLISSGPU_OK;
+}
+
+static int learn_args_ok(const char* who, uint32_t d, int form, const float* init, double lr, double reg, const void* M,
+                         const void* n_iter, const void* best_iter, const void* status) {
+    if (form != BLISSGPU_METRIC_FORM_DIAGONAL && form != BLISSGPU_METRIC_FORM_FULL) return fail(BLISSGPU_ERR_INVALID, who, "unknown form");
+    if (!(reg >= 0.0) || !std::isfinite(reg)) return fail(BLISSGPU_ERR_INVALID, who, "reg must be finite and >= 0");
+    if (!std::isfinite(lr)) return fail(BLISSGPU_ERR_INVALID, who, "lr must be finite");
+    if (init)
+        for (uint32_t r = 0; r < d; r++)
+            if (!(init[r] >= 0.0f) || !std::isfinite(init[r])) return fail(BLISSGPU_ERR_INVALID, who, "init must be finite and >= 0");
+    if (!M || !n_iter || !best_iter || !status) return fail(BLISSGPU_ERR_INVALID, who, "M / n_iter / best_iter / status is NULL");
+    return BLISSGPU_OK;
+}
+
+// the workspace of one evaluation: partials f64 [W][pairs + 1] | counts u64 [W][2] | result f64 [d d + 3] | M f32 [64 x 64]
+struct TripletWs {
+    TripletPlan plan;
+    double *part, *out;
+    unsigned long long* cnt;
+    float* m;
+};
+
+static int triplet_ws(blissgpu_ctx* c, uint64_t T, uint32_t d, TripletWs* w) {
+    w->plan = triplet_plan(T, d);
+    const size_t o_cnt = w->plan.part_doubles, o_out = o_cnt + 2 * (size_t)w->plan.W, o_m = o_out + (size_t)d * d + 3, words = o_m + 2048;
+    int rc = c->mt_ws.ensure(words * sizeof(double));
+    if (rc) return rc;
+    double* base = reinterpret_cast<double*>(c->mt_ws.p);
+    w->part = base;
+    w->cnt = reinterpret_cast<unsigned long long*>(base + o_cnt);
+    w->out = base + o_out;
+    w->m = reinterpret_cast<float*>(base + o_m);
+    return BLISSGPU_OK;
+}
+
+// launches the two kernels and downloads the result block in ONE copy.  T > 0.  h_out: d d + 3 doubles
+static int triplet_eval(blissgpu_ctx* c, const char* who, const TripletWs& w, const float* d_x, uint64_t n, uint32_t d,
+                        const uint32_t* d_trip, uint64_t T, const float* d_M, int mode, double margin, uint8_t* d_flags, double* h_out,
+                        uint64_t* n_active, double* loss) {
+    {
+        Prof p(c, KX_TRIPLET_STEP);
+        launch_triplet_step(d_x, n, d, d_trip, T, d_M, mode, margin, w.plan, d_flags, w.part, w.cnt, c->stream);
+    }
+    {
+        Prof p(c, KX_TRIPLET_REDUCE);
+        launch_triplet_reduce(w.part, w.cnt, w.plan, d, w.out, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    const size_t bytes = ((size_t)d * d + 3) * sizeof(double);
+    HIP_TRY(hipMemcpyAsync(h_out, w.out, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->mt_downloads++;
+    c->mt_bytes += bytes;
+    uint64_t words[2];
+    memcpy(words, h_out + (size_t)d * d + 1, sizeof(words));
+    if (words[1] & TRIPLET_ERR_INDEX) return fail(BLISSGPU_ERR_INVALID, who, "a triplet names a row >= n");
+    if (words[1] & TRIPLET_ERR_NAN) return fail(BLISSGPU_ERR_NAN, who, "NaN hinge");
+    *n_active = words[0];
+    *loss = h_out[(size_t)d * d];
+    return BLISSGPU_OK;
+}
+
+static int m_mode(const float* hM, uint32_t d) {
+    if (!hM) return TRIPLET_M_IDENTITY;
+    return is_diag(hM, d) ? TRIPLET_M_DIAG : TRIPLET_M_FULL;
+}
+
+int blissgpu_triplet_step_device(blissgpu_ctx* c, const float* d_x, uint64_t n, uint32_t d, const uint32_t* d_triplets, uint64_t T,
+                                 const float* d_M, double margin, uint8_t* d_flags, uint64_t* n_active, double* loss, double* G) {
+    const char* who = "blissgpu_triplet_step_device";
+    int rc = triplet_args_ok(who, d_x, n, d, d_triplets, T, margin);
+    if (rc) return rc;
+    if (!n_active || !loss || !G) return fail(BLISSGPU_ERR_INVALID, who, "n_active / loss / G is NULL");
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    if (T == 0) {
+        *n_active = 0;
+        *loss = 0.0;
+        memset(G, 0, (size_t)d * d * sizeof(double));
+        return BLISSGPU_OK;
+    }
+    CTX_ENTER(c, who);
+    std::vector<float> hM;
+    if (d_M) {  // how M is read is decided on its values, as everywhere else
+        hM.resize((size_t)d * d);
+        HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    TripletWs w;
+    if ((rc = triplet_ws(c, T, d, &w))) return rc;
+    std::vector<double> h_out((size_t)d * d + 3);
+    rc = triplet_eval(c, who, w, d_x, n, d, d_triplets, T, d_M, m_mode(d_M ? hM.data() : nullptr, d), margin, d_flags, h_out.data(),
+                      n_active, loss);
+    if (rc) return rc;
+    memcpy(G, h_out.data(), (size_t)d * d * sizeof(double));
+    return BLISSGPU_OK;
+}
+
+// X and the triplets of a host-pointer form, uploaded into the context's staging buffers
+static int stage_triplets(blissgpu_ctx* c, const float* x, uint64_t n, uint32_t d, const uint32_t* triplets, uint64_t T) {
+    int rc = c->st_b.ensure(std::max<size_t>(n * d, 1));
+    if (!rc) rc = c->st_idx.ensure(3 * T);
+    if (rc) return rc;
+    if (n) HIP_TRY(hipMemcpyAsync(c->st_b.p, x, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->st_idx.p, triplets, 3 * T * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    return BLISSGPU_OK;
+}
+
+int blissgpu_triplet_step(const float* x, uint64_t n, uint32_t d, const uint32_t* triplets, uint64_t T, const float* M, double margin,
+                          uint8_t* flags, uint64_t* n_active, double* loss, double* G) {
+    const char* who = "blissgpu_triplet_step";
+    int rc = triplet_args_ok(who, x, n, d, triplets, T, margin);
+    if (rc) return rc;
+    if (!n_active || !loss || !G) return fail(BLISSGPU_ERR_INVALID, who, "n_active / loss / G is NULL");
+    if (T == 0) {
+        *n_active = 0;
+        *loss = 0.0;
+        memset(G, 0, (size_t)d * d * sizeof(double));
+        return BLISSGPU_OK;
+    }
+    blissgpu_ctx* c;
+    if ((rc = default_ctx(&c))) return rc;
+    CTX_ENTER(c, who);
+    TripletWs w;
+    if ((rc = triplet_ws(c, T, d, &w))) return rc;
+    if ((rc = stage_triplets(c, x, n, d, triplets, T))) return rc;
+    if (M) HIP_TRY(hipMemcpyAsync(w.m, M, (size_t)d * d * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    uint8_t* d_flags = nullptr;
+    if (flags) {
+        if ((rc = c->st_out.ensure(T))) return rc;
+        d_flags = c->st_out.p;
+    }
+    std::vector<double> h_out((size_t)d * d + 3);
+    rc = triplet_eval(c, who, w, c->st_b.p, n, d, c->st_idx.p, T, M ? w.m : nullptr, m_mode(M, d), margin, d_flags, h_out.data(),
+                      n_active, loss);
+    if (rc) return rc;
+    memcpy(G, h_out.data(), (size_t)d * d * sizeof(double));
+    if (flags) {
+        HIP_TRY(hipMemcpyAsync(flags, d_flags, T, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return BLISSGPU_OK;
+}
+
+int blissgpu_learn_metric_device(blissgpu_ctx* c, const float* d_x, uint64_t n, uint32_t d, const uint32_t* d_triplets, uint64_t T,
+                                 int form, const float* init, double margin, double lr, double reg, uint32_t max_iter, float* M,
+                                 double* obj, uint64_t* active, uint32_t* n_iter, uint32_t* best_iter, int32_t* status) {
+    const char* who = "blissgpu_learn_metric_device";
+    int rc = triplet_args_ok(who, d_x, n, d, d_triplets, T, margin);
+    if (!rc) rc = learn_args_ok(who, d, form, init, lr, reg, M, n_iter, best_iter, status);
+    if (rc) return rc;
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    CTX_ENTER(c, who);
+    TripletWs w{};
+    if (T && (rc = triplet_ws(c, T, d, &w))) return rc;
+    c->mt_uploads = c->mt_downloads = c->mt_bytes = 0;
+    std::vector<double> h_out((size_t)d * d + 3);
+    const size_t m_bytes = (size_t)d * d * sizeof(float);
+    auto step = [&](const float* hM, double* loss, uint64_t* act, double* G) -> int {
+        if (T == 0) {  // no triplet: no hinge
+            *loss = 0.0;
+            *act = 0;
+            return BLISSGPU_OK;
+        }
+        // (pageable memory: the copy has left hM when the call returns)
+        HIP_TRY(hipMemcpyAsync(w.m, hM, m_bytes, hipMemcpyHostToDevice, c->stream));
+        c->mt_uploads++;
+        int r = triplet_eval(c, who, w, d_x, n, d, d_triplets, T, w.m, m_mode(hM, d), margin, nullptr, h_out.data(), act, loss);
+        if (!r) memcpy(G, h_out.data(), (size_t)d * d * sizeof(double));
+        return r;
+    };
+    return bg::metric::learn(form, d, init, T, lr, reg, max_iter, step, M, obj, active, n_iter, best_iter, status);
+}
+
+int blissgpu_learn_metric(const float* x, uint64_t n, uint32_t d, const uint32_t* triplets, uint64_t T, int form, const float* init,
+                          double margin, double lr, double reg, uint32_t max_iter, float* M, double* obj, uint64_t* active,
+                          uint32_t* n_iter, uint32_t* best_iter, int32_t* status) {
+    const char* who = "blissgpu_learn_metric";
+    int rc = triplet_args_ok(who, x, n, d, triplets, T, margin);
+    if (!rc) rc = learn_args_ok(who, d, form, init, lr, reg, M, n_iter, best_iter, status);
+    if (rc) return rc;
+    blissgpu_ctx* c;
+    if ((rc = default_ctx(&c))) return rc;
+    CTX_ENTER(c, who);
+    if (T && (rc = stage_triplets(c, x, n, d, triplets, T))) return rc;
+    return blissgpu_learn_metric_device(c, c->st_b.p, n, d, c->st_idx.p, T, form, init, margin, lr, reg, max_iter, M, obj, active,
+                                        n_iter, best_iter, status);
 }
 
 // ---- k nearest candidates per seed GROUP: closest_to_songs(&group, candidates, metric) cut after k (src/playlist.rs:36-59,
@@ -2347,6 +2548,15 @@ int blissgpu_debug_kmeans_stats(blissgpu_ctx* c, uint64_t* loop_copies, uint64_t
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     if (loop_copies) *loop_copies = c->km_loop_copies;
     if (loop_bytes) *loop_bytes = c->km_loop_bytes;
+    return BLISSGPU_OK;
+}
+
+int blissgpu_debug_metric_stats(blissgpu_ctx* c, uint64_t* loop_uploads, uint64_t* loop_downloads, uint64_t* loop_bytes) {
+    if (!c) return fail(BLISSGPU_ERR_INVALID, "blissgpu_debug_metric_stats", "ctx is NULL");
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    if (loop_uploads) *loop_uploads = c->mt_uploads;
+    if (loop_downloads) *loop_downloads = c->mt_downloads;
+    if (loop_bytes) *loop_bytes = c->mt_bytes;
     return BLISSGPU_OK;
 }
 

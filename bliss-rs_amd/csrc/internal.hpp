@@ -123,19 +123,21 @@ enum KernelId : int {
     K_CHAIN_STEP, K_CHAIN_WALK,             // song-to-song chains cut after k (kernels_chains.hip)
     // (tests/test_chains_host.py holds this list, and the list of names beside it, to end in the chain kernels: the kernels
     // that came later are numbered behind it, so that no older id or name moves)
-    K_COUNT = K_CHAIN_WALK + 11
+    K_COUNT = K_CHAIN_WALK + 13
 };
 // k-nearest albums per seed group (kernels_albums.hip; its partial lists are merged by knn_merge_kernel)
 constexpr int KX_SEGMENT_MEAN = K_CHAIN_WALK + 1, KX_ALBUM_KNN_SCAN = K_CHAIN_WALK + 2;
 // k-means of a library (kernels_kmeans.hip): the nearest centre of every song, the counting sort of the labels, the select
 constexpr int KX_KMEANS_ASSIGN = K_CHAIN_WALK + 3, KX_KMEANS_HIST = K_CHAIN_WALK + 4, KX_KMEANS_SCAN_TILES = K_CHAIN_WALK + 5,
               KX_KMEANS_SCAN_ADD = K_CHAIN_WALK + 6, KX_KMEANS_SCATTER = K_CHAIN_WALK + 7, KX_KMEANS_SELECT = K_CHAIN_WALK + 8;
+// one gradient evaluation of triplet metric learning (kernels_metric.hip): the wavefronts' partials, their ascending sum
+constexpr int KX_TRIPLET_STEP = K_CHAIN_WALK + 9, KX_TRIPLET_REDUCE = K_CHAIN_WALK + 10;
 // (tests/test_journeys_host.py holds the profile table to END in the next two names: kernels that come later are numbered in
 // front of them; every consumer of the table goes by name)
 // the k lowest forest scores per seed group (kernels_forest.hip; its partial lists are merged by group_knn_merge_kernel)
-constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 9;
+constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 11;
 // a journey's step (kernels_chains.hip: the chains' scan with a waypoint query or a gate)
-constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 10;
+constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 12;
 static_assert(KX_JOURNEY_STEP + 1 == K_COUNT, "every kernel id is below the count");
 
 // lower_bound on a prefix array: largest s with prefix[s] <= x  (prefix has n+1 entries, prefix[0]=0)
@@ -358,6 +360,21 @@ void launch_kmeans_scatter(const uint32_t* labels, uint32_t n, uint32_t K, const
                            hipStream_t st);
 void launch_kmeans_select(const float* prev, float* next, const uint32_t* arow_off, uint32_t K, uint32_t d, uint32_t* sizes,
                           hipStream_t st);
+// triplet metric learning, one gradient evaluation (kernels_metric.hip).  The triplets are dealt out in W contiguous chunks, a
+// function of T alone; part [W][pairs + 1] f64 and cnt [W][2] u64 are the wavefronts' partials, out = G f64 [d][d] | loss f64 |
+// n_active u64 | error bits u64 (TRIPLET_ERR_*).  mode says how M is read; flags (u8 [T]) may be NULL
+constexpr int TRIPLET_M_FULL = 0, TRIPLET_M_DIAG = 1, TRIPLET_M_IDENTITY = 2;
+constexpr uint32_t TRIPLET_ERR_INDEX = 1u, TRIPLET_ERR_NAN = 2u;
+struct TripletPlan {
+    uint32_t W, chunk;      // wavefronts (one workgroup each) and the triplets of each, a multiple of 64
+    uint32_t pairs;         // d (d + 1) / 2
+    uint64_t part_doubles;  // W * (pairs + 1)
+};
+TripletPlan triplet_plan(uint64_t T, uint32_t d);
+void launch_triplet_step(const float* X, uint64_t n, uint32_t d, const uint32_t* trip, uint64_t T, const float* M, int mode,
+                         double margin, const TripletPlan& p, uint8_t* flags, double* part, unsigned long long* cnt, hipStream_t st);
+void launch_triplet_reduce(const double* part, const unsigned long long* cnt, const TripletPlan& p, uint32_t d, double* out,
+                           hipStream_t st);
 // song-to-song chains cut after k, one per seed group (kernels_chains.hip).  Step 0 is the group search with k = 1; a later step
 // t reads idx[chain][0 .. t) and writes idx / dist [chain][t], directly or -- several workgroups per chain -- through the
 // 64-bit minima best[n_chains] (all KNN_NONE before the first step; reset by the step's second launch).  A NaN among the

@@ -512,6 +512,65 @@ class Context:
         _ffi.check(self._L.blissgpu_debug_kmeans_stats(self._h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def triplet_step(self, X, triplets, M=None, margin: float = 0.0, return_flags: bool = False):
+        """One gradient evaluation of triplet metric learning (blissgpu_triplet_step_device) on device tensors:
+        X float32 [n, d], triplets int32 [T, 3] as (a, b, o) (int64 is converted), M float32 [d, d] or None for the identity.
+        -> (n_active, loss, G float64 numpy [d, d]) and, return_flags, a uint8 tensor [T] on the device.  Synchronises."""
+        torch = self.torch
+        assert X.is_cuda and X.dtype == torch.float32 and X.dim() == 2
+        X = X.contiguous()
+        triplets = triplets.to(torch.int32).contiguous() if triplets.dtype != torch.int32 else triplets.contiguous()
+        assert triplets.is_cuda and (triplets.numel() == 0 or (triplets.dim() == 2 and triplets.shape[1] == 3))
+        (n, d), T = X.shape, triplets.numel() // 3
+        if M is not None:
+            assert M.is_cuda and M.dtype == torch.float32 and tuple(M.shape) == (d, d)
+            M = M.contiguous()
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        flags = torch.zeros((T,), dtype=torch.uint8, device=X.device) if return_flags else None
+        G = np.zeros((d, d), np.float64)
+        n_active, loss = C.c_uint64(0), C.c_double(0.0)
+        self._pre()
+        _ffi.check(self._L.blissgpu_triplet_step_device(self._h, ptr(X), n, d, ptr(triplets) if T else None, T, ptr(M), float(margin),
+                                                        ptr(flags) if T else None, C.byref(n_active), C.byref(loss), G.ctypes.data))
+        self._post()
+        out = (int(n_active.value), float(loss.value), G)
+        return out + (flags,) if return_flags else out
+
+    def learn_metric(self, X, triplets, form: str = "full", init=None, margin: float = None, lr: float = None, reg: float = 0.0,
+                     max_iter: int = None):
+        """playlist.learn_metric on device tensors (blissgpu_learn_metric_device): X float32 [n, d] and triplets int32 [T, 3]
+        stay where they are, an iteration uploads M and downloads the gradient.  init: d host weights or None.
+        -> playlist.LearnedMetric (host arrays)."""
+        from . import playlist as P
+
+        torch = self.torch
+        margin = P.LEARN_MARGIN if margin is None else margin
+        lr = P.LEARN_LR if lr is None else lr
+        max_iter = P.LEARN_MAX_ITER if max_iter is None else max_iter
+        assert X.is_cuda and X.dtype == torch.float32 and X.dim() == 2
+        X = X.contiguous()
+        triplets = triplets.to(torch.int32).contiguous() if triplets.dtype != torch.int32 else triplets.contiguous()
+        assert triplets.is_cuda
+        (n, d), T = X.shape, triplets.numel() // 3
+        init, max_iter = P._learn_args(form, init, d, max_iter)
+        M, obj, act = np.zeros((d, d), np.float32), np.zeros(max_iter + 1, np.float64), np.zeros(max_iter + 1, np.uint64)
+        n_iter, best_iter, status = C.c_uint32(0), C.c_uint32(0), C.c_int32(0)
+        self._pre()
+        _ffi.check(self._L.blissgpu_learn_metric_device(self._h, C.c_void_p(X.data_ptr()), n, d,
+                                                        C.c_void_p(triplets.data_ptr()) if T else None, T, P._FORMS[form],
+                                                        None if init is None else init.ctypes.data, float(margin), float(lr),
+                                                        float(reg), max_iter, M.ctypes.data, obj.ctypes.data, act.ctypes.data,
+                                                        C.byref(n_iter), C.byref(best_iter), C.byref(status)))
+        self._post()
+        return P._learned(M, obj, act, n_iter, best_iter, status)
+
+    def metric_stats(self):
+        """(uploads, downloads, bytes downloaded) inside the loop of the last learn_metric on this context: one M up and one
+        result block down per gradient evaluation."""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _ffi.check(self._L.blissgpu_debug_metric_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
     def group_weights(self, S, offsets):
         """variance_based_weight_matrix (src/playlist.rs:173-221) of every seed group on the device: group g's seeds are the
         rows offsets[g] .. offsets[g + 1] of S (offsets: a HOST sequence of G + 1 integers starting at 0).  -> (weights float32

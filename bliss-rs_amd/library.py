@@ -32,6 +32,10 @@ database:
                                           library, one device call (playlist.duplicate_labels); nothing is deleted
     cluster_songs                         the k groups the library falls into (k-means on the device, playlist.cluster_songs),
                                           every group's songs with the most typical first
+    training_triplets, store_training_triplet   the crate's `training_triplet` table ("song_1 and song_2 are closer together
+                                          than they are to odd_one_out", src/library.rs:542-556) as row indices, and a writer
+    learn_metric                          a Mahalanobis M for MahalanobisBuilder, learned on the device from those triplets
+                                          or from triplets drawn from genre / album / artist / cluster labels
 
 SQLite stores `real` as f64; an f32 feature widens exactly on the way in and narrows exactly on the way out, so a
 round trip is bit-exact.  The schema, load and store helpers are host code; the playlists run their distances on the
@@ -622,6 +626,84 @@ def cluster_songs(db: Conn, k: int, seed: int = 0, metric_builder=playlist.eucli
     clustering = playlist.cluster_songs(songs, k, seed, metric_builder, max_iter, init)
     lists = [[songs[int(i)] for i in clustering.members(c)] for c in range(len(clustering.sizes))]
     return (lists, clustering) if return_clustering else lists
+
+
+def _has_triplet_table(conn) -> bool:
+    return conn.execute("select count(*) from sqlite_master where type = 'table' and name = 'training_triplet'").fetchone()[0] > 0
+
+
+def training_triplets(db: Conn, features_version: FeaturesVersion = FeaturesVersion.LATEST) -> np.ndarray:
+    """The `training_triplet` table (src/library.rs:542-556: song_1 and song_2 are closer together than they are to
+    odd_one_out) as int64[T, 3] row indices (a, b, o) into load_feature_matrix(db, features_version), in id order.  A database
+    without the table (create_schema makes none; upgrade of an older file does), or a triplet one of whose songs is not analysed
+    at that version, contributes nothing."""
+    conn, own = _connect(db)
+    try:
+        if not _has_triplet_table(conn):
+            return np.zeros((0, 3), np.int64)
+        ids = [r[0] for r in conn.execute("select id from song where analyzed = true and version = ? order by id",
+                                          (int(FeaturesVersion(features_version)),))]
+        rows = conn.execute("select song_1_id, song_2_id, odd_one_out_id from training_triplet order by id").fetchall()
+    finally:
+        if own:
+            conn.close()
+    row_of = {int(i): k for k, i in enumerate(ids)}
+    out = [[row_of[int(v)] for v in r] for r in rows if all(int(v) in row_of for v in r)]
+    return np.asarray(out, np.int64).reshape(len(out), 3)
+
+
+def store_training_triplet(db: Conn, path_1: str, path_2: str, odd_one_out_path: str) -> None:
+    """One answer of a survey: the songs at path_1 and path_2 are closer together than either is to odd_one_out_path.  The
+    table is created (the crate's migration 4, as it is) when the database has none; an unknown path is a ProviderError."""
+    conn, own = _connect(db)
+    try:
+        ids = []
+        for p in (path_1, path_2, odd_one_out_path):
+            row = conn.execute("select id from song where path = ?", (p,)).fetchone()
+            if row is None:
+                raise ProviderError(f"song '{p}' is not in the library")
+            ids.append(int(row[0]))
+        if not _has_triplet_table(conn):
+            conn.execute(_MIGRATIONS[3])
+        conn.execute("insert into training_triplet (song_1_id, song_2_id, odd_one_out_id) values (?, ?, ?)", ids)
+        conn.commit()
+    finally:
+        if own:
+            conn.close()
+
+
+_LABEL_COLUMNS = ("genre", "album", "artist", "album_artist")
+
+
+def learn_metric(db: Conn, source="triplets", form: str = "full", n_triplets: int = None, seed: int = 0, init=None,
+                 margin: float = playlist.LEARN_MARGIN, lr: float = playlist.LEARN_LR, reg: float = 0.0,
+                 max_iter: int = playlist.LEARN_MAX_ITER, return_result: bool = False):
+    """A Mahalanobis matrix for the library, learned on the device (playlist.learn_metric) -> M float32[d, d], ready for
+    playlist.MahalanobisBuilder; `return_result`: -> the whole playlist.LearnedMetric.
+    source: "triplets" -- the training_triplet table (training_triplets); "genre" / "album" / "artist" / "album_artist" --
+    triplets drawn from that column (two songs that share it, one that does not; a song whose value is NULL takes no part);
+    a label per analysed song in load_feature_matrix order (an integer array, < 0: no label); or a playlist.Clustering.
+    `n_triplets` labelled triplets are drawn with `seed` (playlist.triplets_from_labels; default 10 per song, at least 1000).
+    The songs are those of FeaturesVersion.LATEST.  No usable triplet is a ValueError."""
+    songs, X = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
+    if isinstance(source, str) and source == "triplets":
+        triplets = training_triplets(db)
+    else:
+        if isinstance(source, str):
+            if source not in _LABEL_COLUMNS:
+                raise ValueError(f"source must be 'triplets', one of {_LABEL_COLUMNS}, a label array or a Clustering")
+            code = {}
+            labels = np.asarray([-1 if getattr(s, source) is None else code.setdefault(getattr(s, source), len(code)) for s in songs],
+                                np.int64)
+        else:
+            labels = np.asarray(source.labels if isinstance(source, playlist.Clustering) else source, np.int64).reshape(-1)
+            if labels.shape[0] != len(songs):
+                raise ValueError("a label per analysed song is needed")
+        triplets = playlist.triplets_from_labels(labels, max(1000, 10 * len(songs)) if n_triplets is None else n_triplets, seed)
+    if triplets.shape[0] == 0:
+        raise ValueError("learn_metric found no training triplet")
+    res = playlist.learn_metric(X, triplets, form, init, margin, lr, reg, max_iter)
+    return res if return_result else res.m
 
 
 def album_playlist_from(db: Conn, album_title: str, number_albums: int) -> List[Song]:

@@ -12,6 +12,8 @@
     closest_album_to_group                                       :424-485
     journey_order, waypoint_playlist, directed_playlist (the waypoint and direction features of the reference's TODO.md)
     kmeans, kmeans_init, cluster_songs (the clustering the reference's TODO.md asks for: Lloyd's algorithm on the device)
+    triplet_step, learn_metric, triplet_accuracy, triplets_from_labels (the metric learning the reference's TODO.md and its
+    training_triplet table ask for: a Mahalanobis M from "a and b are closer than o" triplets, the gradient on the device)
 
 A metric builder is one of the strings "euclidean" / "cosine", a `MahalanobisBuilder` (or the pair
 ("mahalanobis", M)), a `ForestOptions` (closest_to_songs and library.playlist_from_custom only: the forest needs at
@@ -598,6 +600,149 @@ def cluster_songs(songs, k, seed=0, metric_builder=euclidean_distance, max_iter=
         raise ValueError("cluster_songs needs at least one song")
     X = _matrix(songs)
     return Clustering(*kmeans(X, kmeans_init(X, k, seed, init), max_iter, metric, m))
+
+
+def _triplet_args(X, triplets, m):
+    X = np.ascontiguousarray(np.atleast_2d(X), dtype=np.float32)
+    tr = np.asarray(triplets)
+    if tr.size and (tr.min() < 0 or tr.max() > 0xFFFFFFFF):
+        raise ValueError("triplets must be row indices")
+    tr = np.ascontiguousarray(tr, dtype=np.uint32).reshape(-1, 3)
+    if m is not None:
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        if m.shape != (X.shape[1], X.shape[1]):
+            raise ValueError("m must be [d, d]")
+    return X, tr, m
+
+
+def triplet_step(X, triplets, m=None, margin=0.0, return_flags=False):
+    """One gradient evaluation of triplet metric learning on the device (blissgpu_triplet_step).  A triplet
+    (a, b, o) of rows of X says "a and b are closer together than either is to o"; with u = x_a - x_b, v = x_a - x_o,
+    w = x_b - x_o and q(t) = t' m t (m None: the identity) its hinges are h1 = margin + q(u) - q(v), h2 = margin + q(u) - q(w).
+    -> (n_active, loss, G float64[d, d]) or, return_flags, (n_active, loss, G, flags uint8[T]) with flags = (h1 > 0) |
+    (h2 > 0) << 1: the number of hinges above 0, their sum, and the sum over the active hinges of u u' - v v' (u u' - w w'),
+    the gradient of the loss in m.  All f64.  An index past the rows or a negative margin raises BlissGpuError(ERR_INVALID), a
+    NaN hinge ValueError."""
+    X, tr, m = _triplet_args(X, triplets, m)
+    (n, d), T = X.shape, tr.shape[0]
+    G, flags = np.zeros((d, d), np.float64), np.zeros(T, np.uint8)
+    n_active, loss = C.c_uint64(0), C.c_double(0.0)
+    try:
+        _ffi.check(_ffi.lib().blissgpu_triplet_step(X.ctypes.data, n, d, tr.ctypes.data if T else None, T,
+                                                    None if m is None else m.ctypes.data, float(margin),
+                                                    flags.ctypes.data if return_flags and T else None, C.byref(n_active),
+                                                    C.byref(loss), G.ctypes.data))
+    except _ffi.BlissGpuError as e:
+        _nan_to_panic(e)
+    out = (int(n_active.value), float(loss.value), G)
+    return out + (flags,) if return_flags else out
+
+
+_FORMS = {"diagonal": _ffi.METRIC_FORM_DIAGONAL, "full": _ffi.METRIC_FORM_FULL}
+_LEARN_STATUS = {_ffi.LEARN_CONVERGED: "converged", _ffi.LEARN_MAX_ITER: "max_iter", _ffi.LEARN_DIVERGED: "diverged"}
+# DESIGN.md 3.22 has the table behind these (planted metrics, numpy on a CPU); nobody has measured them on a real library
+LEARN_MARGIN, LEARN_LR, LEARN_MAX_ITER = 0.1, 1.0, 100
+
+
+class LearnedMetric:
+    """The result of learn_metric: m float32[d, d] (the iterate with the lowest objective, positive semi-definite by
+    construction), objective float64[n_iter + 1], active int64[n_iter + 1] (hinges above 0 per iteration), n_iter (updates
+    made), best_iter, status ("converged": no active hinge; "max_iter"; "diverged": the objective or m left the finite numbers)."""
+
+    def __init__(self, m, objective, active, n_iter, best_iter, status):
+        self.m = np.asarray(m, dtype=np.float32)
+        self.objective = np.asarray(objective, dtype=np.float64)
+        self.active = np.asarray(active, dtype=np.int64)
+        self.n_iter, self.best_iter, self.status = int(n_iter), int(best_iter), str(status)
+
+    def builder(self) -> "MahalanobisBuilder":
+        return MahalanobisBuilder(self.m)
+
+    def __repr__(self):
+        return (f"LearnedMetric(d={self.m.shape[0]}, n_iter={self.n_iter}, best_iter={self.best_iter}, status={self.status!r}, "
+                f"objective={self.objective[self.best_iter] if self.objective.size else float('nan'):.6g})")
+
+
+def _learn_args(form, init, d, max_iter):
+    if form not in _FORMS:
+        raise ValueError(f"form must be one of {tuple(_FORMS)}")
+    max_iter = int(max_iter)
+    if max_iter < 0:
+        raise ValueError("max_iter must be at least 0")
+    if init is not None:
+        init = np.ascontiguousarray(init, dtype=np.float32).reshape(-1)
+        if init.shape[0] != d:
+            raise ValueError("init must hold d weights (the diagonal of the starting matrix)")
+    return init, max_iter
+
+
+def _learned(M, obj, act, n_iter, best_iter, status):
+    k = int(n_iter.value) + 1
+    res = LearnedMetric(M, obj[:k].copy(), act[:k].astype(np.int64), n_iter.value, best_iter.value, _LEARN_STATUS[status.value])
+    if res.status == "diverged":
+        import warnings
+
+        warnings.warn(f"learn_metric diverged at iteration {res.n_iter}; m is iteration {res.best_iter}'s: lower lr", RuntimeWarning,
+                      stacklevel=3)
+    return res
+
+
+def learn_metric(X, triplets, form="full", init=None, margin=LEARN_MARGIN, lr=LEARN_LR, reg=0.0, max_iter=LEARN_MAX_ITER) -> LearnedMetric:
+    """Learn a Mahalanobis matrix from training triplets (blissgpu_learn_metric): projected gradient descent
+    on  sum of the hinges / (2 T) + reg * |m - m_0|^2  over m = diag(w), w >= 0 (form "diagonal") or m = L'L (form "full"),
+    starting from m_0 = diag(init) (None: the identity; FeaturesVersion.feature_weights' diagonal is the obvious other start).
+    X and the triplets stay on the device; an iteration uploads m and downloads the gradient.  -> LearnedMetric; `.m` goes into
+    MahalanobisBuilder.  A RuntimeWarning says when the run diverged (m is then the best iterate before that)."""
+    X, tr, _ = _triplet_args(X, triplets, None)
+    (n, d), T = X.shape, tr.shape[0]
+    init, max_iter = _learn_args(form, init, d, max_iter)
+    M, obj, act = np.zeros((d, d), np.float32), np.zeros(max_iter + 1, np.float64), np.zeros(max_iter + 1, np.uint64)
+    n_iter, best_iter, status = C.c_uint32(0), C.c_uint32(0), C.c_int32(0)
+    try:
+        _ffi.check(_ffi.lib().blissgpu_learn_metric(X.ctypes.data, n, d, tr.ctypes.data if T else None, T, _FORMS[form],
+                                                    None if init is None else init.ctypes.data, float(margin), float(lr),
+                                                    float(reg), max_iter, M.ctypes.data, obj.ctypes.data, act.ctypes.data,
+                                                    C.byref(n_iter), C.byref(best_iter), C.byref(status)))
+    except _ffi.BlissGpuError as e:
+        _nan_to_panic(e)
+    return _learned(M, obj, act, n_iter, best_iter, status)
+
+
+def triplet_accuracy(X, triplets, m=None) -> float:
+    """The share of the 2 T constraints d(a, b) < d(a, o), d(a, b) < d(b, o) that hold under m (None: euclidean): 1 - the
+    active hinges of triplet_step at margin 0 over 2 T.  No triplet: 1.0."""
+    T = np.asarray(triplets).reshape(-1, 3).shape[0]
+    if T == 0:
+        return 1.0
+    return 1.0 - triplet_step(X, triplets, m, 0.0)[0] / (2.0 * T)
+
+
+def triplets_from_labels(labels, n_triplets, seed=0) -> np.ndarray:
+    """n_triplets training triplets (a, b, o) drawn from class labels (genre, album, artist, a k-means label per song): a and b
+    are two DISTINCT rows of one label, o is a row of another label.  int64[n_triplets, 3]; host numpy, a function of its
+    arguments only (numpy.random.default_rng(seed)).  Rows with a label < 0 take no part.  The label of (a, b) is drawn in
+    proportion to its number of pairs, o uniformly from the rows outside it.  ValueError when fewer than two labels are present
+    or no label has two rows."""
+    labels = np.asarray(labels).reshape(-1).astype(np.int64)
+    n_triplets = int(n_triplets)
+    if n_triplets < 0:
+        raise ValueError("n_triplets must be at least 0")
+    rows = np.flatnonzero(labels >= 0)
+    order = rows[np.argsort(labels[rows], kind="stable")]  # rows grouped by label, ascending inside a label
+    values, start, count = np.unique(labels[order], return_index=True, return_counts=True)
+    if values.size < 2:
+        raise ValueError("triplets_from_labels needs at least two different labels")
+    pairs = count.astype(np.float64) * (count - 1)
+    if not (pairs > 0).any():
+        raise ValueError("triplets_from_labels needs a label with at least two rows")
+    rng = np.random.default_rng(int(seed))
+    g = rng.choice(values.size, n_triplets, p=pairs / pairs.sum())
+    ia = rng.integers(0, count[g])
+    ib = rng.integers(0, count[g] - 1)
+    ib = ib + (ib >= ia)  # the other rows of the label, uniformly
+    io = rng.integers(0, order.size - count[g])
+    io = np.where(io >= start[g], io + count[g], io)  # the rows outside the label's block of `order`
+    return np.stack([order[start[g] + ia], order[start[g] + ib], order[io]], axis=1).astype(np.int64).reshape(n_triplets, 3)
 
 
 def _seed_groups(seed_groups):

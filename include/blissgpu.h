@@ -453,6 +453,59 @@ int blissgpu_kmeans_device(blissgpu_ctx *ctx, const float *d_x, uint64_t n, uint
                            int metric, const float *d_M, uint32_t max_iter, uint32_t *d_labels, float *d_dist,
                            float *d_centroids, uint32_t *d_sizes, uint32_t *n_iter, int32_t *converged);
 
+/* ---- Learning the Mahalanobis matrix from training triplets ----
+ * The reference has a `training_triplet` table ("song_1 and song_2 are closer together than they are to odd_one_out",
+ * src/library.rs:542-556), a TODO.md that asks for "a way to learn a metric with a user survey", and no code that learns.
+ *
+ * ONE STEP.  x [n][d] f32, 1 <= d <= 64; triplets [T][3] u32 as (a, b, o); M [d][d] f32, NULL = the identity; margin >= 0.
+ * All arithmetic is f64, every multiply and every add rounded on its own, sums ascending from 0.0.  For one triplet
+ *   u[r] = (double)x[a][r] - (double)x[b][r],  v the same for (a, o),  w for (b, o);
+ *   q(t) = sum_r t[r] * s_r  with  s_r = sum_c (double)M[r][c] * t[c];
+ *   h1 = (margin + q(u)) - q(v),  h2 = (margin + q(u)) - q(w);  f1 = h1 > 0,  f2 = h2 > 0  (a hinge of exactly 0 is inactive).
+ * Outputs: flags [T] u8 (may be NULL) = f1 | f2 << 1;  *n_active = sum(f1 + f2);  *loss = sum(f1 h1 + f2 h2);
+ * G [d][d] f64 = sum((f1 + f2) u u' - f1 v v' - f2 w w'), exactly symmetric.  flags and n_active are exact by this contract: a
+ * diagonal M (detected as everywhere) and the identity take a shorter route that gives the same bits.  loss and G are f64 sums
+ * of those terms (every product of G rounded once) in an order that is a function of (T, d) alone: no floating-point atomics,
+ * two calls return identical bits.
+ * T == 0: BLISSGPU_OK with zero outputs.  A triplet with an index >= n: BLISSGPU_ERR_INVALID, found on the device, which reads
+ * nothing outside x.  A NaN hinge: BLISSGPU_ERR_NAN.  a == b, b == o and the like are legal.  n, T < 2^32 - 1.  The arguments are
+ * checked before the device is touched; n_active, loss and G must not be NULL. */
+int blissgpu_triplet_step(const float *x, uint64_t n, uint32_t d, const uint32_t *triplets, uint64_t T, const float *M,
+                          double margin, uint8_t *flags, uint64_t *n_active, double *loss, double *G);
+/* Device-resident form: d_x, d_triplets, d_M and d_flags are device pointers; n_active, loss and G are HOST pointers (one
+ * download of d d + 3 words).  Synchronises the context's stream. */
+int blissgpu_triplet_step_device(blissgpu_ctx *ctx, const float *d_x, uint64_t n, uint32_t d, const uint32_t *d_triplets,
+                                 uint64_t T, const float *d_M, double margin, uint8_t *d_flags, uint64_t *n_active,
+                                 double *loss, double *G);
+
+/* THE LOOP: projected gradient descent on  obj(M) = loss(M) / (2 T) + reg * |M - M_0|^2  over M = diag(w), w >= 0 (DIAGONAL) or
+ * M = L'L (FULL), so every M it returns is positive semi-definite.  init: d non-negative finite f32 weights or NULL for ones;
+ * w_0 = init, L_0 = diag(sqrt(init)), M_0 = diag(init).  Host arithmetic is f64, ascending, uncontracted (metric_learn.hpp).
+ * Iteration t = 0, 1, ...:
+ *   M_t = diag((float) w), or M_t[i][j] = (float) sum_k L[k][i] L[k][j] (upper half, mirrored);
+ *   the step above at M_t gives loss_t, active_t, G_t;   obj_t = loss_t / (2 T) + reg * sum_ij (M_t - M_0)^2, row-major;
+ *   M_t or obj_t not finite (or, after iteration 0, a NaN hinge: obj_t = NaN): stop, BLISSGPU_LEARN_DIVERGED;
+ *   active_t == 0: stop, BLISSGPU_LEARN_CONVERGED;   t == max_iter: stop, BLISSGPU_LEARN_MAX_ITER;
+ *   Gt = G_t / (2 T) + (2 reg) (M_t - M_0);   DIAGONAL: w <- max(0, w - lr Gt[r][r]);
+ *   FULL: P[i][j] = sum_k L[i][k] Gt[k][j], L <- L - (2 lr) P.
+ * Outputs (HOST pointers in both forms): M [d][d] = the M_t of the finite iteration with the lowest obj, the first such
+ * (*best_iter); obj and active (may be NULL; room for max_iter + 1) get *n_iter + 1 entries; *n_iter = the updates made; *status.
+ * T == 0 converges at once with M = M_0.  x and the triplets stay on the device; per iteration M is uploaded once and
+ * (G, loss, n_active, error bits) downloaded once.  form, init, margin >= 0, reg >= 0, finite lr and the required outputs are
+ * checked before the device is touched. */
+#define BLISSGPU_METRIC_FORM_DIAGONAL 0
+#define BLISSGPU_METRIC_FORM_FULL 1
+#define BLISSGPU_LEARN_CONVERGED 0
+#define BLISSGPU_LEARN_MAX_ITER 1
+#define BLISSGPU_LEARN_DIVERGED 2
+int blissgpu_learn_metric(const float *x, uint64_t n, uint32_t d, const uint32_t *triplets, uint64_t T, int form,
+                          const float *init, double margin, double lr, double reg, uint32_t max_iter, float *M, double *obj,
+                          uint64_t *active, uint32_t *n_iter, uint32_t *best_iter, int32_t *status);
+int blissgpu_learn_metric_device(blissgpu_ctx *ctx, const float *d_x, uint64_t n, uint32_t d, const uint32_t *d_triplets,
+                                 uint64_t T, int form, const float *init, double margin, double lr, double reg,
+                                 uint32_t max_iter, float *M, double *obj, uint64_t *active, uint32_t *n_iter,
+                                 uint32_t *best_iter, int32_t *status);
+
 /* The k nearest candidates of every seed GROUP: closest_to_songs(&group, candidates, metric) cut after k, what
  * Library::playlist_from(&[several songs]).take(k) (src/library.rs:762-842) asks per album, artist, genre or saved playlist,
  * for n_groups groups in one call.  seeds is [group_offsets[n_groups]][d] row-major; group g's seeds are the rows
@@ -788,6 +841,9 @@ int blissgpu_debug_group_forest_stats(blissgpu_ctx *ctx, double *build_ms, doubl
 /* The last blissgpu_kmeans_device call on this context: the device-to-host copies made inside its loop (one per assignment: the
  * pair of flag words) and their bytes.  Either pointer may be NULL. */
 int blissgpu_debug_kmeans_stats(blissgpu_ctx *ctx, uint64_t *loop_copies, uint64_t *loop_bytes);
+/* The last blissgpu_learn_metric_device call on this context: the uploads (M, one per step) and downloads (the result block,
+ * one per step) made inside its loop, and the bytes downloaded.  Any pointer may be NULL. */
+int blissgpu_debug_metric_stats(blissgpu_ctx *ctx, uint64_t *loop_uploads, uint64_t *loop_downloads, uint64_t *loop_bytes);
 
 /* FeaturesVersion::feature_weights (src/lib.rs:168-173, 209-234): d x d row-major diagonal matrix. */
 int blissgpu_feature_weights(uint32_t features_version, float *M);
