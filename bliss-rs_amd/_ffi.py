@@ -114,6 +114,10 @@ SIGNATURES = {
     "blissgpu_kmeans_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_int, _vp, C.c_uint32, _vp, _vp,
                                          _vp, _vp, _u32p, _i32p]),
     "blissgpu_debug_kmeans_stats": (C.c_int, [_vp, _u64p, _u64p]),
+    "blissgpu_silhouette": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_int, _vp, _vp, C.c_uint64, C.c_uint32, _vp,
+                                      _vp, _vp, _vp, _vp]),
+    "blissgpu_silhouette_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_int, _vp, _vp, C.c_uint64,
+                                             C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "blissgpu_triplet_step": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, C.c_double, _vp, _u64p, _f64p, _vp]),
     "blissgpu_triplet_step_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, C.c_double, _vp, _u64p,
                                                _f64p, _vp]),

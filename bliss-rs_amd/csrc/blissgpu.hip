@@ -32,6 +32,7 @@ const char kKmeansAssignName[] = "kmeans_assign_kernel", kKmeansHistName[] = "km
 const char kKmeansScanTilesName[] = "kmeans_scan_tiles_kernel", kKmeansScanAddName[] = "kmeans_scan_add_kernel";
 const char kKmeansScatterName[] = "kmeans_scatter_kernel", kKmeansSelectName[] = "kmeans_select_kernel";
 const char kTripletStepName[] = "triplet_step_kernel", kTripletReduceName[] = "triplet_reduce_kernel";  // KX_TRIPLET_*
+const char kSilhouetteScanName[] = "silhouette_scan_kernel", kSilhouetteFinishName[] = "silhouette_finish_kernel";  // KX_SILHOUETTE_*
 const char* const kKernelNames[K_COUNT] = {
     "fft512_kernel",     "onset_kernel",      "beat_kernel",   "stft8192_kernel", "tune_select_kernel",
     "tune_pass2_kernel", "tune_final_kernel", "chroma_kernel",     "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel", "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel",
@@ -43,6 +44,7 @@ const char* const kKernelNames[K_COUNT] = {
     kSegmentMeanName, kAlbumKnnScanName,
     kKmeansAssignName, kKmeansHistName, kKmeansScanTilesName, kKmeansScanAddName, kKmeansScatterName, kKmeansSelectName,
     kTripletStepName, kTripletReduceName,
+    kSilhouetteScanName, kSilhouetteFinishName,
     kGroupForestScanName, kJourneyStepName};
 }  // namespace
 
@@ -351,7 +353,7 @@ int blissgpu_ctx_destroy(blissgpu_ctx* c) {
         (void)hipFree(c->bt_rwv); (void)hipFree(c->bt_dfwv); (void)hipFree(c->chroma_bank);
         scheduler_release(c);
         c->dbg_tuning.release(); c->dbg_nbpms.release(); c->dbg_chroma.release(); c->dbg_interval.release();
-        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->km_ws.release(); c->mt_ws.release(); c->pl_next.release(); c->st_idx.release();
+        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->km_ws.release(); c->sil_ws.release(); c->mt_ws.release(); c->pl_next.release(); c->st_idx.release();
         c->st_a.release(); c->st_b.release(); c->st_m.release(); c->st_dist.release(); c->st_out.release();
         c->fl_bytes.release(); c->fl_tab.release(); c->fl_pcm.release(); c->fl_status.release(); c->fl_end.release();
         c->fl_bad.release(); c->fl_mono.release(); c->fl_rows.release(); c->fl_htab.release();
@@ -1105,6 +1107,144 @@ int blissgpu_kmeans(const float* x, uint64_t n, uint32_t d, const float* init, u
         if (e == hipSuccess && sizes) e = hipMemcpyAsync(sizes, d_sizes, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(kmeans)", hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+// ---- the silhouette of a labelling: the k-means sort of the labels, then the all-pairs sums per (song, cluster) and the scores
+// (kernels_silhouette.hip); no distance matrix, the host reads one pair of words ----
+// everything that can be said about the scalar arguments and the pointers without a device; *q_eff = the scored songs
+static int silhouette_args_ok(const char* who, const void* x, uint64_t n, uint32_t d, const void* labels, uint32_t k, int metric,
+                              const float* M, const void* rows, uint64_t q, const void* s, uint64_t* q_eff) {
+    if (k == 0 || k > BLISSGPU_KMEANS_MAX_K) return fail(BLISSGPU_ERR_INVALID, who, "k must be 1 .. BLISSGPU_KMEANS_MAX_K");
+    if (d == 0 || d > 64) return fail(BLISSGPU_ERR_INVALID, who, "d must be 1 .. 64");
+    if (metric == BLISSGPU_METRIC_COSINE) return fail(BLISSGPU_ERR_INVALID, who, "cosine: not a metric the clusters were formed with");
+    if (metric != BLISSGPU_METRIC_EUCLIDEAN && metric != BLISSGPU_METRIC_MAHALANOBIS) return fail(BLISSGPU_ERR_INVALID, who, "unknown metric");
+    if (metric == BLISSGPU_METRIC_MAHALANOBIS && !M) return fail(BLISSGPU_ERR_INVALID, who, "mahalanobis needs M");
+    if (n >= 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "n must be below 2^32 - 1 songs");
+    *q_eff = rows ? q : n;
+    if (*q_eff >= 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "q must be below 2^32 - 1 songs");
+    if (n && !x) return fail(BLISSGPU_ERR_INVALID, who, "x is NULL");
+    if (n && !labels) return fail(BLISSGPU_ERR_INVALID, who, "labels is NULL");
+    if (n && *q_eff && !s) return fail(BLISSGPU_ERR_INVALID, who, "s is NULL");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_silhouette_device(blissgpu_ctx* c, const float* d_x, uint64_t n, uint32_t d, const uint32_t* d_labels, uint32_t k,
+                               int metric, const float* d_M, const uint32_t* d_rows, uint64_t q, uint32_t col_groups, float* d_s,
+                               double* d_a, double* d_b, uint32_t* d_neighbour, uint32_t* d_sizes) {
+    const char* who = "blissgpu_silhouette_device";
+    int rc = silhouette_args_ok(who, d_x, n, d, d_labels, k, metric, d_M, d_rows, q, d_s, &q);
+    if (rc) return rc;
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    CTX_ENTER(c, who);
+    if (n == 0) {  // no song: every cluster is empty, nothing is scored
+        if (d_sizes) HIP_TRY(hipMemsetAsync(d_sizes, 0, (size_t)k * sizeof(uint32_t), c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return BLISSGPU_OK;
+    }
+    if (q == 0) return BLISSGPU_OK;
+    int diag = 0;
+    if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
+        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
+            diag = is_diag(c->m_cache.data(), d);
+        } else {
+            std::vector<float> hM((size_t)d * d);
+            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            diag = is_diag(hM.data(), d);
+        }
+    }
+    // workspace, O(n + chunks x K + q Y): flags u32[4] ([0] NaN, [1] SIL_ERR_*) | hist u32[K][W] | scan totals | arow_off u32[K + 1]
+    // | arow u32[n] | (8-byte aligned) own sums f64[Y][q] | best quotients f64[Y][q] | their clusters u32[Y][q]: 20 q Y bytes
+    const KmeansPlan sort = kmeans_plan(n, k, c->n_cus);
+    const SilhouettePlan plan = silhouette_plan(q, k, c->n_cus, col_groups);
+    const size_t qy = (size_t)q * plan.Y;
+    const size_t o_hist = 4, o_bsum = o_hist + (size_t)sort.hist_words, o_off = o_bsum + sort.scan_tiles, o_arow = o_off + k + 1,
+                 o_part = (o_arow + (size_t)n + 1) & ~(size_t)1, words = o_part + 5 * qy;
+    rc = c->sil_ws.ensure(words * sizeof(uint32_t));
+    if (rc) return rc;
+    uint32_t* w = reinterpret_cast<uint32_t*>(c->sil_ws.p);
+    uint32_t *flags = w, *hist = w + o_hist, *bsum = w + o_bsum, *arow_off = w + o_off, *arow = w + o_arow;
+    double* part = reinterpret_cast<double*>(w + o_part);
+    SilhouetteArgs a{};
+    a.X = d_x; a.labels = d_labels; a.arow_off = arow_off; a.arow = arow; a.rows = d_rows; a.M = d_M;
+    a.n = (uint32_t)n; a.K = k; a.q = (uint32_t)q; a.Y = plan.Y; a.d = d; a.metric = metric;
+    a.ws_own = part; a.ws_best_q = part + qy; a.ws_best_i = reinterpret_cast<uint32_t*>(part + 2 * qy);
+    a.flags = flags; a.s = d_s; a.a = d_a; a.b = d_b; a.neighbour = d_neighbour; a.sizes = d_sizes;
+    HIP_TRY(hipMemsetAsync(w, 0, (o_hist + (size_t)sort.hist_words) * sizeof(uint32_t), c->stream));  // the flags and the histograms
+    { Prof p(c, KX_KMEANS_HIST); launch_kmeans_hist(d_labels, (uint32_t)n, k, sort, hist, c->stream); }
+    { Prof p(c, KX_KMEANS_SCAN_TILES); launch_kmeans_scan_tiles(hist, sort, bsum, c->stream); }
+    { Prof p(c, KX_KMEANS_SCAN_ADD); launch_kmeans_scan_add(hist, (uint32_t)n, k, sort, bsum, arow_off, c->stream); }
+    { Prof p(c, KX_KMEANS_SCATTER); launch_kmeans_scatter(d_labels, (uint32_t)n, k, sort, hist, arow, c->stream); }
+    { Prof p(c, KX_SILHOUETTE_SCAN); launch_silhouette_scan(a, diag, plan, c->stream); }
+    { Prof p(c, KX_SILHOUETTE_FINISH); launch_silhouette_finish(a, c->stream); }
+    HIP_TRY(hipGetLastError());
+    // the one synchronisation: the NaN word and the data-dependent errors
+    uint32_t h_flags[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (h_flags[1] & SIL_ERR_LABEL) return fail(BLISSGPU_ERR_INVALID, who, "a label is >= k");
+    if (h_flags[1] & SIL_ERR_ROW) return fail(BLISSGPU_ERR_INVALID, who, "a rows entry is >= n");
+    if (h_flags[1] & SIL_ERR_CLUSTERS) return fail(BLISSGPU_ERR_INVALID, who, "fewer than two non-empty clusters");
+    if (h_flags[0]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance (the reference panics here)");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_silhouette(const float* x, uint64_t n, uint32_t d, const uint32_t* labels, uint32_t k, int metric, const float* M,
+                        const uint32_t* rows, uint64_t q, uint32_t col_groups, float* s, double* a, double* b, uint32_t* neighbour,
+                        uint32_t* sizes) {
+    const char* who = "blissgpu_silhouette";
+    int rc = silhouette_args_ok(who, x, n, d, labels, k, metric, M, rows, q, s, &q);
+    if (rc) return rc;
+    if (n == 0) {  // no song: nothing for a device to do
+        if (sizes) memset(sizes, 0, (size_t)k * sizeof(uint32_t));
+        return BLISSGPU_OK;
+    }
+    if (q == 0) return BLISSGPU_OK;
+    // labels and rows are host memory: what the device form finds after its sort is found here, before the device is touched
+    {
+        std::vector<uint8_t> seen(k, 0);
+        uint32_t distinct = 0;
+        for (uint64_t i = 0; i < n; i++) {
+            if (labels[i] >= k) return fail(BLISSGPU_ERR_INVALID, who, "a label is >= k");
+            if (!seen[labels[i]]) { seen[labels[i]] = 1; distinct++; }
+        }
+        if (distinct < 2) return fail(BLISSGPU_ERR_INVALID, who, "fewer than two non-empty clusters");
+        if (rows)
+            for (uint64_t p = 0; p < q; p++)
+                if (rows[p] >= n) return fail(BLISSGPU_ERR_INVALID, who, "a rows entry is >= n");
+    }
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    const float* dM = nullptr;
+    rc = c->st_b.ensure(n * d);
+    if (!rc) rc = c->st_idx.ensure(n + 2 * q + k);  // labels | rows | neighbour | sizes
+    if (!rc) rc = c->st_dist.ensure(q);
+    if (!rc) rc = c->st_out.ensure(2 * q * sizeof(double));  // a | b
+    if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
+    if (rc) return rc;
+    uint32_t *d_labels = c->st_idx.p, *d_rows = rows ? c->st_idx.p + n : nullptr, *d_nb = c->st_idx.p + n + q,
+             *d_sizes = c->st_idx.p + n + 2 * q;
+    double *d_a = reinterpret_cast<double*>(c->st_out.p), *d_b = d_a + q;
+    hipError_t e = hipMemcpyAsync(c->st_b.p, x, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_labels, labels, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && rows) e = hipMemcpyAsync(d_rows, rows, q * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(silhouette)", hipGetErrorString(e));
+    if (!rc)
+        rc = blissgpu_silhouette_device(c, c->st_b.p, n, d, d_labels, k, metric, dM, d_rows, q, col_groups, c->st_dist.p, d_a, d_b,
+                                        d_nb, d_sizes);
+    if (!rc) {
+        e = hipMemcpyAsync(s, c->st_dist.p, q * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && a) e = hipMemcpyAsync(a, d_a, q * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && b) e = hipMemcpyAsync(b, d_b, q * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && neighbour) e = hipMemcpyAsync(neighbour, d_nb, q * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && sizes) e = hipMemcpyAsync(sizes, d_sizes, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(silhouette)", hipGetErrorString(e));
     }
     (void)hipStreamSynchronize(c->stream);
     return rc;

@@ -123,7 +123,7 @@ enum KernelId : int {
     K_CHAIN_STEP, K_CHAIN_WALK,             // song-to-song chains cut after k (kernels_chains.hip)
     // (tests/test_chains_host.py holds this list, and the list of names beside it, to end in the chain kernels: the kernels
     // that came later are numbered behind it, so that no older id or name moves)
-    K_COUNT = K_CHAIN_WALK + 13
+    K_COUNT = K_CHAIN_WALK + 15
 };
 // k-nearest albums per seed group (kernels_albums.hip; its partial lists are merged by knn_merge_kernel)
 constexpr int KX_SEGMENT_MEAN = K_CHAIN_WALK + 1, KX_ALBUM_KNN_SCAN = K_CHAIN_WALK + 2;
@@ -132,12 +132,14 @@ constexpr int KX_KMEANS_ASSIGN = K_CHAIN_WALK + 3, KX_KMEANS_HIST = K_CHAIN_WALK
               KX_KMEANS_SCAN_ADD = K_CHAIN_WALK + 6, KX_KMEANS_SCATTER = K_CHAIN_WALK + 7, KX_KMEANS_SELECT = K_CHAIN_WALK + 8;
 // one gradient evaluation of triplet metric learning (kernels_metric.hip): the wavefronts' partials, their ascending sum
 constexpr int KX_TRIPLET_STEP = K_CHAIN_WALK + 9, KX_TRIPLET_REDUCE = K_CHAIN_WALK + 10;
+// the silhouette of a labelling (kernels_silhouette.hip): the all-pairs sums per (song, cluster), then a, b, neighbour and s
+constexpr int KX_SILHOUETTE_SCAN = K_CHAIN_WALK + 11, KX_SILHOUETTE_FINISH = K_CHAIN_WALK + 12;
 // (tests/test_journeys_host.py holds the profile table to END in the next two names: kernels that come later are numbered in
 // front of them; every consumer of the table goes by name)
 // the k lowest forest scores per seed group (kernels_forest.hip; its partial lists are merged by group_knn_merge_kernel)
-constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 11;
+constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 13;
 // a journey's step (kernels_chains.hip: the chains' scan with a waypoint query or a gate)
-constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 12;
+constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 14;
 static_assert(KX_JOURNEY_STEP + 1 == K_COUNT, "every kernel id is below the count");
 
 // lower_bound on a prefix array: largest s with prefix[s] <= x  (prefix has n+1 entries, prefix[0]=0)
@@ -360,6 +362,32 @@ void launch_kmeans_scatter(const uint32_t* labels, uint32_t n, uint32_t K, const
                            hipStream_t st);
 void launch_kmeans_select(const float* prev, float* next, const uint32_t* arow_off, uint32_t K, uint32_t d, uint32_t* sizes,
                           hipStream_t st);
+// the silhouette of a labelling (kernels_silhouette.hip), after the k-means sort of the labels into arow_off / arow.  The scored
+// songs are rows[0 .. q) (NULL: every song, q = n), cut into pieces of 256 per wavefront; the clusters are dealt to Y column
+// groups, cluster c to group floor(arow_off[c] Y / n).  The scan writes ws_best_q / ws_best_i [Y][q] (the best other quotient of
+// the group's clusters and its cluster, SIL_NONE: none) and ws_own [Y][q] (the own-cluster sum, in the own cluster's group only);
+// the finish forms s, a, b, neighbour (a, b, neighbour, sizes may be NULL).  flags[0]: a NaN distance; flags[1]: SIL_ERR_*
+constexpr uint32_t SIL_ERR_LABEL = 1u, SIL_ERR_ROW = 2u, SIL_ERR_CLUSTERS = 4u;
+struct SilhouetteArgs {
+    const float* X;
+    const uint32_t *labels, *arow_off, *arow, *rows;
+    const float* M;
+    uint32_t n, K, q, Y, d;
+    int metric;
+    double *ws_own, *ws_best_q;
+    uint32_t* ws_best_i;
+    uint32_t* flags;
+    float* s;
+    double *a, *b;
+    uint32_t *neighbour, *sizes;
+};
+struct SilhouettePlan {
+    uint32_t waves, grid;  // wavefronts per workgroup of the scan (256 scored songs each), its workgroups per column group
+    uint32_t Y;            // column groups: col_groups when not 0, else about two workgroups per CU; at most K
+};
+SilhouettePlan silhouette_plan(uint64_t q, uint32_t K, int n_cus, uint32_t col_groups);
+void launch_silhouette_scan(const SilhouetteArgs& a, int m_is_diag, const SilhouettePlan& p, hipStream_t st);
+void launch_silhouette_finish(const SilhouetteArgs& a, hipStream_t st);
 // triplet metric learning, one gradient evaluation (kernels_metric.hip).  The triplets are dealt out in W contiguous chunks, a
 // function of T alone; part [W][pairs + 1] f64 and cnt [W][2] u64 are the wavefronts' partials, out = G f64 [d][d] | loss f64 |
 // n_active u64 | error bits u64 (TRIPLET_ERR_*).  mode says how M is read; flags (u8 [T]) may be NULL

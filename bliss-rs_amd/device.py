@@ -512,6 +512,62 @@ class Context:
         _ffi.check(self._L.blissgpu_debug_kmeans_stats(self._h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def silhouette(self, X, labels, metric: str = "euclidean", M=None, rows=None, col_groups: int = 0, k: int = None):
+        """The silhouette of the labelling `labels` of the rows of X on the device, without the distance matrix
+        (blissgpu_silhouette_device): for every scored song a = the mean distance to the other songs of its own
+        cluster, b = the smallest mean distance to another non-empty cluster, s = (b - a) / max(a, b), all defined to the bit by
+        include/blissgpu.h.  X float32 [n, d] and labels (int32 / int64, every one in 0 .. k - 1) are tensors on the device, or
+        numpy arrays (uploaded, results returned as arrays); rows: the songs to score (any order, repeats allowed), None = all;
+        k: the number of clusters, None = labels.max() + 1.
+        -> (s float32 [q], a float64 [q], b float64 [q], neighbour int32 [q], sizes int32 [k]).  col_groups: 0 = the plan's
+        choice; no result bit depends on it.  Raises BlissGpuError: ERR_NAN for a NaN among the evaluated distances, ERR_INVALID
+        for a label >= k, fewer than two non-empty clusters or a rows entry past n; synchronises once."""
+        from .playlist import _METRICS
+
+        torch = self.torch
+        as_numpy = not torch.is_tensor(X)
+        dev = torch.device("cuda", self.device)
+
+        def up_f32(a):
+            return None if a is None else (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev))
+
+        def up_u32(a, what):  # -> int32 tensor holding the uint32 bits
+            if a is None:
+                return None
+            if torch.is_tensor(a):
+                assert a.is_cuda and a.dtype in (torch.int32, torch.int64), what
+                return a.to(torch.int32).contiguous().reshape(-1)
+            a = np.asarray(a, dtype=np.int64).reshape(-1)
+            if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+                raise ValueError(f"{what} must be non-negative indices")
+            return torch.from_numpy(a.astype(np.uint32).view(np.int32)).to(dev)
+
+        X, M = up_f32(X), up_f32(M)
+        labels, rows = up_u32(labels, "labels"), up_u32(rows, "rows")
+        assert X.is_cuda and X.dtype == torch.float32 and X.dim() == 2
+        X = X.contiguous()
+        n, d = X.shape
+        if labels.shape[0] != n:
+            raise ValueError("a label per row of X is needed")
+        if M is not None:
+            assert M.is_cuda and M.dtype == torch.float32
+            M = M.contiguous()
+        if k is None:
+            k = int(labels.max().item()) + 1 if n else 1
+        q = n if rows is None else rows.shape[0]
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        s = torch.zeros((q,), dtype=torch.float32, device=X.device)
+        a = torch.zeros((q,), dtype=torch.float64, device=X.device)
+        b = torch.zeros((q,), dtype=torch.float64, device=X.device)
+        nb = torch.full((q,), -1, dtype=torch.int32, device=X.device)
+        sizes = torch.zeros((max(int(k), 0),), dtype=torch.int32, device=X.device)
+        self._pre()
+        _ffi.check(self._L.blissgpu_silhouette_device(self._h, ptr(X), n, d, ptr(labels), int(k), _METRICS[metric], ptr(M), ptr(rows), q,
+                                                      int(col_groups), ptr(s), ptr(a), ptr(b), ptr(nb), ptr(sizes)))
+        self._post()
+        out = (s, a, b, nb, sizes)
+        return tuple(t.cpu().numpy() for t in out) if as_numpy else out
+
     def triplet_step(self, X, triplets, M=None, margin: float = 0.0, return_flags: bool = False):
         """One gradient evaluation of triplet metric learning (blissgpu_triplet_step_device) on device tensors:
         X float32 [n, d], triplets int32 [T, 3] as (a, b, o) (int64 is converted), M float32 [d, d] or None for the identity.

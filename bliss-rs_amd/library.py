@@ -628,6 +628,45 @@ def cluster_songs(db: Conn, k: int, seed: int = 0, metric_builder=playlist.eucli
     return (lists, clustering) if return_clustering else lists
 
 
+def choose_clusters(db: Conn, ks=range(2, 33), seed: int = 0, metric_builder=playlist.euclidean_distance, max_iter: int = 100,
+                    init: str = "k-means++", sample: int = None):
+    """Into how many groups the library falls best: playlist.choose_k over the analysed songs of FeaturesVersion.LATEST, read
+    once (load_songs) and uploaded once -- k-means and the silhouette of its labels for every k of `ks`, the highest silhouette
+    score wins (equal scores: the lower k).  -> (playlist.KSelection, best_k lists of `Song`, each ordered as cluster_songs
+    orders them).  `sample`: score that many songs only (drawn with `seed`)."""
+    playlist._kmeans_metric(metric_builder)  # refused before the database is read
+    songs, X = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
+    if not songs:
+        raise ValueError("choose_clusters needs at least one analysed song")
+    sel = playlist.choose_k(X, ks, seed, metric_builder, max_iter, init, sample)
+    lists = [[songs[int(i)] for i in sel.clustering.members(c)] for c in range(len(sel.clustering.sizes))]
+    return sel, lists
+
+
+_SILHOUETTE_COLUMNS = ("genre", "album", "artist")
+
+
+def label_silhouette(db: Conn, by: str = "genre", metric_builder=playlist.euclidean_distance):
+    """How well a metric separates the library's genres, albums or artists: the silhouette (playlist.silhouette) of the
+    labelling that column gives the analysed songs of FeaturesVersion.LATEST.  Songs whose tag is NULL are left out before the
+    call.  -> (playlist.Silhouette, tags): label c is tags[c], in order of first appearance (id order).  Run it with
+    euclidean_distance and with MahalanobisBuilder(learn_metric(db, source=by)): the before / after check of a learned M.
+    Fewer than two different tags is a ValueError."""
+    playlist._silhouette_metric(metric_builder)  # refused before the database is read
+    if by not in _SILHOUETTE_COLUMNS:
+        raise ValueError(f"by must be one of {_SILHOUETTE_COLUMNS}")
+    songs, X = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
+    code, keep, labels = {}, [], []
+    for i, s in enumerate(songs):
+        tag = getattr(s, by)
+        if tag is not None:
+            keep.append(i)
+            labels.append(code.setdefault(tag, len(code)))
+    if len(code) < 2:
+        raise ValueError(f"label_silhouette needs songs with at least two different {by} tags")
+    return playlist.silhouette(X[np.asarray(keep)], np.asarray(labels, np.int64), metric_builder), list(code)
+
+
 def _has_triplet_table(conn) -> bool:
     return conn.execute("select count(*) from sqlite_master where type = 'table' and name = 'training_triplet'").fetchone()[0] > 0
 

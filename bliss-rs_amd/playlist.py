@@ -12,6 +12,8 @@
     closest_album_to_group                                       :424-485
     journey_order, waypoint_playlist, directed_playlist (the waypoint and direction features of the reference's TODO.md)
     kmeans, kmeans_init, cluster_songs (the clustering the reference's TODO.md asks for: Lloyd's algorithm on the device)
+    silhouette, choose_k (the "objective way to evaluate" of the reference's TODO.md: how well a labelling separates the songs
+    under a metric, all pairs on the device without the distance matrix; and the k whose k-means clusters separate them best)
     triplet_step, learn_metric, triplet_accuracy, triplets_from_labels (the metric learning the reference's TODO.md and its
     training_triplet table ask for: a Mahalanobis M from "a and b are closer than o" triplets, the gradient on the device)
 
@@ -513,7 +515,7 @@ def kmeans(X, init, max_iter=100, metric="euclidean", m=None):
 _KMEANS_INITS = ("k-means++", "sample")
 
 
-def kmeans_init(X, k, seed=0, method="k-means++"):
+def kmeans_init(X, k, seed=0, method="k-means++", _device=None):
     """k rows of X to start k-means from, [k, d]; the same seed gives the same rows (numpy's PCG64).
     "sample": rows numpy.random.Generator(PCG64(seed)).choice(n, k, replace=False), sorted -- host only.
     "k-means++": D^2 sampling -- the first row uniformly, every further row with probability proportional to the squared
@@ -529,12 +531,15 @@ def kmeans_init(X, k, seed=0, method="k-means++"):
     rng = np.random.Generator(np.random.PCG64(int(seed)))
     if method == "sample":
         return X[np.sort(rng.choice(n, k, replace=False))].copy()
-    import torch
+    if _device is None:
+        import torch
 
-    from .device import Context
+        from .device import Context
 
-    ctx = Context.default()
-    Xd = torch.from_numpy(X).to(torch.device("cuda", ctx.device))
+        ctx = Context.default()
+        Xd = torch.from_numpy(X).to(torch.device("cuda", ctx.device))
+    else:  # (choose_k: the context and the rows it has uploaded already)
+        ctx, Xd = _device
     picks = [int(rng.integers(n))]
     picked = np.zeros(n, bool)
     picked[picks[0]] = True
@@ -600,6 +605,168 @@ def cluster_songs(songs, k, seed=0, metric_builder=euclidean_distance, max_iter=
         raise ValueError("cluster_songs needs at least one song")
     X = _matrix(songs)
     return Clustering(*kmeans(X, kmeans_init(X, k, seed, init), max_iter, metric, m))
+
+
+def _silhouette_metric(metric_builder):
+    """the metrics the silhouette can run: euclidean, or Mahalanobis with the caller's matrix"""
+    _no_forest(metric_builder, "the silhouette compares single songs; a forest scores songs against a seed set")
+    _no_variance(metric_builder, "the silhouette has no seed set to take variances from; pass MahalanobisBuilder(m)")
+    metric, m = _metric_of(metric_builder)
+    if metric == "cosine":
+        raise ValueError("the silhouette needs the metric the groups are judged by: euclidean or mahalanobis, not cosine")
+    return metric, m
+
+
+def _rows_of_input(songs_or_X) -> np.ndarray:
+    """[n, d] float32 from an array or from songs"""
+    if isinstance(songs_or_X, np.ndarray):
+        return np.ascontiguousarray(np.atleast_2d(songs_or_X), dtype=np.float32)
+    items = list(songs_or_X)
+    if items and hasattr(_song_of(items[0]), "analysis"):
+        return _matrix(items)
+    return np.ascontiguousarray(np.atleast_2d(np.asarray(items, dtype=np.float32)), dtype=np.float32)
+
+
+def _index_array(a, what):
+    a = np.asarray(a, dtype=np.int64).reshape(-1)
+    if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+        raise ValueError(f"{what} must be non-negative indices")
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+class Silhouette:
+    """The silhouette of a labelling: values float32[q] (s of every scored song), a and b float64[q] (the mean distance to the
+    own cluster / to the nearest other one), neighbour int64[q] (that cluster), sizes int64[k], labels int64[q] (the cluster of
+    every scored song), and the aggregates -- score = math.fsum(values) / q and cluster_scores float64[k] = the fsum mean of
+    every cluster's scored members, NaN where none was scored.  fsum is correctly rounded: the aggregates have no order."""
+
+    def __init__(self, values, a, b, neighbour, sizes, labels):
+        import math
+
+        self.values = np.asarray(values, dtype=np.float32)
+        self.a, self.b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+        self.neighbour = np.asarray(neighbour, dtype=np.int64)
+        self.sizes = np.asarray(sizes, dtype=np.int64)
+        self.labels = np.asarray(labels, dtype=np.int64)
+        q = self.values.shape[0]
+        self.score = math.fsum(float(v) for v in self.values) / q if q else float("nan")
+        self.cluster_scores = np.full(self.sizes.shape[0], np.nan, np.float64)
+        for c in np.unique(self.labels):
+            v = self.values[self.labels == c]
+            self.cluster_scores[int(c)] = math.fsum(float(x) for x in v) / v.shape[0]
+
+    def __repr__(self):
+        return f"Silhouette(score={self.score:.6g}, scored={len(self.values)}, k={len(self.sizes)})"
+
+
+def silhouette(X, labels, metric_builder=euclidean_distance, rows=None, k=None, col_groups=0) -> Silhouette:
+    """How well the labelling `labels` (one cluster index per row) separates the rows of X (an array, or songs) under a
+    metric, in one device call without the distance matrix (blissgpu_silhouette): for every scored song
+    a = the mean distance to the other songs of its cluster, b = the smallest mean distance to another non-empty cluster,
+    s = (b - a) / max(a, b) in [-1, 1]; a singleton scores 0.  Every value is defined to the bit by include/blissgpu.h.
+    rows: the songs to score (any order, repeats allowed; value p belongs to song rows[p]), None = all.  k: the number of
+    clusters, None = labels.max() + 1.  col_groups is for the tests and the bench tool (no result bit depends on it).
+    metric_builder: euclidean_distance or a MahalanobisBuilder (its M) -- the before / after check of learn_metric; a
+    ForestOptions, a VarianceWeights, cosine and arbitrary callables are refused.  Fewer than two non-empty clusters, a label
+    >= k or a row past the songs raise BlissGpuError(ERR_INVALID), a NaN distance ValueError."""
+    metric, m = _silhouette_metric(metric_builder)
+    X = _rows_of_input(X)
+    lab = _index_array(labels, "labels")
+    n, d = X.shape
+    if lab.shape[0] != n:
+        raise ValueError("a label per row of X is needed")
+    if n == 0:
+        raise ValueError("silhouette needs at least one song")
+    k = int(lab.max()) + 1 if k is None else int(k)
+    rp, q = None, n
+    if rows is not None:
+        rows = _index_array(rows, "rows")
+        rp, q = rows.ctypes.data, rows.shape[0]
+    mp = None
+    if m is not None:
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        mp = m.ctypes.data
+    s, a, b = np.zeros(q, np.float32), np.zeros(q, np.float64), np.zeros(q, np.float64)
+    nb, sizes = np.zeros(q, np.uint32), np.zeros(max(k, 0), np.uint32)
+    try:
+        _ffi.check(_ffi.lib().blissgpu_silhouette(X.ctypes.data, n, d, lab.ctypes.data, k, _METRICS[metric], mp, rp, q, int(col_groups),
+                                                  s.ctypes.data, a.ctypes.data, b.ctypes.data, nb.ctypes.data, sizes.ctypes.data))
+    except _ffi.BlissGpuError as e:
+        _nan_to_panic(e)
+    return Silhouette(s, a, b, nb, sizes, lab if rows is None else lab[rows])
+
+
+class KSelection:
+    """The result of choose_k: ks (as given), scores (the silhouette score of each k's clustering), best_k (the k with the
+    highest score; equal scores go to the lower k) and clustering (that k's Clustering)."""
+
+    def __init__(self, ks, scores, best_k, clustering):
+        self.ks = [int(k) for k in ks]
+        self.scores = [float(v) for v in scores]
+        self.best_k = int(best_k)
+        self.clustering = clustering
+
+    def __repr__(self):
+        return f"KSelection(best_k={self.best_k}, scores={dict(zip(self.ks, self.scores))})"
+
+
+def _best_k(ks, scores) -> int:
+    """the k with the highest score; equal scores go to the lower k"""
+    best = None
+    for k, v in zip(ks, scores):
+        if best is None or v > best[1] or (v == best[1] and k < best[0]):
+            best = (int(k), float(v))
+    return best[0]
+
+
+def _sample_rows(n, sample, seed):
+    """the rows choose_k scores: None = all, else `sample` of them drawn without replacement with the seed, sorted"""
+    if sample is None or int(sample) >= n:
+        return None
+    if int(sample) < 1:
+        raise ValueError("sample must be at least 1")
+    return np.sort(np.random.Generator(np.random.PCG64(int(seed))).choice(n, int(sample), replace=False))
+
+
+def choose_k(songs_or_X, ks, seed=0, metric_builder=euclidean_distance, max_iter=100, init="k-means++", sample=None) -> KSelection:
+    """Which k suits the songs: for every k of `ks`, k-means from kmeans_init(rows, k, seed, init) (Context.kmeans) and the
+    silhouette of its labels (Context.silhouette), on rows uploaded once.  -> KSelection: the highest silhouette score wins,
+    equal scores go to the lower k.  sample = m scores m rows only -- numpy.random.Generator(PCG64(seed)).choice(n, m,
+    replace=False), sorted -- which makes a k cost n m distances, not n n.  A k whose clustering leaves fewer than two
+    non-empty clusters raises BlissGpuError(ERR_INVALID).  metric_builder: as cluster_songs."""
+    metric, m = _kmeans_metric(metric_builder)
+    ks = [int(k) for k in ks]
+    if not ks:
+        raise ValueError("choose_k needs at least one k")
+    X = _rows_of_input(songs_or_X)
+    n = X.shape[0]
+    if n == 0:
+        raise ValueError("choose_k needs at least one song")
+    rows = _sample_rows(n, sample, seed)
+    import math
+
+    import torch
+
+    from .device import Context
+
+    ctx = Context.default()
+    dev = torch.device("cuda", ctx.device)
+    Xd = torch.from_numpy(X).to(dev)
+    Md = None if m is None else torch.from_numpy(np.ascontiguousarray(m, dtype=np.float32)).to(dev)
+    rows_d = None if rows is None else torch.from_numpy(rows.astype(np.int32)).to(dev)
+    scores, best = [], None
+    try:
+        for k in ks:
+            init_d = torch.from_numpy(kmeans_init(X, k, seed, init, _device=(ctx, Xd))).to(dev)
+            labels, dist, cent, sizes, n_iter, conv = ctx.kmeans(Xd, init_d, max_iter, metric, Md)
+            s = ctx.silhouette(Xd, labels, metric, Md, rows_d, 0, k)[0]
+            score = math.fsum(float(v) for v in s.cpu().numpy()) / s.shape[0]
+            scores.append(score)
+            if best is None or _best_k(ks, scores) != best[0]:  # (only the winner's clustering is brought to the host)
+                best = (k, Clustering(labels.cpu().numpy(), dist.cpu().numpy(), cent.cpu().numpy(), sizes.cpu().numpy(), n_iter, conv))
+    except _ffi.BlissGpuError as e:
+        _nan_to_panic(e)
+    return KSelection(ks, scores, best[0], best[1])
 
 
 def _triplet_args(X, triplets, m):

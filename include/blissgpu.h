@@ -453,6 +453,42 @@ int blissgpu_kmeans_device(blissgpu_ctx *ctx, const float *d_x, uint64_t n, uint
                            int metric, const float *d_M, uint32_t max_iter, uint32_t *d_labels, float *d_dist,
                            float *d_centroids, uint32_t *d_sizes, uint32_t *n_iter, int32_t *converged);
 
+/* ---- Silhouette of a labelling (the reference's TODO.md asks for "a proper 'objective' way to evaluate" and for
+ * the genre clustering / evaluation code, it has no code) ----
+ * How well a labelling of the rows x [n][d] separates them under a metric: for every scored song the mean distance to its own
+ * cluster against the mean distance to the nearest other cluster, every step defined to the bit.
+ * Inputs: x [n][d] f32; labels [n] u32, every one < k; metric: BLISSGPU_METRIC_EUCLIDEAN, or BLISSGPU_METRIC_MAHALANOBIS with the
+ * caller's M (a diagonal M is detected as everywhere else); rows [q] u32 (may be NULL) = the songs to score, in any order, repeats
+ * allowed: output position p belongs to song rows[p].  rows == NULL scores every song: q is then taken as n, position p = song p.
+ * With dist(i, j) = bit for bit what blissgpu_pairwise_device(x, x) writes at [i][j], and size_c = the member count of cluster c:
+ *   S(i, c) = 0.0 + (double)dist(i, j_0) + (double)dist(i, j_1) + ... over the members of c in ASCENDING j: one sequential f64
+ *             sum, never split or restarted.  The song itself is a member of its own cluster; its term is +0.0;
+ *   own = labels[i];   a = S(i, own) / (double)(size_own - 1), and a = 0.0 when size_own == 1;
+ *   b = the smallest S(i, c) / (double)size_c over c != own with size_c > 0, neighbour = that c: equal quotients go to the lower c;
+ *   s, every operation in f64 rounded on its own, then rounded once to f32:
+ *       s = 0 when size_own == 1;   s = 0 when a == b;   s = 1 - a / b when a < b;   s = b / a - 1 when a > b.
+ * This form equals (b - a) / max(a, b) and stays defined when one side is 0 or infinite.
+ * Outputs, per scored song: s [q] f32; a [q] and b [q] f64 (may be NULL); neighbour [q] u32 (may be NULL); and sizes [k] u32 (may be
+ * NULL) = the members per cluster.
+ * A NaN among the evaluated distances returns BLISSGPU_ERR_NAN (the k-means rule); the outputs are then unspecified.
+ * BLISSGPU_ERR_INVALID: BLISSGPU_METRIC_COSINE (the message names it); a label >= k; fewer than two non-empty clusters; a rows
+ * entry >= n; d outside 1 .. 64; k outside 1 .. BLISSGPU_KMEANS_MAX_K; n or q >= 2^32 - 1; NULL x, labels or s.  n == 0 or q == 0 is
+ * BLISSGPU_OK: nothing is scored (n == 0 writes zeros to sizes; q == 0 writes nothing).
+ * The host form checks all of these before the device is touched; its labels and rows are host memory.
+ * col_groups: 0 lets the plan choose into how many column groups the clusters are dealt, anything else forces
+ * that many (at most k are used).  No bit of any output depends on it: the argument exists for the tests and the bench tool.
+ * No n x n matrix is ever stored.  Workspace, grow-only in the context: the k-means sort's O(n + chunks x k) plus 20 bytes per
+ * (scored song, column group). */
+int blissgpu_silhouette(const float *x, uint64_t n, uint32_t d, const uint32_t *labels, uint32_t k, int metric, const float *M,
+                        const uint32_t *rows, uint64_t q, uint32_t col_groups, float *s, double *a, double *b,
+                        uint32_t *neighbour, uint32_t *sizes);
+/* Device-resident form (device pointers throughout).  It checks the scalar arguments before it looks at its context, and
+ * reports the data-dependent errors (a label >= k, a rows entry >= n, fewer than two non-empty clusters, NaN) after the sort, at
+ * its one synchronisation of the context's stream before returning. */
+int blissgpu_silhouette_device(blissgpu_ctx *ctx, const float *d_x, uint64_t n, uint32_t d, const uint32_t *d_labels, uint32_t k,
+                               int metric, const float *d_M, const uint32_t *d_rows, uint64_t q, uint32_t col_groups, float *d_s,
+                               double *d_a, double *d_b, uint32_t *d_neighbour, uint32_t *d_sizes);
+
 /* ---- Learning the Mahalanobis matrix from training triplets ----
  * The reference has a `training_triplet` table ("song_1 and song_2 are closer together than they are to odd_one_out",
  * src/library.rs:542-556), a TODO.md that asks for "a way to learn a metric with a user survey", and no code that learns.
