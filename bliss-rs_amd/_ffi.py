@@ -32,6 +32,8 @@ GROUP_OK, GROUP_TOO_FEW_SEEDS = 0, 1
 KMEANS_MAX_K = 65535
 METRIC_FORM_DIAGONAL, METRIC_FORM_FULL = 0, 1
 LEARN_CONVERGED, LEARN_MAX_ITER, LEARN_DIVERGED = 0, 1, 2
+COV_OK, COV_NOT_POSITIVE = 0, 1
+MOMENTS_BLOCK = 256
 
 _f32p = C.POINTER(C.c_float)
 _f64p = C.POINTER(C.c_double)
@@ -118,6 +120,9 @@ SIGNATURES = {
                                       _vp, _vp, _vp, _vp]),
     "blissgpu_silhouette_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_int, _vp, _vp, C.c_uint64,
                                              C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "blissgpu_moments": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "blissgpu_moments_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "blissgpu_covariance_metric": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_int, C.c_double, _vp, _i32p]),
     "blissgpu_triplet_step": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, C.c_double, _vp, _u64p, _f64p, _vp]),
     "blissgpu_triplet_step_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, C.c_double, _vp, _u64p,
                                                _f64p, _vp]),

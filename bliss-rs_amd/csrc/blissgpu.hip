@@ -16,6 +16,7 @@
 
 #include "ctx.hpp"
 #include "metric_learn.hpp"
+#include "covariance_metric.hpp"
 #include "forest.hpp"
 
 using namespace bg;
@@ -33,6 +34,9 @@ const char kKmeansScanTilesName[] = "kmeans_scan_tiles_kernel", kKmeansScanAddNa
 const char kKmeansScatterName[] = "kmeans_scatter_kernel", kKmeansSelectName[] = "kmeans_select_kernel";
 const char kTripletStepName[] = "triplet_step_kernel", kTripletReduceName[] = "triplet_reduce_kernel";  // KX_TRIPLET_*
 const char kSilhouetteScanName[] = "silhouette_scan_kernel", kSilhouetteFinishName[] = "silhouette_finish_kernel";  // KX_SILHOUETTE_*
+const char kMomentsPlanName[] = "moments_plan_kernel", kMomentsSumName[] = "moments_sum_kernel", kMomentsM2Name[] = "moments_m2_kernel";
+const char kMomentsScatterName[] = "moments_scatter_kernel", kMomentsReduceName[] = "moments_reduce_kernel";  // KX_MOMENTS_*
+const char kMomentsFinishName[] = "moments_finish_kernel";
 const char* const kKernelNames[K_COUNT] = {
     "fft512_kernel",     "onset_kernel",      "beat_kernel",   "stft8192_kernel", "tune_select_kernel",
     "tune_pass2_kernel", "tune_final_kernel", "chroma_kernel",     "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel", "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel",
@@ -45,6 +49,7 @@ const char* const kKernelNames[K_COUNT] = {
     kKmeansAssignName, kKmeansHistName, kKmeansScanTilesName, kKmeansScanAddName, kKmeansScatterName, kKmeansSelectName,
     kTripletStepName, kTripletReduceName,
     kSilhouetteScanName, kSilhouetteFinishName,
+    kMomentsPlanName, kMomentsSumName, kMomentsM2Name, kMomentsScatterName, kMomentsReduceName, kMomentsFinishName,
     kGroupForestScanName, kJourneyStepName};
 }  // namespace
 
@@ -353,7 +358,7 @@ int blissgpu_ctx_destroy(blissgpu_ctx* c) {
         (void)hipFree(c->bt_rwv); (void)hipFree(c->bt_dfwv); (void)hipFree(c->chroma_bank);
         scheduler_release(c);
         c->dbg_tuning.release(); c->dbg_nbpms.release(); c->dbg_chroma.release(); c->dbg_interval.release();
-        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->km_ws.release(); c->sil_ws.release(); c->mt_ws.release(); c->pl_next.release(); c->st_idx.release();
+        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->km_ws.release(); c->sil_ws.release(); c->mo_ws.release(); c->mt_ws.release(); c->pl_next.release(); c->st_idx.release();
         c->st_a.release(); c->st_b.release(); c->st_m.release(); c->st_dist.release(); c->st_out.release();
         c->fl_bytes.release(); c->fl_tab.release(); c->fl_pcm.release(); c->fl_status.release(); c->fl_end.release();
         c->fl_bad.release(); c->fl_mono.release(); c->fl_rows.release(); c->fl_htab.release();
@@ -1248,6 +1253,180 @@ int blissgpu_silhouette(const float* x, uint64_t n, uint32_t d, const uint32_t* 
     }
     (void)hipStreamSynchronize(c->stream);
     return rc;
+}
+
+// ---- the moments of a library: counts, means, squared deviations and extrema per group of a labelling, and the pooled scatter
+// matrix (kernels_moments.hip); the k-means sort of the labels, then one launch per level of the blocked sum ----
+// everything that can be said about the scalar arguments and the pointers without a device
+static int moments_args_ok(const char* who, const void* x, uint64_t n, uint32_t d, const void* labels, uint32_t k, const void* counts,
+                           const void* mean, const void* mn, const void* mx) {
+    if (k == 0 || k > BLISSGPU_KMEANS_MAX_K) return fail(BLISSGPU_ERR_INVALID, who, "k must be 1 .. BLISSGPU_KMEANS_MAX_K");
+    if (d == 0 || d > 64) return fail(BLISSGPU_ERR_INVALID, who, "d must be 1 .. 64");
+    if (n >= 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "n must be below 2^32 - 1 rows");
+    if (n && !labels && k != 1) return fail(BLISSGPU_ERR_INVALID, who, "without labels k must be 1");
+    if (n && !x) return fail(BLISSGPU_ERR_INVALID, who, "x is NULL");
+    if (!counts) return fail(BLISSGPU_ERR_INVALID, who, "counts is NULL");
+    if (!mean) return fail(BLISSGPU_ERR_INVALID, who, "mean is NULL");
+    if (!mn != !mx) return fail(BLISSGPU_ERR_INVALID, who, "min and max go together: both or neither");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_moments_device(blissgpu_ctx* c, const float* d_x, uint64_t n, uint32_t d, const uint32_t* d_labels, uint32_t k,
+                            uint32_t* d_counts, double* d_mean, double* d_m2, float* d_min, float* d_max, double* d_S) {
+    const char* who = "blissgpu_moments_device";
+    int rc = moments_args_ok(who, d_x, n, d, d_labels, k, d_counts, d_mean, d_min, d_max);
+    if (rc) return rc;
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    CTX_ENTER(c, who);
+    const size_t kd = (size_t)k * d;
+    const uint32_t w = d * (d + 1) / 2;
+    HIP_TRY(hipMemsetAsync(d_mean, 0, kd * sizeof(double), c->stream));  // (an empty group keeps these zeros)
+    if (d_m2) HIP_TRY(hipMemsetAsync(d_m2, 0, kd * sizeof(double), c->stream));
+    if (n == 0) {  // no row: every group is empty
+        HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)k * sizeof(uint32_t), c->stream));
+        if (d_S) HIP_TRY(hipMemsetAsync(d_S, 0, (size_t)d * d * sizeof(double), c->stream));
+        if (d_min) { Prof p(c, KX_MOMENTS_FINISH); launch_moments_finish(d_counts, nullptr, nullptr, k, d, d_min, d_max, c->stream); }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return BLISSGPU_OK;
+    }
+    // workspace: flags u32[4] ([0] not finite, [1] MO_ERR_*) | with labels: hist u32[K][W] | scan totals | arow_off u32[K + 1] |
+    // arow u32[n] | off u32[levels][K + 1] | keys u32[2][K d] | (8-byte aligned) the groups' partials A f64[items_0][d], B
+    // f64[items_1][d] | the scatter's partials A f64[blocks_0][w], B f64[blocks_1][w].  Level l writes A when l is even, B when odd
+    const MomentsPlan plan = moments_plan(n, k);
+    const KmeansPlan sort = kmeans_plan(n, k, c->n_cus);
+    const size_t o_hist = 4, o_bsum = o_hist + (d_labels ? (size_t)sort.hist_words : 0), o_aoff = o_bsum + (d_labels ? sort.scan_tiles : 0),
+                 o_arow = o_aoff + (d_labels ? k + 1 : 0), o_off = o_arow + (d_labels ? (size_t)n : 0),
+                 o_keys = o_off + (size_t)plan.levels * (k + 1), o_pa = (o_keys + 2 * kd + 1) & ~(size_t)1,
+                 o_pb = o_pa + 2 * (size_t)plan.items[0] * d, o_sa = o_pb + 2 * (size_t)(plan.levels > 1 ? plan.items[1] : 0) * d,
+                 o_sb = o_sa + 2 * (d_S ? (size_t)plan.blocks[0] * w : 0),
+                 words = o_sb + 2 * (d_S && plan.levels > 1 ? (size_t)plan.blocks[1] * w : 0);
+    rc = c->mo_ws.ensure(words * sizeof(uint32_t));
+    if (rc) return rc;
+    uint32_t* ws = reinterpret_cast<uint32_t*>(c->mo_ws.p);
+    uint32_t *flags = ws, *hist = ws + o_hist, *bsum = ws + o_bsum, *arow_off = d_labels ? ws + o_aoff : nullptr,
+             *arow = d_labels ? ws + o_arow : nullptr, *off = ws + o_off, *keys = ws + o_keys;
+    double* gpart[2] = {reinterpret_cast<double*>(ws + o_pa), reinterpret_cast<double*>(ws + o_pb)};
+    double* spart[2] = {reinterpret_cast<double*>(ws + o_sa), reinterpret_cast<double*>(ws + o_sb)};
+    MomentsArgs a{};
+    a.X = d_x; a.labels = d_labels; a.arow_off = arow_off; a.arow = arow; a.off = off; a.mean = d_mean;
+    a.n = (uint32_t)n; a.K = k; a.d = d; a.key_min = keys; a.key_max = keys + kd; a.flags = flags;
+    HIP_TRY(hipMemsetAsync(ws, 0, (o_hist + (d_labels ? (size_t)sort.hist_words : 0)) * sizeof(uint32_t), c->stream));
+    if (d_labels) {
+        { Prof p(c, KX_KMEANS_HIST); launch_kmeans_hist(d_labels, (uint32_t)n, k, sort, hist, c->stream); }
+        { Prof p(c, KX_KMEANS_SCAN_TILES); launch_kmeans_scan_tiles(hist, sort, bsum, c->stream); }
+        { Prof p(c, KX_KMEANS_SCAN_ADD); launch_kmeans_scan_add(hist, (uint32_t)n, k, sort, bsum, arow_off, c->stream); }
+        { Prof p(c, KX_KMEANS_SCATTER); launch_kmeans_scatter(d_labels, (uint32_t)n, k, sort, hist, arow, c->stream); }
+    }
+    { Prof p(c, KX_MOMENTS_PLAN); launch_moments_plan(arow_off, (uint32_t)n, k, plan, off, d_counts, c->stream); }
+    // the levels above level 0 of one per-group quantity, and its last step into dst
+    auto group_levels = [&](int mode, double* dst) {
+        for (uint32_t l = 1; l < plan.levels; l++) {
+            Prof p(c, KX_MOMENTS_REDUCE);
+            launch_moments_reduce(gpart[(l - 1) & 1], off + (size_t)(l - 1) * (k + 1), 0, gpart[l & 1], off + (size_t)l * (k + 1), 0,
+                                  plan.items[l], k, d, MO_RED_PART, d_counts, nullptr, d, c->stream);
+        }
+        const uint32_t* last = off + (size_t)(plan.levels - 1) * (k + 1);
+        Prof p(c, KX_MOMENTS_REDUCE);
+        launch_moments_reduce(gpart[(plan.levels - 1) & 1], last, 0, nullptr, last, 0, plan.items[plan.levels - 1], k, d, mode, d_counts,
+                              dst, d, c->stream);
+    };
+    { Prof p(c, KX_MOMENTS_SUM); launch_moments_sum(a, plan, gpart[0], c->stream); }
+    group_levels(MO_RED_MEAN, d_mean);
+    if (d_m2 || d_min) {
+        if (d_min) {
+            HIP_TRY(hipMemsetAsync(a.key_min, 0xFF, kd * sizeof(uint32_t), c->stream));
+            HIP_TRY(hipMemsetAsync(a.key_max, 0, kd * sizeof(uint32_t), c->stream));
+        }
+        { Prof p(c, KX_MOMENTS_M2); launch_moments_m2(a, plan, gpart[0], d_min != nullptr, c->stream); }
+        if (d_m2) group_levels(MO_RED_M2, d_m2);
+        if (d_min) { Prof p(c, KX_MOMENTS_FINISH); launch_moments_finish(d_counts, a.key_min, a.key_max, k, d, d_min, d_max, c->stream); }
+    }
+    if (d_S) {
+        { Prof p(c, KX_MOMENTS_SCATTER); launch_moments_scatter(a, plan, spart[0], c->stream); }
+        for (uint32_t l = 1; l < plan.levels; l++) {
+            Prof p(c, KX_MOMENTS_REDUCE);
+            launch_moments_reduce(spart[(l - 1) & 1], nullptr, plan.blocks[l - 1], spart[l & 1], nullptr, plan.blocks[l], plan.blocks[l], 1, w,
+                                  MO_RED_PART, nullptr, nullptr, d, c->stream);
+        }
+        Prof p(c, KX_MOMENTS_REDUCE);
+        launch_moments_reduce(spart[(plan.levels - 1) & 1], nullptr, plan.blocks[plan.levels - 1], nullptr, nullptr, 1, 1, 1, w,
+                              MO_RED_SCATTER, nullptr, d_S, d, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    // the one synchronisation: the data-dependent errors
+    uint32_t h_flags[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (h_flags[1] & MO_ERR_LABEL) return fail(BLISSGPU_ERR_INVALID, who, "a label is >= k");
+    if (h_flags[0]) return fail(BLISSGPU_ERR_NAN, who, "a NaN or an infinity in x");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_moments(const float* x, uint64_t n, uint32_t d, const uint32_t* labels, uint32_t k, uint32_t* counts, double* mean,
+                     double* m2, float* mn, float* mx, double* S) {
+    const char* who = "blissgpu_moments";
+    int rc = moments_args_ok(who, x, n, d, labels, k, counts, mean, mn, mx);
+    if (rc) return rc;
+    const size_t kd = (size_t)k * d, dd = (size_t)d * d;
+    if (n == 0) {  // no row: nothing for a device to do
+        memset(counts, 0, (size_t)k * sizeof(uint32_t));
+        for (size_t e = 0; e < kd; e++) {
+            mean[e] = 0.0;
+            if (m2) m2[e] = 0.0;
+            if (mn) { mn[e] = INFINITY; mx[e] = -INFINITY; }
+        }
+        if (S) for (size_t e = 0; e < dd; e++) S[e] = 0.0;
+        return BLISSGPU_OK;
+    }
+    if (labels)  // host memory: what the device form finds at its synchronisation is found here, before the device is touched
+        for (uint64_t i = 0; i < n; i++)
+            if (labels[i] >= k) return fail(BLISSGPU_ERR_INVALID, who, "a label is >= k");
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    // staging: x | labels, counts | mean, m2, S (f64), then min, max (f32)
+    rc = c->st_b.ensure(n * d);
+    if (!rc) rc = c->st_idx.ensure(n + k);
+    if (!rc) rc = c->st_out.ensure((2 * kd + dd) * sizeof(double) + 2 * kd * sizeof(float));
+    if (rc) return rc;
+    uint32_t *d_labels = labels ? c->st_idx.p : nullptr, *d_counts = c->st_idx.p + n;
+    double *d_mean = reinterpret_cast<double*>(c->st_out.p), *d_m2 = d_mean + kd, *d_S = d_m2 + kd;
+    float *d_mn = reinterpret_cast<float*>(d_S + dd), *d_mx = d_mn + kd;
+    hipError_t e = hipMemcpyAsync(c->st_b.p, x, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && labels) e = hipMemcpyAsync(d_labels, labels, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(moments)", hipGetErrorString(e));
+    if (!rc)
+        rc = blissgpu_moments_device(c, c->st_b.p, n, d, d_labels, k, d_counts, d_mean, m2 ? d_m2 : nullptr, mn ? d_mn : nullptr,
+                                     mn ? d_mx : nullptr, S ? d_S : nullptr);
+    if (!rc) {
+        e = hipMemcpyAsync(counts, d_counts, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(mean, d_mean, kd * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && m2) e = hipMemcpyAsync(m2, d_m2, kd * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && mn) e = hipMemcpyAsync(mn, d_mn, kd * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && mn) e = hipMemcpyAsync(mx, d_mx, kd * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && S) e = hipMemcpyAsync(S, d_S, dd * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(moments)", hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+// a scatter matrix turned into a Mahalanobis M (covariance_metric.hpp): host arithmetic only, no device is touched
+int blissgpu_covariance_metric(const double* S, uint32_t d, uint64_t dof, int form, double shrink, float* M, int32_t* status) {
+    const char* who = "blissgpu_covariance_metric";
+    if (d == 0 || d > 64) return fail(BLISSGPU_ERR_INVALID, who, "d must be 1 .. 64");
+    if (dof == 0) return fail(BLISSGPU_ERR_INVALID, who, "dof must be positive");
+    if (!(shrink >= 0.0 && shrink <= 1.0)) return fail(BLISSGPU_ERR_INVALID, who, "shrink must be within 0 .. 1");
+    if (form != BLISSGPU_METRIC_FORM_DIAGONAL && form != BLISSGPU_METRIC_FORM_FULL) return fail(BLISSGPU_ERR_INVALID, who, "unknown form");
+    if (!S || !M || !status) return fail(BLISSGPU_ERR_INVALID, who, "S, M and status must not be NULL");
+    static_assert(bg::covmetric::FORM_DIAGONAL == BLISSGPU_METRIC_FORM_DIAGONAL && bg::covmetric::FORM_FULL == BLISSGPU_METRIC_FORM_FULL &&
+                      bg::covmetric::STATUS_OK == BLISSGPU_COV_OK && bg::covmetric::STATUS_NOT_POSITIVE == BLISSGPU_COV_NOT_POSITIVE,
+                  "covariance_metric.hpp and blissgpu.h agree");
+    *status = bg::covmetric::solve(S, d, dof, form, shrink, M);
+    return BLISSGPU_OK;
 }
 
 // ---- triplet metric learning (kernels_metric.hip, metric_learn.hpp): one gradient evaluation on the device, and the projected

@@ -123,7 +123,7 @@ enum KernelId : int {
     K_CHAIN_STEP, K_CHAIN_WALK,             // song-to-song chains cut after k (kernels_chains.hip)
     // (tests/test_chains_host.py holds this list, and the list of names beside it, to end in the chain kernels: the kernels
     // that came later are numbered behind it, so that no older id or name moves)
-    K_COUNT = K_CHAIN_WALK + 15
+    K_COUNT = K_CHAIN_WALK + 21
 };
 // k-nearest albums per seed group (kernels_albums.hip; its partial lists are merged by knn_merge_kernel)
 constexpr int KX_SEGMENT_MEAN = K_CHAIN_WALK + 1, KX_ALBUM_KNN_SCAN = K_CHAIN_WALK + 2;
@@ -134,12 +134,16 @@ constexpr int KX_KMEANS_ASSIGN = K_CHAIN_WALK + 3, KX_KMEANS_HIST = K_CHAIN_WALK
 constexpr int KX_TRIPLET_STEP = K_CHAIN_WALK + 9, KX_TRIPLET_REDUCE = K_CHAIN_WALK + 10;
 // the silhouette of a labelling (kernels_silhouette.hip): the all-pairs sums per (song, cluster), then a, b, neighbour and s
 constexpr int KX_SILHOUETTE_SCAN = K_CHAIN_WALK + 11, KX_SILHOUETTE_FINISH = K_CHAIN_WALK + 12;
+// the moments of a library (kernels_moments.hip): the levels' offsets, level 0 of the means, of the squared deviations and of the
+// scatter matrix, every further level of the blocked sum, the extrema
+constexpr int KX_MOMENTS_PLAN = K_CHAIN_WALK + 13, KX_MOMENTS_SUM = K_CHAIN_WALK + 14, KX_MOMENTS_M2 = K_CHAIN_WALK + 15,
+              KX_MOMENTS_SCATTER = K_CHAIN_WALK + 16, KX_MOMENTS_REDUCE = K_CHAIN_WALK + 17, KX_MOMENTS_FINISH = K_CHAIN_WALK + 18;
 // (tests/test_journeys_host.py holds the profile table to END in the next two names: kernels that come later are numbered in
 // front of them; every consumer of the table goes by name)
 // the k lowest forest scores per seed group (kernels_forest.hip; its partial lists are merged by group_knn_merge_kernel)
-constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 13;
+constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 19;
 // a journey's step (kernels_chains.hip: the chains' scan with a waypoint query or a gate)
-constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 14;
+constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 20;
 static_assert(KX_JOURNEY_STEP + 1 == K_COUNT, "every kernel id is below the count");
 
 // lower_bound on a prefix array: largest s with prefix[s] <= x  (prefix has n+1 entries, prefix[0]=0)
@@ -388,6 +392,37 @@ struct SilhouettePlan {
 SilhouettePlan silhouette_plan(uint64_t q, uint32_t K, int n_cus, uint32_t col_groups);
 void launch_silhouette_scan(const SilhouetteArgs& a, int m_is_diag, const SilhouettePlan& p, hipStream_t st);
 void launch_silhouette_finish(const SilhouetteArgs& a, hipStream_t st);
+// the moments of a library (kernels_moments.hip), after the k-means sort of the labels into arow_off / arow (both NULL without
+// labels: one group, the rows in place).  Every f64 sum is the blocked sum of include/blissgpu.h, one launch per level: off is
+// [levels][K + 1], off[l][g] = where group g's block sums of level l start (moments_plan_kernel); level 0 is the sum / m2 /
+// scatter kernel, every further level and the last step (divide, copy, mirror) moments_reduce_kernel.  flags[0]: a NaN or an
+// infinity in x; flags[1]: MO_ERR_*
+constexpr uint32_t MO_ERR_LABEL = 1u;
+constexpr int MO_RED_PART = 0, MO_RED_MEAN = 1, MO_RED_M2 = 2, MO_RED_SCATTER = 3;
+struct MomentsArgs {
+    const float* X;
+    const uint32_t *labels, *arow_off, *arow, *off;
+    const double* mean;
+    uint32_t n, K, d;
+    uint32_t *key_min, *key_max, *flags;
+};
+struct MomentsPlan {
+    uint32_t levels;     // of the blocked sum over n terms: 1 for n <= 256, 2 up to 65 536, at most 4
+    uint32_t items[4];   // per level: an upper bound of the groups' block sums, floor(n / 256^(l + 1)) + min(K, n)
+    uint32_t blocks[4];  // per level: the block sums over all rows, ceil(n / 256^(l + 1))
+};
+MomentsPlan moments_plan(uint64_t n, uint32_t K);
+void launch_moments_plan(const uint32_t* arow_off, uint32_t n, uint32_t K, const MomentsPlan& p, uint32_t* off, uint32_t* counts,
+                         hipStream_t st);
+void launch_moments_sum(const MomentsArgs& a, const MomentsPlan& p, double* part, hipStream_t st);
+void launch_moments_m2(const MomentsArgs& a, const MomentsPlan& p, double* part, bool extrema, hipStream_t st);
+void launch_moments_scatter(const MomentsArgs& a, const MomentsPlan& p, double* part, hipStream_t st);
+// out_bound: an upper bound of the block sums this launch forms (the grid); the kernel reads the exact number from out_off / out_n
+void launch_moments_reduce(const double* in, const uint32_t* in_off, uint32_t in_n, double* out, const uint32_t* out_off,
+                           uint32_t out_n, uint32_t out_bound, uint32_t K, uint32_t w, int mode, const uint32_t* counts, double* dst,
+                           uint32_t d, hipStream_t st);
+void launch_moments_finish(const uint32_t* counts, const uint32_t* key_min, const uint32_t* key_max, uint32_t K, uint32_t d, float* mn,
+                           float* mx, hipStream_t st);
 // triplet metric learning, one gradient evaluation (kernels_metric.hip).  The triplets are dealt out in W contiguous chunks, a
 // function of T alone; part [W][pairs + 1] f64 and cnt [W][2] u64 are the wavefronts' partials, out = G f64 [d][d] | loss f64 |
 // n_active u64 | error bits u64 (TRIPLET_ERR_*).  mode says how M is read; flags (u8 [T]) may be NULL

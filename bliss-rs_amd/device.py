@@ -568,6 +568,53 @@ class Context:
         out = (s, a, b, nb, sizes)
         return tuple(t.cpu().numpy() for t in out) if as_numpy else out
 
+    def moments(self, X, labels=None, k: int = None, scatter: bool = True):
+        """The first and second moments of the rows of X on the device (blissgpu_moments_device), per group of
+        the labelling `labels` and pooled, every sum the blocked sum of include/blissgpu.h.  X float32 [n, d] and labels (int32 /
+        int64, every one in 0 .. k - 1; None: one group) are tensors on the device, or numpy arrays (uploaded, results returned as
+        arrays); k: the number of groups, None = labels.max() + 1.
+        -> (counts int32 [k], mean float64 [k, d], m2 float64 [k, d], min float32 [k, d], max float32 [k, d], S float64 [d, d] or
+        None when `scatter` is False).  S is the pooled within-group scatter (without labels: the total scatter).  Raises
+        BlissGpuError: ERR_NAN for a NaN or an infinity in X, ERR_INVALID for a label >= k; synchronises once."""
+        torch = self.torch
+        as_numpy = not torch.is_tensor(X)
+        dev = torch.device("cuda", self.device)
+        if as_numpy:
+            X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(dev)
+        assert X.is_cuda and X.dtype == torch.float32 and X.dim() == 2
+        X = X.contiguous()
+        n, d = X.shape
+        if labels is not None:
+            if torch.is_tensor(labels):
+                assert labels.is_cuda and labels.dtype in (torch.int32, torch.int64), "labels"
+                labels = labels.to(torch.int32).contiguous().reshape(-1)
+            else:
+                labels = np.asarray(labels, dtype=np.int64).reshape(-1)
+                if labels.size and (labels.min() < 0 or labels.max() > 0xFFFFFFFF):
+                    raise ValueError("labels must be non-negative indices")
+                labels = torch.from_numpy(labels.astype(np.uint32).view(np.int32)).to(dev)
+            if labels.shape[0] != n:
+                raise ValueError("a label per row of X is needed")
+            if k is None:
+                k = int(labels.max().item()) + 1 if n else 1
+        elif k is None:
+            k = 1
+        k = int(k)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        kk = max(k, 0)
+        counts = torch.zeros((kk,), dtype=torch.int32, device=X.device)
+        mean = torch.zeros((kk, d), dtype=torch.float64, device=X.device)
+        m2 = torch.zeros((kk, d), dtype=torch.float64, device=X.device)
+        mn = torch.zeros((kk, d), dtype=torch.float32, device=X.device)
+        mx = torch.zeros((kk, d), dtype=torch.float32, device=X.device)
+        S = torch.zeros((d, d), dtype=torch.float64, device=X.device) if scatter else None
+        self._pre()
+        _ffi.check(self._L.blissgpu_moments_device(self._h, ptr(X), n, d, ptr(labels), k, ptr(counts), ptr(mean), ptr(m2), ptr(mn),
+                                                   ptr(mx), ptr(S)))
+        self._post()
+        out = (counts, mean, m2, mn, mx, S)
+        return tuple(None if t is None else t.cpu().numpy() for t in out) if as_numpy else out
+
     def triplet_step(self, X, triplets, M=None, margin: float = 0.0, return_flags: bool = False):
         """One gradient evaluation of triplet metric learning (blissgpu_triplet_step_device) on device tensors:
         X float32 [n, d], triplets int32 [T, 3] as (a, b, o) (int64 is converted), M float32 [d, d] or None for the identity.

@@ -745,6 +745,59 @@ def learn_metric(db: Conn, source="triplets", form: str = "full", n_triplets: in
     return res if return_result else res.m
 
 
+def _labels_of(songs, source):
+    """a label per song (< 0: none) from a tag column, a label array or a Clustering"""
+    if isinstance(source, str):
+        if source not in _LABEL_COLUMNS:
+            raise ValueError(f"source must be one of {_LABEL_COLUMNS}, a label array or a Clustering")
+        code = {}
+        return np.asarray([-1 if getattr(s, source) is None else code.setdefault(getattr(s, source), len(code)) for s in songs], np.int64)
+    labels = np.asarray(source.labels if isinstance(source, playlist.Clustering) else source, np.int64).reshape(-1)
+    if labels.shape[0] != len(songs):
+        raise ValueError("a label per analysed song is needed")
+    return labels
+
+
+def covariance_metric(db: Conn, source=None, form: str = "full", shrink: float = playlist.COV_SHRINK, return_result: bool = False):
+    """A Mahalanobis matrix for the library in closed form (playlist.covariance_metric) -> M float32[d, d], ready for
+    playlist.MahalanobisBuilder; `return_result`: -> the whole playlist.CovarianceMetric.
+    source: None -- the inverse of the library's total covariance ("diagonal": every feature standardised, "full": whitened);
+    "genre" / "album" / "artist" / "album_artist", a label per analysed song in load_feature_matrix order (< 0: no label) or a
+    playlist.Clustering -- the inverse of the pooled covariance WITHIN those groups (songs without a label are left out).
+    The songs are those of FeaturesVersion.LATEST.  It needs no iterations and is the baseline to compare learn_metric with."""
+    songs, X = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
+    res = playlist.covariance_metric(X, None if source is None else _labels_of(songs, source), form, shrink)
+    return res if return_result else res.m
+
+
+def statistics(db: Conn, by: str = None):
+    """The library's statistics per feature, computed on the device (playlist.moments), in the stored, normalised units.
+    by None -> {AnalysisIndex name: {"mean", "std", "min", "max", "count"}} over the analysed songs of FeaturesVersion.LATEST
+    (std is the population standard deviation).  by "genre" / "album" / "artist" / "album_artist" -> {tag: that dictionary} for
+    every tag of the column; songs whose tag is NULL are left out."""
+    if by is not None and by not in _LABEL_COLUMNS:
+        raise ValueError(f"by must be None or one of {_LABEL_COLUMNS}")
+    songs, X = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
+    names = [AnalysisIndex(r).name for r in range(X.shape[1])]
+
+    def table(mo, g):
+        return {name: {"mean": float(mo.mean[g, r]), "std": float(mo.std[g, r]), "min": float(mo.min[g, r]), "max": float(mo.max[g, r]),
+                       "count": int(mo.counts[g])} for r, name in enumerate(names)}
+
+    if by is None:
+        return table(playlist.moments(X, None, None, False), 0) if len(songs) else {}
+    code, keep, labels = {}, [], []
+    for i, s in enumerate(songs):
+        tag = getattr(s, by)
+        if tag is not None:
+            keep.append(i)
+            labels.append(code.setdefault(tag, len(code)))
+    if not code:
+        return {}
+    mo = playlist.moments(X[np.asarray(keep)], np.asarray(labels, np.int64), len(code), False)
+    return {tag: table(mo, g) for tag, g in code.items()}
+
+
 def album_playlist_from(db: Conn, album_title: str, number_albums: int) -> List[Song]:
     """`Library::album_playlist_from` (src/library.rs:857-893): the album, then the albums closest to it
     (closest_album_to_group), cut after `number_albums` changes of album."""

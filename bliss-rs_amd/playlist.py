@@ -875,6 +875,123 @@ def learn_metric(X, triplets, form="full", init=None, margin=LEARN_MARGIN, lr=LE
     return _learned(M, obj, act, n_iter, best_iter, status)
 
 
+# ---- library statistics and covariance-based metrics (blissgpu_moments, blissgpu_covariance_metric) ----
+# the share of the mean variance mixed into the covariance before it is inverted, so that a constant feature does not make it
+# singular.  Nobody has measured this default on a real library
+COV_SHRINK = 0.01
+
+
+class Moments:
+    """The result of moments: counts int64[k], mean / var / std float64[k, d] (var = m2 / count, the population variance; an
+    empty group has 0), m2 float64[k, d] (the sums of squared deviations), min / max float32[k, d] (+inf / -inf for an empty
+    group), scatter float64[d, d] (the pooled within-group scatter; without labels the total scatter; None when not asked for)
+    and dof = n - the number of non-empty groups, what the scatter is divided by to estimate a covariance."""
+
+    def __init__(self, counts, mean, m2, mn, mx, scatter):
+        self.counts = np.asarray(counts, dtype=np.int64)
+        self.mean, self.m2 = np.asarray(mean, dtype=np.float64), np.asarray(m2, dtype=np.float64)
+        self.min, self.max = np.asarray(mn, dtype=np.float32), np.asarray(mx, dtype=np.float32)
+        self.scatter = None if scatter is None else np.asarray(scatter, dtype=np.float64)
+        self.var = self.m2 / np.maximum(self.counts, 1)[:, None].astype(np.float64)
+        self.std = np.sqrt(self.var)
+        self.dof = int(self.counts.sum()) - int(np.count_nonzero(self.counts))
+
+    def __repr__(self):
+        return f"Moments(n={int(self.counts.sum())}, k={len(self.counts)}, d={self.mean.shape[1]}, dof={self.dof})"
+
+
+def moments(X, labels=None, k=None, scatter=True) -> Moments:
+    """The first and second moments of the rows of X (an array, or songs) in one device call (blissgpu_moments):
+    per group of the labelling `labels` (None: one group) the count, mean, variance, minimum and maximum of every feature, and
+    the d x d scatter matrix of the rows about their group's mean.  Every sum is f64 in the fixed blocked order of
+    include/blissgpu.h: two calls return the same bits.  k: the number of groups, None = labels.max() + 1.  A label >= k raises
+    BlissGpuError(ERR_INVALID), a NaN or an infinity in X ValueError."""
+    X = _rows_of_input(X)
+    n, d = X.shape
+    lp = None
+    if labels is None:
+        k = 1 if k is None else int(k)
+    else:
+        lab = _index_array(labels, "labels")
+        if lab.shape[0] != n:
+            raise ValueError("a label per row of X is needed")
+        k = (int(lab.max()) + 1 if n else 1) if k is None else int(k)
+        lp = lab.ctypes.data
+    kk = max(k, 0)
+    counts, mean, m2 = np.zeros(kk, np.uint32), np.zeros((kk, d), np.float64), np.zeros((kk, d), np.float64)
+    mn, mx = np.zeros((kk, d), np.float32), np.zeros((kk, d), np.float32)
+    S = np.zeros((d, d), np.float64) if scatter else None
+    try:
+        _ffi.check(_ffi.lib().blissgpu_moments(X.ctypes.data, n, d, lp, k, counts.ctypes.data, mean.ctypes.data, m2.ctypes.data,
+                                               mn.ctypes.data, mx.ctypes.data, None if S is None else S.ctypes.data))
+    except _ffi.BlissGpuError as e:
+        _nan_to_panic(e)
+    return Moments(counts, mean, m2, mn, mx, S)
+
+
+class CovarianceMetric:
+    """The result of covariance_metric: m float32[d, d] (the inverse of the shrunk covariance scaled to trace d, positive
+    definite), scatter float64[d, d] (what it was formed from), dof (what the scatter was divided by), form, shrink."""
+
+    def __init__(self, m, scatter, dof, form, shrink):
+        self.m = np.asarray(m, dtype=np.float32)
+        self.scatter = np.asarray(scatter, dtype=np.float64)
+        self.dof, self.form, self.shrink = int(dof), str(form), float(shrink)
+
+    def builder(self) -> "MahalanobisBuilder":
+        return MahalanobisBuilder(self.m)
+
+    def __repr__(self):
+        return f"CovarianceMetric(d={self.m.shape[0]}, form={self.form!r}, shrink={self.shrink:g}, dof={self.dof})"
+
+
+def metric_from_scatter(scatter, dof, form="full", shrink=COV_SHRINK) -> np.ndarray:
+    """A scatter matrix turned into a Mahalanobis matrix on the host (blissgpu_covariance_metric; no device is touched):
+    C = scatter / dof shrunk towards its mean variance, inverted ("full": by Cholesky; "diagonal": feature by feature) and
+    scaled to trace d.  -> m float32[d, d].  ValueError for dof <= 0, and for a covariance that is not positive definite: that
+    message names `shrink`, which cures it."""
+    if form not in _FORMS:
+        raise ValueError(f"form must be one of {tuple(_FORMS)}")
+    shrink = float(shrink)
+    if not 0.0 <= shrink <= 1.0:
+        raise ValueError("shrink must be within 0 .. 1")
+    if int(dof) <= 0:
+        raise ValueError("covariance_metric needs more rows than non-empty groups (dof = n - groups must be positive)")
+    S = np.ascontiguousarray(scatter, dtype=np.float64)
+    d = S.shape[0]
+    if S.shape != (d, d):
+        raise ValueError("scatter must be a square matrix")
+    M, status = np.zeros((d, d), np.float32), C.c_int32(0)
+    _ffi.check(_ffi.lib().blissgpu_covariance_metric(S.ctypes.data, d, int(dof), _FORMS[form], shrink, M.ctypes.data, C.byref(status)))
+    if status.value != _ffi.COV_OK:
+        raise ValueError(f"the covariance is not positive definite at shrink = {shrink:g} (a constant feature, or fewer rows than "
+                         "features): raise shrink")
+    return M
+
+
+def covariance_metric(X, labels=None, form="full", shrink=COV_SHRINK, k=None) -> CovarianceMetric:
+    """A Mahalanobis matrix in closed form from the second moments of the rows of X (an array, or songs): the inverse of their
+    covariance -- "diagonal": per-feature standardisation, "full": whitening.  With `labels` (genre, album, artist, a k-means
+    label per row) it is the inverse of the pooled WITHIN-group covariance (relevant component analysis): directions in which
+    songs of one group differ count for little, the others for much.  Rows with a label < 0 are left out.  The scatter comes
+    from one device call (moments), the solve runs on the host (metric_from_scatter).  It is the baseline learn_metric is to be
+    compared with: judge both with triplet_accuracy and silhouette.  -> CovarianceMetric; `.m` goes into MahalanobisBuilder."""
+    if form not in _FORMS:
+        raise ValueError(f"form must be one of {tuple(_FORMS)}")
+    X = _rows_of_input(X)
+    if labels is not None:
+        labels = np.asarray(labels).reshape(-1).astype(np.int64)
+        if labels.shape[0] != X.shape[0]:
+            raise ValueError("a label per row of X is needed")
+        keep = labels >= 0
+        if not keep.all():
+            X, labels = np.ascontiguousarray(X[keep]), labels[keep]
+    if X.shape[0] == 0:
+        raise ValueError("covariance_metric needs more rows than non-empty groups (dof = n - groups must be positive)")
+    mo = moments(X, labels, k, True)
+    return CovarianceMetric(metric_from_scatter(mo.scatter, mo.dof, form, shrink), mo.scatter, mo.dof, form, shrink)
+
+
 def triplet_accuracy(X, triplets, m=None) -> float:
     """The share of the 2 T constraints d(a, b) < d(a, o), d(a, b) < d(b, o) that hold under m (None: euclidean): 1 - the
     active hinges of triplet_step at margin 0 over 2 T.  No triplet: 1.0."""

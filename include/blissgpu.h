@@ -542,6 +542,65 @@ int blissgpu_learn_metric_device(blissgpu_ctx *ctx, const float *d_x, uint64_t n
                                  uint32_t max_iter, float *M, double *obj, uint64_t *active, uint32_t *n_iter,
                                  uint32_t *best_iter, int32_t *status);
 
+/* ---- Library statistics and covariance-based Mahalanobis metrics (the reference's TODO.md asks for "statistics
+ * to the library trait", for "an M that neutralizes feature scaling imbalance" and for the genre clustering "to find an
+ * appropriate M matrix", it has no code) ----
+ * The first and second moments of the rows x [n][d] f32, per group of a labelling and pooled, every bit defined.
+ * Inputs: x [n][d] f32, 1 <= d <= 64, n < 2^32 - 1; labels [n] u32, every one < k, 1 <= k <= BLISSGPU_KMEANS_MAX_K.  labels may
+ * be NULL: k must then be 1 and every row is in group 0.
+ * THE BLOCKED SUM  B(t_0 ... t_{m-1})  of f64 terms is the one summation order of this section:
+ *   m <= BLISSGPU_MOMENTS_BLOCK:  0.0 + t_0 + t_1 + ..., sequential (m == 0: 0.0);
+ *   otherwise:  B of the sequence of the sequential sums (each begun at 0.0) of consecutive blocks of BLISSGPU_MOMENTS_BLOCK
+ *               terms, the last block may be short.
+ * It is a function of m and the order of the terms alone; there are no atomics in it, every multiply and every add is rounded
+ * on its own, and no bit of any output depends on how the work is dealt out on the device.
+ * Outputs, with "the members of g" = the rows i with labels[i] == g in ASCENDING i, and count_g their number:
+ *   counts [k] u32 = count_g;
+ *   mean [k][d] f64 = B((double)x[i][r] over the members of g) / (double)count_g; an empty group has mean 0.0;
+ *   m2 [k][d] f64 (may be NULL) = B(u * u over the members of g),  u = (double)x[i][r] - mean[g][r]; 0.0 for an empty group;
+ *   min, max [k][d] f32 (may be NULL, both or neither) = the least and the greatest x[i][r] of the members; -0.0 orders below
+ *       +0.0 here; an empty group gets +inf and -inf;
+ *   S [d][d] f64 (may be NULL: the scatter pass is then skipped) = B(u_i[r] * u_i[c] over ALL rows i in ascending i),
+ *       u_i[r] = (double)x[i][r] - mean[labels[i]][r].  The upper half (r <= c) is computed and mirrored: S is exactly
+ *       symmetric.  With labels S is the pooled within-group scatter, without labels the total scatter.
+ * A NaN or an infinity in x returns BLISSGPU_ERR_NAN; a label >= k returns BLISSGPU_ERR_INVALID; the outputs are then
+ * unspecified.  BLISSGPU_ERR_INVALID also: d outside 1 .. 64; k outside 1 .. BLISSGPU_KMEANS_MAX_K; NULL labels with k != 1
+ * (and n > 0); n >= 2^32 - 1; NULL x (with n > 0), counts or mean; one of min and max NULL and the other not.  n == 0 is BLISSGPU_OK with
+ * zero counts, means, m2 and S, and +inf / -inf extrema.
+ * The host form checks all of these, its labels included, before the device is touched.
+ * Workspace, grow-only in the context: the k-means sort's O(n + chunks x k), 8 (d + d (d + 1) / 2) bytes per block of
+ * BLISSGPU_MOMENTS_BLOCK rows, and O(k d). */
+#define BLISSGPU_MOMENTS_BLOCK 256
+int blissgpu_moments(const float *x, uint64_t n, uint32_t d, const uint32_t *labels, uint32_t k, uint32_t *counts, double *mean,
+                     double *m2, float *min, float *max, double *S);
+/* Device-resident form (device pointers throughout).  It checks the scalar arguments before it looks at its context, and
+ * reports the data-dependent errors (a label >= k, a NaN or an infinity) at its one synchronisation of the context's stream
+ * before returning; it reads nothing outside x and labels whatever the labels hold. */
+int blissgpu_moments_device(blissgpu_ctx *ctx, const float *d_x, uint64_t n, uint32_t d, const uint32_t *d_labels, uint32_t k,
+                            uint32_t *d_counts, double *d_mean, double *d_m2, float *d_min, float *d_max, double *d_S);
+
+/* A scatter matrix turned into a Mahalanobis M.  Pure host code, no device is touched (covariance_metric.hpp); f64, sums
+ * ascending from 0.0, every multiply and every add rounded on its own.  S [d][d] f64 (symmetric; the upper half is read),
+ * dof > 0 the degrees of freedom (n - the number of non-empty groups), 0 <= shrink <= 1.
+ *   C[r][c] = S[r][c] / (double)dof;   T = (0.0 + C[0][0] + C[1][1] + ...) / (double)d;
+ *   BLISSGPU_METRIC_FORM_DIAGONAL:  w[r] = 1.0 / ((1.0 - shrink) * C[r][r] + shrink * T);  a w[r] that is not positive and
+ *       finite is *status = BLISSGPU_COV_NOT_POSITIVE;
+ *   BLISSGPU_METRIC_FORM_FULL:  C'[r][c] = (1.0 - shrink) * C[r][c], and C'[r][r] = (1.0 - shrink) * C[r][r] + shrink * T;
+ *       Cholesky-Banachiewicz C' = L L', row i by row i, column j = 0 .. i:  s = 0.0 + L[i][0] L[j][0] + ... (k < j ascending),
+ *       j < i: L[i][j] = (C'[i][j] - s) / L[j][j];  j == i: pivot = C'[i][i] - s, L[i][i] = sqrt(pivot); a pivot that is not
+ *       positive and finite is BLISSGPU_COV_NOT_POSITIVE;
+ *       Linv by forward substitution, column j, row i = j .. d - 1:  Linv[j][j] = 1.0 / L[j][j],
+ *       Linv[i][j] = (0.0 - (0.0 + L[i][j] Linv[j][j] + ... + L[i][i-1] Linv[i-1][j])) / L[i][i]  (k = j .. i - 1 ascending);
+ *       W[r][c] = 0.0 + Linv[c][r] Linv[c][c] + ... (k = c .. d - 1 ascending) for r <= c, mirrored  (W = Linv' Linv = C'^-1);
+ *   both forms: tr = 0.0 + W[0][0] + W[1][1] + ...;  M[r][c] = (float)(W[r][c] * ((double)d / tr)): the trace of M is d, the
+ *       convention of variance_based_weight_matrix.  A scale that is not positive and finite is BLISSGPU_COV_NOT_POSITIVE.
+ * *status = BLISSGPU_COV_OK and M [d][d] f32 is written; or *status = BLISSGPU_COV_NOT_POSITIVE and M is left untouched.  Both
+ * return BLISSGPU_OK.  BLISSGPU_ERR_INVALID: dof == 0, shrink outside [0, 1] (a NaN is), a form that is neither, d outside
+ * 1 .. 64, a NULL pointer. */
+#define BLISSGPU_COV_OK 0
+#define BLISSGPU_COV_NOT_POSITIVE 1
+int blissgpu_covariance_metric(const double *S, uint32_t d, uint64_t dof, int form, double shrink, float *M, int32_t *status);
+
 /* The k nearest candidates of every seed GROUP: closest_to_songs(&group, candidates, metric) cut after k, what
  * Library::playlist_from(&[several songs]).take(k) (src/library.rs:762-842) asks per album, artist, genre or saved playlist,
  * for n_groups groups in one call.  seeds is [group_offsets[n_groups]][d] row-major; group g's seeds are the rows
