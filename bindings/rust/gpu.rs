@@ -161,6 +161,14 @@ pub mod sys {
         pub fn blissgpu_group_knn_device(ctx: *mut blissgpu_ctx, d_seeds: *const f32, group_offsets: *const u64, n_groups: u64,
                                          d_cand: *const f32, n: u64, d: u32, metric: c_int, d_m: *const f32, d_skip: *const u32, k: u32,
                                          d_idx: *mut u32, d_dist: *mut f32) -> c_int;
+        // the t nearest groups of a labelling per queried group under the average nearest-member distance ("similar artists")
+        pub fn blissgpu_group_neighbours(x: *const f32, n: u64, d: u32, labels: *const u32, k: u32, metric: c_int, m_matrix: *const f32,
+                                         queries: *const u32, q: u64, t: u32, mode: c_int, slab_groups: u32, idx: *mut u32,
+                                         dist: *mut f64, sizes: *mut u32, matrix: *mut f64) -> c_int;
+        pub fn blissgpu_group_neighbours_device(ctx: *mut blissgpu_ctx, d_x: *const f32, n: u64, d: u32, d_labels: *const u32, k: u32,
+                                                metric: c_int, d_m: *const f32, d_queries: *const u32, q: u64, t: u32, mode: c_int,
+                                                slab_groups: u32, d_idx: *mut u32, d_dist: *mut f64, d_sizes: *mut u32,
+                                                d_matrix: *mut f64) -> c_int;
         // one diagonal metric per seed group: variance_based_weight_matrix of every group, and the search under it
         pub fn blissgpu_group_weights(seeds: *const f32, group_offsets: *const u64, n_groups: u64, d: u32, weights: *mut f32,
                                       group_status: *mut i32) -> c_int;

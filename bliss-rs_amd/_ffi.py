@@ -34,6 +34,7 @@ METRIC_FORM_DIAGONAL, METRIC_FORM_FULL = 0, 1
 LEARN_CONVERGED, LEARN_MAX_ITER, LEARN_DIVERGED = 0, 1, 2
 COV_OK, COV_NOT_POSITIVE = 0, 1
 MOMENTS_BLOCK = 256
+GROUPS_SYMMETRIC, GROUPS_DIRECTED = 0, 1
 
 _f32p = C.POINTER(C.c_float)
 _f64p = C.POINTER(C.c_double)
@@ -120,6 +121,10 @@ SIGNATURES = {
                                       _vp, _vp, _vp, _vp]),
     "blissgpu_silhouette_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_int, _vp, _vp, C.c_uint64,
                                              C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "blissgpu_group_neighbours": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_int, _vp, _vp, C.c_uint64, C.c_uint32,
+                                            C.c_int, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "blissgpu_group_neighbours_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_int, _vp, _vp, C.c_uint64,
+                                                   C.c_uint32, C.c_int, C.c_uint32, _vp, _vp, _vp, _vp]),
     "blissgpu_moments": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "blissgpu_moments_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "blissgpu_covariance_metric": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_int, C.c_double, _vp, _i32p]),

@@ -37,6 +37,8 @@ const char kSilhouetteScanName[] = "silhouette_scan_kernel", kSilhouetteFinishNa
 const char kMomentsPlanName[] = "moments_plan_kernel", kMomentsSumName[] = "moments_sum_kernel", kMomentsM2Name[] = "moments_m2_kernel";
 const char kMomentsScatterName[] = "moments_scatter_kernel", kMomentsReduceName[] = "moments_reduce_kernel";  // KX_MOMENTS_*
 const char kMomentsFinishName[] = "moments_finish_kernel";
+const char kChamferScanName[] = "chamfer_scan_kernel", kChamferReduceName[] = "chamfer_reduce_kernel";  // KX_CHAMFER_*
+const char kChamferSelectName[] = "chamfer_select_kernel";
 const char* const kKernelNames[K_COUNT] = {
     "fft512_kernel",     "onset_kernel",      "beat_kernel",   "stft8192_kernel", "tune_select_kernel",
     "tune_pass2_kernel", "tune_final_kernel", "chroma_kernel",     "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel", "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel",
@@ -50,6 +52,7 @@ const char* const kKernelNames[K_COUNT] = {
     kTripletStepName, kTripletReduceName,
     kSilhouetteScanName, kSilhouetteFinishName,
     kMomentsPlanName, kMomentsSumName, kMomentsM2Name, kMomentsScatterName, kMomentsReduceName, kMomentsFinishName,
+    kChamferScanName, kChamferReduceName, kChamferSelectName,
     kGroupForestScanName, kJourneyStepName};
 }  // namespace
 
@@ -358,7 +361,7 @@ int blissgpu_ctx_destroy(blissgpu_ctx* c) {
         (void)hipFree(c->bt_rwv); (void)hipFree(c->bt_dfwv); (void)hipFree(c->chroma_bank);
         scheduler_release(c);
         c->dbg_tuning.release(); c->dbg_nbpms.release(); c->dbg_chroma.release(); c->dbg_interval.release();
-        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->km_ws.release(); c->sil_ws.release(); c->mo_ws.release(); c->mt_ws.release(); c->pl_next.release(); c->st_idx.release();
+        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->km_ws.release(); c->sil_ws.release(); c->mo_ws.release(); c->ch_ws.release(); c->mt_ws.release(); c->pl_next.release(); c->st_idx.release();
         c->st_a.release(); c->st_b.release(); c->st_m.release(); c->st_dist.release(); c->st_out.release();
         c->fl_bytes.release(); c->fl_tab.release(); c->fl_pcm.release(); c->fl_status.release(); c->fl_end.release();
         c->fl_bad.release(); c->fl_mono.release(); c->fl_rows.release(); c->fl_htab.release();
@@ -1250,6 +1253,152 @@ int blissgpu_silhouette(const float* x, uint64_t n, uint32_t d, const uint32_t* 
         if (e == hipSuccess && sizes) e = hipMemcpyAsync(sizes, d_sizes, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(silhouette)", hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+// ---- group neighbours: the k-means sort of the labels, then per slab of target groups the minima per (song, group) and their
+// blocked sums, then the selection per query row (kernels_chamfer.hip); no distance matrix, the host reads one pair of words ----
+// everything that can be said about the scalar arguments and the pointers without a device; *q_eff = the rows to answer
+static int neighbours_args_ok(const char* who, const void* x, uint64_t n, uint32_t d, const void* labels, uint32_t k, int metric,
+                              const float* M, const void* queries, uint64_t q, uint32_t t, int mode, const void* idx, const void* dist,
+                              uint64_t* q_eff) {
+    if (k == 0 || k > BLISSGPU_KMEANS_MAX_K) return fail(BLISSGPU_ERR_INVALID, who, "k must be 1 .. BLISSGPU_KMEANS_MAX_K");
+    if (d == 0 || d > 64) return fail(BLISSGPU_ERR_INVALID, who, "d must be 1 .. 64");
+    if (t == 0 || t > BLISSGPU_KNN_MAX_K) return fail(BLISSGPU_ERR_INVALID, who, "t must be 1 .. BLISSGPU_KNN_MAX_K");
+    if (mode != BLISSGPU_GROUPS_SYMMETRIC && mode != BLISSGPU_GROUPS_DIRECTED) return fail(BLISSGPU_ERR_INVALID, who, "unknown mode");
+    if (metric == BLISSGPU_METRIC_COSINE) return fail(BLISSGPU_ERR_INVALID, who, "cosine: not a distance a nearest member is defined with");
+    if (metric != BLISSGPU_METRIC_EUCLIDEAN && metric != BLISSGPU_METRIC_MAHALANOBIS) return fail(BLISSGPU_ERR_INVALID, who, "unknown metric");
+    if (metric == BLISSGPU_METRIC_MAHALANOBIS && !M) return fail(BLISSGPU_ERR_INVALID, who, "mahalanobis needs M");
+    if (n >= 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "n must be below 2^32 - 1 songs");
+    *q_eff = queries ? q : k;
+    if (*q_eff >= 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "q must be below 2^32 - 1 rows");
+    if (n && !x) return fail(BLISSGPU_ERR_INVALID, who, "x is NULL");
+    if (n && !labels) return fail(BLISSGPU_ERR_INVALID, who, "labels is NULL");
+    if (*q_eff && !idx) return fail(BLISSGPU_ERR_INVALID, who, "idx is NULL");
+    if (*q_eff && !dist) return fail(BLISSGPU_ERR_INVALID, who, "dist is NULL");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_group_neighbours_device(blissgpu_ctx* c, const float* d_x, uint64_t n, uint32_t d, const uint32_t* d_labels, uint32_t k,
+                                     int metric, const float* d_M, const uint32_t* d_queries, uint64_t q, uint32_t t, int mode,
+                                     uint32_t slab_groups, uint32_t* d_idx, double* d_dist, uint32_t* d_sizes, double* d_matrix) {
+    const char* who = "blissgpu_group_neighbours_device";
+    int rc = neighbours_args_ok(who, d_x, n, d, d_labels, k, metric, d_M, d_queries, q, t, mode, d_idx, d_dist, &q);
+    if (rc) return rc;
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    CTX_ENTER(c, who);
+    if (q == 0 && !d_sizes && !d_matrix) return BLISSGPU_OK;  // no row to answer and nothing else asked for
+    const bool pairs = n && (q || d_matrix);                  // whether any distance is evaluated
+    int diag = 0;
+    if (pairs && metric == BLISSGPU_METRIC_MAHALANOBIS) {
+        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
+            diag = is_diag(c->m_cache.data(), d);
+        } else {
+            std::vector<float> hM((size_t)d * d);
+            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            diag = is_diag(hM.data(), d);
+        }
+    }
+    // workspace: flags u32[4] ([0] NaN, [1] CH_ERR_*) | hist u32[K][W] | scan totals | arow_off u32[K + 1] | arow u32[n] | (8-byte
+    // aligned) D f64[K][K] | row buffers f64[select grid][K] | minima f32[slab][n]
+    KmeansPlan sort{};
+    if (n) sort = kmeans_plan(n, k, c->n_cus);
+    const size_t o_hist = 4, o_bsum = o_hist + (size_t)sort.hist_words, o_off = o_bsum + sort.scan_tiles, o_arow = o_off + k + 1,
+                 o_d = (o_arow + (size_t)n + 1) & ~(size_t)1;
+    const ChamferPlan plan = chamfer_plan(n, k, q, d_matrix != nullptr, c->n_cus, slab_groups, c->ws_limit, o_d * sizeof(uint32_t));
+    if (!plan.fits) return fail(BLISSGPU_ERR_OOM, who, "D [k][k], the row buffers and one slab of minima do not fit the workspace limit");
+    rc = c->ch_ws.ensure(plan.bytes);
+    if (rc) return rc;
+    uint32_t* w = reinterpret_cast<uint32_t*>(c->ch_ws.p);
+    uint32_t *flags = w, *hist = w + o_hist, *bsum = w + o_bsum, *arow_off = w + o_off, *arow = w + o_arow;
+    ChamferArgs a{};
+    a.X = d_x; a.labels = d_labels; a.arow_off = arow_off; a.arow = arow; a.queries = d_queries; a.M = d_M;
+    a.n = (uint32_t)n; a.K = k; a.d = d; a.q = (uint32_t)q; a.t = t; a.metric = metric; a.mode = mode;
+    a.D = reinterpret_cast<double*>(w + o_d); a.rowbuf = a.D + (size_t)k * k;
+    a.minima = reinterpret_cast<float*>(a.rowbuf + (size_t)plan.select_grid * k);
+    a.flags = flags; a.idx = d_idx; a.dist = d_dist; a.sizes = d_sizes; a.matrix = d_matrix;
+    // the flags and the histograms; without a song the offsets too (every group is empty)
+    HIP_TRY(hipMemsetAsync(w, 0, (n ? o_hist + (size_t)sort.hist_words : o_arow) * sizeof(uint32_t), c->stream));
+    if (n) {
+        { Prof p(c, KX_KMEANS_HIST); launch_kmeans_hist(d_labels, (uint32_t)n, k, sort, hist, c->stream); }
+        { Prof p(c, KX_KMEANS_SCAN_TILES); launch_kmeans_scan_tiles(hist, sort, bsum, c->stream); }
+        { Prof p(c, KX_KMEANS_SCAN_ADD); launch_kmeans_scan_add(hist, (uint32_t)n, k, sort, bsum, arow_off, c->stream); }
+        { Prof p(c, KX_KMEANS_SCATTER); launch_kmeans_scatter(d_labels, (uint32_t)n, k, sort, hist, arow, c->stream); }
+    }
+    if (pairs)
+        for (uint32_t s0 = 0; s0 < k; s0 += plan.slab) {
+            a.s0 = s0;
+            a.s1 = (uint32_t)std::min<uint64_t>(k, (uint64_t)s0 + plan.slab);
+            { Prof p(c, KX_CHAMFER_SCAN); launch_chamfer_scan(a, diag, plan, c->n_cus, c->stream); }
+            { Prof p(c, KX_CHAMFER_REDUCE); launch_chamfer_reduce(a, c->stream); }
+        }
+    { Prof p(c, KX_CHAMFER_SELECT); launch_chamfer_select(a, plan, c->stream); }
+    HIP_TRY(hipGetLastError());
+    // the one synchronisation: the NaN word and the data-dependent errors
+    uint32_t h_flags[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (h_flags[1] & CH_ERR_LABEL) return fail(BLISSGPU_ERR_INVALID, who, "a label is >= k");
+    if (h_flags[1] & CH_ERR_QUERY) return fail(BLISSGPU_ERR_INVALID, who, "a query is >= k");
+    if (h_flags[0]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance (the reference panics here)");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_group_neighbours(const float* x, uint64_t n, uint32_t d, const uint32_t* labels, uint32_t k, int metric, const float* M,
+                              const uint32_t* queries, uint64_t q, uint32_t t, int mode, uint32_t slab_groups, uint32_t* idx,
+                              double* dist, uint32_t* sizes, double* matrix) {
+    const char* who = "blissgpu_group_neighbours";
+    int rc = neighbours_args_ok(who, x, n, d, labels, k, metric, M, queries, q, t, mode, idx, dist, &q);
+    if (rc) return rc;
+    // labels and queries are host memory: what the device form finds after its sort is found here, before the device is touched
+    for (uint64_t i = 0; i < n; i++)
+        if (labels[i] >= k) return fail(BLISSGPU_ERR_INVALID, who, "a label is >= k");
+    if (queries)
+        for (uint64_t g = 0; g < q; g++)
+            if (queries[g] >= k) return fail(BLISSGPU_ERR_INVALID, who, "a query is >= k");
+    if (n == 0 || (q == 0 && !matrix)) {  // no song, or no row to answer: nothing for a device to do
+        if (sizes) {
+            memset(sizes, 0, (size_t)k * sizeof(uint32_t));
+            for (uint64_t i = 0; i < n; i++) sizes[labels[i]]++;
+        }
+        if (n == 0) {
+            for (uint64_t e = 0; e < q * t; e++) { idx[e] = 0xFFFFFFFFu; dist[e] = INFINITY; }
+            if (matrix)
+                for (uint64_t e = 0; e < (uint64_t)k * k; e++) matrix[e] = (e / k == e % k) ? 0.0 : (double)INFINITY;
+        }
+        return BLISSGPU_OK;
+    }
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    const float* dM = nullptr;
+    const size_t kk = matrix ? (size_t)k * k : 0;
+    rc = c->st_b.ensure(n * d);
+    if (!rc) rc = c->st_idx.ensure(n + q + q * t + k);  // labels | queries | idx | sizes
+    if (!rc) rc = c->st_out.ensure((q * t + kk) * sizeof(double));  // dist | matrix
+    if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
+    if (rc) return rc;
+    uint32_t *d_labels = c->st_idx.p, *d_queries = queries ? c->st_idx.p + n : nullptr, *d_idx = c->st_idx.p + n + q,
+             *d_sizes = c->st_idx.p + n + q + q * t;
+    double *d_dist = reinterpret_cast<double*>(c->st_out.p), *d_matrix = matrix ? d_dist + q * t : nullptr;
+    hipError_t e = hipMemcpyAsync(c->st_b.p, x, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_labels, labels, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && queries && q) e = hipMemcpyAsync(d_queries, queries, q * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(group_neighbours)", hipGetErrorString(e));
+    if (!rc)
+        rc = blissgpu_group_neighbours_device(c, c->st_b.p, n, d, d_labels, k, metric, dM, d_queries, q, t, mode, slab_groups, d_idx,
+                                              d_dist, sizes ? d_sizes : nullptr, d_matrix);
+    if (!rc) {
+        if (q) e = hipMemcpyAsync(idx, d_idx, q * t * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && q) e = hipMemcpyAsync(dist, d_dist, q * t * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && sizes) e = hipMemcpyAsync(sizes, d_sizes, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && matrix) e = hipMemcpyAsync(matrix, d_matrix, kk * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(group_neighbours)", hipGetErrorString(e));
     }
     (void)hipStreamSynchronize(c->stream);
     return rc;

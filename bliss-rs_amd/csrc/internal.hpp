@@ -123,7 +123,7 @@ enum KernelId : int {
     K_CHAIN_STEP, K_CHAIN_WALK,             // song-to-song chains cut after k (kernels_chains.hip)
     // (tests/test_chains_host.py holds this list, and the list of names beside it, to end in the chain kernels: the kernels
     // that came later are numbered behind it, so that no older id or name moves)
-    K_COUNT = K_CHAIN_WALK + 21
+    K_COUNT = K_CHAIN_WALK + 24
 };
 // k-nearest albums per seed group (kernels_albums.hip; its partial lists are merged by knn_merge_kernel)
 constexpr int KX_SEGMENT_MEAN = K_CHAIN_WALK + 1, KX_ALBUM_KNN_SCAN = K_CHAIN_WALK + 2;
@@ -138,12 +138,14 @@ constexpr int KX_SILHOUETTE_SCAN = K_CHAIN_WALK + 11, KX_SILHOUETTE_FINISH = K_C
 // scatter matrix, every further level of the blocked sum, the extrema
 constexpr int KX_MOMENTS_PLAN = K_CHAIN_WALK + 13, KX_MOMENTS_SUM = K_CHAIN_WALK + 14, KX_MOMENTS_M2 = K_CHAIN_WALK + 15,
               KX_MOMENTS_SCATTER = K_CHAIN_WALK + 16, KX_MOMENTS_REDUCE = K_CHAIN_WALK + 17, KX_MOMENTS_FINISH = K_CHAIN_WALK + 18;
+// group-to-group set distances (kernels_chamfer.hip): the minima per (song, group), their blocked sums, the rows' selection
+constexpr int KX_CHAMFER_SCAN = K_CHAIN_WALK + 19, KX_CHAMFER_REDUCE = K_CHAIN_WALK + 20, KX_CHAMFER_SELECT = K_CHAIN_WALK + 21;
 // (tests/test_journeys_host.py holds the profile table to END in the next two names: kernels that come later are numbered in
 // front of them; every consumer of the table goes by name)
 // the k lowest forest scores per seed group (kernels_forest.hip; its partial lists are merged by group_knn_merge_kernel)
-constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 19;
+constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 22;
 // a journey's step (kernels_chains.hip: the chains' scan with a waypoint query or a gate)
-constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 20;
+constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 23;
 static_assert(KX_JOURNEY_STEP + 1 == K_COUNT, "every kernel id is below the count");
 
 // lower_bound on a prefix array: largest s with prefix[s] <= x  (prefix has n+1 entries, prefix[0]=0)
@@ -423,6 +425,40 @@ void launch_moments_reduce(const double* in, const uint32_t* in_off, uint32_t in
                            uint32_t d, hipStream_t st);
 void launch_moments_finish(const uint32_t* counts, const uint32_t* key_min, const uint32_t* key_max, uint32_t K, uint32_t d, float* mn,
                            float* mx, hipStream_t st);
+// group-to-group set distances (kernels_chamfer.hip), after the k-means sort of the labels into arow_off / arow.  The target
+// groups are taken in slabs [s0, s1): the scan writes minima [s1 - s0][n] (m(i, c) at [c - s0][position of i in the sorted
+// order]), the reduce D [K][K] (D(a -> c) for non-empty a != c of the slab; nothing else is written or read).  The select forms
+// A per query row (queries NULL: row g = group g) through rowbuf [select_grid][K], writes idx / dist [q][t], sizes and matrix
+// (both may be NULL).  flags[0]: a NaN among the minima; flags[1]: CH_ERR_*
+constexpr uint32_t CH_ERR_LABEL = 1u, CH_ERR_QUERY = 2u;
+constexpr uint64_t CHAMFER_SLAB_BYTES = 512ull << 20;  // the plan's slab holds at most this many bytes of minima
+struct ChamferArgs {
+    const float* X;
+    const uint32_t *labels, *arow_off, *arow, *queries;
+    const float* M;
+    uint32_t n, K, d, q, t;
+    int metric, mode;
+    uint32_t s0, s1, Y;
+    float* minima;
+    double *D, *rowbuf;
+    uint32_t* flags;
+    uint32_t* idx;
+    double* dist;
+    uint32_t* sizes;
+    double* matrix;
+};
+struct ChamferPlan {
+    uint32_t waves, grid;  // wavefronts per workgroup of the scan (256 positions each), its workgroups per column group
+    uint32_t select_grid;  // workgroups of the select, each with a row buffer
+    uint32_t slab;         // target groups per pass: slab_groups when not 0, else what CHAMFER_SLAB_BYTES and the limit hold
+    uint64_t bytes;        // the whole workspace: fixed_bytes (flags and the sort) + D + row buffers + minima
+    bool fits;             // bytes <= ws_limit
+};
+ChamferPlan chamfer_plan(uint64_t n, uint32_t K, uint64_t q, bool want_matrix, int n_cus, uint32_t slab_groups, uint64_t ws_limit,
+                         uint64_t fixed_bytes);
+void launch_chamfer_scan(ChamferArgs a, int m_is_diag, const ChamferPlan& p, int n_cus, hipStream_t st);  // (sets a.Y for the slab)
+void launch_chamfer_reduce(const ChamferArgs& a, hipStream_t st);
+void launch_chamfer_select(const ChamferArgs& a, const ChamferPlan& p, hipStream_t st);
 // triplet metric learning, one gradient evaluation (kernels_metric.hip).  The triplets are dealt out in W contiguous chunks, a
 // function of T alone; part [W][pairs + 1] f64 and cnt [W][2] u64 are the wavefronts' partials, out = G f64 [d][d] | loss f64 |
 // n_active u64 | error bits u64 (TRIPLET_ERR_*).  mode says how M is read; flags (u8 [T]) may be NULL

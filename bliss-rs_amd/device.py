@@ -568,6 +568,67 @@ class Context:
         out = (s, a, b, nb, sizes)
         return tuple(t.cpu().numpy() for t in out) if as_numpy else out
 
+    def group_neighbours(self, X, labels, k: int = None, t: int = 1, metric: str = "euclidean", M=None, queries=None,
+                         mode: str = "symmetric", slab_groups: int = 0, want_matrix: bool = False):
+        """The t nearest groups of every queried group of the labelling `labels` of the rows of X under the average
+        nearest-member (Chamfer) distance, on the device without the distance matrix (blissgpu_group_neighbours_device,
+        DESIGN.md 3.25), all defined to the bit by include/blissgpu.h.  X float32 [n, d] and labels (int32 / int64, every one in
+        0 .. k - 1) are tensors on the device, or numpy arrays (uploaded, results returned as arrays); k: the number of groups,
+        None = labels.max() + 1; queries: the groups to answer for (any order, repeats allowed), None = all k in order; mode
+        "symmetric" or "directed".
+        -> (idx int32 [q, t] with -1 as padding, dist float64 [q, t] with +inf as padding, sizes int32 [k], matrix float64 [k, k]
+        or None unless `want_matrix`).  slab_groups: 0 = the plan's choice; no result bit depends on it.  Raises BlissGpuError:
+        ERR_NAN for a NaN among the evaluated distances, ERR_INVALID for a label or a query >= k, ERR_OOM when the workspace does
+        not fit the context's limit; synchronises once."""
+        from .playlist import _GROUP_MODES, _METRICS
+
+        torch = self.torch
+        as_numpy = not torch.is_tensor(X)
+        dev = torch.device("cuda", self.device)
+
+        def up_f32(a):
+            return None if a is None else (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev))
+
+        def up_u32(a, what):  # -> int32 tensor holding the uint32 bits
+            if a is None:
+                return None
+            if torch.is_tensor(a):
+                assert a.is_cuda and a.dtype in (torch.int32, torch.int64), what
+                return a.to(torch.int32).contiguous().reshape(-1)
+            a = np.asarray(a, dtype=np.int64).reshape(-1)
+            if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+                raise ValueError(f"{what} must be non-negative indices")
+            return torch.from_numpy(a.astype(np.uint32).view(np.int32)).to(dev)
+
+        if mode not in _GROUP_MODES:
+            raise ValueError(f"mode must be one of {tuple(_GROUP_MODES)}")
+        X, M = up_f32(X), up_f32(M)
+        labels, queries = up_u32(labels, "labels"), up_u32(queries, "queries")
+        assert X.is_cuda and X.dtype == torch.float32 and X.dim() == 2
+        X = X.contiguous()
+        n, d = X.shape
+        if labels.shape[0] != n:
+            raise ValueError("a label per row of X is needed")
+        if M is not None:
+            assert M.is_cuda and M.dtype == torch.float32
+            M = M.contiguous()
+        if k is None:
+            k = int(labels.max().item()) + 1 if n else 1
+        k, t = int(k), int(t)
+        q = max(k, 0) if queries is None else queries.shape[0]
+        ptr = lambda a: None if a is None else C.c_void_p(a.data_ptr())  # noqa: E731
+        idx = torch.full((q, max(t, 0)), -1, dtype=torch.int32, device=X.device)
+        dist = torch.full((q, max(t, 0)), float("inf"), dtype=torch.float64, device=X.device)
+        sizes = torch.zeros((max(k, 0),), dtype=torch.int32, device=X.device)
+        matrix = torch.zeros((max(k, 0), max(k, 0)), dtype=torch.float64, device=X.device) if want_matrix else None
+        self._pre()
+        _ffi.check(self._L.blissgpu_group_neighbours_device(self._h, ptr(X), n, d, ptr(labels), k, _METRICS[metric], ptr(M), ptr(queries),
+                                                            q, t, _GROUP_MODES[mode], int(slab_groups), ptr(idx), ptr(dist), ptr(sizes),
+                                                            ptr(matrix)))
+        self._post()
+        out = (idx, dist, sizes, matrix)
+        return tuple(None if a is None else a.cpu().numpy() for a in out) if as_numpy else out
+
     def moments(self, X, labels=None, k: int = None, scatter: bool = True):
         """The first and second moments of the rows of X on the device (blissgpu_moments_device), per group of
         the labelling `labels` and pooled, every sum the blocked sum of include/blissgpu.h.  X float32 [n, d] and labels (int32 /

@@ -36,6 +36,9 @@ database:
                                           than they are to odd_one_out", src/library.rs:542-556) as row indices, and a writer
     learn_metric                          a Mahalanobis M for MahalanobisBuilder, learned on the device from those triplets
                                           or from triplets drawn from genre / album / artist / cluster labels
+    similar_groups, similar_artists,      which artists (albums, genres) are like each other under the average nearest-member
+    similar_artists_playlist              distance (playlist.group_neighbours), one device call for every key; and the
+                                          "similar artists to the current one" playlist of the reference's TODO.md
 
 SQLite stores `real` as f64; an f32 feature widens exactly on the way in and narrows exactly on the way out, so a
 round trip is bit-exact.  The schema, load and store helpers are host code; the playlists run their distances on the
@@ -884,3 +887,66 @@ def album_playlists(db: Conn, number_albums: int, by: str = "album", groups=None
                 pl.extend(songs[i] for i in sorted((i for i in album_rows[a] if i not in gone), key=disc_track))
         out[key] = pl
     return out
+
+
+def _album_disc_track(s):  # Option / SQLite: None first
+    a, d, t = s.album, s.disc_number, s.track_number
+    return ((0, "") if a is None else (1, a), (0, 0) if d is None else (1, d), (0, 0) if t is None else (1, t))
+
+
+def _similar_groups(db: Conn, number: int, by: str, metric_builder, mode: str, needed=None):
+    """-> (songs, members {key: [row]}, keys, GroupNeighbours or None) for the column `by` of the analysed songs; a `needed` key
+    that no song has is a ProviderError, raised before the device is touched"""
+    playlist._group_neighbours_metric(metric_builder)  # refused before the database is read
+    if by not in _LABEL_COLUMNS:
+        raise ValueError(f"by must be one of {_LABEL_COLUMNS}")
+    number = int(number)
+    if number < 0:
+        raise ValueError("number must not be negative")
+    if number > 1024:
+        raise ValueError("at most 1024 neighbours per group")
+    songs, X = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
+    code, members, labels = {}, {}, np.full(len(songs), -1, np.int64)
+    for i, s in enumerate(songs):
+        tag = getattr(s, by)
+        if tag is not None:
+            labels[i] = code.setdefault(tag, len(code))
+            members.setdefault(tag, []).append(i)
+    keys = list(code)
+    if needed is not None and needed not in members:
+        raise ProviderError(f"target {by} was not found in the database.")
+    if number == 0 or len(keys) < 2:
+        return songs, members, keys, None
+    return songs, members, keys, playlist.group_neighbours(X, labels, min(number, len(keys) - 1), metric_builder, len(keys), None, mode)
+
+
+def similar_groups(db: Conn, number: int, by: str = "artist", metric_builder=playlist.euclidean_distance, mode: str = "symmetric"):
+    """Which artists (albums, genres, album artists) of the library are like each other: {key: [(other_key, distance), ...]} with
+    the `number` nearest other keys of every key of the column `by`, nearest first, under the average nearest-member distance
+    of playlist.group_neighbours (the reference's TODO.md: "similar artists to the current one").  A set-to-set distance: an
+    artist with two styles is near the artists who cover both, where the distance of mean vectors (album_playlists) would put
+    it next to artists who sound like neither.  The songs are those of FeaturesVersion.LATEST; songs whose tag is NULL are left
+    out.  The library is read once and ONE device call answers every key.  mode "directed": how well the other key covers this
+    one.  metric_builder: euclidean_distance or a MahalanobisBuilder."""
+    _, _, keys, res = _similar_groups(db, number, by, metric_builder, mode)
+    if res is None:
+        return {key: [] for key in keys}
+    return {key: [(keys[int(c)], float(v)) for c, v in zip(res.idx[g], res.dist[g]) if c >= 0] for g, key in enumerate(keys)}
+
+
+def similar_artists(db: Conn, number: int, metric_builder=playlist.euclidean_distance, mode: str = "symmetric"):
+    """similar_groups with by="artist": {artist: [(other artist, distance), ...]}, nearest first."""
+    return similar_groups(db, number, "artist", metric_builder, mode)
+
+
+def similar_artists_playlist(db: Conn, artist: str, number_artists: int, metric_builder=playlist.euclidean_distance) -> List[Song]:
+    """The "similar artists to the current one" playlist of the reference's TODO.md: the artist's songs, then the songs of the
+    `number_artists` closest artists (similar_groups, symmetric) in that order, each artist's songs by album, disc and track
+    number, None first.  An unknown artist is a ProviderError; number_artists == 0 returns the artist's songs without touching
+    the device."""
+    number_artists = int(number_artists)
+    songs, members, keys, res = _similar_groups(db, number_artists, "artist", metric_builder, "symmetric", artist)
+    order = [artist]
+    if res is not None:
+        order.extend(keys[int(c)] for c in res.idx[keys.index(artist)] if c >= 0)
+    return [s for key in order for s in sorted((songs[i] for i in members[key]), key=_album_disc_track)]

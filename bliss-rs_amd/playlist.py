@@ -14,6 +14,8 @@
     kmeans, kmeans_init, cluster_songs (the clustering the reference's TODO.md asks for: Lloyd's algorithm on the device)
     silhouette, choose_k (the "objective way to evaluate" of the reference's TODO.md: how well a labelling separates the songs
     under a metric, all pairs on the device without the distance matrix; and the k whose k-means clusters separate them best)
+    group_neighbours (the "similar artists to the current one" of the reference's TODO.md: the nearest groups of a labelling
+    under the average nearest-member distance, all pairs on the device without the distance matrix)
     triplet_step, learn_metric, triplet_accuracy, triplets_from_labels (the metric learning the reference's TODO.md and its
     training_triplet table ask for: a Mahalanobis M from "a and b are closer than o" triplets, the gradient on the device)
 
@@ -25,8 +27,9 @@ because the distances are evaluated by the HIP kernels (there is no CPU path).  
 `.analysis` (Analysis) -- `Song` or a wrapper holding one in `.bliss_song`, like the reference's
 `AsRef<Song>`."""
 import ctypes as C
+import dataclasses
 import os
-from typing import Callable, Sequence
+from typing import Callable, Optional, Sequence
 
 import numpy as np
 
@@ -694,6 +697,79 @@ def silhouette(X, labels, metric_builder=euclidean_distance, rows=None, k=None, 
     except _ffi.BlissGpuError as e:
         _nan_to_panic(e)
     return Silhouette(s, a, b, nb, sizes, lab if rows is None else lab[rows])
+
+
+_GROUP_MODES = {"symmetric": _ffi.GROUPS_SYMMETRIC, "directed": _ffi.GROUPS_DIRECTED}
+
+
+@dataclasses.dataclass
+class GroupNeighbours:
+    """The result of group_neighbours: idx int64[q, t] (row g: the t groups nearest to queries[g], ascending; -1 = padding),
+    dist float64[q, t] (their distances; +inf = padding), sizes int64[k] (the members per group) and matrix float64[k, k] (every
+    A(a, c); None unless asked for)."""
+
+    idx: np.ndarray
+    dist: np.ndarray
+    sizes: np.ndarray
+    matrix: Optional[np.ndarray] = None
+
+
+def _group_neighbours_metric(metric_builder):
+    """the metrics the group distances can run: euclidean, or Mahalanobis with the caller's matrix"""
+    _no_forest(metric_builder, "the group distances compare single songs; a forest scores songs against a seed set")
+    _no_variance(metric_builder, "the group distances have no seed set to take variances from; pass MahalanobisBuilder(m)")
+    metric, m = _metric_of(metric_builder)
+    if metric == "cosine":
+        raise ValueError("the group distances need a distance a nearest member is defined with: euclidean or mahalanobis, not cosine")
+    return metric, m
+
+
+def group_neighbours(songs_or_X, labels, t, metric_builder=euclidean_distance, k=None, queries=None, mode="symmetric", matrix=False,
+                     slab_groups=0) -> GroupNeighbours:
+    """Which groups of a labelling (artists, albums, genres, clusters) are like each other: for every queried group its t
+    nearest groups under the average nearest-member (Chamfer) distance, in one device call without the distance matrix
+    (blissgpu_group_neighbours).  For every song of group a the distance to the closest song of group c,
+    averaged over a: mode "directed" keeps that ("how well c covers a"), "symmetric" takes the mean of the two directions.
+    Every value is defined to the bit by include/blissgpu.h.  labels: one group index per row (an array, or songs' rows); rows
+    with a label < 0 are left out.  k: the number of groups, None = labels.max() + 1.  queries: the groups to answer for (any
+    order, repeats allowed), None = all k in order.  matrix: also return every A(a, c).  slab_groups is for the tests and the
+    bench tool (no result bit depends on it).  metric_builder: euclidean_distance or a MahalanobisBuilder (its M); a
+    ForestOptions, a VarianceWeights, cosine and arbitrary callables are refused.  A label >= k or a query >= k raise
+    BlissGpuError(ERR_INVALID), a NaN distance ValueError."""
+    metric, m = _group_neighbours_metric(metric_builder)
+    if mode not in _GROUP_MODES:
+        raise ValueError(f"mode must be one of {tuple(_GROUP_MODES)}")
+    X = _rows_of_input(songs_or_X)
+    lab = np.asarray(labels).reshape(-1).astype(np.int64)
+    if lab.shape[0] != X.shape[0]:
+        raise ValueError("a label per row of X is needed")
+    keep = lab >= 0
+    if not keep.all():
+        X, lab = np.ascontiguousarray(X[keep]), lab[keep]
+    lab = _index_array(lab, "labels")
+    n, d = X.shape
+    k = (int(lab.max()) + 1 if n else 1) if k is None else int(k)
+    t = int(t)
+    qp, q = None, max(k, 0)
+    if queries is not None:
+        queries = _index_array(queries, "queries")
+        qp, q = queries.ctypes.data, queries.shape[0]
+    mp = None
+    if m is not None:
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        mp = m.ctypes.data
+    idx, dist = np.full((q, max(t, 0)), 0xFFFFFFFF, np.uint32), np.full((q, max(t, 0)), np.inf, np.float64)
+    sizes = np.zeros(max(k, 0), np.uint32)
+    mat = np.zeros((max(k, 0), max(k, 0)), np.float64) if matrix else None
+    try:
+        _ffi.check(_ffi.lib().blissgpu_group_neighbours(X.ctypes.data, n, d, lab.ctypes.data, k, _METRICS[metric], mp, qp, q, t,
+                                                        _GROUP_MODES[mode], int(slab_groups), idx.ctypes.data, dist.ctypes.data,
+                                                        sizes.ctypes.data, None if mat is None else mat.ctypes.data))
+    except _ffi.BlissGpuError as e:
+        _nan_to_panic(e)
+    out = idx.astype(np.int64)
+    out[idx == 0xFFFFFFFF] = -1
+    return GroupNeighbours(out, dist, sizes.astype(np.int64), mat)
 
 
 class KSelection:

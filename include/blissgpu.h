@@ -489,6 +489,53 @@ int blissgpu_silhouette_device(blissgpu_ctx *ctx, const float *d_x, uint64_t n, 
                                int metric, const float *d_M, const uint32_t *d_rows, uint64_t q, uint32_t col_groups, float *d_s,
                                double *d_a, double *d_b, uint32_t *d_neighbour, uint32_t *d_sizes);
 
+/* ---- Group neighbours: which groups of a labelling are like each other (the reference's TODO.md asks: "Have a
+ * 'similar artists to the current one' playlist option", it has no code) ----
+ * The average nearest-member (Chamfer) distance between the groups of a labelling (artists, albums, genres, clusters) of the rows
+ * x [n][d], and per queried group its t nearest groups.  A set-to-set distance, not a distance of means: a group with two styles
+ * is near the groups that cover both.  Every step is defined to the bit.
+ * Inputs: x [n][d] f32; labels [n] u32, every one < k; k groups; metric: BLISSGPU_METRIC_EUCLIDEAN, or BLISSGPU_METRIC_MAHALANOBIS
+ * with the caller's M (a diagonal M is detected as everywhere else); queries [q] u32 (NULL = all k groups in order: q is then taken
+ * as k) = the groups to answer for, any order, repeats allowed; t = neighbours per query; mode BLISSGPU_GROUPS_*.
+ * With dist(i, j) = bit for bit what blissgpu_pairwise_device(x, x) writes at [i][j], size_c = the member count of group c, and
+ * "members in order" = ascending row index:
+ *   m(i, c)  = the minimum of dist(i, j) over the members j of c (f32); defined for c != labels[i] with size_c > 0;
+ *   T(a, c)  = the f64 sum of (double)m(i, c) over the members i of a in order, u = 0, 1, ..., added in this fixed order: the
+ *              terms are cut into blocks of BLISSGPU_MOMENTS_BLOCK = 256, the last block padded with +0.0; within a block, for
+ *              h = 128, 64, ..., 1:  v[u] = v[u] + v[u + h] for every u < h, the block's sum is v[0]; the block sums are added
+ *              sequentially in ascending block order, starting from 0.0.  Every add is rounded on its own;
+ *   D(a->c)  = T(a, c) / (double)size_a;
+ *   A(a, c)  = (D(a->c) + D(c->a)) * 0.5 under BLISSGPU_GROUPS_SYMMETRIC;  D(a->c), "how well c covers a", under
+ *              BLISSGPU_GROUPS_DIRECTED.
+ * Outputs: row g of idx [q][t] u32 and dist [q][t] f64, with a = queries[g]: the t groups c != a with size_c > 0 of smallest
+ * A(a, c), ascending; equal values go to the lower c; with fewer than t such groups, or an empty a, the rest of the row is
+ * 0xFFFFFFFF / +inf (the k-nearest padding).  sizes [k] u32 (may be NULL).  matrix [k][k] f64 (may be NULL) = A, with 0.0 on
+ * the diagonal (of an empty group too) and +inf elsewhere wherever either group is empty.
+ * A NaN among the m(i, c) returns BLISSGPU_ERR_NAN; the outputs are then unspecified.  BLISSGPU_ERR_INVALID:
+ * BLISSGPU_METRIC_COSINE (the message names it); a label >= k; a query >= k; d outside 1 .. 64; k outside
+ * 1 .. BLISSGPU_KMEANS_MAX_K; t outside 1 .. BLISSGPU_KNN_MAX_K; n or q >= 2^32 - 1; NULL x or labels with n > 0, NULL idx or dist with q > 0; an unknown mode.
+ * n == 0 is BLISSGPU_OK: rows of padding, zero sizes.  q == 0 is BLISSGPU_OK: no row is written (sizes and matrix still are).
+ * Fewer than two non-empty groups is not an error: rows of padding.
+ * The host form checks all of these before the device is touched; its labels and queries are host memory.
+ * slab_groups: the target groups c are taken in passes of `slab` groups; 0 lets the plan choose, anything else forces that many
+ * (at most k).  No bit of any output depends on it: the argument exists for the tests and the bench tool.
+ * No n x n matrix is ever stored.  Workspace, grow-only in the context: the k-means sort's O(n + chunks x k), n x slab x 4 bytes of
+ * minima, k x k x 8 bytes of D and O(k) per workgroup of the selection.  When that exceeds the context's workspace limit
+ * (blissgpu_ctx_get_workspace_limit) with the plan's smallest slab, or with a forced one, the call returns BLISSGPU_ERR_OOM
+ * before anything is launched. */
+#define BLISSGPU_GROUPS_SYMMETRIC 0
+#define BLISSGPU_GROUPS_DIRECTED 1
+int blissgpu_group_neighbours(const float *x, uint64_t n, uint32_t d, const uint32_t *labels, uint32_t k, int metric, const float *M,
+                              const uint32_t *queries, uint64_t q, uint32_t t, int mode, uint32_t slab_groups, uint32_t *idx,
+                              double *dist, uint32_t *sizes, double *matrix);
+/* Device-resident form (device pointers throughout).  It checks the scalar arguments before it looks at its context, and
+ * reports the data-dependent errors (a label >= k, a query >= k, NaN) after the sort, at its one synchronisation of the
+ * context's stream before returning. */
+int blissgpu_group_neighbours_device(blissgpu_ctx *ctx, const float *d_x, uint64_t n, uint32_t d, const uint32_t *d_labels,
+                                     uint32_t k, int metric, const float *d_M, const uint32_t *d_queries, uint64_t q, uint32_t t,
+                                     int mode, uint32_t slab_groups, uint32_t *d_idx, double *d_dist, uint32_t *d_sizes,
+                                     double *d_matrix);
+
 /* ---- Learning the Mahalanobis matrix from training triplets ----
  * The reference has a `training_triplet` table ("song_1 and song_2 are closer together than they are to odd_one_out",
  * src/library.rs:542-556), a TODO.md that asks for "a way to learn a metric with a user survey", and no code that learns.
