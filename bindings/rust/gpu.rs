@@ -65,6 +65,7 @@ pub mod sys {
     pub const BLISSGPU_ERR_NAN: c_int = 5;
     pub const BLISSGPU_ERR_RCCL: c_int = 6;
     pub const BLISSGPU_ERR_TIMEOUT: c_int = 7;
+    pub const BLISSGPU_ERR_INTERNAL: c_int = 8;
     pub const BLISSGPU_SONG_OK: i32 = 0;
     pub const BLISSGPU_SONG_TOO_SHORT: i32 = 1;
     pub const BLISSGPU_SONG_DECODE_ERROR: i32 = 2;
@@ -169,6 +170,12 @@ pub mod sys {
                                                 metric: c_int, d_m: *const f32, d_queries: *const u32, q: u64, t: u32, mode: c_int,
                                                 slab_groups: u32, d_idx: *mut u32, d_dist: *mut f64, d_sizes: *mut u32,
                                                 d_matrix: *mut f64) -> c_int;
+        // the minimum spanning tree of a library under (weight bits, lower song, higher song): clusters without k, a tour
+        pub fn blissgpu_mst(x: *const f32, n: u64, d: u32, metric: c_int, m_matrix: *const f32, core: *const f32, edge_u: *mut u32,
+                            edge_v: *mut u32, edge_w: *mut f32, rounds: *mut u32) -> c_int;
+        pub fn blissgpu_mst_device(ctx: *mut blissgpu_ctx, d_x: *const f32, n: u64, d: u32, metric: c_int, d_m: *const f32,
+                                   d_core: *const f32, d_edge_u: *mut u32, d_edge_v: *mut u32, d_edge_w: *mut f32,
+                                   rounds: *mut u32) -> c_int;
         // one diagonal metric per seed group: variance_based_weight_matrix of every group, and the search under it
         pub fn blissgpu_group_weights(seeds: *const f32, group_offsets: *const u64, n_groups: u64, d: u32, weights: *mut f32,
                                       group_status: *mut i32) -> c_int;

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # BLISSGPU_LIB: developer aid for A/B timing of two builds of the library on the same box (never a CPU path)
 LIB_PATH = os.environ.get("BLISSGPU_LIB") or os.path.join(_HERE, "libblissgpu.so")
 
-OK, ERR_NO_DEVICE, ERR_INVALID, ERR_HIP, ERR_OOM, ERR_NAN, ERR_RCCL, ERR_TIMEOUT = 0, 1, 2, 3, 4, 5, 6, 7
+OK, ERR_NO_DEVICE, ERR_INVALID, ERR_HIP, ERR_OOM, ERR_NAN, ERR_RCCL, ERR_TIMEOUT, ERR_INTERNAL = 0, 1, 2, 3, 4, 5, 6, 7, 8
 SAMPLE_F32, SAMPLE_S16, SAMPLE_S32 = 0, 1, 2
 SAMPLE_RATE = 22050
 SONG_OK, SONG_TOO_SHORT, SONG_DECODE_ERROR = 0, 1, 2
@@ -125,6 +125,8 @@ SIGNATURES = {
                                             C.c_int, C.c_uint32, _vp, _vp, _vp, _vp]),
     "blissgpu_group_neighbours_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_int, _vp, _vp, C.c_uint64,
                                                    C.c_uint32, C.c_int, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "blissgpu_mst": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "blissgpu_mst_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "blissgpu_moments": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "blissgpu_moments_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "blissgpu_covariance_metric": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_int, C.c_double, _vp, _i32p]),

@@ -17,6 +17,7 @@
 #include "ctx.hpp"
 #include "metric_learn.hpp"
 #include "covariance_metric.hpp"
+#include "mst_merge.hpp"
 #include "forest.hpp"
 
 using namespace bg;
@@ -39,6 +40,7 @@ const char kMomentsScatterName[] = "moments_scatter_kernel", kMomentsReduceName[
 const char kMomentsFinishName[] = "moments_finish_kernel";
 const char kChamferScanName[] = "chamfer_scan_kernel", kChamferReduceName[] = "chamfer_reduce_kernel";  // KX_CHAMFER_*
 const char kChamferSelectName[] = "chamfer_select_kernel";
+const char kMstScanName[] = "mst_scan_kernel", kMstPickName[] = "mst_pick_kernel";  // KX_MST_*
 const char* const kKernelNames[K_COUNT] = {
     "fft512_kernel",     "onset_kernel",      "beat_kernel",   "stft8192_kernel", "tune_select_kernel",
     "tune_pass2_kernel", "tune_final_kernel", "chroma_kernel",     "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel", "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel",
@@ -53,6 +55,7 @@ const char* const kKernelNames[K_COUNT] = {
     kSilhouetteScanName, kSilhouetteFinishName,
     kMomentsPlanName, kMomentsSumName, kMomentsM2Name, kMomentsScatterName, kMomentsReduceName, kMomentsFinishName,
     kChamferScanName, kChamferReduceName, kChamferSelectName,
+    kMstScanName, kMstPickName,
     kGroupForestScanName, kJourneyStepName};
 }  // namespace
 
@@ -300,6 +303,7 @@ const char* blissgpu_strerror(int code) {
         case BLISSGPU_ERR_OOM: return "out of device memory";
         case BLISSGPU_ERR_RCCL: return "RCCL error";
         case BLISSGPU_ERR_TIMEOUT: return "no default context picked the call up within its deadline";
+        case BLISSGPU_ERR_INTERNAL: return "a bounded loop did not end";
         default: return "unknown error";
     }
 }
@@ -361,7 +365,7 @@ int blissgpu_ctx_destroy(blissgpu_ctx* c) {
         (void)hipFree(c->bt_rwv); (void)hipFree(c->bt_dfwv); (void)hipFree(c->chroma_bank);
         scheduler_release(c);
         c->dbg_tuning.release(); c->dbg_nbpms.release(); c->dbg_chroma.release(); c->dbg_interval.release();
-        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->km_ws.release(); c->sil_ws.release(); c->mo_ws.release(); c->ch_ws.release(); c->mt_ws.release(); c->pl_next.release(); c->st_idx.release();
+        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->km_ws.release(); c->sil_ws.release(); c->mo_ws.release(); c->ch_ws.release(); c->ms_ws.release(); c->mt_ws.release(); c->pl_next.release(); c->st_idx.release();
         c->st_a.release(); c->st_b.release(); c->st_m.release(); c->st_dist.release(); c->st_out.release();
         c->fl_bytes.release(); c->fl_tab.release(); c->fl_pcm.release(); c->fl_status.release(); c->fl_end.release();
         c->fl_bad.release(); c->fl_mono.release(); c->fl_rows.release(); c->fl_htab.release();
@@ -1402,6 +1406,158 @@ int blissgpu_group_neighbours(const float* x, uint64_t n, uint32_t d, const uint
     }
     (void)hipStreamSynchronize(c->stream);
     return rc;
+}
+
+// ---- the minimum spanning tree: Boruvka's rounds, each one scan and one pick on the device (kernels_mst.hip) and the merge on
+// the host (mst_merge.hpp); no distance matrix, the host reads one pair of words and one pick per component per round ----
+// everything that can be said about the scalar arguments and the pointers without a device
+static int mst_args_ok(const char* who, const void* x, uint64_t n, uint32_t d, int metric, const float* M, const void* eu, const void* ev,
+                       const void* ew) {
+    if (d == 0 || d > 64) return fail(BLISSGPU_ERR_INVALID, who, "d must be 1 .. 64");
+    if (metric == BLISSGPU_METRIC_COSINE) return fail(BLISSGPU_ERR_INVALID, who, "cosine: not a distance a spanning tree is defined with");
+    if (metric != BLISSGPU_METRIC_EUCLIDEAN && metric != BLISSGPU_METRIC_MAHALANOBIS) return fail(BLISSGPU_ERR_INVALID, who, "unknown metric");
+    if (metric == BLISSGPU_METRIC_MAHALANOBIS && !M) return fail(BLISSGPU_ERR_INVALID, who, "mahalanobis needs M");
+    if (n >= 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "n must be below 2^32 - 1 songs");
+    if (n >= 2 && !x) return fail(BLISSGPU_ERR_INVALID, who, "x is NULL");
+    if (n >= 2 && !eu) return fail(BLISSGPU_ERR_INVALID, who, "edge_u is NULL");
+    if (n >= 2 && !ev) return fail(BLISSGPU_ERR_INVALID, who, "edge_v is NULL");
+    if (n >= 2 && !ew) return fail(BLISSGPU_ERR_INVALID, who, "edge_w is NULL");
+    return BLISSGPU_OK;
+}
+
+// the rounds on device pointers; the sorted edges arrive in `out` (host memory)
+static int mst_run(blissgpu_ctx* c, const char* who, const float* d_x, uint64_t n, uint32_t d, int metric, const float* d_M,
+                   const float* d_core, MstState& st) {
+    int diag = 0;
+    if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
+        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
+            diag = is_diag(c->m_cache.data(), d);
+        } else {
+            std::vector<float> hM((size_t)d * d);
+            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            diag = is_diag(hM.data(), d);
+        }
+    }
+    // (for the tests and the bench tool: no bit of the result depends on either)
+    uint32_t col_groups = 0, skip = 1;
+    if (const char* e = getenv("BLISSGPU_MST_COL_GROUPS")) col_groups = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 65535ul);
+    if (const char* e = getenv("BLISSGPU_MST_SKIP")) skip = e[0] != '0';
+    const bool trace = getenv("BLISSGPU_MST_TRACE") != nullptr;
+    const MstPlan plan = mst_plan(n, c->n_cus, col_groups, c->ws_limit);
+    if (!plan.fits) return fail(BLISSGPU_ERR_OOM, who, "the order, the picks and the column groups' winners do not fit the workspace limit");
+    int rc = c->ms_ws.ensure(plan.bytes);
+    if (rc) return rc;
+    uint32_t* w = reinterpret_cast<uint32_t*>(c->ms_ws.p);
+    const size_t o_order = 4, o_cpos = o_order + n, o_cw = o_cpos + n, o_pw = o_cw + n, o_pj = o_pw + (size_t)plan.Y * n,
+                 o_uv = (o_pj + (size_t)plan.Y * n + 1) & ~(size_t)1;
+    MstArgs a{};
+    a.X = d_x; a.M = d_M; a.core = d_core; a.order = w + o_order; a.cpos = w + o_cpos;
+    a.n = (uint32_t)n; a.d = d; a.metric = metric; a.Y = plan.Y; a.skip = skip;
+    a.part_w = w + o_pw; a.part_j = w + o_pj; a.comp_w = w + o_cw; a.comp_uv = reinterpret_cast<unsigned long long*>(w + o_uv);
+    a.flags = w;
+    int err = BLISSGPU_OK;  // what the pick below failed with
+    auto pick = [&](MstState& s, uint32_t* pw, uint64_t* puv) -> int {
+        auto hip = [&](hipError_t e, const char* what) {
+            if (e != hipSuccess && !err) err = fail(BLISSGPU_ERR_HIP, what, hipGetErrorString(e));
+            return e == hipSuccess;
+        };
+        const auto t_begin = std::chrono::steady_clock::now();
+        a.comps = s.comps;
+        if (!hip(hipMemsetAsync(w, 0, 4 * sizeof(uint32_t), c->stream), "hipMemsetAsync(mst flags)")) return -1;
+        if (!hip(hipMemcpyAsync(w + o_order, s.order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync(mst order)")) return -1;
+        if (!hip(hipMemcpyAsync(w + o_cpos, s.cpos.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync(mst components)")) return -1;
+        if (!hip(hipMemsetAsync(a.comp_w, 0xFF, (size_t)s.comps * sizeof(uint32_t), c->stream), "hipMemsetAsync(mst picks)")) return -1;
+        if (!hip(hipMemsetAsync(a.comp_uv, 0xFF, (size_t)s.comps * sizeof(uint64_t), c->stream), "hipMemsetAsync(mst picks)")) return -1;
+        double scan_ms = 0.0;
+        if (trace) (void)hipStreamSynchronize(c->stream);  // (tracing only: the scan between two synchronisations of its own)
+        const auto t_scan = std::chrono::steady_clock::now();
+        { Prof p(c, KX_MST_SCAN); launch_mst_scan(a, diag, plan, c->stream); }
+        if (trace) {
+            (void)hipStreamSynchronize(c->stream);
+            scan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_scan).count();
+        }
+        { Prof p(c, KX_MST_PICK); launch_mst_pick(a, 0u, plan, c->stream); }
+        { Prof p(c, KX_MST_PICK); launch_mst_pick(a, 1u, plan, c->stream); }
+        if (!hip(hipGetLastError(), "mst launch")) return -1;
+        uint32_t h_flags[2] = {0, 0};
+        if (!hip(hipMemcpyAsync(h_flags, w, sizeof(h_flags), hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(mst flags)")) return -1;
+        if (!hip(hipMemcpyAsync(pw, a.comp_w, (size_t)s.comps * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(mst picks)")) return -1;
+        if (!hip(hipMemcpyAsync(puv, a.comp_uv, (size_t)s.comps * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(mst picks)")) return -1;
+        if (!hip(hipStreamSynchronize(c->stream), "hipStreamSynchronize(mst)")) return -1;
+        if (trace) {
+            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+            fprintf(stderr, "blissgpu_mst round %u: %u components, scan %.3f ms, round %.3f ms (copies and picks included)\n", s.rounds + 1u,
+                    s.comps, scan_ms, ms);
+        }
+        if (h_flags[1]) { err = fail(BLISSGPU_ERR_INVALID, who, "core holds a NaN or a negative value"); return -1; }
+        if (h_flags[0]) { err = fail(BLISSGPU_ERR_INVALID, who, "NaN distance (a NaN feature, or an M that is not positive semi-definite)"); return -1; }
+        return 0;
+    };
+    const auto t0 = std::chrono::steady_clock::now();
+    const int m = mst_boruvka(st, (uint32_t)n, pick);
+    if (trace)
+        fprintf(stderr, "blissgpu_mst: %u rounds, %.3f ms in all (the rounds and the host's merges between them)\n", st.rounds,
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    if (m == -1) return err;
+    if (m == MST_TOO_MANY_ROUNDS) return fail(BLISSGPU_ERR_INTERNAL, who, "more than 64 rounds: the components stopped merging");
+    if (m != MST_OK || st.edges.size() != (size_t)n - 1) return fail(BLISSGPU_ERR_INTERNAL, who, "a component picked an edge that does not leave it");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_mst_device(blissgpu_ctx* c, const float* d_x, uint64_t n, uint32_t d, int metric, const float* d_M, const float* d_core,
+                        uint32_t* d_edge_u, uint32_t* d_edge_v, float* d_edge_w, uint32_t* rounds) {
+    const char* who = "blissgpu_mst_device";
+    int rc = mst_args_ok(who, d_x, n, d, metric, d_M, d_edge_u, d_edge_v, d_edge_w);
+    if (rc) return rc;
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    if (rounds) *rounds = 0;
+    if (n <= 1) return BLISSGPU_OK;  // no edge: no device is touched
+    CTX_ENTER(c, who);
+    MstState st;
+    rc = mst_run(c, who, d_x, n, d, metric, d_M, d_core, st);
+    if (rc) return rc;
+    const size_t m = st.edges.size();
+    std::vector<uint32_t> out(3 * m);
+    for (size_t e = 0; e < m; e++) { out[e] = st.edges[e].u; out[m + e] = st.edges[e].v; out[2 * m + e] = st.edges[e].w; }
+    HIP_TRY(hipMemcpyAsync(d_edge_u, out.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_edge_v, out.data() + m, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_edge_w, out.data() + 2 * m, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (rounds) *rounds = st.rounds;
+    return BLISSGPU_OK;
+}
+
+int blissgpu_mst(const float* x, uint64_t n, uint32_t d, int metric, const float* M, const float* core, uint32_t* edge_u,
+                 uint32_t* edge_v, float* edge_w, uint32_t* rounds) {
+    const char* who = "blissgpu_mst";
+    int rc = mst_args_ok(who, x, n, d, metric, M, edge_u, edge_v, edge_w);
+    if (rc) return rc;
+    if (rounds) *rounds = 0;
+    if (n <= 1) return BLISSGPU_OK;  // no edge: nothing for a device to do
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    const float* dM = nullptr;
+    rc = c->st_b.ensure(n * d + (core ? n : 0));
+    if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
+    if (rc) return rc;
+    float* d_core = core ? c->st_b.p + n * d : nullptr;
+    hipError_t e = hipMemcpyAsync(c->st_b.p, x, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && core) e = hipMemcpyAsync(d_core, core, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(mst)", hipGetErrorString(e));
+    MstState st;
+    if (!rc) rc = mst_run(c, who, c->st_b.p, n, d, metric, dM, d_core, st);
+    (void)hipStreamSynchronize(c->stream);
+    if (rc) return rc;
+    for (size_t k = 0; k < st.edges.size(); k++) {
+        edge_u[k] = st.edges[k].u;
+        edge_v[k] = st.edges[k].v;
+        memcpy(edge_w + k, &st.edges[k].w, sizeof(float));
+    }
+    if (rounds) *rounds = st.rounds;
+    return BLISSGPU_OK;
 }
 
 // ---- the moments of a library: counts, means, squared deviations and extrema per group of a labelling, and the pooled scatter

@@ -123,7 +123,7 @@ enum KernelId : int {
     K_CHAIN_STEP, K_CHAIN_WALK,             // song-to-song chains cut after k (kernels_chains.hip)
     // (tests/test_chains_host.py holds this list, and the list of names beside it, to end in the chain kernels: the kernels
     // that came later are numbered behind it, so that no older id or name moves)
-    K_COUNT = K_CHAIN_WALK + 24
+    K_COUNT = K_CHAIN_WALK + 26
 };
 // k-nearest albums per seed group (kernels_albums.hip; its partial lists are merged by knn_merge_kernel)
 constexpr int KX_SEGMENT_MEAN = K_CHAIN_WALK + 1, KX_ALBUM_KNN_SCAN = K_CHAIN_WALK + 2;
@@ -140,12 +140,14 @@ constexpr int KX_MOMENTS_PLAN = K_CHAIN_WALK + 13, KX_MOMENTS_SUM = K_CHAIN_WALK
               KX_MOMENTS_SCATTER = K_CHAIN_WALK + 16, KX_MOMENTS_REDUCE = K_CHAIN_WALK + 17, KX_MOMENTS_FINISH = K_CHAIN_WALK + 18;
 // group-to-group set distances (kernels_chamfer.hip): the minima per (song, group), their blocked sums, the rows' selection
 constexpr int KX_CHAMFER_SCAN = K_CHAIN_WALK + 19, KX_CHAMFER_REDUCE = K_CHAIN_WALK + 20, KX_CHAMFER_SELECT = K_CHAIN_WALK + 21;
+// the minimum spanning tree (kernels_mst.hip): every song's smallest edge out of its component, every component's smallest
+constexpr int KX_MST_SCAN = K_CHAIN_WALK + 22, KX_MST_PICK = K_CHAIN_WALK + 23;
 // (tests/test_journeys_host.py holds the profile table to END in the next two names: kernels that come later are numbered in
 // front of them; every consumer of the table goes by name)
 // the k lowest forest scores per seed group (kernels_forest.hip; its partial lists are merged by group_knn_merge_kernel)
-constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 22;
+constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 24;
 // a journey's step (kernels_chains.hip: the chains' scan with a waypoint query or a gate)
-constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 23;
+constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 25;
 static_assert(KX_JOURNEY_STEP + 1 == K_COUNT, "every kernel id is below the count");
 
 // lower_bound on a prefix array: largest s with prefix[s] <= x  (prefix has n+1 entries, prefix[0]=0)
@@ -459,6 +461,32 @@ ChamferPlan chamfer_plan(uint64_t n, uint32_t K, uint64_t q, bool want_matrix, i
 void launch_chamfer_scan(ChamferArgs a, int m_is_diag, const ChamferPlan& p, int n_cus, hipStream_t st);  // (sets a.Y for the slab)
 void launch_chamfer_reduce(const ChamferArgs& a, hipStream_t st);
 void launch_chamfer_select(const ChamferArgs& a, const ChamferPlan& p, hipStream_t st);
+// the minimum spanning tree, one round of Boruvka's algorithm (kernels_mst.hip; mst_merge.hpp is the host half).  order [n] = the
+// songs sorted by (component, index), cpos [n] = the component at every position, comps of them.  The scan writes every column
+// group's winner per position, part_w / part_j [Y][n] (weight bits, other song; 0xFFFFFFFF: none); the pick merges them into
+// [0][.] (phase 0, with the minimum weight per component into comp_w [comps]) and takes the smallest (lower song << 32 | higher
+// song) among a component's positions of that weight into comp_uv [comps] (phase 1).  comp_w / comp_uv start as all ones.
+// flags[0]: a NaN or negative sum among the evaluated pairs; flags[1]: a core that is NaN or negative
+struct MstArgs {
+    const float *X, *M, *core;  // core may be NULL
+    const uint32_t *order, *cpos;
+    uint32_t n, d, comps;
+    int metric;
+    uint32_t Y, skip, phase;  // skip: wavefronts of one component step over that component's tiles
+    uint32_t *part_w, *part_j, *comp_w;
+    unsigned long long* comp_uv;
+    uint32_t* flags;
+};
+struct MstPlan {
+    uint32_t waves, grid;  // wavefronts per workgroup of the scan (256 positions each), its workgroups per column group
+    uint32_t Y;            // column groups: col_groups when not 0, else enough to fill the device
+    uint32_t pick_grid;
+    uint64_t bytes;        // the whole workspace
+    bool fits;             // bytes <= ws_limit
+};
+MstPlan mst_plan(uint64_t n, int n_cus, uint32_t col_groups, uint64_t ws_limit);
+void launch_mst_scan(const MstArgs& a, int m_is_diag, const MstPlan& p, hipStream_t st);
+void launch_mst_pick(MstArgs a, uint32_t phase, const MstPlan& p, hipStream_t st);
 // triplet metric learning, one gradient evaluation (kernels_metric.hip).  The triplets are dealt out in W contiguous chunks, a
 // function of T alone; part [W][pairs + 1] f64 and cnt [W][2] u64 are the wavefronts' partials, out = G f64 [d][d] | loss f64 |
 // n_active u64 | error bits u64 (TRIPLET_ERR_*).  mode says how M is read; flags (u8 [T]) may be NULL

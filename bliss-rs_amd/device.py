@@ -629,6 +629,48 @@ class Context:
         out = (idx, dist, sizes, matrix)
         return tuple(None if a is None else a.cpu().numpy() for a in out) if as_numpy else out
 
+    def mst(self, X, metric: str = "euclidean", M=None, core=None):
+        """The minimum spanning tree of the rows of X on the device without the distance matrix (blissgpu_mst_device,
+        DESIGN.md 3.26): the unique tree under the edge order (bits of the f32 weight, lower row, higher row) of
+        include/blissgpu.h, with weight = the all-pairs distance, or max(distance, core[i], core[j]) when `core` (float32 [n],
+        every value >= 0) is given.  X float32 [n, d], M and core are tensors on the device, or numpy arrays (uploaded, results
+        returned as arrays).  -> (u int32 [n - 1], v int32 [n - 1], w float32 [n - 1], rounds): the edges in ascending order,
+        u < v, and the number of Boruvka rounds run.  metric: "euclidean" or "mahalanobis" with M.  Raises BlissGpuError:
+        ERR_INVALID for cosine, a NaN distance or a bad core, ERR_OOM when the workspace does not fit the context's limit;
+        synchronises once per round."""
+        from .playlist import _METRICS
+
+        torch = self.torch
+        as_numpy = not torch.is_tensor(X)
+        dev = torch.device("cuda", self.device)
+        up = lambda a: None if a is None else (  # noqa: E731
+            a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev))
+        X, M, core = up(X), up(M), up(core)
+        assert X.is_cuda and X.dtype == torch.float32 and X.dim() == 2
+        X = X.contiguous()
+        n, d = X.shape
+        if M is not None:
+            assert M.is_cuda and M.dtype == torch.float32
+            M = M.contiguous()
+        if core is not None:
+            assert core.is_cuda and core.dtype == torch.float32
+            core = core.contiguous().reshape(-1)
+            if core.shape[0] != n:
+                raise ValueError("a core distance per row of X is needed")
+        ptr = lambda a: None if a is None else C.c_void_p(a.data_ptr())  # noqa: E731
+        m = max(n - 1, 0)
+        u = torch.empty((m,), dtype=torch.int32, device=X.device)
+        v = torch.empty((m,), dtype=torch.int32, device=X.device)
+        w = torch.empty((m,), dtype=torch.float32, device=X.device)
+        rounds = C.c_uint32(0)
+        self._pre()
+        _ffi.check(self._L.blissgpu_mst_device(self._h, ptr(X), n, d, _METRICS[metric], ptr(M), ptr(core), ptr(u), ptr(v), ptr(w),
+                                               C.byref(rounds)))
+        self._post()
+        if as_numpy:
+            u, v, w = (t.cpu().numpy() for t in (u, v, w))
+        return u, v, w, int(rounds.value)
+
     def moments(self, X, labels=None, k: int = None, scatter: bool = True):
         """The first and second moments of the rows of X on the device (blissgpu_moments_device), per group of
         the labelling `labels` and pooled, every sum the blocked sum of include/blissgpu.h.  X float32 [n, d] and labels (int32 /

@@ -39,6 +39,9 @@ database:
     similar_groups, similar_artists,      which artists (albums, genres) are like each other under the average nearest-member
     similar_artists_playlist              distance (playlist.group_neighbours), one device call for every key; and the
                                           "similar artists to the current one" playlist of the reference's TODO.md
+    song_tree, linked_clusters, tour      the library's minimum spanning tree (playlist.minimum_spanning_tree, one device
+                                          call): clusters without a number of clusters and of any shape, and every song
+                                          (or one genre's) in an order in which each sounds like one before it
 
 SQLite stores `real` as f64; an f32 feature widens exactly on the way in and narrows exactly on the way out, so a
 round trip is bit-exact.  The schema, load and store helpers are host code; the playlists run their distances on the
@@ -950,3 +953,69 @@ def similar_artists_playlist(db: Conn, artist: str, number_artists: int, metric_
     if res is not None:
         order.extend(keys[int(c)] for c in res.idx[keys.index(artist)] if c >= 0)
     return [s for key in order for s in sorted((songs[i] for i in members[key]), key=_album_disc_track)]
+
+
+def _tree_songs(db: Conn, where):
+    """-> (songs, X) of the analysed songs, or of those whose column where[0] has the value where[1]"""
+    if where is not None:
+        column, value = where
+        if column not in _LABEL_COLUMNS:
+            raise ValueError(f"where must name one of {_LABEL_COLUMNS}")
+    songs, X = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
+    if where is not None and songs:
+        keep = np.asarray([i for i, s in enumerate(songs) if getattr(s, column) == value], np.int64)
+        songs, X = [songs[int(i)] for i in keep], np.ascontiguousarray(X[keep])
+    return songs, X
+
+
+def _song_tree(db: Conn, metric_builder, min_samples, where):
+    """-> (songs, playlist.SpanningTree over them)"""
+    playlist._mst_metric(metric_builder)  # refused before the database is read
+    songs, X = _tree_songs(db, where)
+    if not songs:
+        return songs, playlist.SpanningTree(np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float32), 0, 0)
+    return songs, playlist.minimum_spanning_tree(X, metric_builder, min_samples)
+
+
+def song_tree(db: Conn, metric_builder=playlist.euclidean_distance, min_samples: int = None, where=None):
+    """The minimum spanning tree of the library (playlist.minimum_spanning_tree) over the analysed songs of
+    FeaturesVersion.LATEST, read once, in ONE call of the tree (the core distances of min_samples come from the k-nearest
+    search first).  -> (paths, playlist.SpanningTree): edge e joins the songs at paths[tree.u[e]] and paths[tree.v[e]], in id
+    order.  where = (column, value), such as ("genre", "Jazz"): only the songs whose column has that value."""
+    songs, tree = _song_tree(db, metric_builder, min_samples, where)
+    return [s.path for s in songs], tree
+
+
+def linked_clusters(db: Conn, k: int = None, height: float = None, min_cluster_size: int = 1,
+                    metric_builder=playlist.euclidean_distance, min_samples: int = None, where=None):
+    """Which songs belong together, without a number of clusters and whatever the clusters' shape: the single-linkage clusters
+    of the library's spanning tree (song_tree, SpanningTree.cut) at `height`, or the k of them the last k - 1 edges separate.
+    -> (lists, unclustered): a list of `Song` per cluster, clusters in order of their first song and songs in id order (the
+    shape cluster_songs returns), and the songs of the clusters smaller than min_cluster_size."""
+    songs, tree = _song_tree(db, metric_builder, min_samples, where)
+    if not songs:
+        return [], []
+    labels = tree.cut(k, height, min_cluster_size)
+    lists, loose = [[] for _ in range(int(labels.max()) + 1)], []
+    for s, c in zip(songs, labels):
+        (lists[int(c)] if c >= 0 else loose).append(s)
+    return lists, loose
+
+
+def tour(db: Conn, start_path: str = None, where=None, metric_builder=playlist.euclidean_distance, min_samples: int = None) -> List[Song]:
+    """Play the whole library (or, with where = ("genre", "Jazz"), one genre) so that each song sounds like one before it: the
+    songs in the order of SpanningTree.tour from the song at start_path (None: the first song).  Unlike a greedy
+    song-to-song chain the walk never runs out of near songs and jumps.  An unknown start_path -- or one that `where` leaves
+    out -- is a ProviderError, raised before the device is touched."""
+    playlist._mst_metric(metric_builder)  # refused before the database is read
+    songs, X = _tree_songs(db, where)
+    start = 0
+    if start_path is not None:
+        paths = [s.path for s in songs]
+        if start_path not in paths:
+            raise ProviderError("target song was not found in the database.")
+        start = paths.index(start_path)
+    if not songs:
+        return []
+    tree = playlist.minimum_spanning_tree(X, metric_builder, min_samples)
+    return [songs[int(i)] for i in tree.tour(start)]

@@ -772,6 +772,151 @@ def group_neighbours(songs_or_X, labels, t, metric_builder=euclidean_distance, k
     return GroupNeighbours(out, dist, sizes.astype(np.int64), mat)
 
 
+def _mst_metric(metric_builder):
+    """the metrics the spanning tree can run: euclidean, or Mahalanobis with the caller's matrix"""
+    _no_forest(metric_builder, "the spanning tree compares single songs; a forest scores songs against a seed set")
+    _no_variance(metric_builder, "the spanning tree has no seed set to take variances from; pass MahalanobisBuilder(m)")
+    metric, m = _metric_of(metric_builder)
+    if metric == "cosine":
+        raise ValueError("the spanning tree needs a distance whose bits order as integers: euclidean or mahalanobis, not cosine")
+    return metric, m
+
+
+def _uf_find(parent, x):
+    r = x
+    while parent[r] != r:
+        r = parent[r]
+    while parent[x] != r:
+        parent[x], x = r, parent[x]
+    return r
+
+
+@dataclasses.dataclass
+class SpanningTree:
+    """The result of minimum_spanning_tree: the n - 1 edges of the library's minimum spanning tree in ascending order of
+    (bits of w, u, v) -- u int64[n - 1] (the lower song), v int64[n - 1] (the higher), w float32[n - 1] -- and `rounds`, the
+    Boruvka rounds the device ran.  n is the number of songs.  linkage / cut / tour are host work on those arrays."""
+
+    u: np.ndarray
+    v: np.ndarray
+    w: np.ndarray
+    rounds: int
+    n: int
+
+    def linkage(self) -> np.ndarray:
+        """The single-linkage dendrogram as scipy lays it out: float64 [n - 1, 4], row e = (cluster a, cluster b, height, size)
+        with a < b; the merges are the edges in their order, the cluster made by row e is numbered n + e."""
+        m = len(self.u)
+        Z = np.zeros((m, 4), np.float64)
+        parent, ident, size = list(range(self.n)), list(range(self.n)), [1] * self.n
+        for e in range(m):
+            ra, rb = _uf_find(parent, int(self.u[e])), _uf_find(parent, int(self.v[e]))
+            a, b = sorted((ident[ra], ident[rb]))
+            parent[rb] = ra
+            size[ra] += size[rb]
+            ident[ra] = self.n + e
+            Z[e] = (a, b, float(self.w[e]), size[ra])
+        return Z
+
+    def cut(self, k: int = None, height: float = None, min_cluster_size: int = 1) -> np.ndarray:
+        """Single-linkage clusters: int64 labels [n].  k: remove the k - 1 last edges of the order (k clusters); height: remove
+        every edge with w > height (an edge of exactly that weight stays); neither: one cluster.  The clusters are numbered
+        0, 1, ... by their lowest member; clusters of fewer than min_cluster_size songs get -1 (which silhouette,
+        group_neighbours and moments leave out) and the others keep the order of their lowest members."""
+        if k is not None and height is not None:
+            raise ValueError("cut takes k or height, not both")
+        m = len(self.u)
+        keep = m
+        if k is not None:
+            k = int(k)
+            if not 1 <= k <= max(self.n, 1):
+                raise ValueError("k must be 1 .. n")
+            keep = max(self.n - k, 0)
+        elif height is not None:
+            keep = int(np.count_nonzero(~(self.w > np.float32(height))))  # (ascending weights: a prefix of the order)
+        parent = list(range(self.n))
+        for e in range(keep):
+            ra, rb = _uf_find(parent, int(self.u[e])), _uf_find(parent, int(self.v[e]))
+            parent[max(ra, rb)] = min(ra, rb)  # the root is the lowest member
+        roots = np.fromiter((_uf_find(parent, i) for i in range(self.n)), np.int64, self.n)
+        sizes = np.bincount(roots, minlength=self.n)
+        big = sizes[roots] >= int(min_cluster_size)
+        label_of = np.full(max(self.n, 1), -1, np.int64)
+        live = np.unique(roots[big])  # ascending roots = ascending lowest members
+        label_of[live] = np.arange(live.size)
+        return label_of[roots]
+
+    def tour(self, start: int = 0) -> np.ndarray:
+        """Every song once, int64 [n]: the depth-first preorder of the tree from `start`, a song's neighbours taken in ascending
+        edge order.  Each song is a neighbour in the tree of one heard before it, and the whole walk is at most twice the
+        tree's length: no jumps across the library once the near songs run out."""
+        if self.n == 0:
+            return np.zeros(0, np.int64)
+        start = int(start)
+        if not 0 <= start < self.n:
+            raise ValueError("start must be a song of the tree")
+        deg = np.bincount(np.concatenate([self.u, self.v]).astype(np.int64), minlength=self.n)
+        off = np.concatenate([[0], np.cumsum(deg)]).tolist()
+        fill, adj = off[:-1], [0] * (2 * len(self.u))
+        for a, b in zip(self.u.tolist(), self.v.tolist()):  # edge order: every list ascends in edge key
+            adj[fill[a]] = b
+            fill[a] += 1
+            adj[fill[b]] = a
+            fill[b] += 1
+        out, seen, stack = [], [False] * self.n, [start]
+        while stack:  # (iterative: a chain of a million songs is a valid tree)
+            i = stack.pop()
+            if seen[i]:
+                continue
+            seen[i] = True
+            out.append(i)
+            stack.extend(j for j in reversed(adj[off[i]:off[i + 1]]) if not seen[j])
+        return np.asarray(out, np.int64)
+
+
+def core_distances(songs_or_X, min_samples, metric_builder=euclidean_distance) -> np.ndarray:
+    """Every song's distance to its min_samples-th nearest OTHER song (float32 [n]; with fewer other songs, to the farthest of
+    them; 0 for a lone song): the "core distance" of HDBSCAN, from the k-nearest search on the device (nearest_order).  Small
+    in dense regions, large for outliers."""
+    metric, m = _mst_metric(metric_builder)
+    X = _rows_of_input(songs_or_X)
+    n = X.shape[0]
+    k = int(min_samples)
+    if k < 1:
+        raise ValueError("min_samples must be at least 1")
+    k = min(k, n - 1)
+    if k < 1:
+        return np.zeros(n, np.float32)
+    _, dist = nearest_order(X, X, k, metric, m, skip=np.arange(n))
+    return np.ascontiguousarray(dist[:, k - 1], dtype=np.float32)
+
+
+def minimum_spanning_tree(songs_or_X, metric_builder=euclidean_distance, min_samples=None) -> SpanningTree:
+    """The minimum spanning tree of the songs (or rows of an array) under a metric, exact and without the distance matrix
+    (blissgpu_mst): Boruvka's rounds on the device, at most ceil(log2 n) all-pairs scans.  The tree is the
+    unique one under the edge order (bits of the weight, lower song, higher song), so ties -- duplicate songs -- change nothing.
+    -> SpanningTree; its cut() gives clusters without a number of clusters and of any shape (single linkage), its linkage() the
+    whole dendrogram, its tour() every song in an order without jumps.  min_samples = m: the weights become the mutual
+    reachability max(distance, core[i], core[j]) with core = core_distances(songs, m): sparse songs are pushed away from
+    everything, which keeps single linkage from chaining through noise (the tree HDBSCAN starts from).  metric_builder:
+    euclidean_distance or a MahalanobisBuilder (its M); a ForestOptions, a VarianceWeights, cosine and arbitrary callables are
+    refused.  A NaN distance raises BlissGpuError(ERR_INVALID)."""
+    metric, m = _mst_metric(metric_builder)
+    X = _rows_of_input(songs_or_X)
+    n, d = X.shape
+    core = None if min_samples is None else core_distances(X, min_samples, metric_builder)
+    mp = None
+    if m is not None:
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        mp = m.ctypes.data
+    e = max(n - 1, 0)
+    u, v, w = np.zeros(e, np.uint32), np.zeros(e, np.uint32), np.zeros(e, np.float32)
+    rounds = C.c_uint32(0)
+    _ffi.check(_ffi.lib().blissgpu_mst(X.ctypes.data, n, d, _METRICS[metric], mp, None if core is None else core.ctypes.data,
+                                       u.ctypes.data, v.ctypes.data, w.ctypes.data, C.byref(rounds)))
+    return SpanningTree(u.astype(np.int64), v.astype(np.int64), w, int(rounds.value), n)
+
+
 class KSelection:
     """The result of choose_k: ks (as given), scores (the silhouette score of each k's clustering), best_k (the k with the
     highest score; equal scores go to the lower k) and clustering (that k's Clustering)."""

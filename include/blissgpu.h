@@ -43,6 +43,7 @@ extern "C" {
 #define BLISSGPU_ERR_RCCL 6           /* librccl could not be loaded or a collective failed (blissgpu_node_* only) */
 #define BLISSGPU_ERR_TIMEOUT 7        /* a single-song call was not picked up by any default context within its deadline
                                          (blissgpu_set_single_song_timeout_ms); blissgpu_last_error() names the seats */
+#define BLISSGPU_ERR_INTERNAL 8       /* a bounded loop did not end where it must (blissgpu_mst: more than 64 rounds): a defect */
 
 /* ---- per-song status, maps 1:1 onto BlissError (src/lib.rs:236-252) ---- */
 #define BLISSGPU_SONG_OK 0
@@ -535,6 +536,42 @@ int blissgpu_group_neighbours_device(blissgpu_ctx *ctx, const float *d_x, uint64
                                      uint32_t k, int metric, const float *d_M, const uint32_t *d_queries, uint64_t q, uint32_t t,
                                      int mode, uint32_t slab_groups, uint32_t *d_idx, double *d_dist, uint32_t *d_sizes,
                                      double *d_matrix);
+
+/* ---- The minimum spanning tree of a library (the reference's TODO.md complains of playlists that "drift": a
+ * walk of this tree is a tour in which every song sounds like one heard before it) ----
+ * One object answers "which songs belong together, without a number of clusters", "what are the sub-genres of this genre" and
+ * "play everything so that each song follows from the last": cutting the tree's heaviest edges gives the single-linkage clusters
+ * at every level, its sorted edges are the dendrogram, a depth-first walk is a tour at most twice the tree's length, and with
+ * per-song core distances it is the tree HDBSCAN starts from.  Exact, all pairs, O(n) memory, every bit defined.
+ * Inputs: x [n][d] f32, d <= 64; metric: BLISSGPU_METRIC_EUCLIDEAN, or BLISSGPU_METRIC_MAHALANOBIS with the caller's M (a
+ * diagonal M is detected as everywhere else); core [n] f32 or NULL.
+ *   dist(i, j) = bit for bit what blissgpu_pairwise_device(x, x) writes at [i][j] (the same bits at [j][i]);
+ *   w(i, j)    = max(dist(i, j), core[i], core[j]) with core given (every core >= 0; -0.0 counts as +0.0), dist(i, j) without.
+ *                With core[i] = the distance from i to its m-th nearest other song this is HDBSCAN's mutual reachability;
+ *   key{i, j}  = for i < j the triple (the bits of w(i, j) as a uint32_t, i, j), compared lexicographically.  Weights are >= +0
+ *                or +inf, so the integer order is the float order.  The order is strict and total: whatever the ties --
+ *                duplicate songs, the plateaus core produces -- there is exactly one minimum spanning tree under it.
+ * Outputs: the n - 1 edges of that tree in ascending key: edge_u [n - 1] u32 (the lower song), edge_v [n - 1] u32 (the higher),
+ * edge_w [n - 1] f32.  rounds (host memory in both forms, may be NULL) receives the number of Boruvka rounds run: at most
+ * ceil(log2 n).  n <= 1: no edge, BLISSGPU_OK, *rounds = 0, and no device is touched.
+ * A NaN among the distances -- a NaN feature, a negative sum under an M that is not positive semi-definite -- or a core that
+ * is NaN or negative returns BLISSGPU_ERR_INVALID with a message that says so (the first round evaluates every pair); nothing
+ * is written to the outputs then.  BLISSGPU_ERR_INVALID too, each with a message that names the argument:
+ * BLISSGPU_METRIC_COSINE; an unknown metric; Mahalanobis without M; d outside 1 .. 64; n >= 2^32 - 1; with n >= 2 a NULL x,
+ * edge_u, edge_v or edge_w.  The loop over rounds is bounded: after 64 of them the call returns BLISSGPU_ERR_INTERNAL.
+ * No n x n matrix is ever stored.  Workspace, grow-only in the context: 4 n bytes each of order, components and picked weights,
+ * 8 n of picked edges, and 8 n per column group of the scan (a number the device's size bounds, about 8 192 CUs / n): O(n).
+ * When that exceeds the context's workspace limit (blissgpu_ctx_get_workspace_limit) the call returns BLISSGPU_ERR_OOM before
+ * anything is launched.  Per round the host receives one pick per component and sends the next order: 8 n bytes.
+ * For the tests and the bench tool, read from the environment at every call, and without effect on any bit of the result:
+ * BLISSGPU_MST_COL_GROUPS = the scan's column groups (default: the plan's), BLISSGPU_MST_SKIP = 0 turns off the late rounds'
+ * skip of pairs inside one component, BLISSGPU_MST_TRACE prints every round's components and times to stderr. */
+int blissgpu_mst(const float *x, uint64_t n, uint32_t d, int metric, const float *M, const float *core, uint32_t *edge_u,
+                 uint32_t *edge_v, float *edge_w, uint32_t *rounds);
+/* Device-resident form (device pointers, except rounds).  It checks the scalar arguments before it looks at its context, and
+ * synchronises the context's stream once per round and once more before returning. */
+int blissgpu_mst_device(blissgpu_ctx *ctx, const float *d_x, uint64_t n, uint32_t d, int metric, const float *d_M,
+                        const float *d_core, uint32_t *d_edge_u, uint32_t *d_edge_v, float *d_edge_w, uint32_t *rounds);
 
 /* ---- Learning the Mahalanobis matrix from training triplets ----
  * The reference has a `training_triplet` table ("song_1 and song_2 are closer together than they are to odd_one_out",
