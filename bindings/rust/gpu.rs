@@ -157,6 +157,16 @@ pub mod sys {
         pub fn blissgpu_knn_device(ctx: *mut blissgpu_ctx, d_queries: *const f32, q: u64, d_cand: *const f32, n: u64, d: u32,
                                    metric: c_int, d_m: *const f32, d_skip: *const u32, k: u32, d_idx: *mut u32,
                                    d_dist: *mut f32) -> c_int;
+        // the same selection under dist / sqrt(qscale[i] * cscale[j]) (local scaling against hubs), and the k-occurrence counts
+        pub fn blissgpu_scaled_knn(queries: *const f32, q: u64, qscale: *const f32, cand: *const f32, n: u64, cscale: *const f32,
+                                   d: u32, metric: c_int, m_matrix: *const f32, skip: *const u32, k: u32, idx: *mut u32,
+                                   dist: *mut f32) -> c_int;
+        pub fn blissgpu_scaled_knn_device(ctx: *mut blissgpu_ctx, d_queries: *const f32, q: u64, d_qscale: *const f32,
+                                          d_cand: *const f32, n: u64, d_cscale: *const f32, d: u32, metric: c_int, d_m: *const f32,
+                                          d_skip: *const u32, k: u32, d_idx: *mut u32, d_dist: *mut f32) -> c_int;
+        pub fn blissgpu_knn_occurrence(idx: *const u32, q: u64, k: u32, n: u64, count: *mut u32) -> c_int;
+        pub fn blissgpu_knn_occurrence_device(ctx: *mut blissgpu_ctx, d_idx: *const u32, q: u64, k: u32, n: u64,
+                                              d_count: *mut u32) -> c_int;
         pub fn blissgpu_group_knn(seeds: *const f32, group_offsets: *const u64, n_groups: u64, cand: *const f32, n: u64, d: u32,
                                   metric: c_int, m_matrix: *const f32, skip: *const u32, k: u32, idx: *mut u32, dist: *mut f32) -> c_int;
         pub fn blissgpu_group_knn_device(ctx: *mut blissgpu_ctx, d_seeds: *const f32, group_offsets: *const u64, n_groups: u64,

@@ -112,6 +112,12 @@ SIGNATURES = {
     "blissgpu_knn": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, C.c_uint32, _vp, _vp]),
     "blissgpu_knn_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, C.c_uint32, _vp,
                                       _vp]),
+    "blissgpu_scaled_knn": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, C.c_uint32, C.c_int, _vp, _vp, C.c_uint32, _vp,
+                                      _vp]),
+    "blissgpu_scaled_knn_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, C.c_uint32, C.c_int, _vp, _vp,
+                                             C.c_uint32, _vp, _vp]),
+    "blissgpu_knn_occurrence": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, _vp]),
+    "blissgpu_knn_occurrence_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint64, _vp]),
     "blissgpu_kmeans": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_int, _vp, C.c_uint32, _vp, _vp, _vp, _vp,
                                   _u32p, _i32p]),
     "blissgpu_kmeans_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_int, _vp, C.c_uint32, _vp, _vp,

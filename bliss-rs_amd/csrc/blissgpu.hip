@@ -41,6 +41,7 @@ const char kMomentsFinishName[] = "moments_finish_kernel";
 const char kChamferScanName[] = "chamfer_scan_kernel", kChamferReduceName[] = "chamfer_reduce_kernel";  // KX_CHAMFER_*
 const char kChamferSelectName[] = "chamfer_select_kernel";
 const char kMstScanName[] = "mst_scan_kernel", kMstPickName[] = "mst_pick_kernel";  // KX_MST_*
+const char kScaledKnnScanName[] = "scaled_knn_scan_kernel", kKnnOccurrenceName[] = "knn_occurrence_kernel";  // KX_SCALED_KNN_SCAN, KX_KNN_OCCURRENCE
 const char* const kKernelNames[K_COUNT] = {
     "fft512_kernel",     "onset_kernel",      "beat_kernel",   "stft8192_kernel", "tune_select_kernel",
     "tune_pass2_kernel", "tune_final_kernel", "chroma_kernel",     "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel", "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel",
@@ -56,6 +57,7 @@ const char* const kKernelNames[K_COUNT] = {
     kMomentsPlanName, kMomentsSumName, kMomentsM2Name, kMomentsScatterName, kMomentsReduceName, kMomentsFinishName,
     kChamferScanName, kChamferReduceName, kChamferSelectName,
     kMstScanName, kMstPickName,
+    kScaledKnnScanName, kKnnOccurrenceName,
     kGroupForestScanName, kJourneyStepName};
 }  // namespace
 
@@ -966,6 +968,179 @@ int blissgpu_knn(const float* queries, uint64_t q, const float* cand, uint64_t n
         if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(knn)", hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+// ---- locally scaled k nearest candidates per query: blissgpu_knn's selection under dist / sqrtf(qscale[i] * cscale[j]), the cure
+// for hubs (kernels_scaled_knn.hip); knn_plan's split, knn_merge_kernel's merge, no q x n matrix ----
+static int scaled_knn_args_ok(const char* who, const void* queries, uint64_t q, const void* qscale, const void* cand, uint64_t n,
+                              const void* cscale, uint32_t d, int metric, const float* M, uint32_t k, const void* idx) {
+    int rc = knn_args_ok(who, queries, q, cand, n, d, metric, M, k, idx);
+    if (rc) return rc;
+    if (q && !qscale) return fail(BLISSGPU_ERR_INVALID, who, "qscale is NULL");
+    if (q && n && !cscale) return fail(BLISSGPU_ERR_INVALID, who, "cscale is NULL");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_scaled_knn_device(blissgpu_ctx* c, const float* d_queries, uint64_t q, const float* d_qscale, const float* d_cand,
+                               uint64_t n, const float* d_cscale, uint32_t d, int metric, const float* d_M, const uint32_t* d_skip,
+                               uint32_t k, uint32_t* d_idx, float* d_dist) {
+    const char* who = "blissgpu_scaled_knn_device";
+    int rc = scaled_knn_args_ok(who, d_queries, q, d_qscale, d_cand, n, d_cscale, d, metric, d_M, k, d_idx);
+    if (rc) return rc;
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    if (q == 0) return BLISSGPU_OK;
+    CTX_ENTER(c, who);
+    int diag = 0;
+    if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
+        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
+            diag = is_diag(c->m_cache.data(), d);
+        } else {
+            std::vector<float> hM((size_t)d * d);
+            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            diag = is_diag(hM.data(), d);
+        }
+    }
+    // workspace: the sorted k best keys of every (query, split) -- O(q k), as for blissgpu_knn_device
+    const KnnPlan plan = knn_plan(q, n, k, c->n_cus);
+    rc = c->pl_sync.ensure(4);
+    if (!rc) rc = c->pl_tmp.ensure((size_t)plan.part_keys * sizeof(unsigned long long));
+    if (rc) return rc;
+    unsigned long long* part = reinterpret_cast<unsigned long long*>(c->pl_tmp.p);
+    // pl_sync: [1] NaN among the evaluated distances, [2] a scale outside [2^-60, 2^60], [3] a skip entry >= n
+    HIP_TRY(hipMemsetAsync(c->pl_sync.p, 0, 4 * sizeof(uint32_t), c->stream));
+    {
+        Prof p(c, KX_SCALED_KNN_SCAN);
+        launch_scaled_knn_scan(d_queries, q, d_qscale, d_cand, (uint32_t)n, d_cscale, d, metric, d_M, diag, d_skip, k, plan, part,
+                               c->pl_sync.p + 1, c->pl_sync.p + 3, c->pl_sync.p + 2, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    {
+        Prof p(c, K_KNN_MERGE);
+        launch_knn_merge(part, q, k, plan, d_idx, d_dist, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    uint32_t flags[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(flags, c->pl_sync.p, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (flags[3]) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
+    if (flags[2]) return fail(BLISSGPU_ERR_INVALID, who, "scales must lie in [2^-60, 2^60]");
+    if (flags[1]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance (the reference panics here)");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_scaled_knn(const float* queries, uint64_t q, const float* qscale, const float* cand, uint64_t n, const float* cscale,
+                        uint32_t d, int metric, const float* M, const uint32_t* skip, uint32_t k, uint32_t* idx, float* dist) {
+    const char* who = "blissgpu_scaled_knn";
+    int rc = scaled_knn_args_ok(who, queries, q, qscale, cand, n, cscale, d, metric, M, k, idx);
+    if (rc) return rc;
+    if (skip)
+        for (uint64_t i = 0; i < q; i++)
+            if (skip[i] != 0xFFFFFFFFu && skip[i] >= n) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
+    if (q == 0) return BLISSGPU_OK;
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    // queries that ARE the candidate matrix, with the same scales, travel once: st_b = cand | cscale, st_a = queries | qscale
+    const bool shared = queries == cand && qscale == cscale && q <= n;
+    const size_t out_n = (size_t)q * k;
+    const float* dM = nullptr;
+    rc = c->st_b.ensure(std::max<size_t>(1, n * d + n));
+    if (!rc && !shared) rc = c->st_a.ensure(q * d + q);
+    if (!rc) rc = c->st_idx.ensure(out_n + (skip ? q : 0));
+    if (!rc && dist) rc = c->st_dist.ensure(out_n);
+    if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
+    if (rc) return rc;
+    const float* dQ = shared ? c->st_b.p : c->st_a.p;
+    float* d_cs = c->st_b.p + n * d;
+    const float* d_qs = shared ? d_cs : c->st_a.p + q * d;
+    uint32_t *d_idx = c->st_idx.p, *d_skip = skip ? c->st_idx.p + out_n : nullptr;
+    hipError_t e = hipSuccess;
+    if (n) e = hipMemcpyAsync(c->st_b.p, cand, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && n) e = hipMemcpyAsync(d_cs, cscale, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && !shared) e = hipMemcpyAsync(c->st_a.p, queries, q * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && !shared) e = hipMemcpyAsync(c->st_a.p + q * d, qscale, q * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && skip) e = hipMemcpyAsync(d_skip, skip, q * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(scaled_knn)", hipGetErrorString(e));
+    if (!rc)
+        rc = blissgpu_scaled_knn_device(c, dQ, q, d_qs, c->st_b.p, n, d_cs, d, metric, dM, d_skip, k, d_idx,
+                                        dist ? c->st_dist.p : nullptr);
+    if (!rc) {
+        e = hipMemcpyAsync(idx, d_idx, out_n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(scaled_knn)", hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+// ---- k-occurrence: how many lists of an index matrix every song is in (the counts hubness is measured on) ----
+static int occurrence_args_ok(const char* who, const void* idx, uint64_t q, uint32_t k, uint64_t n, const void* count) {
+    if (k == 0) return fail(BLISSGPU_ERR_INVALID, who, "k must be at least 1");
+    if (n >= 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "n must be below 2^32 - 1 songs");
+    if (q > (1ull << 40) / k) return fail(BLISSGPU_ERR_INVALID, who, "q * k must be at most 2^40 entries");
+    if (q && !idx) return fail(BLISSGPU_ERR_INVALID, who, "idx is NULL");
+    if (n && !count) return fail(BLISSGPU_ERR_INVALID, who, "count is NULL");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_knn_occurrence_device(blissgpu_ctx* c, const uint32_t* d_idx, uint64_t q, uint32_t k, uint64_t n, uint32_t* d_count) {
+    const char* who = "blissgpu_knn_occurrence_device";
+    int rc = occurrence_args_ok(who, d_idx, q, k, n, d_count);
+    if (rc) return rc;
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    if (q == 0 && n == 0) return BLISSGPU_OK;
+    CTX_ENTER(c, who);
+    if (n) HIP_TRY(hipMemsetAsync(d_count, 0, n * sizeof(uint32_t), c->stream));
+    uint32_t flag = 0;
+    if (q) {
+        rc = c->pl_sync.ensure(4);
+        if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(c->pl_sync.p, 0, 4 * sizeof(uint32_t), c->stream));
+        // (for the bench tool's A/B: the windowed LDS histogram counts the same)
+        const char* e = getenv("BLISSGPU_OCCURRENCE_LDS");
+        {
+            Prof p(c, KX_KNN_OCCURRENCE);
+            launch_knn_occurrence(d_idx, q * k, (uint32_t)n, d_count, c->pl_sync.p + 3, e && e[0] == '1', c->n_cus, c->stream);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&flag, c->pl_sync.p + 3, sizeof(flag), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (flag) return fail(BLISSGPU_ERR_INVALID, who, "idx entries must be < n or 0xFFFFFFFF");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_knn_occurrence(const uint32_t* idx, uint64_t q, uint32_t k, uint64_t n, uint32_t* count) {
+    const char* who = "blissgpu_knn_occurrence";
+    int rc = occurrence_args_ok(who, idx, q, k, n, count);
+    if (rc) return rc;
+    const uint64_t entries = q * k;
+    for (uint64_t e = 0; e < entries; e++)
+        if (idx[e] != 0xFFFFFFFFu && idx[e] >= n) return fail(BLISSGPU_ERR_INVALID, who, "idx entries must be < n or 0xFFFFFFFF");
+    if (n == 0) return BLISSGPU_OK;
+    if (q == 0) {  // nothing to count: no device is touched
+        memset(count, 0, n * sizeof(uint32_t));
+        return BLISSGPU_OK;
+    }
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    rc = c->st_idx.ensure(entries + n);
+    if (rc) return rc;
+    hipError_t e = hipMemcpyAsync(c->st_idx.p, idx, entries * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(knn_occurrence)", hipGetErrorString(e));
+    if (!rc) rc = blissgpu_knn_occurrence_device(c, c->st_idx.p, q, k, n, c->st_idx.p + entries);
+    if (!rc) {
+        e = hipMemcpyAsync(count, c->st_idx.p + entries, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(knn_occurrence)", hipGetErrorString(e));
     }
     (void)hipStreamSynchronize(c->stream);
     return rc;

@@ -123,7 +123,7 @@ enum KernelId : int {
     K_CHAIN_STEP, K_CHAIN_WALK,             // song-to-song chains cut after k (kernels_chains.hip)
     // (tests/test_chains_host.py holds this list, and the list of names beside it, to end in the chain kernels: the kernels
     // that came later are numbered behind it, so that no older id or name moves)
-    K_COUNT = K_CHAIN_WALK + 26
+    K_COUNT = K_CHAIN_WALK + 28
 };
 // k-nearest albums per seed group (kernels_albums.hip; its partial lists are merged by knn_merge_kernel)
 constexpr int KX_SEGMENT_MEAN = K_CHAIN_WALK + 1, KX_ALBUM_KNN_SCAN = K_CHAIN_WALK + 2;
@@ -142,12 +142,14 @@ constexpr int KX_MOMENTS_PLAN = K_CHAIN_WALK + 13, KX_MOMENTS_SUM = K_CHAIN_WALK
 constexpr int KX_CHAMFER_SCAN = K_CHAIN_WALK + 19, KX_CHAMFER_REDUCE = K_CHAIN_WALK + 20, KX_CHAMFER_SELECT = K_CHAIN_WALK + 21;
 // the minimum spanning tree (kernels_mst.hip): every song's smallest edge out of its component, every component's smallest
 constexpr int KX_MST_SCAN = K_CHAIN_WALK + 22, KX_MST_PICK = K_CHAIN_WALK + 23;
+// locally scaled k-nearest search and the k-occurrence counts (kernels_scaled_knn.hip; the scan's lists are merged by knn_merge_kernel)
+constexpr int KX_SCALED_KNN_SCAN = K_CHAIN_WALK + 24, KX_KNN_OCCURRENCE = K_CHAIN_WALK + 25;
 // (tests/test_journeys_host.py holds the profile table to END in the next two names: kernels that come later are numbered in
 // front of them; every consumer of the table goes by name)
 // the k lowest forest scores per seed group (kernels_forest.hip; its partial lists are merged by group_knn_merge_kernel)
-constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 24;
+constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 26;
 // a journey's step (kernels_chains.hip: the chains' scan with a waypoint query or a gate)
-constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 25;
+constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 27;
 static_assert(KX_JOURNEY_STEP + 1 == K_COUNT, "every kernel id is below the count");
 
 // lower_bound on a prefix array: largest s with prefix[s] <= x  (prefix has n+1 entries, prefix[0]=0)
@@ -305,6 +307,17 @@ void launch_knn_scan(const float* Q, uint64_t q, const float* X, uint32_t n, uin
                      uint32_t* nan_flag, uint32_t* bad_flag, hipStream_t st);
 void launch_knn_merge(const unsigned long long* part, uint64_t q, uint32_t k, const KnnPlan& p, uint32_t* idx, float* dist,
                       hipStream_t st);
+// k nearest candidates per query under the locally scaled distance dist / sqrtf(qscale[i] * cscale[j]) (kernels_scaled_knn.hip):
+// knn_plan's split, the same partial lists, launch_knn_merge afterwards.  Flags as for knn; a scale outside [2^-60, 2^60] (a NaN
+// included) sets *scale_flag
+void launch_scaled_knn_scan(const float* Q, uint64_t q, const float* qscale, const float* X, uint32_t n, const float* cscale,
+                            uint32_t d, int metric, const float* M, int m_is_diag, const uint32_t* skip, uint32_t k,
+                            const KnnPlan& p, unsigned long long* part, uint32_t* nan_flag, uint32_t* bad_flag,
+                            uint32_t* scale_flag, hipStream_t st);
+// count[idx[e]] += 1 for every entry of idx [entries] that is not 0xFFFFFFFF (count zeroed by the caller); an entry >= n sets
+// *bad_flag.  lds: the windowed LDS-histogram form (the A/B of DESIGN.md 3.27), same result
+void launch_knn_occurrence(const uint32_t* idx, uint64_t entries, uint32_t n, uint32_t* count, uint32_t* bad_flag, bool lds,
+                           int n_cus, hipStream_t st);
 // k nearest candidates per seed GROUP (kernels_group_knn.hip): the groups x candidates plane dealt out in items, then the two
 // launches.  `part` holds list_off[n_groups] lists of k 64-bit keys; flags as for knn
 constexpr int GROUP_KNN_SEED_TILE = 32;  // the most seed rows of one group held in LDS at a time

@@ -469,6 +469,53 @@ class Context:
         self._post()
         return idx, dist
 
+    def scaled_knn(self, Q, qscale, X, cscale, k: int, metric: str = "euclidean", M=None, skip=None):
+        """knn under the locally scaled distance dist(i, j) / sqrt(qscale[i] * cscale[j]) (blissgpu_scaled_knn_device, DESIGN.md
+        3.27: float32 throughout, the product rounded once, the correctly rounded root, true division).  qscale float32 [q] and
+        cscale float32 [n] on the device, every value in [2^-60, 2^60].  -> (idx int32 [q, k], scaled dist float32 [q, k]) on
+        the device; equal scaled distances in candidate order; padding -1 / inf and skip as for knn.  Raises BlissGpuError:
+        ERR_INVALID for a scale outside the range (NaN included) or a bad skip, ERR_NAN for a NaN among the evaluated distances
+        (synchronises for those checks)."""
+        from .playlist import _METRICS
+
+        torch = self.torch
+        assert Q.is_cuda and X.is_cuda and Q.dtype == torch.float32 and X.dtype == torch.float32
+        assert Q.dim() == 2 and X.dim() == 2 and Q.shape[1] == X.shape[1]
+        Q, X = Q.contiguous(), X.contiguous()
+        q, n, k = Q.shape[0], X.shape[0], int(k)
+        assert qscale.is_cuda and cscale.is_cuda and qscale.dtype == torch.float32 and cscale.dtype == torch.float32
+        qscale, cscale = qscale.contiguous().reshape(-1), cscale.contiguous().reshape(-1)
+        if qscale.shape[0] != q or cscale.shape[0] != n:
+            raise ValueError("qscale needs one entry per row of Q and cscale one per row of X")
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        if skip is not None:
+            assert skip.is_cuda and skip.dtype == torch.int32 and skip.shape[0] == q
+            skip = skip.contiguous()
+        if M is not None:
+            M = M.contiguous()
+        idx = torch.empty((q, max(k, 0)), dtype=torch.int32, device=X.device)
+        dist = torch.empty((q, max(k, 0)), dtype=torch.float32, device=X.device)
+        self._pre()
+        _ffi.check(self._L.blissgpu_scaled_knn_device(self._h, ptr(Q), q, ptr(qscale), ptr(X), n, ptr(cscale), Q.shape[1],
+                                                      _METRICS[metric], ptr(M), ptr(skip), k, ptr(idx), ptr(dist)))
+        self._post()
+        return idx, dist
+
+    def knn_occurrence(self, idx, n: int):
+        """In how many lists every song is (blissgpu_knn_occurrence_device): idx int32 [q, k] on the device as knn returns it
+        (-1 = padding, ignored) -> count int32 [n] on the device, count[j] = the entries equal to j.  Raises
+        BlissGpuError(ERR_INVALID) for any other entry outside 0 .. n - 1 (synchronises for that check)."""
+        torch = self.torch
+        assert idx.is_cuda and idx.dtype == torch.int32 and idx.dim() == 2
+        idx = idx.contiguous()
+        q, k, n = idx.shape[0], idx.shape[1], int(n)
+        count = torch.empty((max(n, 0),), dtype=torch.int32, device=idx.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None  # noqa: E731
+        self._pre()
+        _ffi.check(self._L.blissgpu_knn_occurrence_device(self._h, ptr(idx), q, k, n, ptr(count)))
+        self._post()
+        return count
+
     def kmeans(self, X, init, max_iter: int = 100, metric: str = "euclidean", M=None):
         """Lloyd's k-means of the rows of X from the centres `init` [k, d], iterated on the device (blissgpu_kmeans_device,
         DESIGN.md 3.21): nearest centre by the all-pairs kernel's distances with ties to the lower centre, sequential f32 means in

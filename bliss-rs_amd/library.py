@@ -1019,3 +1019,63 @@ def tour(db: Conn, start_path: str = None, where=None, metric_builder=playlist.e
         return []
     tree = playlist.minimum_spanning_tree(X, metric_builder, min_samples)
     return [songs[int(i)] for i in tree.tour(start)]
+
+
+def _scaled_lists(db: Conn, k, m, kind, metric_builder, scaled=True):
+    """-> (paths, idx): every analysed song's k nearest other songs, raw or locally scaled"""
+    metric, mm = playlist._scaled_metric(metric_builder, "a per-song search")  # refused before the database is read
+    _, paths, X = load_feature_matrix(db, FeaturesVersion.LATEST)
+    n = len(paths)
+    if n == 0:
+        return paths, np.zeros((0, int(k)), np.int64)
+    if not scaled:
+        return paths, playlist.nearest_order(X, X, k, metric, mm, skip=np.arange(n))[0]
+    scale = playlist.local_scales(X, m, kind, metric_builder)
+    return paths, playlist.scaled_nearest_order(X, scale, X, scale, k, metric, mm, skip=np.arange(n))[0]
+
+
+def similar_songs_scaled(db: Conn, k: int, m: int = 10, kind: str = "mean", metric_builder=playlist.euclidean_distance,
+                         song_paths: Sequence[str] = None):
+    """similar_songs under the locally scaled distance (playlist.scaled_nearest_order): {path: [(path, scaled
+    distance), ...]} with the k songs closest to each song when every distance is divided by the geometric mean of the two
+    songs' local scales (playlist.local_scales over the m nearest songs of the WHOLE library) -- the lists a few "hub" songs no
+    longer dominate.  Two device searches whatever the library: one for the scales, one scaled.  `song_paths`: only those
+    songs' lists (the scales still come from the whole library); an unknown path is a ProviderError."""
+    metric, mm = playlist._scaled_metric(metric_builder, "similar_songs_scaled")
+    _, paths, X = load_feature_matrix(db, FeaturesVersion.LATEST)
+    if song_paths is None:
+        rows = np.arange(len(paths), dtype=np.int64)
+    else:
+        row_of = {p: i for i, p in enumerate(paths)}
+        for p in song_paths:
+            if p not in row_of:
+                raise ProviderError(f"song '{p}' has not been analyzed")
+        rows = np.asarray([row_of[p] for p in song_paths], np.int64)
+    if rows.size == 0:
+        return {}
+    scale = playlist.local_scales(X, m, kind, metric_builder)
+    if song_paths is None:
+        idx, dist = playlist.scaled_nearest_order(X, scale, X, scale, k, metric, mm, skip=rows)
+    else:
+        idx, dist = playlist.scaled_nearest_order(X[rows], scale[rows], X, scale, k, metric, mm, skip=rows)
+    return {paths[int(r)]: [(paths[int(j)], float(v)) for j, v in zip(idx[i], dist[i]) if j >= 0]
+            for i, r in enumerate(rows)}
+
+
+def hubness(db: Conn, k: int, scaled: bool = False, m: int = 10, kind: str = "mean", metric_builder=playlist.euclidean_distance):
+    """How unevenly the library's similar-songs lists spread their recommendations: -> (playlist.Hubness, paths) over every
+    analysed song's k nearest other songs, raw (`scaled` False: what similar_songs returns) or locally scaled (what
+    similar_songs_scaled returns).  hubness.counts[i] is the number of lists the song at paths[i] is in, hubness.skewness the
+    one number to compare two similarity measures by, hubness.hubs(t) the rows of the songs that dominate."""
+    paths, idx = _scaled_lists(db, k, m, kind, metric_builder, scaled)
+    if not paths:
+        return playlist.Hubness.from_counts(np.zeros(0, np.int64), k), paths
+    return playlist.hubness(idx, len(paths)), paths
+
+
+def orphan_songs(db: Conn, k: int, scaled: bool = False, m: int = 10, kind: str = "mean",
+                 metric_builder=playlist.euclidean_distance) -> List[str]:
+    """The paths no song's list of k similar songs contains -- the part of a library a recommender never plays --, raw or
+    locally scaled, in id order."""
+    h, paths = hubness(db, k, scaled, m, kind, metric_builder)
+    return [paths[int(i)] for i in h.orphans()]

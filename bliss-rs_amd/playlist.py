@@ -917,6 +917,197 @@ def minimum_spanning_tree(songs_or_X, metric_builder=euclidean_distance, min_sam
     return SpanningTree(u.astype(np.int64), v.astype(np.int64), w, int(rounds.value), n)
 
 
+# ---- locally scaled nearest songs and hubness (blissgpu_scaled_knn / blissgpu_knn_occurrence) ----
+SCALE_MIN, SCALE_MAX = np.float32(2.0 ** -60), np.float32(2.0 ** 60)  # the scales blissgpu_scaled_knn accepts
+
+
+def _scaled_metric(metric_builder, what):
+    _no_forest(metric_builder, f"{what} compares single songs; a forest scores songs against a seed set")
+    _no_variance(metric_builder, f"{what} has no seed set to take variances from; pass MahalanobisBuilder(m)")
+    return _metric_of(metric_builder)
+
+
+def scales_from_distances(dist, m, kind="mean") -> np.ndarray:
+    """A local scale per row of `dist` (float32 [q, k]: every song's ascending neighbour distances as nearest_order returns
+    them, short rows padded with inf), device-free.  With c = min(m, the row's finite entries): kind="mean" (NICDM) is the
+    float64 sum of the first c distances, added in order, divided by c and rounded to float32; kind="kth" (Zelnik-Manor and
+    Perona's sigma) is entry c - 1, which with min_samples = m is core_distances.  A row without a finite entry gets 1.
+    Results below 2^-60 -- songs whose m nearest are exact duplicates -- are raised to the smallest result that is not below
+    2^-60 (1 when there is none), results above 2^60 become 2^60: every scale is one blissgpu_scaled_knn accepts."""
+    if kind not in ("mean", "kth"):
+        raise ValueError('kind must be "mean" or "kth"')
+    m = int(m)
+    if m < 1:
+        raise ValueError("m must be at least 1")
+    D = np.asarray(dist, dtype=np.float32)
+    if D.ndim != 2:
+        raise ValueError("dist must be [q, k]")
+    if np.isnan(D).any():
+        raise ValueError("NaN distance")
+    q = D.shape[0]
+    c = np.minimum(m, np.isfinite(D).sum(axis=1))
+    out = np.ones(q, np.float32)
+    rows = np.flatnonzero(c > 0)
+    last = c[rows] - 1
+    if kind == "mean":
+        sums = np.cumsum(D.astype(np.float64), axis=1)  # (sequential: the first c terms in order)
+        out[rows] = (sums[rows, last] / c[rows]).astype(np.float32)
+    else:
+        out[rows] = D[rows, last]
+    ok = out >= SCALE_MIN
+    out[~ok] = out[ok].min() if ok.any() else np.float32(1.0)
+    return np.minimum(out, SCALE_MAX)
+
+
+def local_scales(songs_or_X, m=10, kind="mean", metric_builder=euclidean_distance) -> np.ndarray:
+    """Every song's own idea of "near" (float32 [n]): scales_from_distances over its m nearest OTHER songs, from one k-nearest
+    search on the device (nearest_order, every song skipping itself).  A lone song gets 1."""
+    metric, mm = _scaled_metric(metric_builder, "local_scales")
+    X = _rows_of_input(songs_or_X)
+    n = X.shape[0]
+    m = int(m)
+    if m < 1:
+        raise ValueError("m must be at least 1")
+    k = min(m, n - 1)
+    if k < 1:
+        return np.ones(n, np.float32)
+    _, dist = nearest_order(X, X, k, metric, mm, skip=np.arange(n))
+    return scales_from_distances(dist, m, kind)
+
+
+def scaled_nearest_order(queries, qscale, candidates, cscale, k, metric="euclidean", m=None, skip=None):
+    """nearest_order under the locally scaled distance dist(i, j) / sqrt(qscale[i] * cscale[j]) (float32 throughout: the
+    product rounded once, the correctly rounded root, true division; blissgpu_scaled_knn) -- the cure for
+    hubs, the few songs a raw search puts into everyone's list.  -> (idx int64[q, k], scaled dist float32[q, k]); equal SCALED
+    distances come in candidate order; rows with fewer than k eligible candidates end in -1 / inf.  Scales must lie in
+    [2^-60, 2^60] (local_scales / scales_from_distances return such), else BlissGpuError(ERR_INVALID).  Passing the same array
+    objects as queries / candidates and as qscale / cscale uploads each once.  A NaN distance raises ValueError."""
+    X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
+    Q = X if queries is candidates else np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+    if Q.ndim != 2 or X.ndim != 2 or Q.shape[1] != X.shape[1]:
+        raise ValueError("queries and candidates must be [q, d] and [n, d]")
+    cs = np.ascontiguousarray(cscale, dtype=np.float32).reshape(-1)
+    qs = cs if (qscale is cscale and Q is X) else np.ascontiguousarray(qscale, dtype=np.float32).reshape(-1)
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be at least 1")
+    q, d = Q.shape
+    n = X.shape[0]
+    if qs.shape[0] != q or cs.shape[0] != n:
+        raise ValueError("qscale needs one entry per query and cscale one per candidate")
+    skip_p = None
+    if skip is not None:
+        skip = np.asarray(skip, dtype=np.int64).reshape(-1)
+        if skip.shape[0] != q:
+            raise ValueError("skip needs one entry per query")
+        if ((skip < -1) | (skip >= max(n, 0))).any():
+            raise ValueError("skip entries must be candidate indices or -1")
+        skip = np.where(skip < 0, 0xFFFFFFFF, skip).astype(np.uint32)
+        skip_p = skip.ctypes.data
+    mp = None
+    if m is not None:
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        mp = m.ctypes.data
+    idx, dist = np.empty((q, k), np.uint32), np.empty((q, k), np.float32)
+    try:
+        _ffi.check(_ffi.lib().blissgpu_scaled_knn(Q.ctypes.data, q, qs.ctypes.data, X.ctypes.data, n, cs.ctypes.data, d,
+                                                  _METRICS[metric], mp, skip_p, k, idx.ctypes.data, dist.ctypes.data))
+    except _ffi.BlissGpuError as e:
+        _nan_to_panic(e)
+    out = idx.astype(np.int64)
+    out[idx == 0xFFFFFFFF] = -1
+    return out, dist
+
+
+def _lists(idx):
+    """[q, k] int64 with -1 padding from an index matrix"""
+    idx = np.asarray(idx)
+    if idx.ndim != 2:
+        raise ValueError("idx must be [q, k]")
+    if idx.dtype == np.uint32:
+        out = idx.astype(np.int64)
+        out[idx == 0xFFFFFFFF] = -1
+        return out
+    out = idx.astype(np.int64)
+    if (out < -1).any() or (out >= 0xFFFFFFFF).any():
+        raise ValueError("idx entries must be song indices or -1")
+    return out
+
+
+def k_occurrence(idx, n) -> np.ndarray:
+    """In how many lists every song is: int64 [n], count[j] = the entries of idx [q, k] equal to j, counted on the device
+    (blissgpu_knn_occurrence).  -1 entries (padding) are ignored; any other entry outside 0 .. n - 1 is
+    BlissGpuError(ERR_INVALID)."""
+    L = _lists(idx)
+    n = int(n)
+    if n < 0:
+        raise ValueError("n must not be negative")
+    q, k = L.shape
+    if k < 1:
+        raise ValueError("idx needs at least one column")
+    u = np.ascontiguousarray(np.where(L < 0, 0xFFFFFFFF, L), dtype=np.uint32)
+    count = np.zeros(max(n, 1), np.uint32)
+    _ffi.check(_ffi.lib().blissgpu_knn_occurrence(u.ctypes.data if q else None, q, k, n, count.ctypes.data if n else None))
+    return count[:n].astype(np.int64)
+
+
+@dataclasses.dataclass
+class Hubness:
+    """How unevenly a ranking spreads its recommendations: `counts` int64 [n] (k_occurrence: in how many lists every song is),
+    `skewness` (the population skewness m3 / m2^1.5 of the counts in float64, 0 when all are equal: about 0 for a fair ranking,
+    2 - 3 for raw distances in 20 dimensions), and `k`, the length of the lists."""
+
+    counts: np.ndarray
+    skewness: float
+    k: int
+
+    @classmethod
+    def from_counts(cls, counts, k) -> "Hubness":
+        c = np.asarray(counts, dtype=np.int64).reshape(-1)
+        x = c.astype(np.float64)
+        skew = 0.0
+        if x.size:
+            dev = x - x.mean()
+            m2, m3 = (dev ** 2).mean(), (dev ** 3).mean()
+            skew = 0.0 if m2 == 0 else float(m3 / m2 ** 1.5)
+        return cls(c, skew, int(k))
+
+    def hubs(self, t) -> np.ndarray:
+        """the t most-listed songs, int64, most-listed first, ties to the lower song"""
+        order = np.lexsort((np.arange(self.counts.size), -self.counts))
+        return order[:max(int(t), 0)].astype(np.int64)
+
+    def orphans(self) -> np.ndarray:
+        """the songs no list contains, ascending"""
+        return np.flatnonzero(self.counts == 0).astype(np.int64)
+
+
+def hubness(idx, n) -> Hubness:
+    """The hubness of the lists idx [q, k] over n songs: the counts from the device (k_occurrence), their skewness on the host."""
+    L = _lists(idx)
+    return Hubness.from_counts(k_occurrence(L, n), L.shape[1])
+
+
+def neighbour_agreement(idx, labels) -> float:
+    """The second yardstick of a ranking (Schnitzer et al. 2012): per song, the share of its listed neighbours that carry its
+    label; row i of idx [n, k] is song i's list.  Unlabelled songs (-1) and padding entries are left out on both sides.  -> the
+    float64 mean over the songs with at least one counted neighbour (nan when there is none).  Pure numpy."""
+    L = _lists(idx)
+    lab = np.asarray(labels, dtype=np.int64).reshape(-1)
+    if lab.shape[0] != L.shape[0]:
+        raise ValueError("labels needs one entry per row of idx")
+    if (L >= lab.shape[0]).any():
+        raise ValueError("idx entries must be rows of labels")
+    nb = np.where(L >= 0, lab[np.maximum(L, 0)], -1)  # the neighbours' labels, -1 where nothing counts
+    counted = (nb >= 0) & (lab[:, None] >= 0)
+    same = counted & (nb == lab[:, None])
+    tot = counted.sum(axis=1)
+    rows = tot > 0
+    if not rows.any():
+        return float("nan")
+    return float((same.sum(axis=1)[rows].astype(np.float64) / tot[rows]).mean())
+
+
 class KSelection:
     """The result of choose_k: ks (as given), scores (the silhouette score of each k's clustering), best_k (the k with the
     highest score; equal scores go to the lower k) and clustering (that k's Clustering)."""

@@ -424,6 +424,43 @@ int blissgpu_knn_device(blissgpu_ctx *ctx, const float *d_queries, uint64_t q, c
                         uint32_t d, int metric, const float *d_M, const uint32_t *d_skip, uint32_t k,
                         uint32_t *d_idx, float *d_dist);
 
+/* ---- Locally scaled k nearest candidates, and how often every song is listed (the reference's TODO.md complains
+ * of playlists that "drift" and asks for an objective measure of a similarity) ----
+ * A raw nearest-neighbour search in 20 or 23 dimensions has hubs: a few songs are in everyone's list, many in nobody's.  Local
+ * scaling (NICDM: Schnitzer, Flexer, Schedl, Widmer, JMLR 2012) ranks by
+ *   sdist(i, j) = dist(i, j) / sqrtf(qscale[i] * cscale[j])
+ * with dist(i, j) bit for bit what blissgpu_pairwise_device writes for the pair (what blissgpu_knn ranks by), and all three
+ * operations in IEEE binary32: the product rounded once, the correctly rounded square root, true division.  A scale is a song's
+ * own idea of "near", e.g. the mean distance to its 10 nearest songs from blissgpu_knn.
+ * Every scale lies in [2^-60, 2^60], so the product is a normal f32 and its root is not zero; any other value among qscale [q]
+ * or cscale [n] -- zero, negative, NaN, infinite -- is BLISSGPU_ERR_INVALID (checked on the device; the outputs are then
+ * unspecified).  The selection is exactly blissgpu_knn's with sdist in dist's place: per query the k smallest keys
+ * (f32_key(sdist) << 32) | candidate in ascending order, so equal SCALED distances come in candidate order; skip as for
+ * blissgpu_knn (0xFFFFFFFF skips nothing, any other value >= n is BLISSGPU_ERR_INVALID); rows with fewer than k eligible
+ * candidates end in idx 0xFFFFFFFF / dist +inf; a NaN among the evaluated base distances is BLISSGPU_ERR_NAN.  dist, when not
+ * NULL, receives the scaled distances.  Metrics and feature counts as for blissgpu_knn (a diagonal M is detected).
+ * 1 <= k <= BLISSGPU_KNN_MAX_K, 1 <= d <= 64, n < 2^32 - 1; q == 0 or n == 0 is BLISSGPU_OK.  Arguments (a NULL qscale or cscale
+ * included) are checked before the device is touched.  No q x n matrix is ever stored: the workspace is O(q k) besides the
+ * O(n) scales, two launches whatever q and n.  queries == cand with qscale == cscale (the same pointers, q <= n) uploads each
+ * once. */
+int blissgpu_scaled_knn(const float *queries, uint64_t q, const float *qscale, const float *cand, uint64_t n,
+                        const float *cscale, uint32_t d, int metric, const float *M, const uint32_t *skip, uint32_t k,
+                        uint32_t *idx, float *dist);
+/* Device-resident form (device pointers, d_skip included; d_dist may be NULL); asynchronous except for the NaN / skip / scale
+ * check, which synchronises the context's stream before returning. */
+int blissgpu_scaled_knn_device(blissgpu_ctx *ctx, const float *d_queries, uint64_t q, const float *d_qscale,
+                               const float *d_cand, uint64_t n, const float *d_cscale, uint32_t d, int metric,
+                               const float *d_M, const uint32_t *d_skip, uint32_t k, uint32_t *d_idx, float *d_dist);
+/* k-occurrence: count [n] receives, for every song j, the number of entries of idx [q][k] equal to j -- in how many lists the
+ * song is.  Padding entries (0xFFFFFFFF) are ignored; any other entry >= n is BLISSGPU_ERR_INVALID.  k >= 1, n < 2^32 - 1,
+ * q k <= 2^40; q == 0 writes zeros, n == 0 writes nothing.  One launch (integer atomics: the result does not depend on their
+ * order).  The skewness of these counts is the hubness of the ranking that produced idx.  BLISSGPU_OCCURRENCE_LDS=1 in the
+ * environment, read at every call, counts through a per-workgroup LDS histogram instead (the bench tool's A/B; the same counts). */
+int blissgpu_knn_occurrence(const uint32_t *idx, uint64_t q, uint32_t k, uint64_t n, uint32_t *count);
+/* Device-resident form (device pointers); synchronises the context's stream before returning. */
+int blissgpu_knn_occurrence_device(blissgpu_ctx *ctx, const uint32_t *d_idx, uint64_t q, uint32_t k, uint64_t n,
+                                   uint32_t *d_count);
+
 /* ---- k-means clustering of a library (the reference's TODO.md asks for genre clustering, it has no code) ----
  * Lloyd's algorithm over the rows x [n][d] from the initial centres init [k][d], every step defined to the bit.  With
  * dist(i, c) = bit for bit what blissgpu_pairwise_device(x, C_t) writes at [i][c], and L_-1[i] = 0xFFFFFFFF, iteration
