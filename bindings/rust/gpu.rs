@@ -79,6 +79,9 @@ pub mod sys {
     pub const BLISSGPU_METRIC_EUCLIDEAN: c_int = 0;
     pub const BLISSGPU_METRIC_COSINE: c_int = 1;
     pub const BLISSGPU_METRIC_MAHALANOBIS: c_int = 2;
+    pub const BLISSGPU_RADIO_MAX_RULES: u32 = 4;
+    pub const BLISSGPU_RADIO_CHAIN: c_int = 0;
+    pub const BLISSGPU_RADIO_NEAREST: c_int = 1;
     pub const BLISSGPU_SAMPLE_F32: c_int = 0;
     pub const BLISSGPU_SAMPLE_S16: c_int = 1;
     pub const BLISSGPU_SAMPLE_S32: c_int = 2;
@@ -167,6 +170,14 @@ pub mod sys {
         pub fn blissgpu_knn_occurrence(idx: *const u32, q: u64, k: u32, n: u64, count: *mut u32) -> c_int;
         pub fn blissgpu_knn_occurrence_device(ctx: *mut blissgpu_ctx, d_idx: *const u32, q: u64, k: u32, n: u64,
                                               d_count: *mut u32) -> c_int;
+        // radio playlists: song-to-song chains (mode 0) or the k nearest songs (mode 1) under artist / album separation rules
+        pub fn blissgpu_radio(from: *const f32, n_radios: u64, cand: *const f32, n: u64, d: u32, metric: c_int, m_matrix: *const f32,
+                              labels: *const u32, from_labels: *const u32, n_rules: u32, window: *const u32, limit: *const u32,
+                              skip: *const u32, k: u32, mode: c_int, idx: *mut u32, dist: *mut f32) -> c_int;
+        pub fn blissgpu_radio_device(ctx: *mut blissgpu_ctx, d_from: *const f32, n_radios: u64, d_cand: *const f32, n: u64, d: u32,
+                                     metric: c_int, d_m: *const f32, d_labels: *const u32, d_from_labels: *const u32, n_rules: u32,
+                                     window: *const u32, limit: *const u32, d_skip: *const u32, k: u32, mode: c_int,
+                                     d_idx: *mut u32, d_dist: *mut f32) -> c_int;
         pub fn blissgpu_group_knn(seeds: *const f32, group_offsets: *const u64, n_groups: u64, cand: *const f32, n: u64, d: u32,
                                   metric: c_int, m_matrix: *const f32, skip: *const u32, k: u32, idx: *mut u32, dist: *mut f32) -> c_int;
         pub fn blissgpu_group_knn_device(ctx: *mut blissgpu_ctx, d_seeds: *const f32, group_offsets: *const u64, n_groups: u64,

@@ -22,6 +22,7 @@ METRIC_EUCLIDEAN, METRIC_COSINE, METRIC_MAHALANOBIS = 0, 1, 2
 CHAINS_AUTO, CHAINS_STEPS, CHAINS_LISTS = 0, 1, 2
 JOURNEY_CHAIN, JOURNEY_WAYPOINT = 0, 1
 GATE_NONE, GATE_UP, GATE_DOWN = 0, 1, 2
+RADIO_CHAIN, RADIO_NEAREST, RADIO_MAX_RULES = 0, 1, 4
 OPT_SERIAL, OPT_TAIL_MODE, OPT_PIPELINE_CHUNKS, OPT_CAND_BUDGET, OPT_ROLLOFF_EXACT_ALL, OPT_DEBUG_CHROMA, OPT_TAIL_SPLIT = 0, 1, 2, 3, 4, 5, 6
 OPT_STFT_SHAPE = 7
 OPT_FLUX_ORDER = 8
@@ -169,6 +170,10 @@ SIGNATURES = {
                                     C.c_uint32, _vp, _vp]),
     "blissgpu_journeys_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, C.c_uint32,
                                            C.c_int, C.c_int, C.c_uint32, _vp, _vp]),
+    "blissgpu_radio": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp,
+                                 C.c_uint32, C.c_int, _vp, _vp]),
+    "blissgpu_radio_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, _vp, C.c_uint32, _vp,
+                                        _vp, _vp, C.c_uint32, C.c_int, _vp, _vp]),
     "blissgpu_duplicate_groups": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.c_int, _vp, C.c_float, _vp, _u64p, _vp, _vp,
                                             C.c_uint64]),
     "blissgpu_duplicate_groups_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_int, _vp, C.c_float, _vp, _vp, _vp,

@@ -42,6 +42,7 @@ const char kChamferScanName[] = "chamfer_scan_kernel", kChamferReduceName[] = "c
 const char kChamferSelectName[] = "chamfer_select_kernel";
 const char kMstScanName[] = "mst_scan_kernel", kMstPickName[] = "mst_pick_kernel";  // KX_MST_*
 const char kScaledKnnScanName[] = "scaled_knn_scan_kernel", kKnnOccurrenceName[] = "knn_occurrence_kernel";  // KX_SCALED_KNN_SCAN, KX_KNN_OCCURRENCE
+const char kRadioBanName[] = "radio_ban_kernel", kRadioStepName[] = "radio_step_kernel";  // KX_RADIO_BAN, KX_RADIO_STEP
 const char* const kKernelNames[K_COUNT] = {
     "fft512_kernel",     "onset_kernel",      "beat_kernel",   "stft8192_kernel", "tune_select_kernel",
     "tune_pass2_kernel", "tune_final_kernel", "chroma_kernel",     "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel", "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel",
@@ -58,6 +59,7 @@ const char* const kKernelNames[K_COUNT] = {
     kChamferScanName, kChamferReduceName, kChamferSelectName,
     kMstScanName, kMstPickName,
     kScaledKnnScanName, kKnnOccurrenceName,
+    kRadioBanName, kRadioStepName,
     kGroupForestScanName, kJourneyStepName};
 }  // namespace
 
@@ -2932,6 +2934,163 @@ int blissgpu_journeys(const float* from, const float* to, uint64_t n_journeys, c
         if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(journeys)", hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+// ---- radio playlists: chains (or the k nearest of the start song) under label rules -- no artist twice within w tracks, no
+// album twice within w tracks, at most c songs per artist (kernels_radio.hip) ----
+// everything that can be said about the arguments without a device (both forms check it BEFORE the device is touched)
+static int radio_args_ok(const char* who, const void* from, uint64_t n_radios, const void* cand, uint64_t n, uint32_t d, int metric,
+                         const float* M, const void* labels, uint32_t n_rules, const uint32_t* window, const uint32_t* limit,
+                         uint32_t k, int mode, const void* idx) {
+    if (k == 0 || k > BLISSGPU_KNN_MAX_K) return fail(BLISSGPU_ERR_INVALID, who, "k must be 1 .. BLISSGPU_KNN_MAX_K");
+    if (d == 0 || d > 64) return fail(BLISSGPU_ERR_INVALID, who, "d must be 1 .. 64");
+    if (metric < 0 || metric > 2) return fail(BLISSGPU_ERR_INVALID, who, "unknown metric");
+    if (metric == BLISSGPU_METRIC_MAHALANOBIS && !M) return fail(BLISSGPU_ERR_INVALID, who, "mahalanobis needs M");
+    if (n >= 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "n must be below 2^32 - 1 candidates");
+    if (n_radios >= 0x80000000ull) return fail(BLISSGPU_ERR_INVALID, who, "n_radios must be below 2^31");
+    if (mode != BLISSGPU_RADIO_CHAIN && mode != BLISSGPU_RADIO_NEAREST) return fail(BLISSGPU_ERR_INVALID, who, "unknown mode");
+    if (n_rules > BLISSGPU_RADIO_MAX_RULES) return fail(BLISSGPU_ERR_INVALID, who, "n_rules must be at most BLISSGPU_RADIO_MAX_RULES");
+    if (n_rules) {
+        if (!window) return fail(BLISSGPU_ERR_INVALID, who, "window is NULL");
+        if (!limit) return fail(BLISSGPU_ERR_INVALID, who, "limit is NULL");
+        if (!labels) return fail(BLISSGPU_ERR_INVALID, who, "labels is NULL");
+        for (uint32_t r = 0; r < n_rules; r++)
+            if (limit[r] == 0) return fail(BLISSGPU_ERR_INVALID, who, "limit must be at least 1");
+    }
+    if (n_radios == 0) return BLISSGPU_OK;
+    if (!from) return fail(BLISSGPU_ERR_INVALID, who, "from is NULL");
+    if (n && !cand) return fail(BLISSGPU_ERR_INVALID, who, "cand is NULL");
+    if (!idx) return fail(BLISSGPU_ERR_INVALID, who, "idx is NULL");
+    return BLISSGPU_OK;
+}
+
+// the rules that can ban anything in a list of k songs: window >= 1 (cut to k + 1: the whole list and the start) and
+// limit <= min(window, k), the most history positions a step's window holds
+static RadioRules radio_rules(uint32_t n_rules, const uint32_t* window, const uint32_t* limit, uint32_t k) {
+    RadioRules r{};
+    r.n_total = n_rules;
+    r.cap = 1;
+    for (uint32_t i = 0; i < n_rules; i++) {
+        const uint32_t w = std::min(window[i], k + 1u), most = std::min(w, k);
+        if (w == 0 || limit[i] > most) continue;
+        r.rule[r.n] = i;
+        r.window[r.n] = w;
+        r.limit[r.n] = limit[i];
+        r.cap = std::max(r.cap, most / limit[i]);
+        r.n++;
+    }
+    return r;
+}
+
+int blissgpu_radio_device(blissgpu_ctx* c, const float* d_from, uint64_t n_radios, const float* d_cand, uint64_t n, uint32_t d,
+                          int metric, const float* d_M, const uint32_t* d_labels, const uint32_t* d_from_labels, uint32_t n_rules,
+                          const uint32_t* window, const uint32_t* limit, const uint32_t* d_skip, uint32_t k, int mode,
+                          uint32_t* d_idx, float* d_dist) {
+    const char* who = "blissgpu_radio_device";
+    int rc = radio_args_ok(who, d_from, n_radios, d_cand, n, d, metric, d_M, d_labels, n_rules, window, limit, k, mode, d_idx);
+    if (rc) return rc;
+    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
+    if (n_radios == 0) return BLISSGPU_OK;
+    CTX_ENTER(c, who);
+    int diag = 0;
+    if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
+        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
+            diag = is_diag(c->m_cache.data(), d);
+        } else {
+            std::vector<float> hM((size_t)d * d);
+            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            diag = is_diag(hM.data(), d);
+        }
+    }
+    const RadioRules rules = radio_rules(n_rules, window, limit, k);
+    // pl_chain: minima u64[G] | flags u32[4] ([0] NaN) | ban counts u32[G * rules] | banned labels u32[G * rules * cap]
+    const uint64_t G = n_radios, out_n = G * k, work = G * rules.n;
+    const uint64_t bytes = G * sizeof(unsigned long long) + 4 * sizeof(uint32_t) + (work + work * rules.cap) * sizeof(uint32_t);
+    if (bytes > c->ws_limit) return fail(BLISSGPU_ERR_OOM, who, "the banned labels of every radio do not fit the workspace limit");
+    rc = c->pl_chain.ensure((size_t)bytes);
+    if (rc) return rc;
+    unsigned long long* best = reinterpret_cast<unsigned long long*>(c->pl_chain.p);
+    uint32_t* flags = reinterpret_cast<uint32_t*>(c->pl_chain.p + G * sizeof(unsigned long long));
+    uint32_t* ban_cnt = flags + 4;
+    uint32_t* ban = ban_cnt + work;
+    // every row: 0xFFFFFFFF / +inf until a step writes it
+    HIP_TRY(hipMemsetAsync(d_idx, 0xFF, out_n * sizeof(uint32_t), c->stream));
+    if (d_dist) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_dist, 0x7F800000, out_n, c->stream));
+    HIP_TRY(hipMemsetAsync(flags, 0, 4 * sizeof(uint32_t), c->stream));
+    HIP_TRY(hipMemsetAsync(best, 0xFF, G * sizeof(unsigned long long), c->stream));
+    const ChainPlan plan = chain_plan(n_radios, n, c->n_cus);
+    const RadioArgs a{d_cand, (uint32_t)n, d, metric, d_M, diag, d_from, d_skip, d_labels, d_from_labels, rules, ban, ban_cnt,
+                      mode == BLISSGPU_RADIO_NEAREST, (uint32_t)n_radios, k, d_idx, d_dist, best, flags};
+    const uint32_t steps = (uint32_t)std::min<uint64_t>(k, n);  // (a radio is no longer than the candidates)
+    for (uint32_t t = 0; t < steps; t++) {
+        if (rules.n) {
+            Prof p(c, KX_RADIO_BAN);
+            launch_radio_ban(a, t, c->stream);
+        }
+        Prof p(c, KX_RADIO_STEP);
+        launch_radio_step(a, t, plan, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    uint32_t h_flags[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (h_flags[0]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_radio(const float* from, uint64_t n_radios, const float* cand, uint64_t n, uint32_t d, int metric, const float* M,
+                   const uint32_t* labels, const uint32_t* from_labels, uint32_t n_rules, const uint32_t* window,
+                   const uint32_t* limit, const uint32_t* skip, uint32_t k, int mode, uint32_t* idx, float* dist) {
+    const char* who = "blissgpu_radio";
+    int rc = radio_args_ok(who, from, n_radios, cand, n, d, metric, M, labels, n_rules, window, limit, k, mode, idx);
+    if (rc) return rc;
+    if (n_radios == 0) return BLISSGPU_OK;
+    if (skip)
+        for (uint64_t i = 0; i < 2 * n_radios; i++)
+            if (skip[i] != 0xFFFFFFFFu && skip[i] >= n) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
+    if (n == 0) {  // no candidate: every row is padding, and no device is needed to say so
+        std::fill(idx, idx + (size_t)n_radios * k, 0xFFFFFFFFu);
+        if (dist) std::fill(dist, dist + (size_t)n_radios * k, INFINITY);
+        return BLISSGPU_OK;
+    }
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    // start rows that ARE the candidate matrix travel once
+    const bool shared = (const void*)from == (const void*)cand && n_radios <= n;
+    const size_t G = (size_t)n_radios, out_n = G * k, row_n = G * d;
+    const size_t lab_n = (size_t)n_rules * n, fl_n = from_labels ? G * n_rules : 0;
+    const float* dM = nullptr;
+    rc = c->st_b.ensure(std::max<size_t>(1, n * d));
+    if (!rc && !shared) rc = c->st_a.ensure(row_n);
+    if (!rc) rc = c->st_idx.ensure(out_n + (skip ? 2 * G : 0) + lab_n + fl_n);  // idx | skip | labels | from_labels
+    if (!rc && dist) rc = c->st_dist.ensure(out_n);
+    if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
+    if (rc) return rc;
+    uint32_t *d_idx = c->st_idx.p, *d_skip = skip ? c->st_idx.p + out_n : nullptr;
+    uint32_t* d_lab = c->st_idx.p + out_n + (skip ? 2 * G : 0);
+    uint32_t* d_fl = d_lab + lab_n;
+    hipError_t e = hipSuccess;
+    if (n) e = hipMemcpyAsync(c->st_b.p, cand, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && !shared) e = hipMemcpyAsync(c->st_a.p, from, row_n * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && skip) e = hipMemcpyAsync(d_skip, skip, 2 * G * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && lab_n) e = hipMemcpyAsync(d_lab, labels, lab_n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && fl_n) e = hipMemcpyAsync(d_fl, from_labels, fl_n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(radio)", hipGetErrorString(e));
+    if (!rc)
+        rc = blissgpu_radio_device(c, shared ? c->st_b.p : c->st_a.p, n_radios, c->st_b.p, n, d, metric, dM, n_rules ? d_lab : nullptr,
+                                   fl_n ? d_fl : nullptr, n_rules, window, limit, d_skip, k, mode, d_idx,
+                                   dist ? c->st_dist.p : nullptr);
+    if (!rc) {
+        e = hipMemcpyAsync(idx, d_idx, out_n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(radio)", hipGetErrorString(e));
     }
     (void)hipStreamSynchronize(c->stream);
     return rc;

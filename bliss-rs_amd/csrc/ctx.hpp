@@ -271,6 +271,7 @@ struct blissgpu_ctx {
     bg::DevBuf<uint8_t> pl_tmp;
     bg::DevBuf<unsigned long long> pl_slots;
     bg::DevBuf<uint8_t> pl_chain;                  // chains: offsets, step 0, minima, and the candidates' lists of the lists route
+                                                   // (journeys: minima; radios: minima and the banned labels of every radio and rule)
     bg::DevBuf<uint8_t> km_ws;                     // k-means: flags | histograms | scan totals | row lists | the two sets of centres
     uint64_t km_loop_copies = 0, km_loop_bytes = 0; // the last k-means call: device-to-host copies inside its loop, their bytes
     bg::DevBuf<uint8_t> sil_ws;                    // silhouette: flags | histograms | scan totals | row lists | the groups' partial results

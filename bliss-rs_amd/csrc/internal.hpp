@@ -123,7 +123,7 @@ enum KernelId : int {
     K_CHAIN_STEP, K_CHAIN_WALK,             // song-to-song chains cut after k (kernels_chains.hip)
     // (tests/test_chains_host.py holds this list, and the list of names beside it, to end in the chain kernels: the kernels
     // that came later are numbered behind it, so that no older id or name moves)
-    K_COUNT = K_CHAIN_WALK + 28
+    K_COUNT = K_CHAIN_WALK + 30
 };
 // k-nearest albums per seed group (kernels_albums.hip; its partial lists are merged by knn_merge_kernel)
 constexpr int KX_SEGMENT_MEAN = K_CHAIN_WALK + 1, KX_ALBUM_KNN_SCAN = K_CHAIN_WALK + 2;
@@ -144,12 +144,14 @@ constexpr int KX_CHAMFER_SCAN = K_CHAIN_WALK + 19, KX_CHAMFER_REDUCE = K_CHAIN_W
 constexpr int KX_MST_SCAN = K_CHAIN_WALK + 22, KX_MST_PICK = K_CHAIN_WALK + 23;
 // locally scaled k-nearest search and the k-occurrence counts (kernels_scaled_knn.hip; the scan's lists are merged by knn_merge_kernel)
 constexpr int KX_SCALED_KNN_SCAN = K_CHAIN_WALK + 24, KX_KNN_OCCURRENCE = K_CHAIN_WALK + 25;
+// radio playlists (kernels_radio.hip): the banned labels of every (radio, rule), then the step under them
+constexpr int KX_RADIO_BAN = K_CHAIN_WALK + 26, KX_RADIO_STEP = K_CHAIN_WALK + 27;
 // (tests/test_journeys_host.py holds the profile table to END in the next two names: kernels that come later are numbered in
 // front of them; every consumer of the table goes by name)
 // the k lowest forest scores per seed group (kernels_forest.hip; its partial lists are merged by group_knn_merge_kernel)
-constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 26;
+constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 28;
 // a journey's step (kernels_chains.hip: the chains' scan with a waypoint query or a gate)
-constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 27;
+constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 29;
 static_assert(KX_JOURNEY_STEP + 1 == K_COUNT, "every kernel id is below the count");
 
 // lower_bound on a prefix array: largest s with prefix[s] <= x  (prefix has n+1 entries, prefix[0]=0)
@@ -544,6 +546,40 @@ struct JourneyStep {
 void launch_journey_step(const float* X, uint32_t n, uint32_t d, int metric, const float* M, int m_is_diag, const uint32_t* skip,
                          uint32_t n_journeys, uint32_t k, uint32_t t, const ChainPlan& p, const JourneyStep& j, uint32_t* idx,
                          float* dist, unsigned long long* best, uint32_t* nan_flag, hipStream_t st);
+// radio playlists (kernels_radio.hip): chains (or, nearest != 0, the k nearest of the start row) under label
+// rules.  `rules` holds the ACTIVE rules only (window >= 1 and limit <= window), their windows already cut to k + 1; rule[a] is
+// the row of labels ([n_total][n]) and the column of from_labels ([n_radios][n_total] or NULL) that rule a reads.  Step t is
+// launch_radio_ban (nothing with no active rule) followed by launch_radio_step: ban[(radio, a)][0 .. cap) / ban_cnt[(radio, a)]
+// are the labels banned at that step.  best / nan_flag as for the chains; skip is [n_radios][2] or NULL
+constexpr uint32_t RADIO_NONE = 0xFFFFFFFFu;  // no label: never banned
+constexpr int RADIO_MAX_RULES = 4;
+struct RadioRules {
+    uint32_t n, n_total;  // active rules, rules of the call
+    uint32_t cap;         // banned labels a (radio, rule) can have: max over the rules of min(window, k) / limit
+    uint32_t rule[RADIO_MAX_RULES], window[RADIO_MAX_RULES], limit[RADIO_MAX_RULES];
+};
+struct RadioArgs {
+    const float* X;  // [n][d] candidates
+    uint32_t n, d;
+    int metric;
+    const float* M;
+    int m_is_diag;
+    const float* from;  // [n_radios][d]
+    const uint32_t* skip;
+    const uint32_t* labels;
+    const uint32_t* from_labels;
+    RadioRules rules;
+    uint32_t* ban;
+    uint32_t* ban_cnt;
+    int nearest;
+    uint32_t n_radios, k;
+    uint32_t* idx;
+    float* dist;
+    unsigned long long* best;
+    uint32_t* nan_flag;
+};
+void launch_radio_ban(const RadioArgs& a, uint32_t t, hipStream_t st);
+void launch_radio_step(const RadioArgs& a, uint32_t t, const ChainPlan& p, hipStream_t st);
 // column 0 of idx / dist from step 0's [n_chains] arrays
 void launch_chain_first(const uint32_t* idx0, const float* dist0, uint32_t n_chains, uint32_t k, uint32_t* idx, float* dist,
                         hipStream_t st);

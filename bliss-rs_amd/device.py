@@ -966,6 +966,55 @@ class Context:
         self._post()
         return idx, dist
 
+    def radio(self, A, X, k: int, labels=None, windows=(), limits=(), from_labels=None, mode: str = "chain",
+              metric: str = "euclidean", M=None, skip=None):
+        """Radio playlists (blissgpu_radio_device): song-to-song chains (mode "chain") or the k nearest songs
+        (mode "nearest") from every row of A under label rules, k steps for every radio in one call.  labels: int32 tensor
+        [R, n], one label per rule and candidate (artist id, album id, ...), -1 = no label; from_labels: int32 tensor [G, R],
+        the start songs' labels, or None; windows / limits: HOST sequences of R integers -- among the last windows[r] songs of a
+        radio (the start song is the one before the first) at most limits[r] carry any one label; windows[r] == 0 switches the
+        rule off, windows[r] > k is the whole list.  A picked candidate is never picked again; skip: int32 tensor [G, 2] of
+        candidate indices that are never eligible, -1 = none, or None.  -> (idx int32 [G, k], dist float32 [G, k]) on the
+        device; a radio that runs out of eligible candidates ends in -1 (the library's 0xFFFFFFFF) / inf.  Raises
+        BlissGpuError(ERR_NAN) for a NaN distance of an eligible candidate (synchronises for that check)."""
+        import numpy as np
+
+        from .playlist import _METRICS, _RADIO_MODES
+
+        torch = self.torch
+        assert A.is_cuda and X.is_cuda and A.dtype == torch.float32 and X.dtype == torch.float32
+        assert A.dim() == 2 and X.dim() == 2 and A.shape[1] == X.shape[1]
+        A, X = A.contiguous(), X.contiguous()
+        G, n, k = A.shape[0], X.shape[0], int(k)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        win = np.ascontiguousarray(np.minimum(np.asarray(windows, np.int64).reshape(-1), 0xFFFFFFFF), dtype=np.uint32)
+        lim = np.ascontiguousarray(np.minimum(np.asarray(limits, np.int64).reshape(-1), 0xFFFFFFFF), dtype=np.uint32)
+        R = win.shape[0]
+        assert lim.shape[0] == R
+        if R:
+            assert labels is not None and labels.is_cuda and labels.dtype == torch.int32 and tuple(labels.shape) == (R, n)
+            labels = labels.contiguous()
+        else:
+            labels = None
+        if from_labels is not None and R:
+            assert from_labels.is_cuda and from_labels.dtype == torch.int32 and tuple(from_labels.shape) == (G, R)
+            from_labels = from_labels.contiguous()
+        else:
+            from_labels = None
+        if skip is not None:
+            assert skip.is_cuda and skip.dtype == torch.int32 and tuple(skip.shape) == (G, 2)
+            skip = skip.contiguous()
+        if M is not None:
+            M = M.contiguous()
+        idx = torch.empty((G, max(k, 0)), dtype=torch.int32, device=X.device)
+        dist = torch.empty((G, max(k, 0)), dtype=torch.float32, device=X.device)
+        self._pre()
+        _ffi.check(self._L.blissgpu_radio_device(self._h, ptr(A), G, ptr(X), n, X.shape[1], _METRICS[metric], ptr(M), ptr(labels),
+                                                 ptr(from_labels), R, win.ctypes.data if R else None, lim.ctypes.data if R else None,
+                                                 ptr(skip), k, _RADIO_MODES[mode], ptr(idx), ptr(dist)))
+        self._post()
+        return idx, dist
+
     def album_knn(self, S, offsets, X, album_of, n_albums: int, k: int, skip=None):
         """The k nearest ALBUMS of every seed group (blissgpu_album_knn_device): closest_album_to_group (src/playlist.rs:424-485)
         cut after k albums.  Group g's seeds are the rows offsets[g] .. offsets[g + 1] of S (offsets: a HOST sequence of G + 1

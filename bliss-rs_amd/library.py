@@ -603,6 +603,33 @@ def directed_playlists(db: Conn, k: int, feature=AnalysisIndex.Tempo, direction:
     return {p: [songs[int(j)] for j in row if j >= 0] for p, row in zip(paths, idx)}
 
 
+def radio_playlists(db: Conn, k: int, rules=playlist.DEFAULT_RADIO_RULES, song_paths: Sequence[str] = None, mode: str = "chain",
+                    metric_builder=playlist.euclidean_distance):
+    """A radio (playlist.radio_playlist) starting at every analysed song of FeaturesVersion.LATEST, or at `song_paths` only:
+    {path: [Song, ...]}, up to k songs, each the nearest song not yet played (mode "chain": nearest the song before it;
+    "nearest": nearest the starting song) that breaks none of `rules` (playlist.Rule; by default no artist twice within 5
+    tracks, no album twice within 20).  The starting song is left out of the list and counts as the track before the first.
+    The library is read once and ONE device call (playlist.radio_order) answers every path.  An unknown path is the
+    ProviderError playlist_from_custom raises.  VarianceWeights and ForestOptions are refused."""
+    playlist._no_forest(metric_builder, playlist._RADIO_WHY)
+    playlist._no_variance(metric_builder, playlist._RADIO_WHY)
+    if mode not in playlist._RADIO_MODES:
+        raise ValueError('mode must be "chain" or "nearest"')
+    rules = list(rules)
+    windows, limits = playlist._rule_arrays(rules, k)
+    songs, X = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
+    paths = [s.path for s in songs] if song_paths is None else list(song_paths)
+    rows = _rows_of(songs, paths)
+    if not paths:
+        return {}
+    metric, m = playlist._metric_of(metric_builder)
+    labels = playlist.rule_labels(songs, rules)
+    skip = np.stack([rows, np.full_like(rows, -1)], axis=1)
+    A = X if song_paths is None else X[rows]  # (every song: the rows are the candidates, uploaded once)
+    idx, _ = playlist.radio_order(A, X, k, labels, windows, limits, labels[:, rows].T, mode, metric, m, skip)
+    return {p: [songs[int(j)] for j in row if j >= 0] for p, row in zip(paths, idx)}
+
+
 def duplicate_songs(db: Conn, distance_threshold: float = None, metric_builder=playlist.euclidean_distance) -> List[List[Song]]:
     """Which songs of the library are the same song: the duplicate rule of `dedup_playlist_custom_distance`
     (src/playlist.rs:381-388: closer than the threshold, default 0.05, or the same `Some` title and artist) over every pair

@@ -11,6 +11,8 @@
     duplicate_labels, duplicate_groups (the rule of :381-388 over every pair of a collection, closed transitively)
     closest_album_to_group                                       :424-485
     journey_order, waypoint_playlist, directed_playlist (the waypoint and direction features of the reference's TODO.md)
+    Rule, rule_labels, radio_order, radio_playlist (radio playlists: song-to-song chains or the k nearest songs under artist /
+    album separation rules -- no artist twice within w tracks, at most c songs per artist -- exact, stepped on the device)
     kmeans, kmeans_init, cluster_songs (the clustering the reference's TODO.md asks for: Lloyd's algorithm on the device)
     silhouette, choose_k (the "objective way to evaluate" of the reference's TODO.md: how well a labelling separates the songs
     under a metric, all pairs on the device without the distance matrix; and the k whose k-means clusters separate them best)
@@ -1877,6 +1879,172 @@ def directed_playlist(first_song, candidate_songs, number_songs, feature, direct
     metric, m = _metric_of(metric_builder)
     idx, _ = journey_order(_matrix([first_song]), _matrix(candidate_songs), number_songs, None, metric, m,
                            _end_point_skip([[first_song]], candidate_songs), direction, int(feature))
+    return [candidate_songs[j] for j in idx[0] if j >= 0]
+
+
+# ---- radio playlists: chains (or the k nearest songs) under artist / album separation rules (blissgpu_radio) ----
+_RADIO_MODES = {"chain": _ffi.RADIO_CHAIN, "nearest": _ffi.RADIO_NEAREST}
+_RADIO_WHY = "a radio's metric compares single songs, step by step"
+_RULE_COLUMNS = ("artist", "album", "album_artist", "genre")
+NO_LABEL = 0xFFFFFFFF  # a song without a label: no rule constrains it
+
+
+@dataclasses.dataclass(frozen=True)
+class Rule:
+    """Among the last `window` songs of a radio (the start song included while it is that near) at most `limit` carry any one
+    key.  `by`: "artist", "album", "album_artist", "genre" or a callable Song -> key (None: the song has no key and the rule
+    never constrains it).  window=None: the whole list, i.e. at most `limit` songs per key in it.  Rule("artist", 5): no artist
+    twice within five tracks; Rule("artist", None, 2): at most two songs per artist."""
+    by: object
+    window: Optional[int] = None
+    limit: int = 1
+
+    def __post_init__(self):
+        if not callable(self.by) and self.by not in _RULE_COLUMNS:
+            raise ValueError(f"by must be one of {_RULE_COLUMNS} or a callable Song -> key")
+        if self.window is not None and int(self.window) < 0:
+            raise ValueError("window must be None (the whole list) or >= 0 (0: the rule is off)")
+        if int(self.limit) < 1:
+            raise ValueError("limit must be at least 1")
+
+
+def _rule_key(song, by):
+    s = _song_of(song)
+    if callable(by):
+        return by(s)
+    if by == "album":  # two albums called "Greatest Hits" are two albums
+        owner = s.album_artist if s.album_artist is not None else s.artist
+        return None if s.album is None else (owner, s.album)
+    return getattr(s, by)
+
+
+def rule_labels(songs, rules) -> np.ndarray:
+    """uint32 [len(rules), len(songs)]: one label per rule and song, equal labels exactly for equal keys (a dictionary per rule,
+    so there are no collisions), NO_LABEL for a key of None.  The key of "album" is (album_artist or artist, album)."""
+    songs, rules = list(songs), list(rules)
+    out = np.full((len(rules), len(songs)), NO_LABEL, np.uint32)
+    for r, rule in enumerate(rules):
+        seen = {}
+        for i, s in enumerate(songs):
+            key = _rule_key(s, rule.by)
+            if key is not None:
+                out[r, i] = seen.setdefault(key, len(seen))
+    return out
+
+
+def _rule_arrays(rules, k):
+    """(windows, limits) of blissgpu_radio: None (the whole list) is k + 1"""
+    rules = list(rules)
+    if len(rules) > _ffi.RADIO_MAX_RULES:
+        raise ValueError(f"at most {_ffi.RADIO_MAX_RULES} rules")
+    return [int(k) + 1 if r.window is None else int(r.window) for r in rules], [int(r.limit) for r in rules]
+
+
+def radio_order(from_rows, candidates, k, labels, windows, limits, from_labels=None, mode="chain", metric="euclidean", m=None,
+                skip=None):
+    """Radio playlists in one device call (blissgpu_radio): radio g starts at from_rows[g]; mode "chain": song 0 is the eligible
+    candidate nearest from_rows[g], song t the eligible candidate nearest song t - 1; mode "nearest": every song is the
+    eligible candidate nearest from_rows[g].  labels: [R, n] integers, one label per rule and candidate, -1 or 0xFFFFFFFF = no
+    label; from_labels: [G, R], the start songs' labels, or None (they carry none).  Rule r: among the last windows[r] songs of
+    the radio -- the start song is position -1, the picks follow -- at most limits[r] carry any one label; a candidate whose
+    label has reached that count is not eligible, nor is one already played or in `skip` ([G, 2] candidate indices, -1: none).
+    windows[r] == 0 switches the rule off, windows[r] > k is the whole list.  Equal distances go to the lower index.
+    -> (idx int64[G, k], dist float32[G, k]); a radio that runs out of eligible candidates ends in -1 / inf.  A NaN distance
+    of an eligible candidate raises ValueError.  VarianceWeights and ForestOptions are refused."""
+    _no_forest(metric, _RADIO_WHY)
+    _no_variance(metric, _RADIO_WHY)
+    A = np.ascontiguousarray(np.atleast_2d(from_rows), dtype=np.float32)
+    # (the same object for both: a radio from each candidate, and the library uploads the rows once)
+    X = A if candidates is from_rows else np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
+    if A.ndim != 2 or X.ndim != 2 or A.shape[1] != X.shape[1]:
+        raise ValueError("from_rows and candidates must be [G, d] and [n, d]")
+    if metric not in _METRICS:
+        raise ValueError(f"unknown metric {metric!r}")
+    if mode not in _RADIO_MODES:
+        raise ValueError('mode must be "chain" or "nearest"')
+    k = int(k)
+    if not 1 <= k <= 1024:
+        raise ValueError("k must be 1 .. 1024")
+    (G, d), n = A.shape, X.shape[0]
+    if not 1 <= d <= 64:
+        raise ValueError("d must be 1 .. 64")
+    windows = np.ascontiguousarray(np.asarray(windows, dtype=np.int64).reshape(-1))
+    limits = np.ascontiguousarray(np.asarray(limits, dtype=np.int64).reshape(-1))
+    R = windows.shape[0]
+    if limits.shape[0] != R:
+        raise ValueError("windows and limits must have one entry per rule")
+    if R > _ffi.RADIO_MAX_RULES:
+        raise ValueError(f"at most {_ffi.RADIO_MAX_RULES} rules")
+    if (windows < 0).any() or (limits < 1).any():
+        raise ValueError("windows must be >= 0 and limits >= 1")
+    windows = np.minimum(windows, k + 1).astype(np.uint32)
+    limits = np.minimum(limits, 0xFFFFFFFF).astype(np.uint32)
+    lab_p = fl_p = None
+    if R:
+        lab = np.asarray(labels, dtype=np.int64).reshape(R, -1) if np.size(labels) else np.zeros((R, 0), np.int64)
+        if lab.shape != (R, n):
+            raise ValueError("labels must be [rules, n]")
+        if ((lab < -1) | (lab > 0xFFFFFFFF)).any():
+            raise ValueError("labels must be -1 (none) or fit 32 bits")
+        lab = np.ascontiguousarray(np.where(lab < 0, NO_LABEL, lab).astype(np.uint32))
+        lab_p = lab.ctypes.data
+        if from_labels is not None:
+            fl = np.asarray(from_labels, dtype=np.int64)
+            if fl.shape != (G, R):
+                raise ValueError("from_labels must be [G, rules]")
+            if ((fl < -1) | (fl > 0xFFFFFFFF)).any():
+                raise ValueError("from_labels must be -1 (none) or fit 32 bits")
+            fl = np.ascontiguousarray(np.where(fl < 0, NO_LABEL, fl).astype(np.uint32))
+            fl_p = fl.ctypes.data
+    skip_p = None
+    if skip is not None:
+        skip = np.asarray(skip, dtype=np.int64)
+        if skip.shape != (G, 2):
+            raise ValueError("skip must be [G, 2]")
+        if ((skip < -1) | (skip >= n)).any():
+            raise ValueError("skip entries must be candidate indices or -1")
+        skip = np.ascontiguousarray(np.where(skip < 0, 0xFFFFFFFF, skip).astype(np.uint32))
+        skip_p = skip.ctypes.data
+    mp = None
+    if metric == "mahalanobis":
+        if m is None:
+            raise ValueError("mahalanobis needs m")
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        if m.shape != (d, d):
+            raise ValueError("m must be [d, d]")
+        mp = m.ctypes.data
+    idx, dist = np.empty((G, k), np.uint32), np.empty((G, k), np.float32)
+    try:
+        _ffi.check(_ffi.lib().blissgpu_radio(A.ctypes.data, G, X.ctypes.data, n, d, _METRICS[metric], mp, lab_p, fl_p, R,
+                                             windows.ctypes.data if R else None, limits.ctypes.data if R else None, skip_p, k,
+                                             _RADIO_MODES[mode], idx.ctypes.data, dist.ctypes.data))
+    except _ffi.BlissGpuError as e:
+        _nan_to_panic(e)
+    out = idx.astype(np.int64)
+    out[idx == 0xFFFFFFFF] = -1
+    return out, dist
+
+
+DEFAULT_RADIO_RULES = (Rule("artist", 5), Rule("album", 20))
+
+
+def radio_playlist(first_song, candidate_songs, number_songs, rules=DEFAULT_RADIO_RULES, mode="chain",
+                   metric_builder=euclidean_distance):
+    """A radio from one song: up to `number_songs` songs after first_song, each the nearest candidate not yet played (mode
+    "chain": nearest the song before it; "nearest": nearest first_song) that breaks none of `rules` -- by default no artist
+    twice within 5 tracks and no album twice within 20, first_song counting as the track before the first.  The radio ends
+    early when every remaining candidate is ruled out.  first_song is kept out of the pool (the first candidate that == it)
+    and is not part of the result."""
+    _no_forest(metric_builder, _RADIO_WHY)
+    _no_variance(metric_builder, _RADIO_WHY)
+    candidate_songs, rules = list(candidate_songs), list(rules)
+    if not candidate_songs:
+        return []
+    metric, m = _metric_of(metric_builder)
+    labels = rule_labels(candidate_songs + [first_song], rules)
+    windows, limits = _rule_arrays(rules, number_songs)
+    idx, _ = radio_order(_matrix([first_song]), _matrix(candidate_songs), number_songs, labels[:, :-1], windows, limits,
+                         labels[:, -1:].T, mode, metric, m, _end_point_skip([[first_song]], candidate_songs))
     return [candidate_songs[j] for j in idx[0] if j >= 0]
 
 

@@ -920,6 +920,49 @@ int blissgpu_journeys_device(blissgpu_ctx *ctx, const float *d_from, const float
                              uint64_t n, uint32_t d, int metric, const float *d_M, const uint32_t *d_skip, uint32_t k, int mode,
                              int gate, uint32_t gate_feature, uint32_t *d_idx, float *d_dist);
 
+/* ---- radio playlists: artist and album separation rules ----
+ * Every program built on the reference bolts the same rules onto its playlists on the host: no artist twice within w tracks,
+ * no album twice within w tracks, at most c songs per artist in a list.  A greedy chain cannot be filtered afterwards -- a
+ * banned pick changes every later step -- so the rules are part of the step here.  Radio g has a start row from[g] (d floats)
+ * and two skip slots skip[g][0 .. 2) as for blissgpu_journeys (0xFFFFFFFF = none; skip may be NULL).  Row g of idx / dist
+ * ([n_radios][k]; dist may be NULL) is the radio:
+ *   BLISSGPU_RADIO_CHAIN    the query of step 0 is from[g], the query of step t >= 1 is cand[idx[g][t - 1]] (song to song);
+ *   BLISSGPU_RADIO_NEAREST  the query of every step is from[g] (the k nearest songs under the rules).
+ * labels is [n_rules][n]: one label per rule and candidate (artist id, album id, ...); 0xFFFFFFFF = the song has no label and
+ * the rule never constrains it.  from_labels is [n_radios][n_rules], the start songs' labels; NULL = the starts carry none.
+ * window and limit (HOST arrays of n_rules, in both forms) state rule r: among the last window[r] songs of the radio at most
+ * limit[r] may carry any one label.  The history of radio g at step t is position -1 (the start, labelled from_labels[g][r])
+ * followed by positions 0 .. t - 1 (its picks).  Candidate j is eligible at step t when it is not in skip[g], not in
+ * idx[g][0 .. t), and for every rule r with window[r] >= 1 and L = labels[r][j] != 0xFFFFFFFF the number of history positions
+ * p with t - window[r] <= p < t that carry label L is < limit[r].  window[r] == 0 switches rule r off; window[r] > k behaves
+ * as k + 1 (the whole list and the start); limit[r] == 0 is BLISSGPU_ERR_INVALID.
+ * idx[g][t] is the eligible candidate j with the smallest 0.0f + metric(query, cand[j]) -- bit for bit what
+ * blissgpu_pairwise_device writes for the pair -- the lowest index among equal values (-0.0 and +0.0 are equal); dist[g][t] is
+ * that value.  When no candidate is eligible the radio ends: that step and every later one keep 0xFFFFFFFF / +inf.  An
+ * ineligible candidate's distance is never looked at; BLISSGPU_ERR_NAN exactly when a step that runs evaluates a NaN for an
+ * eligible candidate (the outputs are then unspecified).  Limits, metrics and M as for blissgpu_journeys (1 <= k <=
+ * BLISSGPU_KNN_MAX_K, 1 <= d <= 64, n < 2^32 - 1, n_radios < 2^31, a diagonal M is detected); n_rules <=
+ * BLISSGPU_RADIO_MAX_RULES; labels, window or limit NULL with n_rules > 0 is BLISSGPU_ERR_INVALID; the host form also refuses a
+ * skip entry >= n other than 0xFFFFFFFF.  All of this is checked before the device is touched.  n_radios == 0 or n == 0 is
+ * BLISSGPU_OK (n == 0: every row is padding).  With n_rules == 0 -- or every label 0xFFFFFFFF, every window 0, or limit[r] >
+ * window[r] without from_labels -- CHAIN is blissgpu_journeys(CHAIN, GATE_NONE) and NEAREST the first k entries of
+ * blissgpu_knn, bit for bit.  Two launches per step (three when few radios share the device); the workspace is 8 bytes per
+ * radio plus 4 (1 + max_r min(window[r], k) / limit[r]) bytes per radio and rule that can ban anything, counted against the
+ * context's workspace limit (BLISSGPU_ERR_OOM beyond it).  In the host form from == cand (the same pointer, n_radios <= n: a
+ * radio from each of the first n_radios candidates) uploads the rows once. */
+#define BLISSGPU_RADIO_MAX_RULES 4u
+#define BLISSGPU_RADIO_CHAIN 0
+#define BLISSGPU_RADIO_NEAREST 1
+int blissgpu_radio(const float *from, uint64_t n_radios, const float *cand, uint64_t n, uint32_t d, int metric, const float *M,
+                   const uint32_t *labels, const uint32_t *from_labels, uint32_t n_rules, const uint32_t *window,
+                   const uint32_t *limit, const uint32_t *skip, uint32_t k, int mode, uint32_t *idx, float *dist);
+/* Device-resident form (device pointers, d_labels, d_from_labels and d_skip included; window and limit stay HOST pointers);
+ * synchronises the context's stream before returning (the NaN check). */
+int blissgpu_radio_device(blissgpu_ctx *ctx, const float *d_from, uint64_t n_radios, const float *d_cand, uint64_t n, uint32_t d,
+                          int metric, const float *d_M, const uint32_t *d_labels, const uint32_t *d_from_labels, uint32_t n_rules,
+                          const uint32_t *window, const uint32_t *limit, const uint32_t *d_skip, uint32_t k, int mode,
+                          uint32_t *d_idx, float *d_dist);
+
 /* ---- duplicate songs of a whole collection ----
  * The duplicate rule of dedup_playlist_custom_distance (src/playlist.rs:381-388) applied to EVERY pair of the n x d matrix x
  * instead of the neighbours of an ordered playlist: the pair (i, j), i < j, is an edge when D[i][j] < threshold (D[i][j] is bit
