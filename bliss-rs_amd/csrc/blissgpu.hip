@@ -284,6 +284,22 @@ int is_diag(const float* M, uint32_t d) {
     return 1;
 }
 
+// *diag = whether the Mahalanobis matrix d_M [d][d] on the device is diagonal (0 for another metric).  Staged by a host form
+// (d_M == c->st_m.p): the host copy is at hand; otherwise it is copied back, which synchronises the stream
+int metric_is_diag(blissgpu_ctx* c, const float* d_M, uint32_t d, int metric, int* diag) {
+    *diag = 0;
+    if (metric != BLISSGPU_METRIC_MAHALANOBIS) return BLISSGPU_OK;
+    if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {
+        *diag = is_diag(c->m_cache.data(), d);
+    } else {
+        std::vector<float> hM((size_t)d * d);
+        HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        *diag = is_diag(hM.data(), d);
+    }
+    return BLISSGPU_OK;
+}
+
 }  // namespace
 
 // Locks the context for the duration of one entry point and selects its device.
@@ -497,16 +513,7 @@ int blissgpu_pairwise_device(blissgpu_ctx* c, const float* d_A, uint64_t n, cons
         return fail(BLISSGPU_ERR_INVALID, "blissgpu_pairwise_device", "mahalanobis needs M");
     CTX_ENTER(c, "blissgpu_pairwise_device");
     int diag = 0;
-    if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
-        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
-            diag = is_diag(c->m_cache.data(), d);
-        } else {
-            std::vector<float> hM((size_t)d * d);
-            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            diag = is_diag(hM.data(), d);
-        }
-    }
+    if (int e = metric_is_diag(c, d_M, d, metric, &diag)) return e;
     {
         Prof p(c, K_PAIRWISE);
         launch_pairwise(d_A, n, d_B, m, d, metric, d_M, diag, d_out, ld_out, c->stream);
@@ -888,95 +895,8 @@ static int knn_args_ok(const char* who, const void* queries, uint64_t q, const v
     return BLISSGPU_OK;
 }
 
-int blissgpu_knn_device(blissgpu_ctx* c, const float* d_queries, uint64_t q, const float* d_cand, uint64_t n, uint32_t d,
-                        int metric, const float* d_M, const uint32_t* d_skip, uint32_t k, uint32_t* d_idx, float* d_dist) {
-    const char* who = "blissgpu_knn_device";
-    int rc = knn_args_ok(who, d_queries, q, d_cand, n, d, metric, d_M, k, d_idx);
-    if (rc) return rc;
-    if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
-    if (q == 0) return BLISSGPU_OK;
-    CTX_ENTER(c, who);
-    int diag = 0;
-    if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
-        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
-            diag = is_diag(c->m_cache.data(), d);
-        } else {
-            std::vector<float> hM((size_t)d * d);
-            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            diag = is_diag(hM.data(), d);
-        }
-    }
-    // workspace: the sorted k best keys of every (query, split) -- O(q k), see knn_plan; no q x n tile exists anywhere
-    const KnnPlan plan = knn_plan(q, n, k, c->n_cus);
-    rc = c->pl_sync.ensure(4);
-    if (!rc) rc = c->pl_tmp.ensure((size_t)plan.part_keys * sizeof(unsigned long long));
-    if (rc) return rc;
-    unsigned long long* part = reinterpret_cast<unsigned long long*>(c->pl_tmp.p);
-    // pl_sync: [1] NaN among the evaluated distances, [3] a skip entry >= n
-    HIP_TRY(hipMemsetAsync(c->pl_sync.p, 0, 4 * sizeof(uint32_t), c->stream));
-    {
-        Prof p(c, K_KNN_SCAN);
-        launch_knn_scan(d_queries, q, d_cand, (uint32_t)n, d, metric, d_M, diag, d_skip, k, plan, part, c->pl_sync.p + 1,
-                        c->pl_sync.p + 3, c->stream);
-    }
-    HIP_TRY(hipGetLastError());
-    {
-        Prof p(c, K_KNN_MERGE);
-        launch_knn_merge(part, q, k, plan, d_idx, d_dist, c->stream);
-    }
-    HIP_TRY(hipGetLastError());
-    uint32_t flags[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(flags, c->pl_sync.p, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (flags[3]) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
-    if (flags[1]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance (the reference panics here)");
-    return BLISSGPU_OK;
-}
-
-int blissgpu_knn(const float* queries, uint64_t q, const float* cand, uint64_t n, uint32_t d, int metric, const float* M,
-                 const uint32_t* skip, uint32_t k, uint32_t* idx, float* dist) {
-    const char* who = "blissgpu_knn";
-    int rc = knn_args_ok(who, queries, q, cand, n, d, metric, M, k, idx);
-    if (rc) return rc;
-    if (skip)
-        for (uint64_t i = 0; i < q; i++)
-            if (skip[i] != 0xFFFFFFFFu && skip[i] >= n) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
-    if (q == 0) return BLISSGPU_OK;
-    blissgpu_ctx* c;
-    rc = default_ctx(&c);
-    if (rc) return rc;
-    CTX_ENTER(c, who);
-    // queries that ARE the candidate matrix (the similar-songs table of a library) travel once
-    const bool shared = queries == cand && q <= n;
-    const size_t out_n = (size_t)q * k;
-    const float* dM = nullptr;
-    rc = c->st_b.ensure(std::max<size_t>(1, n * d));
-    if (!rc && !shared) rc = c->st_a.ensure(q * d);
-    if (!rc) rc = c->st_idx.ensure(out_n + (skip ? q : 0));
-    if (!rc && dist) rc = c->st_dist.ensure(out_n);
-    if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
-    if (rc) return rc;
-    const float* dQ = shared ? c->st_b.p : c->st_a.p;
-    uint32_t *d_idx = c->st_idx.p, *d_skip = skip ? c->st_idx.p + out_n : nullptr;
-    hipError_t e = hipSuccess;
-    if (n) e = hipMemcpyAsync(c->st_b.p, cand, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && !shared) e = hipMemcpyAsync(c->st_a.p, queries, q * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && skip) e = hipMemcpyAsync(d_skip, skip, q * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(knn)", hipGetErrorString(e));
-    if (!rc) rc = blissgpu_knn_device(c, dQ, q, c->st_b.p, n, d, metric, dM, d_skip, k, d_idx, dist ? c->st_dist.p : nullptr);
-    if (!rc) {
-        e = hipMemcpyAsync(idx, d_idx, out_n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(knn)", hipGetErrorString(e));
-    }
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
-}
-
-// ---- locally scaled k nearest candidates per query: blissgpu_knn's selection under dist / sqrtf(qscale[i] * cscale[j]), the cure
-// for hubs (kernels_scaled_knn.hip); knn_plan's split, knn_merge_kernel's merge, no q x n matrix ----
+// locally scaled: blissgpu_knn's selection under dist / sqrtf(qscale[i] * cscale[j]), the cure for hubs (kernels_scaled_knn.hip,
+// DESIGN.md 3.27); the same scan, split and merge
 static int scaled_knn_args_ok(const char* who, const void* queries, uint64_t q, const void* qscale, const void* cand, uint64_t n,
                               const void* cscale, uint32_t d, int metric, const float* M, uint32_t k, const void* idx) {
     int rc = knn_args_ok(who, queries, q, cand, n, d, metric, M, k, idx);
@@ -986,38 +906,31 @@ static int scaled_knn_args_ok(const char* who, const void* queries, uint64_t q, 
     return BLISSGPU_OK;
 }
 
-int blissgpu_scaled_knn_device(blissgpu_ctx* c, const float* d_queries, uint64_t q, const float* d_qscale, const float* d_cand,
-                               uint64_t n, const float* d_cscale, uint32_t d, int metric, const float* d_M, const uint32_t* d_skip,
-                               uint32_t k, uint32_t* d_idx, float* d_dist) {
-    const char* who = "blissgpu_scaled_knn_device";
-    int rc = scaled_knn_args_ok(who, d_queries, q, d_qscale, d_cand, n, d_cscale, d, metric, d_M, k, d_idx);
-    if (rc) return rc;
+// the device form of both searches, their arguments checked; d_qscale == NULL: the plain one (d_cscale is then not looked at)
+static int knn_run(blissgpu_ctx* c, const char* who, const float* d_queries, uint64_t q, const float* d_qscale, const float* d_cand,
+                   uint64_t n, const float* d_cscale, uint32_t d, int metric, const float* d_M, const uint32_t* d_skip, uint32_t k,
+                   uint32_t* d_idx, float* d_dist) {
     if (!c) return fail(BLISSGPU_ERR_INVALID, who, "ctx is NULL");
     if (q == 0) return BLISSGPU_OK;
     CTX_ENTER(c, who);
     int diag = 0;
-    if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
-        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
-            diag = is_diag(c->m_cache.data(), d);
-        } else {
-            std::vector<float> hM((size_t)d * d);
-            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            diag = is_diag(hM.data(), d);
-        }
-    }
-    // workspace: the sorted k best keys of every (query, split) -- O(q k), as for blissgpu_knn_device
+    if (int e = metric_is_diag(c, d_M, d, metric, &diag)) return e;
+    // workspace: the sorted k best keys of every (query, split) -- O(q k), see knn_plan; no q x n tile exists anywhere
     const KnnPlan plan = knn_plan(q, n, k, c->n_cus);
-    rc = c->pl_sync.ensure(4);
+    int rc = c->pl_sync.ensure(4);
     if (!rc) rc = c->pl_tmp.ensure((size_t)plan.part_keys * sizeof(unsigned long long));
     if (rc) return rc;
     unsigned long long* part = reinterpret_cast<unsigned long long*>(c->pl_tmp.p);
     // pl_sync: [1] NaN among the evaluated distances, [2] a scale outside [2^-60, 2^60], [3] a skip entry >= n
     HIP_TRY(hipMemsetAsync(c->pl_sync.p, 0, 4 * sizeof(uint32_t), c->stream));
     {
-        Prof p(c, KX_SCALED_KNN_SCAN);
-        launch_scaled_knn_scan(d_queries, q, d_qscale, d_cand, (uint32_t)n, d_cscale, d, metric, d_M, diag, d_skip, k, plan, part,
-                               c->pl_sync.p + 1, c->pl_sync.p + 3, c->pl_sync.p + 2, c->stream);
+        Prof p(c, d_qscale ? KX_SCALED_KNN_SCAN : K_KNN_SCAN);
+        if (d_qscale)
+            launch_scaled_knn_scan(d_queries, q, d_qscale, d_cand, (uint32_t)n, d_cscale, d, metric, d_M, diag, d_skip, k, plan, part,
+                                   c->pl_sync.p + 1, c->pl_sync.p + 3, c->pl_sync.p + 2, c->stream);
+        else
+            launch_knn_scan(d_queries, q, d_cand, (uint32_t)n, d, metric, d_M, diag, d_skip, k, plan, part, c->pl_sync.p + 1,
+                            c->pl_sync.p + 3, c->stream);
     }
     HIP_TRY(hipGetLastError());
     {
@@ -1034,51 +947,81 @@ int blissgpu_scaled_knn_device(blissgpu_ctx* c, const float* d_queries, uint64_t
     return BLISSGPU_OK;
 }
 
-int blissgpu_scaled_knn(const float* queries, uint64_t q, const float* qscale, const float* cand, uint64_t n, const float* cscale,
-                        uint32_t d, int metric, const float* M, const uint32_t* skip, uint32_t k, uint32_t* idx, float* dist) {
-    const char* who = "blissgpu_scaled_knn";
-    int rc = scaled_knn_args_ok(who, queries, q, qscale, cand, n, cscale, d, metric, M, k, idx);
-    if (rc) return rc;
+// the host form of both, their arguments checked; qscale == NULL: the plain one.  run_who: the device form's name
+static int knn_host(const char* who, const char* run_who, const float* queries, uint64_t q, const float* qscale, const float* cand,
+                    uint64_t n, const float* cscale, uint32_t d, int metric, const float* M, const uint32_t* skip, uint32_t k,
+                    uint32_t* idx, float* dist) {
     if (skip)
         for (uint64_t i = 0; i < q; i++)
             if (skip[i] != 0xFFFFFFFFu && skip[i] >= n) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
     if (q == 0) return BLISSGPU_OK;
     blissgpu_ctx* c;
-    rc = default_ctx(&c);
+    int rc = default_ctx(&c);
     if (rc) return rc;
     CTX_ENTER(c, who);
-    // queries that ARE the candidate matrix, with the same scales, travel once: st_b = cand | cscale, st_a = queries | qscale
-    const bool shared = queries == cand && qscale == cscale && q <= n;
+    // queries that ARE the candidate matrix (the similar-songs table of a library), with the same scales, travel once:
+    // st_b = cand | cscale, st_a = queries | qscale
+    const bool scaled = qscale != nullptr, shared = queries == cand && qscale == cscale && q <= n;
     const size_t out_n = (size_t)q * k;
     const float* dM = nullptr;
-    rc = c->st_b.ensure(std::max<size_t>(1, n * d + n));
-    if (!rc && !shared) rc = c->st_a.ensure(q * d + q);
+    rc = c->st_b.ensure(std::max<size_t>(1, n * d + (scaled ? n : 0)));
+    if (!rc && !shared) rc = c->st_a.ensure(q * d + (scaled ? q : 0));
     if (!rc) rc = c->st_idx.ensure(out_n + (skip ? q : 0));
     if (!rc && dist) rc = c->st_dist.ensure(out_n);
     if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
     if (rc) return rc;
     const float* dQ = shared ? c->st_b.p : c->st_a.p;
-    float* d_cs = c->st_b.p + n * d;
-    const float* d_qs = shared ? d_cs : c->st_a.p + q * d;
+    float* d_cs = scaled ? c->st_b.p + n * d : nullptr;
+    const float* d_qs = !scaled ? nullptr : shared ? d_cs : c->st_a.p + q * d;
     uint32_t *d_idx = c->st_idx.p, *d_skip = skip ? c->st_idx.p + out_n : nullptr;
     hipError_t e = hipSuccess;
     if (n) e = hipMemcpyAsync(c->st_b.p, cand, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && n) e = hipMemcpyAsync(d_cs, cscale, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && scaled && n) e = hipMemcpyAsync(d_cs, cscale, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && !shared) e = hipMemcpyAsync(c->st_a.p, queries, q * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && !shared) e = hipMemcpyAsync(c->st_a.p + q * d, qscale, q * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && scaled && !shared)
+        e = hipMemcpyAsync(c->st_a.p + q * d, qscale, q * sizeof(float), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && skip) e = hipMemcpyAsync(d_skip, skip, q * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(scaled_knn)", hipGetErrorString(e));
-    if (!rc)
-        rc = blissgpu_scaled_knn_device(c, dQ, q, d_qs, c->st_b.p, n, d_cs, d, metric, dM, d_skip, k, d_idx,
-                                        dist ? c->st_dist.p : nullptr);
+    if (e != hipSuccess)
+        rc = fail(BLISSGPU_ERR_HIP, scaled ? "hipMemcpyAsync(scaled_knn)" : "hipMemcpyAsync(knn)", hipGetErrorString(e));
+    if (!rc) rc = knn_run(c, run_who, dQ, q, d_qs, c->st_b.p, n, d_cs, d, metric, dM, d_skip, k, d_idx, dist ? c->st_dist.p : nullptr);
     if (!rc) {
         e = hipMemcpyAsync(idx, d_idx, out_n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(scaled_knn)", hipGetErrorString(e));
+        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, scaled ? "copy back(scaled_knn)" : "copy back(knn)", hipGetErrorString(e));
     }
     (void)hipStreamSynchronize(c->stream);
     return rc;
+}
+
+int blissgpu_knn_device(blissgpu_ctx* c, const float* d_queries, uint64_t q, const float* d_cand, uint64_t n, uint32_t d,
+                        int metric, const float* d_M, const uint32_t* d_skip, uint32_t k, uint32_t* d_idx, float* d_dist) {
+    const char* who = "blissgpu_knn_device";
+    const int rc = knn_args_ok(who, d_queries, q, d_cand, n, d, metric, d_M, k, d_idx);
+    return rc ? rc : knn_run(c, who, d_queries, q, nullptr, d_cand, n, nullptr, d, metric, d_M, d_skip, k, d_idx, d_dist);
+}
+
+int blissgpu_knn(const float* queries, uint64_t q, const float* cand, uint64_t n, uint32_t d, int metric, const float* M,
+                 const uint32_t* skip, uint32_t k, uint32_t* idx, float* dist) {
+    const char* who = "blissgpu_knn";
+    const int rc = knn_args_ok(who, queries, q, cand, n, d, metric, M, k, idx);
+    return rc ? rc : knn_host(who, "blissgpu_knn_device", queries, q, nullptr, cand, n, nullptr, d, metric, M, skip, k, idx, dist);
+}
+
+int blissgpu_scaled_knn_device(blissgpu_ctx* c, const float* d_queries, uint64_t q, const float* d_qscale, const float* d_cand,
+                               uint64_t n, const float* d_cscale, uint32_t d, int metric, const float* d_M, const uint32_t* d_skip,
+                               uint32_t k, uint32_t* d_idx, float* d_dist) {
+    const char* who = "blissgpu_scaled_knn_device";
+    const int rc = scaled_knn_args_ok(who, d_queries, q, d_qscale, d_cand, n, d_cscale, d, metric, d_M, k, d_idx);
+    return rc ? rc : knn_run(c, who, d_queries, q, d_qscale, d_cand, n, d_cscale, d, metric, d_M, d_skip, k, d_idx, d_dist);
+}
+
+int blissgpu_scaled_knn(const float* queries, uint64_t q, const float* qscale, const float* cand, uint64_t n, const float* cscale,
+                        uint32_t d, int metric, const float* M, const uint32_t* skip, uint32_t k, uint32_t* idx, float* dist) {
+    const char* who = "blissgpu_scaled_knn";
+    const int rc = scaled_knn_args_ok(who, queries, q, qscale, cand, n, cscale, d, metric, M, k, idx);
+    return rc ? rc
+              : knn_host(who, "blissgpu_scaled_knn_device", queries, q, qscale, cand, n, cscale, d, metric, M, skip, k, idx, dist);
 }
 
 // ---- k-occurrence: how many lists of an index matrix every song is in (the counts hubness is measured on) ----
@@ -1185,16 +1128,7 @@ int blissgpu_kmeans_device(blissgpu_ctx* c, const float* d_x, uint64_t n, uint32
         return BLISSGPU_OK;
     }
     int diag = 0;
-    if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
-        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
-            diag = is_diag(c->m_cache.data(), d);
-        } else {
-            std::vector<float> hM((size_t)d * d);
-            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            diag = is_diag(hM.data(), d);
-        }
-    }
+    if (int e = metric_is_diag(c, d_M, d, metric, &diag)) return e;
     // workspace, O(n + K d + chunks x K): flags u32[4] ([0] labels that moved, [1] NaN) | hist u32[K][W] | scan totals | arow_off
     // u32[K + 1] | arow u32[n] | centres f32[2][K][d]
     const KmeansPlan plan = kmeans_plan(n, k, c->n_cus);
@@ -1335,16 +1269,7 @@ int blissgpu_silhouette_device(blissgpu_ctx* c, const float* d_x, uint64_t n, ui
     }
     if (q == 0) return BLISSGPU_OK;
     int diag = 0;
-    if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
-        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
-            diag = is_diag(c->m_cache.data(), d);
-        } else {
-            std::vector<float> hM((size_t)d * d);
-            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            diag = is_diag(hM.data(), d);
-        }
-    }
+    if (int e = metric_is_diag(c, d_M, d, metric, &diag)) return e;
     // workspace, O(n + chunks x K + q Y): flags u32[4] ([0] NaN, [1] SIL_ERR_*) | hist u32[K][W] | scan totals | arow_off u32[K + 1]
     // | arow u32[n] | (8-byte aligned) own sums f64[Y][q] | best quotients f64[Y][q] | their clusters u32[Y][q]: 20 q Y bytes
     const KmeansPlan sort = kmeans_plan(n, k, c->n_cus);
@@ -1473,16 +1398,7 @@ int blissgpu_group_neighbours_device(blissgpu_ctx* c, const float* d_x, uint64_t
     if (q == 0 && !d_sizes && !d_matrix) return BLISSGPU_OK;  // no row to answer and nothing else asked for
     const bool pairs = n && (q || d_matrix);                  // whether any distance is evaluated
     int diag = 0;
-    if (pairs && metric == BLISSGPU_METRIC_MAHALANOBIS) {
-        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
-            diag = is_diag(c->m_cache.data(), d);
-        } else {
-            std::vector<float> hM((size_t)d * d);
-            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            diag = is_diag(hM.data(), d);
-        }
-    }
+    if (int e = pairs ? metric_is_diag(c, d_M, d, metric, &diag) : 0) return e;
     // workspace: flags u32[4] ([0] NaN, [1] CH_ERR_*) | hist u32[K][W] | scan totals | arow_off u32[K + 1] | arow u32[n] | (8-byte
     // aligned) D f64[K][K] | row buffers f64[select grid][K] | minima f32[slab][n]
     KmeansPlan sort{};
@@ -1606,16 +1522,7 @@ static int mst_args_ok(const char* who, const void* x, uint64_t n, uint32_t d, i
 static int mst_run(blissgpu_ctx* c, const char* who, const float* d_x, uint64_t n, uint32_t d, int metric, const float* d_M,
                    const float* d_core, MstState& st) {
     int diag = 0;
-    if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
-        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
-            diag = is_diag(c->m_cache.data(), d);
-        } else {
-            std::vector<float> hM((size_t)d * d);
-            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            diag = is_diag(hM.data(), d);
-        }
-    }
+    if (int e = metric_is_diag(c, d_M, d, metric, &diag)) return e;
     // (for the tests and the bench tool: no bit of the result depends on either)
     uint32_t col_groups = 0, skip = 1;
     if (const char* e = getenv("BLISSGPU_MST_COL_GROUPS")) col_groups = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 65535ul);
@@ -2167,16 +2074,7 @@ static int group_knn_run(blissgpu_ctx* c, const char* who, const float* d_seeds,
     if (weighted) {
         metric = BLISSGPU_METRIC_MAHALANOBIS;
         diag = GROUP_KNN_M_PER_GROUP;
-    } else if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
-        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
-            diag = is_diag(c->m_cache.data(), d);
-        } else {
-            std::vector<float> hM((size_t)d * d);
-            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            diag = is_diag(hM.data(), d);
-        }
-    }
+    } else if (int e = metric_is_diag(c, d_M, d, metric, &diag)) return e;
     // the plan and its tables: group offsets (32 bits: fewer than 2^32 seeds) | list offsets | items.  Workspace: the sorted k
     // best keys of every (group, item that covers it) -- no seeds x n or groups x n array exists anywhere
     const GroupKnnPlan plan = group_knn_plan(group_offsets, n_groups, n, k, (uint32_t)std::max(1, c->n_cus));
@@ -2697,16 +2595,7 @@ int blissgpu_chains_device(blissgpu_ctx* c, const float* d_seeds, const uint64_t
     if (route == BLISSGPU_CHAINS_AUTO) route = chains_route(n_groups, n, k, L, c->ws_limit);
     if (k < 2 || n == 0) route = BLISSGPU_CHAINS_STEPS;  // (step 0 alone: nothing to walk)
     int diag = 0;
-    if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
-        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
-            diag = is_diag(c->m_cache.data(), d);
-        } else {
-            std::vector<float> hM((size_t)d * d);
-            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            diag = is_diag(hM.data(), d);
-        }
-    }
+    if (int e = metric_is_diag(c, d_M, d, metric, &diag)) return e;
     // pl_chain: minima u64[G] | flags u32[4] ([0] NaN on a chain, [1] a list too short) | offsets u32[G + 1] | step 0: idx u32[G],
     // dist f32[G] | lists route: the candidates' own indices u32[n], lists u32[n][L], their distances f32[n][L]
     const size_t G = (size_t)n_groups, out_n = G * k;
@@ -2860,16 +2749,7 @@ int blissgpu_journeys_device(blissgpu_ctx* c, const float* d_from, const float* 
     if (n_journeys == 0) return BLISSGPU_OK;
     CTX_ENTER(c, who);
     int diag = 0;
-    if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
-        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
-            diag = is_diag(c->m_cache.data(), d);
-        } else {
-            std::vector<float> hM((size_t)d * d);
-            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            diag = is_diag(hM.data(), d);
-        }
-    }
+    if (int e = metric_is_diag(c, d_M, d, metric, &diag)) return e;
     // pl_chain: minima u64[G] | flags u32[4] ([0] NaN on a journey)
     const size_t G = (size_t)n_journeys, out_n = G * k;
     rc = c->pl_chain.ensure(G * sizeof(unsigned long long) + 4 * sizeof(uint32_t));
@@ -2996,16 +2876,7 @@ int blissgpu_radio_device(blissgpu_ctx* c, const float* d_from, uint64_t n_radio
     if (n_radios == 0) return BLISSGPU_OK;
     CTX_ENTER(c, who);
     int diag = 0;
-    if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
-        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
-            diag = is_diag(c->m_cache.data(), d);
-        } else {
-            std::vector<float> hM((size_t)d * d);
-            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            diag = is_diag(hM.data(), d);
-        }
-    }
+    if (int e = metric_is_diag(c, d_M, d, metric, &diag)) return e;
     const RadioRules rules = radio_rules(n_rules, window, limit, k);
     // pl_chain: minima u64[G] | flags u32[4] ([0] NaN) | ban counts u32[G * rules] | banned labels u32[G * rules * cap]
     const uint64_t G = n_radios, out_n = G * k, work = G * rules.n;
@@ -3125,16 +2996,7 @@ int blissgpu_duplicate_groups_device(blissgpu_ctx* c, const float* d_x, uint64_t
         return BLISSGPU_OK;
     }
     int diag = 0;
-    if (metric == BLISSGPU_METRIC_MAHALANOBIS) {
-        if (d_M == c->st_m.p && c->m_cache.size() == (size_t)d * d) {  // staged by a host form: the host copy is at hand
-            diag = is_diag(c->m_cache.data(), d);
-        } else {
-            std::vector<float> hM((size_t)d * d);
-            HIP_TRY(hipMemcpyAsync(hM.data(), d_M, hM.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            diag = is_diag(hM.data(), d);
-        }
-    }
+    if (int e = metric_is_diag(c, d_M, d, metric, &diag)) return e;
     // workspace: none but the caller's label array (the union-find's parents) and pair buffer, and eight words of the context
     // -- pl_sync: [1] NaN among the distances of the pairs i < j, [4..5] the pair list's cursor
     rc = c->pl_sync.ensure(8);

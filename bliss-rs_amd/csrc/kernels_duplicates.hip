@@ -36,6 +36,7 @@
 #include "internal.hpp"
 #include "pairwise_math.hpp"
 #include "playlist_math.hpp"
+#include "scan_block.hpp"
 
 namespace bg {
 
@@ -114,9 +115,9 @@ __global__ __launch_bounds__(256, 2) void dup_join_kernel(const float* __restric
                                                           float* __restrict__ pair_dist, uint64_t max_pairs,
                                                           uint32_t* nan_flag) {
     constexpr bool GENERIC = D == 0;
-    constexpr int DQ = GENERIC ? PL_DMAX : ((D + 3) & ~3);  // LDS pitch of a row: 16-byte aligned -> ds_read_b128 broadcasts
-    constexpr int XP = GENERIC ? 1 : (D | 1);               // LDS pitch of a staged candidate: odd, lanes l and l + 1 on different banks
-    constexpr bool FLAT = XP == D;
+    static_assert(DUP_TILE == KNN_COLS, "the tile's candidates are one block of scan_block.hpp");
+    constexpr int DQ = GENERIC ? PL_DMAX : scan_pitch<D>::DQ;
+    constexpr int XP = scan_pitch<D>::XP;
     constexpr bool ROOT = !GENERIC && METRIC != METRIC_COSINE;  // the bound is on the sum before the square root
     __shared__ __attribute__((aligned(16))) float s_q[DUP_TILE][DQ];
     __shared__ __attribute__((aligned(16))) float s_x[GENERIC ? 4 : DUP_TILE * XP];
@@ -132,16 +133,9 @@ __global__ __launch_bounds__(256, 2) void dup_join_kernel(const float* __restric
     bool saw_nan = false;
 
     if (tid == 0) s_edges = 0ull;
-    if (!GENERIC && METRIC == METRIC_MAHALANOBIS) {
-        for (int e = tid; e < D * D; e += 256) s_m[e] = M[e];
-    }
-    __syncthreads();  // s_edges and M are in place, also for a workgroup whose every work item turns out empty
     float wdiag[GENERIC ? 1 : D];
-    if constexpr (!GENERIC) {
-#pragma unroll
-        for (int kk = 0; kk < D; kk++)  // (the same in every lane: scalar registers)
-            wdiag[kk] = DIAG ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(s_m[(kk * D + kk) % (METRIC == METRIC_MAHALANOBIS ? D * D : 1)]))) : 0.0f;
-    }
+    if constexpr (!GENERIC) scan_load_metric<D, METRIC, DIAG>(M, s_m, wdiag, tid);
+    __syncthreads();  // s_edges and M are in place, also for a workgroup whose every work item turns out empty
 
     for (uint64_t w = blockIdx.x; w < n_work; w += gridDim.x) {
         uint32_t I, J;
@@ -157,23 +151,8 @@ __global__ __launch_bounds__(256, 2) void dup_join_kernel(const float* __restric
         __syncthreads();  // every wavefront has finished with the previous tile
         for (uint32_t e = (uint32_t)tid; e < rows_here * d; e += 256u) s_q[e / d][e % d] = X[(uint64_t)i0 * d + e];
         if ((uint32_t)tid < rows_here) s_qmeta[tid] = meta ? meta[i0 + (uint32_t)tid] : 0u;
-        if constexpr (!GENERIC) {
-            const float* src = X + (uint64_t)j0 * D;
-            const uint32_t floats = cols_here * (uint32_t)D;
-            if (FLAT && (reinterpret_cast<uintptr_t>(X) & 15u) == 0) {  // (a block starts 256 * D * 4 bytes after the last: 16-byte aligned too)
-                const float4* src4 = reinterpret_cast<const float4*>(src);
-                float4* dst4 = reinterpret_cast<float4*>(s_x);
-                for (uint32_t e = (uint32_t)tid; e < floats / 4u; e += 256u) dst4[e] = src4[e];
-                if ((uint32_t)tid < (floats & 3u)) s_x[(floats & ~3u) + (uint32_t)tid] = src[(floats & ~3u) + (uint32_t)tid];
-            } else if (FLAT) {
-                for (uint32_t e = (uint32_t)tid; e < floats; e += 256u) s_x[e] = src[e];
-            } else {
-                for (uint32_t e = (uint32_t)tid; e < floats; e += 256u) s_x[(e / (uint32_t)D) * XP + e % (uint32_t)D] = src[e];
-            }
-            // a ragged last block: zero rows, so that the lanes beyond it compute on defined values (their results are dropped)
-            for (uint32_t e = cols_here * (uint32_t)XP + (uint32_t)tid; e < (uint32_t)(DUP_TILE * XP); e += 256u) s_x[e] = 0.0f;
-        }
-        __syncthreads();
+        if constexpr (GENERIC) __syncthreads();
+        else scan_stage_block<D>(s_x, X, j0, cols_here, tid);  // (its closing barrier: the rows and their keys are in place too)
         if (!GENERIC && METRIC == METRIC_COSINE) {
             if ((uint32_t)tid < rows_here) {
                 const float* a = s_q[tid];
@@ -222,20 +201,8 @@ __global__ __launch_bounds__(256, 2) void dup_join_kernel(const float* __restric
                 }
             } else {
                 f2 ap[DQ / 2];
-#pragma unroll
-                for (int k4 = 0; k4 < DQ / 4; k4++) {  // same address in every lane: LDS broadcast
-                    const float4 v = *reinterpret_cast<const float4*>(&s_q[r][4 * k4]);
-                    ap[2 * k4].x = v.x; ap[2 * k4].y = v.y; ap[2 * k4 + 1].x = v.z; ap[2 * k4 + 1].y = v.w;
-                }
-                f2 s0 = pair_sum<(GENERIC ? 1 : D), METRIC, DIAG>(ap, bp[0], wdiag, s_m);
-                // (general M: one pair's 2 x d differences and products at a time, as in the k-nearest scan)
-                if (METRIC == METRIC_MAHALANOBIS && !DIAG) asm volatile("" : "+v"(s0));
-                f2 s1 = pair_sum<(GENERIC ? 1 : D), METRIC, DIAG>(ap, bp[1], wdiag, s_m);
-                if (METRIC == METRIC_COSINE) {
-                    s0 = splat(1.0f) - s0 / (splat(s_nq[r]) * nb2[0]);
-                    s1 = splat(1.0f) - s1 / (splat(s_nq[r]) * nb2[1]);
-                }
-                pv[0] = s0.x; pv[1] = s0.y; pv[2] = s1.x; pv[3] = s1.y;
+                scan_query_row<DQ>(s_q[r], ap);
+                scan_pair_values<D, METRIC, DIAG>(ap, bp, nb2, s_nq[r], wdiag, s_m, pv);
             }
             // wave-uniform: can any of the wavefront's 256 candidates be an edge of row i?  (a NaN says yes)
             bool maybe;

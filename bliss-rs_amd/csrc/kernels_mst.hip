@@ -36,6 +36,7 @@
 #include "internal.hpp"
 #include "pairwise_math.hpp"
 #include "playlist_math.hpp"
+#include "scan_block.hpp"
 
 namespace bg {
 
@@ -198,11 +199,7 @@ __global__ __launch_bounds__(256) void mst_scan_kernel(const MstArgs a) {
                 }
             } else {
                 f2 ap[DQ / 2];
-#pragma unroll
-                for (int k4 = 0; k4 < DQ / 4; k4++) {  // same address in every lane: LDS broadcast
-                    const float4 v = *reinterpret_cast<const float4*>(&s_c[r * (uint32_t)DQ + 4u * (uint32_t)k4]);
-                    ap[2 * k4].x = v.x; ap[2 * k4].y = v.y; ap[2 * k4 + 1].x = v.z; ap[2 * k4 + 1].y = v.w;
-                }
+                scan_query_row<DQ>(&s_c[r * (uint32_t)DQ], ap);
                 const uint32_t rc = ms_uniform(__float_as_uint((D & 1) ? ap[D / 2].y : ap[D / 2].x));  // feature slot D: the row's component
                 f2 sum0 = pair_sum<DD, METRIC, DIAG>(ap, bp[0], wdiag, s_m);
                 // (general M: one pair's 2 x d differences and products at a time, as in the k-nearest scan)

@@ -412,3 +412,57 @@ def test_not_slower_than_the_parent_route(bliss, ctx):
     t_knn, t_route = float(np.median(t_knn)), float(np.median(t_route))
     print(f"knn {t_knn * 1e3:.1f} ms, parent route {t_route * 1e3:.1f} ms")
     assert t_knn <= t_route
+
+
+# ---- (i) a candidate matrix that does not start on a 16-byte boundary: the scalar copy of an odd-d block (d = 23) ----
+def test_unaligned_candidates(ctx, oracle):
+    """the same values as a fresh tensor (16-byte aligned: float4 copies of a block) and as a view that starts one float into
+    an allocation (the flat scalar copy): a full block plus a ragged block of one row, and a single ragged block.  Through the
+    k-nearest scan, the locally scaled one and one chain step: three kernels that each carry their own copy of the staging text"""
+    import torch
+
+    d, q, k = 23, 5, 3
+    rng = np.random.default_rng(11)
+
+    def pair(X):
+        aligned = torch.from_numpy(X).cuda()
+        buf = torch.empty(X.size + 1, dtype=torch.float32, device="cuda")
+        offset = buf[1:].view(X.shape)
+        offset.copy_(aligned)
+        for t, want in ((aligned, True), (offset, False)):  # (what the Python layer passes on: contiguous() of a contiguous view)
+            assert (t.data_ptr() % 16 == 0) == want and (t.contiguous().data_ptr() % 16 == 0) == want
+        return aligned, offset
+
+    def out(res):
+        ctx.synchronize()
+        return res[0].cpu().numpy().astype(np.int64), res[1].cpu().numpy()
+
+    for n in (257, 255):
+        X, Q = tie_rich(rng, n, d), tie_rich(rng, q, d)
+        tQ = torch.from_numpy(Q).cuda()
+        for metric in ("euclidean", "cosine"):
+            Dm = oracle.pairwise(Q, X, metric, None, n_threads=16)
+            want = expected_from_matrix(Dm, k)
+            for name, tX in zip(("aligned", "offset"), pair(X)):
+                assert_same(out(ctx.knn(tQ, tX, k, metric)), want, (n, metric, name))
+            if (n, metric) != (257, "euclidean"):
+                continue
+            # the locally scaled scan: the contract of tests/test_gpu_scaled_knn.py::scaled_matrix in float32 numpy
+            qs, cs = rng.uniform(0.5, 2.0, q).astype(np.float32), rng.uniform(0.5, 2.0, n).astype(np.float32)
+            want = expected_from_matrix(Dm / np.sqrt(qs[:, None] * cs[None, :]), k)
+            assert want[1].dtype == np.float32
+            for name, tX in zip(("aligned", "offset"), pair(X)):
+                got = out(ctx.scaled_knn(tQ, torch.from_numpy(qs).cuda(), tX, torch.from_numpy(cs).cuda(), k, metric))
+                assert_same(got, want, (n, "scaled", name))
+            # two chains of one seed each, two songs: the song nearest the seed, then one step -- the song nearest that one
+            # which is not taken (equal distances to the lower index; `0.0f +` a distance, as the chain kernels add)
+            idx, dist = np.zeros((2, 2), np.int64), np.zeros((2, 2), np.float32)
+            for g in range(2):
+                idx[g, 0] = np.argsort(Dm[g], kind="stable")[0]
+                dist[g, 0] = np.float32(0.0) + Dm[g, idx[g, 0]]
+                row = oracle.pairwise(X[idx[g, 0]:idx[g, 0] + 1], X, metric, None)[0]
+                order = np.argsort(row, kind="stable")
+                idx[g, 1] = order[order != idx[g, 0]][0]
+                dist[g, 1] = np.float32(0.0) + row[idx[g, 1]]
+            for name, tX in zip(("aligned", "offset"), pair(X)):
+                assert_same(out(ctx.chains(tQ[:2], [0, 1, 2], tX, 2, metric, route="steps")), (idx, dist), (n, "chain", name))
