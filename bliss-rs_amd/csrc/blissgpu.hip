@@ -544,6 +544,103 @@ int stage_matrix(blissgpu_ctx* c, const float* M, uint32_t d, int metric, const 
     return BLISSGPU_OK;
 }
 
+// The copies of one host-pointer form around its device form: inputs up, results down, the first HIP error
+// kept and reported under the family's tag.  An absent array (NULL) and an empty one (0 bytes) are not copied.
+struct HostStage {
+    blissgpu_ctx* c;
+    const char* tag;  // "chains": the family in "hipMemcpyAsync(chains)" / "copy back(chains)"
+    hipError_t e = hipSuccess;
+    bool queued = false;  // a copy back is on the stream
+    void up(void* dst, const void* src, size_t bytes) {
+        if (src && bytes && e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream);
+    }
+    int uploaded() const { return e == hipSuccess ? BLISSGPU_OK : report("hipMemcpyAsync("); }
+    void down(void* dst, const void* src, size_t bytes) {
+        if (!dst || !bytes || e != hipSuccess) return;
+        e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream);
+        queued = true;
+    }
+    // waits for the copies back; a form calls it itself where further copies depend on what came back
+    int landed() {
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        queued = false;
+        return e == hipSuccess ? BLISSGPU_OK : report("copy back(");
+    }
+    // the end of every host form: rc = what the uploads and the device form returned
+    int finish(int rc) {
+        if (!rc && queued) rc = landed();
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    int report(const char* what) const { return fail(BLISSGPU_ERR_HIP, (std::string(what) + tag + ")").c_str(), hipGetErrorString(e)); }
+};
+
+// The host form of the families that answer one list per seed group (group_knn, group_knn_weighted, chains, album_knn,
+// group_forest_knn), the way knn_host serves both searches, in two steps.  group_lists_stage grows the buffers and says where
+// everything goes: candidates in st_b, seeds in st_a (stage_seeds; the forests keep theirs on the host), idx | skip in st_idx,
+// dist_floats floats (0: none) in st_dist, M staged; nothing is queued yet, so a caller returns at once when it fails.
+// group_lists_host copies the inputs up, runs `run`, the family's device form on these pointers, and queues idx and dist back.
+// What a family stages beside that it queues on s itself: uploads in `run` before its device call, copies back after
+// group_lists_host; then s.finish.
+struct GroupLists {
+    float *seeds, *cand;  // seeds == NULL: not staged
+    const float* M;
+    uint32_t *skip, *idx;
+    float* dist;
+};
+int group_lists_stage(blissgpu_ctx* c, uint64_t n_seeds, bool stage_seeds, uint64_t n, uint32_t d, int metric, const float* M,
+                      bool skip, size_t out_n, size_t dist_floats, GroupLists* g) {
+    const float* dM = nullptr;
+    int rc = c->st_b.ensure(std::max<size_t>(1, n * d));
+    if (!rc && stage_seeds) rc = c->st_a.ensure(std::max<size_t>(1, n_seeds * d));
+    if (!rc) rc = c->st_idx.ensure(out_n + (skip ? n_seeds : 0));
+    if (!rc && dist_floats) rc = c->st_dist.ensure(dist_floats);
+    if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
+    if (rc) return rc;
+    *g = GroupLists{stage_seeds ? c->st_a.p : nullptr, c->st_b.p, dM, skip ? c->st_idx.p + out_n : nullptr, c->st_idx.p,
+                    dist_floats ? c->st_dist.p : nullptr};
+    return BLISSGPU_OK;
+}
+template <typename Run>
+int group_lists_host(HostStage& s, const GroupLists& g, const float* seeds, uint64_t n_seeds, const float* cand, uint64_t n, uint32_t d,
+                     const uint32_t* skip, size_t out_n, uint32_t* idx, float* dist, Run run) {
+    s.up(g.cand, cand, n * d * sizeof(float));
+    if (g.seeds) s.up(g.seeds, seeds, n_seeds * d * sizeof(float));
+    s.up(g.skip, skip, n_seeds * sizeof(uint32_t));
+    int rc = s.uploaded();
+    if (!rc) rc = run();
+    if (!rc) {
+        s.down(idx, g.idx, out_n * sizeof(uint32_t));
+        s.down(dist, g.dist, out_n * sizeof(float));
+    }
+    return rc;
+}
+
+// a host form's skip array, checked before the device is touched
+int skip_entries_ok(const char* who, const uint32_t* skip, uint64_t count, uint64_t n) {
+    if (skip)
+        for (uint64_t i = 0; i < count; i++)
+            if (skip[i] != 0xFFFFFFFFu && skip[i] >= n) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
+    return BLISSGPU_OK;
+}
+
+// the device flag words of a call, read back: the synchronisation every device form ends in
+int read_flags(blissgpu_ctx* c, const uint32_t* d_flags, uint32_t count, uint32_t* h_flags) {
+    HIP_TRY(hipMemcpyAsync(h_flags, d_flags, count * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return BLISSGPU_OK;
+}
+
+// the k-means sort of a labelling: labels -> arow_off (the groups' offsets) and arow (their rows; NULL: the offsets alone, hist
+// is then left at the positions the scatter would start from); hist is zero on entry
+void launch_label_sort(blissgpu_ctx* c, const uint32_t* d_labels, uint32_t n, uint32_t k, const KmeansPlan& plan, uint32_t* hist,
+                       uint32_t* bsum, uint32_t* arow_off, uint32_t* arow) {
+    { Prof p(c, KX_KMEANS_HIST); launch_kmeans_hist(d_labels, n, k, plan, hist, c->stream); }
+    { Prof p(c, KX_KMEANS_SCAN_TILES); launch_kmeans_scan_tiles(hist, plan, bsum, c->stream); }
+    { Prof p(c, KX_KMEANS_SCAN_ADD); launch_kmeans_scan_add(hist, n, k, plan, bsum, arow_off, c->stream); }
+    if (arow) { Prof p(c, KX_KMEANS_SCATTER); launch_kmeans_scatter(d_labels, n, k, plan, hist, arow, c->stream); }
+}
+
 }  // namespace
 
 extern "C" {
@@ -619,8 +716,7 @@ static int playlist_args_ok(const char* who, const void* a, const void* b, const
 // reads the device NaN flag (synchronises the stream)
 static int nan_check(blissgpu_ctx* c, const uint32_t* d_flag, const char* who) {
     uint32_t flag = 0;
-    HIP_TRY(hipMemcpyAsync(&flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = read_flags(c, d_flag, 1, &flag)) return rc;
     if (flag) return fail(BLISSGPU_ERR_NAN, who, "NaN distance (the reference panics here)");
     return BLISSGPU_OK;
 }
@@ -743,9 +839,8 @@ int blissgpu_dedup_playlist_device(blissgpu_ctx* c, const float* d_x, uint64_t n
                           c->pl_sync.p + 1, c->pl_sync.p + 3, c->stream);
     }
     HIP_TRY(hipGetLastError());
-    uint32_t flags[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(flags, c->pl_sync.p, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    uint32_t flags[4];
+    if ((rc = read_flags(c, c->pl_sync.p, 4, flags))) return rc;
     if (flags[3]) return fail(BLISSGPU_ERR_INVALID, who, "seq entries must be < n");
     if (flags[1]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance (the reference panics here)");
     return BLISSGPU_OK;
@@ -756,12 +851,14 @@ int blissgpu_dedup_playlist_device(blissgpu_ctx* c, const float* d_x, uint64_t n
 // host-pointer wrappers: stage seeds / candidates / M in the context's buffers, run the device form, copy the result back
 namespace {
 struct PlStage {
-    blissgpu_ctx* c;
+    HostStage s;
     float *seeds = nullptr, *cand = nullptr, *dist = nullptr;
     const float* M = nullptr;
     void* out = nullptr;
+    explicit PlStage(blissgpu_ctx* c) : s{c, "playlist"} {}
     int up(const float* h_seeds, uint32_t n_seeds, const float* h_cand, uint64_t n, uint32_t d, int metric, const float* h_M,
            size_t out_bytes, bool want_dist) {
+        blissgpu_ctx* c = s.c;
         int rc = c->st_a.ensure(std::max<size_t>(1, (size_t)n_seeds * d));
         if (!rc) rc = c->st_b.ensure(std::max<size_t>(1, n * d));
         if (!rc) rc = c->st_out.ensure(std::max<size_t>(4, out_bytes));
@@ -769,19 +866,17 @@ struct PlStage {
         if (!rc) rc = stage_matrix(c, h_M, d, metric, &M);
         if (rc) return rc;
         seeds = c->st_a.p; cand = c->st_b.p; out = c->st_out.p; dist = want_dist ? c->st_dist.p : nullptr;
-        hipError_t e = hipSuccess;
-        if (n_seeds) e = hipMemcpyAsync(seeds, h_seeds, (size_t)n_seeds * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess && n) e = hipMemcpyAsync(cand, h_cand, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) return fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(playlist)", hipGetErrorString(e));
-        return BLISSGPU_OK;
+        s.up(seeds, h_seeds, (size_t)n_seeds * d * sizeof(float));
+        s.up(cand, h_cand, n * d * sizeof(float));
+        return s.uploaded();
     }
-    int down(void* h_out, size_t out_bytes, float* h_dist, uint64_t n) {
-        hipError_t e = hipSuccess;
-        if (out_bytes) e = hipMemcpyAsync(h_out, out, out_bytes, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && h_dist && n) e = hipMemcpyAsync(h_dist, dist, n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) return fail(BLISSGPU_ERR_HIP, "copy back(playlist)", hipGetErrorString(e));
-        return BLISSGPU_OK;
+    // the end of the three forms: rc = what up and the device form returned
+    int down(int rc, void* h_out, size_t out_bytes, float* h_dist, uint64_t n) {
+        if (!rc) {
+            s.down(h_out, out, out_bytes);
+            s.down(h_dist, dist, n * sizeof(float));
+        }
+        return s.finish(rc);
     }
 };
 }  // namespace
@@ -796,12 +891,10 @@ int blissgpu_set_distance(const float* seeds, uint32_t n_seeds, const float* can
     rc = default_ctx(&c);
     if (rc) return rc;
     CTX_ENTER(c, "blissgpu_set_distance");
-    PlStage s{c};
+    PlStage s(c);
     rc = s.up(seeds, n_seeds, cand, n, d, metric, M, n * sizeof(float), false);
     if (!rc) rc = blissgpu_set_distance_device(c, s.seeds, n_seeds, s.cand, n, d, metric, s.M, (float*)s.out);
-    if (!rc) rc = s.down(out, n * sizeof(float), nullptr, 0);
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    return s.down(rc, out, n * sizeof(float), nullptr, 0);
 }
 
 int blissgpu_closest_to_songs(const float* seeds, uint32_t n_seeds, const float* cand, uint64_t n, uint32_t d, int metric,
@@ -812,12 +905,10 @@ int blissgpu_closest_to_songs(const float* seeds, uint32_t n_seeds, const float*
     rc = default_ctx(&c);
     if (rc) return rc;
     CTX_ENTER(c, "blissgpu_closest_to_songs");
-    PlStage s{c};
+    PlStage s(c);
     rc = s.up(seeds, n_seeds, cand, n, d, metric, M, n * sizeof(uint32_t), dist != nullptr);
     if (!rc) rc = blissgpu_closest_to_songs_device(c, s.seeds, n_seeds, s.cand, n, d, metric, s.M, (uint32_t*)s.out, s.dist);
-    if (!rc) rc = s.down(order, n * sizeof(uint32_t), dist, n);
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    return s.down(rc, order, n * sizeof(uint32_t), dist, n);
 }
 
 int blissgpu_song_to_song(const float* seeds, uint32_t n_seeds, const float* cand, uint64_t n, uint32_t d, int metric,
@@ -828,12 +919,10 @@ int blissgpu_song_to_song(const float* seeds, uint32_t n_seeds, const float* can
     rc = default_ctx(&c);
     if (rc) return rc;
     CTX_ENTER(c, "blissgpu_song_to_song");
-    PlStage s{c};
+    PlStage s(c);
     rc = s.up(seeds, n_seeds, cand, n, d, metric, M, n * sizeof(uint32_t), false);
     if (!rc) rc = blissgpu_song_to_song_device(c, s.seeds, n_seeds, s.cand, n, d, metric, s.M, (uint32_t*)s.out);
-    if (!rc) rc = s.down(order, n * sizeof(uint32_t), nullptr, 0);
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    return s.down(rc, order, n * sizeof(uint32_t), nullptr, 0);
 }
 
 int blissgpu_dedup_playlist(const float* x, uint64_t n, uint32_t d, const uint32_t* seq, uint64_t len, const uint32_t* meta,
@@ -858,23 +947,25 @@ int blissgpu_dedup_playlist(const float* x, uint64_t n, uint32_t d, const uint32
     if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
     if (rc) return rc;
     uint32_t* idx = c->st_idx.p;
-    hipError_t e = hipMemcpyAsync(c->st_b.p, x, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && seq) e = hipMemcpyAsync(idx + o_seq, seq, len * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && meta) e = hipMemcpyAsync(idx + o_meta, meta, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(dedup)", hipGetErrorString(e));
+    HostStage s{c, "dedup"};
+    s.up(c->st_b.p, x, n * d * sizeof(float));
+    s.up(idx + o_seq, seq, len * sizeof(uint32_t));
+    s.up(idx + o_meta, meta, n * sizeof(uint32_t));
+    rc = s.uploaded();
     if (!rc)
         rc = blissgpu_dedup_playlist_device(c, c->st_b.p, n, d, seq ? idx + o_seq : nullptr, len, meta ? idx + o_meta : nullptr,
                                             metric, dM, threshold, idx + o_kept, reinterpret_cast<uint64_t*>(idx));
     uint64_t nk = 0;
     if (!rc) {  // the device form has synchronised: the count is there
-        e = hipMemcpyAsync(&nk, idx, sizeof(nk), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess && nk) e = hipMemcpyAsync(kept, idx + o_kept, nk * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(dedup)", hipGetErrorString(e));
-        if (!rc) *n_kept = nk;
+        s.down(&nk, idx, sizeof(nk));
+        rc = s.landed();
+        if (!rc) {
+            s.down(kept, idx + o_kept, nk * sizeof(uint32_t));
+            rc = s.landed();
+        }
     }
-    (void)hipStreamSynchronize(c->stream);
+    rc = s.finish(rc);
+    if (!rc) *n_kept = nk;
     return rc;
 }
 
@@ -938,9 +1029,8 @@ static int knn_run(blissgpu_ctx* c, const char* who, const float* d_queries, uin
         launch_knn_merge(part, q, k, plan, d_idx, d_dist, c->stream);
     }
     HIP_TRY(hipGetLastError());
-    uint32_t flags[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(flags, c->pl_sync.p, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    uint32_t flags[4];
+    if ((rc = read_flags(c, c->pl_sync.p, 4, flags))) return rc;
     if (flags[3]) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
     if (flags[2]) return fail(BLISSGPU_ERR_INVALID, who, "scales must lie in [2^-60, 2^60]");
     if (flags[1]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance (the reference panics here)");
@@ -951,13 +1041,10 @@ static int knn_run(blissgpu_ctx* c, const char* who, const float* d_queries, uin
 static int knn_host(const char* who, const char* run_who, const float* queries, uint64_t q, const float* qscale, const float* cand,
                     uint64_t n, const float* cscale, uint32_t d, int metric, const float* M, const uint32_t* skip, uint32_t k,
                     uint32_t* idx, float* dist) {
-    if (skip)
-        for (uint64_t i = 0; i < q; i++)
-            if (skip[i] != 0xFFFFFFFFu && skip[i] >= n) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
-    if (q == 0) return BLISSGPU_OK;
+    int rc = skip_entries_ok(who, skip, q, n);
+    if (rc || q == 0) return rc;
     blissgpu_ctx* c;
-    int rc = default_ctx(&c);
-    if (rc) return rc;
+    if ((rc = default_ctx(&c))) return rc;
     CTX_ENTER(c, who);
     // queries that ARE the candidate matrix (the similar-songs table of a library), with the same scales, travel once:
     // st_b = cand | cscale, st_a = queries | qscale
@@ -974,24 +1061,21 @@ static int knn_host(const char* who, const char* run_who, const float* queries, 
     float* d_cs = scaled ? c->st_b.p + n * d : nullptr;
     const float* d_qs = !scaled ? nullptr : shared ? d_cs : c->st_a.p + q * d;
     uint32_t *d_idx = c->st_idx.p, *d_skip = skip ? c->st_idx.p + out_n : nullptr;
-    hipError_t e = hipSuccess;
-    if (n) e = hipMemcpyAsync(c->st_b.p, cand, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && scaled && n) e = hipMemcpyAsync(d_cs, cscale, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && !shared) e = hipMemcpyAsync(c->st_a.p, queries, q * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && scaled && !shared)
-        e = hipMemcpyAsync(c->st_a.p + q * d, qscale, q * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && skip) e = hipMemcpyAsync(d_skip, skip, q * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess)
-        rc = fail(BLISSGPU_ERR_HIP, scaled ? "hipMemcpyAsync(scaled_knn)" : "hipMemcpyAsync(knn)", hipGetErrorString(e));
+    HostStage s{c, scaled ? "scaled_knn" : "knn"};
+    s.up(c->st_b.p, cand, n * d * sizeof(float));
+    s.up(d_cs, cscale, n * sizeof(float));
+    if (!shared) {
+        s.up(c->st_a.p, queries, q * d * sizeof(float));
+        s.up(c->st_a.p + q * d, qscale, q * sizeof(float));
+    }
+    s.up(d_skip, skip, q * sizeof(uint32_t));
+    rc = s.uploaded();
     if (!rc) rc = knn_run(c, run_who, dQ, q, d_qs, c->st_b.p, n, d_cs, d, metric, dM, d_skip, k, d_idx, dist ? c->st_dist.p : nullptr);
     if (!rc) {
-        e = hipMemcpyAsync(idx, d_idx, out_n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, scaled ? "copy back(scaled_knn)" : "copy back(knn)", hipGetErrorString(e));
+        s.down(idx, d_idx, out_n * sizeof(uint32_t));
+        s.down(dist, c->st_dist.p, out_n * sizeof(float));
     }
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    return s.finish(rc);
 }
 
 int blissgpu_knn_device(blissgpu_ctx* c, const float* d_queries, uint64_t q, const float* d_cand, uint64_t n, uint32_t d,
@@ -1079,16 +1163,12 @@ int blissgpu_knn_occurrence(const uint32_t* idx, uint64_t q, uint32_t k, uint64_
     CTX_ENTER(c, who);
     rc = c->st_idx.ensure(entries + n);
     if (rc) return rc;
-    hipError_t e = hipMemcpyAsync(c->st_idx.p, idx, entries * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(knn_occurrence)", hipGetErrorString(e));
+    HostStage s{c, "knn_occurrence"};
+    s.up(c->st_idx.p, idx, entries * sizeof(uint32_t));
+    rc = s.uploaded();
     if (!rc) rc = blissgpu_knn_occurrence_device(c, c->st_idx.p, q, k, n, c->st_idx.p + entries);
-    if (!rc) {
-        e = hipMemcpyAsync(count, c->st_idx.p + entries, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(knn_occurrence)", hipGetErrorString(e));
-    }
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    if (!rc) s.down(count, c->st_idx.p + entries, n * sizeof(uint32_t));
+    return s.finish(rc);
 }
 
 // ---- k-means of a library: Lloyd's algorithm with the all-pairs kernel's distances, ties to the lower centre, sequential f32
@@ -1141,11 +1221,6 @@ int blissgpu_kmeans_device(blissgpu_ctx* c, const float* d_x, uint64_t n, uint32
     float* cent[2] = {reinterpret_cast<float*>(w + o_cent), reinterpret_cast<float*>(w + o_cent) + (size_t)k * d};
     const AlbumTables tables{nullptr, arow_off, arow, nullptr, nullptr, nullptr, nullptr, nullptr, k, 0u, 0u};
     const size_t zero_bytes = (o_hist + (size_t)plan.hist_words) * sizeof(uint32_t);  // the flags and the histograms: one memset
-    auto sort_head = [&]() {  // labels -> arow_off (and hist = the positions the scatter starts from)
-        { Prof p(c, KX_KMEANS_HIST); launch_kmeans_hist(d_labels, (uint32_t)n, k, plan, hist, c->stream); }
-        { Prof p(c, KX_KMEANS_SCAN_TILES); launch_kmeans_scan_tiles(hist, plan, bsum, c->stream); }
-        { Prof p(c, KX_KMEANS_SCAN_ADD); launch_kmeans_scan_add(hist, (uint32_t)n, k, plan, bsum, arow_off, c->stream); }
-    };
     HIP_TRY(hipMemcpyAsync(cent[0], d_init, cent_bytes, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(d_labels, 0xFF, (size_t)n * sizeof(uint32_t), c->stream));  // L_-1: no label
     uint32_t t = 0;
@@ -1159,16 +1234,14 @@ int blissgpu_kmeans_device(blissgpu_ctx* c, const float* d_x, uint64_t n, uint32
         }
         HIP_TRY(hipGetLastError());
         // the one word pair the host reads per iteration
-        uint32_t h_flags[2] = {0, 0};
-        HIP_TRY(hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        uint32_t h_flags[2];
+        if ((rc = read_flags(c, flags, 2, h_flags))) return rc;
         c->km_loop_copies++;
         c->km_loop_bytes += sizeof(h_flags);
         if (h_flags[1]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance (the reference panics here)");
         if (h_flags[0] == 0) { conv = 1; break; }
         if (t == max_iter) break;
-        sort_head();
-        { Prof p(c, KX_KMEANS_SCATTER); launch_kmeans_scatter(d_labels, (uint32_t)n, k, plan, hist, arow, c->stream); }
+        launch_label_sort(c, d_labels, (uint32_t)n, k, plan, hist, bsum, arow_off, arow);
         { Prof p(c, KX_SEGMENT_MEAN); launch_segment_mean(d_x, nullptr, d, tables, cent[cur ^ 1], nullptr, nullptr, c->stream); }
         { Prof p(c, KX_KMEANS_SELECT); launch_kmeans_select(cent[cur], cent[cur ^ 1], arow_off, k, d, nullptr, c->stream); }
         HIP_TRY(hipGetLastError());
@@ -1178,7 +1251,7 @@ int blissgpu_kmeans_device(blissgpu_ctx* c, const float* d_x, uint64_t n, uint32
         // converged after an update: the labels are those the last sort saw; otherwise they moved since (or were never sorted)
         if (!conv || t == 0) {
             HIP_TRY(hipMemsetAsync(w, 0, zero_bytes, c->stream));
-            sort_head();
+            launch_label_sort(c, d_labels, (uint32_t)n, k, plan, hist, bsum, arow_off, nullptr);  // (the sizes need the offsets only)
         }
         { Prof p(c, KX_KMEANS_SELECT); launch_kmeans_select(nullptr, nullptr, arow_off, k, d, d_sizes, c->stream); }
         HIP_TRY(hipGetLastError());
@@ -1217,22 +1290,20 @@ int blissgpu_kmeans(const float* x, uint64_t n, uint32_t d, const float* init, u
     if (rc) return rc;
     float* d_cent = c->st_a.p + cent_floats;
     uint32_t *d_labels = c->st_idx.p, *d_sizes = sizes ? c->st_idx.p + n : nullptr;
-    hipError_t e = hipMemcpyAsync(c->st_b.p, x, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->st_a.p, init, cent_floats * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(kmeans)", hipGetErrorString(e));
+    HostStage s{c, "kmeans"};
+    s.up(c->st_b.p, x, n * d * sizeof(float));
+    s.up(c->st_a.p, init, cent_floats * sizeof(float));
+    rc = s.uploaded();
     if (!rc)
         rc = blissgpu_kmeans_device(c, c->st_b.p, n, d, c->st_a.p, k, metric, dM, max_iter, d_labels, dist ? c->st_dist.p : nullptr,
                                     d_cent, d_sizes, n_iter, converged);
     if (!rc) {
-        e = hipMemcpyAsync(labels, d_labels, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(centroids, d_cent, cent_floats * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && sizes) e = hipMemcpyAsync(sizes, d_sizes, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(kmeans)", hipGetErrorString(e));
+        s.down(labels, d_labels, n * sizeof(uint32_t));
+        s.down(dist, c->st_dist.p, n * sizeof(float));
+        s.down(centroids, d_cent, cent_floats * sizeof(float));
+        s.down(sizes, d_sizes, (size_t)k * sizeof(uint32_t));
     }
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    return s.finish(rc);
 }
 
 // ---- the silhouette of a labelling: the k-means sort of the labels, then the all-pairs sums per (song, cluster) and the scores
@@ -1288,17 +1359,13 @@ int blissgpu_silhouette_device(blissgpu_ctx* c, const float* d_x, uint64_t n, ui
     a.ws_own = part; a.ws_best_q = part + qy; a.ws_best_i = reinterpret_cast<uint32_t*>(part + 2 * qy);
     a.flags = flags; a.s = d_s; a.a = d_a; a.b = d_b; a.neighbour = d_neighbour; a.sizes = d_sizes;
     HIP_TRY(hipMemsetAsync(w, 0, (o_hist + (size_t)sort.hist_words) * sizeof(uint32_t), c->stream));  // the flags and the histograms
-    { Prof p(c, KX_KMEANS_HIST); launch_kmeans_hist(d_labels, (uint32_t)n, k, sort, hist, c->stream); }
-    { Prof p(c, KX_KMEANS_SCAN_TILES); launch_kmeans_scan_tiles(hist, sort, bsum, c->stream); }
-    { Prof p(c, KX_KMEANS_SCAN_ADD); launch_kmeans_scan_add(hist, (uint32_t)n, k, sort, bsum, arow_off, c->stream); }
-    { Prof p(c, KX_KMEANS_SCATTER); launch_kmeans_scatter(d_labels, (uint32_t)n, k, sort, hist, arow, c->stream); }
+    launch_label_sort(c, d_labels, (uint32_t)n, k, sort, hist, bsum, arow_off, arow);
     { Prof p(c, KX_SILHOUETTE_SCAN); launch_silhouette_scan(a, diag, plan, c->stream); }
     { Prof p(c, KX_SILHOUETTE_FINISH); launch_silhouette_finish(a, c->stream); }
     HIP_TRY(hipGetLastError());
     // the one synchronisation: the NaN word and the data-dependent errors
-    uint32_t h_flags[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    uint32_t h_flags[2];
+    if ((rc = read_flags(c, flags, 2, h_flags))) return rc;
     if (h_flags[1] & SIL_ERR_LABEL) return fail(BLISSGPU_ERR_INVALID, who, "a label is >= k");
     if (h_flags[1] & SIL_ERR_ROW) return fail(BLISSGPU_ERR_INVALID, who, "a rows entry is >= n");
     if (h_flags[1] & SIL_ERR_CLUSTERS) return fail(BLISSGPU_ERR_INVALID, who, "fewer than two non-empty clusters");
@@ -1344,24 +1411,22 @@ int blissgpu_silhouette(const float* x, uint64_t n, uint32_t d, const uint32_t* 
     uint32_t *d_labels = c->st_idx.p, *d_rows = rows ? c->st_idx.p + n : nullptr, *d_nb = c->st_idx.p + n + q,
              *d_sizes = c->st_idx.p + n + 2 * q;
     double *d_a = reinterpret_cast<double*>(c->st_out.p), *d_b = d_a + q;
-    hipError_t e = hipMemcpyAsync(c->st_b.p, x, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_labels, labels, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && rows) e = hipMemcpyAsync(d_rows, rows, q * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(silhouette)", hipGetErrorString(e));
+    HostStage st{c, "silhouette"};
+    st.up(c->st_b.p, x, n * d * sizeof(float));
+    st.up(d_labels, labels, n * sizeof(uint32_t));
+    st.up(d_rows, rows, q * sizeof(uint32_t));
+    rc = st.uploaded();
     if (!rc)
         rc = blissgpu_silhouette_device(c, c->st_b.p, n, d, d_labels, k, metric, dM, d_rows, q, col_groups, c->st_dist.p, d_a, d_b,
                                         d_nb, d_sizes);
     if (!rc) {
-        e = hipMemcpyAsync(s, c->st_dist.p, q * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && a) e = hipMemcpyAsync(a, d_a, q * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && b) e = hipMemcpyAsync(b, d_b, q * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && neighbour) e = hipMemcpyAsync(neighbour, d_nb, q * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && sizes) e = hipMemcpyAsync(sizes, d_sizes, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(silhouette)", hipGetErrorString(e));
+        st.down(s, c->st_dist.p, q * sizeof(float));
+        st.down(a, d_a, q * sizeof(double));
+        st.down(b, d_b, q * sizeof(double));
+        st.down(neighbour, d_nb, q * sizeof(uint32_t));
+        st.down(sizes, d_sizes, (size_t)k * sizeof(uint32_t));
     }
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    return st.finish(rc);
 }
 
 // ---- group neighbours: the k-means sort of the labels, then per slab of target groups the minima per (song, group) and their
@@ -1419,12 +1484,7 @@ int blissgpu_group_neighbours_device(blissgpu_ctx* c, const float* d_x, uint64_t
     a.flags = flags; a.idx = d_idx; a.dist = d_dist; a.sizes = d_sizes; a.matrix = d_matrix;
     // the flags and the histograms; without a song the offsets too (every group is empty)
     HIP_TRY(hipMemsetAsync(w, 0, (n ? o_hist + (size_t)sort.hist_words : o_arow) * sizeof(uint32_t), c->stream));
-    if (n) {
-        { Prof p(c, KX_KMEANS_HIST); launch_kmeans_hist(d_labels, (uint32_t)n, k, sort, hist, c->stream); }
-        { Prof p(c, KX_KMEANS_SCAN_TILES); launch_kmeans_scan_tiles(hist, sort, bsum, c->stream); }
-        { Prof p(c, KX_KMEANS_SCAN_ADD); launch_kmeans_scan_add(hist, (uint32_t)n, k, sort, bsum, arow_off, c->stream); }
-        { Prof p(c, KX_KMEANS_SCATTER); launch_kmeans_scatter(d_labels, (uint32_t)n, k, sort, hist, arow, c->stream); }
-    }
+    if (n) launch_label_sort(c, d_labels, (uint32_t)n, k, sort, hist, bsum, arow_off, arow);
     if (pairs)
         for (uint32_t s0 = 0; s0 < k; s0 += plan.slab) {
             a.s0 = s0;
@@ -1435,9 +1495,8 @@ int blissgpu_group_neighbours_device(blissgpu_ctx* c, const float* d_x, uint64_t
     { Prof p(c, KX_CHAMFER_SELECT); launch_chamfer_select(a, plan, c->stream); }
     HIP_TRY(hipGetLastError());
     // the one synchronisation: the NaN word and the data-dependent errors
-    uint32_t h_flags[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    uint32_t h_flags[2];
+    if ((rc = read_flags(c, flags, 2, h_flags))) return rc;
     if (h_flags[1] & CH_ERR_LABEL) return fail(BLISSGPU_ERR_INVALID, who, "a label is >= k");
     if (h_flags[1] & CH_ERR_QUERY) return fail(BLISSGPU_ERR_INVALID, who, "a query is >= k");
     if (h_flags[0]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance (the reference panics here)");
@@ -1482,23 +1541,21 @@ int blissgpu_group_neighbours(const float* x, uint64_t n, uint32_t d, const uint
     uint32_t *d_labels = c->st_idx.p, *d_queries = queries ? c->st_idx.p + n : nullptr, *d_idx = c->st_idx.p + n + q,
              *d_sizes = c->st_idx.p + n + q + q * t;
     double *d_dist = reinterpret_cast<double*>(c->st_out.p), *d_matrix = matrix ? d_dist + q * t : nullptr;
-    hipError_t e = hipMemcpyAsync(c->st_b.p, x, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_labels, labels, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && queries && q) e = hipMemcpyAsync(d_queries, queries, q * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(group_neighbours)", hipGetErrorString(e));
+    HostStage s{c, "group_neighbours"};
+    s.up(c->st_b.p, x, n * d * sizeof(float));
+    s.up(d_labels, labels, n * sizeof(uint32_t));
+    s.up(d_queries, queries, q * sizeof(uint32_t));
+    rc = s.uploaded();
     if (!rc)
         rc = blissgpu_group_neighbours_device(c, c->st_b.p, n, d, d_labels, k, metric, dM, d_queries, q, t, mode, slab_groups, d_idx,
                                               d_dist, sizes ? d_sizes : nullptr, d_matrix);
     if (!rc) {
-        if (q) e = hipMemcpyAsync(idx, d_idx, q * t * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && q) e = hipMemcpyAsync(dist, d_dist, q * t * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && sizes) e = hipMemcpyAsync(sizes, d_sizes, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && matrix) e = hipMemcpyAsync(matrix, d_matrix, kk * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(group_neighbours)", hipGetErrorString(e));
+        s.down(idx, d_idx, q * t * sizeof(uint32_t));
+        s.down(dist, d_dist, q * t * sizeof(double));
+        s.down(sizes, d_sizes, (size_t)k * sizeof(uint32_t));
+        s.down(matrix, d_matrix, kk * sizeof(double));
     }
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    return s.finish(rc);
 }
 
 // ---- the minimum spanning tree: Boruvka's rounds, each one scan and one pick on the device (kernels_mst.hip) and the merge on
@@ -1628,13 +1685,13 @@ int blissgpu_mst(const float* x, uint64_t n, uint32_t d, int metric, const float
     if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
     if (rc) return rc;
     float* d_core = core ? c->st_b.p + n * d : nullptr;
-    hipError_t e = hipMemcpyAsync(c->st_b.p, x, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && core) e = hipMemcpyAsync(d_core, core, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(mst)", hipGetErrorString(e));
+    HostStage s{c, "mst"};
+    s.up(c->st_b.p, x, n * d * sizeof(float));
+    s.up(d_core, core, n * sizeof(float));
+    rc = s.uploaded();
     MstState st;
     if (!rc) rc = mst_run(c, who, c->st_b.p, n, d, metric, dM, d_core, st);
-    (void)hipStreamSynchronize(c->stream);
-    if (rc) return rc;
+    if ((rc = s.finish(rc))) return rc;  // (the edges are host memory: nothing to copy back)
     for (size_t k = 0; k < st.edges.size(); k++) {
         edge_u[k] = st.edges[k].u;
         edge_v[k] = st.edges[k].v;
@@ -1701,12 +1758,7 @@ int blissgpu_moments_device(blissgpu_ctx* c, const float* d_x, uint64_t n, uint3
     a.X = d_x; a.labels = d_labels; a.arow_off = arow_off; a.arow = arow; a.off = off; a.mean = d_mean;
     a.n = (uint32_t)n; a.K = k; a.d = d; a.key_min = keys; a.key_max = keys + kd; a.flags = flags;
     HIP_TRY(hipMemsetAsync(ws, 0, (o_hist + (d_labels ? (size_t)sort.hist_words : 0)) * sizeof(uint32_t), c->stream));
-    if (d_labels) {
-        { Prof p(c, KX_KMEANS_HIST); launch_kmeans_hist(d_labels, (uint32_t)n, k, sort, hist, c->stream); }
-        { Prof p(c, KX_KMEANS_SCAN_TILES); launch_kmeans_scan_tiles(hist, sort, bsum, c->stream); }
-        { Prof p(c, KX_KMEANS_SCAN_ADD); launch_kmeans_scan_add(hist, (uint32_t)n, k, sort, bsum, arow_off, c->stream); }
-        { Prof p(c, KX_KMEANS_SCATTER); launch_kmeans_scatter(d_labels, (uint32_t)n, k, sort, hist, arow, c->stream); }
-    }
+    if (d_labels) launch_label_sort(c, d_labels, (uint32_t)n, k, sort, hist, bsum, arow_off, arow);
     { Prof p(c, KX_MOMENTS_PLAN); launch_moments_plan(arow_off, (uint32_t)n, k, plan, off, d_counts, c->stream); }
     // the levels above level 0 of one per-group quantity, and its last step into dst
     auto group_levels = [&](int mode, double* dst) {
@@ -1744,9 +1796,8 @@ int blissgpu_moments_device(blissgpu_ctx* c, const float* d_x, uint64_t n, uint3
     }
     HIP_TRY(hipGetLastError());
     // the one synchronisation: the data-dependent errors
-    uint32_t h_flags[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    uint32_t h_flags[2];
+    if ((rc = read_flags(c, flags, 2, h_flags))) return rc;
     if (h_flags[1] & MO_ERR_LABEL) return fail(BLISSGPU_ERR_INVALID, who, "a label is >= k");
     if (h_flags[0]) return fail(BLISSGPU_ERR_NAN, who, "a NaN or an infinity in x");
     return BLISSGPU_OK;
@@ -1783,24 +1834,22 @@ int blissgpu_moments(const float* x, uint64_t n, uint32_t d, const uint32_t* lab
     uint32_t *d_labels = labels ? c->st_idx.p : nullptr, *d_counts = c->st_idx.p + n;
     double *d_mean = reinterpret_cast<double*>(c->st_out.p), *d_m2 = d_mean + kd, *d_S = d_m2 + kd;
     float *d_mn = reinterpret_cast<float*>(d_S + dd), *d_mx = d_mn + kd;
-    hipError_t e = hipMemcpyAsync(c->st_b.p, x, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && labels) e = hipMemcpyAsync(d_labels, labels, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(moments)", hipGetErrorString(e));
+    HostStage s{c, "moments"};
+    s.up(c->st_b.p, x, n * d * sizeof(float));
+    s.up(d_labels, labels, n * sizeof(uint32_t));
+    rc = s.uploaded();
     if (!rc)
         rc = blissgpu_moments_device(c, c->st_b.p, n, d, d_labels, k, d_counts, d_mean, m2 ? d_m2 : nullptr, mn ? d_mn : nullptr,
                                      mn ? d_mx : nullptr, S ? d_S : nullptr);
     if (!rc) {
-        e = hipMemcpyAsync(counts, d_counts, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(mean, d_mean, kd * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && m2) e = hipMemcpyAsync(m2, d_m2, kd * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && mn) e = hipMemcpyAsync(mn, d_mn, kd * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && mn) e = hipMemcpyAsync(mx, d_mx, kd * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && S) e = hipMemcpyAsync(S, d_S, dd * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(moments)", hipGetErrorString(e));
+        s.down(counts, d_counts, (size_t)k * sizeof(uint32_t));
+        s.down(mean, d_mean, kd * sizeof(double));
+        s.down(m2, d_m2, kd * sizeof(double));
+        s.down(mn, d_mn, kd * sizeof(float));
+        s.down(mx, d_mx, kd * sizeof(float));  // (min and max go together)
+        s.down(S, d_S, dd * sizeof(double));
     }
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    return s.finish(rc);
 }
 
 // a scatter matrix turned into a Mahalanobis M (covariance_metric.hpp): host arithmetic only, no device is touched
@@ -2120,9 +2169,8 @@ static int group_knn_run(blissgpu_ctx* c, const char* who, const float* d_seeds,
         launch_group_knn_merge(part, d_list_off, n_groups, k, plan, d_idx, d_dist, c->stream);
     }
     HIP_TRY(hipGetLastError());
-    uint32_t flags[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(flags, c->pl_sync.p, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // (the tables above have left the host by now too)
+    uint32_t flags[4];
+    if ((rc = read_flags(c, c->pl_sync.p, 4, flags))) return rc;  // (the tables above have left the host by now too)
     if (flags[3]) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
     if (flags[1]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance (the reference panics here)");
     return BLISSGPU_OK;
@@ -2148,38 +2196,18 @@ int blissgpu_group_knn(const float* seeds, const uint64_t* group_offsets, uint64
     if (rc) return rc;
     if (n_groups == 0) return BLISSGPU_OK;
     const uint64_t n_seeds = group_offsets[n_groups];
-    if (skip)
-        for (uint64_t i = 0; i < n_seeds; i++)
-            if (skip[i] != 0xFFFFFFFFu && skip[i] >= n) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
+    if ((rc = skip_entries_ok(who, skip, n_seeds, n))) return rc;
     blissgpu_ctx* c;
-    rc = default_ctx(&c);
-    if (rc) return rc;
+    if ((rc = default_ctx(&c))) return rc;
     CTX_ENTER(c, who);
     const size_t out_n = (size_t)n_groups * k;
-    const float* dM = nullptr;
-    rc = c->st_b.ensure(std::max<size_t>(1, n * d));
-    if (!rc) rc = c->st_a.ensure(std::max<size_t>(1, n_seeds * d));
-    if (!rc) rc = c->st_idx.ensure(out_n + (skip ? n_seeds : 0));
-    if (!rc && dist) rc = c->st_dist.ensure(out_n);
-    if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
-    if (rc) return rc;
-    uint32_t *d_idx = c->st_idx.p, *d_skip = skip ? c->st_idx.p + out_n : nullptr;
-    hipError_t e = hipSuccess;
-    if (n) e = hipMemcpyAsync(c->st_b.p, cand, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && n_seeds) e = hipMemcpyAsync(c->st_a.p, seeds, n_seeds * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && skip && n_seeds) e = hipMemcpyAsync(d_skip, skip, n_seeds * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(group_knn)", hipGetErrorString(e));
-    if (!rc)
-        rc = blissgpu_group_knn_device(c, c->st_a.p, group_offsets, n_groups, c->st_b.p, n, d, metric, dM, d_skip, k, d_idx,
-                                       dist ? c->st_dist.p : nullptr);
-    if (!rc) {
-        e = hipMemcpyAsync(idx, d_idx, out_n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(group_knn)", hipGetErrorString(e));
-    }
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    GroupLists g;
+    if ((rc = group_lists_stage(c, n_seeds, true, n, d, metric, M, skip != nullptr, out_n, dist ? out_n : 0, &g))) return rc;
+    HostStage s{c, "group_knn"};
+    rc = group_lists_host(s, g, seeds, n_seeds, cand, n, d, skip, out_n, idx, dist, [&]() {
+        return blissgpu_group_knn_device(c, g.seeds, group_offsets, n_groups, g.cand, n, d, metric, g.M, g.skip, k, g.idx, g.dist);
+    });
+    return s.finish(rc);
 }
 
 // ---- one diagonal metric per seed group: variance_based_weight_matrix (src/playlist.rs:173-221) of every group on the device,
@@ -2241,19 +2269,15 @@ int blissgpu_group_weights(const float* seeds, const uint64_t* group_offsets, ui
     rc = c->st_a.ensure(std::max<size_t>(1, n_seeds * d));
     if (!rc) rc = stage_group_weights(c, n_groups, d, &d_w, &d_status);
     if (rc) return rc;
-    hipError_t e = hipSuccess;
-    if (n_seeds) e = hipMemcpyAsync(c->st_a.p, seeds, n_seeds * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(group_weights)", hipGetErrorString(e));
+    HostStage s{c, "group_weights"};
+    s.up(c->st_a.p, seeds, n_seeds * d * sizeof(float));
+    rc = s.uploaded();
     if (!rc) rc = blissgpu_group_weights_device(c, c->st_a.p, group_offsets, n_groups, d, d_w, d_status);
     if (!rc) {
-        e = hipMemcpyAsync(weights, d_w, (size_t)n_groups * d * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && group_status)
-            e = hipMemcpyAsync(group_status, d_status, (size_t)n_groups * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(group_weights)", hipGetErrorString(e));
+        s.down(weights, d_w, (size_t)n_groups * d * sizeof(float));
+        s.down(group_status, d_status, (size_t)n_groups * sizeof(int32_t));
     }
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    return s.finish(rc);
 }
 
 int blissgpu_group_knn_weighted_device(blissgpu_ctx* c, const float* d_seeds, const uint64_t* group_offsets, uint64_t n_groups,
@@ -2278,43 +2302,26 @@ int blissgpu_group_knn_weighted(const float* seeds, const uint64_t* group_offset
     if (rc) return rc;
     if (n_groups == 0) return BLISSGPU_OK;
     const uint64_t n_seeds = group_offsets[n_groups];
-    if (skip)
-        for (uint64_t i = 0; i < n_seeds; i++)
-            if (skip[i] != 0xFFFFFFFFu && skip[i] >= n) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
+    if ((rc = skip_entries_ok(who, skip, n_seeds, n))) return rc;
     blissgpu_ctx* c;
-    rc = default_ctx(&c);
-    if (rc) return rc;
+    if ((rc = default_ctx(&c))) return rc;
     CTX_ENTER(c, who);
     const size_t out_n = (size_t)n_groups * k;
     float* d_w = nullptr;
     int32_t* d_status = nullptr;
-    rc = c->st_b.ensure(std::max<size_t>(1, n * d));
-    if (!rc) rc = c->st_a.ensure(std::max<size_t>(1, n_seeds * d));
-    if (!rc) rc = c->st_idx.ensure(out_n + (skip ? n_seeds : 0));
-    if (!rc && dist) rc = c->st_dist.ensure(out_n);
+    GroupLists g;
+    rc = group_lists_stage(c, n_seeds, true, n, d, BLISSGPU_METRIC_EUCLIDEAN, nullptr, skip != nullptr, out_n, dist ? out_n : 0, &g);
     if (!rc) rc = stage_group_weights(c, n_groups, d, &d_w, &d_status);
     if (rc) return rc;
-    uint32_t *d_idx = c->st_idx.p, *d_skip = skip ? c->st_idx.p + out_n : nullptr;
-    hipError_t e = hipSuccess;
-    if (n) e = hipMemcpyAsync(c->st_b.p, cand, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && n_seeds) e = hipMemcpyAsync(c->st_a.p, seeds, n_seeds * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && skip && n_seeds) e = hipMemcpyAsync(d_skip, skip, n_seeds * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && weights)
-        e = hipMemcpyAsync(d_w, weights, (size_t)n_groups * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(group_knn_weighted)", hipGetErrorString(e));
-    if (!rc)
-        rc = blissgpu_group_knn_weighted_device(c, c->st_a.p, group_offsets, n_groups, c->st_b.p, n, d, weights ? d_w : nullptr,
-                                                d_skip, k, d_idx, dist ? c->st_dist.p : nullptr, group_status ? d_status : nullptr);
-    if (!rc) {
-        e = hipMemcpyAsync(idx, d_idx, out_n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && group_status)
-            e = hipMemcpyAsync(group_status, d_status, (size_t)n_groups * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(group_knn_weighted)", hipGetErrorString(e));
-    }
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    HostStage s{c, "group_knn_weighted"};
+    rc = group_lists_host(s, g, seeds, n_seeds, cand, n, d, skip, out_n, idx, dist, [&]() {
+        s.up(d_w, weights, (size_t)n_groups * d * sizeof(float));  // (the weights travel behind seeds, candidates and skip)
+        if (int r = s.uploaded()) return r;
+        return blissgpu_group_knn_weighted_device(c, g.seeds, group_offsets, n_groups, g.cand, n, d, weights ? d_w : nullptr, g.skip, k,
+                                                  g.idx, g.dist, group_status ? d_status : nullptr);
+    });
+    if (!rc) s.down(group_status, d_status, (size_t)n_groups * sizeof(int32_t));
+    return s.finish(rc);
 }
 
 // ---- k nearest ALBUMS per seed group: closest_album_to_group (src/playlist.rs:424-485) cut after k albums, the primitive behind
@@ -2339,10 +2346,7 @@ static int album_knn_data_ok(const char* who, const uint32_t* album_of, uint64_t
     for (uint64_t i = 0; i < n; i++)
         if (album_of[i] != 0xFFFFFFFFu && album_of[i] >= n_albums)
             return fail(BLISSGPU_ERR_INVALID, who, "album_of entries must be < n_albums or 0xFFFFFFFF");
-    if (skip)
-        for (uint64_t i = 0; i < n_seeds; i++)
-            if (skip[i] != 0xFFFFFFFFu && skip[i] >= n) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
-    return BLISSGPU_OK;
+    return skip_entries_ok(who, skip, n_seeds, n);
 }
 
 // The tables of bg::AlbumTables in one array of words, in this order: goff | arow_off | arow | patch_off | patch_album |
@@ -2450,9 +2454,8 @@ static int album_knn_run(blissgpu_ctx* c, const char* who, const float* d_seeds,
         launch_knn_merge(part, n_groups, k, plan, d_idx, d_dist, c->stream);
     }
     HIP_TRY(hipGetLastError());
-    uint32_t flags[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(flags, c->pl_sync.p, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // (the tables above have left the host by now too)
+    uint32_t flags[4];
+    if ((rc = read_flags(c, c->pl_sync.p, 4, flags))) return rc;  // (the tables above have left the host by now too)
     if (flags[1]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance (the reference panics here)");
     return BLISSGPU_OK;
 }
@@ -2497,31 +2500,22 @@ int blissgpu_album_knn(const float* seeds, const uint64_t* group_offsets, uint64
     // staging: st_dist holds dist | group_means | centroids, each only when asked for
     const size_t out_n = (size_t)n_groups * k, gm_n = (size_t)n_groups * d, cent_n = (size_t)n_albums * d;
     const size_t o_gm = dist ? out_n : 0, o_cent = o_gm + (group_means ? gm_n : 0);
-    rc = c->st_b.ensure(std::max<size_t>(1, n * d));
-    if (!rc) rc = c->st_a.ensure(n_seeds * d);
-    if (!rc) rc = c->st_idx.ensure(out_n);
-    if (!rc) rc = c->st_dist.ensure(std::max<size_t>(1, o_cent + (centroids ? cent_n : 0)));
+    // (skip stays on the host, where the patches are built from it; the metric is the Euclidean one)
+    GroupLists g;
+    rc = group_lists_stage(c, n_seeds, true, n, d, BLISSGPU_METRIC_EUCLIDEAN, nullptr, false, out_n,
+                           std::max<size_t>(1, o_cent + (centroids ? cent_n : 0)), &g);
     if (rc) return rc;
-    float *d_dist = dist ? c->st_dist.p : nullptr, *d_gm = group_means ? c->st_dist.p + o_gm : nullptr;
-    float* d_cent = centroids ? c->st_dist.p + o_cent : nullptr;
-    hipError_t e = hipSuccess;
-    if (n) e = hipMemcpyAsync(c->st_b.p, cand, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->st_a.p, seeds, n_seeds * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(album_knn)", hipGetErrorString(e));
-    if (!rc)
-        rc = album_knn_run(c, who, c->st_a.p, group_offsets, n_groups, c->st_b.p, n, d, album_of, n_albums, skip, k, c->st_idx.p,
-                           d_dist, d_gm, d_cent);
+    float *d_gm = group_means ? g.dist + o_gm : nullptr, *d_cent = centroids ? g.dist + o_cent : nullptr;
+    HostStage s{c, "album_knn"};
+    rc = group_lists_host(s, g, seeds, n_seeds, cand, n, d, nullptr, out_n, idx, dist, [&]() {
+        return album_knn_run(c, who, g.seeds, group_offsets, n_groups, g.cand, n, d, album_of, n_albums, skip, k, g.idx,
+                             dist ? g.dist : nullptr, d_gm, d_cent);
+    });
     if (!rc) {
-        e = hipMemcpyAsync(idx, c->st_idx.p, out_n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, d_dist, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && group_means) e = hipMemcpyAsync(group_means, d_gm, gm_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && centroids && cent_n)
-            e = hipMemcpyAsync(centroids, d_cent, cent_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(album_knn)", hipGetErrorString(e));
+        s.down(group_means, d_gm, gm_n * sizeof(float));
+        s.down(centroids, d_cent, cent_n * sizeof(float));
     }
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    return s.finish(rc);
 }
 
 // ---- song-to-song chains cut after k, one per seed group: song_to_song(&group, candidates, metric).take(k)
@@ -2642,8 +2636,7 @@ int blissgpu_chains_device(blissgpu_ctx* c, const float* d_seeds, const uint64_t
                                   c->stream);
             }
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
+            if ((rc = read_flags(c, flags, 4, h_flags))) return rc;
             if (!h_flags[1]) return BLISSGPU_OK;
         } else if (rc != BLISSGPU_ERR_NAN) {
             return rc;
@@ -2665,8 +2658,7 @@ int blissgpu_chains_device(blissgpu_ctx* c, const float* d_seeds, const uint64_t
                           flags, c->stream);
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if ((rc = read_flags(c, flags, 4, h_flags))) return rc;
     if (h_flags[0]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance (the reference panics here)");
     return BLISSGPU_OK;
 }
@@ -2678,38 +2670,18 @@ int blissgpu_chains(const float* seeds, const uint64_t* group_offsets, uint64_t 
     if (rc) return rc;
     if (n_groups == 0) return BLISSGPU_OK;
     const uint64_t n_seeds = group_offsets[n_groups];
-    if (skip)
-        for (uint64_t i = 0; i < n_seeds; i++)
-            if (skip[i] != 0xFFFFFFFFu && skip[i] >= n) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
+    if ((rc = skip_entries_ok(who, skip, n_seeds, n))) return rc;
     blissgpu_ctx* c;
-    rc = default_ctx(&c);
-    if (rc) return rc;
+    if ((rc = default_ctx(&c))) return rc;
     CTX_ENTER(c, who);
     const size_t out_n = (size_t)n_groups * k;
-    const float* dM = nullptr;
-    rc = c->st_b.ensure(std::max<size_t>(1, n * d));
-    if (!rc) rc = c->st_a.ensure(std::max<size_t>(1, n_seeds * d));
-    if (!rc) rc = c->st_idx.ensure(out_n + (skip ? n_seeds : 0));
-    if (!rc && dist) rc = c->st_dist.ensure(out_n);
-    if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
-    if (rc) return rc;
-    uint32_t *d_idx = c->st_idx.p, *d_skip = skip ? c->st_idx.p + out_n : nullptr;
-    hipError_t e = hipSuccess;
-    if (n) e = hipMemcpyAsync(c->st_b.p, cand, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && n_seeds) e = hipMemcpyAsync(c->st_a.p, seeds, n_seeds * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && skip && n_seeds) e = hipMemcpyAsync(d_skip, skip, n_seeds * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(chains)", hipGetErrorString(e));
-    if (!rc)
-        rc = blissgpu_chains_device(c, c->st_a.p, group_offsets, n_groups, c->st_b.p, n, d, metric, dM, d_skip, k, route, d_idx,
-                                    dist ? c->st_dist.p : nullptr);
-    if (!rc) {
-        e = hipMemcpyAsync(idx, d_idx, out_n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(chains)", hipGetErrorString(e));
-    }
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    GroupLists g;
+    if ((rc = group_lists_stage(c, n_seeds, true, n, d, metric, M, skip != nullptr, out_n, dist ? out_n : 0, &g))) return rc;
+    HostStage s{c, "chains"};
+    rc = group_lists_host(s, g, seeds, n_seeds, cand, n, d, skip, out_n, idx, dist, [&]() {
+        return blissgpu_chains_device(c, g.seeds, group_offsets, n_groups, g.cand, n, d, metric, g.M, g.skip, k, route, g.idx, g.dist);
+    });
+    return s.finish(rc);
 }
 
 // ---- journeys: waypoint and directed song-to-song playlists (kernels_chains.hip): the chains' steps with a
@@ -2770,9 +2742,8 @@ int blissgpu_journeys_device(blissgpu_ctx* c, const float* d_from, const float* 
                             flags, c->stream);
     }
     HIP_TRY(hipGetLastError());
-    uint32_t h_flags[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    uint32_t h_flags[4];
+    if ((rc = read_flags(c, flags, 4, h_flags))) return rc;
     if (h_flags[0]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance");
     return BLISSGPU_OK;
 }
@@ -2784,12 +2755,9 @@ int blissgpu_journeys(const float* from, const float* to, uint64_t n_journeys, c
     int rc = journeys_args_ok(who, from, to, n_journeys, cand, n, d, metric, M, k, mode, gate, gate_feature, idx);
     if (rc) return rc;
     if (n_journeys == 0) return BLISSGPU_OK;
-    if (skip)
-        for (uint64_t i = 0; i < 2 * n_journeys; i++)
-            if (skip[i] != 0xFFFFFFFFu && skip[i] >= n) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
+    if ((rc = skip_entries_ok(who, skip, 2 * n_journeys, n))) return rc;
     blissgpu_ctx* c;
-    rc = default_ctx(&c);
-    if (rc) return rc;
+    if ((rc = default_ctx(&c))) return rc;
     CTX_ENTER(c, who);
     const size_t G = (size_t)n_journeys, out_n = G * k, row_n = G * d;
     const float* dM = nullptr;
@@ -2800,23 +2768,20 @@ int blissgpu_journeys(const float* from, const float* to, uint64_t n_journeys, c
     if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
     if (rc) return rc;
     uint32_t *d_idx = c->st_idx.p, *d_skip = skip ? c->st_idx.p + out_n : nullptr;
-    hipError_t e = hipSuccess;
-    if (n) e = hipMemcpyAsync(c->st_b.p, cand, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->st_a.p, from, row_n * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && to) e = hipMemcpyAsync(c->st_a.p + row_n, to, row_n * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && skip) e = hipMemcpyAsync(d_skip, skip, 2 * G * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(journeys)", hipGetErrorString(e));
+    HostStage s{c, "journeys"};
+    s.up(c->st_b.p, cand, n * d * sizeof(float));
+    s.up(c->st_a.p, from, row_n * sizeof(float));
+    s.up(c->st_a.p + row_n, to, row_n * sizeof(float));
+    s.up(d_skip, skip, 2 * G * sizeof(uint32_t));
+    rc = s.uploaded();
     if (!rc)
         rc = blissgpu_journeys_device(c, c->st_a.p, to ? c->st_a.p + row_n : nullptr, n_journeys, c->st_b.p, n, d, metric, dM, d_skip, k,
                                       mode, gate, gate_feature, d_idx, dist ? c->st_dist.p : nullptr);
     if (!rc) {
-        e = hipMemcpyAsync(idx, d_idx, out_n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(journeys)", hipGetErrorString(e));
+        s.down(idx, d_idx, out_n * sizeof(uint32_t));
+        s.down(dist, c->st_dist.p, out_n * sizeof(float));
     }
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    return s.finish(rc);
 }
 
 // ---- radio playlists: chains (or the k nearest of the start song) under label rules -- no artist twice within w tracks, no
@@ -2906,9 +2871,8 @@ int blissgpu_radio_device(blissgpu_ctx* c, const float* d_from, uint64_t n_radio
         launch_radio_step(a, t, plan, c->stream);
     }
     HIP_TRY(hipGetLastError());
-    uint32_t h_flags[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    uint32_t h_flags[4];
+    if ((rc = read_flags(c, flags, 4, h_flags))) return rc;
     if (h_flags[0]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance");
     return BLISSGPU_OK;
 }
@@ -2920,9 +2884,7 @@ int blissgpu_radio(const float* from, uint64_t n_radios, const float* cand, uint
     int rc = radio_args_ok(who, from, n_radios, cand, n, d, metric, M, labels, n_rules, window, limit, k, mode, idx);
     if (rc) return rc;
     if (n_radios == 0) return BLISSGPU_OK;
-    if (skip)
-        for (uint64_t i = 0; i < 2 * n_radios; i++)
-            if (skip[i] != 0xFFFFFFFFu && skip[i] >= n) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
+    if ((rc = skip_entries_ok(who, skip, 2 * n_radios, n))) return rc;
     if (n == 0) {  // no candidate: every row is padding, and no device is needed to say so
         std::fill(idx, idx + (size_t)n_radios * k, 0xFFFFFFFFu);
         if (dist) std::fill(dist, dist + (size_t)n_radios * k, INFINITY);
@@ -2946,25 +2908,22 @@ int blissgpu_radio(const float* from, uint64_t n_radios, const float* cand, uint
     uint32_t *d_idx = c->st_idx.p, *d_skip = skip ? c->st_idx.p + out_n : nullptr;
     uint32_t* d_lab = c->st_idx.p + out_n + (skip ? 2 * G : 0);
     uint32_t* d_fl = d_lab + lab_n;
-    hipError_t e = hipSuccess;
-    if (n) e = hipMemcpyAsync(c->st_b.p, cand, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && !shared) e = hipMemcpyAsync(c->st_a.p, from, row_n * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && skip) e = hipMemcpyAsync(d_skip, skip, 2 * G * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && lab_n) e = hipMemcpyAsync(d_lab, labels, lab_n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && fl_n) e = hipMemcpyAsync(d_fl, from_labels, fl_n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(radio)", hipGetErrorString(e));
+    HostStage s{c, "radio"};
+    s.up(c->st_b.p, cand, n * d * sizeof(float));
+    if (!shared) s.up(c->st_a.p, from, row_n * sizeof(float));
+    s.up(d_skip, skip, 2 * G * sizeof(uint32_t));
+    s.up(d_lab, labels, lab_n * sizeof(uint32_t));
+    s.up(d_fl, from_labels, fl_n * sizeof(uint32_t));
+    rc = s.uploaded();
     if (!rc)
         rc = blissgpu_radio_device(c, shared ? c->st_b.p : c->st_a.p, n_radios, c->st_b.p, n, d, metric, dM, n_rules ? d_lab : nullptr,
                                    fl_n ? d_fl : nullptr, n_rules, window, limit, d_skip, k, mode, d_idx,
                                    dist ? c->st_dist.p : nullptr);
     if (!rc) {
-        e = hipMemcpyAsync(idx, d_idx, out_n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(radio)", hipGetErrorString(e));
+        s.down(idx, d_idx, out_n * sizeof(uint32_t));
+        s.down(dist, c->st_dist.p, out_n * sizeof(float));
     }
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    return s.finish(rc);
 }
 
 // ---- duplicate groups of a collection: the rule of dedup_playlist_custom_distance (src/playlist.rs:381-388) over EVERY pair
@@ -3052,26 +3011,27 @@ int blissgpu_duplicate_groups(const float* x, uint64_t n, uint32_t d, const uint
     if (rc) return rc;
     uint32_t* idx = c->st_idx.p;
     float* d_dist = (pair_dist && max_pairs) ? c->st_dist.p : nullptr;
-    hipError_t e = hipMemcpyAsync(c->st_b.p, x, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && meta) e = hipMemcpyAsync(idx + o_meta, meta, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(duplicates)", hipGetErrorString(e));
+    HostStage s{c, "duplicates"};
+    s.up(c->st_b.p, x, n * d * sizeof(float));
+    s.up(idx + o_meta, meta, n * sizeof(uint32_t));
+    rc = s.uploaded();
     if (!rc)
         rc = blissgpu_duplicate_groups_device(c, c->st_b.p, n, d, meta ? idx + o_meta : nullptr, metric, dM, threshold,
                                               idx + o_label, reinterpret_cast<uint64_t*>(idx), max_pairs ? idx + o_pairs : nullptr,
                                               d_dist, max_pairs);
     if (!rc) {  // the device form has synchronised: the count is there
         uint64_t np = 0;
-        e = hipMemcpyAsync(&np, idx, sizeof(np), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(label, idx + o_label, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess && np && np <= max_pairs) {
+        s.down(&np, idx, sizeof(np));
+        s.down(label, idx + o_label, n * sizeof(uint32_t));
+        rc = s.landed();
+        if (!rc && np && np <= max_pairs) {
             // the list in ascending (i, j): the device appends in the order the wavefronts meet the edges
             std::vector<uint32_t> hp(2 * np);
             std::vector<float> hd(d_dist ? np : 0);
-            e = hipMemcpyAsync(hp.data(), idx + o_pairs, hp.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess && d_dist) e = hipMemcpyAsync(hd.data(), d_dist, np * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            if (e == hipSuccess) {
+            s.down(hp.data(), idx + o_pairs, hp.size() * sizeof(uint32_t));
+            s.down(d_dist ? hd.data() : nullptr, d_dist, np * sizeof(float));
+            rc = s.landed();
+            if (!rc) {
                 std::vector<uint64_t> at(np);
                 for (uint64_t k = 0; k < np; k++) at[k] = k;
                 std::sort(at.begin(), at.end(), [&](uint64_t a, uint64_t b) {
@@ -3084,11 +3044,9 @@ int blissgpu_duplicate_groups(const float* x, uint64_t n, uint32_t d, const uint
                 }
             }
         }
-        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(duplicates)", hipGetErrorString(e));
         if (!rc) *n_pairs = np;
     }
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    return s.finish(rc);
 }
 
 // ---- extended isolation forest (ForestOptions, src/playlist.rs:230-251): build / info / export are host-only ----
@@ -3208,19 +3166,17 @@ static int forest_host(const char* who, void* forest, const float* cand, uint64_
     if (!rc) rc = c->st_dist.ensure(n);
     if (!rc) rc = c->st_out.ensure(n * sizeof(uint64_t));
     if (rc) return rc;
-    hipError_t e = hipMemcpyAsync(c->st_b.p, cand, n * f->d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) return fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(forest)", hipGetErrorString(e));
+    HostStage s{c, "forest"};
+    s.up(c->st_b.p, cand, n * f->d * sizeof(float));
+    if ((rc = s.uploaded())) return rc;
     if (order) rc = blissgpu_forest_closest_to_songs_device(c, forest, c->st_b.p, n, reinterpret_cast<uint32_t*>(c->st_out.p), c->st_dist.p);
     else rc = blissgpu_forest_score_device(c, forest, c->st_b.p, n, c->st_dist.p, path_sum ? reinterpret_cast<uint64_t*>(c->st_out.p) : nullptr);
     if (!rc) {
-        if (score) e = hipMemcpyAsync(score, c->st_dist.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && order) e = hipMemcpyAsync(order, c->st_out.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && path_sum) e = hipMemcpyAsync(path_sum, c->st_out.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(forest)", hipGetErrorString(e));
+        s.down(score, c->st_dist.p, n * sizeof(float));
+        s.down(order, c->st_out.p, n * sizeof(uint32_t));
+        s.down(path_sum, c->st_out.p, n * sizeof(uint64_t));
     }
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    return s.finish(rc);
 }
 
 int blissgpu_forest_score(void* forest, const float* cand, uint64_t n, float* score, uint64_t* path_sum) {
@@ -3313,9 +3269,7 @@ int blissgpu_group_forest_knn(const float* seeds, const uint64_t* group_offsets,
     if (rc) return rc;
     if (n_groups == 0) return BLISSGPU_OK;
     const uint64_t n_seeds = group_offsets[n_groups];
-    if (skip)
-        for (uint64_t i = 0; i < n_seeds; i++)
-            if (skip[i] != 0xFFFFFFFFu && skip[i] >= n) return fail(BLISSGPU_ERR_INVALID, who, "skip entries must be < n or 0xFFFFFFFF");
+    if ((rc = skip_entries_ok(who, skip, n_seeds, n))) return rc;
     const size_t out_n = (size_t)n_groups * k;
     if (n == 0) {  // no candidates: rows of padding and the status, written here -- no forest, no device
         std::fill(idx, idx + out_n, 0xFFFFFFFFu);
@@ -3327,31 +3281,19 @@ int blissgpu_group_forest_knn(const float* seeds, const uint64_t* group_offsets,
         return BLISSGPU_OK;
     }
     blissgpu_ctx* c;
-    rc = default_ctx(&c);
-    if (rc) return rc;
+    if ((rc = default_ctx(&c))) return rc;
     CTX_ENTER(c, who);
-    rc = c->st_b.ensure(std::max<size_t>(1, n * d));
-    if (!rc) rc = c->st_idx.ensure(out_n + (skip ? n_seeds : 0));
-    if (!rc && score) rc = c->st_dist.ensure(out_n);
+    // (the seed rows stay on the host, where the forests are built, and so does the status they are built with)
+    GroupLists g;
+    rc = group_lists_stage(c, n_seeds, false, n, d, BLISSGPU_METRIC_EUCLIDEAN, nullptr, skip != nullptr, out_n, score ? out_n : 0, &g);
     if (rc) return rc;
-    uint32_t *d_idx = c->st_idx.p, *d_skip = (skip && n_seeds) ? c->st_idx.p + out_n : nullptr;
-    hipError_t e = hipSuccess;
-    if (n) e = hipMemcpyAsync(c->st_b.p, cand, n * d * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && d_skip) e = hipMemcpyAsync(d_skip, skip, n_seeds * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "hipMemcpyAsync(group_forest_knn)", hipGetErrorString(e));
-    if (!rc) {
+    HostStage s{c, "group_forest_knn"};
+    rc = group_lists_host(s, g, nullptr, n_seeds, cand, n, d, skip, out_n, idx, score, [&]() {
         const GroupForestOpts o{d, n_trees, sample_size, max_tree_depth, extension_level, seed};
-        rc = group_forest_run(c, who, seeds, group_offsets, n_groups, c->st_b.p, n, o, d_skip, k, d_idx, score ? c->st_dist.p : nullptr,
-                              nullptr, group_status);
-    }
-    if (!rc) {
-        e = hipMemcpyAsync(idx, d_idx, out_n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && score) e = hipMemcpyAsync(score, c->st_dist.p, out_n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(BLISSGPU_ERR_HIP, "copy back(group_forest_knn)", hipGetErrorString(e));
-    }
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+        return group_forest_run(c, who, seeds, group_offsets, n_groups, g.cand, n, o, n_seeds ? g.skip : nullptr, k, g.idx, g.dist, nullptr,
+                                group_status);
+    });
+    return s.finish(rc);
 }
 
 int blissgpu_debug_group_forest_stats(blissgpu_ctx* c, double* build_ms, double* wait_ms, uint64_t* n_batches) {

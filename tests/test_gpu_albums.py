@@ -395,3 +395,18 @@ def test_closest_albums_to_groups_against_closest_album_to_group(bliss, library)
     cut = P.closest_albums_to_groups(groups, pool, 2)
     for g, pl, full in zip(groups, cut, got):
         assert len({s.album for s in pl[len(g):]}) == 2 and [s.path for s in pl] == [s.path for s in full[:len(pl)]]
+
+
+# ---- the host form's staging: every optional argument given and NULL, then a call of another size (tests/staging_cases.py) ----
+@pytest.mark.parametrize("skip,dist,means,cents", ((True, True, True, True), (False, False, False, False), (True, True, False, False),
+                                                   (False, False, True, True), (True, False, True, False), (False, True, False, True)))
+def test_host_form_stages_like_the_device_form(bliss, ctx, skip, dist, means, cents):
+    import staging_cases as sc
+
+    def build(c, dev):
+        idx, dd = dev(sc.out((c.G, c.k), np.uint32)), dev(sc.out((c.G, c.k), np.float32, dist))
+        gm, ce = dev(sc.out((c.G, sc.D), np.float32, means)), dev(sc.out((c.n_albums, sc.D), np.float32, cents))
+        return [dev(c.S), c.off, c.G, dev(c.X), c.n, sc.D, dev(c.album_of), c.n_albums, dev(c.skip if skip else None), c.k, idx, dd, gm,
+                ce], [idx, dd, gm, ce]
+
+    sc.check(bliss, ctx, "album_knn", build)

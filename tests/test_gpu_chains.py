@@ -312,3 +312,16 @@ def test_library_chain_playlists_are_playlist_from_custom(bliss, db):
         members = [s.path for s in L.load_songs(db) if s.album == key]
         full = L.playlist_from_custom(db, members, P.euclidean_distance, P.song_to_song, deduplicate=False)
         assert [q for q, _ in got] == [s.path for s in full[len(members):][:3]], key
+
+
+# ---- the host form's staging: every optional argument given and NULL, then a call of another size (tests/staging_cases.py) ----
+@pytest.mark.parametrize("route", (1, 2))  # BLISSGPU_CHAINS_STEPS, BLISSGPU_CHAINS_LISTS
+@pytest.mark.parametrize("skip,dist", ((True, True), (False, False), (True, False), (False, True)))
+def test_host_form_stages_like_the_device_form(bliss, ctx, skip, dist, route):
+    import staging_cases as sc
+
+    def build(c, dev):
+        idx, dd = dev(sc.out((c.G, c.k), np.uint32)), dev(sc.out((c.G, c.k), np.float32, dist))
+        return [dev(c.S), c.off, c.G, dev(c.X), c.n, sc.D, 2, dev(c.M), dev(c.skip if skip else None), c.k, route, idx, dd], [idx, dd]
+
+    sc.check(bliss, ctx, "chains", build)

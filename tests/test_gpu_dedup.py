@@ -284,3 +284,17 @@ def test_two_launches_per_call_and_no_per_song_loop(bliss, monkeypatch):
     got = P.dedup_playlist_custom_distance(songs, None, P.euclidean_distance, window=64)
     assert calls == {"blissgpu_dedup_playlist": 1, "blissgpu_set_distance": 0}
     assert [s.path for s in got] == [str(i) for i in range(0, 20_000, 2)]
+
+
+# ---- the host form's staging: every optional argument given and NULL, then a call of another size (tests/staging_cases.py) ----
+@pytest.mark.parametrize("seq,meta", ((True, True), (False, False), (True, False), (False, True)))
+def test_host_form_stages_like_the_device_form(bliss, ctx, seq, meta):
+    import staging_cases as sc
+
+    def build(c, dev):
+        order = np.arange(c.n, dtype=np.uint32)[::-1].copy() if seq else None  # (seq == NULL: the rows in their own order, len == n)
+        kept, n_kept = dev(sc.out((c.n,), np.uint32)), dev(np.full(1, 0x5A5A, np.uint64))
+        return [dev(c.X), c.n, sc.D, dev(order), c.n, dev((np.arange(c.n) % 9).astype(np.uint32) if meta else None), 2, dev(c.M), 1.5, kept,
+                n_kept], [kept, n_kept]
+
+    sc.check(bliss, ctx, "dedup_playlist", build, lists=False)

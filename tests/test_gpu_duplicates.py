@@ -601,3 +601,30 @@ def test_library_duplicate_songs(bliss, tmp_path, monkeypatch):
         [[f"/music/{i:04d}.flac" for i in pair]]
     assert len(bliss.library.load_songs(db)) == n
     assert bliss.library.duplicate_songs(db, metric_builder=bliss.playlist.cosine_distance)[0][0].path == "/music/0003.flac"
+
+
+# ---- the host form's staging: every optional argument given and NULL, then a call of another size (tests/staging_cases.py) ----
+@pytest.mark.parametrize("meta,pairs,pair_dist", ((True, True, True), (False, False, False), (True, True, False), (False, True, True)))
+def test_host_form_stages_like_the_device_form(bliss, ctx, meta, pairs, pair_dist):
+    import staging_cases as sc
+
+    def build(c, dev):
+        X = c.X.copy()
+        X[40:60] = X[10:30]  # twenty planted pairs
+        label, n_pairs = dev(sc.out((c.n,), np.uint32)), dev(np.full(1, 0x5A5A, np.uint64))
+        pr, pd = dev(sc.out((64, 2), np.uint32, pairs)), dev(sc.out((64,), np.float32, pairs and pair_dist))
+        tags = np.arange(c.n, dtype=np.uint32)
+        tags[71] = tags[70]  # one more pair, by the metadata rule
+        outs = [label, n_pairs, pr, pd]
+        return [dev(X), c.n, sc.D, dev(tags if meta else None), 2, dev(c.M), 0.01] + outs + [64 if pairs else 0], outs
+
+    def canon(outs):  # the device form appends its pairs in the order the wavefronts meet them: ascending (i, j), as the host form returns them
+        _, n_pairs, pr, pd = outs
+        m = int(n_pairs.view(np.uint64)[0])
+        if pr is not None and 0 < m <= 64:
+            order = np.lexsort((pr[:m, 1], pr[:m, 0]))
+            pr[:m] = pr[:m][order]
+            if pd is not None:
+                pd[:m] = pd[:m][order]
+
+    sc.check(bliss, ctx, "duplicate_groups", build, lists=False, canon=canon)

@@ -225,3 +225,31 @@ def test_through_python_songs_and_library(bliss, tmp_path):
     assert [s.path for s in pl[3:]] == [songs[3 + i].path for i in pool_order]
     # a forest playlist is deduplicated with the euclidean rule afterwards
     assert len(P.dedup_playlist(pl)) <= len(pl)
+
+
+# ---- the host forms' staging: every optional argument given and NULL, then a call of another size (tests/staging_cases.py) ----
+@pytest.mark.parametrize("family,extra", (("forest_score", True), ("forest_score", False), ("forest_closest_to_songs", True),
+                                          ("forest_closest_to_songs", False)))
+def test_host_form_stages_like_the_device_form(bliss, ctx, family, extra):
+    import ctypes as C
+
+    import staging_cases as sc
+    from bliss_rs_amd import _ffi
+
+    lib, forests = _ffi.lib(), []
+
+    def build(c, dev):
+        f = C.c_void_p()
+        assert lib.blissgpu_forest_build(c.S.ctypes.data_as(C.c_void_p), len(c.S), sc.D, 20, 8, 0, 1, 5, C.byref(f)) == 0
+        forests.append(f)
+        if family == "forest_score":
+            score, sums = dev(sc.out((c.n,), np.float32)), dev(sc.out((c.n,), np.uint64, extra))
+            return [f, dev(c.X), c.n, score, sums], [score, sums]
+        order, score = dev(sc.out((c.n,), np.uint32)), dev(sc.out((c.n,), np.float32, extra))
+        return [f, dev(c.X), c.n, order, score], [order, score]
+
+    try:
+        sc.check(bliss, ctx, family, build, lists=family != "forest_score")
+    finally:
+        for f in forests:
+            lib.blissgpu_forest_destroy(f)

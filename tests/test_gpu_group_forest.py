@@ -333,3 +333,17 @@ def test_few_seeds_euclidean_answers_the_singles(bliss, tmp_path):
     lists = P.forest_group_playlists(by_album, songs, k, fo, few_seeds="euclidean")
     assert [[s.path for s in row] for row in lists] == [[p for p, _ in mixed[a]] for a in ("m19", "blue", "m23", "single")]
     assert P.forest_group_playlists(by_album, songs, k, fo, few_seeds="empty")[3] == []
+
+
+# ---- the host form's staging: every optional argument given and NULL, then a call of another size (tests/staging_cases.py) ----
+@pytest.mark.parametrize("skip,score,status", ((True, True, True), (False, False, False), (True, False, False), (False, True, True)))
+def test_host_form_stages_like_the_device_form(bliss, ctx, skip, score, status):
+    import staging_cases as sc
+
+    def build(c, dev):
+        idx, sco = dev(sc.out((c.G, c.k), np.uint32)), dev(sc.out((c.G, c.k), np.float32, score))
+        st = dev(sc.out((c.G,), np.int32, status))
+        seeds = [c.S] if dev(c.S) is c.S else [None, c.S]  # the device form with the seed rows on the host, as the host form has them
+        return seeds + [c.off, c.G, dev(c.X), c.n, sc.D, 20, 8, 0, 1, 5, dev(c.skip if skip else None), c.k, idx, sco, st], [idx, sco, st]
+
+    sc.check(bliss, ctx, "group_forest_knn", build)

@@ -395,3 +395,15 @@ def test_library_group_playlists_is_one_call(bliss, oracle, tmp_path, monkeypatc
     groups = [[songs[i] for i in range(n) if album[i] == key] for key in list(table)[:3]]
     got = bliss.playlist.group_playlists(groups, songs, k)
     assert [[s.path for s in row] for row in got] == [[p for p, _ in table[key]] for key in list(table)[:3]]
+
+
+# ---- the host form's staging: every optional argument given and NULL, then a call of another size (tests/staging_cases.py) ----
+@pytest.mark.parametrize("skip,dist", ((True, True), (False, False), (True, False), (False, True)))
+def test_host_form_stages_like_the_device_form(bliss, ctx, skip, dist):
+    import staging_cases as sc
+
+    def build(c, dev):
+        idx, dd = dev(sc.out((c.G, c.k), np.uint32)), dev(sc.out((c.G, c.k), np.float32, dist))
+        return [dev(c.S), c.off, c.G, dev(c.X), c.n, sc.D, 2, dev(c.M), dev(c.skip if skip else None), c.k, idx, dd], [idx, dd]
+
+    sc.check(bliss, ctx, "group_knn", build)

@@ -473,3 +473,29 @@ def test_library_group_playlists_is_one_call(bliss, oracle, tmp_path, monkeypatc
     paths = [songs[i].path for i in rows]
     got = bliss.library.playlist_from_custom(db, paths, P.VarianceWeights(), P.closest_to_songs, deduplicate=False)
     assert [s.path for s in got[len(paths):][:k]] == [p for p, _ in table[list(table)[0]]]
+
+
+# ---- the host form's staging: every optional argument given and NULL, then a call of another size (tests/staging_cases.py) ----
+@pytest.mark.parametrize("skip,dist,status,weights", ((True, True, True, True), (False, False, False, False), (True, True, True, False),
+                                                      (False, True, False, True), (True, False, True, False), (False, False, True, True)))
+def test_host_form_stages_like_the_device_form(bliss, ctx, skip, dist, status, weights):
+    import staging_cases as sc
+
+    def build(c, dev):
+        idx, dd = dev(sc.out((c.G, c.k), np.uint32)), dev(sc.out((c.G, c.k), np.float32, dist))
+        st = dev(sc.out((c.G,), np.int32, status))
+        return [dev(c.S), c.off, c.G, dev(c.X), c.n, sc.D, dev(c.W if weights else None), dev(c.skip if skip else None), c.k, idx, dd,
+                st], [idx, dd, st]
+
+    sc.check(bliss, ctx, "group_knn_weighted", build)
+
+
+@pytest.mark.parametrize("status", (True, False))
+def test_group_weights_host_form_stages_like_the_device_form(bliss, ctx, status):
+    import staging_cases as sc
+
+    def build(c, dev):
+        w, st = dev(sc.out((c.G, sc.D), np.float32)), dev(sc.out((c.G,), np.int32, status))
+        return [dev(c.S), c.off, c.G, sc.D, w, st], [w, st]
+
+    sc.check(bliss, ctx, "group_weights", build, lists=False)

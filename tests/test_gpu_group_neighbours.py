@@ -346,3 +346,21 @@ def test_library_similar_artists_round_trip(bliss, tmp_path):
     sim_d = bliss.library.similar_groups(db, 2, "artist", mode="directed")
     want_d = bliss.playlist.group_neighbours(Xdb, np.asarray(labels), 2, k=len(keys), mode="directed")
     assert [[name for name, _ in sim_d[key]] for key in keys] == [[keys[int(c)] for c in row] for row in want_d.idx]
+
+
+# ---- the host form's staging: every optional argument given and NULL, then a call of another size (tests/staging_cases.py) ----
+@pytest.mark.parametrize("queries,sizes,matrix", ((True, True, True), (False, False, False), (True, False, True), (False, True, False)))
+def test_host_form_stages_like_the_device_form(bliss, ctx, queries, sizes, matrix):
+    import staging_cases as sc
+
+    K, T = 6, 2
+
+    def build(c, dev):
+        q = c.G if queries else K
+        idx, dist = dev(sc.out((q, T), np.uint32)), dev(sc.out((q, T), np.float64))
+        sz, mat = dev(sc.out((K,), np.uint32, sizes)), dev(sc.out((K, K), np.float64, matrix))
+        qs = (np.arange(c.G) * 5 % K).astype(np.uint32) if queries else None
+        return [dev(c.X), c.n, sc.D, dev((np.arange(c.n) % K).astype(np.uint32)), K, 2, dev(c.M), dev(qs), c.G, T, 0, 0, idx, dist, sz,
+                mat], [idx, dist, sz, mat]
+
+    sc.check(bliss, ctx, "group_neighbours", build, lists=False)

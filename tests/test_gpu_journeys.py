@@ -396,3 +396,18 @@ def test_library_and_playlist_journeys(bliss, db, oracle):
             assert [s.path for s in one] == [s.path for s in table[p]], (direction, p)
     some = [paths[3], paths[1]]
     assert list(L.directed_playlists(db, k, tempo, "down", song_paths=some)) == some
+
+
+# ---- the host form's staging: every optional argument given and NULL, then a call of another size (tests/staging_cases.py) ----
+@pytest.mark.parametrize("waypoint", (True, False))  # with `to` behind `from` in the staged rows, and without
+@pytest.mark.parametrize("skip,dist", ((True, True), (False, False), (True, False), (False, True)))
+def test_host_form_stages_like_the_device_form(bliss, ctx, skip, dist, waypoint):
+    import staging_cases as sc
+
+    def build(c, dev):
+        idx, dd = dev(sc.out((c.q, c.k), np.uint32)), dev(sc.out((c.q, c.k), np.float32, dist))
+        to = np.ascontiguousarray(c.Q[::-1]) if waypoint else None
+        return [dev(c.Q), dev(to), c.q, dev(c.X), c.n, sc.D, 2, dev(c.M), dev(c.qskip2 if skip else None), c.k, int(waypoint), 0, 0, idx,
+                dd], [idx, dd]
+
+    sc.check(bliss, ctx, "journeys", build)

@@ -334,3 +334,19 @@ def test_cluster_songs(bliss, oracle, library, builder):
         keys = [(float(want[1][i]), i) for i in rows]
         assert keys == sorted(keys)
         assert rows == cl.members(c).tolist()
+
+
+# ---- the host form's staging: every optional argument given and NULL, then a call of another size (tests/staging_cases.py) ----
+@pytest.mark.parametrize("dist,sizes", ((True, True), (False, False), (True, False), (False, True)))
+def test_host_form_stages_like_the_device_form(bliss, ctx, dist, sizes):
+    import staging_cases as sc
+
+    def build(c, dev):
+        k = 4
+        labels, dd = dev(sc.out((c.n,), np.uint32)), dev(sc.out((c.n,), np.float32, dist))
+        cent, sz = dev(sc.out((k, sc.D), np.float32)), dev(sc.out((k,), np.uint32, sizes))
+        n_iter, conv = np.full(1, 99, np.uint32), np.full(1, 99, np.int32)  # (host memory in both forms)
+        outs = [labels, dd, cent, sz, n_iter, conv]
+        return [dev(c.X), c.n, sc.D, dev(np.ascontiguousarray(c.X[:k])), k, 2, dev(c.M), 6] + outs, outs
+
+    sc.check(bliss, ctx, "kmeans", build, lists=False)

@@ -466,3 +466,15 @@ def test_unaligned_candidates(ctx, oracle):
                 dist[g, 1] = np.float32(0.0) + row[idx[g, 1]]
             for name, tX in zip(("aligned", "offset"), pair(X)):
                 assert_same(out(ctx.chains(tQ[:2], [0, 1, 2], tX, 2, metric, route="steps")), (idx, dist), (n, "chain", name))
+
+
+# ---- the host form's staging: every optional argument given and NULL, then a call of another size (tests/staging_cases.py) ----
+@pytest.mark.parametrize("skip,dist", ((True, True), (False, False), (True, False), (False, True)))
+def test_host_form_stages_like_the_device_form(bliss, ctx, skip, dist):
+    import staging_cases as sc
+
+    def build(c, dev):
+        idx, dd = dev(sc.out((c.q, c.k), np.uint32)), dev(sc.out((c.q, c.k), np.float32, dist))
+        return [dev(c.Q), c.q, dev(c.X), c.n, sc.D, 2, dev(c.M), dev(c.qskip if skip else None), c.k, idx, dd], [idx, dd]
+
+    sc.check(bliss, ctx, "knn", build)

@@ -305,3 +305,20 @@ def test_library_layer_end_to_end(bliss, planted, tmp_path):
     assert res.dof == int(tagged.sum()) - len(code) and np.array_equal(bits(res.scatter), bits(want.scatter))
     clustering = P.Clustering(*P.kmeans(Xdb, P.kmeans_init(Xdb, 4, 1)))
     assert np.array_equal(bits(Lb.covariance_metric(db, clustering)), bits(P.covariance_metric(Xdb, clustering.labels).m))
+
+
+# ---- the host form's staging: every optional argument given and NULL, then a call of another size (tests/staging_cases.py) ----
+@pytest.mark.parametrize("labels,m2,extrema,scatter", ((True, True, True, True), (False, False, False, False), (True, False, True, False),
+                                                       (True, True, False, True), (False, True, True, False)))
+def test_host_form_stages_like_the_device_form(bliss, ctx, labels, m2, extrema, scatter):
+    import staging_cases as sc
+
+    def build(c, dev):
+        k = 4 if labels else 1
+        counts, mean = dev(sc.out((k,), np.uint32)), dev(sc.out((k, sc.D), np.float64))
+        s2, S = dev(sc.out((k, sc.D), np.float64, m2)), dev(sc.out((sc.D, sc.D), np.float64, scatter))
+        mn, mx = dev(sc.out((k, sc.D), np.float32, extrema)), dev(sc.out((k, sc.D), np.float32, extrema))
+        lab = (np.arange(c.n) % k).astype(np.uint32) if labels else None
+        return [dev(c.X), c.n, sc.D, dev(lab), k, counts, mean, s2, mn, mx, S], [counts, mean, s2, mn, mx, S]
+
+    sc.check(bliss, ctx, "moments", build, lists=False)

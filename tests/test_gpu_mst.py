@@ -250,3 +250,18 @@ def test_launches(bliss, ctx):
     assert torch.is_tensor(u) and u.is_cuda and u.dtype == torch.int32 and w.dtype == torch.float32
     t = P.minimum_spanning_tree(X, min_samples=5)
     assert same_tree((u.cpu().numpy().astype(np.int64), v.cpu().numpy().astype(np.int64), w.cpu().numpy()), (t.u, t.v, t.w))
+
+
+# ---- the host form's staging: core given and NULL, then a call of another size (tests/staging_cases.py) ----
+@pytest.mark.parametrize("core", (True, False))
+def test_host_form_stages_like_the_device_form(bliss, ctx, core):
+    import staging_cases as sc
+
+    def build(c, dev):
+        X = c.X + (np.arange(c.n, dtype=np.float32) * np.float32(1e-3))[:, None]  # (no two rows equal)
+        cr = np.linspace(0.0, 0.5, c.n).astype(np.float32) if core else None
+        u, v, w = dev(sc.out((c.n - 1,), np.uint32)), dev(sc.out((c.n - 1,), np.uint32)), dev(sc.out((c.n - 1,), np.float32))
+        rounds = np.full(1, 99, np.uint32)  # (host memory in both forms)
+        return [dev(X), c.n, sc.D, 2, dev(c.M), dev(cr), u, v, w, rounds], [u, v, w, rounds]
+
+    sc.check(bliss, ctx, "mst", build, lists=False)

@@ -186,3 +186,26 @@ def test_library_drives_the_ordering_kernels(bliss, oracle, tmp_path):
     assert [paths[i] for i in order] == [s.path for s in via_songs]
     chain = ctx.song_to_song(X[:1], X, "euclidean").cpu().numpy()
     assert np.array_equal(chain, oracle.song_to_song(m[:1], m, "euclidean"))
+
+
+# ---- the host forms' staging: every optional argument given and NULL, then a call of another size (tests/staging_cases.py) ----
+@pytest.mark.parametrize("family,dist", (("set_distance", False), ("closest_to_songs", True), ("closest_to_songs", False),
+                                         ("song_to_song", False)))
+def test_host_form_stages_like_the_device_form(bliss, family, dist):
+    import staging_cases as sc
+
+    def build(c, dev):
+        head = [dev(c.S), len(c.S), dev(c.X), c.n, sc.D, 2, dev(c.M)]
+        if family == "set_distance":
+            outs = [dev(sc.out((c.n,), np.float32))]
+        elif family == "song_to_song":
+            outs = [dev(sc.out((c.n,), np.uint32))]
+        else:
+            outs = [dev(sc.out((c.n,), np.uint32)), dev(sc.out((c.n,), np.float32, dist))]
+        return head + outs, outs
+
+    ctx = bliss.Context(0)
+    try:
+        sc.check(bliss, ctx, family, build, lists=family != "set_distance")
+    finally:
+        ctx.close()

@@ -297,3 +297,20 @@ def test_radio_playlist_is_radio_order(bliss):
     idx, _ = P.radio_order(X[[0]], X, k, P.rule_labels(songs, P.DEFAULT_RADIO_RULES), [5, 20], [1, 1],
                            P.rule_labels(songs, P.DEFAULT_RADIO_RULES)[:, [0]].T, skip=[[0, -1]])
     assert [s.path for s in default] == [songs[j].path for j in idx[0] if j >= 0]
+
+
+# ---- the host form's staging: every optional argument given and NULL, then a call of another size (tests/staging_cases.py) ----
+@pytest.mark.parametrize("skip,dist,rules,from_labels", ((True, True, True, True), (False, False, False, False), (True, False, True, False),
+                                                         (False, True, True, True), (True, True, False, False)))
+def test_host_form_stages_like_the_device_form(bliss, ctx, skip, dist, rules, from_labels):
+    import staging_cases as sc
+
+    def build(c, dev):
+        idx, dd = dev(sc.out((c.q, c.k), np.uint32)), dev(sc.out((c.q, c.k), np.float32, dist))
+        lab = np.stack([np.arange(c.n) % 7, np.arange(c.n) % 11]).astype(np.uint32) if rules else None  # [rule][candidate]
+        fl = np.stack([np.arange(c.q) % 7, np.arange(c.q) % 11], 1).astype(np.uint32) if rules and from_labels else None
+        window, limit = np.array([2, 4], np.uint32), np.array([1, 2], np.uint32)  # (host arrays in both forms)
+        return [dev(c.Q), c.q, dev(c.X), c.n, sc.D, 2, dev(c.M), dev(lab), dev(fl), 2 if rules else 0, window, limit,
+                dev(c.qskip2 if skip else None), c.k, 0, idx, dd], [idx, dd]
+
+    sc.check(bliss, ctx, "radio", build)

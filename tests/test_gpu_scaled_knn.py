@@ -414,3 +414,34 @@ def test_local_scaling_removes_most_of_the_hubness(bliss):
           f"{h_scaled.orphans().size} orphans")
     assert h_scaled.skewness < 0.5 * h_raw.skewness
     assert h_scaled.orphans().size < 0.1 * h_raw.orphans().size
+
+
+# ---- the host forms' staging: every optional argument given and NULL, then a call of another size (tests/staging_cases.py) ----
+@pytest.mark.parametrize("shared", (False, True))  # the queries ARE the candidates with the same scales: they travel once
+@pytest.mark.parametrize("skip,dist", ((True, True), (False, False), (True, False), (False, True)))
+def test_host_form_stages_like_the_device_form(bliss, ctx, skip, dist, shared):
+    import staging_cases as sc
+
+    def build(c, dev):
+        q = c.n if shared else c.q
+        cs = np.linspace(0.5, 2.0, c.n).astype(np.float32)
+        X = dev(c.X)  # (one array for both roles in the shared case: the host form tells by the pointers)
+        dcs = dev(cs)
+        Q, qs = (X, dcs) if shared else (dev(c.Q), dev(np.linspace(0.7, 1.5, c.q).astype(np.float32)))
+        sk = (np.arange(c.n, dtype=np.uint32) if shared else c.qskip) if skip else None
+        idx, dd = dev(sc.out((q, c.k), np.uint32)), dev(sc.out((q, c.k), np.float32, dist))
+        return [Q, q, qs, X, c.n, dcs, sc.D, 2, dev(c.M), dev(sk), c.k, idx, dd], [idx, dd]
+
+    sc.check(bliss, ctx, "scaled_knn", build)
+
+
+def test_knn_occurrence_host_form_stages_like_the_device_form(bliss, ctx):
+    import staging_cases as sc
+
+    def build(c, dev):
+        idx = (np.arange(c.q * c.k, dtype=np.uint32) * 37 % c.n).reshape(c.q, c.k)
+        idx[0, -1] = sc.NONE
+        count = dev(sc.out((c.n,), np.uint32))
+        return [dev(idx), c.q, c.k, c.n, count], [count]
+
+    sc.check(bliss, ctx, "knn_occurrence", build, lists=False)

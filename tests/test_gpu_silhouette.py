@@ -427,3 +427,18 @@ def test_library_choose_clusters_and_label_silhouette(bliss, oracle, library):
     assert_same((silw.values, silw.a, silw.b, silw.neighbour, silw.sizes), reference(oracle, X[keep], labels, 3, "mahalanobis", W), None, "weights")
     by_artist, artists = bliss.library.label_silhouette(db, "artist")
     assert len(artists) == 9 and len(by_artist.values) == 240 and by_artist.score < sil.score
+
+
+# ---- the host form's staging: every optional argument given and NULL, then a call of another size (tests/staging_cases.py) ----
+@pytest.mark.parametrize("rows,extras", ((True, True), (False, False), (True, False), (False, True)))
+def test_host_form_stages_like_the_device_form(bliss, ctx, rows, extras):
+    import staging_cases as sc
+
+    def build(c, dev):
+        q = c.q if rows else c.n
+        s, a, b = dev(sc.out((q,), np.float32)), dev(sc.out((q,), np.float64, extras)), dev(sc.out((q,), np.float64, extras))
+        nb, sizes = dev(sc.out((q,), np.uint32, extras)), dev(sc.out((4,), np.uint32, extras))
+        r = (np.arange(c.q) * 7 % c.n).astype(np.uint32) if rows else None
+        return [dev(c.X), c.n, sc.D, dev((np.arange(c.n) % 4).astype(np.uint32)), 4, 2, dev(c.M), dev(r), c.q, 0, s, a, b, nb, sizes], [s, a, b, nb, sizes]
+
+    sc.check(bliss, ctx, "silhouette", build, lists=False)
