@@ -16,10 +16,12 @@ NONE = 0xFFFFFFFF
 
 class Case:
     """the inputs of one shape: X [n, d], the groups' seeds S with offsets off and one skip entry per seed (its own row; one
-    of them "none"), q rows Q with their skip entries, labels for the albums and the radio rules, a full Mahalanobis M"""
+    of them "none"), q rows Q with their skip entries, labels for the albums and the radio rules, a full Mahalanobis M.
+    seed: None = the bytes every staging test has always had; a number = another draw of the same shapes, as valid as the
+    first (tests/test_gpu_streams.py takes seed=1 as the decoy its buffers hold before the real inputs arrive)"""
 
-    def __init__(self, n, sizes, k, q):
-        rng = np.random.default_rng(n)
+    def __init__(self, n, sizes, k, q, seed=None):
+        rng = np.random.default_rng(n if seed is None else (n, seed))
         self.n, self.k, self.q, self.G = n, k, q, len(sizes)
         self.X = (rng.integers(-8, 9, (n, D)) / 8).astype(np.float32)  # a grid of eighths: ties at the cut
         self.off = np.concatenate(([0], np.cumsum(sizes))).astype(np.uint64)

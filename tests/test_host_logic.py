@@ -560,3 +560,282 @@ def test_musical_bench_batch_is_seeded_per_song():
     assert x.dtype == np.float32 and len(x) == 30000 and np.array_equal(x, a[2])
     c, _ = musical_batch(1, 30000, seed=6, procs=1)
     assert not np.array_equal(c[0], a[0])
+
+
+# ---- stream order of device.Context (the GPU half is tests/test_gpu_streams.py) ----
+def _device_entry_points():
+    """the C symbols that take device pointers and run on the context's stream: every `*_device` name of the signature table
+    (the two synth forms are among them)"""
+    from bliss_rs_amd import _ffi
+
+    return {s for s in _ffi.SIGNATURES if s.endswith("_device")}
+
+
+def _stream_bracket_faults(source, entry_points):
+    """Every call of a device entry point in a method of device.Context must stand between a `self._pre()` and a
+    `self._post()` of one statement list (its own, or one that encloses it: synth_white_noise brackets an `if`), with no
+    upload of an input between the `_pre()` and the call and no read of an output between the call and the `_post()`.
+    -> [(method, line, what is wrong)]"""
+    import ast
+
+    def attr_call(node, owner, name=None):  # owner.name(...) with owner a plain name chain such as self._L
+        if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute)):
+            return None
+        if ast.unparse(node.func.value) != owner:
+            return None
+        return node.func.attr if name is None or node.func.attr == name else None
+
+    def is_marker(stmt, name):
+        return isinstance(stmt, ast.Expr) and attr_call(stmt.value, "self", name) is not None
+
+    def c_calls(node):
+        return [n for n in ast.walk(node) if attr_call(n, "self._L") in entry_points]
+
+    def touches(stmt, names, subscripts):
+        """a method call named in `names` (x.to(...), x.cuda(), torch.from_numpy(...)) or, with `subscripts`, an indexing"""
+        for n in ast.walk(stmt):
+            if isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and n.func.attr in names:
+                return n.func.attr
+            if subscripts and isinstance(n, ast.Subscript):
+                return "indexing"
+        return None
+
+    UPLOADS, READS = ("to", "cuda", "from_numpy"), ("to", "cpu", "numpy", "item", "tolist")
+    faults = []
+
+    def upload_helpers(fn):
+        """the names a method binds to a function of its own (a nested def, `name = lambda ...`) whose body uploads: silhouette's
+        up_f32 / up_u32, kmeans' and mst's `up`.  A call of one is an upload like a bare `.to(dev)`"""
+        found = set()
+        for n in ast.walk(fn):
+            if isinstance(n, ast.FunctionDef) and n is not fn and touches(n, UPLOADS, False):
+                found.add(n.name)
+            if isinstance(n, ast.Assign) and isinstance(n.value, ast.Lambda) and touches(n.value, UPLOADS, False):
+                found |= {t.id for t in n.targets if isinstance(t, ast.Name)}
+        return found
+
+    def uploads(stmt, helpers):
+        hit = touches(stmt, UPLOADS, False)
+        if hit:
+            return hit
+        for n in ast.walk(stmt):
+            if isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id in helpers:
+                return n.func.id
+        return None
+
+    def visit(stmts, method, helpers):
+        """-> the device calls of this list that no bracket of this list (or a deeper one) encloses"""
+        loose = []
+        for i, stmt in enumerate(stmts):
+            inner = []
+            blocks = [getattr(stmt, f) for f in ("body", "orelse", "finalbody") if isinstance(getattr(stmt, f, None), list)]
+            blocks += [h.body for h in getattr(stmt, "handlers", [])]
+            if blocks and not isinstance(stmt, (ast.FunctionDef, ast.Lambda, ast.ClassDef)):
+                for b in blocks:
+                    inner += visit(b, method, helpers)
+            else:
+                inner = c_calls(stmt)
+            if not inner:
+                continue
+            pre = max((p for p in range(i) if is_marker(stmts[p], "_pre")), default=None)
+            post = min((p for p in range(i + 1, len(stmts)) if is_marker(stmts[p], "_post")), default=None)
+            if pre is None or post is None:
+                loose += inner
+                continue
+            between = stmts[pre + 1:i] + ([s for b in blocks for s in b if not c_calls(s)] if blocks else [])
+            for s in between:
+                if c_calls(s):
+                    continue  # (another bracketed call of the same list is judged on its own)
+                hit = uploads(s, helpers)
+                if hit:
+                    faults.append((method, s.lineno, f"`{hit}` between _pre() and the device call: an upload the context does not wait for"))
+            for s in stmts[i + 1:post]:
+                hit = touches(s, READS, True)
+                if hit:
+                    faults.append((method, s.lineno, f"`{hit}` between the device call and _post(): an output read before it is ordered"))
+        return loose
+
+    tree = ast.parse(source)
+    ctx = next(n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == "Context")
+    seen = set()
+    for fn in ctx.body:
+        if not isinstance(fn, ast.FunctionDef) or not c_calls(fn):
+            continue
+        seen |= {attr_call(n, "self._L") for n in c_calls(fn)}
+        for call in visit(fn.body, fn.name, upload_helpers(fn)):
+            faults.append((fn.name, call.lineno, f"{call.func.attr} is not between a _pre() and a _post() of one statement list"))
+    return faults, seen
+
+
+# every way the bracket can be wrong, as small methods beside the checker (name -> whether it must be reported)
+_BRACKET_SAMPLES = '''
+class Context:
+    def good(self, X):
+        def up(a):
+            return torch.from_numpy(a).to(dev)
+        X = up(X)
+        out = torch.empty(3)
+        self._pre()
+        _ffi.check(self._L.blissgpu_knn_device(self._h, ptr(X), ptr(out)))
+        self._post()
+        return out.to(torch.int64)
+
+    def good_around_an_if(self, X, indexed):
+        self._pre()
+        if indexed:
+            idx = np.ascontiguousarray(indexed)
+            _ffi.check(self._L.blissgpu_knn_device(self._h, ptr(X), idx.ctypes.data))
+        else:
+            _ffi.check(self._L.blissgpu_chains_device(self._h, ptr(X)))
+        self._post()
+
+    def good_inside_an_if(self, X, weights):
+        if weights is not None:
+            self._pre()
+            _ffi.check(self._L.blissgpu_chains_device(self._h, ptr(X)))
+            self._post()
+            return
+        self._pre()
+        _ffi.check(self._L.blissgpu_knn_device(self._h, ptr(X)))
+        self._post()
+
+    def bad_no_pre(self, X):
+        _ffi.check(self._L.blissgpu_knn_device(self._h, ptr(X)))
+        self._post()
+
+    def bad_no_post(self, X):
+        self._pre()
+        _ffi.check(self._L.blissgpu_knn_device(self._h, ptr(X)))
+        return X
+
+    def bad_no_pre_inside_an_if(self, X, weights):
+        if weights is not None:
+            _ffi.check(self._L.blissgpu_chains_device(self._h, ptr(X)))
+            self._post()
+            return
+        self._pre()
+        _ffi.check(self._L.blissgpu_knn_device(self._h, ptr(X)))
+        self._post()
+
+    def bad_pre_above_an_upload(self, X):
+        self._pre()
+        X = torch.from_numpy(X).to(dev)
+        _ffi.check(self._L.blissgpu_knn_device(self._h, ptr(X)))
+        self._post()
+
+    def bad_pre_above_a_helper_that_uploads(self, X, labels):
+        def up_f32(a):
+            return a if torch.is_tensor(a) else torch.from_numpy(a).to(dev)
+        self._pre()
+        X = up_f32(X)
+        _ffi.check(self._L.blissgpu_knn_device(self._h, ptr(X)))
+        self._post()
+
+    def bad_pre_above_a_lambda_that_uploads(self, X):
+        up = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+        ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        self._pre()
+        X = up(X)
+        _ffi.check(self._L.blissgpu_knn_device(self._h, ptr(X)))
+        self._post()
+
+    def bad_pre_above_a_conversion(self, X, labels):
+        self._pre()
+        labels = labels.to(torch.int32)
+        _ffi.check(self._L.blissgpu_knn_device(self._h, ptr(X), ptr(labels)))
+        self._post()
+
+    def bad_read_before_post(self, X, order):
+        self._pre()
+        _ffi.check(self._L.blissgpu_knn_device(self._h, ptr(X), ptr(order)))
+        order = order.to(torch.int64)
+        self._post()
+        return order
+
+    def bad_index_before_post(self, X, out):
+        self._pre()
+        _ffi.check(self._L.blissgpu_knn_device(self._h, ptr(X), ptr(out)))
+        first = out[:3]
+        self._post()
+        return first
+'''
+
+
+def _method_lines(source, method):
+    """-> (the lines of the `self._pre()` statements of Context.<method>, those of its `self._post()`, the line of its first
+    statement that calls one of its own up* helpers, or None): where the edits below cut, found in the tree, not by matching text"""
+    import ast
+
+    ctx = next(n for n in ast.parse(source).body if isinstance(n, ast.ClassDef) and n.name == "Context")
+    fn = next(n for n in ctx.body if isinstance(n, ast.FunctionDef) and n.name == method)
+    marks = {"_pre": [], "_post": []}
+    for n in ast.walk(fn):
+        if isinstance(n, ast.Expr) and isinstance(n.value, ast.Call) and ast.unparse(n.value.func) in ("self._pre", "self._post"):
+            marks[n.value.func.attr].append(n.lineno)
+    first_up = next((st.lineno for st in fn.body if not isinstance(st, ast.FunctionDef) and not isinstance(getattr(st, "value", None), ast.Lambda)
+                     and any(isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id.startswith("up") for n in ast.walk(st))), None)
+    return marks["_pre"], marks["_post"], first_up
+
+
+def test_every_device_call_of_context_is_bracketed_by_pre_and_post():
+    source = open(os.path.join(ROOT, "bliss-rs_amd", "device.py")).read()
+    import test_gpu_streams as ts
+
+    entry = _device_entry_points() - set(ts.EXCLUDED)  # (blissgpu_default_device takes no device pointer)
+    faults, seen = _stream_bracket_faults(source, entry)
+    assert not faults, faults
+    assert len(seen) >= 35 and "blissgpu_group_knn_device" in seen and "blissgpu_group_knn_weighted_device" in seen
+
+    # the check itself, on the samples above: every bad_* method is reported, no good* one
+    reported = {f[0] for f in _stream_bracket_faults(_BRACKET_SAMPLES, entry)[0]}
+    names = set(re.findall(r"def ((?:good|bad_)\w*)\(self", _BRACKET_SAMPLES))
+    assert len(names) == 12 and reported == {n for n in names if n.startswith("bad_")}, sorted(reported ^ {n for n in names if n.startswith("bad_")})
+
+    # ... and on device.py itself: the edits a host layer rewrite is most likely to make, cut by line
+    lines = source.splitlines(keepends=True)
+
+    def without(*drop, insert=None):
+        out = [ln for i, ln in enumerate(lines, 1) if i not in drop]
+        if insert:
+            at, text = insert
+            out.insert(at - 1 - sum(d < at for d in drop), text)
+        return [f[0] for f in _stream_bracket_faults("".join(out), entry)[0]]
+
+    pre, post, _ = _method_lines(source, "knn")
+    assert len(pre) == len(post) == 1 and without(pre[0]) == ["knn"]
+    pre, post, _ = _method_lines(source, "chains")
+    assert len(pre) == len(post) == 1 and without(post[0]) == ["chains"]
+    pre, post, _ = _method_lines(source, "group_knn")
+    assert len(pre) == len(post) == 2 and all(without(ln) == ["group_knn"] for ln in pre + post)
+    # _pre() moved above the wrapper's own uploads: silhouette's nested up_f32 / up_u32, kmeans' lambda `up`
+    for method, hits in (("silhouette", 2), ("kmeans", 1), ("mst", 1), ("group_neighbours", 2)):
+        pre, post, first = _method_lines(source, method)
+        assert len(pre) == len(post) == 1 and first is not None and first < pre[0], method
+        early = "        self._pre()\n"
+        assert without(pre[0], insert=(first, early)) == [method] * hits, method  # one report per statement that uploads
+        assert without(insert=(first, early)) == [], method  # (a second, early _pre() does no harm: the late one stands)
+
+
+def test_every_device_entry_point_has_a_stream_order_case():
+    """tests/test_gpu_streams.py's table against the signature table: a new `*_device` family without a case fails here"""
+    import test_gpu_streams as ts
+
+    named = {e for c in ts.CASES for e in c.entry}
+    entry = _device_entry_points()
+    assert all(len(reason) > 20 for reason in ts.EXCLUDED.values())
+    assert set(ts.EXCLUDED) <= entry and not named & set(ts.EXCLUDED)
+    assert named == entry - set(ts.EXCLUDED), (sorted(entry - set(ts.EXCLUDED) - named), sorted(named - entry))
+    assert {"blissgpu_synth_white_noise_device", "blissgpu_synth_white_noise_indexed_device", "blissgpu_knn_occurrence_device"} <= named
+    # what the issue of this table asks for by name: both group_knn forms, both modes of journeys and radio
+    by_entry = {}
+    for c in ts.CASES:
+        for e in c.entry:
+            by_entry.setdefault(e, []).append(c.name)
+    assert len(by_entry["blissgpu_journeys_device"]) == 2 and len(by_entry["blissgpu_radio_device"]) == 2
+    assert len(by_entry["blissgpu_mst_device"]) >= 2
+    # every decoy has the shapes and dtypes of the real inputs
+    for c in ts.CASES:
+        real, decoy = c.inputs(False), c.inputs(True)
+        for k in real:
+            if not k.startswith("h_"):
+                assert real[k].shape == decoy[k].shape and real[k].dtype == decoy[k].dtype and not np.array_equal(real[k], decoy[k]), (c.name, k)
