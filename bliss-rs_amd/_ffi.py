@@ -174,6 +174,10 @@ SIGNATURES = {
                                  C.c_uint32, C.c_int, _vp, _vp]),
     "blissgpu_radio_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, _vp, C.c_uint32, _vp,
                                         _vp, _vp, C.c_uint32, C.c_int, _vp, _vp]),
+    "blissgpu_map_step": (C.c_int, [_vp, C.c_uint64, _vp, _vp, _vp, C.c_float, C.c_uint32, _vp, _vp, _vp]),
+    "blissgpu_map_layout": (C.c_int, [_vp, C.c_uint64, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_float, C.c_double, C.c_double,
+                                      C.c_double, C.c_double, C.c_uint32, _vp, _vp]),
+    "blissgpu_map_plan": (C.c_int, [C.c_uint64, C.c_uint32, _u32p]),
     "blissgpu_duplicate_groups": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.c_int, _vp, C.c_float, _vp, _u64p, _vp, _vp,
                                             C.c_uint64]),
     "blissgpu_duplicate_groups_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_int, _vp, C.c_float, _vp, _vp, _vp,

@@ -11,6 +11,7 @@
 #include <chrono>
 #include <deque>
 #include <mutex>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -43,6 +44,8 @@ const char kChamferSelectName[] = "chamfer_select_kernel";
 const char kMstScanName[] = "mst_scan_kernel", kMstPickName[] = "mst_pick_kernel";  // KX_MST_*
 const char kScaledKnnScanName[] = "scaled_knn_scan_kernel", kKnnOccurrenceName[] = "knn_occurrence_kernel";  // KX_SCALED_KNN_SCAN, KX_KNN_OCCURRENCE
 const char kRadioBanName[] = "radio_ban_kernel", kRadioStepName[] = "radio_step_kernel";  // KX_RADIO_BAN, KX_RADIO_STEP
+const char kMapRepulseName[] = "map_repulse_kernel", kMapAttractName[] = "map_attract_kernel";  // KX_MAP_*
+const char kMapUpdateName[] = "map_update_kernel";
 const char* const kKernelNames[K_COUNT] = {
     "fft512_kernel",     "onset_kernel",      "beat_kernel",   "stft8192_kernel", "tune_select_kernel",
     "tune_pass2_kernel", "tune_final_kernel", "chroma_kernel",     "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel", "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel",
@@ -60,6 +63,7 @@ const char* const kKernelNames[K_COUNT] = {
     kMstScanName, kMstPickName,
     kScaledKnnScanName, kKnnOccurrenceName,
     kRadioBanName, kRadioStepName,
+    kMapRepulseName, kMapAttractName, kMapUpdateName,
     kGroupForestScanName, kJourneyStepName};
 }  // namespace
 
@@ -385,7 +389,7 @@ int blissgpu_ctx_destroy(blissgpu_ctx* c) {
         (void)hipFree(c->bt_rwv); (void)hipFree(c->bt_dfwv); (void)hipFree(c->chroma_bank);
         scheduler_release(c);
         c->dbg_tuning.release(); c->dbg_nbpms.release(); c->dbg_chroma.release(); c->dbg_interval.release();
-        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->km_ws.release(); c->sil_ws.release(); c->mo_ws.release(); c->ch_ws.release(); c->ms_ws.release(); c->mt_ws.release(); c->pl_next.release(); c->st_idx.release();
+        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->km_ws.release(); c->sil_ws.release(); c->mo_ws.release(); c->ch_ws.release(); c->ms_ws.release(); c->map_ws.release(); c->mt_ws.release(); c->pl_next.release(); c->st_idx.release();
         c->st_a.release(); c->st_b.release(); c->st_m.release(); c->st_dist.release(); c->st_out.release();
         c->fl_bytes.release(); c->fl_tab.release(); c->fl_pcm.release(); c->fl_status.release(); c->fl_end.release();
         c->fl_bad.release(); c->fl_mono.release(); c->fl_rows.release(); c->fl_htab.release();
@@ -2924,6 +2928,224 @@ int blissgpu_radio(const float* from, uint64_t n_radios, const float* cand, uint
         s.down(dist, c->st_dist.p, out_n * sizeof(float));
     }
     return s.finish(rc);
+}
+
+// ---- the 2-D map of a library: exact t-SNE gradients and the momentum / gain loop around them (kernels_map.hip, DESIGN.md
+// 3.31).  Host-pointer forms only; map_step_core / map_layout_core take the context and device pointers, so a device-pointer
+// form is an export away ----
+int blissgpu_map_plan(uint64_t n, uint32_t n_cus, uint32_t* col_groups) {
+    const char* who = "blissgpu_map_plan";
+    if (!col_groups) return fail(BLISSGPU_ERR_INVALID, who, "col_groups is NULL");
+    if (n >= (1ull << 24)) return fail(BLISSGPU_ERR_INVALID, who, "n must be below 2^24 rows");
+    *col_groups = map_plan_col_groups(n, (int)std::min<uint32_t>(n_cus, 1u << 20));
+    return BLISSGPU_OK;
+}
+
+// everything that can be said about y and the CSR arrays in host memory; long_rows: the rows of more than MAP_LONG_ROW entries
+static int map_input_ok(const char* who, const float* y, uint64_t n, const uint64_t* row_offsets, const uint32_t* cols, const float* vals,
+                        uint32_t col_groups, std::vector<uint32_t>* long_rows) {
+    if (n >= (1ull << 24)) return fail(BLISSGPU_ERR_INVALID, who, "n must be below 2^24 rows");
+    if (col_groups > MAP_MAX_COL_GROUPS) return fail(BLISSGPU_ERR_INVALID, who, "col_groups must be 0 .. 64");
+    if (n == 0) return BLISSGPU_OK;
+    if (!y) return fail(BLISSGPU_ERR_INVALID, who, "y is NULL");
+    if (!row_offsets) return fail(BLISSGPU_ERR_INVALID, who, "row_offsets is NULL");
+    if (row_offsets[0] != 0) return fail(BLISSGPU_ERR_INVALID, who, "row_offsets[0] must be 0");
+    for (uint64_t i = 0; i < n; i++)
+        if (row_offsets[i + 1] < row_offsets[i]) return fail(BLISSGPU_ERR_INVALID, who, "row_offsets must not decrease");
+    const uint64_t nnz = row_offsets[n];
+    if (nnz >= (1ull << 32)) return fail(BLISSGPU_ERR_INVALID, who, "nnz must be below 2^32 entries");
+    if (nnz && !cols) return fail(BLISSGPU_ERR_INVALID, who, "cols is NULL");
+    if (nnz && !vals) return fail(BLISSGPU_ERR_INVALID, who, "vals is NULL");
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t e0 = row_offsets[i], e1 = row_offsets[i + 1];
+        for (uint64_t e = e0; e < e1; e++) {
+            if (cols[e] >= n) return fail(BLISSGPU_ERR_INVALID, who, "a column index is >= n");
+            if (cols[e] == i) return fail(BLISSGPU_ERR_INVALID, who, "a row holds itself");
+            if (e > e0 && cols[e] <= cols[e - 1]) return fail(BLISSGPU_ERR_INVALID, who, "a row's columns must be strictly ascending");
+            if (!(vals[e] >= 0.0f) || !std::isfinite(vals[e])) return fail(BLISSGPU_ERR_INVALID, who, "vals must be finite and >= 0");
+        }
+        if (e1 - e0 > MAP_LONG_ROW) long_rows->push_back((uint32_t)i);
+    }
+    return BLISSGPU_OK;
+}
+
+// how the scan is fed y_j (for the bench tool: no bit of the result depends on it)
+static int map_feed() {
+    const char* e = getenv("BLISSGPU_MAP_FEED");
+    if (e && !strcmp(e, "scalar")) return MAP_FEED_SCALAR;
+    return MAP_FEED_LDS;  // the measured choice
+}
+
+// the scratch of the gradient: col_groups == 0 resolved, the plan, and sums | part | zb | att | U | gain carved out of map_ws;
+// counted against the workspace limit together with the trace the caller keeps on the device (trace_doubles)
+static int map_scratch(blissgpu_ctx* c, const char* who, uint32_t col_groups, size_t trace_doubles, MapArgs* a, MapPlan* plan) {
+    const size_t n = a->n;
+    *plan = map_plan(n, col_groups ? col_groups : map_plan_col_groups(n, c->n_cus));
+    const size_t part = plan->chunks > 1 ? (size_t)plan->chunks * 3 * n : 0;
+    const size_t doubles = 3 * n + part + plan->blocks + 6 * n;
+    if ((doubles + trace_doubles) * sizeof(double) > c->ws_limit)
+        return fail(BLISSGPU_ERR_OOM, who, "the column groups' partial sums and the trace do not fit the workspace limit");
+    int rc = c->map_ws.ensure(doubles * sizeof(double));
+    if (rc) return rc;
+    double* w = reinterpret_cast<double*>(c->map_ws.p);
+    a->sums = w;
+    a->part = w + 3 * n;
+    a->zb = a->part + part;
+    a->att = a->zb + plan->blocks;
+    a->U = a->att + 2 * n;
+    a->gain = a->U + 2 * n;
+    return BLISSGPU_OK;
+}
+
+// one gradient evaluation and what follows it (a.grad: stored; else the update), queued on the context's stream
+static void map_eval(blissgpu_ctx* c, const MapArgs& a, const MapPlan& plan, int feed) {
+    { Prof p(c, KX_MAP_REPULSE); launch_map_repulse(a, plan, feed, c->stream); }
+    { Prof p(c, KX_MAP_ATTRACT); launch_map_attract(a, plan, c->stream); }
+    if (a.n_long) { Prof p(c, KX_MAP_ATTRACT); launch_map_attract_long(a, c->stream); }
+    { Prof p(c, KX_MAP_UPDATE); launch_map_update(a, plan, c->stream); }
+}
+
+// The cores, on device pointers (a: Y, the CSR, the long rows, n >= 2).  Neither synchronises.
+static int map_step_core(blissgpu_ctx* c, const char* who, MapArgs a, float exaggeration, uint32_t col_groups, double* d_grad,
+                         double* d_z_rows, double* d_Z) {
+    MapPlan plan;
+    int rc = map_scratch(c, who, col_groups, 0, &a, &plan);
+    if (rc) return rc;
+    a.grad = d_grad;
+    a.z_out = d_Z;
+    a.exaggeration = (double)exaggeration;
+    map_eval(c, a, plan, map_feed());
+    HIP_TRY(hipGetLastError());
+    if (d_z_rows) HIP_TRY(hipMemcpyAsync(d_z_rows, a.sums, (size_t)a.n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    return BLISSGPU_OK;
+}
+
+static int map_layout_core(blissgpu_ctx* c, const char* who, MapArgs a, uint32_t n_iter, uint32_t exag_iters, float exaggeration,
+                           double lr, double momentum0, double momentum1, double min_gain, uint32_t col_groups, double* d_trace) {
+    MapPlan plan;
+    int rc = map_scratch(c, who, col_groups, n_iter, &a, &plan);
+    if (rc) return rc;
+    const int feed = map_feed();
+    a.grad = nullptr;
+    a.lr = lr;
+    a.min_gain = min_gain;
+    for (uint32_t it = 0; it < n_iter; it++) {  // no host synchronisation in here
+        a.exaggeration = it < exag_iters ? (double)exaggeration : 1.0;
+        a.momentum = it < exag_iters ? momentum0 : momentum1;
+        a.first = it == 0;
+        a.z_out = d_trace + it;
+        map_eval(c, a, plan, feed);
+    }
+    HIP_TRY(hipGetLastError());
+    return BLISSGPU_OK;
+}
+
+// y | vals in st_b, cols | long rows in st_idx, row_offsets and `extra` doubles behind them in st_out
+static int map_stage(blissgpu_ctx* c, HostStage& s, const float* y, uint64_t n, const uint64_t* row_offsets, const uint32_t* cols,
+                     const float* vals, const std::vector<uint32_t>& long_rows, size_t extra, MapArgs* a, double** d_extra) {
+    const size_t nnz = row_offsets[n];
+    int rc = c->st_b.ensure(2 * n + nnz);
+    if (!rc) rc = c->st_idx.ensure(std::max<size_t>(1, nnz + long_rows.size()));
+    if (!rc) rc = c->st_out.ensure((n + 1 + extra) * sizeof(double));
+    if (rc) return rc;
+    *a = MapArgs{};
+    a->Y = c->st_b.p;
+    float* d_vals = c->st_b.p + 2 * n;
+    uint32_t *d_cols = c->st_idx.p, *d_long = c->st_idx.p + nnz;
+    unsigned long long* d_ro = reinterpret_cast<unsigned long long*>(c->st_out.p);
+    a->row_offsets = d_ro;
+    a->cols = d_cols;
+    a->vals = d_vals;
+    a->long_rows = d_long;
+    a->n = (uint32_t)n;
+    a->n_long = (uint32_t)long_rows.size();
+    *d_extra = reinterpret_cast<double*>(d_ro + n + 1);
+    s.up(a->Y, y, 2 * n * sizeof(float));
+    s.up(d_vals, vals, nnz * sizeof(float));
+    s.up(d_cols, cols, nnz * sizeof(uint32_t));
+    s.up(d_long, long_rows.data(), long_rows.size() * sizeof(uint32_t));
+    s.up(d_ro, row_offsets, (n + 1) * sizeof(uint64_t));
+    return s.uploaded();
+}
+
+int blissgpu_map_step(const float* y, uint64_t n, const uint64_t* row_offsets, const uint32_t* cols, const float* vals,
+                      float exaggeration, uint32_t col_groups, double* grad, double* z_rows, double* Z) {
+    const char* who = "blissgpu_map_step";
+    if (!std::isfinite(exaggeration)) return fail(BLISSGPU_ERR_INVALID, who, "exaggeration must be finite");
+    std::vector<uint32_t> long_rows;
+    int rc = map_input_ok(who, y, n, row_offsets, cols, vals, col_groups, &long_rows);
+    if (rc) return rc;
+    if (!Z) return fail(BLISSGPU_ERR_INVALID, who, "Z is NULL");
+    if (n && !grad) return fail(BLISSGPU_ERR_INVALID, who, "grad is NULL");
+    if (n < 2) {  // no pair: nothing for a device to do
+        *Z = 0.0;
+        for (uint64_t e = 0; e < 2 * n; e++) grad[e] = 0.0;
+        if (z_rows && n) z_rows[0] = 0.0;
+        return BLISSGPU_OK;
+    }
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    HostStage s{c, "map_step"};
+    MapArgs a;
+    double* d_out;  // grad [n][2] | z_rows [n] | Z
+    rc = map_stage(c, s, y, n, row_offsets, cols, vals, long_rows, 3 * n + 1, &a, &d_out);
+    if (!rc) rc = map_step_core(c, who, a, exaggeration, col_groups, d_out, z_rows ? d_out + 2 * n : nullptr, d_out + 3 * n);
+    if (!rc) {
+        s.down(grad, d_out, 2 * n * sizeof(double));
+        s.down(z_rows, d_out + 2 * n, n * sizeof(double));
+        s.down(Z, d_out + 3 * n, sizeof(double));
+    }
+    return s.finish(rc);
+}
+
+int blissgpu_map_layout(const float* y0, uint64_t n, const uint64_t* row_offsets, const uint32_t* cols, const float* vals,
+                        uint32_t n_iter, uint32_t exag_iters, float exaggeration, double learning_rate, double momentum0,
+                        double momentum1, double min_gain, uint32_t col_groups, float* y_out, double* z_trace) {
+    const char* who = "blissgpu_map_layout";
+    if (!std::isfinite(exaggeration) || !std::isfinite(learning_rate) || !std::isfinite(momentum0) || !std::isfinite(momentum1) ||
+        !std::isfinite(min_gain))
+        return fail(BLISSGPU_ERR_INVALID, who, "exaggeration, learning_rate, the momenta and min_gain must be finite");
+    std::vector<uint32_t> long_rows;
+    int rc = map_input_ok(who, y0, n, row_offsets, cols, vals, col_groups, &long_rows);
+    if (rc) return rc;
+    if (n == 0) return BLISSGPU_OK;
+    if (!y_out) return fail(BLISSGPU_ERR_INVALID, who, "y_out is NULL");
+    if (n < 2 || n_iter == 0) {  // no pair (every gradient is 0, every Z is 0) or no iteration: y_out = y0
+        if (y_out != y0) memmove(y_out, y0, 2 * n * sizeof(float));
+        if (z_trace) for (uint32_t it = 0; it < n_iter; it++) z_trace[it] = 0.0;
+        return BLISSGPU_OK;
+    }
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    HostStage s{c, "map_layout"};
+    MapArgs a;
+    double* d_trace;
+    // (checked here as well as in the core: the trace is staged before the core runs)
+    if (((size_t)n_iter + 9 * n) * sizeof(double) > c->ws_limit)
+        return fail(BLISSGPU_ERR_OOM, who, "the column groups' partial sums and the trace do not fit the workspace limit");
+    std::vector<double> trace;
+    if (!z_trace) {
+        try {
+            trace.resize(n_iter);
+        } catch (const std::bad_alloc&) {
+            return fail(BLISSGPU_ERR_OOM, who, "no host memory for the trace");
+        }
+    }
+    double* h_trace = z_trace ? z_trace : trace.data();
+    rc = map_stage(c, s, y0, n, row_offsets, cols, vals, long_rows, n_iter, &a, &d_trace);
+    if (!rc) rc = map_layout_core(c, who, a, n_iter, exag_iters, exaggeration, learning_rate, momentum0, momentum1, min_gain, col_groups, d_trace);
+    if (!rc) {
+        s.down(y_out, a.Y, 2 * n * sizeof(float));
+        s.down(h_trace, d_trace, (size_t)n_iter * sizeof(double));
+    }
+    if ((rc = s.finish(rc))) return rc;  // the one synchronisation
+    for (uint32_t it = 0; it < n_iter; it++)
+        if (!std::isfinite(h_trace[it]) || !(h_trace[it] > 0.0)) return fail(BLISSGPU_ERR_NAN, who, "the normaliser Z of an iteration is not finite and positive");
+    return BLISSGPU_OK;
 }
 
 // ---- duplicate groups of a collection: the rule of dedup_playlist_custom_distance (src/playlist.rs:381-388) over EVERY pair

@@ -123,7 +123,7 @@ enum KernelId : int {
     K_CHAIN_STEP, K_CHAIN_WALK,             // song-to-song chains cut after k (kernels_chains.hip)
     // (tests/test_chains_host.py holds this list, and the list of names beside it, to end in the chain kernels: the kernels
     // that came later are numbered behind it, so that no older id or name moves)
-    K_COUNT = K_CHAIN_WALK + 30
+    K_COUNT = K_CHAIN_WALK + 33
 };
 // k-nearest albums per seed group (kernels_albums.hip; its partial lists are merged by knn_merge_kernel)
 constexpr int KX_SEGMENT_MEAN = K_CHAIN_WALK + 1, KX_ALBUM_KNN_SCAN = K_CHAIN_WALK + 2;
@@ -146,12 +146,14 @@ constexpr int KX_MST_SCAN = K_CHAIN_WALK + 22, KX_MST_PICK = K_CHAIN_WALK + 23;
 constexpr int KX_SCALED_KNN_SCAN = K_CHAIN_WALK + 24, KX_KNN_OCCURRENCE = K_CHAIN_WALK + 25;
 // radio playlists (kernels_radio.hip): the banned labels of every (radio, rule), then the step under them
 constexpr int KX_RADIO_BAN = K_CHAIN_WALK + 26, KX_RADIO_STEP = K_CHAIN_WALK + 27;
+// the 2-D map of a library (kernels_map.hip): the all-pairs repulsion, the attraction along the CSR rows, the gradient and update
+constexpr int KX_MAP_REPULSE = K_CHAIN_WALK + 28, KX_MAP_ATTRACT = K_CHAIN_WALK + 29, KX_MAP_UPDATE = K_CHAIN_WALK + 30;
 // (tests/test_journeys_host.py holds the profile table to END in the next two names: kernels that come later are numbered in
 // front of them; every consumer of the table goes by name)
 // the k lowest forest scores per seed group (kernels_forest.hip; its partial lists are merged by group_knn_merge_kernel)
-constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 28;
+constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 31;
 // a journey's step (kernels_chains.hip: the chains' scan with a waypoint query or a gate)
-constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 29;
+constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 32;
 static_assert(KX_JOURNEY_STEP + 1 == K_COUNT, "every kernel id is below the count");
 
 // lower_bound on a prefix array: largest s with prefix[s] <= x  (prefix has n+1 entries, prefix[0]=0)
@@ -580,6 +582,41 @@ struct RadioArgs {
 };
 void launch_radio_ban(const RadioArgs& a, uint32_t t, hipStream_t st);
 void launch_radio_step(const RadioArgs& a, uint32_t t, const ChainPlan& p, hipStream_t st);
+// the 2-D map of a library (kernels_map.hip; the arithmetic is stated in include/blissgpu.h).  One gradient
+// evaluation is launch_map_repulse (rows x column groups: the sums z, rx, ry of every row over one chunk of j), launch_map_attract
+// (the chunk sums added per row, the 256-row block sums of z, and the CSR sums of the rows of at most MAP_LONG_ROW entries; a
+// second launch gives every longer row a wavefront), launch_map_update (Z, the gradient, and either grad or the update of Y).
+// sums is f64 [3][n] (z | rx | ry), part f64 [chunks][3][n] (unused with one chunk: the scan then writes sums itself), zb f64
+// [ceil(n / 256)], att f64 [n][2], U and gain f64 [n][2]; long_rows lists the rows of more than MAP_LONG_ROW entries
+constexpr uint32_t MAP_TILE = 256;      // rows of a workgroup, and the points of a staged tile
+constexpr uint32_t MAP_LONG_ROW = 256;  // CSR entries a lane walks alone
+constexpr uint32_t MAP_MAX_COL_GROUPS = 64;
+constexpr int MAP_FEED_SCALAR = 0, MAP_FEED_LDS = 1;  // how the scan is fed y_j: scalar loads, or LDS broadcasts of a staged tile
+struct MapPlan {
+    uint32_t col_groups;  // C of the contract
+    uint32_t width;       // w = 256 ceil(ceil(n / C) / 256)
+    uint32_t chunks;      // the chunks that are not empty: ceil(n / w)
+    uint32_t blocks;      // ceil(n / 256)
+};
+uint32_t map_plan_col_groups(uint64_t n, int n_cus);  // what col_groups == 0 resolves to (blissgpu_map_plan)
+MapPlan map_plan(uint64_t n, uint32_t col_groups);    // col_groups >= 1
+struct MapArgs {
+    float* Y;  // [n][2]
+    const unsigned long long* row_offsets;
+    const uint32_t* cols;
+    const float* vals;
+    const uint32_t* long_rows;
+    uint32_t n, n_long;
+    double *sums, *part, *zb, *att, *U, *gain;
+    double* grad;   // [n][2]: written instead of the update when not NULL
+    double* z_out;  // where Z goes (an entry of the trace, or the step's result)
+    double exaggeration, lr, momentum, min_gain;
+    uint32_t first;  // the update starts from U = 0, gain = 1 and reads neither
+};
+void launch_map_repulse(const MapArgs& a, const MapPlan& p, int feed, hipStream_t st);
+void launch_map_attract(const MapArgs& a, const MapPlan& p, hipStream_t st);
+void launch_map_attract_long(const MapArgs& a, hipStream_t st);
+void launch_map_update(const MapArgs& a, const MapPlan& p, hipStream_t st);
 // column 0 of idx / dist from step 0's [n_chains] arrays
 void launch_chain_first(const uint32_t* idx0, const float* dist0, uint32_t n_chains, uint32_t k, uint32_t* idx, float* dist,
                         hipStream_t st);

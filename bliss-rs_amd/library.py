@@ -42,6 +42,8 @@ database:
     song_tree, linked_clusters, tour      the library's minimum spanning tree (playlist.minimum_spanning_tree, one device
                                           call): clusters without a number of clusters and of any shape, and every song
                                           (or one genre's) in an order in which each sounds like one before it
+    song_map                              a picture of the library: a point per song on a plane where sonic neighbours are
+                                          neighbours (playlist.song_map: exact t-SNE, every iteration on the device)
 
 SQLite stores `real` as f64; an f32 feature widens exactly on the way in and narrows exactly on the way out, so a
 round trip is bit-exact.  The schema, load and store helpers are host code; the playlists run their distances on the
@@ -1106,3 +1108,14 @@ def orphan_songs(db: Conn, k: int, scaled: bool = False, m: int = 10, kind: str 
     locally scaled, in id order."""
     h, paths = hubness(db, k, scaled, m, kind, metric_builder)
     return [paths[int(i)] for i in h.orphans()]
+
+
+def song_map(db: Conn, perplexity: float = 30.0, n_iter: int = 750, metric_builder=playlist.euclidean_distance, init="pca", **options):
+    """A picture of the library (playlist.song_map) over the analysed songs of FeaturesVersion.LATEST, read
+    once: -> (playlist.SongMap, paths); the point of the song at paths[i] is map.xy[i], in id order, for a front end to draw
+    and colour by genre, album or cluster.  `options` are song_map's further parameters (exag_iters, learning_rate, ...)."""
+    playlist._scaled_metric(metric_builder, "song_map")  # refused before the database is read
+    _, paths, X = load_feature_matrix(db, FeaturesVersion.LATEST)
+    if not paths:
+        return playlist.SongMap(np.zeros((0, 2), np.float32), np.zeros(max(int(n_iter), 0), np.float64), 0.0), paths
+    return playlist.song_map(X, perplexity, n_iter, metric_builder, init, **options), paths

@@ -20,6 +20,8 @@
     under the average nearest-member distance, all pairs on the device without the distance matrix)
     triplet_step, learn_metric, triplet_accuracy, triplets_from_labels (the metric learning the reference's TODO.md and its
     training_triplet table ask for: a Mahalanobis M from "a and b are closer than o" triplets, the gradient on the device)
+    map_affinities, map_init, map_step, map_layout, song_map (a 2-D map of a library, a point per song: exact t-SNE, every
+    pair in every iteration and every iteration on the device)
 
 A metric builder is one of the strings "euclidean" / "cosine", a `MahalanobisBuilder` (or the pair
 ("mahalanobis", M)), a `ForestOptions` (closest_to_songs and library.playlist_from_custom only: the forest needs at
@@ -1108,6 +1110,243 @@ def neighbour_agreement(idx, labels) -> float:
     if not rows.any():
         return float("nan")
     return float((same.sum(axis=1)[rows].astype(np.float64) / tot[rows]).mean())
+
+
+# ---- a 2-D map of a library: exact t-SNE stepped on the device (blissgpu_map_step / blissgpu_map_layout) ----
+MAP_BISECTIONS = 64  # steps of every row's perplexity search: always all of them
+
+
+def map_affinities(idx, dist, perplexity):
+    """The symmetric affinities P of a map from every song's nearest-neighbour list: idx int [n, k] and dist float [n, k] as
+    nearest_order(X, X, k, skip=arange(n)) returns them (-1 / inf padding is left out).  Per row, p_j = exp(-beta (d_j^2 - min
+    d^2)) normalised to sum 1, with beta found by exactly MAP_BISECTIONS bisection steps on the row's entropy against
+    log(perplexity) -- beta starts at 1 and doubles while no upper bound is known; no tolerance ends the search early --, all
+    rows at once in float64.  Then P = (p + p^T) / 2n.  -> (row_offsets uint64[n + 1], cols uint32[nnz], vals float64[nnz]) in
+    the CSR form blissgpu_map_step reads: columns ascending within a row, no diagonal, symmetric in value, summing to 1.  The
+    device takes vals rounded to float32 (map_step and map_layout round them).  Pure numpy."""
+    idx = np.asarray(idx, dtype=np.int64)
+    d = np.asarray(dist, dtype=np.float64)
+    if idx.ndim != 2 or d.shape != idx.shape:
+        raise ValueError("idx and dist must both be [n, k]")
+    perplexity = float(perplexity)
+    if not (perplexity > 0.0 and np.isfinite(perplexity)):
+        raise ValueError("perplexity must be positive and finite")
+    n, k = idx.shape
+    rows = np.arange(n, dtype=np.int64)[:, None]
+    valid = (idx >= 0) & np.isfinite(d) & (idx != rows)
+    if (idx[valid] >= n).any():
+        raise ValueError("idx entries must be rows of the library")
+    if n == 0 or k == 0 or not valid.any():
+        return np.zeros(n + 1, np.uint64), np.zeros(0, np.uint32), np.zeros(0, np.float64)
+    d2 = np.where(valid, d * d, np.inf)
+    d2 = np.where(valid, d2 - d2.min(axis=1, keepdims=True), np.inf)  # rows without a neighbour stay all-inf: p = 0
+    target = np.log(perplexity)
+    beta, lo, hi = np.ones(n), np.zeros(n), np.full(n, np.inf)
+
+    def weights(b):
+        with np.errstate(invalid="ignore", over="ignore"):
+            return np.where(valid, np.exp(-b[:, None] * np.where(valid, d2, 0.0)), 0.0)
+
+    for _ in range(MAP_BISECTIONS):
+        p = weights(beta)
+        s = np.maximum(p.sum(axis=1), np.finfo(np.float64).tiny)
+        h = np.log(s) + beta * (np.where(valid, d2, 0.0) * p).sum(axis=1) / s
+        more = h > target  # too flat: a larger beta
+        lo = np.where(more, beta, lo)
+        hi = np.where(more, hi, beta)
+        beta = np.where(np.isinf(hi), beta * 2.0, (lo + hi) / 2.0)
+    p = weights(beta)
+    p = p / np.maximum(p.sum(axis=1, keepdims=True), np.finfo(np.float64).tiny)
+    # (p + p^T) / 2n: both directions as (row n + column) keys, equal keys added (at most two, so the order cannot matter)
+    r = np.broadcast_to(rows, idx.shape)[valid]
+    c = idx[valid]
+    v = p[valid]
+    keys = np.concatenate([r * n + c, c * n + r])
+    order = np.argsort(keys, kind="stable")
+    keys, v2 = keys[order], np.concatenate([v, v])[order]
+    first = np.concatenate([[True], keys[1:] != keys[:-1]])
+    starts = np.flatnonzero(first)
+    vals = np.add.reduceat(v2, starts) / (2.0 * n)
+    keys = keys[starts]
+    counts = np.bincount(keys // n, minlength=n)
+    row_offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
+    return row_offsets, (keys % n).astype(np.uint32), vals
+
+
+def map_init(X, mom: "Moments" = None) -> np.ndarray:
+    """The starting positions of a map, float32 [n, 2]: the rows of X (an array, or songs) projected onto the two leading
+    eigenvectors of their scatter matrix -- moments(X), from the device; `mom` passes a Moments that is already there -- and
+    scaled so that the first coordinate has standard deviation 1e-4.  Each eigenvector's sign is fixed so that its entry of
+    the largest magnitude is positive (the first such entry), so two runs start alike.  With one feature the second coordinate
+    is 0; rows that do not vary start at 0."""
+    X = _rows_of_input(X)
+    n, d = X.shape
+    if n == 0:
+        return np.zeros((0, 2), np.float32)
+    if mom is None:
+        mom = moments(X)
+    S = np.asarray(mom.scatter, dtype=np.float64)
+    _, vec = np.linalg.eigh((S + S.T) / 2.0)  # ascending eigenvalues
+    V = np.zeros((d, 2), np.float64)
+    for c in range(min(2, d)):
+        v = vec[:, d - 1 - c]
+        V[:, c] = v if v[int(np.argmax(np.abs(v)))] > 0 else -v
+    Y = (X.astype(np.float64) - np.asarray(mom.mean, np.float64).reshape(1, d)) @ V
+    sd = float(Y[:, 0].std())
+    if not (sd > 0.0 and np.isfinite(sd)):
+        return np.zeros((n, 2), np.float32)
+    return np.ascontiguousarray(Y * (1e-4 / sd), dtype=np.float32)
+
+
+def _map_csr(n, row_offsets, cols, vals):
+    """the CSR arrays of a map call, checked (ValueError) and in the dtypes the library reads"""
+    ro = np.ascontiguousarray(np.asarray(row_offsets).reshape(-1))
+    if ro.dtype.kind not in "iu":
+        raise ValueError("row_offsets must be integers")
+    if ro.shape[0] != n + 1:
+        raise ValueError("row_offsets needs n + 1 entries")
+    if (ro.astype(np.int64) < 0).any():
+        raise ValueError("row_offsets must not be negative")
+    ro = ro.astype(np.uint64)
+    if ro[0] != 0 or (ro[1:] < ro[:-1]).any():
+        raise ValueError("row_offsets must start at 0 and must not decrease")
+    nnz = int(ro[-1])
+    co = np.asarray(cols).reshape(-1)
+    va = np.ascontiguousarray(np.asarray(vals).reshape(-1), dtype=np.float32)
+    if co.shape[0] != nnz or va.shape[0] != nnz:
+        raise ValueError("cols and vals need row_offsets[n] entries")
+    if nnz >= 2 ** 32:
+        raise ValueError("nnz must be below 2^32")
+    if nnz:
+        if co.dtype.kind not in "iu" or co.min() < 0 or co.max() >= n:
+            raise ValueError("cols must be row indices below n")
+        co64 = co.astype(np.int64)
+        row = np.repeat(np.arange(n, dtype=np.int64), np.diff(ro.astype(np.int64)))
+        if (co64 == row).any():
+            raise ValueError("a row holds itself")
+        inside = row[1:] == row[:-1]
+        if (inside & (co64[1:] <= co64[:-1])).any():
+            raise ValueError("a row's columns must be strictly ascending")
+        if not np.isfinite(va).all() or (va < 0).any():
+            raise ValueError("vals must be finite and >= 0")
+    return ro, np.ascontiguousarray(co, dtype=np.uint32), va
+
+
+def _map_points(Y):
+    Y = np.ascontiguousarray(Y, dtype=np.float32)
+    if Y.ndim != 2 or Y.shape[1] != 2:
+        raise ValueError("the points must be [n, 2]")
+    if Y.shape[0] >= 2 ** 24:
+        raise ValueError("a map holds fewer than 2^24 points")
+    return Y
+
+
+def _map_col_groups(col_groups):
+    col_groups = int(col_groups)
+    if not 0 <= col_groups <= 64:
+        raise ValueError("col_groups must be 0 .. 64")
+    return col_groups
+
+
+def map_plan(n, n_cus=0) -> int:
+    """The column groups col_groups = 0 stands for on a device of n_cus compute units (blissgpu_map_plan; device-free)."""
+    out = C.c_uint32(0)
+    _ffi.check(_ffi.lib().blissgpu_map_plan(int(n), int(n_cus), C.byref(out)))
+    return int(out.value)
+
+
+def map_step(Y, row_offsets, cols, vals, exaggeration=1.0, col_groups=0):
+    """One gradient of the map's cost at the points Y float32 [n, 2] under the affinities (row_offsets, cols, vals) -- the CSR
+    form map_affinities returns; vals are rounded to float32 -- on the device (blissgpu_map_step; include/blissgpu.h states
+    every operation and its order).  -> (grad float64 [n, 2], z_rows float64 [n], Z float).  Bad CSR input raises ValueError."""
+    Y = _map_points(Y)
+    n = Y.shape[0]
+    ro, co, va = _map_csr(n, row_offsets, cols, vals)
+    exaggeration = float(exaggeration)
+    if not np.isfinite(exaggeration):
+        raise ValueError("exaggeration must be finite")
+    grad, z_rows, Z = np.zeros((n, 2), np.float64), np.zeros(n, np.float64), C.c_double(0.0)
+    _ffi.check(_ffi.lib().blissgpu_map_step(Y.ctypes.data, n, ro.ctypes.data, co.ctypes.data, va.ctypes.data, exaggeration,
+                                            _map_col_groups(col_groups), grad.ctypes.data, z_rows.ctypes.data, C.byref(Z)))
+    return grad, z_rows, float(Z.value)
+
+
+def map_layout(Y0, row_offsets, cols, vals, n_iter=750, exag_iters=250, exaggeration=12.0, learning_rate=200.0, momentum0=0.5,
+               momentum1=0.8, min_gain=0.01, col_groups=0):
+    """n_iter iterations of gradient, gain and momentum from the points Y0 in one device call (blissgpu_map_layout): the first
+    exag_iters of them with (exaggeration, momentum0), the rest with (1, momentum1); nothing crosses to the host between two
+    iterations.  -> (Y float32 [n, 2], z_trace float64 [n_iter], every iteration's normaliser).  Bad CSR input or a parameter
+    that is not finite raises ValueError; a normaliser that is not finite and positive (a NaN in Y0) BlissGpuError(ERR_NAN)."""
+    Y0 = _map_points(Y0)
+    n = Y0.shape[0]
+    ro, co, va = _map_csr(n, row_offsets, cols, vals)
+    n_iter, exag_iters = int(n_iter), int(exag_iters)
+    if n_iter < 0 or exag_iters < 0 or max(n_iter, exag_iters) >= 2 ** 32:
+        raise ValueError("n_iter and exag_iters must be counts")
+    params = [float(exaggeration), float(learning_rate), float(momentum0), float(momentum1), float(min_gain)]
+    if not np.isfinite(params).all():
+        raise ValueError("exaggeration, learning_rate, the momenta and min_gain must be finite")
+    Y, trace = np.zeros((n, 2), np.float32), np.zeros(n_iter, np.float64)
+    _ffi.check(_ffi.lib().blissgpu_map_layout(Y0.ctypes.data, n, ro.ctypes.data, co.ctypes.data, va.ctypes.data, n_iter, exag_iters,
+                                              *params, _map_col_groups(col_groups), Y.ctypes.data, trace.ctypes.data))
+    return Y, trace
+
+
+@dataclasses.dataclass
+class SongMap:
+    """The result of song_map: xy float32 [n, 2] (a point per song), z_trace float64 [n_iter] (every iteration's normaliser Z:
+    it falls as the map spreads out) and kl, the Kullback-Leibler divergence of the map's similarities from the affinities P
+    at xy -- the cost the iterations lower; two maps of the same library are compared by it."""
+    xy: np.ndarray
+    z_trace: np.ndarray
+    kl: float
+
+
+def map_kl(xy, row_offsets, cols, vals, Z) -> float:
+    """sum over the stored entries of P log(P / Q) with Q = q / Z, q = 1 / (1 + |y_i - y_j|^2): float64 on the host, O(nnz)"""
+    xy = np.asarray(xy, dtype=np.float64)
+    ro = np.asarray(row_offsets, dtype=np.int64)
+    row = np.repeat(np.arange(xy.shape[0], dtype=np.int64), np.diff(ro))
+    co = np.asarray(cols, dtype=np.int64)
+    p = np.asarray(vals, dtype=np.float64)
+    keep = p > 0
+    if not keep.any():
+        return 0.0
+    diff = xy[row[keep]] - xy[co[keep]]
+    q = 1.0 / (1.0 + (diff * diff).sum(axis=1))
+    return float((p[keep] * (np.log(p[keep]) - np.log(q) + np.log(Z))).sum())
+
+
+def song_map(songs_or_X, perplexity=30.0, n_iter=750, metric_builder=euclidean_distance, init="pca", exag_iters=250,
+             exaggeration=12.0, learning_rate=None, momentum0=0.5, momentum1=0.8, min_gain=0.01, col_groups=0) -> SongMap:
+    """A picture of a library: a point per song (or row of an array) on a plane where sonic neighbours are neighbours -- exact
+    t-SNE (van der Maaten and Hinton 2008), every pair in every iteration, on the device.  Three device stages: every song's
+    k = min(n - 1, 3 perplexity) nearest other songs under metric_builder (nearest_order: euclidean, cosine or a
+    MahalanobisBuilder, a learned M included; ForestOptions and VarianceWeights are refused), the starting positions
+    (init="pca": map_init; or an [n, 2] array), and the n_iter iterations in one call (map_layout).  The affinities between
+    them are numpy (map_affinities).  learning_rate None = max(n / 12 / 4, 50).  -> SongMap."""
+    metric, m = _scaled_metric(metric_builder, "song_map")
+    X = _rows_of_input(songs_or_X)
+    n = X.shape[0]
+    if isinstance(init, str):
+        if init != "pca":
+            raise ValueError('init must be "pca" or an [n, 2] array')
+    else:
+        init = _map_points(init)
+        if init.shape[0] != n:
+            raise ValueError("init needs a point per song")
+    n_iter = int(n_iter)
+    if n < 2:
+        return SongMap(np.zeros((n, 2), np.float32), np.zeros(max(n_iter, 0), np.float64), 0.0)
+    k = min(n - 1, max(1, int(3.0 * float(perplexity))))
+    idx, dist = nearest_order(X, X, k, metric, m, skip=np.arange(n))
+    ro, co, va = map_affinities(idx, dist, perplexity)
+    va = va.astype(np.float32)
+    Y0 = map_init(X) if isinstance(init, str) else init
+    lr = max(n / 12.0 / 4.0, 50.0) if learning_rate is None else float(learning_rate)
+    xy, trace = map_layout(Y0, ro, co, va, n_iter, exag_iters, exaggeration, lr, momentum0, momentum1, min_gain, col_groups)
+    _, _, Z = map_step(xy, ro, co, va, 1.0, col_groups)  # the normaliser AT xy (the trace ends one update before it)
+    return SongMap(xy, trace, map_kl(xy, ro, co, va, Z))
 
 
 class KSelection:

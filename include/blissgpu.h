@@ -963,6 +963,61 @@ int blissgpu_radio_device(blissgpu_ctx *ctx, const float *d_from, uint64_t n_rad
                           const uint32_t *window, const uint32_t *limit, const uint32_t *d_skip, uint32_t k, int mode,
                           uint32_t *d_idx, float *d_dist);
 
+/* ---- a 2-D map of a library: exact t-SNE, stepped on the device ----
+ * Every other library call returns lists; this one returns a picture: a point per song on a plane where sonic neighbours are
+ * neighbours.  All pairs are visited in every iteration, no n x n matrix is stored, and every sum has a fixed order, so the
+ * result is bit for bit what a sequential loop over the statements below gives.
+ *
+ * Inputs.  Y is [n][2] f32.  P, the symmetric affinity matrix, is in CSR form: row_offsets uint64[n + 1] (row_offsets[0] = 0,
+ * not decreasing, nnz = row_offsets[n]), cols uint32[nnz] (strictly ascending inside a row, never the row itself, < n), vals
+ * float[nnz] (finite, >= 0).  Symmetry is the caller's business: the arithmetic below reads rows only.
+ *
+ * Every operation below is rounded on its own (nothing is fused); f32 division is correctly rounded.
+ * Pair quantities, f32, for a row i and any j != i:
+ *   dx = Y[i][0] - Y[j][0];  dy = Y[i][1] - Y[j][1];  s = dx * dx + dy * dy  (the two products, then their sum; s may be +inf);
+ *   q = 1.0f / (1.0f + s).
+ * Repulsion.  The range of j is cut into C = col_groups chunks of w = 256 * ceil(ceil(n / C) / 256) consecutive indices each
+ * (chunk c is c w <= j < min(n, (c + 1) w); a chunk that starts at or beyond n is empty).  Per row i and chunk, three f64 sums
+ * start at +0.0 and take, for j ascending over the chunk with j != i:
+ *   z += (double)q;   rx += (double)((q * q) * dx);   ry += (double)((q * q) * dy)        (the products are f32).
+ * z_i, rx_i, ry_i are the chunk sums added in chunk order, each from +0.0.
+ * Attraction.  Per row i two f64 sums start at +0.0 and take the row's CSR entries e in stored order, with j = cols[e]:
+ *   w = vals[e] * q(i, j)  (f32);   ax += (double)(w * dx);   ay += (double)(w * dy).
+ * Normaliser.  Z is the f64 sum of the z_i: rows are taken in blocks of 256 consecutive rows, each block's z_i are added in
+ * ascending order from +0.0, and the block sums are added in ascending order from +0.0.
+ * Gradient, f64:  grad[i][c] = 4.0 * (E * a_c - r_c / Z)  with E = (double)exaggeration, a = (ax, ay), r = (rx, ry): the
+ * product, the quotient, their difference, the product with 4.0.  For n < 2: grad = 0, Z = 0, z_rows = 0, BLISSGPU_OK.
+ * Update.  Per element e of [n][2] the f64 state is U[e] (starts at 0) and gain[e] (starts at 1); with g = grad[e]:
+ *   gain = (U * g < 0.0) ? gain + 0.2 : gain * 0.8;   gain = max(gain, min_gain);
+ *   U = mom * U - (lr * gain) * g;   Y[e] = (float)((double)Y[e] + U).
+ * Loop.  Iteration it of [0, n_iter) is a gradient from the current Y, then the update, with (exaggeration, momentum0) while
+ * it < exag_iters and (1.0, momentum1) afterwards; z_trace[it] is that iteration's Z.  U and gain start anew in every call.
+ *
+ * blissgpu_map_step: one gradient evaluation: grad double[n][2], z_rows double[n] (the z_i; may be NULL), *Z.
+ * blissgpu_map_layout: the loop from y0; y_out float[n][2] (may be y0), z_trace double[n_iter] (may be NULL).  The iterations
+ * are queued without a host synchronisation between them and the call synchronises once.  BLISSGPU_ERR_NAN exactly when
+ * n >= 2 and a traced Z is not finite or not > 0 (a NaN or an infinity in y0; every point at infinite distance of every other).
+ * n == 0, and n_iter == 0 (y_out = y0), are BLISSGPU_OK; with n == 1 y_out = y0 and every traced Z is 0.
+ * col_groups: 1 .. 64, or 0 = what blissgpu_map_plan names for the context's device.  No bit of a result depends on anything
+ * but the arguments: two calls with the same col_groups agree on every device.
+ * BLISSGPU_ERR_INVALID, checked before the device is touched: a NULL array (z_rows and z_trace excepted), n >= 2^24, nnz >=
+ * 2^32, row_offsets that do not start at 0 or that decrease, a row that is unsorted, holds a duplicate or holds itself, an
+ * entry of cols >= n, a negative or non-finite entry of vals, col_groups > 64, a parameter that is not finite.  The
+ * workspace is 72 + 24 C bytes per row (no partials with one chunk) and 8 bytes per iteration (the trace), counted against the
+ * context's workspace limit: BLISSGPU_ERR_OOM beyond it.  Host-pointer forms only, run on the default context. */
+int blissgpu_map_step(const float *y, uint64_t n, const uint64_t *row_offsets, const uint32_t *cols, const float *vals,
+                      float exaggeration, uint32_t col_groups, double *grad, double *z_rows, double *Z);
+int blissgpu_map_layout(const float *y0, uint64_t n, const uint64_t *row_offsets, const uint32_t *cols, const float *vals,
+                        uint32_t n_iter, uint32_t exag_iters, float exaggeration, double learning_rate, double momentum0,
+                        double momentum1, double min_gain, uint32_t col_groups, float *y_out, double *z_trace);
+/* What col_groups == 0 resolves to on a device of n_cus compute units (0: 256); pure, no device is touched.  With
+ * B = ceil(n / 256) row blocks: 1 when B <= 1, else min(ceil(4 n_cus / B), B, 64) -- enough 256-row workgroups for four
+ * wavefronts on every SIMD, no chunk narrower than one block.  It is 1 once B >= 4 n_cus, the rows alone filling the device,
+ * so the partials it asks for never pass 24 * 2 * 256 * 4 * n_cus bytes (12 MiB on 256 compute units).  That is the cap: the
+ * function is device-free and does not know a context's workspace limit, whose floor at creation is 256 MiB; on a context
+ * whose limit was set below what 72 + 24 col_groups bytes per row need, col_groups = 0 is BLISSGPU_ERR_OOM like any other. */
+int blissgpu_map_plan(uint64_t n, uint32_t n_cus, uint32_t *col_groups);
+
 /* ---- duplicate songs of a whole collection ----
  * The duplicate rule of dedup_playlist_custom_distance (src/playlist.rs:381-388) applied to EVERY pair of the n x d matrix x
  * instead of the neighbours of an ordered playlist: the pair (i, j), i < j, is an edge when D[i][j] < threshold (D[i][j] is bit
