@@ -19,6 +19,7 @@
 #include "metric_learn.hpp"
 #include "covariance_metric.hpp"
 #include "mst_merge.hpp"
+#include "ward_merge.hpp"
 #include "forest.hpp"
 
 using namespace bg;
@@ -46,6 +47,7 @@ const char kScaledKnnScanName[] = "scaled_knn_scan_kernel", kKnnOccurrenceName[]
 const char kRadioBanName[] = "radio_ban_kernel", kRadioStepName[] = "radio_step_kernel";  // KX_RADIO_BAN, KX_RADIO_STEP
 const char kMapRepulseName[] = "map_repulse_kernel", kMapAttractName[] = "map_attract_kernel";  // KX_MAP_*
 const char kMapUpdateName[] = "map_update_kernel";
+const char kWardScanName[] = "ward_scan_kernel", kWardJoinName[] = "ward_join_kernel";  // KX_WARD_*
 const char* const kKernelNames[K_COUNT] = {
     "fft512_kernel",     "onset_kernel",      "beat_kernel",   "stft8192_kernel", "tune_select_kernel",
     "tune_pass2_kernel", "tune_final_kernel", "chroma_kernel",     "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel", "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel",
@@ -64,6 +66,7 @@ const char* const kKernelNames[K_COUNT] = {
     kScaledKnnScanName, kKnnOccurrenceName,
     kRadioBanName, kRadioStepName,
     kMapRepulseName, kMapAttractName, kMapUpdateName,
+    kWardScanName, kWardJoinName,
     kGroupForestScanName, kJourneyStepName};
 }  // namespace
 
@@ -389,7 +392,7 @@ int blissgpu_ctx_destroy(blissgpu_ctx* c) {
         (void)hipFree(c->bt_rwv); (void)hipFree(c->bt_dfwv); (void)hipFree(c->chroma_bank);
         scheduler_release(c);
         c->dbg_tuning.release(); c->dbg_nbpms.release(); c->dbg_chroma.release(); c->dbg_interval.release();
-        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->km_ws.release(); c->sil_ws.release(); c->mo_ws.release(); c->ch_ws.release(); c->ms_ws.release(); c->map_ws.release(); c->mt_ws.release(); c->pl_next.release(); c->st_idx.release();
+        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->km_ws.release(); c->sil_ws.release(); c->mo_ws.release(); c->ch_ws.release(); c->ms_ws.release(); c->wd_ws.release(); c->wd_host.release(); c->map_ws.release(); c->mt_ws.release(); c->pl_next.release(); c->st_idx.release();
         c->st_a.release(); c->st_b.release(); c->st_m.release(); c->st_dist.release(); c->st_out.release();
         c->fl_bytes.release(); c->fl_tab.release(); c->fl_pcm.release(); c->fl_status.release(); c->fl_end.release();
         c->fl_bad.release(); c->fl_mono.release(); c->fl_rows.release(); c->fl_htab.release();
@@ -1700,6 +1703,248 @@ int blissgpu_mst(const float* x, uint64_t n, uint32_t d, int metric, const float
         edge_u[k] = st.edges[k].u;
         edge_v[k] = st.edges[k].v;
         memcpy(edge_w + k, &st.edges[k].w, sizeof(float));
+    }
+    if (rounds) *rounds = st.rounds;
+    return BLISSGPU_OK;
+}
+
+// ---- Ward clustering: per round one all-pairs scan of the current centroids and one join on the device (kernels_ward.hip), the
+// mutual pairs and the plan on the host (ward_merge.hpp); no distance matrix, the host reads one key per position per round and
+// sends the plan.  Host-pointer forms only: the cores below take the context and device pointers ----
+constexpr uint64_t WARD_MAX_SONGS = 1ull << 24;  // every size and every sum of two sizes is exact in f32 below this
+
+// everything that can be said about the scalar arguments without a device
+static int ward_scalars_ok(const char* who, uint64_t n, uint32_t d, int metric, const float* M) {
+    if (d == 0 || d > 64) return fail(BLISSGPU_ERR_INVALID, who, "d must be 1 .. 64");
+    if (metric == BLISSGPU_METRIC_COSINE) return fail(BLISSGPU_ERR_INVALID, who, "cosine: Ward's cost is the growth of a sum of squares, which cosine does not give");
+    if (metric != BLISSGPU_METRIC_EUCLIDEAN && metric != BLISSGPU_METRIC_MAHALANOBIS) return fail(BLISSGPU_ERR_INVALID, who, "unknown metric");
+    if (metric == BLISSGPU_METRIC_MAHALANOBIS && !M) return fail(BLISSGPU_ERR_INVALID, who, "mahalanobis needs M");
+    if (n >= WARD_MAX_SONGS) return fail(BLISSGPU_ERR_INVALID, who, "n (m) and the sum of the sizes must be below 2^24");
+    return BLISSGPU_OK;
+}
+
+// (for the tests and the bench tool: no bit of the result depends on any of them)
+// The filter in front of the root pays from about 10^4 positions on (per round 0.425 against 0.425 ms at
+// m = 10 186, 0.83 against 0.89 ms at m = 15 497, and slightly slower below), so every scan chooses by its own m
+constexpr uint32_t WARD_FILTER_MIN_M = 12288;
+struct WardSwitches {
+    uint32_t col_groups = 0;
+    int filter = -1;  // -1: by m; 0 / 1: BLISSGPU_WARD_FILTER says
+    bool trace = false;
+    WardSwitches() {
+        if (const char* e = getenv("BLISSGPU_WARD_COL_GROUPS")) col_groups = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 65535ul);
+        if (const char* e = getenv("BLISSGPU_WARD_FILTER")) filter = e[0] != '0';
+        trace = getenv("BLISSGPU_WARD_TRACE") != nullptr;
+    }
+    bool filter_at(uint32_t m) const { return filter < 0 ? m >= WARD_FILTER_MIN_M : filter != 0; }
+};
+
+// the workspace: flags u32[4] | best u64[n] | and for the tree rows f32[n][d] | size u32[2][n] | low u32[2][n] | plan u32[n][2]
+struct WardWs {
+    uint32_t* flags;
+    unsigned long long* best;
+    float* rows;
+    uint32_t *size[2], *low[2], *plan;
+    uint64_t* host;  // page-locked, u64 [2 + n]: what a round brings back -- the flags, then the best keys
+};
+static int ward_workspace(blissgpu_ctx* c, const char* who, uint64_t n, uint32_t d, bool tree, WardWs* ws) {
+    const uint64_t bytes = 16 + 8 * n + (tree ? 4 * n * d + 24 * n : 0);
+    if (bytes > c->ws_limit) return fail(BLISSGPU_ERR_OOM, who, "the rows, the sizes, the plan and the best keys do not fit the workspace limit");
+    int rc = c->wd_ws.ensure(bytes);
+    if (!rc) rc = c->wd_host.ensure(2 + n);
+    if (rc) return rc;
+    ws->host = c->wd_host.p;
+    uint8_t* b = c->wd_ws.p;
+    ws->flags = reinterpret_cast<uint32_t*>(b);
+    ws->best = reinterpret_cast<unsigned long long*>(b + 16);
+    ws->rows = reinterpret_cast<float*>(b + 16 + 8 * n);
+    uint32_t* w = reinterpret_cast<uint32_t*>(b + 16 + 8 * n + 4 * n * d);
+    ws->size[0] = w; ws->size[1] = w + n; ws->low[0] = w + 2 * n; ws->low[1] = w + 3 * n; ws->plan = w + 4 * n;
+    return BLISSGPU_OK;
+}
+
+// one scan: every position's nearest other position.  d_low / d_size may be NULL (X[p], 1).  The smallest (cost bits << 32 |
+// p XOR j) per position arrives in ws.host[2 .. 2 + m); the stream is synchronised when this returns.  fresh: the flags and the
+// best keys are reset here (a call's first scan; after that the join has reset the keys, and a raised flag ends the call)
+static int ward_nearest_core(blissgpu_ctx* c, const char* who, const float* d_rows, const uint32_t* d_low, const uint32_t* d_size, uint32_t m,
+                             uint32_t slots, uint32_t d, int metric, const float* d_M, int diag, const WardSwitches& sw, const WardWs& ws,
+                             bool fresh, double* scan_ms) {
+    const WardPlan plan = ward_plan(m, c->n_cus, sw.col_groups);
+    WardArgs a{};
+    a.X = d_rows; a.M = d_M; a.low = d_low; a.size = d_size; a.m = m; a.d = d; a.slots = slots; a.metric = metric; a.Y = plan.Y;
+    a.best = ws.best; a.flags = ws.flags;
+    if (fresh) {
+        HIP_TRY(hipMemsetAsync(ws.flags, 0, 4 * sizeof(uint32_t), c->stream));
+        HIP_TRY(hipMemsetAsync(ws.best, 0xFF, (size_t)m * sizeof(uint64_t), c->stream));
+    }
+    if (sw.trace) (void)hipStreamSynchronize(c->stream);  // (tracing only: the scan between two synchronisations of its own)
+    const auto t_scan = std::chrono::steady_clock::now();
+    { Prof p(c, KX_WARD_SCAN); launch_ward_scan(a, diag, sw.filter_at(m), plan, c->stream); }
+    HIP_TRY(hipGetLastError());
+    if (sw.trace) {
+        (void)hipStreamSynchronize(c->stream);
+        if (scan_ms) *scan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_scan).count();
+    }
+    // (the flags lie in front of the best keys: one copy brings both)
+    HIP_TRY(hipMemcpyAsync(ws.host, ws.flags, 16 + (size_t)m * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if ((uint32_t)ws.host[0]) return fail(BLISSGPU_ERR_INVALID, who, "NaN cost (a NaN feature, inf - inf, or an M that is not positive semi-definite)");
+    return BLISSGPU_OK;
+}
+
+// the rounds.  The rows are in ws.rows already (d_x == NULL) or are copied there from d_x; the sorted edges arrive in st
+static int ward_core(blissgpu_ctx* c, const char* who, const float* d_x, uint64_t n, uint32_t d, int metric, const float* d_M, const WardWs& ws,
+                     WardState& st) {
+    int diag = 0;
+    if (int e = metric_is_diag(c, d_M, d, metric, &diag)) return e;
+    const WardSwitches sw;
+    if (d_x) HIP_TRY(hipMemcpyAsync(ws.rows, d_x, n * d * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    {
+        std::vector<uint32_t> init(2 * n, 1u);
+        for (uint64_t i = 0; i < n; i++) init[n + i] = (uint32_t)i;
+        HIP_TRY(hipMemcpyAsync(ws.size[0], init.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(ws.low[0], init.data() + n, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));  // (init goes away)
+    }
+    int err = BLISSGPU_OK;  // what a step below failed with
+    int cur = 0;            // which of the two (size, low) pairs holds the current round
+    const uint64_t* keys = ws.host + 2;
+    auto t_round = std::chrono::steady_clock::now();
+    double scan_ms = 0.0;
+    bool round_open = false;  // (tracing only) a round has scanned and its line is not printed yet
+    auto trace_round = [&](const WardState& s) {  // s is the state after the round's merge
+        if (sw.trace && round_open)
+            fprintf(stderr, "%s round %u: %u clusters, %u pairs, scan %.3f ms, round %.3f ms (copies and the join included)\n", who, s.rounds - 1u,
+                    s.prev_m, s.prev_m - s.m, scan_ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_round).count());
+        round_open = false;
+    };
+    auto nearest = [&](WardState& s, uint32_t* nn, uint32_t* cost) -> int {
+        t_round = std::chrono::steady_clock::now();
+        round_open = true;
+        err = ward_nearest_core(c, who, ws.rows, ws.low[cur], ws.size[cur], s.m, (uint32_t)n, d, metric, d_M, diag, sw, ws, s.rounds == 0, &scan_ms);
+        if (err) return -1;
+        for (uint32_t p = 0; p < s.m; p++) {
+            cost[p] = (uint32_t)(keys[p] >> 32);
+            nn[p] = keys[p] == ~0ull ? WARD_NONE : (p ^ (uint32_t)keys[p]);
+        }
+        return 0;
+    };
+    auto join = [&](WardState& s) -> int {
+        auto hip = [&](hipError_t e, const char* what) {
+            if (e != hipSuccess && !err) err = fail(BLISSGPU_ERR_HIP, what, hipGetErrorString(e));
+            return e == hipSuccess;
+        };
+        WardJoinArgs j{};
+        j.X = ws.rows; j.plan = ws.plan; j.size = ws.size[cur]; j.low = ws.low[cur]; j.size_out = ws.size[cur ^ 1]; j.low_out = ws.low[cur ^ 1];
+        j.m_old = s.prev_m; j.m_new = s.m; j.d = d; j.slots = (uint32_t)n; j.best = ws.best;
+        // (the plan is two words per position in the order of WardJoin: p, q)
+        static_assert(sizeof(WardJoin) == 2 * sizeof(uint32_t), "the plan is uploaded as it stands");
+        if (!hip(hipMemcpyAsync(ws.plan, s.plan.data(), (size_t)s.m * sizeof(WardJoin), hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync(ward plan)")) return -1;
+        { Prof p(c, KX_WARD_JOIN); launch_ward_join(j, c->stream); }
+        if (!hip(hipGetLastError(), "ward join launch")) return -1;
+        // (no synchronisation here: the plan is host memory that only the next merge rewrites, and the next scan's
+        // synchronisation comes before that merge; the caller synchronises before the state goes away)
+        cur ^= 1;
+        trace_round(s);
+        return 0;
+    };
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = ward_rounds(st, (uint32_t)n, nearest, join);
+    if (rc == WARD_OK) trace_round(st);  // (the last round has no join)
+    if (sw.trace)
+        fprintf(stderr, "%s: %u rounds, %.3f pairs / n^2, %.3f ms in all (the rounds and the host's merges between them)\n", who, st.rounds,
+                (double)st.pairs_scanned / ((double)n * (double)n), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    if (rc == -1) return err;
+    if (rc == WARD_STALLED) return fail(BLISSGPU_ERR_INTERNAL, who, "a round merged nothing: no two positions are each other's nearest");
+    if (rc != WARD_OK || st.edges.size() != (size_t)n - 1) return fail(BLISSGPU_ERR_INTERNAL, who, "a position's nearest is no other position");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_ward_nearest(const float* cc, const uint32_t* size, uint64_t m, uint32_t d, int metric, const float* M, uint32_t* nn, float* cost) {
+    const char* who = "blissgpu_ward_nearest";
+    int rc = ward_scalars_ok(who, m, d, metric, M);
+    if (rc) return rc;
+    if (m == 0) return BLISSGPU_OK;  // nothing is touched
+    if (m >= 2 && !cc) return fail(BLISSGPU_ERR_INVALID, who, "c is NULL");
+    if (!nn) return fail(BLISSGPU_ERR_INVALID, who, "nn is NULL");
+    if (!cost) return fail(BLISSGPU_ERR_INVALID, who, "cost is NULL");
+    if (size) {
+        uint64_t total = 0;
+        for (uint64_t p = 0; p < m; p++) {
+            if (size[p] == 0) return fail(BLISSGPU_ERR_INVALID, who, "size holds a 0: every cluster has at least one song");
+            total += size[p];
+        }
+        if (total >= WARD_MAX_SONGS) return fail(BLISSGPU_ERR_INVALID, who, "n (m) and the sum of the sizes must be below 2^24");
+    }
+    if (m == 1) {  // no other position: no device is touched
+        nn[0] = WARD_NONE;
+        cost[0] = INFINITY;
+        return BLISSGPU_OK;
+    }
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    const float* dM = nullptr;
+    WardWs ws{};
+    rc = ward_workspace(c, who, m, d, false, &ws);
+    if (!rc) rc = c->st_b.ensure(m * d);
+    if (!rc && size) rc = c->st_idx.ensure(m);
+    if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
+    if (rc) return rc;
+    int diag = 0;
+    if (int e = metric_is_diag(c, dM, d, metric, &diag)) return e;
+    HostStage s{c, "ward_nearest"};
+    s.up(c->st_b.p, cc, m * d * sizeof(float));
+    if (size) s.up(c->st_idx.p, size, m * sizeof(uint32_t));
+    rc = s.uploaded();
+    const uint64_t* keys = ws.host + 2;
+    const WardSwitches sw;
+    if (!rc) rc = ward_nearest_core(c, who, c->st_b.p, nullptr, size ? c->st_idx.p : nullptr, (uint32_t)m, (uint32_t)m, d, metric, dM, diag, sw, ws, true, nullptr);
+    if ((rc = s.finish(rc))) return rc;  // (the keys are host memory: nothing to copy back)
+    for (uint64_t p = 0; p < m; p++)
+        if (keys[p] == ~0ull) return fail(BLISSGPU_ERR_INTERNAL, who, "a position found no other position");
+    for (uint64_t p = 0; p < m; p++) {
+        const uint32_t cb = (uint32_t)(keys[p] >> 32);
+        nn[p] = (uint32_t)p ^ (uint32_t)keys[p];
+        memcpy(cost + p, &cb, sizeof(float));
+    }
+    return BLISSGPU_OK;
+}
+
+int blissgpu_ward(const float* x, uint64_t n, uint32_t d, int metric, const float* M, uint32_t* edge_u, uint32_t* edge_v, float* edge_cost,
+                  uint32_t* edge_size, uint32_t* edge_round, uint32_t* rounds) {
+    const char* who = "blissgpu_ward";
+    int rc = ward_scalars_ok(who, n, d, metric, M);
+    if (rc) return rc;
+    if (n >= 2 && !x) return fail(BLISSGPU_ERR_INVALID, who, "x is NULL");
+    if (n >= 2 && !edge_u) return fail(BLISSGPU_ERR_INVALID, who, "edge_u is NULL");
+    if (n >= 2 && !edge_v) return fail(BLISSGPU_ERR_INVALID, who, "edge_v is NULL");
+    if (n >= 2 && !edge_cost) return fail(BLISSGPU_ERR_INVALID, who, "edge_cost is NULL");
+    if (rounds) *rounds = 0;
+    if (n <= 1) return BLISSGPU_OK;  // no edge: nothing for a device to do
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    const float* dM = nullptr;
+    WardWs ws{};
+    rc = ward_workspace(c, who, n, d, true, &ws);
+    if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
+    if (rc) return rc;
+    HostStage s{c, "ward"};
+    s.up(ws.rows, x, n * d * sizeof(float));  // (the rows go straight into the copy the joins rewrite)
+    rc = s.uploaded();
+    WardState st;
+    if (!rc) rc = ward_core(c, who, nullptr, n, d, metric, dM, ws, st);
+    if ((rc = s.finish(rc))) return rc;  // (the edges are host memory: nothing to copy back)
+    for (size_t k = 0; k < st.edges.size(); k++) {
+        const WardEdge& e = st.edges[k];
+        edge_u[k] = e.u;
+        edge_v[k] = e.v;
+        memcpy(edge_cost + k, &e.cost, sizeof(float));
+        if (edge_size) edge_size[k] = e.size;
+        if (edge_round) edge_round[k] = e.round;
     }
     if (rounds) *rounds = st.rounds;
     return BLISSGPU_OK;

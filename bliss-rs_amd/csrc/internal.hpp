@@ -123,7 +123,7 @@ enum KernelId : int {
     K_CHAIN_STEP, K_CHAIN_WALK,             // song-to-song chains cut after k (kernels_chains.hip)
     // (tests/test_chains_host.py holds this list, and the list of names beside it, to end in the chain kernels: the kernels
     // that came later are numbered behind it, so that no older id or name moves)
-    K_COUNT = K_CHAIN_WALK + 33
+    K_COUNT = K_CHAIN_WALK + 35
 };
 // k-nearest albums per seed group (kernels_albums.hip; its partial lists are merged by knn_merge_kernel)
 constexpr int KX_SEGMENT_MEAN = K_CHAIN_WALK + 1, KX_ALBUM_KNN_SCAN = K_CHAIN_WALK + 2;
@@ -148,12 +148,14 @@ constexpr int KX_SCALED_KNN_SCAN = K_CHAIN_WALK + 24, KX_KNN_OCCURRENCE = K_CHAI
 constexpr int KX_RADIO_BAN = K_CHAIN_WALK + 26, KX_RADIO_STEP = K_CHAIN_WALK + 27;
 // the 2-D map of a library (kernels_map.hip): the all-pairs repulsion, the attraction along the CSR rows, the gradient and update
 constexpr int KX_MAP_REPULSE = K_CHAIN_WALK + 28, KX_MAP_ATTRACT = K_CHAIN_WALK + 29, KX_MAP_UPDATE = K_CHAIN_WALK + 30;
+// Ward clustering (kernels_ward.hip): every cluster's nearest other cluster under Ward's cost, the join that makes the next centroids
+constexpr int KX_WARD_SCAN = K_CHAIN_WALK + 31, KX_WARD_JOIN = K_CHAIN_WALK + 32;
 // (tests/test_journeys_host.py holds the profile table to END in the next two names: kernels that come later are numbered in
 // front of them; every consumer of the table goes by name)
 // the k lowest forest scores per seed group (kernels_forest.hip; its partial lists are merged by group_knn_merge_kernel)
-constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 31;
+constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 33;
 // a journey's step (kernels_chains.hip: the chains' scan with a waypoint query or a gate)
-constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 32;
+constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 34;
 static_assert(KX_JOURNEY_STEP + 1 == K_COUNT, "every kernel id is below the count");
 
 // lower_bound on a prefix array: largest s with prefix[s] <= x  (prefix has n+1 entries, prefix[0]=0)
@@ -504,6 +506,34 @@ struct MstPlan {
 MstPlan mst_plan(uint64_t n, int n_cus, uint32_t col_groups, uint64_t ws_limit);
 void launch_mst_scan(const MstArgs& a, int m_is_diag, const MstPlan& p, hipStream_t st);
 void launch_mst_pick(MstArgs a, uint32_t phase, const MstPlan& p, hipStream_t st);
+// Ward clustering, one round (kernels_ward.hip; ward_merge.hpp is the host half).  The m clusters sit at positions 0 .. m - 1;
+// position p's row is X[low[p]] (low == NULL: X[p]; every slot below `slots`), its size is size[p] (NULL: 1).  The scan folds
+// every position's smallest key (cost bits << 32 | p XOR j) into best [m] by atomic minima (all ones before the launch);
+// flags[0]: a NaN cost among the evaluated pairs.  The join reads plan [m_new][2] = (old position, partner or 0xFFFFFFFF),
+// rewrites the merged rows in place in the lower position's slot, writes size_out / low_out [m_new] and resets best [m_new]
+struct WardArgs {
+    const float *X, *M;
+    const uint32_t *low, *size;  // either may be NULL
+    uint32_t m, d, slots;
+    int metric;
+    uint32_t Y;
+    unsigned long long* best;
+    uint32_t* flags;
+};
+struct WardJoinArgs {
+    float* X;
+    const uint32_t *plan, *size, *low;
+    uint32_t *size_out, *low_out;
+    unsigned long long* best;  // [m_new] reset to all ones for the next scan
+    uint32_t m_old, m_new, d, slots;
+};
+struct WardPlan {
+    uint32_t waves, grid;  // wavefronts per workgroup of the scan (256 positions each), its workgroups per column group
+    uint32_t Y;            // column groups: col_groups when not 0, else enough to fill the device
+};
+WardPlan ward_plan(uint64_t m, int n_cus, uint32_t col_groups);
+void launch_ward_scan(const WardArgs& a, int m_is_diag, bool filter, const WardPlan& p, hipStream_t st);
+void launch_ward_join(const WardJoinArgs& a, hipStream_t st);
 // triplet metric learning, one gradient evaluation (kernels_metric.hip).  The triplets are dealt out in W contiguous chunks, a
 // function of T alone; part [W][pairs + 1] f64 and cnt [W][2] u64 are the wavefronts' partials, out = G f64 [d][d] | loss f64 |
 // n_active u64 | error bits u64 (TRIPLET_ERR_*).  mode says how M is read; flags (u8 [T]) may be NULL

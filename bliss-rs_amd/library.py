@@ -1050,6 +1050,40 @@ def tour(db: Conn, start_path: str = None, where=None, metric_builder=playlist.e
     return [songs[int(i)] for i in tree.tour(start)]
 
 
+def _ward_tree(db: Conn, metric_builder, where):
+    """-> (songs, playlist.WardTree over them)"""
+    playlist._ward_metric(metric_builder)  # refused before the database is read
+    songs, X = _tree_songs(db, where)
+    if not songs:
+        return songs, playlist._empty_ward_tree()
+    return songs, playlist.ward_tree(X, metric_builder)
+
+
+def ward_tree(db: Conn, metric_builder=playlist.euclidean_distance, where=None):
+    """Ward's dendrogram of the library (playlist.ward_tree) over the analysed songs of FeaturesVersion.LATEST, read once, in ONE
+    call of the tree.  -> (paths, playlist.WardTree): merge e joins the clusters whose lowest songs are paths[tree.u[e]] and
+    paths[tree.v[e]], in id order.  where = (column, value), such as ("genre", "Jazz"): only the songs whose column has that
+    value -- the sub-genres of a genre."""
+    songs, tree = _ward_tree(db, metric_builder, where)
+    return [s.path for s in songs], tree
+
+
+def ward_clusters(db: Conn, k: int = None, cost: float = None, min_cluster_size: int = 1, metric_builder=playlist.euclidean_distance,
+                  where=None):
+    """Which songs belong together, as compact clusters that nest: the clusters of the library's Ward tree (ward_tree,
+    WardTree.cut) -- k of them, each a union of clusters of k + 1, or those no merge above `cost` has joined.  -> (lists,
+    unclustered): a list of `Song` per cluster, clusters in order of their first song and songs in id order (the shape
+    linked_clusters returns), and the songs of the clusters smaller than min_cluster_size."""
+    songs, tree = _ward_tree(db, metric_builder, where)
+    if not songs:
+        return [], []
+    labels = tree.cut(k, cost, min_cluster_size)
+    lists, loose = [[] for _ in range(int(labels.max()) + 1)], []
+    for s, c in zip(songs, labels):
+        (lists[int(c)] if c >= 0 else loose).append(s)
+    return lists, loose
+
+
 def _scaled_lists(db: Conn, k, m, kind, metric_builder, scaled=True):
     """-> (paths, idx): every analysed song's k nearest other songs, raw or locally scaled"""
     metric, mm = playlist._scaled_metric(metric_builder, "a per-song search")  # refused before the database is read

@@ -921,6 +921,140 @@ def minimum_spanning_tree(songs_or_X, metric_builder=euclidean_distance, min_sam
     return SpanningTree(u.astype(np.int64), v.astype(np.int64), w, int(rounds.value), n)
 
 
+# ---- Ward clustering: the whole dendrogram (blissgpu_ward / blissgpu_ward_nearest) ----
+def _ward_metric(metric_builder):
+    """the metrics Ward clustering can run: euclidean, or Mahalanobis with the caller's matrix"""
+    _no_forest(metric_builder, "Ward clustering merges clusters by their centroids; a forest scores songs against a seed set")
+    _no_variance(metric_builder, "Ward clustering has no seed set to take variances from; pass MahalanobisBuilder(m)")
+    metric, m = _metric_of(metric_builder)
+    if metric == "cosine":
+        raise ValueError("Ward clustering needs a metric whose squares its centroids minimise: euclidean or mahalanobis, not cosine")
+    return metric, m
+
+
+def ward_nearest(C_rows, sizes=None, metric_builder=euclidean_distance):
+    """One scan of Ward clustering (blissgpu_ward_nearest): for every row of C_rows -- a cluster's centroid, with `sizes` songs in
+    it (None: 1 each) -- the other row that is cheapest to merge with under cost = |A| |B| / (|A| + |B|) * dist^2, ties to the
+    smallest i XOR j.  -> (nn int64 [m], cost float32 [m]); one row alone has nn = -1 and cost = +inf.  Every bit is defined by
+    include/blissgpu.h.  metric_builder: as ward_tree."""
+    metric, m = _ward_metric(metric_builder)
+    X = _rows_of_input(C_rows)
+    n, d = X.shape
+    sp = None
+    if sizes is not None:
+        sizes = _index_array(sizes, "sizes")
+        if sizes.shape[0] != n:
+            raise ValueError("a size per row is needed")
+        sp = sizes.ctypes.data
+    mp = None
+    if m is not None:
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        mp = m.ctypes.data
+    nn, cost = np.zeros(n, np.uint32), np.zeros(n, np.float32)
+    _ffi.check(_ffi.lib().blissgpu_ward_nearest(X.ctypes.data, sp, n, d, _METRICS[metric], mp, nn.ctypes.data, cost.ctypes.data))
+    out = nn.astype(np.int64)
+    out[nn == 0xFFFFFFFF] = -1
+    return out, cost
+
+
+@dataclasses.dataclass
+class WardTree:
+    """The result of ward_tree: the n - 1 merges of Ward's dendrogram in ascending order of (bits of cost, round, u) -- u int64
+    (the lowest song of the one cluster), v int64 (of the other, u < v), cost float32 (the growth of the within-cluster sum of
+    squares), size int64 (songs in the merged cluster), round int64 (the device round that made it) -- and `rounds`, the rounds
+    run.  n is the number of songs.  heights / within / linkage / cut are host work on those arrays."""
+
+    u: np.ndarray
+    v: np.ndarray
+    cost: np.ndarray
+    size: np.ndarray
+    round: np.ndarray
+    rounds: int
+    n: int
+
+    def heights(self) -> np.ndarray:
+        """float64 [n - 1]: sqrt(2 cost), the height scipy's linkage(X, "ward") gives the merge (under euclidean)"""
+        return np.sqrt(2.0 * self.cost.astype(np.float64))
+
+    def within(self) -> np.ndarray:
+        """float64 [n - 1]: the running sum of the costs = the within-cluster sum of squares after each merge (the elbow curve),
+        up to the rounding of the costs"""
+        return np.cumsum(self.cost.astype(np.float64))
+
+    def linkage(self) -> np.ndarray:
+        """The dendrogram as scipy lays it out: float64 [n - 1, 4], row e = (cluster a, cluster b, height, size) with a < b and
+        height = heights()[e]; the merges are the edges in their order, the cluster made by row e is numbered n + e."""
+        m = len(self.u)
+        Z = np.zeros((m, 4), np.float64)
+        h = self.heights()
+        parent, ident, size = list(range(self.n)), list(range(self.n)), [1] * self.n
+        for e in range(m):
+            ra, rb = _uf_find(parent, int(self.u[e])), _uf_find(parent, int(self.v[e]))
+            a, b = sorted((ident[ra], ident[rb]))
+            parent[rb] = ra
+            size[ra] += size[rb]
+            ident[ra] = self.n + e
+            Z[e] = (a, b, h[e], size[ra])
+        return Z
+
+    def cut(self, k: int = None, cost: float = None, min_cluster_size: int = 1) -> np.ndarray:
+        """Ward's clusters: int64 labels [n].  k: undo the k - 1 last merges of the order (k clusters, each a union of clusters
+        of k + 1); cost: undo every merge with cost > `cost` (a merge of exactly that cost stays); neither: one cluster.  The
+        clusters are numbered 0, 1, ... by their lowest member; clusters of fewer than min_cluster_size songs get -1 (which
+        silhouette, group_neighbours and moments leave out) and the others keep the order of their lowest members."""
+        if k is not None and cost is not None:
+            raise ValueError("cut takes k or cost, not both")
+        m = len(self.u)
+        keep = m
+        if k is not None:
+            k = int(k)
+            if not 1 <= k <= max(self.n, 1):
+                raise ValueError("k must be 1 .. n")
+            keep = max(self.n - k, 0)
+        elif cost is not None:
+            keep = int(np.count_nonzero(~(self.cost > np.float32(cost))))  # (ascending costs: a prefix of the order)
+        parent = list(range(self.n))
+        for e in range(keep):
+            ra, rb = _uf_find(parent, int(self.u[e])), _uf_find(parent, int(self.v[e]))
+            parent[max(ra, rb)] = min(ra, rb)  # the root is the lowest member
+        roots = np.fromiter((_uf_find(parent, i) for i in range(self.n)), np.int64, self.n)
+        sizes = np.bincount(roots, minlength=self.n)
+        big = sizes[roots] >= int(min_cluster_size)
+        label_of = np.full(max(self.n, 1), -1, np.int64)
+        live = np.unique(roots[big])  # ascending roots = ascending lowest members
+        label_of[live] = np.arange(live.size)
+        return label_of[roots]
+
+
+def _empty_ward_tree(n=0) -> WardTree:
+    z = np.zeros(0, np.int64)
+    return WardTree(z, z.copy(), np.zeros(0, np.float32), z.copy(), z.copy(), 0, int(n))
+
+
+def ward_tree(songs_or_X, metric_builder=euclidean_distance) -> WardTree:
+    """Ward's minimum-variance dendrogram of the songs (or rows of an array), without the distance matrix (blissgpu_ward,
+    DESIGN.md 3.32): a nested hierarchy of compact clusters -- any K by cutting one tree, K clusters always a refinement of
+    K - 1; the hierarchical counterpart of k-means.  Every pair of clusters that are each other's nearest merges in the same
+    round: a few dozen all-pairs scans of a shrinking set of centroids on the device.  The rounds and their roundings are
+    defined to the bit by include/blissgpu.h.  -> WardTree; its cut() gives the clusters, its linkage() scipy's layout, its
+    within() the elbow curve.  metric_builder: euclidean_distance or a MahalanobisBuilder (its M); a ForestOptions, a
+    VarianceWeights, cosine and arbitrary callables are refused.  A NaN cost raises BlissGpuError(ERR_INVALID)."""
+    metric, m = _ward_metric(metric_builder)
+    X = _rows_of_input(songs_or_X)
+    n, d = X.shape
+    mp = None
+    if m is not None:
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        mp = m.ctypes.data
+    e = max(n - 1, 0)
+    u, v, size, rnd = (np.zeros(e, np.uint32) for _ in range(4))
+    cost = np.zeros(e, np.float32)
+    rounds = C.c_uint32(0)
+    _ffi.check(_ffi.lib().blissgpu_ward(X.ctypes.data, n, d, _METRICS[metric], mp, u.ctypes.data, v.ctypes.data, cost.ctypes.data,
+                                        size.ctypes.data, rnd.ctypes.data, C.byref(rounds)))
+    return WardTree(u.astype(np.int64), v.astype(np.int64), cost, size.astype(np.int64), rnd.astype(np.int64), int(rounds.value), n)
+
+
 # ---- locally scaled nearest songs and hubness (blissgpu_scaled_knn / blissgpu_knn_occurrence, DESIGN.md 3.27) ----
 SCALE_MIN, SCALE_MAX = np.float32(2.0 ** -60), np.float32(2.0 ** 60)  # the scales blissgpu_scaled_knn accepts
 
@@ -1417,6 +1551,44 @@ def choose_k(songs_or_X, ks, seed=0, metric_builder=euclidean_distance, max_iter
             scores.append(score)
             if best is None or _best_k(ks, scores) != best[0]:  # (only the winner's clustering is brought to the host)
                 best = (k, Clustering(labels.cpu().numpy(), dist.cpu().numpy(), cent.cpu().numpy(), sizes.cpu().numpy(), n_iter, conv))
+    except _ffi.BlissGpuError as e:
+        _nan_to_panic(e)
+    return KSelection(ks, scores, best[0], best[1])
+
+
+def choose_k_tree(songs_or_X, tree: "WardTree", ks, metric_builder=euclidean_distance) -> KSelection:
+    """Which k suits the songs, from ONE Ward tree: for every k of `ks` the silhouette (Context.silhouette, on rows uploaded once)
+    of tree.cut(k) -- a cut per k where choose_k runs a whole k-means per k, and the clusterings are nested.  -> KSelection:
+    the highest silhouette score wins, equal scores go to the lower k; `clustering` is the winner's labels (int64 [n], as
+    tree.cut(best_k) gives them).  Every k must be 2 .. n.  metric_builder: as ward_tree."""
+    metric, m = _ward_metric(metric_builder)
+    ks = [int(k) for k in ks]
+    if not ks:
+        raise ValueError("choose_k_tree needs at least one k")
+    X = _rows_of_input(songs_or_X)
+    n = X.shape[0]
+    if n != tree.n:
+        raise ValueError("the tree was made from another number of songs")
+    if min(ks) < 2 or max(ks) > n:
+        raise ValueError("every k must be 2 .. n")
+    import math
+
+    import torch
+
+    from .device import Context
+
+    ctx = Context.default()
+    dev = torch.device("cuda", ctx.device)
+    Xd = torch.from_numpy(X).to(dev)
+    Md = None if m is None else torch.from_numpy(np.ascontiguousarray(m, dtype=np.float32)).to(dev)
+    scores, best = [], None
+    try:
+        for k in ks:
+            labels = tree.cut(k)
+            s = ctx.silhouette(Xd, torch.from_numpy(labels).to(dev), metric, Md, None, 0, k)[0]
+            scores.append(math.fsum(float(v) for v in s.cpu().numpy()) / s.shape[0])
+            if best is None or _best_k(ks, scores) != best[0]:
+                best = (k, labels)
     except _ffi.BlissGpuError as e:
         _nan_to_panic(e)
     return KSelection(ks, scores, best[0], best[1])

@@ -610,6 +610,61 @@ int blissgpu_mst(const float *x, uint64_t n, uint32_t d, int metric, const float
 int blissgpu_mst_device(blissgpu_ctx *ctx, const float *d_x, uint64_t n, uint32_t d, int metric, const float *d_M,
                         const float *d_core, uint32_t *d_edge_u, uint32_t *d_edge_v, float *d_edge_w, uint32_t *rounds);
 
+/* ---- Ward clustering of a library: the whole dendrogram ----
+ * A nested hierarchy of compact clusters -- a genre that opens into sub-genres that open into scenes: one tree, any K by cutting
+ * it, K clusters always a refinement of K - 1.  Ward's minimum-variance linkage needs only the clusters' centroids and sizes,
+ *   cost(A, B) = |A| |B| / (|A| + |B|) * ||c_A - c_B||^2   (the growth of the within-cluster sum of squares the merge causes),
+ * so it is done like every scan here: all pairs on the device, O(n) memory, no n x n matrix.  Ward is reducible: every pair of
+ * clusters that are each other's nearest may merge in the same round, which makes a few dozen rounds of n - 1 merges.
+ * Inputs: rows c [m][d] f32, 1 <= d <= 64; sizes size [m] u32, NULL = all 1, every size >= 1, their sum < 2^24 (every size
+ * and every sum of two is exact in f32); metric: BLISSGPU_METRIC_EUCLIDEAN, or BLISSGPU_METRIC_MAHALANOBIS with the caller's M
+ * (a diagonal M is detected as everywhere else).  All arithmetic is f32, every operation rounded on its own, nothing fused,
+ * division correctly rounded.
+ * PAIR COST, for positions i != j:
+ *   dist(i, j) = bit for bit what blissgpu_pairwise_device(c, c) writes at [i][j] (the same bits at [j][i], see blissgpu_mst);
+ *   w(i, j)    = ((float)size[i] * (float)size[j]) / ((float)size[i] + (float)size[j]);
+ *   cost(i, j) = (dist(i, j) * dist(i, j)) * w(i, j).
+ * Costs are >= +0 or +inf, so the order of their bit patterns as uint32_t is the float order; cost(i, j) and cost(j, i) have
+ * the same bits.
+ * NEAREST.  nn[i] = the j != i with the smallest 64-bit key (bits(cost(i, j)) << 32) | (i XOR j), cost[i] = that cost.  The XOR
+ * tie-break is deliberate: with "ties to the lower index" a block of B identical songs (silent tracks, duplicates) points at
+ * one member and merges one pair per round; under the XOR rule the pair of equal-cost positions with the smallest i XOR j is
+ * always mutual, so equal rows pair up like the leaves of a binary trie (300 identical rows: 9 rounds, not 299).
+ * m == 1: nn[0] = 0xFFFFFFFF, cost[0] = +inf, no device is touched.  m == 0: nothing is touched.
+ * THE TREE.  State: m clusters at positions 0 .. m - 1, each with a row, a size and low, its lowest member song.  Start:
+ * m = n, the rows are x, all sizes 1, low[p] = p.  Round r = 0, 1, ... while m > 1:
+ *   take nn and cost by the rule above; the round's pairs are all (p, q), p < q, with nn[p] == q and nn[q] == p (disjoint by
+ *   construction); each pair emits an edge (u = low[p], v = low[q], cost[p], size[p] + size[q], r) and replaces row p by
+ *     c_p[k] = (float)(((double)size[p] * (double)c_p[k] + (double)size[q] * (double)c_q[k]) / (double)(size[p] + size[q]))
+ *   (the two products, the sum and the quotient each rounded in f64); size[p] += size[q]; position q disappears and the
+ *   survivors keep their relative order, so the positions stay ordered by low and u < v always.
+ * This procedure is the contract: the tree is what these rounds produce on these roundings, not "the" Ward dendrogram of the
+ * exact costs (with which it agrees wherever the costs are apart by more than their rounding).
+ * Outputs of blissgpu_ward: the n - 1 edges ascending in (bits(cost), round, u): edge_u, edge_v [n - 1] u32, edge_cost [n - 1]
+ * f32, edge_size [n - 1] u32 (may be NULL), edge_round [n - 1] u32 (may be NULL); rounds (host memory, may be NULL) receives
+ * the number of rounds.  n <= 1: no edge, BLISSGPU_OK, *rounds = 0, and no device is touched.
+ * BLISSGPU_ERR_INVALID with a message, and nothing written, exactly when some cost of some round is NaN -- a NaN feature,
+ * inf - inf, a negative sum under an M that is not positive semi-definite (every pair is evaluated in every round).
+ * BLISSGPU_ERR_INVALID too, before the device is touched and each with a message that names the argument:
+ * BLISSGPU_METRIC_COSINE; an unknown metric; Mahalanobis without M; d outside 1 .. 64; n (m) or the sum of the sizes >= 2^24;
+ * a size of 0; a NULL c, x, edge_u, edge_v or edge_cost with n (m) >= 2, a NULL nn or cost with m >= 1.  A round that merges
+ * nothing is a defect: BLISSGPU_ERR_INTERNAL.
+ * Workspace, grow-only in the context and O(n): the best key of every position (8 n bytes, which the column groups of the scan
+ * fold their winners into by 64-bit integer minima: a total order, so no split of the columns changes a bit), and for the tree
+ * a copy of the rows (4 n d bytes, rewritten in place by the joins), two sets of sizes and low (16 n) and the join plan (8 n).
+ * Beyond the context's workspace limit (blissgpu_ctx_get_workspace_limit) the call returns BLISSGPU_ERR_OOM before anything is
+ * launched.  Per round the host receives 16 + 8 m bytes (one copy, one synchronisation) and sends the plan, 8 bytes per
+ * surviving position.
+ * For the tests and the bench tool, read from the environment at every call, and without effect on any bit of the result:
+ * BLISSGPU_WARD_COL_GROUPS = the scan's column groups (default: the plan's), BLISSGPU_WARD_FILTER = 0 takes the root and the
+ * weight of every pair, = 1 only of those a one-sided bound lets through (default: the latter in the scans of 12 288 positions
+ * or more), BLISSGPU_WARD_TRACE prints every round's clusters, pairs and milliseconds to stderr.
+ * Both are host-pointer forms over the context of the default device; there is no device-pointer form. */
+int blissgpu_ward_nearest(const float *c, const uint32_t *size, uint64_t m, uint32_t d, int metric, const float *M, uint32_t *nn,
+                          float *cost); /* one scan: what a round computes */
+int blissgpu_ward(const float *x, uint64_t n, uint32_t d, int metric, const float *M, uint32_t *edge_u, uint32_t *edge_v,
+                  float *edge_cost, uint32_t *edge_size, uint32_t *edge_round, uint32_t *rounds);
+
 /* ---- Learning the Mahalanobis matrix from training triplets ----
  * The reference has a `training_triplet` table ("song_1 and song_2 are closer together than they are to odd_one_out",
  * src/library.rs:542-556), a TODO.md that asks for "a way to learn a metric with a user survey", and no code that learns.
