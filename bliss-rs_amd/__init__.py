@@ -18,6 +18,7 @@ bliss-rs / `bliss-audio` 0.13.0):
     playlist.group_neighbours, library.similar_groups / similar_artists / similar_artists_playlist: which artists (albums, genres) are like each other
     playlist.minimum_spanning_tree / core_distances, library.song_tree / linked_clusters / tour: clusters without k, the dendrogram, a tour of the library
     playlist.ward_tree / ward_nearest / choose_k_tree, library.ward_tree / ward_clusters: Ward's dendrogram -- compact clusters that nest, any k by cutting one tree
+    playlist.kmedoids / pam_scan / medoid_songs, library.medoid_songs: k-medoids -- the k SONGS that summarise a library, under cosine too
     playlist.local_scales / scaled_nearest_order / hubness, library.similar_songs_scaled / hubness / orphan_songs: lists that a few hub songs do not dominate, and a measure of how much they do
     playlist.ForestOptions / forest_scores: the extended isolation forest metric for several seed songs   src/playlist.rs:230-251
     library.{load_feature_matrix, load_songs, store_song}   feature table of src/library.rs:500-531, 1355-1372, 1560-1630

@@ -48,6 +48,8 @@ const char kRadioBanName[] = "radio_ban_kernel", kRadioStepName[] = "radio_step_
 const char kMapRepulseName[] = "map_repulse_kernel", kMapAttractName[] = "map_attract_kernel";  // KX_MAP_*
 const char kMapUpdateName[] = "map_update_kernel";
 const char kWardScanName[] = "ward_scan_kernel", kWardJoinName[] = "ward_join_kernel";  // KX_WARD_*
+const char kPamScanName[] = "pam_scan_kernel", kPamFoldName[] = "pam_fold_kernel", kPamPickName[] = "pam_pick_kernel";  // KX_PAM_*
+const char kPamGatherName[] = "pam_gather_kernel", kPamStateName[] = "pam_state_kernel", kPamTdName[] = "pam_td_kernel";
 const char* const kKernelNames[K_COUNT] = {
     "fft512_kernel",     "onset_kernel",      "beat_kernel",   "stft8192_kernel", "tune_select_kernel",
     "tune_pass2_kernel", "tune_final_kernel", "chroma_kernel",     "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel", "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel",
@@ -67,6 +69,7 @@ const char* const kKernelNames[K_COUNT] = {
     kRadioBanName, kRadioStepName,
     kMapRepulseName, kMapAttractName, kMapUpdateName,
     kWardScanName, kWardJoinName,
+    kPamScanName, kPamFoldName, kPamPickName, kPamGatherName, kPamStateName, kPamTdName,
     kGroupForestScanName, kJourneyStepName};
 }  // namespace
 
@@ -392,7 +395,7 @@ int blissgpu_ctx_destroy(blissgpu_ctx* c) {
         (void)hipFree(c->bt_rwv); (void)hipFree(c->bt_dfwv); (void)hipFree(c->chroma_bank);
         scheduler_release(c);
         c->dbg_tuning.release(); c->dbg_nbpms.release(); c->dbg_chroma.release(); c->dbg_interval.release();
-        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->km_ws.release(); c->sil_ws.release(); c->mo_ws.release(); c->ch_ws.release(); c->ms_ws.release(); c->wd_ws.release(); c->wd_host.release(); c->map_ws.release(); c->mt_ws.release(); c->pl_next.release(); c->st_idx.release();
+        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->km_ws.release(); c->sil_ws.release(); c->mo_ws.release(); c->ch_ws.release(); c->ms_ws.release(); c->wd_ws.release(); c->wd_host.release(); c->pam_ws.release(); c->map_ws.release(); c->mt_ws.release(); c->pl_next.release(); c->st_idx.release();
         c->st_a.release(); c->st_b.release(); c->st_m.release(); c->st_dist.release(); c->st_out.release();
         c->fl_bytes.release(); c->fl_tab.release(); c->fl_pcm.release(); c->fl_status.release(); c->fl_end.release();
         c->fl_bad.release(); c->fl_mono.release(); c->fl_rows.release(); c->fl_htab.release();
@@ -1947,6 +1950,360 @@ int blissgpu_ward(const float* x, uint64_t n, uint32_t d, int metric, const floa
         if (edge_round) edge_round[k] = e.round;
     }
     if (rounds) *rounds = st.rounds;
+    return BLISSGPU_OK;
+}
+
+// ---- k-medoids (PAM): the state by the k-nearest core over the medoids' rows, then per round one all-pairs scan of every
+// candidate against every song (kernels_pam.hip); no distance matrix, the host reads one record per round ----
+// (for the tests and the bench tool: no bit of the result depends on either)
+struct PamSwitches {
+    uint32_t col_groups = 0;
+    bool trace = false;
+    PamSwitches() {
+        if (const char* e = getenv("BLISSGPU_PAM_COL_GROUPS")) col_groups = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 65535ul);
+        trace = getenv("BLISSGPU_PAM_TRACE") != nullptr;
+    }
+};
+
+// the workspace, O(n + slab k): the record (32 bytes, then 32 unused) | hist u32[hist_cap] | scan totals u32[tiles_cap + 1] |
+// arow_off u32[k + 1] | arow u32[n] | near u32[n] | ismed u32[n] | med u32[k] | d1 f32[n] | d2 f32[n] | the medoids' rows
+// f32[k][d] | the state's search: idx u32[n][2], dist f32[n][2] | (8-byte aligned) A f64[slab][k] | B f64[slab][k].  The slab is
+// every candidate when that fits the workspace limit, else as many rows as fit (whole wavefronts of 256 where there is room for
+// them).  hist_cap / tiles_cap: the largest histogram table and scan-total count among the sorts the call makes -- K = k_lo .. k
+// slots (BUILD sorts every K from 1; a scan alone sorts k).  kmeans_plan caps its chunks at 2^21 / K and rounds them to 64
+// songs, so K * W is NOT monotone in K: the largest is found by asking the plan of every K, not by asking that of k
+struct PamLayout {
+    size_t o_hist, o_bsum, o_off, o_arow, o_near, o_ismed, o_med, o_d1, o_d2, o_rows, o_kidx, o_kdist, o_ab;
+    uint64_t hist_cap, tiles_cap, fixed, per_row, slab;  // fixed: the bytes in front of A; slab == 0: one candidate's share does not fit
+};
+static PamLayout pam_layout(uint64_t n, uint32_t d, uint32_t k_lo, uint32_t k, uint64_t q, uint64_t ws_limit) {
+    PamLayout L{};
+    for (uint32_t K = k_lo; K <= k; K++) {
+        const KmeansPlan sort = kmeans_plan(n, K, 0);
+        L.hist_cap = std::max<uint64_t>(L.hist_cap, sort.hist_words);
+        L.tiles_cap = std::max<uint64_t>(L.tiles_cap, sort.scan_tiles);
+    }
+    size_t o = 16;
+    L.o_hist = o; o += (size_t)L.hist_cap;
+    L.o_bsum = o; o += (size_t)L.tiles_cap + 1;
+    L.o_off = o; o += (size_t)k + 1;
+    L.o_arow = o; o += n;
+    L.o_near = o; o += n;
+    L.o_ismed = o; o += n;
+    L.o_med = o; o += k;
+    L.o_d1 = o; o += n;
+    L.o_d2 = o; o += n;
+    L.o_rows = o; o += (size_t)k * d;
+    L.o_kidx = o; o += 2 * n;
+    L.o_kdist = o; o += 2 * n;
+    L.o_ab = (o + 1) & ~(size_t)1;
+    L.fixed = (uint64_t)L.o_ab * sizeof(uint32_t);
+    L.per_row = 16ull * k;
+    if (L.fixed + L.per_row > ws_limit) return L;
+    L.slab = std::min<uint64_t>(std::max<uint64_t>(q, 1), (ws_limit - L.fixed) / L.per_row);
+    if (L.slab < q) L.slab = L.slab >= 1024 ? L.slab & ~1023ull : L.slab >= 256 ? L.slab & ~255ull : L.slab;
+    return L;
+}
+struct PamWs {
+    PamRecord* rec;
+    uint32_t *hist, *bsum, *arow_off, *arow, *near, *ismed, *med, *kidx;
+    float *d1, *d2, *medrows, *kdist;
+    double *a, *b;
+    uint64_t slab, hist_cap, tiles_cap;
+    size_t zero_words;  // the record's 16 words: zeroed before a round's first launch
+};
+static int pam_workspace(blissgpu_ctx* c, const char* who, uint64_t n, uint32_t d, uint32_t k_lo, uint32_t k, uint64_t q, PamWs* ws) {
+    const PamLayout L = pam_layout(n, d, k_lo, k, q, c->ws_limit);
+    if (L.slab == 0) return fail(BLISSGPU_ERR_OOM, who, "the state and one candidate's sums do not fit the workspace limit");
+    int rc = c->pam_ws.ensure(L.fixed + L.slab * L.per_row);
+    if (rc) return rc;
+    uint32_t* w = reinterpret_cast<uint32_t*>(c->pam_ws.p);
+    ws->rec = reinterpret_cast<PamRecord*>(w);
+    ws->hist = w + L.o_hist; ws->bsum = w + L.o_bsum; ws->arow_off = w + L.o_off; ws->arow = w + L.o_arow; ws->near = w + L.o_near;
+    ws->ismed = w + L.o_ismed; ws->med = w + L.o_med; ws->kidx = w + L.o_kidx;
+    ws->d1 = reinterpret_cast<float*>(w + L.o_d1); ws->d2 = reinterpret_cast<float*>(w + L.o_d2);
+    ws->medrows = reinterpret_cast<float*>(w + L.o_rows); ws->kdist = reinterpret_cast<float*>(w + L.o_kdist);
+    ws->a = reinterpret_cast<double*>(w + L.o_ab); ws->b = ws->a + L.slab * k;
+    ws->slab = L.slab; ws->hist_cap = L.hist_cap; ws->tiles_cap = L.tiles_cap;
+    ws->zero_words = L.o_hist;
+    static_assert(sizeof(PamRecord) == 32, "the record is the workspace's first 32 bytes");
+    return BLISSGPU_OK;
+}
+
+struct PamPick {  // what the round's winner is taken over
+    enum Kind { NONE, BEST, BTOT, A0 } kind = NONE;
+    bool skip_medoids = false;
+};
+struct PamOut {  // where a scan's results go: btot, best, arg on the device, [q]
+    double *btot, *best;
+    uint32_t* arg;
+    double *host_a, *host_b;  // HOST memory [q][K] (either may be NULL): copied back slab by slab through the call's HostStage
+};
+
+// one scan over the candidates d_rows[0 .. q) (NULL: every song, q = n) under the state in ws (near, d1, d2) with K slots: the
+// sort of near, then per slab of candidates the scan, the fold and -- when asked -- the pick into ws.rec.  The caller has zeroed
+// the record.  Nothing is synchronised unless host_a / host_b want a slab's sums before the next overwrites them
+static int pam_scan_core(blissgpu_ctx* c, HostStage& s, const char* who, const float* d_x, uint64_t n, uint32_t d, uint32_t K, int metric,
+                         const float* d_M, int diag, const uint32_t* d_rows, uint64_t q, const PamSwitches& sw, const PamWs& ws,
+                         const PamOut& out, PamPick pick) {
+    const KmeansPlan sort = kmeans_plan(n, K, c->n_cus);
+    if (sort.hist_words > ws.hist_cap || sort.scan_tiles > ws.tiles_cap)
+        return fail(BLISSGPU_ERR_INTERNAL, who, "the sort of the slots needs more than the workspace holds for it");
+    HIP_TRY(hipMemsetAsync(ws.hist, 0, (size_t)sort.hist_words * sizeof(uint32_t), c->stream));
+    launch_label_sort(c, ws.near, (uint32_t)n, K, sort, ws.hist, ws.bsum, ws.arow_off, ws.arow);
+    HIP_TRY(hipGetLastError());
+    for (uint64_t row0 = 0; row0 < q; row0 += ws.slab) {
+        const uint64_t qs = std::min<uint64_t>(ws.slab, q - row0);
+        const SilhouettePlan plan = silhouette_plan(qs, K, c->n_cus, sw.col_groups);
+        PamArgs a{};
+        a.X = d_x; a.M = d_M; a.arow_off = ws.arow_off; a.arow = ws.arow; a.rows = d_rows ? d_rows + row0 : nullptr;
+        a.d1 = ws.d1; a.d2 = ws.d2; a.n = (uint32_t)n; a.K = K; a.q = (uint32_t)qs; a.row0 = (uint32_t)row0; a.Y = plan.Y; a.d = d;
+        a.metric = metric; a.ws_a = ws.a; a.ws_b = ws.b; a.flags = &ws.rec->nan;
+        a.btot = out.btot + row0; a.best = out.best + row0; a.arg = out.arg + row0;
+        { Prof p(c, KX_PAM_SCAN); launch_pam_scan(a, diag, plan, c->stream); }
+        { Prof p(c, KX_PAM_FOLD); launch_pam_fold(a, c->stream); }
+        if (pick.kind != PamPick::NONE) {
+            const double* val = pick.kind == PamPick::BEST ? a.best : pick.kind == PamPick::BTOT ? a.btot : ws.a;
+            Prof p(c, KX_PAM_PICK);
+            launch_pam_pick(val, pick.kind == PamPick::A0 ? K : 1u, pick.kind == PamPick::BEST ? a.arg : nullptr, a.rows, a.row0, a.q,
+                            pick.skip_medoids ? ws.ismed : nullptr, row0 == 0, ws.rec, c->stream);
+        }
+        HIP_TRY(hipGetLastError());
+        if (out.host_a || out.host_b) {
+            const size_t bytes = (size_t)qs * K * sizeof(double);
+            if (out.host_a) s.down(out.host_a + row0 * K, ws.a, bytes);
+            if (out.host_b) s.down(out.host_b + row0 * K, ws.b, bytes);
+            if (int e = s.landed()) return e;  // (the next slab overwrites A and B)
+        }
+    }
+    return BLISSGPU_OK;
+}
+
+static int pam_scalars_ok(const char* who, uint64_t n, uint32_t d, uint32_t k, int metric, const float* M) {
+    if (d == 0 || d > 64) return fail(BLISSGPU_ERR_INVALID, who, "d must be 1 .. 64");
+    if (k == 0 || k > BLISSGPU_KMEANS_MAX_K) return fail(BLISSGPU_ERR_INVALID, who, "k must be 1 .. BLISSGPU_KMEANS_MAX_K");
+    if (metric != BLISSGPU_METRIC_EUCLIDEAN && metric != BLISSGPU_METRIC_COSINE && metric != BLISSGPU_METRIC_MAHALANOBIS)
+        return fail(BLISSGPU_ERR_INVALID, who, "unknown metric");
+    if (metric == BLISSGPU_METRIC_MAHALANOBIS && !M) return fail(BLISSGPU_ERR_INVALID, who, "mahalanobis needs M");
+    if (n >= 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "n must be below 2^32 - 1 songs");
+    return BLISSGPU_OK;
+}
+
+int blissgpu_pam_scan(const float* x, uint64_t n, uint32_t d, const uint32_t* near, const float* d1, const float* d2, uint32_t k, int metric,
+                      const float* M, const uint32_t* rows, uint64_t q, double* btot, double* best, uint32_t* arg, double* A, double* B) {
+    const char* who = "blissgpu_pam_scan";
+    int rc = pam_scalars_ok(who, n, d, k, metric, M);
+    if (rc) return rc;
+    if (!rows) q = n;
+    if (q >= 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "q must be below 2^32 - 1 candidates");
+    if (n == 0 || q == 0) return BLISSGPU_OK;  // nothing to evaluate: nothing is touched
+    if (!x) return fail(BLISSGPU_ERR_INVALID, who, "x is NULL");
+    if (!near) return fail(BLISSGPU_ERR_INVALID, who, "near is NULL");
+    if (!d1) return fail(BLISSGPU_ERR_INVALID, who, "d1 is NULL");
+    if (!d2) return fail(BLISSGPU_ERR_INVALID, who, "d2 is NULL");
+    if (!btot) return fail(BLISSGPU_ERR_INVALID, who, "btot is NULL");
+    if (!best) return fail(BLISSGPU_ERR_INVALID, who, "best is NULL");
+    if (!arg) return fail(BLISSGPU_ERR_INVALID, who, "arg is NULL");
+    // near, d1, d2 and rows are host memory: what is wrong with them is found here, before the device is touched
+    for (uint64_t o = 0; o < n; o++) {
+        if (near[o] >= k) return fail(BLISSGPU_ERR_INVALID, who, "a near entry is >= k");
+        if (d1[o] != d1[o]) return fail(BLISSGPU_ERR_INVALID, who, "d1 holds a NaN");
+        if (d2[o] != d2[o]) return fail(BLISSGPU_ERR_INVALID, who, "d2 holds a NaN");
+    }
+    if (rows)
+        for (uint64_t p = 0; p < q; p++)
+            if (rows[p] >= n) return fail(BLISSGPU_ERR_INVALID, who, "a rows entry is >= n");
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    const float* dM = nullptr;
+    PamWs ws{};
+    rc = pam_workspace(c, who, n, d, k, k, q, &ws);
+    if (!rc) rc = c->st_b.ensure(n * d);
+    if (!rc) rc = c->st_idx.ensure(2 * q);                     // rows | arg
+    if (!rc) rc = c->st_out.ensure(2 * q * sizeof(double));    // btot | best
+    if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
+    if (rc) return rc;
+    int diag = 0;
+    if (int e = metric_is_diag(c, dM, d, metric, &diag)) return e;
+    uint32_t *d_rows = rows ? c->st_idx.p : nullptr, *d_arg = c->st_idx.p + q;
+    double *d_btot = reinterpret_cast<double*>(c->st_out.p), *d_best = d_btot + q;
+    HostStage s{c, "pam_scan"};
+    s.up(c->st_b.p, x, n * d * sizeof(float));
+    s.up(ws.near, near, n * sizeof(uint32_t));  // (the state goes straight into the workspace)
+    s.up(ws.d1, d1, n * sizeof(float));
+    s.up(ws.d2, d2, n * sizeof(float));
+    s.up(d_rows, rows, q * sizeof(uint32_t));
+    rc = s.uploaded();
+    const PamSwitches sw;
+    auto run = [&]() -> int {
+        HIP_TRY(hipMemsetAsync(ws.rec, 0, ws.zero_words * sizeof(uint32_t), c->stream));
+        const PamOut out{d_btot, d_best, d_arg, A, B};
+        if (int e = pam_scan_core(c, s, who, c->st_b.p, n, d, k, metric, dM, diag, d_rows, q, sw, ws, out, PamPick{})) return e;
+        uint32_t nan_word = 0;
+        if (int e = read_flags(c, &ws.rec->nan, 1, &nan_word)) return e;
+        if (nan_word) return fail(BLISSGPU_ERR_NAN, who, "NaN distance (the reference panics here)");
+        return BLISSGPU_OK;
+    };
+    if (!rc) rc = run();
+    if (!rc) {
+        s.down(btot, d_btot, q * sizeof(double));
+        s.down(best, d_best, q * sizeof(double));
+        s.down(arg, d_arg, q * sizeof(uint32_t));
+    }
+    return s.finish(rc);
+}
+
+int blissgpu_kmedoids(const float* x, uint64_t n, uint32_t d, uint32_t k, int metric, const float* M, const uint32_t* init, uint32_t max_swaps,
+                      uint32_t* medoids, uint32_t* labels, float* dist, uint32_t* sizes, double* td_trace, uint32_t* n_swaps,
+                      int32_t* converged) {
+    const char* who = "blissgpu_kmedoids";
+    int rc = pam_scalars_ok(who, n, d, k, metric, M);
+    if (rc) return rc;
+    if (!n_swaps) return fail(BLISSGPU_ERR_INVALID, who, "n_swaps is NULL");
+    if (!converged) return fail(BLISSGPU_ERR_INVALID, who, "converged is NULL");
+    if (n == 0) {  // no song: nothing for a device to do
+        *n_swaps = 0;
+        *converged = 1;
+        return BLISSGPU_OK;
+    }
+    if (k > n) return fail(BLISSGPU_ERR_INVALID, who, "k must be at most n: the medoids are distinct songs");
+    if (!x) return fail(BLISSGPU_ERR_INVALID, who, "x is NULL");
+    if (!medoids) return fail(BLISSGPU_ERR_INVALID, who, "medoids is NULL");
+    if (!labels) return fail(BLISSGPU_ERR_INVALID, who, "labels is NULL");
+    if (!td_trace) return fail(BLISSGPU_ERR_INVALID, who, "td_trace is NULL");
+    if (init) {
+        std::vector<uint32_t> sorted(init, init + k);
+        std::sort(sorted.begin(), sorted.end());
+        if (sorted.back() >= n) return fail(BLISSGPU_ERR_INVALID, who, "an init entry is >= n");
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(BLISSGPU_ERR_INVALID, who, "init holds a song twice");
+    }
+    blissgpu_ctx* c;
+    rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    const float* dM = nullptr;
+    PamWs ws{};
+    rc = pam_workspace(c, who, n, d, init ? k : 1u, k, n, &ws);
+    if (!rc) rc = c->st_b.ensure(n * d);
+    if (!rc) rc = c->st_idx.ensure(n);                        // arg
+    if (!rc) rc = c->st_out.ensure(2 * n * sizeof(double));   // btot | best
+    if (!rc) rc = c->pl_tmp.ensure((size_t)knn_plan(n, k, 2, c->n_cus).part_keys * sizeof(unsigned long long));
+    if (!rc) rc = stage_matrix(c, M, d, metric, &dM);
+    if (rc) return rc;
+    int diag = 0;
+    if (int e = metric_is_diag(c, dM, d, metric, &diag)) return e;
+    const float* d_x = c->st_b.p;
+    const PamOut out{reinterpret_cast<double*>(c->st_out.p), reinterpret_cast<double*>(c->st_out.p) + n, c->st_idx.p, nullptr, nullptr};
+    HostStage s{c, "kmedoids"};
+    s.up(c->st_b.p, x, n * d * sizeof(float));
+    s.up(ws.med, init, (size_t)k * sizeof(uint32_t));
+    rc = s.uploaded();
+    const PamSwitches sw;
+    const uint32_t nn = (uint32_t)n;
+    PamRecord h{};
+    // the record of a round: zeroed before the round's first launch, read after its last
+    auto reset = [&]() -> int {
+        HIP_TRY(hipMemsetAsync(ws.rec, 0, ws.zero_words * sizeof(uint32_t), c->stream));
+        return BLISSGPU_OK;
+    };
+    auto read = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(&h, ws.rec, sizeof(PamRecord), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (h.nan) return fail(BLISSGPU_ERR_NAN, who, "NaN distance (the reference panics here)");
+        return BLISSGPU_OK;
+    };
+    // the state of the first K medoids: their rows (with a swap or an appended slot applied first), the k-nearest core with k =
+    // min(2, K) over them, near / d1 / d2, and TD into the record
+    auto state = [&](uint32_t K, uint32_t swap_slot, uint32_t swap_c, bool append, bool mark_all) -> int {
+        { Prof p(c, KX_PAM_GATHER); launch_pam_gather(d_x, ws.med, K, d, ws.medrows, swap_slot, swap_c, append, mark_all, ws.ismed, c->stream); }
+        const uint32_t kk = K >= 2 ? 2u : 1u;
+        const KnnPlan plan = knn_plan(n, K, kk, c->n_cus);
+        if (int e = c->pl_tmp.ensure((size_t)plan.part_keys * sizeof(unsigned long long))) return e;
+        unsigned long long* part = reinterpret_cast<unsigned long long*>(c->pl_tmp.p);
+        { Prof p(c, K_KNN_SCAN); launch_knn_scan(d_x, n, ws.medrows, K, d, metric, dM, diag, nullptr, kk, plan, part, &ws.rec->nan, &ws.rec->bad, c->stream); }
+        { Prof p(c, K_KNN_MERGE); launch_knn_merge(part, n, kk, plan, ws.kidx, ws.kdist, c->stream); }
+        { Prof p(c, KX_PAM_STATE); launch_pam_state(ws.kidx, ws.kdist, nn, kk, ws.near, ws.d1, ws.d2, c->stream); }
+        { Prof p(c, KX_PAM_TD); launch_pam_td(ws.d1, nn, ws.rec, c->stream); }
+        HIP_TRY(hipGetLastError());
+        return BLISSGPU_OK;
+    };
+    uint32_t swaps = 0;
+    int conv = 0;
+    auto run = [&]() -> int {
+        const auto now = [&]() { return sw.trace ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point{}; };
+        const auto t0 = now();
+        HIP_TRY(hipMemsetAsync(ws.ismed, 0, n * sizeof(uint32_t), c->stream));
+        uint32_t swap_slot = PAM_NONE, swap_c = 0;
+        bool append = false;
+        if (!init) {
+            // BUILD.  Slot 0: the smallest A(c, 0) under near = 0, d1 = 0, d2 = +inf, k = 1
+            if (int e = reset()) return e;
+            HIP_TRY(hipMemsetAsync(ws.near, 0, n * sizeof(uint32_t), c->stream));
+            HIP_TRY(hipMemsetAsync(ws.d1, 0, n * sizeof(float), c->stream));
+            HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ws.d2), 0x7F800000, n, c->stream));
+            if (int e = pam_scan_core(c, s, who, d_x, n, d, 1u, metric, dM, diag, nullptr, n, sw, ws, out, PamPick{PamPick::A0, false})) return e;
+            if (int e = read()) return e;
+            if (h.c == PAM_NONE) return fail(BLISSGPU_ERR_NAN, who, "no first medoid: every sum of distances is NaN");
+            swap_slot = 0; swap_c = h.c; append = true;
+            // every further slot: the non-medoid c with the smallest btot(c) under the state so far
+            for (uint32_t K = 1; K < k; K++) {
+                if (int e = reset()) return e;
+                if (int e = state(K, swap_slot, swap_c, true, false)) return e;
+                if (int e = pam_scan_core(c, s, who, d_x, n, d, K, metric, dM, diag, nullptr, n, sw, ws, out, PamPick{PamPick::BTOT, true})) return e;
+                if (int e = read()) return e;
+                if (h.c == PAM_NONE) return fail(BLISSGPU_ERR_NAN, who, "no next medoid: every candidate's change is NaN");
+                if (sw.trace) fprintf(stderr, "%s build slot %u: song %u, btot %.17g\n", who, K, h.c, h.val);
+                swap_slot = K; swap_c = h.c;
+            }
+        }
+        for (;;) {
+            if (int e = reset()) return e;
+            if (int e = state(k, swap_slot, swap_c, append, init && swaps == 0)) return e;
+            const auto t_scan = now();
+            if (int e = pam_scan_core(c, s, who, d_x, n, d, k, metric, dM, diag, nullptr, n, sw, ws, out, PamPick{PamPick::BEST, true})) return e;
+            if (int e = read()) return e;
+            td_trace[swaps] = h.td;
+            if (sw.trace)
+                fprintf(stderr, "%s round %u: TD %.17g, winner %u into slot %u, delta %.17g, scan %.3f ms\n", who, swaps, h.td, h.c, h.arg, h.val,
+                        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_scan).count());
+            if (h.c == PAM_NONE || !(h.val < 0.0)) { conv = 1; break; }
+            if (swaps == max_swaps) break;
+            swap_slot = h.arg; swap_c = h.c; append = false;
+            swaps++;
+        }
+        if (sw.trace)
+            fprintf(stderr, "%s: %u swaps, %.3f ms in all\n", who, swaps, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        return BLISSGPU_OK;
+    };
+    if (!rc) rc = run();
+    if (!rc) {
+        s.down(medoids, ws.med, (size_t)k * sizeof(uint32_t));
+        s.down(labels, ws.near, n * sizeof(uint32_t));
+        s.down(dist, ws.d1, n * sizeof(float));
+    }
+    if ((rc = s.finish(rc))) return rc;
+    if (sizes) {
+        memset(sizes, 0, (size_t)k * sizeof(uint32_t));
+        for (uint64_t o = 0; o < n; o++) sizes[labels[o]]++;
+    }
+    *n_swaps = swaps;
+    *converged = conv;
+    return BLISSGPU_OK;
+}
+
+int blissgpu_pam_plan(uint64_t n, uint32_t d, uint32_t k, uint64_t q, int build, uint64_t ws_limit, uint64_t* plan) {
+    const char* who = "blissgpu_pam_plan";
+    int rc = pam_scalars_ok(who, n, d, k, BLISSGPU_METRIC_EUCLIDEAN, nullptr);
+    if (rc) return rc;
+    if (!plan) return fail(BLISSGPU_ERR_INVALID, who, "plan is NULL");
+    const PamLayout L = pam_layout(n, d, build ? 1u : k, k, q, ws_limit);
+    plan[0] = L.fixed + L.slab * L.per_row;
+    plan[1] = L.slab;
+    plan[2] = L.hist_cap;
+    plan[3] = L.tiles_cap;
+    if (L.slab == 0) return fail(BLISSGPU_ERR_OOM, who, "the state and one candidate's sums do not fit the workspace limit");
     return BLISSGPU_OK;
 }
 

@@ -123,7 +123,7 @@ enum KernelId : int {
     K_CHAIN_STEP, K_CHAIN_WALK,             // song-to-song chains cut after k (kernels_chains.hip)
     // (tests/test_chains_host.py holds this list, and the list of names beside it, to end in the chain kernels: the kernels
     // that came later are numbered behind it, so that no older id or name moves)
-    K_COUNT = K_CHAIN_WALK + 35
+    K_COUNT = K_CHAIN_WALK + 41
 };
 // k-nearest albums per seed group (kernels_albums.hip; its partial lists are merged by knn_merge_kernel)
 constexpr int KX_SEGMENT_MEAN = K_CHAIN_WALK + 1, KX_ALBUM_KNN_SCAN = K_CHAIN_WALK + 2;
@@ -150,12 +150,15 @@ constexpr int KX_RADIO_BAN = K_CHAIN_WALK + 26, KX_RADIO_STEP = K_CHAIN_WALK + 2
 constexpr int KX_MAP_REPULSE = K_CHAIN_WALK + 28, KX_MAP_ATTRACT = K_CHAIN_WALK + 29, KX_MAP_UPDATE = K_CHAIN_WALK + 30;
 // Ward clustering (kernels_ward.hip): every cluster's nearest other cluster under Ward's cost, the join that makes the next centroids
 constexpr int KX_WARD_SCAN = K_CHAIN_WALK + 31, KX_WARD_JOIN = K_CHAIN_WALK + 32;
+// k-medoids (kernels_pam.hip): the all-pairs swap scan, its fold per candidate, the round's winner, and the state's three helpers
+constexpr int KX_PAM_SCAN = K_CHAIN_WALK + 33, KX_PAM_FOLD = K_CHAIN_WALK + 34, KX_PAM_PICK = K_CHAIN_WALK + 35;
+constexpr int KX_PAM_GATHER = K_CHAIN_WALK + 36, KX_PAM_STATE = K_CHAIN_WALK + 37, KX_PAM_TD = K_CHAIN_WALK + 38;
 // (tests/test_journeys_host.py holds the profile table to END in the next two names: kernels that come later are numbered in
 // front of them; every consumer of the table goes by name)
 // the k lowest forest scores per seed group (kernels_forest.hip; its partial lists are merged by group_knn_merge_kernel)
-constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 33;
+constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 39;
 // a journey's step (kernels_chains.hip: the chains' scan with a waypoint query or a gate)
-constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 34;
+constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 40;
 static_assert(KX_JOURNEY_STEP + 1 == K_COUNT, "every kernel id is below the count");
 
 // lower_bound on a prefix array: largest s with prefix[s] <= x  (prefix has n+1 entries, prefix[0]=0)
@@ -534,6 +537,37 @@ struct WardPlan {
 WardPlan ward_plan(uint64_t m, int n_cus, uint32_t col_groups);
 void launch_ward_scan(const WardArgs& a, int m_is_diag, bool filter, const WardPlan& p, hipStream_t st);
 void launch_ward_join(const WardJoinArgs& a, hipStream_t st);
+// k-medoids, one scan of a slab of candidates (kernels_pam.hip), after the k-means sort of near into arow_off / arow.  The slab's
+// candidates are rows[0 .. q) (NULL: the songs row0 .. row0 + q), cut into pieces of 256 per wavefront; the slots are dealt to Y
+// column groups as the silhouette deals its clusters (silhouette_plan gives the grid).  The scan writes ws_a / ws_b [q][K] for the
+// non-empty slots, the fold fills in the empty ones and forms btot, best, arg [q].  flags[0]: a NaN among the evaluated distances
+constexpr uint32_t PAM_NONE = 0xFFFFFFFFu;
+struct PamArgs {
+    const float *X, *M;
+    const uint32_t *arow_off, *arow, *rows;
+    const float *d1, *d2;
+    uint32_t n, K, q, row0, Y, d;
+    int metric;
+    double *ws_a, *ws_b;
+    uint32_t* flags;
+    double *btot, *best;
+    uint32_t* arg;
+};
+// what the host reads per round: the winner (c == PAM_NONE: no candidate), its value and slot, TD, the NaN word (and the word the
+// k-nearest scan reports a bad skip entry in: never raised here)
+struct PamRecord {
+    double val, td;
+    uint32_t c, arg, nan, bad;
+};
+void launch_pam_scan(const PamArgs& a, int m_is_diag, const SilhouettePlan& p, hipStream_t st);
+void launch_pam_fold(const PamArgs& a, hipStream_t st);
+void launch_pam_pick(const double* val, uint32_t stride, const uint32_t* arg, const uint32_t* rows, uint32_t row0, uint32_t q,
+                     const uint32_t* ismed, bool fresh, PamRecord* rec, hipStream_t st);
+void launch_pam_gather(const float* X, uint32_t* med, uint32_t K, uint32_t d, float* rows_out, uint32_t swap_slot, uint32_t swap_c,
+                       bool append, bool mark_all, uint32_t* ismed, hipStream_t st);
+void launch_pam_state(const uint32_t* idx, const float* dist, uint32_t n, uint32_t kk, uint32_t* near, float* d1, float* d2,
+                      hipStream_t st);
+void launch_pam_td(const float* d1, uint32_t n, PamRecord* rec, hipStream_t st);
 // triplet metric learning, one gradient evaluation (kernels_metric.hip).  The triplets are dealt out in W contiguous chunks, a
 // function of T alone; part [W][pairs + 1] f64 and cnt [W][2] u64 are the wavefronts' partials, out = G f64 [d][d] | loss f64 |
 // n_active u64 | error bits u64 (TRIPLET_ERR_*).  mode says how M is read; flags (u8 [T]) may be NULL

@@ -1084,6 +1084,19 @@ def ward_clusters(db: Conn, k: int = None, cost: float = None, min_cluster_size:
     return lists, loose
 
 
+def medoid_songs(db: Conn, k: int, metric_builder=playlist.euclidean_distance, where=None, return_medoids: bool = False):
+    """The k songs that summarise the library: k-medoids (playlist.medoid_songs) over the analysed songs of
+    FeaturesVersion.LATEST, read once, every round's all-pairs scan on the device.  Any metric the all-pairs kernel knows:
+    playlist.cosine_distance and a MahalanobisBuilder as well as euclidean_distance.  -> (representatives, clusters): k `Song`s
+    and, per representative, the songs nearest to it, nearest first.  where = (column, value): only the songs whose column has
+    that value.  return_medoids: -> (representatives, clusters, playlist.Medoids)."""
+    playlist._pam_metric(metric_builder)  # refused before the database is read
+    songs, _ = _tree_songs(db, where)
+    if not songs:
+        raise ValueError("medoid_songs needs at least one analysed song")
+    return playlist.medoid_songs(songs, k, metric_builder, return_medoids=return_medoids)
+
+
 def _scaled_lists(db: Conn, k, m, kind, metric_builder, scaled=True):
     """-> (paths, idx): every analysed song's k nearest other songs, raw or locally scaled"""
     metric, mm = playlist._scaled_metric(metric_builder, "a per-song search")  # refused before the database is read

@@ -1055,6 +1055,125 @@ def ward_tree(songs_or_X, metric_builder=euclidean_distance) -> WardTree:
     return WardTree(u.astype(np.int64), v.astype(np.int64), cost, size.astype(np.int64), rnd.astype(np.int64), int(rounds.value), n)
 
 
+# ---- k-medoids: K songs that summarise a library, under any metric (blissgpu_kmedoids / blissgpu_pam_scan) ----
+def _pam_metric(metric_builder):
+    """the metrics k-medoids can run: every one the all-pairs kernel knows -- euclidean, cosine, Mahalanobis with the caller's M"""
+    _no_forest(metric_builder, "k-medoids compares single songs; a forest scores songs against a seed set")
+    _no_variance(metric_builder, "k-medoids has no seed set to take variances from; pass MahalanobisBuilder(m)")
+    return _metric_of(metric_builder)
+
+
+def _pam_m(m):
+    if m is None:
+        return None, None
+    m = np.ascontiguousarray(m, dtype=np.float32)
+    return m, m.ctypes.data
+
+
+def pam_scan(songs_or_X, near, d1, d2, k, metric_builder=euclidean_distance, rows=None, return_sums=False):
+    """One scan of k-medoids (blissgpu_pam_scan): under the state near int [n] (every song's medoid slot, < k), d1 / d2 float32 [n]
+    (its distances to the nearest and the second nearest medoid), what would the total distance change by if song c became a
+    medoid?  For every candidate c of `rows` (None: every song; any order, repeats allowed): btot float64 -- c joins and every
+    medoid stays --, best float64 and arg int64 -- c takes the place of the medoid in slot arg, the best slot for it.
+    return_sums: also A and B float64 [q, k], the two sums per (candidate, slot) that best is made of.  -> (btot, best, arg) or
+    (btot, best, arg, A, B).  Every bit is defined by include/blissgpu.h.  A NaN distance raises BlissGpuError(ERR_NAN)."""
+    metric, m = _pam_metric(metric_builder)
+    X = _rows_of_input(songs_or_X)
+    n, d = X.shape
+    k = int(k)
+    near = _index_array(near, "near")
+    d1 = np.ascontiguousarray(d1, dtype=np.float32).reshape(-1)
+    d2 = np.ascontiguousarray(d2, dtype=np.float32).reshape(-1)
+    if not (near.shape[0] == d1.shape[0] == d2.shape[0] == n):
+        raise ValueError("near, d1 and d2 hold one entry per row")
+    rp, q = None, n
+    if rows is not None:
+        rows = _index_array(rows, "rows")
+        rp, q = rows.ctypes.data, rows.shape[0]
+    m, mp = _pam_m(m)
+    btot, best, arg = np.zeros(q, np.float64), np.zeros(q, np.float64), np.zeros(q, np.uint32)
+    A = np.zeros((q, k), np.float64) if return_sums else None
+    B = np.zeros((q, k), np.float64) if return_sums else None
+    _ffi.check(_ffi.lib().blissgpu_pam_scan(X.ctypes.data, n, d, near.ctypes.data, d1.ctypes.data, d2.ctypes.data, k, _METRICS[metric], mp,
+                                            rp, q, btot.ctypes.data, best.ctypes.data, arg.ctypes.data,
+                                            A.ctypes.data if return_sums else None, B.ctypes.data if return_sums else None))
+    out = (btot, best, arg.astype(np.int64))
+    return out + (A, B) if return_sums else out
+
+
+@dataclasses.dataclass
+class Medoids:
+    """The result of kmedoids: medoids int64 [k] (songs, in slot order), labels int64 [n] (every song's slot: its nearest
+    medoid, equal distances to the lower slot), dist float32 [n] (the distance to it), sizes int64 [k], td (the total distance
+    float64 = td_trace[-1]), td_trace float64 [n_swaps + 1] (TD before every round), n_swaps, converged."""
+
+    medoids: np.ndarray
+    labels: np.ndarray
+    dist: np.ndarray
+    sizes: np.ndarray
+    td: float
+    td_trace: np.ndarray
+    n_swaps: int
+    converged: bool
+
+    def members(self, c) -> np.ndarray:
+        """the songs of slot c, nearest to the medoid first (equal distances in song order)"""
+        idx = np.flatnonzero(self.labels == c)
+        return idx[np.argsort(self.dist[idx], kind="stable")]
+
+
+def kmedoids(songs_or_X, k, metric_builder=euclidean_distance, init="build", max_swaps=None) -> Medoids:
+    """k-medoids (PAM) of the songs (or rows of an array) on the device (blissgpu_kmedoids): the k SONGS whose
+    total distance TD = sum over the songs of the distance to the nearest of them is a local minimum under single swaps.  It
+    needs only pairwise distances, so cosine_distance and a MahalanobisBuilder work as euclidean_distance does.  init: "build"
+    (the greedy start: the song with the smallest sum of distances, then k - 1 times the song that lowers TD most) or k distinct
+    row indices.  Each round scans every (candidate, song) pair and makes the one swap that lowers TD most; it ends when no swap
+    lowers it (converged) or after max_swaps swaps (None: 4 k + 64).  Every bit is defined by include/blissgpu.h.  A
+    ForestOptions, a VarianceWeights and arbitrary callables are refused.  A NaN distance (a zero row under cosine) raises
+    BlissGpuError(ERR_NAN)."""
+    metric, m = _pam_metric(metric_builder)
+    X = _rows_of_input(songs_or_X)
+    n, d = X.shape
+    k = int(k)
+    if not 1 <= k <= max(n, 1):
+        raise ValueError("k must be 1 .. the number of rows")
+    ip = None
+    if not (isinstance(init, str) and init == "build"):
+        if isinstance(init, str):
+            raise ValueError('init must be "build" or k row indices')
+        init = _index_array(init, "init")
+        if init.shape[0] != k:
+            raise ValueError("init must hold k row indices")
+        ip = init.ctypes.data
+    max_swaps = 4 * k + 64 if max_swaps is None else int(max_swaps)
+    if max_swaps < 0:
+        raise ValueError("max_swaps must be at least 0")
+    m, mp = _pam_m(m)
+    med, sizes, labels = np.zeros(k, np.uint32), np.zeros(k, np.uint32), np.zeros(n, np.uint32)
+    dist, trace = np.zeros(n, np.float32), np.zeros(max_swaps + 1, np.float64)
+    swaps, conv = C.c_uint32(0), C.c_int32(0)
+    _ffi.check(_ffi.lib().blissgpu_kmedoids(X.ctypes.data, n, d, k, _METRICS[metric], mp, ip, max_swaps, med.ctypes.data, labels.ctypes.data,
+                                            dist.ctypes.data, sizes.ctypes.data, trace.ctypes.data, C.byref(swaps), C.byref(conv)))
+    trace = trace[: int(swaps.value) + 1] if n else trace[:0]
+    return Medoids(med.astype(np.int64), labels.astype(np.int64), dist, sizes.astype(np.int64), float(trace[-1]) if n else 0.0, trace,
+                   int(swaps.value), bool(conv.value))
+
+
+def medoid_songs(songs, k, metric_builder=euclidean_distance, init="build", max_swaps=None, return_medoids=False):
+    """The k songs that summarise `songs` (kmedoids), and what each stands for.  -> (representatives, clusters): k `Song`s, and
+    per representative the list of the songs nearest to it, nearest first (the representative itself leads its list, unless a
+    duplicate of it comes earlier).  The representatives can seed playlist_from, radio_playlist or group_playlists as they are.
+    return_medoids: -> (representatives, clusters, Medoids)."""
+    _pam_metric(metric_builder)
+    songs = list(songs)
+    if not songs:
+        raise ValueError("medoid_songs needs at least one song")
+    res = kmedoids(_matrix(songs), k, metric_builder, init, max_swaps)
+    reps = [songs[int(i)] for i in res.medoids]
+    clusters = [[songs[int(i)] for i in res.members(c)] for c in range(len(res.medoids))]
+    return (reps, clusters, res) if return_medoids else (reps, clusters)
+
+
 # ---- locally scaled nearest songs and hubness (blissgpu_scaled_knn / blissgpu_knn_occurrence, DESIGN.md 3.27) ----
 SCALE_MIN, SCALE_MAX = np.float32(2.0 ** -60), np.float32(2.0 ** 60)  # the scales blissgpu_scaled_knn accepts
 

@@ -665,6 +665,76 @@ int blissgpu_ward_nearest(const float *c, const uint32_t *size, uint64_t m, uint
 int blissgpu_ward(const float *x, uint64_t n, uint32_t d, int metric, const float *M, uint32_t *edge_u, uint32_t *edge_v,
                   float *edge_cost, uint32_t *edge_size, uint32_t *edge_round, uint32_t *rounds);
 
+/* ---- k-medoids (PAM) of a library: K songs that stand for it, under any metric ----
+ * k-means, the spanning tree and Ward answer with centroids or tree nodes and refuse the cosine; k-medoids answers with SONGS
+ * -- "the 12 songs that summarise this collection" -- and needs only pairwise distances, so every metric of blissgpu_pairwise
+ * works.  One objective, TD = the sum over the songs of the distance to the nearest medoid; each round makes the single swap
+ * (a medoid out, a non-medoid in) that lowers TD most, found by one all-pairs scan on the device.  O(n + slab k) memory, no
+ * n x n matrix.
+ * DISTANCE.  dist(i, j) = bit for bit what blissgpu_pairwise_device(x, x) writes at [i][j] (the same bits at [j][i]); metric:
+ * BLISSGPU_METRIC_EUCLIDEAN, BLISSGPU_METRIC_COSINE, or BLISSGPU_METRIC_MAHALANOBIS with the caller's M (a diagonal M is
+ * detected as everywhere else).  A NaN among the evaluated distances returns BLISSGPU_ERR_NAN (under the cosine a zero row
+ * gives one); the outputs are then unspecified.  Nothing is special-cased for a song's distance to itself: under the cosine it
+ * need not be +0.
+ * STATE.  med [k]: k distinct songs in slot order.  For every song o, idx / dist = what blissgpu_knn returns for the queries
+ * x, the candidates x[med[0]], ..., x[med[k - 1]] and min(k, 2) neighbours (equal distances go to the lower slot):
+ *   near[o] = idx[0],  d1[o] = dist[0],  d2[o] = dist[1], or +inf when k == 1;
+ *   TD = 0.0 + (double)d1[0] + (double)d1[1] + ... + (double)d1[n - 1], one sequential f64 sum in ascending o.
+ * ONE SCAN (blissgpu_pam_scan).  Inputs: x [n][d] f32; near [n] u32 (every entry < k), d1, d2 [n] f32 -- any values the caller
+ * likes, they need not be a state of any medoids; a NaN in d1 or d2 is refused --; k; rows [q] u32 (every entry < n; any order,
+ * repeats allowed), or NULL for every song (q is then ignored and taken as n).  For candidate c = rows[p] and slot m < k, over
+ * the songs o with near[o] == m in ascending o, with doc = dist(c, o), every operation rounded on its own and nothing fused:
+ *   A(c, m)     = 0.0 + sum of ((double)fminf(doc, d2[o]) - (double)d1[o])      (f32 minimum, two conversions, f64 difference)
+ *   B(c, m)     = 0.0 + sum of fmin((double)doc - (double)d1[o], 0.0)           (f64 difference, f64 minimum)
+ *   btot(c)     = 0.0 + B(c, 0) + B(c, 1) + ... + B(c, k - 1)                   (ascending m)
+ *   delta(c, m) = (btot(c) - B(c, m)) + A(c, m)
+ *   best(c), arg(c): start from delta(c, 0) and m = 0; for m = 1, 2, ... a delta(c, m) < best(c) replaces both (a strict
+ *                    f64 <: equal values stay with the lower m, a NaN never replaces).
+ * A slot without songs has A = B = 0.0.  A(c, m) is the change of TD when slot m's medoid leaves and c joins, B(c, m) the change
+ * among slot m's songs when c joins and every medoid stays, so btot(c) is what adding c as a (k + 1)-th medoid would change and
+ * delta(c, m) what swapping c into slot m would.  A candidate that is a medoid already is evaluated like any other.
+ * Outputs, entry p for rows[p]: btot [q] f64, best [q] f64, arg [q] u32; A, B [q][k] f64 (either may be NULL).  No output bit
+ * depends on the scan's column groups, on how the rows are cut into slabs to fit the workspace, or on the order of rows.
+ * n == 0 or q == 0: BLISSGPU_OK, nothing is touched.
+ * THE CLUSTERING (blissgpu_kmedoids).  init == NULL: the start is BUILD --
+ *   slot 0 = the c with the smallest A(c, 0) of a scan with k = 1 under near[o] = 0, d1[o] = 0, d2[o] = +inf (the smallest
+ *   sum of distances); slot j = 1, ..., k - 1 = the c that is not yet a medoid with the smallest btot(c) of a scan under the
+ *   state of slots 0 .. j - 1; values are compared as f64 (-0.0 == +0.0), equal values go to the lower c, a NaN is never taken
+ * -- otherwise init [k] u32, distinct songs < n.  Then rounds t = 0, 1, ...:
+ *   1. take the state of med;  2. td_trace[t] = TD;  3. scan every c that is not a medoid;  4. take the smallest
+ *   (best(c), c), compared as under BUILD;  5. if there is none, or its best(c) is not < 0, stop with converged = 1;
+ *   6. if t == max_swaps, stop with converged = 0;  7. med[arg(c)] = c.
+ * Outputs: medoids [k] u32 = med; labels [n] u32 = near and dist [n] f32 = d1 of the last state taken (dist may be NULL), so
+ * the labels are always the nearest-medoid labels of the medoids returned; sizes [k] u32 (may be NULL) = the songs per slot;
+ * td_trace f64, room for max_swaps + 1 entries, n_swaps + 1 of them written; n_swaps and converged (host memory).
+ * 1 <= d <= 64, 1 <= k <= n, k <= BLISSGPU_KMEANS_MAX_K, n < 2^32 - 1; n == 0 is BLISSGPU_OK (*n_swaps = 0, *converged = 1)
+ * and touches no device.  BLISSGPU_ERR_INVALID, before the device is touched and each with a message that names the argument:
+ * an unknown metric; Mahalanobis without M; d, k, n or q outside those limits; a NULL x, near, d1, d2, btot, best, arg,
+ * medoids, labels, td_trace, n_swaps or converged; a near entry >= k; a NaN in d1 or d2; a rows entry >= n; an init entry >= n
+ * or one that occurs twice.
+ * Workspace, grow-only in the context: O(n) -- the slots' sort, near, d1, d2, the medoids and their rows, the state's search,
+ * about 48 n + 4 k d bytes and the sort's histograms -- and 16 k bytes per candidate of a slab for A and B.  The slab is every
+ * candidate when that fits the context's workspace limit (blissgpu_ctx_get_workspace_limit); beyond it the slab shrinks; when
+ * the O(n) part and ONE candidate's share do not fit, the call returns BLISSGPU_ERR_OOM before anything is launched.  (The
+ * state's search keeps its partial lists in the k-nearest search's own buffer.)  Per round the host receives one record of 32
+ * bytes -- the winner, its slot, its delta, TD, the NaN word -- with one synchronisation, and sends nothing but the swap.
+ * For the tests and the bench tool, read from the environment at every call, and without effect on any bit of the result:
+ * BLISSGPU_PAM_COL_GROUPS = the scan's column groups (default: the plan's; at most k are used), BLISSGPU_PAM_TRACE prints every
+ * round's TD, winner, delta and milliseconds to stderr.
+ * Both are host-pointer forms over the context of the default device; there is no device-pointer form. */
+int blissgpu_pam_scan(const float *x, uint64_t n, uint32_t d, const uint32_t *near, const float *d1, const float *d2, uint32_t k,
+                      int metric, const float *M, const uint32_t *rows, uint64_t q, double *btot, double *best, uint32_t *arg,
+                      double *A, double *B); /* one scan: what a round computes */
+int blissgpu_kmedoids(const float *x, uint64_t n, uint32_t d, uint32_t k, int metric, const float *M, const uint32_t *init,
+                      uint32_t max_swaps, uint32_t *medoids, uint32_t *labels, float *dist, uint32_t *sizes, double *td_trace,
+                      uint32_t *n_swaps, int32_t *converged);
+/* The workspace of a call with these sizes under the limit ws_limit, without a device: plan [4] u64 = the bytes, the slab (the
+ * candidates scanned at a time; q of them when everything fits), and the words and scan totals reserved for the sort of the
+ * slots.  build != 0: blissgpu_kmedoids with init == NULL, which sorts every number of slots from 1 to k and reserves for the
+ * largest of them (the sort's table is not monotone in the slots); build == 0: a scan, or a clustering from a given start.  q
+ * is the number of candidates (n for a clustering).  BLISSGPU_ERR_OOM exactly when the call itself would return it. */
+int blissgpu_pam_plan(uint64_t n, uint32_t d, uint32_t k, uint64_t q, int build, uint64_t ws_limit, uint64_t *plan);
+
 /* ---- Learning the Mahalanobis matrix from training triplets ----
  * The reference has a `training_triplet` table ("song_1 and song_2 are closer together than they are to odd_one_out",
  * src/library.rs:542-556), a TODO.md that asks for "a way to learn a metric with a user survey", and no code that learns.
