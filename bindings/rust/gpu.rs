@@ -281,6 +281,11 @@ pub mod sys {
         pub fn blissgpu_analyze_batch_flac_verified(files: *mut *const c_void, nbytes: *const u64, n_songs: u32, features_version: u32, checks: u32, out: *mut f32, status: *mut i32, flags: *mut u32, first_bad_frame: *mut u32) -> c_int;
         pub fn blissgpu_flac_crc16_device(ctx: *mut blissgpu_ctx, d_bytes: *const c_void, nbytes: u64, frames: *const u64, n_frames: u64, d_frame_status: *const i32, d_frame_end: *const u64, d_frame_crc_ok: *mut i32) -> c_int;
         pub fn blissgpu_flac_md5_device(ctx: *mut blissgpu_ctx, d_pcm: *const c_void, info: *const u64, d_md5: *mut c_void) -> c_int;
+        // acoustic fingerprints (Haitsma & Kalker) and their match over candidate pairs
+        pub fn blissgpu_fingerprint_len(n_samples: u64) -> u64;
+        pub fn blissgpu_fingerprint_bands(edges: *mut u32) -> c_int;
+        pub fn blissgpu_fingerprint_batch(pcm: *const f32, sample_offsets: *const u64, word_offsets: *const u64, n_songs: u32, words: *mut u32, status: *mut i32, energies: *mut f64) -> c_int;
+        pub fn blissgpu_fingerprint_match(words: *const u32, word_offsets: *const u64, n_songs: u32, pairs: *const u32, n_pairs: u64, max_offset: u32, min_overlap: u32, offset: *mut i32, errors: *mut u32, bits: *mut u32) -> c_int;
         pub fn blissgpu_last_error() -> *const c_char;
         pub fn blissgpu_version() -> *const c_char;
     }

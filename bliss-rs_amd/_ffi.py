@@ -141,6 +141,10 @@ SIGNATURES = {
     "blissgpu_kmedoids": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _vp]),
     "blissgpu_pam_plan": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_uint64, _vp]),
+    "blissgpu_fingerprint_len": (C.c_uint64, [C.c_uint64]),
+    "blissgpu_fingerprint_bands": (C.c_int, [_u32p]),
+    "blissgpu_fingerprint_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "blissgpu_fingerprint_match": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "blissgpu_moments": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "blissgpu_moments_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "blissgpu_covariance_metric": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_int, C.c_double, _vp, _i32p]),

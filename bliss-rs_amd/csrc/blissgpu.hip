@@ -50,6 +50,8 @@ const char kMapUpdateName[] = "map_update_kernel";
 const char kWardScanName[] = "ward_scan_kernel", kWardJoinName[] = "ward_join_kernel";  // KX_WARD_*
 const char kPamScanName[] = "pam_scan_kernel", kPamFoldName[] = "pam_fold_kernel", kPamPickName[] = "pam_pick_kernel";  // KX_PAM_*
 const char kPamGatherName[] = "pam_gather_kernel", kPamStateName[] = "pam_state_kernel", kPamTdName[] = "pam_td_kernel";
+const char kFpBandsName[] = "fp_bands_kernel", kFpBitsName[] = "fp_bits_kernel";  // KX_FP_*
+const char kFpMatchName[] = "fp_match_kernel", kFpPickName[] = "fp_pick_kernel";
 const char* const kKernelNames[K_COUNT] = {
     "fft512_kernel",     "onset_kernel",      "beat_kernel",   "stft8192_kernel", "tune_select_kernel",
     "tune_pass2_kernel", "tune_final_kernel", "chroma_kernel",     "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel", "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel",
@@ -70,6 +72,7 @@ const char* const kKernelNames[K_COUNT] = {
     kMapRepulseName, kMapAttractName, kMapUpdateName,
     kWardScanName, kWardJoinName,
     kPamScanName, kPamFoldName, kPamPickName, kPamGatherName, kPamStateName, kPamTdName,
+    kFpBandsName, kFpBitsName, kFpMatchName, kFpPickName,
     kGroupForestScanName, kJourneyStepName};
 }  // namespace
 
@@ -395,7 +398,7 @@ int blissgpu_ctx_destroy(blissgpu_ctx* c) {
         (void)hipFree(c->bt_rwv); (void)hipFree(c->bt_dfwv); (void)hipFree(c->chroma_bank);
         scheduler_release(c);
         c->dbg_tuning.release(); c->dbg_nbpms.release(); c->dbg_chroma.release(); c->dbg_interval.release();
-        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->km_ws.release(); c->sil_ws.release(); c->mo_ws.release(); c->ch_ws.release(); c->ms_ws.release(); c->wd_ws.release(); c->wd_host.release(); c->pam_ws.release(); c->map_ws.release(); c->mt_ws.release(); c->pl_next.release(); c->st_idx.release();
+        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->km_ws.release(); c->sil_ws.release(); c->mo_ws.release(); c->ch_ws.release(); c->ms_ws.release(); c->wd_ws.release(); c->wd_host.release(); c->pam_ws.release(); c->fp_ws.release(); c->map_ws.release(); c->mt_ws.release(); c->pl_next.release(); c->st_idx.release();
         c->st_a.release(); c->st_b.release(); c->st_m.release(); c->st_dist.release(); c->st_out.release();
         c->fl_bytes.release(); c->fl_tab.release(); c->fl_pcm.release(); c->fl_status.release(); c->fl_end.release();
         c->fl_bad.release(); c->fl_mono.release(); c->fl_rows.release(); c->fl_htab.release();
@@ -2305,6 +2308,181 @@ int blissgpu_pam_plan(uint64_t n, uint32_t d, uint32_t k, uint64_t q, int build,
     plan[3] = L.tiles_cap;
     if (L.slab == 0) return fail(BLISSGPU_ERR_OOM, who, "the state and one candidate's sums do not fit the workspace limit");
     return BLISSGPU_OK;
+}
+
+// ---- acoustic fingerprints (kernels_fingerprint.hip): the band energies of every frame and the words from
+// them, a group of songs at a time; and the alignment search over candidate pairs ----
+uint64_t blissgpu_fingerprint_len(uint64_t n_samples) {
+    return n_samples < (uint64_t)(FP_FRAME + FP_HOP) ? 0 : (n_samples - FP_FRAME) / FP_HOP;
+}
+
+int blissgpu_fingerprint_bands(uint32_t* edges) {
+    static const uint32_t kEdges[FP_BANDS + 1] = {FP_EDGE_LIST};
+    if (!edges) return fail(BLISSGPU_ERR_INVALID, "blissgpu_fingerprint_bands", "edges is NULL");
+    memcpy(edges, kEdges, sizeof(kEdges));
+    return BLISSGPU_OK;
+}
+
+static size_t fp_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+static int fp_launched(const char* who) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? BLISSGPU_OK : fail(BLISSGPU_ERR_HIP, who, hipGetErrorString(e));
+}
+
+int blissgpu_fingerprint_batch(const float* pcm, const uint64_t* sample_offsets, const uint64_t* word_offsets, uint32_t n_songs,
+                               uint32_t* words, int32_t* status, double* energies) {
+    const char* who = "blissgpu_fingerprint_batch";
+    if (n_songs == 0) return BLISSGPU_OK;
+    if (!sample_offsets) return fail(BLISSGPU_ERR_INVALID, who, "sample_offsets is NULL");
+    if (!word_offsets) return fail(BLISSGPU_ERR_INVALID, who, "word_offsets is NULL");
+    if (!status) return fail(BLISSGPU_ERR_INVALID, who, "status is NULL");
+    if (word_offsets[0] != 0) return fail(BLISSGPU_ERR_INVALID, who, "word_offsets[0] must be 0");
+    for (uint32_t s = 0; s < n_songs; s++) {
+        if (sample_offsets[s + 1] < sample_offsets[s]) return fail(BLISSGPU_ERR_INVALID, who, "sample_offsets must ascend");
+        const uint64_t w = blissgpu_fingerprint_len(sample_offsets[s + 1] - sample_offsets[s]);
+        if (w > FP_MAX_WORDS) return fail(BLISSGPU_ERR_INVALID, who, "a song has more than 2^22 words");
+        if (word_offsets[s + 1] < word_offsets[s] || word_offsets[s + 1] - word_offsets[s] != w)
+            return fail(BLISSGPU_ERR_INVALID, who, "word_offsets[s + 1] - word_offsets[s] must be blissgpu_fingerprint_len of song s");
+    }
+    if (sample_offsets[n_songs] > sample_offsets[0] && !pcm) return fail(BLISSGPU_ERR_INVALID, who, "pcm is NULL");
+    if (word_offsets[n_songs] && !words) return fail(BLISSGPU_ERR_INVALID, who, "words is NULL");
+    for (uint32_t s = 0; s < n_songs; s++) status[s] = word_offsets[s + 1] == word_offsets[s] ? BLISSGPU_SONG_TOO_SHORT : BLISSGPU_SONG_OK;
+    // a too-short song owns one row of the energies, all zero
+    auto zero_short_rows = [&](uint32_t s0, uint32_t s1) {
+        if (!energies) return;
+        for (uint32_t s = s0; s < s1; s++)
+            if (status[s] != BLISSGPU_SONG_OK) memset(energies + (word_offsets[s] + s) * FP_BANDS, 0, FP_BANDS * sizeof(double));
+    };
+    if (word_offsets[n_songs] == 0) {  // nothing for a device to do
+        zero_short_rows(0, n_songs);
+        return BLISSGPU_OK;
+    }
+    blissgpu_ctx* c;
+    int rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    // the songs go through the device in groups of consecutive songs: at most 1 GiB of energies and 2 GiB of PCM (and a
+    // quarter and a half of the workspace limit), one song at the least
+    const uint64_t row_bytes = FP_BANDS * sizeof(double);
+    const uint64_t e_budget = std::min<uint64_t>(1ull << 30, c->ws_limit / 4), pcm_budget = std::min<uint64_t>(2ull << 30, c->ws_limit / 2);
+    std::vector<FpSong> desc;
+    std::vector<uint32_t> run_pfx, word_pfx;
+    for (uint32_t g0 = 0; g0 < n_songs;) {
+        uint32_t g1 = g0;
+        uint64_t rows = 0, samples = 0;
+        while (g1 < n_songs) {
+            const uint64_t r = word_offsets[g1 + 1] - word_offsets[g1] + 1, sm = sample_offsets[g1 + 1] - sample_offsets[g1];
+            if (g1 > g0 && ((rows + r) * row_bytes > e_budget || (samples + sm) * sizeof(float) > pcm_budget)) break;
+            rows += r;
+            samples += sm;
+            g1++;
+        }
+        const uint32_t ng = g1 - g0;
+        const uint64_t gw = word_offsets[g1] - word_offsets[g0];
+        if (gw == 0) {
+            zero_short_rows(g0, g1);
+            g0 = g1;
+            continue;
+        }
+        desc.resize(ng);
+        run_pfx.assign(ng + 1, 0);
+        word_pfx.assign(ng + 1, 0);
+        for (uint32_t k = 0; k < ng; k++) {
+            const uint32_t w = (uint32_t)(word_offsets[g0 + k + 1] - word_offsets[g0 + k]), frames = w ? w + 1 : 0;
+            desc[k] = FpSong{sample_offsets[g0 + k] - sample_offsets[g0], frames, word_pfx[k] + k};
+            run_pfx[k + 1] = run_pfx[k] + (frames + FP_RUN - 1) / FP_RUN;
+            word_pfx[k + 1] = word_pfx[k] + w;
+        }
+        const size_t o_pcm = 0, o_e = o_pcm + fp_align(samples * sizeof(float)), o_words = o_e + fp_align(rows * row_bytes),
+                     o_desc = o_words + fp_align(gw * sizeof(uint32_t)), o_run = o_desc + fp_align(ng * sizeof(FpSong)),
+                     o_wpfx = o_run + fp_align((ng + 1) * sizeof(uint32_t)), total = o_wpfx + fp_align((ng + 1) * sizeof(uint32_t));
+        if ((rc = c->fp_ws.ensure(total))) return rc;
+        uint8_t* base = c->fp_ws.p;
+        float* d_pcm = reinterpret_cast<float*>(base + o_pcm);
+        double* d_e = reinterpret_cast<double*>(base + o_e);
+        uint32_t* d_words = reinterpret_cast<uint32_t*>(base + o_words);
+        FpSong* d_desc = reinterpret_cast<FpSong*>(base + o_desc);
+        uint32_t *d_run = reinterpret_cast<uint32_t*>(base + o_run), *d_wpfx = reinterpret_cast<uint32_t*>(base + o_wpfx);
+        HostStage s{c, "fingerprint"};
+        s.up(d_pcm, pcm + sample_offsets[g0], samples * sizeof(float));
+        s.up(d_desc, desc.data(), ng * sizeof(FpSong));
+        s.up(d_run, run_pfx.data(), (ng + 1) * sizeof(uint32_t));
+        s.up(d_wpfx, word_pfx.data(), (ng + 1) * sizeof(uint32_t));
+        rc = s.uploaded();
+        if (!rc) {
+            { Prof p(c, KX_FP_BANDS); launch_fp_bands(d_pcm, d_desc, ng, d_run, run_pfx[ng], c->tables.hann8192, c->tables.tw8192, d_e, c->stream); }
+            rc = fp_launched(who);
+        }
+        if (!rc) {
+            { Prof p(c, KX_FP_BITS); launch_fp_bits(d_e, d_wpfx, ng, (uint32_t)gw, d_words, c->stream); }
+            rc = fp_launched(who);
+        }
+        if (!rc) {
+            s.down(words + word_offsets[g0], d_words, gw * sizeof(uint32_t));
+            if (energies) s.down(energies + (word_offsets[g0] + g0) * FP_BANDS, d_e, rows * row_bytes);
+        }
+        if ((rc = s.finish(rc))) return rc;
+        zero_short_rows(g0, g1);
+        g0 = g1;
+    }
+    return BLISSGPU_OK;
+}
+
+int blissgpu_fingerprint_match(const uint32_t* words, const uint64_t* word_offsets, uint32_t n_songs, const uint32_t* pairs, uint64_t n_pairs,
+                               uint32_t max_offset, uint32_t min_overlap, int32_t* offset, uint32_t* errors, uint32_t* bits) {
+    const char* who = "blissgpu_fingerprint_match";
+    if (max_offset > FP_MAX_OFFSET) return fail(BLISSGPU_ERR_INVALID, who, "max_offset must be <= 4096");
+    if (min_overlap == 0) return fail(BLISSGPU_ERR_INVALID, who, "min_overlap must be >= 1");
+    if (n_pairs == 0) return BLISSGPU_OK;
+    if (n_pairs >= (1ull << 32)) return fail(BLISSGPU_ERR_INVALID, who, "n_pairs must be below 2^32");
+    if (!word_offsets) return fail(BLISSGPU_ERR_INVALID, who, "word_offsets is NULL");
+    if (!pairs) return fail(BLISSGPU_ERR_INVALID, who, "pairs is NULL");
+    if (!offset || !errors || !bits) return fail(BLISSGPU_ERR_INVALID, who, "offset, errors or bits is NULL");
+    for (uint32_t s = 0; s < n_songs; s++) {
+        if (word_offsets[s + 1] < word_offsets[s]) return fail(BLISSGPU_ERR_INVALID, who, "word_offsets must ascend");
+        if (word_offsets[s + 1] - word_offsets[s] > FP_MAX_WORDS) return fail(BLISSGPU_ERR_INVALID, who, "a song has more than 2^22 words");
+    }
+    for (uint64_t p = 0; p < 2 * n_pairs; p++) {
+        if (pairs[p] >= n_songs) return fail(BLISSGPU_ERR_INVALID, who, "a pair names a song >= n_songs");
+        if (word_offsets[pairs[p] + 1] == word_offsets[pairs[p]]) return fail(BLISSGPU_ERR_INVALID, who, "a pair names a song without words");
+    }
+    if (!words) return fail(BLISSGPU_ERR_INVALID, who, "words is NULL");
+    blissgpu_ctx* c;
+    int rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    const uint64_t n_words = word_offsets[n_songs];
+    const uint32_t n_blocks = (2 * max_offset + 1 + 255) / 256;
+    const uint64_t batch = std::min<uint64_t>(n_pairs, 65536);  // pairs per launch: the candidates of a batch are 16 n_blocks bytes a pair
+    const size_t o_words = 0, o_off = o_words + fp_align(n_words * sizeof(uint32_t)), o_pairs = o_off + fp_align((n_songs + 1ull) * sizeof(uint64_t)),
+                 o_out = o_pairs + fp_align(2 * n_pairs * sizeof(uint32_t)), o_cand = o_out + fp_align(3 * n_pairs * sizeof(uint32_t)),
+                 total = o_cand + fp_align(batch * n_blocks * sizeof(FpCand));
+    if ((rc = c->fp_ws.ensure(total))) return rc;
+    uint8_t* base = c->fp_ws.p;
+    uint32_t* d_words = reinterpret_cast<uint32_t*>(base + o_words);
+    uint64_t* d_off = reinterpret_cast<uint64_t*>(base + o_off);
+    uint32_t* d_pairs = reinterpret_cast<uint32_t*>(base + o_pairs);
+    uint32_t* d_out = reinterpret_cast<uint32_t*>(base + o_out);  // offset | errors | bits, n_pairs each
+    FpCand* d_cand = reinterpret_cast<FpCand*>(base + o_cand);
+    HostStage s{c, "fingerprint_match"};
+    s.up(d_words, words, n_words * sizeof(uint32_t));
+    s.up(d_off, word_offsets, (n_songs + 1ull) * sizeof(uint64_t));
+    s.up(d_pairs, pairs, 2 * n_pairs * sizeof(uint32_t));
+    rc = s.uploaded();
+    for (uint64_t p0 = 0; !rc && p0 < n_pairs; p0 += batch) {
+        const uint32_t np = (uint32_t)std::min<uint64_t>(batch, n_pairs - p0);
+        { Prof p(c, KX_FP_MATCH); launch_fp_match(d_words, d_off, n_songs, d_pairs + 2 * p0, np, n_blocks, (int)max_offset, min_overlap, d_cand, c->stream); }
+        rc = fp_launched(who);
+        if (rc) break;
+        { Prof p(c, KX_FP_PICK); launch_fp_pick(d_cand, np, n_blocks, reinterpret_cast<int32_t*>(d_out) + p0, d_out + n_pairs + p0, d_out + 2 * n_pairs + p0, c->stream); }
+        rc = fp_launched(who);
+    }
+    if (!rc) {
+        s.down(offset, d_out, n_pairs * sizeof(uint32_t));
+        s.down(errors, d_out + n_pairs, n_pairs * sizeof(uint32_t));
+        s.down(bits, d_out + 2 * n_pairs, n_pairs * sizeof(uint32_t));
+    }
+    return s.finish(rc);
 }
 
 // ---- the moments of a library: counts, means, squared deviations and extrema per group of a labelling, and the pooled scatter

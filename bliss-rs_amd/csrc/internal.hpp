@@ -123,7 +123,7 @@ enum KernelId : int {
     K_CHAIN_STEP, K_CHAIN_WALK,             // song-to-song chains cut after k (kernels_chains.hip)
     // (tests/test_chains_host.py holds this list, and the list of names beside it, to end in the chain kernels: the kernels
     // that came later are numbered behind it, so that no older id or name moves)
-    K_COUNT = K_CHAIN_WALK + 41
+    K_COUNT = K_CHAIN_WALK + 45
 };
 // k-nearest albums per seed group (kernels_albums.hip; its partial lists are merged by knn_merge_kernel)
 constexpr int KX_SEGMENT_MEAN = K_CHAIN_WALK + 1, KX_ALBUM_KNN_SCAN = K_CHAIN_WALK + 2;
@@ -153,12 +153,15 @@ constexpr int KX_WARD_SCAN = K_CHAIN_WALK + 31, KX_WARD_JOIN = K_CHAIN_WALK + 32
 // k-medoids (kernels_pam.hip): the all-pairs swap scan, its fold per candidate, the round's winner, and the state's three helpers
 constexpr int KX_PAM_SCAN = K_CHAIN_WALK + 33, KX_PAM_FOLD = K_CHAIN_WALK + 34, KX_PAM_PICK = K_CHAIN_WALK + 35;
 constexpr int KX_PAM_GATHER = K_CHAIN_WALK + 36, KX_PAM_STATE = K_CHAIN_WALK + 37, KX_PAM_TD = K_CHAIN_WALK + 38;
+// acoustic fingerprints (kernels_fingerprint.hip): the frames' band energies, the words, the match per offset block, its pick
+constexpr int KX_FP_BANDS = K_CHAIN_WALK + 39, KX_FP_BITS = K_CHAIN_WALK + 40, KX_FP_MATCH = K_CHAIN_WALK + 41,
+              KX_FP_PICK = K_CHAIN_WALK + 42;
 // (tests/test_journeys_host.py holds the profile table to END in the next two names: kernels that come later are numbered in
 // front of them; every consumer of the table goes by name)
 // the k lowest forest scores per seed group (kernels_forest.hip; its partial lists are merged by group_knn_merge_kernel)
-constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 39;
+constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 43;
 // a journey's step (kernels_chains.hip: the chains' scan with a waypoint query or a gate)
-constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 40;
+constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 44;
 static_assert(KX_JOURNEY_STEP + 1 == K_COUNT, "every kernel id is below the count");
 
 // lower_bound on a prefix array: largest s with prefix[s] <= x  (prefix has n+1 entries, prefix[0]=0)
@@ -568,6 +571,35 @@ void launch_pam_gather(const float* X, uint32_t* med, uint32_t K, uint32_t d, fl
 void launch_pam_state(const uint32_t* idx, const float* dist, uint32_t n, uint32_t kk, uint32_t* near, float* d1, float* d2,
                       hipStream_t st);
 void launch_pam_td(const float* d1, uint32_t n, PamRecord* rec, hipStream_t st);
+// acoustic fingerprints (kernels_fingerprint.hip).  Frame f of a song is samples [512 f, 512 f + 8192); a workgroup of the band
+// kernel transforms a run of FP_RUN consecutive frames.  A group of songs is described by FpSong [n_songs], run_pfx [n_songs + 1]
+// (runs in front of every song) and word_pfx [n_songs + 1]; song s of the group owns the rows word_pfx[s] + s .. of E [rows][33]
+// (one row per frame = one more than its words; a too-short song owns one row that nothing writes)
+constexpr int FP_FRAME = 8192, FP_HOP = 512, FP_BANDS = 33, FP_RUN = 6;
+constexpr uint32_t FP_MAX_WORDS = 1u << 22, FP_MAX_OFFSET = 4096;
+// the 34 bin edges of the 33 bands, 300 .. 2000 Hz logarithmically: the contract is this table (include/blissgpu.h)
+#define FP_EDGE_LIST                                                                                                             \
+    111, 118, 125, 132, 140, 149, 157, 167, 177, 187, 198, 210, 222, 235, 249, 264, 280, 296, 314, 332, 352, 373, 395, 418, 443, \
+        469, 497, 526, 557, 590, 625, 662, 702, 743
+struct FpSong {
+    uint64_t pcm_off;  // first sample in the group's PCM
+    uint32_t frames;   // 0: too short
+    uint32_t row0;     // first row of E
+};
+// the best offset of one (pair, block of 256 offsets): count = valid positions (bits = 32 count); valid == 0: no offset counts
+struct FpCand {
+    uint32_t errors, count;
+    int32_t offset;
+    uint32_t valid;
+};
+void launch_fp_bands(const float* pcm, const FpSong* songs, uint32_t n_songs, const uint32_t* run_pfx, uint32_t n_runs,
+                     const float* hann, const float2* tw, double* E, hipStream_t st);
+void launch_fp_bits(const double* E, const uint32_t* word_pfx, uint32_t n_songs, uint32_t n_words, uint32_t* words, hipStream_t st);
+// pairs [n_pairs][2]; cand [n_pairs][n_blocks], n_blocks = ceil((2 max_offset + 1) / 256); n_pairs * n_blocks < 2^31
+void launch_fp_match(const uint32_t* words, const uint64_t* word_offsets, uint32_t n_songs, const uint32_t* pairs, uint32_t n_pairs,
+                     uint32_t n_blocks, int max_offset, uint32_t min_overlap, FpCand* cand, hipStream_t st);
+void launch_fp_pick(const FpCand* cand, uint32_t n_pairs, uint32_t n_blocks, int32_t* offset, uint32_t* errors, uint32_t* bits,
+                    hipStream_t st);
 // triplet metric learning, one gradient evaluation (kernels_metric.hip).  The triplets are dealt out in W contiguous chunks, a
 // function of T alone; part [W][pairs + 1] f64 and cnt [W][2] u64 are the wavefronts' partials, out = G f64 [d][d] | loss f64 |
 // n_active u64 | error bits u64 (TRIPLET_ERR_*).  mode says how M is read; flags (u8 [T]) may be NULL

@@ -44,6 +44,10 @@ database:
                                           (or one genre's) in an order in which each sounds like one before it
     song_map                              a picture of the library: a point per song on a plane where sonic neighbours are
                                           neighbours (playlist.song_map: exact t-SNE, every iteration on the device)
+    store_fingerprints, load_fingerprints,   acoustic fingerprints (bliss_rs_amd.fingerprint_batch) in a sidecar table the crate
+    fingerprint_duplicates                ignores, and the groups of songs that are the same RECORDING by them: candidates from
+                                          the k nearest songs by features and equal title and artist, one match call on the
+                                          device (playlist.fingerprint_duplicates); duplicate_songs is unchanged
 
 SQLite stores `real` as f64; an f32 feature widens exactly on the way in and narrows exactly on the way out, so a
 round trip is bit-exact.  The schema, load and store helpers are host code; the playlists run their distances on the
@@ -645,6 +649,95 @@ def duplicate_songs(db: Conn, distance_threshold: float = None, metric_builder=p
         return []
     metric, m = playlist._metric_of(metric_builder)
     labels = playlist.duplicate_labels(X, playlist.meta_keys(songs), metric, m, distance_threshold)
+    return [[songs[i] for i in g] for g in playlist.groups_from_labels(labels)]
+
+
+# ---- acoustic fingerprints: a sidecar table beside the crate's (it ignores tables it does not know) ----
+def _fingerprint_table(conn) -> None:
+    conn.execute("create table if not exists gpu_fingerprint (song_id integer primary key, version integer, words blob)")
+
+
+def store_fingerprints(db: Conn, fingerprints) -> None:
+    """Keep the fingerprints of songs of the library: {path: words} (np.uint32 arrays, as bliss_rs_amd.fingerprint_batch returns
+    them) into the sidecar table gpu_fingerprint(song_id, version, words), created on demand; the words are stored little-endian
+    with song.FINGERPRINT_VERSION beside them.  A path that is not in the library is a ProviderError; a song's earlier
+    fingerprint is replaced."""
+    from .song import FINGERPRINT_VERSION
+
+    conn, own = _connect(db)
+    try:
+        _fingerprint_table(conn)
+        for path, words in dict(fingerprints).items():
+            row = conn.execute("select id from song where path = ?", (path,)).fetchone()
+            if row is None:
+                raise ProviderError(f"song '{path}' is not in the library")
+            blob = np.ascontiguousarray(words, dtype="<u4").reshape(-1).tobytes()
+            conn.execute("insert or replace into gpu_fingerprint (song_id, version, words) values (?, ?, ?)",
+                         (int(row[0]), FINGERPRINT_VERSION, blob))
+        conn.commit()
+    finally:
+        if own:
+            conn.close()
+
+
+def load_fingerprints(db: Conn) -> dict:
+    """{path: words (np.uint32)} of every song with a stored fingerprint of song.FINGERPRINT_VERSION, in id order; a library
+    without the sidecar table has none."""
+    from .song import FINGERPRINT_VERSION
+
+    conn, own = _connect(db)
+    try:
+        if conn.execute("select count(*) from sqlite_master where type = 'table' and name = 'gpu_fingerprint'").fetchone()[0] == 0:
+            return {}
+        rows = conn.execute("select song.path, gpu_fingerprint.words from gpu_fingerprint join song on song.id = gpu_fingerprint.song_id "
+                            "where gpu_fingerprint.version = ? order by song.id", (FINGERPRINT_VERSION,)).fetchall()
+    finally:
+        if own:
+            conn.close()
+    return {p: np.frombuffer(bytes(b), dtype="<u4").astype(np.uint32) for p, b in rows}
+
+
+def fingerprint_candidate_pairs(songs, X, has_fp, k: int, metric_builder=playlist.euclidean_distance) -> np.ndarray:
+    """The pairs worth aligning, int64 [P, 2] with i < j, ascending, each once: every fingerprinted song with its k nearest songs by
+    features (one playlist.nearest_order call) and the pairs with the same `Some` title and artist (playlist.meta_keys); both
+    songs of a pair have a fingerprint."""
+    has_fp = np.asarray(has_fp, dtype=bool)
+    rows = np.flatnonzero(has_fp)
+    found = set()
+    if rows.size and int(k) >= 1 and len(songs) >= 2:
+        metric, m = playlist._metric_of(metric_builder)
+        idx, _ = playlist.nearest_order(X[rows], X, min(int(k), len(songs) - 1), metric, m, skip=rows)
+        for r, near in zip(rows.tolist(), idx.tolist()):
+            found.update((min(r, j), max(r, j)) for j in near if j >= 0 and has_fp[j])
+    by_key = {}
+    for i, key in enumerate(playlist.meta_keys(songs).tolist()):
+        if key and has_fp[i]:
+            by_key.setdefault(key, []).append(i)
+    for members in by_key.values():
+        found.update((a, b) for n, a in enumerate(members) for b in members[n + 1:])
+    return np.asarray(sorted(found), dtype=np.int64).reshape(len(found), 2)
+
+
+def fingerprint_duplicates(db: Conn, k: int = 10, threshold=playlist.FINGERPRINT_THRESHOLD, metric_builder=playlist.euclidean_distance,
+                           max_offset: int = playlist.FINGERPRINT_MAX_OFFSET, min_overlap: int = playlist.FINGERPRINT_MIN_OVERLAP) -> List[List[Song]]:
+    """Which songs of the library are the same RECORDING -- a remaster, a compilation copy with another lead-in, an MP3 beside its
+    FLAC -- by their stored fingerprints (store_fingerprints) and not by their features, which such copies do not share closely
+    enough for duplicate_songs.  Candidates are every fingerprinted song with its k nearest songs by features and the pairs with
+    the same `Some` title and artist (fingerprint_candidate_pairs); ONE match call aligns them all
+    (playlist.fingerprint_duplicates: bit error rate below `threshold`, default the paper's 0.35).  -> groups of two or more `Song`
+    shaped like duplicate_songs' (id order, groups by their first song).  Songs without a fingerprint are in no group."""
+    playlist._no_forest(metric_builder, "fingerprint_duplicates ranks its candidates by single songs")
+    playlist._no_variance(metric_builder, "fingerprint_duplicates ranks its candidates by single songs")
+    songs, X = _load_songs_and_matrix(db, FeaturesVersion.LATEST)
+    stored = load_fingerprints(db)
+    if not songs or not stored:
+        return []
+    fps = [stored.get(s.path, np.zeros(0, np.uint32)) for s in songs]
+    has_fp = np.asarray([f.size > 0 for f in fps], dtype=bool)
+    pairs = fingerprint_candidate_pairs(songs, X, has_fp, k, metric_builder)
+    if pairs.shape[0] == 0:
+        return []
+    labels = playlist.fingerprint_duplicates(fps, pairs, threshold, max_offset, min_overlap)
     return [[songs[i] for i in g] for g in playlist.groups_from_labels(labels)]
 
 

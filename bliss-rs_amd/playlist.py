@@ -2731,6 +2731,114 @@ def duplicate_groups(songs, distance_threshold=None, metric_builder=euclidean_di
     return [[songs[i] for i in g] for g in groups_from_labels(labels)]
 
 
+# ---- acoustic fingerprints: the same RECORDING, whatever the features say (blissgpu_fingerprint_match) ----
+FINGERPRINT_MAX_OFFSET = 430   # hops of 512 samples: +-10 s
+FINGERPRINT_MIN_OVERLAP = 256  # valid positions an alignment needs: 6 s
+FINGERPRINT_THRESHOLD = 0.35   # bit error rate below which two excerpts are one recording (Haitsma & Kalker 2002, section 4.3)
+FINGERPRINT_ALL_PAIRS_MAX = 4096
+
+
+def _fingerprints(fps):
+    fps = [np.ascontiguousarray(f, dtype=np.uint32).reshape(-1) for f in fps]
+    offsets = np.zeros(len(fps) + 1, np.uint64)
+    if fps:
+        offsets[1:] = np.cumsum([f.shape[0] for f in fps], dtype=np.uint64)
+    return fps, offsets
+
+
+def _pair_array(pairs, n):
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if pairs.size and (pairs.min() < 0 or pairs.max() >= n):
+        raise ValueError("pairs must index the fingerprints")
+    return pairs
+
+
+def fingerprint_match(fps, pairs, max_offset=FINGERPRINT_MAX_OFFSET, min_overlap=FINGERPRINT_MIN_OVERLAP):
+    """How well do two fingerprints (fingerprint_batch) align?  For every pair (i, j) of `pairs` and every offset o in
+    [-max_offset, max_offset], the words fps[i][t] and fps[j][t + o] that are both non-zero (a zero word is silence) are
+    compared bit by bit; an offset counts when at least min_overlap positions are compared, and the best one has the smallest
+    errors / bits (compared exactly; ties to the smaller (|o|, o)).  -> (offset int32 [P], errors uint32 [P], bits uint32 [P]);
+    bits == 0 (and offset == errors == 0) where no offset counts, as for a pair with an empty fingerprint, which never reaches
+    the device.  The defaults are +-10 s and 6 s.  One device call; the result is defined to the bit by include/blissgpu.h."""
+    fps, offsets = _fingerprints(fps)
+    pairs = _pair_array(pairs, len(fps))
+    P = pairs.shape[0]
+    offset, errors, bits = np.zeros(P, np.int32), np.zeros(P, np.uint32), np.zeros(P, np.uint32)
+    if not 0 <= int(max_offset) <= 4096:
+        raise ValueError("max_offset must be 0 .. 4096")
+    if int(min_overlap) < 1:
+        raise ValueError("min_overlap must be >= 1")
+    if P == 0:
+        return offset, errors, bits
+    lens = np.diff(offsets.astype(np.int64))
+    live = np.flatnonzero((lens[pairs[:, 0]] > 0) & (lens[pairs[:, 1]] > 0))
+    if live.size == 0:
+        return offset, errors, bits
+    words = np.concatenate(fps)
+    sent = np.ascontiguousarray(pairs[live], dtype=np.uint32)
+    o, e, b = np.zeros(live.size, np.int32), np.zeros(live.size, np.uint32), np.zeros(live.size, np.uint32)
+    _ffi.check(_ffi.lib().blissgpu_fingerprint_match(words.ctypes.data, offsets.ctypes.data, len(fps), sent.ctypes.data, live.size,
+                                                     int(max_offset), int(min_overlap), o.ctypes.data, e.ctypes.data, b.ctypes.data))
+    offset[live], errors[live], bits[live] = o, e, b
+    return offset, errors, bits
+
+
+def _threshold_fraction(threshold):
+    """threshold as an exact fraction (numerator, denominator): a float at its shortest decimal form (0.35 is 7 / 20, not the
+    binary number next to it), a Fraction or an int as it is"""
+    import fractions
+
+    f = threshold if isinstance(threshold, (fractions.Fraction, int)) else fractions.Fraction(repr(float(threshold)))
+    f = fractions.Fraction(f)
+    if f < 0:
+        raise ValueError("threshold must not be negative")
+    return f.numerator, f.denominator
+
+
+def fingerprint_edges(errors, bits, threshold=FINGERPRINT_THRESHOLD) -> np.ndarray:
+    """bool [P]: bits > 0 and errors < threshold * bits, evaluated exactly in integers (errors * den < num * bits with
+    threshold = num / den, see _threshold_fraction)."""
+    num, den = _threshold_fraction(threshold)
+    errors, bits = np.asarray(errors), np.asarray(bits)
+    if max(num, den) < 2 ** 31:  # errors, bits < 2^32: the products fit 63 bits
+        lhs, rhs = errors.astype(np.int64) * den, bits.astype(np.int64) * num
+    else:
+        lhs, rhs = errors.astype(object) * den, bits.astype(object) * num
+    return (bits > 0) & np.asarray(lhs < rhs, dtype=bool)
+
+
+def labels_from_edges(n, pairs, edge) -> np.ndarray:
+    """Connected components of the pairs whose `edge` is set, on the host (union-find): int64 [n], the smallest index of
+    every index's component -- the labels duplicate_labels returns."""
+    parent = list(range(n))
+    for (i, j), on in zip(np.asarray(pairs, dtype=np.int64).reshape(-1, 2).tolist(), np.asarray(edge, dtype=bool).tolist()):
+        if on:
+            a, b = _uf_find(parent, i), _uf_find(parent, j)
+            if a != b:
+                parent[max(a, b)] = min(a, b)  # the root is always the component's smallest index
+    return np.asarray([_uf_find(parent, i) for i in range(n)], dtype=np.int64)
+
+
+def fingerprint_duplicates(fps, pairs=None, threshold=FINGERPRINT_THRESHOLD, max_offset=FINGERPRINT_MAX_OFFSET,
+                           min_overlap=FINGERPRINT_MIN_OVERLAP, return_match=False):
+    """Which fingerprints are the same recording: the pairs (None: every pair i < j, refused above 4096 fingerprints -- build
+    candidate pairs instead, as library.fingerprint_duplicates does) are matched in one device call (fingerprint_match); a pair
+    is an edge when bits > 0 and errors < threshold * bits, exactly (fingerprint_edges; 0.35 is the paper's threshold), and
+    the edges' connected components are found on the host.  -> labels int64 [n], the smallest index of every component, as
+    duplicate_labels returns them (groups_from_labels makes groups).  return_match: -> (labels, pairs, offset, errors, bits)."""
+    fps = list(fps)
+    n = len(fps)
+    if pairs is None:
+        if n > FINGERPRINT_ALL_PAIRS_MAX:
+            raise ValueError(f"all pairs of {n} fingerprints: pass candidate pairs above {FINGERPRINT_ALL_PAIRS_MAX}")
+        i, j = np.triu_indices(n, 1)
+        pairs = np.stack([i, j], axis=1)
+    pairs = _pair_array(pairs, n)
+    offset, errors, bits = fingerprint_match(fps, pairs, max_offset, min_overlap)
+    labels = labels_from_edges(n, pairs, fingerprint_edges(errors, bits, threshold))
+    return (labels, pairs, offset, errors, bits) if return_match else labels
+
+
 def variance_based_weight_matrix(seeds) -> np.ndarray:
     """src/playlist.rs:173-221: diagonal Mahalanobis weights ~ 1 / (variance + 1e-6), normalised to sum to d.
     O(seeds x d) host arithmetic in the reference's f32 evaluation order."""

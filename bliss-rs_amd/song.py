@@ -440,6 +440,90 @@ def analyze_batch(sample_arrays: Sequence[np.ndarray], options: Optional[Analysi
     return _results(out, status, version)
 
 
+# ---- acoustic fingerprints (blissgpu_fingerprint_batch): opt-in, never part of analyze_* ----
+FINGERPRINT_VERSION = 1  # stored beside the words (library.store_fingerprints): another contract, another number
+
+
+def fingerprint_len(n_samples: int) -> int:
+    """Sub-fingerprints of a song of n_samples samples at 22 050 Hz: (n - 8192) // 512, 0 below 8704 (device-free)."""
+    return int(_ffi.lib().blissgpu_fingerprint_len(int(n_samples)))
+
+
+def fingerprint_batch(sample_arrays: Sequence[np.ndarray], return_energies: bool = False):
+    """The Haitsma-Kalker fingerprint of every song, in one call: sample_arrays are the mono 22 050 Hz float32 samples
+    analyze_batch takes (1-D; anything else goes through fingerprint_decoded_batch).  -> a list of np.uint32 arrays, one
+    32-bit word per 512-sample hop, empty for a song of fewer than 8704 samples.  The contract -- frames of 8192 samples,
+    33 logarithmic bands over 300 .. 2000 Hz, a bit per band and frame pair -- is stated in include/blissgpu.h; two copies of
+    one recording differ in few bits once aligned (playlist.fingerprint_match).  return_energies: -> (words, energies), the
+    f64 band energies [frames, 33] of every song (the tests' tap)."""
+    arrays = []
+    for a in sample_arrays:
+        a = np.asarray(a)
+        if a.ndim == 2 and a.shape[1] == 1:
+            a = a[:, 0]
+        if a.ndim != 1 or a.dtype.kind != "f":
+            raise ProviderError("fingerprint_batch takes mono float samples at 22 050 Hz; decoder output goes through fingerprint_decoded_batch")
+        arrays.append(np.ascontiguousarray(a, dtype=np.float32))
+    n = len(arrays)
+    if n == 0:
+        return ([], []) if return_energies else []
+    L = _ffi.lib()
+    sample_offsets = np.zeros(n + 1, np.uint64)
+    sample_offsets[1:] = np.cumsum([a.shape[0] for a in arrays], dtype=np.uint64)
+    word_offsets = np.zeros(n + 1, np.uint64)
+    word_offsets[1:] = np.cumsum([L.blissgpu_fingerprint_len(a.shape[0]) for a in arrays], dtype=np.uint64)
+    pcm = np.concatenate(arrays) if n > 1 else arrays[0]
+    if pcm.size == 0:
+        pcm = np.zeros(1, np.float32)
+    n_words = int(word_offsets[n])
+    words = np.zeros(max(n_words, 1), np.uint32)
+    status = np.zeros(n, np.int32)
+    energies = np.zeros((n_words + n, 33), np.float64) if return_energies else None
+    _ffi.check(L.blissgpu_fingerprint_batch(pcm.ctypes.data, sample_offsets.ctypes.data, word_offsets.ctypes.data, n, words.ctypes.data,
+                                            status.ctypes.data, energies.ctypes.data if return_energies else None))
+    wo = word_offsets.astype(np.int64)
+    out = [words[wo[i]:wo[i + 1]].copy() for i in range(n)]
+    if not return_energies:
+        return out
+    # song i owns rows wo[i] + i .. : one per frame = one more than its words; a too-short song has no frame
+    return out, [energies[wo[i] + i:wo[i + 1] + i + 1] if wo[i + 1] > wo[i] else np.zeros((0, 33)) for i in range(n)]
+
+
+def fingerprint_decoded_batch(sample_arrays: Sequence[np.ndarray], sample_rates):
+    """fingerprint_batch for decoder output at ANY sample rate (1-D mono or [frames, channels]; float32 / int16 / int32): every
+    song goes through the device conversion analyze_decoded_batch uses (blissgpu_pcm_decode_device: downmix, widening,
+    libswresample's resampler to mono 22 050 Hz), then through fingerprint_batch.  sample_rates: one rate or one per song."""
+    arrays = [_as_pcm(a) for a in sample_arrays]
+    n = len(arrays)
+    if n == 0:
+        return []
+    rates = [int(sample_rates)] * n if np.isscalar(sample_rates) else [int(r) for r in sample_rates]
+    if len(rates) != n:
+        raise ProviderError("one sample rate per song")
+    L = _ffi.lib()
+    ctx = C.c_void_p()
+    _ffi.check(L.blissgpu_default_ctx(0, C.byref(ctx)))
+    mono = []
+    for a, rate in zip(arrays, rates):
+        n_out = int(L.blissgpu_resampled_len(a.shape[0], rate))
+        out = np.zeros(n_out, np.float32)
+        if n_out:
+            d_in, d_out = C.c_void_p(), C.c_void_p()
+            _ffi.check(L.blissgpu_malloc(C.byref(d_in), a.nbytes))
+            try:
+                _ffi.check(L.blissgpu_malloc(C.byref(d_out), out.nbytes))
+                try:
+                    _ffi.check(L.blissgpu_memcpy_h2d(ctx, d_in, a.ctypes.data, a.nbytes))
+                    _ffi.check(L.blissgpu_pcm_decode_device(ctx, d_in, _fmt_of(a), 1 if a.ndim == 1 else a.shape[1], a.shape[0], rate, d_out))
+                    _ffi.check(L.blissgpu_memcpy_d2h(ctx, out.ctypes.data, d_out, out.nbytes))  # (on the context's stream, then waits)
+                finally:
+                    L.blissgpu_free(d_out)
+            finally:
+                L.blissgpu_free(d_in)
+        mono.append(out)
+    return fingerprint_batch(mono)
+
+
 @dataclass
 class Song:
     """src/song/mod.rs:45-76 (metadata fields kept, filled by decoders)."""

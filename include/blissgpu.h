@@ -1169,6 +1169,55 @@ int blissgpu_duplicate_groups_device(blissgpu_ctx *ctx, const float *d_x, uint64
                                      int metric, const float *d_M, float threshold, uint32_t *d_label, uint64_t *d_n_pairs,
                                      uint32_t *d_pairs, float *d_pair_dist, uint64_t max_pairs);
 
+/* ---- acoustic fingerprints: the same RECORDING found again ----
+ * The reference's TODO.md asks for "better duplicate finding in the playlist module (sometimes songs have different [features]
+ * across albums but should have the same fingerprint)"; it has no code for it.  The fingerprint is the one of Haitsma & Kalker,
+ * "A Highly Robust Audio Fingerprinting System" (ISMIR 2002), on the 22 050 Hz mono f32 samples blissgpu_analyze_batch takes:
+ * its 0.37 s frame is exactly 8192 samples here.  Opt-in: no analyze_* entry point computes it.
+ *
+ * Frames.  Frame f covers samples [512 f, 512 f + 8192); no padding, no reflection.  A song of n >= 8704 samples has
+ * frames = (n - 8192) / 512 + 1 frames and words = frames - 1 = (n - 8192) / 512 sub-fingerprints (integer division); a song of
+ * n < 8704 samples has status BLISSGPU_SONG_TOO_SHORT and 0 words.  blissgpu_fingerprint_len returns `words` (device-free).
+ *
+ * Spectrum.  The window is the periodic Hann window of the analysis STFT (0.5f - 0.5f * cosf(2.0f * n * PI_F / 8192.0f) in f32);
+ * the window product is rounded to f32, as the STFT does; the FFT is a real FFT-8192 in f32.
+ *
+ * Bands.  33 bands over 300 .. 2000 Hz, logarithmically spaced: the bin edges are k_b = rint(300 (2000 / 300)^(b / 33) 8192 /
+ * 22050), b = 0 .. 33 -- but the contract is the integer table itself, not the formula:
+ *   111 118 125 132 140 149 157 167 177 187 198 210 222 235 249 264 280 296 314 332 352 373 395 418 443 469 497 526 557 590 625
+ *   662 702 743
+ * (blissgpu_fingerprint_bands returns it, device-free).  Band b is bins [k_b, k_{b+1}), and
+ *   E[f][b] = sum over k of ((double)re_k * (double)re_k + (double)im_k * (double)im_k),
+ * an f64 sum in ascending bin order taken from the f32 FFT outputs.
+ *
+ * Bits.  For t = 1 .. frames - 1 and b = 0 .. 31:  m = (E[t][b] - E[t][b+1]) - (E[t-1][b] - E[t-1][b+1]), evaluated in f64 in
+ * exactly this association; bit b (LSB = band 0) of word[t-1] is 1 iff m > 0.  Two consecutive frames of digital silence give
+ * word 0: a word equal to 0 marks silence, and the match leaves it out.
+ *
+ * blissgpu_fingerprint_batch (host pointers): song s is pcm[sample_offsets[s] .. sample_offsets[s + 1]) (n_songs + 1 ascending
+ * offsets); word_offsets [n_songs + 1] is filled BY THE CALLER from blissgpu_fingerprint_len (word_offsets[0] = 0; anything else
+ * is BLISSGPU_ERR_INVALID, as is a song of more than 2^22 words).  words [word_offsets[n_songs]] receives song s's words at
+ * word_offsets[s], status [n_songs] BLISSGPU_SONG_OK or BLISSGPU_SONG_TOO_SHORT.  energies (may be NULL; the tests' tap) is f64
+ * [word_offsets[n_songs] + n_songs][33]: frame f of song s is row word_offsets[s] + s + f; a too-short song owns one row, all
+ * zero.  An all-zero frame has energies exactly 0.0.  Runs on the default context; n_songs == 0 is BLISSGPU_OK. */
+uint64_t blissgpu_fingerprint_len(uint64_t n_samples);
+int blissgpu_fingerprint_bands(uint32_t *edges); /* edges [34] */
+int blissgpu_fingerprint_batch(const float *pcm, const uint64_t *sample_offsets, const uint64_t *word_offsets, uint32_t n_songs,
+                               uint32_t *words, int32_t *status, double *energies);
+/* The match.  For fingerprints a (length la) and b (length lb) and an offset o in [-max_offset, max_offset]: the positions are
+ * those t with 0 <= t < la and 0 <= t + o < lb; a position is valid when a[t] != 0 and b[t + o] != 0;
+ *   bits(o) = 32 * #valid,  errors(o) = sum over the valid positions of popcount(a[t] ^ b[t + o]).
+ * An offset counts only when #valid >= min_overlap.  The best offset minimises errors / bits, compared exactly
+ * (e * bits' < e' * bits in 64-bit integers); ties go to the smaller (|o|, o).  Per pair: offset, errors and bits of the best
+ * offset; bits == 0, errors == 0 and offset == 0 when no offset counts.  Pure integer work: the result is defined to the bit.
+ * pairs is u32 [n_pairs][2], indices into the n_songs fingerprints words[word_offsets[s] .. word_offsets[s + 1]); a pair (i, i)
+ * is allowed.  Limits: at most 2^22 words per song, max_offset <= 4096, min_overlap >= 1, n_pairs < 2^32.  A pair that names a
+ * song >= n_songs or a song without words, or a limit exceeded, is BLISSGPU_ERR_INVALID, checked before the device is touched.
+ * n_pairs == 0 is BLISSGPU_OK.  Host pointers; runs on the default context. */
+int blissgpu_fingerprint_match(const uint32_t *words, const uint64_t *word_offsets, uint32_t n_songs, const uint32_t *pairs,
+                               uint64_t n_pairs, uint32_t max_offset, uint32_t min_overlap, int32_t *offset, uint32_t *errors,
+                               uint32_t *bits);
+
 /* ---- extended isolation forest: the ForestOptions metric of src/playlist.rs:230-251 ----
  * The reference builds extended_isolation_forest::Forest<f32, 23> from the seed songs with the thread RNG and uses its score
  * as the "distance" of closest_to_songs (:247-250): seeds-like songs score low, outliers high.  Here the forest is a pure
