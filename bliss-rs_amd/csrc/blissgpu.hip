@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "launch_forms.hpp"
 #include "metric_learn.hpp"
 #include "covariance_metric.hpp"
 #include "mst_merge.hpp"
@@ -27,53 +28,11 @@ using namespace bg;
 namespace {
 thread_local std::string g_last_error;
 
-// (the names of KX_SEGMENT_MEAN and KX_ALBUM_KNN_SCAN, the ids numbered behind the KernelId list: see internal.hpp)
-const char kSegmentMeanName[] = "segment_mean_kernel", kAlbumKnnScanName[] = "album_knn_scan_kernel";
-const char kGroupForestScanName[] = "group_forest_scan_kernel";  // KX_GROUP_FOREST_SCAN
-const char kJourneyStepName[] = "journey_step_kernel";  // KX_JOURNEY_STEP
-// KX_KMEANS_ASSIGN .. KX_KMEANS_SELECT
-const char kKmeansAssignName[] = "kmeans_assign_kernel", kKmeansHistName[] = "kmeans_hist_kernel";
-const char kKmeansScanTilesName[] = "kmeans_scan_tiles_kernel", kKmeansScanAddName[] = "kmeans_scan_add_kernel";
-const char kKmeansScatterName[] = "kmeans_scatter_kernel", kKmeansSelectName[] = "kmeans_select_kernel";
-const char kTripletStepName[] = "triplet_step_kernel", kTripletReduceName[] = "triplet_reduce_kernel";  // KX_TRIPLET_*
-const char kSilhouetteScanName[] = "silhouette_scan_kernel", kSilhouetteFinishName[] = "silhouette_finish_kernel";  // KX_SILHOUETTE_*
-const char kMomentsPlanName[] = "moments_plan_kernel", kMomentsSumName[] = "moments_sum_kernel", kMomentsM2Name[] = "moments_m2_kernel";
-const char kMomentsScatterName[] = "moments_scatter_kernel", kMomentsReduceName[] = "moments_reduce_kernel";  // KX_MOMENTS_*
-const char kMomentsFinishName[] = "moments_finish_kernel";
-const char kChamferScanName[] = "chamfer_scan_kernel", kChamferReduceName[] = "chamfer_reduce_kernel";  // KX_CHAMFER_*
-const char kChamferSelectName[] = "chamfer_select_kernel";
-const char kMstScanName[] = "mst_scan_kernel", kMstPickName[] = "mst_pick_kernel";  // KX_MST_*
-const char kScaledKnnScanName[] = "scaled_knn_scan_kernel", kKnnOccurrenceName[] = "knn_occurrence_kernel";  // KX_SCALED_KNN_SCAN, KX_KNN_OCCURRENCE
-const char kRadioBanName[] = "radio_ban_kernel", kRadioStepName[] = "radio_step_kernel";  // KX_RADIO_BAN, KX_RADIO_STEP
-const char kMapRepulseName[] = "map_repulse_kernel", kMapAttractName[] = "map_attract_kernel";  // KX_MAP_*
-const char kMapUpdateName[] = "map_update_kernel";
-const char kWardScanName[] = "ward_scan_kernel", kWardJoinName[] = "ward_join_kernel";  // KX_WARD_*
-const char kPamScanName[] = "pam_scan_kernel", kPamFoldName[] = "pam_fold_kernel", kPamPickName[] = "pam_pick_kernel";  // KX_PAM_*
-const char kPamGatherName[] = "pam_gather_kernel", kPamStateName[] = "pam_state_kernel", kPamTdName[] = "pam_td_kernel";
-const char kFpBandsName[] = "fp_bands_kernel", kFpBitsName[] = "fp_bits_kernel";  // KX_FP_*
-const char kFpMatchName[] = "fp_match_kernel", kFpPickName[] = "fp_pick_kernel";
 const char* const kKernelNames[K_COUNT] = {
-    "fft512_kernel",     "onset_kernel",      "beat_kernel",   "stft8192_kernel", "tune_select_kernel",
-    "tune_pass2_kernel", "tune_final_kernel", "chroma_kernel",     "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel", "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel",
-    "dedup_next_kernel", "dedup_walk_kernel", "knn_scan_kernel", "knn_merge_kernel",
-    "forest_walk_kernel", "forest_finish_kernel",
-    "dup_init_kernel", "dup_join_kernel", "dup_flatten_kernel",
-    "group_knn_scan_kernel", "group_knn_merge_kernel", "group_weights_kernel",
-    "chain_step_kernel", "chain_walk_kernel",
-    kSegmentMeanName, kAlbumKnnScanName,
-    kKmeansAssignName, kKmeansHistName, kKmeansScanTilesName, kKmeansScanAddName, kKmeansScatterName, kKmeansSelectName,
-    kTripletStepName, kTripletReduceName,
-    kSilhouetteScanName, kSilhouetteFinishName,
-    kMomentsPlanName, kMomentsSumName, kMomentsM2Name, kMomentsScatterName, kMomentsReduceName, kMomentsFinishName,
-    kChamferScanName, kChamferReduceName, kChamferSelectName,
-    kMstScanName, kMstPickName,
-    kScaledKnnScanName, kKnnOccurrenceName,
-    kRadioBanName, kRadioStepName,
-    kMapRepulseName, kMapAttractName, kMapUpdateName,
-    kWardScanName, kWardJoinName,
-    kPamScanName, kPamFoldName, kPamPickName, kPamGatherName, kPamStateName, kPamTdName,
-    kFpBandsName, kFpBitsName, kFpMatchName, kFpPickName,
-    kGroupForestScanName, kJourneyStepName};
+#define X(id, name) name,
+    BLISSGPU_KERNEL_TABLE(X)
+#undef X
+};
 }  // namespace
 
 namespace bg {
@@ -644,15 +603,25 @@ int read_flags(blissgpu_ctx* c, const uint32_t* d_flags, uint32_t count, uint32_
     return BLISSGPU_OK;
 }
 
-// the k-means sort of a labelling: labels -> arow_off (the groups' offsets) and arow (their rows; NULL: the offsets alone, hist
-// is then left at the positions the scatter would start from); hist is zero on entry
-void launch_label_sort(blissgpu_ctx* c, const uint32_t* d_labels, uint32_t n, uint32_t k, const KmeansPlan& plan, uint32_t* hist,
-                       uint32_t* bsum, uint32_t* arow_off, uint32_t* arow) {
-    { Prof p(c, KX_KMEANS_HIST); launch_kmeans_hist(d_labels, n, k, plan, hist, c->stream); }
-    { Prof p(c, KX_KMEANS_SCAN_TILES); launch_kmeans_scan_tiles(hist, plan, bsum, c->stream); }
-    { Prof p(c, KX_KMEANS_SCAN_ADD); launch_kmeans_scan_add(hist, n, k, plan, bsum, arow_off, c->stream); }
-    if (arow) { Prof p(c, KX_KMEANS_SCATTER); launch_kmeans_scatter(d_labels, n, k, plan, hist, arow, c->stream); }
-}
+// The k-means sort of a labelling of n songs into k groups, at the head of a call's workspace (the words: launch_forms.hpp):
+// labels -> arow_off (the groups' offsets) and arow (their rows).  The call's flags are the workspace's first four words, so that
+// one memset of zero_words() clears them with the histograms, which the sort needs zero on entry
+struct LabelSort : LabelSortWords {
+    KmeansPlan plan;
+    uint32_t k, n;
+    uint32_t *flags = nullptr, *hist = nullptr, *bsum = nullptr, *arow_off = nullptr, *arow = nullptr;
+    LabelSort(const KmeansPlan& plan, uint32_t k, uint64_t n)
+        : LabelSortWords(label_sort_words(plan.hist_words, plan.scan_tiles, k, n)), plan(plan), k(k), n((uint32_t)n) {}
+    void bind(uint32_t* w) { flags = w; hist = w + o_hist; bsum = w + o_bsum; arow_off = w + o_off; arow = w + o_arow; }
+    size_t zero_words() const { return o_bsum; }
+    // (without the rows: the offsets alone; hist is then left at the positions the scatter would start from)
+    void launch(blissgpu_ctx* c, const uint32_t* d_labels, bool with_rows = true) const {
+        { Prof p(c, KX_KMEANS_HIST); launch_kmeans_hist(d_labels, n, k, plan, hist, c->stream); }
+        { Prof p(c, KX_KMEANS_SCAN_TILES); launch_kmeans_scan_tiles(hist, plan, bsum, c->stream); }
+        { Prof p(c, KX_KMEANS_SCAN_ADD); launch_kmeans_scan_add(hist, n, k, plan, bsum, arow_off, c->stream); }
+        if (with_rows) { Prof p(c, KX_KMEANS_SCATTER); launch_kmeans_scatter(d_labels, n, k, plan, hist, arow, c->stream); }
+    }
+};
 
 }  // namespace
 
@@ -1225,15 +1194,16 @@ int blissgpu_kmeans_device(blissgpu_ctx* c, const float* d_x, uint64_t n, uint32
     // workspace, O(n + K d + chunks x K): flags u32[4] ([0] labels that moved, [1] NaN) | hist u32[K][W] | scan totals | arow_off
     // u32[K + 1] | arow u32[n] | centres f32[2][K][d]
     const KmeansPlan plan = kmeans_plan(n, k, c->n_cus);
-    const size_t o_hist = 4, o_bsum = o_hist + (size_t)plan.hist_words, o_off = o_bsum + plan.scan_tiles, o_arow = o_off + k + 1,
-                 o_cent = o_arow + (size_t)n, words = o_cent + 2 * (size_t)k * d;
+    LabelSort sort(plan, k, n);
+    const size_t o_cent = sort.end, words = o_cent + 2 * (size_t)k * d;
     rc = c->km_ws.ensure(words * sizeof(uint32_t));
     if (rc) return rc;
     uint32_t* w = reinterpret_cast<uint32_t*>(c->km_ws.p);
-    uint32_t *flags = w, *hist = w + o_hist, *bsum = w + o_bsum, *arow_off = w + o_off, *arow = w + o_arow;
+    sort.bind(w);
+    uint32_t *flags = sort.flags, *arow_off = sort.arow_off;
     float* cent[2] = {reinterpret_cast<float*>(w + o_cent), reinterpret_cast<float*>(w + o_cent) + (size_t)k * d};
-    const AlbumTables tables{nullptr, arow_off, arow, nullptr, nullptr, nullptr, nullptr, nullptr, k, 0u, 0u};
-    const size_t zero_bytes = (o_hist + (size_t)plan.hist_words) * sizeof(uint32_t);  // the flags and the histograms: one memset
+    const AlbumTables tables{nullptr, arow_off, sort.arow, nullptr, nullptr, nullptr, nullptr, nullptr, k, 0u, 0u};
+    const size_t zero_bytes = sort.zero_words() * sizeof(uint32_t);  // the flags and the histograms: one memset
     HIP_TRY(hipMemcpyAsync(cent[0], d_init, cent_bytes, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(d_labels, 0xFF, (size_t)n * sizeof(uint32_t), c->stream));  // L_-1: no label
     uint32_t t = 0;
@@ -1254,7 +1224,7 @@ int blissgpu_kmeans_device(blissgpu_ctx* c, const float* d_x, uint64_t n, uint32
         if (h_flags[1]) return fail(BLISSGPU_ERR_NAN, who, "NaN distance (the reference panics here)");
         if (h_flags[0] == 0) { conv = 1; break; }
         if (t == max_iter) break;
-        launch_label_sort(c, d_labels, (uint32_t)n, k, plan, hist, bsum, arow_off, arow);
+        sort.launch(c, d_labels);
         { Prof p(c, KX_SEGMENT_MEAN); launch_segment_mean(d_x, nullptr, d, tables, cent[cur ^ 1], nullptr, nullptr, c->stream); }
         { Prof p(c, KX_KMEANS_SELECT); launch_kmeans_select(cent[cur], cent[cur ^ 1], arow_off, k, d, nullptr, c->stream); }
         HIP_TRY(hipGetLastError());
@@ -1264,7 +1234,7 @@ int blissgpu_kmeans_device(blissgpu_ctx* c, const float* d_x, uint64_t n, uint32
         // converged after an update: the labels are those the last sort saw; otherwise they moved since (or were never sorted)
         if (!conv || t == 0) {
             HIP_TRY(hipMemsetAsync(w, 0, zero_bytes, c->stream));
-            launch_label_sort(c, d_labels, (uint32_t)n, k, plan, hist, bsum, arow_off, nullptr);  // (the sizes need the offsets only)
+            sort.launch(c, d_labels, false);  // (the sizes need the offsets only)
         }
         { Prof p(c, KX_KMEANS_SELECT); launch_kmeans_select(nullptr, nullptr, arow_off, k, d, d_sizes, c->stream); }
         HIP_TRY(hipGetLastError());
@@ -1356,23 +1326,23 @@ int blissgpu_silhouette_device(blissgpu_ctx* c, const float* d_x, uint64_t n, ui
     if (int e = metric_is_diag(c, d_M, d, metric, &diag)) return e;
     // workspace, O(n + chunks x K + q Y): flags u32[4] ([0] NaN, [1] SIL_ERR_*) | hist u32[K][W] | scan totals | arow_off u32[K + 1]
     // | arow u32[n] | (8-byte aligned) own sums f64[Y][q] | best quotients f64[Y][q] | their clusters u32[Y][q]: 20 q Y bytes
-    const KmeansPlan sort = kmeans_plan(n, k, c->n_cus);
+    LabelSort sort(kmeans_plan(n, k, c->n_cus), k, n);
     const SilhouettePlan plan = silhouette_plan(q, k, c->n_cus, col_groups);
     const size_t qy = (size_t)q * plan.Y;
-    const size_t o_hist = 4, o_bsum = o_hist + (size_t)sort.hist_words, o_off = o_bsum + sort.scan_tiles, o_arow = o_off + k + 1,
-                 o_part = (o_arow + (size_t)n + 1) & ~(size_t)1, words = o_part + 5 * qy;
+    const size_t o_part = (sort.end + 1) & ~(size_t)1, words = o_part + 5 * qy;
     rc = c->sil_ws.ensure(words * sizeof(uint32_t));
     if (rc) return rc;
     uint32_t* w = reinterpret_cast<uint32_t*>(c->sil_ws.p);
-    uint32_t *flags = w, *hist = w + o_hist, *bsum = w + o_bsum, *arow_off = w + o_off, *arow = w + o_arow;
+    sort.bind(w);
+    uint32_t* flags = sort.flags;
     double* part = reinterpret_cast<double*>(w + o_part);
     SilhouetteArgs a{};
-    a.X = d_x; a.labels = d_labels; a.arow_off = arow_off; a.arow = arow; a.rows = d_rows; a.M = d_M;
+    a.X = d_x; a.labels = d_labels; a.arow_off = sort.arow_off; a.arow = sort.arow; a.rows = d_rows; a.M = d_M;
     a.n = (uint32_t)n; a.K = k; a.q = (uint32_t)q; a.Y = plan.Y; a.d = d; a.metric = metric;
     a.ws_own = part; a.ws_best_q = part + qy; a.ws_best_i = reinterpret_cast<uint32_t*>(part + 2 * qy);
     a.flags = flags; a.s = d_s; a.a = d_a; a.b = d_b; a.neighbour = d_neighbour; a.sizes = d_sizes;
-    HIP_TRY(hipMemsetAsync(w, 0, (o_hist + (size_t)sort.hist_words) * sizeof(uint32_t), c->stream));  // the flags and the histograms
-    launch_label_sort(c, d_labels, (uint32_t)n, k, sort, hist, bsum, arow_off, arow);
+    HIP_TRY(hipMemsetAsync(w, 0, sort.zero_words() * sizeof(uint32_t), c->stream));  // the flags and the histograms
+    sort.launch(c, d_labels);
     { Prof p(c, KX_SILHOUETTE_SCAN); launch_silhouette_scan(a, diag, plan, c->stream); }
     { Prof p(c, KX_SILHOUETTE_FINISH); launch_silhouette_finish(a, c->stream); }
     HIP_TRY(hipGetLastError());
@@ -1479,25 +1449,24 @@ int blissgpu_group_neighbours_device(blissgpu_ctx* c, const float* d_x, uint64_t
     if (int e = pairs ? metric_is_diag(c, d_M, d, metric, &diag) : 0) return e;
     // workspace: flags u32[4] ([0] NaN, [1] CH_ERR_*) | hist u32[K][W] | scan totals | arow_off u32[K + 1] | arow u32[n] | (8-byte
     // aligned) D f64[K][K] | row buffers f64[select grid][K] | minima f32[slab][n]
-    KmeansPlan sort{};
-    if (n) sort = kmeans_plan(n, k, c->n_cus);
-    const size_t o_hist = 4, o_bsum = o_hist + (size_t)sort.hist_words, o_off = o_bsum + sort.scan_tiles, o_arow = o_off + k + 1,
-                 o_d = (o_arow + (size_t)n + 1) & ~(size_t)1;
+    LabelSort sort(n ? kmeans_plan(n, k, c->n_cus) : KmeansPlan{}, k, n);
+    const size_t o_d = (sort.end + 1) & ~(size_t)1;
     const ChamferPlan plan = chamfer_plan(n, k, q, d_matrix != nullptr, c->n_cus, slab_groups, c->ws_limit, o_d * sizeof(uint32_t));
     if (!plan.fits) return fail(BLISSGPU_ERR_OOM, who, "D [k][k], the row buffers and one slab of minima do not fit the workspace limit");
     rc = c->ch_ws.ensure(plan.bytes);
     if (rc) return rc;
     uint32_t* w = reinterpret_cast<uint32_t*>(c->ch_ws.p);
-    uint32_t *flags = w, *hist = w + o_hist, *bsum = w + o_bsum, *arow_off = w + o_off, *arow = w + o_arow;
+    sort.bind(w);
+    uint32_t* flags = sort.flags;
     ChamferArgs a{};
-    a.X = d_x; a.labels = d_labels; a.arow_off = arow_off; a.arow = arow; a.queries = d_queries; a.M = d_M;
+    a.X = d_x; a.labels = d_labels; a.arow_off = sort.arow_off; a.arow = sort.arow; a.queries = d_queries; a.M = d_M;
     a.n = (uint32_t)n; a.K = k; a.d = d; a.q = (uint32_t)q; a.t = t; a.metric = metric; a.mode = mode;
     a.D = reinterpret_cast<double*>(w + o_d); a.rowbuf = a.D + (size_t)k * k;
     a.minima = reinterpret_cast<float*>(a.rowbuf + (size_t)plan.select_grid * k);
     a.flags = flags; a.idx = d_idx; a.dist = d_dist; a.sizes = d_sizes; a.matrix = d_matrix;
     // the flags and the histograms; without a song the offsets too (every group is empty)
-    HIP_TRY(hipMemsetAsync(w, 0, (n ? o_hist + (size_t)sort.hist_words : o_arow) * sizeof(uint32_t), c->stream));
-    if (n) launch_label_sort(c, d_labels, (uint32_t)n, k, sort, hist, bsum, arow_off, arow);
+    HIP_TRY(hipMemsetAsync(w, 0, (n ? sort.zero_words() : sort.o_arow) * sizeof(uint32_t), c->stream));
+    if (n) sort.launch(c, d_labels);
     if (pairs)
         for (uint32_t s0 = 0; s0 < k; s0 += plan.slab) {
             a.s0 = s0;
@@ -2053,7 +2022,9 @@ static int pam_scan_core(blissgpu_ctx* c, HostStage& s, const char* who, const f
     if (sort.hist_words > ws.hist_cap || sort.scan_tiles > ws.tiles_cap)
         return fail(BLISSGPU_ERR_INTERNAL, who, "the sort of the slots needs more than the workspace holds for it");
     HIP_TRY(hipMemsetAsync(ws.hist, 0, (size_t)sort.hist_words * sizeof(uint32_t), c->stream));
-    launch_label_sort(c, ws.near, (uint32_t)n, K, sort, ws.hist, ws.bsum, ws.arow_off, ws.arow);
+    LabelSort slots(sort, K, n);  // (on the tables pam_layout sized for the call's largest K, not on its own words)
+    slots.hist = ws.hist; slots.bsum = ws.bsum; slots.arow_off = ws.arow_off; slots.arow = ws.arow;
+    slots.launch(c, ws.near);
     HIP_TRY(hipGetLastError());
     for (uint64_t row0 = 0; row0 < q; row0 += ws.slab) {
         const uint64_t qs = std::min<uint64_t>(ws.slab, q - row0);
@@ -2524,9 +2495,8 @@ int blissgpu_moments_device(blissgpu_ctx* c, const float* d_x, uint64_t n, uint3
     // arow u32[n] | off u32[levels][K + 1] | keys u32[2][K d] | (8-byte aligned) the groups' partials A f64[items_0][d], B
     // f64[items_1][d] | the scatter's partials A f64[blocks_0][w], B f64[blocks_1][w].  Level l writes A when l is even, B when odd
     const MomentsPlan plan = moments_plan(n, k);
-    const KmeansPlan sort = kmeans_plan(n, k, c->n_cus);
-    const size_t o_hist = 4, o_bsum = o_hist + (d_labels ? (size_t)sort.hist_words : 0), o_aoff = o_bsum + (d_labels ? sort.scan_tiles : 0),
-                 o_arow = o_aoff + (d_labels ? k + 1 : 0), o_off = o_arow + (d_labels ? (size_t)n : 0),
+    LabelSort sort(kmeans_plan(n, k, c->n_cus), k, n);
+    const size_t o_off = d_labels ? sort.end : sort.o_hist,  // (without labels the sort has no tables: the flags alone)
                  o_keys = o_off + (size_t)plan.levels * (k + 1), o_pa = (o_keys + 2 * kd + 1) & ~(size_t)1,
                  o_pb = o_pa + 2 * (size_t)plan.items[0] * d, o_sa = o_pb + 2 * (size_t)(plan.levels > 1 ? plan.items[1] : 0) * d,
                  o_sb = o_sa + 2 * (d_S ? (size_t)plan.blocks[0] * w : 0),
@@ -2534,15 +2504,16 @@ int blissgpu_moments_device(blissgpu_ctx* c, const float* d_x, uint64_t n, uint3
     rc = c->mo_ws.ensure(words * sizeof(uint32_t));
     if (rc) return rc;
     uint32_t* ws = reinterpret_cast<uint32_t*>(c->mo_ws.p);
-    uint32_t *flags = ws, *hist = ws + o_hist, *bsum = ws + o_bsum, *arow_off = d_labels ? ws + o_aoff : nullptr,
-             *arow = d_labels ? ws + o_arow : nullptr, *off = ws + o_off, *keys = ws + o_keys;
+    sort.bind(ws);
+    uint32_t *flags = ws, *arow_off = d_labels ? sort.arow_off : nullptr, *arow = d_labels ? sort.arow : nullptr, *off = ws + o_off,
+             *keys = ws + o_keys;
     double* gpart[2] = {reinterpret_cast<double*>(ws + o_pa), reinterpret_cast<double*>(ws + o_pb)};
     double* spart[2] = {reinterpret_cast<double*>(ws + o_sa), reinterpret_cast<double*>(ws + o_sb)};
     MomentsArgs a{};
     a.X = d_x; a.labels = d_labels; a.arow_off = arow_off; a.arow = arow; a.off = off; a.mean = d_mean;
     a.n = (uint32_t)n; a.K = k; a.d = d; a.key_min = keys; a.key_max = keys + kd; a.flags = flags;
-    HIP_TRY(hipMemsetAsync(ws, 0, (o_hist + (d_labels ? (size_t)sort.hist_words : 0)) * sizeof(uint32_t), c->stream));
-    if (d_labels) launch_label_sort(c, d_labels, (uint32_t)n, k, sort, hist, bsum, arow_off, arow);
+    HIP_TRY(hipMemsetAsync(ws, 0, (d_labels ? sort.zero_words() : sort.o_hist) * sizeof(uint32_t), c->stream));
+    if (d_labels) sort.launch(c, d_labels);
     { Prof p(c, KX_MOMENTS_PLAN); launch_moments_plan(arow_off, (uint32_t)n, k, plan, off, d_counts, c->stream); }
     // the levels above level 0 of one per-group quantity, and its last step into dst
     auto group_levels = [&](int mode, double* dst) {

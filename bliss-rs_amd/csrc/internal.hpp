@@ -100,69 +100,112 @@ struct DeviceTables {   // constant tables, built once per context
     const float* bt_dfwv;     // [512] detection-function weighting, src/aubio.rs:933-936
 };
 
+// The profiling table: one entry per kernel, X(id, name).  enum KernelId, K_COUNT and the names blissgpu_profile_kernel_name
+// returns are all generated from this list, so a new kernel is one new line.  The ids are positions in the list: a new entry
+// goes in front of the last two (tests/test_journeys_host.py holds the table to end in them; tests/test_chains_host.py pins
+// the first 29 names by value), and every consumer of the table goes by name
+#define BLISSGPU_KERNEL_TABLE(X)                                                                                                  \
+    X(K_FFT512, "fft512_kernel")                                                                                                  \
+    X(K_ONSET, "onset_kernel")                                                                                                    \
+    X(K_BEAT, "beat_kernel")                                                                                                      \
+    X(K_STFT8192, "stft8192_kernel")                                                                                              \
+    X(K_TUNE_SELECT, "tune_select_kernel")                                                                                        \
+    X(K_TUNE_PASS2, "tune_pass2_kernel")                                                                                          \
+    X(K_TUNE_FINAL, "tune_final_kernel")                                                                                          \
+    X(K_CHROMA, "chroma_kernel")                                                                                                  \
+    X(K_SUMMARY, "summary_kernel")                                                                                                \
+    X(K_FINALIZE, "assemble_kernel")                                                                                              \
+    X(K_PAIRWISE, "pairwise_kernel")                                                                                              \
+    X(K_SET_DISTANCE, "set_distance_kernel")                                                                                      \
+    X(K_SONG_TO_SONG, "song_to_song_kernel")                                                                                      \
+    X(K_SYNTH, "synth_kernel")                                                                                                    \
+    X(K_ROLLFIX, "rolloff_fix_kernel")                                                                                            \
+    /* playlist deduplication: never launched by the analysis path */                                                             \
+    X(K_DEDUP_NEXT, "dedup_next_kernel")                                                                                          \
+    X(K_DEDUP_WALK, "dedup_walk_kernel")                                                                                          \
+    /* k-nearest search (kernels_knn.hip) */                                                                                      \
+    X(K_KNN_SCAN, "knn_scan_kernel")                                                                                              \
+    X(K_KNN_MERGE, "knn_merge_kernel")                                                                                            \
+    /* isolation-forest scores (kernels_forest.hip) */                                                                            \
+    X(K_FOREST_WALK, "forest_walk_kernel")                                                                                        \
+    X(K_FOREST_FINISH, "forest_finish_kernel")                                                                                    \
+    /* duplicate groups of a collection (kernels_duplicates.hip) */                                                               \
+    X(K_DUP_INIT, "dup_init_kernel")                                                                                              \
+    X(K_DUP_JOIN, "dup_join_kernel")                                                                                              \
+    X(K_DUP_FLATTEN, "dup_flatten_kernel")                                                                                        \
+    /* k-nearest search per seed group, the variance-based weights of every seed group (kernels_group_knn.hip) */                 \
+    X(K_GROUP_KNN_SCAN, "group_knn_scan_kernel")                                                                                  \
+    X(K_GROUP_KNN_MERGE, "group_knn_merge_kernel")                                                                                \
+    X(K_GROUP_WEIGHTS, "group_weights_kernel")                                                                                    \
+    /* song-to-song chains cut after k (kernels_chains.hip) */                                                                    \
+    X(K_CHAIN_STEP, "chain_step_kernel")                                                                                          \
+    X(K_CHAIN_WALK, "chain_walk_kernel")                                                                                          \
+    /* k-nearest albums per seed group (kernels_albums.hip; its partial lists are merged by knn_merge_kernel) */                  \
+    X(KX_SEGMENT_MEAN, "segment_mean_kernel")                                                                                     \
+    X(KX_ALBUM_KNN_SCAN, "album_knn_scan_kernel")                                                                                 \
+    /* k-means (kernels_kmeans.hip): the nearest centre of every song, the counting sort of the labels, the select */             \
+    X(KX_KMEANS_ASSIGN, "kmeans_assign_kernel")                                                                                   \
+    X(KX_KMEANS_HIST, "kmeans_hist_kernel")                                                                                       \
+    X(KX_KMEANS_SCAN_TILES, "kmeans_scan_tiles_kernel")                                                                           \
+    X(KX_KMEANS_SCAN_ADD, "kmeans_scan_add_kernel")                                                                               \
+    X(KX_KMEANS_SCATTER, "kmeans_scatter_kernel")                                                                                 \
+    X(KX_KMEANS_SELECT, "kmeans_select_kernel")                                                                                   \
+    /* one gradient evaluation of triplet metric learning (kernels_metric.hip): the wavefronts' partials, their ascending sum */  \
+    X(KX_TRIPLET_STEP, "triplet_step_kernel")                                                                                     \
+    X(KX_TRIPLET_REDUCE, "triplet_reduce_kernel")                                                                                 \
+    /* the silhouette (kernels_silhouette.hip): the all-pairs sums per (song, cluster), then a, b, neighbour and s */             \
+    X(KX_SILHOUETTE_SCAN, "silhouette_scan_kernel")                                                                               \
+    X(KX_SILHOUETTE_FINISH, "silhouette_finish_kernel")                                                                           \
+    /* the moments (kernels_moments.hip): the levels' offsets, level 0 of the means, of the squared deviations and of the */      \
+    /* scatter matrix, every further level of the blocked sum, the extrema */                                                     \
+    X(KX_MOMENTS_PLAN, "moments_plan_kernel")                                                                                     \
+    X(KX_MOMENTS_SUM, "moments_sum_kernel")                                                                                       \
+    X(KX_MOMENTS_M2, "moments_m2_kernel")                                                                                         \
+    X(KX_MOMENTS_SCATTER, "moments_scatter_kernel")                                                                               \
+    X(KX_MOMENTS_REDUCE, "moments_reduce_kernel")                                                                                 \
+    X(KX_MOMENTS_FINISH, "moments_finish_kernel")                                                                                 \
+    /* group-to-group set distances (kernels_chamfer.hip): the minima per (song, group), their blocked sums, the selection */     \
+    X(KX_CHAMFER_SCAN, "chamfer_scan_kernel")                                                                                     \
+    X(KX_CHAMFER_REDUCE, "chamfer_reduce_kernel")                                                                                 \
+    X(KX_CHAMFER_SELECT, "chamfer_select_kernel")                                                                                 \
+    /* the minimum spanning tree (kernels_mst.hip): every song's smallest edge out of its component, every component's */         \
+    X(KX_MST_SCAN, "mst_scan_kernel")                                                                                             \
+    X(KX_MST_PICK, "mst_pick_kernel")                                                                                             \
+    /* locally scaled k-nearest search and the k-occurrence counts (kernels_scaled_knn.hip; merged by knn_merge_kernel) */        \
+    X(KX_SCALED_KNN_SCAN, "scaled_knn_scan_kernel")                                                                               \
+    X(KX_KNN_OCCURRENCE, "knn_occurrence_kernel")                                                                                 \
+    /* radio playlists (kernels_radio.hip): the banned labels of every (radio, rule), then the step under them */                 \
+    X(KX_RADIO_BAN, "radio_ban_kernel")                                                                                           \
+    X(KX_RADIO_STEP, "radio_step_kernel")                                                                                         \
+    /* the 2-D map (kernels_map.hip): the all-pairs repulsion, the attraction along the CSR rows, the gradient and update */      \
+    X(KX_MAP_REPULSE, "map_repulse_kernel")                                                                                       \
+    X(KX_MAP_ATTRACT, "map_attract_kernel")                                                                                       \
+    X(KX_MAP_UPDATE, "map_update_kernel")                                                                                         \
+    /* Ward clustering (kernels_ward.hip): every cluster's nearest other cluster under Ward's cost, the join */                   \
+    X(KX_WARD_SCAN, "ward_scan_kernel")                                                                                           \
+    X(KX_WARD_JOIN, "ward_join_kernel")                                                                                           \
+    /* k-medoids (kernels_pam.hip): the all-pairs swap scan, its fold per candidate, the round's winner, the state's helpers */   \
+    X(KX_PAM_SCAN, "pam_scan_kernel")                                                                                             \
+    X(KX_PAM_FOLD, "pam_fold_kernel")                                                                                             \
+    X(KX_PAM_PICK, "pam_pick_kernel")                                                                                             \
+    X(KX_PAM_GATHER, "pam_gather_kernel")                                                                                         \
+    X(KX_PAM_STATE, "pam_state_kernel")                                                                                           \
+    X(KX_PAM_TD, "pam_td_kernel")                                                                                                 \
+    /* acoustic fingerprints (kernels_fingerprint.hip): the frames' band energies, the words, the match per offset block, pick */ \
+    X(KX_FP_BANDS, "fp_bands_kernel")                                                                                             \
+    X(KX_FP_BITS, "fp_bits_kernel")                                                                                               \
+    X(KX_FP_MATCH, "fp_match_kernel")                                                                                             \
+    X(KX_FP_PICK, "fp_pick_kernel")                                                                                               \
+    /* the k lowest forest scores per seed group (kernels_forest.hip; merged by group_knn_merge_kernel) */                        \
+    X(KX_GROUP_FOREST_SCAN, "group_forest_scan_kernel")                                                                           \
+    /* a journey's step (kernels_chains.hip: the chains' scan with a waypoint query or a gate) */                                 \
+    X(KX_JOURNEY_STEP, "journey_step_kernel")
 enum KernelId : int {
-    K_FFT512 = 0,
-    K_ONSET,
-    K_BEAT,
-    K_STFT8192,
-    K_TUNE_SELECT,
-    K_TUNE_PASS2,
-    K_TUNE_FINAL,
-    K_CHROMA,
-    K_SUMMARY,
-    K_FINALIZE,
-    K_PAIRWISE, K_SET_DISTANCE, K_SONG_TO_SONG,
-    K_SYNTH,
-    K_ROLLFIX,
-    K_DEDUP_NEXT, K_DEDUP_WALK,  // playlist deduplication: never launched by the analysis path
-    K_KNN_SCAN, K_KNN_MERGE,     // k-nearest search (kernels_knn.hip)
-    K_FOREST_WALK, K_FOREST_FINISH,  // isolation-forest scores (kernels_forest.hip)
-    K_DUP_INIT, K_DUP_JOIN, K_DUP_FLATTEN,  // duplicate groups of a collection (kernels_duplicates.hip)
-    K_GROUP_KNN_SCAN, K_GROUP_KNN_MERGE,    // k-nearest search per seed group (kernels_group_knn.hip)
-    K_GROUP_WEIGHTS,                        // variance-based weights of every seed group (kernels_group_knn.hip)
-    K_CHAIN_STEP, K_CHAIN_WALK,             // song-to-song chains cut after k (kernels_chains.hip)
-    // (tests/test_chains_host.py holds this list, and the list of names beside it, to end in the chain kernels: the kernels
-    // that came later are numbered behind it, so that no older id or name moves)
-    K_COUNT = K_CHAIN_WALK + 45
+#define X(id, name) id,
+    BLISSGPU_KERNEL_TABLE(X)
+#undef X
+    K_COUNT
 };
-// k-nearest albums per seed group (kernels_albums.hip; its partial lists are merged by knn_merge_kernel)
-constexpr int KX_SEGMENT_MEAN = K_CHAIN_WALK + 1, KX_ALBUM_KNN_SCAN = K_CHAIN_WALK + 2;
-// k-means of a library (kernels_kmeans.hip): the nearest centre of every song, the counting sort of the labels, the select
-constexpr int KX_KMEANS_ASSIGN = K_CHAIN_WALK + 3, KX_KMEANS_HIST = K_CHAIN_WALK + 4, KX_KMEANS_SCAN_TILES = K_CHAIN_WALK + 5,
-              KX_KMEANS_SCAN_ADD = K_CHAIN_WALK + 6, KX_KMEANS_SCATTER = K_CHAIN_WALK + 7, KX_KMEANS_SELECT = K_CHAIN_WALK + 8;
-// one gradient evaluation of triplet metric learning (kernels_metric.hip): the wavefronts' partials, their ascending sum
-constexpr int KX_TRIPLET_STEP = K_CHAIN_WALK + 9, KX_TRIPLET_REDUCE = K_CHAIN_WALK + 10;
-// the silhouette of a labelling (kernels_silhouette.hip): the all-pairs sums per (song, cluster), then a, b, neighbour and s
-constexpr int KX_SILHOUETTE_SCAN = K_CHAIN_WALK + 11, KX_SILHOUETTE_FINISH = K_CHAIN_WALK + 12;
-// the moments of a library (kernels_moments.hip): the levels' offsets, level 0 of the means, of the squared deviations and of the
-// scatter matrix, every further level of the blocked sum, the extrema
-constexpr int KX_MOMENTS_PLAN = K_CHAIN_WALK + 13, KX_MOMENTS_SUM = K_CHAIN_WALK + 14, KX_MOMENTS_M2 = K_CHAIN_WALK + 15,
-              KX_MOMENTS_SCATTER = K_CHAIN_WALK + 16, KX_MOMENTS_REDUCE = K_CHAIN_WALK + 17, KX_MOMENTS_FINISH = K_CHAIN_WALK + 18;
-// group-to-group set distances (kernels_chamfer.hip): the minima per (song, group), their blocked sums, the rows' selection
-constexpr int KX_CHAMFER_SCAN = K_CHAIN_WALK + 19, KX_CHAMFER_REDUCE = K_CHAIN_WALK + 20, KX_CHAMFER_SELECT = K_CHAIN_WALK + 21;
-// the minimum spanning tree (kernels_mst.hip): every song's smallest edge out of its component, every component's smallest
-constexpr int KX_MST_SCAN = K_CHAIN_WALK + 22, KX_MST_PICK = K_CHAIN_WALK + 23;
-// locally scaled k-nearest search and the k-occurrence counts (kernels_scaled_knn.hip; the scan's lists are merged by knn_merge_kernel)
-constexpr int KX_SCALED_KNN_SCAN = K_CHAIN_WALK + 24, KX_KNN_OCCURRENCE = K_CHAIN_WALK + 25;
-// radio playlists (kernels_radio.hip): the banned labels of every (radio, rule), then the step under them
-constexpr int KX_RADIO_BAN = K_CHAIN_WALK + 26, KX_RADIO_STEP = K_CHAIN_WALK + 27;
-// the 2-D map of a library (kernels_map.hip): the all-pairs repulsion, the attraction along the CSR rows, the gradient and update
-constexpr int KX_MAP_REPULSE = K_CHAIN_WALK + 28, KX_MAP_ATTRACT = K_CHAIN_WALK + 29, KX_MAP_UPDATE = K_CHAIN_WALK + 30;
-// Ward clustering (kernels_ward.hip): every cluster's nearest other cluster under Ward's cost, the join that makes the next centroids
-constexpr int KX_WARD_SCAN = K_CHAIN_WALK + 31, KX_WARD_JOIN = K_CHAIN_WALK + 32;
-// k-medoids (kernels_pam.hip): the all-pairs swap scan, its fold per candidate, the round's winner, and the state's three helpers
-constexpr int KX_PAM_SCAN = K_CHAIN_WALK + 33, KX_PAM_FOLD = K_CHAIN_WALK + 34, KX_PAM_PICK = K_CHAIN_WALK + 35;
-constexpr int KX_PAM_GATHER = K_CHAIN_WALK + 36, KX_PAM_STATE = K_CHAIN_WALK + 37, KX_PAM_TD = K_CHAIN_WALK + 38;
-// acoustic fingerprints (kernels_fingerprint.hip): the frames' band energies, the words, the match per offset block, its pick
-constexpr int KX_FP_BANDS = K_CHAIN_WALK + 39, KX_FP_BITS = K_CHAIN_WALK + 40, KX_FP_MATCH = K_CHAIN_WALK + 41,
-              KX_FP_PICK = K_CHAIN_WALK + 42;
-// (tests/test_journeys_host.py holds the profile table to END in the next two names: kernels that come later are numbered in
-// front of them; every consumer of the table goes by name)
-// the k lowest forest scores per seed group (kernels_forest.hip; its partial lists are merged by group_knn_merge_kernel)
-constexpr int KX_GROUP_FOREST_SCAN = K_CHAIN_WALK + 43;
-// a journey's step (kernels_chains.hip: the chains' scan with a waypoint query or a gate)
-constexpr int KX_JOURNEY_STEP = K_CHAIN_WALK + 44;
-static_assert(KX_JOURNEY_STEP + 1 == K_COUNT, "every kernel id is below the count");
 
 // lower_bound on a prefix array: largest s with prefix[s] <= x  (prefix has n+1 entries, prefix[0]=0)
 __device__ __forceinline__ uint32_t find_segment(const uint32_t* __restrict__ prefix, uint32_t n, uint32_t x) {

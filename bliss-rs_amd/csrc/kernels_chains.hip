@@ -394,7 +394,7 @@ __global__ __launch_bounds__(256) void chain_walk_kernel(const uint32_t* __restr
 // when few chains leave the device empty, the workgroups that share a chain's candidates (at least eight blocks each).
 ChainPlan chain_plan(uint64_t n_chains, uint64_t n, int n_cus) {
     ChainPlan p{};
-    const uint64_t cus = (uint64_t)(n_cus > 0 ? n_cus : 256);
+    const uint64_t cus = cus_or_default(n_cus);
     p.qb = (uint32_t)CH_QMAX;
     {
         const uint64_t slots = cus * 2;
@@ -414,36 +414,19 @@ ChainPlan chain_plan(uint64_t n_chains, uint64_t n, int n_cus) {
 }
 
 // (j == NULL: a chains' step; otherwise a journeys' step, which reads no goff)
-template <int D>
-static void step_d(const float* X, uint32_t n, uint32_t d, int metric, const float* M, int diag, const uint32_t* goff,
-                   const uint32_t* skip, uint32_t n_chains, uint32_t k, uint32_t t, const ChainPlan& p, uint32_t* idx, float* dist,
-                   unsigned long long* best, uint32_t* nan_flag, const JourneyStep* j, hipStream_t st) {
-    const dim3 grid(p.grid_cb * p.n_split);
-#define CH_GO(DD, MM, DG)                                                                                                            \
-    if (j)                                                                                                                           \
-        hipLaunchKernelGGL((journey_step_kernel<DD, MM, DG>), grid, dim3(256), 0, st, X, n, d, metric, M, skip, n_chains, k, t, p.qb, \
-                           p.n_split, p.blocks_per_split, idx, dist, best, nan_flag, *j);                                            \
-    else                                                                                                                             \
-        hipLaunchKernelGGL((chain_step_kernel<DD, MM, DG>), grid, dim3(256), 0, st, X, n, d, metric, M, goff, skip, n_chains, k, t,   \
-                           p.qb, p.n_split, p.blocks_per_split, idx, dist, best, nan_flag)
-    if constexpr (D == 0) {
-        CH_GO(0, METRIC_EUCLIDEAN, false);  // (the metric is a run-time argument of the generic path)
-    } else {
-        if (metric == METRIC_EUCLIDEAN) { CH_GO(D, METRIC_EUCLIDEAN, false); }
-        else if (metric == METRIC_COSINE) { CH_GO(D, METRIC_COSINE, false); }
-        else if (diag) { CH_GO(D, METRIC_MAHALANOBIS, true); }
-        else { CH_GO(D, METRIC_MAHALANOBIS, false); }
-    }
-#undef CH_GO
-}
-
 static void step_any(const float* X, uint32_t n, uint32_t d, int metric, const float* M, int m_is_diag, const uint32_t* goff,
                      const uint32_t* skip, uint32_t n_chains, uint32_t k, uint32_t t, const ChainPlan& p, uint32_t* idx, float* dist,
                      unsigned long long* best, uint32_t* nan_flag, const JourneyStep* j, hipStream_t st) {
     if (n_chains == 0 || n == 0) return;
-    if (d == 23) step_d<23>(X, n, d, metric, M, m_is_diag, goff, skip, n_chains, k, t, p, idx, dist, best, nan_flag, j, st);
-    else if (d == 20) step_d<20>(X, n, d, metric, M, m_is_diag, goff, skip, n_chains, k, t, p, idx, dist, best, nan_flag, j, st);
-    else step_d<0>(X, n, d, metric, M, m_is_diag, goff, skip, n_chains, k, t, p, idx, dist, best, nan_flag, j, st);
+    const dim3 grid(p.grid_cb * p.n_split);
+    for_metric_form<true>(d, metric, m_is_diag, [&](auto D, auto M_, auto G) {
+        if (j)
+            hipLaunchKernelGGL((journey_step_kernel<D(), M_(), G()>), grid, dim3(256), 0, st, X, n, d, metric, M, skip, n_chains, k, t, p.qb,
+                               p.n_split, p.blocks_per_split, idx, dist, best, nan_flag, *j);
+        else
+            hipLaunchKernelGGL((chain_step_kernel<D(), M_(), G()>), grid, dim3(256), 0, st, X, n, d, metric, M, goff, skip, n_chains, k, t,
+                               p.qb, p.n_split, p.blocks_per_split, idx, dist, best, nan_flag);
+    });
     if (p.n_split > 1)
         hipLaunchKernelGGL(chain_put_kernel, dim3((n_chains + 255u) / 256u), dim3(256), 0, st, best, nullptr, nullptr, n_chains, k, t,
                            idx, dist);

@@ -337,13 +337,11 @@ __global__ __launch_bounds__(256) void chamfer_select_kernel(const ChamferArgs a
 ChamferPlan chamfer_plan(uint64_t n, uint32_t K, uint64_t q, bool want_matrix, int n_cus, uint32_t slab_groups, uint64_t ws_limit,
                          uint64_t fixed_bytes) {
     ChamferPlan p{};
-    const uint32_t cus = (uint32_t)(n_cus > 0 ? n_cus : 256);
-    // as the silhouette: four wavefronts share a tile when there are enough songs to give every CU two such workgroups
-    const uint64_t pieces = (n + CH_SONGS_PER_WAVE - 1) / CH_SONGS_PER_WAVE;
-    p.waves = pieces >= (uint64_t)8 * cus ? 4u : 1u;
-    p.grid = (uint32_t)std::max<uint64_t>(1, (pieces + p.waves - 1) / p.waves);
+    const ScanFill f = scan_fill((n + CH_SONGS_PER_WAVE - 1) / CH_SONGS_PER_WAVE, n_cus);  // pieces of 256 positions
+    p.waves = f.waves;
+    p.grid = std::max<uint32_t>(1u, f.grid);
     const uint64_t jobs = q + (want_matrix ? K : 0);
-    p.select_grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::max<uint64_t>(jobs, (n + 255) / 256), 4ull * cus));
+    p.select_grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::max<uint64_t>(jobs, (n + 255) / 256), 4ull * f.cus));
     // the slab: what CHAMFER_SLAB_BYTES of minima hold, within the workspace limit; a forced slab must fit the limit as it is
     const uint64_t base = fixed_bytes + (uint64_t)K * K * 8 + (uint64_t)p.select_grid * K * 8;
     const uint64_t per_group = std::max<uint64_t>(n, 1) * 4;
@@ -356,11 +354,9 @@ ChamferPlan chamfer_plan(uint64_t n, uint32_t K, uint64_t q, bool want_matrix, i
     return p;
 }
 
-// column groups of one slab's scan: enough for about 32 wavefronts per CU, at most one per group of the slab
+// column groups of one slab's scan: what fills the device, at most one per group of the slab
 static uint32_t chamfer_col_groups(const ChamferPlan& p, uint32_t groups, int n_cus) {
-    const uint32_t cus = (uint32_t)(n_cus > 0 ? n_cus : 256);
-    const uint64_t in_one = (uint64_t)p.grid * p.waves;
-    const uint64_t Y = (32ull * cus + in_one - 1) / in_one;
+    const uint64_t Y = fill_col_groups(cus_or_default(n_cus), (uint64_t)p.grid * p.waves);
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(Y, groups));
 }
 
@@ -368,18 +364,9 @@ void launch_chamfer_scan(ChamferArgs a, int m_is_diag, const ChamferPlan& p, int
     if (a.n == 0 || a.s1 <= a.s0) return;
     a.Y = chamfer_col_groups(p, a.s1 - a.s0, n_cus);
     const dim3 grid(p.grid, a.Y), block(64u * p.waves);
-#define CH_GO(DD, MM, DG) hipLaunchKernelGGL((chamfer_scan_kernel<DD, MM, DG>), grid, block, 0, st, a)
-#define CH_D(DD)                                                             \
-    do {                                                                     \
-        if (a.metric == METRIC_EUCLIDEAN) CH_GO(DD, METRIC_EUCLIDEAN, false); \
-        else if (m_is_diag) CH_GO(DD, METRIC_MAHALANOBIS, true);             \
-        else CH_GO(DD, METRIC_MAHALANOBIS, false);                           \
-    } while (0)
-    if (a.d == 23) CH_D(23);
-    else if (a.d == 20) CH_D(20);
-    else CH_GO(0, METRIC_EUCLIDEAN, false);  // (the metric is a run-time argument of the generic path)
-#undef CH_D
-#undef CH_GO
+    for_metric_form<false>(a.d, a.metric, m_is_diag, [&](auto D, auto M, auto G) {
+        hipLaunchKernelGGL((chamfer_scan_kernel<D(), M(), G()>), grid, block, 0, st, a);
+    });
 }
 
 void launch_chamfer_reduce(const ChamferArgs& a, hipStream_t st) {

@@ -254,11 +254,11 @@ DupPlan dup_plan(uint64_t n, int n_cus) {
     p.nb = (uint32_t)((n + DUP_TILE - 1) / DUP_TILE);
     const uint64_t tiles = (uint64_t)p.nb * ((uint64_t)p.nb + 1) / 2;
     // a small triangle: slices of a tile's rows go to workgroups of their own until the device has ~4 per CU
-    const uint64_t want = (uint64_t)4 * (uint64_t)(n_cus > 0 ? n_cus : 256);
+    const uint64_t cus = cus_or_default(n_cus), want = 4 * cus;
     p.row_split = 1;
     while (p.row_split < 8 && tiles * p.row_split < want) p.row_split <<= 1;
     p.n_work = tiles * p.row_split;
-    p.grid = (uint32_t)std::min<uint64_t>(p.n_work, (uint64_t)64 * (uint64_t)(n_cus > 0 ? n_cus : 256));
+    p.grid = (uint32_t)std::min<uint64_t>(p.n_work, 64 * cus);
     return p;
 }
 
@@ -284,20 +284,10 @@ void launch_dup_join(const float* X, uint32_t n, uint32_t d, int metric, const f
                      float thr, const DupPlan& p, uint32_t* label, unsigned long long* n_pairs, unsigned long long* cursor,
                      uint32_t* pairs, float* pair_dist, uint64_t max_pairs, uint32_t* nan_flag, hipStream_t st) {
     const float bound = dup_bound(thr);
-#define DUP_GO(DD, MM, DG) hipLaunchKernelGGL((dup_join_kernel<DD, MM, DG>), dim3(p.grid), dim3(256), 0, st, X, n, d, metric, M, meta, thr, \
-                                              bound, p.nb, p.row_split, p.n_work, label, n_pairs, cursor, pairs, pair_dist, max_pairs, nan_flag)
-#define DUP_D(DD)                                                            \
-    do {                                                                     \
-        if (metric == METRIC_EUCLIDEAN) DUP_GO(DD, METRIC_EUCLIDEAN, false); \
-        else if (metric == METRIC_COSINE) DUP_GO(DD, METRIC_COSINE, false);  \
-        else if (m_is_diag) DUP_GO(DD, METRIC_MAHALANOBIS, true);            \
-        else DUP_GO(DD, METRIC_MAHALANOBIS, false);                          \
-    } while (0)
-    if (d == 23) DUP_D(23);
-    else if (d == 20) DUP_D(20);
-    else DUP_GO(0, METRIC_EUCLIDEAN, false);  // (the metric is a run-time argument of the generic path)
-#undef DUP_D
-#undef DUP_GO
+    for_metric_form<true>(d, metric, m_is_diag, [&](auto D, auto M_, auto G) {
+        hipLaunchKernelGGL((dup_join_kernel<D(), M_(), G()>), dim3(p.grid), dim3(256), 0, st, X, n, d, metric, M, meta, thr, bound, p.nb,
+                           p.row_split, p.n_work, label, n_pairs, cursor, pairs, pair_dist, max_pairs, nan_flag);
+    });
 }
 
 }  // namespace bg

@@ -487,43 +487,29 @@ GroupKnnPlan group_knn_plan(const uint64_t* off, uint64_t n_groups, uint64_t n, 
     return p;
 }
 
-template <int D, int KEYS>
-static void gk_scan_d(const float* S, const uint32_t* goff, const float* X, uint32_t n, uint32_t d, int metric, const float* M,
-                      bool pergroup, const uint32_t* skip, uint32_t k, const GroupKnnPlan& p, const GroupKnnItem* items, const uint32_t* list_off,
-                      unsigned long long* part, uint32_t* nan_flag, uint32_t* bad_flag, hipStream_t st) {
-    const dim3 grid((uint32_t)p.items.size());
-#define GK_GO(DD, MM) hipLaunchKernelGGL((group_knn_scan_kernel<DD, MM, KEYS>), grid, dim3(256), 0, st, S, goff, X, n, d, metric, M, skip, \
-                                         k, p.cap, p.qb, items, list_off, part, nan_flag, bad_flag)
-    if (pergroup) {  // M is [n_groups][d]: one diagonal per group
-        hipLaunchKernelGGL((group_knn_scan_kernel<D, METRIC_MAHALANOBIS, KEYS, true>), grid, dim3(256), 0, st, S, goff, X, n, d,
-                           metric, M, skip, k, p.cap, p.qb, items, list_off, part, nan_flag, bad_flag);
-    } else if constexpr (D == 0) {
-        GK_GO(0, METRIC_EUCLIDEAN);  // (the metric is a run-time argument of the generic path)
-    } else {
-        if (metric == METRIC_EUCLIDEAN) GK_GO(D, METRIC_EUCLIDEAN);
-        else if (metric == METRIC_COSINE) GK_GO(D, METRIC_COSINE);
-        else GK_GO(D, METRIC_MAHALANOBIS);
-    }
-#undef GK_GO
-}
-
 void launch_group_knn_scan(const float* S, const uint32_t* goff, const float* X, uint32_t n, uint32_t d, int metric,
                            const float* M, int m_is_diag, const uint32_t* skip, uint32_t k, const GroupKnnPlan& p,
                            const GroupKnnItem* items, const uint32_t* list_off, unsigned long long* part, uint32_t* nan_flag,
                            uint32_t* bad_flag, hipStream_t st) {
     if (p.items.empty()) return;
-    const bool small = p.cap <= 256;
-    const bool pergroup = m_is_diag == GROUP_KNN_M_PER_GROUP;  // (Mahalanobis; M holds a diagonal per group)
+    const dim3 grid((uint32_t)p.items.size());
+    const bool pergroup = m_is_diag == GROUP_KNN_M_PER_GROUP;  // (Mahalanobis; M is [n_groups][d]: one diagonal per group)
     const bool packed = (d == 23 || d == 20) && (metric != METRIC_MAHALANOBIS || m_is_diag);  // general M: pl_distance
-#define GK_D(DD)                                                                                                                  \
-    do {                                                                                                                          \
-        if (small) gk_scan_d<DD, KNN_KEYS_SMALL>(S, goff, X, n, d, metric, M, pergroup, skip, k, p, items, list_off, part, nan_flag, bad_flag, st); \
-        else gk_scan_d<DD, KNN_KEYS_BIG>(S, goff, X, n, d, metric, M, pergroup, skip, k, p, items, list_off, part, nan_flag, bad_flag, st);   \
-    } while (0)
-    if (packed && d == 23) GK_D(23);
-    else if (packed && d == 20) GK_D(20);
-    else GK_D(0);
-#undef GK_D
+    with_d(packed ? d : 0u, [&](auto D_) {
+        constexpr int D = decltype(D_)::value;
+        const auto scan = [&](auto KEYS) {
+            const auto go = [&](auto M_, auto PER) {
+                hipLaunchKernelGGL((group_knn_scan_kernel<D, decltype(M_)::value, decltype(KEYS)::value, decltype(PER)::value>), grid,
+                                   dim3(256), 0, st, S, goff, X, n, d, metric, M, skip, k, p.cap, p.qb, items, list_off, part, nan_flag,
+                                   bad_flag);
+            };
+            // (the packed kernels' Mahalanobis M is always a diagonal -- see `packed` --, so the ladder's diagonal flag names nothing here)
+            if (pergroup) go(std::integral_constant<int, METRIC_MAHALANOBIS>{}, std::true_type{});
+            else for_metric_form<true>(D_, metric, m_is_diag, [&](auto, auto M_, auto) { go(M_, std::false_type{}); });
+        };
+        if (p.cap <= 256) scan(std::integral_constant<int, KNN_KEYS_SMALL>{});
+        else scan(std::integral_constant<int, KNN_KEYS_BIG>{});
+    });
 }
 
 void launch_group_weights(const float* S, const uint32_t* goff, uint64_t n_groups, uint32_t d, float* W, int32_t* status,

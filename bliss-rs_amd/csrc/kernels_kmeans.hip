@@ -300,12 +300,11 @@ __global__ __launch_bounds__(256) void kmeans_select_kernel(const float* __restr
 
 KmeansPlan kmeans_plan(uint64_t n, uint32_t K, int n_cus) {
     KmeansPlan p{};
-    const uint32_t cus = (uint32_t)(n_cus > 0 ? n_cus : 256);
     // assignment: four wavefronts share a tile of centres when there are enough songs to give every CU two such workgroups;
     // a smaller library runs one wavefront per workgroup so that its 256-song pieces spread over the CUs
-    const uint64_t pieces = (n + KM_SONGS_PER_WAVE - 1) / KM_SONGS_PER_WAVE;
-    p.assign_waves = pieces >= (uint64_t)8 * cus ? 4u : 1u;
-    p.assign_grid = (uint32_t)((pieces + p.assign_waves - 1) / p.assign_waves);
+    const ScanFill f = scan_fill((n + KM_SONGS_PER_WAVE - 1) / KM_SONGS_PER_WAVE, n_cus);
+    p.assign_waves = f.waves;
+    p.assign_grid = f.grid;
     // the sort: chunks of at least 256 songs, as many as keep the histogram table K x W within 2^21 words
     uint64_t W = std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (1ull << 21) / std::max<uint32_t>(K, 1u)));
     W = std::min<uint64_t>(W, 1u << 20);
@@ -324,19 +323,10 @@ void launch_kmeans_assign(const float* X, uint32_t n, const float* C, uint32_t K
                           hipStream_t st) {
     if (n == 0) return;
     const dim3 grid(p.assign_grid), block(64u * p.assign_waves);
-#define KM_GO(DD, MM, DG) hipLaunchKernelGGL((kmeans_assign_kernel<DD, MM, DG>), grid, block, 0, st, X, n, C, K, d, metric, M, labels, \
-                                             dist, changed, nan_flag)
-#define KM_D(DD)                                                        \
-    do {                                                                \
-        if (metric == METRIC_EUCLIDEAN) KM_GO(DD, METRIC_EUCLIDEAN, false); \
-        else if (m_is_diag) KM_GO(DD, METRIC_MAHALANOBIS, true);        \
-        else KM_GO(DD, METRIC_MAHALANOBIS, false);                      \
-    } while (0)
-    if (d == 23) KM_D(23);
-    else if (d == 20) KM_D(20);
-    else KM_GO(0, METRIC_EUCLIDEAN, false);  // (the metric is a run-time argument of the generic path)
-#undef KM_D
-#undef KM_GO
+    for_metric_form<false>(d, metric, m_is_diag, [&](auto D, auto M_, auto G) {
+        hipLaunchKernelGGL((kmeans_assign_kernel<D(), M_(), G()>), grid, block, 0, st, X, n, C, K, d, metric, M, labels, dist, changed,
+                           nan_flag);
+    });
 }
 
 void launch_kmeans_hist(const uint32_t* labels, uint32_t n, uint32_t K, const KmeansPlan& p, uint32_t* hist, hipStream_t st) {

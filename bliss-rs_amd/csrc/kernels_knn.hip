@@ -259,7 +259,7 @@ KnnPlan knn_plan(uint64_t q, uint64_t n, uint32_t k, int n_cus) {
     // the queries are spread evenly over that many full rounds (100 000 queries, 32 each: 3125 workgroups = 6.1 rounds of 512
     // take the time of 7; 28 each fill 7 rounds)
     {
-        const uint64_t slots = (uint64_t)(n_cus > 0 ? n_cus : 256) * (p.cap <= 256 ? 2 : 1);
+        const uint64_t slots = (uint64_t)cus_or_default(n_cus) * (p.cap <= 256 ? 2 : 1);
         const uint64_t rounds = ((q + p.qb - 1) / p.qb + slots - 1) / slots;
         const uint64_t even = (q + rounds * slots - 1) / (rounds * slots);  // queries per workgroup that fill the rounds
         p.qb = (uint32_t)std::min<uint64_t>(p.qb, std::max<uint64_t>(4, (even + 3) / 4 * 4));  // whole rows per wavefront
@@ -267,7 +267,7 @@ KnnPlan knn_plan(uint64_t q, uint64_t n, uint32_t k, int n_cus) {
     const uint64_t n_qb = (q + p.qb - 1) / p.qb;
     const uint64_t n_blocks = (n + KNN_COLS - 1) / KNN_COLS;
     // few queries: several workgroups share a query's candidates (at least eight blocks each) until the device has ~4 per CU
-    const uint64_t want = (uint64_t)4 * (uint64_t)(n_cus > 0 ? n_cus : 256);
+    const uint64_t want = (uint64_t)4 * cus_or_default(n_cus);
     uint64_t split = n_qb ? want / n_qb : 1;
     split = std::min<uint64_t>(split, (n_blocks + 7) / 8);
     split = std::max<uint64_t>(split, 1);
@@ -278,37 +278,20 @@ KnnPlan knn_plan(uint64_t q, uint64_t n, uint32_t k, int n_cus) {
     return p;
 }
 
-template <int D, int KEYS>
-static void scan_d(const float* Q, uint64_t q, const float* X, uint32_t n, uint32_t d, int metric, const float* M, int diag,
-                   const uint32_t* skip, uint32_t k, const KnnPlan& p, unsigned long long* part, uint32_t* nan_flag,
-                   uint32_t* bad_flag, hipStream_t st) {
-    const dim3 grid(p.grid_qb * p.n_split);
-#define KNN_GO(DD, MM, DG) hipLaunchKernelGGL((knn_scan_kernel<DD, MM, DG, KEYS>), grid, dim3(256), 0, st, Q, q, X, n, d, metric, M, skip, \
-                                              k, p.cap, p.qb, p.n_split, p.blocks_per_split, part, nan_flag, bad_flag)
-    if constexpr (D == 0) {
-        KNN_GO(0, METRIC_EUCLIDEAN, false);  // (the metric is a run-time argument of the generic path)
-    } else {
-        if (metric == METRIC_EUCLIDEAN) KNN_GO(D, METRIC_EUCLIDEAN, false);
-        else if (metric == METRIC_COSINE) KNN_GO(D, METRIC_COSINE, false);
-        else if (diag) KNN_GO(D, METRIC_MAHALANOBIS, true);
-        else KNN_GO(D, METRIC_MAHALANOBIS, false);
-    }
-#undef KNN_GO
-}
-
 void launch_knn_scan(const float* Q, uint64_t q, const float* X, uint32_t n, uint32_t d, int metric, const float* M,
                      int m_is_diag, const uint32_t* skip, uint32_t k, const KnnPlan& p, unsigned long long* part,
                      uint32_t* nan_flag, uint32_t* bad_flag, hipStream_t st) {
-    const bool small = p.cap <= 256;
-#define KNN_D(DD)                                                                                                          \
-    do {                                                                                                                   \
-        if (small) scan_d<DD, KNN_KEYS_SMALL>(Q, q, X, n, d, metric, M, m_is_diag, skip, k, p, part, nan_flag, bad_flag, st); \
-        else scan_d<DD, KNN_KEYS_BIG>(Q, q, X, n, d, metric, M, m_is_diag, skip, k, p, part, nan_flag, bad_flag, st);       \
-    } while (0)
-    if (d == 23) KNN_D(23);
-    else if (d == 20) KNN_D(20);
-    else KNN_D(0);
-#undef KNN_D
+    const dim3 grid(p.grid_qb * p.n_split);
+    const auto scan = [&](auto D_, auto KEYS) {
+        for_metric_form<true>(D_, metric, m_is_diag, [&](auto D, auto M_, auto G) {
+            hipLaunchKernelGGL((knn_scan_kernel<D(), M_(), G(), decltype(KEYS)::value>), grid, dim3(256), 0, st, Q, q, X, n, d, metric, M,
+                               skip, k, p.cap, p.qb, p.n_split, p.blocks_per_split, part, nan_flag, bad_flag);
+        });
+    };
+    with_d(d, [&](auto D) {
+        if (p.cap <= 256) scan(D, std::integral_constant<int, KNN_KEYS_SMALL>{});
+        else scan(D, std::integral_constant<int, KNN_KEYS_BIG>{});
+    });
 }
 
 void launch_knn_merge(const unsigned long long* part, uint64_t q, uint32_t k, const KnnPlan& p, uint32_t* idx, float* dist,

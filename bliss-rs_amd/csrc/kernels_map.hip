@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "internal.hpp"
+#include "launch_forms.hpp"
 
 namespace bg {
 
@@ -223,7 +224,7 @@ __global__ __launch_bounds__(MAP_TILE) void map_update_kernel(MapArgs a, uint32_
 // with less than one tile of j, at most MAP_MAX_COL_GROUPS.  Once the rows alone are that many the answer is 1, so the partials
 // (24 bytes per row and group) never pass 24 * 2 * 256 * 4 * n_cus bytes: 12 MiB on 256 CUs.
 uint32_t map_plan_col_groups(uint64_t n, int n_cus) {
-    const uint64_t cus = (uint64_t)(n_cus > 0 ? n_cus : 256);
+    const uint64_t cus = cus_or_default(n_cus);
     const uint64_t blocks = (n + MAP_TILE - 1) / MAP_TILE;
     if (blocks <= 1) return 1;
     const uint64_t want = (4 * cus + blocks - 1) / blocks;

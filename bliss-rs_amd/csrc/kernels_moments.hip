@@ -33,6 +33,7 @@
 
 #include "device_utils.hpp"
 #include "internal.hpp"
+#include "launch_forms.hpp"
 
 namespace bg {
 
@@ -369,32 +370,26 @@ void launch_moments_plan(const uint32_t* arow_off, uint32_t n, uint32_t K, const
 
 void launch_moments_sum(const MomentsArgs& a, const MomentsPlan& p, double* part, hipStream_t st) {
     const dim3 grid((p.items[0] + 3u) / 4u), block(256);
-#define MO_GO(DD) hipLaunchKernelGGL((moments_sum_kernel<DD>), grid, block, 0, st, a.X, a.arow, a.arow_off, a.off, a.labels, a.n, a.K, \
-                                     a.d, part, a.flags)
-    if (a.d == 23) MO_GO(23);
-    else if (a.d == 20) MO_GO(20);
-    else MO_GO(0);
-#undef MO_GO
+    with_d(a.d, [&](auto D) {
+        hipLaunchKernelGGL((moments_sum_kernel<D()>), grid, block, 0, st, a.X, a.arow, a.arow_off, a.off, a.labels, a.n, a.K, a.d, part,
+                           a.flags);
+    });
 }
 
 void launch_moments_m2(const MomentsArgs& a, const MomentsPlan& p, double* part, bool extrema, hipStream_t st) {
     const dim3 grid((p.items[0] + 3u) / 4u), block(256);
     uint32_t *kmin = extrema ? a.key_min : nullptr, *kmax = extrema ? a.key_max : nullptr;
-#define MO_GO(DD) hipLaunchKernelGGL((moments_m2_kernel<DD>), grid, block, 0, st, a.X, a.arow, a.arow_off, a.off, a.mean, a.n, a.K, a.d, \
-                                     part, kmin, kmax, a.flags)
-    if (a.d == 23) MO_GO(23);
-    else if (a.d == 20) MO_GO(20);
-    else MO_GO(0);
-#undef MO_GO
+    with_d(a.d, [&](auto D) {
+        hipLaunchKernelGGL((moments_m2_kernel<D()>), grid, block, 0, st, a.X, a.arow, a.arow_off, a.off, a.mean, a.n, a.K, a.d, part, kmin,
+                           kmax, a.flags);
+    });
 }
 
 void launch_moments_scatter(const MomentsArgs& a, const MomentsPlan& p, double* part, hipStream_t st) {
     const dim3 grid((p.blocks[0] + 3u) / 4u), block(256);
-#define MO_GO(DD) hipLaunchKernelGGL((moments_scatter_kernel<DD>), grid, block, 0, st, a.X, a.labels, a.mean, a.n, a.K, a.d, part, a.flags)
-    if (a.d == 23) MO_GO(23);
-    else if (a.d == 20) MO_GO(20);
-    else MO_GO(0);
-#undef MO_GO
+    with_d(a.d, [&](auto D) {
+        hipLaunchKernelGGL((moments_scatter_kernel<D()>), grid, block, 0, st, a.X, a.labels, a.mean, a.n, a.K, a.d, part, a.flags);
+    });
 }
 
 void launch_moments_reduce(const double* in, const uint32_t* in_off, uint32_t in_n, double* out, const uint32_t* out_off,

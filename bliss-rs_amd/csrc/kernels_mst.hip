@@ -269,17 +269,15 @@ __global__ __launch_bounds__(256) void mst_pick_kernel(const MstArgs a) {
 
 MstPlan mst_plan(uint64_t n, int n_cus, uint32_t col_groups, uint64_t ws_limit) {
     MstPlan p{};
-    const uint32_t cus = (uint32_t)(n_cus > 0 ? n_cus : 256);
-    // as the chamfer scan: four wavefronts share a tile when there are enough songs to give every CU two such workgroups
-    const uint64_t pieces = (n + MS_SONGS_PER_WAVE - 1) / MS_SONGS_PER_WAVE;
-    p.waves = pieces >= (uint64_t)8 * cus ? 4u : 1u;
-    p.grid = (uint32_t)std::max<uint64_t>(1, (pieces + p.waves - 1) / p.waves);
-    // column groups: enough for about 32 wavefronts per CU, none with fewer than 64 rows
+    const ScanFill f = scan_fill((n + MS_SONGS_PER_WAVE - 1) / MS_SONGS_PER_WAVE, n_cus);  // pieces of 256 positions
+    p.waves = f.waves;
+    p.grid = std::max<uint32_t>(1u, f.grid);
+    // column groups: what fills the device, none with fewer than 64 rows
     const uint64_t in_one = (uint64_t)p.grid * p.waves;
-    uint64_t Y = col_groups ? col_groups : std::min<uint64_t>((32ull * cus + in_one - 1) / in_one, std::max<uint64_t>(1, n / 64));
+    uint64_t Y = col_groups ? col_groups : std::min<uint64_t>(fill_col_groups(f.cus, in_one), std::max<uint64_t>(1, n / 64));
     Y = std::max<uint64_t>(1, std::min<uint64_t>(Y, std::max<uint64_t>(1, n)));
     p.Y = (uint32_t)std::min<uint64_t>(Y, 65535);
-    p.pick_grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 8ull * cus));
+    p.pick_grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 8ull * f.cus));
     // flags u32[4] | order u32[n] | cpos u32[n] | comp_w u32[n] | part_w u32[Y][n] | part_j u32[Y][n] | comp_uv u64[n]
     p.bytes = 16 + (3 + 2 * (uint64_t)p.Y) * n * 4 + 8 + n * 8;
     p.fits = p.bytes <= ws_limit;
@@ -289,18 +287,9 @@ MstPlan mst_plan(uint64_t n, int n_cus, uint32_t col_groups, uint64_t ws_limit) 
 void launch_mst_scan(const MstArgs& a, int m_is_diag, const MstPlan& p, hipStream_t st) {
     if (a.n == 0) return;
     const dim3 grid(p.grid, a.Y), block(64u * p.waves);
-#define MS_GO(DD, MM, DG) hipLaunchKernelGGL((mst_scan_kernel<DD, MM, DG>), grid, block, 0, st, a)
-#define MS_D(DD)                                                             \
-    do {                                                                     \
-        if (a.metric == METRIC_EUCLIDEAN) MS_GO(DD, METRIC_EUCLIDEAN, false); \
-        else if (m_is_diag) MS_GO(DD, METRIC_MAHALANOBIS, true);             \
-        else MS_GO(DD, METRIC_MAHALANOBIS, false);                           \
-    } while (0)
-    if (a.d == 23) MS_D(23);
-    else if (a.d == 20) MS_D(20);
-    else MS_GO(0, METRIC_EUCLIDEAN, false);  // (the metric is a run-time argument of the generic path)
-#undef MS_D
-#undef MS_GO
+    for_metric_form<false>(a.d, a.metric, m_is_diag, [&](auto D, auto M, auto G) {
+        hipLaunchKernelGGL((mst_scan_kernel<D(), M(), G()>), grid, block, 0, st, a);
+    });
 }
 
 void launch_mst_pick(MstArgs a, uint32_t phase, const MstPlan& p, hipStream_t st) {

@@ -356,43 +356,30 @@ __global__ __launch_bounds__(256) void pairwise_generic_kernel(const float* __re
     out[i * ld_out + j] = res;
 }
 
-template <int D>
-static void launch_d(const float* A, uint64_t n, const float* B, uint64_t m, int metric, const float* M, int diag,
-                     float* out, uint64_t ld, hipStream_t st) {
-    dim3 grid((uint32_t)((m + PW_COLS - 1) / PW_COLS), (uint32_t)((n + (uint64_t)PW_ROWS * PW_RT - 1) / ((uint64_t)PW_ROWS * PW_RT)));
-    if (A == B && n == m) {  // self-distance matrix: upper block triangle + mirrored stores
-        if (metric == METRIC_EUCLIDEAN)
-            hipLaunchKernelGGL((pairwise_kernel<D, METRIC_EUCLIDEAN, false, true>), grid, dim3(256), 0, st, A, n, B, m, M, out, ld);
-        else if (metric == METRIC_COSINE)
-            hipLaunchKernelGGL((pairwise_kernel<D, METRIC_COSINE, false, true>), grid, dim3(256), 0, st, A, n, B, m, M, out, ld);
-        else if (diag)
-            hipLaunchKernelGGL((pairwise_kernel<D, METRIC_MAHALANOBIS, true, true>), grid, dim3(256), 0, st, A, n, B, m, M, out, ld);
-        else
-            hipLaunchKernelGGL((pairwise_kernel<D, METRIC_MAHALANOBIS, false, true>), grid, dim3(256), 0, st, A, n, B, m, M, out, ld);
-        return;
-    }
-    if (metric == METRIC_EUCLIDEAN)
-        hipLaunchKernelGGL((pairwise_kernel<D, METRIC_EUCLIDEAN, false>), grid, dim3(256), 0, st, A, n, B, m, M, out, ld);
-    else if (metric == METRIC_COSINE)
-        hipLaunchKernelGGL((pairwise_kernel<D, METRIC_COSINE, false>), grid, dim3(256), 0, st, A, n, B, m, M, out, ld);
-    else if (diag)
-        hipLaunchKernelGGL((pairwise_kernel<D, METRIC_MAHALANOBIS, true>), grid, dim3(256), 0, st, A, n, B, m, M, out, ld);
-    else
-        hipLaunchKernelGGL((pairwise_kernel<D, METRIC_MAHALANOBIS, false>), grid, dim3(256), 0, st, A, n, B, m, M, out, ld);
-}
-
 void launch_pairwise(const float* A, uint64_t n, const float* B, uint64_t m, uint32_t d, int metric, const float* M,
                      int m_is_diag, float* out, uint64_t ld_out, hipStream_t st) {
     if (n == 0 || m == 0) return;
-    // grid.y is limited to 65535 row tiles (8.3 M rows); larger problems are sliced by the caller
-    if (d == 23) launch_d<23>(A, n, B, m, metric, M, m_is_diag, out, ld_out, st);
-    else if (d == 20) launch_d<20>(A, n, B, m, metric, M, m_is_diag, out, ld_out, st);
-    else
-        for (uint64_t r0 = 0; r0 < n; r0 += 65535) {  // grid.y <= 65535
-            const uint64_t rows = (n - r0 < 65535) ? n - r0 : 65535;
-            hipLaunchKernelGGL(pairwise_generic_kernel, dim3((uint32_t)((m + 255) / 256), (uint32_t)rows), dim3(256), 0,
-                               st, A + r0 * d, rows, B, m, d, metric, M, out + r0 * ld_out, ld_out);
+    with_d(d, [&](auto D) {
+        if constexpr (decltype(D)::value == 0) {
+            for (uint64_t r0 = 0; r0 < n; r0 += 65535) {  // grid.y <= 65535
+                const uint64_t rows = (n - r0 < 65535) ? n - r0 : 65535;
+                hipLaunchKernelGGL(pairwise_generic_kernel, dim3((uint32_t)((m + 255) / 256), (uint32_t)rows), dim3(256), 0,
+                                   st, A + r0 * d, rows, B, m, d, metric, M, out + r0 * ld_out, ld_out);
+            }
+        } else {
+            // grid.y is limited to 65535 row tiles (8.3 M rows); larger problems are sliced by the caller
+            const dim3 grid((uint32_t)((m + PW_COLS - 1) / PW_COLS),
+                            (uint32_t)((n + (uint64_t)PW_ROWS * PW_RT - 1) / ((uint64_t)PW_ROWS * PW_RT)));
+            const auto launch = [&](auto SELF) {
+                with_metric<true>(metric, m_is_diag, [&](auto M_, auto G) {
+                    hipLaunchKernelGGL((pairwise_kernel<decltype(D)::value, M_(), G(), decltype(SELF)::value>), grid, dim3(256), 0, st, A,
+                                       n, B, m, M, out, ld_out);
+                });
+            };
+            if (A == B && n == m) launch(std::true_type{});  // self-distance matrix: upper block triangle + mirrored stores
+            else launch(std::false_type{});
         }
+    });
 }
 
 }  // namespace bg

@@ -334,19 +334,9 @@ __global__ __launch_bounds__(64) void pam_td_kernel(const float* __restrict__ d1
 void launch_pam_scan(const PamArgs& a, int m_is_diag, const SilhouettePlan& p, hipStream_t st) {
     if (a.q == 0 || a.n == 0) return;
     const dim3 grid(p.grid, p.Y), block(64u * p.waves);
-#define PAM_GO(DD, MM, DG) hipLaunchKernelGGL((pam_scan_kernel<DD, MM, DG>), grid, block, 0, st, a)
-#define PAM_D(DD)                                                             \
-    do {                                                                      \
-        if (a.metric == METRIC_EUCLIDEAN) PAM_GO(DD, METRIC_EUCLIDEAN, false); \
-        else if (a.metric == METRIC_COSINE) PAM_GO(DD, METRIC_COSINE, false);  \
-        else if (m_is_diag) PAM_GO(DD, METRIC_MAHALANOBIS, true);             \
-        else PAM_GO(DD, METRIC_MAHALANOBIS, false);                           \
-    } while (0)
-    if (a.d == 23) PAM_D(23);
-    else if (a.d == 20) PAM_D(20);
-    else PAM_GO(0, METRIC_EUCLIDEAN, false);  // (the metric is a run-time argument of the generic path)
-#undef PAM_D
-#undef PAM_GO
+    for_metric_form<true>(a.d, a.metric, m_is_diag, [&](auto D, auto M, auto G) {
+        hipLaunchKernelGGL((pam_scan_kernel<D(), M(), G()>), grid, block, 0, st, a);
+    });
 }
 
 void launch_pam_fold(const PamArgs& a, hipStream_t st) {

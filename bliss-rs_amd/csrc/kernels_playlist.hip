@@ -15,6 +15,7 @@
 // u64 minimum is the first minimum in pool order (Vec::remove keeps the relative order of the pool).
 #include "device_utils.hpp"
 #include "internal.hpp"
+#include "launch_forms.hpp"
 #include "playlist_math.hpp"
 
 namespace bg {
@@ -569,22 +570,18 @@ __global__ __launch_bounds__(256) void dedup_walk_kernel(const float* __restrict
 void launch_dedup_next(const float* x, uint64_t n, uint32_t d, const uint32_t* seq, uint32_t len, const uint32_t* meta,
                        int metric, const float* M, float thr, uint32_t* next, uint32_t* bad, hipStream_t st) {
     const dim3 grid((len + 255u) / 256u);
-#define DD(DD_D) hipLaunchKernelGGL((dedup_next_kernel<DD_D>), grid, dim3(256), 0, st, x, n, d, seq, len, meta, metric, M, thr, next, bad)
-    if (d == 23) DD(23);
-    else if (d == 20) DD(20);
-    else DD(0);
-#undef DD
+    with_d(d, [&](auto D) {
+        hipLaunchKernelGGL((dedup_next_kernel<D()>), grid, dim3(256), 0, st, x, n, d, seq, len, meta, metric, M, thr, next, bad);
+    });
 }
 
 void launch_dedup_walk(const float* x, uint64_t n, uint32_t d, const uint32_t* seq, uint32_t len, const uint32_t* meta,
                        int metric, const float* M, float thr, const uint32_t* next, uint32_t* kept, uint64_t* n_kept,
                        uint32_t* nan_flag, uint32_t* bad, hipStream_t st) {
-#define DD(DD_D) hipLaunchKernelGGL((dedup_walk_kernel<DD_D>), dim3(1), dim3(256), 0, st, x, n, d, seq, len, meta, metric, M, thr, \
-                                    next, kept, n_kept, nan_flag, bad)
-    if (d == 23) DD(23);
-    else if (d == 20) DD(20);
-    else DD(0);
-#undef DD
+    with_d(d, [&](auto D) {
+        hipLaunchKernelGGL((dedup_walk_kernel<D()>), dim3(1), dim3(256), 0, st, x, n, d, seq, len, meta, metric, M, thr, next, kept, n_kept,
+                           nan_flag, bad);
+    });
 }
 
 }  // namespace bg

@@ -352,29 +352,14 @@ void launch_radio_ban(const RadioArgs& a, uint32_t t, hipStream_t st) {
                        a.ban, a.ban_cnt);
 }
 
-template <int D>
-static void radio_step_d(const RadioArgs& a, uint32_t t, const ChainPlan& p, hipStream_t st) {
-    const dim3 grid(p.grid_cb * p.n_split);
-#define RD_GO(DD, MM, DG)                                                                                                          \
-    hipLaunchKernelGGL((radio_step_kernel<DD, MM, DG>), grid, dim3(256), 0, st, a.X, a.n, a.d, a.metric, a.M, a.from, a.skip, a.labels, \
-                       a.rules, a.ban, a.ban_cnt, a.nearest, a.n_radios, a.k, t, p.qb, p.n_split, p.blocks_per_split, a.idx, a.dist, \
-                       a.best, a.nan_flag)
-    if constexpr (D == 0) {
-        RD_GO(0, METRIC_EUCLIDEAN, false);  // (the metric is a run-time argument of the generic path)
-    } else {
-        if (a.metric == METRIC_EUCLIDEAN) { RD_GO(D, METRIC_EUCLIDEAN, false); }
-        else if (a.metric == METRIC_COSINE) { RD_GO(D, METRIC_COSINE, false); }
-        else if (a.m_is_diag) { RD_GO(D, METRIC_MAHALANOBIS, true); }
-        else { RD_GO(D, METRIC_MAHALANOBIS, false); }
-    }
-#undef RD_GO
-}
-
 void launch_radio_step(const RadioArgs& a, uint32_t t, const ChainPlan& p, hipStream_t st) {
     if (a.n_radios == 0 || a.n == 0) return;
-    if (a.d == 23) radio_step_d<23>(a, t, p, st);
-    else if (a.d == 20) radio_step_d<20>(a, t, p, st);
-    else radio_step_d<0>(a, t, p, st);
+    const dim3 grid(p.grid_cb * p.n_split);
+    for_metric_form<true>(a.d, a.metric, a.m_is_diag, [&](auto D, auto M, auto G) {
+        hipLaunchKernelGGL((radio_step_kernel<D(), M(), G()>), grid, dim3(256), 0, st, a.X, a.n, a.d, a.metric, a.M, a.from, a.skip, a.labels,
+                           a.rules, a.ban, a.ban_cnt, a.nearest, a.n_radios, a.k, t, p.qb, p.n_split, p.blocks_per_split, a.idx, a.dist,
+                           a.best, a.nan_flag);
+    });
     if (p.n_split > 1)
         hipLaunchKernelGGL(radio_put_kernel, dim3((a.n_radios + 255u) / 256u), dim3(256), 0, st, a.best, a.n_radios, a.k, t, a.idx,
                            a.dist);

@@ -309,46 +309,27 @@ __global__ __launch_bounds__(256) void knn_occurrence_lds_kernel(const uint32_t*
     if (bad) atomicOr(bad_flag, 1u);
 }
 
-template <int D, int KEYS>
-static void scaled_scan_d(const float* Q, uint64_t q, const float* qscale, const float* X, uint32_t n, const float* cscale, uint32_t d,
-                          int metric, const float* M, int diag, const uint32_t* skip, uint32_t k, const KnnPlan& p,
-                          unsigned long long* part, uint32_t* nan_flag, uint32_t* bad_flag, uint32_t* scale_flag, hipStream_t st) {
-    const dim3 grid(p.grid_qb * p.n_split);
-#define SKNN_GO(DD, MM, DG)                                                                                                         \
-    hipLaunchKernelGGL((scaled_knn_scan_kernel<DD, MM, DG, KEYS>), grid, dim3(256), 0, st, Q, q, qscale, X, n, cscale, d, metric, M, \
-                       skip, k, p.cap, p.qb, p.n_split, p.blocks_per_split, part, nan_flag, bad_flag, scale_flag)
-    if constexpr (D == 0) {
-        SKNN_GO(0, METRIC_EUCLIDEAN, false);  // (the metric is a run-time argument of the generic path)
-    } else {
-        if (metric == METRIC_EUCLIDEAN) SKNN_GO(D, METRIC_EUCLIDEAN, false);
-        else if (metric == METRIC_COSINE) SKNN_GO(D, METRIC_COSINE, false);
-        else if (diag) SKNN_GO(D, METRIC_MAHALANOBIS, true);
-        else SKNN_GO(D, METRIC_MAHALANOBIS, false);
-    }
-#undef SKNN_GO
-}
-
 void launch_scaled_knn_scan(const float* Q, uint64_t q, const float* qscale, const float* X, uint32_t n, const float* cscale,
                             uint32_t d, int metric, const float* M, int m_is_diag, const uint32_t* skip, uint32_t k,
                             const KnnPlan& p, unsigned long long* part, uint32_t* nan_flag, uint32_t* bad_flag,
                             uint32_t* scale_flag, hipStream_t st) {
-    const bool small = p.cap <= 256;
-#define SKNN_D(DD)                                                                                                             \
-    do {                                                                                                                       \
-        if (small) scaled_scan_d<DD, KNN_KEYS_SMALL>(Q, q, qscale, X, n, cscale, d, metric, M, m_is_diag, skip, k, p, part,    \
-                                                     nan_flag, bad_flag, scale_flag, st);                                     \
-        else scaled_scan_d<DD, KNN_KEYS_BIG>(Q, q, qscale, X, n, cscale, d, metric, M, m_is_diag, skip, k, p, part, nan_flag,  \
-                                             bad_flag, scale_flag, st);                                                       \
-    } while (0)
-    if (d == 23) SKNN_D(23);
-    else if (d == 20) SKNN_D(20);
-    else SKNN_D(0);
-#undef SKNN_D
+    const dim3 grid(p.grid_qb * p.n_split);
+    const auto scan = [&](auto D_, auto KEYS) {
+        for_metric_form<true>(D_, metric, m_is_diag, [&](auto D, auto M_, auto G) {
+            hipLaunchKernelGGL((scaled_knn_scan_kernel<D(), M_(), G(), decltype(KEYS)::value>), grid, dim3(256), 0, st, Q, q, qscale, X, n,
+                               cscale, d, metric, M, skip, k, p.cap, p.qb, p.n_split, p.blocks_per_split, part, nan_flag, bad_flag,
+                               scale_flag);
+        });
+    };
+    with_d(d, [&](auto D) {
+        if (p.cap <= 256) scan(D, std::integral_constant<int, KNN_KEYS_SMALL>{});
+        else scan(D, std::integral_constant<int, KNN_KEYS_BIG>{});
+    });
 }
 
 void launch_knn_occurrence(const uint32_t* idx, uint64_t entries, uint32_t n, uint32_t* count, uint32_t* bad_flag, bool lds,
                            int n_cus, hipStream_t st) {
-    const uint64_t cus = (uint64_t)(n_cus > 0 ? n_cus : 256);
+    const uint64_t cus = cus_or_default(n_cus);
     if (lds && n) {  // a workgroup per CU and 4 096 entries at least: every workgroup pays n / OCC_WINDOW passes
         const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(cus * 2, (entries + 4095) / 4096));
         hipLaunchKernelGGL(knn_occurrence_lds_kernel, dim3(grid), dim3(256), 0, st, idx, entries, n, count, bad_flag);

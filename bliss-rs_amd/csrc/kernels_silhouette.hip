@@ -265,16 +265,12 @@ __global__ __launch_bounds__(256) void silhouette_finish_kernel(const Silhouette
 
 SilhouettePlan silhouette_plan(uint64_t q, uint32_t K, int n_cus, uint32_t col_groups) {
     SilhouettePlan p{};
-    const uint32_t cus = (uint32_t)(n_cus > 0 ? n_cus : 256);
-    // as the k-means assignment: four wavefronts share a tile when there are enough scored songs to give every CU two such
-    // workgroups; fewer run one wavefront per workgroup so that their 256-song pieces spread over the CUs
-    const uint64_t pieces = (q + SIL_SONGS_PER_WAVE - 1) / SIL_SONGS_PER_WAVE;
-    p.waves = pieces >= (uint64_t)8 * cus ? 4u : 1u;
-    p.grid = (uint32_t)((pieces + p.waves - 1) / p.waves);
-    // column groups: enough of them for about 32 wavefronts per CU -- four rounds of the eight the registers admit, which
-    // evens out the groups' unequal rows (measured: DESIGN.md 3.23) --, at most one group per cluster (a cluster is never split)
+    const ScanFill f = scan_fill((q + SIL_SONGS_PER_WAVE - 1) / SIL_SONGS_PER_WAVE, n_cus);  // pieces of 256 scored songs
+    p.waves = f.waves;
+    p.grid = f.grid;
+    // column groups: what fills the device, at most one group per cluster (a cluster is never split)
     const uint64_t in_one = (uint64_t)std::max<uint32_t>(p.grid, 1u) * p.waves;
-    uint64_t Y = col_groups ? col_groups : (32ull * cus + in_one - 1) / in_one;
+    const uint64_t Y = col_groups ? col_groups : fill_col_groups(f.cus, in_one);
     p.Y = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(Y, K));
     return p;
 }
@@ -282,18 +278,9 @@ SilhouettePlan silhouette_plan(uint64_t q, uint32_t K, int n_cus, uint32_t col_g
 void launch_silhouette_scan(const SilhouetteArgs& a, int m_is_diag, const SilhouettePlan& p, hipStream_t st) {
     if (a.q == 0 || a.n == 0) return;
     const dim3 grid(p.grid, p.Y), block(64u * p.waves);
-#define SIL_GO(DD, MM, DG) hipLaunchKernelGGL((silhouette_scan_kernel<DD, MM, DG>), grid, block, 0, st, a)
-#define SIL_D(DD)                                                             \
-    do {                                                                      \
-        if (a.metric == METRIC_EUCLIDEAN) SIL_GO(DD, METRIC_EUCLIDEAN, false); \
-        else if (m_is_diag) SIL_GO(DD, METRIC_MAHALANOBIS, true);             \
-        else SIL_GO(DD, METRIC_MAHALANOBIS, false);                           \
-    } while (0)
-    if (a.d == 23) SIL_D(23);
-    else if (a.d == 20) SIL_D(20);
-    else SIL_GO(0, METRIC_EUCLIDEAN, false);  // (the metric is a run-time argument of the generic path)
-#undef SIL_D
-#undef SIL_GO
+    for_metric_form<false>(a.d, a.metric, m_is_diag, [&](auto D, auto M, auto G) {
+        hipLaunchKernelGGL((silhouette_scan_kernel<D(), M(), G()>), grid, block, 0, st, a);
+    });
 }
 
 void launch_silhouette_finish(const SilhouetteArgs& a, hipStream_t st) {

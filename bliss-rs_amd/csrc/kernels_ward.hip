@@ -249,14 +249,12 @@ __global__ __launch_bounds__(256) void ward_join_kernel(const WardJoinArgs a) {
 
 WardPlan ward_plan(uint64_t m, int n_cus, uint32_t col_groups) {
     WardPlan p{};
-    const uint32_t cus = (uint32_t)(n_cus > 0 ? n_cus : 256);
-    // as the spanning tree's scan: four wavefronts share a tile when there are enough positions to give every CU two such workgroups
-    const uint64_t pieces = (m + WD_POS_PER_WAVE - 1) / WD_POS_PER_WAVE;
-    p.waves = pieces >= (uint64_t)8 * cus ? 4u : 1u;
-    p.grid = (uint32_t)std::max<uint64_t>(1, (pieces + p.waves - 1) / p.waves);
-    // column groups: enough for about 32 wavefronts per CU, none with fewer than 64 positions
+    const ScanFill f = scan_fill((m + WD_POS_PER_WAVE - 1) / WD_POS_PER_WAVE, n_cus);  // pieces of 256 positions
+    p.waves = f.waves;
+    p.grid = std::max<uint32_t>(1u, f.grid);
+    // column groups: what fills the device, none with fewer than 64 positions
     const uint64_t in_one = (uint64_t)p.grid * p.waves;
-    uint64_t Y = col_groups ? col_groups : std::min<uint64_t>((32ull * cus + in_one - 1) / in_one, std::max<uint64_t>(1, m / 64));
+    uint64_t Y = col_groups ? col_groups : std::min<uint64_t>(fill_col_groups(f.cus, in_one), std::max<uint64_t>(1, m / 64));
     Y = std::max<uint64_t>(1, std::min<uint64_t>(Y, std::max<uint64_t>(1, m)));
     p.Y = (uint32_t)std::min<uint64_t>(Y, 65535);
     return p;
@@ -265,22 +263,15 @@ WardPlan ward_plan(uint64_t m, int n_cus, uint32_t col_groups) {
 void launch_ward_scan(const WardArgs& a, int m_is_diag, bool filter, const WardPlan& p, hipStream_t st) {
     if (a.m == 0) return;
     const dim3 grid(p.grid, a.Y), block(64u * p.waves);
-#define WD_GO(DD, MM, DG)                                                                                   \
-    do {                                                                                                    \
-        if (filter) hipLaunchKernelGGL((ward_scan_kernel<DD, MM, DG, true>), grid, block, 0, st, a);        \
-        else hipLaunchKernelGGL((ward_scan_kernel<DD, MM, DG, false>), grid, block, 0, st, a);              \
-    } while (0)
-#define WD_D(DD)                                                             \
-    do {                                                                     \
-        if (a.metric == METRIC_EUCLIDEAN) WD_GO(DD, METRIC_EUCLIDEAN, false); \
-        else if (m_is_diag) WD_GO(DD, METRIC_MAHALANOBIS, true);             \
-        else WD_GO(DD, METRIC_MAHALANOBIS, false);                           \
-    } while (0)
-    if (a.d == 23) WD_D(23);
-    else if (a.d == 20) WD_D(20);
-    else hipLaunchKernelGGL((ward_scan_kernel<0, METRIC_EUCLIDEAN, false, false>), grid, block, 0, st, a);  // (the metric is a run-time argument of the generic path)
-#undef WD_D
-#undef WD_GO
+    for_metric_form<false>(a.d, a.metric, m_is_diag, [&](auto D, auto M, auto G) {
+        if constexpr (D() != 0) {  // (the generic kernel has no filtered form)
+            if (filter) {
+                hipLaunchKernelGGL((ward_scan_kernel<D(), M(), G(), true>), grid, block, 0, st, a);
+                return;
+            }
+        }
+        hipLaunchKernelGGL((ward_scan_kernel<D(), M(), G(), false>), grid, block, 0, st, a);
+    });
 }
 
 void launch_ward_join(const WardJoinArgs& a, hipStream_t st) {

@@ -6,10 +6,10 @@
 #include <type_traits>
 
 #include "device_utils.hpp"
+#include "launch_forms.hpp"
 
 namespace bg {
 
-enum { METRIC_EUCLIDEAN = 0, METRIC_COSINE = 1, METRIC_MAHALANOBIS = 2 };
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 

@@ -53,15 +53,23 @@ def test_chains_abi_surface(bliss):
     assert types("blissgpu_chains") == want
     assert types("blissgpu_chains_device") == ["blissgpu_ctx*"] + want
     assert types("blissgpu_chains_plan") == ["const uint64_t*", "uint64_t", "uint64_t", "uint32_t", "uint64_t", "int*", "uint32_t*"]
-    # the two kernels, once each, at the end of the profiling table
-    src = open(os.path.join(ROOT, "bliss-rs_amd", "csrc", "blissgpu.hip")).read()
-    names = re.findall(r'"(\w+_kernel)"', re.search(r"kKernelNames\[K_COUNT\]\s*=\s*\{(.*?)\};", src, flags=re.S).group(1))
-    assert names.count("chain_step_kernel") == 1 and names.count("chain_walk_kernel") == 1
-    assert names[-2:] == ["chain_step_kernel", "chain_walk_kernel"]
-    ids = re.search(r"enum KernelId : int \{(.*?)K_COUNT", open(os.path.join(ROOT, "bliss-rs_amd", "csrc", "internal.hpp")).read(),
-                    flags=re.S).group(1)
-    ids = re.findall(r"\bK_\w+", re.sub(r"//[^\n]*", "", ids))
-    assert ids[-2:] == ["K_CHAIN_STEP", "K_CHAIN_WALK"] and len(ids) == len(names)
+    # the profiling table: the one list of X(id, "name") entries that the ids, the count and the library's names come from
+    src = open(os.path.join(ROOT, "bliss-rs_amd", "csrc", "internal.hpp")).read()
+    table = re.search(r"#define BLISSGPU_KERNEL_TABLE\(X\)(.*?)\nenum KernelId", src, flags=re.S).group(1)
+    entries = re.findall(r'\bX\((\w+),\s*"(\w+)"\)', table)
+    assert len(entries) == table.count("X(") == lib.blissgpu_profile_kernel_count()
+    lib.blissgpu_profile_kernel_name.restype = C.c_char_p
+    assert [lib.blissgpu_profile_kernel_name(i).decode() for i in range(len(entries))] == [name for _, name in entries]
+    assert len({i for i, _ in entries}) == len(entries) and len({name for _, name in entries}) == len(entries)
+    assert all(re.fullmatch(r"KX?_[A-Z0-9_]+", i) and name.endswith("_kernel") for i, name in entries)
+    # the two kernels where they have always been, and no older id moved: the first 29 names by value
+    assert entries[27] == ("K_CHAIN_STEP", "chain_step_kernel") and entries[28] == ("K_CHAIN_WALK", "chain_walk_kernel")
+    assert [name for _, name in entries[:29]] == [
+        "fft512_kernel", "onset_kernel", "beat_kernel", "stft8192_kernel", "tune_select_kernel", "tune_pass2_kernel",
+        "tune_final_kernel", "chroma_kernel", "summary_kernel", "assemble_kernel", "pairwise_kernel", "set_distance_kernel",
+        "song_to_song_kernel", "synth_kernel", "rolloff_fix_kernel", "dedup_next_kernel", "dedup_walk_kernel", "knn_scan_kernel",
+        "knn_merge_kernel", "forest_walk_kernel", "forest_finish_kernel", "dup_init_kernel", "dup_join_kernel", "dup_flatten_kernel",
+        "group_knn_scan_kernel", "group_knn_merge_kernel", "group_weights_kernel", "chain_step_kernel", "chain_walk_kernel"]
 
 
 def _call(bliss, S, off, X, k, d=None, metric=0, M=None, skip=None, route=AUTO):

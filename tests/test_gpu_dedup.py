@@ -145,6 +145,21 @@ def test_planted_runs_match_oracle(bliss, oracle, which, thr):
     assert np.array_equal(got, want.astype(np.int64))
 
 
+# ---- (b2) the other feature counts (the second packed width, the generic kernels) past one block of 256 positions ----
+@pytest.mark.parametrize("d", [20, 5])
+def test_other_feature_counts_match_oracle(bliss, ctx, oracle, d):
+    rng = np.random.default_rng(40 + d)
+    n, thr = 300, np.float32(0.3)
+    X = rng.standard_normal((n, d)).astype(np.float32)
+    for head, L in ((10, 5), (100, 40), (250, 12)):  # runs of near-copies behind a head song, the last across position 256
+        X[head + 1:head + 1 + L] = X[head] + (0.01 * rng.standard_normal((L, d))).astype(np.float32)
+    diag = np.diag(rng.uniform(0.5, 2.0, d)).astype(np.float32)
+    for metric, M in (("euclidean", None), ("cosine", None), ("mahalanobis", diag)):
+        want = oracle.dedup_playlist(X, thr, metric, M)
+        assert 0.5 * n < len(want) <= n - 57  # the planted copies went, and not everything
+        assert np.array_equal(both(bliss, ctx, X, None, None, metric, M, thr), want.astype(np.int64)), (d, metric)
+
+
 # ---- (c) planted title / artist runs: the oracle's n x n same_meta matrix ----
 def test_title_artist_runs_match_oracle(bliss, ctx, oracle):
     rng = np.random.default_rng(11)

@@ -137,7 +137,7 @@ def spd(d, seed):
     return (A @ A.T + 0.1 * np.eye(d)).astype(np.float32)
 
 
-@pytest.mark.parametrize("d,n,name", [(20, 300, "diagonal"), (20, 300, "full"), (23, 300, "diagonal"), (23, 300, "full"),
+@pytest.mark.parametrize("d,n,name", [(20, 300, "euclidean"), (20, 300, "diagonal"), (20, 300, "full"), (23, 300, "diagonal"), (23, 300, "full"),
                                       (1, 120, "euclidean"), (64, 120, "euclidean"), (64, 120, "full"), (5, 120, "diagonal")])
 def test_metrics_and_feature_counts(bliss, ctx, d, n, name):
     rng = np.random.default_rng(100 + d)

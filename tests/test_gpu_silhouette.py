@@ -154,6 +154,7 @@ CASES = [
     (700, 23, 5, "spd"),
     (1500, 20, 7, "euclidean"),
     (300, 20, 3, "spd"),
+    (300, 20, 3, "weights"),
     (600, 1, 4, "euclidean"),
     (300, 64, 3, "spd"),
     (257, 23, 300, "euclidean"),  # k > n, mostly empty clusters

@@ -114,9 +114,10 @@ def test_the_filter_changes_no_bit(bliss, monkeypatch):
     check_nearest(bliss, grid_input(600), np.random.default_rng(9).integers(1, 4, 600), what="grid with sizes")
     for X in (planted(1000), equal_input(300), twice_input(200), grid_input(600), random_input(700, 20, seed=32)):
         check_tree(bliss, X, what="filter")
-    X = random_input(300, 23, seed=40)
-    check_tree(bliss, X, "mahalanobis", pd_matrix(23, 41, diagonal=True), what="diagonal")
-    check_tree(bliss, X, "mahalanobis", pd_matrix(23, 42), what="full")
+    for d in (20, 23):
+        X = random_input(300, d, seed=40)
+        check_tree(bliss, X, "mahalanobis", pd_matrix(d, 41, diagonal=True), what=("diagonal", d))
+        check_tree(bliss, X, "mahalanobis", pd_matrix(d, 42), what=("full", d))
     bad = X.copy()
     bad[123, 4] = np.nan
     rc, err, out = _raw_tree_call(bad)
