@@ -7,6 +7,8 @@ on a machine without a GPU.
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # BLISSGPU_LIB: developer aid for A/B timing of two builds of the library on the same box (never a CPU path)
 LIB_PATH = os.environ.get("BLISSGPU_LIB") or os.path.join(_HERE, "libblissgpu.so")
@@ -36,6 +38,15 @@ LEARN_CONVERGED, LEARN_MAX_ITER, LEARN_DIVERGED = 0, 1, 2
 COV_OK, COV_NOT_POSITIVE = 0, 1
 MOMENTS_BLOCK = 256
 GROUPS_SYMMETRIC, GROUPS_DIRECTED = 0, 1
+
+# the names the Python API gives those constants (playlist.py binds them as _METRICS, _ROUTES, ...)
+METRICS = {"euclidean": METRIC_EUCLIDEAN, "cosine": METRIC_COSINE, "mahalanobis": METRIC_MAHALANOBIS}
+ROUTES = {"auto": CHAINS_AUTO, "steps": CHAINS_STEPS, "lists": CHAINS_LISTS}  # chain_order
+JOURNEY_MODES = {"chain": JOURNEY_CHAIN, "waypoint": JOURNEY_WAYPOINT}  # journey_order
+GATES = {None: GATE_NONE, "up": GATE_UP, "down": GATE_DOWN}
+GROUP_MODES = {"symmetric": GROUPS_SYMMETRIC, "directed": GROUPS_DIRECTED}  # group_neighbours
+RADIO_MODES = {"chain": RADIO_CHAIN, "nearest": RADIO_NEAREST}  # radio_order
+FORMS = {"diagonal": METRIC_FORM_DIAGONAL, "full": METRIC_FORM_FULL}  # learn_metric
 
 _f32p = C.POINTER(C.c_float)
 _f64p = C.POINTER(C.c_double)
@@ -280,3 +291,68 @@ def check(rc):
         L = lib()
         detail = L.blissgpu_last_error().decode() or L.blissgpu_strerror(rc).decode()
         raise BlissGpuError(rc, detail)
+
+
+# the c_int results that are values, not a status
+_INT_VALUES = frozenset({"blissgpu_default_device_count", "blissgpu_default_device", "blissgpu_node_device_count",
+                         "blissgpu_profile_kernel_count"})
+
+
+def _pointer(name, pos, a, argtype):
+    """The C argument for the numpy array or torch tensor `a` at position `pos` of `name`: its address, once it is known to
+    be C-contiguous and, for a typed pointer argtype, of the pointee's dtype."""
+    is_array = isinstance(a, np.ndarray)
+    if not (a.flags.c_contiguous if is_array else a.is_contiguous()):
+        raise TypeError(f"{name}: argument {pos} is not C-contiguous")
+    if not is_array:
+        return C.c_void_p(a.data_ptr())
+    if argtype is _vp:
+        return a.ctypes.data  # (the plain address: what a `void *` argument has always been given here)
+    want = np.dtype(argtype._type_)
+    if (a.dtype.kind, a.dtype.itemsize) != (want.kind, want.itemsize):
+        raise TypeError(f"{name}: argument {pos} is {a.dtype}, the C argument points to {want}")
+    return a.ctypes.data_as(argtype)
+
+
+def address(a) -> int:
+    """the address of a C-contiguous numpy array, for the two places an address is data and not an argument: a pointer
+    table and the `pcm` field of DecodedSong.  The caller keeps the array alive across the call."""
+    if not a.flags.c_contiguous:
+        raise TypeError("an array whose address is handed to the library must be C-contiguous")
+    return a.ctypes.data
+
+
+def pointer_table(arrays):
+    """`void *table[n]` of the arrays' addresses (blissgpu_*_flac*: one file or one output buffer per song)"""
+    return (C.c_void_p * len(arrays))(*[address(a) for a in arrays])
+
+
+_ndarray = np.ndarray
+_PLAIN = frozenset({int, float, bool, type(None)})  # what most arguments are: passed on without a further look
+_status = {name: res is C.c_int and name not in _INT_VALUES for name, (res, _) in SIGNATURES.items()}  # returns a status?
+
+
+def _arguments(name, args, argtypes):
+    """(the second line is _pointer's commonest case, a contiguous array for a `void *`, without the call)"""
+    return [a if (t := type(a)) in _PLAIN else
+            a.ctypes.data if t is _ndarray and argtypes[i] is _vp and a.flags.c_contiguous else
+            _pointer(name, i, a, argtypes[i]) if isinstance(a, _ndarray) or hasattr(a, "data_ptr") else a
+            for i, a in enumerate(args)]
+
+
+def call_unchecked(name, *args):
+    """`name`(*args) in the library -- the one place a Python object becomes a C argument.  None, Python scalars and ctypes
+    objects pass as they are; a numpy array or a torch tensor becomes its address (`_pointer`: a TypeError instead of a call
+    for a strided array or the wrong dtype).  `args` keeps every array and tensor alive until the function has returned.
+    The function is looked up in lib() at every call: the tests replace lib() or single functions of the library.
+    -> what the function returned."""
+    return getattr(lib(), name)(*_arguments(name, args, SIGNATURES[name][1]))
+
+
+def call(name, *args):
+    """call_unchecked, then check() for the functions that return a status; the others return their value."""
+    out = getattr(lib(), name)(*_arguments(name, args, SIGNATURES[name][1]))
+    if not _status[name]:
+        return out
+    if out != OK:
+        check(out)

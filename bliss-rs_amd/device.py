@@ -7,10 +7,29 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _ffi
+from . import playlist as P
+from ._ffi import FORMS, GATES, GROUP_MODES, JOURNEY_MODES, METRICS, RADIO_MODES, ROUTES
+from .song import DecodingError
 
 
 def _u64(a):
     return np.ascontiguousarray(a, dtype=np.uint64)
+
+
+def _offsets(offsets, rows):
+    """a HOST sequence of G + 1 group offsets over `rows` seed rows -> (uint64 array, G)"""
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1)).astype(np.uint64)
+    assert off.shape[0] >= 1 and int(off[-1]) == rows
+    return off, off.shape[0] - 1
+
+
+def _contig(t):
+    return None if t is None else t.contiguous()
+
+
+def _dptr(t):
+    """the address of a tensor that _ffi.call must not hold to contiguity: pairwise's `out` comes with its row stride"""
+    return C.c_void_p(t.data_ptr())
 
 
 class Context:
@@ -26,7 +45,7 @@ class Context:
         torch.cuda.set_device(device)
         self._L = _ffi.lib()
         h = C.c_void_p()
-        _ffi.check(self._L.blissgpu_ctx_create(device, C.byref(h)))
+        _ffi.call("blissgpu_ctx_create", device, C.byref(h))
         self._h = h
         if use_torch_stream:
             self.bind_current_stream()
@@ -41,33 +60,91 @@ class Context:
         self.torch = torch
         self._L = _ffi.lib()
         h = C.c_void_p()
-        _ffi.check(self._L.blissgpu_default_ctx(int(k), C.byref(h)))
+        _ffi.call("blissgpu_default_ctx", int(k), C.byref(h))
         self._h = h
         self._borrowed = True
-        self.device = self._L.blissgpu_default_device(int(k))
+        self.device = _ffi.call("blissgpu_default_device", int(k))
         return self
 
     def staged_bytes(self) -> int:
         """Bytes of pageable host PCM staged through this context's pinned ring so far (blissgpu_ctx_staged_bytes)."""
-        return int(self._L.blissgpu_ctx_staged_bytes(self._h))
+        return int(_ffi.call("blissgpu_ctx_staged_bytes", self._h))
 
     def bind_current_stream(self):
         """Launch on torch's current stream when it is a real stream; the legacy default stream (handle 0) cannot be
         adopted (NULL means "the context's own stream"), so in that case every call below is ordered against it with
         events instead (`_pre` / `_post`)."""
         s = self.torch.cuda.current_stream(self.device).cuda_stream
-        _ffi.check(self._L.blissgpu_ctx_set_stream(self._h, C.c_void_p(s)))
+        _ffi.call("blissgpu_ctx_set_stream", self._h, C.c_void_p(s))
 
     def _torch_stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
     def _pre(self):
         """the context's stream waits for the inputs torch has queued on its current stream"""
-        _ffi.check(self._L.blissgpu_ctx_wait_stream(self._h, self._torch_stream()))
+        _ffi.call("blissgpu_ctx_wait_stream", self._h, self._torch_stream())
 
     def _post(self):
         """torch's current stream waits for the results queued on the context's stream"""
-        _ffi.check(self._L.blissgpu_ctx_signal_stream(self._h, self._torch_stream()))
+        _ffi.call("blissgpu_ctx_signal_stream", self._h, self._torch_stream())
+
+    def _call(self, name, *args):
+        """`name`(this context, *args) between _pre and _post; _post is not run when the call raises"""
+        self._pre()
+        _ffi.call(name, self._h, *args)
+        self._post()
+
+    def _up_f32(self, a):
+        """a float32 array uploaded to the context's device; a tensor and None as they are"""
+        if a is None or self.torch.is_tensor(a):
+            return a
+        return self.torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.torch.device("cuda", self.device))
+
+    def _up_u32(self, a, what):
+        """indices (labels, rows, queries) -> a flat int32 tensor on the device holding the uint32 bits; None as it is"""
+        torch = self.torch
+        if a is None:
+            return None
+        if torch.is_tensor(a):
+            assert a.is_cuda and a.dtype in (torch.int32, torch.int64), what
+            return a.to(torch.int32).contiguous().reshape(-1)
+        a = np.asarray(a, dtype=np.int64).reshape(-1)
+        if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+            raise ValueError(f"{what} must be non-negative indices")
+        return torch.from_numpy(a.astype(np.uint32).view(np.int32)).to(torch.device("cuda", self.device))
+
+    def _f32_metric(self, M):
+        """the M of the families that also take arrays: uploaded, float32 on the device, contiguous; None as it is"""
+        M = self._up_f32(M)
+        if M is not None:
+            assert M.is_cuda and M.dtype == self.torch.float32
+            M = M.contiguous()
+        return M
+
+    def _rows(self, X):
+        """a float32 [n, d] device tensor, made contiguous"""
+        assert X.is_cuda and X.dtype == self.torch.float32 and X.dim() == 2
+        return X.contiguous()
+
+    def _rows_pair(self, A, X):
+        """two float32 [., d] device tensors over the same d, made contiguous"""
+        torch = self.torch
+        assert A.is_cuda and X.is_cuda and A.dtype == torch.float32 and X.dtype == torch.float32
+        assert A.dim() == 2 and X.dim() == 2 and A.shape[1] == X.shape[1]
+        return A.contiguous(), X.contiguous()
+
+    def _i32_per_row(self, t, rows):
+        """an int32 device tensor with one entry per row (a skip, the meta keys), made contiguous; None as it is"""
+        if t is not None:
+            assert t.is_cuda and t.dtype == self.torch.int32 and t.shape[0] == rows
+            t = t.contiguous()
+        return t
+
+    def _lists(self, q, k, device):
+        """the (idx int32 [q, k], dist float32 [q, k]) result pair of a list family, uninitialised"""
+        torch = self.torch
+        return (torch.empty((q, max(k, 0)), dtype=torch.int32, device=device),
+                torch.empty((q, max(k, 0)), dtype=torch.float32, device=device))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -78,7 +155,7 @@ class Context:
     __del__ = close
 
     def synchronize(self):
-        _ffi.check(self._L.blissgpu_ctx_synchronize(self._h))
+        _ffi.call("blissgpu_ctx_synchronize", self._h)
 
     OPTIONS = {"serial": _ffi.OPT_SERIAL, "tail_mode": _ffi.OPT_TAIL_MODE, "pipeline_chunks": _ffi.OPT_PIPELINE_CHUNKS,
                "cand_budget": _ffi.OPT_CAND_BUDGET, "rolloff_exact_all": _ffi.OPT_ROLLOFF_EXACT_ALL,
@@ -90,18 +167,18 @@ class Context:
 
     def set_option(self, name: str, value: int):
         """Scheduling knobs for the measurement tools and the tests (blissgpu_ctx_set_option)."""
-        _ffi.check(self._L.blissgpu_ctx_set_option(self._h, self.OPTIONS[name], int(value)))
+        _ffi.call("blissgpu_ctx_set_option", self._h, self.OPTIONS[name], int(value))
 
     def set_workspace_limit(self, nbytes: int):
         """Scratch bytes of ONE chunk slot; larger batches stream through the two slots in length-bucketed chunks."""
-        _ffi.check(self._L.blissgpu_ctx_set_workspace_limit(self._h, nbytes))
+        _ffi.call("blissgpu_ctx_set_workspace_limit", self._h, nbytes)
 
     def workspace_limit(self) -> int:
-        return int(self._L.blissgpu_ctx_get_workspace_limit(self._h))
+        return int(_ffi.call("blissgpu_ctx_get_workspace_limit", self._h))
 
     def last_chunks(self) -> int:
         """Chunks the last analyze() call was cut into."""
-        return int(self._L.blissgpu_debug_last_chunks(self._h))
+        return int(_ffi.call("blissgpu_debug_last_chunks", self._h))
 
     # ---- analysis ----
     def analyze(self, pcm, offsets: Sequence[int], lengths: Sequence[int], features_version: int = 2, out=None,
@@ -116,34 +193,22 @@ class Context:
             out = torch.empty((n, d), dtype=torch.float32, device=pcm.device)
         if status is None:
             status = torch.empty((n,), dtype=torch.int32, device=pcm.device)
-        self._pre()
-        _ffi.check(self._L.blissgpu_analyze_batch_device(
-            self._h, C.c_void_p(pcm.data_ptr()), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
-            lengths.ctypes.data_as(C.POINTER(C.c_uint64)), n, features_version, C.c_void_p(out.data_ptr()),
-            C.c_void_p(status.data_ptr())))
-        self._post()
+        self._call("blissgpu_analyze_batch_device", pcm, offsets, lengths, n, features_version, out, status)
         return out, status
 
     def synth_white_noise(self, pcm, offsets, lengths, first_song_index: int = 0, song_index=None):
         """Benchmark input: song i gets generator index first_song_index + i, or song_index[i] when given."""
         offsets, lengths = _u64(offsets), _u64(lengths)
-        self._pre()
         if song_index is None:
-            _ffi.check(self._L.blissgpu_synth_white_noise_device(
-                self._h, C.c_void_p(pcm.data_ptr()), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
-                lengths.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets), first_song_index))
+            self._call("blissgpu_synth_white_noise_device", pcm, offsets, lengths, len(offsets), first_song_index)
         else:
             idx = np.ascontiguousarray(song_index, np.uint32)
-            _ffi.check(self._L.blissgpu_synth_white_noise_indexed_device(
-                self._h, C.c_void_p(pcm.data_ptr()), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
-                lengths.ctypes.data_as(C.POINTER(C.c_uint64)), idx.ctypes.data_as(C.POINTER(C.c_uint32)), len(offsets)))
-        self._post()
+            self._call("blissgpu_synth_white_noise_indexed_device", pcm, offsets, lengths, idx, len(offsets))
 
     def last_tuning(self, n):
         t = np.empty(n, np.float64)
         b = np.empty(n, np.uint32)
-        _ffi.check(self._L.blissgpu_debug_last_tuning(self._h, t.ctypes.data_as(C.POINTER(C.c_double)),
-                                                      b.ctypes.data_as(C.POINTER(C.c_uint32)), n))
+        _ffi.call("blissgpu_debug_last_tuning", self._h, t, b, n)
         return t, b
 
     TAPS = {"centroid": (0, np.float32), "rolloff": (1, np.float32), "flatness": (2, np.float32),
@@ -170,31 +235,23 @@ class Context:
         code, dt = self.TAPS[what]
         n = C.c_uint64()
         probe = np.empty(1, dt)
-        _ffi.check(self._L.blissgpu_debug_fetch(self._h, code, song, C.c_void_p(probe.ctypes.data), 0, C.byref(n)))
+        _ffi.call("blissgpu_debug_fetch", self._h, code, song, probe, 0, C.byref(n))
         out = np.empty(n.value, dt)
         if n.value:
-            _ffi.check(self._L.blissgpu_debug_fetch(self._h, code, song, C.c_void_p(out.ctypes.data), n.value, C.byref(n)))
+            _ffi.call("blissgpu_debug_fetch", self._h, code, song, out, n.value, C.byref(n))
         return out
 
     # ---- distances ----
     def pairwise(self, A, B, metric: str = "euclidean", M=None, out=None):
         torch = self.torch
-        from .playlist import _METRICS
-
         assert A.is_cuda and B.is_cuda and A.dtype == torch.float32 and B.dtype == torch.float32
         A, B = A.contiguous(), B.contiguous()
         n, d = A.shape
         m = B.shape[0]
         if out is None:
             out = torch.empty((n, m), dtype=torch.float32, device=A.device)
-        Mp = None
-        if M is not None:
-            M = M.contiguous()
-            Mp = C.c_void_p(M.data_ptr())
-        self._pre()
-        _ffi.check(self._L.blissgpu_pairwise_device(self._h, C.c_void_p(A.data_ptr()), n, C.c_void_p(B.data_ptr()), m,
-                                                    d, _METRICS[metric], Mp, C.c_void_p(out.data_ptr()), out.stride(0)))
-        self._post()
+        M = _contig(M)
+        self._call("blissgpu_pairwise_device", A, n, B, m, d, METRICS[metric], M, _dptr(out), out.stride(0))
         return out
 
     def pcm_s16_to_f32(self, pcm_s16, out=None):
@@ -204,10 +261,7 @@ class Context:
         pcm_s16 = pcm_s16.contiguous()
         if out is None:
             out = torch.empty(pcm_s16.shape, dtype=torch.float32, device=pcm_s16.device)
-        self._pre()
-        _ffi.check(self._L.blissgpu_pcm_s16_to_f32_device(self._h, C.c_void_p(pcm_s16.data_ptr()), pcm_s16.numel(),
-                                                          C.c_void_p(out.data_ptr())))
-        self._post()
+        self._call("blissgpu_pcm_s16_to_f32_device", pcm_s16, pcm_s16.numel(), out)
         return out
 
     def pcm_downmix(self, pcm, out=None):
@@ -220,10 +274,7 @@ class Context:
         if out is None:
             out = torch.empty((frames,), dtype=torch.float32, device=pcm.device)
         fmt = _ffi.SAMPLE_S16 if pcm.dtype == torch.int16 else _ffi.SAMPLE_F32
-        self._pre()
-        _ffi.check(self._L.blissgpu_pcm_downmix_device(self._h, C.c_void_p(pcm.data_ptr()), fmt, channels, frames,
-                                                       C.c_void_p(out.data_ptr())))
-        self._post()
+        self._call("blissgpu_pcm_downmix_device", pcm, fmt, channels, frames, out)
         return out
 
     def pcm_decode(self, pcm, sample_rate: int, out=None):
@@ -236,21 +287,18 @@ class Context:
         pcm = pcm.contiguous()
         frames = pcm.shape[0]
         channels = 1 if pcm.dim() == 1 else pcm.shape[1]
-        n_out = int(self._L.blissgpu_resampled_len(frames, int(sample_rate)))
+        n_out = int(_ffi.call("blissgpu_resampled_len", frames, int(sample_rate)))
         if out is None:
             out = torch.empty((n_out,), dtype=torch.float32, device=pcm.device)
         assert out.numel() >= n_out
         fmt = {torch.int16: _ffi.SAMPLE_S16, torch.int32: _ffi.SAMPLE_S32, torch.float32: _ffi.SAMPLE_F32}[pcm.dtype]
-        self._pre()
-        _ffi.check(self._L.blissgpu_pcm_decode_device(self._h, C.c_void_p(pcm.data_ptr()), fmt, channels, frames,
-                                                      int(sample_rate), C.c_void_p(out.data_ptr())))
-        self._post()
+        self._call("blissgpu_pcm_decode_device", pcm, fmt, channels, frames, int(sample_rate), out)
         return out[:n_out]
 
     # ---- FLAC decoded on the device ----
     def flac_slow_songs(self) -> int:
         """Songs of this context whose fast frame table was refused and that went through verified mode."""
-        return int(self._L.blissgpu_ctx_flac_slow_songs(self._h))
+        return int(_ffi.call("blissgpu_ctx_flac_slow_songs", self._h))
 
     def flac_decode(self, data, verified: bool = False, return_frames: bool = False):
         """One .flac file (bytes, a uint8 array, or a path) -> (pcm, sample_rate): the decoder output on the device, interleaved
@@ -260,8 +308,6 @@ class Context:
         the fast mode that the device refuses (a frame that does not stop 2 bytes before the next) is replaced by the
         verified one; what that cannot repair raises DecodingError.
         return_frames: also the per-frame (status, end position) tensors and the table, as they came out of THIS mode."""
-        from .song import DecodingError
-
         torch = self.torch
         if isinstance(data, (str, os.PathLike)):
             with open(data, "rb") as f:
@@ -269,21 +315,19 @@ class Context:
         host = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
         n = int(host.size)
         info = np.zeros(_ffi.FLAC_INFO_WORDS, np.uint64)
-        u64p = C.POINTER(C.c_uint64)
         src = host if n else np.zeros(1, np.uint8)
-        if self._L.blissgpu_flac_info(C.c_void_p(src.ctypes.data), n, info.ctypes.data_as(u64p)) != _ffi.OK:
-            raise DecodingError("not a FLAC stream: " + self._L.blissgpu_last_error().decode())
+        if _ffi.call_unchecked("blissgpu_flac_info", src, n, info) != _ffi.OK:
+            raise DecodingError("not a FLAC stream: " + _ffi.call("blissgpu_last_error").decode())
         channels, bps = int(info[1]), int(info[2])
         if not 4 <= bps <= 24:
             raise DecodingError(f"{bps} bits per sample are not supported")
         nf = C.c_uint64(0)
-        self._L.blissgpu_flac_index(C.c_void_p(src.ctypes.data), n, int(verified), info.ctypes.data_as(u64p), None, 0, C.byref(nf))
+        _ffi.call_unchecked("blissgpu_flac_index", src, n, int(verified), info, None, 0, C.byref(nf))
         table = np.zeros((max(1, nf.value), 4), np.uint64)
-        rc = self._L.blissgpu_flac_index(C.c_void_p(src.ctypes.data), n, int(verified), info.ctypes.data_as(u64p),
-                                         table.ctypes.data_as(u64p), nf.value, C.byref(nf))
+        rc = _ffi.call_unchecked("blissgpu_flac_index", src, n, int(verified), info, table, nf.value, C.byref(nf))
         table = table[:nf.value]
         if rc != _ffi.OK and verified:
-            raise DecodingError(self._L.blissgpu_last_error().decode())
+            raise DecodingError(_ffi.call("blissgpu_last_error").decode())
         total = int(info[3])
         dev = f"cuda:{self.device}"
         d_bytes = torch.zeros(((n + 16 + 7) // 8) * 8, dtype=torch.uint8, device=dev)
@@ -291,11 +335,7 @@ class Context:
         pcm = torch.zeros((total, channels), dtype=torch.int32 if bps > 16 else torch.int16, device=dev)
         status = torch.full((max(1, nf.value),), 8, dtype=torch.int32, device=dev)
         end = torch.zeros((max(1, nf.value),), dtype=torch.int64, device=dev)
-        self._pre()
-        _ffi.check(self._L.blissgpu_flac_decode_device(self._h, C.c_void_p(d_bytes.data_ptr()), n, table.ctypes.data_as(u64p), nf.value,
-                                                       info.ctypes.data_as(u64p), C.c_void_p(pcm.data_ptr()),
-                                                       C.c_void_p(status.data_ptr()), C.c_void_p(end.data_ptr())))
-        self._post()
+        self._call("blissgpu_flac_decode_device", d_bytes, n, table, nf.value, info, pcm, status, end)
         status, end = status[:nf.value], end[:nf.value]
         stops = torch.from_numpy((table[:, 0] + table[:, 1]).astype(np.int64)).to(dev) - 2
         # (the last frame runs to the end of the data in the table and may stop earlier: an ID3v1 tag, padding)
@@ -329,11 +369,7 @@ class Context:
         end = end.contiguous()
         assert status.dtype == torch.int32 and end.dtype == torch.int64 and status.numel() >= nf and end.numel() >= nf
         ok = torch.full((max(1, nf),), -2, dtype=torch.int32, device=d_bytes.device)
-        self._pre()
-        _ffi.check(self._L.blissgpu_flac_crc16_device(self._h, C.c_void_p(d_bytes.data_ptr()), int(nbytes),
-                                                      table.ctypes.data_as(C.POINTER(C.c_uint64)), nf, C.c_void_p(status.data_ptr()),
-                                                      C.c_void_p(end.data_ptr()), C.c_void_p(ok.data_ptr())))
-        self._post()
+        self._call("blissgpu_flac_crc16_device", d_bytes, int(nbytes), table, nf, status, end, ok)
         return ok[:nf]
 
     def flac_md5(self, pcm, bps: int) -> str:
@@ -348,10 +384,7 @@ class Context:
         info = np.zeros(_ffi.FLAC_INFO_WORDS, np.uint64)
         info[1], info[2], info[3] = channels, bps, frames
         out = torch.zeros(16, dtype=torch.uint8, device=pcm.device)
-        self._pre()
-        _ffi.check(self._L.blissgpu_flac_md5_device(self._h, C.c_void_p(pcm.data_ptr() if pcm.numel() else 0), info.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                    C.c_void_p(out.data_ptr())))
-        self._post()
+        self._call("blissgpu_flac_md5_device", pcm if pcm.numel() else None, info, out)  # (no pointer for no samples)
         return bytes(out.cpu().numpy().tobytes()).hex()
 
     # ---- playlist ordering on device-resident feature matrices (src/playlist.rs:24-59, 256-326) ----
@@ -361,55 +394,35 @@ class Context:
         seeds, cand = seeds.contiguous(), cand.contiguous()
         if seeds.dim() == 1:
             seeds = seeds[None, :]
-        Mp = None
-        if M is not None:
-            M = M.contiguous()
-            Mp = C.c_void_p(M.data_ptr())
-        return seeds, cand, M, Mp
+        return seeds, cand, _contig(M)
 
     def set_distance(self, seeds, cand, metric: str = "euclidean", M=None):
         """FunctionDistanceMetric::distance of every candidate row to the seed set."""
-        from .playlist import _METRICS
-
-        seeds, cand, M, Mp = self._pl_args(seeds, cand, M)
+        seeds, cand, M = self._pl_args(seeds, cand, M)
         out = self.torch.empty((cand.shape[0],), dtype=self.torch.float32, device=cand.device)
-        self._pre()
-        _ffi.check(self._L.blissgpu_set_distance_device(self._h, C.c_void_p(seeds.data_ptr()), seeds.shape[0],
-                                                        C.c_void_p(cand.data_ptr()), cand.shape[0], cand.shape[1],
-                                                        _METRICS[metric], Mp, C.c_void_p(out.data_ptr())))
-        self._post()
+        self._call("blissgpu_set_distance_device", seeds, seeds.shape[0], cand, cand.shape[0], cand.shape[1], METRICS[metric], M,
+                   out)
         return out
 
     def closest_to_songs(self, seeds, cand, metric: str = "euclidean", M=None, return_distances=False):
         """Indices of the candidates sorted (stably) by distance to the seed set (int64 tensor)."""
-        from .playlist import _METRICS
-
         torch = self.torch
-        seeds, cand, M, Mp = self._pl_args(seeds, cand, M)
+        seeds, cand, M = self._pl_args(seeds, cand, M)
         n = cand.shape[0]
         order = torch.empty((n,), dtype=torch.int32, device=cand.device)
         dist = torch.empty((n,), dtype=torch.float32, device=cand.device)
-        self._pre()
-        _ffi.check(self._L.blissgpu_closest_to_songs_device(self._h, C.c_void_p(seeds.data_ptr()), seeds.shape[0],
-                                                            C.c_void_p(cand.data_ptr()), n, cand.shape[1], _METRICS[metric],
-                                                            Mp, C.c_void_p(order.data_ptr()), C.c_void_p(dist.data_ptr())))
-        self._post()
+        self._call("blissgpu_closest_to_songs_device", seeds, seeds.shape[0], cand, n, cand.shape[1], METRICS[metric], M, order,
+                   dist)
         order = order.to(torch.int64)
         return (order, dist) if return_distances else order
 
     def song_to_song(self, seeds, cand, metric: str = "euclidean", M=None):
         """Greedy nearest-neighbour chain over the candidates (int64 index tensor)."""
-        from .playlist import _METRICS
-
         torch = self.torch
-        seeds, cand, M, Mp = self._pl_args(seeds, cand, M)
+        seeds, cand, M = self._pl_args(seeds, cand, M)
         n = cand.shape[0]
         order = torch.empty((n,), dtype=torch.int32, device=cand.device)
-        self._pre()
-        _ffi.check(self._L.blissgpu_song_to_song_device(self._h, C.c_void_p(seeds.data_ptr()), seeds.shape[0],
-                                                        C.c_void_p(cand.data_ptr()), n, cand.shape[1], _METRICS[metric], Mp,
-                                                        C.c_void_p(order.data_ptr())))
-        self._post()
+        self._call("blissgpu_song_to_song_device", seeds, seeds.shape[0], cand, n, cand.shape[1], METRICS[metric], M, order)
         return order.to(torch.int64)
 
     def dedup_playlist(self, X, seq=None, meta=None, metric: str = "euclidean", M=None, threshold=None):
@@ -417,29 +430,19 @@ class Context:
         int32 tensor of len(seq) slots whose first n_kept (a one-element int64 tensor) hold the kept positions into seq.
         Stays on the device: nothing is copied back.  meta: one int32 key per row of X (playlist.meta_keys) or None.
         Raises BlissGpuError(ERR_NAN) for a NaN distance on the chain of kept songs (synchronises for that check)."""
-        from .playlist import _METRICS
-
         torch = self.torch
         assert X.is_cuda and X.dtype == torch.float32 and X.dim() == 2
         X = X.contiguous()
         n, d = X.shape
         length = n if seq is None else seq.shape[0]
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
         if seq is not None:
             assert seq.is_cuda and seq.dtype == torch.int32
             seq = seq.contiguous()
-        if meta is not None:
-            assert meta.is_cuda and meta.dtype == torch.int32 and meta.shape[0] == n
-            meta = meta.contiguous()
-        if M is not None:
-            M = M.contiguous()
+        meta, M = self._i32_per_row(meta, n), _contig(M)
         kept = torch.empty((max(length, 1),), dtype=torch.int32, device=X.device)
         n_kept = torch.empty((1,), dtype=torch.int64, device=X.device)
-        self._pre()
-        _ffi.check(self._L.blissgpu_dedup_playlist_device(self._h, ptr(X), n, d, ptr(seq), length, ptr(meta), _METRICS[metric],
-                                                          ptr(M), float(0.05 if threshold is None else threshold), ptr(kept),
-                                                          ptr(n_kept)))
-        self._post()
+        self._call("blissgpu_dedup_playlist_device", X, n, d, seq, length, meta, METRICS[metric], M,
+                   float(0.05 if threshold is None else threshold), kept, n_kept)
         return kept[:length], n_kept
 
     def knn(self, Q, X, k: int, metric: str = "euclidean", M=None, skip=None):
@@ -448,25 +451,11 @@ class Context:
         [q, k]) on the device; equal distances in candidate order; rows with fewer than k eligible candidates end in -1 (the
         library's 0xFFFFFFFF) / inf.  skip: int32 tensor of q candidate indices, -1 = none, or None.  Raises
         BlissGpuError(ERR_NAN) for a NaN among the evaluated distances (synchronises for that check)."""
-        from .playlist import _METRICS
-
-        torch = self.torch
-        assert Q.is_cuda and X.is_cuda and Q.dtype == torch.float32 and X.dtype == torch.float32
-        assert Q.dim() == 2 and X.dim() == 2 and Q.shape[1] == X.shape[1]
-        Q, X = Q.contiguous(), X.contiguous()
+        Q, X = self._rows_pair(Q, X)
         q, n, k = Q.shape[0], X.shape[0], int(k)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        if skip is not None:
-            assert skip.is_cuda and skip.dtype == torch.int32 and skip.shape[0] == q
-            skip = skip.contiguous()
-        if M is not None:
-            M = M.contiguous()
-        idx = torch.empty((q, max(k, 0)), dtype=torch.int32, device=X.device)
-        dist = torch.empty((q, max(k, 0)), dtype=torch.float32, device=X.device)
-        self._pre()
-        _ffi.check(self._L.blissgpu_knn_device(self._h, ptr(Q), q, ptr(X), n, Q.shape[1], _METRICS[metric], ptr(M), ptr(skip), k,
-                                               ptr(idx), ptr(dist)))
-        self._post()
+        skip, M = self._i32_per_row(skip, q), _contig(M)
+        idx, dist = self._lists(q, k, X.device)
+        self._call("blissgpu_knn_device", Q, q, X, n, Q.shape[1], METRICS[metric], M, skip, k, idx, dist)
         return idx, dist
 
     def scaled_knn(self, Q, qscale, X, cscale, k: int, metric: str = "euclidean", M=None, skip=None):
@@ -476,29 +465,16 @@ class Context:
         the device; equal scaled distances in candidate order; padding -1 / inf and skip as for knn.  Raises BlissGpuError:
         ERR_INVALID for a scale outside the range (NaN included) or a bad skip, ERR_NAN for a NaN among the evaluated distances
         (synchronises for those checks)."""
-        from .playlist import _METRICS
-
         torch = self.torch
-        assert Q.is_cuda and X.is_cuda and Q.dtype == torch.float32 and X.dtype == torch.float32
-        assert Q.dim() == 2 and X.dim() == 2 and Q.shape[1] == X.shape[1]
-        Q, X = Q.contiguous(), X.contiguous()
+        Q, X = self._rows_pair(Q, X)
         q, n, k = Q.shape[0], X.shape[0], int(k)
         assert qscale.is_cuda and cscale.is_cuda and qscale.dtype == torch.float32 and cscale.dtype == torch.float32
         qscale, cscale = qscale.contiguous().reshape(-1), cscale.contiguous().reshape(-1)
         if qscale.shape[0] != q or cscale.shape[0] != n:
             raise ValueError("qscale needs one entry per row of Q and cscale one per row of X")
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        if skip is not None:
-            assert skip.is_cuda and skip.dtype == torch.int32 and skip.shape[0] == q
-            skip = skip.contiguous()
-        if M is not None:
-            M = M.contiguous()
-        idx = torch.empty((q, max(k, 0)), dtype=torch.int32, device=X.device)
-        dist = torch.empty((q, max(k, 0)), dtype=torch.float32, device=X.device)
-        self._pre()
-        _ffi.check(self._L.blissgpu_scaled_knn_device(self._h, ptr(Q), q, ptr(qscale), ptr(X), n, ptr(cscale), Q.shape[1],
-                                                      _METRICS[metric], ptr(M), ptr(skip), k, ptr(idx), ptr(dist)))
-        self._post()
+        skip, M = self._i32_per_row(skip, q), _contig(M)
+        idx, dist = self._lists(q, k, X.device)
+        self._call("blissgpu_scaled_knn_device", Q, q, qscale, X, n, cscale, Q.shape[1], METRICS[metric], M, skip, k, idx, dist)
         return idx, dist
 
     def knn_occurrence(self, idx, n: int):
@@ -510,10 +486,8 @@ class Context:
         idx = idx.contiguous()
         q, k, n = idx.shape[0], idx.shape[1], int(n)
         count = torch.empty((max(n, 0),), dtype=torch.int32, device=idx.device)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None  # noqa: E731
-        self._pre()
-        _ffi.check(self._L.blissgpu_knn_occurrence_device(self._h, ptr(idx), q, k, n, ptr(count)))
-        self._post()
+        # (this entry point is given no pointer for an empty tensor)
+        self._call("blissgpu_knn_occurrence_device", idx if idx.numel() else None, q, k, n, count if count.numel() else None)
         return count
 
     def kmeans(self, X, init, max_iter: int = 100, metric: str = "euclidean", M=None):
@@ -523,31 +497,18 @@ class Context:
         float32 tensors on the device, or numpy arrays (uploaded, results returned as arrays).  -> (labels int32 [n], dist float32
         [n], centroids float32 [k, d], sizes int32 [k], n_iter, converged).  metric: "euclidean" or "mahalanobis" with M.  Raises
         BlissGpuError(ERR_NAN) for a NaN among the evaluated distances; synchronises once per iteration."""
-        from .playlist import _METRICS
-
         torch = self.torch
         as_numpy = not torch.is_tensor(X)
-        dev = torch.device("cuda", self.device)
-        up = lambda a: None if a is None else (  # noqa: E731
-            a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev))
-        X, init, M = up(X), up(init), up(M)
-        assert X.is_cuda and init.is_cuda and X.dtype == torch.float32 and init.dtype == torch.float32
-        assert X.dim() == 2 and init.dim() == 2 and X.shape[1] == init.shape[1]
-        X, init = X.contiguous(), init.contiguous()
-        if M is not None:
-            assert M.is_cuda and M.dtype == torch.float32
-            M = M.contiguous()
+        X, init = self._rows_pair(self._up_f32(X), self._up_f32(init))
+        M = self._f32_metric(M)
         (n, d), k = X.shape, init.shape[0]
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
         labels = torch.empty((n,), dtype=torch.int32, device=X.device)
         dist = torch.empty((n,), dtype=torch.float32, device=X.device)
         cent = torch.empty((k, d), dtype=torch.float32, device=X.device)
         sizes = torch.empty((k,), dtype=torch.int32, device=X.device)
         n_iter, conv = C.c_uint32(0), C.c_int32(0)
-        self._pre()
-        _ffi.check(self._L.blissgpu_kmeans_device(self._h, ptr(X), n, d, ptr(init), k, _METRICS[metric], ptr(M), int(max_iter),
-                                                  ptr(labels), ptr(dist), ptr(cent), ptr(sizes), C.byref(n_iter), C.byref(conv)))
-        self._post()
+        self._call("blissgpu_kmeans_device", X, n, d, init, k, METRICS[metric], M, int(max_iter), labels, dist, cent, sizes,
+                   C.byref(n_iter), C.byref(conv))
         if as_numpy:
             labels, dist, cent, sizes = (t.cpu().numpy() for t in (labels, dist, cent, sizes))
         return labels, dist, cent, sizes, int(n_iter.value), bool(conv.value)
@@ -556,7 +517,7 @@ class Context:
         """(device-to-host copies inside the loop, their bytes) of the last kmeans on this context: one pair of flag words per
         assignment."""
         a, b = C.c_uint64(), C.c_uint64()
-        _ffi.check(self._L.blissgpu_debug_kmeans_stats(self._h, C.byref(a), C.byref(b)))
+        _ffi.call("blissgpu_debug_kmeans_stats", self._h, C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
 
     def silhouette(self, X, labels, metric: str = "euclidean", M=None, rows=None, col_groups: int = 0, k: int = None):
@@ -569,49 +530,25 @@ class Context:
         -> (s float32 [q], a float64 [q], b float64 [q], neighbour int32 [q], sizes int32 [k]).  col_groups: 0 = the plan's
         choice; no result bit depends on it.  Raises BlissGpuError: ERR_NAN for a NaN among the evaluated distances, ERR_INVALID
         for a label >= k, fewer than two non-empty clusters or a rows entry past n; synchronises once."""
-        from .playlist import _METRICS
-
         torch = self.torch
         as_numpy = not torch.is_tensor(X)
-        dev = torch.device("cuda", self.device)
-
-        def up_f32(a):
-            return None if a is None else (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev))
-
-        def up_u32(a, what):  # -> int32 tensor holding the uint32 bits
-            if a is None:
-                return None
-            if torch.is_tensor(a):
-                assert a.is_cuda and a.dtype in (torch.int32, torch.int64), what
-                return a.to(torch.int32).contiguous().reshape(-1)
-            a = np.asarray(a, dtype=np.int64).reshape(-1)
-            if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
-                raise ValueError(f"{what} must be non-negative indices")
-            return torch.from_numpy(a.astype(np.uint32).view(np.int32)).to(dev)
-
-        X, M = up_f32(X), up_f32(M)
-        labels, rows = up_u32(labels, "labels"), up_u32(rows, "rows")
-        assert X.is_cuda and X.dtype == torch.float32 and X.dim() == 2
-        X = X.contiguous()
+        X = self._up_f32(X)
+        labels, rows = self._up_u32(labels, "labels"), self._up_u32(rows, "rows")
+        X = self._rows(X)
         n, d = X.shape
         if labels.shape[0] != n:
             raise ValueError("a label per row of X is needed")
-        if M is not None:
-            assert M.is_cuda and M.dtype == torch.float32
-            M = M.contiguous()
+        M = self._f32_metric(M)
         if k is None:
             k = int(labels.max().item()) + 1 if n else 1
         q = n if rows is None else rows.shape[0]
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
         s = torch.zeros((q,), dtype=torch.float32, device=X.device)
         a = torch.zeros((q,), dtype=torch.float64, device=X.device)
         b = torch.zeros((q,), dtype=torch.float64, device=X.device)
         nb = torch.full((q,), -1, dtype=torch.int32, device=X.device)
         sizes = torch.zeros((max(int(k), 0),), dtype=torch.int32, device=X.device)
-        self._pre()
-        _ffi.check(self._L.blissgpu_silhouette_device(self._h, ptr(X), n, d, ptr(labels), int(k), _METRICS[metric], ptr(M), ptr(rows), q,
-                                                      int(col_groups), ptr(s), ptr(a), ptr(b), ptr(nb), ptr(sizes)))
-        self._post()
+        self._call("blissgpu_silhouette_device", X, n, d, labels, int(k), METRICS[metric], M, rows, q, int(col_groups), s, a, b, nb,
+                   sizes)
         out = (s, a, b, nb, sizes)
         return tuple(t.cpu().numpy() for t in out) if as_numpy else out
 
@@ -627,52 +564,27 @@ class Context:
         or None unless `want_matrix`).  slab_groups: 0 = the plan's choice; no result bit depends on it.  Raises BlissGpuError:
         ERR_NAN for a NaN among the evaluated distances, ERR_INVALID for a label or a query >= k, ERR_OOM when the workspace does
         not fit the context's limit; synchronises once."""
-        from .playlist import _GROUP_MODES, _METRICS
-
         torch = self.torch
         as_numpy = not torch.is_tensor(X)
-        dev = torch.device("cuda", self.device)
-
-        def up_f32(a):
-            return None if a is None else (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev))
-
-        def up_u32(a, what):  # -> int32 tensor holding the uint32 bits
-            if a is None:
-                return None
-            if torch.is_tensor(a):
-                assert a.is_cuda and a.dtype in (torch.int32, torch.int64), what
-                return a.to(torch.int32).contiguous().reshape(-1)
-            a = np.asarray(a, dtype=np.int64).reshape(-1)
-            if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
-                raise ValueError(f"{what} must be non-negative indices")
-            return torch.from_numpy(a.astype(np.uint32).view(np.int32)).to(dev)
-
-        if mode not in _GROUP_MODES:
-            raise ValueError(f"mode must be one of {tuple(_GROUP_MODES)}")
-        X, M = up_f32(X), up_f32(M)
-        labels, queries = up_u32(labels, "labels"), up_u32(queries, "queries")
-        assert X.is_cuda and X.dtype == torch.float32 and X.dim() == 2
-        X = X.contiguous()
+        if mode not in GROUP_MODES:
+            raise ValueError(f"mode must be one of {tuple(GROUP_MODES)}")
+        X = self._up_f32(X)
+        labels, queries = self._up_u32(labels, "labels"), self._up_u32(queries, "queries")
+        X = self._rows(X)
         n, d = X.shape
         if labels.shape[0] != n:
             raise ValueError("a label per row of X is needed")
-        if M is not None:
-            assert M.is_cuda and M.dtype == torch.float32
-            M = M.contiguous()
+        M = self._f32_metric(M)
         if k is None:
             k = int(labels.max().item()) + 1 if n else 1
         k, t = int(k), int(t)
         q = max(k, 0) if queries is None else queries.shape[0]
-        ptr = lambda a: None if a is None else C.c_void_p(a.data_ptr())  # noqa: E731
         idx = torch.full((q, max(t, 0)), -1, dtype=torch.int32, device=X.device)
         dist = torch.full((q, max(t, 0)), float("inf"), dtype=torch.float64, device=X.device)
         sizes = torch.zeros((max(k, 0),), dtype=torch.int32, device=X.device)
         matrix = torch.zeros((max(k, 0), max(k, 0)), dtype=torch.float64, device=X.device) if want_matrix else None
-        self._pre()
-        _ffi.check(self._L.blissgpu_group_neighbours_device(self._h, ptr(X), n, d, ptr(labels), k, _METRICS[metric], ptr(M), ptr(queries),
-                                                            q, t, _GROUP_MODES[mode], int(slab_groups), ptr(idx), ptr(dist), ptr(sizes),
-                                                            ptr(matrix)))
-        self._post()
+        self._call("blissgpu_group_neighbours_device", X, n, d, labels, k, METRICS[metric], M, queries, q, t, GROUP_MODES[mode],
+                   int(slab_groups), idx, dist, sizes, matrix)
         out = (idx, dist, sizes, matrix)
         return tuple(None if a is None else a.cpu().numpy() for a in out) if as_numpy else out
 
@@ -685,35 +597,21 @@ class Context:
         u < v, and the number of Boruvka rounds run.  metric: "euclidean" or "mahalanobis" with M.  Raises BlissGpuError:
         ERR_INVALID for cosine, a NaN distance or a bad core, ERR_OOM when the workspace does not fit the context's limit;
         synchronises once per round."""
-        from .playlist import _METRICS
-
         torch = self.torch
         as_numpy = not torch.is_tensor(X)
-        dev = torch.device("cuda", self.device)
-        up = lambda a: None if a is None else (  # noqa: E731
-            a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev))
-        X, M, core = up(X), up(M), up(core)
-        assert X.is_cuda and X.dtype == torch.float32 and X.dim() == 2
-        X = X.contiguous()
+        X, M, core = self._rows(self._up_f32(X)), self._f32_metric(M), self._up_f32(core)
         n, d = X.shape
-        if M is not None:
-            assert M.is_cuda and M.dtype == torch.float32
-            M = M.contiguous()
         if core is not None:
             assert core.is_cuda and core.dtype == torch.float32
             core = core.contiguous().reshape(-1)
             if core.shape[0] != n:
                 raise ValueError("a core distance per row of X is needed")
-        ptr = lambda a: None if a is None else C.c_void_p(a.data_ptr())  # noqa: E731
         m = max(n - 1, 0)
         u = torch.empty((m,), dtype=torch.int32, device=X.device)
         v = torch.empty((m,), dtype=torch.int32, device=X.device)
         w = torch.empty((m,), dtype=torch.float32, device=X.device)
         rounds = C.c_uint32(0)
-        self._pre()
-        _ffi.check(self._L.blissgpu_mst_device(self._h, ptr(X), n, d, _METRICS[metric], ptr(M), ptr(core), ptr(u), ptr(v), ptr(w),
-                                               C.byref(rounds)))
-        self._post()
+        self._call("blissgpu_mst_device", X, n, d, METRICS[metric], M, core, u, v, w, C.byref(rounds))
         if as_numpy:
             u, v, w = (t.cpu().numpy() for t in (u, v, w))
         return u, v, w, int(rounds.value)
@@ -728,21 +626,10 @@ class Context:
         BlissGpuError: ERR_NAN for a NaN or an infinity in X, ERR_INVALID for a label >= k; synchronises once."""
         torch = self.torch
         as_numpy = not torch.is_tensor(X)
-        dev = torch.device("cuda", self.device)
-        if as_numpy:
-            X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(dev)
-        assert X.is_cuda and X.dtype == torch.float32 and X.dim() == 2
-        X = X.contiguous()
+        X = self._rows(self._up_f32(X))
         n, d = X.shape
         if labels is not None:
-            if torch.is_tensor(labels):
-                assert labels.is_cuda and labels.dtype in (torch.int32, torch.int64), "labels"
-                labels = labels.to(torch.int32).contiguous().reshape(-1)
-            else:
-                labels = np.asarray(labels, dtype=np.int64).reshape(-1)
-                if labels.size and (labels.min() < 0 or labels.max() > 0xFFFFFFFF):
-                    raise ValueError("labels must be non-negative indices")
-                labels = torch.from_numpy(labels.astype(np.uint32).view(np.int32)).to(dev)
+            labels = self._up_u32(labels, "labels")
             if labels.shape[0] != n:
                 raise ValueError("a label per row of X is needed")
             if k is None:
@@ -750,7 +637,6 @@ class Context:
         elif k is None:
             k = 1
         k = int(k)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
         kk = max(k, 0)
         counts = torch.zeros((kk,), dtype=torch.int32, device=X.device)
         mean = torch.zeros((kk, d), dtype=torch.float64, device=X.device)
@@ -758,10 +644,7 @@ class Context:
         mn = torch.zeros((kk, d), dtype=torch.float32, device=X.device)
         mx = torch.zeros((kk, d), dtype=torch.float32, device=X.device)
         S = torch.zeros((d, d), dtype=torch.float64, device=X.device) if scatter else None
-        self._pre()
-        _ffi.check(self._L.blissgpu_moments_device(self._h, ptr(X), n, d, ptr(labels), k, ptr(counts), ptr(mean), ptr(m2), ptr(mn),
-                                                   ptr(mx), ptr(S)))
-        self._post()
+        self._call("blissgpu_moments_device", X, n, d, labels, k, counts, mean, m2, mn, mx, S)
         out = (counts, mean, m2, mn, mx, S)
         return tuple(None if t is None else t.cpu().numpy() for t in out) if as_numpy else out
 
@@ -778,14 +661,11 @@ class Context:
         if M is not None:
             assert M.is_cuda and M.dtype == torch.float32 and tuple(M.shape) == (d, d)
             M = M.contiguous()
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
         flags = torch.zeros((T,), dtype=torch.uint8, device=X.device) if return_flags else None
         G = np.zeros((d, d), np.float64)
         n_active, loss = C.c_uint64(0), C.c_double(0.0)
-        self._pre()
-        _ffi.check(self._L.blissgpu_triplet_step_device(self._h, ptr(X), n, d, ptr(triplets) if T else None, T, ptr(M), float(margin),
-                                                        ptr(flags) if T else None, C.byref(n_active), C.byref(loss), G.ctypes.data))
-        self._post()
+        self._call("blissgpu_triplet_step_device", X, n, d, triplets if T else None, T, M, float(margin), flags if T else None,
+                   C.byref(n_active), C.byref(loss), G)
         out = (int(n_active.value), float(loss.value), G)
         return out + (flags,) if return_flags else out
 
@@ -794,8 +674,6 @@ class Context:
         """playlist.learn_metric on device tensors (blissgpu_learn_metric_device): X float32 [n, d] and triplets int32 [T, 3]
         stay where they are, an iteration uploads M and downloads the gradient.  init: d host weights or None.
         -> playlist.LearnedMetric (host arrays)."""
-        from . import playlist as P
-
         torch = self.torch
         margin = P.LEARN_MARGIN if margin is None else margin
         lr = P.LEARN_LR if lr is None else lr
@@ -808,20 +686,15 @@ class Context:
         init, max_iter = P._learn_args(form, init, d, max_iter)
         M, obj, act = np.zeros((d, d), np.float32), np.zeros(max_iter + 1, np.float64), np.zeros(max_iter + 1, np.uint64)
         n_iter, best_iter, status = C.c_uint32(0), C.c_uint32(0), C.c_int32(0)
-        self._pre()
-        _ffi.check(self._L.blissgpu_learn_metric_device(self._h, C.c_void_p(X.data_ptr()), n, d,
-                                                        C.c_void_p(triplets.data_ptr()) if T else None, T, P._FORMS[form],
-                                                        None if init is None else init.ctypes.data, float(margin), float(lr),
-                                                        float(reg), max_iter, M.ctypes.data, obj.ctypes.data, act.ctypes.data,
-                                                        C.byref(n_iter), C.byref(best_iter), C.byref(status)))
-        self._post()
+        self._call("blissgpu_learn_metric_device", X, n, d, triplets if T else None, T, FORMS[form], init, float(margin), float(lr),
+                   float(reg), max_iter, M, obj, act, C.byref(n_iter), C.byref(best_iter), C.byref(status))
         return P._learned(M, obj, act, n_iter, best_iter, status)
 
     def metric_stats(self):
         """(uploads, downloads, bytes downloaded) inside the loop of the last learn_metric on this context: one M up and one
         result block down per gradient evaluation."""
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _ffi.check(self._L.blissgpu_debug_metric_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        _ffi.call("blissgpu_debug_metric_stats", self._h, C.byref(a), C.byref(b), C.byref(c))
         return int(a.value), int(b.value), int(c.value)
 
     def group_weights(self, S, offsets):
@@ -829,20 +702,13 @@ class Context:
         rows offsets[g] .. offsets[g + 1] of S (offsets: a HOST sequence of G + 1 integers starting at 0).  -> (weights float32
         [G, d], status int32 [G]) on the device: row g is the DIAGONAL of the reference's matrix; a group of fewer than two
         seeds gets ones and status 1 (BLISSGPU_GROUP_TOO_FEW_SEEDS), every other group status 0."""
-        import numpy as np
-
         torch = self.torch
-        assert S.is_cuda and S.dtype == torch.float32 and S.dim() == 2
-        S = S.contiguous()
-        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1)).astype(np.uint64)
-        assert off.shape[0] >= 1 and int(off[-1]) == S.shape[0]
-        G, d = off.shape[0] - 1, S.shape[1]
+        S = self._rows(S)
+        off, G = _offsets(offsets, S.shape[0])
+        d = S.shape[1]
         weights = torch.empty((G, d), dtype=torch.float32, device=S.device)
         status = torch.empty((G,), dtype=torch.int32, device=S.device)
-        self._pre()
-        _ffi.check(self._L.blissgpu_group_weights_device(self._h, C.c_void_p(S.data_ptr()), off.ctypes.data, G, d,
-                                                         C.c_void_p(weights.data_ptr()), C.c_void_p(status.data_ptr())))
-        self._post()
+        self._call("blissgpu_group_weights_device", S, off, G, d, weights, status)
         return weights, status
 
     def group_knn(self, S, offsets, X, k: int, metric: str = "euclidean", M=None, skip=None, weights=None):
@@ -857,25 +723,12 @@ class Context:
         float32 [G, d] tensor, or the string "variance" for the variance-based weights of each group's own seeds, computed on
         the device (group_weights) in the same call.  -> (idx, dist, status int32 [G]): status as group_weights returns it
         (all 0 with given weights)."""
-        import numpy as np
-
-        from .playlist import _METRICS
-
         torch = self.torch
-        assert S.is_cuda and X.is_cuda and S.dtype == torch.float32 and X.dtype == torch.float32
-        assert S.dim() == 2 and X.dim() == 2 and S.shape[1] == X.shape[1]
-        S, X = S.contiguous(), X.contiguous()
-        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1)).astype(np.uint64)
-        assert off.shape[0] >= 1 and int(off[-1]) == S.shape[0]
-        G, n, k = off.shape[0] - 1, X.shape[0], int(k)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        if skip is not None:
-            assert skip.is_cuda and skip.dtype == torch.int32 and skip.shape[0] == S.shape[0]
-            skip = skip.contiguous()
-        if M is not None:
-            M = M.contiguous()
-        idx = torch.empty((G, max(k, 0)), dtype=torch.int32, device=X.device)
-        dist = torch.empty((G, max(k, 0)), dtype=torch.float32, device=X.device)
+        S, X = self._rows_pair(S, X)
+        off, G = _offsets(offsets, S.shape[0])
+        n, k = X.shape[0], int(k)
+        skip, M = self._i32_per_row(skip, S.shape[0]), _contig(M)
+        idx, dist = self._lists(G, k, X.device)
         if weights is not None:
             if isinstance(weights, str):
                 if weights != "variance":
@@ -885,15 +738,9 @@ class Context:
                 assert weights.is_cuda and weights.dtype == torch.float32 and tuple(weights.shape) == (G, X.shape[1])
                 weights = weights.contiguous()
             status = torch.empty((G,), dtype=torch.int32, device=X.device)
-            self._pre()
-            _ffi.check(self._L.blissgpu_group_knn_weighted_device(self._h, ptr(S), off.ctypes.data, G, ptr(X), n, X.shape[1],
-                                                                  ptr(weights), ptr(skip), k, ptr(idx), ptr(dist), ptr(status)))
-            self._post()
+            self._call("blissgpu_group_knn_weighted_device", S, off, G, X, n, X.shape[1], weights, skip, k, idx, dist, status)
             return idx, dist, status
-        self._pre()
-        _ffi.check(self._L.blissgpu_group_knn_device(self._h, ptr(S), off.ctypes.data, G, ptr(X), n, X.shape[1], _METRICS[metric],
-                                                     ptr(M), ptr(skip), k, ptr(idx), ptr(dist)))
-        self._post()
+        self._call("blissgpu_group_knn_device", S, off, G, X, n, X.shape[1], METRICS[metric], M, skip, k, idx, dist)
         return idx, dist
 
     def chains(self, S, offsets, X, k: int, metric: str = "euclidean", M=None, skip=None, route: str = "auto"):
@@ -905,29 +752,12 @@ class Context:
         int32 tensor with one candidate index per SEED ROW, -1 = none, or None.  route: "auto", "steps" (a launch per step) or
         "lists" (the candidates' own k-nearest lists, then one walk); the result does not depend on it.  Raises
         BlissGpuError(ERR_NAN) for a NaN among the distances a chain evaluates (synchronises for that check)."""
-        import numpy as np
-
-        from .playlist import _METRICS, _ROUTES
-
-        torch = self.torch
-        assert S.is_cuda and X.is_cuda and S.dtype == torch.float32 and X.dtype == torch.float32
-        assert S.dim() == 2 and X.dim() == 2 and S.shape[1] == X.shape[1]
-        S, X = S.contiguous(), X.contiguous()
-        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1)).astype(np.uint64)
-        assert off.shape[0] >= 1 and int(off[-1]) == S.shape[0]
-        G, n, k = off.shape[0] - 1, X.shape[0], int(k)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        if skip is not None:
-            assert skip.is_cuda and skip.dtype == torch.int32 and skip.shape[0] == S.shape[0]
-            skip = skip.contiguous()
-        if M is not None:
-            M = M.contiguous()
-        idx = torch.empty((G, max(k, 0)), dtype=torch.int32, device=X.device)
-        dist = torch.empty((G, max(k, 0)), dtype=torch.float32, device=X.device)
-        self._pre()
-        _ffi.check(self._L.blissgpu_chains_device(self._h, ptr(S), off.ctypes.data, G, ptr(X), n, X.shape[1], _METRICS[metric],
-                                                  ptr(M), ptr(skip), k, _ROUTES[route], ptr(idx), ptr(dist)))
-        self._post()
+        S, X = self._rows_pair(S, X)
+        off, G = _offsets(offsets, S.shape[0])
+        n, k = X.shape[0], int(k)
+        skip, M = self._i32_per_row(skip, S.shape[0]), _contig(M)
+        idx, dist = self._lists(G, k, X.device)
+        self._call("blissgpu_chains_device", S, off, G, X, n, X.shape[1], METRICS[metric], M, skip, k, ROUTES[route], idx, dist)
         return idx, dist
 
     def journeys(self, A, B, X, k: int, metric: str = "euclidean", M=None, skip=None, mode: str = "chain", gate: str = None,
@@ -941,29 +771,19 @@ class Context:
         candidate indices that are never eligible, -1 = none, or None.  -> (idx int32 [G, k], dist float32 [G, k]) on the
         device; a journey that runs out of eligible candidates ends in -1 (the library's 0xFFFFFFFF) / inf.  Raises
         BlissGpuError(ERR_NAN) for a NaN distance of an eligible candidate (synchronises for that check)."""
-        from .playlist import _GATES, _JOURNEY_MODES, _METRICS
-
         torch = self.torch
-        assert A.is_cuda and X.is_cuda and A.dtype == torch.float32 and X.dtype == torch.float32
-        assert A.dim() == 2 and X.dim() == 2 and A.shape[1] == X.shape[1]
-        A, X = A.contiguous(), X.contiguous()
+        A, X = self._rows_pair(A, X)
         G, n, k = A.shape[0], X.shape[0], int(k)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
         if B is not None:
             assert B.is_cuda and B.dtype == torch.float32 and tuple(B.shape) == tuple(A.shape)
             B = B.contiguous()
         if skip is not None:
             assert skip.is_cuda and skip.dtype == torch.int32 and tuple(skip.shape) == (G, 2)
             skip = skip.contiguous()
-        if M is not None:
-            M = M.contiguous()
-        idx = torch.empty((G, max(k, 0)), dtype=torch.int32, device=X.device)
-        dist = torch.empty((G, max(k, 0)), dtype=torch.float32, device=X.device)
-        self._pre()
-        _ffi.check(self._L.blissgpu_journeys_device(self._h, ptr(A), ptr(B), G, ptr(X), n, X.shape[1], _METRICS[metric], ptr(M),
-                                                    ptr(skip), k, _JOURNEY_MODES[mode], _GATES[gate], int(feature), ptr(idx),
-                                                    ptr(dist)))
-        self._post()
+        M = _contig(M)
+        idx, dist = self._lists(G, k, X.device)
+        self._call("blissgpu_journeys_device", A, B, G, X, n, X.shape[1], METRICS[metric], M, skip, k, JOURNEY_MODES[mode],
+                   GATES[gate], int(feature), idx, dist)
         return idx, dist
 
     def radio(self, A, X, k: int, labels=None, windows=(), limits=(), from_labels=None, mode: str = "chain",
@@ -977,16 +797,9 @@ class Context:
         candidate indices that are never eligible, -1 = none, or None.  -> (idx int32 [G, k], dist float32 [G, k]) on the
         device; a radio that runs out of eligible candidates ends in -1 (the library's 0xFFFFFFFF) / inf.  Raises
         BlissGpuError(ERR_NAN) for a NaN distance of an eligible candidate (synchronises for that check)."""
-        import numpy as np
-
-        from .playlist import _METRICS, _RADIO_MODES
-
         torch = self.torch
-        assert A.is_cuda and X.is_cuda and A.dtype == torch.float32 and X.dtype == torch.float32
-        assert A.dim() == 2 and X.dim() == 2 and A.shape[1] == X.shape[1]
-        A, X = A.contiguous(), X.contiguous()
+        A, X = self._rows_pair(A, X)
         G, n, k = A.shape[0], X.shape[0], int(k)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
         win = np.ascontiguousarray(np.minimum(np.asarray(windows, np.int64).reshape(-1), 0xFFFFFFFF), dtype=np.uint32)
         lim = np.ascontiguousarray(np.minimum(np.asarray(limits, np.int64).reshape(-1), 0xFFFFFFFF), dtype=np.uint32)
         R = win.shape[0]
@@ -1004,15 +817,10 @@ class Context:
         if skip is not None:
             assert skip.is_cuda and skip.dtype == torch.int32 and tuple(skip.shape) == (G, 2)
             skip = skip.contiguous()
-        if M is not None:
-            M = M.contiguous()
-        idx = torch.empty((G, max(k, 0)), dtype=torch.int32, device=X.device)
-        dist = torch.empty((G, max(k, 0)), dtype=torch.float32, device=X.device)
-        self._pre()
-        _ffi.check(self._L.blissgpu_radio_device(self._h, ptr(A), G, ptr(X), n, X.shape[1], _METRICS[metric], ptr(M), ptr(labels),
-                                                 ptr(from_labels), R, win.ctypes.data if R else None, lim.ctypes.data if R else None,
-                                                 ptr(skip), k, _RADIO_MODES[mode], ptr(idx), ptr(dist)))
-        self._post()
+        M = _contig(M)
+        idx, dist = self._lists(G, k, X.device)
+        self._call("blissgpu_radio_device", A, G, X, n, X.shape[1], METRICS[metric], M, labels, from_labels, R, win if R else None,
+                   lim if R else None, skip, k, RADIO_MODES[mode], idx, dist)
         return idx, dist
 
     def album_knn(self, S, offsets, X, album_of, n_albums: int, k: int, skip=None):
@@ -1025,29 +833,17 @@ class Context:
         to the group's mean, album index), rows with fewer than k existing albums ending in -1 / inf; centroids are the
         full-album means, NaN rows for albums without songs.  Raises BlissGpuError(ERR_NAN) for a NaN distance (album_of and
         skip are read back, which synchronises)."""
-        import numpy as np
-
         torch = self.torch
-        assert S.is_cuda and X.is_cuda and S.dtype == torch.float32 and X.dtype == torch.float32
-        assert S.dim() == 2 and X.dim() == 2 and S.shape[1] == X.shape[1]
-        S, X = S.contiguous(), X.contiguous()
-        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1)).astype(np.uint64)
-        assert off.shape[0] >= 1 and int(off[-1]) == S.shape[0]
-        G, n, d, k, A = off.shape[0] - 1, X.shape[0], X.shape[1], int(k), int(n_albums)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        S, X = self._rows_pair(S, X)
+        off, G = _offsets(offsets, S.shape[0])
+        n, d, k, A = X.shape[0], X.shape[1], int(k), int(n_albums)
         assert album_of.is_cuda and album_of.dtype == torch.int32 and album_of.shape[0] == n
         album_of = album_of.contiguous()
-        if skip is not None:
-            assert skip.is_cuda and skip.dtype == torch.int32 and skip.shape[0] == S.shape[0]
-            skip = skip.contiguous()
-        idx = torch.empty((G, max(k, 0)), dtype=torch.int32, device=X.device)
-        dist = torch.empty((G, max(k, 0)), dtype=torch.float32, device=X.device)
+        skip = self._i32_per_row(skip, S.shape[0])
+        idx, dist = self._lists(G, k, X.device)
         means = torch.empty((G, d), dtype=torch.float32, device=X.device)
         centroids = torch.empty((max(A, 0), d), dtype=torch.float32, device=X.device)
-        self._pre()
-        _ffi.check(self._L.blissgpu_album_knn_device(self._h, ptr(S), off.ctypes.data, G, ptr(X), n, d, ptr(album_of), A,
-                                                     ptr(skip), k, ptr(idx), ptr(dist), ptr(means), ptr(centroids)))
-        self._post()
+        self._call("blissgpu_album_knn_device", S, off, G, X, n, d, album_of, A, skip, k, idx, dist, means, centroids)
         return idx, dist, means, centroids
 
     def duplicate_labels(self, x, meta=None, metric: str = "euclidean", m=None, threshold=0.05, max_pairs: int = 0):
@@ -1058,18 +854,10 @@ class Context:
         [max_pairs]): the first n_pairs entries hold the edges in unspecified order when n_pairs <= max_pairs, otherwise the
         contents are unspecified.  Stays on the device; raises BlissGpuError(ERR_NAN) for a NaN distance (synchronises for
         that check)."""
-        from .playlist import _METRICS
-
         torch = self.torch
-        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
-        x = x.contiguous()
+        x = self._rows(x)
         n, d = x.shape
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        if meta is not None:
-            assert meta.is_cuda and meta.dtype == torch.int32 and meta.shape[0] == n
-            meta = meta.contiguous()
-        if m is not None:
-            m = m.contiguous()
+        meta, m = self._i32_per_row(meta, n), _contig(m)
         max_pairs = int(max_pairs)
         labels = torch.empty((max(n, 1),), dtype=torch.int32, device=x.device)
         n_pairs = torch.empty((1,), dtype=torch.int64, device=x.device)
@@ -1077,11 +865,8 @@ class Context:
         if max_pairs > 0:
             pairs = torch.empty((max_pairs, 2), dtype=torch.int32, device=x.device)
             dist = torch.empty((max_pairs,), dtype=torch.float32, device=x.device)
-        self._pre()
-        _ffi.check(self._L.blissgpu_duplicate_groups_device(self._h, ptr(x), n, d, ptr(meta), _METRICS[metric], ptr(m),
-                                                            float(threshold), ptr(labels), ptr(n_pairs), ptr(pairs), ptr(dist),
-                                                            max(max_pairs, 0)))
-        self._post()
+        self._call("blissgpu_duplicate_groups_device", x, n, d, meta, METRICS[metric], m, float(threshold), labels, n_pairs, pairs,
+                   dist, max(max_pairs, 0))
         if max_pairs > 0:
             return labels[:n], n_pairs, pairs, dist
         return labels[:n], n_pairs
@@ -1096,10 +881,7 @@ class Context:
         n = cand.shape[0]
         score = torch.empty((n,), dtype=torch.float32, device=cand.device)
         ps = torch.empty((n,), dtype=torch.int64, device=cand.device) if return_path_sum else None
-        self._pre()
-        _ffi.check(self._L.blissgpu_forest_score_device(self._h, forest.handle, C.c_void_p(cand.data_ptr()), n,
-                                                        C.c_void_p(score.data_ptr()), None if ps is None else C.c_void_p(ps.data_ptr())))
-        self._post()
+        self._call("blissgpu_forest_score_device", forest.handle, cand, n, score, ps)
         return (score, ps) if return_path_sum else score
 
     def forest_closest_to_songs(self, forest, cand, return_scores=False):
@@ -1111,10 +893,7 @@ class Context:
         n = cand.shape[0]
         order = torch.empty((n,), dtype=torch.int32, device=cand.device)
         score = torch.empty((n,), dtype=torch.float32, device=cand.device)
-        self._pre()
-        _ffi.check(self._L.blissgpu_forest_closest_to_songs_device(self._h, forest.handle, C.c_void_p(cand.data_ptr()), n,
-                                                                   C.c_void_p(order.data_ptr()), C.c_void_p(score.data_ptr())))
-        self._post()
+        self._call("blissgpu_forest_closest_to_songs_device", forest.handle, cand, n, order, score)
         order = order.to(torch.int64)
         return (order, score) if return_scores else order
 
@@ -1126,56 +905,42 @@ class Context:
         status 1 (BLISSGPU_GROUP_TOO_FEW_SEEDS) and a row of padding for a group with min(sample_size, seeds) < 2.
         skip: int32 tensor with one candidate index per SEED ROW, -1 = none, or None.  The forests are built on the host:
         `seeds_host` (a float32 array equal to S) saves the device-to-host copy of S.  Synchronises before it returns."""
-        import numpy as np
-
         torch = self.torch
-        assert S.is_cuda and X.is_cuda and S.dtype == torch.float32 and X.dtype == torch.float32
-        assert S.dim() == 2 and X.dim() == 2 and S.shape[1] == X.shape[1]
-        S, X = S.contiguous(), X.contiguous()
-        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1)).astype(np.uint64)
-        assert off.shape[0] >= 1 and int(off[-1]) == S.shape[0]
-        G, n, k = off.shape[0] - 1, X.shape[0], int(k)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        if skip is not None:
-            assert skip.is_cuda and skip.dtype == torch.int32 and skip.shape[0] == S.shape[0]
-            skip = skip.contiguous()
+        S, X = self._rows_pair(S, X)
+        off, G = _offsets(offsets, S.shape[0])
+        n, k = X.shape[0], int(k)
+        skip = self._i32_per_row(skip, S.shape[0])
         hs = None
         if seeds_host is not None:
             hs = np.ascontiguousarray(seeds_host, dtype=np.float32)
             assert hs.shape == tuple(S.shape)
-        idx = torch.empty((G, max(k, 0)), dtype=torch.int32, device=X.device)
-        score = torch.empty((G, max(k, 0)), dtype=torch.float32, device=X.device)
+        idx, score = self._lists(G, k, X.device)
         status = torch.empty((G,), dtype=torch.int32, device=X.device)
-        depth = options.max_tree_depth
-        self._pre()
-        _ffi.check(self._L.blissgpu_group_forest_knn_device(self._h, ptr(S), None if hs is None else hs.ctypes.data, off.ctypes.data,
-                                                            G, ptr(X), n, X.shape[1], options.n_trees, options.sample_size,
-                                                            depth or 0, options.extension_level, options.seed, ptr(skip), k,
-                                                            ptr(idx), ptr(score), ptr(status)))
-        self._post()
+        self._call("blissgpu_group_forest_knn_device", S, hs, off, G, X, n, X.shape[1], options.n_trees, options.sample_size,
+                   options.max_tree_depth or 0, options.extension_level, options.seed, skip, k, idx, score, status)
         return idx, score, status
 
     def group_forest_stats(self):
         """(host ms building forests, host ms waiting for the device, batches) of the last group_forest_knn on this context."""
         a, b, nb = C.c_double(), C.c_double(), C.c_uint64()
-        _ffi.check(self._L.blissgpu_debug_group_forest_stats(self._h, C.byref(a), C.byref(b), C.byref(nb)))
+        _ffi.call("blissgpu_debug_group_forest_stats", self._h, C.byref(a), C.byref(b), C.byref(nb))
         return a.value, b.value, int(nb.value)
 
     # ---- profiling ----
     def profile_enable(self, on: bool = True):
-        _ffi.check(self._L.blissgpu_profile_enable(self._h, int(on)))
+        _ffi.call("blissgpu_profile_enable", self._h, int(on))
 
     def profile_reset(self):
-        _ffi.check(self._L.blissgpu_profile_reset(self._h))
+        _ffi.call("blissgpu_profile_reset", self._h)
 
     def profile(self):
         """{kernel name: (total_ms, launches)} since the last reset."""
         res = {}
-        for k in range(self._L.blissgpu_profile_kernel_count()):
+        for k in range(_ffi.call("blissgpu_profile_kernel_count")):
             ms, n = C.c_double(), C.c_uint64()
-            _ffi.check(self._L.blissgpu_profile_get(self._h, k, C.byref(ms), C.byref(n)))
+            _ffi.call("blissgpu_profile_get", self._h, k, C.byref(ms), C.byref(n))
             if n.value:
-                res[self._L.blissgpu_profile_kernel_name(k).decode()] = (ms.value, n.value)
+                res[_ffi.call("blissgpu_profile_kernel_name", k).decode()] = (ms.value, n.value)
         return res
 
 
@@ -1187,7 +952,7 @@ class Node:
         self._L = _ffi.lib()
         h = C.c_void_p()
         dev = (C.c_int * n_devices)(*devices) if devices is not None else None
-        _ffi.check(self._L.blissgpu_node_create(n_devices, dev, C.byref(h)))
+        _ffi.call("blissgpu_node_create", n_devices, dev, C.byref(h))
         self._h = h
         self.n_devices = n_devices
 
@@ -1202,26 +967,23 @@ class Node:
         """Benchmark input on `rank`'s device: song i (at d_pcm_ptr + offsets[i]) gets generator index song_index[i]."""
         offsets, lengths = _u64(offsets), _u64(lengths)
         idx = np.ascontiguousarray(song_index, np.uint32)
-        ctx = self._L.blissgpu_node_ctx(self._h, rank)
-        _ffi.check(self._L.blissgpu_synth_white_noise_indexed_device(
-            ctx, C.c_void_p(int(d_pcm_ptr)), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
-            lengths.ctypes.data_as(C.POINTER(C.c_uint64)), idx.ctypes.data_as(C.POINTER(C.c_uint32)), len(offsets)))
-        _ffi.check(self._L.blissgpu_ctx_synchronize(ctx))
+        ctx = _ffi.call("blissgpu_node_ctx", self._h, rank)
+        _ffi.call("blissgpu_synth_white_noise_indexed_device", ctx, C.c_void_p(int(d_pcm_ptr)), offsets, lengths, idx, len(offsets))
+        _ffi.call("blissgpu_ctx_synchronize", ctx)
 
     def ctx_set_workspace_limit(self, rank: int, nbytes: int):
         """Scratch bytes of one chunk slot of `rank`'s context (several loopback ranks share one GPU's memory)."""
-        _ffi.check(self._L.blissgpu_ctx_set_workspace_limit(self._L.blissgpu_node_ctx(self._h, rank), nbytes))
+        _ffi.call("blissgpu_ctx_set_workspace_limit", _ffi.call("blissgpu_node_ctx", self._h, rank), nbytes)
 
     def shard(self, lengths) -> np.ndarray:
         lengths = _u64(lengths)
         ranks = np.empty(len(lengths), np.uint32)
-        _ffi.check(self._L.blissgpu_node_shard(self._h, lengths.ctypes.data_as(C.POINTER(C.c_uint64)), len(lengths),
-                                               ranks.ctypes.data_as(C.POINTER(C.c_uint32))))
+        _ffi.call("blissgpu_node_shard", self._h, lengths, len(lengths), ranks)
         return ranks
 
     def row_block(self, n_rows: int, rank: int):
         lo, hi = C.c_uint64(), C.c_uint64()
-        self._L.blissgpu_node_row_block(self._h, n_rows, rank, C.byref(lo), C.byref(hi))
+        _ffi.call("blissgpu_node_row_block", self._h, n_rows, rank, C.byref(lo), C.byref(hi))
         return lo.value, hi.value
 
     def analyze(self, pcm: np.ndarray, offsets, lengths, features_version: int = 2):
@@ -1232,10 +994,8 @@ class Node:
         d = 23 if features_version == 2 else 20
         out = np.empty((n, d), np.float32)
         status = np.empty(n, np.int32)
-        _ffi.check(self._L.blissgpu_node_analyze(self._h, pcm.ctypes.data, offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                 lengths.ctypes.data_as(C.POINTER(C.c_uint64)), n, features_version,
-                                                 out.ctypes.data, status.ctypes.data_as(C.POINTER(C.c_int32))))
-        _ffi.check(self._L.blissgpu_node_synchronize(self._h))
+        _ffi.call("blissgpu_node_analyze", self._h, pcm, offsets, lengths, n, features_version, out, status)
+        _ffi.call("blissgpu_node_synchronize", self._h)
         self._n, self._d = n, d
         return out, status
 
@@ -1244,28 +1004,21 @@ class Node:
         offsets, lengths = _u64(offsets), _u64(lengths)
         ranks = np.ascontiguousarray(rank_of_song, np.uint32)
         ptrs = (C.c_void_p * self.n_devices)(*[C.c_void_p(int(p)) for p in d_pcm_ptrs])
-        _ffi.check(self._L.blissgpu_node_analyze_device(self._h, ptrs, offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                        lengths.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                        ranks.ctypes.data_as(C.POINTER(C.c_uint32)), len(offsets),
-                                                        features_version))
-        _ffi.check(self._L.blissgpu_node_synchronize(self._h))
+        _ffi.call("blissgpu_node_analyze_device", self._h, ptrs, offsets, lengths, ranks, len(offsets), features_version)
+        _ffi.call("blissgpu_node_synchronize", self._h)
         self._n, self._d = len(offsets), 23 if features_version == 2 else 20
 
     def features(self, rank: int = 0) -> np.ndarray:
         """The gathered matrix as held by `rank`'s device."""
         out = np.empty((self._n, self._d), np.float32)
-        ctx = self._L.blissgpu_node_ctx(self._h, rank)
-        src = self._L.blissgpu_node_features(self._h, rank)
-        _ffi.check(self._L.blissgpu_memcpy_d2h(ctx, out.ctypes.data, src, out.nbytes))
+        ctx = _ffi.call("blissgpu_node_ctx", self._h, rank)
+        src = _ffi.call("blissgpu_node_features", self._h, rank)
+        _ffi.call("blissgpu_memcpy_d2h", ctx, out, src, out.nbytes)
         return out
 
     def pairwise(self, metric: str = "euclidean", M: Optional[np.ndarray] = None) -> np.ndarray:
-        from .playlist import _METRICS
-
         out = np.empty((self._n, self._n), np.float32)
-        Mp = None
         if M is not None:
             M = np.ascontiguousarray(M, np.float32)
-            Mp = M.ctypes.data
-        _ffi.check(self._L.blissgpu_node_pairwise(self._h, _METRICS[metric], Mp, out.ctypes.data))
+        _ffi.call("blissgpu_node_pairwise", self._h, METRICS[metric], M, out)
         return out

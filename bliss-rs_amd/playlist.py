@@ -38,10 +38,19 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 
 from . import _ffi
+from ._marshal import check_k_d, metric_matrix, rows_f32, signed_idx, skip_words
 
 
 def _vec(a):
     return np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+
+
+def _call(name, *args):
+    """_ffi.call for the entry points whose NaN distance is the reference's panic: ERR_NAN becomes that ValueError"""
+    try:
+        return _ffi.call(name, *args)
+    except _ffi.BlissGpuError as e:
+        _nan_to_panic(e)
 
 
 def _single(a, b, metric, m=None) -> float:
@@ -49,11 +58,7 @@ def _single(a, b, metric, m=None) -> float:
     if a.shape != b.shape:
         raise ValueError("vectors must have the same length")
     out = C.c_float()
-    mp = None
-    if m is not None:
-        m = np.ascontiguousarray(m, dtype=np.float32)
-        mp = m.ctypes.data
-    _ffi.check(_ffi.lib().blissgpu_distance(a.ctypes.data, b.ctypes.data, a.shape[0], metric, mp, C.byref(out)))
+    _ffi.call("blissgpu_distance", a, b, a.shape[0], metric, metric_matrix(metric, m), C.byref(out))
     return float(out.value)
 
 
@@ -78,10 +83,8 @@ def mahalanobis_distance_builder(m) -> Callable[[np.ndarray, np.ndarray], float]
     return lambda a, b: mahalanobis_distance(a, b, m)
 
 
-_METRICS = {"euclidean": _ffi.METRIC_EUCLIDEAN, "cosine": _ffi.METRIC_COSINE, "mahalanobis": _ffi.METRIC_MAHALANOBIS}
-_ROUTES = {"auto": _ffi.CHAINS_AUTO, "steps": _ffi.CHAINS_STEPS, "lists": _ffi.CHAINS_LISTS}  # chain_order
-_JOURNEY_MODES = {"chain": _ffi.JOURNEY_CHAIN, "waypoint": _ffi.JOURNEY_WAYPOINT}  # journey_order
-_GATES = {None: _ffi.GATE_NONE, "up": _ffi.GATE_UP, "down": _ffi.GATE_DOWN}
+_METRICS, _ROUTES, _JOURNEY_MODES, _GATES = _ffi.METRICS, _ffi.ROUTES, _ffi.JOURNEY_MODES, _ffi.GATES
+_GROUP_MODES, _RADIO_MODES, _FORMS = _ffi.GROUP_MODES, _ffi.RADIO_MODES, _ffi.FORMS
 
 
 def pairwise_distances(A, B, metric="euclidean", m=None) -> np.ndarray:
@@ -92,12 +95,7 @@ def pairwise_distances(A, B, metric="euclidean", m=None) -> np.ndarray:
     if A.ndim != 2 or B.ndim != 2 or A.shape[1] != B.shape[1]:
         raise ValueError("A and B must be [n, d] and [m, d]")
     out = np.empty((A.shape[0], B.shape[0]), np.float32)
-    mp = None
-    if m is not None:
-        m = np.ascontiguousarray(m, dtype=np.float32)
-        mp = m.ctypes.data
-    _ffi.check(_ffi.lib().blissgpu_pairwise(A.ctypes.data, A.shape[0], B.ctypes.data, B.shape[0], A.shape[1],
-                                            _METRICS[metric], mp, out.ctypes.data))
+    _ffi.call("blissgpu_pairwise", A, A.shape[0], B, B.shape[0], A.shape[1], _METRICS[metric], metric_matrix(metric, m), out)
     return out
 
 
@@ -210,7 +208,7 @@ class Forest:
     (src/playlist.rs:230-251).  `export()` gives the canonical dense form documented in include/blissgpu.h."""
 
     def __init__(self, seeds, options: ForestOptions):
-        S = np.ascontiguousarray(np.atleast_2d(seeds), dtype=np.float32)
+        S = rows_f32(seeds)
         if not isinstance(options, ForestOptions):
             raise TypeError("options must be a ForestOptions")
         depth = options.max_tree_depth
@@ -224,8 +222,8 @@ class Forest:
         self.options, self._h = options, None
         h = C.c_void_p()
         try:
-            _ffi.check(_ffi.lib().blissgpu_forest_build(S.ctypes.data, S.shape[0], S.shape[1], options.n_trees, options.sample_size,
-                                                        depth or 0, options.extension_level, options.seed, C.byref(h)))
+            _ffi.call("blissgpu_forest_build", S, S.shape[0], S.shape[1], options.n_trees, options.sample_size, depth or 0,
+                      options.extension_level, options.seed, C.byref(h))
         except _ffi.BlissGpuError as e:
             if e.code == _ffi.ERR_INVALID:
                 raise ValueError(str(e)) from e
@@ -233,7 +231,7 @@ class Forest:
         self._h = h
         v = [C.c_uint32() for _ in range(5)]
         nn = C.c_uint64()
-        _ffi.check(_ffi.lib().blissgpu_forest_info(h, *[C.byref(x) for x in v], C.byref(nn)))
+        _ffi.call("blissgpu_forest_info", h, *[C.byref(x) for x in v], C.byref(nn))
         self.d, self.n_trees, self.psi, self.depth_limit, self.extension_level = (int(x.value) for x in v)
         self.n_nodes = int(nn.value)
 
@@ -257,11 +255,11 @@ class Forest:
         out = {"sample_idx": np.empty((T, self.psi), np.uint32), "tree_first": np.empty(T + 1, np.uint64),
                "normal": np.empty((N, d), np.float32), "b": np.empty(N, np.float32), "left": np.empty(N, np.uint32),
                "right": np.empty(N, np.uint32), "leaf_size": np.empty(N, np.uint32), "leaf_q": np.empty(N, np.uint32)}
-        _ffi.check(_ffi.lib().blissgpu_forest_export(self._h, *[a.ctypes.data for a in out.values()]))
+        _ffi.call("blissgpu_forest_export", self._h, *out.values())
         return out
 
     def _cand(self, candidates):
-        X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
+        X = rows_f32(candidates)
         if X.ndim != 2 or (X.shape[0] and X.shape[1] != self.d):
             raise ValueError(f"candidates must be [n, {self.d}]")
         return X
@@ -271,8 +269,7 @@ class Forest:
         X = self._cand(candidates)
         n = X.shape[0]
         score, ps = np.empty(n, np.float32), np.empty(n, np.uint64)
-        _ffi.check(_ffi.lib().blissgpu_forest_score(self._h, X.ctypes.data, n, score.ctypes.data,
-                                                    ps.ctypes.data if return_path_sum else None))
+        _ffi.call("blissgpu_forest_score", self._h, X, n, score, ps if return_path_sum else None)
         return (score, ps) if return_path_sum else score
 
     def closest_to_songs_order(self, candidates):
@@ -280,7 +277,7 @@ class Forest:
         X = self._cand(candidates)
         n = X.shape[0]
         order, score = np.empty(n, np.uint32), np.empty(n, np.float32)
-        _ffi.check(_ffi.lib().blissgpu_forest_closest_to_songs(self._h, X.ctypes.data, n, order.ctypes.data, score.ctypes.data))
+        _ffi.call("blissgpu_forest_closest_to_songs", self._h, X, n, order, score)
         return order, score
 
 
@@ -317,6 +314,17 @@ def _metric_of(builder):
                     "are evaluated on the GPU, arbitrary callables are not supported")
 
 
+def _plain_metric(metric_builder, why_forest, why_variance, cosine=None):
+    """(metric, m) of an entry point that compares single songs: a ForestOptions and a VarianceWeights are refused with the
+    entry point's reasons, cosine with the text `cosine` where the entry point cannot run it"""
+    _no_forest(metric_builder, why_forest)
+    _no_variance(metric_builder, why_variance)
+    metric, m = _metric_of(metric_builder)
+    if cosine is not None and metric == "cosine":
+        raise ValueError(cosine)
+    return metric, m
+
+
 def _song_of(s):
     return getattr(s, "bliss_song", s)  # AsRef<Song>
 
@@ -337,16 +345,11 @@ def _nan_to_panic(e: "_ffi.BlissGpuError"):
 def set_distances(seeds, candidates, metric="euclidean", m=None) -> np.ndarray:
     """FunctionDistanceMetric::distance (src/playlist.rs:52-58) for every row of `candidates`.  `metric` may be a
     VarianceWeights: M is then variance_based_weight_matrix(seeds)."""
-    S = np.ascontiguousarray(np.atleast_2d(seeds), dtype=np.float32)
+    S = rows_f32(seeds)
     metric, m = _seed_set_metric(metric, m, S)
-    X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
+    X = rows_f32(candidates)
     out = np.empty(X.shape[0], np.float32)
-    mp = None
-    if m is not None:
-        m = np.ascontiguousarray(m, dtype=np.float32)
-        mp = m.ctypes.data
-    _ffi.check(_ffi.lib().blissgpu_set_distance(S.ctypes.data, S.shape[0], X.ctypes.data, X.shape[0], X.shape[1],
-                                                _METRICS[metric], mp, out.ctypes.data))
+    _ffi.call("blissgpu_set_distance", S, S.shape[0], X, X.shape[0], X.shape[1], _METRICS[metric], metric_matrix(metric, m), out)
     return out
 
 
@@ -355,19 +358,12 @@ def closest_to_songs_order(seeds, candidates, metric="euclidean", m=None):
     scores are the distances; see forest_closest_to_songs_order)."""
     if isinstance(metric, ForestOptions):
         return forest_closest_to_songs_order(seeds, candidates, metric)
-    S = np.ascontiguousarray(np.atleast_2d(seeds), dtype=np.float32)
+    S = rows_f32(seeds)
     metric, m = _seed_set_metric(metric, m, S)  # (a VarianceWeights: M = variance_based_weight_matrix(seeds))
-    X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
+    X = rows_f32(candidates)
     order, dist = np.empty(X.shape[0], np.uint32), np.empty(X.shape[0], np.float32)
-    mp = None
-    if m is not None:
-        m = np.ascontiguousarray(m, dtype=np.float32)
-        mp = m.ctypes.data
-    try:
-        _ffi.check(_ffi.lib().blissgpu_closest_to_songs(S.ctypes.data, S.shape[0], X.ctypes.data, X.shape[0], X.shape[1],
-                                                        _METRICS[metric], mp, order.ctypes.data, dist.ctypes.data))
-    except _ffi.BlissGpuError as e:
-        _nan_to_panic(e)
+    _call("blissgpu_closest_to_songs", S, S.shape[0], X, X.shape[0], X.shape[1], _METRICS[metric], metric_matrix(metric, m), order,
+          dist)
     return order, dist
 
 
@@ -375,24 +371,15 @@ def song_to_song_order(seeds, candidates, metric="euclidean", m=None, k=None) ->
     """Index form of song_to_song.  `k`: only the first k songs of the chain, through one chain_order call (k steps instead
     of one per candidate); None walks the whole pool."""
     if k is not None:
-        X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
+        X = rows_f32(candidates)
         k = min(int(k), X.shape[0])
         if k < 1:
             return np.zeros(0, np.uint32)
         idx, _ = chain_order([np.atleast_2d(np.asarray(seeds, dtype=np.float32))], X, k, metric, m)
         return idx[0][idx[0] >= 0].astype(np.uint32)
-    S = np.ascontiguousarray(np.atleast_2d(seeds), dtype=np.float32)
-    X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
+    S, X = rows_f32(seeds), rows_f32(candidates)
     order = np.empty(X.shape[0], np.uint32)
-    mp = None
-    if m is not None:
-        m = np.ascontiguousarray(m, dtype=np.float32)
-        mp = m.ctypes.data
-    try:
-        _ffi.check(_ffi.lib().blissgpu_song_to_song(S.ctypes.data, S.shape[0], X.ctypes.data, X.shape[0], X.shape[1],
-                                                    _METRICS[metric], mp, order.ctypes.data))
-    except _ffi.BlissGpuError as e:
-        _nan_to_panic(e)
+    _call("blissgpu_song_to_song", S, S.shape[0], X, X.shape[0], X.shape[1], _METRICS[metric], metric_matrix(metric, m), order)
     return order
 
 
@@ -430,8 +417,8 @@ def nearest_order(queries, candidates, k, metric="euclidean", m=None, skip=None)
     `skip`: None, or one candidate index per query that is left out of that query's list (-1: none).  Passing the same
     array object as queries and candidates uploads it once.  A NaN distance raises ValueError (the reference's n32()
     panic)."""
-    X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
-    Q = X if queries is candidates else np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+    X = rows_f32(candidates)
+    Q = X if queries is candidates else rows_f32(queries)
     if Q.ndim != 2 or X.ndim != 2 or Q.shape[1] != X.shape[1]:
         raise ValueError("queries and candidates must be [q, d] and [n, d]")
     k = int(k)
@@ -439,28 +426,11 @@ def nearest_order(queries, candidates, k, metric="euclidean", m=None, skip=None)
         raise ValueError("k must be at least 1")
     q, d = Q.shape
     n = X.shape[0]
-    skip_p = None
     if skip is not None:
-        skip = np.asarray(skip, dtype=np.int64).reshape(-1)
-        if skip.shape[0] != q:
-            raise ValueError("skip needs one entry per query")
-        if ((skip < -1) | (skip >= max(n, 0))).any():
-            raise ValueError("skip entries must be candidate indices or -1")
-        skip = np.where(skip < 0, 0xFFFFFFFF, skip).astype(np.uint32)
-        skip_p = skip.ctypes.data
-    mp = None
-    if m is not None:
-        m = np.ascontiguousarray(m, dtype=np.float32)
-        mp = m.ctypes.data
+        skip = skip_words(skip, q, n)
     idx, dist = np.empty((q, k), np.uint32), np.empty((q, k), np.float32)
-    try:
-        _ffi.check(_ffi.lib().blissgpu_knn(Q.ctypes.data, q, X.ctypes.data, n, d, _METRICS[metric], mp, skip_p, k,
-                                           idx.ctypes.data, dist.ctypes.data))
-    except _ffi.BlissGpuError as e:
-        _nan_to_panic(e)
-    out = idx.astype(np.int64)
-    out[idx == 0xFFFFFFFF] = -1
-    return out, dist
+    _call("blissgpu_knn", Q, q, X, n, d, _METRICS[metric], metric_matrix(metric, m), skip, k, idx, dist)
+    return signed_idx(idx), dist
 
 
 def nearest_songs(songs, candidate_songs, k, metric_builder=euclidean_distance, exclude_self=False):
@@ -495,27 +465,18 @@ def kmeans(X, init, max_iter=100, metric="euclidean", m=None):
     "euclidean" or "mahalanobis" with m; "cosine" is refused (a mean does not minimise it).  A NaN distance raises ValueError."""
     if metric == "cosine":
         raise ValueError("k-means needs a metric its means minimise: euclidean or mahalanobis, not cosine")
-    X = np.ascontiguousarray(np.atleast_2d(X), dtype=np.float32)
-    init = np.ascontiguousarray(np.atleast_2d(init), dtype=np.float32)
+    X, init = rows_f32(X), rows_f32(init)
     if X.ndim != 2 or init.ndim != 2 or X.shape[1] != init.shape[1]:
         raise ValueError("X and init must be [n, d] and [k, d]")
     max_iter = int(max_iter)
     if max_iter < 0:
         raise ValueError("max_iter must be at least 0")
     (n, d), k = X.shape, init.shape[0]
-    mp = None
-    if m is not None:
-        m = np.ascontiguousarray(m, dtype=np.float32)
-        mp = m.ctypes.data
     labels, dist = np.empty(n, np.uint32), np.empty(n, np.float32)
     cent, sizes = np.empty((k, d), np.float32), np.empty(k, np.uint32)
     n_iter, conv = C.c_uint32(0), C.c_int32(0)
-    try:
-        _ffi.check(_ffi.lib().blissgpu_kmeans(X.ctypes.data, n, d, init.ctypes.data, k, _METRICS[metric], mp, max_iter,
-                                              labels.ctypes.data, dist.ctypes.data, cent.ctypes.data, sizes.ctypes.data,
-                                              C.byref(n_iter), C.byref(conv)))
-    except _ffi.BlissGpuError as e:
-        _nan_to_panic(e)
+    _call("blissgpu_kmeans", X, n, d, init, k, _METRICS[metric], metric_matrix(metric, m), max_iter, labels, dist, cent, sizes,
+          C.byref(n_iter), C.byref(conv))
     return labels.astype(np.int64), dist, cent, sizes.astype(np.int64), int(n_iter.value), bool(conv.value)
 
 
@@ -529,7 +490,7 @@ def kmeans_init(X, k, seed=0, method="k-means++", _device=None):
     euclidean distance to the nearest row picked so far.  Each pick's n distances come from the device (Context.pairwise against
     the last pick); the running minimum and the draw are numpy.  A row at distance 0 from the picks (a picked row, or a
     duplicate of one) is never drawn while a row at a non-zero distance exists; after that the lowest unpicked rows follow."""
-    X = np.ascontiguousarray(np.atleast_2d(X), dtype=np.float32)
+    X = rows_f32(X)
     n, k = X.shape[0], int(k)
     if method not in _KMEANS_INITS:
         raise ValueError(f"method must be one of {_KMEANS_INITS}")
@@ -594,12 +555,9 @@ class Clustering:
 
 def _kmeans_metric(metric_builder):
     """the metrics k-means can run: euclidean, or Mahalanobis with the caller's matrix"""
-    _no_forest(metric_builder, "k-means assigns single songs to centres and needs a metric its means minimise")
-    _no_variance(metric_builder, "k-means has no seed set to take variances from; pass MahalanobisBuilder(m)")
-    metric, m = _metric_of(metric_builder)
-    if metric == "cosine":
-        raise ValueError("k-means needs a metric its means minimise: euclidean or mahalanobis, not cosine")
-    return metric, m
+    return _plain_metric(metric_builder, "k-means assigns single songs to centres and needs a metric its means minimise",
+                         "k-means has no seed set to take variances from; pass MahalanobisBuilder(m)",
+                         "k-means needs a metric its means minimise: euclidean or mahalanobis, not cosine")
 
 
 def cluster_songs(songs, k, seed=0, metric_builder=euclidean_distance, max_iter=100, init="k-means++") -> Clustering:
@@ -616,22 +574,19 @@ def cluster_songs(songs, k, seed=0, metric_builder=euclidean_distance, max_iter=
 
 def _silhouette_metric(metric_builder):
     """the metrics the silhouette can run: euclidean, or Mahalanobis with the caller's matrix"""
-    _no_forest(metric_builder, "the silhouette compares single songs; a forest scores songs against a seed set")
-    _no_variance(metric_builder, "the silhouette has no seed set to take variances from; pass MahalanobisBuilder(m)")
-    metric, m = _metric_of(metric_builder)
-    if metric == "cosine":
-        raise ValueError("the silhouette needs the metric the groups are judged by: euclidean or mahalanobis, not cosine")
-    return metric, m
+    return _plain_metric(metric_builder, "the silhouette compares single songs; a forest scores songs against a seed set",
+                         "the silhouette has no seed set to take variances from; pass MahalanobisBuilder(m)",
+                         "the silhouette needs the metric the groups are judged by: euclidean or mahalanobis, not cosine")
 
 
 def _rows_of_input(songs_or_X) -> np.ndarray:
     """[n, d] float32 from an array or from songs"""
     if isinstance(songs_or_X, np.ndarray):
-        return np.ascontiguousarray(np.atleast_2d(songs_or_X), dtype=np.float32)
+        return rows_f32(songs_or_X)
     items = list(songs_or_X)
     if items and hasattr(_song_of(items[0]), "analysis"):
         return _matrix(items)
-    return np.ascontiguousarray(np.atleast_2d(np.asarray(items, dtype=np.float32)), dtype=np.float32)
+    return rows_f32(np.asarray(items, dtype=np.float32))
 
 
 def _index_array(a, what):
@@ -685,25 +640,15 @@ def silhouette(X, labels, metric_builder=euclidean_distance, rows=None, k=None, 
     if n == 0:
         raise ValueError("silhouette needs at least one song")
     k = int(lab.max()) + 1 if k is None else int(k)
-    rp, q = None, n
+    q = n
     if rows is not None:
         rows = _index_array(rows, "rows")
-        rp, q = rows.ctypes.data, rows.shape[0]
-    mp = None
-    if m is not None:
-        m = np.ascontiguousarray(m, dtype=np.float32)
-        mp = m.ctypes.data
+        q = rows.shape[0]
     s, a, b = np.zeros(q, np.float32), np.zeros(q, np.float64), np.zeros(q, np.float64)
     nb, sizes = np.zeros(q, np.uint32), np.zeros(max(k, 0), np.uint32)
-    try:
-        _ffi.check(_ffi.lib().blissgpu_silhouette(X.ctypes.data, n, d, lab.ctypes.data, k, _METRICS[metric], mp, rp, q, int(col_groups),
-                                                  s.ctypes.data, a.ctypes.data, b.ctypes.data, nb.ctypes.data, sizes.ctypes.data))
-    except _ffi.BlissGpuError as e:
-        _nan_to_panic(e)
+    _call("blissgpu_silhouette", X, n, d, lab, k, _METRICS[metric], metric_matrix(metric, m), rows, q, int(col_groups), s, a, b, nb,
+          sizes)
     return Silhouette(s, a, b, nb, sizes, lab if rows is None else lab[rows])
-
-
-_GROUP_MODES = {"symmetric": _ffi.GROUPS_SYMMETRIC, "directed": _ffi.GROUPS_DIRECTED}
 
 
 @dataclasses.dataclass
@@ -720,12 +665,9 @@ class GroupNeighbours:
 
 def _group_neighbours_metric(metric_builder):
     """the metrics the group distances can run: euclidean, or Mahalanobis with the caller's matrix"""
-    _no_forest(metric_builder, "the group distances compare single songs; a forest scores songs against a seed set")
-    _no_variance(metric_builder, "the group distances have no seed set to take variances from; pass MahalanobisBuilder(m)")
-    metric, m = _metric_of(metric_builder)
-    if metric == "cosine":
-        raise ValueError("the group distances need a distance a nearest member is defined with: euclidean or mahalanobis, not cosine")
-    return metric, m
+    return _plain_metric(metric_builder, "the group distances compare single songs; a forest scores songs against a seed set",
+                         "the group distances have no seed set to take variances from; pass MahalanobisBuilder(m)",
+                         "the group distances need a distance a nearest member is defined with: euclidean or mahalanobis, not cosine")
 
 
 def group_neighbours(songs_or_X, labels, t, metric_builder=euclidean_distance, k=None, queries=None, mode="symmetric", matrix=False,
@@ -754,36 +696,23 @@ def group_neighbours(songs_or_X, labels, t, metric_builder=euclidean_distance, k
     n, d = X.shape
     k = (int(lab.max()) + 1 if n else 1) if k is None else int(k)
     t = int(t)
-    qp, q = None, max(k, 0)
+    q = max(k, 0)
     if queries is not None:
         queries = _index_array(queries, "queries")
-        qp, q = queries.ctypes.data, queries.shape[0]
-    mp = None
-    if m is not None:
-        m = np.ascontiguousarray(m, dtype=np.float32)
-        mp = m.ctypes.data
+        q = queries.shape[0]
     idx, dist = np.full((q, max(t, 0)), 0xFFFFFFFF, np.uint32), np.full((q, max(t, 0)), np.inf, np.float64)
     sizes = np.zeros(max(k, 0), np.uint32)
     mat = np.zeros((max(k, 0), max(k, 0)), np.float64) if matrix else None
-    try:
-        _ffi.check(_ffi.lib().blissgpu_group_neighbours(X.ctypes.data, n, d, lab.ctypes.data, k, _METRICS[metric], mp, qp, q, t,
-                                                        _GROUP_MODES[mode], int(slab_groups), idx.ctypes.data, dist.ctypes.data,
-                                                        sizes.ctypes.data, None if mat is None else mat.ctypes.data))
-    except _ffi.BlissGpuError as e:
-        _nan_to_panic(e)
-    out = idx.astype(np.int64)
-    out[idx == 0xFFFFFFFF] = -1
-    return GroupNeighbours(out, dist, sizes.astype(np.int64), mat)
+    _call("blissgpu_group_neighbours", X, n, d, lab, k, _METRICS[metric], metric_matrix(metric, m), queries, q, t, _GROUP_MODES[mode],
+          int(slab_groups), idx, dist, sizes, mat)
+    return GroupNeighbours(signed_idx(idx), dist, sizes.astype(np.int64), mat)
 
 
 def _mst_metric(metric_builder):
     """the metrics the spanning tree can run: euclidean, or Mahalanobis with the caller's matrix"""
-    _no_forest(metric_builder, "the spanning tree compares single songs; a forest scores songs against a seed set")
-    _no_variance(metric_builder, "the spanning tree has no seed set to take variances from; pass MahalanobisBuilder(m)")
-    metric, m = _metric_of(metric_builder)
-    if metric == "cosine":
-        raise ValueError("the spanning tree needs a distance whose bits order as integers: euclidean or mahalanobis, not cosine")
-    return metric, m
+    return _plain_metric(metric_builder, "the spanning tree compares single songs; a forest scores songs against a seed set",
+                         "the spanning tree has no seed set to take variances from; pass MahalanobisBuilder(m)",
+                         "the spanning tree needs a distance whose bits order as integers: euclidean or mahalanobis, not cosine")
 
 
 def _uf_find(parent, x):
@@ -909,27 +838,19 @@ def minimum_spanning_tree(songs_or_X, metric_builder=euclidean_distance, min_sam
     X = _rows_of_input(songs_or_X)
     n, d = X.shape
     core = None if min_samples is None else core_distances(X, min_samples, metric_builder)
-    mp = None
-    if m is not None:
-        m = np.ascontiguousarray(m, dtype=np.float32)
-        mp = m.ctypes.data
     e = max(n - 1, 0)
     u, v, w = np.zeros(e, np.uint32), np.zeros(e, np.uint32), np.zeros(e, np.float32)
     rounds = C.c_uint32(0)
-    _ffi.check(_ffi.lib().blissgpu_mst(X.ctypes.data, n, d, _METRICS[metric], mp, None if core is None else core.ctypes.data,
-                                       u.ctypes.data, v.ctypes.data, w.ctypes.data, C.byref(rounds)))
+    _ffi.call("blissgpu_mst", X, n, d, _METRICS[metric], metric_matrix(metric, m), core, u, v, w, C.byref(rounds))
     return SpanningTree(u.astype(np.int64), v.astype(np.int64), w, int(rounds.value), n)
 
 
 # ---- Ward clustering: the whole dendrogram (blissgpu_ward / blissgpu_ward_nearest) ----
 def _ward_metric(metric_builder):
     """the metrics Ward clustering can run: euclidean, or Mahalanobis with the caller's matrix"""
-    _no_forest(metric_builder, "Ward clustering merges clusters by their centroids; a forest scores songs against a seed set")
-    _no_variance(metric_builder, "Ward clustering has no seed set to take variances from; pass MahalanobisBuilder(m)")
-    metric, m = _metric_of(metric_builder)
-    if metric == "cosine":
-        raise ValueError("Ward clustering needs a metric whose squares its centroids minimise: euclidean or mahalanobis, not cosine")
-    return metric, m
+    return _plain_metric(metric_builder, "Ward clustering merges clusters by their centroids; a forest scores songs against a seed set",
+                         "Ward clustering has no seed set to take variances from; pass MahalanobisBuilder(m)",
+                         "Ward clustering needs a metric whose squares its centroids minimise: euclidean or mahalanobis, not cosine")
 
 
 def ward_nearest(C_rows, sizes=None, metric_builder=euclidean_distance):
@@ -940,21 +861,13 @@ def ward_nearest(C_rows, sizes=None, metric_builder=euclidean_distance):
     metric, m = _ward_metric(metric_builder)
     X = _rows_of_input(C_rows)
     n, d = X.shape
-    sp = None
     if sizes is not None:
         sizes = _index_array(sizes, "sizes")
         if sizes.shape[0] != n:
             raise ValueError("a size per row is needed")
-        sp = sizes.ctypes.data
-    mp = None
-    if m is not None:
-        m = np.ascontiguousarray(m, dtype=np.float32)
-        mp = m.ctypes.data
     nn, cost = np.zeros(n, np.uint32), np.zeros(n, np.float32)
-    _ffi.check(_ffi.lib().blissgpu_ward_nearest(X.ctypes.data, sp, n, d, _METRICS[metric], mp, nn.ctypes.data, cost.ctypes.data))
-    out = nn.astype(np.int64)
-    out[nn == 0xFFFFFFFF] = -1
-    return out, cost
+    _ffi.call("blissgpu_ward_nearest", X, sizes, n, d, _METRICS[metric], metric_matrix(metric, m), nn, cost)
+    return signed_idx(nn), cost
 
 
 @dataclasses.dataclass
@@ -1042,32 +955,19 @@ def ward_tree(songs_or_X, metric_builder=euclidean_distance) -> WardTree:
     metric, m = _ward_metric(metric_builder)
     X = _rows_of_input(songs_or_X)
     n, d = X.shape
-    mp = None
-    if m is not None:
-        m = np.ascontiguousarray(m, dtype=np.float32)
-        mp = m.ctypes.data
     e = max(n - 1, 0)
     u, v, size, rnd = (np.zeros(e, np.uint32) for _ in range(4))
     cost = np.zeros(e, np.float32)
     rounds = C.c_uint32(0)
-    _ffi.check(_ffi.lib().blissgpu_ward(X.ctypes.data, n, d, _METRICS[metric], mp, u.ctypes.data, v.ctypes.data, cost.ctypes.data,
-                                        size.ctypes.data, rnd.ctypes.data, C.byref(rounds)))
+    _ffi.call("blissgpu_ward", X, n, d, _METRICS[metric], metric_matrix(metric, m), u, v, cost, size, rnd, C.byref(rounds))
     return WardTree(u.astype(np.int64), v.astype(np.int64), cost, size.astype(np.int64), rnd.astype(np.int64), int(rounds.value), n)
 
 
 # ---- k-medoids: K songs that summarise a library, under any metric (blissgpu_kmedoids / blissgpu_pam_scan) ----
 def _pam_metric(metric_builder):
     """the metrics k-medoids can run: every one the all-pairs kernel knows -- euclidean, cosine, Mahalanobis with the caller's M"""
-    _no_forest(metric_builder, "k-medoids compares single songs; a forest scores songs against a seed set")
-    _no_variance(metric_builder, "k-medoids has no seed set to take variances from; pass MahalanobisBuilder(m)")
-    return _metric_of(metric_builder)
-
-
-def _pam_m(m):
-    if m is None:
-        return None, None
-    m = np.ascontiguousarray(m, dtype=np.float32)
-    return m, m.ctypes.data
+    return _plain_metric(metric_builder, "k-medoids compares single songs; a forest scores songs against a seed set",
+                         "k-medoids has no seed set to take variances from; pass MahalanobisBuilder(m)")
 
 
 def pam_scan(songs_or_X, near, d1, d2, k, metric_builder=euclidean_distance, rows=None, return_sums=False):
@@ -1086,17 +986,14 @@ def pam_scan(songs_or_X, near, d1, d2, k, metric_builder=euclidean_distance, row
     d2 = np.ascontiguousarray(d2, dtype=np.float32).reshape(-1)
     if not (near.shape[0] == d1.shape[0] == d2.shape[0] == n):
         raise ValueError("near, d1 and d2 hold one entry per row")
-    rp, q = None, n
+    q = n
     if rows is not None:
         rows = _index_array(rows, "rows")
-        rp, q = rows.ctypes.data, rows.shape[0]
-    m, mp = _pam_m(m)
+        q = rows.shape[0]
     btot, best, arg = np.zeros(q, np.float64), np.zeros(q, np.float64), np.zeros(q, np.uint32)
     A = np.zeros((q, k), np.float64) if return_sums else None
     B = np.zeros((q, k), np.float64) if return_sums else None
-    _ffi.check(_ffi.lib().blissgpu_pam_scan(X.ctypes.data, n, d, near.ctypes.data, d1.ctypes.data, d2.ctypes.data, k, _METRICS[metric], mp,
-                                            rp, q, btot.ctypes.data, best.ctypes.data, arg.ctypes.data,
-                                            A.ctypes.data if return_sums else None, B.ctypes.data if return_sums else None))
+    _ffi.call("blissgpu_pam_scan", X, n, d, near, d1, d2, k, _METRICS[metric], metric_matrix(metric, m), rows, q, btot, best, arg, A, B)
     out = (btot, best, arg.astype(np.int64))
     return out + (A, B) if return_sums else out
 
@@ -1137,23 +1034,22 @@ def kmedoids(songs_or_X, k, metric_builder=euclidean_distance, init="build", max
     k = int(k)
     if not 1 <= k <= max(n, 1):
         raise ValueError("k must be 1 .. the number of rows")
-    ip = None
-    if not (isinstance(init, str) and init == "build"):
-        if isinstance(init, str):
+    if isinstance(init, str):
+        if init != "build":
             raise ValueError('init must be "build" or k row indices')
+        init = None
+    else:
         init = _index_array(init, "init")
         if init.shape[0] != k:
             raise ValueError("init must hold k row indices")
-        ip = init.ctypes.data
     max_swaps = 4 * k + 64 if max_swaps is None else int(max_swaps)
     if max_swaps < 0:
         raise ValueError("max_swaps must be at least 0")
-    m, mp = _pam_m(m)
     med, sizes, labels = np.zeros(k, np.uint32), np.zeros(k, np.uint32), np.zeros(n, np.uint32)
     dist, trace = np.zeros(n, np.float32), np.zeros(max_swaps + 1, np.float64)
     swaps, conv = C.c_uint32(0), C.c_int32(0)
-    _ffi.check(_ffi.lib().blissgpu_kmedoids(X.ctypes.data, n, d, k, _METRICS[metric], mp, ip, max_swaps, med.ctypes.data, labels.ctypes.data,
-                                            dist.ctypes.data, sizes.ctypes.data, trace.ctypes.data, C.byref(swaps), C.byref(conv)))
+    _ffi.call("blissgpu_kmedoids", X, n, d, k, _METRICS[metric], metric_matrix(metric, m), init, max_swaps, med, labels, dist, sizes,
+              trace, C.byref(swaps), C.byref(conv))
     trace = trace[: int(swaps.value) + 1] if n else trace[:0]
     return Medoids(med.astype(np.int64), labels.astype(np.int64), dist, sizes.astype(np.int64), float(trace[-1]) if n else 0.0, trace,
                    int(swaps.value), bool(conv.value))
@@ -1179,9 +1075,8 @@ SCALE_MIN, SCALE_MAX = np.float32(2.0 ** -60), np.float32(2.0 ** 60)  # the scal
 
 
 def _scaled_metric(metric_builder, what):
-    _no_forest(metric_builder, f"{what} compares single songs; a forest scores songs against a seed set")
-    _no_variance(metric_builder, f"{what} has no seed set to take variances from; pass MahalanobisBuilder(m)")
-    return _metric_of(metric_builder)
+    return _plain_metric(metric_builder, f"{what} compares single songs; a forest scores songs against a seed set",
+                         f"{what} has no seed set to take variances from; pass MahalanobisBuilder(m)")
 
 
 def scales_from_distances(dist, m, kind="mean") -> np.ndarray:
@@ -1239,8 +1134,8 @@ def scaled_nearest_order(queries, qscale, candidates, cscale, k, metric="euclide
     distances come in candidate order; rows with fewer than k eligible candidates end in -1 / inf.  Scales must lie in
     [2^-60, 2^60] (local_scales / scales_from_distances return such), else BlissGpuError(ERR_INVALID).  Passing the same array
     objects as queries / candidates and as qscale / cscale uploads each once.  A NaN distance raises ValueError."""
-    X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
-    Q = X if queries is candidates else np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+    X = rows_f32(candidates)
+    Q = X if queries is candidates else rows_f32(queries)
     if Q.ndim != 2 or X.ndim != 2 or Q.shape[1] != X.shape[1]:
         raise ValueError("queries and candidates must be [q, d] and [n, d]")
     cs = np.ascontiguousarray(cscale, dtype=np.float32).reshape(-1)
@@ -1252,28 +1147,11 @@ def scaled_nearest_order(queries, qscale, candidates, cscale, k, metric="euclide
     n = X.shape[0]
     if qs.shape[0] != q or cs.shape[0] != n:
         raise ValueError("qscale needs one entry per query and cscale one per candidate")
-    skip_p = None
     if skip is not None:
-        skip = np.asarray(skip, dtype=np.int64).reshape(-1)
-        if skip.shape[0] != q:
-            raise ValueError("skip needs one entry per query")
-        if ((skip < -1) | (skip >= max(n, 0))).any():
-            raise ValueError("skip entries must be candidate indices or -1")
-        skip = np.where(skip < 0, 0xFFFFFFFF, skip).astype(np.uint32)
-        skip_p = skip.ctypes.data
-    mp = None
-    if m is not None:
-        m = np.ascontiguousarray(m, dtype=np.float32)
-        mp = m.ctypes.data
+        skip = skip_words(skip, q, n)
     idx, dist = np.empty((q, k), np.uint32), np.empty((q, k), np.float32)
-    try:
-        _ffi.check(_ffi.lib().blissgpu_scaled_knn(Q.ctypes.data, q, qs.ctypes.data, X.ctypes.data, n, cs.ctypes.data, d,
-                                                  _METRICS[metric], mp, skip_p, k, idx.ctypes.data, dist.ctypes.data))
-    except _ffi.BlissGpuError as e:
-        _nan_to_panic(e)
-    out = idx.astype(np.int64)
-    out[idx == 0xFFFFFFFF] = -1
-    return out, dist
+    _call("blissgpu_scaled_knn", Q, q, qs, X, n, cs, d, _METRICS[metric], metric_matrix(metric, m), skip, k, idx, dist)
+    return signed_idx(idx), dist
 
 
 def _lists(idx):
@@ -1282,9 +1160,7 @@ def _lists(idx):
     if idx.ndim != 2:
         raise ValueError("idx must be [q, k]")
     if idx.dtype == np.uint32:
-        out = idx.astype(np.int64)
-        out[idx == 0xFFFFFFFF] = -1
-        return out
+        return signed_idx(idx)
     out = idx.astype(np.int64)
     if (out < -1).any() or (out >= 0xFFFFFFFF).any():
         raise ValueError("idx entries must be song indices or -1")
@@ -1304,7 +1180,7 @@ def k_occurrence(idx, n) -> np.ndarray:
         raise ValueError("idx needs at least one column")
     u = np.ascontiguousarray(np.where(L < 0, 0xFFFFFFFF, L), dtype=np.uint32)
     count = np.zeros(max(n, 1), np.uint32)
-    _ffi.check(_ffi.lib().blissgpu_knn_occurrence(u.ctypes.data if q else None, q, k, n, count.ctypes.data if n else None))
+    _ffi.call("blissgpu_knn_occurrence", u if q else None, q, k, n, count if n else None)
     return count[:n].astype(np.int64)
 
 
@@ -1504,7 +1380,7 @@ def _map_col_groups(col_groups):
 def map_plan(n, n_cus=0) -> int:
     """The column groups col_groups = 0 stands for on a device of n_cus compute units (blissgpu_map_plan; device-free)."""
     out = C.c_uint32(0)
-    _ffi.check(_ffi.lib().blissgpu_map_plan(int(n), int(n_cus), C.byref(out)))
+    _ffi.call("blissgpu_map_plan", int(n), int(n_cus), C.byref(out))
     return int(out.value)
 
 
@@ -1519,8 +1395,7 @@ def map_step(Y, row_offsets, cols, vals, exaggeration=1.0, col_groups=0):
     if not np.isfinite(exaggeration):
         raise ValueError("exaggeration must be finite")
     grad, z_rows, Z = np.zeros((n, 2), np.float64), np.zeros(n, np.float64), C.c_double(0.0)
-    _ffi.check(_ffi.lib().blissgpu_map_step(Y.ctypes.data, n, ro.ctypes.data, co.ctypes.data, va.ctypes.data, exaggeration,
-                                            _map_col_groups(col_groups), grad.ctypes.data, z_rows.ctypes.data, C.byref(Z)))
+    _ffi.call("blissgpu_map_step", Y, n, ro, co, va, exaggeration, _map_col_groups(col_groups), grad, z_rows, C.byref(Z))
     return grad, z_rows, float(Z.value)
 
 
@@ -1540,8 +1415,7 @@ def map_layout(Y0, row_offsets, cols, vals, n_iter=750, exag_iters=250, exaggera
     if not np.isfinite(params).all():
         raise ValueError("exaggeration, learning_rate, the momenta and min_gain must be finite")
     Y, trace = np.zeros((n, 2), np.float32), np.zeros(n_iter, np.float64)
-    _ffi.check(_ffi.lib().blissgpu_map_layout(Y0.ctypes.data, n, ro.ctypes.data, co.ctypes.data, va.ctypes.data, n_iter, exag_iters,
-                                              *params, _map_col_groups(col_groups), Y.ctypes.data, trace.ctypes.data))
+    _ffi.call("blissgpu_map_layout", Y0, n, ro, co, va, n_iter, exag_iters, *params, _map_col_groups(col_groups), Y, trace)
     return Y, trace
 
 
@@ -1714,15 +1588,14 @@ def choose_k_tree(songs_or_X, tree: "WardTree", ks, metric_builder=euclidean_dis
 
 
 def _triplet_args(X, triplets, m):
-    X = np.ascontiguousarray(np.atleast_2d(X), dtype=np.float32)
+    X = rows_f32(X)
     tr = np.asarray(triplets)
     if tr.size and (tr.min() < 0 or tr.max() > 0xFFFFFFFF):
         raise ValueError("triplets must be row indices")
     tr = np.ascontiguousarray(tr, dtype=np.uint32).reshape(-1, 3)
-    if m is not None:
-        m = np.ascontiguousarray(m, dtype=np.float32)
-        if m.shape != (X.shape[1], X.shape[1]):
-            raise ValueError("m must be [d, d]")
+    m = metric_matrix(None, m)  # (None: the identity)
+    if m is not None and m.shape != (X.shape[1], X.shape[1]):
+        raise ValueError("m must be [d, d]")
     return X, tr, m
 
 
@@ -1738,18 +1611,12 @@ def triplet_step(X, triplets, m=None, margin=0.0, return_flags=False):
     (n, d), T = X.shape, tr.shape[0]
     G, flags = np.zeros((d, d), np.float64), np.zeros(T, np.uint8)
     n_active, loss = C.c_uint64(0), C.c_double(0.0)
-    try:
-        _ffi.check(_ffi.lib().blissgpu_triplet_step(X.ctypes.data, n, d, tr.ctypes.data if T else None, T,
-                                                    None if m is None else m.ctypes.data, float(margin),
-                                                    flags.ctypes.data if return_flags and T else None, C.byref(n_active),
-                                                    C.byref(loss), G.ctypes.data))
-    except _ffi.BlissGpuError as e:
-        _nan_to_panic(e)
+    _call("blissgpu_triplet_step", X, n, d, tr if T else None, T, m, float(margin), flags if return_flags and T else None,
+          C.byref(n_active), C.byref(loss), G)
     out = (int(n_active.value), float(loss.value), G)
     return out + (flags,) if return_flags else out
 
 
-_FORMS = {"diagonal": _ffi.METRIC_FORM_DIAGONAL, "full": _ffi.METRIC_FORM_FULL}
 _LEARN_STATUS = {_ffi.LEARN_CONVERGED: "converged", _ffi.LEARN_MAX_ITER: "max_iter", _ffi.LEARN_DIVERGED: "diverged"}
 # DESIGN.md 3.22 has the table behind these (planted metrics, numpy on a CPU); nobody has measured them on a real library
 LEARN_MARGIN, LEARN_LR, LEARN_MAX_ITER = 0.1, 1.0, 100
@@ -1809,13 +1676,8 @@ def learn_metric(X, triplets, form="full", init=None, margin=LEARN_MARGIN, lr=LE
     init, max_iter = _learn_args(form, init, d, max_iter)
     M, obj, act = np.zeros((d, d), np.float32), np.zeros(max_iter + 1, np.float64), np.zeros(max_iter + 1, np.uint64)
     n_iter, best_iter, status = C.c_uint32(0), C.c_uint32(0), C.c_int32(0)
-    try:
-        _ffi.check(_ffi.lib().blissgpu_learn_metric(X.ctypes.data, n, d, tr.ctypes.data if T else None, T, _FORMS[form],
-                                                    None if init is None else init.ctypes.data, float(margin), float(lr),
-                                                    float(reg), max_iter, M.ctypes.data, obj.ctypes.data, act.ctypes.data,
-                                                    C.byref(n_iter), C.byref(best_iter), C.byref(status)))
-    except _ffi.BlissGpuError as e:
-        _nan_to_panic(e)
+    _call("blissgpu_learn_metric", X, n, d, tr if T else None, T, _FORMS[form], init, float(margin), float(lr), float(reg), max_iter, M,
+          obj, act, C.byref(n_iter), C.byref(best_iter), C.byref(status))
     return _learned(M, obj, act, n_iter, best_iter, status)
 
 
@@ -1852,7 +1714,7 @@ def moments(X, labels=None, k=None, scatter=True) -> Moments:
     BlissGpuError(ERR_INVALID), a NaN or an infinity in X ValueError."""
     X = _rows_of_input(X)
     n, d = X.shape
-    lp = None
+    lab = None
     if labels is None:
         k = 1 if k is None else int(k)
     else:
@@ -1860,16 +1722,11 @@ def moments(X, labels=None, k=None, scatter=True) -> Moments:
         if lab.shape[0] != n:
             raise ValueError("a label per row of X is needed")
         k = (int(lab.max()) + 1 if n else 1) if k is None else int(k)
-        lp = lab.ctypes.data
     kk = max(k, 0)
     counts, mean, m2 = np.zeros(kk, np.uint32), np.zeros((kk, d), np.float64), np.zeros((kk, d), np.float64)
     mn, mx = np.zeros((kk, d), np.float32), np.zeros((kk, d), np.float32)
     S = np.zeros((d, d), np.float64) if scatter else None
-    try:
-        _ffi.check(_ffi.lib().blissgpu_moments(X.ctypes.data, n, d, lp, k, counts.ctypes.data, mean.ctypes.data, m2.ctypes.data,
-                                               mn.ctypes.data, mx.ctypes.data, None if S is None else S.ctypes.data))
-    except _ffi.BlissGpuError as e:
-        _nan_to_panic(e)
+    _call("blissgpu_moments", X, n, d, lab, k, counts, mean, m2, mn, mx, S)
     return Moments(counts, mean, m2, mn, mx, S)
 
 
@@ -1906,7 +1763,7 @@ def metric_from_scatter(scatter, dof, form="full", shrink=COV_SHRINK) -> np.ndar
     if S.shape != (d, d):
         raise ValueError("scatter must be a square matrix")
     M, status = np.zeros((d, d), np.float32), C.c_int32(0)
-    _ffi.check(_ffi.lib().blissgpu_covariance_metric(S.ctypes.data, d, int(dof), _FORMS[form], shrink, M.ctypes.data, C.byref(status)))
+    _ffi.call("blissgpu_covariance_metric", S, d, int(dof), _FORMS[form], shrink, M, C.byref(status))
     if status.value != _ffi.COV_OK:
         raise ValueError(f"the covariance is not positive definite at shrink = {shrink:g} (a constant feature, or fewer rows than "
                          "features): raise shrink")
@@ -2037,7 +1894,7 @@ def nearest_to_groups(seed_groups, candidates, k, metric="euclidean", m=None, sk
     the group sizes before the device is touched)."""
     _no_forest(metric, "nearest_to_groups takes the distance metrics; forest_nearest_to_groups builds one forest per seed group")
     S, off = _seed_groups(seed_groups)
-    X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
+    X = rows_f32(candidates)
     if X.ndim != 2 or (S is not None and S.shape[1] != X.shape[1]):
         raise ValueError("seed groups and candidates must be [s_g, d] and [n, d]")
     if isinstance(metric, VarianceWeights):
@@ -2047,43 +1904,22 @@ def nearest_to_groups(seed_groups, candidates, k, metric="euclidean", m=None, sk
     if not per_group and metric not in _METRICS:
         raise ValueError(f"unknown metric {metric!r}")
     k = int(k)
-    if not 1 <= k <= 1024:
-        raise ValueError("k must be 1 .. 1024")
     n, d = X.shape
-    if not 1 <= d <= 64:
-        raise ValueError("d must be 1 .. 64")
-    G, total = off.shape[0] - 1, int(off[-1])
+    check_k_d(k, d)
+    G = off.shape[0] - 1
     skip = _group_skip(skip, off, n)
-    skip_p = None if skip is None else skip.ctypes.data
-    mp = None
-    if metric == "mahalanobis":
-        if m is None:
-            raise ValueError("mahalanobis needs m")
-        m = np.ascontiguousarray(m, dtype=np.float32)
-        if m.shape != (d, d):
-            raise ValueError("m must be [d, d]")
-        mp = m.ctypes.data
-    elif metric == "diagonal":
+    if metric == "diagonal":
         if m is None:
             raise ValueError("diagonal needs m, one row of d weights per group")
-        m = np.ascontiguousarray(m, dtype=np.float32)
-        if m.shape != (G, d):
-            raise ValueError("m must be [G, d]")
-        mp = m.ctypes.data
+        m = metric_matrix(metric, m, d, groups=G)
+    else:
+        m = metric_matrix(metric, m, d)
     idx, dist = np.empty((G, k), np.uint32), np.empty((G, k), np.float32)
-    try:
-        if per_group:
-            _ffi.check(_ffi.lib().blissgpu_group_knn_weighted(None if S is None else S.ctypes.data, off.ctypes.data, G,
-                                                              X.ctypes.data, n, d, mp, skip_p, k, idx.ctypes.data,
-                                                              dist.ctypes.data, None))
-        else:
-            _ffi.check(_ffi.lib().blissgpu_group_knn(None if S is None else S.ctypes.data, off.ctypes.data, G, X.ctypes.data, n,
-                                                     d, _METRICS[metric], mp, skip_p, k, idx.ctypes.data, dist.ctypes.data))
-    except _ffi.BlissGpuError as e:
-        _nan_to_panic(e)
-    out = idx.astype(np.int64)
-    out[idx == 0xFFFFFFFF] = -1
-    return out, dist
+    if per_group:
+        _call("blissgpu_group_knn_weighted", S, off, G, X, n, d, m, skip, k, idx, dist, None)
+    else:
+        _call("blissgpu_group_knn", S, off, G, X, n, d, _METRICS[metric], m, skip, k, idx, dist)
+    return signed_idx(idx), dist
 
 
 def group_variance_weights(seed_groups):
@@ -2102,8 +1938,7 @@ def group_variance_weights(seed_groups):
     if not 1 <= d <= 64:
         raise ValueError("d must be 1 .. 64")
     weights, status = np.empty((G, d), np.float32), np.empty(G, np.int32)
-    _ffi.check(_ffi.lib().blissgpu_group_weights(S.ctypes.data if S.shape[0] else None, off.ctypes.data, G, d,
-                                                 weights.ctypes.data, status.ctypes.data))
+    _ffi.call("blissgpu_group_weights", S if S.shape[0] else None, off, G, d, weights, status)
     return weights, status != 0
 
 
@@ -2172,15 +2007,12 @@ def forest_nearest_to_groups(seed_groups, candidates, k, options, skip=None, few
     "empty" gives such a group a row of -1 / inf."""
     S, off = _seed_groups(seed_groups)
     _forest_few_seeds(few_seeds, np.diff(off.astype(np.int64)), options)
-    X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
+    X = rows_f32(candidates)
     if X.ndim != 2 or (S is not None and S.shape[1] != X.shape[1]):
         raise ValueError("seed groups and candidates must be [s_g, d] and [n, d]")
     k = int(k)
-    if not 1 <= k <= 1024:
-        raise ValueError("k must be 1 .. 1024")
     n, d = X.shape
-    if not 1 <= d <= 32:
-        raise ValueError("d must be 1 .. 32")
+    check_k_d(k, d, 32)
     depth = options.max_tree_depth
     if depth is not None and not 1 <= depth <= 128:
         raise ValueError("max_tree_depth must be None or 1 .. 128")
@@ -2191,17 +2023,13 @@ def forest_nearest_to_groups(seed_groups, candidates, k, options, skip=None, few
     skip = _group_skip(skip, off, n)
     idx, score, status = np.empty((G, k), np.uint32), np.empty((G, k), np.float32), np.zeros(G, np.int32)
     try:
-        _ffi.check(_ffi.lib().blissgpu_group_forest_knn(None if S is None else S.ctypes.data, off.ctypes.data, G, X.ctypes.data, n, d,
-                                                        options.n_trees, options.sample_size, depth or 0, options.extension_level,
-                                                        options.seed, None if skip is None else skip.ctypes.data, k,
-                                                        idx.ctypes.data, score.ctypes.data, status.ctypes.data))
+        _ffi.call("blissgpu_group_forest_knn", S, off, G, X, n, d, options.n_trees, options.sample_size, depth or 0,
+                  options.extension_level, options.seed, skip, k, idx, score, status)
     except _ffi.BlissGpuError as e:
         if e.code == _ffi.ERR_INVALID:
             raise ValueError(str(e)) from e
         raise
-    out = idx.astype(np.int64)
-    out[idx == 0xFFFFFFFF] = -1
-    return out, score
+    return signed_idx(idx), score
 
 
 def forest_group_playlists(groups, candidate_songs, k, options, exclude_members=True, few_seeds="raise"):
@@ -2241,7 +2069,7 @@ def chain_order(seed_groups, candidates, k, metric="euclidean", m=None, skip=Non
     _no_forest(metric, "song_to_song rebuilds its metric from one song after the first step (:285-295)")
     _no_variance(metric, "song_to_song rebuilds its metric from one song after the first step (:285-295)")
     S, off = _seed_groups(seed_groups)
-    X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
+    X = rows_f32(candidates)
     if X.ndim != 2 or (S is not None and S.shape[1] != X.shape[1]):
         raise ValueError("seed groups and candidates must be [s_g, d] and [n, d]")
     if metric not in _METRICS:
@@ -2249,33 +2077,16 @@ def chain_order(seed_groups, candidates, k, metric="euclidean", m=None, skip=Non
     if route not in _ROUTES:
         raise ValueError(f"route must be one of {tuple(_ROUTES)}")
     k = int(k)
-    if not 1 <= k <= 1024:
-        raise ValueError("k must be 1 .. 1024")
     n, d = X.shape
-    if not 1 <= d <= 64:
-        raise ValueError("d must be 1 .. 64")
+    check_k_d(k, d)
     G = off.shape[0] - 1
     if route == "lists" and k >= 2 and G and k + int(np.diff(off.astype(np.int64)).max()) - 1 > 1024:
         raise ValueError("the lists route needs k + largest group - 1 <= 1024")
     skip = _group_skip(skip, off, n)
-    skip_p = None if skip is None else skip.ctypes.data
-    mp = None
-    if metric == "mahalanobis":
-        if m is None:
-            raise ValueError("mahalanobis needs m")
-        m = np.ascontiguousarray(m, dtype=np.float32)
-        if m.shape != (d, d):
-            raise ValueError("m must be [d, d]")
-        mp = m.ctypes.data
+    m = metric_matrix(metric, m, d)
     idx, dist = np.empty((G, k), np.uint32), np.empty((G, k), np.float32)
-    try:
-        _ffi.check(_ffi.lib().blissgpu_chains(None if S is None else S.ctypes.data, off.ctypes.data, G, X.ctypes.data, n, d,
-                                              _METRICS[metric], mp, skip_p, k, _ROUTES[route], idx.ctypes.data, dist.ctypes.data))
-    except _ffi.BlissGpuError as e:
-        _nan_to_panic(e)
-    out = idx.astype(np.int64)
-    out[idx == 0xFFFFFFFF] = -1
-    return out, dist
+    _call("blissgpu_chains", S, off, G, X, n, d, _METRICS[metric], m, skip, k, _ROUTES[route], idx, dist)
+    return signed_idx(idx), dist
 
 
 def song_chains(groups, candidate_songs, k, metric_builder=euclidean_distance, exclude_members=True):
@@ -2313,13 +2124,12 @@ def journey_order(from_rows, candidates, k, to_rows=None, metric="euclidean", m=
     of an eligible candidate raises ValueError.  VarianceWeights and ForestOptions are refused."""
     _no_forest(metric, _JOURNEY_WHY)
     _no_variance(metric, _JOURNEY_WHY)
-    A = np.ascontiguousarray(np.atleast_2d(from_rows), dtype=np.float32)
-    X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
+    A, X = rows_f32(from_rows), rows_f32(candidates)
     if A.ndim != 2 or X.ndim != 2 or A.shape[1] != X.shape[1]:
         raise ValueError("from_rows and candidates must be [G, d] and [n, d]")
     B = None
     if to_rows is not None:
-        B = np.ascontiguousarray(np.atleast_2d(to_rows), dtype=np.float32)
+        B = rows_f32(to_rows)
         if B.shape != A.shape:
             raise ValueError("to_rows must have the shape of from_rows")
     if metric not in _METRICS:
@@ -2327,44 +2137,21 @@ def journey_order(from_rows, candidates, k, to_rows=None, metric="euclidean", m=
     if direction not in _GATES:
         raise ValueError('direction must be None, "up" or "down"')
     k = int(k)
-    if not 1 <= k <= 1024:
-        raise ValueError("k must be 1 .. 1024")
     (G, d), n = A.shape, X.shape[0]
-    if not 1 <= d <= 64:
-        raise ValueError("d must be 1 .. 64")
+    check_k_d(k, d)
     if direction is not None:
         if B is not None:
             raise ValueError("a direction cannot be combined with to_rows")
         if feature is None or not 0 <= int(feature) < d:
             raise ValueError("a direction needs a feature: an AnalysisIndex or a column number below d")
-    skip_p = None
     if skip is not None:
-        skip = np.asarray(skip, dtype=np.int64)
-        if skip.shape != (G, 2):
-            raise ValueError("skip must be [G, 2]")
-        if ((skip < -1) | (skip >= n)).any():
-            raise ValueError("skip entries must be candidate indices or -1")
-        skip = np.ascontiguousarray(np.where(skip < 0, 0xFFFFFFFF, skip).astype(np.uint32))
-        skip_p = skip.ctypes.data
-    mp = None
-    if metric == "mahalanobis":
-        if m is None:
-            raise ValueError("mahalanobis needs m")
-        m = np.ascontiguousarray(m, dtype=np.float32)
-        if m.shape != (d, d):
-            raise ValueError("m must be [d, d]")
-        mp = m.ctypes.data
+        skip = skip_words(skip, (G, 2), n, "skip must be [G, 2]")
+    m = metric_matrix(metric, m, d)
     idx, dist = np.empty((G, k), np.uint32), np.empty((G, k), np.float32)
-    try:
-        _ffi.check(_ffi.lib().blissgpu_journeys(A.ctypes.data, None if B is None else B.ctypes.data, G, X.ctypes.data, n, d,
-                                                _METRICS[metric], mp, skip_p, k,
-                                                _ffi.JOURNEY_CHAIN if B is None else _ffi.JOURNEY_WAYPOINT, _GATES[direction],
-                                                0 if direction is None else int(feature), idx.ctypes.data, dist.ctypes.data))
-    except _ffi.BlissGpuError as e:
-        _nan_to_panic(e)
-    out = idx.astype(np.int64)
-    out[idx == 0xFFFFFFFF] = -1
-    return out, dist
+    _call("blissgpu_journeys", A, B, G, X, n, d, _METRICS[metric], m, skip, k,
+          _ffi.JOURNEY_CHAIN if B is None else _ffi.JOURNEY_WAYPOINT, _GATES[direction], 0 if direction is None else int(feature),
+          idx, dist)
+    return signed_idx(idx), dist
 
 
 def _end_point_skip(journeys, candidate_songs):
@@ -2413,7 +2200,6 @@ def directed_playlist(first_song, candidate_songs, number_songs, feature, direct
 
 
 # ---- radio playlists: chains (or the k nearest songs) under artist / album separation rules (blissgpu_radio) ----
-_RADIO_MODES = {"chain": _ffi.RADIO_CHAIN, "nearest": _ffi.RADIO_NEAREST}
 _RADIO_WHY = "a radio's metric compares single songs, step by step"
 _RULE_COLUMNS = ("artist", "album", "album_artist", "genre")
 NO_LABEL = 0xFFFFFFFF  # a song without a label: no rule constrains it
@@ -2483,9 +2269,9 @@ def radio_order(from_rows, candidates, k, labels, windows, limits, from_labels=N
     of an eligible candidate raises ValueError.  VarianceWeights and ForestOptions are refused."""
     _no_forest(metric, _RADIO_WHY)
     _no_variance(metric, _RADIO_WHY)
-    A = np.ascontiguousarray(np.atleast_2d(from_rows), dtype=np.float32)
+    A = rows_f32(from_rows)
     # (the same object for both: a radio from each candidate, and the library uploads the rows once)
-    X = A if candidates is from_rows else np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
+    X = A if candidates is from_rows else rows_f32(candidates)
     if A.ndim != 2 or X.ndim != 2 or A.shape[1] != X.shape[1]:
         raise ValueError("from_rows and candidates must be [G, d] and [n, d]")
     if metric not in _METRICS:
@@ -2493,11 +2279,8 @@ def radio_order(from_rows, candidates, k, labels, windows, limits, from_labels=N
     if mode not in _RADIO_MODES:
         raise ValueError('mode must be "chain" or "nearest"')
     k = int(k)
-    if not 1 <= k <= 1024:
-        raise ValueError("k must be 1 .. 1024")
     (G, d), n = A.shape, X.shape[0]
-    if not 1 <= d <= 64:
-        raise ValueError("d must be 1 .. 64")
+    check_k_d(k, d)
     windows = np.ascontiguousarray(np.asarray(windows, dtype=np.int64).reshape(-1))
     limits = np.ascontiguousarray(np.asarray(limits, dtype=np.int64).reshape(-1))
     R = windows.shape[0]
@@ -2509,7 +2292,7 @@ def radio_order(from_rows, candidates, k, labels, windows, limits, from_labels=N
         raise ValueError("windows must be >= 0 and limits >= 1")
     windows = np.minimum(windows, k + 1).astype(np.uint32)
     limits = np.minimum(limits, 0xFFFFFFFF).astype(np.uint32)
-    lab_p = fl_p = None
+    lab = fl = None
     if R:
         lab = np.asarray(labels, dtype=np.int64).reshape(R, -1) if np.size(labels) else np.zeros((R, 0), np.int64)
         if lab.shape != (R, n):
@@ -2517,7 +2300,6 @@ def radio_order(from_rows, candidates, k, labels, windows, limits, from_labels=N
         if ((lab < -1) | (lab > 0xFFFFFFFF)).any():
             raise ValueError("labels must be -1 (none) or fit 32 bits")
         lab = np.ascontiguousarray(np.where(lab < 0, NO_LABEL, lab).astype(np.uint32))
-        lab_p = lab.ctypes.data
         if from_labels is not None:
             fl = np.asarray(from_labels, dtype=np.int64)
             if fl.shape != (G, R):
@@ -2525,34 +2307,13 @@ def radio_order(from_rows, candidates, k, labels, windows, limits, from_labels=N
             if ((fl < -1) | (fl > 0xFFFFFFFF)).any():
                 raise ValueError("from_labels must be -1 (none) or fit 32 bits")
             fl = np.ascontiguousarray(np.where(fl < 0, NO_LABEL, fl).astype(np.uint32))
-            fl_p = fl.ctypes.data
-    skip_p = None
     if skip is not None:
-        skip = np.asarray(skip, dtype=np.int64)
-        if skip.shape != (G, 2):
-            raise ValueError("skip must be [G, 2]")
-        if ((skip < -1) | (skip >= n)).any():
-            raise ValueError("skip entries must be candidate indices or -1")
-        skip = np.ascontiguousarray(np.where(skip < 0, 0xFFFFFFFF, skip).astype(np.uint32))
-        skip_p = skip.ctypes.data
-    mp = None
-    if metric == "mahalanobis":
-        if m is None:
-            raise ValueError("mahalanobis needs m")
-        m = np.ascontiguousarray(m, dtype=np.float32)
-        if m.shape != (d, d):
-            raise ValueError("m must be [d, d]")
-        mp = m.ctypes.data
+        skip = skip_words(skip, (G, 2), n, "skip must be [G, 2]")
+    m = metric_matrix(metric, m, d)
     idx, dist = np.empty((G, k), np.uint32), np.empty((G, k), np.float32)
-    try:
-        _ffi.check(_ffi.lib().blissgpu_radio(A.ctypes.data, G, X.ctypes.data, n, d, _METRICS[metric], mp, lab_p, fl_p, R,
-                                             windows.ctypes.data if R else None, limits.ctypes.data if R else None, skip_p, k,
-                                             _RADIO_MODES[mode], idx.ctypes.data, dist.ctypes.data))
-    except _ffi.BlissGpuError as e:
-        _nan_to_panic(e)
-    out = idx.astype(np.int64)
-    out[idx == 0xFFFFFFFF] = -1
-    return out, dist
+    _call("blissgpu_radio", A, G, X, n, d, _METRICS[metric], m, lab, fl, R, windows if R else None, limits if R else None, skip, k,
+          _RADIO_MODES[mode], idx, dist)
+    return signed_idx(idx), dist
 
 
 DEFAULT_RADIO_RULES = (Rule("artist", 5), Rule("album", 20))
@@ -2595,28 +2356,19 @@ def dedup_order(X, seq=None, meta=None, metric="euclidean", m=None, threshold=No
     X[seq] (seq = None: every row of X in order), meta holds one key per ROW of X (see meta_keys; None: no title /
     artist rule).  Returns the kept positions into seq (int64).  A NaN distance the reference would evaluate raises
     ValueError, like its n32() panic."""
-    X = np.ascontiguousarray(np.atleast_2d(X), dtype=np.float32)
+    X = rows_f32(X)
     n, d = X.shape
-    seq_p = None
     if seq is not None:
         seq = np.ascontiguousarray(seq, dtype=np.uint32).reshape(-1)
-        seq_p = seq.ctypes.data
     length = n if seq is None else seq.shape[0]
-    meta_p = None
     if meta is not None:
         meta = np.ascontiguousarray(meta, dtype=np.uint32).reshape(-1)
         if meta.shape[0] != n:
             raise ValueError("meta needs one key per row of X")
-        meta_p = meta.ctypes.data
-    mp = None
-    if m is not None:
-        m = np.ascontiguousarray(m, dtype=np.float32)
-        mp = m.ctypes.data
     kept, n_kept = np.empty(max(length, 1), np.uint32), C.c_uint64()
     try:
-        _ffi.check(_ffi.lib().blissgpu_dedup_playlist(X.ctypes.data, n, d, seq_p, length, meta_p, _METRICS[metric], mp,
-                                                      np.float32(0.05 if threshold is None else threshold),
-                                                      kept.ctypes.data, C.byref(n_kept)))
+        _ffi.call("blissgpu_dedup_playlist", X, n, d, seq, length, meta, _METRICS[metric], metric_matrix(metric, m),
+                  np.float32(0.05 if threshold is None else threshold), kept, C.byref(n_kept))
     except _ffi.BlissGpuError as e:
         if e.code == _ffi.ERR_NAN:
             raise ValueError("NaN distance (noisy_float::n32 panic in the reference)") from e
@@ -2661,18 +2413,14 @@ def duplicate_labels(X, meta=None, metric="euclidean", m=None, threshold=None, r
     thr = np.float32(0.05 if threshold is None else threshold)
     if np.isnan(thr):
         raise ValueError("threshold is NaN")
-    meta_p = None
     if meta is not None:
         meta = np.ascontiguousarray(meta, dtype=np.uint32).reshape(-1)
         if meta.shape[0] != n:
             raise ValueError("meta needs one key per row of X")
-        meta_p = meta.ctypes.data
-    mp = None
-    if m is not None:
-        m = np.ascontiguousarray(m, dtype=np.float32)
+    if m is not None:  # (this entry point checks, and passes, an m beside any metric)
+        m = metric_matrix(metric, m)
         if m.shape != (d, d):
             raise ValueError("m must be [d, d]")
-        mp = m.ctypes.data
     elif metric == "mahalanobis":
         raise ValueError("mahalanobis needs m")
     labels, n_pairs = np.empty(max(n, 1), np.uint32), C.c_uint64()
@@ -2681,11 +2429,8 @@ def duplicate_labels(X, meta=None, metric="euclidean", m=None, threshold=None, r
         pairs = np.empty((max(cap, 1), 2), np.uint32) if return_pairs else None
         dist = np.empty(max(cap, 1), np.float32) if return_pairs else None
         try:
-            _ffi.check(_ffi.lib().blissgpu_duplicate_groups(X.ctypes.data, n, d, meta_p, _METRICS[metric], mp, thr,
-                                                            labels.ctypes.data, C.byref(n_pairs),
-                                                            pairs.ctypes.data if return_pairs else None,
-                                                            dist.ctypes.data if return_pairs else None,
-                                                            cap if return_pairs else 0))
+            _ffi.call("blissgpu_duplicate_groups", X, n, d, meta, _METRICS[metric], m, thr, labels, C.byref(n_pairs), pairs, dist,
+                      cap if return_pairs else 0)
         except _ffi.BlissGpuError as e:
             if e.code == _ffi.ERR_NAN:
                 raise ValueError("NaN distance (noisy_float::n32 panic in the reference)") from e
@@ -2777,8 +2522,7 @@ def fingerprint_match(fps, pairs, max_offset=FINGERPRINT_MAX_OFFSET, min_overlap
     words = np.concatenate(fps)
     sent = np.ascontiguousarray(pairs[live], dtype=np.uint32)
     o, e, b = np.zeros(live.size, np.int32), np.zeros(live.size, np.uint32), np.zeros(live.size, np.uint32)
-    _ffi.check(_ffi.lib().blissgpu_fingerprint_match(words.ctypes.data, offsets.ctypes.data, len(fps), sent.ctypes.data, live.size,
-                                                     int(max_offset), int(min_overlap), o.ctypes.data, e.ctypes.data, b.ctypes.data))
+    _ffi.call("blissgpu_fingerprint_match", words, offsets, len(fps), sent, live.size, int(max_offset), int(min_overlap), o, e, b)
     offset[live], errors[live], bits[live] = o, e, b
     return offset, errors, bits
 
@@ -2932,7 +2676,7 @@ def nearest_albums(seed_groups, candidates, album_of, k, skip=None, return_means
     from .song import ProviderError
 
     S, off = _seed_groups(seed_groups)
-    X = np.ascontiguousarray(np.atleast_2d(candidates), dtype=np.float32)
+    X = rows_f32(candidates)
     if X.ndim != 2 or (S is not None and S.shape[1] != X.shape[1]):
         raise ValueError("seed groups and candidates must be [s_g, d] and [n, d]")
     n, d = X.shape
@@ -2943,10 +2687,7 @@ def nearest_albums(seed_groups, candidates, album_of, k, skip=None, return_means
     if (album_of < -1).any() or (album_of >= max(n, 0)).any():
         raise ValueError("album_of entries must be album indices below the number of candidates, or -1")
     k = int(k)
-    if not 1 <= k <= 1024:
-        raise ValueError("k must be 1 .. 1024")
-    if not 1 <= d <= 64:
-        raise ValueError("d must be 1 .. 64")
+    check_k_d(k, d)
     G = off.shape[0] - 1
     if (np.diff(off.astype(np.int64)) == 0).any():
         raise ProviderError("Mean of empty slice")
@@ -2956,16 +2697,8 @@ def nearest_albums(seed_groups, candidates, album_of, k, skip=None, return_means
     idx, dist = np.empty((G, k), np.uint32), np.empty((G, k), np.float32)
     means = np.empty((G, d), np.float32) if return_means else None
     centroids = np.empty((A, d), np.float32) if return_means else None
-    try:
-        _ffi.check(_ffi.lib().blissgpu_album_knn(None if S is None else S.ctypes.data, off.ctypes.data, G, X.ctypes.data, n, d,
-                                                 album_u32.ctypes.data, A, None if skip is None else skip.ctypes.data, k,
-                                                 idx.ctypes.data, dist.ctypes.data,
-                                                 None if means is None else means.ctypes.data,
-                                                 None if centroids is None else centroids.ctypes.data))
-    except _ffi.BlissGpuError as e:
-        _nan_to_panic(e)
-    out = idx.astype(np.int64)
-    out[idx == 0xFFFFFFFF] = -1
+    _call("blissgpu_album_knn", S, off, G, X, n, d, album_u32, A, skip, k, idx, dist, means, centroids)
+    out = signed_idx(idx)
     return (out, dist, means, centroids) if return_means else (out, dist)
 
 

@@ -31,14 +31,11 @@ def shard_songs(lengths: Sequence[int], world_size: int) -> List[np.ndarray]:
 def shard_plan(lengths: Sequence[int], world_size: int) -> np.ndarray:
     """rank_of_song as computed by the C ABI (blissgpu_shard_plan: device-free, the plan blissgpu_node_* uses); the
     same assignment as shard_songs, which is the readable statement of the rule."""
-    import ctypes as C
-
     from . import _ffi
 
     lengths = np.ascontiguousarray(lengths, dtype=np.uint64)
     ranks = np.empty(len(lengths), np.uint32)
-    _ffi.check(_ffi.lib().blissgpu_shard_plan(lengths.ctypes.data_as(C.POINTER(C.c_uint64)), len(lengths), world_size,
-                                              ranks.ctypes.data_as(C.POINTER(C.c_uint32))))
+    _ffi.call("blissgpu_shard_plan", lengths, len(lengths), world_size, ranks)
     return ranks
 
 

@@ -53,7 +53,7 @@ class FeaturesVersion(enum.IntEnum):
     def feature_weights(self) -> np.ndarray:
         d = self.feature_count()
         m = np.zeros((d, d), np.float32)
-        _ffi.check(_ffi.lib().blissgpu_feature_weights(int(self), m.ctypes.data))
+        _ffi.call("blissgpu_feature_weights", int(self), m)
         return m
 
     def distance_metric(self):
@@ -174,7 +174,7 @@ def _fmt_of(a: np.ndarray) -> int:
 
 def resampled_len(frames: int, sample_rate: int) -> int:
     """Samples at 22 050 Hz that `frames` frames at `sample_rate` become (libswresample's count; device-free)."""
-    return int(_ffi.lib().blissgpu_resampled_len(int(frames), int(sample_rate)))
+    return int(_ffi.call("blissgpu_resampled_len", int(frames), int(sample_rate)))
 
 
 def _results(out, status, version):
@@ -205,20 +205,18 @@ def analyze_decoded_batch(sample_arrays: Sequence[np.ndarray], sample_rates, opt
     d = version.feature_count()
     out = np.empty((n, d), np.float32)
     status = np.zeros(n, np.int32)
-    L = _ffi.lib()
     keep = [a if a.size else np.zeros(1, a.dtype) for a in arrays]
     if n == 1:
         a = arrays[0]
         st = C.c_int32(0)
-        _ffi.check(L.blissgpu_analyze_decoded(keep[0].ctypes.data, _fmt_of(a), 1 if a.ndim == 1 else a.shape[1], a.shape[0],
-                                              rates[0], int(version), out.ctypes.data, C.byref(st)))
+        _ffi.call("blissgpu_analyze_decoded", keep[0], _fmt_of(a), 1 if a.ndim == 1 else a.shape[1], a.shape[0], rates[0],
+                  int(version), out, C.byref(st))
         status[0] = st.value
     else:
         songs = (_ffi.DecodedSong * n)()
         for i, a in enumerate(arrays):
-            songs[i] = _ffi.DecodedSong(keep[i].ctypes.data, a.shape[0], rates[i], 1 if a.ndim == 1 else a.shape[1], _fmt_of(a))
-        _ffi.check(L.blissgpu_analyze_batch_decoded(songs, n, int(version), out.ctypes.data,
-                                                    status.ctypes.data_as(C.POINTER(C.c_int32))))
+            songs[i] = _ffi.DecodedSong(_ffi.address(keep[i]), a.shape[0], rates[i], 1 if a.ndim == 1 else a.shape[1], _fmt_of(a))
+        _ffi.call("blissgpu_analyze_batch_decoded", songs, n, int(version), out, status)
     return _results(out, status, version)
 
 
@@ -268,18 +266,14 @@ def analyze_flac_batch(files, options: Optional[AnalysisOptions] = None, verify:
     out = np.empty((n, d), np.float32)
     status = np.zeros(n, np.int32)
     keep = [b if b.size else np.zeros(1, np.uint8) for b in blobs]
-    ptrs = (C.c_void_p * n)(*[k.ctypes.data for k in keep])
+    ptrs = _ffi.pointer_table(keep)
     sizes = np.array([b.size for b in blobs], np.uint64)
     flags = np.zeros(n, np.uint32)
     first_bad = np.full(n, 0xFFFFFFFF, np.uint32)
     if checks:
-        u32p = C.POINTER(C.c_uint32)
-        _ffi.check(_ffi.lib().blissgpu_analyze_batch_flac_verified(
-            ptrs, sizes.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(version), checks, out.ctypes.data,
-            status.ctypes.data_as(C.POINTER(C.c_int32)), flags.ctypes.data_as(u32p), first_bad.ctypes.data_as(u32p)))
+        _ffi.call("blissgpu_analyze_batch_flac_verified", ptrs, sizes, n, int(version), checks, out, status, flags, first_bad)
     else:
-        _ffi.check(_ffi.lib().blissgpu_analyze_batch_flac(ptrs, sizes.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(version),
-                                                          out.ctypes.data, status.ctypes.data_as(C.POINTER(C.c_int32))))
+        _ffi.call("blissgpu_analyze_batch_flac", ptrs, sizes, n, int(version), out, status)
     results = _results(out, status, version)
     for i in range(n):
         if status[i] == _ffi.SONG_DECODE_ERROR:
@@ -327,15 +321,13 @@ def flac_verify_batch(files, md5: bool = True):
     if n == 0:
         return []
     keep = [b if b.size else np.zeros(1, np.uint8) for b in blobs]
-    ptrs = (C.c_void_p * n)(*[k.ctypes.data for k in keep])
+    ptrs = _ffi.pointer_table(keep)
     sizes = np.array([b.size for b in blobs], np.uint64)
     flags = np.zeros(n, np.uint32)
     first_bad = np.zeros(n, np.uint32)
     digests = np.zeros((n, 16), np.uint8)
-    u32p = C.POINTER(C.c_uint32)
     checks = _ffi.FLAC_CHECK_CRC16 | (_ffi.FLAC_CHECK_MD5 if md5 else 0)
-    _ffi.check(_ffi.lib().blissgpu_flac_verify_batch(ptrs, sizes.ctypes.data_as(C.POINTER(C.c_uint64)), n, checks, flags.ctypes.data_as(u32p),
-                                                     first_bad.ctypes.data_as(u32p), C.c_void_p(digests.ctypes.data)))
+    _ffi.call("blissgpu_flac_verify_batch", ptrs, sizes, n, checks, flags, first_bad, digests)
     computed = (flags & (_ffi.FLAC_MD5_UNCHECKED | _ffi.FLAC_BAD_STREAM)) == 0
     return [FlacVerdict(int(f), int(b) if b != 0xFFFFFFFF else None, d.tobytes().hex() if c else None)
             for f, b, d, c in zip(flags, first_bad, digests, computed)]
@@ -348,24 +340,19 @@ def flac_decode_batch(files):
     n = len(blobs)
     if n == 0:
         return []
-    L = _ffi.lib()
-    u64p = C.POINTER(C.c_uint64)
     keep = [b if b.size else np.zeros(1, np.uint8) for b in blobs]
     infos = np.zeros((n, _ffi.FLAC_INFO_WORDS), np.uint64)
     pcm = []
     for b, k, info in zip(blobs, keep, infos):   # sizes first (device-free)
         nf = C.c_uint64(0)
-        ok = L.blissgpu_flac_index(C.c_void_p(k.ctypes.data), b.size, 0, info.ctypes.data_as(u64p), None, 0, C.byref(nf)) == _ffi.OK
+        ok = _ffi.call_unchecked("blissgpu_flac_index", k, b.size, 0, info, None, 0, C.byref(nf)) == _ffi.OK
         ok = ok and 1 <= int(info[1]) <= 8 and 4 <= int(info[2]) <= 24
         pcm.append(np.zeros((int(info[3]) if ok else 0, int(info[1]) if ok else 1), np.int32 if int(info[2]) > 16 else np.int16))
     hold = [p if p.size else np.zeros((1, 1), p.dtype) for p in pcm]
-    files_p = (C.c_void_p * n)(*[k.ctypes.data for k in keep])
-    pcm_p = (C.c_void_p * n)(*[h.ctypes.data for h in hold])
     sizes = np.array([b.size for b in blobs], np.uint64)
     room = np.array([p.nbytes for p in pcm], np.uint64)
     status = np.zeros(n, np.int32)
-    _ffi.check(L.blissgpu_flac_decode_batch(files_p, sizes.ctypes.data_as(u64p), n, pcm_p, room.ctypes.data_as(u64p),
-                                            infos.ctypes.data_as(u64p), status.ctypes.data_as(C.POINTER(C.c_int32))))
+    _ffi.call("blissgpu_flac_decode_batch", _ffi.pointer_table(keep), sizes, n, _ffi.pointer_table(hold), room, infos, status)
     return [(p[:int(i[3])], int(i[0]), int(i[2])) if st == _ffi.SONG_OK else DecodingError("the FLAC stream cannot be decoded")
             for p, i, st in zip(pcm, infos, status)]
 
@@ -375,19 +362,16 @@ def flac_decode(data):
     [frames, channels] int16 (sample << (16 - bps)) up to 16 bits per sample, int32 (sample << (32 - bps)) above
     (blissgpu_flac_decode).  Raises DecodingError."""
     blob = _file_bytes(data)
-    L = _ffi.lib()
     info = np.zeros(_ffi.FLAC_INFO_WORDS, np.uint64)
     st = C.c_int32(0)
     src = blob if blob.size else np.zeros(1, np.uint8)
-    u64p = C.POINTER(C.c_uint64)
-    _ffi.check(L.blissgpu_flac_decode(C.c_void_p(src.ctypes.data), blob.size, None, 0, info.ctypes.data_as(u64p), C.byref(st)))
+    _ffi.call("blissgpu_flac_decode", src, blob.size, None, 0, info, C.byref(st))
     if st.value != _ffi.SONG_OK:
         raise DecodingError("the FLAC stream cannot be decoded")
     channels, bps = int(info[1]), int(info[2])
     pcm = np.zeros((int(info[3]), channels), np.int32 if bps > 16 else np.int16)
     if pcm.size:
-        _ffi.check(L.blissgpu_flac_decode(C.c_void_p(src.ctypes.data), blob.size, C.c_void_p(pcm.ctypes.data), pcm.nbytes,
-                                          info.ctypes.data_as(u64p), C.byref(st)))
+        _ffi.call("blissgpu_flac_decode", src, blob.size, pcm, pcm.nbytes, info, C.byref(st))
         if st.value != _ffi.SONG_OK:
             raise DecodingError("the FLAC stream cannot be decoded")
     return pcm[:int(info[3])], int(info[0]), bps
@@ -407,7 +391,6 @@ def analyze_batch(sample_arrays: Sequence[np.ndarray], options: Optional[Analysi
     d = version.feature_count()
     out = np.empty((n, d), np.float32)
     status = np.empty(n, np.int32)
-    L = _ffi.lib()
     # one device batch per (sample format, channel count) class -- normally there is exactly one
     classes = {}
     for i, a in enumerate(arrays):
@@ -418,8 +401,7 @@ def analyze_batch(sample_arrays: Sequence[np.ndarray], options: Optional[Analysi
             buf = a if a.size else np.zeros(1, a.dtype)
             row = np.empty(d, np.float32)
             st = C.c_int32(0)
-            _ffi.check(L.blissgpu_analyze_interleaved(buf.ctypes.data, fmt, channels, a.shape[0], int(version),
-                                                      row.ctypes.data, C.byref(st)))
+            _ffi.call("blissgpu_analyze_interleaved", buf, fmt, channels, a.shape[0], int(version), row, C.byref(st))
             out[idx[0]] = row
             status[idx[0]] = st.value
             continue
@@ -431,10 +413,7 @@ def analyze_batch(sample_arrays: Sequence[np.ndarray], options: Optional[Analysi
             pcm = np.zeros(1, arrays[idx[0]].dtype)
         res = np.empty((len(idx), d), np.float32)
         st = np.empty(len(idx), np.int32)
-        _ffi.check(L.blissgpu_analyze_batch_interleaved(
-            pcm.ctypes.data, fmt, channels, offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
-            lengths.ctypes.data_as(C.POINTER(C.c_uint64)), len(idx), int(version), res.ctypes.data,
-            st.ctypes.data_as(C.POINTER(C.c_int32))))
+        _ffi.call("blissgpu_analyze_batch_interleaved", pcm, fmt, channels, offsets, lengths, len(idx), int(version), res, st)
         out[idx] = res
         status[idx] = st
     return _results(out, status, version)
@@ -446,7 +425,7 @@ FINGERPRINT_VERSION = 1  # stored beside the words (library.store_fingerprints):
 
 def fingerprint_len(n_samples: int) -> int:
     """Sub-fingerprints of a song of n_samples samples at 22 050 Hz: (n - 8192) // 512, 0 below 8704 (device-free)."""
-    return int(_ffi.lib().blissgpu_fingerprint_len(int(n_samples)))
+    return int(_ffi.call("blissgpu_fingerprint_len", int(n_samples)))
 
 
 def fingerprint_batch(sample_arrays: Sequence[np.ndarray], return_energies: bool = False):
@@ -467,11 +446,10 @@ def fingerprint_batch(sample_arrays: Sequence[np.ndarray], return_energies: bool
     n = len(arrays)
     if n == 0:
         return ([], []) if return_energies else []
-    L = _ffi.lib()
     sample_offsets = np.zeros(n + 1, np.uint64)
     sample_offsets[1:] = np.cumsum([a.shape[0] for a in arrays], dtype=np.uint64)
     word_offsets = np.zeros(n + 1, np.uint64)
-    word_offsets[1:] = np.cumsum([L.blissgpu_fingerprint_len(a.shape[0]) for a in arrays], dtype=np.uint64)
+    word_offsets[1:] = np.cumsum([fingerprint_len(a.shape[0]) for a in arrays], dtype=np.uint64)
     pcm = np.concatenate(arrays) if n > 1 else arrays[0]
     if pcm.size == 0:
         pcm = np.zeros(1, np.float32)
@@ -479,8 +457,7 @@ def fingerprint_batch(sample_arrays: Sequence[np.ndarray], return_energies: bool
     words = np.zeros(max(n_words, 1), np.uint32)
     status = np.zeros(n, np.int32)
     energies = np.zeros((n_words + n, 33), np.float64) if return_energies else None
-    _ffi.check(L.blissgpu_fingerprint_batch(pcm.ctypes.data, sample_offsets.ctypes.data, word_offsets.ctypes.data, n, words.ctypes.data,
-                                            status.ctypes.data, energies.ctypes.data if return_energies else None))
+    _ffi.call("blissgpu_fingerprint_batch", pcm, sample_offsets, word_offsets, n, words, status, energies)
     wo = word_offsets.astype(np.int64)
     out = [words[wo[i]:wo[i + 1]].copy() for i in range(n)]
     if not return_energies:
@@ -500,26 +477,25 @@ def fingerprint_decoded_batch(sample_arrays: Sequence[np.ndarray], sample_rates)
     rates = [int(sample_rates)] * n if np.isscalar(sample_rates) else [int(r) for r in sample_rates]
     if len(rates) != n:
         raise ProviderError("one sample rate per song")
-    L = _ffi.lib()
     ctx = C.c_void_p()
-    _ffi.check(L.blissgpu_default_ctx(0, C.byref(ctx)))
+    _ffi.call("blissgpu_default_ctx", 0, C.byref(ctx))
     mono = []
     for a, rate in zip(arrays, rates):
-        n_out = int(L.blissgpu_resampled_len(a.shape[0], rate))
+        n_out = resampled_len(a.shape[0], rate)
         out = np.zeros(n_out, np.float32)
         if n_out:
             d_in, d_out = C.c_void_p(), C.c_void_p()
-            _ffi.check(L.blissgpu_malloc(C.byref(d_in), a.nbytes))
+            _ffi.call("blissgpu_malloc", C.byref(d_in), a.nbytes)
             try:
-                _ffi.check(L.blissgpu_malloc(C.byref(d_out), out.nbytes))
+                _ffi.call("blissgpu_malloc", C.byref(d_out), out.nbytes)
                 try:
-                    _ffi.check(L.blissgpu_memcpy_h2d(ctx, d_in, a.ctypes.data, a.nbytes))
-                    _ffi.check(L.blissgpu_pcm_decode_device(ctx, d_in, _fmt_of(a), 1 if a.ndim == 1 else a.shape[1], a.shape[0], rate, d_out))
-                    _ffi.check(L.blissgpu_memcpy_d2h(ctx, out.ctypes.data, d_out, out.nbytes))  # (on the context's stream, then waits)
+                    _ffi.call("blissgpu_memcpy_h2d", ctx, d_in, a, a.nbytes)
+                    _ffi.call("blissgpu_pcm_decode_device", ctx, d_in, _fmt_of(a), 1 if a.ndim == 1 else a.shape[1], a.shape[0], rate, d_out)
+                    _ffi.call("blissgpu_memcpy_d2h", ctx, out, d_out, out.nbytes)  # (on the context's stream, then waits)
                 finally:
-                    L.blissgpu_free(d_out)
+                    _ffi.call_unchecked("blissgpu_free", d_out)
             finally:
-                L.blissgpu_free(d_in)
+                _ffi.call_unchecked("blissgpu_free", d_in)
         mono.append(out)
     return fingerprint_batch(mono)
 

@@ -573,9 +573,13 @@ def _device_entry_points():
 
 def _stream_bracket_faults(source, entry_points):
     """Every call of a device entry point in a method of device.Context must stand between a `self._pre()` and a
-    `self._post()` of one statement list (its own, or one that encloses it: synth_white_noise brackets an `if`), with no
-    upload of an input between the `_pre()` and the call and no read of an output between the call and the `_post()`.
-    -> [(method, line, what is wrong)]"""
+    `self._post()` of one statement list (its own, or one that encloses it), with no upload of an input between the `_pre()`
+    and the call and no read of an output between the call and the `_post()`.  A device call is `self._L.<name>(...)` or
+    `_ffi.call("<name>", ...)` / `_ffi.call_unchecked("<name>", ...)`; one that forwards a name it was given
+    (`_ffi.call(name, ...)`, the body of Context._call) is a device call too.  `self._call("<name>", ...)` is in order by
+    construction -- its arguments are evaluated before its `_pre()`, nothing can stand before its `_post()` -- provided
+    Context._call itself passes the rule above, which is checked like any other method.
+    -> [(method, line, what is wrong)], the entry points seen"""
     import ast
 
     def attr_call(node, owner, name=None):  # owner.name(...) with owner a plain name chain such as self._L
@@ -588,8 +592,23 @@ def _stream_bracket_faults(source, entry_points):
     def is_marker(stmt, name):
         return isinstance(stmt, ast.Expr) and attr_call(stmt.value, "self", name) is not None
 
+    def named(node):
+        """the first argument of a call when it is a string"""
+        a = node.args[0] if node.args else None
+        return a.value if isinstance(a, ast.Constant) and isinstance(a.value, str) else None
+
+    def entry_of(node):
+        """the device entry point this node calls itself (not through self._call): its name, "*" for a forwarded one, or None"""
+        name = attr_call(node, "self._L")
+        if name is None and attr_call(node, "_ffi") in ("call", "call_unchecked") and node.args:
+            name = "*" if isinstance(node.args[0], (ast.Name, ast.Starred)) else named(node)
+        return name if name == "*" or name in entry_points else None
+
     def c_calls(node):
-        return [n for n in ast.walk(node) if attr_call(n, "self._L") in entry_points]
+        return [n for n in ast.walk(node) if entry_of(n) is not None]
+
+    def routed(node):
+        return [named(n) for n in ast.walk(node) if attr_call(n, "self", "_call") and named(n) in entry_points]
 
     def touches(stmt, names, subscripts):
         """a method call named in `names` (x.to(...), x.cuda(), torch.from_numpy(...)) or, with `subscripts`, an indexing"""
@@ -657,13 +676,19 @@ def _stream_bracket_faults(source, entry_points):
 
     tree = ast.parse(source)
     ctx = next(n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == "Context")
-    seen = set()
+    seen, forwards = set(), False
     for fn in ctx.body:
-        if not isinstance(fn, ast.FunctionDef) or not c_calls(fn):
+        if not isinstance(fn, ast.FunctionDef):
             continue
-        seen |= {attr_call(n, "self._L") for n in c_calls(fn)}
+        seen |= set(routed(fn))
+        if not c_calls(fn):
+            continue
+        seen |= {entry_of(n) for n in c_calls(fn)} - {"*"}
+        forwards |= fn.name == "_call"
         for call in visit(fn.body, fn.name, upload_helpers(fn)):
-            faults.append((fn.name, call.lineno, f"{call.func.attr} is not between a _pre() and a _post() of one statement list"))
+            faults.append((fn.name, call.lineno, f"{entry_of(call)} is not between a _pre() and a _post() of one statement list"))
+    if not forwards and any(routed(fn) for fn in ctx.body):
+        faults.append(("_call", ctx.lineno, "self._call is used, but Context._call does not forward to _ffi.call"))
     return faults, seen
 
 
@@ -758,6 +783,23 @@ class Context:
         first = out[:3]
         self._post()
         return first
+
+    def _call(self, name, *args):
+        self._pre()
+        _ffi.call(name, self._h, *args)
+        self._post()
+
+    def good_through_call(self, X, labels):
+        out = torch.empty(3)
+        self._call("blissgpu_knn_device", self._up_f32(X), labels.to(torch.int32), out)
+        return out.to(torch.int64)
+
+    def bad_past_call(self, X, out):
+        _ffi.call("blissgpu_knn_device", self._h, X, out)
+        return out
+
+    def bad_unchecked_past_call(self, X):
+        return _ffi.call_unchecked("blissgpu_chains_device", self._h, X)
 '''
 
 
@@ -789,31 +831,39 @@ def test_every_device_call_of_context_is_bracketed_by_pre_and_post():
     # the check itself, on the samples above: every bad_* method is reported, no good* one
     reported = {f[0] for f in _stream_bracket_faults(_BRACKET_SAMPLES, entry)[0]}
     names = set(re.findall(r"def ((?:good|bad_)\w*)\(self", _BRACKET_SAMPLES))
-    assert len(names) == 12 and reported == {n for n in names if n.startswith("bad_")}, sorted(reported ^ {n for n in names if n.startswith("bad_")})
+    assert len(names) == 15 and reported == {n for n in names if n.startswith("bad_")}, sorted(reported ^ {n for n in names if n.startswith("bad_")})
+    no_forward = _BRACKET_SAMPLES.replace("        _ffi.call(name, self._h, *args)\n", "        pass\n")
+    assert "_call" in {f[0] for f in _stream_bracket_faults(no_forward, entry)[0]}
 
-    # ... and on device.py itself: the edits a host layer rewrite is most likely to make, cut by line
+    # ... and on device.py itself: the edits a host layer rewrite is most likely to make.  Every device call of Context goes
+    # through Context._call, so the bracket has one copy: cutting a line of it is reported there, and a call that goes past it
+    # -- straight to _ffi.call -- is reported at its method
     lines = source.splitlines(keepends=True)
 
-    def without(*drop, insert=None):
-        out = [ln for i, ln in enumerate(lines, 1) if i not in drop]
-        if insert:
-            at, text = insert
-            out.insert(at - 1 - sum(d < at for d in drop), text)
+    def without(*drop):
+        return [f[0] for f in _stream_bracket_faults("".join(ln for i, ln in enumerate(lines, 1) if i not in drop), entry)[0]]
+
+    def past_call(method, which=0):
+        """the source with the `which`-th self._call of `method` sent straight to _ffi.call"""
+        import ast
+
+        ctx = next(n for n in ast.parse(source).body if isinstance(n, ast.ClassDef) and n.name == "Context")
+        fn = next(n for n in ctx.body if isinstance(n, ast.FunctionDef) and n.name == method)
+        at = sorted(n.lineno for n in ast.walk(fn) if isinstance(n, ast.Call) and ast.unparse(n.func) == "self._call")[which]
+        assert 'self._call("' in lines[at - 1]
+        out = list(lines)
+        out[at - 1] = out[at - 1].replace('self._call("', '_ffi.call("', 1)
         return [f[0] for f in _stream_bracket_faults("".join(out), entry)[0]]
 
-    pre, post, _ = _method_lines(source, "knn")
-    assert len(pre) == len(post) == 1 and without(pre[0]) == ["knn"]
-    pre, post, _ = _method_lines(source, "chains")
-    assert len(pre) == len(post) == 1 and without(post[0]) == ["chains"]
-    pre, post, _ = _method_lines(source, "group_knn")
-    assert len(pre) == len(post) == 2 and all(without(ln) == ["group_knn"] for ln in pre + post)
-    # _pre() moved above the wrapper's own uploads: silhouette's nested up_f32 / up_u32, kmeans' lambda `up`
-    for method, hits in (("silhouette", 2), ("kmeans", 1), ("mst", 1), ("group_neighbours", 2)):
-        pre, post, first = _method_lines(source, method)
-        assert len(pre) == len(post) == 1 and first is not None and first < pre[0], method
-        early = "        self._pre()\n"
-        assert without(pre[0], insert=(first, early)) == [method] * hits, method  # one report per statement that uploads
-        assert without(insert=(first, early)) == [], method  # (a second, early _pre() does no harm: the late one stands)
+    pre, post, _ = _method_lines(source, "_call")
+    assert len(pre) == len(post) == 1 and without(pre[0]) == ["_call"] and without(post[0]) == ["_call"]
+    assert past_call("knn") == ["knn"] and past_call("chains") == ["chains"]
+    assert past_call("group_knn", 0) == ["group_knn"] and past_call("group_knn", 1) == ["group_knn"]
+    # the wrappers that upload arrays themselves (silhouette, kmeans, mst, group_neighbours) have no _pre() of their own that
+    # could stand above an upload: their one bracket is _call's, entered after every argument is ready
+    for method in ("silhouette", "kmeans", "mst", "group_neighbours"):
+        pre, post, _ = _method_lines(source, method)
+        assert pre == post == [] and past_call(method) == [method], method
 
 
 def test_every_device_entry_point_has_a_stream_order_case():
