@@ -286,6 +286,15 @@ pub mod sys {
         pub fn blissgpu_fingerprint_bands(edges: *mut u32) -> c_int;
         pub fn blissgpu_fingerprint_batch(pcm: *const f32, sample_offsets: *const u64, word_offsets: *const u64, n_songs: u32, words: *mut u32, status: *mut i32, energies: *mut f64) -> c_int;
         pub fn blissgpu_fingerprint_match(words: *const u32, word_offsets: *const u64, n_songs: u32, pairs: *const u32, n_pairs: u64, max_offset: u32, min_overlap: u32, offset: *mut i32, errors: *mut u32, bits: *mut u32) -> c_int;
+        // loudness (EBU R 128 / ReplayGain 2.0): the device-free tables and gates, the device's energies and peaks, the whole batch
+        pub fn blissgpu_loudness_subblocks(frames: u64, sample_rate: u32) -> u64;
+        pub fn blissgpu_loudness_kweighting(sample_rate: u32, coef: *mut f64) -> c_int;
+        pub fn blissgpu_true_peak_filter(sample_rate: u32, factor: *mut u32, h: *mut f64) -> c_int;
+        pub fn blissgpu_loudness_blocks(z: *const f64, channels: u32, n_sub: u64, sample_rate: u32, p: *mut f64, st: *mut f64) -> c_int;
+        pub fn blissgpu_loudness_gate(p: *const f64, n: u64, power: *mut f64, lufs: *mut f64) -> c_int;
+        pub fn blissgpu_loudness_range(st: *const f64, n: u64, range_lu: *mut f64, lo: *mut f64, hi: *mut f64) -> c_int;
+        pub fn blissgpu_loudness_energies(songs: *const blissgpu_decoded_song, n_songs: u32, z: *mut f64, sample_peak: *mut f64, true_peak: *mut f64, status: *mut i32) -> c_int;
+        pub fn blissgpu_loudness_batch(songs: *const blissgpu_decoded_song, n_songs: u32, album: *const u32, n_albums: u32, song_out: *mut f64, album_out: *mut f64, status: *mut i32) -> c_int;
         pub fn blissgpu_last_error() -> *const c_char;
         pub fn blissgpu_version() -> *const c_char;
     }

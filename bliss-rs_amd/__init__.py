@@ -20,6 +20,7 @@ bliss-rs / `bliss-audio` 0.13.0):
     playlist.ward_tree / ward_nearest / choose_k_tree, library.ward_tree / ward_clusters: Ward's dendrogram -- compact clusters that nest, any k by cutting one tree
     playlist.kmedoids / pam_scan / medoid_songs, library.medoid_songs: k-medoids -- the k SONGS that summarise a library, under cosine too
     fingerprint_batch / fingerprint_decoded_batch, playlist.fingerprint_match / fingerprint_duplicates, library.fingerprint_duplicates: acoustic fingerprints -- the same RECORDING found again, whatever its features say
+    loudness_batch / loudness_flac_batch / Loudness.replaygain, library.store_loudness / load_loudness / loudness_statistics: EBU R 128 loudness, range and true peak per song and album at the files' native rates -- ReplayGain without a second scanner
     playlist.local_scales / scaled_nearest_order / hubness, library.similar_songs_scaled / hubness / orphan_songs: lists that a few hub songs do not dominate, and a measure of how much they do
     playlist.ForestOptions / forest_scores: the extended isolation forest metric for several seed songs   src/playlist.rs:230-251
     library.{load_feature_matrix, load_songs, store_song}   feature table of src/library.rs:500-531, 1355-1372, 1560-1630
@@ -33,7 +34,8 @@ from .song import (  # noqa: F401
     SAMPLE_RATE, CHANNELS, NUMBER_FEATURES, Analysis, AnalysisError, AnalysisIndex, AnalysisIndexv1,
     AnalysisOptions, BlissError, DecodingError, FeaturesVersion, ProviderError, Song, analyze_batch, analyze_decoded_batch,
     FlacVerdict, analyze_flac_batch, flac_decode, flac_decode_batch, flac_verify_batch, resampled_len,
-    FINGERPRINT_VERSION, fingerprint_batch, fingerprint_decoded_batch, fingerprint_len)
+    FINGERPRINT_VERSION, fingerprint_batch, fingerprint_decoded_batch, fingerprint_len,
+    LOUDNESS_VERSION, Loudness, loudness_batch, loudness_flac_batch, loudness_blocks, loudness_gate, loudness_range)
 from .decoder import Decoder, FlacDecoder, PreAnalyzedSong, RawPcmDecoder  # noqa: F401
 from . import playlist  # noqa: F401
 from . import cue  # noqa: F401

@@ -156,6 +156,14 @@ SIGNATURES = {
     "blissgpu_fingerprint_bands": (C.c_int, [_u32p]),
     "blissgpu_fingerprint_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
     "blissgpu_fingerprint_match": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "blissgpu_loudness_subblocks": (C.c_uint64, [C.c_uint64, C.c_uint32]),
+    "blissgpu_loudness_kweighting": (C.c_int, [C.c_uint32, _f64p]),
+    "blissgpu_true_peak_filter": (C.c_int, [C.c_uint32, _u32p, _f64p]),
+    "blissgpu_loudness_blocks": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint32, _vp, _vp]),
+    "blissgpu_loudness_gate": (C.c_int, [_vp, C.c_uint64, _f64p, _f64p]),
+    "blissgpu_loudness_range": (C.c_int, [_vp, C.c_uint64, _f64p, _f64p, _f64p]),
+    "blissgpu_loudness_energies": (C.c_int, [C.POINTER(DecodedSong), C.c_uint32, _vp, _vp, _vp, _i32p]),
+    "blissgpu_loudness_batch": (C.c_int, [C.POINTER(DecodedSong), C.c_uint32, _vp, C.c_uint32, _vp, _vp, _i32p]),
     "blissgpu_moments": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "blissgpu_moments_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "blissgpu_covariance_metric": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_int, C.c_double, _vp, _i32p]),

@@ -10,6 +10,7 @@
 #include <atomic>
 #include <chrono>
 #include <deque>
+#include <limits>
 #include <mutex>
 #include <new>
 #include <string>
@@ -21,6 +22,7 @@
 #include "covariance_metric.hpp"
 #include "mst_merge.hpp"
 #include "ward_merge.hpp"
+#include "loudness_gate.hpp"
 #include "forest.hpp"
 
 using namespace bg;
@@ -357,7 +359,7 @@ int blissgpu_ctx_destroy(blissgpu_ctx* c) {
         (void)hipFree(c->bt_rwv); (void)hipFree(c->bt_dfwv); (void)hipFree(c->chroma_bank);
         scheduler_release(c);
         c->dbg_tuning.release(); c->dbg_nbpms.release(); c->dbg_chroma.release(); c->dbg_interval.release();
-        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->km_ws.release(); c->sil_ws.release(); c->mo_ws.release(); c->ch_ws.release(); c->ms_ws.release(); c->wd_ws.release(); c->wd_host.release(); c->pam_ws.release(); c->fp_ws.release(); c->map_ws.release(); c->mt_ws.release(); c->pl_next.release(); c->st_idx.release();
+        c->pl_sync.release(); c->pl_keys.release(); c->pl_tmp.release(); c->pl_slots.release(); c->pl_chain.release(); c->km_ws.release(); c->sil_ws.release(); c->mo_ws.release(); c->ch_ws.release(); c->ms_ws.release(); c->wd_ws.release(); c->wd_host.release(); c->pam_ws.release(); c->fp_ws.release(); c->ld_ws.release(); c->map_ws.release(); c->mt_ws.release(); c->pl_next.release(); c->st_idx.release();
         c->st_a.release(); c->st_b.release(); c->st_m.release(); c->st_dist.release(); c->st_out.release();
         c->fl_bytes.release(); c->fl_tab.release(); c->fl_pcm.release(); c->fl_status.release(); c->fl_end.release();
         c->fl_bad.release(); c->fl_mono.release(); c->fl_rows.release(); c->fl_htab.release();
@@ -2454,6 +2456,309 @@ int blissgpu_fingerprint_match(const uint32_t* words, const uint64_t* word_offse
         s.down(bits, d_out + 2 * n_pairs, n_pairs * sizeof(uint32_t));
     }
     return s.finish(rc);
+}
+
+// ---- loudness (kernels_loudness.hip, loudness_gate.hpp): the device delivers the sub-block energies and the
+// peaks of a group of songs at a time; the blocks, the gates and the range behind them are host arithmetic ----
+uint64_t blissgpu_loudness_subblocks(uint64_t frames, uint32_t sample_rate) { return loud_subblocks(frames, sample_rate); }
+
+int blissgpu_loudness_kweighting(uint32_t sample_rate, double* coef) {
+    const char* who = "blissgpu_loudness_kweighting";
+    if (!loud_rate_ok(sample_rate)) return fail(BLISSGPU_ERR_INVALID, who, "sample_rate must be 8000 .. 768000");
+    if (!coef) return fail(BLISSGPU_ERR_INVALID, who, "coef is NULL");
+    loud_kweighting(sample_rate, coef);
+    return BLISSGPU_OK;
+}
+
+int blissgpu_true_peak_filter(uint32_t sample_rate, uint32_t* factor, double* h) {
+    const char* who = "blissgpu_true_peak_filter";
+    if (!loud_rate_ok(sample_rate)) return fail(BLISSGPU_ERR_INVALID, who, "sample_rate must be 8000 .. 768000");
+    if (!factor || !h) return fail(BLISSGPU_ERR_INVALID, who, "factor or h is NULL");
+    *factor = loud_peak_factor(sample_rate);
+    loud_peak_filter(*factor, h);
+    return BLISSGPU_OK;
+}
+
+int blissgpu_loudness_blocks(const double* z, uint32_t channels, uint64_t n_sub, uint32_t sample_rate, double* P, double* ST) {
+    const char* who = "blissgpu_loudness_blocks";
+    if (!loud_rate_ok(sample_rate)) return fail(BLISSGPU_ERR_INVALID, who, "sample_rate must be 8000 .. 768000");
+    if (channels < 1 || channels > 2) return fail(BLISSGPU_ERR_INVALID, who, "channels must be 1 or 2");
+    if (n_sub && !z) return fail(BLISSGPU_ERR_INVALID, who, "z is NULL");
+    loud_blocks(z, channels, n_sub, loud_hop(sample_rate), P, ST);
+    return BLISSGPU_OK;
+}
+
+int blissgpu_loudness_gate(const double* P, uint64_t n, double* power, double* lufs) {
+    const char* who = "blissgpu_loudness_gate";
+    if (n && !P) return fail(BLISSGPU_ERR_INVALID, who, "P is NULL");
+    if (!power || !lufs) return fail(BLISSGPU_ERR_INVALID, who, "power or lufs is NULL");
+    *power = loud_gate(P, n);
+    *lufs = loud_lufs(*power);
+    return BLISSGPU_OK;
+}
+
+int blissgpu_loudness_range(const double* ST, uint64_t n, double* range_lu, double* lo, double* hi) {
+    const char* who = "blissgpu_loudness_range";
+    if (n && !ST) return fail(BLISSGPU_ERR_INVALID, who, "ST is NULL");
+    if (!range_lu || !lo || !hi) return fail(BLISSGPU_ERR_INVALID, who, "range_lu, lo or hi is NULL");
+    *range_lu = loud_range(ST, n, lo, hi);
+    return BLISSGPU_OK;
+}
+
+// what can be said about the songs of a call without a device: the arguments, every song's status and where its energies go
+// (zoff [n_songs + 1], in doubles: channels * n_sub per song, too-short songs included)
+static int loud_songs_ok(const char* who, const blissgpu_decoded_song* songs, uint32_t n_songs, int32_t* status, std::vector<uint64_t>& zoff) {
+    if (!songs) return fail(BLISSGPU_ERR_INVALID, who, "songs is NULL");
+    if (!status) return fail(BLISSGPU_ERR_INVALID, who, "status is NULL");
+    zoff.assign((size_t)n_songs + 1, 0);
+    for (uint32_t s = 0; s < n_songs; s++) {
+        const blissgpu_decoded_song& d = songs[s];
+        if (d.channels < 1 || d.channels > 2)
+            return fail(BLISSGPU_ERR_INVALID, who, "channels must be 1 or 2 (surround weights need a channel layout)");
+        if (!loud_rate_ok(d.sample_rate)) return fail(BLISSGPU_ERR_INVALID, who, "sample_rate must be 8000 .. 768000");
+        if (d.sample_format != BLISSGPU_SAMPLE_F32 && d.sample_format != BLISSGPU_SAMPLE_S16 && d.sample_format != BLISSGPU_SAMPLE_S32)
+            return fail(BLISSGPU_ERR_INVALID, who, "sample_format must be F32, S16 or S32");
+        if (d.frames > (1ull << 40)) return fail(BLISSGPU_ERR_INVALID, who, "a song has more than 2^40 frames");
+        if (d.frames && !d.pcm) return fail(BLISSGPU_ERR_INVALID, who, "a song's pcm is NULL");
+        const uint64_t n_sub = loud_subblocks(d.frames, d.sample_rate);
+        status[s] = n_sub < LOUD_BLOCK_SUBS ? BLISSGPU_SONG_TOO_SHORT : BLISSGPU_SONG_OK;
+        zoff[s + 1] = zoff[s] + n_sub * d.channels;
+    }
+    return BLISSGPU_OK;
+}
+
+// The device half on the context and device pointers: the energies and the peaks of one group of songs whose PCM, descriptors,
+// class lists and taps are already there.  classes: per (format, channels) the offset of its list in song_of / row_pfx terms.
+struct LoudClass {
+    int format, channels;
+    uint32_t n_class, n_rows;
+    const uint32_t *d_song_of, *d_row_pfx;
+};
+static int loud_group_device(blissgpu_ctx* c, const char* who, const uint8_t* d_pcm, const LoudSong* d_desc, uint32_t n_songs,
+                             const LoudClass* classes, int n_classes, const uint32_t* d_tile_pfx, uint32_t n_tiles,
+                             const double* d_htab, double* d_part, double* d_z, double* d_peaks) {
+    int rc = BLISSGPU_OK;
+    for (int k = 0; k < n_classes && !rc; k++) {
+        const LoudClass& lc = classes[k];
+        { Prof p(c, KX_LOUD_ENERGY); launch_loud_energy(d_pcm, d_desc, lc.format, lc.channels, lc.d_song_of, lc.d_row_pfx, lc.n_class, lc.n_rows, d_z, c->stream); }
+        rc = fp_launched(who);
+    }
+    if (!rc) {
+        { Prof p(c, KX_LOUD_PEAK); launch_loud_peak(d_pcm, d_desc, n_songs, d_tile_pfx, n_tiles, d_htab, d_part, c->stream); }
+        rc = fp_launched(who);
+    }
+    if (!rc) {
+        { Prof p(c, KX_LOUD_FOLD); launch_loud_fold(d_part, d_tile_pfx, n_songs, d_peaks, c->stream); }
+        rc = fp_launched(who);
+    }
+    return rc;
+}
+
+static int loud_energies_host(const char* who, const blissgpu_decoded_song* songs, uint32_t n_songs, const std::vector<uint64_t>& zoff,
+                              double* z, double* sample_peak, double* true_peak, const int32_t* status) {
+    if (zoff[n_songs] && !z) return fail(BLISSGPU_ERR_INVALID, who, "z is NULL");
+    if (!sample_peak || !true_peak) return fail(BLISSGPU_ERR_INVALID, who, "sample_peak or true_peak is NULL");
+    // a too-short song never reaches the device: its energies and peaks are zero.  Its energies are cleared once, when its group
+    // is done (a group's z comes back in one copy that runs over them)
+    auto zero_short = [&](uint32_t s0, uint32_t s1) {
+        for (uint32_t s = s0; s < s1; s++)
+            if (status[s] != BLISSGPU_SONG_OK && zoff[s + 1] > zoff[s]) memset(z + zoff[s], 0, (zoff[s + 1] - zoff[s]) * sizeof(double));
+    };
+    bool any = false;
+    for (uint32_t s = 0; s < n_songs; s++) {
+        sample_peak[s] = true_peak[s] = 0.0;
+        any = any || status[s] == BLISSGPU_SONG_OK;
+    }
+    if (!any) {
+        zero_short(0, n_songs);
+        return BLISSGPU_OK;
+    }
+    blissgpu_ctx* c;
+    int rc = default_ctx(&c);
+    if (rc) return rc;
+    CTX_ENTER(c, who);
+    static const std::vector<double> htab = [] {
+        std::vector<double> h(3 * LOUD_TAPS);
+        loud_peak_filter(4, h.data());
+        loud_peak_filter(2, h.data() + LOUD_TAPS);
+        loud_peak_filter(1, h.data() + 2 * LOUD_TAPS);
+        return h;
+    }();
+    // groups of consecutive songs: at most 8 GiB of PCM (and half the workspace limit), one song at the least.  The energy kernel
+    // is bound by the latency of its longest row, not by throughput, until a launch has several workgroups per CU: large groups
+    const uint64_t pcm_budget = std::min<uint64_t>(8ull << 30, c->ws_limit / 2);
+    auto pcm_bytes = [&](uint32_t s) {
+        const blissgpu_decoded_song& d = songs[s];
+        return status[s] == BLISSGPU_SONG_OK ? (uint64_t)fp_align(d.frames * d.channels * (d.sample_format == BLISSGPU_SAMPLE_S16 ? 2 : 4)) : 0ull;
+    };
+    std::vector<LoudSong> desc;
+    std::vector<uint32_t> ok, tile_pfx, lists;  // lists: per class song_of | row_pfx, one after the other
+    std::vector<double> peaks;
+    for (uint32_t g0 = 0; g0 < n_songs;) {
+        uint32_t g1 = g0;
+        uint64_t bytes = 0;
+        while (g1 < n_songs && (g1 == g0 || bytes + pcm_bytes(g1) <= pcm_budget)) bytes += pcm_bytes(g1++);
+        ok.clear();
+        for (uint32_t s = g0; s < g1; s++)
+            if (status[s] == BLISSGPU_SONG_OK) ok.push_back(s);
+        const uint32_t ng = (uint32_t)ok.size();
+        if (ng == 0) {
+            zero_short(g0, g1);
+            g0 = g1;
+            continue;
+        }
+        desc.resize(ng);
+        tile_pfx.assign(ng + 1, 0);
+        uint64_t off = 0;
+        for (uint32_t k = 0; k < ng; k++) {
+            const blissgpu_decoded_song& d = songs[ok[k]];
+            LoudSong& L = desc[k];
+            L.pcm_off = off;
+            L.frames = d.frames;
+            L.z_off = zoff[ok[k]] - zoff[g0];
+            L.hop = loud_hop(d.sample_rate);
+            L.n_sub = (uint32_t)loud_subblocks(d.frames, d.sample_rate);
+            L.channels = d.channels;
+            L.format = d.sample_format;
+            L.factor = loud_peak_factor(d.sample_rate);
+            loud_kweighting(d.sample_rate, L.coef);
+            off += pcm_bytes(ok[k]);
+            const uint64_t tiles = (uint64_t)tile_pfx[k] + loud_peak_tiles(d.frames, d.channels);
+            if (tiles >= 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "a group of songs has 2^32 peak tiles or more");
+            tile_pfx[k + 1] = (uint32_t)tiles;
+        }
+        // the classes present in the group, each with its songs and the rows in front of them
+        LoudClass classes[6];
+        size_t list_at[6];
+        int n_classes = 0;
+        lists.clear();
+        for (int fmt = 0; fmt < 3; fmt++)
+            for (int ch = 1; ch <= 2; ch++) {
+                const size_t at = lists.size();
+                for (uint32_t k = 0; k < ng; k++)
+                    if (desc[k].format == fmt && desc[k].channels == ch) lists.push_back(k);
+                const uint32_t nc = (uint32_t)(lists.size() - at);
+                if (!nc) continue;
+                uint64_t rows = 0;
+                lists.push_back(0);
+                for (uint32_t i = 0; i < nc; i++) {
+                    rows += (desc[lists[at + i]].n_sub + BLISSGPU_LOUDNESS_SEGMENT - 1) / BLISSGPU_LOUDNESS_SEGMENT;
+                    lists.push_back((uint32_t)rows);
+                }
+                if (rows >= 0xFFFFFFFFull) return fail(BLISSGPU_ERR_INVALID, who, "a group of songs has 2^32 segments or more");
+                classes[n_classes] = LoudClass{fmt, ch, nc, (uint32_t)rows, nullptr, nullptr};
+                list_at[n_classes++] = at;
+            }
+        const uint64_t gz = zoff[g1] - zoff[g0];
+        const uint32_t n_tiles = tile_pfx[ng];
+        const size_t o_pcm = 0, o_z = o_pcm + fp_align(off + 256), o_desc = o_z + fp_align(gz * sizeof(double)),
+                     o_lists = o_desc + fp_align(ng * sizeof(LoudSong)), o_tile = o_lists + fp_align(lists.size() * sizeof(uint32_t)),
+                     o_part = o_tile + fp_align((ng + 1) * sizeof(uint32_t)), o_peaks = o_part + fp_align(2 * (size_t)n_tiles * sizeof(double)),
+                     o_htab = o_peaks + fp_align(2 * (size_t)ng * sizeof(double)), total = o_htab + fp_align(htab.size() * sizeof(double));
+        if ((rc = c->ld_ws.ensure(total))) return rc;
+        uint8_t* base = c->ld_ws.p;
+        uint32_t* d_lists = reinterpret_cast<uint32_t*>(base + o_lists);
+        for (int k = 0; k < n_classes; k++) {
+            classes[k].d_song_of = d_lists + list_at[k];
+            classes[k].d_row_pfx = d_lists + list_at[k] + classes[k].n_class;
+        }
+        HostStage s{c, "loudness"};
+        for (uint32_t k = 0; k < ng; k++) {
+            const blissgpu_decoded_song& d = songs[ok[k]];
+            s.up(base + o_pcm + desc[k].pcm_off, d.pcm, d.frames * d.channels * (d.sample_format == BLISSGPU_SAMPLE_S16 ? 2 : 4));
+        }
+        s.up(base + o_desc, desc.data(), ng * sizeof(LoudSong));
+        s.up(d_lists, lists.data(), lists.size() * sizeof(uint32_t));
+        s.up(base + o_tile, tile_pfx.data(), (ng + 1) * sizeof(uint32_t));
+        s.up(base + o_htab, htab.data(), htab.size() * sizeof(double));
+        rc = s.uploaded();
+        if (!rc)
+            rc = loud_group_device(c, who, base + o_pcm, reinterpret_cast<const LoudSong*>(base + o_desc), ng, classes, n_classes,
+                                   reinterpret_cast<const uint32_t*>(base + o_tile), n_tiles, reinterpret_cast<const double*>(base + o_htab),
+                                   reinterpret_cast<double*>(base + o_part), reinterpret_cast<double*>(base + o_z),
+                                   reinterpret_cast<double*>(base + o_peaks));
+        peaks.assign(2 * (size_t)ng, 0.0);
+        if (!rc) {
+            s.down(z + zoff[g0], base + o_z, gz * sizeof(double));
+            s.down(peaks.data(), base + o_peaks, peaks.size() * sizeof(double));
+        }
+        if ((rc = s.finish(rc))) return rc;
+        for (uint32_t k = 0; k < ng; k++) {
+            sample_peak[ok[k]] = peaks[2 * (size_t)k];
+            true_peak[ok[k]] = peaks[2 * (size_t)k + 1];
+        }
+        zero_short(g0, g1);  // (the device wrote nothing there)
+        g0 = g1;
+    }
+    return BLISSGPU_OK;
+}
+
+int blissgpu_loudness_energies(const blissgpu_decoded_song* songs, uint32_t n_songs, double* z, double* sample_peak, double* true_peak,
+                               int32_t* status) {
+    const char* who = "blissgpu_loudness_energies";
+    if (n_songs == 0) return BLISSGPU_OK;
+    std::vector<uint64_t> zoff;
+    const int rc = loud_songs_ok(who, songs, n_songs, status, zoff);
+    if (rc) return rc;
+    return loud_energies_host(who, songs, n_songs, zoff, z, sample_peak, true_peak, status);
+}
+
+int blissgpu_loudness_batch(const blissgpu_decoded_song* songs, uint32_t n_songs, const uint32_t* album, uint32_t n_albums,
+                            double* song_out, double* album_out, int32_t* status) {
+    const char* who = "blissgpu_loudness_batch";
+    if (album) {
+        if (!album_out) return fail(BLISSGPU_ERR_INVALID, who, "album labels without album_out");
+        for (uint32_t s = 0; s < n_songs; s++)
+            if (album[s] >= n_albums) return fail(BLISSGPU_ERR_INVALID, who, "an album label is >= n_albums");
+    }
+    std::vector<uint64_t> zoff(1, 0);
+    std::vector<double> z, sp(n_songs), tp(n_songs);
+    if (n_songs) {
+        if (!song_out) return fail(BLISSGPU_ERR_INVALID, who, "song_out is NULL");
+        int rc = loud_songs_ok(who, songs, n_songs, status, zoff);
+        if (rc) return rc;
+        z.resize(std::max<uint64_t>(1, zoff[n_songs]));
+        if ((rc = loud_energies_host(who, songs, n_songs, zoff, z.data(), sp.data(), tp.data(), status))) return rc;
+    }
+    // the gates: per song over its own blocks, per album over the concatenation of its OK songs' blocks in song order
+    std::vector<std::vector<double>> aP(album ? n_albums : 0), aST(album ? n_albums : 0);
+    std::vector<double> P, ST, apk(album ? 2 * (size_t)n_albums : 0, 0.0);
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (uint32_t s = 0; s < n_songs; s++) {
+        double* row = song_out + 5 * (size_t)s;
+        if (status[s] != BLISSGPU_SONG_OK) {
+            for (int k = 0; k < 5; k++) row[k] = nan;
+            continue;
+        }
+        const uint64_t n_sub = (zoff[s + 1] - zoff[s]) / songs[s].channels;
+        P.assign(n_sub - (LOUD_BLOCK_SUBS - 1), 0.0);
+        ST.assign(n_sub >= LOUD_SHORT_SUBS ? n_sub - (LOUD_SHORT_SUBS - 1) : 0, 0.0);
+        loud_blocks(z.data() + zoff[s], songs[s].channels, n_sub, loud_hop(songs[s].sample_rate), P.data(), ST.data());
+        double lo, hi;
+        row[0] = loud_gate(P.data(), P.size());
+        row[1] = loud_lufs(row[0]);
+        row[2] = loud_range(ST.data(), ST.size(), &lo, &hi);
+        row[3] = sp[s];
+        row[4] = tp[s];
+        if (album) {
+            const uint32_t a = album[s];
+            aP[a].insert(aP[a].end(), P.begin(), P.end());
+            aST[a].insert(aST[a].end(), ST.begin(), ST.end());
+            apk[2 * (size_t)a] = std::max(apk[2 * (size_t)a], sp[s]);
+            apk[2 * (size_t)a + 1] = std::max(apk[2 * (size_t)a + 1], tp[s]);
+        }
+    }
+    if (album)
+        for (uint32_t a = 0; a < n_albums; a++) {
+            double* row = album_out + 5 * (size_t)a;
+            double lo, hi;
+            row[0] = loud_gate(aP[a].data(), aP[a].size());
+            row[1] = loud_lufs(row[0]);
+            row[2] = loud_range(aST[a].data(), aST[a].size(), &lo, &hi);
+            row[3] = apk[2 * (size_t)a];
+            row[4] = apk[2 * (size_t)a + 1];
+        }
+    return BLISSGPU_OK;
 }
 
 // ---- the moments of a library: counts, means, squared deviations and extrema per group of a labelling, and the pooled scatter

@@ -282,6 +282,7 @@ struct blissgpu_ctx {
     bg::PinnedBuf<uint64_t> wd_host;               // Ward clustering: the flags and best keys of a round, page-locked
     bg::DevBuf<uint8_t> pam_ws;                    // k-medoids: the record | the label sort | near, d1, d2 | medoids and their rows | the state's search | A and B of a slab
     bg::DevBuf<uint8_t> fp_ws;                     // fingerprints: a group's PCM | E | words | descriptors; the match: words | offsets | pairs | candidates | results
+    bg::DevBuf<uint8_t> ld_ws;                     // loudness: a group's PCM | z | descriptors | class lists | tile prefix | partial peaks | peaks | taps
     bg::DevBuf<uint8_t> map_ws;                    // the 2-D map's scratch: the rows' sums | the chunks' partials | the block sums of z | attraction | U | gain
     bg::DevBuf<uint8_t> mt_ws;                     // metric learning: the wavefronts' partials | their counts | the result block | M
     uint64_t mt_uploads = 0, mt_downloads = 0, mt_bytes = 0;  // the last learn_metric call: copies inside its loop, bytes downloaded

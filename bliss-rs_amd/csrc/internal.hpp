@@ -196,6 +196,10 @@ struct DeviceTables {   // constant tables, built once per context
     X(KX_FP_BITS, "fp_bits_kernel")                                                                                               \
     X(KX_FP_MATCH, "fp_match_kernel")                                                                                             \
     X(KX_FP_PICK, "fp_pick_kernel")                                                                                               \
+    /* loudness (kernels_loudness.hip): the K-weighted sub-block energies, the peaks per tile, their fold per song */              \
+    X(KX_LOUD_ENERGY, "loud_energy_kernel")                                                                                       \
+    X(KX_LOUD_PEAK, "loud_peak_kernel")                                                                                           \
+    X(KX_LOUD_FOLD, "loud_fold_kernel")                                                                                           \
     /* the k lowest forest scores per seed group (kernels_forest.hip; merged by group_knn_merge_kernel) */                        \
     X(KX_GROUP_FOREST_SCAN, "group_forest_scan_kernel")                                                                           \
     /* a journey's step (kernels_chains.hip: the chains' scan with a waypoint query or a gate) */                                 \
@@ -643,6 +647,28 @@ void launch_fp_match(const uint32_t* words, const uint64_t* word_offsets, uint32
                      uint32_t n_blocks, int max_offset, uint32_t min_overlap, FpCand* cand, hipStream_t st);
 void launch_fp_pick(const FpCand* cand, uint32_t n_pairs, uint32_t n_blocks, int32_t* offset, uint32_t* errors, uint32_t* bits,
                     hipStream_t st);
+// loudness (kernels_loudness.hip).  A group of songs is described by LoudSong [n_songs]; the energy kernel is launched once per
+// (sample format, channel count) present in the group, over the songs of that class: song_of [n_class] names them, row_pfx
+// [n_class + 1] counts the rows (segments of BLISSGPU_LOUDNESS_SEGMENT sub-blocks) in front of each.  z is the group's energies,
+// song s channel c sub-block u at z_off + c n_sub + u.  Every song's PCM starts on a multiple of 256 bytes and is padded to one.
+struct LoudSong {
+    uint64_t pcm_off;   // bytes into the group's PCM
+    uint64_t frames;
+    uint64_t z_off;     // doubles into the group's z
+    uint32_t hop;       // samples per sub-block
+    uint32_t n_sub;     // >= 4
+    uint16_t channels, format;
+    uint32_t factor;    // the true peak's oversampling: 4, 2 or 1
+    double coef[10];    // the K-weighting table (blissgpu_loudness_kweighting)
+};
+void launch_loud_energy(const uint8_t* pcm, const LoudSong* songs, int format, int channels, const uint32_t* song_of,
+                        const uint32_t* row_pfx, uint32_t n_class, uint32_t n_rows, double* z, hipStream_t st);
+// tile_pfx [n_songs + 1]: loud_peak_tiles() of every song; htab [3][49]: the interpolators of factor 4, 2, 1; part [n_tiles][2];
+// peaks [n_songs][2] = sample peak, true peak
+uint32_t loud_peak_tiles(uint64_t frames, uint32_t channels);
+void launch_loud_peak(const uint8_t* pcm, const LoudSong* songs, uint32_t n_songs, const uint32_t* tile_pfx, uint32_t n_tiles,
+                      const double* htab, double* part, hipStream_t st);
+void launch_loud_fold(const double* part, const uint32_t* tile_pfx, uint32_t n_songs, double* peaks, hipStream_t st);
 // triplet metric learning, one gradient evaluation (kernels_metric.hip).  The triplets are dealt out in W contiguous chunks, a
 // function of T alone; part [W][pairs + 1] f64 and cnt [W][2] u64 are the wavefronts' partials, out = G f64 [d][d] | loss f64 |
 // n_active u64 | error bits u64 (TRIPLET_ERR_*).  mode says how M is read; flags (u8 [T]) may be NULL

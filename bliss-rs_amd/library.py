@@ -48,6 +48,9 @@ database:
     fingerprint_duplicates                ignores, and the groups of songs that are the same RECORDING by them: candidates from
                                           the k nearest songs by features and equal title and artist, one match call on the
                                           device (playlist.fingerprint_duplicates); duplicate_songs is unchanged
+    store_loudness, load_loudness,        EBU R 128 loudness (bliss_rs_amd.loudness_batch) in a sidecar table the crate ignores:
+    loudness_statistics                   track and album loudness and peaks for ReplayGain, the loudness range, and the
+                                          library's count, mean and extrema of both (host arithmetic over the table)
 
 SQLite stores `real` as f64; an f32 feature widens exactly on the way in and narrows exactly on the way out, so a
 round trip is bit-exact.  The schema, load and store helpers are host code; the playlists run their distances on the
@@ -695,6 +698,69 @@ def load_fingerprints(db: Conn) -> dict:
         if own:
             conn.close()
     return {p: np.frombuffer(bytes(b), dtype="<u4").astype(np.uint32) for p, b in rows}
+
+
+# ---- loudness: a second sidecar table (bliss_rs_amd.loudness_batch measures, this keeps) ----
+def store_loudness(db: Conn, loudness, albums=None) -> None:
+    """Keep the loudness of songs of the library: {path: Loudness} into the sidecar table gpu_loudness(song_id, version, lufs,
+    range_lu, sample_peak, true_peak, album_lufs, album_peak), created on demand, with song.LOUDNESS_VERSION beside the
+    figures.  albums: {path: Loudness}, the figures of the ALBUM each song belongs to (loudness_batch(albums=)'s second
+    result, looked up per song); a song without an entry keeps NULL there.  A path that is not in the library is a
+    ProviderError; a song's earlier row is replaced.  (SQLite stores -inf, the loudness of digital silence, as it is.)"""
+    from .song import LOUDNESS_VERSION
+
+    albums = dict(albums or {})
+    conn, own = _connect(db)
+    try:
+        conn.execute("create table if not exists gpu_loudness (song_id integer primary key, version integer, lufs real, range_lu real, "
+                     "sample_peak real, true_peak real, album_lufs real, album_peak real)")
+        for path, ld in dict(loudness).items():
+            row = conn.execute("select id from song where path = ?", (path,)).fetchone()
+            if row is None:
+                raise ProviderError(f"song '{path}' is not in the library")
+            al = albums.get(path)
+            conn.execute("insert or replace into gpu_loudness (song_id, version, lufs, range_lu, sample_peak, true_peak, album_lufs, "
+                         "album_peak) values (?, ?, ?, ?, ?, ?, ?, ?)",
+                         (int(row[0]), LOUDNESS_VERSION, float(ld.lufs), float(ld.range_lu), float(ld.sample_peak), float(ld.true_peak),
+                          None if al is None else float(al.lufs), None if al is None else float(al.true_peak)))
+        conn.commit()
+    finally:
+        if own:
+            conn.close()
+
+
+def load_loudness(db: Conn) -> dict:
+    """{path: (Loudness, album_lufs, album_peak)} of every song with a stored row of song.LOUDNESS_VERSION, in id order
+    (album_lufs and album_peak are None where none was stored); a library without the sidecar table has none.  The table
+    keeps lufs, not the gated power: Loudness.power is 10 ** ((lufs + 0.691) / 10) here, not the measured bits."""
+    from .song import LOUDNESS_VERSION, Loudness
+
+    conn, own = _connect(db)
+    try:
+        if conn.execute("select count(*) from sqlite_master where type = 'table' and name = 'gpu_loudness'").fetchone()[0] == 0:
+            return {}
+        rows = conn.execute("select song.path, g.lufs, g.range_lu, g.sample_peak, g.true_peak, g.album_lufs, g.album_peak from gpu_loudness g "
+                            "join song on song.id = g.song_id where g.version = ? order by song.id", (LOUDNESS_VERSION,)).fetchall()
+    finally:
+        if own:
+            conn.close()
+    return {p: (Loudness(lufs=lufs, range_lu=lra, sample_peak=sp, true_peak=tp, power=10.0 ** ((lufs + 0.691) / 10.0)), al, ap)
+            for p, lufs, lra, sp, tp, al, ap in rows}
+
+
+def loudness_statistics(db: Conn) -> dict:
+    """How loud the library is, from the stored rows (host arithmetic): {"count", "silent", "lufs": {"mean", "min", "max"},
+    "range_lu": {"mean", "min", "max"}}.  Songs of digital silence (lufs -inf) are counted in "silent" and left out of the
+    means and extrema; a library without rows has count 0 and None figures.  The loudness range is the number that tells a
+    compressed modern master (a few LU) from an orchestral recording (15 LU and more)."""
+    stored = load_loudness(db)
+    rows = [ld for ld, _, _ in stored.values() if ld.lufs != float("-inf")]
+
+    def summary(values):
+        return {"mean": sum(values) / len(values), "min": min(values), "max": max(values)} if values else {"mean": None, "min": None, "max": None}
+
+    return {"count": len(stored), "silent": len(stored) - len(rows), "lufs": summary([ld.lufs for ld in rows]),
+            "range_lu": summary([ld.range_lu for ld in rows])}
 
 
 def fingerprint_candidate_pairs(songs, X, has_fp, k: int, metric_builder=playlist.euclidean_distance) -> np.ndarray:

@@ -500,6 +500,150 @@ def fingerprint_decoded_batch(sample_arrays: Sequence[np.ndarray], sample_rates)
     return fingerprint_batch(mono)
 
 
+# ---- loudness (blissgpu_loudness_batch): EBU R 128 / ReplayGain 2.0, opt-in, never part of analyze_* ----
+LOUDNESS_VERSION = 1  # stored beside the figures (library.store_loudness): another contract, another number
+
+
+@dataclass
+class Loudness:
+    """The loudness of one song or one album: integrated loudness (LUFS, BS.1770-4 with both gates), loudness range (LU, EBU
+    Tech 3342), sample peak and 4x-oversampled true peak (linear, 1.0 = full scale), and `power`, the gated mean square the
+    LUFS figure is the logarithm of (the quantity that is defined to the bit)."""
+    lufs: float
+    range_lu: float
+    sample_peak: float
+    true_peak: float
+    power: float
+
+    def replaygain(self, reference: float = -18.0):
+        """(gain_db, peak) of ReplayGain 2.0: the gain that brings the song to `reference` LUFS, and its true peak"""
+        return reference - self.lufs, self.true_peak
+
+
+def _loudness_songs(sample_arrays, sample_rates):
+    arrays = [_as_pcm(a) for a in sample_arrays]
+    n = len(arrays)
+    rates = [int(sample_rates)] * n if np.isscalar(sample_rates) else [int(r) for r in sample_rates]
+    if len(rates) != n:
+        raise ProviderError("one sample rate per song")
+    keep = [a if a.size else np.zeros(1, a.dtype) for a in arrays]
+    songs = (_ffi.DecodedSong * max(n, 1))()
+    for i, a in enumerate(arrays):
+        songs[i] = _ffi.DecodedSong(_ffi.address(keep[i]), a.shape[0], rates[i], 1 if a.ndim == 1 else a.shape[1], _fmt_of(a))
+    return arrays, rates, keep, songs
+
+
+def _album_indices(albums, n):
+    """labels of any hashable kind -> (uint32 indices in order of first appearance, the labels in that order)"""
+    albums = list(albums)
+    if len(albums) != n:
+        raise ProviderError("one album label per song")
+    order = {}
+    idx = np.array([order.setdefault(a, len(order)) for a in albums], np.uint32)
+    return idx, list(order)
+
+
+def loudness_gate(block_powers) -> tuple:
+    """(power, lufs) of BS.1770-4's two gates over 400 ms block powers (blissgpu_loudness_gate; device-free)"""
+    P = np.ascontiguousarray(block_powers, dtype=np.float64).reshape(-1)
+    power, lufs = C.c_double(0.0), C.c_double(0.0)
+    _ffi.call("blissgpu_loudness_gate", P if P.size else None, P.size, C.byref(power), C.byref(lufs))
+    return power.value, lufs.value
+
+
+def loudness_range(short_term_powers) -> tuple:
+    """(range_lu, lo, hi) of EBU Tech 3342 over 3 s short-term powers (blissgpu_loudness_range; device-free)"""
+    ST = np.ascontiguousarray(short_term_powers, dtype=np.float64).reshape(-1)
+    r, lo, hi = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+    _ffi.call("blissgpu_loudness_range", ST if ST.size else None, ST.size, C.byref(r), C.byref(lo), C.byref(hi))
+    return r.value, lo.value, hi.value
+
+
+def loudness_blocks(z, sample_rate: int) -> tuple:
+    """Sub-block energies z [channels, n_sub] -> (P, ST): the 400 ms block powers and the 3 s short-term powers, hop 100 ms
+    (blissgpu_loudness_blocks; device-free)"""
+    z = np.ascontiguousarray(np.atleast_2d(z), dtype=np.float64)
+    channels, n_sub = z.shape
+    P = np.zeros(max(n_sub - 3, 0), np.float64)
+    ST = np.zeros(max(n_sub - 29, 0), np.float64)
+    _ffi.call("blissgpu_loudness_blocks", z if z.size else None, channels, n_sub, int(sample_rate), P if P.size else None,
+              ST if ST.size else None)
+    return P, ST
+
+
+def loudness_batch(sample_arrays: Sequence[np.ndarray], sample_rates, albums=None, return_energies: bool = False):
+    """EBU R 128 loudness of every song, in one call, at the songs' NATIVE rates: sample_arrays are decoder output (1-D mono or
+    [frames, 2]; float32 / int16 / int32), sample_rates one rate or one per song (8 000 .. 768 000 Hz).  -> a list with a
+    `Loudness` per song, or AnalysisError for a song of fewer than four 100 ms sub-blocks.  albums: one hashable label per song
+    -> (songs, {label: Loudness}), the album figures gated over all blocks of the album's songs (ReplayGain's album gain).
+    The K-weighting filter, the energies and both peaks run on the device (blissgpu_loudness_batch); the contract is in
+    include/blissgpu.h.  return_energies (the tests' tap): the result is followed by a list of (z [channels, n_sub],
+    sample_peak, true_peak) per song, and the gates run through the device-free entry points on those energies -- the same
+    arithmetic, the same figures."""
+    arrays, rates, keep, songs = _loudness_songs(sample_arrays, sample_rates)
+    n = len(arrays)
+    labels, names = _album_indices(albums, n) if albums is not None else (None, [])
+    status = np.zeros(max(n, 1), np.int32)
+    channels = [1 if a.ndim == 1 else a.shape[1] for a in arrays]
+    if not return_energies:
+        rows = np.zeros((max(n, 1), 5), np.float64)
+        album_rows = np.zeros((max(len(names), 1), 5), np.float64)
+        _ffi.call("blissgpu_loudness_batch", songs, n, labels, len(names), rows, album_rows if labels is not None else None, status)
+        taps = None
+    else:
+        n_sub = [int(_ffi.call("blissgpu_loudness_subblocks", a.shape[0], r)) for a, r in zip(arrays, rates)]
+        zoff = np.zeros(n + 1, np.int64)
+        zoff[1:] = np.cumsum([c * u for c, u in zip(channels, n_sub)])
+        z = np.zeros(max(int(zoff[n]), 1), np.float64)
+        sp, tp = np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.float64)
+        _ffi.call("blissgpu_loudness_energies", songs, n, z, sp, tp, status)
+        taps = [(z[zoff[i]:zoff[i + 1]].reshape(channels[i], n_sub[i]).copy(), float(sp[i]), float(tp[i])) for i in range(n)]
+        rows = np.full((max(n, 1), 5), np.nan)
+        blocks = {}
+        for i in range(n):
+            if status[i] == _ffi.SONG_OK:
+                blocks[i] = loudness_blocks(taps[i][0], rates[i])
+                rows[i, :2] = loudness_gate(blocks[i][0])
+                rows[i, 2] = loudness_range(blocks[i][1])[0]
+                rows[i, 3:] = sp[i], tp[i]
+        album_rows = np.zeros((max(len(names), 1), 5), np.float64)
+        for a in range(len(names)):
+            members = [i for i in blocks if labels[i] == a]
+            album_rows[a, :2] = loudness_gate(np.concatenate([blocks[i][0] for i in members]) if members else [])
+            album_rows[a, 2] = loudness_range(np.concatenate([blocks[i][1] for i in members]) if members else [])[0]
+            album_rows[a, 3] = max([sp[i] for i in members], default=0.0)
+            album_rows[a, 4] = max([tp[i] for i in members], default=0.0)
+
+    def of(row):
+        return Loudness(lufs=float(row[1]), range_lu=float(row[2]), sample_peak=float(row[3]), true_peak=float(row[4]), power=float(row[0]))
+
+    out = [of(rows[i]) if status[i] == _ffi.SONG_OK else AnalysisError("empty or too short song.") for i in range(n)]
+    result = (out,) if albums is None else (out, {name: of(album_rows[a]) for a, name in enumerate(names)})
+    if return_energies:
+        result += (taps,)
+    return result[0] if len(result) == 1 else result
+
+
+def loudness_flac_batch(files, albums=None):
+    """loudness_batch for compressed .flac files (bytes, uint8 arrays or paths): flac_decode_batch (decoded on the device, the
+    PCM copied back) followed by loudness_batch on that PCM at the files' own rates -- a host round trip of the PCM between the
+    two device calls, not a fused path.  A file that cannot be decoded yields its DecodingError and takes no part in its
+    album."""
+    decoded = flac_decode_batch(files)
+    good = [i for i, d in enumerate(decoded) if not isinstance(d, BlissError)]
+    if albums is not None:
+        albums = list(albums)
+        if len(albums) != len(decoded):
+            raise ProviderError("one album label per song")
+    out = list(decoded)
+    res = loudness_batch([decoded[i][0] for i in good], [decoded[i][1] for i in good],
+                         albums=None if albums is None else [albums[i] for i in good])
+    songs = res if albums is None else res[0]
+    for i, r in zip(good, songs):
+        out[i] = r
+    return out if albums is None else (out, res[1])
+
+
 @dataclass
 class Song:
     """src/song/mod.rs:45-76 (metadata fields kept, filled by decoders)."""

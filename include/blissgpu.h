@@ -1218,6 +1218,75 @@ int blissgpu_fingerprint_match(const uint32_t *words, const uint64_t *word_offse
                                uint64_t n_pairs, uint32_t max_offset, uint32_t min_overlap, int32_t *offset, uint32_t *errors,
                                uint32_t *bits);
 
+/* ---- loudness: EBU R 128 / ReplayGain 2.0 track and album loudness, loudness range, sample and true peak ----
+ * What every program around a music library computes per file, measured on the device at the file's NATIVE rate and channel
+ * count (ITU-R BS.1770-4, EBU Tech 3341 / 3342).  Opt-in: no analyze_* entry point computes it, no feature row holds it.
+ *
+ * Input.  blissgpu_decoded_song rows: F32, S16 or S32 interleaved, 8 000 .. 768 000 Hz, 1 or 2 channels, each of weight 1.0
+ * (mono is ONE channel, the libebur128 / FFmpeg convention).  More than 2 channels, a rate outside the range or an unknown
+ * format is BLISSGPU_ERR_INVALID, checked before the device is touched.  Samples widen to f64 exactly: S16 v / 32768.0, S32
+ * (double)v / 2147483648.0 (not the f32 rounding of the analysis path), F32 as it is.  F32 samples must be finite: the results of a
+ * song that holds a NaN or an infinity are undefined (no other song of the call is affected).
+ *
+ * K-weighting.  Two biquads whose coefficients are computed on the host in f64 by the bilinear form.  Stage 1: f0 =
+ * 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196, K = tan(pi f0 / fs), Vh = 10^(G/20), Vb =
+ * Vh^0.4996667741545416, a0 = 1 + K/Q + K^2, b = [(Vh + Vb K/Q + K^2)/a0, 2 (K^2 - Vh)/a0, (Vh - Vb K/Q + K^2)/a0], a1 =
+ * 2 (K^2 - 1)/a0, a2 = (1 - K/Q + K^2)/a0.  Stage 2: f0 = 38.13547087602444, Q = 0.5003270373238773, b = [1, -2, 1], the same
+ * a1 and a2.  blissgpu_loudness_kweighting returns coef [10] = b0 b1 b2 a1 a2 of stage 1, then of stage 2 (device-free); the
+ * TABLE is the contract, a libm may differ from another in the last bit.  At 48 000 Hz it is BS.1770-4's.
+ * Per sample and stage, in f64, every operation rounded on its own, in exactly this association:
+ *   y = b0 x + s1;   s1 = (b1 x - a1 y) + s2;   s2 = b2 x - a2 y;      stage 2 takes stage 1's y.
+ *
+ * Sub-blocks.  H = (rate + 5) / 10 samples (integer division: 100 ms), n_sub = frames / H (blissgpu_loudness_subblocks; 0 for a
+ * rate out of range).  z[c][u] = the sum of y2^2 over the samples of sub-block u of channel c, sequential in sample order.  The
+ * tail beyond n_sub H enters the peaks and no energy.  n_sub < 4: BLISSGPU_SONG_TOO_SHORT.
+ *
+ * Segments.  Segment g covers sub-blocks [g S, min((g + 1) S, n_sub)); its filter starts from ZERO state at sample
+ * max(0, g S - W) H and runs sequentially to the segment's end; outputs before sample g S H are discarded.  The segments that
+ * start at sample 0 are the sequential filter; for the others the high-pass poles (radius 0.995 at 48 kHz) have decayed by
+ * e^-96 over W = 4 sub-blocks.  S and W are the constants below, the same for every input; because the segmentation is part of
+ * the contract, the device's energies are defined to the bit. */
+#define BLISSGPU_LOUDNESS_SEGMENT 8
+#define BLISSGPU_LOUDNESS_WARMUP 4
+/* Peaks.  The sample peak is max |x| over all samples and channels.  The true peak oversamples by F = 4 below 96 000 Hz, 2 below
+ * 192 000 Hz, 1 from there on, with the 49-tap Hann-windowed sinc h[i] = sinc((i - 24) / F) 0.5 (1 - cos(2 pi i / 48)), i = 0 ..
+ * 48 (blissgpu_true_peak_filter returns F and h, device-free; the table is the contract):
+ *   u[k] = sum over i of h[i] xz[k - i + 24], over the taps of that phase (those whose xz is a sample) in ascending i, from 0.0,
+ * products and sums in f64; xz is the zero-stuffed channel (xz[F n] = x[n]), zero outside the song.  True peak = max |u[k]| over
+ * k < F frames and the channels.
+ *
+ * Blocks and gates (device-free).  H and the sums in f64:
+ *   P[j]  = (sum over c ascending of (((z[c][j] + z[c][j+1]) + z[c][j+2]) + z[c][j+3])) / (double)(4 H),   j = 0 .. n_sub - 4
+ *   ST[j] = (sum over c, then u = j .. j + 29, of z[c][u], one sequential sum) / (double)(30 H),           j = 0 .. n_sub - 30
+ * (blissgpu_loudness_blocks: z is [channels][n_sub]; P has n_sub - 3 entries, ST n_sub - 29 or none; either may be NULL).
+ * Integrated loudness (blissgpu_loudness_gate): of the blocks with P > ABS = 1.1724653045822981e-07 (-70 LUFS; the literal is the
+ * contract) Gamma = (sequential sum / count) 0.1; power = sequential sum / count of the blocks with P > ABS and P > Gamma, in
+ * ascending order; lufs = -0.691 + 10 log10(power).  No block above ABS: power = 0, lufs = -inf.
+ * Loudness range (blissgpu_loudness_range): of the ST > ABS the gate is (sequential sum / count) 0.01; the ST above both, sorted
+ * ascending, n of them: lo = sorted[(uint64)((n - 1) 0.10 + 0.5)], hi = sorted[(uint64)((n - 1) 0.95 + 0.5)], range_lu =
+ * 10 log10(hi / lo); n = 0: range_lu = lo = hi = 0.
+ * An album: the same gates over the concatenation of its OK songs' P (and ST) in song order -- blocks never span songs --, the
+ * peaks are the maxima; an album without an OK song has power 0, lufs -inf, range and peaks 0.
+ * power, lo, hi, the energies and the peaks are defined to the bit; lufs and range_lu pass through the host's log10.
+ *
+ * blissgpu_loudness_energies (host pointers, the default context; the device half and the tests' tap): z receives the energies
+ * song after song, song s at zoff[s] = sum over the songs before it of channels n_sub, channel-major: z[zoff[s] + c n_sub + u];
+ * sample_peak, true_peak and status are [n_songs].  A too-short song never reaches the device: its energies and peaks are 0.
+ * blissgpu_loudness_batch: album is NULL or [n_songs] labels < n_albums; song_out is f64 [n_songs][5] = power, lufs, range_lu,
+ * sample_peak, true_peak (NaN for a song that is too short); album_out f64 [n_albums][5] (NULL without labels).
+ * The PCM is uploaded in its native format; a call whose PCM exceeds half the context's workspace limit (or 8 GiB) runs in
+ * groups of consecutive songs, with the same results.  n_songs == 0 is BLISSGPU_OK. */
+uint64_t blissgpu_loudness_subblocks(uint64_t frames, uint32_t sample_rate);
+int blissgpu_loudness_kweighting(uint32_t sample_rate, double *coef); /* coef [10] */
+int blissgpu_true_peak_filter(uint32_t sample_rate, uint32_t *factor, double *h); /* h [49] */
+int blissgpu_loudness_blocks(const double *z, uint32_t channels, uint64_t n_sub, uint32_t sample_rate, double *P, double *ST);
+int blissgpu_loudness_gate(const double *P, uint64_t n, double *power, double *lufs);
+int blissgpu_loudness_range(const double *ST, uint64_t n, double *range_lu, double *lo, double *hi);
+int blissgpu_loudness_energies(const blissgpu_decoded_song *songs, uint32_t n_songs, double *z, double *sample_peak,
+                               double *true_peak, int32_t *status);
+int blissgpu_loudness_batch(const blissgpu_decoded_song *songs, uint32_t n_songs, const uint32_t *album, uint32_t n_albums,
+                            double *song_out, double *album_out, int32_t *status);
+
 /* ---- extended isolation forest: the ForestOptions metric of src/playlist.rs:230-251 ----
  * The reference builds extended_isolation_forest::Forest<f32, 23> from the seed songs with the thread RNG and uses its score
  * as the "distance" of closest_to_songs (:247-250): seeds-like songs score low, outliers high.  Here the forest is a pure
